@@ -23,12 +23,18 @@ The job is FIXED, like the reference's `-channels 512` (controller.go:3262-3269,
     (64 / 128 / 256 channels on the one GPU: `strong_split_legs`).
   * --weak ("scaling": "weak"): 512 channels on EVERY GPU as the headline, the strong split as the extra leg `strong_split`.
   * --total-channels T: another fixed job, headline only.
-When --steps / --warmup are shorter than the settled default (40 after 25), `settled` carries the same context's rate after 25 more
-warm-up steps over 40 steps, so one line holds the caller's figure and the settled one.
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line (rank 0) with the headline: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step, max over ranks) and the job's `config`.
 
-Prints ONE JSON line (rank 0) with the metric, the roofline of the dominant kernel measured with
-HIP events over the timed region, the PCIe-inclusive host-buffer rates ("end_to_end"), the other
-BASELINE configs' rates ("configs") and a CPU baseline (the oracle "port") timed on the host cores.
+--full adds everything else to the same line: the repeats of the timed region, the roofline of the dominant kernel (HIP events over
+the timed region and passes of their own), the in-run parity gate against the oracle, the PCIe-inclusive host-buffer rates
+("end_to_end"), the other BASELINE configs' rates ("configs"), the split / weak legs and a CPU baseline (the oracle "port") timed on
+the host cores.  When --steps / --warmup are shorter than the settled default (40 after 25), `settled` carries the same context's
+rate after 25 more warm-up steps over 40 steps, so one line holds the caller's figure and the settled one.
+
+--dump-outputs DIR writes what the last timed step computed -- the output block a caller of the timed path receives, every channel
+of the job in global channel order -- as DIR/output.npy (float64 [channels, frames]; above 64 MB a fixed, seeded sample of the
+channels, listed in the line).  Inputs and IRs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import datetime
@@ -667,6 +673,42 @@ def parity_gate(ctx_step, read_output, x_blocks, n_calls, nch, channel0, frames,
             "what": "oracle (C restatement of the Go reference) vs the device output of the timed context, per-channel RMS over the compared blocks"}
 
 
+# ---- --dump-outputs: what the timed path computed ------------------------------------------------------------------------------
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 2024
+
+
+def dump_channels(total_channels, frames, limit=DUMP_LIMIT_BYTES):
+    """The global channels --dump-outputs writes: all of them when [total_channels, frames] float64 fits in `limit`, else a fixed, seeded
+    sample of as many as fit (ascending)."""
+    fit = max(1, limit // (8 * frames))
+    if total_channels <= fit:
+        return np.arange(total_channels)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(total_channels, size=fit, replace=False))
+
+
+def dump_outputs(out_dir, y_local, channel0, total_channels, rank, dist=None):
+    """Rank 0 writes the job's output block to out_dir/output.npy (float64 [channels, frames], global channel order); every rank sends
+    the rows of its own channels (a collective when `dist` is given).  Returns, on rank 0, what the result line says about the file."""
+    nch, frames = y_local.shape
+    chans = dump_channels(total_channels, frames)
+    mine = chans[(chans >= channel0) & (chans < channel0 + nch)]
+    part = (int(channel0), np.ascontiguousarray(y_local[mine - channel0], dtype=np.float64))
+    parts = [part]
+    if dist is not None:
+        parts = [None] * dist.get_world_size() if rank == 0 else None
+        dist.gather_object(part, parts, dst=0)
+    if rank != 0:
+        return None
+    out = np.concatenate([rows for _, rows in sorted(parts, key=lambda p: p[0])])
+    assert out.shape == (len(chans), frames)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "output.npy"), out)
+    return {"dir": out_dir, "files": {"output.npy": list(out.shape)}, "dtype": "float64",
+            "channels": "all" if len(chans) == total_channels else [int(c) for c in chans]}
+
+
 # ---- main ----------------------------------------------------------------------------------------------------------------------
 
 def main():
@@ -686,11 +728,16 @@ def main():
     ap.add_argument("--taps", type=int, default=65536)
     ap.add_argument("--channel-groups", type=int, default=0,
                     help="free-running channel groups on the GPU (gdg_ctx_set_overlap); 0 = 2 from 384 channels on, else 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity gate (oracle follows 3 channels of the timed context)")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement (no end_to_end / configs / split legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the in-run parity gate (oracle follows 3 channels of the timed context)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra legs (end_to_end / configs / split legs)")
     ap.add_argument("--distinct-irs", type=int, default=0,
                     help="number of distinct IR tap sets (0 = one per channel = the metric's d = 1; fewer lets power amps share spectra)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: repeats, settled rate, roofline passes, parity gate, "
+                         "extra legs and the CPU baseline (--no-parity / --no-extras / --no-cpu-baseline trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/output.npy (float64, at most 64 MB)")
     args = ap.parse_args()
 
     import __graft_entry__ as entry
@@ -819,10 +866,67 @@ def main():
         ctx.synchronize()
         torch.cuda.synchronize()
 
-    # barrier + synchronize | exactly K steps | synchronize; MAX over ranks (tested on CPU with gloo)
+    # barrier + synchronize | exactly K steps | synchronize; MAX over ranks (tested on CPU with gloo).  The timed region is the same in a
+    # plain and a --full run (the events above included), so `ms_per_step` means the same in both
     elapsed = shard.timed_steps(step, args.steps, synchronize, dist if distributed else None, None)
     ctx.profile_enable(False)
     ctx.profile_sample(1)
+    # the last timed step's output, before anything else steps the context (collective: every rank sends its rows)
+    outputs = None
+    if args.dump_outputs:
+        outputs = dump_outputs(args.dump_outputs, y.cpu().numpy(), channel0, total_channels, rank, dist if distributed else None)
+        if outputs is not None:
+            outputs["calls"] = calls[0]         # the file holds the output of this call (counting the warm-up steps)
+
+    def headline(finite):
+        value = total_channels * frames * args.steps / elapsed / 1e6
+        line = {
+            "metric": METRIC,
+            "value": value,
+            "unit": "Msamples/s",
+            "n_gpus": world,
+            "n_gpus_requested": args.gpus,
+            "devices": devices,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "full": args.full,
+            "config": {
+                "workload": "%s @ %d Hz, %d-frame blocks, full chain: compressor>overdrive>tone_stack>chorus>power_amp(%d-tap cab IR)>power_amp(%d-tap reverb IR)>cabinet>reverb; %s; input resident in HBM"
+                            % (("%d channels in total, split over %d GPU(s) in contiguous blocks" % (total_channels, world)) if strong
+                               else ("%d channels/GPU" % nch), sr, frames, taps, taps,
+                               "per-channel IRs (d = 1)" if n_distinct == 0 else "%d distinct IR sets shared by the channels" % n_distinct),
+                "channels_per_gpu": nch, "total_channels": total_channels, "sample_rate": sr, "frames": frames, "ir_taps": taps,
+                "partitions": (taps + frames - 1) // frames,
+                "realtime_factor": value * 1e6 / (total_channels * sr),
+                "output_finite": finite,
+                "inputs": "SURVEY 8(d): two sines + 0.05 x the reference LCG (random/random.go) seeded 1337 + channel; IRs (1 - 2 r) exp(-6.9 k / L) on the "
+                          "LCG seeded 4242 + 2 channel (cabinet) / 4243 + 2 channel (reverb), unit energy",
+                "channel_groups": headline_groups,
+                "library_options": library_options,
+                "channel_groups_note": "opt-in through gdg_ctx_set_overlap (free-running groups; the library's default is 1, ordered on the context's stream)",
+                "control_plane": "gloo barrier + max of one scalar; no RCCL, no data-path collective",
+            },
+        }
+        if outputs is not None:
+            line["outputs"] = outputs
+        return line
+
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline(bool(torch.isfinite(y).all().item()))), flush=True)
+        ctx.close()
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # the timed region twice more (same K steps, same bracketing, rank-local): how far one run of it can be off
     repeats = []
     for _ in range(2):
@@ -1050,64 +1154,33 @@ def main():
                 seg_traffic = pmc.get("segment_kernel", {}).get("traffic_bytes_per_launch")
         except (OSError, ValueError, KeyError):
             pass
-        value = total_channels * frames * args.steps / elapsed / 1e6
-        out = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "n_gpus_requested": args.gpus,
-            "devices": devices,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_repeats": repeats,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": "%s @ %d Hz, %d-frame blocks, full chain: compressor>overdrive>tone_stack>chorus>power_amp(%d-tap cab IR)>power_amp(%d-tap reverb IR)>cabinet>reverb; %s; input resident in HBM"
-                            % (("%d channels in total, split over %d GPU(s) in contiguous blocks" % (total_channels, world)) if strong
-                               else ("%d channels/GPU" % nch), sr, frames, taps, taps,
-                               "per-channel IRs (d = 1)" if n_distinct == 0 else "%d distinct IR sets shared by the channels" % n_distinct),
-                "channels_per_gpu": nch, "total_channels": total_channels, "sample_rate": sr, "frames": frames, "ir_taps": taps, "partitions": K,
-                "realtime_factor": value * 1e6 / (total_channels * sr),
-                "output_finite": finite,
-                "inputs": "SURVEY 8(d): two sines + 0.05 x the reference LCG (random/random.go) seeded 1337 + channel; IRs (1 - 2 r) exp(-6.9 k / L) on the "
-                          "LCG seeded 4242 + 2 channel (cabinet) / 4243 + 2 channel (reverb), unit energy",
-                "channel_groups": headline_groups,
-                "library_options": library_options,
-                "channel_groups_note": "opt-in through gdg_ctx_set_overlap (free-running groups; the library's default is 1, ordered on the context's stream)",
-                "control_plane": "gloo barrier + max of one scalar; no RCCL, no data-path collective",
-            },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "fir_inv_kernel<13, 1> (spectrum multiply-accumulate fused into the inverse FFT)" if fused else "fir_mac_kernel",
-                "achieved": mac_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": (mac_gbs / HBM_PEAK_GBS) if mac_gbs else None,
-                "traffic": traffic,
-                "algorithmic_bytes_per_launch": mac_bytes, "avg_launch_ms": mac["avg_ms"], "launches": mac.get("launches_timed_region", mac["launches"]),
-                "chained_variant": {"kernel": "fir_inv_kernel<13, 1, CHAIN> (amp 1 of two adjacent power amps: + the forward transform of amp 2)",
-                                    "algorithmic_bytes_per_launch": chain_bytes, "avg_launch_ms": chain["avg_ms"], "launches": chain["launches"],
-                                    "achieved": chain_gbs, "frac": (chain_gbs / HBM_PEAK_GBS) if chain_gbs else None},
-                "fir_unit_all_three_kernels": {"bytes_per_channel_sample": fir_bytes_per_sample, "achieved": fir_gbs,
-                                               "frac": (fir_gbs / HBM_PEAK_GBS) if fir_gbs else None},
-                "kernels_ms": kernels,
-                "roofline_pass": {"channel_groups": 1, "ms_per_step": t_alone / args.steps * 1e3,
-                                  "value_this_rank": nch * frames * args.steps / t_alone / 1e6,
-                                  "note": "the same steps with every kernel alone on the chip (the pass `achieved` / `frac` come from)"},
-                "timed_region": {"channel_groups": groups, "mac_launches": timed_mac["launches"], "mac_avg_launch_ms": timed_mac["avg_ms"],
-                                 "bracketed_steps": "every %d-th of the %d timed steps" % (PROFILE_EVERY, args.steps),
-                                 "mac_achieved_while_sharing_the_chip": (mac_bytes / groups / (timed_mac["avg_ms"] * 1e-3) / 1e9) if timed_mac["avg_ms"] else None,
-                                 "note": "with channel groups > 1 a launch covers 1/groups of the channels and overlaps the other group's kernels"},
-                "segment_kernel": {"bytes_per_channel_sample_frame_only": 16.0,
-                                   "achieved": (seg["launches"] * samples_per_step * 16.0 / (seg["ms_total"] * 1e-3) / 1e9) if seg["ms_total"] else None,
-                                   # counter traffic incl. the state of the delay-type units (rings that cannot stay on chip)
-                                   "traffic": seg_traffic,
-                                   "achieved_incl_state": (seg_traffic / (seg["avg_ms"] * 1e-3) / 1e9) if (seg_traffic and seg["avg_ms"]) else None},
-            },
+        out = headline(finite)
+        out["ms_per_step_repeats"] = repeats
+        out["roofline"] = {
+            "bound": "hbm",
+            "kernel": "fir_inv_kernel<13, 1> (spectrum multiply-accumulate fused into the inverse FFT)" if fused else "fir_mac_kernel",
+            "achieved": mac_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": (mac_gbs / HBM_PEAK_GBS) if mac_gbs else None,
+            "traffic": traffic,
+            "algorithmic_bytes_per_launch": mac_bytes, "avg_launch_ms": mac["avg_ms"], "launches": mac.get("launches_timed_region", mac["launches"]),
+            "chained_variant": {"kernel": "fir_inv_kernel<13, 1, CHAIN> (amp 1 of two adjacent power amps: + the forward transform of amp 2)",
+                                "algorithmic_bytes_per_launch": chain_bytes, "avg_launch_ms": chain["avg_ms"], "launches": chain["launches"],
+                                "achieved": chain_gbs, "frac": (chain_gbs / HBM_PEAK_GBS) if chain_gbs else None},
+            "fir_unit_all_three_kernels": {"bytes_per_channel_sample": fir_bytes_per_sample, "achieved": fir_gbs,
+                                           "frac": (fir_gbs / HBM_PEAK_GBS) if fir_gbs else None},
+            "kernels_ms": kernels,
+            "roofline_pass": {"channel_groups": 1, "ms_per_step": t_alone / args.steps * 1e3,
+                              "value_this_rank": nch * frames * args.steps / t_alone / 1e6,
+                              "note": "the same steps with every kernel alone on the chip (the pass `achieved` / `frac` come from)"},
+            "timed_region": {"channel_groups": groups, "mac_launches": timed_mac["launches"], "mac_avg_launch_ms": timed_mac["avg_ms"],
+                             "bracketed_steps": "every %d-th of the %d timed steps" % (PROFILE_EVERY, args.steps),
+                             "mac_achieved_while_sharing_the_chip": (mac_bytes / groups / (timed_mac["avg_ms"] * 1e-3) / 1e9) if timed_mac["avg_ms"] else None,
+                             "note": "with channel groups > 1 a launch covers 1/groups of the channels and overlaps the other group's kernels"},
+            "segment_kernel": {"bytes_per_channel_sample_frame_only": 16.0,
+                               "achieved": (seg["launches"] * samples_per_step * 16.0 / (seg["ms_total"] * 1e-3) / 1e9) if seg["ms_total"] else None,
+                               # counter traffic incl. the state of the delay-type units (rings that cannot stay on chip)
+                               "traffic": seg_traffic,
+                               "achieved_incl_state": (seg_traffic / (seg["avg_ms"] * 1e-3) / 1e9) if (seg_traffic and seg["avg_ms"]) else None},
         }
         if parity is not None:
             out["parity"] = parity

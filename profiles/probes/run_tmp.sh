@@ -5,7 +5,7 @@ for rep in 1 2; do
     if [ $which = old ]; then cp profiles/probes/bin/libgdg_old.so go-dsp-guitar_amd/lib/libgdg.so; else cp /tmp/libgdg_new.so go-dsp-guitar_amd/lib/libgdg.so; fi
     echo "== $which rep $rep"
     python profiles/seg_breakdown.py 2>&1 | grep -E "copy|compressor|overdrive |tone_stack|chorus|cabinet|reverb|seg0|seg1"
-    timeout 300 python bench.py --steps 20 --warmup 25 --no-cpu-baseline --no-extras --no-parity --channel-groups 1 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 25 --no-cpu-baseline --no-extras --no-parity --channel-groups 1 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

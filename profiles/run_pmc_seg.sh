@@ -5,7 +5,7 @@ TAG=${1:-r03}
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p "$REPO/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extras --no-parity --channel-groups 1"
+CMD="python $REPO/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extras --no-parity --channel-groups 1"
 OUT="$REPO/gpurun_out/${TAG}_seg_valu_pmc.txt"
 echo "# rocprofv3 --pmc <set> -- $CMD   (one pass per counter set)" > "$OUT"
 i=0

@@ -15,7 +15,7 @@ def test_plain_python_bench_gpus_2_prints_a_two_rank_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["GDG_BENCH_ONE_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--channels", "64",
-                        "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                      # rank 0 alone prints
@@ -44,3 +44,52 @@ def test_two_ranks_on_one_gpu_are_refused_unless_asked_for():
     else:
         assert r.returncode != 0 and not lines, r.stdout[-500:]
         assert "share 1 device" in r.stderr
+
+
+def _oracle_output(oracle, bench, channel, blocks, frames, sr, taps, calls):
+    """What the oracle's chain for `channel` returns on call number `calls`, fed the bench's round-robin input blocks."""
+    ch = oracle.Chain()
+    for name, p in bench.CHAIN:
+        if isinstance(p, str):
+            ch.append_unit(name, fir=bench.ir_for(p, channel, taps))
+        else:
+            ch.append_unit(name, params=p)
+    for k in range(calls):
+        want = ch.process(blocks[k % len(blocks)][channel], sr)
+    return want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_run_prints_the_headline_alone_and_dumps_the_last_timed_step(tmp_path, oracle, gpus):
+    """A plain run (no --full): exactly --steps timed steps and the headline, none of what --full measures besides.  --dump-outputs writes
+    the output of the last timed step for every channel of the job, in global order (with two ranks on one device: gathered from both);
+    the oracle, fed the same blocks for the same number of calls, gives the same samples."""
+    import numpy as np
+    import bench
+    nch, frames, sr, taps, steps, warmup = 6, 1024, 48000, 4096, 3, 2
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    if gpus > 1:
+        env["GDG_BENCH_ONE_DEVICE"] = "1"           # both ranks on device 0: what is tested is the gather of the rows, not scaling
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup),
+                        "--channels", str(nch), "--frames", str(frames), "--sample-rate", str(sr), "--taps", str(taps),
+                        "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["n_gpus"] == gpus and line["steps"] == steps and line["warmup"] == warmup
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and line["value"] > 0
+    assert abs(line["value"] - nch * frames / (line["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * line["value"]
+    assert line["config"]["output_finite"] and line["config"]["total_channels"] == nch
+    for key in ("ms_per_step_repeats", "roofline", "parity", "settled", "cpu_baseline", "end_to_end", "configs", "strong_split_legs", "one_gpu_alone"):
+        assert key not in line, key
+    assert line["outputs"]["channels"] == "all" and line["outputs"]["calls"] == warmup + steps
+    assert sorted(os.listdir(out_dir)) == ["output.npy"]
+    y = np.load(out_dir / "output.npy")
+    assert y.dtype == np.float64 and y.shape == (nch, frames)
+    blocks = bench.synth_blocks(nch, frames, sr)
+    for c in (0, nch - 1):                      # with two ranks: one channel of each
+        want = _oracle_output(oracle, bench, c, blocks, frames, sr, taps, warmup + steps)
+        assert float(np.sqrt(np.mean((y[c] - want) ** 2))) <= 1e-9, c
