@@ -425,8 +425,7 @@ int gdg_unit_set_param(gdg_ctx *ctx, int handle, int param_index, int32_t value)
          * taps (gdg_unit_set_fir), and a unit that is not in the plan (bypassed, or in no chain) has nothing on the device to update.
          * Layout changes (gdg_chain_set), frame size, rate and new filters still rebuild the plan. */
         /* a shaper's oversampling factor decides which LAUNCHES the plan holds (a segment cut at the unit, os_tiles_kernel<2 / 4>): a new plan */
-        const bool shaper = u->type == GDG_UNIT_OVERDRIVE || u->type == GDG_UNIT_DISTORTION || u->type == GDG_UNIT_EXCESS;
-        const bool os_changed = shaper && param_index == (u->type == GDG_UNIT_OVERDRIVE ? 5 : (u->type == GDG_UNIT_DISTORTION ? 3 : 2));
+        const bool os_changed = param_index == shaper_os_param(u->type);
         if (ctx->dirty || !ctx->plan_patch || os_changed) ctx->dirty = true;
         else if (u->type != GDG_UNIT_POWERAMP && (size_t)handle < ctx->plan_unit_slot.size() && ctx->plan_unit_slot[(size_t)handle] >= 0) {
             if (std::find(ctx->patch_units.begin(), ctx->patch_units.end(), handle) == ctx->patch_units.end()) ctx->patch_units.push_back(handle);

@@ -295,7 +295,7 @@ int prepare_unit(gdg_ctx *ctx, Unit &u, int frames, uint32_t sample_rate, gdg_se
         }
         /* behind the rings (even offset): the sums  tapped + all-passed  of a frame whose wet path an earlier launch of the call makes (seg.hip, REVERB_AHEAD) */
         len = ((len + 1) & ~(size_t)1) + GDG_MAX_FRAMES;
-        d.ip[7] = 0;                    /* 1: an earlier launch of the call makes the unit's wet path (build_plan decides) */
+        d.ip[7] = 0;                    /* 1: an earlier launch of the call makes the unit's wet path (decide_shapes) */
         /* the reference rebuilds every reverb buffer when the sample rate changes (reverb.go:207-271) */
         if (u.hist_key != (long long)sample_rate) rc = zero_is(ctx, u, 0, 4);
         if (rc == GDG_OK) rc = ensure_hist(ctx, u, len, (long long)sample_rate);
@@ -642,6 +642,183 @@ static int prepare_fir(gdg_ctx *ctx, Unit &u, int hop, uint32_t sample_rate) {
 }
 
 struct Op { bool is_fir; std::vector<int> handles; };
+enum { K_SEG = 0, K_FIR = 1, K_OS2 = 2, K_OS4 = 3 };       /* what a slot holds: segment pieces, a power amp, a 2 x / 4 x oversampled shaper */
+/* one step of the plan under construction: its kind, its (channel, op) pairs in `active` order, its first unit in the plan's unit array */
+struct PlanStep { int kind; std::vector<std::pair<int, Op>> ops; int unit_begin; };
+
+/* How a unit of a WAVE launch hands its state to the next frame's workgroup (seg.hip, wave_mask): 0 it has none (a shaper without
+ * oversampling), 1 stores written through, 2 plain stores and a write-back of the XCD's L2 -- a shaper's oversampler state is written
+ * through on the general kernel only. */
+static int wave_hand_off(const Unit &u, bool fast) {
+    const int os = shaper_os_param(u.type);
+    if (os >= 0 && u.params[os] == 0) return 0;
+    const bool through = u.type == GDG_UNIT_COMPRESSOR || u.type == GDG_UNIT_TONESTACK || u.type == GDG_UNIT_CABINET || u.type == GDG_UNIT_CHORUS ||
+                         u.type == GDG_UNIT_REVERB || (os >= 0 && !fast);
+    return through ? 1 : 2;
+}
+
+/* ---- launch shapes: every option that picks a kernel or a launch shape is read here and nowhere else -------------------------------- */
+
+/* calls of few channels run every oversampled shaper as a launch of its own (the one decision the slot grid itself depends on) */
+static bool shapers_launch_alone(const gdg_ctx *ctx, int n_act, int frames) {
+    return ctx->seg_os_tiles_max > 0 && n_act <= ctx->seg_os_tiles_max && frames == GDG_MAX_FRAMES;
+}
+
+/* a tiled launch's workgroups, 2 x channels + the reverbs' extra ones, leave the chip room: of 256 CUs, one workgroup each.  Per step, tile
+ * kernel off / on (profiles/tile_ab_r06.txt, shape_sweep_r06.txt): bench chain 64 channels (192 workgroups) 142.9 -> 138.4 us, 72 (216)
+ * 148.8 -> 146.6, 80 (240) 155.9 -> 158.0; no reverb, 96 channels (192) 111.5 -> 103.6; 96 kHz chain with a reverb, 96 channels (288) 110.9 -> 118.7 */
+#define GDG_TILE_WORKGROUP_BUDGET 224
+
+/* What the plan's descriptors need of the decisions besides the shapes in StepDesc */
+struct Decisions {
+    std::vector<char> fast;                    /* per step: a segment on the two-per-CU kernel (its units' scan tables in 16-sample chunks) */
+    std::vector<char> made_ahead;              /* per unit of the plan's array: a reverb whose wet path an earlier launch of the call makes (ip[7]) */
+    std::vector<std::vector<int>> ahead;       /* per step: the reverbs (indices into the unit array) whose wet paths its launch makes */
+};
+
+/* The launch shape of every step for both call kinds.  The plan fixes channels, groups and frame size; only per-frame call or window is
+ * open, so each step gets one shape per kind (and per channel group for the power amps: the split / fused test counts the group's channels). */
+static void decide_shapes(gdg_ctx *ctx, const std::vector<PlanStep> &plan, int n_act, int frames, uint32_t sample_rate, int G, int n_units, Decisions &dec) {
+    std::vector<StepDesc> &steps = ctx->steps;
+    const size_t S = steps.size();
+    const bool batch = frames == GDG_MAX_FRAMES;
+    dec.fast.assign(S, 0);
+    dec.made_ahead.assign((size_t)n_units, 0);
+    dec.ahead.assign(S, std::vector<int>());
+    int fir_steps = 0;
+    for (auto &st : steps) fir_steps += st.is_fir ? 1 : 0;
+
+    /* power amps.  Split: the multiply-accumulate as its own bin-tiled kernel, up to fir_split_max channels -- by the number of power amps
+     * per channel (ctx.h); above, the fused kernel (a workgroup per channel) fills the chip.  Premac: the terms k >= 1 of the next frame
+     * summed ahead -- the split shape, one group, batch frames, every channel K >= 2, enough partitions to pay for the hops. */
+    const int split_max = fir_steps >= 2 ? ctx->fir_split_max : std::min(ctx->fir_split_max, ctx->fir_split_max_single);
+    auto fused = [&](int n) { return ctx->fir_fused < 0 ? n > split_max : ctx->fir_fused != 0; };
+    const long premac_min = fir_steps >= 2 ? std::min(ctx->fir_premac_min, ctx->fir_premac_min_two) : ctx->fir_premac_min;
+    int premac_steps = 0;
+    for (size_t i = 0; i < S; i++) {
+        StepDesc &st = steps[i];
+        if (!st.is_fir) continue;
+        long partitions = 0;
+        bool every_k2 = true;
+        for (auto &e : plan[i].ops) {
+            const int K = ctx->units[(size_t)e.second.handles[0]].fir_K;
+            partitions += K;
+            every_k2 = every_k2 && K >= 2;
+        }
+        const bool premac = ctx->fir_premac != 0 && !fused(st.n) && G == 1 && batch && every_k2 && partitions >= premac_min;
+        premac_steps += premac ? 1 : 0;
+        for (auto &r : st.runs) r.frame = fused(r.n) ? Shape::FUSED : premac ? Shape::SPLIT_PREMAC : Shape::SPLIT;
+        st.window = Shape::FIR_WINDOW;
+        /* LDS the premac's workgroups ask for and never touch: such a workgroup does not fit on a CU beside a general or tile segment
+         * workgroup (159 KiB), and at most one fits beside a two-per-CU one (80 KiB), so the sums run on the CUs the segments leave idle
+         * and not among their waves.  Pays where the sums are neither a sliver nor the whole frame -- 5 .. 32 partitions per channel:
+         * 48 channels x 65536 taps 124.5 -> 119.9 us per frame, 128 channels 195.3 -> 185.2; 128 x 32768 taps 168 -> 172 and 64 x 1048576
+         * taps 305 -> 320 WITH it, hence the bounds (profiles/premac_loads_ab_r06.txt) */
+        const long per_channel = st.n > 0 ? partitions / st.n : 0;
+        st.premac_lds = ctx->fir_premac_lds >= 0 ? ctx->fir_premac_lds : ((per_channel >= 5 && per_channel <= 32) ? (st.n < 120 ? 16384 : 49152) : 0);
+        /* adjacent power amps (the benchmark chain: cabinet IR, then reverb IR): when EVERY channel hands its frame to the next step, that
+         * step's forward transform is produced by this step's inverse kernel -- no launch, no round trip of the frame */
+        if (ctx->fir_chain && batch && i + 1 < S && steps[i + 1].is_fir && plan[i].ops.size() == plan[i + 1].ops.size()) {
+            bool same = true;
+            for (size_t k = 0; same && k < plan[i].ops.size(); k++) same = plan[i].ops[k].first == plan[i + 1].ops[k].first;
+            st.chain_next = same;
+        }
+    }
+
+    /* segments, in order.  Reverbs' wet paths as extra workgroups of an earlier general-kernel launch of the call, in per-frame calls of one
+     * group of few channels -- fewer with the premac, whose launches want the same idle CUs (ctx.h seg_reverb_ahead_max) */
+    const int ahead_max = premac_steps > 0 ? ctx->seg_reverb_ahead_max : std::max(ctx->seg_reverb_ahead_max, 127);
+    const bool ahead_ok = G == 1 && ctx->seg_reverb_ahead_max > 0 && n_act <= ahead_max && reverb_ahead_ok(frames, sample_rate);
+    std::vector<char> skip(S, 0);              /* a compressor step the next step's OS_TILES_PREFIX launch runs */
+    int host = -1;                             /* the general-kernel step, among those already decided, that makes the reverbs' wet paths */
+    double host_weight = 0.0;
+    for (size_t i = 0; i < S; i++) {
+        const StepDesc &st = steps[i];
+        if (st.is_fir) continue;
+        const bool is_os = st.os_factor != 0;
+        /* the two-per-CU kernel when EVERY unit of EVERY channel of the step can (one launch per step) */
+        bool fast = !is_os && ctx->seg_fast && batch && n_act >= ctx->seg_fast_min;
+        for (auto &e : plan[i].ops)
+            for (int h : e.second.handles) fast = fast && segf_unit_ok(ctx->units[(size_t)h], frames, sample_rate);
+        dec.fast[i] = fast ? 1 : 0;
+        int unit = plan[i].unit_begin;
+        for (auto &e : plan[i].ops)
+            for (int h : e.second.handles) {
+                if (ctx->units[(size_t)h].type == GDG_UNIT_REVERB && !fast && !is_os && host >= 0 && ahead_ok) {
+                    dec.made_ahead[(size_t)unit] = 1;
+                    dec.ahead[(size_t)host].push_back(unit);
+                }
+                unit++;
+            }
+        if (is_os && ctx->seg_os_prefix && G == 1 && i > 0 && !steps[i - 1].is_fir && !steps[i - 1].os_factor && !dec.fast[i - 1] && steps[i - 1].n == st.n) {
+            /* the step in front: the same channels in the same order, each with ONE unit, a compressor, feeding this shaper */
+            bool lone = true;
+            for (size_t k = 0; lone && k < plan[i].ops.size(); k++) {
+                const auto &pe = plan[i - 1].ops[k];
+                lone = pe.first == plan[i].ops[k].first && pe.second.handles.size() == 1 && ctx->units[(size_t)pe.second.handles[0]].type == GDG_UNIT_COMPRESSOR;
+            }
+            if (lone) {
+                steps[i].os_prefix_step = (int)i - 1;
+                skip[i - 1] = 1;
+                if (host == (int)i - 1) { host = -1; host_weight = 0.0; }      /* nothing has been given to it yet: it is the step right in front */
+            }
+        }
+        if (!is_os && !fast) {
+            /* the host: the earlier general-kernel launch that lives longest (the extra workgroups take ~15 us at 192 kHz; behind a short
+             * launch -- a lone compressor -- they would BE the launch).  Rough unit times in us, one workgroup per CU (profiles/seg_latency_by_channels_r04.txt) */
+            double w = 0.0;
+            for (int h : plan[i].ops[0].second.handles) {
+                switch (ctx->units[(size_t)h].type) {
+                case GDG_UNIT_COMPRESSOR: w += 2.6; break;
+                case GDG_UNIT_TONESTACK: case GDG_UNIT_CABINET: w += 6.5; break;
+                case GDG_UNIT_CHORUS: w += 9.2; break;
+                case GDG_UNIT_REVERB: w += 18.0; break;
+                case GDG_UNIT_AUTOWAH: w += 14.0; break;
+                default: w += 4.0; break;
+                }
+            }
+            if (host < 0 || w > host_weight) { host = (int)i; host_weight = w; }
+        }
+    }
+    /* Two power amps' sums made ahead stream twice as long beside the segments: the tile kernel then only pays up to the channel count the
+     * reverbs' extra workgroups pay to (bench chain, tile kernel off / on: 80 channels 162.4 -> 157.8 us, 96: 173.4 -> 177.4; one amp, 96: 112.9 -> 104.2) */
+    const bool tiles = n_act <= ctx->seg_tile_max && G == 1 && batch && !(premac_steps >= 2 && n_act > ctx->seg_reverb_ahead_max);
+    for (size_t i = 0; i < S; i++) {
+        StepDesc &st = steps[i];
+        if (st.is_fir) continue;
+        if (st.os_factor) {
+            st.window = Shape::OS_TILES;
+            st.runs[0].frame = st.os_prefix_step >= 0 ? Shape::OS_TILES_PREFIX : Shape::OS_TILES;
+            for (auto &r : st.runs) r.frame = st.runs[0].frame;
+            continue;
+        }
+        const bool fast = dec.fast[i] != 0;
+        /* windows of few channels: a workgroup per FRAME and channel (seg_wave_max); fewer when a unit hands its state on through a write-back */
+        bool release = false;
+        int unit = plan[i].unit_begin;
+        for (auto &e : plan[i].ops)
+            for (int h : e.second.handles) release = release || wave_hand_off(ctx->units[(size_t)h], fast) == 2;
+        const int wave_max = release ? std::min(ctx->seg_wave_max, ctx->seg_wave_release_max) : ctx->seg_wave_max;
+        const bool wave = n_act <= wave_max && st.wave_tickets >= 0;
+        st.window = fast ? (wave ? Shape::SEGF_WAVE : Shape::SEGF_WALK) : (wave ? Shape::WAVE : Shape::WALK);
+        /* a channel's frame on two workgroups: unit types, no oversampling, at most 32 exchange ids and 16 units per segment; a reverb only
+         * as the mix of a wet path an earlier launch made (seg.hip unit_reverb_mix_tile) */
+        bool tile = tiles && !fast && st.wave_tickets >= 0 && 2 * st.n + (int)dec.ahead[i].size() <= GDG_TILE_WORKGROUP_BUDGET;
+        for (auto &e : plan[i].ops) {
+            int xids = 0;
+            for (int h : e.second.handles) {
+                const Unit &tu = ctx->units[(size_t)h];
+                const int os = shaper_os_param(tu.type);
+                if (!gdg_segt_supported(tu.type) || (os >= 0 && tu.params[os] != 0) || (gdg_segt_supported(tu.type) == 2 && !dec.made_ahead[(size_t)unit])) tile = false;
+                xids += gdg_segt_exchanges(tu.type);
+                unit++;
+            }
+            if (xids > 32 || e.second.handles.size() > 16 || e.second.handles.empty()) tile = false;
+        }
+        const Shape frame = skip[i] ? Shape::SKIP : fast ? Shape::SEGF : tile ? Shape::SEGT : dec.ahead[i].empty() ? Shape::GENERAL : Shape::GENERAL_AHEAD;
+        for (auto &r : st.runs) r.frame = frame;
+    }
+}
 
 /* `active`: the channels taking part in this call; row i of d_in / d_out belongs to channel active[i] */
 int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in, double *d_out, int frames, uint32_t sample_rate,
@@ -649,6 +826,7 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
     const int nch = ctx->nch;
     int ptrace = 0;
     { const char *e = getenv("GDG_PLAN_TRACE"); ptrace = e ? atoi(e) : 0; }        /* read per plan: a test switches it on */
+    ctx->plan_trace = ptrace;
     auto pnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_fir = 0.0, t_unit = 0.0;
     const double t_plan0 = pnow();
@@ -666,24 +844,24 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
             ctx->scan_tabs.clear();
         }
     }
+    const int n_act = (int)active.size();
+    /* ---- 1. the slot grid ---- */
     /* channel groups: contiguous runs of `active`, group g = [bounds[g], bounds[g + 1]) (equal shares unless the caller weights them) */
     std::vector<int> group_of((size_t)nch, 0);
     for (int g = 0; g < G; g++)
         for (size_t i = bounds[(size_t)g]; i < bounds[(size_t)g + 1]; i++) group_of[(size_t)active[i]] = g;
     ctx->plan_groups = G;
-    /* per channel: ops placed on a common grid of slots: 2k = segment k, 2k+1 = FIR k */
+    /* per channel: ops placed on a common grid of slots */
     std::map<int, std::vector<std::pair<int, Op>>> by_slot;           /* slot -> (channel, op) */
     std::vector<int> n_ops((size_t)nch, 0);
     std::vector<int> row_of((size_t)nch, -1);
     for (size_t i = 0; i < active.size(); i++) row_of[(size_t)active[i]] = rows_by_channel ? active[i] : (int)i;
-    bool any_fir = false;
     /* Slots: the ops of all channels are laid on one grid so that one launch takes the same op of every channel that has it.  Power amp number k
      * of a channel sits at slot_key(k, 63, fir); what stands between power amps k - 1 and k is segment pieces (kind 0) and -- when the channels
      * are too few to fill the chip -- oversampled shapers as launches of their own (kinds 2 / 3 for 2 x / 4 x: seg.hip os_tiles_kernel), numbered
      * j = 0, 1, 2 ... in the order they come.  A channel without such a shaper has ONE piece (j = 0), as before. */
-    enum { K_SEG = 0, K_FIR = 1, K_OS2 = 2, K_OS4 = 3 };
     auto slot_key = [](int k, int j, int kind) { return (k * 64 + j) * 4 + kind; };
-    const bool os_tiles = ctx->seg_os_tiles_max > 0 && (int)active.size() <= ctx->seg_os_tiles_max && frames == GDG_MAX_FRAMES;
+    const bool os_tiles = shapers_launch_alone(ctx, n_act, frames);
     for (int c : active) {
         std::vector<int> seg;
         int k = 0, j = 0, count = 0;
@@ -697,11 +875,10 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
                 count++;
                 k++;
                 j = 0;
-                any_fir = true;
             } else {
                 if (!gdg_seg_supported(u.type)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unit type %d has no HIP implementation yet", u.type);
-                const bool shaper = u.type == GDG_UNIT_OVERDRIVE || u.type == GDG_UNIT_DISTORTION || u.type == GDG_UNIT_EXCESS;
-                const int os_index = !shaper ? 0 : u.params[u.type == GDG_UNIT_OVERDRIVE ? 5 : (u.type == GDG_UNIT_DISTORTION ? 3 : 2)];      /* 0 none, 1 "2", 2 "4" */
+                const int os_param = shaper_os_param(u.type);
+                const int os_index = os_param < 0 ? 0 : u.params[os_param];      /* 0 none, 1 "2", 2 "4" */
                 if (os_tiles && os_index > 0 && j < 60) {
                     close_seg();
                     by_slot[slot_key(k, j, os_index == 1 ? K_OS2 : K_OS4)].push_back({ c, Op{ false, { s.handle } } });
@@ -714,7 +891,6 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
         if (count == 0) { by_slot[slot_key(0, 0, K_SEG)].push_back({ c, Op{ false, {} } }); count = 1; }     /* empty chain: copy */
         n_ops[(size_t)c] = count;
     }
-    (void)any_fir;
     /* counters of the WAVE launches: tickets per (segment step, channel group), then one frame counter per unit that sits in a segment */
     {
         /* 8 cells per unit in a segment + a flag and an arrival counter per oversampled shaper that is a launch of its own (each such unit is one descriptor of one step) */
@@ -728,56 +904,76 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
             HIP_TRY(ctx, hipMemsetAsync(ctx->d_wave, 0, ctx->d_wave_cap * sizeof(int), ctx->stream));
         }
     }
+    /* the steps, in slot order; descriptors are in `active` order, so every channel group owns one contiguous run of them */
+    std::vector<PlanStep> plan;
+    ctx->steps.clear();
+    int seg_steps = 0, n_units = 0;
+    for (auto &kv : by_slot) {
+        PlanStep ps{ kv.first & 3, std::move(kv.second), n_units };
+        StepDesc st;
+        st.is_fir = ps.kind == K_FIR;
+        st.os_factor = ps.kind == K_OS2 ? 2 : ps.kind == K_OS4 ? 4 : 0;
+        st.n = (int)ps.ops.size();
+        st.offset = 0;
+        st.runs.assign((size_t)G, StepDesc::Run());
+        for (int pos = 0; pos < st.n; pos++) {
+            auto &r = st.runs[(size_t)group_of[(size_t)ps.ops[(size_t)pos].first]];
+            if (r.n == 0) r.first = pos;
+            r.n++;
+        }
+        if (!st.is_fir) {
+            for (auto &e : ps.ops) n_units += (int)e.second.handles.size();
+            if (seg_steps < GDG_WAVE_STEPS && G <= GDG_WAVE_GROUPS) st.wave_tickets = GDG_WAVE_GROUPS * seg_steps++;
+        }
+        ctx->steps.push_back(st);
+        plan.push_back(std::move(ps));
+    }
+    /* ---- 2. the filters: delay lines and spectra for this frame size (the premac's bound counts their partitions) ---- */
+    for (auto &ps : plan) {
+        if (ps.kind != K_FIR) continue;
+        for (auto &e : ps.ops) {
+            const double tq = pnow();
+            int rc = prepare_fir(ctx, ctx->units[(size_t)e.second.handles[0]], frames, sample_rate);
+            t_fir += pnow() - tq;
+            if (rc != GDG_OK) return rc;
+        }
+    }
+    /* ---- 3. the launch shapes ---- */
+    Decisions dec;
+    decide_shapes(ctx, plan, n_act, frames, sample_rate, G, n_units, dec);
+    /* ---- 4. the descriptors ---- */
     size_t wave_next = (size_t)GDG_WAVE_STEPS * GDG_WAVE_GROUPS;
-    int seg_steps = 0;
-    /* blob layout: [step 0 descs][step 1 descs]...[seg units] */
+    /* blob layout: [step 0 descs][step 1 descs]...[seg units][ahead lists] */
     std::vector<gdg_seg_unit> seg_units;
-    std::vector<std::pair<int, int>> tile_conditional;     /* (step, index into seg_units) of reverbs in steps that could run tiled: they can if their wet path is made ahead */
-    std::vector<std::vector<int>> ahead_lists; /* per step: reverbs of later steps (indices into seg_units) whose wet path the step's launch makes (seg.hip REVERB_AHEAD) */
-    int ahead_host = -1;                       /* the general-kernel segment step, among those already laid out, that hosts them */
-    double ahead_host_weight = 0.0;
     std::vector<std::vector<gdg_seg_chan>> seg_descs;
     std::vector<std::vector<gdg_fir_chan>> fir_descs;
     std::vector<int> done((size_t)nch, 0);
     std::vector<const double *> cur((size_t)nch);
     for (int c : active) cur[(size_t)c] = d_in + (size_t)row_of[(size_t)c] * stride;
-    ctx->steps.clear();
     ctx->plan_unit_slot.assign(ctx->units.size(), -1);
     ctx->patch_units.clear();                  /* this plan reads every unit's current parameters */
     ctx->plan_unit_fast.assign(ctx->units.size(), 0);
     ctx->plan_unit_fast_ok.assign(ctx->units.size(), 0);
-    ctx->plan_fir_steps = 0;
-    for (auto &kv : by_slot) if ((kv.first & 3) == K_FIR) ctx->plan_fir_steps++;
-    for (auto &kv : by_slot) {
-        const int kind = kv.first & 3;
-        const bool is_fir = kind == K_FIR, is_os = kind == K_OS2 || kind == K_OS4;
+    for (size_t i = 0; i < plan.size(); i++) {
+        StepDesc &st = ctx->steps[i];
+        const bool step_fast = dec.fast[i] != 0;
         std::vector<gdg_seg_chan> sd;
         std::vector<gdg_fir_chan> fd;
-        /* a segment step goes to the two-per-CU kernel when EVERY unit of EVERY channel in it can (one launch per step) */
-        const int n_act = (int)active.size();
-        const int fast_min = ctx->seg_fast_min;
-        bool step_fast = !is_fir && !is_os && ctx->seg_fast && frames == GDG_MAX_FRAMES && n_act >= fast_min;
-        if (step_fast)
-            for (auto &entry : kv.second)
-                for (int h : entry.second.handles) if (!segf_unit_ok(ctx->units[(size_t)h], frames, sample_rate)) { step_fast = false; break; }
-        for (auto &entry : kv.second) {
+        for (auto &entry : plan[i].ops) {
             int c = entry.first;
-            Op &op = entry.second;
+            const Op &op = entry.second;
             bool last = (done[(size_t)c] + 1 == n_ops[(size_t)c]);
             double *dst;
             if (last) dst = d_out + (size_t)row_of[(size_t)c] * stride_out;
             else dst = ((done[(size_t)c] & 1) ? ctx->d_w1 : ctx->d_w0) + (size_t)c * ctx->w_stride;
-            if (is_fir) {
+            if (st.is_fir) {
                 Unit &u = ctx->units[(size_t)op.handles[0]];
-                const double tq = pnow();
-                int rc = prepare_fir(ctx, u, frames, sample_rate);
-                t_fir += pnow() - tq;
-                if (rc != GDG_OK) return rc;
                 gdg_fir_chan f;
                 memset(&f, 0, sizeof(f));
                 f.src = cur[(size_t)c]; f.dst = dst; f.prev = u.d_prev; f.fdl = u.d_fdl; f.H = u.H->d_H; f.Y = u.d_Y;
                 f.pos = u.d_pos; f.K = u.fir_K; f.R = u.fir_R; f.hop = frames;
-                f.flags = (done[(size_t)c] == 0 ? GDG_SRC_IS_INPUT : 0) | (last ? GDG_DST_IS_OUTPUT : 0);
+                f.flags = (done[(size_t)c] == 0 ? GDG_SRC_IS_INPUT : 0) | (last ? GDG_DST_IS_OUTPUT : 0) |
+                          (st.chain_next ? GDG_DST_UNUSED : 0);      /* only the chained transform reads the frame (window-mode kernels ignore the flag) */
                 fd.push_back(f);
                 u.fir_live = true;
             } else {
@@ -794,15 +990,12 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
                     unsigned mask = 0;
                     for (size_t ui = 0; ui < op.handles.size(); ui++) {
                         const Unit &wu = ctx->units[(size_t)op.handles[ui]];
-                        const bool shaper = wu.type == GDG_UNIT_OVERDRIVE || wu.type == GDG_UNIT_DISTORTION || wu.type == GDG_UNIT_EXCESS;
-                        const int os_param = wu.type == GDG_UNIT_OVERDRIVE ? 5 : (wu.type == GDG_UNIT_DISTORTION ? 3 : 2);
-                        if (shaper && wu.params[os_param] == 0) continue;                       /* memoryless: no state, no meeting */
+                        const int hand_off = wave_hand_off(wu, step_fast);
+                        if (hand_off == 0) continue;
                         if (ui < 15) mask |= 1u << ui;
                         if (ui < 15 && (wu.type == GDG_UNIT_COMPRESSOR || wu.type == GDG_UNIT_TONESTACK || wu.type == GDG_UNIT_CABINET))
                             mask |= 1u << (16 + ui);                                              /* all their state is a few cells, read past the L1 */
-                        const bool write_through = wu.type == GDG_UNIT_COMPRESSOR || wu.type == GDG_UNIT_TONESTACK || wu.type == GDG_UNIT_CABINET ||
-                                                   wu.type == GDG_UNIT_CHORUS || wu.type == GDG_UNIT_REVERB || (shaper && !step_fast);
-                        if (!write_through) mask |= 1u << 31;
+                        if (hand_off == 2) mask |= 1u << 31;
                     }
                     s.wave_mask = (int)mask;
                 }
@@ -816,13 +1009,7 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
                      * line exactly one batch frame longer than the longest tap (seg.hip): a change of one side without the other stops here */
                     if (du.type == GDG_UNIT_REVERB && du.jp[4] != std::max(std::max(du.jp[0], du.jp[1]), std::max(du.jp[2], du.jp[3])) + GDG_MAX_FRAMES)
                         return fail(ctx, GDG_ERR_INVALID, "reverb delay line of %d cells, expected the longest tap + %d", du.jp[4], GDG_MAX_FRAMES);
-                    /* a reverb behind an earlier general-kernel segment launch of the same call: that launch makes its wet path beside its own
-                     * channels (extra workgroups: the channels are too few to fill the chip), the unit itself only mixes */
-                    if (du.type == GDG_UNIT_REVERB && !step_fast && !is_os && ahead_host >= 0 && ctx->seg_reverb_ahead_max > 0 && n_act <= std::max(ctx->seg_reverb_ahead_max, 127) &&
-                        reverb_ahead_ok(frames, sample_rate)) {
-                        du.ip[7] = 1;
-                        ahead_lists[(size_t)ahead_host].push_back((int)seg_units.size());
-                    }
+                    if (du.type == GDG_UNIT_REVERB) du.ip[7] = dec.made_ahead[seg_units.size()];
                     ctx->plan_unit_slot[(size_t)h] = (int)seg_units.size();
                     ctx->plan_unit_fast[(size_t)h] = step_fast ? 1 : 0;
                     ctx->plan_unit_fast_ok[(size_t)h] = segf_unit_ok(ctx->units[(size_t)h], frames, sample_rate) ? 1 : 0;
@@ -833,133 +1020,21 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
             cur[(size_t)c] = dst;
             done[(size_t)c]++;
         }
-        StepDesc st;
-        st.is_fir = is_fir;
-        st.os_factor = is_os ? (kind == K_OS2 ? 2 : 4) : 0;
-        st.fast = step_fast;
-        st.n = is_fir ? (int)fd.size() : (int)sd.size();
-        for (auto &d : sd) if ((unsigned)d.wave_mask >> 31) st.wave_release = true;
-        if (!is_fir && !is_os && !step_fast && frames == GDG_MAX_FRAMES && n_act <= ctx->seg_tile_max && !sd.empty()) {
-            /* a channel's frame on two workgroups in per-frame calls: unit types, no oversampling, the exchange ids of a segment within the area */
-            st.tile_ok = true;
-            for (auto &entry : kv.second) {
-                int xids = 0;
-                for (int h : entry.second.handles) {
-                    const Unit &tu = ctx->units[(size_t)h];
-                    const bool shaper = tu.type == GDG_UNIT_OVERDRIVE || tu.type == GDG_UNIT_DISTORTION || tu.type == GDG_UNIT_EXCESS;
-                    const int os_param = tu.type == GDG_UNIT_OVERDRIVE ? 5 : (tu.type == GDG_UNIT_DISTORTION ? 3 : 2);
-                    if (!gdg_segt_supported(tu.type) || (shaper && tu.params[os_param] != 0)) st.tile_ok = false;
-                    if (gdg_segt_supported(tu.type) == 2) tile_conditional.push_back(std::make_pair((int)ctx->steps.size(), ctx->plan_unit_slot[(size_t)h]));   /* a reverb: only as a mix (below) */
-                    xids += gdg_segt_exchanges(tu.type);
-                }
-                if (xids > 32 || entry.second.handles.size() > 16 || entry.second.handles.empty()) st.tile_ok = false;
-            }
-        }
-        st.offset = 0;
-        if (!is_fir && seg_steps < GDG_WAVE_STEPS && G <= GDG_WAVE_GROUPS) st.wave_tickets = GDG_WAVE_GROUPS * seg_steps++;
-        if (is_os) { st.os_flags = (int)wave_next; wave_next += sd.size(); st.os_arrive = (int)wave_next; wave_next += sd.size(); }    /* a flag and an arrival counter per channel of the launch (os_tiles_kernel) */
-        if (is_os && ctx->seg_os_prefix && !ctx->steps.empty() && !ctx->steps.back().is_fir && !ctx->steps.back().os_factor && !ctx->steps.back().fast &&
-            ctx->steps.back().n == (int)sd.size() && seg_descs.back().size() == sd.size() && G == 1) {
-            /* the step in front of this launch: the same channels in the same order, each with ONE unit, a compressor, feeding this shaper */
-            bool lone = true;
-            for (size_t i = 0; i < sd.size(); i++) {
-                const gdg_seg_chan &pc = seg_descs.back()[i];
-                if (pc.unit_count != 1 || seg_units[(size_t)pc.unit_begin].type != GDG_UNIT_COMPRESSOR || pc.dst != sd[i].src) lone = false;
-            }
-            if (lone) {
-                st.os_prefix_step = (int)ctx->steps.size() - 1;
-                ctx->steps.back().absorbed_per_frame = true;
-                /* a step that per-frame calls do not launch cannot carry other steps' extra workgroups (nothing has been given to it yet: it is the step right in front) */
-                if (ahead_host == st.os_prefix_step) { ahead_host = -1; ahead_host_weight = 0.0; }
-            }
-        }
-        /* descriptors are in `active` order, so every channel group owns one contiguous run of them */
-        st.group_range.assign((size_t)G, std::make_pair(0, 0));
-        {
-            int pos = 0;
-            for (auto &entry : kv.second) {
-                auto &r = st.group_range[(size_t)group_of[(size_t)entry.first]];
-                if (r.second == 0) r.first = pos;
-                r.second++;
-                pos++;
-            }
-        }
-        if (is_fir) {
+        if (st.os_factor) { st.os_flags = (int)wave_next; wave_next += sd.size(); st.os_arrive = (int)wave_next; wave_next += sd.size(); }    /* a flag and an arrival counter per channel of the launch (os_tiles_kernel) */
+        if (st.is_fir) {
             std::vector<const void *> hp;
             for (auto &f : fd) hp.push_back(f.H);
             std::sort(hp.begin(), hp.end());
             st.shared_spectra = std::adjacent_find(hp.begin(), hp.end()) != hp.end();
-            /* the terms k >= 1 ahead of the frame (premac): the split launch shape of few channels, one group, batch frames, every channel K >= 2 */
-            const bool split = ctx->fir_fused < 0 ? (st.n <= fir_split_limit(ctx)) : (ctx->fir_fused == 0);
-            long partitions = 0;
-            for (auto &f : fd) partitions += f.K;
-            const long premac_min = ctx->plan_fir_steps >= 2 ? std::min(ctx->fir_premac_min, ctx->fir_premac_min_two) : ctx->fir_premac_min;
-            st.premac_ok = ctx->fir_premac != 0 && split && G == 1 && frames == GDG_MAX_FRAMES && partitions >= premac_min;
-            for (auto &f : fd) if (f.K < 2 || f.hop != frames) st.premac_ok = false;
-            /* LDS the premac's workgroups ask for and never touch: such a workgroup does not fit on a CU beside a general or tile segment
-             * workgroup (159 KiB), and at most one fits beside a two-per-CU one (80 KiB), so the sums run on the CUs the segments leave idle
-             * and not among their waves.  Pays where the sums are neither a sliver nor the whole frame -- 5 .. 32 partitions per channel:
-             * 48 channels x 65536 taps 124.5 -> 119.9 us per frame, 128 channels 195.3 -> 185.2; 128 x 32768 taps 168 -> 172 and 64 x 1048576
-             * taps 305 -> 320 WITH it, hence the bounds (profiles/premac_loads_ab_r06.txt) */
-            const long per_channel = st.n > 0 ? partitions / st.n : 0;
-            st.premac_lds = ctx->fir_premac_lds >= 0 ? ctx->fir_premac_lds : ((per_channel >= 5 && per_channel <= 32) ? (st.n < 120 ? 16384 : 49152) : 0);
         }
-        if (!is_fir && !is_os && !step_fast && !sd.empty()) {
-            /* the host of later reverbs' wet paths: the earlier general-kernel launch that lives longest (the extra workgroups take ~15 us at
-             * 192 kHz; behind a short launch -- a lone compressor -- they would BE the launch).  Rough unit times in us, one workgroup per CU
-             * (profiles/seg_latency_by_channels_r04.txt) */
-            double w = 0.0;
-            for (int h : kv.second[0].second.handles) {
-                switch (ctx->units[(size_t)h].type) {
-                case GDG_UNIT_COMPRESSOR: w += 2.6; break;
-                case GDG_UNIT_TONESTACK: case GDG_UNIT_CABINET: w += 6.5; break;
-                case GDG_UNIT_CHORUS: w += 9.2; break;
-                case GDG_UNIT_REVERB: w += 18.0; break;
-                case GDG_UNIT_AUTOWAH: w += 14.0; break;
-                default: w += 4.0; break;
-                }
-            }
-            if (ahead_host < 0 || w > ahead_host_weight) { ahead_host = (int)ctx->steps.size(); ahead_host_weight = w; }
-        }
-        ahead_lists.emplace_back();
-        ctx->steps.push_back(st);
         seg_descs.push_back(sd);
         fir_descs.push_back(fd);
     }
-    {   /* the reverbs' wet paths as extra workgroups share the chip with the premac's launches: with both, fewer channels (ctx.h) */
-        bool any_premac = false;
-        for (auto &st : ctx->steps) any_premac = any_premac || (st.is_fir && st.premac_ok);
-        if (any_premac && (int)active.size() > ctx->seg_reverb_ahead_max) {
-            for (auto &l : ahead_lists) { for (int idx : l) seg_units[(size_t)idx].ip[7] = 0; l.clear(); }
-        }
-    }
-    {   /* two power amps' sums made ahead stream twice as long beside the segments: the tile kernel then only pays up to the channel count the
-         * reverbs' extra workgroups pay to (bench chain, tile kernel off / on: 80 channels 162.4 -> 157.8 us, 96: 173.4 -> 177.4; one amp, 96: 112.9 -> 104.2) */
-        int premac_steps = 0;
-        for (auto &st : ctx->steps) premac_steps += (st.is_fir && st.premac_ok) ? 1 : 0;
-        if (premac_steps >= 2 && (int)active.size() > ctx->seg_reverb_ahead_max) for (auto &st : ctx->steps) st.tile_ok = false;
-    }
-    /* a tiled step runs a reverb only as the mix of a wet path made by an earlier launch (seg.hip unit_reverb_mix_tile) */
-    for (auto &tc : tile_conditional)
-        if (tc.second < 0 || !seg_units[(size_t)tc.second].ip[7]) ctx->steps[(size_t)tc.first].tile_ok = false;
     {   /* the new filters' spectra, all together */
         const double tq = pnow();
         int rc = flush_ir(ctx);
         if (ptrace) fprintf(stderr, "[plan] prepare_fir %.1f ms, prepare_unit %.1f ms, flush_ir %.1f ms, so far %.1f ms\n", t_fir, t_unit, pnow() - tq, pnow() - t_plan0);
         if (rc != GDG_OK) return rc;
-    }
-    /* adjacent power amps (the benchmark chain: cabinet IR, then reverb IR): when EVERY channel of a FIR step hands its frame to the
-     * next FIR step, that step's forward transform is produced by this step's inverse kernel -- no launch, no round trip of the frame */
-    if (ctx->fir_chain && frames == GDG_MAX_FRAMES) {
-        for (size_t i = 0; i + 1 < ctx->steps.size(); i++) {
-            if (!ctx->steps[i].is_fir || !ctx->steps[i + 1].is_fir) continue;
-            auto &a = fir_descs[i], &b = fir_descs[i + 1];
-            bool ok = !a.empty() && a.size() == b.size() && ctx->steps[i].group_range == ctx->steps[i + 1].group_range;
-            for (size_t k = 0; ok && k < a.size(); k++) ok = a[k].dst == b[k].src && !(a[k].flags & GDG_DST_IS_OUTPUT) && a[k].hop == frames && b[k].hop == frames;
-            if (!ok) continue;
-            ctx->steps[i].chain_next = true;
-            for (auto &f : a) f.flags |= GDG_DST_UNUSED;      /* only the chained transform reads the frame (window-mode kernels ignore the flag) */
-        }
     }
     /* serialise */
     ctx->blob.clear();
@@ -975,8 +1050,8 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
     }
     ctx->units_offset = append(seg_units.data(), seg_units.size() * sizeof(gdg_seg_unit));
     for (size_t i = 0; i < ctx->steps.size(); i++) {
-        ctx->steps[i].ahead_n = (int)ahead_lists[i].size();
-        if (ctx->steps[i].ahead_n) ctx->steps[i].ahead_offset = append(ahead_lists[i].data(), ahead_lists[i].size() * sizeof(int));
+        ctx->steps[i].ahead_n = (int)dec.ahead[i].size();
+        if (ctx->steps[i].ahead_n) ctx->steps[i].ahead_offset = append(dec.ahead[i].data(), dec.ahead[i].size() * sizeof(int));
     }
     if (ctx->blob.size() > ctx->d_blob_cap) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -995,7 +1070,7 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
     if (ctx->d_wave) HIP_TRY(ctx, hipMemsetAsync(ctx->d_wave, 0, ctx->d_wave_cap * sizeof(int), ctx->stream));
     {   /* the tiles' exchange area: one block per descriptor of the largest tile launch; zero with every plan (tags of another layout) */
         size_t need = 0;
-        for (auto &st : ctx->steps) if (st.tile_ok) need = std::max(need, (size_t)st.n * gdg_segt_xch_words());
+        for (auto &st : ctx->steps) if (!st.is_fir && st.runs[0].frame == Shape::SEGT) need = std::max(need, (size_t)st.n * gdg_segt_xch_words());
         if (need > ctx->d_tile_xch_cap) {
             hipFree(ctx->d_tile_xch);
             ctx->d_tile_xch = nullptr;

@@ -29,7 +29,7 @@ static int apply_patches(gdg_ctx *ctx, int frames, uint32_t sample_rate) {
         int rc = prepare_unit(ctx, *u, frames, sample_rate, du, fast ? GDG_CHK_FAST : GDG_CHK);
         if (rc != GDG_OK) { ctx->dirty = true; return rc; }
         const size_t off = ctx->units_offset + (size_t)slot * sizeof(gdg_seg_unit);
-        if (du.type == GDG_UNIT_REVERB) du.ip[7] = reinterpret_cast<const gdg_seg_unit *>(ctx->blob.data() + off)->ip[7];      /* the plan's decision (build_plan: wet path made by an earlier launch) */
+        if (du.type == GDG_UNIT_REVERB) du.ip[7] = reinterpret_cast<const gdg_seg_unit *>(ctx->blob.data() + off)->ip[7];      /* the plan's decision (decide_shapes: wet path made by an earlier launch) */
         memcpy(ctx->blob.data() + off, &du, sizeof(du));
         lo = std::min(lo, off); hi = std::max(hi, off + sizeof(du));
     }
@@ -130,8 +130,6 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
     const bool free_run = G > 1 && !before && !after;
     if (!free_run) join_groups(ctx);      /* (a change of the group count rebuilds the plan, and build_plan joins every stream there is) */
     const int P2 = fir_transform_size(frames);
-    /* sums made ahead by the previous call (premac) are this call's if nothing has touched the context since and the plan still fits */
-    bool use_pre = ctx->premac_valid && window == 1 && G == 1;
     std::vector<size_t> bounds;
     if (group_bounds_in && (int)group_bounds_in->size() == G + 1) bounds = *group_bounds_in;
     else bounds = equal_group_bounds(active.size(), G);
@@ -142,12 +140,11 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
         int rc = apply_patches(ctx, frames, sample_rate);            /* knob moves: the affected descriptors only (may fall back to dirty) */
         if (rc != GDG_OK) return rc;
     }
-    if (!plan_fits) use_pre = false;
+    /* sums made ahead by the previous call (premac) are this call's if nothing has touched the context since and the plan still fits */
+    const bool use_pre = ctx->premac_valid && window == 1 && plan_fits;
     if (!use_pre) join_premac(ctx, false);       /* an unused premac still writes Y: this call's launches go behind it */
     ctx->premac_valid = false;                   /* consumed by this call or dropped; the call's end makes the next one */
-    if (ctx->dirty || ctx->plan_frames != frames || ctx->plan_sr != sample_rate ||
-        ctx->plan_active != active || ctx->plan_stride != stride || ctx->plan_stride_out != stride_out || ctx->plan_by_channel != rows_by_channel ||
-        ctx->plan_groups != G || ctx->plan_bounds != bounds) {
+    if (!plan_fits || ctx->dirty) {              /* (a patch may have fallen back to dirty) */
         int rc = build_plan(ctx, active, d_in, d_out, frames, sample_rate, stride, stride_out, rows_by_channel, G, bounds);
         ctx->plan_bounds = bounds;
         ctx->plan_stride = stride;
@@ -188,55 +185,59 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
         if (!ctx->gfork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->gfork, hipEventDisableTiming));
         HIP_TRY(ctx, hipEventRecord(ctx->gfork, ctx->stream));            /* the plan upload and earlier work on the main stream */
     }
-    /* premac: which step is the call's last power amp, and is there anything to sum ahead */
+    /* premac: which step is the call's last power amp, and is there anything to sum ahead (not around the host-buffer hooks or profiling) */
     bool premac_here = false;
     size_t premac_after = 0;
-    if (window == 1 && G == 1 && P2 == GDG_MAX_FRAMES && !ctx->profiling && !before && !after) {
+    if (window == 1 && !ctx->profiling && !before && !after) {
         for (size_t sj = 0; sj < ctx->steps.size(); sj++) {
             if (!ctx->steps[sj].is_fir || !ctx->steps[sj].n) continue;
             premac_after = sj;
-            premac_here = premac_here || ctx->steps[sj].premac_ok;
+            premac_here = premac_here || ctx->steps[sj].runs[0].frame == Shape::SPLIT_PREMAC;
         }
     }
+    /* GDG_PLAN_TRACE=2: the shape every step ran in, a line per launch (no addresses, no times: two runs diff) */
+    auto trace = [ctx](size_t si, int g, Shape shape, int n, int ahead, bool chained) {
+        if (ctx->plan_trace >= 2) fprintf(stderr, "[launch] step=%zu group=%d shape=%s n=%d ahead=%d chained=%d\n", si, g, shape_name(shape), n, ahead, chained ? 1 : 0);
+    };
+    auto next_epoch = [ctx]() { return ctx->wave_epoch = (ctx->wave_epoch % 0x3ffffff) + 1; };          /* epoch * 32 + frame fits an int */
     for (int g = 0; g < G; g++) {
         hipStream_t s = G > 1 ? ctx->gstreams[(size_t)g] : ctx->stream;
         if (G > 1) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->gfork, 0));
         if (before) HIP_TRY(ctx, (*before)(g, s));
         for (size_t si = 0; si < ctx->steps.size(); si++) {
             const StepDesc &st = ctx->steps[si];
-            int first = st.group_range[(size_t)g].first, n = st.group_range[(size_t)g].second;
+            const int first = st.runs[(size_t)g].first, n = st.runs[(size_t)g].n;
             if (n == 0) continue;
+            Shape shape = window > 1 ? st.window : st.runs[(size_t)g].frame;
             if (st.is_fir) {
                 const gdg_fir_chan *d = reinterpret_cast<const gdg_fir_chan *>(ctx->d_blob + st.offset) + first;
-                if (window > 1) {
+                const gdg_fir_chan *d_next = st.chain_next ? reinterpret_cast<const gdg_fir_chan *>(ctx->d_blob + ctx->steps[si + 1].offset) + first : nullptr;
+                const bool chained = si > 0 && ctx->steps[si - 1].chain_next;      /* the previous power amp's inverse made this one's spectrum */
+                if (shape == Shape::FIR_WINDOW) {
                     /* `window` frames per channel: every spectrum is read once for all of them (fir.hip, "Time blocking"); with adjacent
                      * power amps the inverse transforms of one make the forward transforms of the next (one launch, no frame round trip) */
                     const int sh = st.shared_spectra ? 1 : 0;
                     const bool chain_ok = gdg_fir_window_chain_ok(n, window) != 0;
-                    const bool chained_w = chain_ok && si > 0 && ctx->steps[si - 1].chain_next;
-                    const bool chains_w = chain_ok && st.chain_next;
-                    if (!chained_w) { ProfScope ps(ctx, GDG_K_FIR_FWD, s); HIP_TRY(ctx, gdg_launch_fir_window(window, d, n, sh, tw, tw2, 0, shift, s)); }
+                    trace(si, g, shape, n, 0, chain_ok && chained);
+                    if (!(chain_ok && chained)) { ProfScope ps(ctx, GDG_K_FIR_FWD, s); HIP_TRY(ctx, gdg_launch_fir_window(window, d, n, sh, tw, tw2, 0, shift, s)); }
                     { ProfScope ps(ctx, GDG_K_FIR_MAC, s); HIP_TRY(ctx, gdg_launch_fir_window(window, d, n, sh, tw, tw2, 1, shift, s)); }
                     {
                         ProfScope ps(ctx, GDG_K_FIR_INV, s);
-                        if (chains_w) {
-                            const gdg_fir_chan *d_next = reinterpret_cast<const gdg_fir_chan *>(ctx->d_blob + ctx->steps[si + 1].offset) + first;
-                            HIP_TRY(ctx, gdg_launch_fir_window_chain(window, d, d_next, n, tw, tw2, shift, s));
-                        } else HIP_TRY(ctx, gdg_launch_fir_window(window, d, n, sh, tw, tw2, 2, shift, s));
+                        if (chain_ok && d_next) HIP_TRY(ctx, gdg_launch_fir_window_chain(window, d, d_next, n, tw, tw2, shift, s));
+                        else HIP_TRY(ctx, gdg_launch_fir_window(window, d, n, sh, tw, tw2, 2, shift, s));
                         HIP_TRY(ctx, gdg_launch_fir_window(window, d, n, sh, tw, tw2, 3, shift, s));
                     }
                     continue;
                 }
-                const bool chained = si > 0 && ctx->steps[si - 1].chain_next;      /* the previous power amp's inverse made this one's spectrum */
+                if (shape == Shape::SPLIT_PREMAC && !use_pre) shape = Shape::SPLIT;      /* no sums of this frame were made ahead */
+                trace(si, g, shape, n, 0, chained);
                 if (!chained) { ProfScope ps(ctx, GDG_K_FIR_FWD, s); HIP_TRY(ctx, gdg_launch_fir_fwd(P2, frames, d, n, tw, tw2, shift, s)); }
-                const gdg_fir_chan *d_next = st.chain_next ? reinterpret_cast<const gdg_fir_chan *>(ctx->d_blob + ctx->steps[si + 1].offset) + first : nullptr;
-                const bool fused = ctx->fir_fused < 0 ? (n > fir_split_limit(ctx)) : (ctx->fir_fused != 0);
-                if (fused) {
+                if (shape == Shape::FUSED) {
                     /* multiply-accumulate fused into the inverse transform's first stage (reported as the MAC kernel; its chained
                      * variant, which also makes the next amp's forward transform, under a kind of its own) */
                     ProfScope ps(ctx, d_next ? GDG_K_FIR_MAC_CHAIN : GDG_K_FIR_MAC, s, ctx->prof_attach);
                     HIP_TRY(ctx, gdg_launch_fir_inv(P2, d, n, tw, tw2, st.shared_spectra ? 2 : 1, shift, s, d_next, ps.attached ? ps.a : nullptr, ps.attached ? ps.b : nullptr));
-                } else if (use_pre && st.premac_ok) {
+                } else if (shape == Shape::SPLIT_PREMAC) {
                     /* the terms k >= 1 are in Y already (the previous call's premac): the newest term + the inverse transform */
                     if (ctx->premac_outstanding) { HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_premac, 0)); ctx->premac_outstanding = false; }
                     ProfScope ps(ctx, GDG_K_FIR_INV, s);
@@ -251,47 +252,51 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
                     { int rc = ensure_side_stream(ctx); if (rc != GDG_OK) return rc; }
                     HIP_TRY(ctx, hipEventRecord(ctx->ev_fir_done, s));
                 }
-            } else if (st.absorbed_per_frame && window == 1 && G == 1) {
-                continue;                          /* the oversampled shaper's launch behind this step runs its compressor (os_tiles_kernel, pre_chans) */
-            } else if (st.os_factor) {
-                /* an oversampled shaper of few channels: a workgroup per (channel, frame, tile) instead of one per channel */
-                const gdg_seg_chan *d = reinterpret_cast<const gdg_seg_chan *>(ctx->d_blob + st.offset) + first;
-                ProfScope ps(ctx, GDG_K_SEGMENT, s);
-                const int epoch = (ctx->wave_epoch = (ctx->wave_epoch % 0x3ffffff) + 1);
-                /* a per-frame call: the lone compressor in front of the shaper runs inside this launch (the step itself was skipped above) */
-                const gdg_seg_chan *d_pre = (window == 1 && G == 1 && st.os_prefix_step >= 0)
+                continue;
+            }
+            const gdg_seg_chan *d = reinterpret_cast<const gdg_seg_chan *>(ctx->d_blob + st.offset) + first;
+            const int *d_ahead = st.ahead_n > 0 ? reinterpret_cast<const int *>(ctx->d_blob + st.ahead_offset) : nullptr;
+            const bool wave = shape == Shape::WAVE || shape == Shape::SEGF_WAVE;
+            trace(si, g, shape, n, shape == Shape::SEGT || shape == Shape::GENERAL_AHEAD ? st.ahead_n : 0, false);
+            if (shape == Shape::SKIP) continue;
+            ProfScope ps(ctx, GDG_K_SEGMENT, s);
+            switch (shape) {
+            case Shape::OS_TILES:
+            case Shape::OS_TILES_PREFIX: {
+                /* an oversampled shaper of few channels: a workgroup per (channel, frame, tile) instead of one per channel; with the prefix, the lone
+                 * compressor in front of the shaper runs inside this launch */
+                const gdg_seg_chan *d_pre = shape == Shape::OS_TILES_PREFIX
                                             ? reinterpret_cast<const gdg_seg_chan *>(ctx->d_blob + ctx->steps[(size_t)st.os_prefix_step].offset) + first : nullptr;
+                const int epoch = next_epoch();
                 HIP_TRY(ctx, gdg_launch_os_tiles(st.os_factor, d, n, d_units, frames, window, shift, ctx->os, ctx->d_wave + st.os_flags + first, epoch, ctx->d_error, s,
                                                  d_pre, ctx->d_wave + st.os_arrive + first));
-            } else {
-                const gdg_seg_chan *d = reinterpret_cast<const gdg_seg_chan *>(ctx->d_blob + st.offset) + first;
-                ProfScope ps(ctx, GDG_K_SEGMENT, s);
-                /* one launch per window: a channel's workgroup walks its frames in order, the units' state runs through them */
-                /* ... unless the channels are few: then a workgroup per frame, the frames of a channel meeting unit by unit (seg.hip, WAVE) */
-                /* (by the CALL's channel count, not the group's: two groups of 256 channels fill the chip like one launch of 512) */
-                const int wave_max = st.wave_release ? std::min(ctx->seg_wave_max, ctx->seg_wave_release_max) : ctx->seg_wave_max;
-                int *tickets = (window > 1 && (int)active.size() <= wave_max && st.wave_tickets >= 0) ? ctx->d_wave + st.wave_tickets + g : nullptr;
-                const int epoch = tickets ? (ctx->wave_epoch = (ctx->wave_epoch % 0x3ffffff) + 1) : 0;          /* epoch * 32 + frame fits an int */
-                /* option debug_stall_unit: in a WAVE launch frame 0 of that unit's channel withholds the unit's counter (seg.hip) */
+                break;
+            }
+            case Shape::SEGT:
+                /* a per-frame call of few channels: a channel's frame on two workgroups (the bits of the general kernel), the reverbs' wet paths
+                 * of later steps beside them as in GENERAL_AHEAD */
+                HIP_TRY(ctx, gdg_launch_segt(d, n, d_units, shift, ctx->os, ctx->d_error, s, ctx->d_wave + st.wave_tickets + g, next_epoch(),
+                                             ctx->d_tile_xch + (size_t)first * gdg_segt_xch_words(), d_ahead, d_ahead ? st.ahead_n : 0));
+                break;
+            case Shape::GENERAL:
+            case Shape::GENERAL_AHEAD:
+                /* one frame per launch: the launch also makes the wet paths of the reverbs of LATER segment steps (extra workgroups beside the
+                 * channels'; seg.hip REVERB_AHEAD), and reverbs whose wet path an earlier launch of this call made only mix */
+                HIP_TRY(ctx, gdg_launch_seg(d, n, d_units, frames, 1, shift, ctx->os, ctx->d_error, s, nullptr, 0, 1, d_ahead, d_ahead ? st.ahead_n : 0));
+                break;
+            default: {
+                /* SEGF per frame; in a window a channel's workgroup walks its frames in order (WALK), or every frame of a channel has a workgroup
+                 * of its own, the frames meeting unit by unit (WAVE).  Option debug_stall_unit: in a WAVE launch frame 0 of that unit's channel
+                 * withholds the unit's counter (seg.hip) */
+                int *tickets = wave ? ctx->d_wave + st.wave_tickets + g : nullptr;
+                const int epoch = wave ? next_epoch() : 0;
                 int stall = 0;
-                if (tickets && ctx->debug_stall_unit >= 0 && (size_t)ctx->debug_stall_unit < ctx->plan_unit_slot.size() &&
+                if (wave && ctx->debug_stall_unit >= 0 && (size_t)ctx->debug_stall_unit < ctx->plan_unit_slot.size() &&
                     ctx->plan_unit_slot[(size_t)ctx->debug_stall_unit] >= 0) stall = 1 + ctx->plan_unit_slot[(size_t)ctx->debug_stall_unit];
-                if (st.fast) HIP_TRY(ctx, gdg_launch_segf(d, n, d_units, frames, window, shift, ctx->os, ctx->d_error, s, tickets, epoch, stall));
-                else if (tickets) HIP_TRY(ctx, gdg_launch_seg(d, n, d_units, frames, window, shift, ctx->os, ctx->d_error, s, tickets, epoch, stall));
-                else if (st.tile_ok && window == 1 && G == 1 && st.wave_tickets >= 0 && ctx->d_tile_xch && 2 * n + st.ahead_n <= GDG_TILE_WORKGROUP_BUDGET) {
-                    /* a per-frame call of few channels: a channel's frame on two workgroups (seg.hip SEG_TILE; the bits of the general kernel),
-                     * the reverbs' wet paths of later steps beside them as in the general launch below */
-                    const int *d_ahead = st.ahead_n > 0 ? reinterpret_cast<const int *>(ctx->d_blob + st.ahead_offset) : nullptr;
-                    const int tile_epoch = (ctx->wave_epoch = (ctx->wave_epoch % 0x3ffffff) + 1);
-                    HIP_TRY(ctx, gdg_launch_segt(d, n, d_units, shift, ctx->os, ctx->d_error, s, ctx->d_wave + st.wave_tickets + g, tile_epoch, ctx->d_tile_xch + (size_t)first * gdg_segt_xch_words(),
-                                                 d_ahead, d_ahead ? st.ahead_n : 0));
-                } else {
-                    /* one frame per launch: the launch also makes the wet paths of the reverbs of LATER segment steps (extra workgroups beside
-                     * the channels'; seg.hip REVERB_AHEAD), and reverbs whose wet path an earlier launch of this call made only mix */
-                    const bool piggy = window == 1 && G == 1;
-                    const int *d_ahead = piggy && st.ahead_n > 0 ? reinterpret_cast<const int *>(ctx->d_blob + st.ahead_offset) : nullptr;
-                    HIP_TRY(ctx, gdg_launch_seg(d, n, d_units, frames, window, shift, ctx->os, ctx->d_error, s, tickets, epoch, piggy ? 1 : 0, d_ahead, d_ahead ? st.ahead_n : 0));
-                }
+                if (shape == Shape::SEGF || shape == Shape::SEGF_WAVE || shape == Shape::SEGF_WALK)
+                    HIP_TRY(ctx, gdg_launch_segf(d, n, d_units, frames, window, shift, ctx->os, ctx->d_error, s, tickets, epoch, stall));
+                else HIP_TRY(ctx, gdg_launch_seg(d, n, d_units, frames, window, shift, ctx->os, ctx->d_error, s, tickets, epoch, stall));
+            }
             }
         }
         if (after) HIP_TRY(ctx, (*after)(g, s));
@@ -299,10 +304,12 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
             /* every launch of the call is in the context's stream: now the side stream's share (the host must not keep the main stream
              * waiting for its next kernel while it enqueues these: 6 us per step) */
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->premac_stream, ctx->ev_fir_done, 0));
-            for (auto &sx : ctx->steps) {
-                if (!sx.is_fir || !sx.premac_ok || !sx.n) continue;
+            for (size_t sj = 0; sj < ctx->steps.size(); sj++) {
+                const StepDesc &sx = ctx->steps[sj];
+                if (!sx.is_fir || !sx.n || sx.runs[0].frame != Shape::SPLIT_PREMAC) continue;
                 const gdg_fir_chan *dx = reinterpret_cast<const gdg_fir_chan *>(ctx->d_blob + sx.offset);
-                /* ... on the CUs the segments leave idle (premac_lds: api_plan.cpp) */
+                if (ctx->plan_trace >= 2) fprintf(stderr, "[launch] step=%zu group=%d shape=PREMAC n=%d ahead=0 chained=0\n", sj, g, sx.n);
+                /* ... on the CUs the segments leave idle (premac_lds: decide_shapes) */
                 HIP_TRY(ctx, gdg_launch_fir_mac(P2, dx, sx.n, sx.shared_spectra ? 1 : 0, ctx->premac_stream, 1, sx.premac_lds));
             }
             HIP_TRY(ctx, hipEventRecord(ctx->ev_premac, ctx->premac_stream));

@@ -100,28 +100,46 @@ struct Slot { int handle; bool bypass; };
 #define GDG_WAVE_STEPS 64             /* segment steps of a plan that can run as WAVE launches (a chain with more power amps than that walks) */
 #define GDG_WAVE_GROUPS 16            /* = the most channel groups of a call (every group's launch of a step draws its own tickets) */
 
+/* How a step is launched.  decide_shapes (api_plan.cpp) picks one per call kind when the plan is built; process_rows dispatches by it. */
+enum class Shape : unsigned char {
+    SKIP,               /* not launched: the oversampled shaper's launch behind it runs its compressor (OS_TILES_PREFIX) */
+    GENERAL,            /* segment: the general kernel, one frame, a workgroup per channel */
+    GENERAL_AHEAD,      /* ... and extra workgroups that make the wet paths of later steps' reverbs (seg.hip REVERB_AHEAD) */
+    SEGF,               /* segment: the two-per-CU kernel (seg.hip SEG_FAST) */
+    SEGT,               /* segment: a channel's frame on two workgroups (seg.hip SEG_TILE) */
+    WAVE, SEGF_WAVE,    /* window: a workgroup per frame and channel, the frames meeting unit by unit (seg.hip WAVE) */
+    WALK, SEGF_WALK,    /* window: a workgroup per channel walks the frames */
+    OS_TILES,           /* one oversampled shaper per channel as a launch of its own (seg.hip os_tiles_kernel) */
+    OS_TILES_PREFIX,    /* ... whose workgroups also run the lone compressor of the step in front */
+    FUSED,              /* power amp: multiply-accumulate inside the inverse transform's kernel */
+    SPLIT,              /* power amp: the bin-tiled multiply-accumulate, then the inverse transform */
+    SPLIT_PREMAC,       /* ... whose terms k >= 1 the previous call sums ahead of the frame (premac) */
+    FIR_WINDOW,         /* power amp in a window (fir.hip, time blocking) */
+};
+static inline const char *shape_name(Shape s) {
+    static const char *const names[] = { "SKIP", "GENERAL", "GENERAL_AHEAD", "SEGF", "SEGT", "WAVE", "SEGF_WAVE", "WALK", "SEGF_WALK",
+                                         "OS_TILES", "OS_TILES_PREFIX", "FUSED", "SPLIT", "SPLIT_PREMAC", "FIR_WINDOW" };
+    return names[(int)s];
+}
+
 struct StepDesc {
     bool is_fir;
     int n;
     size_t offset;                    /* byte offset of its descriptor array inside the plan blob */
+    Shape window = Shape::SKIP;       /* how a window launches it; per-frame calls: runs[g].frame */
+    struct Run { int first = 0, n = 0; Shape frame = Shape::SKIP; };
+    std::vector<Run> runs;            /* per channel group: (first descriptor, count) and how a per-frame call launches them */
     bool shared_spectra = false;      /* FIR step: some channels read the same IR spectra */
     bool chain_next = false;          /* FIR step whose every channel feeds another power amp next (the following step): that amp's forward
-                                       * transform rides on this step's inverse (fir_inv_kernel CHAIN) in per-frame calls */
-    bool fast = false;                /* segment step: every unit of every channel works in place on 8192-sample frames -> the two-per-CU kernel (segf) */
-    int premac_lds = 0;               /* ... and the LDS its launch asks for without using it (api_plan.cpp) */
-    bool premac_ok = false;           /* FIR step: split shape (few channels), 8192-sample frames, every channel with K >= 2: the terms k >= 1 can be summed ahead */
+                                       * transform rides on this step's inverse (fir_inv_kernel CHAIN) */
+    int premac_lds = 0;               /* FIR step: the LDS its premac launch asks for without using it (decide_shapes) */
     int os_factor = 0;                /* 2 / 4: the step is ONE oversampled shaper per channel, run as a launch of its own (seg.hip os_tiles_kernel) */
     int os_flags = -1;                /* ... and its per-channel flags start here in d_wave */
     int os_arrive = -1;               /* ... its per-channel arrival counters (a compressor step absorbed into the launch, below) */
-    int os_prefix_step = -1;          /* ... the step right in front of it when that is a lone compressor in every one of its channels: in per-frame calls the tiles'
-                                       * workgroups run it themselves and the step is not launched (seg.hip os_tiles_kernel, pre_chans) */
-    bool absorbed_per_frame = false;  /* segment step: a per-frame call skips it -- the oversampled shaper's launch behind it runs its compressor */
-    int ahead_n = 0;                  /* segment step (general kernel, one frame per launch): it also makes the wet paths of this many reverbs of LATER steps ... */
+    int os_prefix_step = -1;          /* ... OS_TILES_PREFIX: the step right in front of it, a lone compressor in every one of its channels */
+    int ahead_n = 0;                  /* segment step (one frame per launch): it also makes the wet paths of this many reverbs of LATER steps ... */
     size_t ahead_offset = 0;          /* ... whose indices into the plan's unit array start here in the blob (seg.hip REVERB_AHEAD) */
-    bool tile_ok = false;             /* segment step: every unit of every channel can run with the frame on two workgroups (seg.hip SEG_TILE) */
-    bool wave_release = false;        /* segment step: some channel's segment hands its state on through a write-back of the XCD's L2 (wave_mask bit 31) */
     int wave_tickets = -1;            /* segment step: first of its GDG_WAVE_GROUPS ticket counters in d_wave (seg.hip, WAVE), -1: none */
-    std::vector<std::pair<int, int>> group_range;     /* per channel group: (first descriptor, count) */
 };
 
 struct ProfEvent { int kind; hipEvent_t a, b; };
@@ -161,10 +179,7 @@ struct gdg_ctx {
      * 52 of the 77 us per frame).  0: never.  gdg_ctx_set_option("seg_wave_max_channels"), env GDG_SEG_WAVE_MAX. */
     int seg_tile_max = 112;                    /* per-frame calls of up to this many channels: a segment of compressor / shapers / tone stack / cabinet / chorus (/ the mix of a
                                                 * reverb made ahead) runs with a channel's frame on TWO workgroups (seg.hip SEG_TILE; same bits) -- as long as the launch's
-                                                * workgroups, 2 x channels + the reverbs' extra ones, leave the chip room (GDG_TILE_WORKGROUP_BUDGET) */
-#define GDG_TILE_WORKGROUP_BUDGET 224          /* of 256 CUs, one workgroup each.  Per step, tile kernel off / on (profiles/tile_ab_r06.txt, shape_sweep_r06.txt): bench chain 64
-                                                * channels (192 workgroups) 142.9 -> 138.4 us, 72 (216) 148.8 -> 146.6, 80 (240) 155.9 -> 158.0; no reverb, 96 channels (192)
-                                                * 111.5 -> 103.6; 96 kHz chain with a reverb, 96 channels (288) 110.9 -> 118.7 */
+                                                * workgroups, 2 x channels + the reverbs' extra ones, leave the chip room (decide_shapes) */
     unsigned long long *d_tile_xch = nullptr;  /* what crosses between the two workgroups of a channel: gdg_segt_xch_words() words per descriptor of a launch */
     size_t d_tile_xch_cap = 0;
     bool seg_os_prefix = true;                 /* a lone compressor in front of an oversampled shaper's own launch runs inside that launch in per-frame calls (option seg_os_tiles_prefix) */
@@ -198,7 +213,7 @@ struct gdg_ctx {
      * on the critical path instead of 2 K.  Every multiply-accumulate kernel sums k DESCENDING, so the split sum has the bits of the whole one.
      * The premac is speculative: any library call but a process call drops it (the next call then runs the whole sum). */
     int fir_premac = 1;                        /* option "fir_premac": 0 never */
-    int fir_premac_lds = -1;                   /* option "fir_premac_lds_bytes": -1 by channel count (api_process.cpp) */
+    int fir_premac_lds = -1;                   /* option "fir_premac_lds_bytes": -1 by channel count (decide_shapes) */
     int fir_premac_min = 384;                  /* fewest partitions (sum of K over a launch's channels) worth it: the two cross-stream hops and the
                                                 * three extra spectra of the inverse kernel cost ~20 us per step -- the multiply-accumulate of 48 x 8
                                                 * partitions takes that long (16 x 8: 113.7 -> 123.4 us per step with it, 64 x 4 (config 3): 137 -> 141) */
@@ -220,6 +235,7 @@ struct gdg_ctx {
     size_t d_wave_cap = 0;
     std::vector<int> patch_units;              /* units whose parameters changed since the plan was built: their descriptors are patched in place */
     bool plan_patch = true;                    /* GDG_PLAN_PATCH=0: every parameter change rebuilds the whole plan (A/B measurements) */
+    int plan_trace = 0;                        /* GDG_PLAN_TRACE as the last plan read it: 1 a line per plan, 2 also a line per launch (process_rows) */
     std::vector<unsigned char> blob;
     unsigned char *d_blob = nullptr;
     size_t d_blob_cap = 0;
@@ -253,7 +269,6 @@ struct gdg_ctx {
                                        * (profiles/shape_sweep_r06.txt, chain d) */
     int fir_split_max_single = 112;   /* ... when the call has ONE power amp per channel: the premac has half as much to hide, and at 128 channels the fused kernel wins
                                        * (one amp: 138.8 split vs 127.1 fused us per step, 96 channels 112 vs 125; profiles/shape_sweep_r06.txt) */
-    int plan_fir_steps = 0;           /* power-amp steps of the current plan */
     bool fir_chain = true;            /* GDG_FIR_CHAIN=0: adjacent power amps keep separate launches (A/B measurements, bit-identity tests) */
     double *d_os = nullptr;
     gdg_os_tables os;
@@ -358,9 +373,9 @@ static inline void enter(gdg_ctx *ctx, bool read_only = false) {
     join_premac(ctx, read_only);
 }
 
-/* largest launch (channels) that takes the split convolution shape: by the number of power amps per channel in the plan */
-static inline int fir_split_limit(const gdg_ctx *ctx) {
-    return ctx->plan_fir_steps >= 2 ? ctx->fir_split_max : std::min(ctx->fir_split_max, ctx->fir_split_max_single);
+/* the parameter index of an overdrive's / distortion's / excess's oversampling (0 none, 1 "2", 2 "4"); -1: the unit type has none */
+static inline int shaper_os_param(int type) {
+    return type == GDG_UNIT_OVERDRIVE ? 5 : type == GDG_UNIT_DISTORTION ? 3 : type == GDG_UNIT_EXCESS ? 2 : -1;
 }
 
 #define HIP_TRY(ctx, call)                                                                          \

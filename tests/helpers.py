@@ -36,6 +36,20 @@ def rms(a):
     return float(np.sqrt(np.mean(np.square(a)))) if a.size else 0.0
 
 
+def launches(err):
+    """The [launch] lines GDG_PLAN_TRACE=2 prints (process_rows: one per step launch and channel group, one per premac launch), as dicts."""
+    out = []
+    for line in err.splitlines():
+        if line.startswith("[launch] "):
+            f = dict(kv.split("=", 1) for kv in line.split()[1:])
+            out.append({k: (v if k == "shape" else int(v)) for k, v in f.items()})
+    return out
+
+
+def shapes(err):
+    return {r["shape"] for r in launches(err)}
+
+
 class ChainPair:
     """The same chain on the HIP context (channel c) and on the oracle."""
 

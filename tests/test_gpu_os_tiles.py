@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as entry
-from helpers import synth_ir, synth_signal, rms, TOL_RMS
+from helpers import shapes, synth_ir, synth_signal, rms, TOL_RMS
 
 pytestmark = pytest.mark.gpu
 
@@ -44,11 +44,12 @@ def build(pkg, nch, frames, chain, tiles):
 
 
 @pytest.mark.parametrize("name", sorted(CHAINS))
-def test_tiles_give_the_bits_of_the_in_segment_unit_and_follow_the_oracle(pkg, oracle, name):
+def test_tiles_give_the_bits_of_the_in_segment_unit_and_follow_the_oracle(pkg, oracle, name, monkeypatch, capfd):
     nch, frames, sr, blocks = 3, 8192, 96000, 6
     chain = CHAINS[name]
     x = np.stack([synth_signal(c + 1, frames * blocks, sr) * (1.0 if c else 0.3) for c in range(nch)])
-    outs = {}
+    monkeypatch.setenv("GDG_PLAN_TRACE", "2")
+    outs, ran = {}, {}
     for tiles in (False, True):
         ctx = build(pkg, nch, frames, chain, tiles)
         got = np.zeros_like(x)
@@ -59,7 +60,9 @@ def test_tiles_give_the_bits_of_the_in_segment_unit_and_follow_the_oracle(pkg, o
             got[:, b * frames:(b + 1) * frames] = d_out.download()
         outs[tiles] = got
         ctx.close()
+        ran[tiles] = shapes(capfd.readouterr().err) & {"OS_TILES", "OS_TILES_PREFIX"}
     np.testing.assert_array_equal(outs[True], outs[False])
+    assert ran[True] and not ran[False], ran
     for c in range(nch):
         ref = oracle.Chain()
         for uname, p in chain:
@@ -145,7 +148,7 @@ def test_switching_oversampling_off_and_on_in_window_mode_relays_the_counters(pk
 
 @pytest.mark.parametrize("factor_index", [1, 2])
 @pytest.mark.parametrize("follow", [0, 1])
-def test_a_lone_compressor_in_front_runs_inside_the_tiles_launch(pkg, oracle, follow, factor_index):
+def test_a_lone_compressor_in_front_runs_inside_the_tiles_launch(pkg, oracle, follow, factor_index, monkeypatch, capfd):
     """compressor > oversampled overdrive (BASELINE config 3's head): a per-frame call does not launch the compressor's step, every tile's workgroup
     runs the unit itself (option seg_os_tiles_prefix) -- the compressor's own code on the same frame: the same bits, with its state handed on
     from frame to frame, through windows in between and a reverb behind a power amp that wants an earlier launch to carry its wet path"""
@@ -153,7 +156,8 @@ def test_a_lone_compressor_in_front_runs_inside_the_tiles_launch(pkg, oracle, fo
     chain = [("compressor", [follow, 30, -20]), ("overdrive", [0, 20, 100, 0, 1, factor_index]), ("tone_stack", None), ("chorus", None),
              ("power_amp", "ir"), ("cabinet", None), ("reverb", [50])]
     x = np.stack([synth_signal(c + 1, frames * blocks, sr) * (1.0 if c else 0.3) for c in range(nch)])
-    outs = {}
+    monkeypatch.setenv("GDG_PLAN_TRACE", "2")
+    outs, ran = {}, {}
     for prefix in (0, 1):
         ctx = build(pkg, nch, frames, chain, True)
         ctx.set_option("seg_os_tiles_prefix", prefix)
@@ -177,9 +181,11 @@ def test_a_lone_compressor_in_front_runs_inside_the_tiles_launch(pkg, oracle, fo
         ctx.synchronize()
         outs[prefix] = got
         ctx.close()
+        ran[prefix] = shapes(capfd.readouterr().err)
     bad = [b for b in range(blocks) if not np.array_equal(outs[1][:, b * frames:(b + 1) * frames], outs[0][:, b * frames:(b + 1) * frames])]
     assert bad == [], "frames that differ: %s" % bad
     np.testing.assert_array_equal(outs[1], outs[0])
+    assert {"SKIP", "OS_TILES_PREFIX", "OS_TILES"} <= ran[1] and not {"SKIP", "OS_TILES_PREFIX"} & ran[0], ran
     ref = oracle.Chain()
     for uname, p in chain:
         if p == "ir":

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as entry
-from helpers import synth_ir, synth_signal, rms, TOL_RMS
+from helpers import launches, synth_ir, synth_signal, rms, TOL_RMS
 
 pytestmark = pytest.mark.gpu
 
@@ -66,16 +66,20 @@ def stream(ctx, x, sr, blocks, events=None):
 
 @pytest.mark.parametrize("sr", [44100, 48000, 96000, 192000])
 @pytest.mark.parametrize("name", sorted(CHAINS))
-def test_ahead_gives_the_bits_of_the_unit_in_one_piece_and_follows_the_oracle(pkg, oracle, name, sr):
+def test_ahead_gives_the_bits_of_the_unit_in_one_piece_and_follows_the_oracle(pkg, oracle, name, sr, monkeypatch, capfd):
     nch, blocks = 3, 7
     chain = CHAINS[name]
     x = np.stack([synth_signal(c + 2, FRAMES * blocks, sr) * (1.0 if c else 0.2) for c in range(nch)])
-    outs = {}
+    monkeypatch.setenv("GDG_PLAN_TRACE", "2")
+    outs, made = {}, {}
     for ahead in (False, True):
         ctx = build(pkg, nch, chain, ahead)
         outs[ahead] = stream(ctx, x, sr, blocks)
         ctx.close()
+        made[ahead] = sum(r["ahead"] for r in launches(capfd.readouterr().err))
     np.testing.assert_array_equal(outs[True], outs[False])
+    # chains with a segment launch in front of the reverb's step make its wet path there; the others have no launch to host it
+    assert made[False] == 0 and (made[True] > 0) == (name in ("bench", "two_hosted", "config3_shape")), made
     for c in range(nch):
         ref = oracle.Chain()
         for uname, p in chain:

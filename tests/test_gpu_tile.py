@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as entry
-from helpers import synth_ir, synth_signal, rms, TOL_RMS
+from helpers import launches, shapes, synth_ir, synth_signal, rms, TOL_RMS
 
 pytestmark = pytest.mark.gpu
 FRAMES = 8192
@@ -63,17 +63,20 @@ def stream(ctx, x, sr, blocks, events=None):
 
 @pytest.mark.parametrize("sr", [44100, 96000, 192000])
 @pytest.mark.parametrize("name", sorted(CHAINS))
-def test_two_workgroups_give_the_bits_of_one(pkg, oracle, name, sr):
+def test_two_workgroups_give_the_bits_of_one(pkg, oracle, name, sr, monkeypatch, capfd):
     nch, blocks = 5, 6
     chain = CHAINS[name]
     x = np.stack([synth_signal(c + 1, FRAMES * blocks, sr) * (0.05 if c == 1 else 1.0) for c in range(nch)])
     x[2, FRAMES:2 * FRAMES] = 0.0                                   # a silent frame in mid-stream
-    outs = {}
+    monkeypatch.setenv("GDG_PLAN_TRACE", "2")
+    outs, ran = {}, {}
     for tile in (False, True):
         ctx = build(pkg, nch, chain, tile)
         outs[tile] = stream(ctx, x, sr, blocks)
         ctx.close()
+        ran[tile] = shapes(capfd.readouterr().err)
     np.testing.assert_array_equal(outs[True], outs[False])
+    assert "SEGT" in ran[True] and "SEGT" not in ran[False], ran
     for c in (0, nch - 1):
         ref = oracle.Chain()
         for uname, p in chain:
@@ -116,10 +119,11 @@ def test_knob_moves_resets_windows_and_other_frame_sizes_between_tiled_frames(pk
     assert np.isfinite(outs[True]).all() and np.abs(outs[True]).max() > 0.01
 
 
-def test_a_channel_with_another_unit_keeps_the_whole_step_on_the_general_kernel(pkg):
+def test_a_channel_with_another_unit_keeps_the_whole_step_on_the_general_kernel(pkg, monkeypatch, capfd):
     """one launch per step: a flanger in ONE channel's segment and the step is not tiled -- results as ever"""
     nch, sr = 3, 96000
     x = np.stack([synth_signal(c + 4, FRAMES * 4, sr) for c in range(nch)])
+    monkeypatch.setenv("GDG_PLAN_TRACE", "2")
     outs = {}
     for tile in (False, True):
         ctx = pkg.Context(nch, FRAMES)
@@ -130,17 +134,21 @@ def test_a_channel_with_another_unit_keeps_the_whole_step_on_the_general_kernel(
             ctx.append_unit(c, "chorus")
         outs[tile] = stream(ctx, x, sr, 4)
         ctx.close()
+        assert shapes(capfd.readouterr().err) == {"GENERAL"}
     np.testing.assert_array_equal(outs[True], outs[False])
 
 
-def test_many_channels_and_a_long_stream(pkg):
+def test_many_channels_and_a_long_stream(pkg, monkeypatch, capfd):
     """64 channels (128 tile workgroups + 64 reverb workgroups in one launch), 12 frames: every channel, every sample"""
     nch, sr, blocks = 64, 192000, 12
     chain = CHAINS["bench"]
     x = np.stack([synth_signal(c, FRAMES * blocks, sr) for c in range(nch)])
-    outs = {}
+    monkeypatch.setenv("GDG_PLAN_TRACE", "2")
+    outs, ran = {}, {}
     for tile in (False, True):
         ctx = build(pkg, nch, chain, tile)
         outs[tile] = stream(ctx, x, sr, blocks)
         ctx.close()
+        ran[tile] = launches(capfd.readouterr().err)
     np.testing.assert_array_equal(outs[True], outs[False])
+    assert {(r["step"], r["shape"], r["ahead"]) for r in ran[True] if r["step"] in (0, 3)} == {(0, "SEGT", 64), (3, "SEGT", 0)}
