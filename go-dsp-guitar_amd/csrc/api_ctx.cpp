@@ -154,6 +154,9 @@ static const OptionDef g_options[] = {
     { "fir_premac_min_partitions", "GDG_FIR_PREMAC_MIN", 1, 1 << 24, -1, &gdg_ctx::fir_premac_min, nullptr, true },
     { "fir_premac_min_partitions_two_amps", "GDG_FIR_PREMAC_MIN_TWO", 1, 1 << 24, -1, &gdg_ctx::fir_premac_min_two, nullptr, true },
     { "stat_premac_launches_used", "GDG_STAT_PREMAC_USED", 0, 0x7fffffff, -1, &gdg_ctx::stat_premac_used, nullptr, false },
+    { "fir_ahead_frames", "GDG_FIR_AHEAD", 0, 4, -1, &gdg_ctx::fir_ahead_frames, nullptr, true },                 /* 1 acts as 0 */
+    { "fir_ahead_min_channels", "GDG_FIR_AHEAD_MIN", 1, 1 << 20, -1, &gdg_ctx::fir_ahead_min, nullptr, true },
+    { "stat_fir_ahead_sums_used", "GDG_STAT_FIR_AHEAD_USED", 0, 0x7fffffff, -1, &gdg_ctx::stat_fir_ahead_used, nullptr, false },
     { "fir_premac_lds_bytes", "GDG_FIR_PREMAC_LDS", -1, 65536, -1, &gdg_ctx::fir_premac_lds, nullptr, true },
     { "share_ir_spectra", "GDG_SHARE_IR_SPECTRA", 0, 1, -1, nullptr, &gdg_ctx::share_spectra, false },
     { "fft_half_lds_mask", "GDG_FFT_HALF_LDS", 0, 63, GDG_KNOB_FFT_HALF_LDS, nullptr, nullptr, false },
@@ -271,7 +274,7 @@ int gdg_ctx_create(int n_channels, int max_frames, int device, gdg_ctx **out) {
 static void free_unit(gdg_ctx *ctx, Unit &u) {
     DevArena &a = ctx->arena;
     a.release(u.d_ds); a.release(u.d_is); a.release(u.d_hist);
-    a.release(u.d_prev); a.release(u.d_fdl); a.release(u.d_Y); a.release(u.d_pos);
+    a.release(u.d_prev); a.release(u.d_fdl); a.release(u.d_Y); a.release(u.d_pos); a.release(u.d_acc);
     u = Unit();                     /* drops the unit's reference to its (possibly shared) IR spectra */
 }
 
@@ -344,6 +347,11 @@ int gdg_ctx_set_option(gdg_ctx *ctx, const char *key, long long value) {
     if (strcmp(key, "numa") == 0 && value != ctx->numa_mode) { int rc = numa_rebind(ctx, (int)value); if (rc != GDG_OK) return rc; }
     option_store(ctx, *o, value);
     if (o->replans) ctx->dirty = true;
+    if (o->field == &gdg_ctx::stat_fir_ahead_used && ctx->d_fir_ahead_used) {      /* the count lives on the device */
+        const unsigned long long v = (unsigned long long)value;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_fir_ahead_used, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     if (strcmp(key, "wave_spin_limit_ms") == 0)       /* the kernels read it from the context's error block (seg.hip wave_spin_expired) */
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_error + 1, &ctx->wave_spin_ms, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     return GDG_OK;
@@ -353,6 +361,14 @@ int gdg_ctx_get_option(gdg_ctx *ctx, const char *key, long long *value) {
     if (!ctx || !value) return GDG_ERR_INVALID;
     const OptionDef *o = find_option(key);
     if (!o) return fail(ctx, GDG_ERR_INVALID, "unknown option \"%s\"", key ? key : "(null)");
+    if (o->field == &gdg_ctx::stat_fir_ahead_used && ctx->d_fir_ahead_used) {
+        /* counted by the inverse kernels themselves: wait for every launch so far, then read */
+        enter(ctx, true);
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        unsigned long long v = 0;
+        HIP_TRY(ctx, hipMemcpy(&v, ctx->d_fir_ahead_used, sizeof(v), hipMemcpyDeviceToHost));
+        ctx->stat_fir_ahead_used = v > 0x7fffffffull ? 0x7fffffff : (int)v;
+    }
     if (o->knob >= 0) *value = gdg_knob_get(o->knob);
     else if (o->field) *value = ctx->*(o->field);
     else *value = (ctx->*(o->flag)) ? 1 : 0;
@@ -495,7 +511,7 @@ int gdg_debug_oversample_decimate(gdg_ctx *ctx, int factor, const double *in, in
     if (!ctx || !in || !state || !decimated) return GDG_ERR_INVALID;
     if (factor != 2 && factor != 4) return fail(ctx, GDG_ERR_INVALID, "oversampling factor %d: 2 or 4", factor);
     if (n <= 0 || n > GDG_MAX_FRAMES) return fail(ctx, GDG_ERR_INVALID, "%d samples: 1 to %d", n, GDG_MAX_FRAMES);
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     const size_t n_state = 8 + (size_t)GDG_OS_TAPS(factor) - 1, n_up = (size_t)factor * (size_t)n;
     double *d = nullptr;                                      /* [in | state | up | down] */
     HIP_TRY(ctx, hipMalloc((void **)&d, ((size_t)n + n_state + n_up + (size_t)n) * sizeof(double)));
@@ -567,7 +583,7 @@ int gdg_profile_read(gdg_ctx *ctx, int kind, double *total_ms, int *launches) {
 
 int gdg_device_alloc(gdg_ctx *ctx, size_t bytes, void **d_ptr) {
     if (!ctx || !d_ptr) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipMalloc(d_ptr, bytes));
     ctx->user_allocs.push_back(*d_ptr);
     return GDG_OK;
@@ -575,7 +591,7 @@ int gdg_device_alloc(gdg_ctx *ctx, size_t bytes, void **d_ptr) {
 
 int gdg_device_free(gdg_ctx *ctx, void *d_ptr) {
     if (!ctx) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     auto it = std::find(ctx->user_allocs.begin(), ctx->user_allocs.end(), d_ptr);
     if (it != ctx->user_allocs.end()) ctx->user_allocs.erase(it);
@@ -585,7 +601,7 @@ int gdg_device_free(gdg_ctx *ctx, void *d_ptr) {
 
 int gdg_copy_to_device(gdg_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
     if (!ctx) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GDG_OK;
@@ -593,7 +609,7 @@ int gdg_copy_to_device(gdg_ctx *ctx, void *d_dst, const void *h_src, size_t byte
 
 int gdg_copy_to_host(gdg_ctx *ctx, void *h_dst, const void *d_src, size_t bytes) {
     if (!ctx) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GDG_OK;
@@ -614,7 +630,7 @@ int gdg_fft_real(gdg_ctx *ctx, const double *samples, int n, double *spectrum) {
     if (n == 1) { spectrum[0] = samples[0]; spectrum[1] = 0.0; return GDG_OK; }          /* fft.go:765-768: one element is its own transform */
     int rc = fft_size_ok(ctx, n);
     if (rc != GDG_OK) return rc;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     const int P = n / 2;
     double2 *tw, *tw2;
     rc = fir_tables(ctx, P, &tw, &tw2);
@@ -651,7 +667,7 @@ int gdg_fft_real_inverse(gdg_ctx *ctx, const double *spectrum, int n, double *sa
     if (n == 1) { samples[0] = spectrum[0]; return GDG_OK; }
     int rc = fft_size_ok(ctx, n);
     if (rc != GDG_OK) return rc;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     const int P = n / 2;
     double2 *tw, *tw2;
     rc = fir_tables(ctx, P, &tw, &tw2);
@@ -688,7 +704,7 @@ int gdg_copy_rows_device(gdg_ctx *ctx, double *d_dst, size_t dst_stride, const d
     if (!ctx || !d_dst || !d_src) return GDG_ERR_INVALID;
     if (row_len > dst_stride || row_len > src_stride) return fail(ctx, GDG_ERR_INVALID, "row length %zu exceeds a row stride", row_len);
     if (row_len == 0 || n_rows == 0) return GDG_OK;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipMemcpy2DAsync(d_dst, dst_stride * sizeof(double), d_src, src_stride * sizeof(double), row_len * sizeof(double), n_rows,
                                   hipMemcpyDeviceToDevice, ctx->stream));
     return GDG_OK;

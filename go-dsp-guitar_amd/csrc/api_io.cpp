@@ -25,7 +25,7 @@ int gdg_wave_decode_device(gdg_ctx *ctx, int format, const void *d_bytes, size_t
     if (channels == 0) return fail(ctx, GDG_ERR_INVALID, "channel count must be positive");
     if (per == 0) return GDG_OK;
     if (!d_bytes || !d_samples) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     ProfScope ps(ctx, GDG_K_WAVE);
     HIP_TRY(ctx, gdg_launch_wave_decode(format, d_bytes, per, channels, d_samples, ctx->stream));
     return GDG_OK;
@@ -37,7 +37,7 @@ int gdg_wave_encode_device(gdg_ctx *ctx, int format, const double *d_samples, si
     if (channels == 0) return fail(ctx, GDG_ERR_INVALID, "channel count must be positive");
     if (per == 0) return GDG_OK;
     if (!d_bytes || !d_samples) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     ProfScope ps(ctx, GDG_K_WAVE);
     HIP_TRY(ctx, gdg_launch_wave_encode(format, d_samples, per, channels, d_bytes, ctx->stream));
     return GDG_OK;
@@ -51,7 +51,7 @@ int gdg_wave_decode(gdg_ctx *ctx, int format, const void *bytes, size_t per, uns
     size_t n = per * channels;
     if (n == 0) return GDG_OK;
     if (!bytes || !samples) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_io(ctx, 0, n * w);
     if (rc == GDG_OK) rc = ensure_io(ctx, 1, n * sizeof(double));
     if (rc != GDG_OK) return rc;
@@ -71,7 +71,7 @@ int gdg_wave_encode(gdg_ctx *ctx, int format, const double *samples, size_t per,
     size_t n = per * channels;
     if (n == 0) return GDG_OK;
     if (!bytes || !samples) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_io(ctx, 0, n * w);
     if (rc == GDG_OK) rc = ensure_io(ctx, 1, n * sizeof(double));
     if (rc != GDG_OK) return rc;
@@ -102,7 +102,7 @@ int gdg_resample_time_device(gdg_ctx *ctx, const double *d_samples, int n, uint3
                     gdg_resample_time_length(n, source_rate, target_rate));
     if (n_out == 0) return GDG_OK;
     if (!d_samples || !d_out) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     double dx = (double)source_rate / (double)target_rate;       /* resample.go:88-90 */
     ProfScope ps(ctx, GDG_K_RESAMPLE);
     HIP_TRY(ctx, gdg_launch_resample_time(d_samples, n, dx, d_out, n_out, ctx->stream));
@@ -113,7 +113,7 @@ int gdg_resample_time(gdg_ctx *ctx, const double *samples, int n, uint32_t sourc
     if (!ctx) return GDG_ERR_INVALID;
     if (n_out == 0 && n >= 0 && source_rate && target_rate && gdg_resample_time_length(n, source_rate, target_rate) == 0) return GDG_OK;
     if (!samples || !out || n <= 0 || n_out < 0) return fail(ctx, GDG_ERR_INVALID, "invalid buffers");
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_io(ctx, 0, (size_t)n * sizeof(double));
     if (rc == GDG_OK) rc = ensure_io(ctx, 1, (size_t)(n_out > 0 ? n_out : 1) * sizeof(double));
     if (rc != GDG_OK) return rc;
@@ -132,7 +132,7 @@ int gdg_resample_time(gdg_ctx *ctx, const double *samples, int n, uint32_t sourc
 
 int gdg_meter_configure(gdg_ctx *ctx, int n_ports) {
     if (!ctx || n_ports < 0) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->d_meter) { hipFree(ctx->d_meter); ctx->d_meter = nullptr; }
     ctx->n_meter = 0;
@@ -147,7 +147,7 @@ int gdg_meter_set_enabled(gdg_ctx *ctx, int port, int enabled) {
     if (!ctx) return GDG_ERR_INVALID;
     if (port >= ctx->n_meter) return fail(ctx, GDG_ERR_INVALID, "meter port %d out of range (%d configured)", port, ctx->n_meter);
     if (ctx->n_meter == 0) return GDG_OK;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     std::vector<gdg_meter_rec> st(ctx->n_meter);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(st.data(), ctx->d_meter, st.size() * sizeof(gdg_meter_rec), hipMemcpyDeviceToHost));
@@ -180,7 +180,7 @@ int gdg_meter_process_device(gdg_ctx *ctx, const double *d_rows, size_t row_stri
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->n_meter == 0 || frames == 0) return GDG_OK;
     if (!d_rows || frames < 0 || sample_rate == 0) return fail(ctx, GDG_ERR_INVALID, "invalid meter input");
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     return meter_rows(ctx, d_rows, row_stride, 0, ctx->n_meter, frames, sample_rate);
 }
 
@@ -188,7 +188,7 @@ int gdg_meter_process(gdg_ctx *ctx, const double *const *buffers, int frames, ui
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->n_meter == 0 || frames == 0) return GDG_OK;
     if (!buffers || frames < 0) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_io(ctx, 1, (size_t)ctx->n_meter * frames * sizeof(double));
     if (rc != GDG_OK) return rc;
     double *d = static_cast<double *>(ctx->d_io[1]);
@@ -211,7 +211,7 @@ static int32_t to_decibels_int(double value) {                         /* level.
 int gdg_meter_analyze(gdg_ctx *ctx, int32_t *levels, int32_t *peaks) {
     if (!ctx || !levels || !peaks) return GDG_ERR_INVALID;
     if (ctx->n_meter == 0) return GDG_OK;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     std::vector<gdg_meter_rec> st(ctx->n_meter);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(st.data(), ctx->d_meter, st.size() * sizeof(gdg_meter_rec), hipMemcpyDeviceToHost));
@@ -221,7 +221,7 @@ int gdg_meter_analyze(gdg_ctx *ctx, int32_t *levels, int32_t *peaks) {
 
 int gdg_meter_state(gdg_ctx *ctx, int port, double *current, double *peak, uint64_t *counter) {
     if (!ctx || port < 0 || port >= ctx->n_meter) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     gdg_meter_rec st;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(&st, ctx->d_meter + port, sizeof(st), hipMemcpyDeviceToHost));
@@ -317,7 +317,7 @@ int gdg_unit_get_fir(gdg_ctx *ctx, int handle, double *taps, int capacity, int *
 
 static int set_sound(gdg_ctx *ctx, double **d_buf, uint32_t *n_buf, const double *coeffs, int n) {
     if (n < 0) return fail(ctx, GDG_ERR_INVALID, "bad sound length");
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (*d_buf) { hipFree(*d_buf); *d_buf = nullptr; }
     *n_buf = 0;
@@ -351,7 +351,7 @@ int gdg_metronome_configure(gdg_ctx *ctx, uint32_t beats_per_period, uint32_t bp
 int gdg_metronome_process_device(gdg_ctx *ctx, double *d_out, int frames) {
     if (!ctx || (frames > 0 && !d_out) || frames < 0) return GDG_ERR_INVALID;
     if (frames == 0) return GDG_OK;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     const uint32_t sc0 = ctx->met_sample_counter, tc0 = ctx->met_tick_counter;
     const uint32_t spb = (60u * ctx->met_sr) / ctx->met_bpm;                    /* metronome.go:79, uint32 arithmetic */
     const uint32_t beats = ctx->met_beats == 0 ? 1u : ctx->met_beats;           /* :84-86 */
@@ -373,7 +373,7 @@ int gdg_metronome_process_device(gdg_ctx *ctx, double *d_out, int frames) {
 int gdg_metronome_process(gdg_ctx *ctx, double *out, int frames) {
     if (!ctx || (frames > 0 && !out) || frames < 0) return GDG_ERR_INVALID;
     if (frames == 0) return GDG_OK;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_io(ctx, 1, (size_t)frames * sizeof(double));
     if (rc != GDG_OK) return rc;
     rc = gdg_metronome_process_device(ctx, static_cast<double *>(ctx->d_io[1]), frames);

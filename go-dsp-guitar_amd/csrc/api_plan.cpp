@@ -594,7 +594,7 @@ static int prepare_fir(gdg_ctx *ctx, Unit &u, int hop, uint32_t sample_rate) {
         HIP_TRY(ctx, arena.alloc_zeroed((void **)&u.d_prev, 2 * (size_t)P * sizeof(double), ctx->stream));
         HIP_TRY(ctx, arena.alloc_zeroed((void **)&u.d_fdl, spec, ctx->stream));
         HIP_TRY(ctx, arena.alloc((void **)&u.d_Y, (size_t)W * (size_t)P * sizeof(double2)));
-        HIP_TRY(ctx, arena.alloc_zeroed((void **)&u.d_pos, sizeof(int), ctx->stream));
+        HIP_TRY(ctx, arena.alloc_zeroed((void **)&u.d_pos, 4 * sizeof(int), ctx->stream));      /* frame counter, stamp (none) */
         int r = fir_spectra(ctx, u, hop, P, K);
         if (r != GDG_OK) return r;
         if (carry) {
@@ -695,6 +695,10 @@ static void decide_shapes(gdg_ctx *ctx, const std::vector<PlanStep> &plan, int n
     auto fused = [&](int n) { return ctx->fir_fused < 0 ? n > split_max : ctx->fir_fused != 0; };
     const long premac_min = fir_steps >= 2 ? std::min(ctx->fir_premac_min, ctx->fir_premac_min_two) : ctx->fir_premac_min;
     int premac_steps = 0;
+    /* sums made ahead of the next T frames (FUSED_AHEAD): the fused shape, batch frames, every channel K >= 2, at least fir_ahead_min channels
+     * in the group's launch; one pass per call and group serves up to GDG_AHEAD_MAX_STEPS power amps */
+    const int ahead_T = ctx->fir_ahead_frames >= 2 ? ctx->fir_ahead_frames : 0;
+    int ahead_steps = 0;
     for (size_t i = 0; i < S; i++) {
         StepDesc &st = steps[i];
         if (!st.is_fir) continue;
@@ -707,7 +711,21 @@ static void decide_shapes(gdg_ctx *ctx, const std::vector<PlanStep> &plan, int n
         }
         const bool premac = ctx->fir_premac != 0 && !fused(st.n) && G == 1 && batch && every_k2 && partitions >= premac_min;
         premac_steps += premac ? 1 : 0;
-        for (auto &r : st.runs) r.frame = fused(r.n) ? Shape::FUSED : premac ? Shape::SPLIT_PREMAC : Shape::SPLIT;
+        /* ... and only where it moves fewer bytes for EVERY channel: per frame, in spectra, the pass reads 2 (K - 1) and writes T for T frames and
+         * the head reads acc + on average T + 1 more, against 2 K for the whole sum: 2 (K - 1) + T (T + 3) < 2 K T (T = 4: K >= 5; K = 2 at
+         * 96 kHz lost 4-5 %, profiles/shape_sweep_r07.txt) */
+        bool ahead_pays = true;
+        for (auto &e : plan[i].ops) {
+            const long K = ctx->units[(size_t)e.second.handles[0]].fir_K;
+            ahead_pays = ahead_pays && 2 * (K - 1) + (long)ahead_T * (ahead_T + 3) < 2 * K * ahead_T;
+        }
+        const bool ahead = ahead_T > 0 && batch && every_k2 && ahead_pays && ahead_steps < GDG_AHEAD_MAX_STEPS;
+        st.fir_ahead_T = 0;
+        for (auto &r : st.runs) {
+            r.frame = fused(r.n) ? Shape::FUSED : premac ? Shape::SPLIT_PREMAC : Shape::SPLIT;
+            if (r.frame == Shape::FUSED && ahead && r.n >= ctx->fir_ahead_min) { r.frame = Shape::FUSED_AHEAD; st.fir_ahead_T = ahead_T; }
+        }
+        ahead_steps += st.fir_ahead_T > 0 ? 1 : 0;
         st.window = Shape::FIR_WINDOW;
         /* LDS the premac's workgroups ask for and never touch: such a workgroup does not fit on a CU beside a general or tile segment
          * workgroup (159 KiB), and at most one fits beside a two-per-CU one (80 KiB), so the sums run on the CUs the segments leave idle
@@ -832,6 +850,7 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
     const double t_plan0 = pnow();
     join_groups(ctx);                 /* a new plan replaces descriptors (and possibly unit state) the group streams may still be reading */
     join_premac(ctx, false);          /* ... and the sums made ahead belong to the old plan's next frame */
+    drop_fir_ahead(ctx);              /* ... as do those of the next frames (FUSED_AHEAD) */
     /* Scan tables live as long as some plan's descriptors point at them -- there is one plan, this one.  A caller that sweeps a parameter
      * through thousands of values would let the cache grow without bound (12 KB per tone-stack setting): past the limit everything is
      * dropped once the work in flight has drained, and this plan re-makes the few tables it needs. */
@@ -954,6 +973,7 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
     ctx->patch_units.clear();                  /* this plan reads every unit's current parameters */
     ctx->plan_unit_fast.assign(ctx->units.size(), 0);
     ctx->plan_unit_fast_ok.assign(ctx->units.size(), 0);
+    bool acc_synced = false;                   /* one wait before the first sums-ahead buffer is released (below) */
     for (size_t i = 0; i < plan.size(); i++) {
         StepDesc &st = ctx->steps[i];
         const bool step_fast = dec.fast[i] != 0;
@@ -968,10 +988,21 @@ int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in,
             else dst = ((done[(size_t)c] & 1) ? ctx->d_w1 : ctx->d_w0) + (size_t)c * ctx->w_stride;
             if (st.is_fir) {
                 Unit &u = ctx->units[(size_t)op.handles[0]];
+                /* the sums made ahead: T spectra per channel while the step takes the shape, nothing otherwise (their contents belong to an
+                 * older epoch: never read) */
+                const size_t need = (size_t)st.fir_ahead_T * (size_t)u.fir_P * sizeof(double2);
+                if (u.acc_bytes < need || (need == 0 && u.d_acc)) {
+                    if (!acc_synced) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); acc_synced = true; }    /* nothing in flight reads them */
+                    ctx->arena.release(u.d_acc);
+                    u.d_acc = nullptr;
+                    u.acc_bytes = 0;
+                    if (need) { HIP_TRY(ctx, ctx->arena.alloc((void **)&u.d_acc, need)); u.acc_bytes = need; }
+                }
                 gdg_fir_chan f;
                 memset(&f, 0, sizeof(f));
                 f.src = cur[(size_t)c]; f.dst = dst; f.prev = u.d_prev; f.fdl = u.d_fdl; f.H = u.H->d_H; f.Y = u.d_Y;
                 f.pos = u.d_pos; f.K = u.fir_K; f.R = u.fir_R; f.hop = frames;
+                f.acc = st.fir_ahead_T > 0 ? u.d_acc : nullptr;
                 f.flags = (done[(size_t)c] == 0 ? GDG_SRC_IS_INPUT : 0) | (last ? GDG_DST_IS_OUTPUT : 0) |
                           (st.chain_next ? GDG_DST_UNUSED : 0);      /* only the chained transform reads the frame (window-mode kernels ignore the flag) */
                 fd.push_back(f);

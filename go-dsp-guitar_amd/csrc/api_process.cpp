@@ -144,6 +144,7 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
     const bool use_pre = ctx->premac_valid && window == 1 && plan_fits;
     if (!use_pre) join_premac(ctx, false);       /* an unused premac still writes Y: this call's launches go behind it */
     ctx->premac_valid = false;                   /* consumed by this call or dropped; the call's end makes the next one */
+    if (window != 1 || !plan_fits) drop_fir_ahead(ctx);     /* sums made ahead serve per-frame calls of the plan they were made for */
     if (!plan_fits || ctx->dirty) {              /* (a patch may have fallen back to dirty) */
         int rc = build_plan(ctx, active, d_in, d_out, frames, sample_rate, stride, stride_out, rows_by_channel, G, bounds);
         ctx->plan_bounds = bounds;
@@ -200,9 +201,53 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
         if (ctx->plan_trace >= 2) fprintf(stderr, "[launch] step=%zu group=%d shape=%s n=%d ahead=%d chained=%d\n", si, g, shape_name(shape), n, ahead, chained ? 1 : 0);
     };
     auto next_epoch = [ctx]() { return ctx->wave_epoch = (ctx->wave_epoch % 0x3ffffff) + 1; };          /* epoch * 32 + frame fits an int */
+    /* FUSED_AHEAD: this call makes the sums of the next T frames for the channels of phase (calls of the epoch) mod T; from the T-th call of
+     * the epoch on every channel continues sums made ahead */
+    bool ahead_call = false;
+    for (auto &st : ctx->steps) ahead_call = ahead_call || (window == 1 && st.is_fir && st.fir_ahead_T > 0);
+    if (ahead_call && !ctx->d_fir_ahead_used) {
+        HIP_TRY(ctx, ctx->arena.alloc_zeroed((void **)&ctx->d_fir_ahead_used, sizeof(unsigned long long), ctx->stream));
+        const unsigned long long v = (unsigned long long)ctx->stat_fir_ahead_used;      /* a count set before the first launch */
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_fir_ahead_used, &v, sizeof(v), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const gdg_ahead ahead_arg = { ctx->fir_ahead_epoch, ctx->fir_ahead_frames, ctx->d_fir_ahead_used };
     for (int g = 0; g < G; g++) {
         hipStream_t s = G > 1 ? ctx->gstreams[(size_t)g] : ctx->stream;
         if (G > 1) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->gfork, 0));
+        struct AheadLine { size_t step; int n, steps; };
+        std::vector<AheadLine> ahead_trace;      /* its [launch] lines follow the group's step lines (a reader indexes those by step) */
+        if (ahead_call) {
+            /* the pass ahead, on the group's own stream in front of its launches: the power amps of this group's FUSED_AHEAD launches with
+             * the same channel count share one launch (their frames so far are all in the delay lines) */
+            gdg_ahead_steps as;
+            memset(&as, 0, sizeof(as));
+            size_t as_step = 0;
+            int as_n = -1, as_T = 0;
+            auto flush = [&]() -> int {
+                if (as.n_steps == 0) return GDG_OK;
+                const int m = (as_n + as_T - 1) / as_T, phase = (int)(ctx->fir_ahead_calls % as_T);
+                as.first = phase * m;
+                as.n = std::min(as_n, as.first + m) - as.first;
+                if (as.n > 0) {
+                    if (ctx->plan_trace >= 2) ahead_trace.push_back({ as_step, as.n, as.n_steps });
+                    ProfScope ps(ctx, GDG_K_FIR_AHEAD, s);
+                    HIP_TRY(ctx, gdg_launch_fir_ahead(P2, as, gdg_ahead{ ahead_arg.epoch, as_T, nullptr }, s));
+                }
+                memset(&as, 0, sizeof(as));
+                return GDG_OK;
+            };
+            for (size_t sj = 0; sj < ctx->steps.size(); sj++) {
+                const StepDesc &sx = ctx->steps[sj];
+                const StepDesc::Run &r = sx.runs[(size_t)g];
+                if (!sx.is_fir || r.n == 0 || r.frame != Shape::FUSED_AHEAD) continue;
+                if (as.n_steps == GDG_AHEAD_MAX_STEPS || (as.n_steps > 0 && (r.n != as_n || sx.fir_ahead_T != as_T))) { int rc = flush(); if (rc != GDG_OK) return rc; }
+                if (as.n_steps == 0) { as_step = sj; as_n = r.n; as_T = sx.fir_ahead_T; }
+                as.chans[as.n_steps] = reinterpret_cast<const gdg_fir_chan *>(ctx->d_blob + sx.offset) + r.first;
+                as.shared_mask |= sx.shared_spectra ? 1 << as.n_steps : 0;
+                as.n_steps++;
+            }
+            { int rc = flush(); if (rc != GDG_OK) return rc; }
+        }
         if (before) HIP_TRY(ctx, (*before)(g, s));
         for (size_t si = 0; si < ctx->steps.size(); si++) {
             const StepDesc &st = ctx->steps[si];
@@ -230,19 +275,26 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
                     continue;
                 }
                 if (shape == Shape::SPLIT_PREMAC && !use_pre) shape = Shape::SPLIT;      /* no sums of this frame were made ahead */
-                trace(si, g, shape, n, 0, chained);
+                /* the head of the sums made ahead is a fused launch: it traces as FUSED, `ahead` = the frames one pass serves */
+                if (shape == Shape::FUSED_AHEAD) trace(si, g, Shape::FUSED, n, st.fir_ahead_T, chained);
+                else trace(si, g, shape, n, 0, chained);
                 if (!chained) { ProfScope ps(ctx, GDG_K_FIR_FWD, s); HIP_TRY(ctx, gdg_launch_fir_fwd(P2, frames, d, n, tw, tw2, shift, s)); }
                 if (shape == Shape::FUSED) {
                     /* multiply-accumulate fused into the inverse transform's first stage (reported as the MAC kernel; its chained
                      * variant, which also makes the next amp's forward transform, under a kind of its own) */
                     ProfScope ps(ctx, d_next ? GDG_K_FIR_MAC_CHAIN : GDG_K_FIR_MAC, s, ctx->prof_attach);
                     HIP_TRY(ctx, gdg_launch_fir_inv(P2, d, n, tw, tw2, st.shared_spectra ? 2 : 1, shift, s, d_next, ps.attached ? ps.a : nullptr, ps.attached ? ps.b : nullptr));
+                } else if (shape == Shape::FUSED_AHEAD) {
+                    /* the same, continuing the sums the pass ahead made where a channel's stamp says so (the others sum everything) */
+                    ProfScope ps(ctx, d_next ? GDG_K_FIR_MAC_CHAIN : GDG_K_FIR_MAC, s, ctx->prof_attach);
+                    HIP_TRY(ctx, gdg_launch_fir_inv(P2, d, n, tw, tw2, st.shared_spectra ? 6 : 5, shift, s, d_next, ps.attached ? ps.a : nullptr, ps.attached ? ps.b : nullptr,
+                                                    gdg_ahead{ ahead_arg.epoch, st.fir_ahead_T, ahead_arg.used }));
                 } else if (shape == Shape::SPLIT_PREMAC) {
                     /* the terms k >= 1 are in Y already (the previous call's premac): the newest term + the inverse transform */
                     if (ctx->premac_outstanding) { HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_premac, 0)); ctx->premac_outstanding = false; }
                     ProfScope ps(ctx, GDG_K_FIR_INV, s);
                     HIP_TRY(ctx, gdg_launch_fir_inv(P2, d, n, tw, tw2, 4, shift, s, d_next));
-                    ctx->stat_premac_used++;
+                    stat_add(ctx->stat_premac_used);
                 } else {
                     { ProfScope ps(ctx, GDG_K_FIR_MAC, s); HIP_TRY(ctx, gdg_launch_fir_mac(P2, d, n, st.shared_spectra ? 1 : 0, s)); }
                     { ProfScope ps(ctx, GDG_K_FIR_INV, s); HIP_TRY(ctx, gdg_launch_fir_inv(P2, d, n, tw, tw2, 0, shift, s, d_next)); }
@@ -300,6 +352,8 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
             }
         }
         if (after) HIP_TRY(ctx, (*after)(g, s));
+        for (const AheadLine &al : ahead_trace)
+            fprintf(stderr, "[launch] step=%zu group=%d shape=AHEAD n=%d ahead=%d chained=0\n", al.step, g, al.n, al.steps);
         if (premac_here) {
             /* every launch of the call is in the context's stream: now the side stream's share (the host must not keep the main stream
              * waiting for its next kernel while it enqueues these: 6 us per step) */
@@ -322,6 +376,7 @@ int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_i
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->gjoin[(size_t)g], 0));
         }
     }
+    if (ahead_call) ctx->fir_ahead_calls++;
     return GDG_OK;
 }
 
@@ -413,7 +468,7 @@ int check_device_error(gdg_ctx *ctx) {
 
 int gdg_ctx_trim(gdg_ctx *ctx) {
     if (!ctx) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->arena.trim_pending = true;
     ctx->arena.trim();
@@ -497,7 +552,7 @@ int gdg_process_subset(gdg_ctx *ctx, const int *channels, int n, const double *c
         if (c < 0 || c >= ctx->nch || seen[(size_t)c]) return fail(ctx, GDG_ERR_INVALID, "bad or repeated channel %d", c);
         seen[(size_t)c] = 1;
     }
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_staging(ctx);
     if (rc != GDG_OK) return rc;
     /* rows travel compactly ([i][frames]); G channel groups: group g's rows are staged and uploaded on stream g while the
@@ -543,7 +598,7 @@ int gdg_process(gdg_ctx *ctx, const double *const *in, double *const *out, int f
 /* pinned host slabs for callers that must not hand Go (or other managed) pointers to C: row c = channel c */
 int gdg_staging_buffers(gdg_ctx *ctx, double **in, double **out, int *row_stride) {
     if (!ctx || !in || !out || !row_stride) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_staging(ctx);
     if (rc != GDG_OK) return rc;
     *in = ctx->h_stage_in;
@@ -562,7 +617,7 @@ int gdg_process_staged(gdg_ctx *ctx, const int *channels, int n, int frames, uin
         if (c < 0 || c >= ctx->nch || seen[(size_t)c]) return fail(ctx, GDG_ERR_INVALID, "bad or repeated channel %d", c);
         seen[(size_t)c] = 1;
     }
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_staging(ctx);
     if (rc != GDG_OK) return rc;
     const size_t stride = (size_t)ctx->max_frames;

@@ -37,7 +37,7 @@ int tuner_enqueue_rows(gdg_ctx *ctx, const double *d_samples, size_t stride, int
 
 int gdg_tuner_enqueue_device(gdg_ctx *ctx, const double *d_samples, int frames, uint32_t sample_rate) {
     if (!ctx || !d_samples || frames < 0) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     return tuner_enqueue_rows(ctx, d_samples, (size_t)frames, frames, sample_rate);
 }
 
@@ -45,7 +45,7 @@ int gdg_tuner_enqueue_device(gdg_ctx *ctx, const double *d_samples, int frames, 
 int gdg_tuner_enqueue(gdg_ctx *ctx, const double *const *samples, int frames, uint32_t sample_rate) {
     if (!ctx || !samples) return GDG_ERR_INVALID;
     if (frames < 0 || frames > ctx->max_frames) return fail(ctx, GDG_ERR_INVALID, "frames %d out of range (max %d)", frames, ctx->max_frames);
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_staging(ctx);
     if (rc != GDG_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -60,7 +60,7 @@ int gdg_tuner_enqueue(gdg_ctx *ctx, const double *const *samples, int frames, ui
 int gdg_tuner_enqueue_staged(gdg_ctx *ctx, int frames, uint32_t sample_rate) {
     if (!ctx) return GDG_ERR_INVALID;
     if (frames < 0 || frames > ctx->max_frames) return fail(ctx, GDG_ERR_INVALID, "frames %d out of range (max %d)", frames, ctx->max_frames);
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_staging(ctx);
     if (rc != GDG_OK) return rc;
     if (frames == 0) return GDG_OK;
@@ -78,7 +78,7 @@ int gdg_tuner_replace(gdg_ctx *ctx, int channel, const double *samples, int n, u
     if (!ctx || !samples) return GDG_ERR_INVALID;
     if (channel < 0 || channel >= ctx->nch) return fail(ctx, GDG_ERR_INVALID, "channel %d out of range", channel);
     if (n != GDG_TUNER_RING) return fail(ctx, GDG_ERR_INVALID, "%d samples do not replace a ring of %d (tuner/tuner.go:16 NUM_SAMPLES)", n, GDG_TUNER_RING);
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_tuner(ctx);
     if (rc != GDG_OK) return rc;
     /* the oldest sample sits at the write position (shared by the context's channels): two pieces around the ring's end */
@@ -93,7 +93,7 @@ int gdg_tuner_replace(gdg_ctx *ctx, int channel, const double *samples, int n, u
 
 int gdg_tuner_analyze(gdg_ctx *ctx, gdg_tuner_result *results) {
     if (!ctx || !results) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_tuner(ctx);
     if (rc != GDG_OK) return rc;
     const int force_long = ctx->tuner_long;
@@ -192,7 +192,7 @@ int gdg_spatializer_set_position(gdg_ctx *ctx, int channel, double azimuth, doub
 
 int gdg_spatializer_set_sample_rate(gdg_ctx *ctx, uint32_t rate) {
     if (!ctx) return GDG_ERR_INVALID;
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     /* spatializer.go:418-431: new (zeroed) history buffers of ceil(rate * 6.3e-4) samples; this.sampleRate stays 96000 */
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     hipFree(ctx->d_sp_hist);
@@ -260,7 +260,7 @@ static int launch_spatializer(gdg_ctx *ctx, const double *d_in, int in_stride, d
 int gdg_spatialize_device(gdg_ctx *ctx, const double *d_in, double *d_out_lr, int frames) {
     if (!ctx || !d_in || !d_out_lr) return GDG_ERR_INVALID;
     if (frames <= 0 || frames > ctx->max_frames) return fail(ctx, GDG_ERR_INVALID, "frames %d out of range (max %d)", frames, ctx->max_frames);
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_spatializer(ctx);
     if (rc != GDG_OK) return rc;
     if (ctx->sp_dirty) { rc = upload_spat_chans(ctx); if (rc != GDG_OK) return rc; }
@@ -278,7 +278,7 @@ int spatialize_rows(gdg_ctx *ctx, const double *d_in, int in_stride, double *d_l
 int gdg_spatialize(gdg_ctx *ctx, const double *const *in, double *out_left, double *out_right, int frames) {
     if (!ctx || !in || !out_left || !out_right) return GDG_ERR_INVALID;
     if (frames <= 0 || frames > ctx->max_frames) return fail(ctx, GDG_ERR_INVALID, "frames %d out of range (max %d)", frames, ctx->max_frames);
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_staging(ctx);
     if (rc == GDG_OK) rc = ensure_spatializer(ctx);
     if (rc != GDG_OK) return rc;
@@ -297,7 +297,7 @@ int gdg_spatialize(gdg_ctx *ctx, const double *const *in, double *out_left, doub
 int gdg_spatialize_staged(gdg_ctx *ctx, int from_outputs, double *out_left, double *out_right, int frames) {
     if (!ctx || !out_left || !out_right) return GDG_ERR_INVALID;
     if (frames <= 0 || frames > ctx->max_frames) return fail(ctx, GDG_ERR_INVALID, "frames %d out of range (max %d)", frames, ctx->max_frames);
-    enter(ctx);
+    enter_keep_fir_sums(ctx);
     int rc = ensure_staging(ctx);
     if (rc == GDG_OK) rc = ensure_spatializer(ctx);
     if (rc != GDG_OK) return rc;

@@ -93,7 +93,9 @@ struct Unit {
     double *d_prev = nullptr;
     double2 *d_fdl = nullptr, *d_Y = nullptr;
     std::shared_ptr<SharedSpectra> H;
-    int *d_pos = nullptr;
+    int *d_pos = nullptr;                      /* [4]: the frame counter, the stamp of the sums made ahead (gdg_internal.h) */
+    double2 *d_acc = nullptr;                  /* [T][P] sums made ahead of the next T frames (Shape FUSED_AHEAD) */
+    size_t acc_bytes = 0;
 };
 
 struct Slot { int handle; bool bypass; };
@@ -115,10 +117,12 @@ enum class Shape : unsigned char {
     SPLIT,              /* power amp: the bin-tiled multiply-accumulate, then the inverse transform */
     SPLIT_PREMAC,       /* ... whose terms k >= 1 the previous call sums ahead of the frame (premac) */
     FIR_WINDOW,         /* power amp in a window (fir.hip, time blocking) */
+    FUSED_AHEAD,        /* FUSED, continuing the sums a pass at the call's start made for the next T frames (fir_ahead_kernel) */
 };
 static inline const char *shape_name(Shape s) {
     static const char *const names[] = { "SKIP", "GENERAL", "GENERAL_AHEAD", "SEGF", "SEGT", "WAVE", "SEGF_WAVE", "WALK", "SEGF_WALK",
-                                         "OS_TILES", "OS_TILES_PREFIX", "FUSED", "SPLIT", "SPLIT_PREMAC", "FIR_WINDOW" };
+                                         "OS_TILES", "OS_TILES_PREFIX", "FUSED", "SPLIT", "SPLIT_PREMAC", "FIR_WINDOW",
+                                         "FUSED_AHEAD" };
     return names[(int)s];
 }
 
@@ -133,6 +137,7 @@ struct StepDesc {
     bool chain_next = false;          /* FIR step whose every channel feeds another power amp next (the following step): that amp's forward
                                        * transform rides on this step's inverse (fir_inv_kernel CHAIN) */
     int premac_lds = 0;               /* FIR step: the LDS its premac launch asks for without using it (decide_shapes) */
+    int fir_ahead_T = 0;              /* FIR step: > 0 when some group's launch is FUSED_AHEAD -- the frames one pass ahead serves (decide_shapes) */
     int os_factor = 0;                /* 2 / 4: the step is ONE oversampled shaper per channel, run as a launch of its own (seg.hip os_tiles_kernel) */
     int os_flags = -1;                /* ... and its per-channel flags start here in d_wave */
     int os_arrive = -1;               /* ... its per-channel arrival counters (a compressor step absorbed into the launch, below) */
@@ -221,7 +226,22 @@ struct gdg_ctx {
                                                 * per step with it, 32 x 8: 112.4 -> 109.6, 24 x 8: 107.2 -> 108.6 (profiles/premac_loads_ab_r06.txt) */
     hipStream_t premac_stream = nullptr;
     hipEvent_t ev_fir_done = nullptr, ev_premac = nullptr;
-    int stat_premac_used = 0;                  /* option "stat_premac_launches_used" (read it; tests): inverse launches that continued sums made ahead */
+    int stat_premac_used = 0;                  /* option "stat_premac_launches_used" (read it; tests): inverse launches that continued sums made ahead
+                                                * (saturates at INT_MAX) */
+    /* Per-frame calls of many channels (the fused shape): the terms of frame t0 + j with k >= j + 1 only read frames that exist when call t0
+     * starts, so ONE pass over H[1 .. K-1] and X[t0-K+1 .. t0-1] makes them for the next T frames (fir_ahead_kernel, on the group's own
+     * stream at the call's start), and the inverse kernel of frame t0 + j adds the terms k = j .. 0 (FUSED 5 / 6).  The channels are
+     * staggered: call c makes the sums of the channels of phase c mod T (contiguous blocks of n / T of each group), so every call does the
+     * same work.  A stamp next to each frame counter on the device holds (frame, epoch) of the sums; the context's epoch moves on whenever
+     * anything but a per-frame call of the same plan touches the context (drop_fir_ahead), and a stamp of another epoch is never read. */
+    int fir_ahead_frames = 4;                  /* option "fir_ahead_frames": T, 2 .. 4; 0 never */
+    int fir_ahead_min = 128;                   /* option "fir_ahead_min_channels": fewest channels of a group's launch (no reverb / flanger chains,
+                                                * 128 channels: 126.2 -> 120.0 / 120.1 -> 112.9 us per step, profiles/shape_sweep_r07.txt) */
+    int stat_fir_ahead_used = 0;               /* option "stat_fir_ahead_sums_used": channel frames whose inverse kernel continued sums made ahead,
+                                                * counted on the device (d_fir_ahead_used; read back when the option is read, saturates at INT_MAX) */
+    unsigned long long *d_fir_ahead_used = nullptr;
+    unsigned fir_ahead_epoch = 1;              /* 0 is never current: a zeroed stamp is no stamp */
+    long long fir_ahead_calls = 0;             /* per-frame calls of this epoch (the phase of the call: fir_ahead_calls mod T) */
     bool premac_valid = false;                 /* Y of every premac step holds the terms k >= 1 of the plan's NEXT frame */
     bool premac_outstanding = false;           /* ... and the context's stream has not been ordered behind that launch yet */
     /* reverbs' wet paths ahead of the frame (seg.hip REVERB_AHEAD): made by extra workgroups of an EARLIER segment launch of the same call */
@@ -367,11 +387,21 @@ static inline void join_premac(gdg_ctx *ctx, bool keep) {
     }
     if (!keep) ctx->premac_valid = false;
 }
-static inline void enter(gdg_ctx *ctx, bool read_only = false) {
+/* the sums made ahead of the next frames (Shape FUSED_AHEAD) are never read again: a new epoch */
+static inline void drop_fir_ahead(gdg_ctx *ctx) {
+    ctx->fir_ahead_epoch = ctx->fir_ahead_epoch == 0xffffffffu ? 1u : ctx->fir_ahead_epoch + 1u;
+    ctx->fir_ahead_calls = 0;
+}
+static inline void stat_add(int &counter) { if (counter < 0x7fffffff) counter++; }
+/* `keep_fir_sums`: the call changes nothing the sums made ahead of the next frames read -- filters, delay lines, frame counters, ring
+ * layout, plan (caller data, codecs, tuner, spatializer, meters, the host-buffer process calls, whose plan process_rows checks itself) */
+static inline void enter(gdg_ctx *ctx, bool read_only = false, bool keep_fir_sums = false) {
     hipSetDevice(ctx->device);
     join_groups(ctx);
     join_premac(ctx, read_only);
+    if (!read_only && !keep_fir_sums) drop_fir_ahead(ctx);
 }
+static inline void enter_keep_fir_sums(gdg_ctx *ctx) { enter(ctx, false, true); }
 
 /* the parameter index of an overdrive's / distortion's / excess's oversampling (0 none, 1 "2", 2 "4"); -1: the unit type has none */
 static inline int shaper_os_param(int type) {

@@ -824,25 +824,42 @@ __device__ __forceinline__ void inv_head_store(int k, cplx yk, cplx yn, double *
  * partitions of one bin pair at once) had 32 interleaved streams per workgroup, 8192 on the chip, and lost 25 % of the
  * bandwidth to DRAM page conflicts (profiles/experiments/README.md). */
 /* PRE: the terms k = K - 1 .. 1 are already summed in Y (the premac launch, fir_mac_kernel with k_lo = 1): the sums start from there and
- * only the newest partition is added -- two spectra per channel instead of 2 K on the critical path of a small shard. */
-template <int LOGN, bool HNT, bool PRE = false>
-__device__ __forceinline__ void mac_head(const gdg_fir_chan &ch, int cur, int tid, double *sre, double *sim, const cplx *__restrict__ tw2) {
+ * only the newest partition is added -- two spectra per channel instead of 2 K on the critical path of a small shard.
+ * AHEAD: a pass ahead (fir_ahead_kernel) stamped the channel with (frame s, epoch): for frame pos = s + j, j < T and j < K - 1, acc[j] holds
+ * the terms k = K - 1 .. j + 1 and the sum goes on with k = j .. 0.  Any other channel -- no stamp of this epoch, a stamp too old, a filter
+ * too short to have terms ahead -- runs the whole sum, as FUSED 1 / 2 do. */
+template <int LOGN, bool HNT, bool PRE = false, bool AHEAD = false>
+__device__ __forceinline__ void mac_head(const gdg_fir_chan &ch, int cur, int tid, double *sre, double *sim, const cplx *__restrict__ tw2,
+                                         gdg_ahead ah = gdg_ahead{ 0u, 0, nullptr }) {
 #pragma clang fp contract(off)
     constexpr int N = FftCfg<LOGN>::N, T = FftCfg<LOGN>::T, ITER = (N / 2) / T;
     const int K = ch.K;
     double kr[ITER], ki[ITER], nr[ITER], ni[ITER], br = 0.0, bi = 0.0;
 #pragma unroll
     for (int i = 0; i < ITER; i++) { kr[i] = 0.0; ki[i] = 0.0; nr[i] = 0.0; ni[i] = 0.0; }
-    if constexpr (PRE) {
+    int u0 = PRE ? 0 : K - 1;
+    const cplx *__restrict__ pre = PRE ? ch.Y : nullptr;
+    if constexpr (AHEAD) {
+        const int pos = ch.pos[0], stamp = ch.pos[1];
+        const unsigned epoch = (unsigned)ch.pos[2];
+        int j = pos - stamp;
+        if (j < 0) j += 2 * ch.R;                       /* the frame counter wraps at 2 R (the end of this kernel) */
+        if (ah.epoch != 0u && epoch == ah.epoch && j < ah.T && j < K - 1) {
+            u0 = j;
+            pre = ch.acc + (size_t)j * N;
+            if (tid == 0 && ah.used) atomicAdd(ah.used, 1ull);        /* the counter the tests read: the device's own word on the path taken */
+        }
+    }
+    if (PRE || pre) {
 #pragma unroll
         for (int i = 0; i < ITER; i++) {
             const int k = tid + T * i, n = (k == 0) ? N / 2 : N - k;
-            const cplx yk = gload(ch.Y + k), yn = gload(ch.Y + n);
+            const cplx yk = AHEAD ? mac_load<true>(pre + k) : gload(pre + k), yn = AHEAD ? mac_load<true>(pre + n) : gload(pre + n);
             if (k == 0) { br = yk.x; bi = yk.y; } else { kr[i] = yk.x; ki[i] = yk.y; }
             nr[i] = yn.x; ni[i] = yn.y;
         }
     }
-    for (int u = PRE ? 0 : K - 1; u >= 0; u--) {        /* k descending: the order of the sum (fir_mac_kernel) */
+    for (int u = u0; u >= 0; u--) {        /* k descending: the order of the sum (fir_mac_kernel) */
         int slot = cur - u;
         if (slot < 0) slot += ch.R;
         const cplx *__restrict__ x = ch.fdl + (size_t)slot * N;
@@ -879,7 +896,103 @@ __device__ __forceinline__ void mac_head(const gdg_fir_chan &ch, int cur, int ti
     }
 }
 
-/* FUSED 4: Y holds the sum of the terms k = K - 1 .. 1 (fir_mac_kernel with k_lo = 1, launched ahead of the frame); the newest term is added here.
+/* The pass ahead (per-frame calls, Shape FUSED_AHEAD).  The sum of frame t0 + j is Y = sum_{k = K-1 .. 0} H[k] X[t0 + j - k]; its terms
+ * k >= j + 1 only read frames that exist before frame t0 does.  One pass over H[K-1 .. 1] and X[t0-K+1 .. t0-1] therefore makes the sums
+ * of the next TT frames at once: acc[j] = sum_{k = K-1 .. j+1} H[k] X[t0 + j - k], j < min(TT, K - 1), each in the order of every other
+ * multiply-accumulate kernel (k descending, bin 0 component-wise, no contraction), so the head that continues it (mac_head AHEAD) gives
+ * the bits of the whole sum.  A thread per bin; the TT frames' delay-line spectra slide through registers, so every spectrum is read
+ * once: 2 (K - 1) spectra for TT sums instead of 2 (K - 1) per sum.  Grid: (bins / 256, channels, steps). */
+template <int TT, int U, bool HNT>
+__device__ __forceinline__ void ahead_sums(const gdg_fir_chan &ch, int P, int b) {
+#pragma clang fp contract(off)
+    const int K = ch.K, R = ch.R, pos = ch.pos[0];
+    const int cur = pos % R;
+    const cplx *__restrict__ fdl = ch.fdl + b;
+    const cplx *__restrict__ H = ch.H + b;
+    auto X = [&](int d) {                               /* the spectrum of frame pos - d, d >= 1 */
+        int slot = cur - d;
+        if (slot < 0) slot += R;
+        return mac_load<true>(fdl + (size_t)slot * P);
+    };
+    double ar[TT], ai[TT], br[TT], bi[TT];
+    cplx w[TT];                                         /* step k: w[j] = X[pos + j - k] */
+    int k = K - 1;
+#pragma unroll
+    for (int j = 0; j < TT; j++) {
+        ar[j] = 0.0; ai[j] = 0.0; br[j] = 0.0; bi[j] = 0.0;
+        w[j] = (k - j >= 1) ? X(k - j) : make_double2(0.0, 0.0);
+    }
+    auto term = [&](int j, cplx x, cplx h) {
+        ar[j] += x.x * h.x - x.y * h.y;
+        ai[j] += x.x * h.y + x.y * h.x;
+        br[j] += x.x * h.x;
+        bi[j] += x.y * h.y;
+    };
+    /* U steps at a time while every sum has its term in each of them (k - U >= TT): U partitions' and U frames' loads in flight */
+    while (k - U >= TT) {
+        cplx all[TT + U], h[U];
+#pragma unroll
+        for (int j = 0; j < TT; j++) all[j] = w[j];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            h[u] = mac_load<HNT>(H + (size_t)(k - u) * P);
+            all[TT + u] = X(k - u - TT);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int j = 0; j < TT; j++) term(j, all[u + j], h[u]);
+#pragma unroll
+        for (int j = 0; j < TT; j++) w[j] = all[U + j];
+        k -= U;
+    }
+    /* the rest, k < TT + U: every load first, then the terms that exist (sum j takes k down to j + 1) */
+    {
+        constexpr int TL = TT + U - 1;
+        cplx all[TT + TL], h[TL];
+#pragma unroll
+        for (int j = 0; j < TT; j++) all[j] = w[j];
+#pragma unroll
+        for (int t = 0; t < TL; t++) {
+            h[t] = (t < k) ? mac_load<HNT>(H + (size_t)(k - t) * P) : make_double2(0.0, 0.0);
+            all[TT + t] = (k - t - TT >= 1) ? X(k - t - TT) : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int t = 0; t < TL; t++) {
+            if (t < k) {
+#pragma unroll
+                for (int j = 0; j < TT; j++)
+                    if (j <= k - t - 1) term(j, all[t + j], h[t]);
+            }
+        }
+    }
+    const int TJ = K - 1 < TT ? K - 1 : TT;
+#pragma unroll
+    for (int j = 0; j < TT; j++)
+        if (j < TJ) gstore_nt(ch.acc + (size_t)j * P + b, (b == 0) ? make_double2(br[j], bi[j]) : make_double2(ar[j], ai[j]));
+}
+
+template <int TT>
+__global__ void __launch_bounds__(256)
+fir_ahead_kernel(gdg_ahead_steps steps, gdg_ahead ah, int P) {
+    const int step = (int)blockIdx.z;
+    const gdg_fir_chan ch = steps.chans[step][steps.first + (int)blockIdx.y];
+    const int b = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (b >= P) return;
+    if (ch.K >= 2) {
+        /* private IR spectra are read once per pass: past the caches like the delay line; shared ones through them */
+        if ((steps.shared_mask >> step) & 1) ahead_sums<TT, 4, false>(ch, P, b);
+        else ahead_sums<TT, 4, true>(ch, P, b);
+    }
+    if (b == 0) {
+        /* the stamp: these sums belong to frame pos[0] + j of this epoch (the head kernels of this stream run behind this launch) */
+        ch.pos[1] = ch.pos[0];
+        ch.pos[2] = (int)ah.epoch;
+    }
+}
+
+/* FUSED 5 / 6: as 1 / 2, continuing the sums a pass ahead made (fir_ahead_kernel, mac_head AHEAD) where the channel's stamp says so.
+ * FUSED 4: Y holds the sum of the terms k = K - 1 .. 1 (fir_mac_kernel with k_lo = 1, launched ahead of the frame); the newest term is added here.
  * FUSED 0: Y comes from fir_mac_kernel.  FUSED 1 / 2: the multiply-accumulate runs here, straight into the inverse's
  * first stage (no Y round trip through HBM: the 6 % of extra bytes cost the separate MAC 20 % of its time, see
  * profiles/probes/); 2 = the IR spectra are shared between channels and read with cacheable loads. */
@@ -892,7 +1005,7 @@ __device__ __forceinline__ void mac_head(const gdg_fir_chan &ch, int cur, int ti
 template <int LOGN, int FUSED, bool CHAIN = false>
 __global__ void __launch_bounds__(FftCfg<LOGN>::T)
 fir_inv_kernel(const gdg_fir_chan *__restrict__ chans, int W, gdg_shift shift, const cplx *__restrict__ tw, const cplx *__restrict__ tw2,
-               const gdg_fir_chan *__restrict__ next_chans = nullptr) {
+               const gdg_fir_chan *__restrict__ next_chans, gdg_ahead ah) {
     constexpr int N = FftCfg<LOGN>::N, T = FftCfg<LOGN>::T;
     static_assert(!CHAIN || (LOGN == 13 && FUSED != 3), "the chained forward transform is the 8 x 1024 one of the batch block size");
     constexpr int LDS_WORDS = (CHAIN && GDG_W_LDS > FftCfg<LOGN>::LDS) ? GDG_W_LDS : FftCfg<LOGN>::LDS;
@@ -905,10 +1018,12 @@ fir_inv_kernel(const gdg_fir_chan *__restrict__ chans, int W, gdg_shift shift, c
     gdg_fir_chan ch = chans[(FUSED == 3) ? blockIdx.x / (unsigned)W : blockIdx.x];
     const cplx *__restrict__ Y = ch.Y + (size_t)jw * N;
     int cur = 0;
-    if constexpr (FUSED == 1 || FUSED == 2 || FUSED == 4) cur = (*ch.pos) % ch.R;
+    if constexpr (FUSED == 1 || FUSED == 2 || FUSED == 4 || FUSED == 5 || FUSED == 6) cur = (*ch.pos) % ch.R;
 
     if constexpr (FUSED == 1) mac_head<LOGN, true>(ch, cur, tid, sre, sim, tw2);
     else if constexpr (FUSED == 2) mac_head<LOGN, false>(ch, cur, tid, sre, sim, tw2);
+    else if constexpr (FUSED == 5) mac_head<LOGN, true, false, true>(ch, cur, tid, sre, sim, tw2, ah);       /* sums made ahead, if stamped */
+    else if constexpr (FUSED == 6) mac_head<LOGN, false, false, true>(ch, cur, tid, sre, sim, tw2, ah);
     else if constexpr (FUSED == 4) mac_head<LOGN, false, true>(ch, cur, tid, sre, sim, tw2);       /* Y holds the terms k >= 1 (premac) */
     else {
         constexpr int ITER = (N / 2) / T;
@@ -1527,21 +1642,25 @@ template <int LG> static void launch_raw_inv(const gdg_fir_rawjob *d_jobs, int n
         else hipLaunchKernelGGL((KERNEL), dim3(n), dim3(FftCfg<LG>::T), 0, s, __VA_ARGS__);                                           \
     } while (0)
 template <int LG> static void launch_inv(const gdg_fir_chan *d_chans, int n, const cplx *tw, const cplx *tw2, int fused, gdg_shift shift, hipStream_t s,
-                                         const gdg_fir_chan *d_next, hipEvent_t e0, hipEvent_t e1) {
+                                         const gdg_fir_chan *d_next, hipEvent_t e0, hipEvent_t e1, gdg_ahead ah) {
     const gdg_fir_chan *none = nullptr;
     if constexpr (LG == 13) {
         if (d_next) {       /* the next unit of every channel is a power amp: its forward transform rides along */
-            if (fused == 0) GDG_LAUNCH_INV((fir_inv_kernel<13, 0, true>), d_chans, 1, shift, tw, tw2, d_next);
-            else if (fused == 4) GDG_LAUNCH_INV((fir_inv_kernel<13, 4, true>), d_chans, 1, shift, tw, tw2, d_next);
-            else if (fused == 1) GDG_LAUNCH_INV((fir_inv_kernel<13, 1, true>), d_chans, 1, shift, tw, tw2, d_next);
-            else GDG_LAUNCH_INV((fir_inv_kernel<13, 2, true>), d_chans, 1, shift, tw, tw2, d_next);
+            if (fused == 0) GDG_LAUNCH_INV((fir_inv_kernel<13, 0, true>), d_chans, 1, shift, tw, tw2, d_next, ah);
+            else if (fused == 4) GDG_LAUNCH_INV((fir_inv_kernel<13, 4, true>), d_chans, 1, shift, tw, tw2, d_next, ah);
+            else if (fused == 1) GDG_LAUNCH_INV((fir_inv_kernel<13, 1, true>), d_chans, 1, shift, tw, tw2, d_next, ah);
+            else if (fused == 5) GDG_LAUNCH_INV((fir_inv_kernel<13, 5, true>), d_chans, 1, shift, tw, tw2, d_next, ah);
+            else if (fused == 6) GDG_LAUNCH_INV((fir_inv_kernel<13, 6, true>), d_chans, 1, shift, tw, tw2, d_next, ah);
+            else GDG_LAUNCH_INV((fir_inv_kernel<13, 2, true>), d_chans, 1, shift, tw, tw2, d_next, ah);
             return;
         }
+        if (fused == 5) { GDG_LAUNCH_INV((fir_inv_kernel<13, 5>), d_chans, 1, shift, tw, tw2, none, ah); return; }
+        if (fused == 6) { GDG_LAUNCH_INV((fir_inv_kernel<13, 6>), d_chans, 1, shift, tw, tw2, none, ah); return; }
     }
-    if (fused == 0) GDG_LAUNCH_INV((fir_inv_kernel<LG, 0>), d_chans, 1, shift, tw, tw2, none);
-    else if (fused == 4) { if constexpr (LG == 13) GDG_LAUNCH_INV((fir_inv_kernel<13, 4>), d_chans, 1, shift, tw, tw2, none); }
-    else if (fused == 1) GDG_LAUNCH_INV((fir_inv_kernel<LG, 1>), d_chans, 1, shift, tw, tw2, none);
-    else GDG_LAUNCH_INV((fir_inv_kernel<LG, 2>), d_chans, 1, shift, tw, tw2, none);
+    if (fused == 0) GDG_LAUNCH_INV((fir_inv_kernel<LG, 0>), d_chans, 1, shift, tw, tw2, none, ah);
+    else if (fused == 4) { if constexpr (LG == 13) GDG_LAUNCH_INV((fir_inv_kernel<13, 4>), d_chans, 1, shift, tw, tw2, none, ah); }
+    else if (fused == 1) GDG_LAUNCH_INV((fir_inv_kernel<LG, 1>), d_chans, 1, shift, tw, tw2, none, ah);
+    else GDG_LAUNCH_INV((fir_inv_kernel<LG, 2>), d_chans, 1, shift, tw, tw2, none, ah);
 }
 #undef GDG_LAUNCH_INV
 
@@ -1617,7 +1736,7 @@ hipError_t gdg_launch_fir_window(int W, const gdg_fir_chan *d_chans, int n_chans
         else if (W == 8) launch_mac_tb<8, 8>(d_chans, n_chans, shared_spectra != 0, s);
         else launch_mac_tb<16, 8>(d_chans, n_chans, shared_spectra != 0, s);
     } else if (what == 2 && (half & 2)) fir_inv13h_kernel<<<dim3(n_chans * W), dim3(512), 0, s>>>(d_chans, W, shift, d_tw, d_tw2);
-    else if (what == 2) fir_inv_kernel<13, 3><<<dim3(n_chans * W), dim3(FftCfg<13>::T), 0, s>>>(d_chans, W, shift, d_tw, d_tw2);
+    else if (what == 2) fir_inv_kernel<13, 3><<<dim3(n_chans * W), dim3(FftCfg<13>::T), 0, s>>>(d_chans, W, shift, d_tw, d_tw2, nullptr, gdg_ahead{ 0u, 0, nullptr });
     else fir_tb_finish_kernel<<<dim3(n_chans), dim3(256), 0, s>>>(d_chans, W, shift);
     return hipGetLastError();
 }
@@ -1719,13 +1838,27 @@ hipError_t gdg_launch_fir_mac(int P, const gdg_fir_chan *d_chans, int n_chans, i
 }
 
 /* fused: 0 = inverse only (Y from gdg_launch_fir_mac), 1 = MAC + inverse, 2 = MAC + inverse with shared (cacheable) IR spectra,
- * 4 (P = 8192 only) = Y from gdg_launch_fir_mac(.., k_lo = 1) + the newest partition's term + inverse */
+ * 4 (P = 8192 only) = Y from gdg_launch_fir_mac(.., k_lo = 1) + the newest partition's term + inverse,
+ * 5 / 6 (P = 8192 only) = 1 / 2 continuing the sums of gdg_launch_fir_ahead where a channel's stamp is of `ahead.epoch` and recent enough */
 hipError_t gdg_launch_fir_inv(int P, const gdg_fir_chan *d_chans, int n_chans, const cplx *d_tw, const cplx *d_tw2, int fused, gdg_shift shift, hipStream_t s,
-                              const gdg_fir_chan *d_next_chans, hipEvent_t ev_begin, hipEvent_t ev_end) {
+                              const gdg_fir_chan *d_next_chans, hipEvent_t ev_begin, hipEvent_t ev_end, gdg_ahead ahead) {
     if (n_chans <= 0) return hipSuccess;
     int L = ilog2_exact(P);
-    if ((d_next_chans || fused == 4) && L != 13) return hipErrorInvalidValue;
-    GDG_DISPATCH_LOGN(L, launch_inv<LG>(d_chans, n_chans, d_tw, d_tw2, fused, shift, s, d_next_chans, ev_begin, ev_end));
+    if ((d_next_chans || fused == 4 || fused == 5 || fused == 6) && L != 13) return hipErrorInvalidValue;
+    GDG_DISPATCH_LOGN(L, launch_inv<LG>(d_chans, n_chans, d_tw, d_tw2, fused, shift, s, d_next_chans, ev_begin, ev_end, ahead));
+    return hipGetLastError();
+}
+
+hipError_t gdg_launch_fir_ahead(int P, const gdg_ahead_steps &steps, gdg_ahead ahead, hipStream_t s) {
+    if (steps.n <= 0 || steps.n_steps <= 0) return hipSuccess;
+    if (P != 8192 || steps.n_steps > GDG_AHEAD_MAX_STEPS) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(P / 256), (unsigned)steps.n, (unsigned)steps.n_steps);
+    switch (ahead.T) {
+    case 2: fir_ahead_kernel<2><<<grid, dim3(256), 0, s>>>(steps, ahead, P); break;
+    case 3: fir_ahead_kernel<3><<<grid, dim3(256), 0, s>>>(steps, ahead, P); break;
+    case 4: fir_ahead_kernel<4><<<grid, dim3(256), 0, s>>>(steps, ahead, P); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -20,7 +20,9 @@
  *                        (P complex128; bin 0 carries (Re X[0], Re X[P])) of [x_{t-1} | x_t]
  *   H     [K][P] cplx    packed half spectra of the IR partitions, pre-scaled by 1/(2P)
  *   Y     [P]    cplx    accumulated product spectrum (scratch between MAC and inverse)
- *   pos   int            frame counter; slot of the current frame = pos % K
+ *   pos   int[4]         [0] frame counter; slot of the current frame = pos % R.  [1], [2]: the frame counter and the epoch the sums
+ *                        made ahead were made for (fir_ahead_kernel; epoch 0 = none)
+ *   acc   [T][P] cplx    sums made ahead (fir_ahead_kernel): acc[j] = the terms k = K - 1 .. j + 1 of frame pos[1] + j
  * ---------------------------------------------------------------------------------------------- */
 /* A plan's descriptors hold absolute pointers; those into the caller's buffers are flagged, and every launch carries the distance
  * (in samples) from the buffers the plan was built on to the ones of this call -- walking through a file does not rebuild the plan. */
@@ -37,6 +39,7 @@ struct gdg_fir_chan {
     const double2 *H;
     double2 *Y;
     int *pos;
+    double2 *acc;            /* [T][P] sums made ahead of the next T frames (per-frame calls, Shape FUSED_AHEAD); null elsewhere */
     int K;
     int R;                   /* slots of the delay-line ring: K, or K + W - 1 when the context runs windows of W blocks (time blocking) */
     int flags;               /* GDG_SRC_IS_INPUT / GDG_DST_IS_OUTPUT */
@@ -84,8 +87,18 @@ hipError_t gdg_launch_fir_window(int W, const gdg_fir_chan *d_chans, int n_chans
 int gdg_fir_window_chain_ok(int n_chans, int W);
 hipError_t gdg_launch_fir_window_chain(int W, const gdg_fir_chan *d_chans, const gdg_fir_chan *d_next_chans, int n_chans, const double2 *d_tw,
                                        const double2 *d_tw2, gdg_shift shift, hipStream_t s);
+/* Sums made ahead of several frames (fused = 5 / 6 below): the sums of frame t hold the terms k = K - 1 .. j + 1 for j = t - stamp; `epoch` is
+ * the context's current one (a stamp of another epoch is never read), T the frames one pass serves (2 .. 4); `used` (may be null) counts the
+ * workgroups -- channel frames -- that continued sums made ahead */
+struct gdg_ahead { unsigned epoch; int T; unsigned long long *used; };
 hipError_t gdg_launch_fir_inv(int P, const gdg_fir_chan *d_chans, int n_chans, const double2 *d_tw, const double2 *d_tw2, int fused, gdg_shift shift, hipStream_t s,
-                              const gdg_fir_chan *d_next_chans = nullptr, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+                              const gdg_fir_chan *d_next_chans = nullptr, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr,
+                              gdg_ahead ahead = gdg_ahead{ 0u, 0, nullptr });
+/* the pass ahead (P = 8192 only): for every step s < n_steps, the channels [first, first + n) of d_chans[s] get acc[j] = the terms
+ * k = K - 1 .. j + 1 of frame pos + j, j = 0 .. min(T, K - 1) - 1, and the stamp (pos, epoch); shared_spectra as gdg_launch_fir_mac */
+#define GDG_AHEAD_MAX_STEPS 4
+struct gdg_ahead_steps { const gdg_fir_chan *chans[GDG_AHEAD_MAX_STEPS]; int n_steps; int first, n; int shared_mask; };
+hipError_t gdg_launch_fir_ahead(int P, const gdg_ahead_steps &steps, gdg_ahead ahead, hipStream_t s);
 hipError_t gdg_launch_fir_ir(int P, const gdg_fir_irjob *d_jobs, int n_jobs, double scale, const double2 *d_tw, const double2 *d_tw2, hipStream_t s);
 hipError_t gdg_launch_fir_raw_inv(int P, const gdg_fir_rawjob *d_jobs, int n_jobs, double scale, const double2 *d_tw, const double2 *d_tw2, hipStream_t s);
 

@@ -98,10 +98,23 @@ int gdg_ctx_share_ir_spectra(gdg_ctx *ctx, int enable);
  *                                            taps: below, the two cross-stream hops cost more than they hide)
  *   fir_premac_min_partitions_two_amps >= 1  ... and when a channel has two or more power amps, the smaller of the two (320 = 40 channels x 65536 taps)
  *   stat_premac_launches_used    >= 0        a counter, not a setting: inverse-transform launches so far that continued sums made ahead (tests read it to
- *                                            see that the path under test is the one that ran; setting it sets the count) (0)
+ *                                            see that the path under test is the one that ran; saturates; setting it sets the count) (0)
  *   fir_premac_lds_bytes         -1 .. 65536 ... whose workgroups ask for this much LDS they never touch, so that they land on the CUs the segments leave
  *                                            idle instead of among the segments' waves; -1: 16384 below 120 channels, 49152 from there, 0 when a channel
  *                                            has fewer than 5 or more than 32 partitions (-1)
+ *   fir_ahead_frames             0, 2 .. 4   per-frame calls of the fused launch shape (many channels, 8192-sample frames, every filter longer than one
+ *                                            frame): a pass at the call's start sums, for a 1/T share of the channels, the terms of the next T frames that
+ *                                            only need frames already in the delay line; the inverse kernels of those frames add the rest.  Every filter
+ *                                            spectrum and delay-line slot is then read once per T frames instead of once per frame.  The sums belong to
+ *                                            per-frame calls of one plan: a window call, a plan change (new filters, chains, options, frame size or
+ *                                            channels) or a call that touches units, filters or the context's shape makes the next calls sum everything
+ *                                            again; calls on caller data, codecs, tuner, spatializer and meters keep them.  Same bits either way
+ *                                            (4; 0 or 1: never)
+ *   fir_ahead_min_channels       >= 1        ... in launches (a channel group's power amp) of at least this many channels, when every channel's filter
+ *                                            has enough partitions for the pass to move fewer bytes (K >= 5 at T = 4) (128)
+ *   stat_fir_ahead_sums_used     >= 0        a counter, not a setting: channel frames so far whose inverse kernel continued sums made ahead, counted
+ *                                            by the kernels on the device (reading it waits for the context's work; saturates; setting it sets
+ *                                            the count) (0)
  *   share_ir_spectra             0, 1        = gdg_ctx_share_ir_spectra (1)
  *   seg_two_per_cu               0, 1        segments of in-place units on 8192-sample frames take the 512-thread kernel, two workgroups per CU (1)
  *   seg_two_per_cu_min_channels  >= 0        ... from this many channels per call on (128)
@@ -327,6 +340,8 @@ enum gdg_kernel_kind {
     GDG_K_METER,         /* level meters */
     GDG_K_FIR_MAC_CHAIN, /* GDG_K_FIR_MAC of a power amp that is followed by another one: the same kernel also makes the next amp's forward
                           * transform (fir_inv_kernel CHAIN); kept apart so that GDG_K_FIR_MAC times the plain kernel only */
+    GDG_K_FIR_AHEAD,     /* per-frame calls of many channels: the pass that sums the older partitions' terms of the next frames ahead
+                          * (option fir_ahead_frames) */
     GDG_K_COUNT
 };
 /* enable == 1: bracket every kernel launch with a HIP event pair from now on (costs a few microseconds per launch);

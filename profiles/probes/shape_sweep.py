@@ -6,7 +6,7 @@ two-per-CU kernel does not run); the bench's own (two power amps per channel) --
 other side of its threshold (the shape it would take if the threshold were elsewhere):
 
     per-frame calls:  fir_split_max_channels, fir_premac, seg_two_per_cu_min_channels, seg_os_tiles_max_channels, seg_reverb_ahead_max_channels,
-                      seg_tile_max_channels, seg_os_tiles_prefix
+                      seg_tile_max_channels, seg_os_tiles_prefix, fir_ahead_min_channels (where the convolution is fused)
     windows of 16:    seg_wave_max_channels, seg_two_per_cu_min_channels, seg_os_tiles_max_channels
 
 A cell is a VIOLATION when the default is more than TOL (5 %) slower than an alternative -- after the pair has been measured again (the
@@ -38,7 +38,7 @@ CHAINS = {
 }
 DEFAULTS = {"fir_split_max_channels": 192, "fir_split_max_channels_one_amp": 112, "fir_premac": 1, "seg_two_per_cu_min_channels": 128,
             "seg_os_tiles_max_channels": 192, "seg_reverb_ahead_max_channels": 72, "seg_wave_max_channels": 448, "seg_wave_release_max_channels": 112,
-            "seg_tile_max_channels": 112, "seg_os_tiles_prefix": 1}
+            "seg_tile_max_channels": 112, "seg_os_tiles_prefix": 1, "fir_ahead_min_channels": 128}
 RELEASE_UNITS = {"flanger", "phaser", "delay", "fuzz", "auto_yoy", "auto_wah", "bandpass", "octaver", "noise_gate"}
 
 
@@ -60,6 +60,8 @@ def flips(nch, window, defaults, chain):
         out.append(("fir_split_max_channels", other(split_keys, split_thr, True)))
         if nch <= split_thr:
             out.append(("fir_premac", {"fir_premac": 0 if defaults["fir_premac"] else 1}))
+        else:           # the fused shape: sums made ahead of several frames from fir_ahead_min_channels on
+            out.append(("fir_ahead_min_channels", {"fir_ahead_min_channels": BIG if nch >= defaults["fir_ahead_min_channels"] else 1}))
         taps_parts = None
         out.append(("seg_reverb_ahead_max_channels", None))          # resolved by the caller (needs the plan's premac state)
         out.append(("seg_tile_max_channels", None))                  # resolved by the caller (the launch's workgroup budget)
