@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "gdg_metronome_set_tick", "gdg_metronome_set_tock", "gdg_metronome_configure", "gdg_metronome_process", "gdg_metronome_process_device",
     "gdg_batch_length", "gdg_batch_run", "gdg_batch_run_shard", "gdg_batch_finish_master", "gdg_batch_release", "gdg_profile_sample", "gdg_ctx_set_window", "gdg_process_window_device", "gdg_ctx_set_overlap",
     "gdg_ctx_set_option", "gdg_ctx_get_option", "gdg_option_count", "gdg_option_name", "gdg_numa_probe", "gdg_ctx_trim", "gdg_tuner_replace",
+    "gdg_state_size", "gdg_state_save", "gdg_state_save_device", "gdg_state_load", "gdg_state_load_device",
 ]
 
 
@@ -126,6 +127,11 @@ def lib():
             "gdg_unit_compile_fir": (i32, [vp, i32, i32, vp, vp, vp, vp, u32]),
             "gdg_unit_get_fir": (i32, [vp, i32, vp, i32, C.POINTER(i32)]),
             "gdg_chain_set": (i32, [vp, i32, vp, vp, i32]),
+            "gdg_state_size": (i32, [vp, vp, i32, C.POINTER(C.c_size_t)]),
+            "gdg_state_save": (i32, [vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+            "gdg_state_save_device": (i32, [vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+            "gdg_state_load": (i32, [vp, vp, i32, vp, C.c_size_t]),
+            "gdg_state_load_device": (i32, [vp, vp, i32, vp, C.c_size_t]),
             "gdg_process": (i32, [vp, vp, vp, i32, u32]),
             "gdg_process_subset": (i32, [vp, vp, i32, vp, vp, i32, u32]),
             "gdg_process_device": (i32, [vp, vp, vp, i32, u32]),
@@ -318,6 +324,49 @@ class Context:
         chain = self._chains[channel] + [(h, bypass)]
         self.chain_set(channel, [c[0] for c in chain], [c[1] for c in chain])
         return h
+
+    # -- channel state (gdg_state_*): save / load what the channels carry from one call to the next ---------
+    @staticmethod
+    def _channels(channels):
+        if channels is None:
+            return None, 0
+        n = len(channels)
+        return (C.c_int * max(n, 1))(*channels), n
+
+    def state_size(self, channels=None):
+        chans, n = self._channels(channels)
+        b = C.c_size_t(0)
+        self._check(lib().gdg_state_size(self._h, chans, n, C.byref(b)))
+        return b.value
+
+    def save_state(self, channels=None):
+        """-> bytes: one record per listed channel (None: all), in list order."""
+        chans, n = self._channels(channels)
+        size = self.state_size(channels)
+        buf = C.create_string_buffer(max(size, 1))
+        written = C.c_size_t(0)
+        self._check(lib().gdg_state_save(self._h, chans, n, buf, size, C.byref(written)))
+        return buf.raw[:written.value]
+
+    def load_state(self, blob, channels=None):
+        """Record i of `blob` into channels[i] (None: all channels in order); nothing changes when it is rejected."""
+        chans, n = self._channels(channels)
+        blob = bytes(blob)
+        self._check(lib().gdg_state_load(self._h, chans, n, blob, len(blob)))
+
+    def save_state_device(self, dev, channels=None, capacity=None):
+        """Into a device buffer (a DeviceBuffer or a plain 16-byte-aligned device pointer with `capacity`); -> bytes written."""
+        chans, n = self._channels(channels)
+        ptr = dev.ptr if isinstance(dev, DeviceBuffer) else dev
+        cap = dev.rows * dev.cols * 8 if isinstance(dev, DeviceBuffer) else capacity
+        written = C.c_size_t(0)
+        self._check(lib().gdg_state_save_device(self._h, chans, n, ptr, cap, C.byref(written)))
+        return written.value
+
+    def load_state_device(self, dev, nbytes, channels=None):
+        chans, n = self._channels(channels)
+        ptr = dev.ptr if isinstance(dev, DeviceBuffer) else dev
+        self._check(lib().gdg_state_load_device(self._h, chans, n, ptr, nbytes))
 
     # -- processing --------------------------------------------------------------------------------
     def process(self, x, sample_rate):

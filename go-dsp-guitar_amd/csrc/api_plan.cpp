@@ -401,6 +401,7 @@ int prepare_unit(gdg_ctx *ctx, Unit &u, int frames, uint32_t sample_rate, gdg_se
     if (rc != GDG_OK) return rc;
     d.ds = u.d_ds;
     d.is = u.d_is;
+    u.ran = true;
     return GDG_OK;
 }
 
@@ -535,7 +536,7 @@ static int flush_ir_body(gdg_ctx *ctx, const std::vector<std::shared_ptr<SharedS
  *     line is RE-PARTITIONED: its slots are transformed back to the last (K + 1) hop input samples (raw inverse, ~1e-16), which
  *     are re-cut into frames of the new size and transformed into the new delay line.  Samples older than that only ever meet
  *     zero-padded taps, so the continuation is exact.  Happens once per change, never in the steady state. */
-static int prepare_fir(gdg_ctx *ctx, Unit &u, int hop, uint32_t sample_rate) {
+int prepare_fir(gdg_ctx *ctx, Unit &u, int hop, uint32_t sample_rate) {
     const int P = fir_transform_size(hop);
     if (u.fir_sr != sample_rate) {
         /* poweramp.go:191-203: a sample-rate change recompiles the filter, i.e. fresh state */

@@ -161,7 +161,7 @@ const char *gdg_tuner_note_name(int note_index) { return (note_index >= 0 && not
 #define SPAT_GROUP_DELAY 6.3e-4                   /* spatializer/spatializer.go:23 */
 #define SPAT_DEFAULT_RATE 96000                   /* spatializer.go:20; the delay computation never leaves this rate */
 
-static int ensure_spatializer(gdg_ctx *ctx) {
+int ensure_spatializer(gdg_ctx *ctx) {
     if (ctx->d_sp_hist) return GDG_OK;
     ctx->sp_hist_len = (int)ceil((double)ctx->sp_hist_sr * SPAT_GROUP_DELAY);
     if (ctx->sp_hist_len > 1024)       /* the mix kernel's limit (spat.hip): rates beyond 1.6 MHz */

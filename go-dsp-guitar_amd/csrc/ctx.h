@@ -10,6 +10,7 @@
  *   api_tuner_spat.cpp  tuner and spatializer glue
  *   api_io.cpp          wave codecs, resample.Time, level meters, power-amp compilation, metronome
  *   api_batch.cpp       the batch run (gdg_batch_run, its sharded form, the master mix)
+ *   api_state.cpp       channel state saved into / loaded from a blob (gdg_state_*; the copies: state.hip)
  */
 #ifndef GDG_CTX_H
 #define GDG_CTX_H
@@ -83,6 +84,7 @@ struct Unit {
     long long hist_key = -1;          /* what the current history layout was built for */
     int os_frames[2] = { -1, -1 };    /* frame size the 2x / 4x oversampler last saw */
     int bp_half_order = -1;
+    bool ran = false;                 /* a plan has laid the unit out (prepare_unit): a state save records it, a unit that never ran saves as fresh */
     /* FIR */
     std::vector<double> taps;
     bool fir_dirty = true;
@@ -533,9 +535,11 @@ int meter_rows(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int port0,
 int numa_rebind(gdg_ctx *ctx, int mode);
 int numa_target(const gdg_ctx *ctx, const std::vector<int> **cpus);
 int prepare_unit(gdg_ctx *ctx, Unit &u, int frames, uint32_t sample_rate, gdg_seg_unit &d, int chk = GDG_CHK);
+int prepare_fir(gdg_ctx *ctx, Unit &u, int hop, uint32_t sample_rate);
 int process_rows(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in, double *d_out, int frames, uint32_t sample_rate,
                         int stride = 0, bool rows_by_channel = false, int groups = 1, const GroupHook *before = nullptr, const GroupHook *after = nullptr,
                         int window = 1, int stride_out = 0, const std::vector<size_t> *group_bounds_in = nullptr);
+int ensure_spatializer(gdg_ctx *ctx);
 int spatialize_rows(gdg_ctx *ctx, const double *d_in, int in_stride, double *d_left, int out_stride, int frames);
 int tuner_enqueue_rows(gdg_ctx *ctx, const double *d_samples, size_t stride, int frames, uint32_t sample_rate);
 void copy_rows_parallel(gdg_ctx *ctx, size_t a, size_t b, const std::function<void(size_t)> &copy_row, size_t row_bytes, int which = 0);      /* which: 1 = the upload side's workers */

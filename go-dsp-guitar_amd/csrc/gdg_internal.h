@@ -293,4 +293,10 @@ void gdg_filter_reduce_sizes(int n, unsigned order, size_t *work_points, size_t 
 hipError_t gdg_launch_normalize_scale_add(const double *d_src, int n, double compensation, double level, double *d_partial, double *d_composite,
                                           hipStream_t s);
 
+/* state.hip: channel state saved / loaded (api_state.cpp) -- `bytes` from src to dst for every piece, zeros where src is null.  A piece
+ * occupies ceil(bytes / GDG_STATE_CHUNK) chunks, the first of them d_first[i] (ascending); n_chunks in all, a workgroup each. */
+#define GDG_STATE_CHUNK 16384
+struct gdg_state_piece { const void *src; void *dst; unsigned long long bytes; };
+hipError_t gdg_launch_state_copy(const gdg_state_piece *d_pieces, const unsigned *d_first, int n_pieces, unsigned n_chunks, hipStream_t s);
+
 #endif

@@ -146,6 +146,47 @@ func (this *Context) ChainSet(channel int, handles []int, bypass []bool) error {
 	return this.err(C.gdg_chain_set(this.ctx, C.int(channel), &hs[0], &bs[0], C.int(n)))
 }
 
+// ---- channel state: no reference counterpart (include/gdg.h, gdg_state_*) ----------------------------------------------
+
+// stateChannels: the channel list of a gdg_state_* call (nil = every channel in order, the pointer then stays nil).
+func stateChannels(channels []int) (*C.int, C.int) {
+	if channels == nil {
+		return nil, 0
+	}
+	cs := make([]C.int, len(channels)+1) // one spare element: &cs[0] of an empty list is still valid
+	for i, c := range channels {
+		cs[i] = C.int(c)
+	}
+	return &cs[0], C.int(len(channels))
+}
+
+// SaveState returns what the listed channels (nil: all, in order) carry from one call to the next, one record per channel.  The
+// context is not changed: a stream with saves between its calls gives the same samples.  A runShard that fails can load the last
+// good blob back instead of resetting every unit of the shard.
+func (this *Context) SaveState(channels []int) ([]byte, error) {
+	pc, n := stateChannels(channels)
+	var size C.size_t
+	if err := this.err(C.gdg_state_size(this.ctx, pc, n, &size)); err != nil {
+		return nil, err
+	}
+	buf := make([]byte, int(size)+1)
+	var written C.size_t
+	if err := this.err(C.gdg_state_save(this.ctx, pc, n, unsafe.Pointer(&buf[0]), size, &written)); err != nil {
+		return nil, err
+	}
+	return buf[:int(written)], nil
+}
+
+// LoadState applies record i of blob to channels[i] (nil: every channel in order; the count must be the blob's).  All or
+// nothing: a blob that does not fit the channels' chains is an error and changes nothing.
+func (this *Context) LoadState(channels []int, blob []byte) error {
+	if len(blob) == 0 {
+		return fmt.Errorf("gdg: an empty state blob")
+	}
+	pc, n := stateChannels(channels)
+	return this.err(C.gdg_state_load(this.ctx, pc, n, unsafe.Pointer(&blob[0]), C.size_t(len(blob))))
+}
+
 // Row returns channel c's rows of the pinned staging slabs as Go slices over C memory.  The slab has `channels` rows of
 // `stride` (= max_frames) float64: anything outside is an error, never a slice (a longer slice would run into the next
 // channel's row and, for the last channel, past the hipHostMalloc slab).

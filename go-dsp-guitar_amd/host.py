@@ -41,6 +41,8 @@ def lib():
             "gdgh_engine_batch_run": (cs, [vp, vp, i32, vp, i32, vp, C.POINTER(C.c_size_t)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
+            "gdgh_engine_save_state": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+            "gdgh_engine_load_state": (cs, [vp, vp, C.c_size_t, C.c_uint32]), "gdgh_free": (None, [vp]),
             "gdgh_spatializer_create": (vp, [vp, C.c_uint32]), "gdgh_spatializer_destroy": (None, [vp]),
             "gdgh_spatializer_set": (cs, [vp, i32, C.c_uint32, C.c_double]), "gdgh_spatializer_get": (cs, [vp, i32, C.c_uint32, C.POINTER(C.c_double)]),
             "gdgh_spatializer_input_count": (C.c_uint32, [vp]), "gdgh_spatializer_output_count": (C.c_uint32, [vp]),
@@ -142,6 +144,20 @@ class Engine:
         _err(lib().gdgh_engine_process_all(self._h, ins, outs, x.shape[1], sample_rate))
         return out
 
+
+    def save_state(self):
+        """Engine::SaveState -> bytes (every channel of the engine)"""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        _err(lib().gdgh_engine_save_state(self._h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            lib().gdgh_free(p)
+
+    def load_state(self, blob, sample_rate):
+        """Engine::LoadState: sync every chain at `sample_rate`, then load (the engine may have another shard count than the saver)"""
+        blob = bytes(blob)
+        _err(lib().gdgh_engine_load_state(self._h, blob, len(blob), sample_rate))
 
     def shard_range(self, shard):
         first, count = C.c_int(0), C.c_int(0)

@@ -811,6 +811,85 @@ Error Engine::ProcessAll(const double *const *in, double *const *out, int frames
     return LastError();
 }
 
+/* The engine's state blob: "GDGENGN" + version byte, the channel count, then per channel the byte size of its gdg_state blob, then those
+ * blobs in channel order, each starting on a multiple of 16. */
+static const char kEngineMagic[8] = { 'G', 'D', 'G', 'E', 'N', 'G', 'N', 1 };
+static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+Error Engine::SaveState(std::vector<uint8_t> &blob) {
+    const size_t N = (size_t)nChannels_;
+    std::vector<std::vector<uint8_t>> per(N);
+    for (size_t c = 0; c < N; c++) {
+        int local = 0;
+        const int g = shardOf((int)c, &local);
+        if (g < 0) return format("SaveState: channel %zu has no shard", c);
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        gdg_ctx *ctx = context(g);
+        if (!ctx) return LastError();
+        size_t bytes = 0;
+        if (gdg_state_size(ctx, &local, 1, &bytes) != GDG_OK) return gdg_last_error(ctx);
+        per[c].resize(bytes);
+        size_t written = 0;
+        if (gdg_state_save(ctx, &local, 1, per[c].data(), bytes, &written) != GDG_OK) return gdg_last_error(ctx);
+        per[c].resize(written);
+    }
+    size_t off = round16(16 + 8 * N);
+    blob.assign(off, 0);
+    memcpy(blob.data(), kEngineMagic, 8);
+    const uint32_t n32 = (uint32_t)N;
+    memcpy(blob.data() + 8, &n32, 4);
+    for (size_t c = 0; c < N; c++) {
+        const uint64_t size = per[c].size();
+        memcpy(blob.data() + 16 + 8 * c, &size, 8);
+        blob.resize(off + round16(per[c].size()), 0);
+        memcpy(blob.data() + off, per[c].data(), per[c].size());
+        off += round16(per[c].size());
+    }
+    return "";
+}
+
+Error Engine::LoadState(const uint8_t *blob, size_t bytes, uint32_t sampleRate) {
+    const size_t N = (size_t)nChannels_;
+    if (!blob || bytes < 16 || memcmp(blob, kEngineMagic, 8) != 0) return "LoadState: not an engine state blob";
+    uint32_t n32 = 0;
+    memcpy(&n32, blob + 8, 4);
+    if (n32 != N) return format("LoadState: the blob holds %u channels, the engine has %zu", n32, N);
+    size_t off = round16(16 + 8 * N);
+    if (bytes < off) return "LoadState: the blob is truncated";
+    std::vector<size_t> at(N), size(N);
+    for (size_t c = 0; c < N; c++) {
+        uint64_t s = 0;
+        memcpy(&s, blob + 16 + 8 * c, 8);
+        if (s > bytes || off > bytes - s) return format("LoadState: the blob is truncated (channel %zu)", c);
+        at[c] = off; size[c] = (size_t)s;
+        off += round16((size_t)s);
+    }
+    std::vector<std::shared_ptr<signal::Chain>> chains;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        chains = chains_;
+    }
+    for (int g = 0; g < shards(); g++) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        if (count <= 0) continue;
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        gdg_ctx *ctx = context(g);
+        if (!ctx) return LastError();
+        std::vector<signal::Chain *> mine;
+        for (auto &ch : chains)
+            if (shardOf(ch->channel()) == g) mine.push_back(ch.get());
+        Error e = sync(g, mine, sampleRate);              /* the taps are pushed now: the next sync leaves the loaded convolution alone */
+        if (!e.empty()) return e;
+        for (int c = first; c < first + count; c++) {
+            const int local = c - first;
+            if (gdg_state_load(ctx, &local, 1, blob + at[(size_t)c], size[(size_t)c]) != GDG_OK)
+                return format("LoadState: channel %d: %s", c, gdg_last_error(ctx));
+        }
+    }
+    return "";
+}
+
 Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, void *const *outs, size_t *samples) {
     if (!inputs || !outs) return "BatchRun: no inputs or no outputs";
     if (nInputs != nChannels_) return format("BatchRun: %d inputs for %d channels", nInputs, nChannels_);
@@ -1090,6 +1169,21 @@ void *gdgh_engine_create_sharded(int n_channels, int max_frames, const int *devi
     return new Engine(n_channels, max_frames, std::vector<int>(devices, devices + n_devices));
 }
 int gdgh_engine_shards(void *e) { return ((Engine *)e)->shards(); }
+/* *blob: malloc'ed (gdgh_free) */
+const char *gdgh_engine_save_state(void *e, void **blob, size_t *bytes) {
+    std::vector<uint8_t> b;
+    Error err = ((Engine *)e)->SaveState(b);
+    *blob = nullptr; *bytes = 0;
+    if (!err.empty()) return ret(err);
+    *blob = malloc(b.size() ? b.size() : 1);
+    memcpy(*blob, b.data(), b.size());
+    *bytes = b.size();
+    return nullptr;
+}
+const char *gdgh_engine_load_state(void *e, const void *blob, size_t bytes, uint32_t sr) {
+    return ret(((Engine *)e)->LoadState(static_cast<const uint8_t *>(blob), bytes, sr));
+}
+void gdgh_free(void *p) { free(p); }
 int gdgh_engine_shard_of(void *e, int channel) { return ((Engine *)e)->shardOf(channel); }
 
 /* spatializer.Spatializer */

@@ -206,6 +206,13 @@ public:
      * controller.go:3123-3219).  inputs: one per channel of the engine; outs: N + 3 host buffers as for gdg_batch_run
      * (NULL = "skipping output"); `samples` receives the length of every output. */
     Error BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, void *const *outs, size_t *samples);
+    /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
+     * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
+     * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
+     * (sync: units, parameters, taps, slot lists) and only then loads, so that the next sync finds the taps pushed and leaves the
+     * restored convolution alone.  It is all or nothing per channel; a rejected channel keeps its state and the error names it. */
+    Error SaveState(std::vector<uint8_t> &blob);
+    Error LoadState(const uint8_t *blob, size_t bytes, uint32_t sampleRate);
     std::string LastError() const;
     int channels() const { return nChannels_; }
     int shards() const { return (int)shards_.size(); }

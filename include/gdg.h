@@ -142,7 +142,8 @@ int gdg_ctx_share_ir_spectra(gdg_ctx *ctx, int enable);
  *                                            for its predecessor before the launch gives up: the wait ends, the context's error word is set and the next
  *                                            gdg_ctx_synchronize (or batch run) returns GDG_ERR_HIP -- the device never hangs.  RESULTS OF WINDOW CALLS ARE
  *                                            VALID ONLY AFTER A gdg_ctx_synchronize THAT RETURNED GDG_OK; after such an error the units' state is undefined
- *                                            (gdg_unit_reset them), the context itself stays usable (1000)
+ *                                            (gdg_unit_reset them, or gdg_state_load a state saved before the failed call), the context itself
+ *                                            stays usable (1000)
  *   debug_stall_unit             -1, handle  test hook: in the next windows' first frame this unit withholds its hand-off, so that the bounded wait can
  *                                            be seen to expire (-1)
  *   plan_patch                   0, 1        parameter changes patch the device descriptors in place instead of rebuilding the plan (1)
@@ -229,6 +230,41 @@ int gdg_unit_get_fir(gdg_ctx *ctx, int handle, double *taps, int capacity, int *
  * (signal.go:390-401).  State stays with the unit handle, not with the slot index.
  */
 int gdg_chain_set(gdg_ctx *ctx, int channel, const int *handles, const uint8_t *bypass, int n);
+
+/* ---- channel state: what a channel carries from one call to the next -------------------------------- */
+
+/*
+ * No reference counterpart.  Save the state of some channels into a blob and load it back into the same context (rollback after a failed
+ * call, A/B rendering from one point) or into another one (another channel, another context or device, another channel count, window
+ * or channel-group setting).  `channels` NULL: every channel of the context in order, `n` ignored.  A save writes one record per listed
+ * channel in list order; a load applies record i to channels[i] and `n` must equal the blob's record count.  The _device variants take
+ * a 16-byte-aligned buffer on the context's device (gdg_device_alloc).  Every call returns when the blob is complete or applied.
+ *
+ * State is what a call reads and an earlier call wrote: per unit its small state, FSM words and history ring (delay, chorus, flanger,
+ * phaser, auto-yoy, reverb rings, oversampler histories) with the host's record of their layout; per power amp the overlap-save history,
+ * the newest K delay-line slots in age order and the frame counter; per channel the spatializer's history row.  NOT state, not saved:
+ * parameters and filter taps (they stay with the target's units: a parameter that changes no layout may differ), sums made ahead of the
+ * frame, scan tables, spectra.  Out of scope: the tuner rings (gdg_tuner_replace restores them), meters, the metronome, batch-run buffers.
+ *
+ * A save has no side effects: it is ordered after everything queued on the context and keeps the sums made ahead, so a stream with
+ * saves between its calls gives the same bits as one without.  A load is all or nothing: it lays the target's units out at the blob's
+ * frame size and rate as a process call would, checks every record -- slot count, unit type per slot, ring layout (hist_key / hist_len),
+ * oversampler frame size, band-pass order, the power amp's P / K / frame size / rate -- and only then writes.  A mismatch returns
+ * GDG_ERR_INVALID naming channel, slot, unit type and key in gdg_last_error, and writes nothing.  A loaded delay line is rotated into
+ * the target's ring, so a state saved per frame loads into a context with a window (gdg_ctx_set_window) and the other way round; a later
+ * call at another frame size re-partitions it as usual.  A slot whose unit never ran is recorded as fresh and loads as a reset;
+ * gdg_unit_set_fir after a load still resets.  Bypassed slots carry their state too.  A load drops whatever was summed ahead.
+ *
+ * Format (opaque; stable only within one format version, a blob of another version is rejected): little-endian; a 64-byte header
+ * ("GDGSTATE", version 1, record count, frame size, rate, max_frames, metadata size, total size), per channel a record (slot count,
+ * spatializer row) and its slot table (type, flags, layout keys, frame counter, payload offsets), then the payload at 16-byte alignment.
+ * gdg_state_size gives the bytes a save of the same channels writes; a save into less capacity fails (*written = the size needed).
+ */
+int gdg_state_size(gdg_ctx *ctx, const int *channels, int n, size_t *bytes);
+int gdg_state_save(gdg_ctx *ctx, const int *channels, int n, void *blob, size_t capacity, size_t *written);
+int gdg_state_save_device(gdg_ctx *ctx, const int *channels, int n, void *d_blob, size_t capacity, size_t *written);
+int gdg_state_load(gdg_ctx *ctx, const int *channels, int n, const void *blob, size_t bytes);
+int gdg_state_load_device(gdg_ctx *ctx, const int *channels, int n, const void *d_blob, size_t bytes);
 
 /* ---- processing: signal.Chain.Process for all channels of the shard at once ------------------- */
 
