@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "gdg_resample_time_length", "gdg_resample_time", "gdg_resample_time_device",
     "gdg_meter_configure", "gdg_meter_set_enabled", "gdg_meter_process", "gdg_meter_process_device", "gdg_meter_analyze", "gdg_meter_state",
     "gdg_metronome_set_tick", "gdg_metronome_set_tock", "gdg_metronome_configure", "gdg_metronome_process", "gdg_metronome_process_device",
-    "gdg_batch_length", "gdg_batch_run", "gdg_batch_run_shard", "gdg_batch_finish_master", "gdg_batch_release", "gdg_profile_sample", "gdg_ctx_set_window", "gdg_process_window_device", "gdg_ctx_set_overlap",
+    "gdg_batch_length", "gdg_batch_run", "gdg_batch_run_shard", "gdg_batch_finish_master", "gdg_batch_release", "gdg_batch_stream_span", "gdg_batch_stream_open", "gdg_batch_stream_need", "gdg_batch_stream_step", "gdg_batch_stream_close", "gdg_profile_sample", "gdg_ctx_set_window", "gdg_process_window_device", "gdg_ctx_set_overlap",
     "gdg_ctx_set_option", "gdg_ctx_get_option", "gdg_option_count", "gdg_option_name", "gdg_numa_probe", "gdg_ctx_trim", "gdg_tuner_replace",
     "gdg_state_size", "gdg_state_save", "gdg_state_save_device", "gdg_state_load", "gdg_state_load_device",
 ]
@@ -61,6 +61,16 @@ def numa_probe(sysfs_root, pci_bus_id, capacity=4096):
     if rc != GDG_OK:
         raise GdgError(rc, "gdg_numa_probe")
     return int(node.value), [int(cpus[i]) for i in range(min(capacity, n.value))]
+
+
+def batch_stream_span(samples_per_channel, source_rate, target_rate, out_first, out_count):
+    """(first, count): the source frames of an input that the job's output samples [out_first, out_first + out_count) read
+    (gdg_batch_stream_span; pure arithmetic, no device needed)."""
+    first, count = C.c_size_t(0), C.c_size_t(0)
+    rc = lib().gdg_batch_stream_span(samples_per_channel, source_rate, target_rate, out_first, out_count, C.byref(first), C.byref(count))
+    if rc != GDG_OK:
+        raise GdgError(rc, "gdg_batch_stream_span")
+    return first.value, count.value
 
 
 class GdgError(RuntimeError):
@@ -184,6 +194,11 @@ def lib():
             "gdg_batch_release": (i32, [vp]),
             "gdg_batch_run_shard": (i32, [vp, vp, i32, vp, vp, vp]),
             "gdg_batch_finish_master": (i32, [vp, i32, vp, vp, i32, vp, C.c_size_t, u32, i32, vp, vp]),
+            "gdg_batch_stream_span": (i32, [C.c_size_t, u32, u32, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+            "gdg_batch_stream_open": (i32, [vp, vp, i32, vp, C.POINTER(C.c_size_t)]),
+            "gdg_batch_stream_need": (i32, [vp, i32, vp, vp]),
+            "gdg_batch_stream_step": (i32, [vp, i32, vp, vp]),
+            "gdg_batch_stream_close": (i32, [vp]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
             "gdg_ctx_get_option": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -714,6 +729,80 @@ class Context:
         self._check(lib().gdg_batch_finish_master(self._h, fo, lp, rp, G, a.ctypes.data if a is not None else None, n, sample_rate,
                                                   int(bool(run_meters)), ml.ctypes.data if n else None, mr.ctypes.data if n else None))
         return ml, mr
+
+    # -- the streamed batch run: the job of batch_run in slices of whole blocks (gdg_batch_stream_*) --------------------------
+    def batch_stream_open(self, inputs, target_rate, out_format, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
+        """inputs: per channel None or (samples_per_channel of the FILE, format, sample_rate[, channels, channel]); returns the samples of
+        every output."""
+        n = len(inputs)
+        arr = (BatchInput * n)()
+        for i, it in enumerate(inputs):
+            if it is None or not it[0]:
+                continue
+            channels, channel = (it[3], it[4]) if len(it) > 3 else (1, 0)
+            f = WAVE_FORMATS[it[1]] if isinstance(it[1], str) else it[1]
+            arr[i] = BatchInput(C.addressof(arr), int(it[0]), f, it[2], channels, channel)      # bytes: never read, only "not NULL"
+        fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
+        opt = BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
+        length = C.c_size_t(0)
+        self._check(lib().gdg_batch_stream_open(self._h, arr, n, C.byref(opt), C.byref(length)))
+        self._stream_width = lib().gdg_wave_bytes_per_sample(fo)
+        return length.value
+
+    def batch_stream_need(self, blocks):
+        """[(first, count)] per input: the source frames the next slice of `blocks` blocks must bring."""
+        n = self.n_channels
+        first, count = (C.c_size_t * n)(), (C.c_size_t * n)()
+        self._check(lib().gdg_batch_stream_need(self._h, blocks, first, count))
+        return [(first[i], count[i]) for i in range(n)]
+
+    def batch_stream_step(self, blocks, in_bytes, outs=None):
+        """One slice: in_bytes[i] = the interleaved frames batch_stream_need asked for (bytes-like or None); returns the N + 3 output
+        pieces of blocks * 8192 samples each (uint8 arrays)."""
+        n = self.n_channels
+        keep = [None if b is None else np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b, dtype=np.uint8)
+                for b in in_bytes]
+        assert len(keep) == n
+        ins = (C.c_void_p * n)(*[(b.ctypes.data if b is not None and b.size else None) for b in keep])
+        size = blocks * 8192 * self._stream_width
+        if outs is None:
+            outs = [np.zeros(size, dtype=np.uint8) for _ in range(n + 3)]
+        assert len(outs) == n + 3 and all(o is None or (o.dtype == np.uint8 and o.size == size) for o in outs)
+        ptrs = (C.c_void_p * (n + 3))(*[(o.ctypes.data if o is not None else None) for o in outs])
+        self._check(lib().gdg_batch_stream_step(self._h, blocks, ins, ptrs))
+        return outs
+
+    def batch_stream_close(self):
+        self._check(lib().gdg_batch_stream_close(self._h))
+
+    def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
+        """batch_run as a generator: the same `inputs` tuples (whole data sections; a real host would read each slice's frames from its
+        files instead), cut into slices of `blocks_per_slice` blocks (an int, or a function (blocks_left) -> blocks).  Yields every
+        slice's N + 3 output pieces; their concatenation is batch_run's result."""
+        metas, datas, widths = [], [], []
+        for it in inputs:
+            if it is None:
+                metas.append(None), datas.append(None), widths.append(0)
+                continue
+            data = np.ascontiguousarray(it[0], dtype=np.uint8)
+            f = WAVE_FORMATS[it[1]] if isinstance(it[1], str) else it[1]
+            channels = it[3] if len(it) > 3 else 1
+            w = max(lib().gdg_wave_bytes_per_sample(f), 1) * max(channels, 1)
+            metas.append((data.size // w,) + tuple(it[1:])), datas.append(data), widths.append(w)
+        length = self.batch_stream_open(metas, target_rate, out_format, metronome_to_master, run_meters, tuner_enqueue)
+        try:
+            left = length // 8192
+            while left:
+                blocks = min(left, blocks_per_slice(left) if callable(blocks_per_slice) else blocks_per_slice)
+                need = self.batch_stream_need(blocks)
+                ins = [None if d is None or not c else d[f * w:(f + c) * w] for d, w, (f, c) in zip(datas, widths, need)]
+                yield self.batch_stream_step(blocks, ins)
+                left -= blocks
+        finally:
+            try:
+                self.batch_stream_close()
+            except GdgError:
+                pass                            # a slice that failed has closed the job itself
 
     def batch_release(self):
         self._check(lib().gdg_batch_release(self._h))

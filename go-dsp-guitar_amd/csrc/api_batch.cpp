@@ -1,5 +1,6 @@
 /*
- * api_batch.cpp -- controller.processFiles on the device: gdg_batch_run, its sharded form and the master mix.
+ * api_batch.cpp -- controller.processFiles on the device: gdg_batch_run, its streamed form (slices of whole blocks), its sharded form
+ * and the master mix.
  * Part of the host side of libgdg.so (the C-ABI of include/gdg.h on top of the HIP kernels; see ctx.h for the map).
  * There is no CPU compute path here: every sample is produced by a HIP kernel.
  */
@@ -41,6 +42,7 @@ static int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out) {
 
 int gdg_batch_release(gdg_ctx *ctx) {
     if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is open on this context: its buffers are in use");
     enter(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < 6; i++) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
@@ -89,6 +91,252 @@ static void move_pieces(gdg_ctx *ctx, const std::vector<BatchPiece> &pieces, int
                        pieces.empty() ? 0 : total / pieces.size(), which);
 }
 
+/* ---- the block loop of a batch run, shared by the one-call run and the streamed run's slices ---------------------------------------- */
+struct BatchLoop {
+    int N, enc_rows, f64_rows, out_width, W;
+    size_t length;                              /* samples of every row of d_inputs = the samples this loop walks */
+    size_t ws, enc_bytes;
+    double *d_inputs, *d_win;
+    unsigned char *d_enc;
+    const gdg_batch_options *opt;
+    void *const *out_bytes;
+    const gdg_batch_shard_out *shard;
+    bool run_metro, n_streamed;                 /* n_streamed: some inputs come with their step (stage) */
+    int trace;
+    double t_begin;
+    size_t job_blocks, origin_blocks;           /* a slice of a streamed job of job_blocks blocks that starts at block origin_blocks; 0, 0: a whole job */
+};
+
+/* the step [first, first + w) of the one-call run of a job of `job` blocks in windows of W that holds block p (the steps batch_block_loop
+ * makes for a whole job, in closed form) */
+static void one_call_step(size_t job, int W, size_t p, size_t *first, int *w) {
+    const size_t head = (W >= 8 && job >= (size_t)3 * W) ? (size_t)(W / 4 + W / 2) : 0;
+    if (head && p < (size_t)(W / 4)) { *first = 0; *w = W / 4; return; }
+    if (head && p < head) { *first = (size_t)(W / 4); *w = W / 2; return; }
+    const size_t full = (job - head) / (size_t)W * (size_t)W;
+    if (p - head < full) { *first = head + (p - head) / (size_t)W * (size_t)W; *w = W; return; }
+    size_t off = head + full;
+    int k = W;
+    for (;;) {
+        while ((size_t)k > job - off) k >>= 1;
+        if (p < off + (size_t)k || k <= 1) { *first = off; *w = k; return; }
+        off += (size_t)k;
+    }
+}
+/* the inputs of step i (samples [off, off + w * 8192) of the loop) go up: gathered into a pinned half, moved and decoded on the upload stream */
+typedef std::function<int(size_t i, size_t off, int w, int pool)> BatchStage;
+
+static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &stage_fn) {
+    const int N = p.N, NO = N + 3, B = GDG_BLOCK_SIZE, enc_rows = p.enc_rows, f64_rows = p.f64_rows, out_width = p.out_width, W = p.W;
+    const size_t length = p.length, ws = p.ws, enc_bytes = p.enc_bytes;
+    double *const d_inputs = p.d_inputs, *const d_win = p.d_win;
+    unsigned char *const d_enc = p.d_enc;
+    const gdg_batch_options *opt = p.opt;
+    void *const *out_bytes = p.out_bytes;
+    const gdg_batch_shard_out *shard = p.shard;
+    const bool sharded = shard != nullptr, run_metro = p.run_metro, n_streamed = p.n_streamed;
+    const int trace = p.trace;
+    const double t_begin = p.t_begin;
+    auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    int r;
+    /* 2. the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
+    if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
+    struct Step { size_t off; int w; };
+    std::vector<Step> steps;
+    /* A long run opens with a quarter window and a half window: the device has nothing to do until the first step's bytes are gathered and uploaded (16 blocks
+     * of 512 files: 1.9 + 2.4 ms), and what it computes first comes down and is scattered while nothing else waits for the host.  The blocks
+     * that step leaves over make the tail shorter the same way (W/2, W/4: the last download and scatter are a quarter step's).  Window sizes
+     * only change the time blocking, never a sample (tests/test_gpu_window.py). */
+    size_t off0 = 0;
+    if (p.job_blocks) {
+        /* a slice of a streamed job steps where the one-call run of the whole job would: a step ends where that run's step ends (or the
+         * slice does), so that the windows -- and with them what the units keep beyond the samples, the convolution's two history
+         * halves -- are the one-call run's wherever the slicing allows it */
+        for (size_t off = 0; off < length;) {
+            const size_t at = p.origin_blocks + off / B, end = p.origin_blocks + length / B;
+            size_t first = 0;
+            int w1 = 1, w = 1;
+            one_call_step(p.job_blocks, W, at, &first, &w1);
+            const size_t room = std::min(first + (size_t)w1, end) - at;
+            while ((size_t)w * 2 <= room) w *= 2;
+            steps.push_back({ off, w });
+            off += (size_t)w * B;
+        }
+        off0 = length;
+    } else if (W >= 8 && length >= (size_t)3 * W * B) {                             /* W/4, W/2, then whole windows: each step's upload fits behind the step before */
+        steps.push_back({ 0, W / 4 });
+        steps.push_back({ (size_t)(W / 4) * B, W / 2 });
+        off0 = (size_t)(W / 4 + W / 2) * B;
+    }
+    for (size_t off = off0; off < length;) {
+        int w = W;
+        while ((size_t)w * B > length - off) w >>= 1;                        /* the tail: windows of W/2, W/4 .. 1 */
+        steps.push_back({ off, w });
+        off += (size_t)w * B;
+    }
+    /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
+     * scatter of piece c runs while piece c + 1 is on the bus -- the run's tail (last download, then last scatter) and its head are that
+     * much shorter; in between the device sets the pace either way. */
+    auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
+    auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
+    auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
+        const unsigned char *src = ctx->h_batch[i & 1];
+        const size_t wb = (size_t)steps[i].w * B, row_bytes = wb * out_width, at = steps[i].off * out_width;
+        const size_t f64_at = ((size_t)enc_rows * row_bytes + 15) & ~(size_t)15;
+        const int K = chunks_of(i);
+        for (int c = 0; c < K; c++) {
+            HIP_TRY(ctx, hipEventSynchronize(ctx->batch_chunk[i & 1][c]));    /* piece c has landed */
+            const size_t o0 = chunk_rows(i, c), o1 = (c + 1 == K) ? (size_t)enc_rows + (size_t)f64_rows : chunk_rows(i, c + 1);
+            copy_rows_parallel(ctx, o0, o1, [&](size_t o) {
+                if (o < (size_t)enc_rows) {
+                    /* NULL: "skipping output" (:3143); a shard's row N is the metronome track */
+                    void *dst = (sharded && o == (size_t)N) ? shard->metronome_bytes : out_bytes[o];
+                    if (dst) memcpy(static_cast<unsigned char *>(dst) + at, src + o * row_bytes, row_bytes);
+                } else {
+                    const size_t k = o - (size_t)enc_rows;
+                    double *dst = k == 0 ? shard->master_left : (k == 1 ? shard->master_right : shard->metronome);
+                    memcpy(dst + steps[i].off, src + f64_at + k * wb * sizeof(double), wb * sizeof(double));
+                }
+            }, row_bytes);
+        }
+        return GDG_OK;
+    };
+    HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed, whole-file inputs decoded */
+    if (n_streamed) HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_up_stream, ctx->batch_begin, 0));
+    auto stage = [&](size_t i, int pool = 0) -> int {
+        if (!n_streamed || i >= steps.size()) return GDG_OK;
+        return stage_fn(i, steps[i].off, steps[i].w, pool);
+    };
+    /* step i on the compute stream: the block loop's work for its w blocks, then the encoder into the step's half of `enc` */
+    auto enqueue_compute = [&](size_t i) -> int {
+        const size_t off = steps[i].off;
+        const int w = steps[i].w, h = (int)(i & 1), wb = w * B;               /* this step fills the first wb samples of the window's rows */
+        if (n_streamed) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_up_ready[h], 0));
+        const double *d_in = d_inputs + off;
+        double *d_master = d_win + (size_t)N * ws, *d_metro = d_master + 2 * ws;
+        unsigned char *enc = d_enc + h * enc_bytes;
+        if (opt->tuner_enqueue)
+            for (int j = 0; j < w; j++) if ((r = tuner_enqueue_rows(ctx, d_in + (size_t)j * B, length, B, opt->target_rate)) != GDG_OK) return r;
+        if ((r = process_rows(ctx, ctx->all_channels, d_in, d_win, B, opt->target_rate, (int)length, false, 1, nullptr, nullptr, w, (int)ws)) != GDG_OK) return r;
+        if (run_metro && (r = gdg_metronome_process_device(ctx, d_metro, wb)) != GDG_OK) return r;
+        /* the step's w frames are consecutive in their rows: ONE mix over w x 8192 samples gives the samples of w calls (a frame's first
+         * samples find their delayed neighbours in the frame before instead of in the history, which holds the same values) */
+        if ((r = spatialize_rows(ctx, d_win, (int)ws, d_master, (int)ws, wb)) != GDG_OK) return r;
+        /* a shard's master rows stay partial sums: the aux input is added once, after the shards' sums (gdg_batch_finish_master) */
+        if (opt->metronome_to_master && !sharded) HIP_TRY(ctx, gdg_launch_add_aux(d_master, d_master + ws, d_metro, wb, ctx->stream));
+        if (opt->run_meters) {                                               /* ports: inputs | outputs | metronome | left, right (:2707-2777) */
+            if ((r = meter_rows(ctx, d_in, length, 0, N, wb, opt->target_rate)) != GDG_OK) return r;
+            if ((r = meter_rows(ctx, d_win, ws, N, N, wb, opt->target_rate)) != GDG_OK) return r;
+            if (run_metro && (r = meter_rows(ctx, d_metro, ws, 2 * N, 1, wb, opt->target_rate)) != GDG_OK) return r;
+            if (!sharded && (r = meter_rows(ctx, d_master, ws, 2 * N + 1, 2, wb, opt->target_rate)) != GDG_OK) return r;     /* a shard's master ports: gdg_batch_finish_master */
+        }
+        if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_moved[h], 0));     /* step i - 2 has left enc */
+        {
+            ProfScope ps(ctx, GDG_K_WAVE);
+            const size_t row_bytes = (size_t)wb * out_width;
+            if (!sharded) HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)NO, enc, ctx->stream));
+            else {
+                HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)N, enc, ctx->stream));
+                if (shard->metronome_bytes)
+                    HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_metro, ws, (size_t)wb, 1u, enc + (size_t)N * row_bytes, ctx->stream));
+                unsigned char *f64 = enc + (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15);
+                HIP_TRY(ctx, hipMemcpy2DAsync(f64, (size_t)wb * sizeof(double), d_master, ws * sizeof(double), (size_t)wb * sizeof(double), 2,
+                                              hipMemcpyDeviceToDevice, ctx->stream));
+                if (shard->metronome)
+                    HIP_TRY(ctx, hipMemcpyAsync(f64 + 2 * (size_t)wb * sizeof(double), d_metro, (size_t)wb * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+            }
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->batch_ready[h], ctx->stream));
+        return GDG_OK;
+    };
+    /* ... and its way down on the download stream, into the step's pinned half (which step i - 2 must have left: scatter(i - 2) is done) */
+    auto enqueue_down = [&](size_t i) -> int {
+        const int h = (int)(i & 1), wb = steps[i].w * B;
+        unsigned char *enc = d_enc + h * enc_bytes;
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
+        const size_t row_bytes = (size_t)wb * out_width;
+        const size_t down = sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NO * row_bytes;
+        const int K = chunks_of(i);
+        for (int c = 0; c < K; c++) {
+            const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
+            if (b1 > b0) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_batch[h] + b0, enc + b0, b1 - b0, hipMemcpyDeviceToHost, ctx->batch_stream));
+            HIP_TRY(ctx, hipEventRecord(ctx->batch_chunk[h][c], ctx->batch_stream));
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->batch_moved[h], ctx->batch_stream));
+        return GDG_OK;
+    };
+    /* The compute stream is kept TWO steps ahead of the files.  Round 2 enqueued step i + 1 only after step i - 1 had been scattered into
+     * the caller's buffers, which closed a loop of compute -> download -> scatter over two steps: (5.7 + 4.0 + 3.1) / 2 = 6.4 ms per step
+     * of 16 blocks where the device needs 5.7 (GDG_BATCH_TRACE).  Now step i + 2 is enqueued as soon as step i's download has finished (before
+     * its bytes are scattered), while step i + 1 is already queued behind step i on the device. */
+    if (trace) fprintf(stderr, "[batch] set-up %.2f ms\n", now_ms() - t_begin);
+    /* Gathering step i + 2's input bytes (1.9 ms of 16 blocks x 512 files) and scattering step i's output bytes (3.0 ms) were one thread's
+     * work, one after the other: 4.8 ms per step beside the device's 4.7 -- the host set the pace half of the time.  With windows of four
+     * blocks or more the gather runs on a helper thread with copy workers of its own (copy_pool_up), one step further ahead (step i + 3 while
+     * step i is scattered; its pinned half and its device half were step i + 1's, whose upload and decode are long done -- stage() waits
+     * for their event): the host's step is the scatter alone and the device sets the pace. */
+    const bool helper = n_streamed && ws >= (size_t)4 * B && steps.size() > 3;
+    std::future<int> staged;
+    struct Join { std::future<int> &f; ~Join() { if (f.valid()) f.wait(); } } join_on_exit{ staged };     /* stage() captures this frame by reference */
+    /* the upload side's copy workers are made HERE, by the caller's thread, and the helper thread goes where they go: with option "numa" = 2
+     * workers are bound to the node of the thread that makes them, and a helper the scheduler happened to start on the other socket would
+     * put the gather's workers a socket away from the caller's buffers and the pinned halves */
+    const std::vector<int> *helper_cpus = nullptr;
+    if (helper) { ensure_copy_pool(ctx, 1); numa_target(ctx, &helper_cpus); }
+    auto on_helper = [&](size_t first, size_t last) {                        /* stage(first .. last), one after the other, on the helper thread */
+        if (first >= steps.size()) return;
+        try {
+            staged = std::async(std::launch::async, [&, first, last]() -> int {
+                if (helper_cpus) numa_bind_thread(*helper_cpus);
+                if (hipSetDevice(ctx->device) != hipSuccess) return GDG_ERR_HIP;
+                for (size_t k = first; k <= last && k < steps.size(); k++) { const int rr = stage(k, 1); if (rr != GDG_OK) return rr; }
+                return GDG_OK;
+            });
+        } catch (...) {                                                    /* no thread to be had: gather here, as the short runs do */
+            int rr = GDG_OK;
+            for (size_t k = first; k <= last && k < steps.size() && rr == GDG_OK; k++) rr = stage(k, 0);
+            std::promise<int> done;
+            done.set_value(rr);
+            staged = done.get_future();
+        }
+    };
+    auto stage_async = [&](size_t i) { on_helper(i, i); };
+    if (helper) {
+        /* the head: step 0 is gathered here; steps 1 and 2 on the helper meanwhile, so that the first whole window's bytes are on the bus
+         * while the quarter and the half window compute */
+        if ((r = stage(0)) != GDG_OK) return r;
+        on_helper(1, 2);
+        if ((r = enqueue_compute(0)) != GDG_OK || (r = enqueue_down(0)) != GDG_OK) return r;
+        if ((r = staged.get()) != GDG_OK) return r;
+        if ((r = enqueue_compute(1)) != GDG_OK || (r = enqueue_down(1)) != GDG_OK) return r;
+    } else {
+        for (size_t i = 0; i < 2 && i < steps.size(); i++) {
+            if ((r = stage(i)) != GDG_OK) return r;
+            if ((r = enqueue_compute(i)) != GDG_OK || (r = enqueue_down(i)) != GDG_OK) return r;
+        }
+    }
+    if (trace) fprintf(stderr, "[batch] steps 0 and 1 staged and enqueued at %.2f ms\n", now_ms() - t_begin);
+    for (size_t i = 0; i < steps.size(); i++) {
+        const double t_it = now_ms();
+        if (helper) {
+            if (staged.valid() && (r = staged.get()) != GDG_OK) return r;     /* step i + 2's inputs are on their way up (i = 0: since the head) */
+            stage_async(i + 3);
+        } else if ((r = stage(i + 2)) != GDG_OK) return r;                   /* while steps i, i + 1 run: the inputs of step i + 2 go up ... */
+        const double t_st = now_ms();
+        const double t_wait = t_st;
+        /* step i + 2 needs step i's half of `enc` (the compute stream waits for its download itself) but not its pinned half: it goes onto
+         * the compute stream BEFORE the scatter, so the loop compute -> download -> compute spans 5.7 + 4.0 ms per two steps and the device,
+         * not the host, sets the pace */
+        if (i + 2 < steps.size() && (r = enqueue_compute(i + 2)) != GDG_OK) return r;
+        const double t_enq = now_ms();
+        if ((r = scatter(i)) != GDG_OK) return r;                            /* ... step i comes down and goes into the files, piece by piece */
+        if (i + 2 < steps.size() && (r = enqueue_down(i + 2)) != GDG_OK) return r;     /* its pinned half is free again */
+        if (trace) fprintf(stderr, "[batch] step %zu: stage %zu %.2f | (%.2f) | enqueue %zu %.2f | download + scatter %.2f  (at %.2f ms)\n", i, i + 2,
+                           t_st - t_it, t_wait - t_st, i + 2, t_enq - t_wait, now_ms() - t_enq, now_ms() - t_begin);
+    }
+    return check_device_error(ctx);
+}
+
 /*
  * Phases (all device work on the context's stream; PCIe on the copy stream through two pinned halves):
  *   1. the file bytes of all inputs, packed into one arena, go up in half-sized chunks: the copy threads gather chunk k + 1 while
@@ -100,6 +348,7 @@ static void move_pieces(gdg_ctx *ctx, const std::vector<BatchPiece> &pieces, int
 static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes,
                           const gdg_batch_shard_out *shard) {
     if (!ctx || !inputs || !opt || !out_bytes) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is open on this context: gdg_batch_stream_close it first");
     if (n_inputs != ctx->nch) return fail(ctx, GDG_ERR_INVALID, "the batch has %d inputs, the context %d channels", n_inputs, ctx->nch);
     if (ctx->max_frames < GDG_BLOCK_SIZE)
         return fail(ctx, GDG_ERR_INVALID, "the batch loop runs blocks of %d frames, the context allows %d", GDG_BLOCK_SIZE, ctx->max_frames);
@@ -239,60 +488,10 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
         /* the pinned halves change direction: every upload has been consumed by the DMA engine (events above), nothing else reads them */
         for (int h = 0; h < 2; h++) if (used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_moved[h]));
 
-        /* 2. the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
-        if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-        struct Step { size_t off; int w; };
-        std::vector<Step> steps;
-        /* A long run opens with a quarter window and a half window: the device has nothing to do until the first step's bytes are gathered and uploaded (16 blocks
-         * of 512 files: 1.9 + 2.4 ms), and what it computes first comes down and is scattered while nothing else waits for the host.  The blocks
-         * that step leaves over make the tail shorter the same way (W/2, W/4: the last download and scatter are a quarter step's).  Window sizes
-         * only change the time blocking, never a sample (tests/test_gpu_window.py). */
-        size_t off0 = 0;
-        if (W >= 8 && length >= (size_t)3 * W * B) {                             /* W/4, W/2, then whole windows: each step's upload fits behind the step before */
-            steps.push_back({ 0, W / 4 });
-            steps.push_back({ (size_t)(W / 4) * B, W / 2 });
-            off0 = (size_t)(W / 4 + W / 2) * B;
-        }
-        for (size_t off = off0; off < length;) {
-            int w = W;
-            while ((size_t)w * B > length - off) w >>= 1;                        /* the tail: windows of W/2, W/4 .. 1 */
-            steps.push_back({ off, w });
-            off += (size_t)w * B;
-        }
-        /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
-         * scatter of piece c runs while piece c + 1 is on the bus -- the run's tail (last download, then last scatter) and its head are that
-         * much shorter; in between the device sets the pace either way. */
-        auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
-        auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
-        auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
-            const unsigned char *src = ctx->h_batch[i & 1];
-            const size_t wb = (size_t)steps[i].w * B, row_bytes = wb * out_width, at = steps[i].off * out_width;
-            const size_t f64_at = ((size_t)enc_rows * row_bytes + 15) & ~(size_t)15;
-            const int K = chunks_of(i);
-            for (int c = 0; c < K; c++) {
-                HIP_TRY(ctx, hipEventSynchronize(ctx->batch_chunk[i & 1][c]));    /* piece c has landed */
-                const size_t o0 = chunk_rows(i, c), o1 = (c + 1 == K) ? (size_t)enc_rows + (size_t)f64_rows : chunk_rows(i, c + 1);
-                copy_rows_parallel(ctx, o0, o1, [&](size_t o) {
-                    if (o < (size_t)enc_rows) {
-                        /* NULL: "skipping output" (:3143); a shard's row N is the metronome track */
-                        void *dst = (sharded && o == (size_t)N) ? shard->metronome_bytes : out_bytes[o];
-                        if (dst) memcpy(static_cast<unsigned char *>(dst) + at, src + o * row_bytes, row_bytes);
-                    } else {
-                        const size_t k = o - (size_t)enc_rows;
-                        double *dst = k == 0 ? shard->master_left : (k == 1 ? shard->master_right : shard->metronome);
-                        memcpy(dst + steps[i].off, src + f64_at + k * wb * sizeof(double), wb * sizeof(double));
-                    }
-                }, row_bytes);
-            }
-            return GDG_OK;
-        };
         /* the streamed inputs of step i: gathered into a pinned half by the copy threads, moved and decoded on the upload stream while
          * the block loop is busy with the steps before */
-        HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed, whole-file inputs decoded */
-        if (n_streamed) HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_up_stream, ctx->batch_begin, 0));
         int up_used[2] = { 0, 0 };
-        auto stage = [&](size_t i, int pool = 0) -> int {                        /* pool 1: from the helper thread, with the upload side's copy workers */
-            if (!n_streamed || i >= steps.size()) return GDG_OK;
+        BatchStage stage = [&](size_t i, size_t a, int w, int pool) -> int {      /* pool 1: from the helper thread, with the upload side's copy workers */
             const int h = (int)(i & 1);
             if (up_used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_up_ready[h]));     /* step i - 2 has left this half */
             unsigned char *hb = ctx->h_up[h], *db = d_up + (size_t)h * up_half;
@@ -301,7 +500,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
             size_t cur = up_rows_bytes;
             int n_rows = 0;
             unsigned max_count = 0;
-            const size_t a = steps[i].off, span = (size_t)steps[i].w * B;
+            const size_t span = (size_t)w * B;
             for (int c = 0; c < N; c++) {
                 if (!streamed[(size_t)c]) continue;
                 const gdg_batch_input &in = inputs[c];
@@ -323,134 +522,9 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
             HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
             return GDG_OK;
         };
-        /* step i on the compute stream: the block loop's work for its w blocks, then the encoder into the step's half of `enc` */
-        auto enqueue_compute = [&](size_t i) -> int {
-            const size_t off = steps[i].off;
-            const int w = steps[i].w, h = (int)(i & 1), wb = w * B;               /* this step fills the first wb samples of the window's rows */
-            if (n_streamed) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_up_ready[h], 0));
-            const double *d_in = d_inputs + off;
-            double *d_master = d_win + (size_t)N * ws, *d_metro = d_master + 2 * ws;
-            unsigned char *enc = d_enc + h * enc_bytes;
-            if (opt->tuner_enqueue)
-                for (int j = 0; j < w; j++) if ((r = tuner_enqueue_rows(ctx, d_in + (size_t)j * B, length, B, opt->target_rate)) != GDG_OK) return r;
-            if ((r = process_rows(ctx, ctx->all_channels, d_in, d_win, B, opt->target_rate, (int)length, false, 1, nullptr, nullptr, w, (int)ws)) != GDG_OK) return r;
-            if (run_metro && (r = gdg_metronome_process_device(ctx, d_metro, wb)) != GDG_OK) return r;
-            /* the step's w frames are consecutive in their rows: ONE mix over w x 8192 samples gives the samples of w calls (a frame's first
-             * samples find their delayed neighbours in the frame before instead of in the history, which holds the same values) */
-            if ((r = spatialize_rows(ctx, d_win, (int)ws, d_master, (int)ws, wb)) != GDG_OK) return r;
-            /* a shard's master rows stay partial sums: the aux input is added once, after the shards' sums (gdg_batch_finish_master) */
-            if (opt->metronome_to_master && !sharded) HIP_TRY(ctx, gdg_launch_add_aux(d_master, d_master + ws, d_metro, wb, ctx->stream));
-            if (opt->run_meters) {                                               /* ports: inputs | outputs | metronome | left, right (:2707-2777) */
-                if ((r = meter_rows(ctx, d_in, length, 0, N, wb, opt->target_rate)) != GDG_OK) return r;
-                if ((r = meter_rows(ctx, d_win, ws, N, N, wb, opt->target_rate)) != GDG_OK) return r;
-                if (run_metro && (r = meter_rows(ctx, d_metro, ws, 2 * N, 1, wb, opt->target_rate)) != GDG_OK) return r;
-                if (!sharded && (r = meter_rows(ctx, d_master, ws, 2 * N + 1, 2, wb, opt->target_rate)) != GDG_OK) return r;     /* a shard's master ports: gdg_batch_finish_master */
-            }
-            if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_moved[h], 0));     /* step i - 2 has left enc */
-            {
-                ProfScope ps(ctx, GDG_K_WAVE);
-                const size_t row_bytes = (size_t)wb * out_width;
-                if (!sharded) HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)NO, enc, ctx->stream));
-                else {
-                    HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)N, enc, ctx->stream));
-                    if (shard->metronome_bytes)
-                        HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_metro, ws, (size_t)wb, 1u, enc + (size_t)N * row_bytes, ctx->stream));
-                    unsigned char *f64 = enc + (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15);
-                    HIP_TRY(ctx, hipMemcpy2DAsync(f64, (size_t)wb * sizeof(double), d_master, ws * sizeof(double), (size_t)wb * sizeof(double), 2,
-                                                  hipMemcpyDeviceToDevice, ctx->stream));
-                    if (shard->metronome)
-                        HIP_TRY(ctx, hipMemcpyAsync(f64 + 2 * (size_t)wb * sizeof(double), d_metro, (size_t)wb * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                }
-            }
-            HIP_TRY(ctx, hipEventRecord(ctx->batch_ready[h], ctx->stream));
-            return GDG_OK;
-        };
-        /* ... and its way down on the download stream, into the step's pinned half (which step i - 2 must have left: scatter(i - 2) is done) */
-        auto enqueue_down = [&](size_t i) -> int {
-            const int h = (int)(i & 1), wb = steps[i].w * B;
-            unsigned char *enc = d_enc + h * enc_bytes;
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
-            const size_t row_bytes = (size_t)wb * out_width;
-            const size_t down = sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NO * row_bytes;
-            const int K = chunks_of(i);
-            for (int c = 0; c < K; c++) {
-                const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
-                if (b1 > b0) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_batch[h] + b0, enc + b0, b1 - b0, hipMemcpyDeviceToHost, ctx->batch_stream));
-                HIP_TRY(ctx, hipEventRecord(ctx->batch_chunk[h][c], ctx->batch_stream));
-            }
-            HIP_TRY(ctx, hipEventRecord(ctx->batch_moved[h], ctx->batch_stream));
-            return GDG_OK;
-        };
-        /* The compute stream is kept TWO steps ahead of the files.  Round 2 enqueued step i + 1 only after step i - 1 had been scattered into
-         * the caller's buffers, which closed a loop of compute -> download -> scatter over two steps: (5.7 + 4.0 + 3.1) / 2 = 6.4 ms per step
-         * of 16 blocks where the device needs 5.7 (GDG_BATCH_TRACE).  Now step i + 2 is enqueued as soon as step i's download has finished (before
-         * its bytes are scattered), while step i + 1 is already queued behind step i on the device. */
-        if (trace) fprintf(stderr, "[batch] set-up %.2f ms\n", now_ms() - t_begin);
-        /* Gathering step i + 2's input bytes (1.9 ms of 16 blocks x 512 files) and scattering step i's output bytes (3.0 ms) were one thread's
-         * work, one after the other: 4.8 ms per step beside the device's 4.7 -- the host set the pace half of the time.  With windows of four
-         * blocks or more the gather runs on a helper thread with copy workers of its own (copy_pool_up), one step further ahead (step i + 3 while
-         * step i is scattered; its pinned half and its device half were step i + 1's, whose upload and decode are long done -- stage() waits
-         * for their event): the host's step is the scatter alone and the device sets the pace. */
-        const bool helper = n_streamed && ws >= (size_t)4 * B && steps.size() > 3;
-        std::future<int> staged;
-        struct Join { std::future<int> &f; ~Join() { if (f.valid()) f.wait(); } } join_on_exit{ staged };     /* stage() captures this frame by reference */
-        /* the upload side's copy workers are made HERE, by the caller's thread, and the helper thread goes where they go: with option "numa" = 2
-         * workers are bound to the node of the thread that makes them, and a helper the scheduler happened to start on the other socket would
-         * put the gather's workers a socket away from the caller's buffers and the pinned halves */
-        const std::vector<int> *helper_cpus = nullptr;
-        if (helper) { ensure_copy_pool(ctx, 1); numa_target(ctx, &helper_cpus); }
-        auto on_helper = [&](size_t first, size_t last) {                        /* stage(first .. last), one after the other, on the helper thread */
-            if (first >= steps.size()) return;
-            try {
-                staged = std::async(std::launch::async, [&, first, last]() -> int {
-                    if (helper_cpus) numa_bind_thread(*helper_cpus);
-                    if (hipSetDevice(ctx->device) != hipSuccess) return GDG_ERR_HIP;
-                    for (size_t k = first; k <= last && k < steps.size(); k++) { const int rr = stage(k, 1); if (rr != GDG_OK) return rr; }
-                    return GDG_OK;
-                });
-            } catch (...) {                                                    /* no thread to be had: gather here, as the short runs do */
-                int rr = GDG_OK;
-                for (size_t k = first; k <= last && k < steps.size() && rr == GDG_OK; k++) rr = stage(k, 0);
-                std::promise<int> done;
-                done.set_value(rr);
-                staged = done.get_future();
-            }
-        };
-        auto stage_async = [&](size_t i) { on_helper(i, i); };
-        if (helper) {
-            /* the head: step 0 is gathered here; steps 1 and 2 on the helper meanwhile, so that the first whole window's bytes are on the bus
-             * while the quarter and the half window compute */
-            if ((r = stage(0)) != GDG_OK) return r;
-            on_helper(1, 2);
-            if ((r = enqueue_compute(0)) != GDG_OK || (r = enqueue_down(0)) != GDG_OK) return r;
-            if ((r = staged.get()) != GDG_OK) return r;
-            if ((r = enqueue_compute(1)) != GDG_OK || (r = enqueue_down(1)) != GDG_OK) return r;
-        } else {
-            for (size_t i = 0; i < 2 && i < steps.size(); i++) {
-                if ((r = stage(i)) != GDG_OK) return r;
-                if ((r = enqueue_compute(i)) != GDG_OK || (r = enqueue_down(i)) != GDG_OK) return r;
-            }
-        }
-        if (trace) fprintf(stderr, "[batch] steps 0 and 1 staged and enqueued at %.2f ms\n", now_ms() - t_begin);
-        for (size_t i = 0; i < steps.size(); i++) {
-            const double t_it = now_ms();
-            if (helper) {
-                if (staged.valid() && (r = staged.get()) != GDG_OK) return r;     /* step i + 2's inputs are on their way up (i = 0: since the head) */
-                stage_async(i + 3);
-            } else if ((r = stage(i + 2)) != GDG_OK) return r;                   /* while steps i, i + 1 run: the inputs of step i + 2 go up ... */
-            const double t_st = now_ms();
-            const double t_wait = t_st;
-            /* step i + 2 needs step i's half of `enc` (the compute stream waits for its download itself) but not its pinned half: it goes onto
-             * the compute stream BEFORE the scatter, so the loop compute -> download -> compute spans 5.7 + 4.0 ms per two steps and the device,
-             * not the host, sets the pace */
-            if (i + 2 < steps.size() && (r = enqueue_compute(i + 2)) != GDG_OK) return r;
-            const double t_enq = now_ms();
-            if ((r = scatter(i)) != GDG_OK) return r;                            /* ... step i comes down and goes into the files, piece by piece */
-            if (i + 2 < steps.size() && (r = enqueue_down(i + 2)) != GDG_OK) return r;     /* its pinned half is free again */
-            if (trace) fprintf(stderr, "[batch] step %zu: stage %zu %.2f | (%.2f) | enqueue %zu %.2f | download + scatter %.2f  (at %.2f ms)\n", i, i + 2,
-                               t_st - t_it, t_wait - t_st, i + 2, t_enq - t_wait, now_ms() - t_enq, now_ms() - t_begin);
-        }
-        return check_device_error(ctx);
+        BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, shard, run_metro, n_streamed != 0,
+                        trace, t_begin, 0, 0 };
+        return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
     hipStreamSynchronize(ctx->batch_up_stream);
@@ -458,6 +532,251 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
     hipStreamSynchronize(ctx->stream);
     /* the device buffers stay with the context for the next batch (gdg_batch_release) */
     return rc;
+}
+
+/* ================================================================================================
+ * The streamed batch run: the same job in slices of whole blocks.  Every input comes with its step -- decoded (with the channel pick)
+ * straight into its row, or into the resampler's source buffer behind the frames kept from the step before -- so the device holds one
+ * slice of decoded input and nothing of the job's length.
+ * ============================================================================================== */
+#define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */
+
+/* resample/resample.go:72-87 with 64-bit lengths (gdg_resample_time_length for files of any length) */
+static size_t resample_length64(size_t n, uint32_t source_rate, uint32_t target_rate) {
+    const double expansion = (double)target_rate / (double)source_rate;
+    const double out_len_f = (double)n * expansion, out_len_floor = floor(out_len_f);
+    long long out_len = (long long)out_len_floor;
+    if (out_len_floor == out_len_f) out_len--;
+    return out_len < 0 ? 0 : (size_t)out_len;
+}
+
+int gdg_batch_stream_span(size_t samples_per_channel, uint32_t source_rate, uint32_t target_rate, size_t out_first, size_t out_count,
+                          size_t *src_first, size_t *src_count) {
+    if (!src_first || !src_count || source_rate == 0 || target_rate == 0) return GDG_ERR_INVALID;
+    const size_t n = samples_per_channel;
+    const size_t covered = source_rate == target_rate ? n : resample_length64(n, source_rate, target_rate);
+    if (out_first >= covered || out_count == 0) { *src_first = n; *src_count = 0; return GDG_OK; }      /* zero padding: no source frame */
+    const size_t out_end = out_count > covered - out_first ? covered : out_first + out_count;
+    if (source_rate == target_rate) { *src_first = out_first; *src_count = out_end - out_first; return GDG_OK; }
+    const double dx = (double)source_rate / (double)target_rate;                                     /* resample.go:88-90 */
+    long long lo = (long long)floor((double)out_first * dx) - 2, hi = (long long)floor((double)(out_end - 1) * dx) + 4;
+    if (lo < 0) lo = 0;
+    if (hi > (long long)n) hi = (long long)n;
+    if (hi < lo) hi = lo;
+    *src_first = (size_t)lo;
+    *src_count = (size_t)(hi - lo);
+    return GDG_OK;
+}
+
+int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t *samples) {
+    if (!ctx || !inputs || !opt || !samples) return GDG_ERR_INVALID;
+    auto &S = ctx->bstream;
+    if (S.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is already open on this context");
+    if (n_inputs != ctx->nch) return fail(ctx, GDG_ERR_INVALID, "the batch has %d inputs, the context %d channels", n_inputs, ctx->nch);
+    if (ctx->max_frames < GDG_BLOCK_SIZE)
+        return fail(ctx, GDG_ERR_INVALID, "the batch loop runs blocks of %d frames, the context allows %d", GDG_BLOCK_SIZE, ctx->max_frames);
+    if (!gdg_wave_bytes_per_sample(opt->out_format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", opt->out_format);
+    if (opt->target_rate == 0) return fail(ctx, GDG_ERR_INVALID, "sample rate must be positive");
+    if (opt->run_meters && ctx->n_meter != 2 * n_inputs + 3)
+        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d", ctx->n_meter, 2 * n_inputs + 3);
+    std::vector<size_t> n_out((size_t)n_inputs, 0);
+    size_t max_len = 0;
+    for (int i = 0; i < n_inputs; i++) {
+        const gdg_batch_input &in = inputs[i];
+        if (!in.bytes || !in.samples_per_channel) continue;
+        if (!gdg_wave_bytes_per_sample(in.format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "input %d: unknown sample format %d", i, in.format);
+        if (in.channels == 0 || in.channel >= in.channels) return fail(ctx, GDG_ERR_INVALID, "input %d: channel %u of %u", i, in.channel, in.channels);
+        if (in.sample_rate == 0) return fail(ctx, GDG_ERR_INVALID, "input %d: sample rate must be positive", i);
+        n_out[(size_t)i] = in.sample_rate == opt->target_rate ? in.samples_per_channel : resample_length64(in.samples_per_channel, in.sample_rate, opt->target_rate);
+        max_len = std::max(max_len, n_out[(size_t)i]);
+    }
+    if (max_len % GDG_BLOCK_SIZE) max_len = GDG_BLOCK_SIZE * (max_len / GDG_BLOCK_SIZE + 1);       /* controller.go:3014-3016 */
+    S.inputs.assign(inputs, inputs + n_inputs);
+    S.opt = *opt;
+    S.length = max_len;
+    S.pos = 0;
+    S.brought.assign((size_t)n_inputs, 0);
+    S.n_out = n_out;
+    S.open = true;
+    *samples = max_len;
+    return GDG_OK;
+}
+
+/* the source frames [first, first + count) of every input that the job's samples [pos, pos + blocks * 8192) bring */
+static void stream_need(const gdg_ctx::BatchStreamState &S, size_t out_count, size_t *first, size_t *count) {
+    for (size_t i = 0; i < S.inputs.size(); i++) {
+        const gdg_batch_input &in = S.inputs[i];
+        first[i] = S.brought[i];
+        count[i] = 0;
+        if (!in.bytes || !in.samples_per_channel) continue;
+        size_t sf = 0, sc = 0;
+        gdg_batch_stream_span(in.samples_per_channel, in.sample_rate, S.opt.target_rate, S.pos, out_count, &sf, &sc);
+        if (sc && sf + sc > S.brought[i]) count[i] = sf + sc - S.brought[i];
+    }
+}
+
+static int stream_check_blocks(gdg_ctx *ctx, int blocks) {
+    const auto &S = ctx->bstream;
+    if (!S.open) return fail(ctx, GDG_ERR_INVALID, "no streamed batch run is open on this context");
+    if (S.pos >= S.length) return fail(ctx, GDG_ERR_INVALID, "the streamed batch run has delivered its last block");
+    if (blocks < 1 || (size_t)blocks > (S.length - S.pos) / GDG_BLOCK_SIZE)
+        return fail(ctx, GDG_ERR_INVALID, "a slice of %d blocks: 1 to the %zu blocks left of the job", blocks, (S.length - S.pos) / GDG_BLOCK_SIZE);
+    if ((size_t)blocks * GDG_BLOCK_SIZE > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "a slice of %d blocks is too long", blocks);
+    return GDG_OK;
+}
+
+int gdg_batch_stream_need(gdg_ctx *ctx, int blocks, size_t *first, size_t *count) {
+    if (!ctx || !first || !count) return GDG_ERR_INVALID;
+    const int rc = stream_check_blocks(ctx, blocks);
+    if (rc != GDG_OK) return rc;
+    stream_need(ctx->bstream, (size_t)blocks * GDG_BLOCK_SIZE, first, count);
+    return GDG_OK;
+}
+
+int gdg_batch_stream_close(gdg_ctx *ctx) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (!ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "no streamed batch run is open on this context");
+    ctx->bstream.open = false;                 /* the buffers stay with the context (gdg_batch_release) */
+    return GDG_OK;
+}
+
+int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = stream_check_blocks(ctx, blocks);
+    if (rc != GDG_OK) return rc;
+    if (!in_bytes || !out_bytes) return fail(ctx, GDG_ERR_INVALID, "a slice needs its input and output buffer lists");
+    auto &S = ctx->bstream;
+    const gdg_batch_options *opt = &S.opt;
+    const int N = ctx->nch, NO = N + 3, B = GDG_BLOCK_SIZE, out_width = gdg_wave_bytes_per_sample(opt->out_format);
+    const size_t length = (size_t)blocks * B, pos = S.pos;                       /* the slice: rows of `length` samples, the job's [pos, pos + length) */
+    std::vector<size_t> first((size_t)N), count((size_t)N);
+    stream_need(S, length, first.data(), count.data());
+    for (int i = 0; i < N; i++)
+        if (count[(size_t)i] && !in_bytes[i]) return fail(ctx, GDG_ERR_INVALID, "input %d: the slice needs %zu frames from %zu on", i, count[(size_t)i], first[(size_t)i]);
+    if (opt->run_meters && ctx->n_meter != 2 * N + 3)
+        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d", ctx->n_meter, 2 * N + 3);
+    enter(ctx);
+    const int W = ctx->window;
+    const size_t ws = (size_t)W * B;
+    const size_t enc_bytes = ((size_t)NO * ws * (size_t)out_width + 15) & ~(size_t)15;
+    const size_t half = std::max(enc_bytes, (size_t)8 << 20);
+    /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
+    std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
+    std::vector<double> dx((size_t)N, 1.0);
+    const size_t dec_rows_bytes = ((size_t)2 * N * sizeof(gdg_decode_row) + 255) & ~(size_t)255;     /* a piece and a carry per input */
+    const size_t up_rows_bytes = dec_rows_bytes + (((size_t)N * sizeof(gdg_resample_span) + 255) & ~(size_t)255);
+    size_t up_half = up_rows_bytes, src_half = 0;
+    bool any = false;
+    for (int i = 0; i < N; i++) {
+        const gdg_batch_input &in = S.inputs[(size_t)i];
+        if (!in.bytes || !in.samples_per_channel) continue;
+        any = true;
+        cap[(size_t)i] = ws;
+        if (in.sample_rate != opt->target_rate) {
+            dx[(size_t)i] = (double)in.sample_rate / (double)opt->target_rate;
+            cap[(size_t)i] = (size_t)((double)ws * dx[(size_t)i]) + 16;
+            src_off[(size_t)i] = src_half;
+            src_half += ((cap[(size_t)i] + GDG_STREAM_CARRY) * sizeof(double) + 15) & ~(size_t)15;
+        }
+        up_half += (cap[(size_t)i] * in.channels * (size_t)gdg_wave_bytes_per_sample(in.format) + 15) & ~(size_t)15;
+    }
+    up_half = (up_half + 255) & ~(size_t)255;                                   /* the second half starts with descriptors: aligned like the first */
+    src_half = (src_half + 255) & ~(size_t)255;
+    rc = ensure_batch_pipe(ctx, half, up_half);
+    if (rc != GDG_OK) return rc;
+    double *d_inputs = nullptr, *d_win = nullptr, *d_carry = nullptr;
+    unsigned char *d_enc = nullptr, *d_up = nullptr, *d_src = nullptr;
+    static int trace = -1;
+    if (trace < 0) { const char *e = getenv("GDG_BATCH_TRACE"); trace = e ? atoi(e) : 0; }
+    const double t_begin = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    std::vector<size_t> run(S.brought);                                          /* frames handed over, step by step */
+    auto body = [&]() -> int {
+        int r;
+        if ((r = batch_buffer(ctx, 0, (size_t)N * length * sizeof(double), (void **)&d_inputs)) != GDG_OK) return r;
+        if ((r = batch_buffer(ctx, 1, (size_t)NO * ws * sizeof(double), (void **)&d_win)) != GDG_OK) return r;
+        if ((r = batch_buffer(ctx, 2, 2 * enc_bytes, (void **)&d_enc)) != GDG_OK) return r;
+        /* slot 3, the one-call run's arena: the frames every resampled input keeps for its next step (never grows while a job is open) */
+        if ((r = batch_buffer(ctx, 3, (size_t)N * GDG_STREAM_CARRY * sizeof(double), (void **)&d_carry)) != GDG_OK) return r;
+        if ((r = batch_buffer(ctx, 4, 2 * up_half, (void **)&d_up)) != GDG_OK) return r;
+        if (src_half && (r = batch_buffer(ctx, 5, 2 * src_half, (void **)&d_src)) != GDG_OK) return r;     /* the resampler's source frames, per half */
+        /* the zero padding (controller.go:3018-3045): what no step of this slice will write */
+        for (int i = 0; i < N; i++) {
+            const size_t n_out = S.n_out[(size_t)i];
+            const size_t covered = n_out <= pos ? 0 : std::min(n_out - pos, length);
+            if (covered < length)
+                HIP_TRY(ctx, hipMemsetAsync(d_inputs + (size_t)i * length + covered, 0, (length - covered) * sizeof(double), ctx->stream));
+        }
+        int up_used[2] = { 0, 0 };
+        BatchStage stage = [&](size_t i, size_t a, int w, int pool) -> int {
+            const int h = (int)(i & 1);
+            if (up_used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_up_ready[h]));     /* step i - 2 has left this half */
+            unsigned char *hb = ctx->h_up[h], *db = d_up + (size_t)h * up_half, *sb = d_src + (size_t)h * src_half;
+            gdg_decode_row *rows = reinterpret_cast<gdg_decode_row *>(hb);
+            gdg_resample_span *spans = reinterpret_cast<gdg_resample_span *>(hb + dec_rows_bytes);
+            std::vector<BatchPiece> pieces;
+            size_t cur = up_rows_bytes;
+            int n_rows = 0, n_spans = 0;
+            unsigned max_count = 0, max_out = 0;
+            const size_t span = (size_t)w * B, abs = pos + a;                    /* the step: the job's samples [abs, abs + span) */
+            for (int c = 0; c < N; c++) {
+                const gdg_batch_input &in = S.inputs[(size_t)c];
+                if (!in.bytes || !in.samples_per_channel || abs >= S.n_out[(size_t)c]) continue;      /* empty, or ended in an earlier step: zeros */
+                const size_t cnt = std::min(S.n_out[(size_t)c] - abs, span), width = (size_t)gdg_wave_bytes_per_sample(in.format) * in.channels;
+                size_t sf = 0, sc = 0;
+                gdg_batch_stream_span(in.samples_per_channel, in.sample_rate, opt->target_rate, abs, cnt, &sf, &sc);
+                const size_t bs = run[(size_t)c], e = std::max(bs, sf + sc), fresh = e - bs;
+                if (fresh > cap[(size_t)c] || bs < first[(size_t)c] || e > first[(size_t)c] + count[(size_t)c])
+                    return fail(ctx, GDG_ERR_INVALID, "input %d: a step of %zu frames from %zu does not fit its slice", c, fresh, bs);
+                run[(size_t)c] = e;
+                const unsigned char *src = static_cast<const unsigned char *>(in_bytes[c]) + (bs - first[(size_t)c]) * width;
+                const unsigned stride = in.channels > 1 ? in.channels : 0;
+                double *row = d_inputs + (size_t)c * length + a;
+                unsigned char *piece = db + cur;
+                if (fresh) {
+                    for (size_t q = 0; q < fresh * width; q += (size_t)1 << 20)
+                        pieces.push_back({ hb + cur + q, src + q, std::min(fresh * width - q, (size_t)1 << 20) });
+                    cur += (fresh * width + 15) & ~(size_t)15;
+                    if (fresh > max_count) max_count = (unsigned)fresh;
+                }
+                if (in.sample_rate == opt->target_rate) {
+                    if (bs != abs || fresh != cnt) return fail(ctx, GDG_ERR_INVALID, "input %d: step at %zu, frames from %zu", c, abs, bs);
+                    rows[n_rows++] = gdg_decode_row{ piece, row, (unsigned)cnt, in.format, stride, in.channel };
+                    continue;
+                }
+                /* resample.Time: [the frames kept from the step before | this step's], then the span kernel */
+                const size_t keep_in = std::min(bs, (size_t)GDG_STREAM_CARRY), held = keep_in + fresh;
+                if (sf < bs - keep_in) return fail(ctx, GDG_ERR_INVALID, "input %d: the resampler looks back to frame %zu, kept from %zu", c, sf, bs - keep_in);
+                double *frames = reinterpret_cast<double *>(sb + src_off[(size_t)c]), *carry = d_carry + (size_t)c * GDG_STREAM_CARRY;
+                if (keep_in) rows[n_rows++] = gdg_decode_row{ reinterpret_cast<const unsigned char *>(carry), frames, (unsigned)keep_in, GDG_FMT_IEEE64, 0, 0 };
+                if (fresh) rows[n_rows++] = gdg_decode_row{ piece, frames + keep_in, (unsigned)fresh, in.format, stride, in.channel };
+                if (keep_in > max_count) max_count = (unsigned)keep_in;
+                spans[n_spans++] = gdg_resample_span{ frames, row, carry, (long long)(bs - keep_in), (long long)in.samples_per_channel, (long long)abs,
+                                                      dx[(size_t)c], (unsigned)cnt, (unsigned)held, (unsigned)std::min(held, (size_t)GDG_STREAM_CARRY), 0 };
+                if (cnt > max_out) max_out = (unsigned)cnt;
+            }
+            up_used[h] = 1;
+            if (n_rows) {
+                move_pieces(ctx, pieces, pool);
+                HIP_TRY(ctx, hipMemcpyAsync(db, hb, cur, hipMemcpyHostToDevice, ctx->batch_up_stream));
+                /* ONE decode launch for every piece and every kept frame, ONE resample launch for every resampled input */
+                HIP_TRY(ctx, gdg_launch_wave_decode_rows(reinterpret_cast<const gdg_decode_row *>(db), n_rows, max_count, ctx->batch_up_stream));
+                HIP_TRY(ctx, gdg_launch_resample_spans(reinterpret_cast<const gdg_resample_span *>(db + dec_rows_bytes), n_spans, max_out, ctx->batch_up_stream));
+            }
+            HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
+            return GDG_OK;
+        };
+        BatchLoop loop{ N, NO, 0, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, nullptr, true, any, trace, t_begin,
+                        S.length / B, pos / B };
+        return batch_block_loop(ctx, loop, stage);
+    };
+    rc = body();
+    hipStreamSynchronize(ctx->batch_up_stream);
+    hipStreamSynchronize(ctx->batch_stream);
+    hipStreamSynchronize(ctx->stream);
+    if (rc != GDG_OK) { S.open = false; return rc; }                            /* a slice that failed half-way: the job cannot go on */
+    for (int i = 0; i < N; i++) S.brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
+    S.pos += length;
+    return GDG_OK;
 }
 
 int gdg_batch_run(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes) {

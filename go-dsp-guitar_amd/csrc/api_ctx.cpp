@@ -154,6 +154,7 @@ static const OptionDef g_options[] = {
     { "fir_premac_min_partitions", "GDG_FIR_PREMAC_MIN", 1, 1 << 24, -1, &gdg_ctx::fir_premac_min, nullptr, true },
     { "fir_premac_min_partitions_two_amps", "GDG_FIR_PREMAC_MIN_TWO", 1, 1 << 24, -1, &gdg_ctx::fir_premac_min_two, nullptr, true },
     { "stat_premac_launches_used", "GDG_STAT_PREMAC_USED", 0, 0x7fffffff, -1, &gdg_ctx::stat_premac_used, nullptr, false },
+    { "stat_batch_device_kib", "GDG_STAT_BATCH_DEVICE_KIB", 0, 0x7fffffff, -1, &gdg_ctx::stat_batch_dev_kib, nullptr, false },
     { "fir_ahead_frames", "GDG_FIR_AHEAD", 0, 4, -1, &gdg_ctx::fir_ahead_frames, nullptr, true },                 /* 1 acts as 0 */
     { "fir_ahead_min_channels", "GDG_FIR_AHEAD_MIN", 1, 1 << 20, -1, &gdg_ctx::fir_ahead_min, nullptr, true },
     { "stat_fir_ahead_sums_used", "GDG_STAT_FIR_AHEAD_USED", 0, 0x7fffffff, -1, &gdg_ctx::stat_fir_ahead_used, nullptr, false },
@@ -368,6 +369,12 @@ int gdg_ctx_get_option(gdg_ctx *ctx, const char *key, long long *value) {
         unsigned long long v = 0;
         HIP_TRY(ctx, hipMemcpy(&v, ctx->d_fir_ahead_used, sizeof(v), hipMemcpyDeviceToHost));
         ctx->stat_fir_ahead_used = v > 0x7fffffffull ? 0x7fffffff : (int)v;
+    }
+    if (o->field == &gdg_ctx::stat_batch_dev_kib) {
+        size_t bytes = 0;
+        for (int i = 0; i < 6; i++) bytes += ctx->batch_dev_cap[i];
+        const size_t kib = (bytes + 1023) / 1024;
+        ctx->stat_batch_dev_kib = kib > 0x7fffffffull ? 0x7fffffff : (int)kib;
     }
     if (o->knob >= 0) *value = gdg_knob_get(o->knob);
     else if (o->field) *value = ctx->*(o->field);

@@ -340,6 +340,16 @@ struct gdg_ctx {
      * grown when a batch needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
     void *batch_dev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     size_t batch_dev_cap[6] = { 0, 0, 0, 0, 0, 0 };
+    int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
+    /* the streamed batch run (gdg_batch_stream_open .. _close): the job, how far it has come, and per input the source frames handed over */
+    struct BatchStreamState {
+        bool open = false;
+        std::vector<gdg_batch_input> inputs;   /* bytes: non-null = the input has samples (never read) */
+        gdg_batch_options opt = {};
+        size_t length = 0, pos = 0;            /* samples of every output; samples done */
+        std::vector<size_t> brought;           /* source frames [0, brought) of input i have been handed over */
+        std::vector<size_t> n_out;             /* samples the input covers in the job: its (resampled) length */
+    } bstream;
     /* channel groups of the host-buffer paths: group g's upload, kernels and download run on stream g, so one group's
      * PCIe transfers overlap the other groups' kernels (channels are independent) */
     int plan_groups = 1;

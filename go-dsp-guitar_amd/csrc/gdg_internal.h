@@ -273,8 +273,19 @@ hipError_t gdg_launch_wave_encode(int fmt, const double *d_in, size_t per, unsig
 /* rows of one strided array -> compact encoded rows (row_len % 4 == 0) */
 hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes, hipStream_t s);
 /* many mono pieces in one launch (the batch run's streamed upload): piece r = `count` samples of format `fmt` at `src` -> dst */
-struct gdg_decode_row { const unsigned char *src; double *dst; unsigned count; int fmt; };
+/* stride > 1: the piece holds interleaved frames of `stride` channels, of which channel `offset` is decoded (0 / 1: mono, as above) */
+struct gdg_decode_row { const unsigned char *src; double *dst; unsigned count; int fmt; unsigned stride, offset; };
 hipError_t gdg_launch_wave_decode_rows(const gdg_decode_row *d_rows, int n_rows, unsigned max_count, hipStream_t s);
+/* resample.Time over spans of several files in one launch (the streamed batch run; io.hip resample_span_kernel) */
+struct gdg_resample_span {
+    const double *src;           /* source frames [src_first, src_first + src_count) of the file */
+    double *dst;                 /* output samples [out_first, out_first + count) */
+    double *carry;               /* receives the last `keep` (<= 256) frames of src */
+    long long src_first, n, out_first;
+    double dx;
+    unsigned count, src_count, keep, pad;
+};
+hipError_t gdg_launch_resample_spans(const gdg_resample_span *d_spans, int n_spans, unsigned max_count, hipStream_t s);
 hipError_t gdg_launch_resample_time(const double *d_in, int n, double dx, double *d_out, int n_out, hipStream_t s);
 hipError_t gdg_launch_meter(const double *d_rows, size_t stride, int n_ports, int n, gdg_meter_rec *d_state,
                             double decay, unsigned long long hold, hipStream_t s);

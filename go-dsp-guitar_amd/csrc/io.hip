@@ -469,10 +469,38 @@ __device__ __forceinline__ void decode_piece(const gdg_decode_row &r) {
     }
 }
 
+/* a piece that picks one channel out of interleaved frames (samplesToChannels, wave.go:237-270, for that channel alone): sample i is the
+ * file's sample i * stride + offset.  One sample per thread, byte loads: neighbouring lanes read `stride` samples apart. */
+template <int FMT>
+__device__ __forceinline__ void decode_piece_strided(const gdg_decode_row &r) {
+    constexpr int W = fmt_width<FMT>::W;
+    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < r.count; i += gridDim.x * 256) {
+        const size_t at = ((size_t)i * r.stride + r.offset) * W;
+        unsigned code = 0;
+#pragma unroll
+        for (int k = 0; k < W; k++) code |= (unsigned)r.src[at + k] << (8 * k);
+        r.dst[i] = decode_code<FMT>(code);
+    }
+}
+
 /* blockIdx.y = piece; every piece has its own format (uniform per workgroup), source and destination */
 __global__ void __launch_bounds__(256)
 wave_decode_rows_kernel(const gdg_decode_row *__restrict__ rows) {
     const gdg_decode_row r = rows[blockIdx.y];
+    if (r.stride > 1) {                                        /* a channel of an interleaved file (the streamed batch run) */
+        switch (r.fmt) {
+        case GDG_FMT_LPCM8: decode_piece_strided<GDG_FMT_LPCM8>(r); break;
+        case GDG_FMT_LPCM16: decode_piece_strided<GDG_FMT_LPCM16>(r); break;
+        case GDG_FMT_LPCM24: decode_piece_strided<GDG_FMT_LPCM24>(r); break;
+        case GDG_FMT_LPCM32: decode_piece_strided<GDG_FMT_LPCM32>(r); break;
+        case GDG_FMT_IEEE32: decode_piece_strided<GDG_FMT_IEEE32>(r); break;
+        default:
+            for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < r.count; i += gridDim.x * 256)
+                r.dst[i] = reinterpret_cast<const double *>(r.src)[(size_t)i * r.stride + r.offset];
+            break;
+        }
+        return;
+    }
     switch (r.fmt) {
     case GDG_FMT_LPCM8: decode_piece<GDG_FMT_LPCM8>(r); break;
     case GDG_FMT_LPCM16: decode_piece<GDG_FMT_LPCM16>(r); break;
@@ -575,6 +603,43 @@ hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_s
         return hipMemcpy2DAsync(p, row_len * sizeof(double), d_in, row_stride * sizeof(double), row_len * sizeof(double), n_rows, hipMemcpyDeviceToDevice, s);
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+/* resample.Time over a span of a file (the streamed batch run): blockIdx.y = input.  Output samples [out_first, out_first + count) from
+ * the source frames [src_first, src_first + src_count) at `src`; n = the FILE's frames (the j < n bound).  x, floor(x) and x - j are
+ * formed from the absolute 64-bit i and j in the operation order of resample_time_kernel, so every sample has the whole-file kernel's
+ * bits (both kernels are compiled without contraction).  The host sizes the span so that every j in [0, n) a sample reads lies inside
+ * it (gdg_batch_stream_span); the bounds test on the span itself is there so that a wrong span can never read outside the buffer.
+ * The last workgroup of an input also copies the span's last `keep` frames to `carry`: the frames the next slice looks back at. */
+__global__ void __launch_bounds__(256)
+resample_span_kernel(const gdg_resample_span *__restrict__ spans) {
+    const gdg_resample_span r = spans[blockIdx.y];
+    for (unsigned k = blockIdx.x * 256 + threadIdx.x; k < r.count; k += gridDim.x * 256) {
+        const long long i = r.out_first + (long long)k;
+        double x = (double)i * r.dx;
+        long long idx = (long long)floor(x);
+        double sum = 0.0;
+#pragma unroll
+        for (long long j = idx - 2; j < idx + 4; j++) {
+            if (j >= 0 && j < r.n) {
+                double diff = x - (double)j;
+                const long long at = j - r.src_first;
+                const double v = (at >= 0 && at < (long long)r.src_count) ? r.src[at] : 0.0;
+                sum += v * lanczos_kernel(diff, 3.0);
+            }
+        }
+        r.dst[k] = sum;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < r.keep) r.carry[threadIdx.x] = r.src[r.src_count - r.keep + threadIdx.x];
+}
+
+hipError_t gdg_launch_resample_spans(const gdg_resample_span *d_spans, int n_spans, unsigned max_count, hipStream_t s) {
+    if (n_spans <= 0) return hipSuccess;
+    unsigned tiles = (max_count + 255) / 256;
+    if (tiles > 256) tiles = 256;
+    if (tiles == 0) tiles = 1;
+    resample_span_kernel<<<dim3(tiles, (unsigned)n_spans), dim3(256), 0, s>>>(d_spans);
     return hipGetLastError();
 }
 

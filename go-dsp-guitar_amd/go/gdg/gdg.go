@@ -37,6 +37,9 @@ type Context struct {
 	channels int
 	scratch  unsafe.Pointer // C memory for MetersProcess: [ports pointers | ports x frames float64]
 	scratchN int
+	// the streamed batch run that is open (BatchStreamOpen): its inputs and the width of an output sample
+	streamInputs int
+	streamWidth  int
 }
 
 // DeviceCount: HIP devices visible to the process (0 without a driver).
@@ -770,6 +773,126 @@ func (this *Context) BatchRunShard(inputs []BatchInput, opt BatchOptions, jobSam
 		res.Metronome = goFloats(unsafe.Pointer(so.metronome), jobSamples)
 	}
 	return res, nil
+}
+
+// BatchStreamInput: one input file of the streamed batch run, described by its RIFF header alone: Frames is the FILE's total samples
+// per channel (0 leaves the channel empty); the bytes come slice by slice.
+type BatchStreamInput struct {
+	Frames     uint64
+	Format     int // gdg_wave_format
+	SampleRate uint32
+	Channels   int
+	Channel    int
+}
+
+// BatchStreamOpen begins the job of BatchRun in slices of whole 8192-sample blocks (gdg_batch_stream_open): files of any length in
+// bounded memory, the outputs byte for byte BatchRun's.  Returns the samples of every output.
+func (this *Context) BatchStreamOpen(inputs []BatchStreamInput, opt BatchOptions) (uint64, error) {
+	n := len(inputs)
+	if n == 0 {
+		return 0, fmt.Errorf("gdg: no inputs")
+	}
+	arr := (*[1 << 20]C.gdg_batch_input)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.gdg_batch_input{}))))
+	if arr == nil {
+		return 0, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(arr))
+	for i, in := range inputs {
+		if in.Frames == 0 {
+			continue
+		}
+		arr[i].bytes = unsafe.Pointer(arr) // never read: only "not NULL"
+		arr[i].samples_per_channel = C.size_t(in.Frames)
+		arr[i].format = C.int(in.Format)
+		arr[i].sample_rate = C.uint32_t(in.SampleRate)
+		arr[i].channels = C.uint(in.Channels)
+		arr[i].channel = C.uint(in.Channel)
+	}
+	o := C.gdg_batch_options{target_rate: C.uint32_t(opt.TargetRate), out_format: C.int(opt.OutFormat),
+		metronome_to_master: cbool(opt.MetronomeToMaster), run_meters: cbool(opt.RunMeters), tuner_enqueue: cbool(opt.TunerEnqueue)}
+	var samples C.size_t
+	if e := this.err(C.gdg_batch_stream_open(this.ctx, &arr[0], C.int(n), &o, &samples)); e != nil {
+		return 0, e
+	}
+	this.streamInputs = n
+	this.streamWidth = int(C.gdg_wave_bytes_per_sample(o.out_format))
+	return uint64(samples), nil
+}
+
+// BatchStreamNeed: the source frames [first[i], first[i] + count[i]) of every input that the next slice of `blocks` blocks must bring.
+func (this *Context) BatchStreamNeed(blocks int) (first []uint64, count []uint64, err error) {
+	n := this.streamInputs
+	if n == 0 {
+		return nil, nil, fmt.Errorf("gdg: no streamed batch run is open")
+	}
+	buf := (*[1 << 20]C.size_t)(C.calloc(C.size_t(2*n), C.size_t(unsafe.Sizeof(C.size_t(0)))))
+	if buf == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(buf))
+	if e := this.err(C.gdg_batch_stream_need(this.ctx, C.int(blocks), &buf[0], &buf[n])); e != nil {
+		return nil, nil, e
+	}
+	first, count = make([]uint64, n), make([]uint64, n)
+	for i := 0; i < n; i++ {
+		first[i], count[i] = uint64(buf[i]), uint64(buf[n+i])
+	}
+	return first, count, nil
+}
+
+// BatchStreamStep runs one slice: frames[i] holds the interleaved frames BatchStreamNeed asked for (nil where it asked for none);
+// returns the slice's N + 3 output pieces of blocks * 8192 samples each.  The bytes live in C memory for the duration of the call.
+func (this *Context) BatchStreamStep(blocks int, frames [][]byte) ([][]byte, error) {
+	n := this.streamInputs
+	if n == 0 || len(frames) != n {
+		return nil, fmt.Errorf("gdg: %d inputs for a streamed batch run of %d", len(frames), n)
+	}
+	each := blocks * 8192 * this.streamWidth
+	if blocks <= 0 || each <= 0 {
+		return nil, fmt.Errorf("gdg: a slice of %d blocks", blocks)
+	}
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	ptrs := (*[1 << 20]unsafe.Pointer)(C.calloc(C.size_t(2*n+3), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if ptrs == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(ptrs))
+	for i, f := range frames {
+		if len(f) == 0 {
+			continue
+		}
+		ptrs[i] = C.CBytes(f)
+		if ptrs[i] == nil {
+			return nil, fmt.Errorf("gdg: out of memory (%d bytes of input %d)", len(f), i)
+		}
+		owned = append(owned, ptrs[i])
+	}
+	for i := n; i < 2*n+3; i++ {
+		ptrs[i] = C.malloc(C.size_t(each))
+		if ptrs[i] == nil {
+			return nil, fmt.Errorf("gdg: out of memory (%d bytes per output)", each)
+		}
+		owned = append(owned, ptrs[i])
+	}
+	if e := this.err(C.gdg_batch_stream_step(this.ctx, C.int(blocks), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[0])), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[n])))); e != nil {
+		return nil, e
+	}
+	outs := make([][]byte, n+3)
+	for i := range outs {
+		outs[i] = goBytes(ptrs[n+i], each)
+	}
+	return outs, nil
+}
+
+// BatchStreamClose ends the streamed job, also before its last block (gdg_batch_stream_close); the context stays usable.
+func (this *Context) BatchStreamClose() error {
+	this.streamInputs = 0
+	return this.err(C.gdg_batch_stream_close(this.ctx))
 }
 
 // BatchRelease returns the device buffers of the last batch run to the context's arena (gdg_batch_release); the next run re-makes them.

@@ -39,6 +39,9 @@ def lib():
             "gdgh_engine_set_rendezvous": (None, [vp, i32, i32]), "gdgh_engine_last_error": (cs, [vp]),
             "gdgh_engine_process_all": (cs, [vp, vp, vp, i32, C.c_uint32]),
             "gdgh_engine_batch_run": (cs, [vp, vp, i32, vp, i32, vp, C.POINTER(C.c_size_t)]),
+            "gdgh_engine_batch_stream_open": (cs, [vp, vp, i32, vp, i32, C.POINTER(C.c_size_t)]),
+            "gdgh_engine_batch_stream_need": (cs, [vp, i32, vp, vp]), "gdgh_engine_batch_stream_step": (cs, [vp, i32, vp, vp]),
+            "gdgh_engine_batch_stream_close": (cs, [vp]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
             "gdgh_engine_save_state": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -208,6 +211,44 @@ class Engine:
         _err(lib().gdgh_engine_batch_run(self._h, arr, n, C.byref(opt), window, ptrs, C.byref(samples)))
         assert samples.value == length
         return outs
+
+    def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
+        """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
+        yields every slice's N + 3 output pieces."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        n = len(inputs)
+        arr = (pkg.BatchInput * n)()
+        datas, widths = [None] * n, [0] * n
+        for i, it in enumerate(inputs):
+            if it is None:
+                continue
+            channels, channel = (it[3], it[4]) if len(it) > 3 else (1, 0)
+            f = pkg.WAVE_FORMATS[it[1]] if isinstance(it[1], str) else it[1]
+            datas[i] = np.ascontiguousarray(it[0], dtype=np.uint8)
+            widths[i] = max(pkg.lib().gdg_wave_bytes_per_sample(f), 1) * max(channels, 1)
+            arr[i] = pkg.BatchInput(datas[i].ctypes.data if datas[i].size else None, datas[i].size // widths[i], f, it[2], channels, channel)
+        fo = pkg.WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
+        opt = pkg.BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
+        wo = pkg.lib().gdg_wave_bytes_per_sample(fo)
+        samples = C.c_size_t(0)
+        _err(lib().gdgh_engine_batch_stream_open(self._h, arr, n, C.byref(opt), window, C.byref(samples)))
+        try:
+            left = samples.value // 8192
+            first, count = (C.c_size_t * n)(), (C.c_size_t * n)()
+            while left:
+                blocks = min(left, blocks_per_slice)
+                _err(lib().gdgh_engine_batch_stream_need(self._h, blocks, first, count))
+                pieces = [None if datas[i] is None or not count[i] else datas[i][first[i] * widths[i]:(first[i] + count[i]) * widths[i]] for i in range(n)]
+                ins = (C.c_void_p * n)(*[(p.ctypes.data if p is not None else None) for p in pieces])
+                outs = [np.zeros(blocks * 8192 * wo, dtype=np.uint8) for _ in range(n + 3)]
+                ptrs = (C.c_void_p * (n + 3))(*[o.ctypes.data for o in outs])
+                _err(lib().gdgh_engine_batch_stream_step(self._h, blocks, ins, ptrs))
+                yield outs
+                left -= blocks
+        finally:
+            lib().gdgh_engine_batch_stream_close(self._h)
+
 
 class Chain:
     """signal.Chain: the 14 methods of signal/signal.go:21-36."""

@@ -964,6 +964,67 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     return "";
 }
 
+/* the one context of a one-shard engine, for the streamed batch run */
+static Error streamShard(Engine *e, const char *what) {
+    if (e->shards() != 1) return format("BatchStream: unsupported on an engine of %d shards (%s)", e->shards(), what);
+    return "";
+}
+
+Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, size_t *samples) {
+    if (!inputs || !samples) return "BatchStreamOpen: no inputs or nowhere to put the length";
+    if (nInputs != nChannels_) return format("BatchStreamOpen: %d inputs for %d channels", nInputs, nChannels_);
+    Error e = streamShard(this, "open");
+    if (!e.empty()) { setError(e); return e; }
+    setError("");
+    std::vector<std::shared_ptr<signal::Chain>> chains;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        chains = chains_;
+    }
+    std::lock_guard<std::mutex> lk(shards_[0]->mu);
+    gdg_ctx *ctx = context(0);
+    if (!ctx) return LastError();
+    std::vector<signal::Chain *> mine;
+    for (auto &c : chains) mine.push_back(c.get());
+    e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
+    if (!e.empty()) { setError(e); return e; }
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+        setError(gdg_last_error(ctx));
+        return LastError();
+    }
+    return "";
+}
+
+Error Engine::BatchStreamNeed(int blocks, size_t *first, size_t *count) {
+    Error e = streamShard(this, "need");
+    if (!e.empty()) { setError(e); return e; }
+    std::lock_guard<std::mutex> lk(shards_[0]->mu);
+    gdg_ctx *ctx = shards_[0]->ctx;
+    if (!ctx) return "BatchStreamNeed: no streamed batch run is open";
+    if (gdg_batch_stream_need(ctx, blocks, first, count) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+    return "";
+}
+
+Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *outs) {
+    Error e = streamShard(this, "step");
+    if (!e.empty()) { setError(e); return e; }
+    std::lock_guard<std::mutex> lk(shards_[0]->mu);
+    gdg_ctx *ctx = shards_[0]->ctx;
+    if (!ctx) return "BatchStreamStep: no streamed batch run is open";
+    if (gdg_batch_stream_step(ctx, blocks, ins, outs) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+    return "";
+}
+
+Error Engine::BatchStreamClose() {
+    Error e = streamShard(this, "close");
+    if (!e.empty()) { setError(e); return e; }
+    std::lock_guard<std::mutex> lk(shards_[0]->mu);
+    gdg_ctx *ctx = shards_[0]->ctx;
+    if (!ctx) return "BatchStreamClose: no streamed batch run is open";
+    if (gdg_batch_stream_close(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+    return "";
+}
+
 /* ================================ spatializer ============================================= */
 namespace spatializer {
 
@@ -1163,6 +1224,14 @@ const char *gdgh_engine_process_all(void *e, const double *const *in, double *co
 const char *gdgh_engine_batch_run(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, void *const *outs, size_t *samples) {
     return ret(((Engine *)e)->BatchRun(inputs, n, *opt, window, outs, samples));
 }
+const char *gdgh_engine_batch_stream_open(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, size_t *samples) {
+    return ret(((Engine *)e)->BatchStreamOpen(inputs, n, *opt, window, samples));
+}
+const char *gdgh_engine_batch_stream_need(void *e, int blocks, size_t *first, size_t *count) { return ret(((Engine *)e)->BatchStreamNeed(blocks, first, count)); }
+const char *gdgh_engine_batch_stream_step(void *e, int blocks, const void *const *ins, void *const *outs) {
+    return ret(((Engine *)e)->BatchStreamStep(blocks, ins, outs));
+}
+const char *gdgh_engine_batch_stream_close(void *e) { return ret(((Engine *)e)->BatchStreamClose()); }
 void *gdgh_engine_context(void *e, int shard) { return ((Engine *)e)->context(shard); }
 void gdgh_engine_shard_range(void *e, int shard, int *first, int *count) { ((Engine *)e)->shardRange(shard, first, count); }
 void *gdgh_engine_create_sharded(int n_channels, int max_frames, const int *devices, int n_devices) {

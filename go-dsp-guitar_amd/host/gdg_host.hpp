@@ -206,6 +206,16 @@ public:
      * controller.go:3123-3219).  inputs: one per channel of the engine; outs: N + 3 host buffers as for gdg_batch_run
      * (NULL = "skipping output"); `samples` receives the length of every output. */
     Error BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, void *const *outs, size_t *samples);
+    /* BatchRun in slices of whole 8192-sample blocks, files of any length in bounded memory (gdg_batch_stream_open / _need / _step /
+     * _close, include/gdg.h): Open synchronises the chains to the device and sets the window, `samples` receives the job's length; Need
+     * fills first[i] / count[i] (one per input) with the source frames the next slice of `blocks` blocks must bring; Step takes those
+     * frames (ins[i], interleaved, the file's format) and writes the slice's N + 3 output pieces.  The chains must not change between
+     * Open and Close.  For an engine of ONE shard: the streamed form of a shard does not exist yet, and an engine of several shards
+     * answers "BatchStream: unsupported ...". */
+    Error BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, size_t *samples);
+    Error BatchStreamNeed(int blocks, size_t *first, size_t *count);
+    Error BatchStreamStep(int blocks, const void *const *ins, void *const *outs);
+    Error BatchStreamClose();
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`

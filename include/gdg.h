@@ -99,6 +99,8 @@ int gdg_ctx_share_ir_spectra(gdg_ctx *ctx, int enable);
  *   fir_premac_min_partitions_two_amps >= 1  ... and when a channel has two or more power amps, the smaller of the two (320 = 40 channels x 65536 taps)
  *   stat_premac_launches_used    >= 0        a counter, not a setting: inverse-transform launches so far that continued sums made ahead (tests read it to
  *                                            see that the path under test is the one that ran; saturates; setting it sets the count) (0)
+ *   stat_batch_device_kib        >= 0        a figure, not a setting: the capacity of the batch runs' device buffers in KiB, rounded up (what gdg_batch_release
+ *                                            frees; saturates; a value set is replaced by the figure at the next read) (0)
  *   fir_premac_lds_bytes         -1 .. 65536 ... whose workgroups ask for this much LDS they never touch, so that they land on the CUs the segments leave
  *                                            idle instead of among the segments' waves; -1: 16384 below 120 channels, 49152 from there, 0 when a channel
  *                                            has fewer than 5 or more than 32 partitions (-1)
@@ -550,6 +552,47 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
                         const gdg_batch_shard_out *shard);
 int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                             size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes);
+/*
+ * The STREAMED batch run: the job of gdg_batch_run, fed and drained in slices of whole 8192-sample blocks.  Device and pinned memory
+ * depend on the slice (one slice of decoded input, N x blocks x 8192 x 8 bytes) and on the context's window, not on the job's length,
+ * and the outputs are byte for byte the one-call run's whatever the slicing: files of any length run in bounded memory, and the host
+ * needs no more than one slice of every file resident.
+ *   gdg_batch_stream_open(ctx, inputs, N, &options, &samples)          once; inputs[i].bytes is never read: NULL (or samples_per_channel
+ *                                                                      == 0) still means "leaving channel empty", anything else "has
+ *                                                                      samples"; samples_per_channel is the FILE's total (the RIFF header's)
+ *   until `samples` are done:
+ *     gdg_batch_stream_need(ctx, blocks, first, count)                 the source frames [first[i], first[i] + count[i]) of every input
+ *                                                                      that the next slice of `blocks` blocks must bring (N entries each)
+ *     gdg_batch_stream_step(ctx, blocks, in_bytes, out_bytes)          in_bytes[i]: those count[i] interleaved frames (all of the file's
+ *                                                                      channels, the file's format; may be NULL when count[i] == 0);
+ *                                                                      out_bytes: N + 3 buffers of blocks * 8192 * width bytes (NULL =
+ *                                                                      "skipping output"), complete when the call returns
+ *   gdg_batch_stream_close(ctx)                                        also before the end (an abandoned job); the context stays usable
+ * `blocks` is any count from 1 to what is left of the job and may differ from slice to slice (one slice is at most 2^31 - 1 samples, the
+ * job any size_t); inside a slice the block loop steps by the context's window as gdg_batch_run does, and the last slice carries the
+ * job's zero padding.  first[i] continues exactly where the slice before ended: every source frame is handed over once, in order --
+ * also frames no output sample reads -- and the few frames resample.Time looks back at are kept on the device.
+ * Between open and close gdg_batch_run, gdg_batch_run_shard, gdg_batch_release and a second open return GDG_ERR_INVALID; so do step and
+ * need without open, with `blocks` beyond the job's end, and after the last block.  A slice steps where the one-call run of the whole job
+ * would step (or where the slice ends), so meters, tuner, metronome and the units' state are the one-call context's; a gdg_state_save
+ * blob is equal as well where the job's last steps coincide (the convolution keeps two history halves, of which the one not read next
+ * holds whatever frame the window grouping left there).  A slice that fails half-way closes the job.  State
+ * save / load and parameter changes between slices behave as between two gdg_batch_run calls.  The buffers are the batch run's own
+ * (option stat_batch_device_kib reads their size, gdg_batch_release frees them).  The streamed form of a SHARD (gdg_batch_run_shard /
+ * gdg_batch_finish_master) does not exist yet.
+ *
+ * gdg_batch_stream_span is pure arithmetic and needs no context or device: the source frames of one input that the job's output samples
+ * [out_first, out_first + out_count) read, for an input of samples_per_channel frames at source_rate in a job at target_rate.  Same
+ * rate: the range itself, cut at the file's end.  Otherwise the hull of the resampler's windows floor(i dx) - 2 .. floor(i dx) + 3,
+ * dx = source_rate / target_rate (resample/resample.go:88-103), over the samples the input covers (resample.go:72-87), cut to
+ * [0, samples_per_channel).  A range that reads nothing gives src_count = 0 (src_first = samples_per_channel).
+ */
+int gdg_batch_stream_span(size_t samples_per_channel, uint32_t source_rate, uint32_t target_rate, size_t out_first, size_t out_count,
+                          size_t *src_first, size_t *src_count);
+int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *options, size_t *samples);
+int gdg_batch_stream_need(gdg_ctx *ctx, int blocks, size_t *first, size_t *count);
+int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes);
+int gdg_batch_stream_close(gdg_ctx *ctx);
 /* The device buffers of a batch run (the decoded inputs are the large part: N x length x 8 bytes) stay with the context for the next
  * run of the same or a smaller size; this frees them. */
 int gdg_batch_release(gdg_ctx *ctx);
