@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "gdg_resample_time_length", "gdg_resample_time", "gdg_resample_time_device",
     "gdg_meter_configure", "gdg_meter_set_enabled", "gdg_meter_process", "gdg_meter_process_device", "gdg_meter_analyze", "gdg_meter_state",
     "gdg_metronome_set_tick", "gdg_metronome_set_tock", "gdg_metronome_configure", "gdg_metronome_process", "gdg_metronome_process_device",
-    "gdg_batch_length", "gdg_batch_run", "gdg_batch_run_shard", "gdg_batch_finish_master", "gdg_batch_release", "gdg_batch_stream_span", "gdg_batch_stream_open", "gdg_batch_stream_need", "gdg_batch_stream_step", "gdg_batch_stream_close", "gdg_profile_sample", "gdg_ctx_set_window", "gdg_process_window_device", "gdg_ctx_set_overlap",
+    "gdg_batch_length", "gdg_batch_run", "gdg_batch_run_shard", "gdg_batch_finish_master", "gdg_batch_release", "gdg_batch_stream_span", "gdg_batch_stream_open", "gdg_batch_stream_need", "gdg_batch_stream_step", "gdg_batch_stream_close", "gdg_batch_stream_open_shard", "gdg_batch_stream_step_shard", "gdg_batch_finish_master_slice", "gdg_profile_sample", "gdg_ctx_set_window", "gdg_process_window_device", "gdg_ctx_set_overlap",
     "gdg_ctx_set_option", "gdg_ctx_get_option", "gdg_option_count", "gdg_option_name", "gdg_numa_probe", "gdg_ctx_trim", "gdg_tuner_replace",
     "gdg_state_size", "gdg_state_save", "gdg_state_save_device", "gdg_state_load", "gdg_state_load_device",
 ]
@@ -199,6 +199,9 @@ def lib():
             "gdg_batch_stream_need": (i32, [vp, i32, vp, vp]),
             "gdg_batch_stream_step": (i32, [vp, i32, vp, vp]),
             "gdg_batch_stream_close": (i32, [vp]),
+            "gdg_batch_stream_open_shard": (i32, [vp, vp, i32, vp, C.c_size_t, i32, C.POINTER(C.c_size_t)]),
+            "gdg_batch_stream_step_shard": (i32, [vp, i32, vp, vp, vp]),
+            "gdg_batch_finish_master_slice": (i32, [vp, i32, vp, vp, i32, vp, C.c_size_t, u32, i32, vp, vp]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
             "gdg_ctx_get_option": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -731,17 +734,37 @@ class Context:
         return ml, mr
 
     # -- the streamed batch run: the job of batch_run in slices of whole blocks (gdg_batch_stream_*) --------------------------
-    def batch_stream_open(self, inputs, target_rate, out_format, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
-        """inputs: per channel None or (samples_per_channel of the FILE, format, sample_rate[, channels, channel]); returns the samples of
-        every output."""
-        n = len(inputs)
-        arr = (BatchInput * n)()
+    @staticmethod
+    def _stream_metas(inputs):
+        arr = (BatchInput * len(inputs))()
         for i, it in enumerate(inputs):
             if it is None or not it[0]:
                 continue
             channels, channel = (it[3], it[4]) if len(it) > 3 else (1, 0)
             f = WAVE_FORMATS[it[1]] if isinstance(it[1], str) else it[1]
             arr[i] = BatchInput(C.addressof(arr), int(it[0]), f, it[2], channels, channel)      # bytes: never read, only "not NULL"
+        return arr
+
+    @staticmethod
+    def _stream_split(inputs):
+        """(metas, datas, widths) of batch_run's input tuples: what the open call is told, the data sections, bytes per frame"""
+        metas, datas, widths = [], [], []
+        for it in inputs:
+            if it is None:
+                metas.append(None), datas.append(None), widths.append(0)
+                continue
+            data = np.ascontiguousarray(it[0], dtype=np.uint8)
+            f = WAVE_FORMATS[it[1]] if isinstance(it[1], str) else it[1]
+            channels = it[3] if len(it) > 3 else 1
+            w = max(lib().gdg_wave_bytes_per_sample(f), 1) * max(channels, 1)
+            metas.append((data.size // w,) + tuple(it[1:])), datas.append(data), widths.append(w)
+        return metas, datas, widths
+
+    def batch_stream_open(self, inputs, target_rate, out_format, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
+        """inputs: per channel None or (samples_per_channel of the FILE, format, sample_rate[, channels, channel]); returns the samples of
+        every output."""
+        n = len(inputs)
+        arr = self._stream_metas(inputs)
         fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
         opt = BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
         length = C.c_size_t(0)
@@ -779,16 +802,7 @@ class Context:
         """batch_run as a generator: the same `inputs` tuples (whole data sections; a real host would read each slice's frames from its
         files instead), cut into slices of `blocks_per_slice` blocks (an int, or a function (blocks_left) -> blocks).  Yields every
         slice's N + 3 output pieces; their concatenation is batch_run's result."""
-        metas, datas, widths = [], [], []
-        for it in inputs:
-            if it is None:
-                metas.append(None), datas.append(None), widths.append(0)
-                continue
-            data = np.ascontiguousarray(it[0], dtype=np.uint8)
-            f = WAVE_FORMATS[it[1]] if isinstance(it[1], str) else it[1]
-            channels = it[3] if len(it) > 3 else 1
-            w = max(lib().gdg_wave_bytes_per_sample(f), 1) * max(channels, 1)
-            metas.append((data.size // w,) + tuple(it[1:])), datas.append(data), widths.append(w)
+        metas, datas, widths = self._stream_split(inputs)
         length = self.batch_stream_open(metas, target_rate, out_format, metronome_to_master, run_meters, tuner_enqueue)
         try:
             left = length // 8192
@@ -797,6 +811,80 @@ class Context:
                 need = self.batch_stream_need(blocks)
                 ins = [None if d is None or not c else d[f * w:(f + c) * w] for d, w, (f, c) in zip(datas, widths, need)]
                 yield self.batch_stream_step(blocks, ins)
+                left -= blocks
+        finally:
+            try:
+                self.batch_stream_close()
+            except GdgError:
+                pass                            # a slice that failed has closed the job itself
+
+    # -- ... and of ONE SHARD of a job split over several contexts (gdg_batch_stream_open_shard / _step_shard, gdg_batch_finish_master_slice)
+    def batch_stream_open_shard(self, inputs, target_rate, out_format, job_samples=0, metronome=False, run_meters=False, tuner_enqueue=False,
+                                metronome_to_master=False):
+        """batch_stream_open for the channels of one shard; `metronome`: this shard runs the job's metronome.  Returns the job's samples
+        (metronome_to_master is only there to be refused: the aux input joins the master in batch_finish_master_slice)."""
+        n = len(inputs)
+        arr = self._stream_metas(inputs)
+        fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
+        opt = BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
+        length = C.c_size_t(0)
+        self._check(lib().gdg_batch_stream_open_shard(self._h, arr, n, C.byref(opt), job_samples, int(bool(metronome)), C.byref(length)))
+        self._stream_width = lib().gdg_wave_bytes_per_sample(fo)
+        return length.value
+
+    def batch_stream_step_shard(self, blocks, in_bytes, metronome=False, outs=None):
+        """One slice of a shard's job: returns (outs, left, right, metronome_bytes, metronome_f64) as batch_run_shard does, of
+        blocks * 8192 samples each.  metronome: True, False, or a pair (encoded track?, float64 track?)."""
+        n = self.n_channels
+        keep = [None if b is None else np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b, dtype=np.uint8)
+                for b in in_bytes]
+        assert len(keep) == n
+        ins = (C.c_void_p * n)(*[(b.ctypes.data if b is not None and b.size else None) for b in keep])
+        count = blocks * 8192
+        size = count * self._stream_width
+        if outs is None:
+            outs = [np.zeros(size, dtype=np.uint8) for _ in range(n)]
+        assert len(outs) == n and all(o is None or (o.dtype == np.uint8 and o.size == size) for o in outs)
+        ptrs = (C.c_void_p * n)(*[(o.ctypes.data if o is not None else None) for o in outs])
+        want_bytes, want_f64 = metronome if isinstance(metronome, tuple) else (metronome, metronome)
+        left, right = np.zeros(count), np.zeros(count)
+        mb = np.zeros(size, dtype=np.uint8) if want_bytes else None
+        mf = np.zeros(count) if want_f64 else None
+        so = BatchShardOut(left.ctypes.data, right.ctypes.data, mb.ctypes.data if mb is not None else None,
+                           mf.ctypes.data if mf is not None else None, 0)
+        self._check(lib().gdg_batch_stream_step_shard(self._h, blocks, ins, ptrs, C.byref(so)))
+        return outs, left, right, mb, mf
+
+    def batch_finish_master_slice(self, out_format, lefts, rights, aux=None, sample_rate=0, run_meters=False):
+        """batch_finish_master for one slice (whole blocks) of a streamed sharded job: the same bytes, one upload, one kernel and one
+        download per piece (gdg_batch_finish_master_slice)."""
+        G, n = len(lefts), lefts[0].size
+        fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
+        wo = lib().gdg_wave_bytes_per_sample(fo)
+        lefts = [_f64(a) for a in lefts]
+        rights = [_f64(a) for a in rights]
+        lp = (C.c_void_p * G)(*[a.ctypes.data for a in lefts])
+        rp = (C.c_void_p * G)(*[a.ctypes.data for a in rights])
+        ml, mr = np.zeros(n * wo, dtype=np.uint8), np.zeros(n * wo, dtype=np.uint8)
+        a = _f64(aux) if aux is not None else None
+        self._check(lib().gdg_batch_finish_master_slice(self._h, fo, lp, rp, G, a.ctypes.data if a is not None else None, n, sample_rate,
+                                                        int(bool(run_meters)), ml.ctypes.data if n else None, mr.ctypes.data if n else None))
+        return ml, mr
+
+    def batch_stream_shard(self, inputs, target_rate, out_format, blocks_per_slice, job_samples=0, metronome=False, run_meters=False,
+                           tuner_enqueue=False):
+        """batch_run_shard as a generator, in the style of batch_stream: yields (outs, left, right, metronome_bytes, metronome_f64) per
+        slice; their concatenation is batch_run_shard's result.  Every shard of a job is sliced alike; the caller finishes each slice's
+        master with batch_finish_master_slice."""
+        metas, datas, widths = self._stream_split(inputs)
+        length = self.batch_stream_open_shard(metas, target_rate, out_format, job_samples, metronome, run_meters, tuner_enqueue)
+        try:
+            left = length // 8192
+            while left:
+                blocks = min(left, blocks_per_slice(left) if callable(blocks_per_slice) else blocks_per_slice)
+                need = self.batch_stream_need(blocks)
+                ins = [None if d is None or not c else d[f * w:(f + c) * w] for d, w, (f, c) in zip(datas, widths, need)]
+                yield self.batch_stream_step_shard(blocks, ins, metronome)
                 left -= blocks
         finally:
             try:

@@ -1,6 +1,6 @@
 /*
- * api_batch.cpp -- controller.processFiles on the device: gdg_batch_run, its streamed form (slices of whole blocks), its sharded form
- * and the master mix.
+ * api_batch.cpp -- controller.processFiles on the device: gdg_batch_run, its sharded form, the streamed form of both (slices of whole
+ * blocks) and the master mix of a job and of a slice.
  * Part of the host side of libgdg.so (the C-ABI of include/gdg.h on top of the HIP kernels; see ctx.h for the map).
  * There is no CPU compute path here: every sample is produced by a HIP kernel.
  */
@@ -568,7 +568,9 @@ int gdg_batch_stream_span(size_t samples_per_channel, uint32_t source_rate, uint
     return GDG_OK;
 }
 
-int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t *samples) {
+/* `shard`: the job of gdg_batch_run_shard (job_samples, run_metronome) instead of gdg_batch_run's */
+static int stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
+                       bool run_metronome, size_t *samples) {
     if (!ctx || !inputs || !opt || !samples) return GDG_ERR_INVALID;
     auto &S = ctx->bstream;
     if (S.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is already open on this context");
@@ -578,7 +580,8 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
     if (!gdg_wave_bytes_per_sample(opt->out_format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", opt->out_format);
     if (opt->target_rate == 0) return fail(ctx, GDG_ERR_INVALID, "sample rate must be positive");
     if (opt->run_meters && ctx->n_meter != 2 * n_inputs + 3)
-        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d", ctx->n_meter, 2 * n_inputs + 3);
+        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d%s", ctx->n_meter, 2 * n_inputs + 3,
+                    shard ? " (a shard: its N inputs, its N outputs, metronome, left, right)" : "");
     std::vector<size_t> n_out((size_t)n_inputs, 0);
     size_t max_len = 0;
     for (int i = 0; i < n_inputs; i++) {
@@ -591,6 +594,13 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
         max_len = std::max(max_len, n_out[(size_t)i]);
     }
     if (max_len % GDG_BLOCK_SIZE) max_len = GDG_BLOCK_SIZE * (max_len / GDG_BLOCK_SIZE + 1);       /* controller.go:3014-3016 */
+    if (shard && job_samples) {                                                  /* the shard pads to the job's length, as gdg_batch_run_shard does */
+        if (job_samples < max_len || job_samples % GDG_BLOCK_SIZE)
+            return fail(ctx, GDG_ERR_INVALID, "the job's %zu samples: at least this shard's %zu and a multiple of %d", job_samples, max_len, GDG_BLOCK_SIZE);
+        max_len = job_samples;
+    }
+    S.shard = shard;
+    S.run_metro = shard ? run_metronome : true;
     S.inputs.assign(inputs, inputs + n_inputs);
     S.opt = *opt;
     S.length = max_len;
@@ -600,6 +610,19 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
     S.open = true;
     *samples = max_len;
     return GDG_OK;
+}
+
+int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t *samples) {
+    return stream_open(ctx, inputs, n_inputs, opt, false, 0, true, samples);
+}
+
+int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t job_samples,
+                                int run_metronome, size_t *samples) {
+    /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
+    if (ctx && opt && opt->metronome_to_master)
+        return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_open_shard: metronome_to_master must be 0 -- a shard's master mix is a partial sum; pass the metronome's "
+                    "float64 track (gdg_batch_shard_out.metronome of the shard that runs it) as `aux` to gdg_batch_finish_master_slice");
+    return stream_open(ctx, inputs, n_inputs, opt, true, job_samples, run_metronome != 0, samples);
 }
 
 /* the source frames [first, first + count) of every input that the job's samples [pos, pos + blocks * 8192) bring */
@@ -640,12 +663,20 @@ int gdg_batch_stream_close(gdg_ctx *ctx) {
     return GDG_OK;
 }
 
-int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes) {
+/* one slice; `slice` non-null: of a job opened as a shard (the slice's partial master and metronome buffers) */
+static int stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice, bool as_shard) {
     if (!ctx) return GDG_ERR_INVALID;
     int rc = stream_check_blocks(ctx, blocks);
     if (rc != GDG_OK) return rc;
-    if (!in_bytes || !out_bytes) return fail(ctx, GDG_ERR_INVALID, "a slice needs its input and output buffer lists");
     auto &S = ctx->bstream;
+    if (as_shard != S.shard)
+        return fail(ctx, GDG_ERR_INVALID, as_shard ? "gdg_batch_stream_step_shard: the open job is not a shard's (gdg_batch_stream_open): gdg_batch_stream_step runs its slices"
+                                                   : "gdg_batch_stream_step: the open job is a shard's (gdg_batch_stream_open_shard): gdg_batch_stream_step_shard runs its slices");
+    if (!in_bytes || !out_bytes) return fail(ctx, GDG_ERR_INVALID, "a slice needs its input and output buffer lists");
+    if (as_shard && (!slice || !slice->master_left || !slice->master_right)) return fail(ctx, GDG_ERR_INVALID, "a shard needs buffers for its partial master mix");
+    if (as_shard && !S.run_metro && (slice->metronome_bytes || slice->metronome))
+        return fail(ctx, GDG_ERR_INVALID, "this shard's job was opened without the metronome (run_metronome = 0): a slice cannot ask for its track");
+    const bool sharded = as_shard;
     const gdg_batch_options *opt = &S.opt;
     const int N = ctx->nch, NO = N + 3, B = GDG_BLOCK_SIZE, out_width = gdg_wave_bytes_per_sample(opt->out_format);
     const size_t length = (size_t)blocks * B, pos = S.pos;                       /* the slice: rows of `length` samples, the job's [pos, pos + length) */
@@ -658,7 +689,11 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
     enter(ctx);
     const int W = ctx->window;
     const size_t ws = (size_t)W * B;
-    const size_t enc_bytes = ((size_t)NO * ws * (size_t)out_width + 15) & ~(size_t)15;
+    /* a shard's slice: the rows that leave the device encoded and as float64 are this slice's (which metronome buffers it passes), the
+     * room for them is the job's (whether the shard runs the metronome): no slice makes a buffer grow */
+    const int enc_rows = !sharded ? NO : N + (slice->metronome_bytes ? 1 : 0), f64_rows = !sharded ? 0 : 2 + (slice->metronome ? 1 : 0);
+    const int enc_room = !sharded ? NO : N + (S.run_metro ? 1 : 0), f64_room = !sharded ? 0 : 2 + (S.run_metro ? 1 : 0);
+    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -765,8 +800,8 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
             HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
             return GDG_OK;
         };
-        BatchLoop loop{ N, NO, 0, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, nullptr, true, any, trace, t_begin,
-                        S.length / B, pos / B };
+        BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, sharded ? slice : nullptr,
+                        S.run_metro, any, trace, t_begin, S.length / B, pos / B };
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -777,6 +812,14 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
     for (int i = 0; i < N; i++) S.brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
     S.pos += length;
     return GDG_OK;
+}
+
+int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes) {
+    return stream_step(ctx, blocks, in_bytes, out_bytes, nullptr, false);
+}
+
+int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
+    return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
 
 int gdg_batch_run(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes) {
@@ -836,4 +879,111 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return GDG_OK;
+}
+
+/* gdg_batch_finish_master for one slice of a streamed sharded job, where it runs once per slice on the job's critical path: the same sums
+ * and the same encoder, hence the same bits, but per piece ONE upload, ONE kernel and ONE download.  The copy workers gather the G partial
+ * pairs and aux into a pinned slab half ([2 G + 1][n] float64) while the piece before is on the bus; finish_master_kernel (io.hip) adds and
+ * encodes; the encoded piece comes down into a pinned half and is scattered into the caller's buffers while the next piece computes. */
+int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
+                                  size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+    if (!ctx || !left || !right || n_shards <= 0) return GDG_ERR_INVALID;
+    const int width = gdg_wave_bytes_per_sample(out_format);
+    if (!width) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", out_format);
+    for (int g = 0; g < n_shards; g++) if (!left[g] || !right[g]) return fail(ctx, GDG_ERR_INVALID, "shard %d has no partial master mix", g);
+    if (run_meters && (ctx->n_meter < 2 || sample_rate == 0)) return fail(ctx, GDG_ERR_INVALID, "master meters: the context's last two ports, at a positive rate");
+    if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);
+    if (samples == 0) return GDG_OK;
+    enter(ctx);
+    const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0), B = GDG_BLOCK_SIZE;
+    /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the slice and the shard count */
+    const size_t piece = B * std::min((size_t)128, std::max((size_t)1, ((size_t)8 << 20) / ((2 * G + 1) * B * sizeof(double))));
+    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = 2 * piece * (size_t)width;
+    if (!ctx->fin_up[0])
+        for (int h = 0; h < 2; h++) {
+            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_down[h], hipEventDisableTiming));
+        }
+    if (up_bytes > ctx->h_fin_up_cap) {
+        for (int h = 0; h < 2; h++) { if (ctx->h_fin_up[h]) hipHostFree(ctx->h_fin_up[h]); ctx->h_fin_up[h] = nullptr; }
+        ctx->h_fin_up_cap = 0;
+        for (int h = 0; h < 2; h++) HIP_TRY(ctx, pinned_alloc(ctx, (void **)&ctx->h_fin_up[h], up_bytes));
+        ctx->h_fin_up_cap = up_bytes;
+    }
+    if (down_bytes > ctx->h_fin_down_cap) {
+        for (int h = 0; h < 2; h++) { if (ctx->h_fin_down[h]) hipHostFree(ctx->h_fin_down[h]); ctx->h_fin_down[h] = nullptr; }
+        ctx->h_fin_down_cap = 0;
+        for (int h = 0; h < 2; h++) HIP_TRY(ctx, pinned_alloc(ctx, (void **)&ctx->h_fin_down[h], down_bytes));
+        ctx->h_fin_down_cap = down_bytes;
+    }
+    /* the device side: two slab halves (+ the two rows of sums the meters read), two halves of encoded rows */
+    int rc = ensure_io(ctx, 1, 2 * up_bytes + 2 * piece * sizeof(double));
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * down_bytes);
+    if (rc != GDG_OK) return rc;
+    unsigned char *d_slab = static_cast<unsigned char *>(ctx->d_io[1]), *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
+    double *d_sums = run_meters ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
+    const size_t n_pieces = (samples + piece - 1) / piece;
+    auto span = [&](size_t k) { return std::min(piece, samples - k * piece); };
+    auto body = [&]() -> int {
+        /* piece k's rows into its pinned half: [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux], n samples apart */
+        auto gather = [&](size_t k) -> int {
+            const int h = (int)(k & 1);
+            const size_t n = span(k), at = k * piece;
+            if (k >= 2) HIP_TRY(ctx, hipEventSynchronize(ctx->fin_up[h]));     /* piece k - 2 has left this half */
+            std::vector<BatchPiece> pieces;
+            for (size_t r = 0; r < rows; r++) {
+                const double *src = (r < G ? left[r] : r < 2 * G ? right[r - G] : aux) + at;
+                const size_t row_at = (r < 2 * G ? r : 2 * G) * n * sizeof(double);
+                for (size_t q = 0; q < n * sizeof(double); q += (size_t)1 << 18)      /* pieces of <= 256 KiB: every worker gets some */
+                    pieces.push_back({ ctx->h_fin_up[h] + row_at + q, reinterpret_cast<const unsigned char *>(src) + q, std::min(n * sizeof(double) - q, (size_t)1 << 18) });
+            }
+            move_pieces(ctx, pieces);
+            return GDG_OK;
+        };
+        auto enqueue = [&](size_t k) -> int {
+            const int h = (int)(k & 1);
+            const size_t n = span(k);
+            unsigned char *slab = d_slab + (size_t)h * up_bytes, *enc = d_enc + (size_t)h * down_bytes;
+            HIP_TRY(ctx, hipMemcpyAsync(slab, ctx->h_fin_up[h], rows * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(ctx->fin_up[h], ctx->stream));
+            {
+                ProfScope ps(ctx, GDG_K_WAVE);
+                HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), n, n_shards, aux != nullptr, n, enc, enc + piece * (size_t)width,
+                                                      d_sums, piece, ctx->stream));
+            }
+            if (run_meters)
+                for (size_t o = 0; o < n; o += B)                                /* block by block, like the loop that fed the other ports */
+                    if ((rc = meter_rows(ctx, d_sums + o, piece, ctx->n_meter - 2, 2, (int)B, sample_rate)) != GDG_OK) return rc;
+            /* the download of piece k - 2 into this pinned half has been scattered: scatter(k - 2) ran before enqueue(k) */
+            if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * (size_t)width, hipMemcpyDeviceToHost, ctx->stream));
+            if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + piece * (size_t)width, enc + piece * (size_t)width, n * (size_t)width, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(ctx->fin_down[h], ctx->stream));
+            return GDG_OK;
+        };
+        auto scatter = [&](size_t k) -> int {
+            const int h = (int)(k & 1);
+            const size_t nb = span(k) * (size_t)width, at = k * piece * (size_t)width;
+            HIP_TRY(ctx, hipEventSynchronize(ctx->fin_down[h]));
+            std::vector<BatchPiece> pieces;
+            for (int side = 0; side < 2; side++) {
+                unsigned char *dst = static_cast<unsigned char *>(side ? right_bytes : left_bytes);
+                if (!dst) continue;
+                const unsigned char *src = ctx->h_fin_down[h] + (size_t)side * piece * (size_t)width;
+                for (size_t q = 0; q < nb; q += (size_t)1 << 18) pieces.push_back({ dst + at + q, src + q, std::min(nb - q, (size_t)1 << 18) });
+            }
+            move_pieces(ctx, pieces);
+            return GDG_OK;
+        };
+        int r;
+        if ((r = gather(0)) != GDG_OK || (r = enqueue(0)) != GDG_OK) return r;
+        for (size_t k = 0; k < n_pieces; k++) {
+            if (k + 1 < n_pieces && (r = gather(k + 1)) != GDG_OK) return r;    /* while piece k is on the bus */
+            if (k >= 1 && (r = scatter(k - 1)) != GDG_OK) return r;             /* frees the pinned half piece k + 1 comes down into */
+            if (k + 1 < n_pieces && (r = enqueue(k + 1)) != GDG_OK) return r;
+        }
+        return scatter(n_pieces - 1);
+    };
+    rc = body();
+    hipStreamSynchronize(ctx->stream);                                           /* the caller's rows are never read after the call, whatever happened */
+    return rc;
 }

@@ -314,6 +314,12 @@ int gdg_ctx_destroy(gdg_ctx *ctx) {
         if (ctx->h_up[h]) hipHostFree(ctx->h_up[h]);
         if (ctx->batch_up_ready[h]) hipEventDestroy(ctx->batch_up_ready[h]);
     }
+    for (int h = 0; h < 2; h++) {
+        if (ctx->h_fin_up[h]) hipHostFree(ctx->h_fin_up[h]);
+        if (ctx->h_fin_down[h]) hipHostFree(ctx->h_fin_down[h]);
+        if (ctx->fin_up[h]) hipEventDestroy(ctx->fin_up[h]);
+        if (ctx->fin_down[h]) hipEventDestroy(ctx->fin_down[h]);
+    }
     if (ctx->batch_begin) hipEventDestroy(ctx->batch_begin);
     for (int i = 0; i < 6; i++) hipFree(ctx->batch_dev[i]);
     if (ctx->batch_up_stream) hipStreamDestroy(ctx->batch_up_stream);

@@ -9,7 +9,7 @@
  *   api_process.cpp     parameter patches, process_rows (the launch sequence of a call), the process entry points, staging + copy workers
  *   api_tuner_spat.cpp  tuner and spatializer glue
  *   api_io.cpp          wave codecs, resample.Time, level meters, power-amp compilation, metronome
- *   api_batch.cpp       the batch run (gdg_batch_run, its sharded form, the master mix)
+ *   api_batch.cpp       the batch run (gdg_batch_run, its sharded form, the streamed forms of both, the master mix of a job and of a slice)
  *   api_state.cpp       channel state saved into / loaded from a blob (gdg_state_*; the copies: state.hip)
  */
 #ifndef GDG_CTX_H
@@ -349,7 +349,12 @@ struct gdg_ctx {
         size_t length = 0, pos = 0;            /* samples of every output; samples done */
         std::vector<size_t> brought;           /* source frames [0, brought) of input i have been handed over */
         std::vector<size_t> n_out;             /* samples the input covers in the job: its (resampled) length */
+        bool shard = false, run_metro = false; /* opened with gdg_batch_stream_open_shard; ... and this shard runs the job's metronome */
     } bstream;
+    /* gdg_batch_finish_master_slice: the partials of a piece gathered into a pinned slab half, the encoded piece back through another */
+    unsigned char *h_fin_up[2] = { nullptr, nullptr }, *h_fin_down[2] = { nullptr, nullptr };
+    size_t h_fin_up_cap = 0, h_fin_down_cap = 0;
+    hipEvent_t fin_up[2] = { nullptr, nullptr }, fin_down[2] = { nullptr, nullptr };     /* a half's upload has left it / its download has landed */
     /* channel groups of the host-buffer paths: group g's upload, kernels and download run on stream g, so one group's
      * PCIe transfers overlap the other groups' kernels (channels are independent) */
     int plan_groups = 1;

@@ -606,6 +606,92 @@ hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_s
     return hipGetLastError();
 }
 
+/* The master of one piece of a sharded job in ONE launch (gdg_batch_finish_master_slice): the slab holds G left rows, G right rows and the
+ * aux row, `stride` samples apart.  A thread takes four consecutive samples of both sides: p_0, then + p_1 .. + p_{G-1} in shard order,
+ * then + aux -- the adds of accumulate_kernel and add_aux_kernel one after the other, so the same bits -- and encodes them into whole
+ * words as wave_encode4_kernel does (IEEE64: the sums are the bytes, wave.go:694-709).  Every partial is read once and never again:
+ * non-temporal loads, and non-temporal stores for what goes straight down the bus.  SUMS: the float64 sums stay for the meters. */
+template <int FMT, bool SUMS>
+__global__ void __launch_bounds__(256)
+finish_master_kernel(const double *__restrict__ slab, size_t stride, int G, int has_aux, size_t groups, unsigned *__restrict__ words_left,
+                     unsigned *__restrict__ words_right, double *__restrict__ sums, size_t sums_stride) {
+    constexpr int W = fmt_width<FMT>::W;
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= groups) return;
+    const size_t rs = stride / 2;                                  /* v2d per row */
+    const v2d *col = reinterpret_cast<const v2d *>(slab) + 2 * g;
+    v2d xa = { 0.0, 0.0 }, xb = { 0.0, 0.0 };
+    if (has_aux) { const v2d *q = col + (size_t)(2 * G) * rs; xa = __builtin_nontemporal_load(q); xb = __builtin_nontemporal_load(q + 1); }
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+        const v2d *p = col + (size_t)(side * G) * rs;
+        v2d a = __builtin_nontemporal_load(p), b = __builtin_nontemporal_load(p + 1);
+#pragma unroll 4
+        for (int k = 1; k < G; k++) {
+            p += rs;
+            a += __builtin_nontemporal_load(p);
+            b += __builtin_nontemporal_load(p + 1);
+        }
+        if (has_aux) { a += xa; b += xb; }
+        if (SUMS) {
+            v2d *out = reinterpret_cast<v2d *>(sums + (size_t)side * sums_stride) + 2 * g;
+            out[0] = a;
+            out[1] = b;
+        }
+        unsigned *words = side ? words_right : words_left;
+        if (!words) continue;
+        if (FMT == GDG_FMT_IEEE64) {
+            v2d *out = reinterpret_cast<v2d *>(words) + 2 * g;
+            __builtin_nontemporal_store(a, out);
+            __builtin_nontemporal_store(b, out + 1);
+        } else {
+            const double r[4] = { a.x, a.y, b.x, b.y };
+            unsigned w[W];
+#pragma unroll
+            for (int k = 0; k < W; k++) w[k] = 0;
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                unsigned code = encode_code<FMT>(r[s]);
+#pragma unroll
+                for (int k = 0; k < W; k++) {
+                    int byte = s * W + k;
+                    w[byte >> 2] |= ((code >> (8 * k)) & 0xffu) << ((byte & 3) * 8);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], words + g * W + k);
+        }
+    }
+}
+
+template <int FMT>
+static void launch_finish_master(const double *d_slab, size_t stride, int G, int has_aux, size_t n, void *d_left, void *d_right, double *d_sums,
+                                 size_t sums_stride, hipStream_t s) {
+    const size_t groups = n / 4;
+    const unsigned grid = (unsigned)((groups + 255) / 256);
+    unsigned *wl = static_cast<unsigned *>(d_left), *wr = static_cast<unsigned *>(d_right);
+    if (d_sums) finish_master_kernel<FMT, true><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride);
+    else finish_master_kernel<FMT, false><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, nullptr, 0);
+}
+
+hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
+                                    void *d_right_bytes, double *d_sums, size_t sums_stride, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n_shards < 1 || (n & 3) || n > stride || (stride & 1) || (sums_stride & 1) || (d_sums && n > sums_stride) || ((uintptr_t)d_slab & 15) ||
+        ((uintptr_t)d_left_bytes & 15) || ((uintptr_t)d_right_bytes & 15) || ((uintptr_t)d_sums & 15))
+        return hipErrorInvalidValue;
+    switch (fmt) {
+    case GDG_FMT_LPCM8: launch_finish_master<GDG_FMT_LPCM8>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
+    case GDG_FMT_LPCM16: launch_finish_master<GDG_FMT_LPCM16>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
+    case GDG_FMT_LPCM24: launch_finish_master<GDG_FMT_LPCM24>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
+    case GDG_FMT_LPCM32: launch_finish_master<GDG_FMT_LPCM32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
+    case GDG_FMT_IEEE32: launch_finish_master<GDG_FMT_IEEE32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
+    case GDG_FMT_IEEE64: launch_finish_master<GDG_FMT_IEEE64>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 /* resample.Time over a span of a file (the streamed batch run): blockIdx.y = input.  Output samples [out_first, out_first + count) from
  * the source frames [src_first, src_first + src_count) at `src`; n = the FILE's frames (the j < n bound).  x, floor(x) and x - j are
  * formed from the absolute 64-bit i and j in the operation order of resample_time_kernel, so every sample has the whole-file kernel's

@@ -895,6 +895,117 @@ func (this *Context) BatchStreamClose() error {
 	return this.err(C.gdg_batch_stream_close(this.ctx))
 }
 
+// BatchStreamOpenShard begins the job of BatchRunShard in slices (gdg_batch_stream_open_shard): one shard of a job split over several
+// contexts whose files are too long to hold.  jobSamples = the job's length (the longest BatchLength over all shards, 0 = this shard's
+// own); runMetronome says once, for the whole job, whether this shard runs the metronome.  opt.MetronomeToMaster must be false: the aux
+// input joins the master in FinishMasterSlice.  Returns the samples of every output.  BatchStreamNeed and BatchStreamClose serve the job.
+func (this *Context) BatchStreamOpenShard(inputs []BatchStreamInput, opt BatchOptions, jobSamples uint64, runMetronome bool) (uint64, error) {
+	n := len(inputs)
+	if n == 0 {
+		return 0, fmt.Errorf("gdg: no inputs")
+	}
+	arr := (*[1 << 20]C.gdg_batch_input)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.gdg_batch_input{}))))
+	if arr == nil {
+		return 0, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(arr))
+	for i, in := range inputs {
+		if in.Frames == 0 {
+			continue
+		}
+		arr[i].bytes = unsafe.Pointer(arr) // never read: only "not NULL"
+		arr[i].samples_per_channel = C.size_t(in.Frames)
+		arr[i].format = C.int(in.Format)
+		arr[i].sample_rate = C.uint32_t(in.SampleRate)
+		arr[i].channels = C.uint(in.Channels)
+		arr[i].channel = C.uint(in.Channel)
+	}
+	o := C.gdg_batch_options{target_rate: C.uint32_t(opt.TargetRate), out_format: C.int(opt.OutFormat),
+		metronome_to_master: cbool(opt.MetronomeToMaster), run_meters: cbool(opt.RunMeters), tuner_enqueue: cbool(opt.TunerEnqueue)}
+	var samples C.size_t
+	if e := this.err(C.gdg_batch_stream_open_shard(this.ctx, &arr[0], C.int(n), &o, C.size_t(jobSamples), cbool(runMetronome), &samples)); e != nil {
+		return 0, e
+	}
+	this.streamInputs = n
+	this.streamWidth = int(C.gdg_wave_bytes_per_sample(o.out_format))
+	return uint64(samples), nil
+}
+
+// BatchStreamStepShard runs one slice of a shard's job (gdg_batch_stream_step_shard): frames as for BatchStreamStep; the result holds the
+// slice's n chain outputs, the shard's partial master mix of the slice and, with wantMetronome (only on a job opened with
+// runMetronome), the slice's metronome track -- blocks * 8192 samples each.
+func (this *Context) BatchStreamStepShard(blocks int, frames [][]byte, wantMetronome bool) (*ShardResult, error) {
+	n := this.streamInputs
+	if n == 0 || len(frames) != n {
+		return nil, fmt.Errorf("gdg: %d inputs for a streamed batch run of %d", len(frames), n)
+	}
+	count := blocks * 8192
+	each := count * this.streamWidth
+	if blocks <= 0 || each <= 0 {
+		return nil, fmt.Errorf("gdg: a slice of %d blocks", blocks)
+	}
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	alloc := func(bytes int) unsafe.Pointer {
+		p := C.malloc(C.size_t(bytes))
+		if p != nil {
+			owned = append(owned, p)
+		}
+		return p
+	}
+	ptrs := (*[1 << 20]unsafe.Pointer)(C.calloc(C.size_t(2*n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if ptrs == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(ptrs))
+	for i, f := range frames {
+		if len(f) == 0 {
+			continue
+		}
+		ptrs[i] = C.CBytes(f)
+		if ptrs[i] == nil {
+			return nil, fmt.Errorf("gdg: out of memory (%d bytes of input %d)", len(f), i)
+		}
+		owned = append(owned, ptrs[i])
+	}
+	for i := n; i < 2*n; i++ {
+		if ptrs[i] = alloc(each); ptrs[i] == nil {
+			return nil, fmt.Errorf("gdg: out of memory (%d bytes per output)", each)
+		}
+	}
+	var so C.gdg_batch_shard_out
+	so.master_left = (*C.double)(alloc(count * 8))
+	so.master_right = (*C.double)(alloc(count * 8))
+	if so.master_left == nil || so.master_right == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	if wantMetronome {
+		so.metronome_bytes = alloc(each)
+		so.metronome = (*C.double)(alloc(count * 8))
+		if so.metronome_bytes == nil || so.metronome == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+	}
+	if e := this.err(C.gdg_batch_stream_step_shard(this.ctx, C.int(blocks), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[0])), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[n])), &so)); e != nil {
+		return nil, e
+	}
+	res := &ShardResult{Outputs: make([][]byte, n)}
+	for i := range res.Outputs {
+		res.Outputs[i] = goBytes(ptrs[n+i], each)
+	}
+	res.Left = goFloats(unsafe.Pointer(so.master_left), count)
+	res.Right = goFloats(unsafe.Pointer(so.master_right), count)
+	if wantMetronome {
+		res.MetronomeBytes = goBytes(so.metronome_bytes, each)
+		res.Metronome = goFloats(unsafe.Pointer(so.metronome), count)
+	}
+	return res, nil
+}
+
 // BatchRelease returns the device buffers of the last batch run to the context's arena (gdg_batch_release); the next run re-makes them.
 func (this *Context) BatchRelease() error { return this.err(C.gdg_batch_release(this.ctx)) }
 
@@ -907,6 +1018,18 @@ func Version() string { return C.GoString(C.gdg_version()) }
 // FinishMaster: master = ((p_0 + p_1) + ... + p_{G-1}) + aux per side, summed and encoded on this context's device
 // (gdg_batch_finish_master; spatializer/spatializer.go:300-310, controller/controller.go:3123-3219).  aux == nil: no aux input.
 func (this *Context) FinishMaster(outFormat int, shards []*ShardResult, aux []float64, sampleRate uint32, runMeters bool) (left []byte, right []byte, err error) {
+	return this.finishMaster(false, outFormat, shards, aux, sampleRate, runMeters)
+}
+
+// FinishMasterSlice: FinishMaster for one slice of a streamed sharded job (gdg_batch_finish_master_slice): shards = every shard's
+// BatchStreamStepShard result of the slice, in shard order; the same bytes, made for the job's critical path (one upload, one kernel
+// and one download per piece).  A context runs one call at a time: a caller who wants the finish beside shard 0's next slice gives it
+// a context of its own.
+func (this *Context) FinishMasterSlice(outFormat int, shards []*ShardResult, aux []float64, sampleRate uint32, runMeters bool) (left []byte, right []byte, err error) {
+	return this.finishMaster(true, outFormat, shards, aux, sampleRate, runMeters)
+}
+
+func (this *Context) finishMaster(slice bool, outFormat int, shards []*ShardResult, aux []float64, sampleRate uint32, runMeters bool) (left []byte, right []byte, err error) {
 	g := len(shards)
 	if g == 0 {
 		return nil, nil, fmt.Errorf("gdg: no shards")
@@ -961,7 +1084,12 @@ func (this *Context) FinishMaster(outFormat int, shards []*ShardResult, aux []fl
 		return nil, nil, fmt.Errorf("gdg: out of memory")
 	}
 	owned = append(owned, lb, rb)
-	if e := this.err(C.gdg_batch_finish_master(this.ctx, C.int(outFormat), &lp[0], &lp[g], C.int(g), cAux, C.size_t(samples), C.uint32_t(sampleRate),
+	if slice {
+		if e := this.err(C.gdg_batch_finish_master_slice(this.ctx, C.int(outFormat), &lp[0], &lp[g], C.int(g), cAux, C.size_t(samples), C.uint32_t(sampleRate),
+			cbool(runMeters), lb, rb)); e != nil {
+			return nil, nil, e
+		}
+	} else if e := this.err(C.gdg_batch_finish_master(this.ctx, C.int(outFormat), &lp[0], &lp[g], C.int(g), cAux, C.size_t(samples), C.uint32_t(sampleRate),
 		cbool(runMeters), lb, rb)); e != nil {
 		return nil, nil, e
 	}

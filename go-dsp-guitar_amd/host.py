@@ -42,6 +42,9 @@ def lib():
             "gdgh_engine_batch_stream_open": (cs, [vp, vp, i32, vp, i32, C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_need": (cs, [vp, i32, vp, vp]), "gdgh_engine_batch_stream_step": (cs, [vp, i32, vp, vp]),
             "gdgh_engine_batch_stream_close": (cs, [vp]),
+            "gdgh_engine_batch_stream_sharded_open": (cs, [vp, vp, i32, vp, i32, C.POINTER(C.c_size_t)]),
+            "gdgh_engine_batch_stream_sharded_need": (cs, [vp, i32, vp, vp]), "gdgh_engine_batch_stream_sharded_step": (cs, [vp, i32, vp, vp]),
+            "gdgh_engine_batch_stream_sharded_close": (cs, [vp]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
             "gdgh_engine_save_state": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -215,6 +218,23 @@ class Engine:
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces."""
+        L = lib()
+        return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
+                                   L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
+                                  metronome_to_master, run_meters, tuner_enqueue)
+
+    def batch_stream_sharded(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False,
+                             tuner_enqueue=False):
+        """Engine::BatchStreamShardedOpen / Need / Step / Close: batch_stream for an engine of any shard count -- every shard streams its
+        channels, the master is finished per slice; yields every slice's N + 3 output pieces (blocks_per_slice: an int or a function
+        (blocks_left) -> blocks)."""
+        L = lib()
+        return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
+                                   L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
+                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue)
+
+    def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue):
+        f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
         n = len(inputs)
@@ -232,22 +252,22 @@ class Engine:
         opt = pkg.BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
         wo = pkg.lib().gdg_wave_bytes_per_sample(fo)
         samples = C.c_size_t(0)
-        _err(lib().gdgh_engine_batch_stream_open(self._h, arr, n, C.byref(opt), window, C.byref(samples)))
+        _err(f_open(self._h, arr, n, C.byref(opt), window, C.byref(samples)))
         try:
             left = samples.value // 8192
             first, count = (C.c_size_t * n)(), (C.c_size_t * n)()
             while left:
-                blocks = min(left, blocks_per_slice)
-                _err(lib().gdgh_engine_batch_stream_need(self._h, blocks, first, count))
+                blocks = min(left, blocks_per_slice(left) if callable(blocks_per_slice) else blocks_per_slice)
+                _err(f_need(self._h, blocks, first, count))
                 pieces = [None if datas[i] is None or not count[i] else datas[i][first[i] * widths[i]:(first[i] + count[i]) * widths[i]] for i in range(n)]
                 ins = (C.c_void_p * n)(*[(p.ctypes.data if p is not None else None) for p in pieces])
                 outs = [np.zeros(blocks * 8192 * wo, dtype=np.uint8) for _ in range(n + 3)]
                 ptrs = (C.c_void_p * (n + 3))(*[o.ctypes.data for o in outs])
-                _err(lib().gdgh_engine_batch_stream_step(self._h, blocks, ins, ptrs))
+                _err(f_step(self._h, blocks, ins, ptrs))
                 yield outs
                 left -= blocks
         finally:
-            lib().gdgh_engine_batch_stream_close(self._h)
+            f_close(self._h)
 
 
 class Chain:

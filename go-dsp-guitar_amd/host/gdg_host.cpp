@@ -1025,6 +1025,146 @@ Error Engine::BatchStreamClose() {
     return "";
 }
 
+/* ---- the streamed run over all shards: BatchRun's algorithm, slice by slice ---- */
+void Engine::closeSharded() {
+    for (int g = 0; g < shards(); g++) {
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        if (shards_[(size_t)g]->ctx) (void)gdg_batch_stream_close(shards_[(size_t)g]->ctx);      /* a shard whose slice failed has closed its job itself */
+    }
+    shardedOpen_ = false;
+}
+
+Error Engine::BatchStreamShardedOpen(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, size_t *samples) {
+    if (!inputs || !samples) return "BatchStreamShardedOpen: no inputs or nowhere to put the length";
+    if (nInputs != nChannels_) return format("BatchStreamShardedOpen: %d inputs for %d channels", nInputs, nChannels_);
+    if (shardedOpen_) { setError("BatchStreamShardedOpen: a streamed batch run is already open on this engine"); return LastError(); }
+    const int G = shards();
+    setError("");
+    std::vector<std::shared_ptr<signal::Chain>> chains;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        chains = chains_;
+    }
+    /* 1. as BatchRun: every shard follows its chains, the job's length is the longest shard's */
+    size_t job = 0;
+    for (int g = 0; g < G; g++) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        if (count <= 0) continue;
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        gdg_ctx *ctx = context(g);
+        if (!ctx) return LastError();
+        std::vector<signal::Chain *> mine;
+        for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
+        Error e = sync(g, mine, options.target_rate);
+        if (!e.empty()) { setError(e); return e; }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        size_t len = 0;
+        if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        job = std::max(job, len);
+    }
+    /* 2. every shard's job, padded to that length; shard 0 runs the metronome */
+    gdg_batch_options o = options;
+    o.metronome_to_master = 0;                           /* the aux input joins the master once per slice, after the shards' sums */
+    for (int g = 0; g < G; g++) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        if (count <= 0) continue;
+        Error e;
+        {
+            std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+            gdg_ctx *ctx = shards_[(size_t)g]->ctx;
+            size_t len = 0;
+            if (gdg_batch_stream_open_shard(ctx, inputs + first, count, &o, job, g == 0, &len) != GDG_OK) e = format("shard %d: %s", g, gdg_last_error(ctx));
+        }
+        if (!e.empty()) {
+            for (int k = 0; k < g; k++) {
+                std::lock_guard<std::mutex> lk(shards_[(size_t)k]->mu);
+                if (shards_[(size_t)k]->ctx) (void)gdg_batch_stream_close(shards_[(size_t)k]->ctx);
+            }
+            setError(e);
+            return e;
+        }
+    }
+    shardedOpen_ = true;
+    shardedOptions_ = options;
+    *samples = job;
+    return "";
+}
+
+Error Engine::BatchStreamShardedNeed(int blocks, size_t *first, size_t *count) {
+    if (!first || !count) return "BatchStreamShardedNeed: nowhere to put the frames";
+    if (!shardedOpen_) return "BatchStreamShardedNeed: no streamed batch run is open";
+    for (int g = 0; g < shards(); g++) {
+        int f = 0, n = 0;
+        shardRange(g, &f, &n);
+        if (n <= 0) continue;
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        gdg_ctx *ctx = shards_[(size_t)g]->ctx;
+        if (gdg_batch_stream_need(ctx, blocks, first + f, count + f) != GDG_OK) { setError(format("shard %d: %s", g, gdg_last_error(ctx))); return LastError(); }
+    }
+    return "";
+}
+
+Error Engine::BatchStreamShardedStep(int blocks, const void *const *ins, void *const *outs) {
+    if (!ins || !outs) return "BatchStreamShardedStep: no inputs or no outputs";
+    if (!shardedOpen_) return "BatchStreamShardedStep: no streamed batch run is open";
+    if (blocks < 1) return "BatchStreamShardedStep: a slice has at least one block";
+    const int G = shards(), N = nChannels_;
+    const gdg_batch_options &options = shardedOptions_;
+    const size_t n = (size_t)blocks * 8192;
+    /* the shards' slices, concurrently: encoded chain outputs straight into the caller's pieces, partial master mixes as float64 */
+    std::vector<std::vector<double>> left((size_t)G), right((size_t)G);
+    std::vector<double> metronome(n, 0.0);
+    std::vector<Error> errs((size_t)G);
+    auto one = [&](int g) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        if (count <= 0) return;
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        gdg_ctx *ctx = shards_[(size_t)g]->ctx;
+        left[(size_t)g].assign(n, 0.0);
+        right[(size_t)g].assign(n, 0.0);
+        gdg_batch_shard_out so;
+        memset(&so, 0, sizeof(so));
+        so.master_left = left[(size_t)g].data();
+        so.master_right = right[(size_t)g].data();
+        if (g == 0) { so.metronome_bytes = outs[N + 2]; so.metronome = metronome.data(); }
+        if (gdg_batch_stream_step_shard(ctx, blocks, ins + first, outs + first, &so) != GDG_OK) errs[(size_t)g] = gdg_last_error(ctx);
+    };
+    {
+        std::vector<std::thread> workers;
+        for (int g = 1; g < G; g++) workers.emplace_back(one, g);
+        one(0);
+        for (auto &w : workers) w.join();
+    }
+    for (int g = 0; g < G; g++)
+        if (!errs[(size_t)g].empty()) {
+            closeSharded();                              /* the shards are no longer at the same block: the job cannot go on */
+            setError(format("shard %d: %s", g, errs[(size_t)g].c_str()));
+            return LastError();
+        }
+    /* the slice's master, finished on shard 0's device */
+    std::vector<const double *> lp, rp;
+    for (int g = 0; g < G; g++) if (!left[(size_t)g].empty()) { lp.push_back(left[(size_t)g].data()); rp.push_back(right[(size_t)g].data()); }
+    Error e;
+    {
+        std::lock_guard<std::mutex> lk(shards_[0]->mu);
+        gdg_ctx *ctx0 = shards_[0]->ctx;
+        if (gdg_batch_finish_master_slice(ctx0, options.out_format, lp.data(), rp.data(), (int)lp.size(), options.metronome_to_master ? metronome.data() : nullptr, n,
+                                          options.target_rate, options.run_meters, outs[N], outs[N + 1]) != GDG_OK)
+            e = gdg_last_error(ctx0);
+    }
+    if (!e.empty()) { closeSharded(); setError(e); return LastError(); }
+    return "";
+}
+
+Error Engine::BatchStreamShardedClose() {
+    if (!shardedOpen_) return "BatchStreamShardedClose: no streamed batch run is open";
+    closeSharded();
+    return "";
+}
+
 /* ================================ spatializer ============================================= */
 namespace spatializer {
 
@@ -1232,6 +1372,16 @@ const char *gdgh_engine_batch_stream_step(void *e, int blocks, const void *const
     return ret(((Engine *)e)->BatchStreamStep(blocks, ins, outs));
 }
 const char *gdgh_engine_batch_stream_close(void *e) { return ret(((Engine *)e)->BatchStreamClose()); }
+const char *gdgh_engine_batch_stream_sharded_open(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, size_t *samples) {
+    return ret(((Engine *)e)->BatchStreamShardedOpen(inputs, n, *opt, window, samples));
+}
+const char *gdgh_engine_batch_stream_sharded_need(void *e, int blocks, size_t *first, size_t *count) {
+    return ret(((Engine *)e)->BatchStreamShardedNeed(blocks, first, count));
+}
+const char *gdgh_engine_batch_stream_sharded_step(void *e, int blocks, const void *const *ins, void *const *outs) {
+    return ret(((Engine *)e)->BatchStreamShardedStep(blocks, ins, outs));
+}
+const char *gdgh_engine_batch_stream_sharded_close(void *e) { return ret(((Engine *)e)->BatchStreamShardedClose()); }
 void *gdgh_engine_context(void *e, int shard) { return ((Engine *)e)->context(shard); }
 void gdgh_engine_shard_range(void *e, int shard, int *first, int *count) { ((Engine *)e)->shardRange(shard, first, count); }
 void *gdgh_engine_create_sharded(int n_channels, int max_frames, const int *devices, int n_devices) {

@@ -210,12 +210,22 @@ public:
      * _close, include/gdg.h): Open synchronises the chains to the device and sets the window, `samples` receives the job's length; Need
      * fills first[i] / count[i] (one per input) with the source frames the next slice of `blocks` blocks must bring; Step takes those
      * frames (ins[i], interleaved, the file's format) and writes the slice's N + 3 output pieces.  The chains must not change between
-     * Open and Close.  For an engine of ONE shard: the streamed form of a shard does not exist yet, and an engine of several shards
-     * answers "BatchStream: unsupported ...". */
+     * Open and Close.  For an engine of ONE shard: an engine of several shards answers "BatchStream: unsupported ..." (its streamed
+     * run is BatchStreamSharded*, below). */
     Error BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, size_t *samples);
     Error BatchStreamNeed(int blocks, size_t *first, size_t *count);
     Error BatchStreamStep(int blocks, const void *const *ins, void *const *outs);
     Error BatchStreamClose();
+    /* The streamed run of an engine of ANY shard count, one included: the same caller-side shape (N inputs in, N + 3 output pieces per
+     * slice), inside BatchRun's algorithm per slice.  Open synchronises every shard and opens its job at the longest shard's length
+     * (gdg_batch_stream_open_shard, the metronome on shard 0); Step runs the shards' slices concurrently, one thread each and shard 0 on
+     * the caller's (gdg_batch_stream_step_shard), then finishes the slice's master on shard 0 (gdg_batch_finish_master_slice).  The host
+     * holds one slice of partial sums (a pair per shard and the metronome row, blocks * 8192 float64 each), nothing of the job's length.
+     * A shard that fails closes every shard's job. */
+    Error BatchStreamShardedOpen(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, size_t *samples);
+    Error BatchStreamShardedNeed(int blocks, size_t *first, size_t *count);
+    Error BatchStreamShardedStep(int blocks, const void *const *ins, void *const *outs);
+    Error BatchStreamShardedClose();
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -250,6 +260,9 @@ private:
     bool executing_ = false;
     uint64_t generation_ = 0;
     int expected_ = 0, timeoutMs_ = 50;
+    bool shardedOpen_ = false;                             /* BatchStreamSharded*: a job is open on every shard, with these options */
+    gdg_batch_options shardedOptions_ = {};
+    void closeSharded();
     mutable std::mutex errMu_;
     std::string lastError_;
 };

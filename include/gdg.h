@@ -578,8 +578,41 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
  * blob is equal as well where the job's last steps coincide (the convolution keeps two history halves, of which the one not read next
  * holds whatever frame the window grouping left there).  A slice that fails half-way closes the job.  State
  * save / load and parameter changes between slices behave as between two gdg_batch_run calls.  The buffers are the batch run's own
- * (option stat_batch_device_kib reads their size, gdg_batch_release frees them).  The streamed form of a SHARD (gdg_batch_run_shard /
- * gdg_batch_finish_master) does not exist yet.
+ * (option stat_batch_device_kib reads their size, gdg_batch_release frees them).
+ *
+ * The streamed form of a SHARD (gdg_batch_run_shard / gdg_batch_finish_master in slices): a job split over several contexts / GPUs whose
+ * files are too long to hold.  Per shard g, one context each:
+ *   gdg_batch_stream_open_shard(ctx_g, inputs of g's channels, n, &options, job_samples, run_metronome, &samples)
+ *                                                                      gdg_batch_stream_open under gdg_batch_run_shard's rules:
+ *                                                                      options->metronome_to_master must be 0; job_samples = the job's
+ *                                                                      length (the longest gdg_batch_length over the shards, a multiple
+ *                                                                      of 8192 and not shorter than the shard's own; 0 = the shard's own),
+ *                                                                      returned in `samples` -- the shard pads to it; run_metronome says
+ *                                                                      ONCE, for the whole job, whether this shard runs the metronome
+ *                                                                      (exactly one shard should); with run_meters the context carries
+ *                                                                      2 n + 3 ports, fed as gdg_batch_run_shard feeds them
+ *   per slice: gdg_batch_stream_need as above, then
+ *     gdg_batch_stream_step_shard(ctx_g, blocks, in_bytes, out_bytes, &slice)
+ *                                                                      out_bytes: the shard's n chain outputs of blocks * 8192 * width
+ *                                                                      bytes (NULL = "skipping output"); slice.master_left / master_right
+ *                                                                      (required) receive blocks * 8192 float64 each: this shard's partial
+ *                                                                      mix of the slice, no aux, not clipped; slice.metronome_bytes /
+ *                                                                      slice.metronome (either may be NULL in any slice) the slice's
+ *                                                                      encoded / float64 metronome track -- GDG_ERR_INVALID when the job
+ *                                                                      was opened with run_metronome == 0; slice.job_samples is ignored
+ *   gdg_batch_stream_close(ctx_g)
+ * and once per slice, when every shard has delivered it:
+ *   gdg_batch_finish_master_slice(ctx, fmt, {left_g}, {right_g}, G, aux, blocks * 8192, rate, meters, left_bytes, right_bytes)
+ *                                                                      the arguments, the result and the bits of gdg_batch_finish_master
+ *                                                                      for a whole number of blocks (GDG_ERR_INVALID otherwise), made
+ *                                                                      for the job's critical path: the partials gathered into one pinned
+ *                                                                      slab, one upload, one kernel and one download per piece
+ * A shard's slices step where the ONE-CALL gdg_batch_run_shard of the whole job would step, so chain outputs, partial sums, metronome,
+ * meters, tuner and unit state are that run's whatever the slicing, and the finished slices put together are gdg_batch_finish_master's
+ * bytes.  gdg_batch_stream_step on a job opened as a shard and gdg_batch_stream_step_shard on a job opened with gdg_batch_stream_open
+ * return GDG_ERR_INVALID and write nothing; every other rule of the streamed run above holds for a shard's job as well.
+ * A context runs ONE call at a time.  Any context may finish slice s (its last two meter ports receive the master when asked); a caller
+ * who wants the finish of slice s to run beside shard 0's slice s + 1 gives the finish a context of its own.
  *
  * gdg_batch_stream_span is pure arithmetic and needs no context or device: the source frames of one input that the job's output samples
  * [out_first, out_first + out_count) read, for an input of samples_per_channel frames at source_rate in a job at target_rate.  Same
@@ -593,6 +626,11 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
 int gdg_batch_stream_need(gdg_ctx *ctx, int blocks, size_t *first, size_t *count);
 int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes);
 int gdg_batch_stream_close(gdg_ctx *ctx);
+int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *options, size_t job_samples,
+                                int run_metronome, size_t *samples);
+int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice);
+int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
+                                  size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes);
 /* The device buffers of a batch run (the decoded inputs are the large part: N x length x 8 bytes) stay with the context for the next
  * run of the same or a smaller size; this frees them. */
 int gdg_batch_release(gdg_ctx *ctx);
