@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "gdg_batch_length", "gdg_batch_run", "gdg_batch_run_shard", "gdg_batch_finish_master", "gdg_batch_release", "gdg_batch_stream_span", "gdg_batch_stream_open", "gdg_batch_stream_need", "gdg_batch_stream_step", "gdg_batch_stream_close", "gdg_batch_stream_open_shard", "gdg_batch_stream_step_shard", "gdg_batch_finish_master_slice", "gdg_profile_sample", "gdg_ctx_set_window", "gdg_process_window_device", "gdg_ctx_set_overlap",
     "gdg_ctx_set_option", "gdg_ctx_get_option", "gdg_option_count", "gdg_option_name", "gdg_numa_probe", "gdg_ctx_trim", "gdg_tuner_replace",
     "gdg_state_size", "gdg_state_save", "gdg_state_save_device", "gdg_state_load", "gdg_state_load_device",
+    "gdg_batch_stream_checkpoint_size", "gdg_batch_stream_checkpoint", "gdg_batch_stream_resume", "gdg_batch_stream_resume_shard", "gdg_state_verify",
 ]
 
 
@@ -61,6 +62,33 @@ def numa_probe(sysfs_root, pci_bus_id, capacity=4096):
     if rc != GDG_OK:
         raise GdgError(rc, "gdg_numa_probe")
     return int(node.value), [int(cpus[i]) for i in range(min(capacity, n.value))]
+
+
+def checkpoint_digest(payload):
+    """The 128-bit digest a checkpoint container carries over its payload (include/gdg.h states the function; the device computes it in
+    state.hip).  Plain Python over the bytes: for tools that inspect a container without a GPU.  -> 16 bytes (D0, D1 little-endian)."""
+    M, K, M0, M1 = (1 << 64) - 1, 0x9e3779b97f4a7c15, 0xff51afd7ed558ccd, 0xc4ceb9fe1a85ec53
+    payload = bytes(payload)
+    if len(payload) % 16:
+        raise ValueError("a payload is a whole number of 16-byte granules")
+    words = np.frombuffer(payload, dtype="<u8")
+    s0 = s1 = 0
+    for g in range(len(words) // 2):
+        t = ((int(words[2 * g]) + (g + 1) * K) * M0) & M
+        u = t ^ (t >> 32)
+        s = ((int(words[2 * g + 1]) ^ u) * M1) & M
+        s0 = (s0 + u) & M
+        s1 ^= s ^ (s >> 29)
+
+    def fmix(x):
+        x ^= x >> 33
+        x = (x * M0) & M
+        x ^= x >> 33
+        x = (x * M1) & M
+        return x ^ (x >> 33)
+    d0 = fmix((s0 + K + len(words) // 2) & M)
+    d1 = fmix(s1 ^ d0)
+    return d0.to_bytes(8, "little") + d1.to_bytes(8, "little")
 
 
 def batch_stream_span(samples_per_channel, source_rate, target_rate, out_first, out_count):
@@ -142,6 +170,11 @@ def lib():
             "gdg_state_save_device": (i32, [vp, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdg_state_load": (i32, [vp, vp, i32, vp, C.c_size_t]),
             "gdg_state_load_device": (i32, [vp, vp, i32, vp, C.c_size_t]),
+            "gdg_batch_stream_checkpoint_size": (i32, [vp, C.POINTER(C.c_size_t)]),
+            "gdg_batch_stream_checkpoint": (i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+            "gdg_batch_stream_resume": (i32, [vp, vp, i32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+            "gdg_batch_stream_resume_shard": (i32, [vp, vp, i32, vp, C.c_size_t, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+            "gdg_state_verify": (i32, [vp, vp, C.c_size_t]),
             "gdg_process": (i32, [vp, vp, vp, i32, u32]),
             "gdg_process_subset": (i32, [vp, vp, i32, vp, vp, i32, u32]),
             "gdg_process_device": (i32, [vp, vp, vp, i32, u32]),
@@ -817,6 +850,48 @@ class Context:
                 self.batch_stream_close()
             except GdgError:
                 pass                            # a slice that failed has closed the job itself
+
+    # -- checkpoint / resume of the open streamed job (gdg_batch_stream_checkpoint / _resume, gdg_state_verify) ----------------------
+    def batch_stream_checkpoint(self):
+        """-> bytes: the open job (plain or a shard's) with everything it carries between slices; the context is not changed."""
+        size = C.c_size_t(0)
+        self._check(lib().gdg_batch_stream_checkpoint_size(self._h, C.byref(size)))
+        buf = C.create_string_buffer(max(size.value, 1))
+        written = C.c_size_t(0)
+        self._check(lib().gdg_batch_stream_checkpoint(self._h, buf, size.value, C.byref(written)))
+        return buf.raw[:written.value]
+
+    def batch_stream_resume(self, inputs, target_rate, out_format, blob, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
+        """In the place of batch_stream_open, with its arguments and a checkpoint of that job: returns the samples done.  Nothing changes
+        when the blob is rejected."""
+        n = len(inputs)
+        arr = self._stream_metas(inputs)
+        fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
+        opt = BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
+        blob = bytes(blob)
+        done = C.c_size_t(0)
+        self._check(lib().gdg_batch_stream_resume(self._h, arr, n, C.byref(opt), blob, len(blob), C.byref(done)))
+        self._stream_width = lib().gdg_wave_bytes_per_sample(fo)
+        return done.value
+
+    def batch_stream_resume_shard(self, inputs, target_rate, out_format, blob, job_samples=0, metronome=False, run_meters=False,
+                                  tuner_enqueue=False):
+        """In the place of batch_stream_open_shard (same job_samples and metronome); returns the samples done."""
+        n = len(inputs)
+        arr = self._stream_metas(inputs)
+        fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
+        opt = BatchOptions(target_rate, fo, 0, int(bool(run_meters)), int(bool(tuner_enqueue)))
+        blob = bytes(blob)
+        done = C.c_size_t(0)
+        self._check(lib().gdg_batch_stream_resume_shard(self._h, arr, n, C.byref(opt), job_samples, int(bool(metronome)), blob, len(blob),
+                                                        C.byref(done)))
+        self._stream_width = lib().gdg_wave_bytes_per_sample(fo)
+        return done.value
+
+    def state_verify(self, blob):
+        """The digest of a checkpoint container, checked on the device; raises GdgError when it does not hold (or for a bare state blob)."""
+        blob = bytes(blob)
+        self._check(lib().gdg_state_verify(self._h, blob, len(blob)))
 
     # -- ... and of ONE SHARD of a job split over several contexts (gdg_batch_stream_open_shard / _step_shard, gdg_batch_finish_master_slice)
     def batch_stream_open_shard(self, inputs, target_rate, out_format, job_samples=0, metronome=False, run_meters=False, tuner_enqueue=False,

@@ -28,7 +28,7 @@ int gdg_batch_length(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, 
 }
 
 /* slot i of the batch run's device buffers with at least `bytes` */
-static int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out) {
+int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out) {
     if (bytes > ctx->batch_dev_cap[i]) {
         hipFree(ctx->batch_dev[i]);
         ctx->batch_dev[i] = nullptr;
@@ -539,7 +539,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
  * straight into its row, or into the resampler's source buffer behind the frames kept from the step before -- so the device holds one
  * slice of decoded input and nothing of the job's length.
  * ============================================================================================== */
-#define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */
+/* GDG_STREAM_CARRY (ctx.h): the source frames kept per resampled input */
 
 /* resample/resample.go:72-87 with 64-bit lengths (gdg_resample_time_length for files of any length) */
 static size_t resample_length64(size_t n, uint32_t source_rate, uint32_t target_rate) {
@@ -569,11 +569,10 @@ int gdg_batch_stream_span(size_t samples_per_channel, uint32_t source_rate, uint
 }
 
 /* `shard`: the job of gdg_batch_run_shard (job_samples, run_metronome) instead of gdg_batch_run's */
-static int stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
-                       bool run_metronome, size_t *samples) {
-    if (!ctx || !inputs || !opt || !samples) return GDG_ERR_INVALID;
-    auto &S = ctx->bstream;
-    if (S.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is already open on this context");
+int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
+               bool run_metronome, gdg_ctx::BatchStreamState &S) {
+    if (!ctx || !inputs || !opt) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is already open on this context");
     if (n_inputs != ctx->nch) return fail(ctx, GDG_ERR_INVALID, "the batch has %d inputs, the context %d channels", n_inputs, ctx->nch);
     if (ctx->max_frames < GDG_BLOCK_SIZE)
         return fail(ctx, GDG_ERR_INVALID, "the batch loop runs blocks of %d frames, the context allows %d", GDG_BLOCK_SIZE, ctx->max_frames);
@@ -608,7 +607,17 @@ static int stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs
     S.brought.assign((size_t)n_inputs, 0);
     S.n_out = n_out;
     S.open = true;
-    *samples = max_len;
+    return GDG_OK;
+}
+
+static int stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
+                       bool run_metronome, size_t *samples) {
+    if (!ctx || !samples) return GDG_ERR_INVALID;
+    gdg_ctx::BatchStreamState job;
+    const int rc = stream_job(ctx, inputs, n_inputs, opt, shard, job_samples, run_metronome, job);
+    if (rc != GDG_OK) return rc;
+    ctx->bstream = job;
+    *samples = job.length;
     return GDG_OK;
 }
 

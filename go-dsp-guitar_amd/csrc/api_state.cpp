@@ -45,8 +45,6 @@ static_assert(sizeof(StateHeader) == 64, "blob header layout");
 static_assert(sizeof(StateRecord) == 32, "blob record layout");
 static_assert(sizeof(StateSlot) == 96, "blob slot layout");
 
-static inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 /* which oversampler (0: 2x, 1: 4x) the unit's parameters use, -1 none */
 static int os_in_use(const Unit &u) {
     int idx = -1;
@@ -142,42 +140,6 @@ static void layout(const gdg_ctx *ctx, const std::vector<int> &chans, std::vecto
     memcpy(meta.data(), &h, sizeof(h));
 }
 
-/* The pieces of one launch, the prefix table of their chunks, and the launch (synchronous: the caller's buffers are complete after it) */
-struct Pieces {
-    std::vector<gdg_state_piece> p;
-    void add(const void *src, void *dst, size_t bytes) { if (bytes) p.push_back(gdg_state_piece{ src, dst, (unsigned long long)bytes }); }
-    /* a region of `bytes` and the zeros that round it up to 16 in the blob */
-    void add_padded(const void *src, void *dst, size_t bytes, bool dst_is_blob) {
-        add(src, dst, bytes);
-        const size_t pad = round16(bytes) - bytes;
-        if (pad && dst_is_blob) add(nullptr, (char *)dst + bytes, pad);
-    }
-    int run(gdg_ctx *ctx) {
-        if (p.empty()) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); return GDG_OK; }
-        std::vector<unsigned> first(p.size());
-        unsigned long long chunks = 0;
-        for (size_t i = 0; i < p.size(); i++) {
-            first[i] = (unsigned)chunks;
-            chunks += (p[i].bytes + GDG_STATE_CHUNK - 1) / GDG_STATE_CHUNK;
-        }
-        if (chunks > 0x7fffffffull) return fail(ctx, GDG_ERR_INVALID, "state: %llu chunks in one launch", chunks);
-        const size_t pb = round16(p.size() * sizeof(gdg_state_piece));
-        void *d = nullptr;
-        HIP_TRY(ctx, ctx->arena.alloc(&d, pb + first.size() * sizeof(unsigned)));
-        std::vector<unsigned char> host(pb + first.size() * sizeof(unsigned), 0);
-        memcpy(host.data(), p.data(), p.size() * sizeof(gdg_state_piece));
-        memcpy(host.data() + pb, first.data(), first.size() * sizeof(unsigned));
-        hipError_t e = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess)
-            e = gdg_launch_state_copy((const gdg_state_piece *)d, (const unsigned *)((char *)d + pb), (int)p.size(), (unsigned)chunks, ctx->stream);
-        hipError_t w = hipStreamSynchronize(ctx->stream);
-        ctx->arena.release(d);
-        if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "state copy: %s", hipGetErrorString(e));
-        if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "state copy: %s", hipGetErrorString(w));
-        return GDG_OK;
-    }
-};
-
 static inline int ring_slot(int pos, int m, int R) { return (((pos - 1 - m) % R) + R) % R; }      /* frame pos - 1 - m (prepare_fir) */
 
 int gdg_state_size(gdg_ctx *ctx, const int *channels, int n, size_t *bytes) {
@@ -191,7 +153,7 @@ int gdg_state_size(gdg_ctx *ctx, const int *channels, int n, size_t *bytes) {
 }
 
 /* blob: the caller's device buffer, or staging in the arena */
-static int save_into(gdg_ctx *ctx, const std::vector<int> &chans, unsigned char *blob, const std::vector<unsigned char> &meta_in) {
+static int save_into(gdg_ctx *ctx, const std::vector<int> &chans, unsigned char *blob, const std::vector<unsigned char> &meta_in, const Pieces *extra = nullptr) {
     std::vector<unsigned char> meta = meta_in;
     /* 1. the frame counters of the live delay lines: the ring rotation is decided on the host */
     std::vector<std::pair<size_t, const Unit *>> firs;          /* (offset of the slot in meta, unit) */
@@ -253,10 +215,11 @@ static int save_into(gdg_ctx *ctx, const std::vector<int> &chans, unsigned char 
         }
         at += sizeof(StateRecord) + chain.size() * sizeof(StateSlot);
     }
+    ps.append(extra);
     return ps.run(ctx);
 }
 
-static int save_common(gdg_ctx *ctx, const int *channels, int n, void *blob, size_t capacity, size_t *written, bool device) {
+static int save_common(gdg_ctx *ctx, const int *channels, int n, void *blob, size_t capacity, size_t *written, bool device, const Pieces *extra = nullptr) {
     if (!ctx || !blob) return GDG_ERR_INVALID;
     std::vector<int> chans;
     int rc = channel_list(ctx, channels, n, chans);
@@ -269,7 +232,7 @@ static int save_common(gdg_ctx *ctx, const int *channels, int n, void *blob, siz
     if (device && ((uintptr_t)blob & 15)) return fail(ctx, GDG_ERR_INVALID, "state save: the device buffer must be 16-byte aligned");
     /* ordered after everything queued on the context; nothing it made ahead is dropped (a save changes no state) */
     enter(ctx, /*read_only=*/true);
-    if (device) return save_into(ctx, chans, static_cast<unsigned char *>(blob), meta);
+    if (device) return save_into(ctx, chans, static_cast<unsigned char *>(blob), meta, extra);
     unsigned char *stage = nullptr;
     HIP_TRY(ctx, ctx->arena.alloc((void **)&stage, total));
     rc = save_into(ctx, chans, stage, meta);
@@ -415,7 +378,7 @@ static int check_all(gdg_ctx *ctx, const std::vector<int> &chans, const std::vec
 /* The metadata against the target: structure and every layout key first, against the layouts the load will build (nothing touched, the
  * sums made ahead kept); then the target's layouts at the blob's frame size and rate, and the keys once more.  GDG_OK: the blob can be
  * applied as it is. */
-static int validate(gdg_ctx *ctx, const std::vector<int> &chans, const std::vector<unsigned char> &meta, const StateHeader &h) {
+static int validate(gdg_ctx *ctx, const std::vector<int> &chans, const std::vector<unsigned char> &meta, const StateHeader &h, bool check_only = false) {
     size_t at = sizeof(StateHeader);
     /* 1. structure: records, slot counts, unit types, offsets inside the blob */
     for (size_t i = 0; i < chans.size(); i++) {
@@ -454,7 +417,7 @@ static int validate(gdg_ctx *ctx, const std::vector<int> &chans, const std::vect
         return fail(ctx, GDG_ERR_INVALID, "state load: the blob was laid out for %d-sample frames, this context takes at most %d", h.frames, ctx->max_frames);
     /* 2. the keys against the layouts the target WILL have (expected_layout): nothing of the target is touched before every record fits */
     int rc = check_all(ctx, chans, meta, h, false);
-    if (rc != GDG_OK) return rc;
+    if (rc != GDG_OK || check_only) return rc;
     /* 3. the target's layouts at the blob's frame size and rate, built as a process call would build them; the sums made ahead die here */
     enter(ctx);
     if (h.frames > 0) {
@@ -477,7 +440,7 @@ static int validate(gdg_ctx *ctx, const std::vector<int> &chans, const std::vect
 }
 
 /* blob: the blob on the device (the caller's buffer or staging), meta: its metadata on the host */
-static int apply(gdg_ctx *ctx, const std::vector<int> &chans, const unsigned char *blob, const std::vector<unsigned char> &meta) {
+static int apply(gdg_ctx *ctx, const std::vector<int> &chans, const unsigned char *blob, const std::vector<unsigned char> &meta, const Pieces *extra = nullptr) {
     bool any_sp = false;
     size_t at = sizeof(StateHeader);
     for (size_t i = 0; i < chans.size(); i++) {
@@ -532,10 +495,13 @@ static int apply(gdg_ctx *ctx, const std::vector<int> &chans, const unsigned cha
         }
         at += sizeof(r) + chain.size() * sizeof(StateSlot);
     }
+    ps.append(extra);
     return ps.run(ctx);
 }
 
-static int load_common(gdg_ctx *ctx, const int *channels, int n, const void *blob, size_t bytes, bool device) {
+/* check_only: everything a load checks before it touches the target, and nothing else */
+static int load_common(gdg_ctx *ctx, const int *channels, int n, const void *blob, size_t bytes, bool device, const Pieces *extra = nullptr,
+                       bool check_only = false) {
     if (!ctx || !blob) return GDG_ERR_INVALID;
     std::vector<int> chans;
     int rc = channel_list(ctx, channels, n, chans);
@@ -556,10 +522,10 @@ static int load_common(gdg_ctx *ctx, const int *channels, int n, const void *blo
     std::vector<unsigned char> meta(h.meta_bytes);
     if (device) HIP_TRY(ctx, hipMemcpy(meta.data(), blob, meta.size(), hipMemcpyDeviceToHost));
     else memcpy(meta.data(), blob, meta.size());
-    rc = validate(ctx, chans, meta, h);
-    if (rc != GDG_OK) return rc;
+    rc = validate(ctx, chans, meta, h, check_only);
+    if (rc != GDG_OK || check_only) return rc;
     if (device) {
-        rc = apply(ctx, chans, static_cast<const unsigned char *>(blob), meta);
+        rc = apply(ctx, chans, static_cast<const unsigned char *>(blob), meta, extra);
     } else {
         unsigned char *stage = nullptr;
         HIP_TRY(ctx, ctx->arena.alloc((void **)&stage, h.total_bytes));
@@ -569,6 +535,9 @@ static int load_common(gdg_ctx *ctx, const int *channels, int n, const void *blo
         ctx->arena.release(stage);
     }
     if (rc != GDG_OK) return rc;
+    /* a context that never built a plan now holds state laid out at the blob's frame size and rate: a save before its first process
+     * call records them (with frames = 0 that blob would say "every slot is fresh" beside slots that are not, and would not load) */
+    if (h.frames > 0 && ctx->plan_frames == 0) { ctx->plan_frames = h.frames; ctx->plan_sr = h.rate; }
     drop_fir_ahead(ctx);
     ctx->premac_valid = false;
     ctx->dirty = true;
@@ -580,4 +549,15 @@ int gdg_state_load(gdg_ctx *ctx, const int *channels, int n, const void *blob, s
 }
 int gdg_state_load_device(gdg_ctx *ctx, const int *channels, int n, const void *d_blob, size_t bytes) {
     return load_common(ctx, channels, n, d_blob, bytes, true);
+}
+
+/* ---- for a checkpoint (api_checkpoint.cpp): all channels, a device buffer, the caller's pieces in the same launch ------------------------ */
+int state_save_device_with(gdg_ctx *ctx, void *d_blob, size_t capacity, const Pieces *extra) {
+    return save_common(ctx, nullptr, 0, d_blob, capacity, nullptr, true, extra);
+}
+int state_check_device(gdg_ctx *ctx, const void *d_blob, size_t bytes) {
+    return load_common(ctx, nullptr, 0, d_blob, bytes, true, nullptr, true);
+}
+int state_load_device_with(gdg_ctx *ctx, const void *d_blob, size_t bytes, const Pieces *extra) {
+    return load_common(ctx, nullptr, 0, d_blob, bytes, true, extra);
 }

@@ -7,7 +7,7 @@
 
 /* ---- tuner: tuner.Process / tuner.Analyze for every channel of the shard ------------------------------------------ */
 
-static int ensure_tuner(gdg_ctx *ctx) {
+int ensure_tuner(gdg_ctx *ctx) {
     if (ctx->d_tuner_ring) return GDG_OK;
     size_t ring_bytes = (size_t)ctx->nch * GDG_TUNER_RING * sizeof(double);
     HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tuner_ring, ring_bytes));

@@ -11,6 +11,7 @@
  *   api_io.cpp          wave codecs, resample.Time, level meters, power-amp compilation, metronome
  *   api_batch.cpp       the batch run (gdg_batch_run, its sharded form, the streamed forms of both, the master mix of a job and of a slice)
  *   api_state.cpp       channel state saved into / loaded from a blob (gdg_state_*; the copies: state.hip)
+ *   api_checkpoint.cpp  a streamed batch run checkpointed into a container and resumed from it (gdg_batch_stream_checkpoint / _resume; the digest: state.hip)
  */
 #ifndef GDG_CTX_H
 #define GDG_CTX_H
@@ -560,6 +561,59 @@ int tuner_enqueue_rows(gdg_ctx *ctx, const double *d_samples, size_t stride, int
 void copy_rows_parallel(gdg_ctx *ctx, size_t a, size_t b, const std::function<void(size_t)> &copy_row, size_t row_bytes, int which = 0);      /* which: 1 = the upload side's workers */
 void destroy_copy_pool(CopyPool *p);
 void ensure_copy_pool(gdg_ctx *ctx, int which);     /* makes the pool NOW, on the calling thread (option "numa" = 2 binds the workers to the node of the thread that makes them) */
+
+/* ---- state blobs and checkpoints (api_state.cpp, api_checkpoint.cpp; the copies: state.hip) --------------------------------------- */
+static inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+/* The pieces of one launch, the prefix table of their chunks, and the launch (synchronous: the caller's buffers are complete after it) */
+struct Pieces {
+    std::vector<gdg_state_piece> p;
+    void add(const void *src, void *dst, size_t bytes) { if (bytes) p.push_back(gdg_state_piece{ src, dst, (unsigned long long)bytes }); }
+    /* a region of `bytes` and the zeros that round it up to 16 in the blob */
+    void add_padded(const void *src, void *dst, size_t bytes, bool dst_is_blob) {
+        add(src, dst, bytes);
+        const size_t pad = round16(bytes) - bytes;
+        if (pad && dst_is_blob) add(nullptr, (char *)dst + bytes, pad);
+    }
+    void append(const Pieces *more) { if (more) p.insert(p.end(), more->p.begin(), more->p.end()); }
+    int run(gdg_ctx *ctx) {
+        if (p.empty()) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); return GDG_OK; }
+        std::vector<unsigned> first(p.size());
+        unsigned long long chunks = 0;
+        for (size_t i = 0; i < p.size(); i++) {
+            first[i] = (unsigned)chunks;
+            chunks += (p[i].bytes + GDG_STATE_CHUNK - 1) / GDG_STATE_CHUNK;
+        }
+        if (chunks > 0x7fffffffull) return fail(ctx, GDG_ERR_INVALID, "state: %llu chunks in one launch", chunks);
+        const size_t pb = round16(p.size() * sizeof(gdg_state_piece));
+        void *d = nullptr;
+        HIP_TRY(ctx, ctx->arena.alloc(&d, pb + first.size() * sizeof(unsigned)));
+        std::vector<unsigned char> host(pb + first.size() * sizeof(unsigned), 0);
+        memcpy(host.data(), p.data(), p.size() * sizeof(gdg_state_piece));
+        memcpy(host.data() + pb, first.data(), first.size() * sizeof(unsigned));
+        hipError_t e = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = gdg_launch_state_copy((const gdg_state_piece *)d, (const unsigned *)((char *)d + pb), (int)p.size(), (unsigned)chunks, ctx->stream);
+        hipError_t w = hipStreamSynchronize(ctx->stream);
+        ctx->arena.release(d);
+        if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "state copy: %s", hipGetErrorString(e));
+        if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "state copy: %s", hipGetErrorString(w));
+        return GDG_OK;
+    }
+};
+
+/* api_state.cpp, for a checkpoint: every channel's state into / out of a 16-byte-aligned device buffer, the caller's own pieces (`extra`)
+ * riding in the same launch as the state's.  state_check_device only reads: header, structure and every layout key against the layouts
+ * a load WOULD build (what gdg_state_load checks before it touches the target). */
+int state_save_device_with(gdg_ctx *ctx, void *d_blob, size_t capacity, const Pieces *extra);
+int state_check_device(gdg_ctx *ctx, const void *d_blob, size_t bytes);
+int state_load_device_with(gdg_ctx *ctx, const void *d_blob, size_t bytes, const Pieces *extra);
+/* api_batch.cpp: the job a streamed run would open (validated, nothing of the context touched); the batch run's device buffer `i` */
+int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
+               bool run_metronome, gdg_ctx::BatchStreamState &job);
+int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out);
+#define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */
+int ensure_tuner(gdg_ctx *ctx);
 
 #pragma GCC visibility pop
 

@@ -315,4 +315,14 @@ hipError_t gdg_launch_normalize_scale_add(const double *d_src, int n, double com
 struct gdg_state_piece { const void *src; void *dst; unsigned long long bytes; };
 hipError_t gdg_launch_state_copy(const gdg_state_piece *d_pieces, const unsigned *d_first, int n_pieces, unsigned n_chunks, hipStream_t s);
 
+/* state.hip: the payload digest of a checkpoint container (include/gdg.h states the function; api_checkpoint.cpp finishes it).  Granule g
+ * (16 bytes: the little-endian 64-bit words a, b) gives u = mix(a + (g + 1) K, M0, 32), v = mix(b ^ u, M1, 29) with mix(x, M, r) = (x M) ^
+ * ((x M) >> r) mod 2^64; the launch leaves per workgroup {sum of u mod 2^64, XOR of v} in d_partials[2 * group ..].  Sum and XOR commute,
+ * so the two totals do not depend on `groups` (1 .. GDG_DIGEST_GROUPS) or on which workgroup met which granule. */
+#define GDG_DIGEST_K  0x9e3779b97f4a7c15ull
+#define GDG_DIGEST_M0 0xff51afd7ed558ccdull
+#define GDG_DIGEST_M1 0xc4ceb9fe1a85ec53ull
+#define GDG_DIGEST_GROUPS 2048
+hipError_t gdg_launch_state_digest(const void *d_payload, unsigned long long granules, unsigned long long *d_partials, int groups, hipStream_t s);
+
 #endif

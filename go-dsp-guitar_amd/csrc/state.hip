@@ -7,6 +7,9 @@
  * Memory bound and read once: 16-byte non-temporal loads through the global address space (a FLAT load would also count as an LDS
  * operation, fir.hip), plain 16-byte stores.  Every piece is cut into chunks of GDG_STATE_CHUNK bytes, a workgroup per chunk, found
  * through the prefix table `first` (first[i] = the first chunk of piece i).
+ *
+ * ... and the digest a checkpoint container carries over its payload (api_checkpoint.cpp): one pass of the same 16-byte loads, two 64-bit
+ * multiplies per granule, a reduction per workgroup in LDS, one 16-byte store per workgroup; the host adds the partials up.
  */
 #include "gdg_internal.h"
 
@@ -84,5 +87,57 @@ __global__ __launch_bounds__(STATE_THREADS) void state_copy_kernel(const gdg_sta
 hipError_t gdg_launch_state_copy(const gdg_state_piece *d_pieces, const unsigned *d_first, int n_pieces, unsigned n_chunks, hipStream_t s) {
     if (n_pieces <= 0 || n_chunks == 0) return hipSuccess;
     hipLaunchKernelGGL(state_copy_kernel, dim3(n_chunks), dim3(STATE_THREADS), 0, s, d_pieces, d_first, n_pieces);
+    return hipGetLastError();
+}
+
+/* ---- the payload digest (gdg_internal.h states the function) ---------------------------------------------------------------------- */
+#define DIGEST_V4 4                                              /* 16-byte loads a lane has in flight */
+
+__global__ __launch_bounds__(STATE_THREADS) void state_digest_kernel(const char *__restrict__ payload, unsigned long long granules,
+                                                                     unsigned long long *__restrict__ partials) {
+    __shared__ unsigned long long red[2][STATE_THREADS];
+    unsigned long long s0 = 0, s1 = 0;
+    const unsigned long long round = (unsigned long long)STATE_THREADS * DIGEST_V4;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * round; base < granules; base += (unsigned long long)gridDim.x * round) {
+        v4u w[DIGEST_V4];
+#pragma unroll
+        for (int j = 0; j < DIGEST_V4; j++) {
+            const unsigned long long g = base + (unsigned long long)j * STATE_THREADS + threadIdx.x;
+            w[j] = g < granules ? state_load<v4u>(payload + g * 16) : v4u(0);
+        }
+#pragma unroll
+        for (int j = 0; j < DIGEST_V4; j++) {
+            const unsigned long long g = base + (unsigned long long)j * STATE_THREADS + threadIdx.x;
+            if (g >= granules) continue;
+            const unsigned long long a = (unsigned long long)w[j].x | ((unsigned long long)w[j].y << 32);
+            const unsigned long long b = (unsigned long long)w[j].z | ((unsigned long long)w[j].w << 32);
+            unsigned long long u = (a + (g + 1) * GDG_DIGEST_K) * GDG_DIGEST_M0;
+            u ^= u >> 32;
+            unsigned long long v = (b ^ u) * GDG_DIGEST_M1;
+            v ^= v >> 29;
+            s0 += u;
+            s1 ^= v;
+        }
+    }
+    red[0][threadIdx.x] = s0;
+    red[1][threadIdx.x] = s1;
+    __syncthreads();
+    for (int h = STATE_THREADS / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + h];
+            red[1][threadIdx.x] ^= red[1][threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const unsigned long long t0 = red[0][0], t1 = red[1][0];
+        v4u out = { (unsigned)t0, (unsigned)(t0 >> 32), (unsigned)t1, (unsigned)(t1 >> 32) };
+        state_store<v4u>(reinterpret_cast<char *>(partials + 2 * (size_t)blockIdx.x), out);
+    }
+}
+
+hipError_t gdg_launch_state_digest(const void *d_payload, unsigned long long granules, unsigned long long *d_partials, int groups, hipStream_t s) {
+    if (granules == 0 || groups <= 0) return hipSuccess;
+    hipLaunchKernelGGL(state_digest_kernel, dim3((unsigned)groups), dim3(STATE_THREADS), 0, s, static_cast<const char *>(d_payload), granules, d_partials);
     return hipGetLastError();
 }

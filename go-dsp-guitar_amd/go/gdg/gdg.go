@@ -895,6 +895,86 @@ func (this *Context) BatchStreamClose() error {
 	return this.err(C.gdg_batch_stream_close(this.ctx))
 }
 
+// BatchStreamCheckpoint writes the open streamed job (plain or a shard's) into one blob: its position, the channel state, the frames the
+// resampler looks back at, meters, tuner rings and the metronome's counters (gdg_batch_stream_checkpoint).  Valid between any two
+// slices, before the first and after the last; the context is not changed.  The blob carries a digest of its payload (StateVerify).
+func (this *Context) BatchStreamCheckpoint() ([]byte, error) {
+	var size C.size_t
+	if err := this.err(C.gdg_batch_stream_checkpoint_size(this.ctx, &size)); err != nil {
+		return nil, err
+	}
+	buf := make([]byte, int(size)+1)
+	var written C.size_t
+	if err := this.err(C.gdg_batch_stream_checkpoint(this.ctx, unsafe.Pointer(&buf[0]), size, &written)); err != nil {
+		return nil, err
+	}
+	return buf[:int(written)], nil
+}
+
+// streamResume: BatchStreamResume and BatchStreamResumeShard.
+func (this *Context) streamResume(inputs []BatchStreamInput, opt BatchOptions, shard bool, jobSamples uint64, runMetronome bool, blob []byte) (uint64, error) {
+	n := len(inputs)
+	if n == 0 {
+		return 0, fmt.Errorf("gdg: no inputs")
+	}
+	if len(blob) == 0 {
+		return 0, fmt.Errorf("gdg: an empty checkpoint")
+	}
+	arr := (*[1 << 20]C.gdg_batch_input)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.gdg_batch_input{}))))
+	if arr == nil {
+		return 0, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(arr))
+	for i, in := range inputs {
+		if in.Frames == 0 {
+			continue
+		}
+		arr[i].bytes = unsafe.Pointer(arr) // never read: only "not NULL"
+		arr[i].samples_per_channel = C.size_t(in.Frames)
+		arr[i].format = C.int(in.Format)
+		arr[i].sample_rate = C.uint32_t(in.SampleRate)
+		arr[i].channels = C.uint(in.Channels)
+		arr[i].channel = C.uint(in.Channel)
+	}
+	o := C.gdg_batch_options{target_rate: C.uint32_t(opt.TargetRate), out_format: C.int(opt.OutFormat),
+		metronome_to_master: cbool(opt.MetronomeToMaster), run_meters: cbool(opt.RunMeters), tuner_enqueue: cbool(opt.TunerEnqueue)}
+	var done C.size_t
+	var rc C.int
+	if shard {
+		rc = C.gdg_batch_stream_resume_shard(this.ctx, &arr[0], C.int(n), &o, C.size_t(jobSamples), cbool(runMetronome), unsafe.Pointer(&blob[0]), C.size_t(len(blob)), &done)
+	} else {
+		rc = C.gdg_batch_stream_resume(this.ctx, &arr[0], C.int(n), &o, unsafe.Pointer(&blob[0]), C.size_t(len(blob)), &done)
+	}
+	if e := this.err(rc); e != nil {
+		return 0, e
+	}
+	this.streamInputs = n
+	this.streamWidth = int(C.gdg_wave_bytes_per_sample(o.out_format))
+	return uint64(done), nil
+}
+
+// BatchStreamResume takes the place of BatchStreamOpen on a context configured as for a fresh job (chains, parameters, taps,
+// positions, metronome, meter ports): the job of the checkpoint, given again with inputs and opt, is open at the recorded position,
+// which is returned (samples done).  All or nothing: a blob that is damaged or does not fit the job or the chains is an error, changes
+// nothing and leaves no job open.
+func (this *Context) BatchStreamResume(inputs []BatchStreamInput, opt BatchOptions, blob []byte) (uint64, error) {
+	return this.streamResume(inputs, opt, false, 0, true, blob)
+}
+
+// BatchStreamResumeShard is BatchStreamResume for a job opened with BatchStreamOpenShard (same jobSamples and runMetronome).
+func (this *Context) BatchStreamResumeShard(inputs []BatchStreamInput, opt BatchOptions, jobSamples uint64, runMetronome bool, blob []byte) (uint64, error) {
+	return this.streamResume(inputs, opt, true, jobSamples, runMetronome, blob)
+}
+
+// StateVerify checks the digest of a checkpoint container on the device and writes nothing (gdg_state_verify).  The digest is for
+// integrity only.  A bare SaveState blob has none and is an error.
+func (this *Context) StateVerify(blob []byte) error {
+	if len(blob) == 0 {
+		return fmt.Errorf("gdg: an empty checkpoint")
+	}
+	return this.err(C.gdg_state_verify(this.ctx, unsafe.Pointer(&blob[0]), C.size_t(len(blob))))
+}
+
 // BatchStreamOpenShard begins the job of BatchRunShard in slices (gdg_batch_stream_open_shard): one shard of a job split over several
 // contexts whose files are too long to hold.  jobSamples = the job's length (the longest BatchLength over all shards, 0 = this shard's
 // own); runMetronome says once, for the whole job, whether this shard runs the metronome.  opt.MetronomeToMaster must be false: the aux

@@ -1088,6 +1088,7 @@ Error Engine::BatchStreamShardedOpen(const gdg_batch_input *inputs, int nInputs,
     }
     shardedOpen_ = true;
     shardedOptions_ = options;
+    shardedSlices_ = 0;
     *samples = job;
     return "";
 }
@@ -1156,12 +1157,176 @@ Error Engine::BatchStreamShardedStep(int blocks, const void *const *ins, void *c
             e = gdg_last_error(ctx0);
     }
     if (!e.empty()) { closeSharded(); setError(e); return LastError(); }
+    shardedSlices_++;
     return "";
 }
 
 Error Engine::BatchStreamShardedClose() {
     if (!shardedOpen_) return "BatchStreamShardedClose: no streamed batch run is open";
     closeSharded();
+    return "";
+}
+
+/* ---- checkpoint and resume of the streamed runs (gdg_batch_stream_checkpoint / _resume) ---- */
+static Error checkpointOf(gdg_ctx *ctx, std::vector<uint8_t> &blob) {
+    size_t bytes = 0, written = 0;
+    if (gdg_batch_stream_checkpoint_size(ctx, &bytes) != GDG_OK) return gdg_last_error(ctx);
+    blob.assign(bytes ? bytes : 1, 0);
+    if (gdg_batch_stream_checkpoint(ctx, blob.data(), bytes, &written) != GDG_OK) return gdg_last_error(ctx);
+    blob.resize(written);
+    return "";
+}
+
+Error Engine::BatchStreamCheckpoint(std::vector<uint8_t> &blob) {
+    Error e = streamShard(this, "checkpoint");
+    if (!e.empty()) { setError(e); return e; }
+    std::lock_guard<std::mutex> lk(shards_[0]->mu);
+    gdg_ctx *ctx = shards_[0]->ctx;
+    if (!ctx) return "BatchStreamCheckpoint: no streamed batch run is open";
+    e = checkpointOf(ctx, blob);
+    if (!e.empty()) setError(e);
+    return e;
+}
+
+Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, const uint8_t *blob, size_t bytes,
+                                size_t *samplesDone) {
+    if (!inputs || !blob || !samplesDone) return "BatchStreamResume: no inputs, no checkpoint or nowhere to put the position";
+    if (nInputs != nChannels_) return format("BatchStreamResume: %d inputs for %d channels", nInputs, nChannels_);
+    Error e = streamShard(this, "resume");
+    if (!e.empty()) { setError(e); return e; }
+    setError("");
+    std::vector<std::shared_ptr<signal::Chain>> chains;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        chains = chains_;
+    }
+    std::lock_guard<std::mutex> lk(shards_[0]->mu);
+    gdg_ctx *ctx = context(0);
+    if (!ctx) return LastError();
+    std::vector<signal::Chain *> mine;
+    for (auto &c : chains) mine.push_back(c.get());
+    e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
+    if (!e.empty()) { setError(e); return e; }
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+        setError(gdg_last_error(ctx));
+        return LastError();
+    }
+    return "";
+}
+
+namespace {
+struct EngineCheckpoint { char magic[8]; uint32_t version, shards; uint64_t slices; };      /* then per shard: uint64 bytes, the container */
+static_assert(sizeof(EngineCheckpoint) == 24, "engine checkpoint wrapper layout");
+const char kEngineCheckpointMagic[8] = { 'G', 'D', 'G', 'E', 'N', 'G', 'C', 'K' };
+}
+
+Error Engine::BatchStreamShardedCheckpoint(std::vector<uint8_t> &blob) {
+    if (!shardedOpen_) return "BatchStreamShardedCheckpoint: no streamed batch run is open";
+    const int G = shards();
+    EngineCheckpoint h;
+    memset(&h, 0, sizeof(h));
+    memcpy(h.magic, kEngineCheckpointMagic, 8);
+    h.version = 1;
+    h.shards = (uint32_t)G;
+    h.slices = shardedSlices_;
+    blob.assign(reinterpret_cast<const uint8_t *>(&h), reinterpret_cast<const uint8_t *>(&h) + sizeof(h));
+    for (int g = 0; g < G; g++) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        std::vector<uint8_t> one;
+        if (count > 0) {
+            std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+            Error e = checkpointOf(shards_[(size_t)g]->ctx, one);
+            if (!e.empty()) { setError(format("shard %d: %s", g, e.c_str())); return LastError(); }
+        }
+        const uint64_t n = one.size();
+        blob.insert(blob.end(), reinterpret_cast<const uint8_t *>(&n), reinterpret_cast<const uint8_t *>(&n) + sizeof(n));
+        blob.insert(blob.end(), one.begin(), one.end());
+    }
+    return "";
+}
+
+Error Engine::BatchStreamShardedResume(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, const uint8_t *blob,
+                                       size_t bytes, size_t *samplesDone, uint64_t *slicesDone) {
+    if (!inputs || !blob || !samplesDone) return "BatchStreamShardedResume: no inputs, no checkpoint or nowhere to put the position";
+    if (nInputs != nChannels_) return format("BatchStreamShardedResume: %d inputs for %d channels", nInputs, nChannels_);
+    if (shardedOpen_) { setError("BatchStreamShardedResume: a streamed batch run is already open on this engine"); return LastError(); }
+    const int G = shards();
+    EngineCheckpoint h;
+    if (bytes < sizeof(h)) { setError("BatchStreamShardedResume: the checkpoint is truncated"); return LastError(); }
+    memcpy(&h, blob, sizeof(h));
+    if (memcmp(h.magic, kEngineCheckpointMagic, 8) != 0 || h.version != 1) { setError("BatchStreamShardedResume: not an engine checkpoint of version 1"); return LastError(); }
+    if (h.shards != (uint32_t)G) { setError(format("BatchStreamShardedResume: the checkpoint is of %u shards, this engine has %d", h.shards, G)); return LastError(); }
+    std::vector<std::pair<const uint8_t *, size_t>> parts;
+    size_t at = sizeof(h);
+    for (int g = 0; g < G; g++) {
+        uint64_t n = 0;
+        if (bytes - at < sizeof(n)) { setError("BatchStreamShardedResume: the checkpoint is truncated"); return LastError(); }
+        memcpy(&n, blob + at, sizeof(n));
+        at += sizeof(n);
+        if (n > bytes - at) { setError(format("BatchStreamShardedResume: the checkpoint is truncated in shard %d", g)); return LastError(); }
+        parts.emplace_back(blob + at, (size_t)n);
+        at += (size_t)n;
+    }
+    setError("");
+    std::vector<std::shared_ptr<signal::Chain>> chains;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        chains = chains_;
+    }
+    /* as BatchStreamShardedOpen: every shard follows its chains, the job's length is the longest shard's */
+    size_t job = 0;
+    for (int g = 0; g < G; g++) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        if (count <= 0) continue;
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        gdg_ctx *ctx = context(g);
+        if (!ctx) return LastError();
+        std::vector<signal::Chain *> mine;
+        for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
+        Error e = sync(g, mine, options.target_rate);
+        if (!e.empty()) { setError(e); return e; }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        size_t len = 0;
+        if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        job = std::max(job, len);
+    }
+    gdg_batch_options o = options;
+    o.metronome_to_master = 0;
+    size_t done = 0;
+    bool have = false;
+    for (int g = 0; g < G; g++) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        if (count <= 0) continue;
+        Error e;
+        {
+            std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+            gdg_ctx *ctx = shards_[(size_t)g]->ctx;
+            size_t pos = 0;
+            if (gdg_batch_stream_resume_shard(ctx, inputs + first, count, &o, job, g == 0, parts[(size_t)g].first, parts[(size_t)g].second, &pos) != GDG_OK)
+                e = format("shard %d: %s", g, gdg_last_error(ctx));
+            else if (have && pos != done) {
+                (void)gdg_batch_stream_close(ctx);
+                e = format("shard %d stands at sample %zu, the shards before it at %zu", g, pos, done);
+            }
+            if (e.empty()) { done = pos; have = true; }
+        }
+        if (!e.empty()) {
+            for (int k = 0; k < g; k++) {
+                std::lock_guard<std::mutex> lk(shards_[(size_t)k]->mu);
+                if (shards_[(size_t)k]->ctx) (void)gdg_batch_stream_close(shards_[(size_t)k]->ctx);
+            }
+            setError(e);
+            return e;
+        }
+    }
+    shardedOpen_ = true;
+    shardedOptions_ = options;
+    shardedSlices_ = h.slices;
+    *samplesDone = done;
+    if (slicesDone) *slicesDone = h.slices;
     return "";
 }
 

@@ -226,6 +226,19 @@ public:
     Error BatchStreamShardedNeed(int blocks, size_t *first, size_t *count);
     Error BatchStreamShardedStep(int blocks, const void *const *ins, void *const *outs);
     Error BatchStreamShardedClose();
+    /* No reference counterpart.  The open streamed job as a blob, and a job continued from one (gdg_batch_stream_checkpoint / _resume,
+     * include/gdg.h): Checkpoint is valid between any two slices and changes nothing; Resume takes the place of Open on an engine whose
+     * chains are set up as for the fresh job -- it synchronises them to the device, sets the window (which may differ from the
+     * source's) and opens the job at the recorded position, returned in `samplesDone`.  All or nothing.  The pair without "Sharded" is
+     * for an engine of ONE shard, as BatchStreamOpen is.  The sharded pair writes one container per shard behind a small host-side
+     * wrapper ("GDGENGCK", version, shard count, slices done, then per shard its size and its container); Resume refuses a wrapper of
+     * another shard count, and a shard that rejects its container closes the shards already resumed.  `slicesDone`: the wrapper's. */
+    Error BatchStreamCheckpoint(std::vector<uint8_t> &blob);
+    Error BatchStreamResume(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, const uint8_t *blob, size_t bytes,
+                            size_t *samplesDone);
+    Error BatchStreamShardedCheckpoint(std::vector<uint8_t> &blob);
+    Error BatchStreamShardedResume(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, const uint8_t *blob,
+                                   size_t bytes, size_t *samplesDone, uint64_t *slicesDone = nullptr);
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -262,6 +275,7 @@ private:
     int expected_ = 0, timeoutMs_ = 50;
     bool shardedOpen_ = false;                             /* BatchStreamSharded*: a job is open on every shard, with these options */
     gdg_batch_options shardedOptions_ = {};
+    uint64_t shardedSlices_ = 0;                           /* ... and this many slices done (a checkpoint's wrapper records it) */
     void closeSharded();
     mutable std::mutex errMu_;
     std::string lastError_;

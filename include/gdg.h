@@ -246,7 +246,9 @@ int gdg_chain_set(gdg_ctx *ctx, int channel, const int *handles, const uint8_t *
  * phaser, auto-yoy, reverb rings, oversampler histories) with the host's record of their layout; per power amp the overlap-save history,
  * the newest K delay-line slots in age order and the frame counter; per channel the spatializer's history row.  NOT state, not saved:
  * parameters and filter taps (they stay with the target's units: a parameter that changes no layout may differ), sums made ahead of the
- * frame, scan tables, spectra.  Out of scope: the tuner rings (gdg_tuner_replace restores them), meters, the metronome, batch-run buffers.
+ * frame, scan tables, spectra.  Out of scope of THIS blob: the tuner rings, meters, the metronome's counters and a streamed job's position
+ * and resampler frames -- the checkpoint container (gdg_batch_stream_checkpoint, below) carries them beside this blob; a batch run's
+ * other buffers hold nothing between two calls.
  *
  * A save has no side effects: it is ordered after everything queued on the context and keeps the sums made ahead, so a stream with
  * saves between its calls gives the same bits as one without.  A load is all or nothing: it lays the target's units out at the blob's
@@ -576,7 +578,8 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
  * need without open, with `blocks` beyond the job's end, and after the last block.  A slice steps where the one-call run of the whole job
  * would step (or where the slice ends), so meters, tuner, metronome and the units' state are the one-call context's; a gdg_state_save
  * blob is equal as well where the job's last steps coincide (the convolution keeps two history halves, of which the one not read next
- * holds whatever frame the window grouping left there).  A slice that fails half-way closes the job.  State
+ * holds whatever frame the window grouping left there).  A slice that fails half-way closes the job (a checkpoint taken before it, below,
+ * continues the job in a fresh context).  State
  * save / load and parameter changes between slices behave as between two gdg_batch_run calls.  The buffers are the batch run's own
  * (option stat_batch_device_kib reads their size, gdg_batch_release frees them).
  *
@@ -631,6 +634,58 @@ int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice);
 int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                                   size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes);
+/*
+ * CHECKPOINT of a streamed batch run: no reference counterpart.  One blob that holds everything a streamed job (plain or a shard's)
+ * carries from one slice to the next, written between any two slices -- also before the first and after the last -- and loaded into a
+ * new process, context or device, where the job continues with the bytes the uninterrupted run would have written:
+ *   gdg_batch_stream_checkpoint_size(ctx, &bytes); gdg_batch_stream_checkpoint(ctx, blob, capacity, &written)
+ *                                                                      valid between open and close; ordered after everything queued
+ *                                                                      on the context; NO side effects (gdg_state_save's contract: the
+ *                                                                      sums made ahead are kept, a job with a checkpoint between every
+ *                                                                      two slices writes the same bytes as one without); into less
+ *                                                                      capacity it fails with *written = the size needed
+ *   gdg_batch_stream_resume(ctx, inputs, N, &options, blob, bytes, &samples_done)
+ *   gdg_batch_stream_resume_shard(ctx, inputs, n, &options, job_samples, run_metronome, blob, bytes, &samples_done)
+ *                                                                      in the place of gdg_batch_stream_open / _open_shard on a context
+ *                                                                      with no job open; on success the job is open at the recorded
+ *                                                                      position (*samples_done), gdg_batch_stream_need continues first[i]
+ *                                                                      where the checkpointed job stood, and a blob taken after the last
+ *                                                                      block gives a job that has delivered its last block
+ * STATE, in the blob: the job (position, length, per input the frames handed over and the samples it covers, the inputs' metadata, the
+ * options, for a shard `shard`, run_metronome and job_samples); the gdg_state_save blob of all channels, unchanged (version 1); per
+ * resampled input the GDG_STREAM_CARRY = 8 source frames resample.Time looks back at and how many of them are valid; per meter port
+ * value, held peak and hold counter; the tuner rings (oldest sample first) with their rate, present when the source had rings; the
+ * metronome's sample and tick counters.  CONFIGURATION, with the target: chains, parameters, filter taps, spatializer positions,
+ * metronome sounds and settings, gdg_meter_configure and the ports' enabled flags, window (gdg_ctx_set_window) and channel groups --
+ * the caller sets the target up as for a fresh job; window and groups may differ from the source's (a delay line is rotated into the
+ * target's ring and windows give the bits of single frames, so the continued bytes depend on neither).
+ * inputs and options are given again (the blob holds no pointers) and checked against the recorded job: channel count; per input
+ * has-samples, samples_per_channel, format, rate, channels, channel; target_rate, out_format, the three flags; a shard's job_samples and
+ * run_metronome; a shard's blob is refused by gdg_batch_stream_resume and a plain one by _resume_shard.  A resume is ALL OR NOTHING, in
+ * this order: the digest; the job; every layout key of the embedded channel state (as gdg_state_load); meter port count and tuner ring
+ * length; only then it writes.  A mismatch returns GDG_ERR_INVALID with gdg_last_error naming what did not fit, writes nothing and
+ * leaves no job open.
+ * Container (opaque; little-endian, stable within one version): a 48-byte header {"GDGCKPT\0", version 1, payload offset = 48, total
+ * bytes, reserved, 16 bytes of digest}, then the payload -- a directory of six sections {offset, bytes} (job, channel state, meters,
+ * tuner, metronome, resampler carry; bytes 0 = absent) and the sections at 16-byte alignment.
+ * DIGEST, over the payload bytes [48, total) cut into n granules of 16 bytes, granule g = two little-endian 64-bit words a_g, b_g; all
+ * arithmetic modulo 2^64, K = 0x9e3779b97f4a7c15, M0 = 0xff51afd7ed558ccd, M1 = 0xc4ceb9fe1a85ec53:
+ *   u_g = t ^ (t >> 32) with t = (a_g + (g + 1) K) M0;     v_g = s ^ (s >> 29) with s = (b_g ^ u_g) M1
+ *   S0 = sum of u_g;  S1 = XOR of v_g;     fmix(x): x ^= x >> 33, x *= M0, x ^= x >> 33, x *= M1, x ^= x >> 33
+ *   D0 = fmix(S0 + K + n);  D1 = fmix(S1 ^ D0);     stored as D0, D1 little-endian
+ * Order-sensitive (g enters every term) and independent of how the device splits the work (sum and XOR commute).  It is taken on the
+ * device: over the staged blob just gathered in a checkpoint, over the uploaded copy before anything else in a resume.  The digest is
+ * for INTEGRITY ONLY -- truncation, bit rot, a torn write; it is no authentication and no defence against a crafted blob.
+ * gdg_state_verify checks a container's digest (on ctx's device) and writes nothing; a bare gdg_state_save blob carries no digest and
+ * is GDG_ERR_INVALID, saying so.
+ */
+int gdg_batch_stream_checkpoint_size(gdg_ctx *ctx, size_t *bytes);
+int gdg_batch_stream_checkpoint(gdg_ctx *ctx, void *blob, size_t capacity, size_t *written);
+int gdg_batch_stream_resume(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *options, const void *blob,
+                            size_t bytes, size_t *samples_done);
+int gdg_batch_stream_resume_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *options, size_t job_samples,
+                                  int run_metronome, const void *blob, size_t bytes, size_t *samples_done);
+int gdg_state_verify(gdg_ctx *ctx, const void *blob, size_t bytes);
 /* The device buffers of a batch run (the decoded inputs are the large part: N x length x 8 bytes) stay with the context for the next
  * run of the same or a smaller size; this frees them. */
 int gdg_batch_release(gdg_ctx *ctx);
