@@ -9,26 +9,40 @@
 
 #define GDG_BLOCK_SIZE 8192           /* controller/controller.go:36 */
 
+/* resample/resample.go:72-87 with 64-bit lengths (gdg_resample_time_length for files of any length; a rate of 0: nothing) */
+static size_t resample_length64(size_t n, uint32_t source_rate, uint32_t target_rate) {
+    if (source_rate == 0 || target_rate == 0) return 0;
+    const double expansion = (double)target_rate / (double)source_rate;
+    const double out_len_f = (double)n * expansion, out_len_floor = floor(out_len_f);
+    long long out_len = (long long)out_len_floor;
+    if (out_len_floor == out_len_f) out_len--;
+    return out_len < 0 ? 0 : (size_t)out_len;
+}
+
+/* the samples an input covers in a job at target_rate: its (resampled) length, controller.go:2993-2999; none without bytes */
+static size_t input_covers(const gdg_batch_input &in, uint32_t target_rate) {
+    if (!in.bytes || !in.samples_per_channel) return 0;
+    return in.sample_rate == target_rate ? in.samples_per_channel : resample_length64(in.samples_per_channel, in.sample_rate, target_rate);
+}
+
+/* every channel is padded to the longest input, in whole blocks (controller.go:3005-3016) */
+static size_t whole_blocks(size_t samples) {
+    return samples % GDG_BLOCK_SIZE ? GDG_BLOCK_SIZE * (samples / GDG_BLOCK_SIZE + 1) : samples;
+}
+
 int gdg_batch_length(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, uint32_t target_rate, size_t *samples) {
     if (!ctx || !inputs || !samples || n_inputs <= 0) return GDG_ERR_INVALID;
     size_t max_len = 0;
     for (int i = 0; i < n_inputs; i++) {
-        const gdg_batch_input &in = inputs[i];
-        size_t len = (in.bytes && in.samples_per_channel) ? in.samples_per_channel : 0;
-        if (len > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "input %d is too long", i);
-        if (len > 0 && in.sample_rate != target_rate) {                       /* controller.go:2993-2999 */
-            int r = gdg_resample_time_length((int)len, in.sample_rate, target_rate);
-            len = r > 0 ? (size_t)r : 0;
-        }
-        if (len > max_len) max_len = len;
+        if (inputs[i].bytes && inputs[i].samples_per_channel > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "input %d is too long", i);
+        max_len = std::max(max_len, input_covers(inputs[i], target_rate));
     }
-    if (max_len % GDG_BLOCK_SIZE) max_len = GDG_BLOCK_SIZE * (max_len / GDG_BLOCK_SIZE + 1);       /* :3014-3016 */
-    *samples = max_len;
+    *samples = whole_blocks(max_len);
     return GDG_OK;
 }
 
-/* slot i of the batch run's device buffers with at least `bytes` */
-int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out) {
+/* slot i of the batch run's device buffers (ctx.h: BATCH_INPUTS ..) with at least `bytes` */
+static int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out) {
     if (bytes > ctx->batch_dev_cap[i]) {
         hipFree(ctx->batch_dev[i]);
         ctx->batch_dev[i] = nullptr;
@@ -38,6 +52,11 @@ int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out) {
     }
     *out = ctx->batch_dev[i];
     return GDG_OK;
+}
+
+/* the frames every resampled input keeps for its next step: the same few bytes for every job of the context's channels */
+int batch_carry_buffer(gdg_ctx *ctx, double **d_carry) {
+    return batch_buffer(ctx, BATCH_CARRY, (size_t)ctx->nch * GDG_STREAM_CARRY * sizeof(double), (void **)d_carry);
 }
 
 int gdg_batch_release(gdg_ctx *ctx) {
@@ -91,7 +110,7 @@ static void move_pieces(gdg_ctx *ctx, const std::vector<BatchPiece> &pieces, int
                        pieces.empty() ? 0 : total / pieces.size(), which);
 }
 
-/* ---- the block loop of a batch run, shared by the one-call run and the streamed run's slices ---------------------------------------- */
+/* ---- the block loop of one slice of a batch job -------------------------------------------------------------------------------------- */
 struct BatchLoop {
     int N, enc_rows, f64_rows, out_width, W;
     size_t length;                              /* samples of every row of d_inputs = the samples this loop walks */
@@ -101,15 +120,18 @@ struct BatchLoop {
     const gdg_batch_options *opt;
     void *const *out_bytes;
     const gdg_batch_shard_out *shard;
-    bool run_metro, n_streamed;                 /* n_streamed: some inputs come with their step (stage) */
+    bool run_metro, has_input;                  /* has_input: some input has samples, which come with their step (stage) */
     int trace;
     double t_begin;
-    size_t job_blocks, origin_blocks;           /* a slice of a streamed job of job_blocks blocks that starts at block origin_blocks; 0, 0: a whole job */
+    size_t job_blocks, origin_blocks;           /* the slice of a job of job_blocks blocks that starts at block origin_blocks */
 };
 
-/* the step [first, first + w) of the one-call run of a job of `job` blocks in windows of W that holds block p (the steps batch_block_loop
- * makes for a whole job, in closed form) */
-static void one_call_step(size_t job, int W, size_t p, size_t *first, int *w) {
+/* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
+ * A long job opens with a quarter window and a half window: the device has nothing to do until the first step's bytes are gathered and
+ * uploaded (16 blocks of 512 files: 1.9 + 2.4 ms), and what it computes first comes down and is scattered while nothing else waits for the
+ * host; each step's upload fits behind the step before.  Then whole windows, then a tail of W/2, W/4 .. 1 (the last download and scatter
+ * are a quarter step's).  Window sizes only change the time blocking, never a sample (tests/test_gpu_window.py). */
+static void job_step(size_t job, int W, size_t p, size_t *first, int *w) {
     const size_t head = (W >= 8 && job >= (size_t)3 * W) ? (size_t)(W / 4 + W / 2) : 0;
     if (head && p < (size_t)(W / 4)) { *first = 0; *w = W / 4; return; }
     if (head && p < head) { *first = (size_t)(W / 4); *w = W / 2; return; }
@@ -134,43 +156,25 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     const gdg_batch_options *opt = p.opt;
     void *const *out_bytes = p.out_bytes;
     const gdg_batch_shard_out *shard = p.shard;
-    const bool sharded = shard != nullptr, run_metro = p.run_metro, n_streamed = p.n_streamed;
+    const bool sharded = shard != nullptr, run_metro = p.run_metro, has_input = p.has_input;
     const int trace = p.trace;
     const double t_begin = p.t_begin;
     auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     int r;
-    /* 2. the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
+    /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
     struct Step { size_t off; int w; };
     std::vector<Step> steps;
-    /* A long run opens with a quarter window and a half window: the device has nothing to do until the first step's bytes are gathered and uploaded (16 blocks
-     * of 512 files: 1.9 + 2.4 ms), and what it computes first comes down and is scattered while nothing else waits for the host.  The blocks
-     * that step leaves over make the tail shorter the same way (W/2, W/4: the last download and scatter are a quarter step's).  Window sizes
-     * only change the time blocking, never a sample (tests/test_gpu_window.py). */
-    size_t off0 = 0;
-    if (p.job_blocks) {
-        /* a slice of a streamed job steps where the one-call run of the whole job would: a step ends where that run's step ends (or the
-         * slice does), so that the windows -- and with them what the units keep beyond the samples, the convolution's two history
-         * halves -- are the one-call run's wherever the slicing allows it */
-        for (size_t off = 0; off < length;) {
-            const size_t at = p.origin_blocks + off / B, end = p.origin_blocks + length / B;
-            size_t first = 0;
-            int w1 = 1, w = 1;
-            one_call_step(p.job_blocks, W, at, &first, &w1);
-            const size_t room = std::min(first + (size_t)w1, end) - at;
-            while ((size_t)w * 2 <= room) w *= 2;
-            steps.push_back({ off, w });
-            off += (size_t)w * B;
-        }
-        off0 = length;
-    } else if (W >= 8 && length >= (size_t)3 * W * B) {                             /* W/4, W/2, then whole windows: each step's upload fits behind the step before */
-        steps.push_back({ 0, W / 4 });
-        steps.push_back({ (size_t)(W / 4) * B, W / 2 });
-        off0 = (size_t)(W / 4 + W / 2) * B;
-    }
-    for (size_t off = off0; off < length;) {
-        int w = W;
-        while ((size_t)w * B > length - off) w >>= 1;                        /* the tail: windows of W/2, W/4 .. 1 */
+    /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
+     * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
+     * wherever the slicing allows it */
+    for (size_t off = 0; off < length;) {
+        const size_t at = p.origin_blocks + off / B, end = p.origin_blocks + length / B;
+        size_t first = 0;
+        int w1 = 1, w = 1;
+        job_step(p.job_blocks, W, at, &first, &w1);
+        const size_t room = std::min(first + (size_t)w1, end) - at;
+        while ((size_t)w * 2 <= room) w *= 2;
         steps.push_back({ off, w });
         off += (size_t)w * B;
     }
@@ -201,17 +205,17 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         }
         return GDG_OK;
     };
-    HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed, whole-file inputs decoded */
-    if (n_streamed) HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_up_stream, ctx->batch_begin, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
+    if (has_input) HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_up_stream, ctx->batch_begin, 0));
     auto stage = [&](size_t i, int pool = 0) -> int {
-        if (!n_streamed || i >= steps.size()) return GDG_OK;
+        if (!has_input || i >= steps.size()) return GDG_OK;
         return stage_fn(i, steps[i].off, steps[i].w, pool);
     };
     /* step i on the compute stream: the block loop's work for its w blocks, then the encoder into the step's half of `enc` */
     auto enqueue_compute = [&](size_t i) -> int {
         const size_t off = steps[i].off;
         const int w = steps[i].w, h = (int)(i & 1), wb = w * B;               /* this step fills the first wb samples of the window's rows */
-        if (n_streamed) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_up_ready[h], 0));
+        if (has_input) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_up_ready[h], 0));
         const double *d_in = d_inputs + off;
         double *d_master = d_win + (size_t)N * ws, *d_metro = d_master + 2 * ws;
         unsigned char *enc = d_enc + h * enc_bytes;
@@ -275,7 +279,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
      * blocks or more the gather runs on a helper thread with copy workers of its own (copy_pool_up), one step further ahead (step i + 3 while
      * step i is scattered; its pinned half and its device half were step i + 1's, whose upload and decode are long done -- stage() waits
      * for their event): the host's step is the scatter alone and the device sets the pace. */
-    const bool helper = n_streamed && ws >= (size_t)4 * B && steps.size() > 3;
+    const bool helper = has_input && ws >= (size_t)4 * B && steps.size() > 3;
     std::future<int> staged;
     struct Join { std::future<int> &f; ~Join() { if (f.valid()) f.wait(); } } join_on_exit{ staged };     /* stage() captures this frame by reference */
     /* the upload side's copy workers are made HERE, by the caller's thread, and the helper thread goes where they go: with option "numa" = 2
@@ -331,224 +335,18 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         const double t_enq = now_ms();
         if ((r = scatter(i)) != GDG_OK) return r;                            /* ... step i comes down and goes into the files, piece by piece */
         if (i + 2 < steps.size() && (r = enqueue_down(i + 2)) != GDG_OK) return r;     /* its pinned half is free again */
-        if (trace) fprintf(stderr, "[batch] step %zu: stage %zu %.2f | (%.2f) | enqueue %zu %.2f | download + scatter %.2f  (at %.2f ms)\n", i, i + 2,
+        if (trace) fprintf(stderr, "[batch] step %zu (w %d): stage %zu %.2f | (%.2f) | enqueue %zu %.2f | download + scatter %.2f  (at %.2f ms)\n", i, steps[i].w, i + 2,
                            t_st - t_it, t_wait - t_st, i + 2, t_enq - t_wait, now_ms() - t_enq, now_ms() - t_begin);
     }
     return check_device_error(ctx);
 }
 
-/*
- * Phases (all device work on the context's stream; PCIe on the copy stream through two pinned halves):
- *   1. the file bytes of all inputs, packed into one arena, go up in half-sized chunks: the copy threads gather chunk k + 1 while
- *      the DMA engine moves chunk k; then one decode (+ resample.Time) per input into its row of the [N][length] inputs.
- *   2. per block: copy in, tuner, N x Chain.Process, metronome, spatializer, meters, encode the block's N + 3 rows in one launch;
- *      the encoded block (N + 3 rows x 8192 x width bytes) goes down on the copy stream while the next block computes, and the
- *      copy threads scatter it into the caller's N + 3 buffers.
- */
-static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes,
-                          const gdg_batch_shard_out *shard) {
-    if (!ctx || !inputs || !opt || !out_bytes) return GDG_ERR_INVALID;
-    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is open on this context: gdg_batch_stream_close it first");
-    if (n_inputs != ctx->nch) return fail(ctx, GDG_ERR_INVALID, "the batch has %d inputs, the context %d channels", n_inputs, ctx->nch);
-    if (ctx->max_frames < GDG_BLOCK_SIZE)
-        return fail(ctx, GDG_ERR_INVALID, "the batch loop runs blocks of %d frames, the context allows %d", GDG_BLOCK_SIZE, ctx->max_frames);
-    const int out_width = gdg_wave_bytes_per_sample(opt->out_format);
-    if (!out_width) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", opt->out_format);
-    if (opt->target_rate == 0) return fail(ctx, GDG_ERR_INVALID, "sample rate must be positive");
-    const int N = n_inputs, NO = N + 3, B = GDG_BLOCK_SIZE, ports = 2 * N + 3;
-    /* One shard of a job split over several contexts (SURVEY.md 8e): the master mix is the sum over ALL channels, then the aux input,
-     * then the encoder's clip (spatializer.go:300-310, controller.go:3123-3219) -- so a shard hands out its PARTIAL sums as float64
-     * and gdg_batch_finish_master adds the shards' partials in shard order, then aux, then encodes.  The metronome runs on the shard
-     * that is given somewhere to put it. */
-    const bool sharded = shard != nullptr;
-    if (sharded && (!shard->master_left || !shard->master_right)) return fail(ctx, GDG_ERR_INVALID, "a shard needs buffers for its partial master mix");
-    const bool run_metro = !sharded || shard->metronome_bytes || shard->metronome;
-    const int enc_rows = sharded ? N + (shard->metronome_bytes ? 1 : 0) : NO;      /* rows that leave the device encoded */
-    const int f64_rows = sharded ? 2 + (shard->metronome ? 1 : 0) : 0;             /* rows that leave it as float64 */
-    /* inputs that are mono and already at the target rate are STREAMED: their bytes go up step by step while the block loop runs;
-     * the others (a channel picked out of an interleaved file, resample.Time over the whole file) go up before the loop */
-    std::vector<size_t> arena_off((size_t)N, 0);
-    std::vector<char> streamed((size_t)N, 0);
-    size_t arena_bytes = 0, src_cap = 0, up_sample_bytes = 0;
-    int n_streamed = 0;
-    for (int i = 0; i < N; i++) {
-        const gdg_batch_input &in = inputs[i];
-        if (!in.bytes || !in.samples_per_channel) continue;
-        const int w = gdg_wave_bytes_per_sample(in.format);
-        if (!w) return fail(ctx, GDG_ERR_UNSUPPORTED, "input %d: unknown sample format %d", i, in.format);
-        if (in.channels == 0 || in.channel >= in.channels) return fail(ctx, GDG_ERR_INVALID, "input %d: channel %u of %u", i, in.channel, in.channels);
-        if (in.sample_rate == 0) return fail(ctx, GDG_ERR_INVALID, "input %d: sample rate must be positive", i);
-        const size_t count = in.samples_per_channel * in.channels;
-        if (in.sample_rate == opt->target_rate && in.channels == 1) {
-            streamed[(size_t)i] = 1;
-            n_streamed++;
-            up_sample_bytes += (size_t)w;
-            continue;
-        }
-        arena_off[(size_t)i] = arena_bytes;
-        arena_bytes += (count * (size_t)w + 15) & ~(size_t)15;
-        if (count > src_cap) src_cap = count;
-    }
-    size_t length = 0;
-    int rc = gdg_batch_length(ctx, inputs, n_inputs, opt->target_rate, &length);
-    if (rc != GDG_OK) return rc;
-    if (sharded && shard->job_samples) {
-        if (shard->job_samples < length || shard->job_samples % GDG_BLOCK_SIZE)
-            return fail(ctx, GDG_ERR_INVALID, "the job's %zu samples: at least this shard's %zu and a multiple of %d", shard->job_samples, length, GDG_BLOCK_SIZE);
-        length = shard->job_samples;
-    }
-    if (length == 0) return GDG_OK;                                            /* every output has 0 samples */
-    if (opt->run_meters && ctx->n_meter != ports)
-        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d (a shard: its N inputs, its N outputs, metronome, left, right)",
-                    ctx->n_meter, ports);
-    enter(ctx);
-    const int W = ctx->window;                                                 /* frames per step (gdg_ctx_set_window; 1 = the reference's loop) */
-    const size_t ws = (size_t)W * B;                                           /* row stride of the window, the same for every step */
-    const size_t enc_bytes = (((size_t)enc_rows * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_rows * ws * sizeof(double);   /* one window on its way down */
-    const size_t half = std::max(enc_bytes, (size_t)8 << 20);
-    if (length > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "files of %zu samples are too long", length);
-    /* one step of the streamed inputs: the piece descriptors, then every piece on a 16-byte boundary */
-    const size_t up_rows_bytes = ((size_t)n_streamed * sizeof(gdg_decode_row) + 255) & ~(size_t)255;
-    const size_t up_half = n_streamed ? up_rows_bytes + up_sample_bytes * (size_t)W * B + 16 * (size_t)n_streamed : 0;
-    rc = ensure_batch_pipe(ctx, half, up_half);
-    if (rc != GDG_OK) return rc;
-    double *d_inputs = nullptr, *d_win = nullptr, *d_src = nullptr;
-    unsigned char *d_arena = nullptr, *d_enc = nullptr, *d_up = nullptr;
-    static int trace = -1;
-    if (trace < 0) { const char *e = getenv("GDG_BATCH_TRACE"); trace = e ? atoi(e) : 0; }
-    auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now_ms();
-    auto body = [&]() -> int {
-        int r;
-        if ((r = batch_buffer(ctx, 0, (size_t)N * length * sizeof(double), (void **)&d_inputs)) != GDG_OK) return r;
-        /* one window of the N + 3 outputs, rows in the output files' order (out_0 .. out_{N-1}, master left, master right, metronome,
-         * controller.go:3123-3219); the inputs are read where they lie */
-        if ((r = batch_buffer(ctx, 1, (size_t)NO * ws * sizeof(double), (void **)&d_win)) != GDG_OK) return r;
-        if ((r = batch_buffer(ctx, 2, 2 * enc_bytes, (void **)&d_enc)) != GDG_OK) return r;
-        if (arena_bytes && (r = batch_buffer(ctx, 3, arena_bytes, (void **)&d_arena)) != GDG_OK) return r;
-        if (up_half && (r = batch_buffer(ctx, 4, 2 * up_half, (void **)&d_up)) != GDG_OK) return r;
-        if (src_cap && (r = batch_buffer(ctx, 5, src_cap * sizeof(double), (void **)&d_src)) != GDG_OK) return r;
-        /* the zero padding (:3018-3045): only what no decode / resample will write -- the tail of every row behind its file's samples, the
-         * whole row of an empty input (zeroing all N x length samples first cost 1.5 ms of a 60 ms run at 512 x 1 Mi samples) */
-        for (int i = 0; i < N; i++) {
-            const gdg_batch_input &in = inputs[i];
-            size_t covered = 0;
-            if (in.bytes && in.samples_per_channel) {
-                covered = in.samples_per_channel;
-                if (in.sample_rate != opt->target_rate) {
-                    int n_out = gdg_resample_time_length((int)in.samples_per_channel, in.sample_rate, opt->target_rate);
-                    covered = n_out > 0 ? (size_t)n_out : 0;
-                }
-                if (covered > length) covered = length;
-            }
-            if (covered < length)
-                HIP_TRY(ctx, hipMemsetAsync(d_inputs + (size_t)i * length + covered, 0, (length - covered) * sizeof(double), ctx->stream));
-        }
-
-        /* 1a. the arena goes up */
-        int used[2] = { 0, 0 };
-        int next_input = 0;
-        for (size_t k = 0, lo = 0; lo < arena_bytes; k++, lo += half) {
-            const size_t hi = std::min(arena_bytes, lo + half);
-            const int h = (int)(k & 1);
-            if (used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_moved[h]));
-            std::vector<BatchPiece> pieces;
-            while (next_input < N && (!inputs[next_input].bytes || !inputs[next_input].samples_per_channel || streamed[(size_t)next_input])) next_input++;
-            for (int i = next_input; i < N; i++) {
-                const gdg_batch_input &in = inputs[i];
-                if (!in.bytes || !in.samples_per_channel || streamed[(size_t)i]) continue;
-                const size_t a = arena_off[(size_t)i], nb = in.samples_per_channel * in.channels * (size_t)gdg_wave_bytes_per_sample(in.format);
-                if (a >= hi) break;
-                if (a + nb <= lo) { if (i == next_input) next_input++; continue; }
-                size_t s0 = std::max(a, lo), s1 = std::min(a + nb, hi);
-                for (size_t q = s0; q < s1; q += (size_t)1 << 20)                 /* pieces of <= 1 MiB */
-                    pieces.push_back({ ctx->h_batch[h] + (q - lo), static_cast<const unsigned char *>(in.bytes) + (q - a), std::min(s1 - q, (size_t)1 << 20) });
-            }
-            move_pieces(ctx, pieces);
-            HIP_TRY(ctx, hipMemcpyAsync(d_arena + lo, ctx->h_batch[h], hi - lo, hipMemcpyHostToDevice, ctx->batch_stream));
-            HIP_TRY(ctx, hipEventRecord(ctx->batch_moved[h], ctx->batch_stream));
-            used[h] = 1;
-        }
-        for (int h = 0; h < 2; h++) if (used[h]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_moved[h], 0));
-        /* 1b. decode (+ resample.Time) every input into its row */
-        for (int i = 0; i < N; i++) {
-            const gdg_batch_input &in = inputs[i];
-            if (!in.bytes || !in.samples_per_channel || streamed[(size_t)i]) continue;        /* "leaving channel empty" / comes with its step */
-            const size_t per = in.samples_per_channel;
-            double *row = d_inputs + (size_t)i * length;
-            if ((r = gdg_wave_decode_device(ctx, in.format, d_arena + arena_off[(size_t)i], per, in.channels, d_src)) != GDG_OK) return r;
-            const double *chan = d_src + (size_t)in.channel * per;           /* planar: samplesToChannels */
-            if (in.sample_rate == opt->target_rate)
-                HIP_TRY(ctx, hipMemcpyAsync(row, chan, per * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            else {
-                int n_out = gdg_resample_time_length((int)per, in.sample_rate, opt->target_rate);
-                if (n_out > 0 && (r = gdg_resample_time_device(ctx, chan, (int)per, in.sample_rate, opt->target_rate, row, n_out)) != GDG_OK) return r;
-            }
-        }
-        /* the pinned halves change direction: every upload has been consumed by the DMA engine (events above), nothing else reads them */
-        for (int h = 0; h < 2; h++) if (used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_moved[h]));
-
-        /* the streamed inputs of step i: gathered into a pinned half by the copy threads, moved and decoded on the upload stream while
-         * the block loop is busy with the steps before */
-        int up_used[2] = { 0, 0 };
-        BatchStage stage = [&](size_t i, size_t a, int w, int pool) -> int {      /* pool 1: from the helper thread, with the upload side's copy workers */
-            const int h = (int)(i & 1);
-            if (up_used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_up_ready[h]));     /* step i - 2 has left this half */
-            unsigned char *hb = ctx->h_up[h], *db = d_up + (size_t)h * up_half;
-            gdg_decode_row *rows = reinterpret_cast<gdg_decode_row *>(hb);
-            std::vector<BatchPiece> pieces;
-            size_t cur = up_rows_bytes;
-            int n_rows = 0;
-            unsigned max_count = 0;
-            const size_t span = (size_t)w * B;
-            for (int c = 0; c < N; c++) {
-                if (!streamed[(size_t)c]) continue;
-                const gdg_batch_input &in = inputs[c];
-                if (a >= in.samples_per_channel) continue;                       /* the file ended in an earlier step: zeros */
-                const size_t cnt = std::min(in.samples_per_channel - a, span), width = (size_t)gdg_wave_bytes_per_sample(in.format);
-                rows[n_rows++] = gdg_decode_row{ db + cur, d_inputs + (size_t)c * length + a, (unsigned)cnt, in.format };
-                const unsigned char *src = static_cast<const unsigned char *>(in.bytes) + a * width;
-                for (size_t q = 0; q < cnt * width; q += (size_t)1 << 20)
-                    pieces.push_back({ hb + cur + q, src + q, std::min(cnt * width - q, (size_t)1 << 20) });
-                if (cnt > max_count) max_count = (unsigned)cnt;
-                cur += (cnt * width + 15) & ~(size_t)15;
-            }
-            up_used[h] = 1;
-            if (n_rows) {
-                move_pieces(ctx, pieces, pool);
-                HIP_TRY(ctx, hipMemcpyAsync(db, hb, cur, hipMemcpyHostToDevice, ctx->batch_up_stream));
-                HIP_TRY(ctx, gdg_launch_wave_decode_rows(reinterpret_cast<const gdg_decode_row *>(db), n_rows, max_count, ctx->batch_up_stream));
-            }
-            HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
-            return GDG_OK;
-        };
-        BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, shard, run_metro, n_streamed != 0,
-                        trace, t_begin, 0, 0 };
-        return batch_block_loop(ctx, loop, stage);
-    };
-    rc = body();
-    hipStreamSynchronize(ctx->batch_up_stream);
-    hipStreamSynchronize(ctx->batch_stream);
-    hipStreamSynchronize(ctx->stream);
-    /* the device buffers stay with the context for the next batch (gdg_batch_release) */
-    return rc;
-}
-
 /* ================================================================================================
- * The streamed batch run: the same job in slices of whole blocks.  Every input comes with its step -- decoded (with the channel pick)
- * straight into its row, or into the resampler's source buffer behind the frames kept from the step before -- so the device holds one
- * slice of decoded input and nothing of the job's length.
+ * A batch job runs in slices of whole blocks (the one-call run: in one).  Every input comes with its step -- decoded (with the channel
+ * pick) straight into its row, or into the resampler's source buffer behind the frames kept from the step before -- so the device holds
+ * one slice of decoded input and nothing of the files' length.
  * ============================================================================================== */
 /* GDG_STREAM_CARRY (ctx.h): the source frames kept per resampled input */
-
-/* resample/resample.go:72-87 with 64-bit lengths (gdg_resample_time_length for files of any length) */
-static size_t resample_length64(size_t n, uint32_t source_rate, uint32_t target_rate) {
-    const double expansion = (double)target_rate / (double)source_rate;
-    const double out_len_f = (double)n * expansion, out_len_floor = floor(out_len_f);
-    long long out_len = (long long)out_len_floor;
-    if (out_len_floor == out_len_f) out_len--;
-    return out_len < 0 ? 0 : (size_t)out_len;
-}
 
 int gdg_batch_stream_span(size_t samples_per_channel, uint32_t source_rate, uint32_t target_rate, size_t out_first, size_t out_count,
                           size_t *src_first, size_t *src_count) {
@@ -568,9 +366,18 @@ int gdg_batch_stream_span(size_t samples_per_channel, uint32_t source_rate, uint
     return GDG_OK;
 }
 
-/* `shard`: the job of gdg_batch_run_shard (job_samples, run_metronome) instead of gdg_batch_run's */
+#define SHARD_PORTS " (a shard: its N inputs, its N outputs, metronome, left, right)"
+static int check_meter_ports(gdg_ctx *ctx, const gdg_batch_options *opt, const char *note) {
+    if (opt->run_meters && ctx->n_meter != 2 * ctx->nch + 3)
+        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d%s", ctx->n_meter, 2 * ctx->nch + 3, note);
+    return GDG_OK;
+}
+
+/* The one description of a batch job: inputs and options validated, every input's covered samples, the job's padded length.
+ * `shard`: the job of gdg_batch_run_shard (job_samples, run_metronome) instead of gdg_batch_run's.  `meters_at_open`: a job that stays
+ * open refuses at once what each of its slices would refuse; the one-call run checks its ports itself, behind its empty job's early end. */
 int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
-               bool run_metronome, gdg_ctx::BatchStreamState &S) {
+               bool run_metronome, gdg_ctx::BatchStreamState &S, bool meters_at_open) {
     if (!ctx || !inputs || !opt) return GDG_ERR_INVALID;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is already open on this context");
     if (n_inputs != ctx->nch) return fail(ctx, GDG_ERR_INVALID, "the batch has %d inputs, the context %d channels", n_inputs, ctx->nch);
@@ -578,9 +385,8 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
         return fail(ctx, GDG_ERR_INVALID, "the batch loop runs blocks of %d frames, the context allows %d", GDG_BLOCK_SIZE, ctx->max_frames);
     if (!gdg_wave_bytes_per_sample(opt->out_format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", opt->out_format);
     if (opt->target_rate == 0) return fail(ctx, GDG_ERR_INVALID, "sample rate must be positive");
-    if (opt->run_meters && ctx->n_meter != 2 * n_inputs + 3)
-        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d%s", ctx->n_meter, 2 * n_inputs + 3,
-                    shard ? " (a shard: its N inputs, its N outputs, metronome, left, right)" : "");
+    int rc;
+    if (meters_at_open && (rc = check_meter_ports(ctx, opt, shard ? SHARD_PORTS : "")) != GDG_OK) return rc;
     std::vector<size_t> n_out((size_t)n_inputs, 0);
     size_t max_len = 0;
     for (int i = 0; i < n_inputs; i++) {
@@ -589,10 +395,10 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
         if (!gdg_wave_bytes_per_sample(in.format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "input %d: unknown sample format %d", i, in.format);
         if (in.channels == 0 || in.channel >= in.channels) return fail(ctx, GDG_ERR_INVALID, "input %d: channel %u of %u", i, in.channel, in.channels);
         if (in.sample_rate == 0) return fail(ctx, GDG_ERR_INVALID, "input %d: sample rate must be positive", i);
-        n_out[(size_t)i] = in.sample_rate == opt->target_rate ? in.samples_per_channel : resample_length64(in.samples_per_channel, in.sample_rate, opt->target_rate);
+        n_out[(size_t)i] = input_covers(in, opt->target_rate);
         max_len = std::max(max_len, n_out[(size_t)i]);
     }
-    if (max_len % GDG_BLOCK_SIZE) max_len = GDG_BLOCK_SIZE * (max_len / GDG_BLOCK_SIZE + 1);       /* controller.go:3014-3016 */
+    max_len = whole_blocks(max_len);
     if (shard && job_samples) {                                                  /* the shard pads to the job's length, as gdg_batch_run_shard does */
         if (job_samples < max_len || job_samples % GDG_BLOCK_SIZE)
             return fail(ctx, GDG_ERR_INVALID, "the job's %zu samples: at least this shard's %zu and a multiple of %d", job_samples, max_len, GDG_BLOCK_SIZE);
@@ -672,20 +478,14 @@ int gdg_batch_stream_close(gdg_ctx *ctx) {
     return GDG_OK;
 }
 
-/* one slice; `slice` non-null: of a job opened as a shard (the slice's partial master and metronome buffers) */
-static int stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice, bool as_shard) {
-    if (!ctx) return GDG_ERR_INVALID;
-    int rc = stream_check_blocks(ctx, blocks);
-    if (rc != GDG_OK) return rc;
-    auto &S = ctx->bstream;
-    if (as_shard != S.shard)
-        return fail(ctx, GDG_ERR_INVALID, as_shard ? "gdg_batch_stream_step_shard: the open job is not a shard's (gdg_batch_stream_open): gdg_batch_stream_step runs its slices"
-                                                   : "gdg_batch_stream_step: the open job is a shard's (gdg_batch_stream_open_shard): gdg_batch_stream_step_shard runs its slices");
-    if (!in_bytes || !out_bytes) return fail(ctx, GDG_ERR_INVALID, "a slice needs its input and output buffer lists");
-    if (as_shard && (!slice || !slice->master_left || !slice->master_right)) return fail(ctx, GDG_ERR_INVALID, "a shard needs buffers for its partial master mix");
-    if (as_shard && !S.run_metro && (slice->metronome_bytes || slice->metronome))
-        return fail(ctx, GDG_ERR_INVALID, "this shard's job was opened without the metronome (run_metronome = 0): a slice cannot ask for its track");
-    const bool sharded = as_shard;
+/* The slice runner: the job's samples [S.pos, S.pos + blocks * 8192), which the caller has checked to lie in the job; `slice`: the partial
+ * master and metronome buffers of a shard's job, null for any other.  The job is the caller's (an open one of the context, or the
+ * one-call run's own) and is left as it is: `brought` gets what the caller commits with S.pos once the slice has run.  `begun`: the
+ * slice got as far as the device -- a failure from there on leaves units and meters part-way through it. */
+static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int blocks, const void *const *in_bytes, void *const *out_bytes,
+                     const gdg_batch_shard_out *slice, std::vector<size_t> &brought, bool &begun) {
+    begun = false;
+    const bool sharded = S.shard;
     const gdg_batch_options *opt = &S.opt;
     const int N = ctx->nch, NO = N + 3, B = GDG_BLOCK_SIZE, out_width = gdg_wave_bytes_per_sample(opt->out_format);
     const size_t length = (size_t)blocks * B, pos = S.pos;                       /* the slice: rows of `length` samples, the job's [pos, pos + length) */
@@ -693,8 +493,8 @@ static int stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, vo
     stream_need(S, length, first.data(), count.data());
     for (int i = 0; i < N; i++)
         if (count[(size_t)i] && !in_bytes[i]) return fail(ctx, GDG_ERR_INVALID, "input %d: the slice needs %zu frames from %zu on", i, count[(size_t)i], first[(size_t)i]);
-    if (opt->run_meters && ctx->n_meter != 2 * N + 3)
-        return fail(ctx, GDG_ERR_INVALID, "level meters: %d ports configured, the batch needs 2 N + 3 = %d", ctx->n_meter, 2 * N + 3);
+    int rc = check_meter_ports(ctx, opt, "");
+    if (rc != GDG_OK) return rc;
     enter(ctx);
     const int W = ctx->window;
     const size_t ws = (size_t)W * B;
@@ -734,15 +534,17 @@ static int stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, vo
     if (trace < 0) { const char *e = getenv("GDG_BATCH_TRACE"); trace = e ? atoi(e) : 0; }
     const double t_begin = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
     std::vector<size_t> run(S.brought);                                          /* frames handed over, step by step */
+    begun = true;
     auto body = [&]() -> int {
         int r;
-        if ((r = batch_buffer(ctx, 0, (size_t)N * length * sizeof(double), (void **)&d_inputs)) != GDG_OK) return r;
-        if ((r = batch_buffer(ctx, 1, (size_t)NO * ws * sizeof(double), (void **)&d_win)) != GDG_OK) return r;
-        if ((r = batch_buffer(ctx, 2, 2 * enc_bytes, (void **)&d_enc)) != GDG_OK) return r;
-        /* slot 3, the one-call run's arena: the frames every resampled input keeps for its next step (never grows while a job is open) */
-        if ((r = batch_buffer(ctx, 3, (size_t)N * GDG_STREAM_CARRY * sizeof(double), (void **)&d_carry)) != GDG_OK) return r;
-        if ((r = batch_buffer(ctx, 4, 2 * up_half, (void **)&d_up)) != GDG_OK) return r;
-        if (src_half && (r = batch_buffer(ctx, 5, 2 * src_half, (void **)&d_src)) != GDG_OK) return r;     /* the resampler's source frames, per half */
+        if ((r = batch_buffer(ctx, BATCH_INPUTS, (size_t)N * length * sizeof(double), (void **)&d_inputs)) != GDG_OK) return r;
+        /* one window of the N + 3 outputs, rows in the output files' order (out_0 .. out_{N-1}, master left, master right, metronome,
+         * controller.go:3123-3219); the inputs are read where they lie */
+        if ((r = batch_buffer(ctx, BATCH_WINDOW, (size_t)NO * ws * sizeof(double), (void **)&d_win)) != GDG_OK) return r;
+        if ((r = batch_buffer(ctx, BATCH_ENCODED, 2 * enc_bytes, (void **)&d_enc)) != GDG_OK) return r;
+        if ((r = batch_carry_buffer(ctx, &d_carry)) != GDG_OK) return r;
+        if ((r = batch_buffer(ctx, BATCH_UPLOAD, 2 * up_half, (void **)&d_up)) != GDG_OK) return r;
+        if (src_half && (r = batch_buffer(ctx, BATCH_SOURCE, 2 * src_half, (void **)&d_src)) != GDG_OK) return r;
         /* the zero padding (controller.go:3018-3045): what no step of this slice will write */
         for (int i = 0; i < N; i++) {
             const size_t n_out = S.n_out[(size_t)i];
@@ -809,17 +611,39 @@ static int stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, vo
             HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
             return GDG_OK;
         };
-        BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, sharded ? slice : nullptr,
-                        S.run_metro, any, trace, t_begin, S.length / B, pos / B };
+        BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
+                        S.length / B, pos / B };
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
     hipStreamSynchronize(ctx->batch_up_stream);
     hipStreamSynchronize(ctx->batch_stream);
     hipStreamSynchronize(ctx->stream);
-    if (rc != GDG_OK) { S.open = false; return rc; }                            /* a slice that failed half-way: the job cannot go on */
-    for (int i = 0; i < N; i++) S.brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
-    S.pos += length;
+    /* the device buffers stay with the context for the next slice or job (gdg_batch_release) */
+    brought.resize((size_t)N);
+    for (int i = 0; i < N; i++) brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
+    return rc;
+}
+
+/* one slice of the context's open job; `slice`: of a job opened as a shard (the slice's partial master and metronome buffers) */
+static int stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice, bool as_shard) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = stream_check_blocks(ctx, blocks);
+    if (rc != GDG_OK) return rc;
+    auto &S = ctx->bstream;
+    if (as_shard != S.shard)
+        return fail(ctx, GDG_ERR_INVALID, as_shard ? "gdg_batch_stream_step_shard: the open job is not a shard's (gdg_batch_stream_open): gdg_batch_stream_step runs its slices"
+                                                   : "gdg_batch_stream_step: the open job is a shard's (gdg_batch_stream_open_shard): gdg_batch_stream_step_shard runs its slices");
+    if (!in_bytes || !out_bytes) return fail(ctx, GDG_ERR_INVALID, "a slice needs its input and output buffer lists");
+    if (as_shard && (!slice || !slice->master_left || !slice->master_right)) return fail(ctx, GDG_ERR_INVALID, "a shard needs buffers for its partial master mix");
+    if (as_shard && !S.run_metro && (slice->metronome_bytes || slice->metronome))
+        return fail(ctx, GDG_ERR_INVALID, "this shard's job was opened without the metronome (run_metronome = 0): a slice cannot ask for its track");
+    std::vector<size_t> brought;
+    bool begun = false;
+    rc = run_slice(ctx, S, blocks, in_bytes, out_bytes, as_shard ? slice : nullptr, brought, begun);
+    if (rc != GDG_OK) { if (begun) S.open = false; return rc; }                 /* a slice that failed half-way: the job cannot go on */
+    S.brought = brought;
+    S.pos += (size_t)blocks * GDG_BLOCK_SIZE;
     return GDG_OK;
 }
 
@@ -829,6 +653,33 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
+}
+
+/* The one-call run (controller.processFiles in one call) is the single slice [0, job) of a job that is opened and closed inside the call:
+ * a job of its own, never the context's, which stays closed throughout. */
+static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes,
+                          const gdg_batch_shard_out *shard) {
+    if (!ctx || !inputs || !opt || !out_bytes) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is open on this context: gdg_batch_stream_close it first");
+    /* One shard of a job split over several contexts (SURVEY.md 8e): the master mix is the sum over ALL channels, then the aux input,
+     * then the encoder's clip (spatializer.go:300-310, controller.go:3123-3219) -- so a shard hands out its PARTIAL sums as float64
+     * and gdg_batch_finish_master adds the shards' partials in shard order, then aux, then encodes.  The metronome runs on the shard
+     * that is given somewhere to put it. */
+    if (shard && (!shard->master_left || !shard->master_right)) return fail(ctx, GDG_ERR_INVALID, "a shard needs buffers for its partial master mix");
+    gdg_ctx::BatchStreamState job;
+    int rc = stream_job(ctx, inputs, n_inputs, opt, shard != nullptr, shard ? shard->job_samples : 0, shard && (shard->metronome_bytes || shard->metronome), job,
+                        /*meters_at_open=*/false);
+    if (rc != GDG_OK) return rc;
+    for (int i = 0; i < n_inputs; i++)                                           /* a one-call run holds its inputs' rows whole: gdg_batch_length's bound */
+        if (inputs[i].bytes && inputs[i].samples_per_channel > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "input %d is too long", i);
+    if (job.length == 0) return GDG_OK;                                          /* every output has 0 samples */
+    if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
+    if (job.length > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "files of %zu samples are too long", job.length);
+    std::vector<const void *> in_bytes((size_t)n_inputs);
+    for (int i = 0; i < n_inputs; i++) in_bytes[(size_t)i] = inputs[i].bytes;
+    std::vector<size_t> brought;
+    bool begun = false;
+    return run_slice(ctx, job, (int)(job.length / GDG_BLOCK_SIZE), in_bytes.data(), out_bytes, shard, brought, begun);
 }
 
 int gdg_batch_run(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes) {

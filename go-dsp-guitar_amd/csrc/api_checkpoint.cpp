@@ -173,7 +173,7 @@ int gdg_batch_stream_checkpoint(gdg_ctx *ctx, void *blob, size_t capacity, size_
         if (P.dir.s[SEC_TUNER].bytes) HIP_TRY(ctx, hipMemcpyAsync(stage + P.dir.s[SEC_TUNER].off, &th, sizeof(th), hipMemcpyHostToDevice, ctx->stream));
         /* 2. what the device holds, as more pieces of the state save's one launch */
         Pieces extra;
-        const double *d_carry = ctx->batch_dev_cap[3] >= N * GDG_STREAM_CARRY * sizeof(double) ? static_cast<const double *>(ctx->batch_dev[3]) : nullptr;
+        const double *d_carry = ctx->batch_dev_cap[BATCH_CARRY] >= N * GDG_STREAM_CARRY * sizeof(double) ? static_cast<const double *>(ctx->batch_dev[BATCH_CARRY]) : nullptr;
         for (size_t i = 0; i < N; i++) {
             unsigned char *dst = stage + P.dir.s[SEC_CARRY].off + i * GDG_STREAM_CARRY * sizeof(double);
             const size_t valid = d_carry ? carry_valid(S, i) * sizeof(double) : 0;
@@ -341,7 +341,7 @@ static int resume(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
         memcpy(&m, hb + dir.s[SEC_METRONOME].off, sizeof(m));
         /* 5. everything fits: the buffers the pieces land in, then ONE launch for the channel state and all the rest */
         double *d_carry = nullptr;
-        if ((r = batch_buffer(ctx, 3, N * GDG_STREAM_CARRY * sizeof(double), (void **)&d_carry)) != GDG_OK) return r;
+        if ((r = batch_carry_buffer(ctx, &d_carry)) != GDG_OK) return r;
         if (rings && (r = ensure_tuner(ctx)) != GDG_OK) return r;
         Pieces extra;
         extra.add(stage + dir.s[SEC_CARRY].off, d_carry, N * GDG_STREAM_CARRY * sizeof(double));

@@ -332,17 +332,18 @@ struct gdg_ctx {
     hipStream_t batch_stream = nullptr;
     hipEvent_t batch_ready[2] = { nullptr, nullptr }, batch_moved[2] = { nullptr, nullptr };
     hipEvent_t batch_chunk[2][4] = {};         /* a step's download in four pieces: the scatter into the caller's files starts when the first has landed */
-    /* ... and the streamed upload of the inputs that need no resampling: two more pinned halves, a stream, events */
+    /* ... and the inputs' way up, step by step: two more pinned halves, a stream, events */
     unsigned char *h_up[2] = { nullptr, nullptr };
     size_t h_up_cap = 0;
     hipStream_t batch_up_stream = nullptr;
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
-    /* the batch run's device buffers (inputs, window, encoded steps, arena, upload halves, planar scratch): kept from call to call,
-     * grown when a batch needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
+    /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
+     * grown when a slice needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
     void *batch_dev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     size_t batch_dev_cap[6] = { 0, 0, 0, 0, 0, 0 };
     int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
-    /* the streamed batch run (gdg_batch_stream_open .. _close): the job, how far it has come, and per input the source frames handed over */
+    /* a batch job, how far it has come, and per input the source frames handed over: the context's is the streamed run's
+     * (gdg_batch_stream_open .. _close); a one-call run describes its own and leaves this one closed */
     struct BatchStreamState {
         bool open = false;
         std::vector<gdg_batch_input> inputs;   /* bytes: non-null = the input has samples (never read) */
@@ -608,11 +609,20 @@ struct Pieces {
 int state_save_device_with(gdg_ctx *ctx, void *d_blob, size_t capacity, const Pieces *extra);
 int state_check_device(gdg_ctx *ctx, const void *d_blob, size_t bytes);
 int state_load_device_with(gdg_ctx *ctx, const void *d_blob, size_t bytes, const Pieces *extra);
-/* api_batch.cpp: the job a streamed run would open (validated, nothing of the context touched); the batch run's device buffer `i` */
+/* api_batch.cpp: the job a run describes (validated, nothing of the context touched); the context's BATCH_CARRY buffer */
 int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
-               bool run_metronome, gdg_ctx::BatchStreamState &job);
-int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out);
+               bool run_metronome, gdg_ctx::BatchStreamState &job, bool meters_at_open = true);
+int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
 #define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */
+/* gdg_ctx::batch_dev, slot by slot (the slice runner, api_batch.cpp) */
+enum {
+    BATCH_INPUTS,                          /* [N][slice] decoded (and resampled) inputs */
+    BATCH_WINDOW,                          /* [N + 3][window] one step's outputs */
+    BATCH_ENCODED,                         /* two halves of a step on its way down: encoded rows, a shard's float64 rows */
+    BATCH_CARRY,                           /* [N][GDG_STREAM_CARRY] source frames every resampled input keeps for its next step */
+    BATCH_UPLOAD,                          /* two halves of a step on its way up: descriptors, then the inputs' bytes */
+    BATCH_SOURCE                           /* two halves of the resampler's source frames: [kept | this step's] per resampled input */
+};
 int ensure_tuner(gdg_ctx *ctx);
 
 #pragma GCC visibility pop

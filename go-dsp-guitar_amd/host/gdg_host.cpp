@@ -890,21 +890,17 @@ Error Engine::LoadState(const uint8_t *blob, size_t bytes, uint32_t sampleRate) 
     return "";
 }
 
-Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, void *const *outs, size_t *samples) {
-    if (!inputs || !outs) return "BatchRun: no inputs or no outputs";
-    if (nInputs != nChannels_) return format("BatchRun: %d inputs for %d channels", nInputs, nChannels_);
-    const int G = shards();
-    const int N = nChannels_;
-    setError("");
+/* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
+ * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
+ * controller.go:3005-3045). */
+Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_options &options, int window, size_t *jobSamples) {
     std::vector<std::shared_ptr<signal::Chain>> chains;
     {
         std::lock_guard<std::mutex> lk(mu_);
         chains = chains_;
     }
-    /* 1. per shard: the device follows the chains (units, parameters, filters, layout) as before a Process call; the job's length is
-     *    the longest shard's (the reference pads every channel to the longest input, controller.go:3005-3045) */
     size_t job = 0;
-    for (int g = 0; g < G; g++) {
+    for (int g = 0; g < shards(); g++) {
         int first = 0, count = 0;
         shardRange(g, &first, &count);
         if (count <= 0) continue;
@@ -920,6 +916,19 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
     }
+    *jobSamples = job;
+    return "";
+}
+
+Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, void *const *outs, size_t *samples) {
+    if (!inputs || !outs) return "BatchRun: no inputs or no outputs";
+    if (nInputs != nChannels_) return format("BatchRun: %d inputs for %d channels", nInputs, nChannels_);
+    const int G = shards();
+    const int N = nChannels_;
+    setError("");
+    size_t job = 0;
+    Error prepared = prepareShards(inputs, options, window, &job);
+    if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     if (job == 0) return "";
     /* 2. the shards, concurrently: encoded chain outputs straight into the caller's buffers, partial master mixes as float64 */
@@ -1040,29 +1049,9 @@ Error Engine::BatchStreamShardedOpen(const gdg_batch_input *inputs, int nInputs,
     if (shardedOpen_) { setError("BatchStreamShardedOpen: a streamed batch run is already open on this engine"); return LastError(); }
     const int G = shards();
     setError("");
-    std::vector<std::shared_ptr<signal::Chain>> chains;
-    {
-        std::lock_guard<std::mutex> lk(mu_);
-        chains = chains_;
-    }
-    /* 1. as BatchRun: every shard follows its chains, the job's length is the longest shard's */
-    size_t job = 0;
-    for (int g = 0; g < G; g++) {
-        int first = 0, count = 0;
-        shardRange(g, &first, &count);
-        if (count <= 0) continue;
-        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
-        gdg_ctx *ctx = context(g);
-        if (!ctx) return LastError();
-        std::vector<signal::Chain *> mine;
-        for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
-        Error e = sync(g, mine, options.target_rate);
-        if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
-        size_t len = 0;
-        if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
-        job = std::max(job, len);
-    }
+    size_t job = 0;                                      /* 1. as BatchRun */
+    Error prepared = prepareShards(inputs, options, window, &job);
+    if (!prepared.empty()) return prepared;
     /* 2. every shard's job, padded to that length; shard 0 runs the metronome */
     gdg_batch_options o = options;
     o.metronome_to_master = 0;                           /* the aux input joins the master once per slice, after the shards' sums */
@@ -1269,29 +1258,9 @@ Error Engine::BatchStreamShardedResume(const gdg_batch_input *inputs, int nInput
         at += (size_t)n;
     }
     setError("");
-    std::vector<std::shared_ptr<signal::Chain>> chains;
-    {
-        std::lock_guard<std::mutex> lk(mu_);
-        chains = chains_;
-    }
-    /* as BatchStreamShardedOpen: every shard follows its chains, the job's length is the longest shard's */
-    size_t job = 0;
-    for (int g = 0; g < G; g++) {
-        int first = 0, count = 0;
-        shardRange(g, &first, &count);
-        if (count <= 0) continue;
-        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
-        gdg_ctx *ctx = context(g);
-        if (!ctx) return LastError();
-        std::vector<signal::Chain *> mine;
-        for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
-        Error e = sync(g, mine, options.target_rate);
-        if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
-        size_t len = 0;
-        if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
-        job = std::max(job, len);
-    }
+    size_t job = 0;                                      /* as BatchStreamShardedOpen */
+    Error prepared = prepareShards(inputs, options, window, &job);
+    if (!prepared.empty()) return prepared;
     gdg_batch_options o = options;
     o.metronome_to_master = 0;
     size_t done = 0;

@@ -264,6 +264,7 @@ private:
     void runBatch(std::vector<Pending> batch);
     Error runShard(int shard, std::vector<Pending> &group, int frames, uint32_t sampleRate);
     Error sync(int shard, const std::vector<signal::Chain *> &chains, uint32_t sampleRate);
+    Error prepareShards(const gdg_batch_input *inputs, const gdg_batch_options &options, int window, size_t *jobSamples);   /* chains synced, window set, the job's length */
     int nChannels_, maxFrames_;
     std::vector<std::unique_ptr<Shard>> shards_;
     std::vector<std::shared_ptr<signal::Chain>> chains_;

@@ -190,6 +190,82 @@ def test_sliced_job_has_the_bytes_of_the_one_call_run(oracle, out_fmt, W):
                 assert abs(got["frequency"] - ref["frequency"]) <= 1e-9 * max(1.0, abs(ref["frequency"]))
 
 
+def shard_run_with_encoded_metronome_only(ctx, inputs, rate, out_fmt, job_samples, **kw):
+    """gdg_batch_run_shard with the encoded metronome track asked for and the float64 one not: (outs, left, right, metronome_bytes)"""
+    import ctypes as C
+    pkg = package()
+    n = len(inputs)
+    arr, _keep = ctx._batch_inputs(inputs)
+    fo = pkg.WAVE_FORMATS[out_fmt]
+    wo = pkg_width(out_fmt)
+    opt = pkg.BatchOptions(rate, fo, 0, int(kw.get("run_meters", False)), int(kw.get("tuner_enqueue", False)))
+    outs = [np.zeros(job_samples * wo, dtype=np.uint8) for _ in range(n)]
+    left, right, mb = np.zeros(job_samples), np.zeros(job_samples), np.zeros(job_samples * wo, dtype=np.uint8)
+    ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    so = pkg.BatchShardOut(left.ctypes.data, right.ctypes.data, mb.ctypes.data, None, job_samples)
+    ctx._check(pkg.lib().gdg_batch_run_shard(ctx._h, arr, n, C.byref(opt), ptrs, C.byref(so)))
+    return outs, left, right, mb
+
+
+def test_one_call_runs_between_a_streamed_and_a_shard_job_on_one_context(oracle):
+    """The one-call run is the single slice of a job of its own.  One context, no batch_release in between: a one-call run, the same job
+    streamed in slices [4, 4, 1], a one-call shard run (job_samples one block longer than its files need, only the encoded metronome
+    track asked for) and the one-call run again.  Everything the first and the last run leave -- outputs, meters, tuner, saved state --
+    equals, byte for byte, a fresh context's that did the same four jobs through batch_run / batch_run_shard only: the six device buffers
+    serve all three kinds of run, the one-call run's job never becomes the context's, and a shard's rows fit the room its job sized."""
+    pkg = package()
+    case = batch_case(oracle)
+    rate, nch, inputs, length = case.rate, case.nch, case.inputs, case.length
+    out_fmt, kw = "lpcm24", dict(run_meters=True, tuner_enqueue=True)
+    not_open = "no streamed batch run is open"
+
+    def one_call(ctx):
+        outs = ctx.batch_run(inputs, rate, out_fmt, metronome_to_master=True, **kw)
+        with pytest.raises(pkg.GdgError, match=not_open):        # the job it ran was its own: the context's stayed closed
+            ctx.batch_stream_need(1)
+        return outs, after_job(ctx)
+
+    def sequence(streamed):
+        ctx = case.configured()
+        ctx.set_window(2)
+        first = one_call(ctx)
+        if streamed:
+            parts = []
+            slicing = iter([4, 4, 1])
+            for part in ctx.batch_stream(inputs, rate, out_fmt, lambda left: next(slicing), metronome_to_master=True, **kw):
+                parts.append(part)
+                if len(parts) == 1:                              # a one-call run while the job is open: refused, and the job goes on
+                    for run in (ctx.batch_run, ctx.batch_run_shard):
+                        with pytest.raises(pkg.GdgError, match="a streamed batch run is open on this context: gdg_batch_stream_close it first") as e:
+                            run(inputs, rate, out_fmt)
+                        assert e.value.code == pkg.GDG_ERR_INVALID
+                    assert len(ctx.batch_stream_need(4)) == nch
+            assert [p[0].size for p in parts] == [4 * BLOCK * 3, 4 * BLOCK * 3, BLOCK * 3]
+            second = [np.concatenate([p[r] for p in parts]) for r in range(nch + 3)]
+        else:
+            second = ctx.batch_run(inputs, rate, out_fmt, metronome_to_master=True, **kw)
+        shard = shard_run_with_encoded_metronome_only(ctx, inputs, rate, out_fmt, length + BLOCK, **kw)
+        with pytest.raises(pkg.GdgError, match=not_open):
+            ctx.batch_stream_need(1)
+        last = one_call(ctx)
+        assert ctx.get_option("stat_batch_device_kib") > 0
+        ctx.close()
+        return first, second, shard, last
+
+    got, want = sequence(True), sequence(False)
+    for name, g, w in (("first", got[0], want[0]), ("last", got[3], want[3])):
+        for r in range(nch + 3):
+            assert np.array_equal(g[0][r], w[0][r]), "%s run, output %d" % (name, r)
+        assert g[1][0] == w[1][0] and g[1][1] == w[1][1], "%s run: meters" % name
+        same_tuners(g[1][2], w[1][2])
+        assert g[1][3] == w[1][3], "%s run: saved state" % name
+    for r in range(nch + 3):
+        assert np.array_equal(got[1][r], want[1][r]), "streamed job, output %d" % r
+    for g, w in zip(got[2][0] + list(got[2][1:]), want[2][0] + list(want[2][1:])):
+        assert np.array_equal(g, w), "shard job"
+    assert got[2][3].any()                                       # the encoded metronome track came down
+
+
 @pytest.mark.parametrize("rate", [48000, 44100])
 def test_resampler_across_slices_has_the_bits_of_the_whole_file(oracle, rate):
     """resample.Time alone: every container format as input, rates up and down, files longer than three slices and one shorter than a
