@@ -46,7 +46,13 @@ ABI_SYMBOLS = [
     "gdg_ctx_set_option", "gdg_ctx_get_option", "gdg_option_count", "gdg_option_name", "gdg_numa_probe", "gdg_ctx_trim", "gdg_tuner_replace",
     "gdg_state_size", "gdg_state_save", "gdg_state_save_device", "gdg_state_load", "gdg_state_load_device",
     "gdg_batch_stream_checkpoint_size", "gdg_batch_stream_checkpoint", "gdg_batch_stream_resume", "gdg_batch_stream_resume_shard", "gdg_state_verify",
+    "gdg_block_stats_rows", "gdg_block_stats_rows_device", "gdg_batch_report_enable", "gdg_batch_report",
 ]
+
+# gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
+BLOCK_STATS_DTYPE = np.dtype([("peak", "<f8"), ("sum_sq", "<f8"), ("peak_index", "<u4"), ("clipped", "<u4"), ("full_scale", "<u4"),
+                              ("nonfinite", "<u4")])
+assert BLOCK_STATS_DTYPE.itemsize == 32
 
 
 def option_names():
@@ -235,6 +241,10 @@ def lib():
             "gdg_batch_stream_open_shard": (i32, [vp, vp, i32, vp, C.c_size_t, i32, C.POINTER(C.c_size_t)]),
             "gdg_batch_stream_step_shard": (i32, [vp, i32, vp, vp, vp]),
             "gdg_batch_finish_master_slice": (i32, [vp, i32, vp, vp, i32, vp, C.c_size_t, u32, i32, vp, vp]),
+            "gdg_block_stats_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp]),
+            "gdg_block_stats_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp]),
+            "gdg_batch_report_enable": (i32, [vp, i32]),
+            "gdg_batch_report": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
             "gdg_ctx_get_option": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -969,6 +979,39 @@ class Context:
 
     def batch_release(self):
         self._check(lib().gdg_batch_release(self._h))
+
+    # -- the render report: peak, sum of squares and clip counts per output port and block (gdg_block_stats) ---------------------------------
+    def block_stats(self, rows, block):
+        """rows: a [n_rows][samples] float64 array or a list of equally long 1-D arrays (each row is read where it lies); returns the
+        [n_rows][ceil(samples / block)] records (BLOCK_STATS_DTYPE) of gdg_block_stats_rows."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        if block < 1:
+            raise ValueError("a block has at least one sample")
+        out = np.zeros((n, -(-samples // block)), dtype=BLOCK_STATS_DTYPE)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_stats_rows(self._h, ptrs, n, samples, block, out.ctypes.data if out.size else None))
+        return out
+
+    def block_stats_device(self, d_rows, row_stride, n_rows, samples, block, d_records):
+        """gdg_block_stats_rows_device on plain device pointers (ints), enqueued on the context's stream."""
+        self._check(lib().gdg_block_stats_rows_device(self._h, d_rows, row_stride, n_rows, samples, block, d_records))
+
+    def batch_report_enable(self, enable=True):
+        """From the next batch call on, every batch call keeps the records of what it rendered (configuration: not in a checkpoint)."""
+        self._check(lib().gdg_batch_report_enable(self._h, 1 if enable else 0))
+
+    def batch_report(self):
+        """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_report(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=BLOCK_STATS_DTYPE)
+        self._check(lib().gdg_batch_report(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
 
     def metronome_process(self, frames):
         out = np.empty(frames, dtype=np.float64)

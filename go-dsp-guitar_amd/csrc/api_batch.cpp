@@ -124,6 +124,7 @@ struct BatchLoop {
     int trace;
     double t_begin;
     size_t job_blocks, origin_blocks;           /* the slice of a job of job_blocks blocks that starts at block origin_blocks */
+    bool report;                                /* the render report: a record per output row and block rides behind each step's bytes */
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -181,6 +182,15 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
      * scatter of piece c runs while piece c + 1 is on the bus -- the run's tail (last download, then last scatter) and its head are that
      * much shorter; in between the device sets the pace either way. */
+    /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; with the render report the step's records follow
+     * at the next 16 bytes, [rows][w] -- N + 3 rows, a shard's N chain rows and the metronome's -- and come down with the last piece */
+    auto down_bytes = [&](size_t i) {
+        const size_t wb = (size_t)steps[i].w * B, row_bytes = wb * out_width;
+        return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NO * row_bytes;
+    };
+    const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NO;
+    auto rec_at = [&](size_t i) { return (down_bytes(i) + 15) & ~(size_t)15; };
+    auto rec_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_stats); };
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
     auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
@@ -202,6 +212,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                     memcpy(dst + steps[i].off, src + f64_at + k * wb * sizeof(double), wb * sizeof(double));
                 }
             }, row_bytes);
+        }
+        if (p.report) {                                                      /* the last piece brought the step's records */
+            const gdg_block_stats *rec = reinterpret_cast<const gdg_block_stats *>(src + rec_at(i));
+            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
+            const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;      /* a shard without the metronome: that row stays zero */
+            for (size_t o = 0; o < rows; o++) memcpy(&ctx->report[o * ctx->report_blocks + b0], rec + o * w, w * sizeof(gdg_block_stats));
         }
         return GDG_OK;
     };
@@ -238,6 +254,11 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         {
             ProfScope ps(ctx, GDG_K_WAVE);
             const size_t row_bytes = (size_t)wb * out_width;
+            if (p.report) {                                                  /* the rows as the encoder is about to read them */
+                gdg_block_stats *rec = reinterpret_cast<gdg_block_stats *>(enc + rec_at(i));
+                HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, (unsigned)B, rec, ctx->stream));
+                if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_stats(d_metro, ws, 1u, (size_t)wb, (unsigned)B, rec + (size_t)N * w, ctx->stream));
+            }
             if (!sharded) HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)NO, enc, ctx->stream));
             else {
                 HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)N, enc, ctx->stream));
@@ -259,7 +280,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NO * row_bytes;
+        const size_t down = p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i);
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -489,6 +510,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const gdg_batch_options *opt = &S.opt;
     const int N = ctx->nch, NO = N + 3, B = GDG_BLOCK_SIZE, out_width = gdg_wave_bytes_per_sample(opt->out_format);
     const size_t length = (size_t)blocks * B, pos = S.pos;                       /* the slice: rows of `length` samples, the job's [pos, pos + length) */
+    report_begin(ctx, sharded ? N + 1 : NO, (size_t)blocks);
     std::vector<size_t> first((size_t)N), count((size_t)N);
     stream_need(S, length, first.data(), count.data());
     for (int i = 0; i < N; i++)
@@ -502,7 +524,10 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
      * room for them is the job's (whether the shard runs the metronome): no slice makes a buffer grow */
     const int enc_rows = !sharded ? NO : N + (slice->metronome_bytes ? 1 : 0), f64_rows = !sharded ? 0 : 2 + (slice->metronome ? 1 : 0);
     const int enc_room = !sharded ? NO : N + (S.run_metro ? 1 : 0), f64_room = !sharded ? 0 : 2 + (S.run_metro ? 1 : 0);
-    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double);
+    const bool report = ctx->report_live;
+    /* with the render report a half also holds a window's records behind its rows (batch_block_loop: rec_at) */
+    const size_t rec_room = report ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_stats) : 0;
+    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room;
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -612,7 +637,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             return GDG_OK;
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
-                        S.length / B, pos / B };
+                        S.length / B, pos / B, report };
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -622,7 +647,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* the device buffers stay with the context for the next slice or job (gdg_batch_release) */
     brought.resize((size_t)N);
     for (int i = 0; i < N; i++) brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
-    return rc;
+    return report_end(ctx, rc);
 }
 
 /* one slice of the context's open job; `slice`: of a job opened as a shard (the slice's partial master and metronome buffers) */
@@ -672,7 +697,10 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
     if (rc != GDG_OK) return rc;
     for (int i = 0; i < n_inputs; i++)                                           /* a one-call run holds its inputs' rows whole: gdg_batch_length's bound */
         if (inputs[i].bytes && inputs[i].samples_per_channel > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "input %d is too long", i);
-    if (job.length == 0) return GDG_OK;                                          /* every output has 0 samples */
+    if (job.length == 0) {                                                       /* every output has 0 samples */
+        report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3, 0);
+        return report_end(ctx, GDG_OK);
+    }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
     if (job.length > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "files of %zu samples are too long", job.length);
     std::vector<const void *> in_bytes((size_t)n_inputs);
@@ -706,14 +734,19 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
     if (!width) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", out_format);
     for (int g = 0; g < n_shards; g++) if (!left[g] || !right[g]) return fail(ctx, GDG_ERR_INVALID, "shard %d has no partial master mix", g);
     if (run_meters && (ctx->n_meter < 2 || sample_rate == 0)) return fail(ctx, GDG_ERR_INVALID, "master meters: the context's last two ports, at a positive rate");
-    if (samples == 0) return GDG_OK;
+    report_begin(ctx, 2, (samples + GDG_BLOCK_SIZE - 1) / GDG_BLOCK_SIZE);
+    if (samples == 0) return report_end(ctx, GDG_OK);
     enter(ctx);
     const size_t piece = (size_t)1 << 20;
+    const bool report = ctx->report_live;
+    /* the render report: a piece's records, [2][piece / 8192], behind the encoded rows */
+    const size_t piece_blocks = piece / GDG_BLOCK_SIZE, rec_off = (2 * piece * (size_t)width + 15) & ~(size_t)15;
     int rc = ensure_io(ctx, 1, 3 * piece * sizeof(double));                     /* [left | right | incoming partial or aux] */
-    if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * piece * (size_t)width);
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, report ? rec_off + 2 * piece_blocks * sizeof(gdg_block_stats) : 2 * piece * (size_t)width);
     if (rc != GDG_OK) return rc;
     double *d_l = static_cast<double *>(ctx->d_io[1]), *d_r = d_l + piece, *d_p = d_r + piece;
     unsigned char *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
+    std::vector<gdg_block_stats> rec(report ? 2 * piece_blocks : 0);
     for (size_t at = 0; at < samples; at += piece) {
         const size_t n = std::min(piece, samples - at);
         HIP_TRY(ctx, hipMemcpyAsync(d_l, left[0] + at, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -732,13 +765,21 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
             for (size_t o = 0; o < n; o += GDG_BLOCK_SIZE)                       /* block by block, like the loop that fed the other ports */
                 if ((rc = meter_rows(ctx, d_l + o, piece, ctx->n_meter - 2, 2, (int)std::min((size_t)GDG_BLOCK_SIZE, n - o), sample_rate)) != GDG_OK) return rc;
         }
+        const size_t nb = (n + GDG_BLOCK_SIZE - 1) / GDG_BLOCK_SIZE;             /* d_l and d_r are `piece` apart: two rows, records [2][nb] */
+        if (report) {
+            HIP_TRY(ctx, gdg_launch_block_stats(d_l, piece, 2u, n, GDG_BLOCK_SIZE, d_enc + rec_off, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_enc + rec_off, 2 * nb * sizeof(gdg_block_stats), hipMemcpyDeviceToHost, ctx->stream));
+        }
         HIP_TRY(ctx, gdg_launch_wave_encode(out_format, d_l, n, 1, d_enc, ctx->stream));
         HIP_TRY(ctx, gdg_launch_wave_encode(out_format, d_r, n, 1, d_enc + piece * (size_t)width, ctx->stream));
         if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(static_cast<unsigned char *>(left_bytes) + at * width, d_enc, n * width, hipMemcpyDeviceToHost, ctx->stream));
         if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(static_cast<unsigned char *>(right_bytes) + at * width, d_enc + piece * (size_t)width, n * width, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (report)
+            for (size_t side = 0; side < 2; side++)
+                memcpy(&ctx->report[side * ctx->report_blocks + at / GDG_BLOCK_SIZE], &rec[side * nb], nb * sizeof(gdg_block_stats));
     }
-    return GDG_OK;
+    return report_end(ctx, GDG_OK);
 }
 
 /* gdg_batch_finish_master for one slice of a streamed sharded job, where it runs once per slice on the job's critical path: the same sums
@@ -753,12 +794,16 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
     for (int g = 0; g < n_shards; g++) if (!left[g] || !right[g]) return fail(ctx, GDG_ERR_INVALID, "shard %d has no partial master mix", g);
     if (run_meters && (ctx->n_meter < 2 || sample_rate == 0)) return fail(ctx, GDG_ERR_INVALID, "master meters: the context's last two ports, at a positive rate");
     if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);
-    if (samples == 0) return GDG_OK;
+    report_begin(ctx, 2, samples / GDG_BLOCK_SIZE);
+    if (samples == 0) return report_end(ctx, GDG_OK);
+    const bool report = ctx->report_live;
     enter(ctx);
     const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0), B = GDG_BLOCK_SIZE;
     /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the slice and the shard count */
     const size_t piece = B * std::min((size_t)128, std::max((size_t)1, ((size_t)8 << 20) / ((2 * G + 1) * B * sizeof(double))));
-    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = 2 * piece * (size_t)width;
+    /* the render report: a piece's records, [2][piece / 8192], come down behind its encoded rows */
+    const size_t rec_off = 2 * piece * (size_t)width, rec_bytes = report ? 2 * (piece / B) * sizeof(gdg_block_stats) : 0;
+    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = rec_off + rec_bytes;
     if (!ctx->fin_up[0])
         for (int h = 0; h < 2; h++) {
             HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
@@ -781,7 +826,7 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
     if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * down_bytes);
     if (rc != GDG_OK) return rc;
     unsigned char *d_slab = static_cast<unsigned char *>(ctx->d_io[1]), *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
-    double *d_sums = run_meters ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
+    double *d_sums = (run_meters || report) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
     const size_t n_pieces = (samples + piece - 1) / piece;
     auto span = [&](size_t k) { return std::min(piece, samples - k * piece); };
     auto body = [&]() -> int {
@@ -814,6 +859,10 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
             if (run_meters)
                 for (size_t o = 0; o < n; o += B)                                /* block by block, like the loop that fed the other ports */
                     if ((rc = meter_rows(ctx, d_sums + o, piece, ctx->n_meter - 2, 2, (int)B, sample_rate)) != GDG_OK) return rc;
+            if (report) {                                                    /* the sums: after the aux, before the encoder's clamp */
+                HIP_TRY(ctx, gdg_launch_block_stats(d_sums, piece, 2u, n, (unsigned)B, enc + rec_off, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + rec_off, enc + rec_off, 2 * (n / B) * sizeof(gdg_block_stats), hipMemcpyDeviceToHost, ctx->stream));
+            }
             /* the download of piece k - 2 into this pinned half has been scattered: scatter(k - 2) ran before enqueue(k) */
             if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * (size_t)width, hipMemcpyDeviceToHost, ctx->stream));
             if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + piece * (size_t)width, enc + piece * (size_t)width, n * (size_t)width, hipMemcpyDeviceToHost, ctx->stream));
@@ -832,6 +881,12 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
                 for (size_t q = 0; q < nb; q += (size_t)1 << 18) pieces.push_back({ dst + at + q, src + q, std::min(nb - q, (size_t)1 << 18) });
             }
             move_pieces(ctx, pieces);
+            if (report) {
+                const gdg_block_stats *rec = reinterpret_cast<const gdg_block_stats *>(ctx->h_fin_down[h] + rec_off);
+                const size_t nb = span(k) / B;
+                for (size_t side = 0; side < 2; side++)
+                    memcpy(&ctx->report[side * ctx->report_blocks + k * (piece / B)], rec + side * nb, nb * sizeof(gdg_block_stats));
+            }
             return GDG_OK;
         };
         int r;
@@ -845,5 +900,5 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
     };
     rc = body();
     hipStreamSynchronize(ctx->stream);                                           /* the caller's rows are never read after the call, whatever happened */
-    return rc;
+    return report_end(ctx, rc);
 }

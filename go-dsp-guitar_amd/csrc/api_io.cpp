@@ -386,3 +386,72 @@ int gdg_metronome_process(gdg_ctx *ctx, double *out, int frames) {
 /* ================================================================================================
  * The batch run (controller.processFiles, controller/controller.go:2809-3219, without prompts and file I/O)
  * ============================================================================================== */
+
+/* ---- the render report (include/gdg.h; the kernel: io.hip block_stats_kernel; the batch calls fill it: api_batch.cpp) ------------------ */
+static_assert(sizeof(gdg_block_stats) == 32 && offsetof(gdg_block_stats, peak_index) == 16 && offsetof(gdg_block_stats, nonfinite) == 28,
+              "gdg_block_stats: 32 bytes, no padding");
+static int block_stats_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, size_t *blocks) {
+    if (n_rows < 0) return fail(ctx, GDG_ERR_INVALID, "block statistics: %d rows", n_rows);
+    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block statistics: blocks of %d samples (at least 1)", block);
+    *blocks = (samples + (size_t)block - 1) / (size_t)block;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block statistics: %zu blocks per row are too many for one launch", *blocks);
+    return GDG_OK;
+}
+
+int gdg_block_stats_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, gdg_block_stats *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_stats_check(ctx, n_rows, samples, block, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_rows == 0 || samples == 0) return GDG_OK;
+    if (!d_rows || !d_records) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block statistics: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block statistics: rows and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    HIP_TRY(ctx, gdg_launch_block_stats(d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, d_records, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_block_stats_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, gdg_block_stats *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    int rc = block_stats_check(ctx, n_rows, samples, block, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_rows == 0 || samples == 0) return GDG_OK;
+    if (!rows || !records) return GDG_ERR_INVALID;
+    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block statistics: row %d is NULL", r);
+    enter_keep_fir_sums(ctx);
+    /* the rows go up compact: an odd `samples` puts every other row at 8 bytes past a 16-byte boundary, which the kernel takes as it comes */
+    const size_t rec_bytes = (size_t)n_rows * blocks * sizeof(gdg_block_stats);
+    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, rec_bytes);
+    if (rc != GDG_OK) return rc;
+    double *d_rows = static_cast<double *>(ctx->d_io[1]);
+    for (int r = 0; r < n_rows; r++)
+        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_block_stats_rows_device(ctx, d_rows, samples, n_rows, samples, block, static_cast<gdg_block_stats *>(ctx->d_io[0]));
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(records, ctx->d_io[0], rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_batch_report_enable(gdg_ctx *ctx, int enable) {
+    if (!ctx) return GDG_ERR_INVALID;
+    ctx->report_on = enable != 0;              /* read when a batch call begins; the report of the last call stays what it is */
+    return GDG_OK;
+}
+
+int gdg_batch_report(gdg_ctx *ctx, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (!ctx->report_valid)
+        return fail(ctx, GDG_ERR_INVALID, "no report: the last batch call of this context %s", ctx->report_on ? "has not completed (or none has run since "
+                    "gdg_batch_report_enable)" : "ran without one (gdg_batch_report_enable comes before the call)");
+    if (ports) *ports = ctx->report_ports;
+    if (blocks) *blocks = ctx->report_blocks;
+    if (!records) return GDG_OK;
+    const size_t n = (size_t)ctx->report_ports * ctx->report_blocks;
+    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "report: room for %zu records, the report has %d ports x %zu blocks = %zu", capacity, ctx->report_ports, ctx->report_blocks, n);
+    if (n) memcpy(records, ctx->report.data(), n * sizeof(gdg_block_stats));
+    return GDG_OK;
+}

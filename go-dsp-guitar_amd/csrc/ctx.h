@@ -353,6 +353,12 @@ struct gdg_ctx {
         std::vector<size_t> n_out;             /* samples the input covers in the job: its (resampled) length */
         bool shard = false, run_metro = false; /* opened with gdg_batch_stream_open_shard; ... and this shard runs the job's metronome */
     } bstream;
+    /* the render report (gdg_batch_report_enable): the records of the last completed batch call, [report_ports][report_blocks]; a call
+     * that collects (report_live: the switch as it stood when the call began) fills `report` step by step and validates it at its end */
+    bool report_on = false, report_live = false, report_valid = false;
+    int report_ports = 0;
+    size_t report_blocks = 0;
+    std::vector<gdg_block_stats> report;
     /* gdg_batch_finish_master_slice: the partials of a piece gathered into a pinned slab half, the encoded piece back through another */
     unsigned char *h_fin_up[2] = { nullptr, nullptr }, *h_fin_down[2] = { nullptr, nullptr };
     size_t h_fin_up_cap = 0, h_fin_down_cap = 0;
@@ -613,6 +619,21 @@ int state_load_device_with(gdg_ctx *ctx, const void *d_blob, size_t bytes, const
 int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
                bool run_metronome, gdg_ctx::BatchStreamState &job, bool meters_at_open = true);
 int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
+/* a batch call begins: the report of the call before is gone; with the report enabled, zeroed records for `ports` x `blocks` */
+static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks) {
+    ctx->report_valid = false;
+    ctx->report_live = ctx->report_on;
+    if (!ctx->report_live) return;
+    ctx->report_ports = ports;
+    ctx->report_blocks = blocks;
+    ctx->report.assign((size_t)ports * blocks, gdg_block_stats{ 0.0, 0.0, 0u, 0u, 0u, 0u });
+}
+/* ... and has completed (rc == GDG_OK) or not */
+static inline int report_end(gdg_ctx *ctx, int rc) {
+    ctx->report_valid = ctx->report_live && rc == GDG_OK;
+    ctx->report_live = false;
+    return rc;
+}
 #define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */
 /* gdg_ctx::batch_dev, slot by slot (the slice runner, api_batch.cpp) */
 enum {

@@ -300,6 +300,9 @@ hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride
                                     void *d_right_bytes, double *d_sums, size_t sums_stride, hipStream_t s);
 hipError_t gdg_launch_metronome(const double *d_tick, unsigned n_tick, const double *d_tock, unsigned n_tock, double *d_out, int n,
                                 unsigned sc0, unsigned tc0, unsigned spb, unsigned beats, unsigned j0, hipStream_t s);
+/* the render report (include/gdg.h): one gdg_block_stats per block of `block` samples (the last of a row may be short) of n_rows rows of
+ * `samples` samples, row r at d_rows + r * row_stride (8-byte aligned, row_stride >= samples), into d_records[r][ceil(samples / block)] */
+hipError_t gdg_launch_block_stats(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, void *d_records, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

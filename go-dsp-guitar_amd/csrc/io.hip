@@ -692,7 +692,112 @@ hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride
     return hipGetLastError();
 }
 
-/* resample.Time over a span of a file (the streamed batch run): blockIdx.y = input.  Output samples [out_first, out_first + count) from
+/* ------------------------------------------------------------------------------------------------
+ * The render report (include/gdg.h, gdg_block_stats): peak, sum of squares and three counts per block of a row.  No reference
+ * counterpart.  One workgroup of 256 threads per (block, row): blockIdx.x = block, blockIdx.y = row.
+ *
+ * The order of every operation is a function of the block's length L alone:
+ *   thread t walks the sample pairs p = t, t + 256, t + 512 ... (2 p < L), the samples 2 p and 2 p + 1 of each one after the other, into
+ *   ONE running sum and one running (peak, index) -- indices ascend, so "strictly greater" keeps the first;
+ *   the 64 lanes of a wave meet in the fixed tree lane i <- lane i + 32, + 16 .. + 1; the four wave results through LDS, added 0, 1, 2, 3.
+ * Nothing depends on the row, the grid, where the block lies or who arrives first, and the square and the adds are __dmul_rn / __dadd_rn
+ * (never contracted): the same samples give the same 64 bits wherever they sit and however this file is compiled.  VEC reads a pair with
+ * one 16-byte load where the launcher has seen that every block starts 16-byte aligned and `block` is even; the values and their order
+ * are the scalar path's.  A pair's second sample is read only when it lies inside the block: nothing outside [row, row + samples).
+ * ---------------------------------------------------------------------------------------------- */
+#define STATS_T 256
+struct StatsAcc { double peak, ssq; unsigned idx, clipped, full, nonfin; };
+__device__ __forceinline__ void stats_take(StatsAcc &a, double x, unsigned i) {
+    const double m = fabs(x);
+    if (m <= 1.7976931348623157e308) {                  /* finite: false for NaN and for +-inf */
+        if (m > a.peak) { a.peak = m; a.idx = i; }
+        a.ssq = __dadd_rn(a.ssq, __dmul_rn(x, x));
+        a.clipped += m > 1.0 ? 1u : 0u;
+        a.full += m >= 1.0 ? 1u : 0u;
+    } else a.nonfin++;
+}
+/* the pair (peak, index) in the order "larger peak, then lower index"; sums as (mine + theirs) */
+__device__ __forceinline__ void stats_join(StatsAcc &a, double peak, unsigned idx, double ssq, unsigned clipped, unsigned full, unsigned nonfin) {
+    if (peak > a.peak || (peak == a.peak && idx < a.idx)) { a.peak = peak; a.idx = idx; }
+    a.ssq = __dadd_rn(a.ssq, ssq);
+    a.clipped += clipped;
+    a.full += full;
+    a.nonfin += nonfin;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(STATS_T)
+block_stats_kernel(const double *__restrict__ rows, size_t row_stride, size_t samples, unsigned block, unsigned row0, unsigned blocks_per_row,
+                   gdg_block_stats *__restrict__ records) {
+    __shared__ double s_peak[STATS_T / 64], s_ssq[STATS_T / 64];
+    __shared__ unsigned s_idx[STATS_T / 64], s_cnt[STATS_T / 64][3];
+    const unsigned tid = threadIdx.x, lane = tid & 63u, row = row0 + blockIdx.y;
+    const size_t first = (size_t)blockIdx.x * block;
+    const unsigned L = (unsigned)(samples - first < (size_t)block ? samples - first : (size_t)block);
+    const double *x = rows + (size_t)row * row_stride + first;
+    StatsAcc a = { 0.0, 0.0, 0u, 0u, 0u, 0u };
+    /* four pairs per round, their loads in flight together; the sums follow in the pairs' order */
+    for (unsigned p0 = tid; 2u * p0 < L; p0 += 4u * STATS_T) {
+        double v[4][2];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned i = 2u * (p0 + (unsigned)k * STATS_T);
+            v[k][0] = v[k][1] = 0.0;
+            if (VEC && i + 1u < L) {
+                const v2d q = *reinterpret_cast<const v2d *>(x + i);
+                v[k][0] = q.x;
+                v[k][1] = q.y;
+            } else {
+                if (i < L) v[k][0] = x[i];
+                if (i + 1u < L) v[k][1] = x[i + 1u];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned i = 2u * (p0 + (unsigned)k * STATS_T);
+            if (i < L) stats_take(a, v[k][0], i);
+            if (i + 1u < L) stats_take(a, v[k][1], i + 1u);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        stats_join(a, __shfl_down(a.peak, o), __shfl_down(a.idx, o), __shfl_down(a.ssq, o), __shfl_down(a.clipped, o), __shfl_down(a.full, o),
+                   __shfl_down(a.nonfin, o));
+    if (lane == 0) {
+        const unsigned w = tid >> 6;
+        s_peak[w] = a.peak; s_ssq[w] = a.ssq; s_idx[w] = a.idx;
+        s_cnt[w][0] = a.clipped; s_cnt[w][1] = a.full; s_cnt[w][2] = a.nonfin;
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < STATS_T / 64; w++) stats_join(a, s_peak[w], s_idx[w], s_ssq[w], s_cnt[w][0], s_cnt[w][1], s_cnt[w][2]);
+        gdg_block_stats *r = records + (size_t)row * blocks_per_row + blockIdx.x;
+        r->peak = a.peak;
+        r->sum_sq = a.ssq;
+        r->peak_index = a.idx;
+        r->clipped = a.clipped;
+        r->full_scale = a.full;
+        r->nonfinite = a.nonfin;
+    }
+}
+
+hipError_t gdg_launch_block_stats(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, void *d_out, hipStream_t s) {
+    gdg_block_stats *d_records = static_cast<gdg_block_stats *>(d_out);
+    if (n_rows == 0 || samples == 0) return hipSuccess;
+    if (block == 0) return hipErrorInvalidValue;
+    const size_t blocks = (samples + block - 1) / block;
+    if (row_stride < samples || blocks > 0x7fffffffu || ((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return hipErrorInvalidValue;
+    const bool vec = !((uintptr_t)d_rows & 15) && !(row_stride & 1) && !(block & 1);
+    for (unsigned r0 = 0; r0 < n_rows; r0 += 65535u) {                      /* gridDim.y holds 65535 rows */
+        const dim3 grid((unsigned)blocks, n_rows - r0 < 65535u ? n_rows - r0 : 65535u);
+        if (vec) block_stats_kernel<true><<<grid, STATS_T, 0, s>>>(d_rows, row_stride, samples, block, r0, (unsigned)blocks, d_records);
+        else block_stats_kernel<false><<<grid, STATS_T, 0, s>>>(d_rows, row_stride, samples, block, r0, (unsigned)blocks, d_records);
+    }
+    return hipGetLastError();
+}
+
+/* resample.Time over a span of a file (the streamed batch run): blockIdx.y = input. Output samples [out_first, out_first + count) from
  * the source frames [src_first, src_first + src_count) at `src`; n = the FILE's frames (the j < n bound).  x, floor(x) and x - j are
  * formed from the absolute 64-bit i and j in the operation order of resample_time_kernel, so every sample has the whole-file kernel's
  * bits (both kernels are compiled without contraction).  The host sizes the span so that every j in [0, n) a sample reads lies inside

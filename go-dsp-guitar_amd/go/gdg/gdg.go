@@ -1175,3 +1175,122 @@ func (this *Context) finishMaster(slice bool, outFormat int, shards []*ShardResu
 	}
 	return goBytes(lb, samples*width), goBytes(rb, samples*width), nil
 }
+
+// BlockStats is one record of the render report (gdg_block_stats): what one block of one output port held just before the encoder
+// read it.  Peak: max |x| over the finite samples; SumSq: the sum of their squares, added in an order that depends on the block's
+// length alone; PeakIndex: the first index with |x| == Peak; Clipped: |x| > 1 (the samples the encoder's clamp changes); FullScale:
+// |x| >= 1; Nonfinite: NaN and +-Inf, counted and left out of the rest.
+type BlockStats struct {
+	Peak      float64
+	SumSq     float64
+	PeakIndex uint32
+	Clipped   uint32
+	FullScale uint32
+	Nonfinite uint32
+}
+
+func goBlockStats(p unsafe.Pointer, rows int, blocks int) [][]BlockStats {
+	out := make([][]BlockStats, rows)
+	if rows*blocks == 0 {
+		for r := range out {
+			out[r] = []BlockStats{}
+		}
+		return out
+	}
+	recs := (*[1 << 26]C.gdg_block_stats)(p)[: rows*blocks : rows*blocks]
+	for r := range out {
+		out[r] = make([]BlockStats, blocks)
+		for b := range out[r] {
+			c := recs[r*blocks+b]
+			out[r][b] = BlockStats{float64(c.peak), float64(c.sum_sq), uint32(c.peak_index), uint32(c.clipped), uint32(c.full_scale), uint32(c.nonfinite)}
+		}
+	}
+	return out
+}
+
+// BlockStatsRows: the records of equally long host rows cut into blocks of `block` samples, the last one of a row possibly short
+// (gdg_block_stats_rows); result[row][block].
+func (this *Context) BlockStatsRows(rows [][]float64, block int) ([][]BlockStats, error) {
+	n := len(rows)
+	if n == 0 {
+		return [][]BlockStats{}, nil
+	}
+	if block < 1 {
+		return nil, fmt.Errorf("gdg: a block has at least one sample")
+	}
+	samples := len(rows[0])
+	blocks := (samples + block - 1) / block
+	if samples == 0 {
+		return goBlockStats(nil, n, 0), nil
+	}
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples * 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	rec := C.calloc(C.size_t(n*blocks), 32)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, rec)
+	if e := this.err(C.gdg_block_stats_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(block), (*C.gdg_block_stats)(rec))); e != nil {
+		return nil, e
+	}
+	return goBlockStats(rec, n, blocks), nil
+}
+
+// BlockStatsRowsDevice: the same on device memory, enqueued on the context's stream (gdg_block_stats_rows_device): row r at
+// dRows + r*rowStride float64 (any 8-byte alignment, rowStride >= samples), the records into dRecords[nRows][ceil(samples/block)].
+func (this *Context) BlockStatsRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, block int, dRecords unsafe.Pointer) error {
+	return this.err(C.gdg_block_stats_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(block),
+		(*C.gdg_block_stats)(dRecords)))
+}
+
+// BatchReportEnable: from the next batch call on, every batch call of the context keeps the records of what it rendered, per output
+// port and block of 8192 samples (gdg_batch_report_enable).  Configuration, like the window: a checkpoint does not carry it -- set it
+// again on the target of a resume.
+func (this *Context) BatchReportEnable(enable bool) error {
+	return this.err(C.gdg_batch_report_enable(this.ctx, cbool(enable)))
+}
+
+// BatchReport: the records of the last completed batch call, result[port][block] (gdg_batch_report).  BatchRun and BatchStreamStep
+// report the N chain outputs, master left, master right and the metronome; a shard's calls its n chain outputs and the metronome;
+// FinishMaster and FinishMasterSlice master left and right.  An error when the call ran without the report enabled.
+func (this *Context) BatchReport() ([][]BlockStats, error) {
+	var ports C.int
+	var blocks C.size_t
+	if e := this.err(C.gdg_batch_report(this.ctx, nil, 0, &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	n := int(ports) * int(blocks)
+	if n == 0 {
+		return goBlockStats(nil, int(ports), int(blocks)), nil
+	}
+	rec := C.calloc(C.size_t(n), 32)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	if e := this.err(C.gdg_batch_report(this.ctx, (*C.gdg_block_stats)(rec), C.size_t(n), &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	return goBlockStats(rec, int(ports), int(blocks)), nil
+}

@@ -45,6 +45,8 @@ def lib():
             "gdgh_engine_batch_stream_sharded_open": (cs, [vp, vp, i32, vp, i32, C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_need": (cs, [vp, i32, vp, vp]), "gdgh_engine_batch_stream_sharded_step": (cs, [vp, i32, vp, vp]),
             "gdgh_engine_batch_stream_sharded_close": (cs, [vp]),
+            "gdgh_engine_set_batch_report": (None, [vp, i32]),
+            "gdgh_engine_last_batch_report": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
             "gdgh_engine_save_state": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -110,6 +112,7 @@ class Engine:
             self._h = lib().gdgh_engine_create_sharded(n_channels, max_frames, arr, len(devices))
         self.n_channels = n_channels
         self.chains = []
+        self.last_report = None          # the render report of the last batch call made with report=True: [N + 3, blocks] records
 
     def shards(self):
         return lib().gdgh_engine_shards(self._h)
@@ -182,10 +185,24 @@ class Engine:
         ctx.close = lambda: None                      # the engine owns the context
         return ctx
 
-    def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
-        """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections."""
+    def _fetch_report(self):
+        """Engine::LastBatchReport -> [N + 3, blocks] records (the package's BLOCK_STATS_DTYPE)"""
         import __graft_entry__ as entry
         pkg = entry.load_package()
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_report(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=pkg.BLOCK_STATS_DTYPE)
+        _err(lib().gdgh_engine_last_batch_report(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
+    def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
+                  report=False):
+        """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
+        render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count)."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
+        self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
         keep = []
@@ -213,30 +230,38 @@ class Engine:
         samples = C.c_size_t(0)
         _err(lib().gdgh_engine_batch_run(self._h, arr, n, C.byref(opt), window, ptrs, C.byref(samples)))
         assert samples.value == length
+        if report:
+            self.last_report = self._fetch_report()
         return outs
 
-    def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False):
+    def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
+                     report=False):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
-        yields every slice's N + 3 output pieces."""
+        yields every slice's N + 3 output pieces.  report: last_report grows by every slice's records and is the whole job's,
+        [N + 3, blocks], when the generator ends."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue)
+                                  metronome_to_master, run_meters, tuner_enqueue, report)
 
     def batch_stream_sharded(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False,
-                             tuner_enqueue=False):
+                             tuner_enqueue=False, report=False):
         """Engine::BatchStreamShardedOpen / Need / Step / Close: batch_stream for an engine of any shard count -- every shard streams its
         channels, the master is finished per slice; yields every slice's N + 3 output pieces (blocks_per_slice: an int or a function
-        (blocks_left) -> blocks)."""
+        (blocks_left) -> blocks).  report: as batch_stream's -- the chain rows come from the shards, the master from the finish, the
+        metronome from shard 0."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
                                    L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
-                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue)
+                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report)
 
-    def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue):
+    def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
+                      report=False):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
+        lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
+        self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
         datas, widths = [None] * n, [0] * n
@@ -264,6 +289,9 @@ class Engine:
                 outs = [np.zeros(blocks * 8192 * wo, dtype=np.uint8) for _ in range(n + 3)]
                 ptrs = (C.c_void_p * (n + 3))(*[o.ctypes.data for o in outs])
                 _err(f_step(self._h, blocks, ins, ptrs))
+                if report:
+                    rec = self._fetch_report()
+                    self.last_report = rec if self.last_report is None else np.concatenate([self.last_report, rec], axis=1)
                 yield outs
                 left -= blocks
         finally:

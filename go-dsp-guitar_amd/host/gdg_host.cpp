@@ -911,7 +911,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -930,7 +930,8 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     Error prepared = prepareShards(inputs, options, window, &job);
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
-    if (job == 0) return "";
+    reportBegin(job / 8192);
+    if (job == 0) { reportValid_ = report_; return ""; }
     /* 2. the shards, concurrently: encoded chain outputs straight into the caller's buffers, partial master mixes as float64 */
     std::vector<std::vector<double>> left((size_t)G), right((size_t)G);
     std::vector<double> metronome(job, 0.0);
@@ -952,6 +953,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
         gdg_batch_options o = options;
         o.metronome_to_master = 0;                       /* the aux input joins the master once, after the shards' sums */
         if (gdg_batch_run_shard(ctx, inputs + first, count, &o, outs + first, &so) != GDG_OK) errs[(size_t)g] = gdg_last_error(ctx);
+        else errs[(size_t)g] = reportOfShard(g, ctx);      /* before the finish below puts the master's report on shard 0's context */
     };
     {
         std::vector<std::thread> workers;
@@ -970,6 +972,50 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
         setError(gdg_last_error(ctx0));
         return LastError();
     }
+    Error re = reportOfMaster(ctx0);
+    if (!re.empty()) { setError(re); return LastError(); }
+    return "";
+}
+
+/* ---- the render report of the last batch call, [N + 3][blocks] in gdg_batch_run's port order, from three sources ---- */
+void Engine::reportBegin(size_t blocks) {
+    reportValid_ = false;
+    reportBlocks_ = blocks;
+    if (report_) lastReport_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_stats{ 0.0, 0.0, 0u, 0u, 0u, 0u });
+}
+
+/* shard g's report (its n chain outputs, then the metronome): the chain rows to the shard's channels, shard 0's last row to the metronome's */
+Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
+    if (!report_) return "";
+    int first = 0, count = 0, ports = 0;
+    size_t blocks = 0;
+    shardRange(g, &first, &count);
+    std::vector<gdg_block_stats> rec((size_t)(count + 1) * reportBlocks_);
+    if (gdg_batch_report(ctx, rec.data(), rec.size(), &ports, &blocks) != GDG_OK) return gdg_last_error(ctx);
+    if (ports != count + 1 || blocks != reportBlocks_) return format("a report of %d ports x %zu blocks where %d x %zu were expected", ports, blocks, count + 1, reportBlocks_);
+    if (blocks) memcpy(&lastReport_[(size_t)first * blocks], rec.data(), (size_t)count * blocks * sizeof(gdg_block_stats));
+    if (g == 0 && blocks) memcpy(&lastReport_[(size_t)(nChannels_ + 2) * blocks], &rec[(size_t)count * blocks], blocks * sizeof(gdg_block_stats));
+    return "";
+}
+
+/* the finish's report (master left, master right) completes the call's */
+Error Engine::reportOfMaster(gdg_ctx *ctx) {
+    if (!report_) return "";
+    int ports = 0;
+    size_t blocks = 0;
+    std::vector<gdg_block_stats> rec(2 * reportBlocks_);
+    if (gdg_batch_report(ctx, rec.data(), rec.size(), &ports, &blocks) != GDG_OK) return gdg_last_error(ctx);
+    if (ports != 2 || blocks != reportBlocks_) return format("a master report of %d ports x %zu blocks where 2 x %zu were expected", ports, blocks, reportBlocks_);
+    if (blocks) memcpy(&lastReport_[(size_t)nChannels_ * blocks], rec.data(), 2 * blocks * sizeof(gdg_block_stats));
+    reportValid_ = true;
+    return "";
+}
+
+Error Engine::LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const {
+    if (!reportValid_) return "LastBatchReport: the last batch call kept no report (SetBatchReport comes before the call)";
+    records = lastReport_;
+    if (ports) *ports = nChannels_ + 3;
+    if (blocks) *blocks = reportBlocks_;
     return "";
 }
 
@@ -997,7 +1043,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1020,7 +1066,14 @@ Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *o
     std::lock_guard<std::mutex> lk(shards_[0]->mu);
     gdg_ctx *ctx = shards_[0]->ctx;
     if (!ctx) return "BatchStreamStep: no streamed batch run is open";
+    reportBegin(blocks > 0 ? (size_t)blocks : 0);
     if (gdg_batch_stream_step(ctx, blocks, ins, outs) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+    if (report_) {                                       /* one shard, the plain run: the context's report is the engine's */
+        int ports = 0;
+        size_t nb = 0;
+        if (gdg_batch_report(ctx, lastReport_.data(), lastReport_.size(), &ports, &nb) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        reportValid_ = true;
+    }
     return "";
 }
 
@@ -1103,6 +1156,7 @@ Error Engine::BatchStreamShardedStep(int blocks, const void *const *ins, void *c
     const int G = shards(), N = nChannels_;
     const gdg_batch_options &options = shardedOptions_;
     const size_t n = (size_t)blocks * 8192;
+    reportBegin((size_t)blocks);
     /* the shards' slices, concurrently: encoded chain outputs straight into the caller's pieces, partial master mixes as float64 */
     std::vector<std::vector<double>> left((size_t)G), right((size_t)G);
     std::vector<double> metronome(n, 0.0);
@@ -1121,6 +1175,7 @@ Error Engine::BatchStreamShardedStep(int blocks, const void *const *ins, void *c
         so.master_right = right[(size_t)g].data();
         if (g == 0) { so.metronome_bytes = outs[N + 2]; so.metronome = metronome.data(); }
         if (gdg_batch_stream_step_shard(ctx, blocks, ins + first, outs + first, &so) != GDG_OK) errs[(size_t)g] = gdg_last_error(ctx);
+        else errs[(size_t)g] = reportOfShard(g, ctx);
     };
     {
         std::vector<std::thread> workers;
@@ -1144,6 +1199,7 @@ Error Engine::BatchStreamShardedStep(int blocks, const void *const *ins, void *c
         if (gdg_batch_finish_master_slice(ctx0, options.out_format, lp.data(), rp.data(), (int)lp.size(), options.metronome_to_master ? metronome.data() : nullptr, n,
                                           options.target_rate, options.run_meters, outs[N], outs[N + 1]) != GDG_OK)
             e = gdg_last_error(ctx0);
+        else e = reportOfMaster(ctx0);
     }
     if (!e.empty()) { closeSharded(); setError(e); return LastError(); }
     shardedSlices_++;
@@ -1196,7 +1252,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1497,6 +1553,22 @@ const char *gdgh_engine_process_all(void *e, const double *const *in, double *co
 
 const char *gdgh_engine_batch_run(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, void *const *outs, size_t *samples) {
     return ret(((Engine *)e)->BatchRun(inputs, n, *opt, window, outs, samples));
+}
+void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchReport(on != 0); }
+/* records == NULL: the two counts only */
+const char *gdgh_engine_last_batch_report(void *e, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks) {
+    std::vector<gdg_block_stats> rec;
+    int p = 0;
+    size_t b = 0;
+    Error err = ((Engine *)e)->LastBatchReport(rec, &p, &b);
+    if (!err.empty()) return ret(err);
+    if (ports) *ports = p;
+    if (blocks) *blocks = b;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchReport: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_stats));
+    }
+    return ret(Error(""));
 }
 const char *gdgh_engine_batch_stream_open(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, size_t *samples) {
     return ret(((Engine *)e)->BatchStreamOpen(inputs, n, *opt, window, samples));

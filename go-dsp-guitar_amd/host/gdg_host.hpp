@@ -239,6 +239,13 @@ public:
     Error BatchStreamShardedCheckpoint(std::vector<uint8_t> &blob);
     Error BatchStreamShardedResume(const gdg_batch_input *inputs, int nInputs, const gdg_batch_options &options, int window, const uint8_t *blob,
                                    size_t bytes, size_t *samplesDone, uint64_t *slicesDone = nullptr);
+    /* No reference counterpart.  The render report (include/gdg.h, gdg_block_stats): with SetBatchReport(true), BatchRun and every
+     * BatchStreamStep / BatchStreamShardedStep keep the records of what the call rendered, [N + 3][blocks] in gdg_batch_run's port order
+     * (the N chain outputs, master left, master right, metronome) whatever the shard count: the chain rows come from the shards'
+     * reports, put side by side by channel, the master from the finish, the metronome from the shard that ran it.  The switch is read
+     * when a job is set up (BatchRun, the Open and Resume calls); it is not part of a checkpoint. */
+    void SetBatchReport(bool on) { report_ = on; }
+    Error LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const;
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -278,6 +285,12 @@ private:
     gdg_batch_options shardedOptions_ = {};
     uint64_t shardedSlices_ = 0;                           /* ... and this many slices done (a checkpoint's wrapper records it) */
     void closeSharded();
+    bool report_ = false, reportValid_ = false;            /* the render report: asked for; the last call's is complete */
+    size_t reportBlocks_ = 0;
+    std::vector<gdg_block_stats> lastReport_;
+    void reportBegin(size_t blocks);
+    Error reportOfShard(int shard, gdg_ctx *ctx);
+    Error reportOfMaster(gdg_ctx *ctx);
     mutable std::mutex errMu_;
     std::string lastError_;
 };

@@ -689,6 +689,55 @@ int gdg_state_verify(gdg_ctx *ctx, const void *blob, size_t bytes);
 /* The device buffers of a batch run (the decoded inputs are the large part: N x length x 8 bytes) stay with the context for the next
  * run of the same or a smaller size; this frees them. */
 int gdg_batch_release(gdg_ctx *ctx);
+/*
+ * RENDER REPORT: no reference counterpart.  What a batch call rendered, per output port and per block of 8192 samples, taken on the
+ * device from the float64 rows just before the encoder reads them (filter.Process clamps every power amp to +-1 and the encoder clamps
+ * again before it quantises; neither says so).  One record per (port, block):
+ */
+typedef struct {
+    double   peak;        /* max |x| over the block's finite samples; 0 when there is none */
+    double   sum_sq;      /* sum of x*x over the block's finite samples */
+    uint32_t peak_index;  /* first index inside the block with |x| == peak; 0 when peak == 0 */
+    uint32_t clipped;     /* samples with |x| > 1: the ones the encoder's clamp changes */
+    uint32_t full_scale;  /* samples with |x| >= 1 (a power amp's clamp leaves exactly +-1) */
+    uint32_t nonfinite;   /* NaN, +inf, -inf: counted, and left out of the four fields above */
+} gdg_block_stats;        /* 32 bytes, little-endian, no padding */
+/*
+ * The statistics of a block are stateless.  sum_sq is added in an order that depends on the block's LENGTH and on nothing else -- not on
+ * the row, the row count, the block's place in the buffer, the window, the slicing or the sharding -- with every square and every add
+ * rounded on its own (no fused multiply-add): the same samples give the same 64 bits wherever they sit.  A tie on the peak goes to the
+ * lower index.
+ *   gdg_block_stats_rows(ctx, rows, n_rows, samples, block, records)   n_rows host rows of `samples` float64 each, cut into blocks of
+ *                                                                      `block` >= 1 samples (the last one of a row may be short);
+ *                                                                      records: [n_rows][ceil(samples / block)], row-major
+ *   gdg_block_stats_rows_device(ctx, d_rows, row_stride, n_rows, samples, block, d_records)
+ *                                                                      the same on device memory, enqueued on gdg_ctx_stream: row r
+ *                                                                      at d_rows + r * row_stride (row_stride >= samples, any 8-byte
+ *                                                                      alignment); no sample outside [row, row + samples) is read
+ *   gdg_batch_report_enable(ctx, enable)                               from the next batch call on, every batch call of the context
+ *                                                                      keeps the records of what it rendered (blocks of 8192).
+ *                                                                      Configuration, like the window: not part of a checkpoint
+ *                                                                      (the container stays version 1) -- set it again on the target
+ *                                                                      of a resume.  Off (the default): no launch, allocation or
+ *                                                                      byte differs from a context that never heard of it
+ *   gdg_batch_report(ctx, records, capacity, &ports, &blocks)          the records of the LAST COMPLETED batch call of the context,
+ *                                                                      [ports][blocks] row-major; records == NULL: the two counts
+ *                                                                      only.  GDG_ERR_INVALID (gdg_last_error says which) when
+ *                                                                      capacity < ports * blocks, or when there is no report: none
+ *                                                                      was enabled before the call ran, or no call has completed
+ * Ports, in this order:
+ *   gdg_batch_run, gdg_batch_stream_step                   the N chain outputs, master left, master right, metronome -- the order of
+ *                                                          out_bytes, the master after the aux add; a NULL in out_bytes changes nothing
+ *   gdg_batch_run_shard, gdg_batch_stream_step_shard       the n chain outputs, then the metronome (all-zero records on a shard that
+ *                                                          does not run it); the partial master is not a port
+ *   gdg_batch_finish_master, gdg_batch_finish_master_slice master left, master right: the sums after the aux add, before the clamp
+ * The records come down with each step's own download; a slice's report covers the slice's blocks.
+ */
+int gdg_block_stats_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, gdg_block_stats *records);
+int gdg_block_stats_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block,
+                                gdg_block_stats *d_records);
+int gdg_batch_report_enable(gdg_ctx *ctx, int enable);
+int gdg_batch_report(gdg_ctx *ctx, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks);
 
 #ifdef __cplusplus
 
