@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "gdg_ctx_set_option", "gdg_ctx_get_option", "gdg_option_count", "gdg_option_name", "gdg_numa_probe", "gdg_ctx_trim", "gdg_tuner_replace",
     "gdg_state_size", "gdg_state_save", "gdg_state_save_device", "gdg_state_load", "gdg_state_load_device",
     "gdg_batch_stream_checkpoint_size", "gdg_batch_stream_checkpoint", "gdg_batch_stream_resume", "gdg_batch_stream_resume_shard", "gdg_state_verify",
-    "gdg_block_stats_rows", "gdg_block_stats_rows_device", "gdg_batch_report_enable", "gdg_batch_report",
+    "gdg_block_stats_rows", "gdg_block_stats_rows_device", "gdg_batch_report_enable", "gdg_batch_report", "gdg_batch_set_sources",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -244,6 +244,7 @@ def lib():
             "gdg_block_stats_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp]),
             "gdg_block_stats_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp]),
             "gdg_batch_report_enable": (i32, [vp, i32]),
+            "gdg_batch_set_sources": (i32, [vp, vp, i32]),
             "gdg_batch_report": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
@@ -1004,6 +1005,15 @@ class Context:
     def batch_report_enable(self, enable=True):
         """From the next batch call on, every batch call keeps the records of what it rendered (configuration: not in a checkpoint)."""
         self._check(lib().gdg_batch_report_enable(self._h, 1 if enable else 0))
+
+    def batch_set_sources(self, source):
+        """The source map of the next batch calls (gdg_batch_set_sources): source[c] = the channel whose input entry channel c reads, a list of
+        n_channels ints; None (or an empty list) clears it.  A reader's entry in `inputs` may be None; configuration: not in a checkpoint."""
+        if source is None or len(source) == 0:
+            self._check(lib().gdg_batch_set_sources(self._h, None, 0))
+            return
+        arr = (C.c_int * len(source))(*[int(v) for v in source])
+        self._check(lib().gdg_batch_set_sources(self._h, arr, len(source)))
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

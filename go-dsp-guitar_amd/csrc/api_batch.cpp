@@ -387,6 +387,24 @@ int gdg_batch_stream_span(size_t samples_per_channel, uint32_t source_rate, uint
     return GDG_OK;
 }
 
+/* the source map: validated whole before it replaces the one in force (batch_sources.h); read when a job is described */
+int gdg_batch_set_sources(gdg_ctx *ctx, const int *source, int n) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set sources: a streamed batch run is open on this context; its map holds until gdg_batch_stream_close");
+    if (!source || n == 0) { ctx->batch_source.clear(); return GDG_OK; }
+    int bad = -1;
+    switch (sources_check(source, n, ctx->nch, &bad)) {
+    case SOURCES_OK: break;
+    case SOURCES_WRONG_N: return fail(ctx, GDG_ERR_INVALID, "set sources: a map of %d entries, the context has %d channels", n, ctx->nch);
+    case SOURCES_OUT_OF_RANGE: return fail(ctx, GDG_ERR_INVALID, "set sources: channel %d reads channel %d, the context has channels 0 to %d", bad, source[bad], ctx->nch - 1);
+    default:
+        return fail(ctx, GDG_ERR_INVALID, "set sources: channel %d reads channel %d, which itself reads channel %d: a reader's source must read its own input",
+                    bad, source[bad], source[source[bad]]);
+    }
+    ctx->batch_source.assign(source, source + n);
+    return GDG_OK;
+}
+
 #define SHARD_PORTS " (a shard: its N inputs, its N outputs, metronome, left, right)"
 static int check_meter_ports(gdg_ctx *ctx, const gdg_batch_options *opt, const char *note) {
     if (opt->run_meters && ctx->n_meter != 2 * ctx->nch + 3)
@@ -410,8 +428,11 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
     if (meters_at_open && (rc = check_meter_ports(ctx, opt, shard ? SHARD_PORTS : "")) != GDG_OK) return rc;
     std::vector<size_t> n_out((size_t)n_inputs, 0);
     size_t max_len = 0;
+    /* a source map with a reader (gdg_batch_set_sources): only the roots' entries are looked at, and the job's length is theirs */
+    const bool shared = batch_sources_shared(ctx);
     for (int i = 0; i < n_inputs; i++) {
         const gdg_batch_input &in = inputs[i];
+        if (shared && ctx->batch_source[(size_t)i] != i) continue;
         if (!in.bytes || !in.samples_per_channel) continue;
         if (!gdg_wave_bytes_per_sample(in.format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "input %d: unknown sample format %d", i, in.format);
         if (in.channels == 0 || in.channel >= in.channels) return fail(ctx, GDG_ERR_INVALID, "input %d: channel %u of %u", i, in.channel, in.channels);
@@ -428,6 +449,16 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
     S.shard = shard;
     S.run_metro = shard ? run_metronome : true;
     S.inputs.assign(inputs, inputs + n_inputs);
+    S.source.clear();
+    if (shared) {                                                                /* a reader: metadata, length and empty-or-not of its root */
+        S.source = ctx->batch_source;
+        for (int i = 0; i < n_inputs; i++) {
+            const size_t root = (size_t)S.source[(size_t)i];
+            if (root == (size_t)i) continue;
+            S.inputs[(size_t)i] = inputs[root];
+            n_out[(size_t)i] = n_out[root];
+        }
+    }
     S.opt = *opt;
     S.length = max_len;
     S.pos = 0;
@@ -472,6 +503,8 @@ static void stream_need(const gdg_ctx::BatchStreamState &S, size_t out_count, si
         gdg_batch_stream_span(in.samples_per_channel, in.sample_rate, S.opt.target_rate, S.pos, out_count, &sf, &sc);
         if (sc && sf + sc > S.brought[i]) count[i] = sf + sc - S.brought[i];
     }
+    for (size_t i = 0; i < S.source.size(); i++)                                 /* a reader brings nothing: its frames are its root's */
+        if (S.source[i] != (int)i) { first[i] = first[(size_t)S.source[i]]; count[i] = 0; }
 }
 
 static int stream_check_blocks(gdg_ctx *ctx, int blocks) {
@@ -511,6 +544,11 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const int N = ctx->nch, NO = N + 3, B = GDG_BLOCK_SIZE, out_width = gdg_wave_bytes_per_sample(opt->out_format);
     const size_t length = (size_t)blocks * B, pos = S.pos;                       /* the slice: rows of `length` samples, the job's [pos, pos + length) */
     report_begin(ctx, sharded ? N + 1 : NO, (size_t)blocks);
+    ctx->batch_up_bytes = ctx->batch_resampled = 0;
+    /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
+    const bool shared = !S.source.empty();
+    const SourceFans fans = shared ? sources_fans(S.source) : SourceFans();
+    auto reader = [&](int c) { return shared && S.source[(size_t)c] != c; };
     std::vector<size_t> first((size_t)N), count((size_t)N);
     stream_need(S, length, first.data(), count.data());
     for (int i = 0; i < N; i++)
@@ -532,14 +570,19 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
     std::vector<double> dx((size_t)N, 1.0);
-    const size_t dec_rows_bytes = ((size_t)2 * N * sizeof(gdg_decode_row) + 255) & ~(size_t)255;     /* a piece and a carry per input */
-    const size_t up_rows_bytes = dec_rows_bytes + (((size_t)N * sizeof(gdg_resample_span) + 255) & ~(size_t)255);
+    /* a piece and a carry per input; with shared sources the descriptors are the fan-out forms (a step without a reader writes the plain ones
+     * into the same room) and a table of the rows they name follows: every channel's row once, two source-buffer rows per resampled root */
+    const size_t dec_rows_bytes = ((size_t)2 * N * (shared ? sizeof(gdg_decode_fan) : sizeof(gdg_decode_row)) + 255) & ~(size_t)255;
+    const size_t spans_bytes = ((size_t)N * (shared ? sizeof(gdg_resample_fan) : sizeof(gdg_resample_span)) + 255) & ~(size_t)255;
+    const size_t table_bytes = shared ? ((size_t)3 * N * sizeof(double *) + 255) & ~(size_t)255 : 0;
+    const size_t up_rows_bytes = dec_rows_bytes + spans_bytes + table_bytes;
     size_t up_half = up_rows_bytes, src_half = 0;
     bool any = false;
     for (int i = 0; i < N; i++) {
         const gdg_batch_input &in = S.inputs[(size_t)i];
         if (!in.bytes || !in.samples_per_channel) continue;
         any = true;
+        if (reader(i)) continue;                                                 /* only roots size the upload halves and the source halves */
         cap[(size_t)i] = ws;
         if (in.sample_rate != opt->target_rate) {
             dx[(size_t)i] = (double)in.sample_rate / (double)opt->target_rate;
@@ -584,6 +627,30 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             unsigned char *hb = ctx->h_up[h], *db = d_up + (size_t)h * up_half, *sb = d_src + (size_t)h * src_half;
             gdg_decode_row *rows = reinterpret_cast<gdg_decode_row *>(hb);
             gdg_resample_span *spans = reinterpret_cast<gdg_resample_span *>(hb + dec_rows_bytes);
+            /* shared sources: the step's descriptors in their fan-out form, made here and written into the half once the step is known to have
+             * a reader (or not: then as the plain descriptors, for the kernels every other job runs) */
+            std::vector<gdg_decode_fan> dfans;
+            std::vector<gdg_resample_fan> rfans;
+            std::vector<double *> table;
+            bool step_fans = false;
+            /* the rows root c feeds in this step into the table: `own` (its row, or its place in the source buffer), then its readers' rows */
+            auto fan_rows = [&](double *own, int c, size_t a, bool with_readers, unsigned *dst_first, unsigned *n_dst, unsigned *vec) {
+                *dst_first = (unsigned)table.size();
+                table.push_back(own);
+                if (with_readers)
+                    for (int k = 0; k < fans.fan(c); k++) table.push_back(d_inputs + (size_t)fans.readers(c)[k] * length + a);
+                *n_dst = (unsigned)table.size() - *dst_first;
+                *vec = 1;
+                for (size_t k = *dst_first; k < table.size(); k++) if ((uintptr_t)table[k] & 15) *vec = 0;
+                if (*n_dst > 1) step_fans = true;
+            };
+            auto put_row = [&](const unsigned char *src, double *dst, int c, size_t a, bool with_readers, unsigned cnt, int fmt, unsigned stride, unsigned offset, int &n_rows) {
+                if (!shared) { rows[n_rows++] = gdg_decode_row{ src, dst, cnt, fmt, stride, offset }; return; }
+                gdg_decode_fan f = { src, cnt, fmt, stride, offset, 0, 0, 0, 0 };
+                fan_rows(dst, c, a, with_readers, &f.dst_first, &f.n_dst, &f.vec);
+                dfans.push_back(f);
+                n_rows++;
+            };
             std::vector<BatchPiece> pieces;
             size_t cur = up_rows_bytes;
             int n_rows = 0, n_spans = 0;
@@ -591,6 +658,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             const size_t span = (size_t)w * B, abs = pos + a;                    /* the step: the job's samples [abs, abs + span) */
             for (int c = 0; c < N; c++) {
                 const gdg_batch_input &in = S.inputs[(size_t)c];
+                if (reader(c)) continue;                                         /* its root's piece is stored to its row as well */
                 if (!in.bytes || !in.samples_per_channel || abs >= S.n_out[(size_t)c]) continue;      /* empty, or ended in an earlier step: zeros */
                 const size_t cnt = std::min(S.n_out[(size_t)c] - abs, span), width = (size_t)gdg_wave_bytes_per_sample(in.format) * in.channels;
                 size_t sf = 0, sc = 0;
@@ -608,30 +676,59 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
                         pieces.push_back({ hb + cur + q, src + q, std::min(fresh * width - q, (size_t)1 << 20) });
                     cur += (fresh * width + 15) & ~(size_t)15;
                     if (fresh > max_count) max_count = (unsigned)fresh;
+                    ctx->batch_up_bytes += fresh * width;
                 }
                 if (in.sample_rate == opt->target_rate) {
                     if (bs != abs || fresh != cnt) return fail(ctx, GDG_ERR_INVALID, "input %d: step at %zu, frames from %zu", c, abs, bs);
-                    rows[n_rows++] = gdg_decode_row{ piece, row, (unsigned)cnt, in.format, stride, in.channel };
+                    put_row(piece, row, c, a, true, (unsigned)cnt, in.format, stride, in.channel, n_rows);
                     continue;
                 }
                 /* resample.Time: [the frames kept from the step before | this step's], then the span kernel */
                 const size_t keep_in = std::min(bs, (size_t)GDG_STREAM_CARRY), held = keep_in + fresh;
                 if (sf < bs - keep_in) return fail(ctx, GDG_ERR_INVALID, "input %d: the resampler looks back to frame %zu, kept from %zu", c, sf, bs - keep_in);
                 double *frames = reinterpret_cast<double *>(sb + src_off[(size_t)c]), *carry = d_carry + (size_t)c * GDG_STREAM_CARRY;
-                if (keep_in) rows[n_rows++] = gdg_decode_row{ reinterpret_cast<const unsigned char *>(carry), frames, (unsigned)keep_in, GDG_FMT_IEEE64, 0, 0 };
-                if (fresh) rows[n_rows++] = gdg_decode_row{ piece, frames + keep_in, (unsigned)fresh, in.format, stride, in.channel };
+                if (keep_in) put_row(reinterpret_cast<const unsigned char *>(carry), frames, c, a, false, (unsigned)keep_in, GDG_FMT_IEEE64, 0, 0, n_rows);
+                if (fresh) put_row(piece, frames + keep_in, c, a, false, (unsigned)fresh, in.format, stride, in.channel, n_rows);
                 if (keep_in > max_count) max_count = (unsigned)keep_in;
-                spans[n_spans++] = gdg_resample_span{ frames, row, carry, (long long)(bs - keep_in), (long long)in.samples_per_channel, (long long)abs,
-                                                      dx[(size_t)c], (unsigned)cnt, (unsigned)held, (unsigned)std::min(held, (size_t)GDG_STREAM_CARRY), 0 };
+                const gdg_resample_span sp = { frames, row, carry, (long long)(bs - keep_in), (long long)in.samples_per_channel, (long long)abs,
+                                               dx[(size_t)c], (unsigned)cnt, (unsigned)held, (unsigned)std::min(held, (size_t)GDG_STREAM_CARRY), 0 };
+                if (!shared) spans[n_spans++] = sp;
+                else {
+                    gdg_resample_fan f = { sp, 0, 0 };
+                    unsigned vec = 0;
+                    fan_rows(row, c, a, true, &f.dst_first, &f.n_dst, &vec);
+                    rfans.push_back(f);
+                    n_spans++;
+                }
+                ctx->batch_resampled += cnt;
                 if (cnt > max_out) max_out = (unsigned)cnt;
             }
             up_used[h] = 1;
+            if (shared && n_rows) {
+                if (table.size() * sizeof(double *) > table_bytes) return fail(ctx, GDG_ERR_INVALID, "a step names %zu rows, its table holds %d", table.size(), 3 * N);
+                if (step_fans) {
+                    memcpy(hb, dfans.data(), dfans.size() * sizeof(gdg_decode_fan));
+                    if (n_spans) memcpy(hb + dec_rows_bytes, rfans.data(), rfans.size() * sizeof(gdg_resample_fan));
+                    memcpy(hb + dec_rows_bytes + spans_bytes, table.data(), table.size() * sizeof(double *));
+                } else {                                                         /* no reader in this step: every fan is its first row */
+                    for (size_t k = 0; k < dfans.size(); k++)
+                        rows[k] = gdg_decode_row{ dfans[k].src, table[dfans[k].dst_first], dfans[k].count, dfans[k].fmt, dfans[k].stride, dfans[k].offset };
+                    for (size_t k = 0; k < rfans.size(); k++) spans[k] = rfans[k].span;
+                }
+            }
             if (n_rows) {
                 move_pieces(ctx, pieces, pool);
                 HIP_TRY(ctx, hipMemcpyAsync(db, hb, cur, hipMemcpyHostToDevice, ctx->batch_up_stream));
-                /* ONE decode launch for every piece and every kept frame, ONE resample launch for every resampled input */
-                HIP_TRY(ctx, gdg_launch_wave_decode_rows(reinterpret_cast<const gdg_decode_row *>(db), n_rows, max_count, ctx->batch_up_stream));
-                HIP_TRY(ctx, gdg_launch_resample_spans(reinterpret_cast<const gdg_resample_span *>(db + dec_rows_bytes), n_spans, max_out, ctx->batch_up_stream));
+                if (step_fans) {
+                    /* the fan-out launches: a root's piece decoded once, its span resampled once, stored to every row of its fan */
+                    double *const *d_table = reinterpret_cast<double *const *>(db + dec_rows_bytes + spans_bytes);
+                    HIP_TRY(ctx, gdg_launch_wave_decode_fans(reinterpret_cast<const gdg_decode_fan *>(db), d_table, n_rows, max_count, ctx->batch_up_stream));
+                    HIP_TRY(ctx, gdg_launch_resample_fans(reinterpret_cast<const gdg_resample_fan *>(db + dec_rows_bytes), d_table, n_spans, max_out, ctx->batch_up_stream));
+                } else {
+                    /* ONE decode launch for every piece and every kept frame, ONE resample launch for every resampled input */
+                    HIP_TRY(ctx, gdg_launch_wave_decode_rows(reinterpret_cast<const gdg_decode_row *>(db), n_rows, max_count, ctx->batch_up_stream));
+                    HIP_TRY(ctx, gdg_launch_resample_spans(reinterpret_cast<const gdg_resample_span *>(db + dec_rows_bytes), n_spans, max_out, ctx->batch_up_stream));
+                }
             }
             HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
             return GDG_OK;
@@ -647,6 +744,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* the device buffers stay with the context for the next slice or job (gdg_batch_release) */
     brought.resize((size_t)N);
     for (int i = 0; i < N; i++) brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
+    for (int i = 0; i < N; i++) if (reader(i)) brought[(size_t)i] = brought[(size_t)S.source[(size_t)i]];
     return report_end(ctx, rc);
 }
 
@@ -696,15 +794,16 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
                         /*meters_at_open=*/false);
     if (rc != GDG_OK) return rc;
     for (int i = 0; i < n_inputs; i++)                                           /* a one-call run holds its inputs' rows whole: gdg_batch_length's bound */
-        if (inputs[i].bytes && inputs[i].samples_per_channel > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "input %d is too long", i);
+        if (job.inputs[(size_t)i].bytes && job.inputs[(size_t)i].samples_per_channel > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "input %d is too long", i);
     if (job.length == 0) {                                                       /* every output has 0 samples */
+        ctx->batch_up_bytes = ctx->batch_resampled = 0;
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3, 0);
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
     if (job.length > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "files of %zu samples are too long", job.length);
     std::vector<const void *> in_bytes((size_t)n_inputs);
-    for (int i = 0; i < n_inputs; i++) in_bytes[(size_t)i] = inputs[i].bytes;
+    for (int i = 0; i < n_inputs; i++) in_bytes[(size_t)i] = inputs[i].bytes;       /* a reader's is never read */
     std::vector<size_t> brought;
     bool begun = false;
     return run_slice(ctx, job, (int)(job.length / GDG_BLOCK_SIZE), in_bytes.data(), out_bytes, shard, brought, begun);

@@ -155,6 +155,8 @@ static const OptionDef g_options[] = {
     { "fir_premac_min_partitions_two_amps", "GDG_FIR_PREMAC_MIN_TWO", 1, 1 << 24, -1, &gdg_ctx::fir_premac_min_two, nullptr, true },
     { "stat_premac_launches_used", "GDG_STAT_PREMAC_USED", 0, 0x7fffffff, -1, &gdg_ctx::stat_premac_used, nullptr, false },
     { "stat_batch_device_kib", "GDG_STAT_BATCH_DEVICE_KIB", 0, 0x7fffffff, -1, &gdg_ctx::stat_batch_dev_kib, nullptr, false },
+    { "stat_batch_upload_bytes", "GDG_STAT_BATCH_UPLOAD_BYTES", 0, 0x7fffffff, -1, &gdg_ctx::stat_batch_up_bytes, nullptr, false },
+    { "stat_batch_resampled_samples", "GDG_STAT_BATCH_RESAMPLED", 0, 0x7fffffff, -1, &gdg_ctx::stat_batch_resampled, nullptr, false },
     { "fir_ahead_frames", "GDG_FIR_AHEAD", 0, 4, -1, &gdg_ctx::fir_ahead_frames, nullptr, true },                 /* 1 acts as 0 */
     { "fir_ahead_min_channels", "GDG_FIR_AHEAD_MIN", 1, 1 << 20, -1, &gdg_ctx::fir_ahead_min, nullptr, true },
     { "stat_fir_ahead_sums_used", "GDG_STAT_FIR_AHEAD_USED", 0, 0x7fffffff, -1, &gdg_ctx::stat_fir_ahead_used, nullptr, false },
@@ -382,6 +384,8 @@ int gdg_ctx_get_option(gdg_ctx *ctx, const char *key, long long *value) {
         const size_t kib = (bytes + 1023) / 1024;
         ctx->stat_batch_dev_kib = kib > 0x7fffffffull ? 0x7fffffff : (int)kib;
     }
+    if (o->field == &gdg_ctx::stat_batch_up_bytes) ctx->stat_batch_up_bytes = ctx->batch_up_bytes > 0x7fffffffull ? 0x7fffffff : (int)ctx->batch_up_bytes;
+    if (o->field == &gdg_ctx::stat_batch_resampled) ctx->stat_batch_resampled = ctx->batch_resampled > 0x7fffffffull ? 0x7fffffff : (int)ctx->batch_resampled;
     if (o->knob >= 0) *value = gdg_knob_get(o->knob);
     else if (o->field) *value = ctx->*(o->field);
     else *value = (ctx->*(o->flag)) ? 1 : 0;

@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "arena.h"
+#include "batch_sources.h"
 
 #define NUM_FILTERS 8
 
@@ -352,6 +353,8 @@ struct gdg_ctx {
         std::vector<size_t> brought;           /* source frames [0, brought) of input i have been handed over */
         std::vector<size_t> n_out;             /* samples the input covers in the job: its (resampled) length */
         bool shard = false, run_metro = false; /* opened with gdg_batch_stream_open_shard; ... and this shard runs the job's metronome */
+        std::vector<int> source;               /* the source map as it stood when the job was described, when it has a reader (empty otherwise):
+                                                * inputs and n_out of a reader are its root's */
     } bstream;
     /* the render report (gdg_batch_report_enable): the records of the last completed batch call, [report_ports][report_blocks]; a call
      * that collects (report_live: the switch as it stood when the call began) fills `report` step by step and validates it at its end */
@@ -359,6 +362,13 @@ struct gdg_ctx {
     int report_ports = 0;
     size_t report_blocks = 0;
     std::vector<gdg_block_stats> report;
+    /* the source map (gdg_batch_set_sources; batch_sources.h): batch_source[c] = the channel whose input entry channel c reads, empty = every
+     * channel its own.  Configuration like report_on: read when a job is described, in no blob. */
+    std::vector<int> batch_source;
+    /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
+     * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
+    unsigned long long batch_up_bytes = 0, batch_resampled = 0;
+    int stat_batch_up_bytes = 0, stat_batch_resampled = 0;
     /* gdg_batch_finish_master_slice: the partials of a piece gathered into a pinned slab half, the encoded piece back through another */
     unsigned char *h_fin_up[2] = { nullptr, nullptr }, *h_fin_down[2] = { nullptr, nullptr };
     size_t h_fin_up_cap = 0, h_fin_down_cap = 0;
@@ -619,6 +629,8 @@ int state_load_device_with(gdg_ctx *ctx, const void *d_blob, size_t bytes, const
 int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
                bool run_metronome, gdg_ctx::BatchStreamState &job, bool meters_at_open = true);
 int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
+/* the map in force has a reader: what a checkpoint cannot record yet */
+static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_have_reader(ctx->batch_source); }
 /* a batch call begins: the report of the call before is gone; with the report enabled, zeroed records for `ports` x `blocks` */
 static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks) {
     ctx->report_valid = false;

@@ -286,6 +286,17 @@ struct gdg_resample_span {
     unsigned count, src_count, keep, pad;
 };
 hipError_t gdg_launch_resample_spans(const gdg_resample_span *d_spans, int n_spans, unsigned max_count, hipStream_t s);
+/* The fan-out forms of the two launches above (a batch job with a source map, gdg_batch_set_sources): a root's piece is read and
+ * converted -- a root's span resampled -- ONCE and stored to n_dst rows, d_table[dst_first .. dst_first + n_dst): the root's own row and
+ * its readers'.  The table travels in the same upload as the descriptors.  vec: every row of the fan is 16-byte aligned (the word-wise
+ * path of the decoder).  The single-destination kernels are untouched and serve every step without a reader. */
+struct gdg_decode_fan { const unsigned char *src; unsigned count; int fmt; unsigned stride, offset; unsigned dst_first, n_dst; unsigned vec, pad; };
+hipError_t gdg_launch_wave_decode_fans(const gdg_decode_fan *d_fans, double *const *d_table, int n_fans, unsigned max_count, hipStream_t s);
+struct gdg_resample_fan {
+    gdg_resample_span span;      /* span.dst is not used: the rows are the table's */
+    unsigned dst_first, n_dst;
+};
+hipError_t gdg_launch_resample_fans(const gdg_resample_fan *d_fans, double *const *d_table, int n_fans, unsigned max_count, hipStream_t s);
 hipError_t gdg_launch_resample_time(const double *d_in, int n, double dx, double *d_out, int n_out, hipStream_t s);
 hipError_t gdg_launch_meter(const double *d_rows, size_t stride, int n_ports, int n, gdg_meter_rec *d_state,
                             double decay, unsigned long long hold, hipStream_t s);

@@ -521,6 +521,83 @@ hipError_t gdg_launch_wave_decode_rows(const gdg_decode_row *d_rows, int n_rows,
     return hipGetLastError();
 }
 
+/* ---- the fan-out form: a piece decoded once, stored to every row of its fan (a batch job with a source map) ------------------------------ */
+/* the four samples of group g through word-sized loads, as decode_piece's fast path reads them */
+template <int FMT>
+__device__ __forceinline__ void decode_group(const unsigned *words, unsigned g, double v[4]) {
+    constexpr int W = fmt_width<FMT>::W;
+    unsigned w[W];
+#pragma unroll
+    for (int k = 0; k < W; k++) w[k] = __builtin_nontemporal_load(words + (size_t)g * W + k);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        unsigned code = 0;
+#pragma unroll
+        for (int k = 0; k < W; k++) code |= getb(w, q * W + k) << (8 * k);
+        v[q] = decode_code<FMT>(code);
+    }
+}
+/* the file's sample `at` through byte loads (tails, unaligned pieces, a channel of interleaved frames) */
+template <int FMT>
+__device__ __forceinline__ double decode_at(const unsigned char *src, size_t at) {
+    constexpr int W = fmt_width<FMT>::W;
+    unsigned code = 0;
+#pragma unroll
+    for (int k = 0; k < W; k++) code |= (unsigned)src[at * W + k] << (8 * k);
+    return decode_code<FMT>(code);
+}
+
+/* blockIdx.y = fan.  The format switch yields values in registers; the loop over the fan's rows lies outside it, and in it consecutive
+ * lanes store consecutive samples of ONE row before the next row (rows of a slice lie a slice apart).  No workgroup waits for another. */
+__global__ void __launch_bounds__(256)
+wave_decode_fans_kernel(const gdg_decode_fan *__restrict__ fans, double *const *__restrict__ table) {
+    const gdg_decode_fan r = fans[blockIdx.y];
+    double *const *rows = table + r.dst_first;
+    unsigned done = 0;
+    if (r.stride <= 1 && r.fmt != GDG_FMT_IEEE64 && r.vec && (((uintptr_t)r.src) & 3) == 0) {
+        const unsigned *words = reinterpret_cast<const unsigned *>(r.src);
+        const unsigned groups = r.count / 4;
+        for (unsigned g = blockIdx.x * 256 + threadIdx.x; g < groups; g += gridDim.x * 256) {
+            double v[4];
+            switch (r.fmt) {
+            case GDG_FMT_LPCM8: decode_group<GDG_FMT_LPCM8>(words, g, v); break;
+            case GDG_FMT_LPCM16: decode_group<GDG_FMT_LPCM16>(words, g, v); break;
+            case GDG_FMT_LPCM24: decode_group<GDG_FMT_LPCM24>(words, g, v); break;
+            case GDG_FMT_LPCM32: decode_group<GDG_FMT_LPCM32>(words, g, v); break;
+            default: decode_group<GDG_FMT_IEEE32>(words, g, v); break;
+            }
+            const v2d a = { v[0], v[1] }, b = { v[2], v[3] };
+            for (unsigned d = 0; d < r.n_dst; d++) {
+                v2d *out = reinterpret_cast<v2d *>(rows[d]);
+                out[2 * (size_t)g] = a;
+                out[2 * (size_t)g + 1] = b;
+            }
+        }
+        done = groups * 4;
+    }
+    for (unsigned i = done + blockIdx.x * 256 + threadIdx.x; i < r.count; i += gridDim.x * 256) {
+        const size_t at = r.stride > 1 ? (size_t)i * r.stride + r.offset : (size_t)i;
+        double v;
+        switch (r.fmt) {
+        case GDG_FMT_LPCM8: v = decode_at<GDG_FMT_LPCM8>(r.src, at); break;
+        case GDG_FMT_LPCM16: v = decode_at<GDG_FMT_LPCM16>(r.src, at); break;
+        case GDG_FMT_LPCM24: v = decode_at<GDG_FMT_LPCM24>(r.src, at); break;
+        case GDG_FMT_LPCM32: v = decode_at<GDG_FMT_LPCM32>(r.src, at); break;
+        case GDG_FMT_IEEE32: v = decode_at<GDG_FMT_IEEE32>(r.src, at); break;
+        default: v = reinterpret_cast<const double *>(r.src)[at]; break;      /* IEEE64: the bytes are the sample; src is 8-byte aligned */
+        }
+        for (unsigned d = 0; d < r.n_dst; d++) rows[d][i] = v;
+    }
+}
+
+hipError_t gdg_launch_wave_decode_fans(const gdg_decode_fan *d_fans, double *const *d_table, int n_fans, unsigned max_count, hipStream_t s) {
+    if (n_fans <= 0 || max_count == 0) return hipSuccess;
+    unsigned tiles = (max_count + 1023) / 1024;                /* four samples per thread */
+    if (tiles > 256) tiles = 256;                              /* a thread's stores grow with its fan: more workgroups than the single-row launch */
+    wave_decode_fans_kernel<<<dim3(tiles, (unsigned)n_fans), dim3(256), 0, s>>>(d_fans, d_table);
+    return hipGetLastError();
+}
+
 hipError_t gdg_launch_wave_decode(int fmt, const void *d_bytes, size_t per, unsigned channels, double *d_out, hipStream_t s) {
     size_t n = per * channels;
     if (n == 0) return hipSuccess;
@@ -831,6 +908,42 @@ hipError_t gdg_launch_resample_spans(const gdg_resample_span *d_spans, int n_spa
     if (tiles > 256) tiles = 256;
     if (tiles == 0) tiles = 1;
     resample_span_kernel<<<dim3(tiles, (unsigned)n_spans), dim3(256), 0, s>>>(d_spans);
+    return hipGetLastError();
+}
+
+/* resample_span_kernel with a fan: the six weights and the sum are formed once per output sample -- the same operations in the same order,
+ * so every row gets the bits the single-row kernel gives -- and stored to every row of the fan, a row at a time across the lanes.  The
+ * carry is the root's, kept once. */
+__global__ void __launch_bounds__(256)
+resample_fans_kernel(const gdg_resample_fan *__restrict__ fans, double *const *__restrict__ table) {
+    const gdg_resample_span r = fans[blockIdx.y].span;
+    double *const *rows = table + fans[blockIdx.y].dst_first;
+    const unsigned n_dst = fans[blockIdx.y].n_dst;
+    for (unsigned k = blockIdx.x * 256 + threadIdx.x; k < r.count; k += gridDim.x * 256) {
+        const long long i = r.out_first + (long long)k;
+        double x = (double)i * r.dx;
+        long long idx = (long long)floor(x);
+        double sum = 0.0;
+#pragma unroll
+        for (long long j = idx - 2; j < idx + 4; j++) {
+            if (j >= 0 && j < r.n) {
+                double diff = x - (double)j;
+                const long long at = j - r.src_first;
+                const double v = (at >= 0 && at < (long long)r.src_count) ? r.src[at] : 0.0;
+                sum += v * lanczos_kernel(diff, 3.0);
+            }
+        }
+        for (unsigned d = 0; d < n_dst; d++) rows[d][k] = sum;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < r.keep) r.carry[threadIdx.x] = r.src[r.src_count - r.keep + threadIdx.x];
+}
+
+hipError_t gdg_launch_resample_fans(const gdg_resample_fan *d_fans, double *const *d_table, int n_fans, unsigned max_count, hipStream_t s) {
+    if (n_fans <= 0) return hipSuccess;
+    unsigned tiles = (max_count + 255) / 256;
+    if (tiles > 256) tiles = 256;
+    if (tiles == 0) tiles = 1;
+    resample_fans_kernel<<<dim3(tiles, (unsigned)n_fans), dim3(256), 0, s>>>(d_fans, d_table);
     return hipGetLastError();
 }
 

@@ -1294,3 +1294,24 @@ func (this *Context) BatchReport() ([][]BlockStats, error) {
 	}
 	return goBlockStats(rec, int(ports), int(blocks)), nil
 }
+
+// BatchSetSources: the source map of the next batch calls (gdg_batch_set_sources): source[c] is the channel whose input entry channel c
+// reads -- c itself for a channel that reads its own, a root; any other entry makes c a reader, and its source must be a root.  One entry
+// per channel; nil or an empty slice clears the map.  A shared input is uploaded, decoded and resampled once and stored to every row
+// that reads it; the outputs are those of the job with the entry copied.  Configuration, like the window: no blob carries it, and a job
+// with a reader cannot be checkpointed yet.
+func (this *Context) BatchSetSources(source []int) error {
+	n := len(source)
+	if n == 0 {
+		return this.err(C.gdg_batch_set_sources(this.ctx, nil, 0))
+	}
+	p := (*[1 << 28]C.int)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.int(0)))))
+	if p == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(p))
+	for i, v := range source {
+		p[i] = C.int(v)
+	}
+	return this.err(C.gdg_batch_set_sources(this.ctx, &p[0], C.int(n)))
+}

@@ -46,6 +46,7 @@ def lib():
             "gdgh_engine_batch_stream_sharded_need": (cs, [vp, i32, vp, vp]), "gdgh_engine_batch_stream_sharded_step": (cs, [vp, i32, vp, vp]),
             "gdgh_engine_batch_stream_sharded_close": (cs, [vp]),
             "gdgh_engine_set_batch_report": (None, [vp, i32]),
+            "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
             "gdgh_engine_last_batch_report": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
@@ -194,6 +195,15 @@ class Engine:
         out = np.zeros((ports.value, blocks.value), dtype=pkg.BLOCK_STATS_DTYPE)
         _err(lib().gdgh_engine_last_batch_report(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
         return out
+
+    def batch_set_sources(self, source):
+        """Engine::SetBatchSources: the source map of the next jobs in JOB channel numbers (None clears it); a reader whose root lives on
+        another shard is refused."""
+        if source is None or len(source) == 0:
+            _err(lib().gdgh_engine_set_batch_sources(self._h, None, 0))
+            return
+        arr = (C.c_int * len(source))(*[int(v) for v in source])
+        _err(lib().gdgh_engine_set_batch_sources(self._h, arr, len(source)))
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
                   report=False):

@@ -890,6 +890,30 @@ Error Engine::LoadState(const uint8_t *blob, size_t bytes, uint32_t sampleRate) 
     return "";
 }
 
+Error Engine::SetBatchSources(const std::vector<int> &source) {
+    if (source.empty()) { sources_.clear(); return ""; }
+    if ((int)source.size() != nChannels_) return format("SetBatchSources: a map of %zu entries for %d channels", source.size(), nChannels_);
+    for (int c = 0; c < nChannels_; c++) {
+        const int r = source[(size_t)c];
+        if (r < 0 || r >= nChannels_) return format("SetBatchSources: channel %d reads channel %d, the engine has channels 0 to %d", c, r, nChannels_ - 1);
+        if (source[(size_t)r] != r) return format("SetBatchSources: channel %d reads channel %d, which itself reads channel %d", c, r, source[(size_t)r]);
+        if (shardOf(r) != shardOf(c))
+            return format("SetBatchSources: channel %d (shard %d) reads channel %d on shard %d: a reader and its root live on one shard", c, shardOf(c), r, shardOf(r));
+    }
+    sources_ = source;
+    return "";
+}
+
+/* the shard's part of the map, in the shard's own channel numbers (SetBatchSources has kept every root on its readers' shard) */
+int Engine::applySources(int shard, gdg_ctx *ctx) {
+    if (sources_.empty()) return gdg_batch_set_sources(ctx, nullptr, 0);
+    int first = 0, count = 0;
+    shardRange(shard, &first, &count);
+    std::vector<int> local((size_t)count);
+    for (int c = 0; c < count; c++) local[(size_t)c] = sources_[(size_t)(first + c)] - first;
+    return gdg_batch_set_sources(ctx, local.data(), count);
+}
+
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
  * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
  * controller.go:3005-3045). */
@@ -911,7 +935,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1043,7 +1067,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1252,7 +1276,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1553,6 +1577,9 @@ const char *gdgh_engine_process_all(void *e, const double *const *in, double *co
 
 const char *gdgh_engine_batch_run(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, void *const *outs, size_t *samples) {
     return ret(((Engine *)e)->BatchRun(inputs, n, *opt, window, outs, samples));
+}
+const char *gdgh_engine_set_batch_sources(void *e, const int *source, int n) {
+    return ret(((Engine *)e)->SetBatchSources(source && n > 0 ? std::vector<int>(source, source + n) : std::vector<int>()));
 }
 void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchReport(on != 0); }
 /* records == NULL: the two counts only */

@@ -246,6 +246,11 @@ public:
      * when a job is set up (BatchRun, the Open and Resume calls); it is not part of a checkpoint. */
     void SetBatchReport(bool on) { report_ = on; }
     Error LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const;
+    /* No reference counterpart.  Shared sources (include/gdg.h, gdg_batch_set_sources): source[c] = the JOB channel whose input entry channel
+     * c reads, one entry per channel of the engine; an empty vector clears the map.  The engine splits the map per shard when a job is set
+     * up (BatchRun, the Open and Resume calls).  A map spans one context: a reader whose root lives on another shard is refused here,
+     * with a message, and the map in force stays. */
+    Error SetBatchSources(const std::vector<int> &source);
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -288,6 +293,8 @@ private:
     bool report_ = false, reportValid_ = false;            /* the render report: asked for; the last call's is complete */
     size_t reportBlocks_ = 0;
     std::vector<gdg_block_stats> lastReport_;
+    std::vector<int> sources_;                             /* the source map in job channel numbers; empty: none */
+    int applySources(int shard, gdg_ctx *ctx);             /* the shard's part of it onto its context: a gdg_* status */
     void reportBegin(size_t blocks);
     Error reportOfShard(int shard, gdg_ctx *ctx);
     Error reportOfMaster(gdg_ctx *ctx);

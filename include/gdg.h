@@ -101,6 +101,11 @@ int gdg_ctx_share_ir_spectra(gdg_ctx *ctx, int enable);
  *                                            see that the path under test is the one that ran; saturates; setting it sets the count) (0)
  *   stat_batch_device_kib        >= 0        a figure, not a setting: the capacity of the batch runs' device buffers in KiB, rounded up (what gdg_batch_release
  *                                            frees; saturates; a value set is replaced by the figure at the next read) (0)
+ *   stat_batch_upload_bytes      >= 0        a counter, not a setting: bytes of input file data the last batch run call (or slice) moved to the device --
+ *                                            with a source map (gdg_batch_set_sources) the roots' alone; reset when such a call begins (saturates; a
+ *                                            value set is replaced by the figure at the next read) (0)
+ *   stat_batch_resampled_samples >= 0        ... and the output samples for which that call evaluated resample.Time's Lanczos sum: once per sample
+ *                                            of a root, however many channels read it (0)
  *   fir_premac_lds_bytes         -1 .. 65536 ... whose workgroups ask for this much LDS they never touch, so that they land on the CUs the segments leave
  *                                            idle instead of among the segments' waves; -1: 16384 below 120 channels, 49152 from there, 0 when a channel
  *                                            has fewer than 5 or more than 32 partitions (-1)
@@ -738,6 +743,38 @@ int gdg_block_stats_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_s
                                 gdg_block_stats *d_records);
 int gdg_batch_report_enable(gdg_ctx *ctx, int enable);
 int gdg_batch_report(gdg_ctx *ctx, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks);
+/*
+ * SHARED SOURCES: no reference counterpart.  Re-amping renders one take, or a handful, through hundreds of rigs: with a source map every
+ * shared input is gathered, uploaded, decoded and (when its rate is not the job's) resampled ONCE and stored to the row of every channel
+ * that reads it, instead of once per channel.
+ *   gdg_batch_set_sources(ctx, source, n)                              source[c] = the channel whose input entry channel c reads.
+ *                                                                      source[c] == c: the channel reads its own entry (a ROOT; what
+ *                                                                      every channel does without a map).  Anything else makes c a
+ *                                                                      READER, and source[c] must be a root: source[source[c]] ==
+ *                                                                      source[c].  n = the context's channel count.  source == NULL
+ *                                                                      or n == 0 clears the map.
+ * Configuration, like the window and gdg_batch_report_enable: it holds from the next batch call on, survives batch calls and is part of
+ * no blob.  A malformed map -- an entry out of range, a reader of a reader, the wrong n -- is GDG_ERR_INVALID, gdg_last_error names the
+ * offending channel, and the map in force stays in force; so does a call while a streamed job is open.
+ * With a map in force, in gdg_batch_run, gdg_batch_run_shard, gdg_batch_stream_open and gdg_batch_stream_open_shard:
+ *   n_inputs stays the channel count.  inputs[c] of a reader is never looked at: the reader takes the metadata, the length, the
+ *   empty-or-not status and the samples of its root (a reader of an empty root is silent).
+ *   gdg_batch_length is unchanged: it looks at every entry it is given and knows no map.  The engine computes the job's length over
+ *   the ROOTS; a caller that sizes its buffers with gdg_batch_length leaves the readers' entries empty (or copies of their roots').
+ *   gdg_batch_stream_need reports count[c] == 0 for a reader and first[c] = its root's first; in_bytes[c] of a reader is never read
+ *   and may be NULL.
+ *   Everything downstream is byte for byte that of the same job without a map whose readers' entries are copies of their roots': the
+ *   N + 3 files, a shard's partial master and metronome, the meters over the 2 N + 3 ports, the tuner rings, the render report, and the
+ *   units' state as an equal gdg_state_save blob.  A reader's row gets the bits the per-channel decoder and resampler give.
+ *   A map spans one context: a reader and its root live on the same shard.
+ * LIMIT: a job with shared sources cannot be checkpointed yet.  While the map in force has at least one reader,
+ * gdg_batch_stream_checkpoint, gdg_batch_stream_checkpoint_size, gdg_batch_stream_resume and gdg_batch_stream_resume_shard return
+ * GDG_ERR_UNSUPPORTED (the version-1 container records positions and resampler carries per input).  No map, or a map without a reader,
+ * checkpoints exactly as before.
+ * Off -- no map, or every channel its own root -- no launch, allocation, upload or byte differs from a context that never heard of the
+ * call.  Options stat_batch_upload_bytes and stat_batch_resampled_samples read what the last call moved and resampled.
+ */
+int gdg_batch_set_sources(gdg_ctx *ctx, const int *source, int n);
 
 #ifdef __cplusplus
 
