@@ -942,8 +942,8 @@ class Context:
         return outs, left, right, mb, mf
 
     def batch_finish_master_slice(self, out_format, lefts, rights, aux=None, sample_rate=0, run_meters=False):
-        """batch_finish_master for one slice (whole blocks) of a streamed sharded job: the same bytes, one upload, one kernel and one
-        download per piece (gdg_batch_finish_master_slice)."""
+        """batch_finish_master for one slice (whole blocks) of a streamed sharded job: the same code path, hence the same bytes
+        (gdg_batch_finish_master_slice)."""
         G, n = len(lefts), lefts[0].size
         fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
         wo = lib().gdg_wave_bytes_per_sample(fo)

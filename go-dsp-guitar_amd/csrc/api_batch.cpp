@@ -80,24 +80,8 @@ static int ensure_batch_pipe(gdg_ctx *ctx, size_t half_bytes, size_t up_half_byt
             for (int c = 0; c < 4; c++) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->batch_chunk[h][c], hipEventDisableTiming));
         }
     }
-    if (up_half_bytes > ctx->h_up_cap) {
-        for (int h = 0; h < 2; h++) {
-            if (ctx->h_up[h]) hipHostFree(ctx->h_up[h]);
-            ctx->h_up[h] = nullptr;
-        }
-        ctx->h_up_cap = 0;
-        for (int h = 0; h < 2; h++) HIP_TRY(ctx, pinned_alloc(ctx, (void **)&ctx->h_up[h], up_half_bytes));
-        ctx->h_up_cap = up_half_bytes;
-    }
-    if (half_bytes > ctx->h_batch_cap) {
-        for (int h = 0; h < 2; h++) {
-            if (ctx->h_batch[h]) hipHostFree(ctx->h_batch[h]);
-            ctx->h_batch[h] = nullptr;
-        }
-        ctx->h_batch_cap = 0;
-        for (int h = 0; h < 2; h++) HIP_TRY(ctx, pinned_alloc(ctx, (void **)&ctx->h_batch[h], half_bytes));
-        ctx->h_batch_cap = half_bytes;
-    }
+    HIP_TRY(ctx, ctx->h_up.grow(ctx, up_half_bytes));
+    HIP_TRY(ctx, ctx->h_batch.grow(ctx, half_bytes));
     return GDG_OK;
 }
 
@@ -824,102 +808,43 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
     return batch_run_impl(ctx, inputs, n_inputs, opt, out_bytes, shard);
 }
 
-/* master = ((p_0 + p_1) + ... + p_{G-1}) + aux per side, then the encoder (its clip included) -- all on this context's device; the host
- * only moves the G partial pairs up and the two encoded rows down, in pieces of <= 2^20 samples through the context's io scratch */
-int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
-                            size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+/* what both forms of the master mix refuse, in this order */
+static int finish_master_check(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, uint32_t sample_rate,
+                               int run_meters) {
     if (!ctx || !left || !right || n_shards <= 0) return GDG_ERR_INVALID;
-    const int width = gdg_wave_bytes_per_sample(out_format);
-    if (!width) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", out_format);
+    if (!gdg_wave_bytes_per_sample(out_format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", out_format);
     for (int g = 0; g < n_shards; g++) if (!left[g] || !right[g]) return fail(ctx, GDG_ERR_INVALID, "shard %d has no partial master mix", g);
     if (run_meters && (ctx->n_meter < 2 || sample_rate == 0)) return fail(ctx, GDG_ERR_INVALID, "master meters: the context's last two ports, at a positive rate");
-    report_begin(ctx, 2, (samples + GDG_BLOCK_SIZE - 1) / GDG_BLOCK_SIZE);
-    if (samples == 0) return report_end(ctx, GDG_OK);
-    enter(ctx);
-    const size_t piece = (size_t)1 << 20;
-    const bool report = ctx->report_live;
-    /* the render report: a piece's records, [2][piece / 8192], behind the encoded rows */
-    const size_t piece_blocks = piece / GDG_BLOCK_SIZE, rec_off = (2 * piece * (size_t)width + 15) & ~(size_t)15;
-    int rc = ensure_io(ctx, 1, 3 * piece * sizeof(double));                     /* [left | right | incoming partial or aux] */
-    if (rc == GDG_OK) rc = ensure_io(ctx, 0, report ? rec_off + 2 * piece_blocks * sizeof(gdg_block_stats) : 2 * piece * (size_t)width);
-    if (rc != GDG_OK) return rc;
-    double *d_l = static_cast<double *>(ctx->d_io[1]), *d_r = d_l + piece, *d_p = d_r + piece;
-    unsigned char *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
-    std::vector<gdg_block_stats> rec(report ? 2 * piece_blocks : 0);
-    for (size_t at = 0; at < samples; at += piece) {
-        const size_t n = std::min(piece, samples - at);
-        HIP_TRY(ctx, hipMemcpyAsync(d_l, left[0] + at, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_r, right[0] + at, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        for (int g = 1; g < n_shards; g++) {
-            HIP_TRY(ctx, hipMemcpyAsync(d_p, left[g] + at, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, gdg_launch_accumulate(d_l, d_p, (int)n, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(d_p, right[g] + at, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, gdg_launch_accumulate(d_r, d_p, (int)n, ctx->stream));
-        }
-        if (aux) {                                                               /* spatializer.go:300-310 */
-            HIP_TRY(ctx, hipMemcpyAsync(d_p, aux + at, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, gdg_launch_add_aux(d_l, d_r, d_p, (int)n, ctx->stream));
-        }
-        if (run_meters) {
-            for (size_t o = 0; o < n; o += GDG_BLOCK_SIZE)                       /* block by block, like the loop that fed the other ports */
-                if ((rc = meter_rows(ctx, d_l + o, piece, ctx->n_meter - 2, 2, (int)std::min((size_t)GDG_BLOCK_SIZE, n - o), sample_rate)) != GDG_OK) return rc;
-        }
-        const size_t nb = (n + GDG_BLOCK_SIZE - 1) / GDG_BLOCK_SIZE;             /* d_l and d_r are `piece` apart: two rows, records [2][nb] */
-        if (report) {
-            HIP_TRY(ctx, gdg_launch_block_stats(d_l, piece, 2u, n, GDG_BLOCK_SIZE, d_enc + rec_off, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_enc + rec_off, 2 * nb * sizeof(gdg_block_stats), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIP_TRY(ctx, gdg_launch_wave_encode(out_format, d_l, n, 1, d_enc, ctx->stream));
-        HIP_TRY(ctx, gdg_launch_wave_encode(out_format, d_r, n, 1, d_enc + piece * (size_t)width, ctx->stream));
-        if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(static_cast<unsigned char *>(left_bytes) + at * width, d_enc, n * width, hipMemcpyDeviceToHost, ctx->stream));
-        if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(static_cast<unsigned char *>(right_bytes) + at * width, d_enc + piece * (size_t)width, n * width, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (report)
-            for (size_t side = 0; side < 2; side++)
-                memcpy(&ctx->report[side * ctx->report_blocks + at / GDG_BLOCK_SIZE], &rec[side * nb], nb * sizeof(gdg_block_stats));
-    }
-    return report_end(ctx, GDG_OK);
+    return GDG_OK;
 }
 
-/* gdg_batch_finish_master for one slice of a streamed sharded job, where it runs once per slice on the job's critical path: the same sums
- * and the same encoder, hence the same bits, but per piece ONE upload, ONE kernel and ONE download.  The copy workers gather the G partial
- * pairs and aux into a pinned slab half ([2 G + 1][n] float64) while the piece before is on the bus; finish_master_kernel (io.hip) adds and
- * encodes; the encoded piece comes down into a pinned half and is scattered into the caller's buffers while the next piece computes. */
-int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
-                                  size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
-    if (!ctx || !left || !right || n_shards <= 0) return GDG_ERR_INVALID;
-    const int width = gdg_wave_bytes_per_sample(out_format);
-    if (!width) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", out_format);
-    for (int g = 0; g < n_shards; g++) if (!left[g] || !right[g]) return fail(ctx, GDG_ERR_INVALID, "shard %d has no partial master mix", g);
-    if (run_meters && (ctx->n_meter < 2 || sample_rate == 0)) return fail(ctx, GDG_ERR_INVALID, "master meters: the context's last two ports, at a positive rate");
-    if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);
-    report_begin(ctx, 2, samples / GDG_BLOCK_SIZE);
+/* The master mix of a sharded job, or of one slice of it: master = ((p_0 + p_1) + ... + p_{G-1}) + aux per side, then the encoder (its clip
+ * included) -- all on this context's device, per piece ONE upload, ONE kernel and ONE download.  The copy workers gather the G partial
+ * pairs and aux into a pinned slab half ([2 G + 1][stride] float64) while the piece before is on the bus; finish_master_kernel (io.hip)
+ * adds and encodes; the encoded piece comes down into a pinned half and is scattered into the caller's buffers while the next piece
+ * computes.  Pieces are whole blocks but for the last, which has whatever is left (n >= 1): its rows lie stride = n rounded up to 4 samples
+ * apart, the gather writes the 0 .. 3 samples behind each row as zeros, the kernel runs over stride / 4 groups, and what it makes of the
+ * pad stays on the device -- the meters, the report and the download take n samples. */
+static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
+                         size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+    const size_t width = (size_t)gdg_wave_bytes_per_sample(out_format), B = GDG_BLOCK_SIZE;
+    report_begin(ctx, 2, (samples + B - 1) / B);
     if (samples == 0) return report_end(ctx, GDG_OK);
     const bool report = ctx->report_live;
     enter(ctx);
-    const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0), B = GDG_BLOCK_SIZE;
-    /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the slice and the shard count */
+    const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0);
+    /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the sample count and the shard count */
     const size_t piece = B * std::min((size_t)128, std::max((size_t)1, ((size_t)8 << 20) / ((2 * G + 1) * B * sizeof(double))));
     /* the render report: a piece's records, [2][piece / 8192], come down behind its encoded rows */
-    const size_t rec_off = 2 * piece * (size_t)width, rec_bytes = report ? 2 * (piece / B) * sizeof(gdg_block_stats) : 0;
+    const size_t rec_off = 2 * piece * width, rec_bytes = report ? 2 * (piece / B) * sizeof(gdg_block_stats) : 0;
     const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = rec_off + rec_bytes;
     if (!ctx->fin_up[0])
         for (int h = 0; h < 2; h++) {
             HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_down[h], hipEventDisableTiming));
         }
-    if (up_bytes > ctx->h_fin_up_cap) {
-        for (int h = 0; h < 2; h++) { if (ctx->h_fin_up[h]) hipHostFree(ctx->h_fin_up[h]); ctx->h_fin_up[h] = nullptr; }
-        ctx->h_fin_up_cap = 0;
-        for (int h = 0; h < 2; h++) HIP_TRY(ctx, pinned_alloc(ctx, (void **)&ctx->h_fin_up[h], up_bytes));
-        ctx->h_fin_up_cap = up_bytes;
-    }
-    if (down_bytes > ctx->h_fin_down_cap) {
-        for (int h = 0; h < 2; h++) { if (ctx->h_fin_down[h]) hipHostFree(ctx->h_fin_down[h]); ctx->h_fin_down[h] = nullptr; }
-        ctx->h_fin_down_cap = 0;
-        for (int h = 0; h < 2; h++) HIP_TRY(ctx, pinned_alloc(ctx, (void **)&ctx->h_fin_down[h], down_bytes));
-        ctx->h_fin_down_cap = down_bytes;
-    }
+    HIP_TRY(ctx, ctx->h_fin_up.grow(ctx, up_bytes));
+    HIP_TRY(ctx, ctx->h_fin_down.grow(ctx, down_bytes));
     /* the device side: two slab halves (+ the two rows of sums the meters read), two halves of encoded rows */
     int rc = ensure_io(ctx, 1, 2 * up_bytes + 2 * piece * sizeof(double));
     if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * down_bytes);
@@ -928,61 +853,63 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
     double *d_sums = (run_meters || report) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
     const size_t n_pieces = (samples + piece - 1) / piece;
     auto span = [&](size_t k) { return std::min(piece, samples - k * piece); };
+    auto stride_of = [](size_t n) { return (n + 3) & ~(size_t)3; };                /* <= piece: a piece is whole blocks */
     auto body = [&]() -> int {
-        /* piece k's rows into its pinned half: [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux], n samples apart */
+        /* piece k's rows into its pinned half: [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux], stride samples apart */
         auto gather = [&](size_t k) -> int {
             const int h = (int)(k & 1);
-            const size_t n = span(k), at = k * piece;
+            const size_t n = span(k), stride = stride_of(n), at = k * piece;
             if (k >= 2) HIP_TRY(ctx, hipEventSynchronize(ctx->fin_up[h]));     /* piece k - 2 has left this half */
             std::vector<BatchPiece> pieces;
             for (size_t r = 0; r < rows; r++) {
                 const double *src = (r < G ? left[r] : r < 2 * G ? right[r - G] : aux) + at;
-                const size_t row_at = (r < 2 * G ? r : 2 * G) * n * sizeof(double);
+                unsigned char *row = ctx->h_fin_up[h] + r * stride * sizeof(double);
                 for (size_t q = 0; q < n * sizeof(double); q += (size_t)1 << 18)      /* pieces of <= 256 KiB: every worker gets some */
-                    pieces.push_back({ ctx->h_fin_up[h] + row_at + q, reinterpret_cast<const unsigned char *>(src) + q, std::min(n * sizeof(double) - q, (size_t)1 << 18) });
+                    pieces.push_back({ row + q, reinterpret_cast<const unsigned char *>(src) + q, std::min(n * sizeof(double) - q, (size_t)1 << 18) });
+                memset(row + n * sizeof(double), 0, (stride - n) * sizeof(double));
             }
             move_pieces(ctx, pieces);
             return GDG_OK;
         };
         auto enqueue = [&](size_t k) -> int {
             const int h = (int)(k & 1);
-            const size_t n = span(k);
+            const size_t n = span(k), stride = stride_of(n), nb = (n + B - 1) / B;
             unsigned char *slab = d_slab + (size_t)h * up_bytes, *enc = d_enc + (size_t)h * down_bytes;
-            HIP_TRY(ctx, hipMemcpyAsync(slab, ctx->h_fin_up[h], rows * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(slab, ctx->h_fin_up[h], rows * stride * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipEventRecord(ctx->fin_up[h], ctx->stream));
             {
                 ProfScope ps(ctx, GDG_K_WAVE);
-                HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), n, n_shards, aux != nullptr, n, enc, enc + piece * (size_t)width,
+                HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc, enc + piece * width,
                                                       d_sums, piece, ctx->stream));
             }
             if (run_meters)
                 for (size_t o = 0; o < n; o += B)                                /* block by block, like the loop that fed the other ports */
-                    if ((rc = meter_rows(ctx, d_sums + o, piece, ctx->n_meter - 2, 2, (int)B, sample_rate)) != GDG_OK) return rc;
+                    if ((rc = meter_rows(ctx, d_sums + o, piece, ctx->n_meter - 2, 2, (int)std::min(B, n - o), sample_rate)) != GDG_OK) return rc;
             if (report) {                                                    /* the sums: after the aux, before the encoder's clamp */
                 HIP_TRY(ctx, gdg_launch_block_stats(d_sums, piece, 2u, n, (unsigned)B, enc + rec_off, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + rec_off, enc + rec_off, 2 * (n / B) * sizeof(gdg_block_stats), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + rec_off, enc + rec_off, 2 * nb * sizeof(gdg_block_stats), hipMemcpyDeviceToHost, ctx->stream));
             }
             /* the download of piece k - 2 into this pinned half has been scattered: scatter(k - 2) ran before enqueue(k) */
-            if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * (size_t)width, hipMemcpyDeviceToHost, ctx->stream));
-            if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + piece * (size_t)width, enc + piece * (size_t)width, n * (size_t)width, hipMemcpyDeviceToHost, ctx->stream));
+            if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * width, hipMemcpyDeviceToHost, ctx->stream));
+            if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + piece * width, enc + piece * width, n * width, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipEventRecord(ctx->fin_down[h], ctx->stream));
             return GDG_OK;
         };
         auto scatter = [&](size_t k) -> int {
             const int h = (int)(k & 1);
-            const size_t nb = span(k) * (size_t)width, at = k * piece * (size_t)width;
+            const size_t bytes = span(k) * width, at = k * piece * width;
             HIP_TRY(ctx, hipEventSynchronize(ctx->fin_down[h]));
             std::vector<BatchPiece> pieces;
             for (int side = 0; side < 2; side++) {
                 unsigned char *dst = static_cast<unsigned char *>(side ? right_bytes : left_bytes);
                 if (!dst) continue;
-                const unsigned char *src = ctx->h_fin_down[h] + (size_t)side * piece * (size_t)width;
-                for (size_t q = 0; q < nb; q += (size_t)1 << 18) pieces.push_back({ dst + at + q, src + q, std::min(nb - q, (size_t)1 << 18) });
+                const unsigned char *src = ctx->h_fin_down[h] + (size_t)side * piece * width;
+                for (size_t q = 0; q < bytes; q += (size_t)1 << 18) pieces.push_back({ dst + at + q, src + q, std::min(bytes - q, (size_t)1 << 18) });
             }
             move_pieces(ctx, pieces);
             if (report) {
                 const gdg_block_stats *rec = reinterpret_cast<const gdg_block_stats *>(ctx->h_fin_down[h] + rec_off);
-                const size_t nb = span(k) / B;
+                const size_t nb = (span(k) + B - 1) / B;
                 for (size_t side = 0; side < 2; side++)
                     memcpy(&ctx->report[side * ctx->report_blocks + k * (piece / B)], rec + side * nb, nb * sizeof(gdg_block_stats));
             }
@@ -1000,4 +927,21 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
     rc = body();
     hipStreamSynchronize(ctx->stream);                                           /* the caller's rows are never read after the call, whatever happened */
     return report_end(ctx, rc);
+}
+
+/* the master mix of a whole job: any sample count */
+int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
+                            size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+    const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
+    if (rc != GDG_OK) return rc;
+    return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes);
+}
+
+/* ... and of one slice of a streamed sharded job, where it runs once per slice on the job's critical path: whole blocks, as the slices are */
+int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
+                                  size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+    const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
+    if (rc != GDG_OK) return rc;
+    if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);
+    return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes);
 }

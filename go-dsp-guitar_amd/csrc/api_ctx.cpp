@@ -306,22 +306,19 @@ int gdg_ctx_destroy(gdg_ctx *ctx) {
     for (auto e : ctx->gjoin) hipEventDestroy(e);
     if (ctx->gfork) hipEventDestroy(ctx->gfork);
     for (int h = 0; h < 2; h++) {
-        if (ctx->h_batch[h]) hipHostFree(ctx->h_batch[h]);
         if (ctx->batch_ready[h]) hipEventDestroy(ctx->batch_ready[h]);
         if (ctx->batch_moved[h]) hipEventDestroy(ctx->batch_moved[h]);
         for (int c = 0; c < 4; c++) if (ctx->batch_chunk[h][c]) hipEventDestroy(ctx->batch_chunk[h][c]);
     }
     if (ctx->batch_stream) hipStreamDestroy(ctx->batch_stream);
     for (int h = 0; h < 2; h++) {
-        if (ctx->h_up[h]) hipHostFree(ctx->h_up[h]);
         if (ctx->batch_up_ready[h]) hipEventDestroy(ctx->batch_up_ready[h]);
     }
     for (int h = 0; h < 2; h++) {
-        if (ctx->h_fin_up[h]) hipHostFree(ctx->h_fin_up[h]);
-        if (ctx->h_fin_down[h]) hipHostFree(ctx->h_fin_down[h]);
         if (ctx->fin_up[h]) hipEventDestroy(ctx->fin_up[h]);
         if (ctx->fin_down[h]) hipEventDestroy(ctx->fin_down[h]);
     }
+    for (PinnedHalves *p : { &ctx->h_batch, &ctx->h_up, &ctx->h_fin_up, &ctx->h_fin_down }) p->release();
     if (ctx->batch_begin) hipEventDestroy(ctx->batch_begin);
     for (int i = 0; i < 6; i++) hipFree(ctx->batch_dev[i]);
     if (ctx->batch_up_stream) hipStreamDestroy(ctx->batch_up_stream);

@@ -154,6 +154,16 @@ struct StepDesc {
 struct ProfEvent { int kind; hipEvent_t a, b; };
 class CopyPool;
 
+/* two pinned host halves of one size, for a transfer that fills one while the other is on the bus: kept from call to call, grown when a
+ * call needs more (never shrunk), freed with the context */
+struct PinnedHalves {
+    unsigned char *half[2] = { nullptr, nullptr };
+    size_t cap = 0;
+    unsigned char *operator[](size_t h) const { return half[h]; }
+    hipError_t grow(gdg_ctx *ctx, size_t bytes);      /* both halves hold at least `bytes` afterwards; what they held is gone when they grew */
+    void release();
+};
+
 struct gdg_ctx {
     int nch = 0, max_frames = 0, device = 0;
     hipStream_t stream = nullptr;
@@ -328,14 +338,12 @@ struct gdg_ctx {
     gdg_meter_rec *d_meter = nullptr;
     int n_meter = 0;
     /* the batch run's PCIe side: two pinned halves, a copy stream and events (ensure_batch_pipe) */
-    unsigned char *h_batch[2] = { nullptr, nullptr };
-    size_t h_batch_cap = 0;
+    PinnedHalves h_batch;
     hipStream_t batch_stream = nullptr;
     hipEvent_t batch_ready[2] = { nullptr, nullptr }, batch_moved[2] = { nullptr, nullptr };
     hipEvent_t batch_chunk[2][4] = {};         /* a step's download in four pieces: the scatter into the caller's files starts when the first has landed */
     /* ... and the inputs' way up, step by step: two more pinned halves, a stream, events */
-    unsigned char *h_up[2] = { nullptr, nullptr };
-    size_t h_up_cap = 0;
+    PinnedHalves h_up;
     hipStream_t batch_up_stream = nullptr;
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
     /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
@@ -369,9 +377,8 @@ struct gdg_ctx {
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;
     int stat_batch_up_bytes = 0, stat_batch_resampled = 0;
-    /* gdg_batch_finish_master_slice: the partials of a piece gathered into a pinned slab half, the encoded piece back through another */
-    unsigned char *h_fin_up[2] = { nullptr, nullptr }, *h_fin_down[2] = { nullptr, nullptr };
-    size_t h_fin_up_cap = 0, h_fin_down_cap = 0;
+    /* the master mix of a job or a slice (finish_master): the partials of a piece gathered into a pinned slab half, the encoded piece back through another */
+    PinnedHalves h_fin_up, h_fin_down;
     hipEvent_t fin_up[2] = { nullptr, nullptr }, fin_down[2] = { nullptr, nullptr };     /* a half's upload has left it / its download has landed */
     /* channel groups of the host-buffer paths: group g's upload, kernels and download run on stream g, so one group's
      * PCIe transfers overlap the other groups' kernels (channels are independent) */
@@ -557,6 +564,23 @@ Unit *get_unit(gdg_ctx *ctx, int handle);
 bool segf_unit_ok(const Unit &u, int frames, uint32_t sample_rate);
 bool reverb_ahead_ok(int frames, uint32_t sample_rate);
 hipError_t pinned_alloc(gdg_ctx *ctx, void **p, size_t bytes);
+inline void PinnedHalves::release() {
+    for (int h = 0; h < 2; h++) {
+        if (half[h]) hipHostFree(half[h]);
+        half[h] = nullptr;
+    }
+    cap = 0;
+}
+inline hipError_t PinnedHalves::grow(gdg_ctx *ctx, size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    for (int h = 0; h < 2; h++) {
+        const hipError_t e = pinned_alloc(ctx, (void **)&half[h], bytes);
+        if (e != hipSuccess) return e;
+    }
+    cap = bytes;
+    return hipSuccess;
+}
 int build_plan(gdg_ctx *ctx, const std::vector<int> &active, const double *d_in, double *d_out, int frames, uint32_t sample_rate,
                       int stride, int stride_out, bool rows_by_channel, int G, const std::vector<size_t> &bounds);
 int check_device_error(gdg_ctx *ctx);

@@ -303,10 +303,9 @@ hipError_t gdg_launch_meter(const double *d_rows, size_t stride, int n_ports, in
 
 /* dst_a[i] += src[i]; dst_b[i] += src[i]  (the aux input of the spatializer, spatializer.go:300-310) */
 hipError_t gdg_launch_add_aux(double *d_a, double *d_b, const double *d_src, int n, hipStream_t s);
-hipError_t gdg_launch_accumulate(double *d_dst, const double *d_src, int n, hipStream_t s);      /* dst[i] += src[i] */
-/* the master of one piece of a sharded job (gdg_batch_finish_master_slice): d_slab = [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux] rows of
+/* the master of one piece of a sharded job (gdg_batch_finish_master, gdg_batch_finish_master_slice): d_slab = [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux] rows of
  * `stride` samples; per side ((p_0 + p_1) + ... + p_{G-1}) + aux, encoded into n * width bytes at d_left_bytes / d_right_bytes; d_sums
- * non-null: the float64 sums as well, left at d_sums, right at d_sums + sums_stride (the meters read them).  n a multiple of 4. */
+ * non-null: the float64 sums as well, left at d_sums, right at d_sums + sums_stride (the meters read them).  n a multiple of 4: a ragged piece comes with zeros up to the next one. */
 hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
                                     void *d_right_bytes, double *d_sums, size_t sums_stride, hipStream_t s);
 hipError_t gdg_launch_metronome(const double *d_tick, unsigned n_tick, const double *d_tock, unsigned n_tock, double *d_out, int n,

@@ -284,17 +284,6 @@ hipError_t gdg_launch_add_aux(double *d_a, double *d_b, const double *d_src, int
     return hipGetLastError();
 }
 
-/* dst[i] += src[i]: the shards' partial master sums, added in shard order (gdg_batch_finish_master) */
-__global__ void __launch_bounds__(256) accumulate_kernel(double *__restrict__ dst, const double *__restrict__ src, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] += src[i];
-}
-hipError_t gdg_launch_accumulate(double *d_dst, const double *d_src, int n, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    accumulate_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_dst, d_src, n);
-    return hipGetLastError();
-}
-
 hipError_t gdg_launch_metronome(const double *d_tick, unsigned n_tick, const double *d_tock, unsigned n_tock, double *d_out, int n,
                                 unsigned sc0, unsigned tc0, unsigned spb, unsigned beats, unsigned j0, hipStream_t s) {
     if (n <= 0) return hipSuccess;
@@ -683,10 +672,10 @@ hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_s
     return hipGetLastError();
 }
 
-/* The master of one piece of a sharded job in ONE launch (gdg_batch_finish_master_slice): the slab holds G left rows, G right rows and the
- * aux row, `stride` samples apart.  A thread takes four consecutive samples of both sides: p_0, then + p_1 .. + p_{G-1} in shard order,
- * then + aux -- the adds of accumulate_kernel and add_aux_kernel one after the other, so the same bits -- and encodes them into whole
- * words as wave_encode4_kernel does (IEEE64: the sums are the bytes, wave.go:694-709).  Every partial is read once and never again:
+/* The master of one piece of a sharded job in ONE launch (gdg_batch_finish_master and _slice): the slab holds G left rows, G right rows and
+ * the aux row, `stride` samples apart.  A thread takes four consecutive samples of both sides: p_0, then + p_1 .. + p_{G-1} in shard order,
+ * then + aux -- one IEEE add after the other, never contracted, so the bits of that order wherever it is computed -- and encodes them into
+ * whole words as wave_encode4_kernel does (IEEE64: the sums are the bytes, wave.go:694-709).  Every partial is read once and never again:
  * non-temporal loads, and non-temporal stores for what goes straight down the bus.  SUMS: the float64 sums stay for the meters. */
 template <int FMT, bool SUMS>
 __global__ void __launch_bounds__(256)

@@ -612,9 +612,10 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
  * and once per slice, when every shard has delivered it:
  *   gdg_batch_finish_master_slice(ctx, fmt, {left_g}, {right_g}, G, aux, blocks * 8192, rate, meters, left_bytes, right_bytes)
  *                                                                      the arguments, the result and the bits of gdg_batch_finish_master
- *                                                                      for a whole number of blocks (GDG_ERR_INVALID otherwise), made
- *                                                                      for the job's critical path: the partials gathered into one pinned
- *                                                                      slab, one upload, one kernel and one download per piece
+ *                                                                      for a whole number of blocks (GDG_ERR_INVALID otherwise) -- the
+ *                                                                      same code path, made for the job's critical path: the partials
+ *                                                                      gathered into one pinned slab, one upload, one kernel and one
+ *                                                                      download per piece
  * A shard's slices step where the ONE-CALL gdg_batch_run_shard of the whole job would step, so chain outputs, partial sums, metronome,
  * meters, tuner and unit state are that run's whatever the slicing, and the finished slices put together are gdg_batch_finish_master's
  * bytes.  gdg_batch_stream_step on a job opened as a shard and gdg_batch_stream_step_shard on a job opened with gdg_batch_stream_open

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""gdg_batch_finish_master_slice beside gdg_batch_finish_master on the same host arrays: G = 8, lpcm24, aux, meters off, slices of 4, 16
-and 64 blocks; host wall-clock of the C call alone, both alternated in one process, 5 warm-up calls and 25 measured calls each.
+"""The master mix of a sharded job, timed once per entry point: gdg_batch_finish_master and gdg_batch_finish_master_slice share ONE engine
+(finish_master, api_batch.cpp), so the two rows of a size are two series of the same code and their difference is noise -- the probe no
+longer compares two implementations.  Run on a commit where the whole-job finish still had a loop of its own, the rows are that loop and
+the engine; that is how profiles/finish_master_one_engine.txt was made.
+On the same host arrays: G = 8, lpcm24, aux, meters off, 4, 16 and 64 blocks; host wall-clock of the C call alone, the entry points
+alternated in one process, 5 warm-up calls and 25 measured calls each.
 Then, for information, one 3-context job of tests/test_gpu_batch_stream.py's _long_job: the streamed sharded run beside the one-call
-sharded run (one device carries all three shards: it says nothing about a job over several GPUs).
-Usage: finish_master_slice.py [output file]"""
+sharded run (one device carries all three shards: it says nothing about a job over several GPUs); --finish-only leaves it out.
+Usage: finish_master_slice.py [--finish-only] [output file]"""
 import ctypes as C
 import os
 import sys
@@ -24,12 +28,13 @@ def stats(v):
     return "median %8.3f  min %8.3f  max %8.3f  p25 %8.3f  p75 %8.3f" % (np.median(v), v[0], v[-1], v[len(v) // 4], v[(3 * len(v)) // 4])
 
 
-def finish_ab(pkg, lines):
+def finish_times(pkg, lines):
     G, fmt, rate, warm, reps = 8, pkg.WAVE_FORMATS["lpcm24"], 48000, 5, 25
     lib = pkg.lib()
     ctx = pkg.Context(1, BLOCK)
     rng = np.random.default_rng(1)
-    lines.append("finish of one slice: G = %d, lpcm24, aux, meters off; ms per call (host wall-clock), %d calls after %d warm-up calls, alternated" % (G, reps, warm))
+    lines.append("the finish: G = %d, lpcm24, aux, meters off; ms per call (host wall-clock), %d calls after %d warm-up calls, the entry points alternated" % (G, reps, warm))
+    entries = {"gdg_batch_finish_master": lib.gdg_batch_finish_master, "gdg_batch_finish_master_slice": lib.gdg_batch_finish_master_slice}
     for blocks in (4, 16, 64):
         n = blocks * BLOCK
         lefts = [rng.uniform(-0.2, 0.2, n) for _ in range(G)]
@@ -37,21 +42,21 @@ def finish_ab(pkg, lines):
         aux = rng.uniform(-0.2, 0.2, n)
         lp = (C.c_void_p * G)(*[a.ctypes.data for a in lefts])
         rp = (C.c_void_p * G)(*[a.ctypes.data for a in rights])
-        outs = {name: (np.zeros(n * 3, dtype=np.uint8), np.zeros(n * 3, dtype=np.uint8)) for name in ("old", "new")}
-        calls = {"old": lib.gdg_batch_finish_master, "new": lib.gdg_batch_finish_master_slice}
-        times = {"old": [], "new": []}
+        outs = {name: (np.zeros(n * 3, dtype=np.uint8), np.zeros(n * 3, dtype=np.uint8)) for name in entries}
+        times = {name: [] for name in entries}
         for i in range(warm + reps):
-            for name in ("old", "new"):
+            for name, call in entries.items():
                 ml, mr = outs[name]
                 t0 = time.perf_counter()
-                rc = calls[name](ctx._h, fmt, lp, rp, G, aux.ctypes.data, n, rate, 0, ml.ctypes.data, mr.ctypes.data)
+                rc = call(ctx._h, fmt, lp, rp, G, aux.ctypes.data, n, rate, 0, ml.ctypes.data, mr.ctypes.data)
                 dt = time.perf_counter() - t0
                 assert rc == 0, (name, rc)
                 if i >= warm:
                     times[name].append(dt)
-        assert all(np.array_equal(a, b) for a, b in zip(outs["old"], outs["new"])), "the two finishes differ"
-        lines.append("  %2d blocks  gdg_batch_finish_master        %s" % (blocks, stats(times["old"])))
-        lines.append("  %2d blocks  gdg_batch_finish_master_slice  %s" % (blocks, stats(times["new"])))
+        a, b = outs.values()
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), "the two entry points differ"
+        for name in entries:
+            lines.append("  %2d blocks  %-30s %s" % (blocks, name, stats(times[name])))
     ctx.close()
 
 
@@ -114,13 +119,15 @@ def job_ab(pkg, lines):
 
 def main():
     pkg = entry.load_package()
+    args = [a for a in sys.argv[1:] if a != "--finish-only"]
     lines = []
-    finish_ab(pkg, lines)
-    job_ab(pkg, lines)
+    finish_times(pkg, lines)
+    if "--finish-only" not in sys.argv[1:]:
+        job_ab(pkg, lines)
     text = "\n".join(lines) + "\n"
     print(text, end="", flush=True)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if args:
+        with open(args[0], "w") as f:
             f.write(text)
 
 

@@ -1,7 +1,9 @@
 """The streamed form of a SHARD (gdg_batch_stream_open_shard / gdg_batch_stream_step_shard) and the per-slice finish of the master
 (gdg_batch_finish_master_slice).  The yardstick is the one-call form on fresh, identically configured contexts -- gdg_batch_run_shard
 per shard, then gdg_batch_finish_master -- byte for byte: the same kernels in the same order (the finish: the same adds in the same
-order, then the same encoder), so no tolerance anywhere; beside it the oracle pipeline under the one-call sharded test's own rules."""
+order, then the same encoder), so no tolerance anywhere; beside it the oracle pipeline under the one-call sharded test's own rules.
+The finish alone: both entry points run one engine, so each is held against numpy's float64 sums in the documented order, the oracle's
+encoder, a third context's meters and block_stats of the sums -- exact equality as well."""
 import numpy as np
 import pytest
 
@@ -258,39 +260,109 @@ def test_the_block_counts_of_the_finish_cases_cover_1_to_20():
     assert sorted(set(blocks_of(i) for i in range(len(COMBOS)))) == list(range(1, 21))
 
 
-@pytest.mark.parametrize("i", range(len(COMBOS)), ids=["G%d-%s-%s" % (G, fmt, "aux" if aux else "noaux") for G, fmt, aux in COMBOS])
-def test_finish_master_slice_has_the_bytes_of_finish_master(i):
+def yardstick(oracle, fmt, lefts, rights, aux):
+    """What a finish must give, made without the code under test: the float64 sums of both sides in the documented order (numpy: IEEE adds of
+    the same operands in the same order give the same bits) and their bytes from the oracle's encoder, to which tests/test_gpu_io.py pins
+    the device's"""
+    sums = [seq_sum(lefts, aux), seq_sum(rights, aux)]
+    return sums, [oracle.wave_encode(fmt, s) for s in sums]
+
+
+def finish_against_the_yardstick(finish, fmt, lefts, rights, aux, sums, want, rate=48000):
+    """`finish` (the name of an entry point) on fresh contexts: the bytes without and with meters, the master ports' meters against a third,
+    identically configured context that is fed the numpy sums block by block (the last block with its true length), and the render report
+    against block_stats of the numpy sums.  Returns the bytes and the two contexts' meter readings of the master ports."""
     pkg = package()
+    n, wo, what = lefts[0].size, pkg_width(fmt), "%s, G = %d, %s, aux %s, %d samples" % (finish, len(lefts), fmt, aux is not None, lefts[0].size)
+    plain = pkg.Context(1, BLOCK)
+    got = getattr(plain, finish)(fmt, lefts, rights, aux=aux)
+    plain.close()
+    for side in range(2):
+        assert got[side].size == want[side].size == n * wo, what
+        assert np.array_equal(got[side], want[side]), "%s side, %s: %d samples differ" % (
+            ("left", "right")[side], what, np.count_nonzero((got[side] != want[side]).reshape(-1, wo).any(axis=1)))
+    ctx, third = pkg.Context(1, BLOCK), pkg.Context(1, BLOCK)
+    for c in (ctx, third):
+        c.meter_configure(5)
+        c.meter_set_enabled(True)
+    ctx.batch_report_enable()
+    got_m = getattr(ctx, finish)(fmt, lefts, rights, aux=aux, sample_rate=rate, run_meters=True)
+    for side in range(2):
+        assert np.array_equal(got_m[side], want[side]), what
+    rep = ctx.batch_report()
+    assert rep.shape == (2, -(-n // BLOCK)), what
+    assert rep.tobytes() == ctx.block_stats(sums, BLOCK).tobytes(), "the render report, " + what
+    for o in range(0, n, BLOCK):
+        rows = np.zeros((5, min(BLOCK, n - o)))
+        rows[3], rows[4] = sums[0][o:o + BLOCK], sums[1][o:o + BLOCK]
+        third.meter_process(rows, rate)
+    readings = []
+    for c in (ctx, third):
+        level, peak = c.meter_analyze()
+        readings.append((list(level[3:]), list(peak[3:]), c.meter_state(3), c.meter_state(4)))
+    assert readings[0] == readings[1], "the master ports' meters, " + what
+    assert ctx.meter_state(3)[1] > 0 and ctx.meter_state(2)[1] == 0  # the master ports were fed, the others were not
+    ctx.close()
+    third.close()
+    return got, readings[0]
+
+
+@pytest.mark.parametrize("i", range(len(COMBOS)), ids=["G%d-%s-%s" % (G, fmt, "aux" if aux else "noaux") for G, fmt, aux in COMBOS])
+def test_finish_master_slice_has_the_bytes_of_finish_master(oracle, i):
+    """both entry points run one engine, so each is held against the yardstick; their comparison with each other stays beside it"""
     G, fmt, with_aux = COMBOS[i]
     blocks = blocks_of(i)
     lefts, rights, aux = finish_case(G, fmt, with_aux, blocks, 9000 + i)
-    rate = 48000
-    plain = pkg.Context(1, BLOCK)
-    want = plain.batch_finish_master(fmt, lefts, rights, aux=aux)
-    got = plain.batch_finish_master_slice(fmt, lefts, rights, aux=aux)
-    plain.close()
+    sums, expect = yardstick(oracle, fmt, lefts, rights, aux)
+    want, want_meters = finish_against_the_yardstick("batch_finish_master", fmt, lefts, rights, aux, sums, expect)
+    got, got_meters = finish_against_the_yardstick("batch_finish_master_slice", fmt, lefts, rights, aux, sums, expect)
     wo = pkg_width(fmt)
     for side in range(2):
         assert got[side].size == want[side].size == blocks * BLOCK * wo
         assert np.array_equal(got[side], want[side]), "%s side, G = %d, %s, aux %s, %d blocks: %d samples differ" % (
             ("left", "right")[side], G, fmt, with_aux, blocks, np.count_nonzero((got[side] != want[side]).reshape(-1, wo).any(axis=1)))
-    # with meters, on two identically configured contexts: the two last ports
-    a, b = pkg.Context(1, BLOCK), pkg.Context(1, BLOCK)
-    for ctx in (a, b):
-        ctx.meter_configure(5)
-        ctx.meter_set_enabled(True)
-    want_m = a.batch_finish_master(fmt, lefts, rights, aux=aux, sample_rate=rate, run_meters=True)
-    got_m = b.batch_finish_master_slice(fmt, lefts, rights, aux=aux, sample_rate=rate, run_meters=True)
-    for side in range(2):
-        assert np.array_equal(got_m[side], want_m[side]) and np.array_equal(got_m[side], want[side])
-    la, pa = a.meter_analyze()
-    lb, pb = b.meter_analyze()
-    assert list(la) == list(lb) and list(pa) == list(pb)
-    for port in (3, 4):
-        assert a.meter_state(port) == b.meter_state(port), "meter port %d" % port
-    assert a.meter_state(3)[1] > 0 and a.meter_state(2)[1] == 0      # the master ports were fed, the others were not
-    a.close()
-    b.close()
+    assert got_meters == want_meters
+
+
+# ragged lengths: no whole number of blocks, no multiple of 4.  With G = 17 a piece of the finish is 3 blocks, so the longest crosses two piece
+# boundaries and ends in a piece of 5 samples; with G = 1 every length is one piece.
+RAGGED_SHAPES = [(n, G) for n in (1, 3, 4, 5, 8191, 8193, 7 * BLOCK + 5) for G in (1, 17)]
+RAGGED = [(n, G, FORMATS[(3 * j + k) % 6], (j + k) % 2 == 0) for j, (n, G) in enumerate(RAGGED_SHAPES) for k in range(3)]
+
+
+def test_the_ragged_cases_cover_every_format_and_both_aux_forms_of_every_shape():
+    assert set(fmt for _, _, fmt, _ in RAGGED) == set(FORMATS)
+    for n, G in RAGGED_SHAPES:
+        assert set(aux for m, g, _, aux in RAGGED if (m, g) == (n, G)) == {False, True}
+
+
+def ragged_case(G, n, with_aux, seed):
+    """partials() of n samples; a length too short for what it plants takes the head of a longer case (samples beyond +-1 among them)
+    and, in its last sample, a sum far outside +-1 on both sides: the zeros behind a row's end cannot pass for the row's tail"""
+    rng = np.random.default_rng(seed)
+    m = max(n, 2048)
+    lefts, aux = partials(rng, G, m, with_aux)
+    rights, _ = partials(rng, G, m, False)
+    if aux is not None:                                              # as in finish_case
+        rights = [np.roll(r, m // 2) for r in rights]
+    lefts, rights = [r[:n].copy() for r in lefts], [r[:n].copy() for r in rights]
+    aux = aux[:n].copy() if aux is not None else None
+    if n < 4096:
+        for rows, v in ((lefts, 7.5), (rights, -7.5)):
+            for r in rows:
+                r[n - 1] = 0.0
+            rows[0][n - 1] = v                                       # the aux is within +-0.3
+    return lefts, rights, aux
+
+
+@pytest.mark.parametrize("i", range(len(RAGGED)), ids=["%d-G%d-%s-%s" % (n, G, fmt, "aux" if aux else "noaux") for n, G, fmt, aux in RAGGED])
+def test_finish_master_of_a_ragged_length(oracle, i):
+    n, G, fmt, with_aux = RAGGED[i]
+    lefts, rights, aux = ragged_case(G, n, with_aux, 9500 + i)
+    sums, expect = yardstick(oracle, fmt, lefts, rights, aux)
+    if n < 4096:
+        assert abs(sums[0][-1]) > 7 and abs(sums[1][-1]) > 7
+    finish_against_the_yardstick("batch_finish_master", fmt, lefts, rights, aux, sums, expect)
 
 
 @pytest.mark.parametrize("G,fmt", [(3, "lpcm24"), (8, "lpcm16"), (17, "ieee32"), (2, "ieee64")])
@@ -324,6 +396,8 @@ def test_finish_master_slice_refusals():
     with pytest.raises(pkg.GdgError, match="whole blocks") as e:
         ctx.batch_finish_master_slice("lpcm16", rows, rows)
     assert e.value.code == pkg.GDG_ERR_INVALID
+    left, right = ctx.batch_finish_master("lpcm16", rows, rows)     # the whole-job entry takes any length
+    assert left.size == right.size == (BLOCK + 4) * 2 and not left.any() and not right.any()
     with pytest.raises(pkg.GdgError, match="master meters"):
         ctx.batch_finish_master_slice("lpcm16", [np.zeros(BLOCK)], [np.zeros(BLOCK)], sample_rate=48000, run_meters=True)      # no ports configured
     ctx.close()
