@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "gdg_state_size", "gdg_state_save", "gdg_state_save_device", "gdg_state_load", "gdg_state_load_device",
     "gdg_batch_stream_checkpoint_size", "gdg_batch_stream_checkpoint", "gdg_batch_stream_resume", "gdg_batch_stream_resume_shard", "gdg_state_verify",
     "gdg_block_stats_rows", "gdg_block_stats_rows_device", "gdg_batch_report_enable", "gdg_batch_report", "gdg_batch_set_sources",
+    "gdg_batch_set_dither", "gdg_batch_dither_seek", "gdg_wave_encode_dither", "gdg_wave_encode_dither_device",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -245,6 +246,10 @@ def lib():
             "gdg_block_stats_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp]),
             "gdg_batch_report_enable": (i32, [vp, i32]),
             "gdg_batch_set_sources": (i32, [vp, vp, i32]),
+            "gdg_batch_set_dither": (i32, [vp, i32, C.c_uint64, u32]),
+            "gdg_batch_dither_seek": (i32, [vp, C.c_uint64]),
+            "gdg_wave_encode_dither": (i32, [vp, i32, vp, C.c_size_t, i32, C.c_uint64, u32, C.c_uint64, vp]),
+            "gdg_wave_encode_dither_device": (i32, [vp, i32, vp, C.c_size_t, i32, C.c_uint64, u32, C.c_uint64, vp]),
             "gdg_batch_report": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
@@ -1014,6 +1019,29 @@ class Context:
             return
         arr = (C.c_int * len(source))(*[int(v) for v in source])
         self._check(lib().gdg_batch_set_sources(self._h, arr, len(source)))
+
+    def batch_set_dither(self, mode, seed=0, port_base=0):
+        """The dither of the LPCM outputs of the next batch calls (gdg_batch_set_dither): mode 0 = off, 1 = TPDF with rounding; the noise of
+        a sample depends on (seed, port, sample index) alone; port_base = the job-wide index of this context's first channel.
+        Configuration: not in a checkpoint."""
+        self._check(lib().gdg_batch_set_dither(self._h, int(mode), int(seed), int(port_base)))
+
+    def batch_dither_seek(self, sample_index):
+        """The sample index the next batch_finish_master_slice starts at (gdg_batch_dither_seek)."""
+        self._check(lib().gdg_batch_dither_seek(self._h, int(sample_index)))
+
+    def wave_encode_dither(self, fmt, samples, mode=1, seed=0, port=0, first_index=0):
+        """A mono row of float64 -> bytes through the dithered encoder (gdg_wave_encode_dither); sample i has index first_index + i."""
+        f = WAVE_FORMATS[fmt] if isinstance(fmt, str) else fmt
+        x = _f64(samples).reshape(-1)
+        out = np.empty(x.size * max(lib().gdg_wave_bytes_per_sample(f), 1), dtype=np.uint8)
+        self._check(lib().gdg_wave_encode_dither(self._h, f, x.ctypes.data, x.size, int(mode), int(seed), int(port), int(first_index), out.ctypes.data))
+        return out
+
+    def wave_encode_dither_device(self, fmt, d_samples, n, d_bytes, mode=1, seed=0, port=0, first_index=0):
+        """gdg_wave_encode_dither_device on plain device pointers (ints), enqueued on the context's stream."""
+        f = WAVE_FORMATS[fmt] if isinstance(fmt, str) else fmt
+        self._check(lib().gdg_wave_encode_dither_device(self._h, f, d_samples, n, int(mode), int(seed), int(port), int(first_index), d_bytes))
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

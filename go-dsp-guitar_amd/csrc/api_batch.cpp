@@ -109,6 +109,8 @@ struct BatchLoop {
     double t_begin;
     size_t job_blocks, origin_blocks;           /* the slice of a job of job_blocks blocks that starts at block origin_blocks */
     bool report;                                /* the render report: a record per output row and block rides behind each step's bytes */
+    bool dither;                                /* the dithered encoders (gdg_batch_set_dither in force and an LPCM out_format) ... */
+    uint64_t dither_first;                      /* ... and the job's sample index of this loop's first sample */
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -243,11 +245,17 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, (unsigned)B, rec, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_stats(d_metro, ws, 1u, (size_t)wb, (unsigned)B, rec + (size_t)N * w, ctx->stream));
             }
-            if (!sharded) HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)NO, enc, ctx->stream));
+            /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
+            auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst) -> hipError_t {
+                if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
+                const gdg_dither_rows dz = { ctx->dither_seed, p.dither_first + off, port_base, n_chain };
+                return gdg_launch_wave_encode_rows_dither(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, dz, ctx->stream);
+            };
+            if (!sharded) HIP_TRY(ctx, encode_rows(d_win, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc));
             else {
-                HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_win, ws, (size_t)wb, (unsigned)N, enc, ctx->stream));
+                HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc));
                 if (shard->metronome_bytes)
-                    HIP_TRY(ctx, gdg_launch_wave_encode_rows(opt->out_format, d_metro, ws, (size_t)wb, 1u, enc + (size_t)N * row_bytes, ctx->stream));
+                    HIP_TRY(ctx, encode_rows(d_metro, 1u, 1u, GDG_DITHER_PORT_METRONOME, enc + (size_t)N * row_bytes));
                 unsigned char *f64 = enc + (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15);
                 HIP_TRY(ctx, hipMemcpy2DAsync(f64, (size_t)wb * sizeof(double), d_master, ws * sizeof(double), (size_t)wb * sizeof(double), 2,
                                               hipMemcpyDeviceToDevice, ctx->stream));
@@ -386,6 +394,27 @@ int gdg_batch_set_sources(gdg_ctx *ctx, const int *source, int n) {
                     bad, source[bad], source[source[bad]]);
     }
     ctx->batch_source.assign(source, source + n);
+    return GDG_OK;
+}
+
+/* the dither of the LPCM outputs: validated whole before it replaces the setting in force; read by every call that encodes */
+int gdg_batch_set_dither(gdg_ctx *ctx, int mode, uint64_t seed, uint32_t port_base) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set dither: a streamed batch run is open on this context; its setting holds until gdg_batch_stream_close");
+    if (mode != 0 && mode != 1) return fail(ctx, GDG_ERR_INVALID, "set dither: mode %d; 0 is off, 1 is TPDF", mode);
+    if (mode != 0 && !gdg_dither_ports_ok(port_base, ctx->nch))              /* off: port_base is not used and cannot be wrong */
+        return fail(ctx, GDG_ERR_INVALID, "set dither: port_base %u + %d channels reaches the job-wide ports from 0x%x on", port_base, ctx->nch, GDG_DITHER_PORT_MASTER_LEFT);
+    ctx->dither_mode = mode;
+    ctx->dither_seed = seed;
+    ctx->dither_port_base = port_base;
+    ctx->dither_cursor = 0;
+    return GDG_OK;
+}
+
+/* the master cursor belongs to gdg_batch_finish_master_slice, which is no part of an open job: it may be set while one is open */
+int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
+    if (!ctx) return GDG_ERR_INVALID;
+    ctx->dither_cursor = sample_index;
     return GDG_OK;
 }
 
@@ -718,7 +747,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             return GDG_OK;
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
-                        S.length / B, pos / B, report };
+                        S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos };
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -826,11 +855,11 @@ static int finish_master_check(gdg_ctx *ctx, int out_format, const double *const
  * apart, the gather writes the 0 .. 3 samples behind each row as zeros, the kernel runs over stride / 4 groups, and what it makes of the
  * pad stays on the device -- the meters, the report and the download take n samples. */
 static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
-                         size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+                         size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes, uint64_t dither_first) {
     const size_t width = (size_t)gdg_wave_bytes_per_sample(out_format), B = GDG_BLOCK_SIZE;
     report_begin(ctx, 2, (samples + B - 1) / B);
     if (samples == 0) return report_end(ctx, GDG_OK);
-    const bool report = ctx->report_live;
+    const bool report = ctx->report_live, dither = gdg_dither_applies(ctx->dither_mode, out_format);
     enter(ctx);
     const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0);
     /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the sample count and the shard count */
@@ -879,8 +908,12 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
             HIP_TRY(ctx, hipEventRecord(ctx->fin_up[h], ctx->stream));
             {
                 ProfScope ps(ctx, GDG_K_WAVE);
-                HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc, enc + piece * width,
-                                                      d_sums, piece, ctx->stream));
+                if (!dither)
+                    HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc, enc + piece * width,
+                                                          d_sums, piece, ctx->stream));
+                else                                                             /* the piece's first sample: dither_first + k * piece */
+                    HIP_TRY(ctx, gdg_launch_finish_master_dither(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc,
+                                                                 enc + piece * width, d_sums, piece, ctx->dither_seed, dither_first + k * piece, ctx->stream));
             }
             if (run_meters)
                 for (size_t o = 0; o < n; o += B)                                /* block by block, like the loop that fed the other ports */
@@ -934,7 +967,7 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
                             size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
-    return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes);
+    return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes, 0);      /* the cursor stays */
 }
 
 /* ... and of one slice of a streamed sharded job, where it runs once per slice on the job's critical path: whole blocks, as the slices are */
@@ -943,5 +976,11 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);
-    return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes);
+    /* the slice starts at the master cursor (gdg_batch_dither_seek) and a finished slice moves it on, dither on or off */
+    uint64_t next = ctx->dither_cursor + samples;
+    if (ctx->dither_mode && !gdg_dither_advance(ctx->dither_cursor, samples, &next))
+        return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples from sample index %llu on passes 2^64", samples, (unsigned long long)ctx->dither_cursor);
+    const int r = finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes, ctx->dither_cursor);
+    if (r == GDG_OK) ctx->dither_cursor = next;
+    return r;
 }

@@ -83,6 +83,42 @@ int gdg_wave_encode(gdg_ctx *ctx, int format, const double *samples, size_t per,
     return GDG_OK;
 }
 
+/* the dithered encoder on its own (dither.h): mono; mode 0 and the IEEE formats are gdg_wave_encode's calls, kernels and bytes */
+int gdg_wave_encode_dither_device(gdg_ctx *ctx, int format, const double *d_samples, size_t n, int mode, uint64_t seed, uint32_t port, uint64_t first_index,
+                                  void *d_bytes) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (!gdg_wave_bytes_per_sample(format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", format);
+    if (mode != 0 && mode != 1) return fail(ctx, GDG_ERR_INVALID, "encode dither: mode %d; 0 is off, 1 is TPDF", mode);
+    if (!gdg_dither_applies(mode, format)) return gdg_wave_encode_device(ctx, format, d_samples, n, 1, d_bytes);
+    if (n == 0) return GDG_OK;
+    if (!d_bytes || !d_samples) return GDG_ERR_INVALID;
+    if ((uintptr_t)d_samples & 7) return fail(ctx, GDG_ERR_INVALID, "encode dither: the samples are float64, 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    ProfScope ps(ctx, GDG_K_WAVE);
+    HIP_TRY(ctx, gdg_launch_wave_encode_dither(format, d_samples, n, d_bytes, seed, port, first_index, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_wave_encode_dither(gdg_ctx *ctx, int format, const double *samples, size_t n, int mode, uint64_t seed, uint32_t port, uint64_t first_index, void *bytes) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const int w = gdg_wave_bytes_per_sample(format);
+    if (!w) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", format);
+    if (mode != 0 && mode != 1) return fail(ctx, GDG_ERR_INVALID, "encode dither: mode %d; 0 is off, 1 is TPDF", mode);
+    if (!gdg_dither_applies(mode, format)) return gdg_wave_encode(ctx, format, samples, n, 1, bytes);
+    if (n == 0) return GDG_OK;
+    if (!bytes || !samples) return GDG_ERR_INVALID;
+    enter_keep_fir_sums(ctx);
+    int rc = ensure_io(ctx, 0, n * w);
+    if (rc == GDG_OK) rc = ensure_io(ctx, 1, n * sizeof(double));
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_io[1], samples, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_wave_encode_dither_device(ctx, format, static_cast<const double *>(ctx->d_io[1]), n, mode, seed, port, first_index, ctx->d_io[0]);
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(bytes, ctx->d_io[0], n * w, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
 /* resample/resample.go:72-87 */
 int gdg_resample_time_length(int input_length, uint32_t source_rate, uint32_t target_rate) {
     if (input_length < 0 || source_rate == 0 || target_rate == 0) return -1;

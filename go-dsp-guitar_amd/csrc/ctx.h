@@ -46,6 +46,7 @@
 
 #include "arena.h"
 #include "batch_sources.h"
+#include "dither.h"
 
 #define NUM_FILTERS 8
 
@@ -373,6 +374,11 @@ struct gdg_ctx {
     /* the source map (gdg_batch_set_sources; batch_sources.h): batch_source[c] = the channel whose input entry channel c reads, empty = every
      * channel its own.  Configuration like report_on: read when a job is described, in no blob. */
     std::vector<int> batch_source;
+    /* the dither of the LPCM outputs (gdg_batch_set_dither; dither.h): mode 0 = off, 1 = TPDF; the job-wide index of the context's first
+     * channel; the sample index the next gdg_batch_finish_master_slice starts at.  Configuration like the source map: in no blob. */
+    int dither_mode = 0;
+    uint64_t dither_seed = 0, dither_cursor = 0;
+    uint32_t dither_port_base = 0;
     /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;

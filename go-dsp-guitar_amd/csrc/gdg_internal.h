@@ -308,6 +308,19 @@ hipError_t gdg_launch_add_aux(double *d_a, double *d_b, const double *d_src, int
  * non-null: the float64 sums as well, left at d_sums, right at d_sums + sums_stride (the meters read them).  n a multiple of 4: a ragged piece comes with zeros up to the next one. */
 hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
                                     void *d_right_bytes, double *d_sums, size_t sums_stride, hipStream_t s);
+/* The dithered siblings of the three encoders above (dither.h; include/gdg.h, gdg_batch_set_dither): LPCM formats only -- the callers send
+ * every other call (dither off, IEEE32, IEEE64) to the plain launchers, which stay as they are.  A sample's noise depends on (seed, port,
+ * index) alone.  Rows: row r of the launch is sample `first` .. of port gdg_dither_row_port(port_base, n_chain, r). */
+struct gdg_dither_rows { unsigned long long seed, first; unsigned port_base, n_chain; };
+hipError_t gdg_launch_wave_encode_rows_dither(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
+                                              gdg_dither_rows dither, hipStream_t s);
+/* the master: left is port 0xfffffffd, right 0xfffffffe, the piece's first sample has index `first`; the sums (d_sums) are taken before the dither */
+hipError_t gdg_launch_finish_master_dither(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
+                                           void *d_right_bytes, double *d_sums, size_t sums_stride, unsigned long long seed, unsigned long long first,
+                                           hipStream_t s);
+/* mono, any 8-byte alignment of d_in and any byte alignment of d_bytes (unaligned buffers and n % 4 go one sample per thread) */
+hipError_t gdg_launch_wave_encode_dither(int fmt, const double *d_in, size_t n, void *d_bytes, unsigned long long seed, unsigned port,
+                                         unsigned long long first, hipStream_t s);
 hipError_t gdg_launch_metronome(const double *d_tick, unsigned n_tick, const double *d_tock, unsigned n_tock, double *d_out, int n,
                                 unsigned sc0, unsigned tc0, unsigned spb, unsigned beats, unsigned j0, hipStream_t s);
 /* the render report (include/gdg.h): one gdg_block_stats per block of `block` samples (the last of a row may be short) of n_rows rows of

@@ -7,6 +7,7 @@
  */
 #include "../../include/gdg.h"
 #include "gdg_internal.h"
+#include "dither.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -753,6 +754,196 @@ hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride
     case GDG_FMT_LPCM32: launch_finish_master<GDG_FMT_LPCM32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
     case GDG_FMT_IEEE32: launch_finish_master<GDG_FMT_IEEE32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
     case GDG_FMT_IEEE64: launch_finish_master<GDG_FMT_IEEE64>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * The dithered encoders (dither.h; include/gdg.h, gdg_batch_set_dither): TPDF dither with rounding for the four LPCM formats.  No reference
+ * counterpart.  The noise of a sample is a hash of (seed, port, index) -- one fmix per sample, two 64-bit multiplies, both 32-bit words
+ * used -- so the bytes of a file do not depend on the window, the slicing, the sharding or the launch shape.  Product and adds of the
+ * quantiser are __dmul_rn / __dadd_rn (dither.h): never contracted, the bits of the numpy restatement.  Loads, packing and the word-sized
+ * non-temporal stores are those of the plain kernels, which stay as they are and serve every call with dither off.
+ * ---------------------------------------------------------------------------------------------- */
+static_assert(GDG_DITHER_K == GDG_DIGEST_K && GDG_DITHER_M0 == GDG_DIGEST_M0 && GDG_DITHER_M1 == GDG_DIGEST_M1, "the dither hashes with the digest's constants");
+
+/* four consecutive samples of one port, the first at index `at`, into W whole words */
+template <int FMT>
+__device__ __forceinline__ void encode4_dither(const double (&r)[4], unsigned long long key, unsigned long long at, unsigned (&w)[fmt_width<FMT>::W]) {
+    constexpr int W = fmt_width<FMT>::W;
+#pragma unroll
+    for (int k = 0; k < W; k++) w[k] = 0;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const unsigned code = gdg_dither_code(FMT, r[s], key, at + (unsigned long long)s);
+#pragma unroll
+        for (int k = 0; k < W; k++) {
+            int byte = s * W + k;
+            w[byte >> 2] |= ((code >> (8 * k)) & 0xffu) << ((byte & 3) * 8);
+        }
+    }
+}
+
+/* wave_encode4_rows_kernel's sibling: blockIdx.y = row, whose port follows from the row number (uniform over the workgroup: the key is
+ * made on the scalar unit); sample i of every row has index dz.first + i */
+template <int FMT>
+__global__ void __launch_bounds__(256)
+wave_encode4_rows_dither_kernel(const double *__restrict__ in, size_t row_stride, size_t groups_per_row, unsigned *__restrict__ words, gdg_dither_rows dz) {
+    constexpr int W = fmt_width<FMT>::W;
+    const v2d *row = reinterpret_cast<const v2d *>(in + (size_t)blockIdx.y * row_stride);
+    unsigned *dst = words + (size_t)blockIdx.y * groups_per_row * W;
+    const unsigned long long key = gdg_dither_key(dz.seed, gdg_dither_row_port(dz.port_base, dz.n_chain, blockIdx.y));
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups_per_row; g += (size_t)gridDim.x * 256) {
+        v2d a = __builtin_nontemporal_load(row + 2 * g), b = __builtin_nontemporal_load(row + 2 * g + 1);
+        const double r[4] = { a.x, a.y, b.x, b.y };
+        unsigned w[W];
+        encode4_dither<FMT>(r, key, dz.first + 4ull * g, w);
+#pragma unroll
+        for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], dst + g * W + k);
+    }
+}
+
+template <int FMT>
+static void launch_encode_rows_dither(const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, unsigned char *p, gdg_dither_rows dz, hipStream_t s) {
+    size_t groups = row_len / 4;
+    unsigned tiles = (unsigned)((groups + 255) / 256);
+    wave_encode4_rows_dither_kernel<FMT><<<dim3(tiles, n_rows), dim3(256), 0, s>>>(d_in, row_stride, groups, reinterpret_cast<unsigned *>(p), dz);
+}
+
+hipError_t gdg_launch_wave_encode_rows_dither(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
+                                              gdg_dither_rows dz, hipStream_t s) {
+    if (n_rows == 0 || row_len == 0) return hipSuccess;
+    if ((row_len & 3) || (row_stride & 1) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_bytes & 3)) return hipErrorInvalidValue;
+    unsigned char *p = static_cast<unsigned char *>(d_bytes);
+    switch (fmt) {
+    case GDG_FMT_LPCM8: launch_encode_rows_dither<GDG_FMT_LPCM8>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
+    case GDG_FMT_LPCM16: launch_encode_rows_dither<GDG_FMT_LPCM16>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
+    case GDG_FMT_LPCM24: launch_encode_rows_dither<GDG_FMT_LPCM24>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
+    case GDG_FMT_LPCM32: launch_encode_rows_dither<GDG_FMT_LPCM32>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
+    default: return hipErrorInvalidValue;                      /* IEEE formats are never dithered: the plain launcher's */
+    }
+    return hipGetLastError();
+}
+
+/* finish_master_kernel's sibling: the same loads and the same adds in the same order; SUMS keeps the float64 sums for the meters and the
+ * report BEFORE the dither; the left side is port 0xfffffffd, the right 0xfffffffe, the piece's first sample has index `first` */
+template <int FMT, bool SUMS>
+__global__ void __launch_bounds__(256)
+finish_master_dither_kernel(const double *__restrict__ slab, size_t stride, int G, int has_aux, size_t groups, unsigned *__restrict__ words_left,
+                            unsigned *__restrict__ words_right, double *__restrict__ sums, size_t sums_stride, unsigned long long seed,
+                            unsigned long long first) {
+    constexpr int W = fmt_width<FMT>::W;
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= groups) return;
+    const size_t rs = stride / 2;                                  /* v2d per row */
+    const v2d *col = reinterpret_cast<const v2d *>(slab) + 2 * g;
+    v2d xa = { 0.0, 0.0 }, xb = { 0.0, 0.0 };
+    if (has_aux) { const v2d *q = col + (size_t)(2 * G) * rs; xa = __builtin_nontemporal_load(q); xb = __builtin_nontemporal_load(q + 1); }
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+        const v2d *p = col + (size_t)(side * G) * rs;
+        v2d a = __builtin_nontemporal_load(p), b = __builtin_nontemporal_load(p + 1);
+#pragma unroll 4
+        for (int k = 1; k < G; k++) {
+            p += rs;
+            a += __builtin_nontemporal_load(p);
+            b += __builtin_nontemporal_load(p + 1);
+        }
+        if (has_aux) { a += xa; b += xb; }
+        if (SUMS) {
+            v2d *out = reinterpret_cast<v2d *>(sums + (size_t)side * sums_stride) + 2 * g;
+            out[0] = a;
+            out[1] = b;
+        }
+        unsigned *words = side ? words_right : words_left;
+        if (!words) continue;
+        const unsigned long long key = gdg_dither_key(seed, side ? GDG_DITHER_PORT_MASTER_RIGHT : GDG_DITHER_PORT_MASTER_LEFT);
+        const double r[4] = { a.x, a.y, b.x, b.y };
+        unsigned w[W];
+        encode4_dither<FMT>(r, key, first + 4ull * g, w);
+#pragma unroll
+        for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], words + g * W + k);
+    }
+}
+
+template <int FMT>
+static void launch_finish_master_dither(const double *d_slab, size_t stride, int G, int has_aux, size_t n, void *d_left, void *d_right, double *d_sums,
+                                        size_t sums_stride, unsigned long long seed, unsigned long long first, hipStream_t s) {
+    const size_t groups = n / 4;
+    const unsigned grid = (unsigned)((groups + 255) / 256);
+    unsigned *wl = static_cast<unsigned *>(d_left), *wr = static_cast<unsigned *>(d_right);
+    if (d_sums) finish_master_dither_kernel<FMT, true><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride, seed, first);
+    else finish_master_dither_kernel<FMT, false><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, nullptr, 0, seed, first);
+}
+
+hipError_t gdg_launch_finish_master_dither(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
+                                           void *d_right_bytes, double *d_sums, size_t sums_stride, unsigned long long seed, unsigned long long first,
+                                           hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n_shards < 1 || (n & 3) || n > stride || (stride & 1) || (sums_stride & 1) || (d_sums && n > sums_stride) || ((uintptr_t)d_slab & 15) ||
+        ((uintptr_t)d_left_bytes & 15) || ((uintptr_t)d_right_bytes & 15) || ((uintptr_t)d_sums & 15))
+        return hipErrorInvalidValue;
+    switch (fmt) {
+    case GDG_FMT_LPCM8: launch_finish_master_dither<GDG_FMT_LPCM8>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
+    case GDG_FMT_LPCM16: launch_finish_master_dither<GDG_FMT_LPCM16>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
+    case GDG_FMT_LPCM24: launch_finish_master_dither<GDG_FMT_LPCM24>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
+    case GDG_FMT_LPCM32: launch_finish_master_dither<GDG_FMT_LPCM32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+/* the stand-alone mono form: wave_encode4_kernel's sibling for the aligned bulk ... */
+template <int FMT>
+__global__ void __launch_bounds__(256)
+wave_encode4_dither_kernel(const v2d *__restrict__ in, size_t groups, unsigned *__restrict__ words, unsigned long long key, unsigned long long first) {
+    constexpr int W = fmt_width<FMT>::W;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (size_t)gridDim.x * 256) {
+        v2d a = __builtin_nontemporal_load(in + 2 * g), b = __builtin_nontemporal_load(in + 2 * g + 1);
+        const double r[4] = { a.x, a.y, b.x, b.y };
+        unsigned w[W];
+        encode4_dither<FMT>(r, key, first + 4ull * g, w);
+#pragma unroll
+        for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], words + g * W + k);
+    }
+}
+
+/* ... and one sample per thread, byte stores: the n % 4 samples behind the bulk, or everything when a buffer is not aligned for it */
+template <int FMT>
+__global__ void __launch_bounds__(256)
+wave_encode_dither_tail_kernel(const double *__restrict__ in, size_t n, unsigned char *__restrict__ data, unsigned long long key, unsigned long long first) {
+    constexpr int W = fmt_width<FMT>::W;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const unsigned code = gdg_dither_code(FMT, in[i], key, first + (unsigned long long)i);
+#pragma unroll
+        for (int k = 0; k < W; k++) data[i * W + k] = (unsigned char)((code >> (8 * k)) & 0xffu);
+    }
+}
+
+template <int FMT>
+static void launch_encode_dither(const double *d_in, size_t n, unsigned char *p, unsigned long long key, unsigned long long first, hipStream_t s) {
+    size_t done = 0;
+    if (n >= 4 && ((uintptr_t)p & 3) == 0 && ((uintptr_t)d_in & 15) == 0) {
+        const size_t groups = n / 4;
+        wave_encode4_dither_kernel<FMT><<<(unsigned)((groups + 255) / 256), 256, 0, s>>>(reinterpret_cast<const v2d *>(d_in), groups, reinterpret_cast<unsigned *>(p), key, first);
+        done = groups * 4;
+    }
+    if (done < n)
+        wave_encode_dither_tail_kernel<FMT><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + done * fmt_width<FMT>::W, key, first + done);
+}
+
+hipError_t gdg_launch_wave_encode_dither(int fmt, const double *d_in, size_t n, void *d_bytes, unsigned long long seed, unsigned port,
+                                         unsigned long long first, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uintptr_t)d_in & 7) return hipErrorInvalidValue;
+    unsigned char *p = static_cast<unsigned char *>(d_bytes);
+    const unsigned long long key = gdg_dither_key(seed, port);
+    switch (fmt) {
+    case GDG_FMT_LPCM8: launch_encode_dither<GDG_FMT_LPCM8>(d_in, n, p, key, first, s); break;
+    case GDG_FMT_LPCM16: launch_encode_dither<GDG_FMT_LPCM16>(d_in, n, p, key, first, s); break;
+    case GDG_FMT_LPCM24: launch_encode_dither<GDG_FMT_LPCM24>(d_in, n, p, key, first, s); break;
+    case GDG_FMT_LPCM32: launch_encode_dither<GDG_FMT_LPCM32>(d_in, n, p, key, first, s); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

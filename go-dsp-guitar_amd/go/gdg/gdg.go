@@ -1315,3 +1315,39 @@ func (this *Context) BatchSetSources(source []int) error {
 	}
 	return this.err(C.gdg_batch_set_sources(this.ctx, &p[0], C.int(n)))
 }
+
+// Ports of the job-wide outputs under dither (gdg_batch_set_dither): a shard need not know the job's channel count.
+const (
+	DitherPortMasterLeft  = 0xfffffffd
+	DitherPortMasterRight = 0xfffffffe
+	DitherPortMetronome   = 0xffffffff
+)
+
+// BatchSetDither: the dither of the LPCM outputs of the next batch calls (gdg_batch_set_dither).  mode 0 is off, 1 is TPDF with
+// rounding; the noise of a sample depends on (seed, port, sample index) alone, so a file has the same bytes however the job is cut;
+// portBase is the job-wide index of this context's first channel (0 for an unsharded job).  Configuration, like the window: a
+// checkpoint does not carry it -- set it again on the target of a resume.  Resets the master cursor to 0.
+func (this *Context) BatchSetDither(mode int, seed uint64, portBase uint32) error {
+	return this.err(C.gdg_batch_set_dither(this.ctx, C.int(mode), C.uint64_t(seed), C.uint32_t(portBase)))
+}
+
+// BatchDitherSeek: the sample index the next FinishMasterSlice starts at (gdg_batch_dither_seek); a finished slice moves it on by its
+// samples.  A caller that resumes a sharded job from a checkpoint seeks to the samples done.
+func (this *Context) BatchDitherSeek(sampleIndex uint64) error {
+	return this.err(C.gdg_batch_dither_seek(this.ctx, C.uint64_t(sampleIndex)))
+}
+
+// WaveEncodeDither: one mono row through the dithered encoder (gdg_wave_encode_dither); sample i has index firstIndex + i.  mode 0, or an
+// IEEE format, gives WaveEncode's bytes.
+func (this *Context) WaveEncodeDither(format int, samples []float64, mode int, seed uint64, port uint32, firstIndex uint64) ([]byte, error) {
+	width := int(C.gdg_wave_bytes_per_sample(C.int(format)))
+	if width == 0 {
+		return nil, fmt.Errorf("gdg: unknown sample format %d", format)
+	}
+	data := make([]byte, len(samples)*width)
+	if len(samples) == 0 {
+		return data, nil
+	}
+	rc := C.gdg_wave_encode_dither(this.ctx, C.int(format), (*C.double)(unsafe.Pointer(&samples[0])), C.size_t(len(samples)), C.int(mode), C.uint64_t(seed), C.uint32_t(port), C.uint64_t(firstIndex), unsafe.Pointer(&data[0]))
+	return data, this.err(rc)
+}

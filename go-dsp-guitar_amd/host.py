@@ -46,6 +46,9 @@ def lib():
             "gdgh_engine_batch_stream_sharded_need": (cs, [vp, i32, vp, vp]), "gdgh_engine_batch_stream_sharded_step": (cs, [vp, i32, vp, vp]),
             "gdgh_engine_batch_stream_sharded_close": (cs, [vp]),
             "gdgh_engine_set_batch_report": (None, [vp, i32]),
+            "gdgh_engine_set_batch_dither": (None, [vp, i32, C.c_uint64]),
+            "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+            "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
             "gdgh_engine_last_batch_report": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
@@ -205,13 +208,19 @@ class Engine:
         arr = (C.c_int * len(source))(*[int(v) for v in source])
         _err(lib().gdgh_engine_set_batch_sources(self._h, arr, len(source)))
 
+    def _set_dither(self, seed):
+        """Engine::SetBatchDither, from the `dither` argument of the batch calls: TPDF dither of the job's LPCM outputs with this seed
+        (None: off); every shard gets its port_base from the engine, so the files do not depend on the shard count."""
+        lib().gdgh_engine_set_batch_dither(self._h, 0 if seed is None else 1, 0 if seed is None else int(seed))
+
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False):
+                  report=False, dither=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
+        self._set_dither(dither)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -245,32 +254,43 @@ class Engine:
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False):
+                     report=False, dither=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces.  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue, report)
+                                  metronome_to_master, run_meters, tuner_enqueue, report, dither)
+
+    def batch_stream_sharded_checkpoint(self):
+        """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        _err(lib().gdgh_engine_batch_stream_sharded_checkpoint(self._h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            lib().gdgh_free(p)
 
     def batch_stream_sharded(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False,
-                             tuner_enqueue=False, report=False):
+                             tuner_enqueue=False, report=False, dither=None, resume=None):
         """Engine::BatchStreamShardedOpen / Need / Step / Close: batch_stream for an engine of any shard count -- every shard streams its
         channels, the master is finished per slice; yields every slice's N + 3 output pieces (blocks_per_slice: an int or a function
         (blocks_left) -> blocks).  report: as batch_stream's -- the chain rows come from the shards, the master from the finish, the
-        metronome from shard 0."""
+        metronome from shard 0.  resume: a blob of batch_stream_sharded_checkpoint -- Engine::BatchStreamShardedResume in the place of the
+        Open call (same inputs and options, set up again on this engine); the slices go on where the checkpoint was taken."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
                                    L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
-                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report)
+                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report, dither, resume)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False):
+                      report=False, dither=None, resume=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
+        self._set_dither(dither)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -286,10 +306,18 @@ class Engine:
         fo = pkg.WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
         opt = pkg.BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
         wo = pkg.lib().gdg_wave_bytes_per_sample(fo)
-        samples = C.c_size_t(0)
-        _err(f_open(self._h, arr, n, C.byref(opt), window, C.byref(samples)))
+        samples, done = C.c_size_t(0), C.c_size_t(0)
+        if resume is None:
+            _err(f_open(self._h, arr, n, C.byref(opt), window, C.byref(samples)))
+        else:                                                # the job's length as the Open call computes it: the longest shard's
+            for g in range(self.shards()):
+                first, count = self.shard_range(g)
+                if count > 0:
+                    samples.value = max(samples.value, self.raw_context(g).batch_length(inputs[first:first + count], target_rate))
+            blob = bytes(resume)
+            _err(lib().gdgh_engine_batch_stream_sharded_resume(self._h, arr, n, C.byref(opt), window, blob, len(blob), C.byref(done)))
         try:
-            left = samples.value // 8192
+            left = (samples.value - done.value) // 8192
             first, count = (C.c_size_t * n)(), (C.c_size_t * n)()
             while left:
                 blocks = min(left, blocks_per_slice(left) if callable(blocks_per_slice) else blocks_per_slice)

@@ -914,6 +914,13 @@ int Engine::applySources(int shard, gdg_ctx *ctx) {
     return gdg_batch_set_sources(ctx, local.data(), count);
 }
 
+/* port_base = the job-wide index of the shard's first channel; also resets the context's master cursor */
+int Engine::applyDither(int shard, gdg_ctx *ctx) {
+    int first = 0, count = 0;
+    shardRange(shard, &first, &count);
+    return gdg_batch_set_dither(ctx, dither_ ? 1 : 0, ditherSeed_, dither_ ? (uint32_t)first : 0u);
+}
+
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
  * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
  * controller.go:3005-3045). */
@@ -935,7 +942,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1067,7 +1074,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1276,7 +1283,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1370,6 +1377,10 @@ Error Engine::BatchStreamShardedResume(const gdg_batch_input *inputs, int nInput
             setError(e);
             return e;
         }
+    }
+    if (have) {                                          /* the master's slices go on where the job stands (the dither's sample index) */
+        std::lock_guard<std::mutex> lk(shards_[0]->mu);
+        if (shards_[0]->ctx) (void)gdg_batch_dither_seek(shards_[0]->ctx, (uint64_t)done);
     }
     shardedOpen_ = true;
     shardedOptions_ = options;
@@ -1581,6 +1592,7 @@ const char *gdgh_engine_batch_run(void *e, const gdg_batch_input *inputs, int n,
 const char *gdgh_engine_set_batch_sources(void *e, const int *source, int n) {
     return ret(((Engine *)e)->SetBatchSources(source && n > 0 ? std::vector<int>(source, source + n) : std::vector<int>()));
 }
+void gdgh_engine_set_batch_dither(void *e, int on, uint64_t seed) { ((Engine *)e)->SetBatchDither(seed, on != 0); }
 void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchReport(on != 0); }
 /* records == NULL: the two counts only */
 const char *gdgh_engine_last_batch_report(void *e, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks) {
@@ -1615,6 +1627,21 @@ const char *gdgh_engine_batch_stream_sharded_step(void *e, int blocks, const voi
     return ret(((Engine *)e)->BatchStreamShardedStep(blocks, ins, outs));
 }
 const char *gdgh_engine_batch_stream_sharded_close(void *e) { return ret(((Engine *)e)->BatchStreamShardedClose()); }
+/* *blob: malloc'ed (gdgh_free) */
+const char *gdgh_engine_batch_stream_sharded_checkpoint(void *e, void **blob, size_t *bytes) {
+    std::vector<uint8_t> b;
+    Error err = ((Engine *)e)->BatchStreamShardedCheckpoint(b);
+    *blob = nullptr; *bytes = 0;
+    if (!err.empty()) return ret(err);
+    *blob = malloc(b.size() ? b.size() : 1);
+    memcpy(*blob, b.data(), b.size());
+    *bytes = b.size();
+    return nullptr;
+}
+const char *gdgh_engine_batch_stream_sharded_resume(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, const void *blob,
+                                                    size_t bytes, size_t *samples_done) {
+    return ret(((Engine *)e)->BatchStreamShardedResume(inputs, n, *opt, window, static_cast<const uint8_t *>(blob), bytes, samples_done));
+}
 void *gdgh_engine_context(void *e, int shard) { return ((Engine *)e)->context(shard); }
 void gdgh_engine_shard_range(void *e, int shard, int *first, int *count) { ((Engine *)e)->shardRange(shard, first, count); }
 void *gdgh_engine_create_sharded(int n_channels, int max_frames, const int *devices, int n_devices) {

@@ -251,6 +251,11 @@ public:
      * up (BatchRun, the Open and Resume calls).  A map spans one context: a reader whose root lives on another shard is refused here,
      * with a message, and the map in force stays. */
     Error SetBatchSources(const std::vector<int> &source);
+    /* No reference counterpart.  Dither of the LPCM outputs (include/gdg.h, gdg_batch_set_dither): TPDF with rounding, the noise of a sample
+     * a function of (seed, port, sample index) alone.  The engine gives every shard the job-wide index of its first channel as port_base when
+     * a job is set up (BatchRun, the Open and Resume calls) and keeps the master cursor over the slices of a sharded streamed job (a resumed
+     * one seeks to the samples done): an engine of any shard count writes the files of one shard.  on = false: the plain encoders. */
+    void SetBatchDither(uint64_t seed, bool on = true) { dither_ = on; ditherSeed_ = seed; }
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -295,6 +300,9 @@ private:
     std::vector<gdg_block_stats> lastReport_;
     std::vector<int> sources_;                             /* the source map in job channel numbers; empty: none */
     int applySources(int shard, gdg_ctx *ctx);             /* the shard's part of it onto its context: a gdg_* status */
+    bool dither_ = false;                                  /* SetBatchDither: on, and the seed */
+    uint64_t ditherSeed_ = 0;
+    int applyDither(int shard, gdg_ctx *ctx);              /* mode, seed and the shard's port_base onto its context: a gdg_* status */
     void reportBegin(size_t blocks);
     Error reportOfShard(int shard, gdg_ctx *ctx);
     Error reportOfMaster(gdg_ctx *ctx);

@@ -776,6 +776,53 @@ int gdg_batch_report(gdg_ctx *ctx, gdg_block_stats *records, size_t capacity, in
  * call.  Options stat_batch_upload_bytes and stat_batch_resampled_samples read what the last call moved and resampled.
  */
 int gdg_batch_set_sources(gdg_ctx *ctx, const int *source, int n);
+/*
+ * DITHER: no reference counterpart.  samplesToBytes (and gdg_wave_encode, which restates it) scales and TRUNCATES TOWARD ZERO: the zero code
+ * is two steps wide, everything below one code vanishes, and the error follows the signal.  With dither in force the four LPCM formats of
+ * a batch call are written with TPDF dither and rounding instead; IEEE32 and IEEE64 outputs are never dithered and keep their bytes.
+ * The noise of a sample depends on (seed, port, absolute sample index) alone, so a file comes out byte for byte the same whatever the
+ * window, the slicing, the sharding, a checkpoint / resume in between or a source map.  All integer arithmetic modulo 2^64; K, M0, M1 and
+ * fmix are the checkpoint digest's (above):
+ *   key = fmix(seed + (port + 1) K)                once per row
+ *   h   = fmix((index + K) ^ key)                  index: 64-bit sample index within the job, 0 = first sample of the file
+ *   a   = h >> 32,  b = h & 0xffffffff
+ *   d   = (double)((int64)a - (int64)b) * 2^-32    triangular on (-1, 1) codes; exact in float64
+ *   t   = S * clamp1(x)                            S = 127, 32767.5, 8388607.5, 2147483647.5: the plain encoder's constants
+ *   q   = floor((t + d) + 0.5)                     the product and the two adds each rounded on their own (no fused multiply-add)
+ *   code = clamp(q, the format's range)            LPCM8: + 128 afterwards, clamped to 0 .. 255
+ * Known answers (seed, port, index, x -> h, LPCM16 code, LPCM24 code):
+ *   0x0, 0, 0, 0.0 -> 0xdf9545e13007448a, 1, 1          0x63, 3, 8192, 1e-5 -> 0x33a34e84d34b5c4b, 0, 83
+ *   0x3039, 7, 0x100000000, -0.7 -> 0xe8f8277b0aa97796, -22936, -5872024
+ * NaN and infinities: whatever the conversion gives; not specified.
+ * PORTS: chain output c of a context is port port_base + c, port_base = the job-wide index of the context's first channel (0 for an
+ * unsharded job).  The job-wide outputs have fixed ports, so a shard need not know the job's channel count: master left 0xfffffffd,
+ * master right 0xfffffffe, metronome 0xffffffff.  port_base + the context's channel count stays below 0xfffffffd.
+ * INDEX: a sample's position in the job.  gdg_batch_run and gdg_batch_run_shard start at 0; a slice of a streamed job starts at the job's
+ * position, which gdg_batch_stream_resume and _resume_shard restore.  gdg_batch_finish_master starts at 0 and leaves the master cursor
+ * alone; gdg_batch_finish_master_slice starts at the context's master cursor and, when it returns GDG_OK, advances it by its `samples`.
+ *   gdg_batch_set_dither(ctx, mode, seed, port_base)   mode 0 = off, 1 = TPDF as above; anything else is GDG_ERR_INVALID (gdg_last_error
+ *                                                      says so) and the setting in force stays; so does a port_base out of range (mode 1), and
+ *                                                      a call while a streamed job is open.  Resets the master cursor to 0.
+ *   gdg_batch_dither_seek(ctx, sample_index)           the sample index the next gdg_batch_finish_master_slice starts at (a caller that
+ *                                                      resumes a sharded job from a checkpoint seeks to samples_done).  The cursor is no
+ *                                                      part of a streamed job: it may be set while one is open.
+ * Configuration, like gdg_batch_report_enable and gdg_batch_set_sources: it holds from the next batch call on, survives batch calls and is
+ * part of no blob (the checkpoint container stays version 1) -- set it again on the target of a resume.  The render report is taken from
+ * the float64 rows, before the dither: its records are the same with dither on and off; so are the meters, and a NULL in out_bytes
+ * changes nothing else.  Off -- never set, or mode 0 -- no launch, allocation, upload or byte differs from a context that never heard of
+ * the call.  No noise shaping: error feedback is a serial recurrence per port that would carry state across slices.
+ * The encoder on its own, mono, for callers with their own buffers:
+ *   gdg_wave_encode_dither(ctx, format, samples, n, mode, seed, port, first_index, bytes)            host buffers, blocking
+ *   gdg_wave_encode_dither_device(ctx, format, d_samples, n, mode, seed, port, first_index, d_bytes) enqueued on gdg_ctx_stream; any
+ *                                                      8-byte alignment of d_samples, any byte alignment of d_bytes
+ * sample i of the buffer has index first_index + i.  mode 0, or an IEEE format, gives gdg_wave_encode's bytes.
+ */
+int gdg_batch_set_dither(gdg_ctx *ctx, int mode, uint64_t seed, uint32_t port_base);
+int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index);
+int gdg_wave_encode_dither(gdg_ctx *ctx, int format, const double *samples, size_t n, int mode, uint64_t seed, uint32_t port, uint64_t first_index,
+                           void *bytes);
+int gdg_wave_encode_dither_device(gdg_ctx *ctx, int format, const double *d_samples, size_t n, int mode, uint64_t seed, uint32_t port,
+                                  uint64_t first_index, void *d_bytes);
 
 #ifdef __cplusplus
 
