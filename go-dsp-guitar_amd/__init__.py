@@ -48,12 +48,29 @@ ABI_SYMBOLS = [
     "gdg_batch_stream_checkpoint_size", "gdg_batch_stream_checkpoint", "gdg_batch_stream_resume", "gdg_batch_stream_resume_shard", "gdg_state_verify",
     "gdg_block_stats_rows", "gdg_block_stats_rows_device", "gdg_batch_report_enable", "gdg_batch_report", "gdg_batch_set_sources",
     "gdg_batch_set_dither", "gdg_batch_dither_seek", "gdg_wave_encode_dither", "gdg_wave_encode_dither_device",
+    "gdg_block_spectrum_rows", "gdg_block_spectrum_rows_device", "gdg_batch_spectrum_enable", "gdg_batch_spectrum",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
 BLOCK_STATS_DTYPE = np.dtype([("peak", "<f8"), ("sum_sq", "<f8"), ("peak_index", "<u4"), ("clipped", "<u4"), ("full_scale", "<u4"),
                               ("nonfinite", "<u4")])
 assert BLOCK_STATS_DTYPE.itemsize == 32
+
+SPECTRUM_BLOCK = 8192        # the band spectrum's block = its transform (include/gdg.h)
+SPECTRUM_MAX_EDGES = 33
+
+
+def spectrum_edges(edges):
+    """An edge list of the band spectrum as a float64 array, refused here as gdg_batch_spectrum_enable refuses it: 2 to 33 edges, finite,
+    >= 0, strictly ascending."""
+    e = np.array(edges, dtype=np.float64).reshape(-1)
+    if e.size < 2 or e.size > SPECTRUM_MAX_EDGES:
+        raise ValueError("%d edges; 2 to %d make 1 to %d bands" % (e.size, SPECTRUM_MAX_EDGES, SPECTRUM_MAX_EDGES - 1))
+    if not np.all(np.isfinite(e)) or np.any(e < 0):
+        raise ValueError("an edge is a finite frequency >= 0")
+    if np.any(np.diff(e) <= 0):
+        raise ValueError("edges ascend strictly")
+    return e
 
 
 def option_names():
@@ -251,6 +268,10 @@ def lib():
             "gdg_wave_encode_dither": (i32, [vp, i32, vp, C.c_size_t, i32, C.c_uint64, u32, C.c_uint64, vp]),
             "gdg_wave_encode_dither_device": (i32, [vp, i32, vp, C.c_size_t, i32, C.c_uint64, u32, C.c_uint64, vp]),
             "gdg_batch_report": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdg_block_spectrum_rows": (i32, [vp, vp, i32, C.c_size_t, C.c_uint32, vp, i32, vp]),
+            "gdg_block_spectrum_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, C.c_uint32, vp, i32, vp]),
+            "gdg_batch_spectrum_enable": (i32, [vp, vp, i32]),
+            "gdg_batch_spectrum": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t), C.POINTER(i32)]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
             "gdg_ctx_get_option": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -1049,6 +1070,46 @@ class Context:
         self._check(lib().gdg_batch_report(self._h, None, 0, C.byref(ports), C.byref(blocks)))
         out = np.zeros((ports.value, blocks.value), dtype=BLOCK_STATS_DTYPE)
         self._check(lib().gdg_batch_report(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
+    # -- the band spectrum: the power per output port, block of 8192 samples and frequency band (include/gdg.h) ------------------------------
+    def block_spectrum(self, rows, sample_rate, edges):
+        """rows: a [n_rows][samples] float64 array or a list of equally long 1-D arrays; returns the [n_rows][ceil(samples / 8192)][bands]
+        float64 array of gdg_block_spectrum_rows for the len(edges) - 1 bands between the edges (Hz)."""
+        e = spectrum_edges(edges)
+        if int(sample_rate) <= 0:
+            raise ValueError("sample rate must be positive")
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        out = np.zeros((n, -(-samples // SPECTRUM_BLOCK), e.size - 1), dtype=np.float64)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_spectrum_rows(self._h, ptrs, n, samples, int(sample_rate), e.ctypes.data, e.size, out.ctypes.data if out.size else None))
+        return out
+
+    def block_spectrum_device(self, d_rows, row_stride, n_rows, samples, sample_rate, edges, d_bands):
+        """gdg_block_spectrum_rows_device on plain device pointers (ints), enqueued on the context's stream; the edges are host values."""
+        e = spectrum_edges(edges)
+        self._check(lib().gdg_block_spectrum_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(sample_rate), e.ctypes.data, e.size, d_bands))
+
+    def batch_spectrum_enable(self, edges):
+        """From the next batch call on, every batch call keeps the band powers of what it rendered, for the bands between `edges` (Hz) at the
+        job's rate; None (or an empty list) switches it off.  Configuration: not in a checkpoint, refused while a streamed job is open."""
+        if edges is None or len(edges) == 0:
+            self._check(lib().gdg_batch_spectrum_enable(self._h, None, 0))
+            return
+        e = spectrum_edges(edges)
+        self._check(lib().gdg_batch_spectrum_enable(self._h, e.ctypes.data, e.size))
+
+    def batch_spectrum(self):
+        """The [ports][blocks][bands] float64 band powers of the last completed batch call; GdgError when there is none."""
+        ports, blocks, bands = C.c_int(0), C.c_size_t(0), C.c_int(0)
+        self._check(lib().gdg_batch_spectrum(self._h, None, 0, C.byref(ports), C.byref(blocks), C.byref(bands)))
+        out = np.zeros((ports.value, blocks.value, bands.value), dtype=np.float64)
+        self._check(lib().gdg_batch_spectrum(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks), C.byref(bands)))
         return out
 
     def metronome_process(self, frames):

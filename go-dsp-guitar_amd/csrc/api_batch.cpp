@@ -111,6 +111,7 @@ struct BatchLoop {
     bool report;                                /* the render report: a record per output row and block rides behind each step's bytes */
     bool dither;                                /* the dithered encoders (gdg_batch_set_dither in force and an LPCM out_format) ... */
     uint64_t dither_first;                      /* ... and the job's sample index of this loop's first sample */
+    const gdg_spectrum_bands *bands;            /* the band spectrum: n_bands doubles per output row and block ride behind the records; null = off */
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -177,6 +178,14 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NO;
     auto rec_at = [&](size_t i) { return (down_bytes(i) + 15) & ~(size_t)15; };
     auto rec_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_stats); };
+    /* ... and with the band spectrum the step's bands, [rows][w][n_bands], at the next 16 bytes behind the records (behind the rows when the
+     * report is off): they come down with the last piece too */
+    const size_t n_bands = p.bands ? (size_t)p.bands->n_bands : 0;
+    auto spec_at = [&](size_t i) { return ((p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i)) + 15) & ~(size_t)15; };
+    auto spec_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * n_bands * sizeof(double); };
+    const double *spec_win = nullptr;
+    double2 *spec_tw = nullptr, *spec_tw2 = nullptr;
+    if (p.bands && (r = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2)) != GDG_OK) return r;
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
     auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
@@ -204,6 +213,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
             const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;      /* a shard without the metronome: that row stays zero */
             for (size_t o = 0; o < rows; o++) memcpy(&ctx->report[o * ctx->report_blocks + b0], rec + o * w, w * sizeof(gdg_block_stats));
+        }
+        if (p.bands) {                                                       /* ... and the step's bands, filed under the step's blocks */
+            const double *sp = reinterpret_cast<const double *>(src + spec_at(i));
+            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
+            const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;
+            for (size_t o = 0; o < rows; o++) memcpy(&ctx->spectrum[(o * ctx->spec_blocks + b0) * n_bands], sp + o * w * n_bands, w * n_bands * sizeof(double));
         }
         return GDG_OK;
     };
@@ -245,6 +260,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, (unsigned)B, rec, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_stats(d_metro, ws, 1u, (size_t)wb, (unsigned)B, rec + (size_t)N * w, ctx->stream));
             }
+            if (p.bands) {                                                   /* the same rows, one more reader */
+                double *sp = reinterpret_cast<double *>(enc + spec_at(i));
+                HIP_TRY(ctx, gdg_launch_block_spectrum(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp, ctx->stream));
+                if (sharded && run_metro)
+                    HIP_TRY(ctx, gdg_launch_block_spectrum(d_metro, ws, 1u, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp + (size_t)N * w * n_bands, ctx->stream));
+            }
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst) -> hipError_t {
                 if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
@@ -272,7 +293,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i);
+        const size_t down = p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i);
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -578,7 +599,11 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const bool report = ctx->report_live;
     /* with the render report a half also holds a window's records behind its rows (batch_block_loop: rec_at) */
     const size_t rec_room = report ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_stats) : 0;
-    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room;
+    /* ... and with the band spectrum a window's bands behind those (spec_at) */
+    const bool spectrum = !ctx->spec_live_edges.empty();
+    const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), opt->target_rate) : gdg_spectrum_bands();
+    const size_t spec_room = spectrum ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * (size_t)bands.n_bands * sizeof(double) : 0;
+    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room + spec_room;
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -747,7 +772,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             return GDG_OK;
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
-                        S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos };
+                        S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, spectrum ? &bands : nullptr };
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -858,15 +883,24 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
                          size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes, uint64_t dither_first) {
     const size_t width = (size_t)gdg_wave_bytes_per_sample(out_format), B = GDG_BLOCK_SIZE;
     report_begin(ctx, 2, (samples + B - 1) / B);
+    if (!ctx->spec_live_edges.empty() && sample_rate == 0)                       /* like every refusal from here on: the call before's report and spectrum are gone */
+        return report_end(ctx, fail(ctx, GDG_ERR_INVALID, "master mix: the band spectrum needs a positive sample rate"));
     if (samples == 0) return report_end(ctx, GDG_OK);
-    const bool report = ctx->report_live, dither = gdg_dither_applies(ctx->dither_mode, out_format);
+    const bool report = ctx->report_live, dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = !ctx->spec_live_edges.empty();
     enter(ctx);
+    const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), sample_rate) : gdg_spectrum_bands();
+    const size_t n_bands = spectrum ? (size_t)bands.n_bands : 0;
+    const double *spec_win = nullptr;
+    double2 *spec_tw = nullptr, *spec_tw2 = nullptr;
+    if (spectrum) { const int rs = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2); if (rs != GDG_OK) return report_end(ctx, rs); }
     const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0);
     /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the sample count and the shard count */
     const size_t piece = B * std::min((size_t)128, std::max((size_t)1, ((size_t)8 << 20) / ((2 * G + 1) * B * sizeof(double))));
     /* the render report: a piece's records, [2][piece / 8192], come down behind its encoded rows */
     const size_t rec_off = 2 * piece * width, rec_bytes = report ? 2 * (piece / B) * sizeof(gdg_block_stats) : 0;
-    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = rec_off + rec_bytes;
+    /* ... and the band spectrum: a piece's bands, [2][piece / 8192][n_bands], behind those */
+    const size_t spec_off = rec_off + rec_bytes, spec_bytes = 2 * (piece / B) * n_bands * sizeof(double);
+    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = spec_off + spec_bytes;
     if (!ctx->fin_up[0])
         for (int h = 0; h < 2; h++) {
             HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
@@ -879,7 +913,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
     if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * down_bytes);
     if (rc != GDG_OK) return rc;
     unsigned char *d_slab = static_cast<unsigned char *>(ctx->d_io[1]), *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
-    double *d_sums = (run_meters || report) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
+    double *d_sums = (run_meters || report || spectrum) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
     const size_t n_pieces = (samples + piece - 1) / piece;
     auto span = [&](size_t k) { return std::min(piece, samples - k * piece); };
     auto stride_of = [](size_t n) { return (n + 3) & ~(size_t)3; };                /* <= piece: a piece is whole blocks */
@@ -922,6 +956,10 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
                 HIP_TRY(ctx, gdg_launch_block_stats(d_sums, piece, 2u, n, (unsigned)B, enc + rec_off, ctx->stream));
                 HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + rec_off, enc + rec_off, 2 * nb * sizeof(gdg_block_stats), hipMemcpyDeviceToHost, ctx->stream));
             }
+            if (spectrum) {                                                  /* the same sums; a short last block is zero-padded by the kernel */
+                HIP_TRY(ctx, gdg_launch_block_spectrum(d_sums, piece, 2u, n, spec_win, spec_tw, spec_tw2, bands, reinterpret_cast<double *>(enc + spec_off), ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + spec_off, enc + spec_off, 2 * nb * n_bands * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            }
             /* the download of piece k - 2 into this pinned half has been scattered: scatter(k - 2) ran before enqueue(k) */
             if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * width, hipMemcpyDeviceToHost, ctx->stream));
             if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + piece * width, enc + piece * width, n * width, hipMemcpyDeviceToHost, ctx->stream));
@@ -945,6 +983,12 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
                 const size_t nb = (span(k) + B - 1) / B;
                 for (size_t side = 0; side < 2; side++)
                     memcpy(&ctx->report[side * ctx->report_blocks + k * (piece / B)], rec + side * nb, nb * sizeof(gdg_block_stats));
+            }
+            if (spectrum) {
+                const double *sp = reinterpret_cast<const double *>(ctx->h_fin_down[h] + spec_off);
+                const size_t nb = (span(k) + B - 1) / B;
+                for (size_t side = 0; side < 2; side++)
+                    memcpy(&ctx->spectrum[(side * ctx->spec_blocks + k * (piece / B)) * n_bands], sp + side * nb * n_bands, nb * n_bands * sizeof(double));
             }
             return GDG_OK;
         };

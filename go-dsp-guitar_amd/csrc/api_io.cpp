@@ -491,3 +491,114 @@ int gdg_batch_report(gdg_ctx *ctx, gdg_block_stats *records, size_t capacity, in
     if (n) memcpy(records, ctx->report.data(), n * sizeof(gdg_block_stats));
     return GDG_OK;
 }
+
+/* ---- the band spectrum (include/gdg.h; the kernel: spectrum_kernels.h in fir.hip; the edges and bins: spectrum_bands.h; the batch calls fill it: api_batch.cpp) ---- */
+int spectrum_tables(gdg_ctx *ctx, const double **win, double2 **tw, double2 **tw2) {
+    if (!ctx->d_spec_win) {
+        std::vector<double> w((size_t)GDG_SPECTRUM_BLOCK);
+        spectrum_window(w.data());
+        double *d = nullptr;
+        HIP_TRY(ctx, hipMalloc((void **)&d, w.size() * sizeof(double)));
+        const hipError_t e = hipMemcpy(d, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(d); HIP_TRY(ctx, e); }
+        ctx->d_spec_win = d;
+    }
+    *win = ctx->d_spec_win;
+    return fir_tables(ctx, GDG_SPECTRUM_BLOCK / 2, tw, tw2);
+}
+
+static int spectrum_edges_refuse(gdg_ctx *ctx, const char *what, const double *edges_hz, int n_edges) {
+    int bad = -1;
+    switch (spectrum_edges_check(edges_hz, n_edges, &bad)) {
+    case SPECTRUM_OK: return GDG_OK;
+    case SPECTRUM_COUNT: return fail(ctx, GDG_ERR_INVALID, "%s: %d edges; 2 to %d make 1 to %d bands", what, n_edges, GDG_SPECTRUM_MAX_EDGES, GDG_SPECTRUM_MAX_EDGES - 1);
+    case SPECTRUM_NULL: return fail(ctx, GDG_ERR_INVALID, "%s: no edge list", what);
+    case SPECTRUM_VALUE: return fail(ctx, GDG_ERR_INVALID, "%s: edge %d is not a finite frequency >= 0", what, bad);
+    default: return fail(ctx, GDG_ERR_INVALID, "%s: edge %d does not lie above edge %d (strictly ascending)", what, bad, bad - 1);
+    }
+}
+
+static int block_spectrum_check(gdg_ctx *ctx, int n_rows, size_t samples, uint32_t sample_rate, const double *edges_hz, int n_edges, size_t *blocks) {
+    if (n_rows < 0) return fail(ctx, GDG_ERR_INVALID, "block spectrum: %d rows", n_rows);
+    if (sample_rate == 0) return fail(ctx, GDG_ERR_INVALID, "block spectrum: sample rate must be positive");
+    const int rc = spectrum_edges_refuse(ctx, "block spectrum", edges_hz, n_edges);
+    if (rc != GDG_OK) return rc;
+    *blocks = (samples + GDG_SPECTRUM_BLOCK - 1) / GDG_SPECTRUM_BLOCK;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block spectrum: %zu blocks per row are too many for one launch", *blocks);
+    return GDG_OK;
+}
+
+int gdg_block_spectrum_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, uint32_t sample_rate,
+                                   const double *edges_hz, int n_edges, double *d_bands) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    int rc = block_spectrum_check(ctx, n_rows, samples, sample_rate, edges_hz, n_edges, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_rows == 0 || samples == 0) return GDG_OK;
+    if (!d_rows || !d_bands) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block spectrum: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_bands & 7)) return fail(ctx, GDG_ERR_INVALID, "block spectrum: rows and bands are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    const double *win = nullptr;
+    double2 *tw = nullptr, *tw2 = nullptr;
+    if ((rc = spectrum_tables(ctx, &win, &tw, &tw2)) != GDG_OK) return rc;
+    HIP_TRY(ctx, gdg_launch_block_spectrum(d_rows, row_stride, (unsigned)n_rows, samples, win, tw, tw2, spectrum_bands(edges_hz, n_edges, sample_rate), d_bands, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_block_spectrum_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, uint32_t sample_rate, const double *edges_hz, int n_edges,
+                            double *bands) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    int rc = block_spectrum_check(ctx, n_rows, samples, sample_rate, edges_hz, n_edges, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_rows == 0 || samples == 0) return GDG_OK;
+    if (!rows || !bands) return GDG_ERR_INVALID;
+    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block spectrum: row %d is NULL", r);
+    enter_keep_fir_sums(ctx);
+    /* the rows go up compact, like gdg_block_stats_rows': an odd `samples` puts every other row 8 bytes past a 16-byte boundary */
+    const size_t band_bytes = (size_t)n_rows * blocks * (size_t)(n_edges - 1) * sizeof(double);
+    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, band_bytes);
+    if (rc != GDG_OK) return rc;
+    double *d_rows = static_cast<double *>(ctx->d_io[1]);
+    for (int r = 0; r < n_rows; r++)
+        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_block_spectrum_rows_device(ctx, d_rows, samples, n_rows, samples, sample_rate, edges_hz, n_edges, static_cast<double *>(ctx->d_io[0]));
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(bands, ctx->d_io[0], band_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_batch_spectrum_enable(gdg_ctx *ctx, const double *edges_hz, int n_edges) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open)
+        return fail(ctx, GDG_ERR_INVALID, "batch spectrum: a streamed batch run is open on this context; its setting holds until gdg_batch_stream_close");
+    if (n_edges == 0) { ctx->spec_edges.clear(); return GDG_OK; }             /* off; the spectrum of the last call stays what it is */
+    int rc = spectrum_edges_refuse(ctx, "batch spectrum", edges_hz, n_edges);   /* the whole list, before it replaces the one in force */
+    if (rc != GDG_OK) return rc;
+    const double *win = nullptr;
+    double2 *tw = nullptr, *tw2 = nullptr;
+    enter(ctx, true);                                                        /* configuration: no state of the context changes */
+    if ((rc = spectrum_tables(ctx, &win, &tw, &tw2)) != GDG_OK) return rc;     /* made here: no batch call allocates or uploads them */
+    ctx->spec_edges.assign(edges_hz, edges_hz + n_edges);
+    return GDG_OK;
+}
+
+int gdg_batch_spectrum(gdg_ctx *ctx, double *bands, size_t capacity, int *ports, size_t *blocks, int *n_bands) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (!ctx->spec_valid)
+        return fail(ctx, GDG_ERR_INVALID, "no spectrum: the last batch call of this context %s", !ctx->spec_edges.empty() ? "has not completed (or none has run since "
+                    "gdg_batch_spectrum_enable)" : "ran without one (gdg_batch_spectrum_enable comes before the call)");
+    if (ports) *ports = ctx->spec_ports;
+    if (blocks) *blocks = ctx->spec_blocks;
+    if (n_bands) *n_bands = ctx->spec_bands;
+    if (!bands) return GDG_OK;
+    const size_t n = (size_t)ctx->spec_ports * ctx->spec_blocks * (size_t)ctx->spec_bands;
+    if (capacity < n)
+        return fail(ctx, GDG_ERR_INVALID, "spectrum: room for %zu values, the spectrum has %d ports x %zu blocks x %d bands = %zu", capacity, ctx->spec_ports,
+                    ctx->spec_blocks, ctx->spec_bands, n);
+    if (n) memcpy(bands, ctx->spectrum.data(), n * sizeof(double));
+    return GDG_OK;
+}

@@ -371,6 +371,14 @@ struct gdg_ctx {
     int report_ports = 0;
     size_t report_blocks = 0;
     std::vector<gdg_block_stats> report;
+    /* the band spectrum (gdg_batch_spectrum_enable; spectrum_bands.h): the edges in force (empty = off), the bands of the last completed batch
+     * call, [spec_ports][spec_blocks][spec_bands], and the 8192 window weights (made with the first use, never with the switch off).  A call
+     * that collects takes the edges as they stood when it began (spec_live_edges); configuration like report_on, in no blob. */
+    std::vector<double> spec_edges, spec_live_edges, spectrum;
+    bool spec_valid = false;
+    int spec_ports = 0, spec_bands = 0;
+    size_t spec_blocks = 0;
+    double *d_spec_win = nullptr;
     /* the source map (gdg_batch_set_sources; batch_sources.h): batch_source[c] = the channel whose input entry channel c reads, empty = every
      * channel its own.  Configuration like report_on: read when a job is described, in no blob. */
     std::vector<int> batch_source;
@@ -593,6 +601,8 @@ int check_device_error(gdg_ctx *ctx);
 int ensure_io(gdg_ctx *ctx, int which, size_t bytes);
 int ensure_staging(gdg_ctx *ctx);
 int fir_tables(gdg_ctx *ctx, int P, double2 **tw, double2 **tw2);
+/* the band spectrum's tables: the window weights (made and uploaded with the first use) and the 4096-point transform's twiddles */
+int spectrum_tables(gdg_ctx *ctx, const double **win, double2 **tw, double2 **tw2);
 int fir_transform_size(int frames);
 int meter_rows(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int port0, int n_ports, int frames, uint32_t sample_rate);
 int numa_rebind(gdg_ctx *ctx, int mode);
@@ -663,6 +673,14 @@ int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
 static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_have_reader(ctx->batch_source); }
 /* a batch call begins: the report of the call before is gone; with the report enabled, zeroed records for `ports` x `blocks` */
 static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks) {
+    ctx->spec_valid = false;                                                 /* ... and so is its spectrum; with edges in force, zeroed bands */
+    ctx->spec_live_edges = ctx->spec_edges;
+    if (!ctx->spec_live_edges.empty()) {
+        ctx->spec_ports = ports;
+        ctx->spec_blocks = blocks;
+        ctx->spec_bands = (int)ctx->spec_live_edges.size() - 1;
+        ctx->spectrum.assign((size_t)ports * blocks * (size_t)ctx->spec_bands, 0.0);
+    }
     ctx->report_valid = false;
     ctx->report_live = ctx->report_on;
     if (!ctx->report_live) return;
@@ -674,6 +692,8 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks) {
 static inline int report_end(gdg_ctx *ctx, int rc) {
     ctx->report_valid = ctx->report_live && rc == GDG_OK;
     ctx->report_live = false;
+    ctx->spec_valid = !ctx->spec_live_edges.empty() && rc == GDG_OK;
+    ctx->spec_live_edges.clear();
     return rc;
 }
 #define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */

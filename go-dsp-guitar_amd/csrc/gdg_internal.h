@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "spectrum_bands.h"
 
 #define GDG_MAX_FRAMES 8192          /* controller/controller.go:36 BLOCK_SIZE; one frame must fit the LDS */
 #define GDG_MIN_FIR_FRAMES 64
@@ -326,6 +327,10 @@ hipError_t gdg_launch_metronome(const double *d_tick, unsigned n_tick, const dou
 /* the render report (include/gdg.h): one gdg_block_stats per block of `block` samples (the last of a row may be short) of n_rows rows of
  * `samples` samples, row r at d_rows + r * row_stride (8-byte aligned, row_stride >= samples), into d_records[r][ceil(samples / block)] */
 hipError_t gdg_launch_block_stats(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, void *d_records, hipStream_t s);
+/* the band spectrum (include/gdg.h; fir.hip, spectrum_kernels.h): per block of 8192 samples of every row (the last of a row may be short: zero-padded)
+ * the powers of bands.n_bands bands into d_bands[r][ceil(samples / 8192)][n_bands].  d_win: the 8192 window weights; tw, tw2: the 4096-point tables */
+hipError_t gdg_launch_block_spectrum(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, const double *d_win, const double2 *tw4096,
+                                     const double2 *tw2_4096, const gdg_spectrum_bands &bands, double *d_bands, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

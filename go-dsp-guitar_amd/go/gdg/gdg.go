@@ -1295,6 +1295,139 @@ func (this *Context) BatchReport() ([][]BlockStats, error) {
 	return goBlockStats(rec, int(ports), int(blocks)), nil
 }
 
+// cEdges: an edge list of the band spectrum in C memory (the caller frees it); the library validates it.
+func cEdges(edges []float64) (unsafe.Pointer, error) {
+	n := len(edges)
+	if n == 0 {
+		return nil, fmt.Errorf("gdg: no edges")
+	}
+	p := C.malloc(C.size_t(n * 8))
+	if p == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	copy((*[1 << 20]float64)(p)[:n:n], edges)
+	return p, nil
+}
+
+// goSpectrum: [rows][blocks][bands] from the library's row-major float64 values.
+func goSpectrum(p unsafe.Pointer, rows int, blocks int, bands int) [][][]float64 {
+	out := make([][][]float64, rows)
+	for r := 0; r < rows; r++ {
+		out[r] = make([][]float64, blocks)
+		for b := 0; b < blocks; b++ {
+			out[r][b] = make([]float64, bands)
+			if p != nil && bands > 0 {
+				at := (r*blocks + b) * bands
+				copy(out[r][b], (*[1 << 37]float64)(p)[at:at+bands:at+bands])
+			}
+		}
+	}
+	return out
+}
+
+// BlockSpectrumRows: the band powers of equally long host rows, per block of 8192 samples (the last one of a row possibly short:
+// zero-padded) and per band between the edges in Hz (gdg_block_spectrum_rows): periodic Hann window, 8192-point transform, bin powers
+// summed from ceil(edge*8192/rate) on; result[row][block][band].  2 to 33 edges, finite, >= 0, strictly ascending.
+func (this *Context) BlockSpectrumRows(rows [][]float64, sampleRate uint32, edges []float64) ([][][]float64, error) {
+	n := len(rows)
+	if n == 0 {
+		return [][][]float64{}, nil
+	}
+	samples := len(rows[0])
+	blocks := (samples + 8191) / 8192
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	ep, e := cEdges(edges)
+	if e != nil {
+		return nil, e
+	}
+	owned = append(owned, ep)
+	bands := len(edges) - 1
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	out := C.calloc(C.size_t(n*blocks*bands+1), 8)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_spectrum_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.uint32_t(sampleRate), (*C.double)(ep), C.int(len(edges)),
+		(*C.double)(out))); e != nil {
+		return nil, e
+	}
+	return goSpectrum(out, n, blocks, bands), nil
+}
+
+// BlockSpectrumRowsDevice: the same on device memory, enqueued on the context's stream (gdg_block_spectrum_rows_device): row r at
+// dRows + r*rowStride float64 (any 8-byte alignment, rowStride >= samples), the bands into dBands[nRows][ceil(samples/8192)][len(edges)-1].
+func (this *Context) BlockSpectrumRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, sampleRate uint32, edges []float64, dBands unsafe.Pointer) error {
+	ep, e := cEdges(edges)
+	if e != nil {
+		return e
+	}
+	defer C.free(ep)
+	return this.err(C.gdg_block_spectrum_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.uint32_t(sampleRate),
+		(*C.double)(ep), C.int(len(edges)), (*C.double)(dBands)))
+}
+
+// BatchSpectrumEnable: from the next batch call on, every batch call of the context keeps the band powers of what it rendered, per output
+// port, block of 8192 samples and band between the edges in Hz, at the job's rate (gdg_batch_spectrum_enable); nil or an empty slice
+// switches it off.  Configuration, like BatchReportEnable: a checkpoint does not carry it -- set it again on the target of a resume --
+// and an error while a streamed job is open.
+func (this *Context) BatchSpectrumEnable(edges []float64) error {
+	if len(edges) == 0 {
+		return this.err(C.gdg_batch_spectrum_enable(this.ctx, nil, 0))
+	}
+	ep, e := cEdges(edges)
+	if e != nil {
+		return e
+	}
+	defer C.free(ep)
+	return this.err(C.gdg_batch_spectrum_enable(this.ctx, (*C.double)(ep), C.int(len(edges))))
+}
+
+// BatchSpectrum: the band powers of the last completed batch call, result[port][block][band] (gdg_batch_spectrum); the ports and their
+// order are BatchReport's.  An error when the call ran without the spectrum enabled.
+func (this *Context) BatchSpectrum() ([][][]float64, error) {
+	var ports C.int
+	var blocks C.size_t
+	var bands C.int
+	if e := this.err(C.gdg_batch_spectrum(this.ctx, nil, 0, &ports, &blocks, &bands)); e != nil {
+		return nil, e
+	}
+	n := int(ports) * int(blocks) * int(bands)
+	if n == 0 {
+		return goSpectrum(nil, int(ports), int(blocks), int(bands)), nil
+	}
+	val := C.calloc(C.size_t(n), 8)
+	if val == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(val)
+	if e := this.err(C.gdg_batch_spectrum(this.ctx, (*C.double)(val), C.size_t(n), &ports, &blocks, &bands)); e != nil {
+		return nil, e
+	}
+	return goSpectrum(val, int(ports), int(blocks), int(bands)), nil
+}
+
 // BatchSetSources: the source map of the next batch calls (gdg_batch_set_sources): source[c] is the channel whose input entry channel c
 // reads -- c itself for a channel that reads its own, a root; any other entry makes c a reader, and its source must be a root.  One entry
 // per channel; nil or an empty slice clears the map.  A shared input is uploaded, decoded and resampled once and stored to every row

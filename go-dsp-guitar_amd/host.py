@@ -51,6 +51,8 @@ def lib():
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
             "gdgh_engine_last_batch_report": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdgh_engine_set_batch_spectrum": (cs, [vp, vp, i32]),
+            "gdgh_engine_last_batch_spectrum": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t), C.POINTER(i32)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
             "gdgh_engine_save_state": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -117,6 +119,7 @@ class Engine:
         self.n_channels = n_channels
         self.chains = []
         self.last_report = None          # the render report of the last batch call made with report=True: [N + 3, blocks] records
+        self.last_spectrum = None        # the band spectrum of the last batch call made with spectrum=edges: [N + 3, blocks, bands] float64
 
     def shards(self):
         return lib().gdgh_engine_shards(self._h)
@@ -199,6 +202,23 @@ class Engine:
         _err(lib().gdgh_engine_last_batch_report(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
         return out
 
+    def _set_spectrum(self, edges):
+        """Engine::SetBatchSpectrum, from the `spectrum` argument of the batch calls: the band edges in Hz (None: off)"""
+        self.last_spectrum = None
+        if edges is None or len(edges) == 0:
+            _err(lib().gdgh_engine_set_batch_spectrum(self._h, None, 0))
+            return
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        _err(lib().gdgh_engine_set_batch_spectrum(self._h, e.ctypes.data, e.size))
+
+    def _fetch_spectrum(self):
+        """Engine::LastBatchSpectrum -> [N + 3, blocks, bands] float64"""
+        ports, blocks, bands = C.c_int(0), C.c_size_t(0), C.c_int(0)
+        _err(lib().gdgh_engine_last_batch_spectrum(self._h, None, 0, C.byref(ports), C.byref(blocks), C.byref(bands)))
+        out = np.zeros((ports.value, blocks.value, bands.value), dtype=np.float64)
+        _err(lib().gdgh_engine_last_batch_spectrum(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks), C.byref(bands)))
+        return out
+
     def batch_set_sources(self, source):
         """Engine::SetBatchSources: the source map of the next jobs in JOB channel numbers (None clears it); a reader whose root lives on
         another shard is refused."""
@@ -214,13 +234,15 @@ class Engine:
         lib().gdgh_engine_set_batch_dither(self._h, 0 if seed is None else 1, 0 if seed is None else int(seed))
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None):
+                  report=False, dither=None, spectrum=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
-        render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count)."""
+        render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
+        edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
+        self._set_spectrum(spectrum)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -251,17 +273,19 @@ class Engine:
         assert samples.value == length
         if report:
             self.last_report = self._fetch_report()
+        if spectrum is not None and len(spectrum):
+            self.last_spectrum = self._fetch_spectrum()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None):
+                     report=False, dither=None, spectrum=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces.  report: last_report grows by every slice's records and is the whole job's,
-        [N + 3, blocks], when the generator ends."""
+        [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue, report, dither)
+                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -273,24 +297,26 @@ class Engine:
             lib().gdgh_free(p)
 
     def batch_stream_sharded(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False,
-                             tuner_enqueue=False, report=False, dither=None, resume=None):
+                             tuner_enqueue=False, report=False, dither=None, resume=None, spectrum=None):
         """Engine::BatchStreamShardedOpen / Need / Step / Close: batch_stream for an engine of any shard count -- every shard streams its
         channels, the master is finished per slice; yields every slice's N + 3 output pieces (blocks_per_slice: an int or a function
         (blocks_left) -> blocks).  report: as batch_stream's -- the chain rows come from the shards, the master from the finish, the
-        metronome from shard 0.  resume: a blob of batch_stream_sharded_checkpoint -- Engine::BatchStreamShardedResume in the place of the
+        metronome from shard 0; spectrum=edges: last_spectrum, from the same three sources.  resume: a blob of batch_stream_sharded_checkpoint -- Engine::BatchStreamShardedResume in the place of the
         Open call (same inputs and options, set up again on this engine); the slices go on where the checkpoint was taken."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
                                    L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
-                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report, dither, resume)
+                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report, dither, resume,
+                                  spectrum=spectrum)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None):
+                      report=False, dither=None, resume=None, spectrum=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
+        self._set_spectrum(spectrum)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -330,6 +356,9 @@ class Engine:
                 if report:
                     rec = self._fetch_report()
                     self.last_report = rec if self.last_report is None else np.concatenate([self.last_report, rec], axis=1)
+                if spectrum is not None and len(spectrum):
+                    sp = self._fetch_spectrum()
+                    self.last_spectrum = sp if self.last_spectrum is None else np.concatenate([self.last_spectrum, sp], axis=1)
                 yield outs
                 left -= blocks
         finally:

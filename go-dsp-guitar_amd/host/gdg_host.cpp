@@ -942,7 +942,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -962,7 +962,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { reportValid_ = report_; return ""; }
+    if (job == 0) { reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); return ""; }
     /* 2. the shards, concurrently: encoded chain outputs straight into the caller's buffers, partial master mixes as float64 */
     std::vector<std::vector<double>> left((size_t)G), right((size_t)G);
     std::vector<double> metronome(job, 0.0);
@@ -1013,14 +1013,42 @@ void Engine::reportBegin(size_t blocks) {
     reportValid_ = false;
     reportBlocks_ = blocks;
     if (report_) lastReport_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_stats{ 0.0, 0.0, 0u, 0u, 0u, 0u });
+    spectrumValid_ = false;                              /* the band spectrum rides along: the same ports, blocks and three sources */
+    spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
+    if (!spectrumEdges_.empty()) lastSpectrum_.assign((size_t)(nChannels_ + 3) * blocks * (spectrumEdges_.size() - 1), 0.0);
+}
+
+/* the edges in force onto a context (an empty list: off): a gdg_* status */
+int Engine::applySpectrum(gdg_ctx *ctx) {
+    return gdg_batch_spectrum_enable(ctx, spectrumEdges_.empty() ? nullptr : spectrumEdges_.data(), (int)spectrumEdges_.size());
+}
+
+/* `ports` x reportBlocks_ x bands values of a context's last call, checked against what the engine expects */
+Error Engine::spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val) {
+    const int nb = (int)spectrumEdges_.size() - 1;
+    int p = 0, b = 0;
+    size_t blocks = 0;
+    val.assign((size_t)ports * reportBlocks_ * (size_t)nb, 0.0);
+    if (gdg_batch_spectrum(ctx, val.data(), val.size(), &p, &blocks, &b) != GDG_OK) return gdg_last_error(ctx);
+    if (p != ports || blocks != reportBlocks_ || b != nb)
+        return format("a spectrum of %d ports x %zu blocks x %d bands where %d x %zu x %d were expected", p, blocks, b, ports, reportBlocks_, nb);
+    return "";
 }
 
 /* shard g's report (its n chain outputs, then the metronome): the chain rows to the shard's channels, shard 0's last row to the metronome's */
 Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
-    if (!report_) return "";
     int first = 0, count = 0, ports = 0;
     size_t blocks = 0;
     shardRange(g, &first, &count);
+    if (!spectrumEdges_.empty()) {                       /* the shard's bands: chain rows to its channels, shard 0's last row to the metronome's */
+        std::vector<double> val;
+        Error e = spectrumOf(ctx, count + 1, val);
+        if (!e.empty()) return e;
+        const size_t row = reportBlocks_ * (spectrumEdges_.size() - 1);
+        if (row) memcpy(&lastSpectrum_[(size_t)first * row], val.data(), (size_t)count * row * sizeof(double));
+        if (g == 0 && row) memcpy(&lastSpectrum_[(size_t)(nChannels_ + 2) * row], &val[(size_t)count * row], row * sizeof(double));
+    }
+    if (!report_) return "";
     std::vector<gdg_block_stats> rec((size_t)(count + 1) * reportBlocks_);
     if (gdg_batch_report(ctx, rec.data(), rec.size(), &ports, &blocks) != GDG_OK) return gdg_last_error(ctx);
     if (ports != count + 1 || blocks != reportBlocks_) return format("a report of %d ports x %zu blocks where %d x %zu were expected", ports, blocks, count + 1, reportBlocks_);
@@ -1031,6 +1059,14 @@ Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
 
 /* the finish's report (master left, master right) completes the call's */
 Error Engine::reportOfMaster(gdg_ctx *ctx) {
+    if (!spectrumEdges_.empty()) {
+        std::vector<double> val;
+        Error e = spectrumOf(ctx, 2, val);
+        if (!e.empty()) return e;
+        const size_t row = reportBlocks_ * (spectrumEdges_.size() - 1);
+        if (row) memcpy(&lastSpectrum_[(size_t)nChannels_ * row], val.data(), 2 * row * sizeof(double));
+        spectrumValid_ = true;
+    }
     if (!report_) return "";
     int ports = 0;
     size_t blocks = 0;
@@ -1039,6 +1075,26 @@ Error Engine::reportOfMaster(gdg_ctx *ctx) {
     if (ports != 2 || blocks != reportBlocks_) return format("a master report of %d ports x %zu blocks where 2 x %zu were expected", ports, blocks, reportBlocks_);
     if (blocks) memcpy(&lastReport_[(size_t)nChannels_ * blocks], rec.data(), 2 * blocks * sizeof(gdg_block_stats));
     reportValid_ = true;
+    return "";
+}
+
+Error Engine::SetBatchSpectrum(const std::vector<double> &edges) {
+    if (edges.empty()) { spectrumEdges_.clear(); return ""; }
+    if (edges.size() < 2 || edges.size() > 33) return format("SetBatchSpectrum: %zu edges; 2 to 33 make 1 to 32 bands", edges.size());
+    for (size_t i = 0; i < edges.size(); i++) {
+        if (!(edges[i] >= 0.0) || !(edges[i] <= 1.7976931348623157e308)) return format("SetBatchSpectrum: edge %zu is not a finite frequency >= 0", i);
+        if (i && !(edges[i] > edges[i - 1])) return format("SetBatchSpectrum: edge %zu does not lie above edge %zu", i, i - 1);
+    }
+    spectrumEdges_ = edges;                              /* whole or not at all: a refused list leaves the one in force */
+    return "";
+}
+
+Error Engine::LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *blocks, int *nBands) const {
+    if (!spectrumValid_) return "LastBatchSpectrum: the last batch call kept no spectrum (SetBatchSpectrum comes before the call)";
+    bands = lastSpectrum_;
+    if (ports) *ports = nChannels_ + 3;
+    if (blocks) *blocks = reportBlocks_;
+    if (nBands) *nBands = spectrumBands_;
     return "";
 }
 
@@ -1074,7 +1130,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1104,6 +1160,11 @@ Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *o
         size_t nb = 0;
         if (gdg_batch_report(ctx, lastReport_.data(), lastReport_.size(), &ports, &nb) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         reportValid_ = true;
+    }
+    if (!spectrumEdges_.empty()) {                       /* ... and so is its spectrum */
+        Error se = spectrumOf(ctx, nChannels_ + 3, lastSpectrum_);
+        if (!se.empty()) { setError(se); return LastError(); }
+        spectrumValid_ = true;
     }
     return "";
 }
@@ -1283,7 +1344,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1594,6 +1655,26 @@ const char *gdgh_engine_set_batch_sources(void *e, const int *source, int n) {
 }
 void gdgh_engine_set_batch_dither(void *e, int on, uint64_t seed) { ((Engine *)e)->SetBatchDither(seed, on != 0); }
 void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchReport(on != 0); }
+/* n == 0: off */
+const char *gdgh_engine_set_batch_spectrum(void *e, const double *edges, int n) {
+    return ret(((Engine *)e)->SetBatchSpectrum(edges && n > 0 ? std::vector<double>(edges, edges + n) : std::vector<double>()));
+}
+/* bands == NULL: the three counts only */
+const char *gdgh_engine_last_batch_spectrum(void *e, double *bands, size_t capacity, int *ports, size_t *blocks, int *n_bands) {
+    std::vector<double> val;
+    int p = 0, nb = 0;
+    size_t b = 0;
+    Error err = ((Engine *)e)->LastBatchSpectrum(val, &p, &b, &nb);
+    if (!err.empty()) return ret(err);
+    if (ports) *ports = p;
+    if (blocks) *blocks = b;
+    if (n_bands) *n_bands = nb;
+    if (bands) {
+        if (capacity < val.size()) return ret(Error("LastBatchSpectrum: too little room for the bands"));
+        if (!val.empty()) memcpy(bands, val.data(), val.size() * sizeof(double));
+    }
+    return ret(Error(""));
+}
 /* records == NULL: the two counts only */
 const char *gdgh_engine_last_batch_report(void *e, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks) {
     std::vector<gdg_block_stats> rec;

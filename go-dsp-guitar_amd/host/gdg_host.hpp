@@ -246,6 +246,12 @@ public:
      * when a job is set up (BatchRun, the Open and Resume calls); it is not part of a checkpoint. */
     void SetBatchReport(bool on) { report_ = on; }
     Error LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const;
+    /* No reference counterpart.  The band spectrum (include/gdg.h, gdg_batch_spectrum_enable): with edges set (2 to 33, Hz, finite, >= 0,
+     * strictly ascending; an empty vector: off), the same calls keep the power per port, block and band, [N + 3][blocks][bands] in the
+     * report's port order and from the report's three sources whatever the shard count.  A refused list leaves the one in force.  Read
+     * when a job is set up, like the report's switch; not part of a checkpoint. */
+    Error SetBatchSpectrum(const std::vector<double> &edges);
+    Error LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *blocks, int *nBands) const;
     /* No reference counterpart.  Shared sources (include/gdg.h, gdg_batch_set_sources): source[c] = the JOB channel whose input entry channel
      * c reads, one entry per channel of the engine; an empty vector clears the map.  The engine splits the map per shard when a job is set
      * up (BatchRun, the Open and Resume calls).  A map spans one context: a reader whose root lives on another shard is refused here,
@@ -298,6 +304,11 @@ private:
     bool report_ = false, reportValid_ = false;            /* the render report: asked for; the last call's is complete */
     size_t reportBlocks_ = 0;
     std::vector<gdg_block_stats> lastReport_;
+    std::vector<double> spectrumEdges_, lastSpectrum_;     /* the band spectrum: the edges in force (empty: off); the last call's, over reportBlocks_ */
+    bool spectrumValid_ = false;
+    int spectrumBands_ = 0;                                /* ... and its band count */
+    int applySpectrum(gdg_ctx *ctx);
+    Error spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val);
     std::vector<int> sources_;                             /* the source map in job channel numbers; empty: none */
     int applySources(int shard, gdg_ctx *ctx);             /* the shard's part of it onto its context: a gdg_* status */
     bool dither_ = false;                                  /* SetBatchDither: on, and the seed */

@@ -745,6 +745,57 @@ int gdg_block_stats_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_s
 int gdg_batch_report_enable(gdg_ctx *ctx, int enable);
 int gdg_batch_report(gdg_ctx *ctx, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks);
 /*
+ * BAND SPECTRUM: no reference counterpart.  What a block of the render report sounds like: the power of every block of 8192 samples in up
+ * to 32 frequency bands, from the same float64 rows, on the device.  Stateless like the record beside it: a block's bands are a function
+ * of that block's samples (and of the rate and the edges) and of nothing else.  The quantity, for block j of a row at sample rate R, with
+ * L = 8192 samples x[n] (a non-finite sample is taken as 0 -- gdg_block_stats.nonfinite counts them; a short last block is zero-padded):
+ *   window     w[n] = 0.5 - 0.5 cos(2 pi n / L)                          (periodic Hann)
+ *   transform  X[k] = sum_n w[n] x[n] exp(-2 pi i k n / L),              k = 0 .. L/2
+ *   bin power  P[k] = c_k |X[k]|^2 / (L^2 * 3/8),                        c_0 = c_{L/2} = 1, c_k = 2 otherwise
+ *   bands      n_edges edges in Hz, 2 <= n_edges <= 33, finite, >= 0, strictly ascending: n_edges - 1 bands, at most 32;
+ *              k_lo[b] = clamp((long long)ceil(edges[b] * 8192.0 / R), 0, 4097), computed on the host in float64 as written;
+ *              band b = the sum of P[k] over k_lo[b] <= k < k_lo[b + 1]
+ * Known answers: by Parseval the sum of P[k] over all bins is sum((w x)^2) / (L * 3/8), the block's mean square; a bin-centred sine of
+ * amplitude A puts A^2/3 into its own bin and A^2/12 into each neighbour, A^2/2 in all (a sine of amplitude 0.5 at bin 100: 0.25/12,
+ * 0.25/3, 0.25/12 in bins 99, 100, 101).  A band that holds no bin -- edges above Nyquist, two edges inside one bin -- is exactly 0.0, and
+ * so is every band of an all-zero block.
+ * The sums are added in an order that depends on L and the bin ranges alone -- not on the row, the row count, the grid, the block's place,
+ * the window, the slicing or the sharding -- with every square and every add rounded on its own, and without atomics: the same samples
+ * give the same 64 bits wherever they sit.
+ *   gdg_block_spectrum_rows(ctx, rows, n_rows, samples, sample_rate, edges_hz, n_edges, bands)
+ *                                                                      n_rows host rows of `samples` float64 each;
+ *                                                                      bands: [n_rows][ceil(samples / 8192)][n_edges - 1], row-major
+ *   gdg_block_spectrum_rows_device(ctx, d_rows, row_stride, n_rows, samples, sample_rate, edges_hz, n_edges, d_bands)
+ *                                                                      the same on device memory, enqueued on gdg_ctx_stream: row r
+ *                                                                      at d_rows + r * row_stride (row_stride >= samples, any 8-byte
+ *                                                                      alignment); no sample outside [row, row + samples) is read.
+ *                                                                      edges_hz is host memory
+ *   gdg_batch_spectrum_enable(ctx, edges_hz, n_edges)                  from the next batch call on, every batch call of the context
+ *                                                                      keeps the bands of what it rendered.  n_edges == 0: off (the
+ *                                                                      default: no launch, allocation, upload or byte differs from a
+ *                                                                      context that never heard of it).  The list is validated whole
+ *                                                                      before it replaces the one in force.  Configuration, like
+ *                                                                      gdg_batch_report_enable, the source map and the dither: part
+ *                                                                      of no blob (the checkpoint container stays version 1) -- set
+ *                                                                      it again on the target of a resume -- and GDG_ERR_INVALID
+ *                                                                      while a streamed job is open.  R is the job's target_rate;
+ *                                                                      the two finish calls use their sample_rate argument (which
+ *                                                                      must then be positive)
+ *   gdg_batch_spectrum(ctx, bands, capacity, &ports, &blocks, &n_bands) the bands of the LAST COMPLETED batch call of the context,
+ *                                                                      [ports][blocks][n_bands] row-major; bands == NULL: the three
+ *                                                                      counts only.  GDG_ERR_INVALID when capacity < ports * blocks
+ *                                                                      * n_bands (the three counts are filled in), or when there
+ *                                                                      is no spectrum
+ * Ports and their order are the render report's, call by call (above); the report and the spectrum are independent switches.  The bands
+ * come down with each step's own download, behind the records; a slice's spectrum covers the slice's blocks.
+ */
+int gdg_block_spectrum_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, uint32_t sample_rate, const double *edges_hz,
+                            int n_edges, double *bands);
+int gdg_block_spectrum_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, uint32_t sample_rate,
+                                   const double *edges_hz, int n_edges, double *d_bands);
+int gdg_batch_spectrum_enable(gdg_ctx *ctx, const double *edges_hz, int n_edges);
+int gdg_batch_spectrum(gdg_ctx *ctx, double *bands, size_t capacity, int *ports, size_t *blocks, int *n_bands);
+/*
  * SHARED SOURCES: no reference counterpart.  Re-amping renders one take, or a handful, through hundreds of rigs: with a source map every
  * shared input is gathered, uploaded, decoded and (when its rate is not the job's) resampled ONCE and stored to the row of every channel
  * that reads it, instead of once per channel.
