@@ -49,12 +49,33 @@ ABI_SYMBOLS = [
     "gdg_block_stats_rows", "gdg_block_stats_rows_device", "gdg_batch_report_enable", "gdg_batch_report", "gdg_batch_set_sources",
     "gdg_batch_set_dither", "gdg_batch_dither_seek", "gdg_wave_encode_dither", "gdg_wave_encode_dither_device",
     "gdg_block_spectrum_rows", "gdg_block_spectrum_rows_device", "gdg_batch_spectrum_enable", "gdg_batch_spectrum",
+    "gdg_block_align_rows", "gdg_block_align_rows_device", "gdg_batch_align_enable", "gdg_batch_align",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
 BLOCK_STATS_DTYPE = np.dtype([("peak", "<f8"), ("sum_sq", "<f8"), ("peak_index", "<u4"), ("clipped", "<u4"), ("full_scale", "<u4"),
                               ("nonfinite", "<u4")])
 assert BLOCK_STATS_DTYPE.itemsize == 32
+
+# gdg_block_align (include/gdg.h): one record of the alignment report, 40 bytes, little-endian
+BLOCK_ALIGN_DTYPE = np.dtype([("corr", "<f8"), ("corr0", "<f8"), ("ref_sq", "<f8"), ("sq_at_lag", "<f8"), ("lag", "<i4"), ("reserved", "<u4")])
+assert BLOCK_ALIGN_DTYPE.itemsize == 40
+ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
+ALIGN_MAX_LAG = 2048
+
+
+def align_refs(ref, max_lag):
+    """A reference list of the alignment report as an int32 array, refused here as gdg_batch_align_enable refuses it: every entry -1 or a
+    port of the list, 1 <= max_lag <= 2048."""
+    r = np.array(ref, dtype=np.int64).reshape(-1)
+    if r.size < 1:
+        raise ValueError("an empty reference list")
+    if not 1 <= int(max_lag) <= ALIGN_MAX_LAG:
+        raise ValueError("a lag range of %d; 1 to %d" % (int(max_lag), ALIGN_MAX_LAG))
+    if np.any(r < -1) or np.any(r >= r.size):
+        raise ValueError("a reference is -1 or a port below %d" % r.size)
+    return np.ascontiguousarray(r, dtype=np.int32)
+
 
 SPECTRUM_BLOCK = 8192        # the band spectrum's block = its transform (include/gdg.h)
 SPECTRUM_MAX_EDGES = 33
@@ -272,6 +293,10 @@ def lib():
             "gdg_block_spectrum_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, C.c_uint32, vp, i32, vp]),
             "gdg_batch_spectrum_enable": (i32, [vp, vp, i32]),
             "gdg_batch_spectrum": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t), C.POINTER(i32)]),
+            "gdg_block_align_rows": (i32, [vp, vp, i32, C.c_size_t, vp, i32, vp]),
+            "gdg_block_align_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp, i32, vp]),
+            "gdg_batch_align_enable": (i32, [vp, vp, i32, i32]),
+            "gdg_batch_align": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
             "gdg_ctx_get_option": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -1110,6 +1135,49 @@ class Context:
         self._check(lib().gdg_batch_spectrum(self._h, None, 0, C.byref(ports), C.byref(blocks), C.byref(bands)))
         out = np.zeros((ports.value, blocks.value, bands.value), dtype=np.float64)
         self._check(lib().gdg_batch_spectrum(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks), C.byref(bands)))
+        return out
+
+    # -- the alignment report: lag and polarity per output port and block of 8192 samples against a reference port (include/gdg.h) ------------
+    def block_align(self, rows, ref, max_lag):
+        """rows: a [n_rows][samples] float64 array or a list of equally long 1-D arrays; ref[r]: -1 or the row that row r is measured
+        against; returns the [n_rows][ceil(samples / 8192)] BLOCK_ALIGN_DTYPE records of gdg_block_align_rows."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        refs = align_refs(ref, max_lag)
+        if refs.size != n:
+            raise ValueError("%d references for %d rows" % (refs.size, n))
+        samples = keep[0].size
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        out = np.zeros((n, -(-samples // ALIGN_BLOCK)), dtype=BLOCK_ALIGN_DTYPE)
+        ptrs = (C.c_void_p * n)(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_align_rows(self._h, ptrs, n, samples, refs.ctypes.data, int(max_lag), out.ctypes.data if out.size else None))
+        return out
+
+    def block_align_device(self, d_rows, row_stride, n_rows, samples, ref, max_lag, d_records):
+        """gdg_block_align_rows_device on plain device pointers (ints), enqueued on the context's stream; the references are host values."""
+        refs = align_refs(ref, max_lag)
+        if refs.size != n_rows:
+            raise ValueError("%d references for %d rows" % (refs.size, n_rows))
+        self._check(lib().gdg_block_align_rows_device(self._h, d_rows, row_stride, n_rows, samples, refs.ctypes.data, int(max_lag), d_records))
+
+    def batch_align_enable(self, ref, max_lag=ALIGN_MAX_LAG):
+        """From the next batch call on, every batch call keeps the alignment records of what it rendered: port p against port ref[p] (-1:
+        not measured), one entry per port of the calls to come; None (or an empty list) switches it off.  Configuration: not in a
+        checkpoint, refused while a streamed job is open."""
+        if ref is None or len(ref) == 0:
+            self._check(lib().gdg_batch_align_enable(self._h, None, 0, 0))
+            return
+        refs = align_refs(ref, max_lag)
+        self._check(lib().gdg_batch_align_enable(self._h, refs.ctypes.data, refs.size, int(max_lag)))
+
+    def batch_align(self):
+        """The [ports][blocks] BLOCK_ALIGN_DTYPE records of the last completed batch call; GdgError when there are none."""
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_align(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=BLOCK_ALIGN_DTYPE)
+        self._check(lib().gdg_batch_align(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
         return out
 
     def metronome_process(self, frames):

@@ -112,6 +112,7 @@ struct BatchLoop {
     bool dither;                                /* the dithered encoders (gdg_batch_set_dither in force and an LPCM out_format) ... */
     uint64_t dither_first;                      /* ... and the job's sample index of this loop's first sample */
     const gdg_spectrum_bands *bands;            /* the band spectrum: n_bands doubles per output row and block ride behind the records; null = off */
+    const std::vector<gdg_align_pairs> *align;  /* the alignment report: the measured ports of this call, a launch's worth to a piece; null = off */
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -186,6 +187,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     const double *spec_win = nullptr;
     double2 *spec_tw = nullptr, *spec_tw2 = nullptr;
     if (p.bands && (r = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2)) != GDG_OK) return r;
+    /* ... and with the alignment report the step's records of that kind, [rows][w], at the next 16 bytes behind the bands (behind the records,
+     * or the rows, when those switches are off): the last piece brings them as well.  Only the measured ports' are written, and read */
+    auto align_at = [&](size_t i) { return ((p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i)) + 15) & ~(size_t)15; };
+    auto align_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_align); };
+    double2 *align_tw = nullptr, *align_tw2 = nullptr;
+    if (p.align && (r = fir_tables(ctx, GDG_ALIGN_BLOCK, &align_tw, &align_tw2)) != GDG_OK) return r;
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
     auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
@@ -219,6 +226,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
             const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;
             for (size_t o = 0; o < rows; o++) memcpy(&ctx->spectrum[(o * ctx->spec_blocks + b0) * n_bands], sp + o * w * n_bands, w * n_bands * sizeof(double));
+        }
+        if (p.align) {                                                       /* ... and the measured ports' alignment records; the others stay zero */
+            const gdg_block_align *al = reinterpret_cast<const gdg_block_align *>(src + align_at(i));
+            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
+            for (const gdg_align_pairs &q : *p.align)
+                for (int k = 0; k < q.n; k++) memcpy(&ctx->align[(size_t)q.port[k] * ctx->align_blocks + b0], al + (size_t)q.port[k] * w, w * sizeof(gdg_block_align));
         }
         return GDG_OK;
     };
@@ -266,6 +279,10 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 if (sharded && run_metro)
                     HIP_TRY(ctx, gdg_launch_block_spectrum(d_metro, ws, 1u, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp + (size_t)N * w * n_bands, ctx->stream));
             }
+            if (p.align)                                                     /* ... and one more: a shard's metronome port is row N + 2, as d_metro is */
+                for (const gdg_align_pairs &q : *p.align)
+                    HIP_TRY(ctx, gdg_launch_block_align(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (unsigned)N + 2u, (unsigned)rec_rows, (size_t)wb, q, align_tw,
+                                                        enc + align_at(i), ctx->stream));
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst) -> hipError_t {
                 if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
@@ -293,7 +310,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i);
+        const size_t down = p.align ? align_at(i) + align_bytes(i) : p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i);
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -458,6 +475,9 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
         return fail(ctx, GDG_ERR_INVALID, "the batch loop runs blocks of %d frames, the context allows %d", GDG_BLOCK_SIZE, ctx->max_frames);
     if (!gdg_wave_bytes_per_sample(opt->out_format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", opt->out_format);
     if (opt->target_rate == 0) return fail(ctx, GDG_ERR_INVALID, "sample rate must be positive");
+    if (!ctx->align_ref.empty() && (int)ctx->align_ref.size() != n_inputs + (shard ? 1 : 3))      /* before anything is done */
+        return fail(ctx, GDG_ERR_INVALID, "batch align: the list in force has %zu ports, this call %d (%s)", ctx->align_ref.size(), n_inputs + (shard ? 1 : 3),
+                    shard ? "a shard's n chain outputs and the metronome" : "the N chain outputs, master left, master right, metronome");
     int rc;
     if (meters_at_open && (rc = check_meter_ports(ctx, opt, shard ? SHARD_PORTS : "")) != GDG_OK) return rc;
     std::vector<size_t> n_out((size_t)n_inputs, 0);
@@ -603,7 +623,12 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const bool spectrum = !ctx->spec_live_edges.empty();
     const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), opt->target_rate) : gdg_spectrum_bands();
     const size_t spec_room = spectrum ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * (size_t)bands.n_bands * sizeof(double) : 0;
-    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room + spec_room;
+    /* ... and with the alignment report a window's records of that kind behind those (align_at).  A shard that does not run the metronome
+     * measures nothing against that port */
+    const bool align = !ctx->align_live_ref.empty();
+    const std::vector<gdg_align_pairs> pairs = align ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
+    const size_t align_room = align ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_align) : 0;
+    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room + spec_room + align_room;
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -772,7 +797,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             return GDG_OK;
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
-                        S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, spectrum ? &bands : nullptr };
+                        S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, spectrum ? &bands : nullptr,
+                        align ? &pairs : nullptr };
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -882,7 +908,7 @@ static int finish_master_check(gdg_ctx *ctx, int out_format, const double *const
 static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                          size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes, uint64_t dither_first) {
     const size_t width = (size_t)gdg_wave_bytes_per_sample(out_format), B = GDG_BLOCK_SIZE;
-    report_begin(ctx, 2, (samples + B - 1) / B);
+    report_begin(ctx, 2, (samples + B - 1) / B, /*align=*/false);                /* the master's two sides: no alignment records (include/gdg.h) */
     if (!ctx->spec_live_edges.empty() && sample_rate == 0)                       /* like every refusal from here on: the call before's report and spectrum are gone */
         return report_end(ctx, fail(ctx, GDG_ERR_INVALID, "master mix: the band spectrum needs a positive sample rate"));
     if (samples == 0) return report_end(ctx, GDG_OK);

@@ -602,3 +602,100 @@ int gdg_batch_spectrum(gdg_ctx *ctx, double *bands, size_t capacity, int *ports,
     if (n) memcpy(bands, ctx->spectrum.data(), n * sizeof(double));
     return GDG_OK;
 }
+
+/* ---- the alignment report (include/gdg.h; the kernel: align_kernels.h in fir.hip; the list's validation: align_map.h; the batch calls fill it: api_batch.cpp) ---- */
+static int align_refuse(gdg_ctx *ctx, const char *what, int status, int n_ports, int max_lag, int bad, const int *ref) {
+    switch (status) {
+    case ALIGN_OK: return GDG_OK;
+    case ALIGN_COUNT: return fail(ctx, GDG_ERR_INVALID, "%s: a list of %d ports", what, n_ports);
+    case ALIGN_NULL: return fail(ctx, GDG_ERR_INVALID, "%s: no reference list", what);
+    case ALIGN_LAG: return fail(ctx, GDG_ERR_INVALID, "%s: a lag range of %d; 1 to %d", what, max_lag, GDG_ALIGN_MAX_LAG);
+    default: return fail(ctx, GDG_ERR_INVALID, "%s: port %d names reference %d; -1 or a port below %d", what, bad, ref[bad], n_ports);
+    }
+}
+
+static int block_align_check(gdg_ctx *ctx, int n_rows, size_t samples, const int *ref, int max_lag, size_t *blocks) {
+    if (n_rows < 0) return fail(ctx, GDG_ERR_INVALID, "block align: %d rows", n_rows);
+    if (n_rows > 0) {
+        int bad = -1;
+        const int st = align_map_check(ref, n_rows, max_lag, &bad);
+        if (st != ALIGN_OK) return align_refuse(ctx, "block align", st, n_rows, max_lag, bad, ref);
+    } else if (max_lag < 1 || max_lag > GDG_ALIGN_MAX_LAG) return align_refuse(ctx, "block align", ALIGN_LAG, n_rows, max_lag, -1, ref);
+    *blocks = (samples + GDG_ALIGN_BLOCK - 1) / GDG_ALIGN_BLOCK;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block align: %zu blocks per row are too many for one launch", *blocks);
+    return GDG_OK;
+}
+
+int gdg_block_align_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, const int *ref, int max_lag,
+                                gdg_block_align *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    int rc = block_align_check(ctx, n_rows, samples, ref, max_lag, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_rows == 0 || samples == 0) return GDG_OK;
+    if (!d_rows || !d_records) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block align: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block align: rows and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    double2 *tw = nullptr, *tw2 = nullptr;
+    if ((rc = fir_tables(ctx, GDG_ALIGN_BLOCK, &tw, &tw2)) != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_records, 0, (size_t)n_rows * blocks * sizeof(gdg_block_align), ctx->stream));      /* an unmeasured row: zeros */
+    for (const gdg_align_pairs &q : align_map_pieces(std::vector<int>(ref, ref + n_rows), max_lag))
+        HIP_TRY(ctx, gdg_launch_block_align(d_rows, row_stride, (unsigned)n_rows, 0u, (unsigned)n_rows, samples, q, tw, d_records, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_block_align_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, const int *ref, int max_lag, gdg_block_align *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    int rc = block_align_check(ctx, n_rows, samples, ref, max_lag, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_rows == 0 || samples == 0) return GDG_OK;
+    if (!rows || !records) return GDG_ERR_INVALID;
+    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block align: row %d is NULL", r);
+    enter_keep_fir_sums(ctx);
+    /* the rows go up compact, like gdg_block_spectrum_rows': an odd `samples` puts every other row 8 bytes past a 16-byte boundary */
+    const size_t rec_bytes = (size_t)n_rows * blocks * sizeof(gdg_block_align);
+    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, rec_bytes);
+    if (rc != GDG_OK) return rc;
+    double *d_rows = static_cast<double *>(ctx->d_io[1]);
+    for (int r = 0; r < n_rows; r++)
+        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_block_align_rows_device(ctx, d_rows, samples, n_rows, samples, ref, max_lag, static_cast<gdg_block_align *>(ctx->d_io[0]));
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(records, ctx->d_io[0], rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_batch_align_enable(gdg_ctx *ctx, const int *ref, int n_ports, int max_lag) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open)
+        return fail(ctx, GDG_ERR_INVALID, "batch align: a streamed batch run is open on this context; its setting holds until gdg_batch_stream_close");
+    if (!ref || n_ports == 0) { ctx->align_ref.clear(); ctx->align_lag = 0; return GDG_OK; }      /* off; the records of the last call stay what they are */
+    int bad = -1;
+    const int st = align_map_check(ref, n_ports, max_lag, &bad);                /* the whole list, before it replaces the one in force */
+    if (st != ALIGN_OK) return align_refuse(ctx, "batch align", st, n_ports, max_lag, bad, ref);
+    double2 *tw = nullptr, *tw2 = nullptr;
+    enter(ctx, true);                                                        /* configuration: no state of the context changes */
+    const int rc = fir_tables(ctx, GDG_ALIGN_BLOCK, &tw, &tw2);                /* made here: no batch call allocates or uploads them */
+    if (rc != GDG_OK) return rc;
+    align_map_replace(ctx->align_ref, ctx->align_lag, ref, n_ports, max_lag, &bad);
+    return GDG_OK;
+}
+
+int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int *ports, size_t *blocks) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (!ctx->align_valid)
+        return fail(ctx, GDG_ERR_INVALID, "no alignment records: the last batch call of this context %s", !ctx->align_ref.empty() ? "has not completed, was a master "
+                    "finish, or none has run since gdg_batch_align_enable" : "ran without them (gdg_batch_align_enable comes before the call)");
+    if (ports) *ports = ctx->align_ports;
+    if (blocks) *blocks = ctx->align_blocks;
+    if (!records) return GDG_OK;
+    const size_t n = (size_t)ctx->align_ports * ctx->align_blocks;
+    if (capacity < n)
+        return fail(ctx, GDG_ERR_INVALID, "alignment: room for %zu records, the call has %d ports x %zu blocks = %zu", capacity, ctx->align_ports, ctx->align_blocks, n);
+    if (n) memcpy(records, ctx->align.data(), n * sizeof(gdg_block_align));
+    return GDG_OK;
+}

@@ -379,6 +379,15 @@ struct gdg_ctx {
     int spec_ports = 0, spec_bands = 0;
     size_t spec_blocks = 0;
     double *d_spec_win = nullptr;
+    /* the alignment report (gdg_batch_align_enable; align_map.h): the reference list and the lag range in force (empty = off) and the records
+     * of the last completed batch call, [align_ports][align_blocks].  A call that collects takes list and lag as they stood when it began
+     * (align_live_*); configuration like the spectrum's edges, in no blob.  The finish calls never collect. */
+    std::vector<int> align_ref, align_live_ref;
+    int align_lag = 0, align_live_lag = 0;
+    std::vector<gdg_block_align> align;
+    bool align_valid = false;
+    int align_ports = 0;
+    size_t align_blocks = 0;
     /* the source map (gdg_batch_set_sources; batch_sources.h): batch_source[c] = the channel whose input entry channel c reads, empty = every
      * channel its own.  Configuration like report_on: read when a job is described, in no blob. */
     std::vector<int> batch_source;
@@ -672,7 +681,16 @@ int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
 /* the map in force has a reader: what a checkpoint cannot record yet */
 static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_have_reader(ctx->batch_source); }
 /* a batch call begins: the report of the call before is gone; with the report enabled, zeroed records for `ports` x `blocks` */
-static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks) {
+static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool align = true) {
+    ctx->align_valid = false;                                                /* its alignment records are gone too; `align`: this call may collect them */
+    ctx->align_live_ref.clear();
+    if (align && (int)ctx->align_ref.size() == ports) {                      /* any other count was refused when the job was described */
+        ctx->align_live_ref = ctx->align_ref;
+        ctx->align_live_lag = ctx->align_lag;
+        ctx->align_ports = ports;
+        ctx->align_blocks = blocks;
+        ctx->align.assign((size_t)ports * blocks, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
+    }
     ctx->spec_valid = false;                                                 /* ... and so is its spectrum; with edges in force, zeroed bands */
     ctx->spec_live_edges = ctx->spec_edges;
     if (!ctx->spec_live_edges.empty()) {
@@ -694,6 +712,8 @@ static inline int report_end(gdg_ctx *ctx, int rc) {
     ctx->report_live = false;
     ctx->spec_valid = !ctx->spec_live_edges.empty() && rc == GDG_OK;
     ctx->spec_live_edges.clear();
+    ctx->align_valid = !ctx->align_live_ref.empty() && rc == GDG_OK;
+    ctx->align_live_ref.clear();
     return rc;
 }
 #define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */

@@ -1863,6 +1863,7 @@ hipError_t gdg_launch_fir_ahead(int P, const gdg_ahead_steps &steps, gdg_ahead a
 }
 
 #include "spectrum_kernels.h"        /* the band spectrum of the render report: still without contraction */
+#include "align_kernels.h"           /* ... and its alignment records: the same passes, forward and inverse */
 
 #pragma clang fp contract(fast)     /* the tuner has no second path to agree with bit for bit */
 #include "tuner_kernels.h"

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "spectrum_bands.h"
+#include "align_map.h"
 
 #define GDG_MAX_FRAMES 8192          /* controller/controller.go:36 BLOCK_SIZE; one frame must fit the LDS */
 #define GDG_MIN_FIR_FRAMES 64
@@ -331,6 +332,11 @@ hipError_t gdg_launch_block_stats(const double *d_rows, size_t row_stride, unsig
  * the powers of bands.n_bands bands into d_bands[r][ceil(samples / 8192)][n_bands].  d_win: the 8192 window weights; tw, tw2: the 4096-point tables */
 hipError_t gdg_launch_block_spectrum(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, const double *d_win, const double2 *tw4096,
                                      const double2 *tw2_4096, const gdg_spectrum_bands &bands, double *d_bands, hipStream_t s);
+/* the alignment report (include/gdg.h; fir.hip, align_kernels.h): per block of 8192 samples (the last of a row may be short: zero-padded) and
+ * per entry of `pairs` one gdg_block_align into d_records[port][ceil(samples / 8192)].  Ports below n_chain are the rows of their number, the
+ * ports from n_chain on the rows from tail_row on (row r at d_rows + r * row_stride); tw8192: the 8192-point table */
+hipError_t gdg_launch_block_align(const double *d_rows, size_t row_stride, unsigned n_chain, unsigned tail_row, unsigned n_ports, size_t samples,
+                                  const gdg_align_pairs &pairs, const double2 *tw8192, void *d_records, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

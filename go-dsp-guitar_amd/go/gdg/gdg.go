@@ -1428,6 +1428,156 @@ func (this *Context) BatchSpectrum() ([][][]float64, error) {
 	return goSpectrum(val, int(ports), int(blocks), int(bands)), nil
 }
 
+// BlockAlign: one record of the alignment report (gdg_block_align): lag and polarity of a block of 8192 samples of one row against the
+// same block of its reference row.  Corr = r[Lag], signed (negative: opposite polarity); Corr0 = r[0]; Corr / sqrt(RefSq * SqAtLag) is the
+// normalised coefficient.  A positive Lag: the row arrives later than its reference.
+type BlockAlign struct {
+	Corr    float64
+	Corr0   float64
+	RefSq   float64
+	SqAtLag float64
+	Lag     int32
+}
+
+func goBlockAlign(p unsafe.Pointer, rows int, blocks int) [][]BlockAlign {
+	out := make([][]BlockAlign, rows)
+	if rows*blocks == 0 {
+		for r := range out {
+			out[r] = []BlockAlign{}
+		}
+		return out
+	}
+	recs := (*[1 << 25]C.gdg_block_align)(p)[: rows*blocks : rows*blocks]
+	for r := range out {
+		out[r] = make([]BlockAlign, blocks)
+		for b := range out[r] {
+			c := recs[r*blocks+b]
+			out[r][b] = BlockAlign{float64(c.corr), float64(c.corr0), float64(c.ref_sq), float64(c.sq_at_lag), int32(c.lag)}
+		}
+	}
+	return out
+}
+
+// cRefs: a reference list of the alignment report in C memory (the caller frees it); the library validates it.
+func cRefs(ref []int) (unsafe.Pointer, error) {
+	n := len(ref)
+	if n == 0 {
+		return nil, fmt.Errorf("gdg: no references")
+	}
+	p := C.malloc(C.size_t(n * 4))
+	if p == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	dst := (*[1 << 28]C.int)(p)[:n:n]
+	for i, v := range ref {
+		dst[i] = C.int(v)
+	}
+	return p, nil
+}
+
+// BlockAlignRows: the alignment records of equally long host rows, per block of 8192 samples (the last one of a row possibly short:
+// zero-padded): row r against row ref[r], -1 for a row that is not measured (gdg_block_align_rows); 1 <= maxLag <= 2048;
+// result[row][block].
+func (this *Context) BlockAlignRows(rows [][]float64, ref []int, maxLag int) ([][]BlockAlign, error) {
+	n := len(rows)
+	if n == 0 {
+		return [][]BlockAlign{}, nil
+	}
+	if len(ref) != n {
+		return nil, fmt.Errorf("gdg: %d references for %d rows", len(ref), n)
+	}
+	samples := len(rows[0])
+	blocks := (samples + 8191) / 8192
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	fp, e := cRefs(ref)
+	if e != nil {
+		return nil, e
+	}
+	owned = append(owned, fp)
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	out := C.calloc(C.size_t(n*blocks+1), 40)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_align_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), (*C.int)(fp), C.int(maxLag), (*C.gdg_block_align)(out))); e != nil {
+		return nil, e
+	}
+	return goBlockAlign(out, n, blocks), nil
+}
+
+// BlockAlignRowsDevice: the same on device memory, enqueued on the context's stream (gdg_block_align_rows_device): row r at
+// dRows + r*rowStride float64 (any 8-byte alignment, rowStride >= samples), the records into dRecords[len(ref)][ceil(samples/8192)].
+func (this *Context) BlockAlignRowsDevice(dRows unsafe.Pointer, rowStride int, samples int, ref []int, maxLag int, dRecords unsafe.Pointer) error {
+	fp, e := cRefs(ref)
+	if e != nil {
+		return e
+	}
+	defer C.free(fp)
+	return this.err(C.gdg_block_align_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(len(ref)), C.size_t(samples), (*C.int)(fp), C.int(maxLag),
+		(*C.gdg_block_align)(dRecords)))
+}
+
+// BatchAlignEnable: from the next batch call on, every batch call of the context keeps the alignment records of what it rendered: port p
+// against port ref[p], -1 for a port that is not measured, one entry per port of the calls to come (gdg_batch_align_enable); nil or an
+// empty slice switches it off.  Configuration, like BatchSpectrumEnable: a checkpoint does not carry it -- set it again on the target of
+// a resume -- and an error while a streamed job is open.
+func (this *Context) BatchAlignEnable(ref []int, maxLag int) error {
+	if len(ref) == 0 {
+		return this.err(C.gdg_batch_align_enable(this.ctx, nil, 0, 0))
+	}
+	fp, e := cRefs(ref)
+	if e != nil {
+		return e
+	}
+	defer C.free(fp)
+	return this.err(C.gdg_batch_align_enable(this.ctx, (*C.int)(fp), C.int(len(ref)), C.int(maxLag)))
+}
+
+// BatchAlign: the alignment records of the last completed batch call, result[port][block] (gdg_batch_align); the ports and their order
+// are BatchReport's.  An error when the call ran without them, or was a master finish.
+func (this *Context) BatchAlign() ([][]BlockAlign, error) {
+	var ports C.int
+	var blocks C.size_t
+	if e := this.err(C.gdg_batch_align(this.ctx, nil, 0, &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	n := int(ports) * int(blocks)
+	if n == 0 {
+		return goBlockAlign(nil, int(ports), int(blocks)), nil
+	}
+	rec := C.calloc(C.size_t(n), 40)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	if e := this.err(C.gdg_batch_align(this.ctx, (*C.gdg_block_align)(rec), C.size_t(n), &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	return goBlockAlign(rec, int(ports), int(blocks)), nil
+}
+
 // BatchSetSources: the source map of the next batch calls (gdg_batch_set_sources): source[c] is the channel whose input entry channel c
 // reads -- c itself for a channel that reads its own, a root; any other entry makes c a reader, and its source must be a root.  One entry
 // per channel; nil or an empty slice clears the map.  A shared input is uploaded, decoded and resampled once and stored to every row

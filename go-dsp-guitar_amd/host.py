@@ -52,6 +52,8 @@ def lib():
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
             "gdgh_engine_last_batch_report": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_spectrum": (cs, [vp, vp, i32]),
+            "gdgh_engine_set_batch_align": (cs, [vp, vp, i32, i32]),
+            "gdgh_engine_last_batch_align": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_last_batch_spectrum": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t), C.POINTER(i32)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
@@ -120,6 +122,7 @@ class Engine:
         self.chains = []
         self.last_report = None          # the render report of the last batch call made with report=True: [N + 3, blocks] records
         self.last_spectrum = None        # the band spectrum of the last batch call made with spectrum=edges: [N + 3, blocks, bands] float64
+        self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
     def shards(self):
         return lib().gdgh_engine_shards(self._h)
@@ -219,6 +222,25 @@ class Engine:
         _err(lib().gdgh_engine_last_batch_spectrum(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks), C.byref(bands)))
         return out
 
+    def _set_align(self, align):
+        """Engine::SetBatchAlign, from the `align` argument of the batch calls: (ref over the job's N + 3 ports, max_lag) (None: off)"""
+        self.last_align = None
+        if align is None or align[0] is None or len(align[0]) == 0:
+            _err(lib().gdgh_engine_set_batch_align(self._h, None, 0, 0))
+            return False
+        ref = np.ascontiguousarray(align[0], dtype=np.int32).reshape(-1)
+        _err(lib().gdgh_engine_set_batch_align(self._h, ref.ctypes.data, ref.size, int(align[1])))
+        return True
+
+    def _fetch_align(self):
+        """Engine::LastBatchAlign -> [N + 3, blocks] records (the package's BLOCK_ALIGN_DTYPE)"""
+        import __graft_entry__ as entry
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_align(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=entry.load_package().BLOCK_ALIGN_DTYPE)
+        _err(lib().gdgh_engine_last_batch_align(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
     def batch_set_sources(self, source):
         """Engine::SetBatchSources: the source map of the next jobs in JOB channel numbers (None clears it); a reader whose root lives on
         another shard is refused."""
@@ -234,15 +256,17 @@ class Engine:
         lib().gdgh_engine_set_batch_dither(self._h, 0 if seed is None else 1, 0 if seed is None else int(seed))
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None):
+                  report=False, dither=None, spectrum=None, align=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
-        edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order)."""
+        edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
+        keep the alignment records in last_align ([N + 3, blocks]); over shards the master rows are zero records."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_spectrum(spectrum)
+        aligned = self._set_align(align)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -275,17 +299,19 @@ class Engine:
             self.last_report = self._fetch_report()
         if spectrum is not None and len(spectrum):
             self.last_spectrum = self._fetch_spectrum()
+        if aligned:
+            self.last_align = self._fetch_align()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None):
+                     report=False, dither=None, spectrum=None, align=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces.  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum)
+                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -297,7 +323,7 @@ class Engine:
             lib().gdgh_free(p)
 
     def batch_stream_sharded(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False,
-                             tuner_enqueue=False, report=False, dither=None, resume=None, spectrum=None):
+                             tuner_enqueue=False, report=False, dither=None, resume=None, spectrum=None, align=None):
         """Engine::BatchStreamShardedOpen / Need / Step / Close: batch_stream for an engine of any shard count -- every shard streams its
         channels, the master is finished per slice; yields every slice's N + 3 output pieces (blocks_per_slice: an int or a function
         (blocks_left) -> blocks).  report: as batch_stream's -- the chain rows come from the shards, the master from the finish, the
@@ -307,16 +333,17 @@ class Engine:
         return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
                                    L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
                                   out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report, dither, resume,
-                                  spectrum=spectrum)
+                                  spectrum=spectrum, align=align)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_spectrum(spectrum)
+        aligned = self._set_align(align)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -359,6 +386,9 @@ class Engine:
                 if spectrum is not None and len(spectrum):
                     sp = self._fetch_spectrum()
                     self.last_spectrum = sp if self.last_spectrum is None else np.concatenate([self.last_spectrum, sp], axis=1)
+                if aligned:
+                    al = self._fetch_align()
+                    self.last_align = al if self.last_align is None else np.concatenate([self.last_align, al], axis=1)
                 yield outs
                 left -= blocks
         finally:

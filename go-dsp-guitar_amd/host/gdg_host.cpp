@@ -931,6 +931,10 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         chains = chains_;
     }
     size_t job = 0;
+    {
+        Error ae = alignOverShards(1);                   /* the shard forms make the master in the finish, at any shard count */
+        if (!ae.empty()) { setError(ae); return ae; }
+    }
     for (int g = 0; g < shards(); g++) {
         int first = 0, count = 0;
         shardRange(g, &first, &count);
@@ -942,7 +946,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -962,7 +966,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); return ""; }
+    if (job == 0) { reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); return ""; }
     /* 2. the shards, concurrently: encoded chain outputs straight into the caller's buffers, partial master mixes as float64 */
     std::vector<std::vector<double>> left((size_t)G), right((size_t)G);
     std::vector<double> metronome(job, 0.0);
@@ -1016,6 +1020,54 @@ void Engine::reportBegin(size_t blocks) {
     spectrumValid_ = false;                              /* the band spectrum rides along: the same ports, blocks and three sources */
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
     if (!spectrumEdges_.empty()) lastSpectrum_.assign((size_t)(nChannels_ + 3) * blocks * (spectrumEdges_.size() - 1), 0.0);
+    alignValid_ = false;                                 /* ... and so do the alignment records; the master's rows stay zero over shards */
+    if (!alignRef_.empty()) lastAlign_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
+}
+
+/* the shard a port of the job lives on: a chain output on its channel's, the metronome on shard 0, the master (made by the finish) on none */
+int Engine::shardOfPort(int port) {
+    if (port < nChannels_) return shardOf(port);
+    return port == nChannels_ + 2 ? 0 : -1;
+}
+
+/* what a list in force needs to be split over `minShards` or more shards: no master port, every reference on its port's shard */
+Error Engine::alignOverShards(int minShards) {
+    if (alignRef_.empty() || shards() < minShards) return "";
+    for (int p = 0; p < nChannels_ + 3; p++) {
+        const int r = alignRef_[(size_t)p];
+        if (r < 0) continue;
+        if (shardOfPort(p) < 0 || shardOfPort(r) < 0)
+            return format("SetBatchAlign: port %d is measured against port %d, and ports %d and %d are the master mix: over shards the finish makes it, and the finish "
+                          "carries no alignment records", p, r, nChannels_, nChannels_ + 1);
+        if (shardOfPort(p) != shardOfPort(r))
+            return format("SetBatchAlign: port %d (shard %d) is measured against port %d on shard %d: a port and its reference live on one shard", p, shardOfPort(p), r,
+                          shardOfPort(r));
+    }
+    return "";
+}
+
+/* the list in force onto a context (an empty list: off): shard < 0: the plain form's N + 3 ports; otherwise the shard's chain outputs and
+ * the metronome, in the shard's own port numbers (alignOverShards has kept every reference on its port's shard).  A gdg_* status */
+int Engine::applyAlign(int shard, gdg_ctx *ctx) {
+    if (alignRef_.empty()) return gdg_batch_align_enable(ctx, nullptr, 0, 0);
+    if (shard < 0) return gdg_batch_align_enable(ctx, alignRef_.data(), nChannels_ + 3, alignLag_);
+    int first = 0, count = 0;
+    shardRange(shard, &first, &count);
+    auto local = [&](int port) { return port < 0 ? -1 : (port < nChannels_ ? port - first : count); };
+    std::vector<int> ref((size_t)count + 1, -1);
+    for (int c = 0; c < count; c++) ref[(size_t)c] = local(alignRef_[(size_t)(first + c)]);
+    if (shard == 0) ref[(size_t)count] = local(alignRef_[(size_t)(nChannels_ + 2)]);
+    return gdg_batch_align_enable(ctx, ref.data(), count + 1, alignLag_);
+}
+
+/* `ports` x reportBlocks_ records of a context's last call, checked against what the engine expects */
+Error Engine::alignOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_align> &rec) {
+    int p = 0;
+    size_t blocks = 0;
+    rec.assign((size_t)ports * reportBlocks_, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
+    if (gdg_batch_align(ctx, rec.data(), rec.size(), &p, &blocks) != GDG_OK) return gdg_last_error(ctx);
+    if (p != ports || blocks != reportBlocks_) return format("alignment records of %d ports x %zu blocks where %d x %zu were expected", p, blocks, ports, reportBlocks_);
+    return "";
 }
 
 /* the edges in force onto a context (an empty list: off): a gdg_* status */
@@ -1040,6 +1092,14 @@ Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
     int first = 0, count = 0, ports = 0;
     size_t blocks = 0;
     shardRange(g, &first, &count);
+    if (!alignRef_.empty()) {                            /* the shard's alignment records: the same two destinations */
+        std::vector<gdg_block_align> rec;
+        Error e = alignOf(ctx, count + 1, rec);
+        if (!e.empty()) return e;
+        const size_t nb = reportBlocks_;
+        if (nb) memcpy(&lastAlign_[(size_t)first * nb], rec.data(), (size_t)count * nb * sizeof(gdg_block_align));
+        if (g == 0 && nb) memcpy(&lastAlign_[(size_t)(nChannels_ + 2) * nb], &rec[(size_t)count * nb], nb * sizeof(gdg_block_align));
+    }
     if (!spectrumEdges_.empty()) {                       /* the shard's bands: chain rows to its channels, shard 0's last row to the metronome's */
         std::vector<double> val;
         Error e = spectrumOf(ctx, count + 1, val);
@@ -1059,6 +1119,7 @@ Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
 
 /* the finish's report (master left, master right) completes the call's */
 Error Engine::reportOfMaster(gdg_ctx *ctx) {
+    alignValid_ = !alignRef_.empty();                    /* the finish has no alignment records: the shards' are the call's, the master rows zero */
     if (!spectrumEdges_.empty()) {
         std::vector<double> val;
         Error e = spectrumOf(ctx, 2, val);
@@ -1086,6 +1147,28 @@ Error Engine::SetBatchSpectrum(const std::vector<double> &edges) {
         if (i && !(edges[i] > edges[i - 1])) return format("SetBatchSpectrum: edge %zu does not lie above edge %zu", i, i - 1);
     }
     spectrumEdges_ = edges;                              /* whole or not at all: a refused list leaves the one in force */
+    return "";
+}
+
+Error Engine::SetBatchAlign(const std::vector<int> &ref, int maxLag) {
+    if (ref.empty()) { alignRef_.clear(); alignLag_ = 0; return ""; }
+    if ((int)ref.size() != nChannels_ + 3) return format("SetBatchAlign: a list of %zu ports; the job has N + 3 = %d", ref.size(), nChannels_ + 3);
+    if (maxLag < 1 || maxLag > 2048) return format("SetBatchAlign: a lag range of %d; 1 to 2048", maxLag);
+    for (size_t p = 0; p < ref.size(); p++)
+        if (ref[p] < -1 || ref[p] >= nChannels_ + 3) return format("SetBatchAlign: port %zu names reference %d; -1 or a port below %d", p, ref[p], nChannels_ + 3);
+    const std::vector<int> keep = alignRef_;
+    alignRef_ = ref;
+    Error e = alignOverShards(2);                        /* more than one shard: the list must split */
+    if (!e.empty()) { alignRef_ = keep; return e; }      /* whole or not at all: a refused list leaves the one in force */
+    alignLag_ = maxLag;
+    return "";
+}
+
+Error Engine::LastBatchAlign(std::vector<gdg_block_align> &records, int *ports, size_t *blocks) const {
+    if (!alignValid_) return "LastBatchAlign: the last batch call kept no alignment records (SetBatchAlign comes before the call)";
+    records = lastAlign_;
+    if (ports) *ports = nChannels_ + 3;
+    if (blocks) *blocks = reportBlocks_;
     return "";
 }
 
@@ -1130,7 +1213,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1160,6 +1243,11 @@ Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *o
         size_t nb = 0;
         if (gdg_batch_report(ctx, lastReport_.data(), lastReport_.size(), &ports, &nb) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         reportValid_ = true;
+    }
+    if (!alignRef_.empty()) {                            /* ... and so are its alignment records */
+        Error ae = alignOf(ctx, nChannels_ + 3, lastAlign_);
+        if (!ae.empty()) { setError(ae); return LastError(); }
+        alignValid_ = true;
     }
     if (!spectrumEdges_.empty()) {                       /* ... and so is its spectrum */
         Error se = spectrumOf(ctx, nChannels_ + 3, lastSpectrum_);
@@ -1344,7 +1432,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1672,6 +1760,25 @@ const char *gdgh_engine_last_batch_spectrum(void *e, double *bands, size_t capac
     if (bands) {
         if (capacity < val.size()) return ret(Error("LastBatchSpectrum: too little room for the bands"));
         if (!val.empty()) memcpy(bands, val.data(), val.size() * sizeof(double));
+    }
+    return ret(Error(""));
+}
+/* n == 0: off */
+const char *gdgh_engine_set_batch_align(void *e, const int *ref, int n, int max_lag) {
+    return ret(((Engine *)e)->SetBatchAlign(ref && n > 0 ? std::vector<int>(ref, ref + n) : std::vector<int>(), max_lag));
+}
+/* records == NULL: the two counts only */
+const char *gdgh_engine_last_batch_align(void *e, gdg_block_align *records, size_t capacity, int *ports, size_t *blocks) {
+    std::vector<gdg_block_align> rec;
+    int p = 0;
+    size_t b = 0;
+    Error err = ((Engine *)e)->LastBatchAlign(rec, &p, &b);
+    if (!err.empty()) return ret(err);
+    if (ports) *ports = p;
+    if (blocks) *blocks = b;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchAlign: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_align));
     }
     return ret(Error(""));
 }

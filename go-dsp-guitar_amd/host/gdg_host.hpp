@@ -252,6 +252,15 @@ public:
      * when a job is set up, like the report's switch; not part of a checkpoint. */
     Error SetBatchSpectrum(const std::vector<double> &edges);
     Error LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *blocks, int *nBands) const;
+    /* No reference counterpart.  The alignment report (include/gdg.h, gdg_batch_align_enable): ref[p] = the port of the job's N + 3 that
+     * port p is measured against, -1 for a port that is not measured (an empty vector: off); 1 <= maxLag <= 2048.  The same calls keep
+     * [N + 3][blocks] records in the report's port order whatever the shard count.  The engine splits the list per shard when a job is
+     * set up: with more than one shard a reference that lives on another shard is refused here (the metronome lives on shard 0), and so
+     * is a list that measures or references a master port -- the finish makes the master and carries no alignment records; BatchRun and
+     * the BatchStreamSharded calls go through the shard forms at any shard count and refuse such a list when the job is set up (a one-shard
+     * engine measures its master through BatchStreamOpen / Step).  A refused list leaves the one in force.  Not part of a checkpoint. */
+    Error SetBatchAlign(const std::vector<int> &ref, int maxLag);
+    Error LastBatchAlign(std::vector<gdg_block_align> &records, int *ports, size_t *blocks) const;
     /* No reference counterpart.  Shared sources (include/gdg.h, gdg_batch_set_sources): source[c] = the JOB channel whose input entry channel
      * c reads, one entry per channel of the engine; an empty vector clears the map.  The engine splits the map per shard when a job is set
      * up (BatchRun, the Open and Resume calls).  A map spans one context: a reader whose root lives on another shard is refused here,
@@ -308,6 +317,14 @@ private:
     bool spectrumValid_ = false;
     int spectrumBands_ = 0;                                /* ... and its band count */
     int applySpectrum(gdg_ctx *ctx);
+    std::vector<int> alignRef_;                            /* the alignment report: the list in force over the job's N + 3 ports (empty: off) ... */
+    int alignLag_ = 0;                                     /* ... its lag range, the last call's records over reportBlocks_, and whether they are complete */
+    std::vector<gdg_block_align> lastAlign_;
+    bool alignValid_ = false;
+    int shardOfPort(int port);
+    Error alignOverShards(int minShards);
+    int applyAlign(int shard, gdg_ctx *ctx);               /* shard < 0: the plain form's list */
+    Error alignOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_align> &rec);
     Error spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val);
     std::vector<int> sources_;                             /* the source map in job channel numbers; empty: none */
     int applySources(int shard, gdg_ctx *ctx);             /* the shard's part of it onto its context: a gdg_* status */

@@ -796,6 +796,66 @@ int gdg_block_spectrum_rows_device(gdg_ctx *ctx, const double *d_rows, size_t ro
 int gdg_batch_spectrum_enable(gdg_ctx *ctx, const double *edges_hz, int n_edges);
 int gdg_batch_spectrum(gdg_ctx *ctx, double *bands, size_t capacity, int *ports, size_t *blocks, int *n_bands);
 /*
+ * ALIGNMENT: no reference counterpart.  When a block of one output arrives relative to the same block of another, and with which polarity:
+ * the first question when two renders of one take are blended or summed (a few samples of offset comb-filter the sum, an inverted rig
+ * cancels).  From the same float64 rows, on the device; stateless like the record and the bands: a function of the two blocks and M.
+ * L = 8192.  A call has `ports` rows; port p has a reference ref[p]: -1 (not measured) or a port of the same call (ref[p] == p is
+ * allowed).  M = max_lag, 1 <= M <= 2048.  For block b, x = the block of row ref[p], y = the block of row p, NaN and +-inf taken as 0, a
+ * short last block zero-padded to L:
+ *   r[l] = sum_{n = M}^{L-M-1} x[n] * y[n + l]                          for -M <= l <= M
+ * The central L - 2M samples of the reference against the whole block of p: every product lies inside the block for every lag, so this is
+ * a linear correlation without wrap-around and without edge weighting.  A positive lag: p arrives LATER than its reference.
+ */
+typedef struct {
+    double   corr;        /* r[lag], signed: negative = opposite polarity */
+    double   corr0;       /* r[0]: what the pair has without a shift */
+    double   ref_sq;      /* sum_{n=M}^{L-M-1} x[n]^2 */
+    double   sq_at_lag;   /* sum_{n=M}^{L-M-1} y[n + lag]^2; corr / sqrt(ref_sq * sq_at_lag) is the normalised coefficient in [-1, 1] */
+    int32_t  lag;         /* the l with the greatest |r[l]| as computed on the device; equal magnitudes: the smaller |l|, then the negative one */
+    uint32_t reserved;    /* 0 */
+} gdg_block_align;        /* 40 bytes, little-endian, no padding other than the last field */
+/*
+ * r is computed by transform (one 8192-point complex transform of x' + i y, x' = x zeroed outside [M, L - M), and one inverse), so corr and
+ * corr0 carry the transform's rounding: a few 1e-16 of (ref_sq + sum y^2), which is of the order of sqrt(ref_sq * sum y^2) when the two
+ * rows are of one size and more than that when one is much the quieter.  The choice among equal magnitudes is made lexicographically at every level of a fixed reduction tree, so `lag` is a function
+ * of the two blocks and M alone; ref_sq and sq_at_lag are added in an order that depends on M (and lag) alone, every square and add rounded
+ * on its own, without atomics: the same samples give the same bits whatever the row, the grid, the window, the slicing or the sharding.
+ * A port with ref[p] = -1 gets an all-zero record; two silent blocks give lag = 0 and zeros everywhere.
+ *   gdg_block_align_rows(ctx, rows, n_rows, samples, ref, max_lag, records)
+ *                                                                      n_rows host rows of `samples` float64 each, ref: n_rows
+ *                                                                      entries; records: [n_rows][ceil(samples / 8192)], row-major
+ *   gdg_block_align_rows_device(ctx, d_rows, row_stride, n_rows, samples, ref, max_lag, d_records)
+ *                                                                      the same on device memory, enqueued on gdg_ctx_stream: row r
+ *                                                                      at d_rows + r * row_stride (row_stride >= samples, any 8-byte
+ *                                                                      alignment); no sample outside [row, row + samples) is read.
+ *                                                                      ref is host memory; d_records (8-byte aligned) gets the
+ *                                                                      records of the measured rows, the others are zeroed
+ *   gdg_batch_align_enable(ctx, ref, n_ports, max_lag)                 from the next batch call on, every batch call of the context
+ *                                                                      keeps the alignment records of what it rendered.  ref == NULL
+ *                                                                      or n_ports == 0: off (the default: no launch, allocation,
+ *                                                                      upload or byte differs).  The list is validated whole before
+ *                                                                      it replaces the one in force.  n_ports is the port count of
+ *                                                                      the calls to come -- N + 3 for gdg_batch_run and
+ *                                                                      gdg_batch_stream_step, n + 1 for the shard forms -- and a
+ *                                                                      batch call with another count is refused before it does
+ *                                                                      anything.  Configuration, like gdg_batch_spectrum_enable:
+ *                                                                      part of no blob -- set it again on the target of a resume --
+ *                                                                      and GDG_ERR_INVALID while a streamed job is open
+ *   gdg_batch_align(ctx, records, capacity, &ports, &blocks)           the records of the LAST COMPLETED batch call of the context,
+ *                                                                      [ports][blocks] row-major; records == NULL: the two counts
+ *                                                                      only.  GDG_ERR_INVALID when capacity < ports * blocks (the
+ *                                                                      counts are filled in), or when there are no records
+ * Ports and their order are the render report's.  The two finish calls carry no alignment records (after one, there are none): a
+ * reference is a port of the same call, and the master's two sides are one mix.  On a shard that does not run the metronome, a record that
+ * measures or references the metronome port is all-zero.  The records come down with each step's own download, behind the bands; report,
+ * spectrum and alignment are independent switches.
+ */
+int gdg_block_align_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, const int *ref, int max_lag, gdg_block_align *records);
+int gdg_block_align_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, const int *ref, int max_lag,
+                                gdg_block_align *d_records);
+int gdg_batch_align_enable(gdg_ctx *ctx, const int *ref, int n_ports, int max_lag);
+int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int *ports, size_t *blocks);
+/*
  * SHARED SOURCES: no reference counterpart.  Re-amping renders one take, or a handful, through hundreds of rigs: with a source map every
  * shared input is gathered, uploaded, decoded and (when its rate is not the job's) resampled ONCE and stored to the row of every channel
  * that reads it, instead of once per channel.
