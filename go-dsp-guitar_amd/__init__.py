@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "gdg_batch_set_dither", "gdg_batch_dither_seek", "gdg_wave_encode_dither", "gdg_wave_encode_dither_device",
     "gdg_block_spectrum_rows", "gdg_block_spectrum_rows_device", "gdg_batch_spectrum_enable", "gdg_batch_spectrum",
     "gdg_block_align_rows", "gdg_block_align_rows_device", "gdg_batch_align_enable", "gdg_batch_align",
+    "gdg_true_peak_taps", "gdg_block_true_peak_rows", "gdg_block_true_peak_rows_device", "gdg_batch_true_peak_enable", "gdg_batch_true_peak",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -60,6 +61,21 @@ assert BLOCK_STATS_DTYPE.itemsize == 32
 # gdg_block_align (include/gdg.h): one record of the alignment report, 40 bytes, little-endian
 BLOCK_ALIGN_DTYPE = np.dtype([("corr", "<f8"), ("corr0", "<f8"), ("ref_sq", "<f8"), ("sq_at_lag", "<f8"), ("lag", "<i4"), ("reserved", "<u4")])
 assert BLOCK_ALIGN_DTYPE.itemsize == 40
+# gdg_block_true_peak (include/gdg.h): one true-peak record, 16 bytes, little-endian, no padding
+BLOCK_TRUE_PEAK_DTYPE = np.dtype([("true_peak", "<f8"), ("position", "<u4"), ("overs", "<u4")])
+assert BLOCK_TRUE_PEAK_DTYPE.itemsize == 16
+TRUE_PEAK_BLOCK = 8192       # the true-peak record's block (include/gdg.h)
+
+
+def true_peak_taps():
+    """gdg_true_peak_taps: the library's [3][24] float64 interpolation taps (phases 1, 2, 3; j = -11 .. 12); no context, no device"""
+    out = np.zeros((3, 24), dtype=np.float64)
+    rc = lib().gdg_true_peak_taps(out.ctypes.data, out.size)
+    if rc != GDG_OK:
+        raise GdgError(rc, "gdg_true_peak_taps")
+    return out
+
+
 ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
 ALIGN_MAX_LAG = 2048
 
@@ -297,6 +313,11 @@ def lib():
             "gdg_block_align_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp, i32, vp]),
             "gdg_batch_align_enable": (i32, [vp, vp, i32, i32]),
             "gdg_batch_align": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdg_true_peak_taps": (i32, [vp, i32]),
+            "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
+            "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
+            "gdg_batch_true_peak_enable": (i32, [vp, i32]),
+            "gdg_batch_true_peak": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdg_profile_sample": (i32, [vp, i32]),
             "gdg_ctx_set_option": (i32, [vp, C.c_char_p, C.c_longlong]),
             "gdg_ctx_get_option": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -1178,6 +1199,38 @@ class Context:
         self._check(lib().gdg_batch_align(self._h, None, 0, C.byref(ports), C.byref(blocks)))
         out = np.zeros((ports.value, blocks.value), dtype=BLOCK_ALIGN_DTYPE)
         self._check(lib().gdg_batch_align(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
+    # -- the true-peak record: the 4x oversampled peak per output port and block of 8192 samples (include/gdg.h) -----------------------------
+    def block_true_peak(self, rows):
+        """rows: a [n_rows][samples] float64 array or a list of equally long 1-D arrays; returns the [n_rows][ceil(samples / 8192)]
+        BLOCK_TRUE_PEAK_DTYPE records of gdg_block_true_peak_rows."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        out = np.zeros((n, -(-samples // TRUE_PEAK_BLOCK)), dtype=BLOCK_TRUE_PEAK_DTYPE)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_true_peak_rows(self._h, ptrs, n, samples, out.ctypes.data if out.size else None))
+        return out
+
+    def block_true_peak_device(self, d_rows, row_stride, n_rows, samples, d_records):
+        """gdg_block_true_peak_rows_device on plain device pointers (ints), enqueued on the context's stream."""
+        self._check(lib().gdg_block_true_peak_rows_device(self._h, d_rows, row_stride, n_rows, samples, d_records))
+
+    def batch_true_peak_enable(self, enable=True):
+        """From the next batch call on, every batch call keeps the true-peak records of what it rendered (off by default).  Configuration:
+        not in a checkpoint, refused while a streamed job is open."""
+        self._check(lib().gdg_batch_true_peak_enable(self._h, 1 if enable else 0))
+
+    def batch_true_peak(self):
+        """The [ports][blocks] BLOCK_TRUE_PEAK_DTYPE records of the last completed batch call; GdgError when there are none."""
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_true_peak(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=BLOCK_TRUE_PEAK_DTYPE)
+        self._check(lib().gdg_batch_true_peak(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
         return out
 
     def metronome_process(self, frames):

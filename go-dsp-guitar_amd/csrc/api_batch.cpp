@@ -113,6 +113,7 @@ struct BatchLoop {
     uint64_t dither_first;                      /* ... and the job's sample index of this loop's first sample */
     const gdg_spectrum_bands *bands;            /* the band spectrum: n_bands doubles per output row and block ride behind the records; null = off */
     const std::vector<gdg_align_pairs> *align;  /* the alignment report: the measured ports of this call, a launch's worth to a piece; null = off */
+    bool true_peak;                             /* the true-peak records: 16 bytes per output row and block ride behind the alignment records */
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -193,6 +194,10 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     auto align_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_align); };
     double2 *align_tw = nullptr, *align_tw2 = nullptr;
     if (p.align && (r = fir_tables(ctx, GDG_ALIGN_BLOCK, &align_tw, &align_tw2)) != GDG_OK) return r;
+    /* ... and with the true-peak switch the step's records of that kind, [rows][w], at the next 16 bytes behind whatever precedes them */
+    auto before_tp = [&](size_t i) { return p.align ? align_at(i) + align_bytes(i) : p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i); };
+    auto tp_at = [&](size_t i) { return (before_tp(i) + 15) & ~(size_t)15; };
+    auto tp_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_true_peak); };
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
     auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
@@ -232,6 +237,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
             for (const gdg_align_pairs &q : *p.align)
                 for (int k = 0; k < q.n; k++) memcpy(&ctx->align[(size_t)q.port[k] * ctx->align_blocks + b0], al + (size_t)q.port[k] * w, w * sizeof(gdg_block_align));
+        }
+        if (p.true_peak) {                                                   /* ... and the step's true-peak records, as the report's are filed */
+            const gdg_block_true_peak *tp = reinterpret_cast<const gdg_block_true_peak *>(src + tp_at(i));
+            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
+            const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;      /* a shard without the metronome: that row stays zero */
+            for (size_t o = 0; o < rows; o++) memcpy(&ctx->true_peak[o * ctx->tp_blocks + b0], tp + o * w, w * sizeof(gdg_block_true_peak));
         }
         return GDG_OK;
     };
@@ -283,6 +294,11 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 for (const gdg_align_pairs &q : *p.align)
                     HIP_TRY(ctx, gdg_launch_block_align(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (unsigned)N + 2u, (unsigned)rec_rows, (size_t)wb, q, align_tw,
                                                         enc + align_at(i), ctx->stream));
+            if (p.true_peak) {                                               /* ... and the inter-sample peaks of the same rows */
+                gdg_block_true_peak *tp = reinterpret_cast<gdg_block_true_peak *>(enc + tp_at(i));
+                HIP_TRY(ctx, gdg_launch_block_true_peak(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, true_peak_table(), tp, ctx->stream));
+                if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_true_peak(d_metro, ws, 1u, (size_t)wb, true_peak_table(), tp + (size_t)N * w, ctx->stream));
+            }
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst) -> hipError_t {
                 if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
@@ -310,7 +326,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = p.align ? align_at(i) + align_bytes(i) : p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i);
+        const size_t down = p.true_peak ? tp_at(i) + tp_bytes(i) : before_tp(i);
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -628,7 +644,10 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const bool align = !ctx->align_live_ref.empty();
     const std::vector<gdg_align_pairs> pairs = align ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t align_room = align ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_align) : 0;
-    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room + spec_room + align_room;
+    /* ... and with the true-peak switch a window's records of that kind behind those (tp_at) */
+    const bool true_peak = ctx->tp_live;
+    const size_t tp_room = true_peak ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_true_peak) : 0;
+    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room + spec_room + align_room + tp_room;
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -798,7 +817,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, spectrum ? &bands : nullptr,
-                        align ? &pairs : nullptr };
+                        align ? &pairs : nullptr, true_peak };
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -912,7 +931,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
     if (!ctx->spec_live_edges.empty() && sample_rate == 0)                       /* like every refusal from here on: the call before's report and spectrum are gone */
         return report_end(ctx, fail(ctx, GDG_ERR_INVALID, "master mix: the band spectrum needs a positive sample rate"));
     if (samples == 0) return report_end(ctx, GDG_OK);
-    const bool report = ctx->report_live, dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = !ctx->spec_live_edges.empty();
+    const bool report = ctx->report_live, dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = !ctx->spec_live_edges.empty(), true_peak = ctx->tp_live;
     enter(ctx);
     const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), sample_rate) : gdg_spectrum_bands();
     const size_t n_bands = spectrum ? (size_t)bands.n_bands : 0;
@@ -926,7 +945,9 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
     const size_t rec_off = 2 * piece * width, rec_bytes = report ? 2 * (piece / B) * sizeof(gdg_block_stats) : 0;
     /* ... and the band spectrum: a piece's bands, [2][piece / 8192][n_bands], behind those */
     const size_t spec_off = rec_off + rec_bytes, spec_bytes = 2 * (piece / B) * n_bands * sizeof(double);
-    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = spec_off + spec_bytes;
+    /* ... and the true-peak records, [2][piece / 8192], behind those */
+    const size_t tp_off = spec_off + spec_bytes, tp_bytes = true_peak ? 2 * (piece / B) * sizeof(gdg_block_true_peak) : 0;
+    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = tp_off + tp_bytes;
     if (!ctx->fin_up[0])
         for (int h = 0; h < 2; h++) {
             HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
@@ -939,7 +960,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
     if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * down_bytes);
     if (rc != GDG_OK) return rc;
     unsigned char *d_slab = static_cast<unsigned char *>(ctx->d_io[1]), *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
-    double *d_sums = (run_meters || report || spectrum) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
+    double *d_sums = (run_meters || report || spectrum || true_peak) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
     const size_t n_pieces = (samples + piece - 1) / piece;
     auto span = [&](size_t k) { return std::min(piece, samples - k * piece); };
     auto stride_of = [](size_t n) { return (n + 3) & ~(size_t)3; };                /* <= piece: a piece is whole blocks */
@@ -986,6 +1007,10 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
                 HIP_TRY(ctx, gdg_launch_block_spectrum(d_sums, piece, 2u, n, spec_win, spec_tw, spec_tw2, bands, reinterpret_cast<double *>(enc + spec_off), ctx->stream));
                 HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + spec_off, enc + spec_off, 2 * nb * n_bands * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             }
+            if (true_peak) {                                                 /* the same sums; a short last block is just shorter */
+                HIP_TRY(ctx, gdg_launch_block_true_peak(d_sums, piece, 2u, n, true_peak_table(), enc + tp_off, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + tp_off, enc + tp_off, 2 * nb * sizeof(gdg_block_true_peak), hipMemcpyDeviceToHost, ctx->stream));
+            }
             /* the download of piece k - 2 into this pinned half has been scattered: scatter(k - 2) ran before enqueue(k) */
             if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * width, hipMemcpyDeviceToHost, ctx->stream));
             if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + piece * width, enc + piece * width, n * width, hipMemcpyDeviceToHost, ctx->stream));
@@ -1015,6 +1040,12 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
                 const size_t nb = (span(k) + B - 1) / B;
                 for (size_t side = 0; side < 2; side++)
                     memcpy(&ctx->spectrum[(side * ctx->spec_blocks + k * (piece / B)) * n_bands], sp + side * nb * n_bands, nb * n_bands * sizeof(double));
+            }
+            if (true_peak) {
+                const gdg_block_true_peak *tp = reinterpret_cast<const gdg_block_true_peak *>(ctx->h_fin_down[h] + tp_off);
+                const size_t nb = (span(k) + B - 1) / B;
+                for (size_t side = 0; side < 2; side++)
+                    memcpy(&ctx->true_peak[side * ctx->tp_blocks + k * (piece / B)], tp + side * nb, nb * sizeof(gdg_block_true_peak));
             }
             return GDG_OK;
         };

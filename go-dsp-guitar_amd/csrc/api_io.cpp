@@ -699,3 +699,81 @@ int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int
     if (n) memcpy(records, ctx->align.data(), n * sizeof(gdg_block_align));
     return GDG_OK;
 }
+
+/* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */
+static_assert(sizeof(gdg_block_true_peak) == 16 && offsetof(gdg_block_true_peak, position) == 8 && offsetof(gdg_block_true_peak, overs) == 12,
+              "gdg_block_true_peak: 16 bytes, no padding");
+const gdg_true_peak_table &true_peak_table() {
+    static const gdg_true_peak_table table = [] { gdg_true_peak_table t; true_peak_build(&t); return t; }();
+    return table;
+}
+
+int gdg_true_peak_taps(double *taps, int capacity) { return true_peak_copy(&true_peak_table(), taps, capacity) ? GDG_OK : GDG_ERR_INVALID; }
+
+static int block_true_peak_check(gdg_ctx *ctx, int n_rows, size_t samples, size_t *blocks) {
+    if (n_rows <= 0) return fail(ctx, GDG_ERR_INVALID, "block true peak: %d rows (at least 1)", n_rows);
+    *blocks = (samples + GDG_TRUE_PEAK_BLOCK - 1) / GDG_TRUE_PEAK_BLOCK;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block true peak: %zu blocks per row are too many for one launch", *blocks);
+    return GDG_OK;
+}
+
+int gdg_block_true_peak_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, gdg_block_true_peak *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_true_peak_check(ctx, n_rows, samples, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (samples == 0) return GDG_OK;
+    if (!d_rows || !d_records) return fail(ctx, GDG_ERR_INVALID, "block true peak: %s is NULL", !d_rows ? "the rows' pointer" : "the records' pointer");
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block true peak: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block true peak: rows and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    HIP_TRY(ctx, gdg_launch_block_true_peak(d_rows, row_stride, (unsigned)n_rows, samples, true_peak_table(), d_records, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_block_true_peak_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, gdg_block_true_peak *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    int rc = block_true_peak_check(ctx, n_rows, samples, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (samples == 0) return GDG_OK;
+    if (!rows || !records) return fail(ctx, GDG_ERR_INVALID, "block true peak: %s is NULL", !rows ? "the rows' list" : "the records' pointer");
+    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block true peak: row %d is NULL", r);
+    enter_keep_fir_sums(ctx);
+    /* the rows go up compact, like gdg_block_stats_rows': an odd `samples` puts every other row 8 bytes past a 16-byte boundary */
+    const size_t rec_bytes = (size_t)n_rows * blocks * sizeof(gdg_block_true_peak);
+    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, rec_bytes);
+    if (rc != GDG_OK) return rc;
+    double *d_rows = static_cast<double *>(ctx->d_io[1]);
+    for (int r = 0; r < n_rows; r++)
+        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_block_true_peak_rows_device(ctx, d_rows, samples, n_rows, samples, static_cast<gdg_block_true_peak *>(ctx->d_io[0]));
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(records, ctx->d_io[0], rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_batch_true_peak_enable(gdg_ctx *ctx, int enable) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open)
+        return fail(ctx, GDG_ERR_INVALID, "batch true peak: a streamed batch run is open on this context; its setting holds until gdg_batch_stream_close");
+    ctx->tp_on = enable != 0;                  /* read when a batch call begins; the records of the last call stay what they are */
+    return GDG_OK;
+}
+
+int gdg_batch_true_peak(gdg_ctx *ctx, gdg_block_true_peak *records, size_t capacity, int *ports, size_t *blocks) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (!ctx->tp_valid)
+        return fail(ctx, GDG_ERR_INVALID, "no true-peak records: the last batch call of this context %s", ctx->tp_on ? "has not completed (or none has run since "
+                    "gdg_batch_true_peak_enable)" : "ran without them (gdg_batch_true_peak_enable comes before the call)");
+    if (ports) *ports = ctx->tp_ports;
+    if (blocks) *blocks = ctx->tp_blocks;
+    if (!records) return GDG_OK;
+    const size_t n = (size_t)ctx->tp_ports * ctx->tp_blocks;
+    if (capacity < n)
+        return fail(ctx, GDG_ERR_INVALID, "true peak: room for %zu records, the call has %d ports x %zu blocks = %zu", capacity, ctx->tp_ports, ctx->tp_blocks, n);
+    if (n) memcpy(records, ctx->true_peak.data(), n * sizeof(gdg_block_true_peak));
+    return GDG_OK;
+}

@@ -388,6 +388,12 @@ struct gdg_ctx {
     bool align_valid = false;
     int align_ports = 0;
     size_t align_blocks = 0;
+    /* the true-peak records (gdg_batch_true_peak_enable; true_peak_taps.h): the switch, the switch as it stood when the collecting call began
+     * (tp_live), and the records of the last completed batch call, [tp_ports][tp_blocks].  Configuration like report_on, in no blob. */
+    bool tp_on = false, tp_live = false, tp_valid = false;
+    int tp_ports = 0;
+    size_t tp_blocks = 0;
+    std::vector<gdg_block_true_peak> true_peak;
     /* the source map (gdg_batch_set_sources; batch_sources.h): batch_source[c] = the channel whose input entry channel c reads, empty = every
      * channel its own.  Configuration like report_on: read when a job is described, in no blob. */
     std::vector<int> batch_source;
@@ -612,6 +618,8 @@ int ensure_staging(gdg_ctx *ctx);
 int fir_tables(gdg_ctx *ctx, int P, double2 **tw, double2 **tw2);
 /* the band spectrum's tables: the window weights (made and uploaded with the first use) and the 4096-point transform's twiddles */
 int spectrum_tables(gdg_ctx *ctx, const double **win, double2 **tw, double2 **tw2);
+/* api_io.cpp: the true-peak record's 3 x 24 taps, built on the host with the first use (true_peak_taps.h) */
+const gdg_true_peak_table &true_peak_table();
 int fir_transform_size(int frames);
 int meter_rows(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int port0, int n_ports, int frames, uint32_t sample_rate);
 int numa_rebind(gdg_ctx *ctx, int mode);
@@ -691,6 +699,13 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
         ctx->align_blocks = blocks;
         ctx->align.assign((size_t)ports * blocks, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
     }
+    ctx->tp_valid = false;                                                   /* ... and its true-peak records; with the switch on, zeroed ones */
+    ctx->tp_live = ctx->tp_on;
+    if (ctx->tp_live) {
+        ctx->tp_ports = ports;
+        ctx->tp_blocks = blocks;
+        ctx->true_peak.assign((size_t)ports * blocks, gdg_block_true_peak{ 0.0, 0u, 0u });
+    }
     ctx->spec_valid = false;                                                 /* ... and so is its spectrum; with edges in force, zeroed bands */
     ctx->spec_live_edges = ctx->spec_edges;
     if (!ctx->spec_live_edges.empty()) {
@@ -714,6 +729,8 @@ static inline int report_end(gdg_ctx *ctx, int rc) {
     ctx->spec_live_edges.clear();
     ctx->align_valid = !ctx->align_live_ref.empty() && rc == GDG_OK;
     ctx->align_live_ref.clear();
+    ctx->tp_valid = ctx->tp_live && rc == GDG_OK;
+    ctx->tp_live = false;
     return rc;
 }
 #define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */

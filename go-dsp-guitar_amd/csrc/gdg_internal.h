@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include "spectrum_bands.h"
 #include "align_map.h"
+#include "true_peak_taps.h"
 
 #define GDG_MAX_FRAMES 8192          /* controller/controller.go:36 BLOCK_SIZE; one frame must fit the LDS */
 #define GDG_MIN_FIR_FRAMES 64
@@ -337,6 +338,10 @@ hipError_t gdg_launch_block_spectrum(const double *d_rows, size_t row_stride, un
  * ports from n_chain on the rows from tail_row on (row r at d_rows + r * row_stride); tw8192: the 8192-point table */
 hipError_t gdg_launch_block_align(const double *d_rows, size_t row_stride, unsigned n_chain, unsigned tail_row, unsigned n_ports, size_t samples,
                                   const gdg_align_pairs &pairs, const double2 *tw8192, void *d_records, hipStream_t s);
+/* the true-peak record (include/gdg.h; io.hip, true_peak_kernels.h): per block of 8192 samples (the last of a row may be short: just shorter) of
+ * n_rows rows one gdg_block_true_peak into d_records[r][ceil(samples / 8192)]; taps: the table of true_peak_taps.h, passed by value */
+hipError_t gdg_launch_block_true_peak(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, const gdg_true_peak_table &taps, void *d_records,
+                                      hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

@@ -1054,6 +1054,8 @@ hipError_t gdg_launch_block_stats(const double *d_rows, size_t row_stride, unsig
     return hipGetLastError();
 }
 
+#include "true_peak_kernels.h"      /* the render report's true-peak record: the same rows, the same load rule */
+
 /* resample.Time over a span of a file (the streamed batch run): blockIdx.y = input. Output samples [out_first, out_first + count) from
  * the source frames [src_first, src_first + src_count) at `src`; n = the FILE's frames (the j < n bound).  x, floor(x) and x - j are
  * formed from the absolute 64-bit i and j in the operation order of resample_time_kernel, so every sample has the whole-file kernel's

@@ -1578,6 +1578,137 @@ func (this *Context) BatchAlign() ([][]BlockAlign, error) {
 	return goBlockAlign(rec, int(ports), int(blocks)), nil
 }
 
+// BlockTruePeak: one true-peak record (gdg_block_true_peak): the largest magnitude of a block of 8192 samples 4x oversampled -- its samples
+// and the three points a 24-tap windowed-sinc interpolator puts between two of them.  Position = 4*n + phase (phase 0: a sample) of the
+// first point that attains it; Overs counts the interpolated points above 1.
+type BlockTruePeak struct {
+	TruePeak float64
+	Position uint32
+	Overs    uint32
+}
+
+func goBlockTruePeak(p unsafe.Pointer, rows int, blocks int) [][]BlockTruePeak {
+	out := make([][]BlockTruePeak, rows)
+	if rows*blocks == 0 {
+		for r := range out {
+			out[r] = []BlockTruePeak{}
+		}
+		return out
+	}
+	recs := (*[1 << 26]C.gdg_block_true_peak)(p)[: rows*blocks : rows*blocks]
+	for r := range out {
+		out[r] = make([]BlockTruePeak, blocks)
+		for b := range out[r] {
+			c := recs[r*blocks+b]
+			out[r][b] = BlockTruePeak{float64(c.true_peak), uint32(c.position), uint32(c.overs)}
+		}
+	}
+	return out
+}
+
+// TruePeakTaps: the library's interpolation taps (gdg_true_peak_taps): result[phase-1][j+11] for phase 1, 2, 3 and j = -11 .. 12.
+// No context and no device are needed.
+func TruePeakTaps() ([3][24]float64, error) {
+	var out [3][24]float64
+	p := C.malloc(C.size_t(72 * 8))
+	if p == nil {
+		return out, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(p)
+	if rc := C.gdg_true_peak_taps((*C.double)(p), C.int(72)); rc != 0 {
+		return out, fmt.Errorf("gdg: gdg_true_peak_taps: %d", int(rc))
+	}
+	flat := (*[72]float64)(p)
+	for i := 0; i < 72; i++ {
+		out[i/24][i%24] = flat[i]
+	}
+	return out, nil
+}
+
+// BlockTruePeakRows: the true-peak records of equally long host rows, per block of 8192 samples (the last one of a row possibly short)
+// (gdg_block_true_peak_rows); result[row][block].
+func (this *Context) BlockTruePeakRows(rows [][]float64) ([][]BlockTruePeak, error) {
+	n := len(rows)
+	if n == 0 {
+		return [][]BlockTruePeak{}, nil
+	}
+	samples := len(rows[0])
+	blocks := (samples + 8191) / 8192
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	out := C.calloc(C.size_t(n*blocks+1), 16)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_true_peak_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), (*C.gdg_block_true_peak)(out))); e != nil {
+		return nil, e
+	}
+	return goBlockTruePeak(out, n, blocks), nil
+}
+
+// BlockTruePeakRowsDevice: the same on device memory, enqueued on the context's stream (gdg_block_true_peak_rows_device): row r at
+// dRows + r*rowStride float64 (any 8-byte alignment, rowStride >= samples), the records into dRecords[nRows][ceil(samples/8192)].
+func (this *Context) BlockTruePeakRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, dRecords unsafe.Pointer) error {
+	return this.err(C.gdg_block_true_peak_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples),
+		(*C.gdg_block_true_peak)(dRecords)))
+}
+
+// BatchTruePeakEnable: from the next batch call on, every batch call of the context keeps the true-peak records of what it rendered
+// (gdg_batch_true_peak_enable); off by default.  Configuration, like BatchReportEnable: a checkpoint does not carry it -- set it again
+// on the target of a resume -- and an error while a streamed job is open.
+func (this *Context) BatchTruePeakEnable(enable bool) error {
+	v := C.int(0)
+	if enable {
+		v = 1
+	}
+	return this.err(C.gdg_batch_true_peak_enable(this.ctx, v))
+}
+
+// BatchTruePeak: the true-peak records of the last completed batch call, result[port][block] (gdg_batch_true_peak); the ports and their
+// order are BatchReport's, the two finish calls included.  An error when the call ran without them.
+func (this *Context) BatchTruePeak() ([][]BlockTruePeak, error) {
+	var ports C.int
+	var blocks C.size_t
+	if e := this.err(C.gdg_batch_true_peak(this.ctx, nil, 0, &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	n := int(ports) * int(blocks)
+	if n == 0 {
+		return goBlockTruePeak(nil, int(ports), int(blocks)), nil
+	}
+	rec := C.calloc(C.size_t(n), 16)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	if e := this.err(C.gdg_batch_true_peak(this.ctx, (*C.gdg_block_true_peak)(rec), C.size_t(n), &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	return goBlockTruePeak(rec, int(ports), int(blocks)), nil
+}
+
 // BatchSetSources: the source map of the next batch calls (gdg_batch_set_sources): source[c] is the channel whose input entry channel c
 // reads -- c itself for a channel that reads its own, a root; any other entry makes c a reader, and its source must be a root.  One entry
 // per channel; nil or an empty slice clears the map.  A shared input is uploaded, decoded and resampled once and stored to every row

@@ -53,6 +53,8 @@ def lib():
             "gdgh_engine_last_batch_report": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_spectrum": (cs, [vp, vp, i32]),
             "gdgh_engine_set_batch_align": (cs, [vp, vp, i32, i32]),
+            "gdgh_engine_set_batch_true_peak": (None, [vp, i32]),
+            "gdgh_engine_last_batch_true_peak": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_last_batch_align": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_last_batch_spectrum": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t), C.POINTER(i32)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
@@ -122,6 +124,7 @@ class Engine:
         self.chains = []
         self.last_report = None          # the render report of the last batch call made with report=True: [N + 3, blocks] records
         self.last_spectrum = None        # the band spectrum of the last batch call made with spectrum=edges: [N + 3, blocks, bands] float64
+        self.last_true_peak = None       # the true-peak records of the last batch call made with true_peak=True: [N + 3, blocks] records
         self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
     def shards(self):
@@ -222,6 +225,21 @@ class Engine:
         _err(lib().gdgh_engine_last_batch_spectrum(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks), C.byref(bands)))
         return out
 
+    def _set_true_peak(self, true_peak):
+        """Engine::SetBatchTruePeak, from the `true_peak` argument of the batch calls"""
+        self.last_true_peak = None
+        lib().gdgh_engine_set_batch_true_peak(self._h, int(bool(true_peak)))
+        return bool(true_peak)
+
+    def _fetch_true_peak(self):
+        """Engine::LastBatchTruePeak -> [N + 3, blocks] records (the package's BLOCK_TRUE_PEAK_DTYPE)"""
+        import __graft_entry__ as entry
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_true_peak(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=entry.load_package().BLOCK_TRUE_PEAK_DTYPE)
+        _err(lib().gdgh_engine_last_batch_true_peak(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
     def _set_align(self, align):
         """Engine::SetBatchAlign, from the `align` argument of the batch calls: (ref over the job's N + 3 ports, max_lag) (None: off)"""
         self.last_align = None
@@ -256,17 +274,19 @@ class Engine:
         lib().gdgh_engine_set_batch_dither(self._h, 0 if seed is None else 1, 0 if seed is None else int(seed))
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
-        keep the alignment records in last_align ([N + 3, blocks]); over shards the master rows are zero records."""
+        keep the alignment records in last_align ([N + 3, blocks]); over shards the master rows are zero records.  true_peak: keep the
+        true-peak records in last_true_peak ([N + 3, blocks], the same order)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
+        peaked = self._set_true_peak(true_peak)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -301,17 +321,19 @@ class Engine:
             self.last_spectrum = self._fetch_spectrum()
         if aligned:
             self.last_align = self._fetch_align()
+        if peaked:
+            self.last_true_peak = self._fetch_true_peak()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces.  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align)
+                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -323,7 +345,7 @@ class Engine:
             lib().gdgh_free(p)
 
     def batch_stream_sharded(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False,
-                             tuner_enqueue=False, report=False, dither=None, resume=None, spectrum=None, align=None):
+                             tuner_enqueue=False, report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False):
         """Engine::BatchStreamShardedOpen / Need / Step / Close: batch_stream for an engine of any shard count -- every shard streams its
         channels, the master is finished per slice; yields every slice's N + 3 output pieces (blocks_per_slice: an int or a function
         (blocks_left) -> blocks).  report: as batch_stream's -- the chain rows come from the shards, the master from the finish, the
@@ -333,10 +355,10 @@ class Engine:
         return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
                                    L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
                                   out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report, dither, resume,
-                                  spectrum=spectrum, align=align)
+                                  spectrum=spectrum, align=align, true_peak=true_peak)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
@@ -344,6 +366,7 @@ class Engine:
         self._set_dither(dither)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
+        peaked = self._set_true_peak(true_peak)
         self.last_report = None
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
@@ -389,6 +412,9 @@ class Engine:
                 if aligned:
                     al = self._fetch_align()
                     self.last_align = al if self.last_align is None else np.concatenate([self.last_align, al], axis=1)
+                if peaked:
+                    tp = self._fetch_true_peak()
+                    self.last_true_peak = tp if self.last_true_peak is None else np.concatenate([self.last_true_peak, tp], axis=1)
                 yield outs
                 left -= blocks
         finally:

@@ -946,7 +946,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -966,7 +966,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); return ""; }
+    if (job == 0) { reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
     /* 2. the shards, concurrently: encoded chain outputs straight into the caller's buffers, partial master mixes as float64 */
     std::vector<std::vector<double>> left((size_t)G), right((size_t)G);
     std::vector<double> metronome(job, 0.0);
@@ -1020,6 +1020,8 @@ void Engine::reportBegin(size_t blocks) {
     spectrumValid_ = false;                              /* the band spectrum rides along: the same ports, blocks and three sources */
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
     if (!spectrumEdges_.empty()) lastSpectrum_.assign((size_t)(nChannels_ + 3) * blocks * (spectrumEdges_.size() - 1), 0.0);
+    truePeakValid_ = false;                              /* ... and the true-peak records: the report's ports, blocks and three sources */
+    if (truePeak_) lastTruePeak_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_true_peak{ 0.0, 0u, 0u });
     alignValid_ = false;                                 /* ... and so do the alignment records; the master's rows stay zero over shards */
     if (!alignRef_.empty()) lastAlign_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
 }
@@ -1075,6 +1077,24 @@ int Engine::applySpectrum(gdg_ctx *ctx) {
     return gdg_batch_spectrum_enable(ctx, spectrumEdges_.empty() ? nullptr : spectrumEdges_.data(), (int)spectrumEdges_.size());
 }
 
+/* `ports` x reportBlocks_ true-peak records of a context's last call, checked against what the engine expects */
+Error Engine::truePeakOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_true_peak> &rec) {
+    int p = 0;
+    size_t blocks = 0;
+    rec.assign((size_t)ports * reportBlocks_, gdg_block_true_peak{ 0.0, 0u, 0u });
+    if (gdg_batch_true_peak(ctx, rec.data(), rec.size(), &p, &blocks) != GDG_OK) return gdg_last_error(ctx);
+    if (p != ports || blocks != reportBlocks_) return format("true-peak records of %d ports x %zu blocks where %d x %zu were expected", p, blocks, ports, reportBlocks_);
+    return "";
+}
+
+Error Engine::LastBatchTruePeak(std::vector<gdg_block_true_peak> &records, int *ports, size_t *blocks) const {
+    if (!truePeakValid_) return "LastBatchTruePeak: the last batch call kept no true-peak records (SetBatchTruePeak comes before the call)";
+    records = lastTruePeak_;
+    if (ports) *ports = nChannels_ + 3;
+    if (blocks) *blocks = reportBlocks_;
+    return "";
+}
+
 /* `ports` x reportBlocks_ x bands values of a context's last call, checked against what the engine expects */
 Error Engine::spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val) {
     const int nb = (int)spectrumEdges_.size() - 1;
@@ -1092,6 +1112,14 @@ Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
     int first = 0, count = 0, ports = 0;
     size_t blocks = 0;
     shardRange(g, &first, &count);
+    if (truePeak_) {                                     /* the shard's true-peak records: chain rows to its channels, shard 0's last row to the metronome's */
+        std::vector<gdg_block_true_peak> rec;
+        Error e = truePeakOf(ctx, count + 1, rec);
+        if (!e.empty()) return e;
+        const size_t nb = reportBlocks_;
+        if (nb) memcpy(&lastTruePeak_[(size_t)first * nb], rec.data(), (size_t)count * nb * sizeof(gdg_block_true_peak));
+        if (g == 0 && nb) memcpy(&lastTruePeak_[(size_t)(nChannels_ + 2) * nb], &rec[(size_t)count * nb], nb * sizeof(gdg_block_true_peak));
+    }
     if (!alignRef_.empty()) {                            /* the shard's alignment records: the same two destinations */
         std::vector<gdg_block_align> rec;
         Error e = alignOf(ctx, count + 1, rec);
@@ -1120,6 +1148,13 @@ Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
 /* the finish's report (master left, master right) completes the call's */
 Error Engine::reportOfMaster(gdg_ctx *ctx) {
     alignValid_ = !alignRef_.empty();                    /* the finish has no alignment records: the shards' are the call's, the master rows zero */
+    if (truePeak_) {                                     /* the finish's two rows complete the call's true-peak records */
+        std::vector<gdg_block_true_peak> rec;
+        Error e = truePeakOf(ctx, 2, rec);
+        if (!e.empty()) return e;
+        if (reportBlocks_) memcpy(&lastTruePeak_[(size_t)nChannels_ * reportBlocks_], rec.data(), 2 * reportBlocks_ * sizeof(gdg_block_true_peak));
+        truePeakValid_ = true;
+    }
     if (!spectrumEdges_.empty()) {
         std::vector<double> val;
         Error e = spectrumOf(ctx, 2, val);
@@ -1213,7 +1248,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1243,6 +1278,11 @@ Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *o
         size_t nb = 0;
         if (gdg_batch_report(ctx, lastReport_.data(), lastReport_.size(), &ports, &nb) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         reportValid_ = true;
+    }
+    if (truePeak_) {                                     /* ... and so are its true-peak records */
+        Error te = truePeakOf(ctx, nChannels_ + 3, lastTruePeak_);
+        if (!te.empty()) { setError(te); return LastError(); }
+        truePeakValid_ = true;
     }
     if (!alignRef_.empty()) {                            /* ... and so are its alignment records */
         Error ae = alignOf(ctx, nChannels_ + 3, lastAlign_);
@@ -1432,7 +1472,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1760,6 +1800,22 @@ const char *gdgh_engine_last_batch_spectrum(void *e, double *bands, size_t capac
     if (bands) {
         if (capacity < val.size()) return ret(Error("LastBatchSpectrum: too little room for the bands"));
         if (!val.empty()) memcpy(bands, val.data(), val.size() * sizeof(double));
+    }
+    return ret(Error(""));
+}
+void gdgh_engine_set_batch_true_peak(void *e, int on) { ((Engine *)e)->SetBatchTruePeak(on != 0); }
+/* records == NULL: the two counts only */
+const char *gdgh_engine_last_batch_true_peak(void *e, gdg_block_true_peak *records, size_t capacity, int *ports, size_t *blocks) {
+    std::vector<gdg_block_true_peak> rec;
+    int p = 0;
+    size_t b = 0;
+    Error err = ((Engine *)e)->LastBatchTruePeak(rec, &p, &b);
+    if (!err.empty()) return ret(err);
+    if (ports) *ports = p;
+    if (blocks) *blocks = b;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchTruePeak: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_true_peak));
     }
     return ret(Error(""));
 }

@@ -261,6 +261,11 @@ public:
      * engine measures its master through BatchStreamOpen / Step).  A refused list leaves the one in force.  Not part of a checkpoint. */
     Error SetBatchAlign(const std::vector<int> &ref, int maxLag);
     Error LastBatchAlign(std::vector<gdg_block_align> &records, int *ports, size_t *blocks) const;
+    /* No reference counterpart.  The true-peak records (include/gdg.h, gdg_batch_true_peak_enable): the same calls keep [N + 3][blocks]
+     * records of the 4x oversampled peak in the report's port order whatever the shard count -- chain rows from the shards, the master's
+     * two from the finish, the metronome from shard 0.  Read when a job is set up, like the report's switch; not part of a checkpoint. */
+    void SetBatchTruePeak(bool on) { truePeak_ = on; }
+    Error LastBatchTruePeak(std::vector<gdg_block_true_peak> &records, int *ports, size_t *blocks) const;
     /* No reference counterpart.  Shared sources (include/gdg.h, gdg_batch_set_sources): source[c] = the JOB channel whose input entry channel
      * c reads, one entry per channel of the engine; an empty vector clears the map.  The engine splits the map per shard when a job is set
      * up (BatchRun, the Open and Resume calls).  A map spans one context: a reader whose root lives on another shard is refused here,
@@ -326,6 +331,9 @@ private:
     int applyAlign(int shard, gdg_ctx *ctx);               /* shard < 0: the plain form's list */
     Error alignOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_align> &rec);
     Error spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val);
+    bool truePeak_ = false, truePeakValid_ = false;        /* the true-peak records: asked for; the last call's, over reportBlocks_, are complete */
+    std::vector<gdg_block_true_peak> lastTruePeak_;
+    Error truePeakOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_true_peak> &rec);
     std::vector<int> sources_;                             /* the source map in job channel numbers; empty: none */
     int applySources(int shard, gdg_ctx *ctx);             /* the shard's part of it onto its context: a gdg_* status */
     bool dither_ = false;                                  /* SetBatchDither: on, and the seed */

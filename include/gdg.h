@@ -856,6 +856,69 @@ int gdg_block_align_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_s
 int gdg_batch_align_enable(gdg_ctx *ctx, const int *ref, int n_ports, int max_lag);
 int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int *ports, size_t *blocks);
 /*
+ * TRUE PEAK: no reference counterpart.  gdg_block_stats.peak is the largest SAMPLE; it cannot see the waveform between the samples.  A sine
+ * at a quarter of the sample rate whose samples fall 45 degrees off its crests reads peak = 0.707 A, and every DAC, sample-rate converter
+ * and lossy encoder downstream reconstructs A.  The true-peak record is the largest magnitude of the block 4x oversampled: its samples and
+ * the three points a 24-tap windowed-sinc interpolator puts between two of them.  From the same float64 rows, on the device; stateless
+ * like the record, the bands and the alignment record: a function of the block's samples and of nothing else.
+ * Block length L = 8192, oversampling factor 4, half-width H = 12.  A non-finite sample is taken as 0.  A short last block is just
+ * shorter (length l); it is not padded.
+ * Taps, for phase p = 1, 2, 3 and j = -H+1 .. H (24 per phase), with t = p/4 - j:
+ *   g_p[j] = sinc(t) * (0.5 + 0.5 cos(pi t / H)),  sinc(t) = sin(pi t) / (pi t);   h_p[j] = g_p[j] / sum_j g_p[j]
+ * built in float64 on the host, once (csrc/true_peak_taps.h), the normalising sum added in ascending j.  Each phase sums to 1: DC is exact.
+ * Interpolated points, for every n with H-1 <= n <= l-H-1:
+ *   v_p[n] = sum_j x[n + j] * h_p[j]                                    the value at position n + p/4
+ * accumulated from 0.0 in ascending j, every product and every add rounded on its own (no fused multiply-add, no use of the taps'
+ * symmetry).  Only points whose 24 samples all lie inside the block are evaluated: in each block the 11 sample intervals at either end
+ * are not looked at, and neither is the interval that crosses into the next block -- 23 intervals per block boundary, 0.28 % of the
+ * stream.  That is the price of statelessness, the price the alignment record pays with its central slice.  A block with l < 24 has no
+ * interpolated point.
+ */
+typedef struct {
+    double   true_peak;   /* max of |x[n]| over all l samples and of |v_p[n]| over all evaluated points; never below gdg_block_stats.peak; 0 for a silent block */
+    uint32_t position;    /* 4 n + p (p = 0 for a sample) of the FIRST point that attains it: a tie goes to the lower position; 0 when true_peak == 0 */
+    uint32_t overs;       /* interpolated points (p != 0) with |v| > 1; the samples' own overs are gdg_block_stats.clipped */
+} gdg_block_true_peak;    /* 16 bytes, little-endian, no padding */
+/*
+ * A value is a fixed-order sum over 24 samples and max is exact, so the record's 16 bytes are a function of the block's samples alone: not
+ * of the row, the grid, the block's place, the window, the slice or the shard.  Known answers (L = 8192):
+ *   an impulse of 1.0 at sample 4000                    true_peak 1.0, position 16000, overs 0; its two half-way neighbours read 0.633825
+ *   a constant 0.5                                      true_peak in [0.5, 0.5 (1 + 24 * 2^-52)], overs 0
+ *   0.9 sin(2 pi n / 4 + pi / 4)                        sample peak 0.636396, true_peak 0.900330 (the p = 2 gain at fs/4 is 1.000366),
+ *                                                       position = 2 (mod 4)
+ *   the gain of the three phases                        within 5e-4 of 1 up to 0.25 fs and within 1.5e-3 up to 0.35 fs (the worst, p = 2: +1.46e-3
+ *                                                       at fs/3), +0.5 % (p = 2) at 0.4 fs, -10 % (p = 2) at 0.45 fs
+ *   gdg_true_peak_taps(taps, capacity)                                 the library's table into taps[3][24] (phase 1, 2, 3; j ascending).
+ *                                                                      No context, no device.  GDG_ERR_INVALID when taps is NULL or
+ *                                                                      capacity < 72
+ *   gdg_block_true_peak_rows(ctx, rows, n_rows, samples, records)      n_rows >= 1 host rows of `samples` float64 each, in blocks of
+ *                                                                      8192 (the last of a row may be short); records:
+ *                                                                      [n_rows][ceil(samples / 8192)], row-major
+ *   gdg_block_true_peak_rows_device(ctx, d_rows, row_stride, n_rows, samples, d_records)
+ *                                                                      the same on device memory, enqueued on gdg_ctx_stream: row r
+ *                                                                      at d_rows + r * row_stride (row_stride >= samples, any 8-byte
+ *                                                                      alignment); no sample outside [row, row + samples) is read;
+ *                                                                      d_records is 8-byte aligned
+ *   gdg_batch_true_peak_enable(ctx, enable)                            from the next batch call on, every batch call of the context
+ *                                                                      keeps the true-peak records of what it rendered.  Off (the
+ *                                                                      default): no launch, allocation, upload or byte differs.
+ *                                                                      Configuration, like gdg_batch_report_enable: part of no blob
+ *                                                                      -- set it again on the target of a resume -- and
+ *                                                                      GDG_ERR_INVALID while a streamed job is open
+ *   gdg_batch_true_peak(ctx, records, capacity, &ports, &blocks)       the records of the LAST COMPLETED batch call of the context,
+ *                                                                      [ports][blocks] row-major; records == NULL: the two counts
+ *                                                                      only.  GDG_ERR_INVALID when capacity < ports * blocks (the
+ *                                                                      counts are filled in), or when there are no records
+ * Ports and their order are the render report's, call by call, the two finish calls included: they measure the sums the record measures
+ * (after the aux, before the encoder's clamp).  The rows are read before the dither.  The records come down with each step's own download,
+ * behind the alignment records; report, spectrum, alignment and true peak are independent switches.
+ */
+int gdg_true_peak_taps(double *taps, int capacity);
+int gdg_block_true_peak_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, gdg_block_true_peak *records);
+int gdg_block_true_peak_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, gdg_block_true_peak *d_records);
+int gdg_batch_true_peak_enable(gdg_ctx *ctx, int enable);
+int gdg_batch_true_peak(gdg_ctx *ctx, gdg_block_true_peak *records, size_t capacity, int *ports, size_t *blocks);
+/*
  * SHARED SOURCES: no reference counterpart.  Re-amping renders one take, or a handful, through hundreds of rigs: with a source map every
  * shared input is gathered, uploaded, decoded and (when its rate is not the job's) resampled ONCE and stored to the row of every channel
  * that reads it, instead of once per channel.
