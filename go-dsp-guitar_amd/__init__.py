@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "gdg_block_spectrum_rows", "gdg_block_spectrum_rows_device", "gdg_batch_spectrum_enable", "gdg_batch_spectrum",
     "gdg_block_align_rows", "gdg_block_align_rows_device", "gdg_batch_align_enable", "gdg_batch_align",
     "gdg_true_peak_taps", "gdg_block_true_peak_rows", "gdg_block_true_peak_rows_device", "gdg_batch_true_peak_enable", "gdg_batch_true_peak",
+    "gdg_batch_set_trim", "gdg_wave_encode_trim", "gdg_wave_encode_trim_device", "gdg_trim_from_true_peak",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -74,6 +75,21 @@ def true_peak_taps():
     if rc != GDG_OK:
         raise GdgError(rc, "gdg_true_peak_taps")
     return out
+
+
+def trim_from_true_peak(records, target, max_gain):
+    """gdg_trim_from_true_peak: the gain of every port from its true-peak records ([ports, blocks], BLOCK_TRUE_PEAK_DTYPE, as batch_true_peak
+    hands them out) -- 1.0 for a silent port, else min(target / the port's largest true_peak, max_gain).  Host arithmetic: no context, no
+    device.  GdgError for a NaN record (the message names the port) or a target / max_gain that is not finite and positive."""
+    rec = np.ascontiguousarray(records, dtype=BLOCK_TRUE_PEAK_DTYPE)
+    if rec.ndim != 2:
+        raise ValueError("records: [ports, blocks]")
+    gain = np.zeros(rec.shape[0], dtype=np.float64)
+    rc = lib().gdg_trim_from_true_peak(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], float(target), float(max_gain),
+                                       gain.ctypes.data if gain.size else None)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return gain
 
 
 ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
@@ -314,6 +330,10 @@ def lib():
             "gdg_batch_align_enable": (i32, [vp, vp, i32, i32]),
             "gdg_batch_align": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdg_true_peak_taps": (i32, [vp, i32]),
+            "gdg_batch_set_trim": (i32, [vp, vp, i32, C.c_double, C.c_double, C.c_double]),
+            "gdg_wave_encode_trim": (i32, [vp, i32, vp, C.c_size_t, C.c_double, i32, C.c_uint64, u32, C.c_uint64, vp]),
+            "gdg_wave_encode_trim_device": (i32, [vp, i32, vp, C.c_size_t, C.c_double, i32, C.c_uint64, u32, C.c_uint64, vp]),
+            "gdg_trim_from_true_peak": (i32, [vp, i32, C.c_size_t, C.c_double, C.c_double, vp]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1109,6 +1129,30 @@ class Context:
         """gdg_wave_encode_dither_device on plain device pointers (ints), enqueued on the context's stream."""
         f = WAVE_FORMATS[fmt] if isinstance(fmt, str) else fmt
         self._check(lib().gdg_wave_encode_dither_device(self._h, f, d_samples, n, int(mode), int(seed), int(port), int(first_index), d_bytes))
+
+    def batch_set_trim(self, chain_gain=None, master_left=1.0, master_right=1.0, metronome=1.0):
+        """The output trim of the next batch calls (gdg_batch_set_trim): a gain per output port in front of the encoders -- chain_gain: one per
+        channel of this context (None: all 1), then the job-wide ports.  y = x * g, rounded once, then the encoder; records, meters and
+        float64 rows stay as rendered.  All gains 1.0: off.  Configuration: not in a checkpoint."""
+        if chain_gain is None:
+            self._check(lib().gdg_batch_set_trim(self._h, None, 0, float(master_left), float(master_right), float(metronome)))
+            return
+        g = np.ascontiguousarray(chain_gain, dtype=np.float64).reshape(-1)
+        self._check(lib().gdg_batch_set_trim(self._h, g.ctypes.data if g.size else None, g.size, float(master_left), float(master_right), float(metronome)))
+
+    def wave_encode_trim(self, fmt, samples, gain, mode=0, seed=0, port=0, first_index=0):
+        """A mono row of float64 times `gain` -> bytes (gdg_wave_encode_trim): mode 0 the plain encoder, 1 the dithered one; sample i has
+        index first_index + i.  gain 1.0 gives wave_encode_dither's bytes."""
+        f = WAVE_FORMATS[fmt] if isinstance(fmt, str) else fmt
+        x = _f64(samples).reshape(-1)
+        out = np.empty(x.size * max(lib().gdg_wave_bytes_per_sample(f), 1), dtype=np.uint8)
+        self._check(lib().gdg_wave_encode_trim(self._h, f, x.ctypes.data, x.size, float(gain), int(mode), int(seed), int(port), int(first_index), out.ctypes.data))
+        return out
+
+    def wave_encode_trim_device(self, fmt, d_samples, n, d_bytes, gain, mode=0, seed=0, port=0, first_index=0):
+        """gdg_wave_encode_trim_device on plain device pointers (ints), enqueued on the context's stream."""
+        f = WAVE_FORMATS[fmt] if isinstance(fmt, str) else fmt
+        self._check(lib().gdg_wave_encode_trim_device(self._h, f, d_samples, n, float(gain), int(mode), int(seed), int(port), int(first_index), d_bytes))
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

@@ -114,6 +114,7 @@ struct BatchLoop {
     const gdg_spectrum_bands *bands;            /* the band spectrum: n_bands doubles per output row and block ride behind the records; null = off */
     const std::vector<gdg_align_pairs> *align;  /* the alignment report: the measured ports of this call, a launch's worth to a piece; null = off */
     bool true_peak;                             /* the true-peak records: 16 bytes per output row and block ride behind the alignment records */
+    const double *d_trim;                       /* the output trim: the gains of the window's N + 3 rows on the device; null = off */
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -300,16 +301,19 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_true_peak(d_metro, ws, 1u, (size_t)wb, true_peak_table(), tp + (size_t)N * w, ctx->stream));
             }
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
-            auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst) -> hipError_t {
-                if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
+            /* trim on: the trimmed siblings of either; `gain_row` = the launch's first row in the window's order (the order of the gains) */
+            auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, unsigned gain_row) -> hipError_t {
                 const gdg_dither_rows dz = { ctx->dither_seed, p.dither_first + off, port_base, n_chain };
+                if (p.d_trim)
+                    return gdg_launch_wave_encode_rows_trim(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, p.d_trim + gain_row, p.dither ? &dz : nullptr, ctx->stream);
+                if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
                 return gdg_launch_wave_encode_rows_dither(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, dz, ctx->stream);
             };
-            if (!sharded) HIP_TRY(ctx, encode_rows(d_win, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc));
+            if (!sharded) HIP_TRY(ctx, encode_rows(d_win, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, 0u));
             else {
-                HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc));
+                HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc, 0u));
                 if (shard->metronome_bytes)
-                    HIP_TRY(ctx, encode_rows(d_metro, 1u, 1u, GDG_DITHER_PORT_METRONOME, enc + (size_t)N * row_bytes));
+                    HIP_TRY(ctx, encode_rows(d_metro, 1u, 1u, GDG_DITHER_PORT_METRONOME, enc + (size_t)N * row_bytes, (unsigned)N + GDG_TRIM_METRONOME));
                 unsigned char *f64 = enc + (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15);
                 HIP_TRY(ctx, hipMemcpy2DAsync(f64, (size_t)wb * sizeof(double), d_master, ws * sizeof(double), (size_t)wb * sizeof(double), 2,
                                               hipMemcpyDeviceToDevice, ctx->stream));
@@ -462,6 +466,26 @@ int gdg_batch_set_dither(gdg_ctx *ctx, int mode, uint64_t seed, uint32_t port_ba
     ctx->dither_seed = seed;
     ctx->dither_port_base = port_base;
     ctx->dither_cursor = 0;
+    return GDG_OK;
+}
+
+/* the output trim: validated whole before it replaces the setting in force; read by every call that encodes (trim.h) */
+int gdg_batch_set_trim(gdg_ctx *ctx, const double *chain_gain, int n, double master_left, double master_right, double metronome) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set trim: a streamed batch run is open on this context; its setting holds until gdg_batch_stream_close");
+    if (!(chain_gain == nullptr && n == 0) && (chain_gain == nullptr || n != ctx->nch))
+        return fail(ctx, GDG_ERR_INVALID, "set trim: %d chain gains, the context has %d channels (NULL and 0: every chain gain 1)", n, ctx->nch);
+    const int bad = chain_gain ? gdg_trim_first_nonfinite(chain_gain, n) : -1;
+    if (bad >= 0) return fail(ctx, GDG_ERR_INVALID, "set trim: chain_gain[%d] = %g is not finite", bad, chain_gain[bad]);
+    const double wide[3] = { master_left, master_right, metronome };
+    static const char *const names[3] = { "master_left", "master_right", "metronome" };
+    const int bad_wide = gdg_trim_first_nonfinite(wide, 3);
+    if (bad_wide >= 0) return fail(ctx, GDG_ERR_INVALID, "set trim: %s = %g is not finite", names[bad_wide], wide[bad_wide]);
+    std::vector<double> gain((size_t)ctx->nch + 3, 1.0);
+    if (chain_gain) std::copy(chain_gain, chain_gain + n, gain.begin());
+    std::copy(wide, wide + 3, gain.begin() + ctx->nch);
+    if (gdg_trim_all_unit(gain.data(), (int)gain.size())) gain.clear();           /* off: as if never called */
+    ctx->trim_gain.swap(gain);
     return GDG_OK;
 }
 
@@ -817,7 +841,14 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, spectrum ? &bands : nullptr,
-                        align ? &pairs : nullptr, true_peak };
+                        align ? &pairs : nullptr, true_peak, nullptr };
+        /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
+        if (!ctx->trim_gain.empty()) {
+            if (!ctx->d_trim && hipMalloc((void **)&ctx->d_trim, (size_t)NO * sizeof(double)) != hipSuccess)
+                return fail(ctx, GDG_ERR_NOMEM, "the batch run cannot allocate the trim's %d gains on the device", NO);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_trim, ctx->trim_gain.data(), (size_t)NO * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            loop.d_trim = ctx->d_trim;
+        }
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -932,6 +963,9 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
         return report_end(ctx, fail(ctx, GDG_ERR_INVALID, "master mix: the band spectrum needs a positive sample rate"));
     if (samples == 0) return report_end(ctx, GDG_OK);
     const bool report = ctx->report_live, dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = !ctx->spec_live_edges.empty(), true_peak = ctx->tp_live;
+    /* the trim in force on the context that finishes: its two master gains, as kernel arguments */
+    const bool trim = !ctx->trim_gain.empty();
+    const double trim_left = trim ? ctx->trim_gain[(size_t)ctx->nch + GDG_TRIM_MASTER_LEFT] : 1.0, trim_right = trim ? ctx->trim_gain[(size_t)ctx->nch + GDG_TRIM_MASTER_RIGHT] : 1.0;
     enter(ctx);
     const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), sample_rate) : gdg_spectrum_bands();
     const size_t n_bands = spectrum ? (size_t)bands.n_bands : 0;
@@ -989,7 +1023,11 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
             HIP_TRY(ctx, hipEventRecord(ctx->fin_up[h], ctx->stream));
             {
                 ProfScope ps(ctx, GDG_K_WAVE);
-                if (!dither)
+                if (trim)                                                        /* the sums stay as they are; the encoder reads them times the gains */
+                    HIP_TRY(ctx, gdg_launch_finish_master_trim(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc,
+                                                               enc + piece * width, d_sums, piece, trim_left, trim_right, dither ? 1 : 0, ctx->dither_seed,
+                                                               dither_first + k * piece, ctx->stream));
+                else if (!dither)
                     HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc, enc + piece * width,
                                                           d_sums, piece, ctx->stream));
                 else                                                             /* the piece's first sample: dither_first + k * piece */

@@ -119,6 +119,66 @@ int gdg_wave_encode_dither(gdg_ctx *ctx, int format, const double *samples, size
     return GDG_OK;
 }
 
+/* the trimmed encoder on its own (trim.h): mono, y = x * gain in front of gdg_wave_encode_dither's encoder; gain 1.0 is that call itself */
+static int encode_trim_check(gdg_ctx *ctx, int format, int mode, double gain) {
+    if (!gdg_wave_bytes_per_sample(format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", format);
+    if (mode != 0 && mode != 1) return fail(ctx, GDG_ERR_INVALID, "encode trim: mode %d; 0 is the plain encoder, 1 is TPDF dither", mode);
+    if (!isfinite(gain)) return fail(ctx, GDG_ERR_INVALID, "encode trim: gain = %g is not finite", gain);
+    return GDG_OK;
+}
+
+int gdg_wave_encode_trim_device(gdg_ctx *ctx, int format, const double *d_samples, size_t n, double gain, int mode, uint64_t seed, uint32_t port,
+                                uint64_t first_index, void *d_bytes) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const int rc = encode_trim_check(ctx, format, mode, gain);
+    if (rc != GDG_OK) return rc;
+    if (gain == 1.0) return gdg_wave_encode_dither_device(ctx, format, d_samples, n, mode, seed, port, first_index, d_bytes);
+    if (n == 0) return GDG_OK;
+    if (!d_bytes || !d_samples) return GDG_ERR_INVALID;
+    if ((uintptr_t)d_samples & 7) return fail(ctx, GDG_ERR_INVALID, "encode trim: the samples are float64, 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    ProfScope ps(ctx, GDG_K_WAVE);
+    HIP_TRY(ctx, gdg_launch_wave_encode_trim(format, d_samples, n, d_bytes, gain, gdg_dither_applies(mode, format) ? 1 : 0, seed, port, first_index, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_wave_encode_trim(gdg_ctx *ctx, int format, const double *samples, size_t n, double gain, int mode, uint64_t seed, uint32_t port, uint64_t first_index,
+                         void *bytes) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = encode_trim_check(ctx, format, mode, gain);
+    if (rc != GDG_OK) return rc;
+    if (gain == 1.0) return gdg_wave_encode_dither(ctx, format, samples, n, mode, seed, port, first_index, bytes);
+    if (n == 0) return GDG_OK;
+    if (!bytes || !samples) return GDG_ERR_INVALID;
+    const size_t w = (size_t)gdg_wave_bytes_per_sample(format);
+    enter_keep_fir_sums(ctx);
+    rc = ensure_io(ctx, 0, n * w);
+    if (rc == GDG_OK) rc = ensure_io(ctx, 1, n * sizeof(double));
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_io[1], samples, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_wave_encode_trim_device(ctx, format, static_cast<const double *>(ctx->d_io[1]), n, gain, mode, seed, port, first_index, ctx->d_io[0]);
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(bytes, ctx->d_io[0], n * w, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
+/* the planner (trim.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
+int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_t blocks, double target, double max_gain, double *gain) {
+    static_assert(sizeof(gdg_block_true_peak) == 2 * sizeof(double) && offsetof(gdg_block_true_peak, true_peak) == 0, "the planner strides over true_peak in doubles");
+    int bad = -1;
+    char msg[160];
+    switch (gdg_trim_plan(reinterpret_cast<const double *>(records), 2, ports, blocks, target, max_gain, gain, &bad)) {
+    case GDG_TRIM_PLAN_OK: return GDG_OK;
+    case GDG_TRIM_PLAN_TARGET: snprintf(msg, sizeof msg, "trim from true peak: target = %g; finite and greater than 0", target); break;
+    case GDG_TRIM_PLAN_MAX_GAIN: snprintf(msg, sizeof msg, "trim from true peak: max_gain = %g; finite and greater than 0", max_gain); break;
+    case GDG_TRIM_PLAN_NAN: snprintf(msg, sizeof msg, "trim from true peak: port %d has a NaN true_peak", bad); break;
+    default: snprintf(msg, sizeof msg, "trim from true peak: %d ports, records %s, gain %s", ports, records ? "given" : "NULL", gain ? "given" : "NULL"); break;
+    }
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
+}
+
 /* resample/resample.go:72-87 */
 int gdg_resample_time_length(int input_length, uint32_t source_rate, uint32_t target_rate) {
     if (input_length < 0 || source_rate == 0 || target_rate == 0) return -1;

@@ -47,6 +47,7 @@
 #include "arena.h"
 #include "batch_sources.h"
 #include "dither.h"
+#include "trim.h"
 
 #define NUM_FILTERS 8
 
@@ -402,6 +403,11 @@ struct gdg_ctx {
     int dither_mode = 0;
     uint64_t dither_seed = 0, dither_cursor = 0;
     uint32_t dither_port_base = 0;
+    /* the output trim (gdg_batch_set_trim; trim.h): a gain per output port in front of the encoders -- the context's chain outputs, then
+     * master left, master right, metronome: nch + 3 entries, the rows of a batch window -- empty = off (never set, or every gain 1.0).  The
+     * device copy is made and uploaded at the start of a batch call, only while a trim is in force.  Configuration like the dither: in no blob. */
+    std::vector<double> trim_gain;
+    double *d_trim = nullptr;
     /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;
@@ -439,6 +445,10 @@ inline int fail(const gdg_ctx *ctx, int code, const char *fmt, ...) {       /* o
     }
     return code;
 }
+
+/* what a call without a context refuses (gdg_trim_from_true_peak): kept per thread, read by gdg_last_error(NULL) */
+inline std::string &free_error() { static thread_local std::string e; return e; }
+inline void set_free_error(const char *msg) { free_error() = msg; }
 
 /* Device-resident calls may leave their channel groups running on streams of their own (process_rows, `free_run`); whatever
  * touches the context next -- any entry point -- first makes the context's stream wait for them. */

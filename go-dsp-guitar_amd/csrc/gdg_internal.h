@@ -324,6 +324,19 @@ hipError_t gdg_launch_finish_master_dither(int fmt, const double *d_slab, size_t
 /* mono, any 8-byte alignment of d_in and any byte alignment of d_bytes (unaligned buffers and n % 4 go one sample per thread) */
 hipError_t gdg_launch_wave_encode_dither(int fmt, const double *d_in, size_t n, void *d_bytes, unsigned long long seed, unsigned port,
                                          unsigned long long first, hipStream_t s);
+/* The trimmed siblings of the encoders above (trim.h; include/gdg.h, gdg_batch_set_trim): every sample times its row's gain -- one rounded
+ * product -- and then the plain encoder (all six formats) or the dithered one (LPCM formats).  The callers send every call with the trim off
+ * to the launchers above, which stay as they are.  Rows: row r has gain d_gains[r] (device memory); `dither` null = the plain encoder.
+ * IEEE64 needs d_bytes 8-byte aligned. */
+hipError_t gdg_launch_wave_encode_rows_trim(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
+                                            const double *d_gains, const gdg_dither_rows *dither, hipStream_t s);
+/* the master: the gains are kernel arguments; the sums (d_sums) are taken before the trim; dither != 0: seed and first as above */
+hipError_t gdg_launch_finish_master_trim(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
+                                         void *d_right_bytes, double *d_sums, size_t sums_stride, double gain_left, double gain_right, int dither,
+                                         unsigned long long seed, unsigned long long first, hipStream_t s);
+/* mono, any 8-byte alignment of d_in and any byte alignment of d_bytes (unaligned buffers and n % 4 go one sample per thread) */
+hipError_t gdg_launch_wave_encode_trim(int fmt, const double *d_in, size_t n, void *d_bytes, double gain, int dither, unsigned long long seed,
+                                       unsigned port, unsigned long long first, hipStream_t s);
 hipError_t gdg_launch_metronome(const double *d_tick, unsigned n_tick, const double *d_tock, unsigned n_tock, double *d_out, int n,
                                 unsigned sc0, unsigned tc0, unsigned spb, unsigned beats, unsigned j0, hipStream_t s);
 /* the render report (include/gdg.h): one gdg_block_stats per block of `block` samples (the last of a row may be short) of n_rows rows of

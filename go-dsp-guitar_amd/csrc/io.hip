@@ -8,6 +8,7 @@
 #include "../../include/gdg.h"
 #include "gdg_internal.h"
 #include "dither.h"
+#include "trim.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -944,6 +945,264 @@ hipError_t gdg_launch_wave_encode_dither(int fmt, const double *d_in, size_t n, 
     case GDG_FMT_LPCM16: launch_encode_dither<GDG_FMT_LPCM16>(d_in, n, p, key, first, s); break;
     case GDG_FMT_LPCM24: launch_encode_dither<GDG_FMT_LPCM24>(d_in, n, p, key, first, s); break;
     case GDG_FMT_LPCM32: launch_encode_dither<GDG_FMT_LPCM32>(d_in, n, p, key, first, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * The trimmed encoders (trim.h; include/gdg.h, gdg_batch_set_trim): a gain per output port in front of the encoder.  No reference
+ * counterpart.  y = x * g is ONE __dmul_rn -- rounded before the encoder's scale sees it, never contracted with it -- and then the plain
+ * encoder's code (DITHER false: all six formats) or the dithered one's (DITHER true: the four LPCM formats) of y.  Siblings of the four
+ * encode paths and of the stand-alone form: the same 16-byte non-temporal loads, packing and word-sized non-temporal stores; the plain
+ * and the dithered kernels stay as they are and serve every call with the trim off.  A row's gain is uniform over its workgroup: read once
+ * from a small device array through the scalar unit (the rows kernel) or a kernel argument (the finish and the stand-alone form).  IEEE64
+ * has no code: the product's 8 bytes are the sample's (the plain path copies the rows; here a kernel has to touch them).
+ * One FP64 multiply per sample beside 8 bytes read and 1 .. 8 written: no atomics, no LDS, no scratch.
+ * ---------------------------------------------------------------------------------------------- */
+template <int FMT, bool DITHER>
+__device__ __forceinline__ unsigned trim_code(double y, unsigned long long key, unsigned long long at) {
+    if (DITHER) return gdg_dither_code(FMT, y, key, at);
+    return encode_code<FMT>(y);
+}
+
+/* four consecutive samples of one port times its gain, the first at index `at`, into W whole words */
+template <int FMT, bool DITHER>
+__device__ __forceinline__ void encode4_trim(const double (&r)[4], double g, unsigned long long key, unsigned long long at, unsigned (&w)[fmt_width<FMT>::W]) {
+    constexpr int W = fmt_width<FMT>::W;
+#pragma unroll
+    for (int k = 0; k < W; k++) w[k] = 0;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const unsigned code = trim_code<FMT, DITHER>(gdg_trim_apply(r[s], g), key, at + (unsigned long long)s);
+#pragma unroll
+        for (int k = 0; k < W; k++) {
+            int byte = s * W + k;
+            w[byte >> 2] |= ((code >> (8 * k)) & 0xffu) << ((byte & 3) * 8);
+        }
+    }
+}
+
+/* a group's four samples from their two 16-byte halves, trimmed, encoded and stored: `words` is the row's (or the side's) first word */
+template <int FMT, bool DITHER>
+__device__ __forceinline__ void store4_trim(v2d a, v2d b, double g, unsigned long long key, unsigned long long at, unsigned *words, size_t group) {
+    if (FMT == GDG_FMT_IEEE64) {
+        const v2d ya = { gdg_trim_apply(a.x, g), gdg_trim_apply(a.y, g) }, yb = { gdg_trim_apply(b.x, g), gdg_trim_apply(b.y, g) };
+        if (((uintptr_t)words & 15) == 0) {                            /* uniform: 16-byte stores where the row allows them, the 8-byte rule otherwise */
+            v2d *out = reinterpret_cast<v2d *>(words) + 2 * group;
+            __builtin_nontemporal_store(ya, out);
+            __builtin_nontemporal_store(yb, out + 1);
+        } else {
+            double *out = reinterpret_cast<double *>(words) + 4 * group;
+            __builtin_nontemporal_store(ya.x, out);
+            __builtin_nontemporal_store(ya.y, out + 1);
+            __builtin_nontemporal_store(yb.x, out + 2);
+            __builtin_nontemporal_store(yb.y, out + 3);
+        }
+    } else {
+        constexpr int W = fmt_width<FMT>::W;
+        const double r[4] = { a.x, a.y, b.x, b.y };
+        unsigned w[W];
+        encode4_trim<FMT, DITHER>(r, g, key, at, w);
+#pragma unroll
+        for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], words + group * W + k);
+    }
+}
+
+/* words of 32 bits per group of four samples */
+template <int FMT> struct trim_group_words { static const int N = FMT == GDG_FMT_IEEE64 ? 8 : fmt_width<FMT>::W; };
+
+/* wave_encode4_rows_kernel's and wave_encode4_rows_dither_kernel's sibling: blockIdx.y = row, gains[row] its gain */
+template <int FMT, bool DITHER>
+__global__ void __launch_bounds__(256)
+wave_encode4_rows_trim_kernel(const double *__restrict__ in, size_t row_stride, size_t groups_per_row, unsigned *__restrict__ words,
+                              const double *__restrict__ gains, gdg_dither_rows dz) {
+    const v2d *row = reinterpret_cast<const v2d *>(in + (size_t)blockIdx.y * row_stride);
+    unsigned *dst = words + (size_t)blockIdx.y * groups_per_row * trim_group_words<FMT>::N;
+    const double g = gains[blockIdx.y];
+    const unsigned long long key = DITHER ? gdg_dither_key(dz.seed, gdg_dither_row_port(dz.port_base, dz.n_chain, blockIdx.y)) : 0ull;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < groups_per_row; i += (size_t)gridDim.x * 256) {
+        v2d a = __builtin_nontemporal_load(row + 2 * i), b = __builtin_nontemporal_load(row + 2 * i + 1);
+        store4_trim<FMT, DITHER>(a, b, g, key, dz.first + 4ull * i, dst, i);
+    }
+}
+
+template <int FMT, bool DITHER>
+static void launch_encode_rows_trim(const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, unsigned char *p, const double *d_gains,
+                                    gdg_dither_rows dz, hipStream_t s) {
+    size_t groups = row_len / 4;
+    unsigned tiles = (unsigned)((groups + 255) / 256);
+    wave_encode4_rows_trim_kernel<FMT, DITHER><<<dim3(tiles, n_rows), dim3(256), 0, s>>>(d_in, row_stride, groups, reinterpret_cast<unsigned *>(p), d_gains, dz);
+}
+
+hipError_t gdg_launch_wave_encode_rows_trim(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
+                                            const double *d_gains, const gdg_dither_rows *dither, hipStream_t s) {
+    if (n_rows == 0 || row_len == 0) return hipSuccess;
+    if (!d_gains || ((uintptr_t)d_gains & 7) || (row_len & 3) || (row_stride & 1) || ((uintptr_t)d_in & 15) ||
+        ((uintptr_t)d_bytes & (fmt == GDG_FMT_IEEE64 ? 7 : 3)))
+        return hipErrorInvalidValue;
+    unsigned char *p = static_cast<unsigned char *>(d_bytes);
+    const gdg_dither_rows none = { 0, 0, 0, 0 };
+    if (dither) {
+        switch (fmt) {
+        case GDG_FMT_LPCM8: launch_encode_rows_trim<GDG_FMT_LPCM8, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
+        case GDG_FMT_LPCM16: launch_encode_rows_trim<GDG_FMT_LPCM16, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
+        case GDG_FMT_LPCM24: launch_encode_rows_trim<GDG_FMT_LPCM24, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
+        case GDG_FMT_LPCM32: launch_encode_rows_trim<GDG_FMT_LPCM32, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
+        default: return hipErrorInvalidValue;                  /* IEEE formats are never dithered */
+        }
+        return hipGetLastError();
+    }
+    switch (fmt) {
+    case GDG_FMT_LPCM8: launch_encode_rows_trim<GDG_FMT_LPCM8, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
+    case GDG_FMT_LPCM16: launch_encode_rows_trim<GDG_FMT_LPCM16, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
+    case GDG_FMT_LPCM24: launch_encode_rows_trim<GDG_FMT_LPCM24, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
+    case GDG_FMT_LPCM32: launch_encode_rows_trim<GDG_FMT_LPCM32, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
+    case GDG_FMT_IEEE32: launch_encode_rows_trim<GDG_FMT_IEEE32, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
+    case GDG_FMT_IEEE64: launch_encode_rows_trim<GDG_FMT_IEEE64, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+/* finish_master_kernel's and finish_master_dither_kernel's sibling: the same loads and the same adds in the same order; SUMS keeps the
+ * float64 sums for the meters and the records BEFORE the trim; the left side is encoded times gain_left, the right times gain_right */
+template <int FMT, bool SUMS, bool DITHER>
+__global__ void __launch_bounds__(256)
+finish_master_trim_kernel(const double *__restrict__ slab, size_t stride, int G, int has_aux, size_t groups, unsigned *__restrict__ words_left,
+                          unsigned *__restrict__ words_right, double *__restrict__ sums, size_t sums_stride, double gain_left, double gain_right,
+                          unsigned long long seed, unsigned long long first) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= groups) return;
+    const size_t rs = stride / 2;                                  /* v2d per row */
+    const v2d *col = reinterpret_cast<const v2d *>(slab) + 2 * g;
+    v2d xa = { 0.0, 0.0 }, xb = { 0.0, 0.0 };
+    if (has_aux) { const v2d *q = col + (size_t)(2 * G) * rs; xa = __builtin_nontemporal_load(q); xb = __builtin_nontemporal_load(q + 1); }
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+        const v2d *p = col + (size_t)(side * G) * rs;
+        v2d a = __builtin_nontemporal_load(p), b = __builtin_nontemporal_load(p + 1);
+#pragma unroll 4
+        for (int k = 1; k < G; k++) {
+            p += rs;
+            a += __builtin_nontemporal_load(p);
+            b += __builtin_nontemporal_load(p + 1);
+        }
+        if (has_aux) { a += xa; b += xb; }
+        if (SUMS) {
+            v2d *out = reinterpret_cast<v2d *>(sums + (size_t)side * sums_stride) + 2 * g;
+            out[0] = a;
+            out[1] = b;
+        }
+        unsigned *words = side ? words_right : words_left;
+        if (!words) continue;
+        const unsigned long long key = DITHER ? gdg_dither_key(seed, side ? GDG_DITHER_PORT_MASTER_RIGHT : GDG_DITHER_PORT_MASTER_LEFT) : 0ull;
+        store4_trim<FMT, DITHER>(a, b, side ? gain_right : gain_left, key, first + 4ull * g, words, g);
+    }
+}
+
+template <int FMT, bool DITHER>
+static void launch_finish_master_trim(const double *d_slab, size_t stride, int G, int has_aux, size_t n, void *d_left, void *d_right, double *d_sums,
+                                      size_t sums_stride, double gl, double gr, unsigned long long seed, unsigned long long first, hipStream_t s) {
+    const size_t groups = n / 4;
+    const unsigned grid = (unsigned)((groups + 255) / 256);
+    unsigned *wl = static_cast<unsigned *>(d_left), *wr = static_cast<unsigned *>(d_right);
+    if (d_sums) finish_master_trim_kernel<FMT, true, DITHER><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride, gl, gr, seed, first);
+    else finish_master_trim_kernel<FMT, false, DITHER><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, nullptr, 0, gl, gr, seed, first);
+}
+
+hipError_t gdg_launch_finish_master_trim(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
+                                         void *d_right_bytes, double *d_sums, size_t sums_stride, double gain_left, double gain_right, int dither,
+                                         unsigned long long seed, unsigned long long first, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n_shards < 1 || (n & 3) || n > stride || (stride & 1) || (sums_stride & 1) || (d_sums && n > sums_stride) || ((uintptr_t)d_slab & 15) ||
+        ((uintptr_t)d_left_bytes & 15) || ((uintptr_t)d_right_bytes & 15) || ((uintptr_t)d_sums & 15))
+        return hipErrorInvalidValue;
+#define GDG_FINISH_TRIM(F, D) launch_finish_master_trim<F, D>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, gain_left, gain_right, seed, first, s)
+    if (dither) {
+        switch (fmt) {
+        case GDG_FMT_LPCM8: GDG_FINISH_TRIM(GDG_FMT_LPCM8, true); break;
+        case GDG_FMT_LPCM16: GDG_FINISH_TRIM(GDG_FMT_LPCM16, true); break;
+        case GDG_FMT_LPCM24: GDG_FINISH_TRIM(GDG_FMT_LPCM24, true); break;
+        case GDG_FMT_LPCM32: GDG_FINISH_TRIM(GDG_FMT_LPCM32, true); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    switch (fmt) {
+    case GDG_FMT_LPCM8: GDG_FINISH_TRIM(GDG_FMT_LPCM8, false); break;
+    case GDG_FMT_LPCM16: GDG_FINISH_TRIM(GDG_FMT_LPCM16, false); break;
+    case GDG_FMT_LPCM24: GDG_FINISH_TRIM(GDG_FMT_LPCM24, false); break;
+    case GDG_FMT_LPCM32: GDG_FINISH_TRIM(GDG_FMT_LPCM32, false); break;
+    case GDG_FMT_IEEE32: GDG_FINISH_TRIM(GDG_FMT_IEEE32, false); break;
+    case GDG_FMT_IEEE64: GDG_FINISH_TRIM(GDG_FMT_IEEE64, false); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef GDG_FINISH_TRIM
+    return hipGetLastError();
+}
+
+/* the stand-alone mono form: wave_encode4_kernel's and wave_encode4_dither_kernel's sibling for the aligned bulk ... */
+template <int FMT, bool DITHER>
+__global__ void __launch_bounds__(256)
+wave_encode4_trim_kernel(const v2d *__restrict__ in, size_t groups, unsigned *__restrict__ words, double g, unsigned long long key, unsigned long long first) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (size_t)gridDim.x * 256) {
+        v2d a = __builtin_nontemporal_load(in + 2 * i), b = __builtin_nontemporal_load(in + 2 * i + 1);
+        store4_trim<FMT, DITHER>(a, b, g, key, first + 4ull * i, words, i);
+    }
+}
+
+/* ... and one sample per thread, 8-byte loads and byte stores: the n % 4 samples behind the bulk, or everything when a buffer is not aligned for it */
+template <int FMT, bool DITHER>
+__global__ void __launch_bounds__(256)
+wave_encode_trim_tail_kernel(const double *__restrict__ in, size_t n, unsigned char *__restrict__ data, double g, unsigned long long key, unsigned long long first) {
+    constexpr int BYTES = FMT == GDG_FMT_IEEE64 ? 8 : fmt_width<FMT>::W;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const double y = gdg_trim_apply(in[i], g);
+        unsigned long long bits;
+        if (FMT == GDG_FMT_IEEE64) bits = (unsigned long long)__double_as_longlong(y);
+        else bits = trim_code<FMT, DITHER>(y, key, first + (unsigned long long)i);
+#pragma unroll
+        for (int k = 0; k < BYTES; k++) data[i * BYTES + k] = (unsigned char)((bits >> (8 * k)) & 0xffu);
+    }
+}
+
+template <int FMT, bool DITHER>
+static void launch_encode_trim(const double *d_in, size_t n, unsigned char *p, double g, unsigned long long key, unsigned long long first, hipStream_t s) {
+    constexpr size_t BYTES = FMT == GDG_FMT_IEEE64 ? 8 : fmt_width<FMT>::W;
+    size_t done = 0;
+    if (n >= 4 && ((uintptr_t)p & (FMT == GDG_FMT_IEEE64 ? 7 : 3)) == 0 && ((uintptr_t)d_in & 15) == 0) {
+        const size_t groups = n / 4;
+        wave_encode4_trim_kernel<FMT, DITHER><<<(unsigned)((groups + 255) / 256), 256, 0, s>>>(reinterpret_cast<const v2d *>(d_in), groups, reinterpret_cast<unsigned *>(p), g, key, first);
+        done = groups * 4;
+    }
+    if (done < n)
+        wave_encode_trim_tail_kernel<FMT, DITHER><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + done * BYTES, g, key, first + done);
+}
+
+hipError_t gdg_launch_wave_encode_trim(int fmt, const double *d_in, size_t n, void *d_bytes, double gain, int dither, unsigned long long seed, unsigned port,
+                                       unsigned long long first, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if ((uintptr_t)d_in & 7) return hipErrorInvalidValue;
+    unsigned char *p = static_cast<unsigned char *>(d_bytes);
+    if (dither) {
+        const unsigned long long key = gdg_dither_key(seed, port);
+        switch (fmt) {
+        case GDG_FMT_LPCM8: launch_encode_trim<GDG_FMT_LPCM8, true>(d_in, n, p, gain, key, first, s); break;
+        case GDG_FMT_LPCM16: launch_encode_trim<GDG_FMT_LPCM16, true>(d_in, n, p, gain, key, first, s); break;
+        case GDG_FMT_LPCM24: launch_encode_trim<GDG_FMT_LPCM24, true>(d_in, n, p, gain, key, first, s); break;
+        case GDG_FMT_LPCM32: launch_encode_trim<GDG_FMT_LPCM32, true>(d_in, n, p, gain, key, first, s); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    switch (fmt) {
+    case GDG_FMT_LPCM8: launch_encode_trim<GDG_FMT_LPCM8, false>(d_in, n, p, gain, 0, first, s); break;
+    case GDG_FMT_LPCM16: launch_encode_trim<GDG_FMT_LPCM16, false>(d_in, n, p, gain, 0, first, s); break;
+    case GDG_FMT_LPCM24: launch_encode_trim<GDG_FMT_LPCM24, false>(d_in, n, p, gain, 0, first, s); break;
+    case GDG_FMT_LPCM32: launch_encode_trim<GDG_FMT_LPCM32, false>(d_in, n, p, gain, 0, first, s); break;
+    case GDG_FMT_IEEE32: launch_encode_trim<GDG_FMT_IEEE32, false>(d_in, n, p, gain, 0, first, s); break;
+    case GDG_FMT_IEEE64: launch_encode_trim<GDG_FMT_IEEE64, false>(d_in, n, p, gain, 0, first, s); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -1765,3 +1765,91 @@ func (this *Context) WaveEncodeDither(format int, samples []float64, mode int, s
 	rc := C.gdg_wave_encode_dither(this.ctx, C.int(format), (*C.double)(unsafe.Pointer(&samples[0])), C.size_t(len(samples)), C.int(mode), C.uint64_t(seed), C.uint32_t(port), C.uint64_t(firstIndex), unsafe.Pointer(&data[0]))
 	return data, this.err(rc)
 }
+
+// BatchSetTrim: the output trim of the next batch calls (gdg_batch_set_trim): a gain per output port in front of the encoders.  chainGain
+// has one entry per channel of this context (a shard passes its own channels'; nil or empty: every chain gain 1); masterLeft, masterRight
+// and metronome are the gains of the job-wide ports.  y = x * g, rounded once, then the encoder as ever; a negative gain inverts the
+// polarity.  Records, meters, float64 partials and the channel state stay as rendered.  All gains 1: off.  Configuration, like
+// BatchSetDither: a checkpoint does not carry it -- set it again on the target of a resume -- and an error while a streamed job is open.
+func (this *Context) BatchSetTrim(chainGain []float64, masterLeft float64, masterRight float64, metronome float64) error {
+	n := len(chainGain)
+	if n == 0 {
+		return this.err(C.gdg_batch_set_trim(this.ctx, nil, 0, C.double(masterLeft), C.double(masterRight), C.double(metronome)))
+	}
+	p := (*[1 << 28]C.double)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.double(0)))))
+	if p == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(p))
+	for i, v := range chainGain {
+		p[i] = C.double(v)
+	}
+	return this.err(C.gdg_batch_set_trim(this.ctx, &p[0], C.int(n), C.double(masterLeft), C.double(masterRight), C.double(metronome)))
+}
+
+// WaveEncodeTrim: one mono row times gain through the encoder (gdg_wave_encode_trim): mode 0 the plain encoder, 1 the dithered one of
+// WaveEncodeDither; sample i has index firstIndex + i.  gain 1 gives WaveEncodeDither's bytes.
+func (this *Context) WaveEncodeTrim(format int, samples []float64, gain float64, mode int, seed uint64, port uint32, firstIndex uint64) ([]byte, error) {
+	width := int(C.gdg_wave_bytes_per_sample(C.int(format)))
+	if width == 0 {
+		return nil, fmt.Errorf("gdg: unknown sample format %d", format)
+	}
+	data := make([]byte, len(samples)*width)
+	if len(samples) == 0 {
+		return data, nil
+	}
+	rc := C.gdg_wave_encode_trim(this.ctx, C.int(format), (*C.double)(unsafe.Pointer(&samples[0])), C.size_t(len(samples)), C.double(gain), C.int(mode), C.uint64_t(seed), C.uint32_t(port), C.uint64_t(firstIndex), unsafe.Pointer(&data[0]))
+	return data, this.err(rc)
+}
+
+// WaveEncodeTrimDevice: the same on device memory, enqueued on the context's stream (gdg_wave_encode_trim_device): any 8-byte alignment
+// of dSamples, any byte alignment of dBytes.
+func (this *Context) WaveEncodeTrimDevice(format int, dSamples unsafe.Pointer, n int, gain float64, mode int, seed uint64, port uint32, firstIndex uint64, dBytes unsafe.Pointer) error {
+	return this.err(C.gdg_wave_encode_trim_device(this.ctx, C.int(format), (*C.double)(dSamples), C.size_t(n), C.double(gain), C.int(mode), C.uint64_t(seed), C.uint32_t(port), C.uint64_t(firstIndex), unsafe.Pointer(dBytes)))
+}
+
+// TrimFromTruePeak: the gain of every port from its true-peak records (gdg_trim_from_true_peak), records[port][block] as BatchTruePeak
+// hands them out: 1 for a silent port, else min(target / the port's largest TruePeak, maxGain).  Host arithmetic: no context and no
+// device.  target and maxGain are finite and greater than 0; a NaN record is an error that names the port.
+func TrimFromTruePeak(records [][]BlockTruePeak, target float64, maxGain float64) ([]float64, error) {
+	ports := len(records)
+	gain := make([]float64, ports)
+	if ports == 0 {
+		return gain, nil
+	}
+	blocks := len(records[0])
+	for r, row := range records {
+		if len(row) != blocks {
+			return nil, fmt.Errorf("gdg: port %d has %d records, port 0 has %d", r, len(row), blocks)
+		}
+		for _, rec := range row {
+			if rec.TruePeak != rec.TruePeak {
+				return nil, fmt.Errorf("gdg: port %d has a NaN true peak", r)
+			}
+		}
+	}
+	rec := (*[1 << 26]C.gdg_block_true_peak)(C.calloc(C.size_t(ports*blocks+1), 16))
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	for r, row := range records {
+		for b, v := range row {
+			rec[r*blocks+b].true_peak = C.double(v.TruePeak)
+			rec[r*blocks+b].position = C.uint32_t(v.Position)
+			rec[r*blocks+b].overs = C.uint32_t(v.Overs)
+		}
+	}
+	out := (*[1 << 28]C.double)(C.calloc(C.size_t(ports), 8))
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(out))
+	if rc := C.gdg_trim_from_true_peak(&rec[0], C.int(ports), C.size_t(blocks), C.double(target), C.double(maxGain), &out[0]); rc != 0 {
+		return nil, fmt.Errorf("gdg: gdg_trim_from_true_peak: %d (target and maxGain: finite and greater than 0)", int(rc))
+	}
+	for i := range gain {
+		gain[i] = float64(out[i])
+	}
+	return gain, nil
+}

@@ -47,6 +47,8 @@ def lib():
             "gdgh_engine_batch_stream_sharded_close": (cs, [vp]),
             "gdgh_engine_set_batch_report": (None, [vp, i32]),
             "gdgh_engine_set_batch_dither": (None, [vp, i32, C.c_uint64]),
+            "gdgh_engine_set_batch_trim": (cs, [vp, vp, i32, C.c_double, C.c_double, C.c_double]),
+            "gdgh_engine_sync_chains": (cs, [vp, C.c_uint32]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
@@ -273,17 +275,52 @@ class Engine:
         (None: off); every shard gets its port_base from the engine, so the files do not depend on the shard count."""
         lib().gdgh_engine_set_batch_dither(self._h, 0 if seed is None else 1, 0 if seed is None else int(seed))
 
+    def _set_trim(self, trim):
+        """Engine::SetBatchTrim, from the `trim` argument of the batch calls: the gains of the job's N + 3 output ports in the files' order
+        (N chain outputs, master left, master right, metronome), or None: off.  Every shard gets its slice of the chain gains, the finishing
+        context the master's."""
+        if trim is None:
+            _err(lib().gdgh_engine_set_batch_trim(self._h, None, 0, 1.0, 1.0, 1.0))
+            return
+        g = np.ascontiguousarray(trim, dtype=np.float64).reshape(-1)
+        if g.size != self.n_channels + 3:
+            raise HostError("trim: %d gains for the job's %d ports" % (g.size, self.n_channels + 3))
+        n = self.n_channels
+        _err(lib().gdgh_engine_set_batch_trim(self._h, g.ctypes.data, n, float(g[n]), float(g[n + 1]), float(g[n + 2])))
+
+    def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
+        """Two passes over one job: every output file is written with the gain that brings its true peak to target_dbtp (dBTP), capped at
+        max_gain_db.  save_state; pass 1 renders with the true-peak records (and the report) on and every output skipped; the planner
+        (trim_from_true_peak) turns the records into gains; load_state; pass 2 renders with the trim.  Returns (outs, gains): the N + 3
+        output data sections and the N + 3 gains used.  The master's gains come from the finish's own records of pass 1, whatever the
+        shard count.  Pass 1's records stay in normalize_true_peak / normalize_report.  The state blob is the channels': a configured
+        metronome and the meters run on from pass 1.  kw: batch_run's other arguments (dither, run_meters ...)."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        rate = target_rate if sample_rate is None else sample_rate
+        _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
+        blob = self.save_state()
+        self.batch_run(inputs, target_rate, out_format, window=window, report=True, true_peak=True, skip_outputs=True,
+                       **{k: v for k, v in kw.items() if k not in ("report", "true_peak", "trim")})
+        self.normalize_true_peak, self.normalize_report = self.last_true_peak, self.last_report
+        gains = pkg.trim_from_true_peak(self.normalize_true_peak, 10.0 ** (target_dbtp / 20.0), 10.0 ** (max_gain_db / 20.0))
+        self.load_state(blob, rate)
+        outs = self.batch_run(inputs, target_rate, out_format, window=window, trim=gains, **{k: v for k, v in kw.items() if k != "trim"})
+        return outs, gains
+
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
         keep the alignment records in last_align ([N + 3, blocks]); over shards the master rows are zero records.  true_peak: keep the
-        true-peak records in last_true_peak ([N + 3, blocks], the same order)."""
+        true-peak records in last_true_peak ([N + 3, blocks], the same order).  trim: the N + 3 gains in front of the encoders (None:
+        off).  skip_outputs: every output pointer NULL -- the job renders and measures, nothing is written; returns None."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
+        self._set_trim(trim)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -310,8 +347,8 @@ class Engine:
             first, count = self.shard_range(g)
             if count > 0:
                 length = max(length, self.raw_context(g).batch_length(inputs[first:first + count], target_rate))
-        outs = [np.zeros(length * wo, dtype=np.uint8) for _ in range(n + 3)]
-        ptrs = (C.c_void_p * (n + 3))(*[(o.ctypes.data if o.size else None) for o in outs])
+        outs = None if skip_outputs else [np.zeros(length * wo, dtype=np.uint8) for _ in range(n + 3)]
+        ptrs = (C.c_void_p * (n + 3))(*([None] * (n + 3) if skip_outputs else [(o.ctypes.data if o.size else None) for o in outs]))
         samples = C.c_size_t(0)
         _err(lib().gdgh_engine_batch_run(self._h, arr, n, C.byref(opt), window, ptrs, C.byref(samples)))
         assert samples.value == length
@@ -326,14 +363,14 @@ class Engine:
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces.  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak)
+                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -345,7 +382,7 @@ class Engine:
             lib().gdgh_free(p)
 
     def batch_stream_sharded(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False,
-                             tuner_enqueue=False, report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False):
+                             tuner_enqueue=False, report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None):
         """Engine::BatchStreamShardedOpen / Need / Step / Close: batch_stream for an engine of any shard count -- every shard streams its
         channels, the master is finished per slice; yields every slice's N + 3 output pieces (blocks_per_slice: an int or a function
         (blocks_left) -> blocks).  report: as batch_stream's -- the chain rows come from the shards, the master from the finish, the
@@ -355,15 +392,16 @@ class Engine:
         return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
                                    L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
                                   out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report, dither, resume,
-                                  spectrum=spectrum, align=align, true_peak=true_peak)
+                                  spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
+        self._set_trim(trim)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)

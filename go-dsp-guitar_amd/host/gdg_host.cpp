@@ -890,6 +890,29 @@ Error Engine::LoadState(const uint8_t *blob, size_t bytes, uint32_t sampleRate) 
     return "";
 }
 
+/* the device side of every chain brought up to date at sampleRate, as before a Process call: what SaveState then saves has the layout
+ * LoadState will find (RenderNormalized's first step on an engine that has not processed yet) */
+Error Engine::SyncChains(uint32_t sampleRate) {
+    std::vector<std::shared_ptr<signal::Chain>> chains;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        chains = chains_;
+    }
+    for (int g = 0; g < shards(); g++) {
+        int first = 0, count = 0;
+        shardRange(g, &first, &count);
+        if (count <= 0) continue;
+        std::lock_guard<std::mutex> lk(shards_[(size_t)g]->mu);
+        if (!context(g)) return LastError();
+        std::vector<signal::Chain *> mine;
+        for (auto &ch : chains)
+            if (shardOf(ch->channel()) == g) mine.push_back(ch.get());
+        Error e = sync(g, mine, sampleRate);
+        if (!e.empty()) return e;
+    }
+    return "";
+}
+
 Error Engine::SetBatchSources(const std::vector<int> &source) {
     if (source.empty()) { sources_.clear(); return ""; }
     if ((int)source.size() != nChannels_) return format("SetBatchSources: a map of %zu entries for %d channels", source.size(), nChannels_);
@@ -921,6 +944,31 @@ int Engine::applyDither(int shard, gdg_ctx *ctx) {
     return gdg_batch_set_dither(ctx, dither_ ? 1 : 0, ditherSeed_, dither_ ? (uint32_t)first : 0u);
 }
 
+/* Engine::SetBatchTrim: the job's N chain gains and the three job-wide ones, validated whole before they replace the ones in force */
+Error Engine::SetBatchTrim(const std::vector<double> &chainGain, double masterLeft, double masterRight, double metronome) {
+    if (!chainGain.empty() && (int)chainGain.size() != nChannels_)
+        return format("SetBatchTrim: %zu chain gains for %d channels (none: every chain gain 1)", chainGain.size(), nChannels_);
+    for (size_t c = 0; c < chainGain.size(); c++) if (!std::isfinite(chainGain[c])) return format("SetBatchTrim: the gain of channel %zu is not finite", c);
+    if (!std::isfinite(masterLeft) || !std::isfinite(masterRight) || !std::isfinite(metronome)) return "SetBatchTrim: a job-wide gain is not finite";
+    std::vector<double> gain((size_t)nChannels_ + 3, 1.0);
+    std::copy(chainGain.begin(), chainGain.end(), gain.begin());
+    gain[(size_t)nChannels_] = masterLeft;
+    gain[(size_t)nChannels_ + 1] = masterRight;
+    gain[(size_t)nChannels_ + 2] = metronome;
+    trim_.swap(gain);
+    return "";
+}
+
+/* the shard's slice of the chain gains onto its context; the job-wide gains go to shard 0's, which runs the metronome and finishes the master */
+int Engine::applyTrim(int shard, gdg_ctx *ctx) {
+    if (trim_.empty()) return gdg_batch_set_trim(ctx, nullptr, 0, 1.0, 1.0, 1.0);
+    int first = 0, count = 0;
+    shardRange(shard, &first, &count);
+    const size_t N = (size_t)nChannels_;
+    const bool wide = shard == 0;
+    return gdg_batch_set_trim(ctx, trim_.data() + first, count, wide ? trim_[N] : 1.0, wide ? trim_[N + 1] : 1.0, wide ? trim_[N + 2] : 1.0);
+}
+
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
  * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
  * controller.go:3005-3045). */
@@ -946,7 +994,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1248,7 +1296,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1472,7 +1520,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1782,6 +1830,11 @@ const char *gdgh_engine_set_batch_sources(void *e, const int *source, int n) {
     return ret(((Engine *)e)->SetBatchSources(source && n > 0 ? std::vector<int>(source, source + n) : std::vector<int>()));
 }
 void gdgh_engine_set_batch_dither(void *e, int on, uint64_t seed) { ((Engine *)e)->SetBatchDither(seed, on != 0); }
+const char *gdgh_engine_sync_chains(void *e, uint32_t sample_rate) { return ret(((Engine *)e)->SyncChains(sample_rate)); }
+/* chain_gain == NULL or n == 0: every chain gain 1 */
+const char *gdgh_engine_set_batch_trim(void *e, const double *chain_gain, int n, double master_left, double master_right, double metronome) {
+    return ret(((Engine *)e)->SetBatchTrim(chain_gain && n > 0 ? std::vector<double>(chain_gain, chain_gain + n) : std::vector<double>(), master_left, master_right, metronome));
+}
 void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchReport(on != 0); }
 /* n == 0: off */
 const char *gdgh_engine_set_batch_spectrum(void *e, const double *edges, int n) {

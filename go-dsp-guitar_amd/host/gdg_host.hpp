@@ -276,6 +276,15 @@ public:
      * a job is set up (BatchRun, the Open and Resume calls) and keeps the master cursor over the slices of a sharded streamed job (a resumed
      * one seeks to the samples done): an engine of any shard count writes the files of one shard.  on = false: the plain encoders. */
     void SetBatchDither(uint64_t seed, bool on = true) { dither_ = on; ditherSeed_ = seed; }
+    /* No reference counterpart.  The output trim (include/gdg.h, gdg_batch_set_trim): a gain per output port in front of the encoders, in the
+     * job's channel numbers -- chainGain has one entry per channel of the engine (or none: every chain gain 1).  When a job is set up
+     * (BatchRun, the Open and Resume calls) every shard gets its own slice of the chain gains; the two master gains and the metronome's
+     * go to shard 0's context, which runs the metronome and finishes the master.  Records, meters and float64 partials stay as rendered.
+     * A wrong count or a gain that is not finite is refused and the gains in force stay.  All gains 1.0: off. */
+    /* the device side of every chain brought up to date at sampleRate without processing anything: a SaveState behind it saves the layout
+     * a later LoadState finds, also on an engine that has not processed yet (the two-pass render saves before its first pass) */
+    Error SyncChains(uint32_t sampleRate);
+    Error SetBatchTrim(const std::vector<double> &chainGain, double masterLeft = 1.0, double masterRight = 1.0, double metronome = 1.0);
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -339,6 +348,8 @@ private:
     bool dither_ = false;                                  /* SetBatchDither: on, and the seed */
     uint64_t ditherSeed_ = 0;
     int applyDither(int shard, gdg_ctx *ctx);              /* mode, seed and the shard's port_base onto its context: a gdg_* status */
+    std::vector<double> trim_;                             /* SetBatchTrim: N chain gains, master left, master right, metronome; empty: off */
+    int applyTrim(int shard, gdg_ctx *ctx);                /* the shard's slice of it onto its context: a gdg_* status */
     void reportBegin(size_t blocks);
     Error reportOfShard(int shard, gdg_ctx *ctx);
     Error reportOfMaster(gdg_ctx *ctx);

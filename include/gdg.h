@@ -997,6 +997,65 @@ int gdg_wave_encode_dither(gdg_ctx *ctx, int format, const double *samples, size
                            void *bytes);
 int gdg_wave_encode_dither_device(gdg_ctx *ctx, int format, const double *d_samples, size_t n, int mode, uint64_t seed, uint32_t port,
                                   uint64_t first_index, void *d_bytes);
+/*
+ * TRIM: no reference counterpart.  The batch calls measure what they render -- peak, RMS and clip counts, bands, lag and polarity, true peak
+ * -- and the trim acts on those numbers where it costs nothing and loses nothing: one gain per output port in front of the encoders, read
+ * from the float64 rows as they lie on the device.  A file that would clip in the encoder's clamp is written below full scale instead, a
+ * quiet rig keeps the bits a 16-bit truncation would drop, an inverted rig is written upright.  Stateless per sample: no place in the
+ * checkpoint, no rule for windows, slices or shards, no change to the container version.
+ *   gdg_batch_set_trim(ctx, chain_gain, n, master_left, master_right, metronome)
+ *                                                      chain_gain: n gains, n = the context's channel count -- the gains of the
+ *                                                      context's OWN chain outputs (a shard passes its own channels');
+ *                                                      chain_gain == NULL with n == 0: every chain gain is 1.  The three scalars are
+ *                                                      the gains of the job-wide ports.  Every gain is finite; a negative gain inverts
+ *                                                      the polarity; zero is allowed.
+ * GDG_ERR_INVALID, with gdg_last_error naming the offending entry, and the setting in force unchanged: a gain that is not finite, a wrong
+ * n, a call while a streamed job is open.
+ * OFF: all gains equal to 1.0, or never called.  Off, no launch, allocation, upload or byte differs from a context that never heard of
+ * the call; option stat_batch_device_kib is unchanged and the existing kernels are dispatched unchanged.
+ * Configuration, like gdg_batch_set_dither: it holds from the next batch call on, survives batch calls and is part of no blob -- set it
+ * again on the target of a resume.
+ * DEFINITION, for a sample x of a port with gain g:
+ *   y = x * g                                          ONE IEEE-754 double multiply, rounded once; never contracted with what follows (no
+ *                                                      fused multiply-add with the encoder's scale S)
+ * and the encoder does with y exactly what it does with x without a trim: the plain encoders clamp, scale and truncate toward zero; the
+ * dither encoders (DITHER, above) compute t = S * clamp1(y), q = floor((t + d) + 0.5) with the noise d of the same (seed, port, index);
+ * IEEE32 and IEEE64 go through their conversion and clipping rule, applied to y (IEEE32: (float)clamp1(y); IEEE64: y's 8 bytes).  A gain
+ * of exactly 1.0 gives the bytes of off for every finite sample.
+ * WHERE:
+ *   gdg_batch_run, gdg_batch_stream_step                           the N chain outputs, master left, master right, metronome
+ *   gdg_batch_run_shard, gdg_batch_stream_step_shard               the n chain outputs and metronome_bytes
+ *   gdg_batch_finish_master, gdg_batch_finish_master_slice         left_bytes and right_bytes, with the master_left / master_right gains
+ *                                                                  of the context that finishes
+ * WHAT NEVER CHANGES: the float64 rows, the master mix, a shard's float64 partial master and its float64 metronome, the meters, the tuner
+ * rings, the channel state, and all four record kinds -- report, spectrum, alignment, true peak: they describe the render, BEFORE the trim.
+ * Nothing changes for a NULL in out_bytes.
+ * What lets a caller predict the written file: rounding is monotone, so the largest written magnitude of a block is exactly
+ * fl(|g| * peak), clamped to 1 (peak: gdg_block_stats.peak); and with |g| * true_peak <= 1 no sample of the file is clipped.
+ * Known answer: dither on, seed 0x63, port 3, index 8192, x = 2e-5, g = 0.5 gives DITHER's codes of x = 1e-5 -- LPCM16 code 0, LPCM24 code
+ * 83 (a scaling by a power of two commutes with rounding).
+ * The encoder on its own, mono, the sibling of gdg_wave_encode_dither(_device) with its alignment rules:
+ *   gdg_wave_encode_trim(ctx, format, samples, n, gain, mode, seed, port, first_index, bytes)            host buffers, blocking
+ *   gdg_wave_encode_trim_device(ctx, format, d_samples, n, gain, mode, seed, port, first_index, d_bytes) enqueued on gdg_ctx_stream
+ * gain == 1.0 gives gdg_wave_encode_dither's bytes; mode 0 is the plain encoder applied to x * gain.  A gain that is not finite is
+ * GDG_ERR_INVALID.
+ * THE PLANNER, pure host arithmetic (csrc/trim.h), no context and no device:
+ *   gdg_trim_from_true_peak(records, ports, blocks, target, max_gain, gain)
+ *                                                      records: [ports][blocks] as gdg_batch_true_peak hands them out; gain: ports
+ *                                                      doubles.  For each port m = the largest true_peak over its blocks; m == 0:
+ *                                                      gain = 1.0; otherwise gain = min(target / m, max_gain).  blocks == 0: every
+ *                                                      gain 1.0.  target and max_gain are finite and greater than 0; a NaN true_peak in
+ *                                                      a record is refused: GDG_ERR_INVALID, nothing of `gain` written, and
+ *                                                      gdg_last_error(NULL) of the calling thread names the port.
+ * Known answers: maxima {0.5, 2.0, 0}, target 0.891250938, max_gain 4 give {1.782501876, 0.445625469, 1.0}; maxima {0.01}, the same
+ * target and max_gain, give {4.0}.
+ */
+int gdg_batch_set_trim(gdg_ctx *ctx, const double *chain_gain, int n, double master_left, double master_right, double metronome);
+int gdg_wave_encode_trim(gdg_ctx *ctx, int format, const double *samples, size_t n, double gain, int mode, uint64_t seed, uint32_t port,
+                         uint64_t first_index, void *bytes);
+int gdg_wave_encode_trim_device(gdg_ctx *ctx, int format, const double *d_samples, size_t n, double gain, int mode, uint64_t seed, uint32_t port,
+                                uint64_t first_index, void *d_bytes);
+int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_t blocks, double target, double max_gain, double *gain);
 
 #ifdef __cplusplus
 
