@@ -108,12 +108,11 @@ struct BatchLoop {
     int trace;
     double t_begin;
     size_t job_blocks, origin_blocks;           /* the slice of a job of job_blocks blocks that starts at block origin_blocks */
-    bool report;                                /* the render report: a record per output row and block rides behind each step's bytes */
+    ReportLive live;                            /* the render report's kinds this call collects: their sections ride behind each step's bytes (report_sections.h) */
     bool dither;                                /* the dithered encoders (gdg_batch_set_dither in force and an LPCM out_format) ... */
     uint64_t dither_first;                      /* ... and the job's sample index of this loop's first sample */
-    const gdg_spectrum_bands *bands;            /* the band spectrum: n_bands doubles per output row and block ride behind the records; null = off */
+    const gdg_spectrum_bands *bands;            /* the band spectrum's launch argument; null = off */
     const std::vector<gdg_align_pairs> *align;  /* the alignment report: the measured ports of this call, a launch's worth to a piece; null = off */
-    bool true_peak;                             /* the true-peak records: 16 bytes per output row and block ride behind the alignment records */
     const double *d_trim;                       /* the output trim: the gains of the window's N + 3 rows on the device; null = off */
 };
 
@@ -154,7 +153,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; };
+    struct Step { size_t off; int w; ReportSections sec; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -166,39 +165,34 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w });
+        steps.push_back({ off, w, {} });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
      * scatter of piece c runs while piece c + 1 is on the bus -- the run's tail (last download, then last scatter) and its head are that
      * much shorter; in between the device sets the pace either way. */
-    /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; with the render report the step's records follow
-     * at the next 16 bytes, [rows][w] -- N + 3 rows, a shard's N chain rows and the metronome's -- and come down with the last piece */
+    /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; behind them one section per live kind of the render
+     * report, [rows][w] -- N + 3 rows, a shard's N chain rows and the metronome's -- which come down with the last piece */
     auto down_bytes = [&](size_t i) {
         const size_t wb = (size_t)steps[i].w * B, row_bytes = wb * out_width;
         return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NO * row_bytes;
     };
     const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NO;
-    auto rec_at = [&](size_t i) { return (down_bytes(i) + 15) & ~(size_t)15; };
-    auto rec_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_stats); };
-    /* ... and with the band spectrum the step's bands, [rows][w][n_bands], at the next 16 bytes behind the records (behind the rows when the
-     * report is off): they come down with the last piece too */
+    for (size_t i = 0; i < steps.size(); i++) steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
+    /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
+     * the measured ports' are written, and read */
+    std::vector<size_t> filed[REPORT_KINDS];
+    for (int k = 0; k < REPORT_KINDS; k++) {
+        if (!p.live.on(k)) continue;
+        if (k == REPORT_ALIGN) { for (const gdg_align_pairs &q : *p.align) for (int j = 0; j < q.n; j++) filed[k].push_back((size_t)q.port[j]); }
+        else for (size_t o = 0; o < ((sharded && !run_metro) ? (size_t)N : rec_rows); o++) filed[k].push_back(o);
+    }
     const size_t n_bands = p.bands ? (size_t)p.bands->n_bands : 0;
-    auto spec_at = [&](size_t i) { return ((p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i)) + 15) & ~(size_t)15; };
-    auto spec_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * n_bands * sizeof(double); };
     const double *spec_win = nullptr;
     double2 *spec_tw = nullptr, *spec_tw2 = nullptr;
     if (p.bands && (r = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2)) != GDG_OK) return r;
-    /* ... and with the alignment report the step's records of that kind, [rows][w], at the next 16 bytes behind the bands (behind the records,
-     * or the rows, when those switches are off): the last piece brings them as well.  Only the measured ports' are written, and read */
-    auto align_at = [&](size_t i) { return ((p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i)) + 15) & ~(size_t)15; };
-    auto align_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_align); };
     double2 *align_tw = nullptr, *align_tw2 = nullptr;
     if (p.align && (r = fir_tables(ctx, GDG_ALIGN_BLOCK, &align_tw, &align_tw2)) != GDG_OK) return r;
-    /* ... and with the true-peak switch the step's records of that kind, [rows][w], at the next 16 bytes behind whatever precedes them */
-    auto before_tp = [&](size_t i) { return p.align ? align_at(i) + align_bytes(i) : p.bands ? spec_at(i) + spec_bytes(i) : p.report ? rec_at(i) + rec_bytes(i) : down_bytes(i); };
-    auto tp_at = [&](size_t i) { return (before_tp(i) + 15) & ~(size_t)15; };
-    auto tp_bytes = [&](size_t i) { return rec_rows * (size_t)steps[i].w * sizeof(gdg_block_true_peak); };
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
     auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
@@ -221,30 +215,8 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 }
             }, row_bytes);
         }
-        if (p.report) {                                                      /* the last piece brought the step's records */
-            const gdg_block_stats *rec = reinterpret_cast<const gdg_block_stats *>(src + rec_at(i));
-            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
-            const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;      /* a shard without the metronome: that row stays zero */
-            for (size_t o = 0; o < rows; o++) memcpy(&ctx->report[o * ctx->report_blocks + b0], rec + o * w, w * sizeof(gdg_block_stats));
-        }
-        if (p.bands) {                                                       /* ... and the step's bands, filed under the step's blocks */
-            const double *sp = reinterpret_cast<const double *>(src + spec_at(i));
-            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
-            const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;
-            for (size_t o = 0; o < rows; o++) memcpy(&ctx->spectrum[(o * ctx->spec_blocks + b0) * n_bands], sp + o * w * n_bands, w * n_bands * sizeof(double));
-        }
-        if (p.align) {                                                       /* ... and the measured ports' alignment records; the others stay zero */
-            const gdg_block_align *al = reinterpret_cast<const gdg_block_align *>(src + align_at(i));
-            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
-            for (const gdg_align_pairs &q : *p.align)
-                for (int k = 0; k < q.n; k++) memcpy(&ctx->align[(size_t)q.port[k] * ctx->align_blocks + b0], al + (size_t)q.port[k] * w, w * sizeof(gdg_block_align));
-        }
-        if (p.true_peak) {                                                   /* ... and the step's true-peak records, as the report's are filed */
-            const gdg_block_true_peak *tp = reinterpret_cast<const gdg_block_true_peak *>(src + tp_at(i));
-            const size_t w = (size_t)steps[i].w, b0 = steps[i].off / B;
-            const size_t rows = (sharded && !run_metro) ? (size_t)N : rec_rows;      /* a shard without the metronome: that row stays zero */
-            for (size_t o = 0; o < rows; o++) memcpy(&ctx->true_peak[o * ctx->tp_blocks + b0], tp + o * w, w * sizeof(gdg_block_true_peak));
-        }
+        for (int k = 0; k < REPORT_KINDS; k++)                               /* the last piece brought the step's sections: filed under the step's blocks */
+            if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -280,13 +252,14 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         {
             ProfScope ps(ctx, GDG_K_WAVE);
             const size_t row_bytes = (size_t)wb * out_width;
-            if (p.report) {                                                  /* the rows as the encoder is about to read them */
-                gdg_block_stats *rec = reinterpret_cast<gdg_block_stats *>(enc + rec_at(i));
+            const ReportSections &sec = steps[i].sec;
+            if (p.live.on(REPORT_STATS)) {                                   /* the rows as the encoder is about to read them */
+                gdg_block_stats *rec = reinterpret_cast<gdg_block_stats *>(enc + sec.at[REPORT_STATS]);
                 HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, (unsigned)B, rec, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_stats(d_metro, ws, 1u, (size_t)wb, (unsigned)B, rec + (size_t)N * w, ctx->stream));
             }
             if (p.bands) {                                                   /* the same rows, one more reader */
-                double *sp = reinterpret_cast<double *>(enc + spec_at(i));
+                double *sp = reinterpret_cast<double *>(enc + sec.at[REPORT_BANDS]);
                 HIP_TRY(ctx, gdg_launch_block_spectrum(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp, ctx->stream));
                 if (sharded && run_metro)
                     HIP_TRY(ctx, gdg_launch_block_spectrum(d_metro, ws, 1u, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp + (size_t)N * w * n_bands, ctx->stream));
@@ -294,9 +267,9 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             if (p.align)                                                     /* ... and one more: a shard's metronome port is row N + 2, as d_metro is */
                 for (const gdg_align_pairs &q : *p.align)
                     HIP_TRY(ctx, gdg_launch_block_align(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (unsigned)N + 2u, (unsigned)rec_rows, (size_t)wb, q, align_tw,
-                                                        enc + align_at(i), ctx->stream));
-            if (p.true_peak) {                                               /* ... and the inter-sample peaks of the same rows */
-                gdg_block_true_peak *tp = reinterpret_cast<gdg_block_true_peak *>(enc + tp_at(i));
+                                                        enc + sec.at[REPORT_ALIGN], ctx->stream));
+            if (p.live.on(REPORT_TRUE_PEAK)) {                               /* ... and the inter-sample peaks of the same rows */
+                gdg_block_true_peak *tp = reinterpret_cast<gdg_block_true_peak *>(enc + sec.at[REPORT_TRUE_PEAK]);
                 HIP_TRY(ctx, gdg_launch_block_true_peak(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, true_peak_table(), tp, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_true_peak(d_metro, ws, 1u, (size_t)wb, true_peak_table(), tp + (size_t)N * w, ctx->stream));
             }
@@ -330,7 +303,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = p.true_peak ? tp_at(i) + tp_bytes(i) : before_tp(i);
+        const size_t down = steps[i].sec.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -656,22 +629,13 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
      * room for them is the job's (whether the shard runs the metronome): no slice makes a buffer grow */
     const int enc_rows = !sharded ? NO : N + (slice->metronome_bytes ? 1 : 0), f64_rows = !sharded ? 0 : 2 + (slice->metronome ? 1 : 0);
     const int enc_room = !sharded ? NO : N + (S.run_metro ? 1 : 0), f64_room = !sharded ? 0 : 2 + (S.run_metro ? 1 : 0);
-    const bool report = ctx->report_live;
-    /* with the render report a half also holds a window's records behind its rows (batch_block_loop: rec_at) */
-    const size_t rec_room = report ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_stats) : 0;
-    /* ... and with the band spectrum a window's bands behind those (spec_at) */
-    const bool spectrum = !ctx->spec_live_edges.empty();
-    const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), opt->target_rate) : gdg_spectrum_bands();
-    const size_t spec_room = spectrum ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * (size_t)bands.n_bands * sizeof(double) : 0;
-    /* ... and with the alignment report a window's records of that kind behind those (align_at).  A shard that does not run the metronome
-     * measures nothing against that port */
-    const bool align = !ctx->align_live_ref.empty();
-    const std::vector<gdg_align_pairs> pairs = align ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
-    const size_t align_room = align ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_align) : 0;
-    /* ... and with the true-peak switch a window's records of that kind behind those (tp_at) */
-    const bool true_peak = ctx->tp_live;
-    const size_t tp_room = true_peak ? 16 + (size_t)(sharded ? N + 1 : NO) * (size_t)W * sizeof(gdg_block_true_peak) : 0;
-    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double) + rec_room + spec_room + align_room + tp_room;
+    /* a half also holds, behind its rows, a window's section of every kind of the render report the call collects (report_sections.h) */
+    const ReportLive live = report_live(ctx);
+    const gdg_spectrum_bands bands = live.on(REPORT_BANDS) ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), opt->target_rate) : gdg_spectrum_bands();
+    /* a shard that does not run the metronome measures nothing against that port */
+    const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
+    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
+                           + report_room(live, (size_t)(sharded ? N + 1 : NO), (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -840,8 +804,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             return GDG_OK;
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
-                        S.length / B, pos / B, report, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, spectrum ? &bands : nullptr,
-                        align ? &pairs : nullptr, true_peak, nullptr };
+                        S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr };
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
             if (!ctx->d_trim && hipMalloc((void **)&ctx->d_trim, (size_t)NO * sizeof(double)) != hipSuccess)
@@ -962,26 +926,23 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
     if (!ctx->spec_live_edges.empty() && sample_rate == 0)                       /* like every refusal from here on: the call before's report and spectrum are gone */
         return report_end(ctx, fail(ctx, GDG_ERR_INVALID, "master mix: the band spectrum needs a positive sample rate"));
     if (samples == 0) return report_end(ctx, GDG_OK);
-    const bool report = ctx->report_live, dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = !ctx->spec_live_edges.empty(), true_peak = ctx->tp_live;
+    const ReportLive live = report_live(ctx);                                    /* never the alignment records: report_begin above */
+    const bool report = live.on(REPORT_STATS), dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = live.on(REPORT_BANDS), true_peak = live.on(REPORT_TRUE_PEAK);
     /* the trim in force on the context that finishes: its two master gains, as kernel arguments */
     const bool trim = !ctx->trim_gain.empty();
     const double trim_left = trim ? ctx->trim_gain[(size_t)ctx->nch + GDG_TRIM_MASTER_LEFT] : 1.0, trim_right = trim ? ctx->trim_gain[(size_t)ctx->nch + GDG_TRIM_MASTER_RIGHT] : 1.0;
     enter(ctx);
     const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), sample_rate) : gdg_spectrum_bands();
-    const size_t n_bands = spectrum ? (size_t)bands.n_bands : 0;
     const double *spec_win = nullptr;
     double2 *spec_tw = nullptr, *spec_tw2 = nullptr;
     if (spectrum) { const int rs = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2); if (rs != GDG_OK) return report_end(ctx, rs); }
     const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0);
     /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the sample count and the shard count */
     const size_t piece = B * std::min((size_t)128, std::max((size_t)1, ((size_t)8 << 20) / ((2 * G + 1) * B * sizeof(double))));
-    /* the render report: a piece's records, [2][piece / 8192], come down behind its encoded rows */
-    const size_t rec_off = 2 * piece * width, rec_bytes = report ? 2 * (piece / B) * sizeof(gdg_block_stats) : 0;
-    /* ... and the band spectrum: a piece's bands, [2][piece / 8192][n_bands], behind those */
-    const size_t spec_off = rec_off + rec_bytes, spec_bytes = 2 * (piece / B) * n_bands * sizeof(double);
-    /* ... and the true-peak records, [2][piece / 8192], behind those */
-    const size_t tp_off = spec_off + spec_bytes, tp_bytes = true_peak ? 2 * (piece / B) * sizeof(gdg_block_true_peak) : 0;
-    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = tp_off + tp_bytes;
+    /* the render report: a piece's section of every live kind, [2][piece / 8192], comes down behind its encoded rows, packed */
+    const ReportSections sec = report_sections(live, 2, piece / B, 2 * piece * width, false);
+    const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = sec.end;
+    const std::vector<size_t> both_sides = { 0, 1 };
     if (!ctx->fin_up[0])
         for (int h = 0; h < 2; h++) {
             HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
@@ -994,7 +955,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
     if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * down_bytes);
     if (rc != GDG_OK) return rc;
     unsigned char *d_slab = static_cast<unsigned char *>(ctx->d_io[1]), *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
-    double *d_sums = (run_meters || report || spectrum || true_peak) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
+    double *d_sums = (run_meters || live.any()) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
     const size_t n_pieces = (samples + piece - 1) / piece;
     auto span = [&](size_t k) { return std::min(piece, samples - k * piece); };
     auto stride_of = [](size_t n) { return (n + 3) & ~(size_t)3; };                /* <= piece: a piece is whole blocks */
@@ -1037,17 +998,19 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
             if (run_meters)
                 for (size_t o = 0; o < n; o += B)                                /* block by block, like the loop that fed the other ports */
                     if ((rc = meter_rows(ctx, d_sums + o, piece, ctx->n_meter - 2, 2, (int)std::min(B, n - o), sample_rate)) != GDG_OK) return rc;
+            /* kind k's [2][nb] elements of this piece, just launched into its section, on their way down */
+            auto section_down = [&](int k) { return hipMemcpyAsync(ctx->h_fin_down[h] + sec.at[k], enc + sec.at[k], 2 * nb * live.elem[k], hipMemcpyDeviceToHost, ctx->stream); };
             if (report) {                                                    /* the sums: after the aux, before the encoder's clamp */
-                HIP_TRY(ctx, gdg_launch_block_stats(d_sums, piece, 2u, n, (unsigned)B, enc + rec_off, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + rec_off, enc + rec_off, 2 * nb * sizeof(gdg_block_stats), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_block_stats(d_sums, piece, 2u, n, (unsigned)B, enc + sec.at[REPORT_STATS], ctx->stream));
+                HIP_TRY(ctx, section_down(REPORT_STATS));
             }
             if (spectrum) {                                                  /* the same sums; a short last block is zero-padded by the kernel */
-                HIP_TRY(ctx, gdg_launch_block_spectrum(d_sums, piece, 2u, n, spec_win, spec_tw, spec_tw2, bands, reinterpret_cast<double *>(enc + spec_off), ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + spec_off, enc + spec_off, 2 * nb * n_bands * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_block_spectrum(d_sums, piece, 2u, n, spec_win, spec_tw, spec_tw2, bands, reinterpret_cast<double *>(enc + sec.at[REPORT_BANDS]), ctx->stream));
+                HIP_TRY(ctx, section_down(REPORT_BANDS));
             }
             if (true_peak) {                                                 /* the same sums; a short last block is just shorter */
-                HIP_TRY(ctx, gdg_launch_block_true_peak(d_sums, piece, 2u, n, true_peak_table(), enc + tp_off, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + tp_off, enc + tp_off, 2 * nb * sizeof(gdg_block_true_peak), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_block_true_peak(d_sums, piece, 2u, n, true_peak_table(), enc + sec.at[REPORT_TRUE_PEAK], ctx->stream));
+                HIP_TRY(ctx, section_down(REPORT_TRUE_PEAK));
             }
             /* the download of piece k - 2 into this pinned half has been scattered: scatter(k - 2) ran before enqueue(k) */
             if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * width, hipMemcpyDeviceToHost, ctx->stream));
@@ -1067,24 +1030,8 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
                 for (size_t q = 0; q < bytes; q += (size_t)1 << 18) pieces.push_back({ dst + at + q, src + q, std::min(bytes - q, (size_t)1 << 18) });
             }
             move_pieces(ctx, pieces);
-            if (report) {
-                const gdg_block_stats *rec = reinterpret_cast<const gdg_block_stats *>(ctx->h_fin_down[h] + rec_off);
-                const size_t nb = (span(k) + B - 1) / B;
-                for (size_t side = 0; side < 2; side++)
-                    memcpy(&ctx->report[side * ctx->report_blocks + k * (piece / B)], rec + side * nb, nb * sizeof(gdg_block_stats));
-            }
-            if (spectrum) {
-                const double *sp = reinterpret_cast<const double *>(ctx->h_fin_down[h] + spec_off);
-                const size_t nb = (span(k) + B - 1) / B;
-                for (size_t side = 0; side < 2; side++)
-                    memcpy(&ctx->spectrum[(side * ctx->spec_blocks + k * (piece / B)) * n_bands], sp + side * nb * n_bands, nb * n_bands * sizeof(double));
-            }
-            if (true_peak) {
-                const gdg_block_true_peak *tp = reinterpret_cast<const gdg_block_true_peak *>(ctx->h_fin_down[h] + tp_off);
-                const size_t nb = (span(k) + B - 1) / B;
-                for (size_t side = 0; side < 2; side++)
-                    memcpy(&ctx->true_peak[side * ctx->tp_blocks + k * (piece / B)], tp + side * nb, nb * sizeof(gdg_block_true_peak));
-            }
+            for (int j = 0; j < REPORT_KINDS; j++)                           /* the piece's sections: two rows of its blocks, filed under them */
+                if (live.on(j)) report_file(ctx, j, ctx->h_fin_down[h] + sec.at[j], both_sides, (span(k) + B - 1) / B, k * (piece / B));
             return GDG_OK;
         };
         int r;

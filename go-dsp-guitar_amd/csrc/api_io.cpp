@@ -486,6 +486,48 @@ int gdg_metronome_process(gdg_ctx *ctx, double *out, int frames) {
 /* ---- the render report (include/gdg.h; the kernel: io.hip block_stats_kernel; the batch calls fill it: api_batch.cpp) ------------------ */
 static_assert(sizeof(gdg_block_stats) == 32 && offsetof(gdg_block_stats, peak_index) == 16 && offsetof(gdg_block_stats, nonfinite) == 28,
               "gdg_block_stats: 32 bytes, no padding");
+static_assert(sizeof(gdg_block_align) == 40, "gdg_block_align: 40 bytes (report_sections.h)");
+
+/* What the four host-pointer entries gdg_block_*_rows share, behind their own checks: the rows go up compact into d_io[1] (an odd `samples`
+ * puts every other row 8 bytes past a 16-byte boundary, which the kernels take as it comes), `run` -- the kind's _device entry -- reads
+ * them there and writes d_io[0], and `out_bytes` of that come down into `out`; synchronised.  `what` names the kind in a refused row. */
+static int rows_round_trip(gdg_ctx *ctx, const char *what, const double *const *rows, int n_rows, size_t samples, void *out, size_t out_bytes,
+                           const std::function<int(const double *d_rows, void *d_out)> &run) {
+    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "%s: row %d is NULL", what, r);
+    enter_keep_fir_sums(ctx);
+    int rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, out_bytes);
+    if (rc != GDG_OK) return rc;
+    double *d_rows = static_cast<double *>(ctx->d_io[1]);
+    for (int r = 0; r < n_rows; r++)
+        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run(d_rows, ctx->d_io[0])) != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_io[0], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
+/* What the four getters gdg_batch_* share.  The kind's nouns: `none` opens the refusal of a call that kept nothing, `pending` / `without`
+ * end it with the switch on / off; `name`, `unit` and `owner` word the refusal of too little room.  Counts out, NULL gives counts alone. */
+struct KindWords { const char *none, *pending, *without, *name, *unit, *owner; };
+static int batch_kind_get(gdg_ctx *ctx, int kind, bool on, const KindWords &w, void *out, size_t capacity, int *ports, size_t *blocks, int *n_bands) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const gdg_ctx::ReportKind &K = ctx->report[kind];
+    if (!K.valid) return fail(ctx, GDG_ERR_INVALID, "%s: the last batch call of this context %s", w.none, on ? w.pending : w.without);
+    const size_t per = kind == REPORT_BANDS ? K.elem / sizeof(double) : 1;      /* values of a port and block: a record, or the bands */
+    if (ports) *ports = K.ports;
+    if (blocks) *blocks = K.blocks;
+    if (n_bands) *n_bands = (int)per;
+    if (!out) return GDG_OK;
+    const size_t n = (size_t)K.ports * K.blocks * per;
+    if (capacity < n) {
+        char bands[32] = "";
+        if (kind == REPORT_BANDS) snprintf(bands, sizeof bands, " x %zu bands", per);
+        return fail(ctx, GDG_ERR_INVALID, "%s: room for %zu %s, the %s has %d ports x %zu blocks%s = %zu", w.name, capacity, w.unit, w.owner, K.ports, K.blocks, bands, n);
+    }
+    if (n) memcpy(out, K.store.data(), K.store.size());
+    return GDG_OK;
+}
 static int block_stats_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, size_t *blocks) {
     if (n_rows < 0) return fail(ctx, GDG_ERR_INVALID, "block statistics: %d rows", n_rows);
     if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block statistics: blocks of %d samples (at least 1)", block);
@@ -515,21 +557,9 @@ int gdg_block_stats_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, si
     if (rc != GDG_OK) return rc;
     if (n_rows == 0 || samples == 0) return GDG_OK;
     if (!rows || !records) return GDG_ERR_INVALID;
-    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block statistics: row %d is NULL", r);
-    enter_keep_fir_sums(ctx);
-    /* the rows go up compact: an odd `samples` puts every other row at 8 bytes past a 16-byte boundary, which the kernel takes as it comes */
-    const size_t rec_bytes = (size_t)n_rows * blocks * sizeof(gdg_block_stats);
-    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
-    if (rc == GDG_OK) rc = ensure_io(ctx, 0, rec_bytes);
-    if (rc != GDG_OK) return rc;
-    double *d_rows = static_cast<double *>(ctx->d_io[1]);
-    for (int r = 0; r < n_rows; r++)
-        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gdg_block_stats_rows_device(ctx, d_rows, samples, n_rows, samples, block, static_cast<gdg_block_stats *>(ctx->d_io[0]));
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(records, ctx->d_io[0], rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GDG_OK;
+    return rows_round_trip(ctx, "block statistics", rows, n_rows, samples, records, (size_t)n_rows * blocks * sizeof(gdg_block_stats), [&](const double *d_rows, void *d_out) {
+        return gdg_block_stats_rows_device(ctx, d_rows, samples, n_rows, samples, block, static_cast<gdg_block_stats *>(d_out));
+    });
 }
 
 int gdg_batch_report_enable(gdg_ctx *ctx, int enable) {
@@ -539,17 +569,9 @@ int gdg_batch_report_enable(gdg_ctx *ctx, int enable) {
 }
 
 int gdg_batch_report(gdg_ctx *ctx, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks) {
-    if (!ctx) return GDG_ERR_INVALID;
-    if (!ctx->report_valid)
-        return fail(ctx, GDG_ERR_INVALID, "no report: the last batch call of this context %s", ctx->report_on ? "has not completed (or none has run since "
-                    "gdg_batch_report_enable)" : "ran without one (gdg_batch_report_enable comes before the call)");
-    if (ports) *ports = ctx->report_ports;
-    if (blocks) *blocks = ctx->report_blocks;
-    if (!records) return GDG_OK;
-    const size_t n = (size_t)ctx->report_ports * ctx->report_blocks;
-    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "report: room for %zu records, the report has %d ports x %zu blocks = %zu", capacity, ctx->report_ports, ctx->report_blocks, n);
-    if (n) memcpy(records, ctx->report.data(), n * sizeof(gdg_block_stats));
-    return GDG_OK;
+    static const KindWords words = { "no report", "has not completed (or none has run since gdg_batch_report_enable)",
+                                     "ran without one (gdg_batch_report_enable comes before the call)", "report", "records", "report" };
+    return batch_kind_get(ctx, REPORT_STATS, ctx && ctx->report_on, words, records, capacity, ports, blocks, nullptr);
 }
 
 /* ---- the band spectrum (include/gdg.h; the kernel: spectrum_kernels.h in fir.hip; the edges and bins: spectrum_bands.h; the batch calls fill it: api_batch.cpp) ---- */
@@ -614,21 +636,9 @@ int gdg_block_spectrum_rows(gdg_ctx *ctx, const double *const *rows, int n_rows,
     if (rc != GDG_OK) return rc;
     if (n_rows == 0 || samples == 0) return GDG_OK;
     if (!rows || !bands) return GDG_ERR_INVALID;
-    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block spectrum: row %d is NULL", r);
-    enter_keep_fir_sums(ctx);
-    /* the rows go up compact, like gdg_block_stats_rows': an odd `samples` puts every other row 8 bytes past a 16-byte boundary */
-    const size_t band_bytes = (size_t)n_rows * blocks * (size_t)(n_edges - 1) * sizeof(double);
-    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
-    if (rc == GDG_OK) rc = ensure_io(ctx, 0, band_bytes);
-    if (rc != GDG_OK) return rc;
-    double *d_rows = static_cast<double *>(ctx->d_io[1]);
-    for (int r = 0; r < n_rows; r++)
-        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gdg_block_spectrum_rows_device(ctx, d_rows, samples, n_rows, samples, sample_rate, edges_hz, n_edges, static_cast<double *>(ctx->d_io[0]));
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(bands, ctx->d_io[0], band_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GDG_OK;
+    return rows_round_trip(ctx, "block spectrum", rows, n_rows, samples, bands, (size_t)n_rows * blocks * (size_t)(n_edges - 1) * sizeof(double), [&](const double *d_rows, void *d_out) {
+        return gdg_block_spectrum_rows_device(ctx, d_rows, samples, n_rows, samples, sample_rate, edges_hz, n_edges, static_cast<double *>(d_out));
+    });
 }
 
 int gdg_batch_spectrum_enable(gdg_ctx *ctx, const double *edges_hz, int n_edges) {
@@ -647,20 +657,9 @@ int gdg_batch_spectrum_enable(gdg_ctx *ctx, const double *edges_hz, int n_edges)
 }
 
 int gdg_batch_spectrum(gdg_ctx *ctx, double *bands, size_t capacity, int *ports, size_t *blocks, int *n_bands) {
-    if (!ctx) return GDG_ERR_INVALID;
-    if (!ctx->spec_valid)
-        return fail(ctx, GDG_ERR_INVALID, "no spectrum: the last batch call of this context %s", !ctx->spec_edges.empty() ? "has not completed (or none has run since "
-                    "gdg_batch_spectrum_enable)" : "ran without one (gdg_batch_spectrum_enable comes before the call)");
-    if (ports) *ports = ctx->spec_ports;
-    if (blocks) *blocks = ctx->spec_blocks;
-    if (n_bands) *n_bands = ctx->spec_bands;
-    if (!bands) return GDG_OK;
-    const size_t n = (size_t)ctx->spec_ports * ctx->spec_blocks * (size_t)ctx->spec_bands;
-    if (capacity < n)
-        return fail(ctx, GDG_ERR_INVALID, "spectrum: room for %zu values, the spectrum has %d ports x %zu blocks x %d bands = %zu", capacity, ctx->spec_ports,
-                    ctx->spec_blocks, ctx->spec_bands, n);
-    if (n) memcpy(bands, ctx->spectrum.data(), n * sizeof(double));
-    return GDG_OK;
+    static const KindWords words = { "no spectrum", "has not completed (or none has run since gdg_batch_spectrum_enable)",
+                                     "ran without one (gdg_batch_spectrum_enable comes before the call)", "spectrum", "values", "spectrum" };
+    return batch_kind_get(ctx, REPORT_BANDS, ctx && !ctx->spec_edges.empty(), words, bands, capacity, ports, blocks, n_bands);
 }
 
 /* ---- the alignment report (include/gdg.h; the kernel: align_kernels.h in fir.hip; the list's validation: align_map.h; the batch calls fill it: api_batch.cpp) ---- */
@@ -712,21 +711,9 @@ int gdg_block_align_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, si
     if (rc != GDG_OK) return rc;
     if (n_rows == 0 || samples == 0) return GDG_OK;
     if (!rows || !records) return GDG_ERR_INVALID;
-    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block align: row %d is NULL", r);
-    enter_keep_fir_sums(ctx);
-    /* the rows go up compact, like gdg_block_spectrum_rows': an odd `samples` puts every other row 8 bytes past a 16-byte boundary */
-    const size_t rec_bytes = (size_t)n_rows * blocks * sizeof(gdg_block_align);
-    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
-    if (rc == GDG_OK) rc = ensure_io(ctx, 0, rec_bytes);
-    if (rc != GDG_OK) return rc;
-    double *d_rows = static_cast<double *>(ctx->d_io[1]);
-    for (int r = 0; r < n_rows; r++)
-        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gdg_block_align_rows_device(ctx, d_rows, samples, n_rows, samples, ref, max_lag, static_cast<gdg_block_align *>(ctx->d_io[0]));
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(records, ctx->d_io[0], rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GDG_OK;
+    return rows_round_trip(ctx, "block align", rows, n_rows, samples, records, (size_t)n_rows * blocks * sizeof(gdg_block_align), [&](const double *d_rows, void *d_out) {
+        return gdg_block_align_rows_device(ctx, d_rows, samples, n_rows, samples, ref, max_lag, static_cast<gdg_block_align *>(d_out));
+    });
 }
 
 int gdg_batch_align_enable(gdg_ctx *ctx, const int *ref, int n_ports, int max_lag) {
@@ -746,18 +733,9 @@ int gdg_batch_align_enable(gdg_ctx *ctx, const int *ref, int n_ports, int max_la
 }
 
 int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int *ports, size_t *blocks) {
-    if (!ctx) return GDG_ERR_INVALID;
-    if (!ctx->align_valid)
-        return fail(ctx, GDG_ERR_INVALID, "no alignment records: the last batch call of this context %s", !ctx->align_ref.empty() ? "has not completed, was a master "
-                    "finish, or none has run since gdg_batch_align_enable" : "ran without them (gdg_batch_align_enable comes before the call)");
-    if (ports) *ports = ctx->align_ports;
-    if (blocks) *blocks = ctx->align_blocks;
-    if (!records) return GDG_OK;
-    const size_t n = (size_t)ctx->align_ports * ctx->align_blocks;
-    if (capacity < n)
-        return fail(ctx, GDG_ERR_INVALID, "alignment: room for %zu records, the call has %d ports x %zu blocks = %zu", capacity, ctx->align_ports, ctx->align_blocks, n);
-    if (n) memcpy(records, ctx->align.data(), n * sizeof(gdg_block_align));
-    return GDG_OK;
+    static const KindWords words = { "no alignment records", "has not completed, was a master finish, or none has run since gdg_batch_align_enable",
+                                     "ran without them (gdg_batch_align_enable comes before the call)", "alignment", "records", "call" };
+    return batch_kind_get(ctx, REPORT_ALIGN, ctx && !ctx->align_ref.empty(), words, records, capacity, ports, blocks, nullptr);
 }
 
 /* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */
@@ -798,21 +776,9 @@ int gdg_block_true_peak_rows(gdg_ctx *ctx, const double *const *rows, int n_rows
     if (rc != GDG_OK) return rc;
     if (samples == 0) return GDG_OK;
     if (!rows || !records) return fail(ctx, GDG_ERR_INVALID, "block true peak: %s is NULL", !rows ? "the rows' list" : "the records' pointer");
-    for (int r = 0; r < n_rows; r++) if (!rows[r]) return fail(ctx, GDG_ERR_INVALID, "block true peak: row %d is NULL", r);
-    enter_keep_fir_sums(ctx);
-    /* the rows go up compact, like gdg_block_stats_rows': an odd `samples` puts every other row 8 bytes past a 16-byte boundary */
-    const size_t rec_bytes = (size_t)n_rows * blocks * sizeof(gdg_block_true_peak);
-    rc = ensure_io(ctx, 1, (size_t)n_rows * samples * sizeof(double));
-    if (rc == GDG_OK) rc = ensure_io(ctx, 0, rec_bytes);
-    if (rc != GDG_OK) return rc;
-    double *d_rows = static_cast<double *>(ctx->d_io[1]);
-    for (int r = 0; r < n_rows; r++)
-        HIP_TRY(ctx, hipMemcpyAsync(d_rows + (size_t)r * samples, rows[r], samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gdg_block_true_peak_rows_device(ctx, d_rows, samples, n_rows, samples, static_cast<gdg_block_true_peak *>(ctx->d_io[0]));
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(records, ctx->d_io[0], rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GDG_OK;
+    return rows_round_trip(ctx, "block true peak", rows, n_rows, samples, records, (size_t)n_rows * blocks * sizeof(gdg_block_true_peak), [&](const double *d_rows, void *d_out) {
+        return gdg_block_true_peak_rows_device(ctx, d_rows, samples, n_rows, samples, static_cast<gdg_block_true_peak *>(d_out));
+    });
 }
 
 int gdg_batch_true_peak_enable(gdg_ctx *ctx, int enable) {
@@ -824,16 +790,7 @@ int gdg_batch_true_peak_enable(gdg_ctx *ctx, int enable) {
 }
 
 int gdg_batch_true_peak(gdg_ctx *ctx, gdg_block_true_peak *records, size_t capacity, int *ports, size_t *blocks) {
-    if (!ctx) return GDG_ERR_INVALID;
-    if (!ctx->tp_valid)
-        return fail(ctx, GDG_ERR_INVALID, "no true-peak records: the last batch call of this context %s", ctx->tp_on ? "has not completed (or none has run since "
-                    "gdg_batch_true_peak_enable)" : "ran without them (gdg_batch_true_peak_enable comes before the call)");
-    if (ports) *ports = ctx->tp_ports;
-    if (blocks) *blocks = ctx->tp_blocks;
-    if (!records) return GDG_OK;
-    const size_t n = (size_t)ctx->tp_ports * ctx->tp_blocks;
-    if (capacity < n)
-        return fail(ctx, GDG_ERR_INVALID, "true peak: room for %zu records, the call has %d ports x %zu blocks = %zu", capacity, ctx->tp_ports, ctx->tp_blocks, n);
-    if (n) memcpy(records, ctx->true_peak.data(), n * sizeof(gdg_block_true_peak));
-    return GDG_OK;
+    static const KindWords words = { "no true-peak records", "has not completed (or none has run since gdg_batch_true_peak_enable)",
+                                     "ran without them (gdg_batch_true_peak_enable comes before the call)", "true peak", "records", "call" };
+    return batch_kind_get(ctx, REPORT_TRUE_PEAK, ctx && ctx->tp_on, words, records, capacity, ports, blocks, nullptr);
 }

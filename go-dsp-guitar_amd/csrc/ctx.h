@@ -47,6 +47,7 @@
 #include "arena.h"
 #include "batch_sources.h"
 #include "dither.h"
+#include "report_sections.h"
 #include "trim.h"
 
 #define NUM_FILTERS 8
@@ -366,35 +367,26 @@ struct gdg_ctx {
         std::vector<int> source;               /* the source map as it stood when the job was described, when it has a reader (empty otherwise):
                                                 * inputs and n_out of a reader are its root's */
     } bstream;
-    /* the render report (gdg_batch_report_enable): the records of the last completed batch call, [report_ports][report_blocks]; a call
-     * that collects (report_live: the switch as it stood when the call began) fills `report` step by step and validates it at its end */
-    bool report_on = false, report_live = false, report_valid = false;
-    int report_ports = 0;
-    size_t report_blocks = 0;
-    std::vector<gdg_block_stats> report;
-    /* the band spectrum (gdg_batch_spectrum_enable; spectrum_bands.h): the edges in force (empty = off), the bands of the last completed batch
-     * call, [spec_ports][spec_blocks][spec_bands], and the 8192 window weights (made with the first use, never with the switch off).  A call
-     * that collects takes the edges as they stood when it began (spec_live_edges); configuration like report_on, in no blob. */
-    std::vector<double> spec_edges, spec_live_edges, spectrum;
-    bool spec_valid = false;
-    int spec_ports = 0, spec_bands = 0;
-    size_t spec_blocks = 0;
+    /* the render report's record kinds (report_sections.h: block statistics, band spectrum, alignment records, true-peak records), one
+     * state each: the records of the last completed batch call, [ports][blocks] elements of `elem` bytes (zero bytes are a zeroed record
+     * of every kind).  A call that collects a kind (`live`: decided when the call begins, report_begin) fills its store step by step and
+     * validates it at its end. */
+    struct ReportKind {
+        bool live = false, valid = false;
+        int ports = 0;
+        size_t blocks = 0, elem = 0;
+        std::vector<unsigned char> store;
+    } report[REPORT_KINDS];
+    /* ... and what switches each kind on; configuration, in no blob.  A collecting call takes edges, list and lag as they stood when it
+     * began (the *_live copies).  Statistics: gdg_batch_report_enable.  Spectrum: gdg_batch_spectrum_enable (spectrum_bands.h), the edges
+     * in force (empty = off) and the 8192 window weights (made with the first use, never with the switch off).  Alignment:
+     * gdg_batch_align_enable (align_map.h), the reference list and the lag range in force (empty = off); the finish calls never collect.
+     * True peak: gdg_batch_true_peak_enable (true_peak_taps.h). */
+    bool report_on = false, tp_on = false;
+    std::vector<double> spec_edges, spec_live_edges;
     double *d_spec_win = nullptr;
-    /* the alignment report (gdg_batch_align_enable; align_map.h): the reference list and the lag range in force (empty = off) and the records
-     * of the last completed batch call, [align_ports][align_blocks].  A call that collects takes list and lag as they stood when it began
-     * (align_live_*); configuration like the spectrum's edges, in no blob.  The finish calls never collect. */
     std::vector<int> align_ref, align_live_ref;
     int align_lag = 0, align_live_lag = 0;
-    std::vector<gdg_block_align> align;
-    bool align_valid = false;
-    int align_ports = 0;
-    size_t align_blocks = 0;
-    /* the true-peak records (gdg_batch_true_peak_enable; true_peak_taps.h): the switch, the switch as it stood when the collecting call began
-     * (tp_live), and the records of the last completed batch call, [tp_ports][tp_blocks].  Configuration like report_on, in no blob. */
-    bool tp_on = false, tp_live = false, tp_valid = false;
-    int tp_ports = 0;
-    size_t tp_blocks = 0;
-    std::vector<gdg_block_true_peak> true_peak;
     /* the source map (gdg_batch_set_sources; batch_sources.h): batch_source[c] = the channel whose input entry channel c reads, empty = every
      * channel its own.  Configuration like report_on: read when a job is described, in no blob. */
     std::vector<int> batch_source;
@@ -698,50 +690,48 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
 int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
 /* the map in force has a reader: what a checkpoint cannot record yet */
 static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_have_reader(ctx->batch_source); }
-/* a batch call begins: the report of the call before is gone; with the report enabled, zeroed records for `ports` x `blocks` */
+/* a batch call begins: every kind's records of the call before are gone; a kind that is switched on gets zeroed records for `ports` x
+ * `blocks`.  `align`: this call may collect alignment records (the finish calls never do) */
 static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool align = true) {
-    ctx->align_valid = false;                                                /* its alignment records are gone too; `align`: this call may collect them */
+    ctx->spec_live_edges = ctx->spec_edges;
     ctx->align_live_ref.clear();
     if (align && (int)ctx->align_ref.size() == ports) {                      /* any other count was refused when the job was described */
         ctx->align_live_ref = ctx->align_ref;
         ctx->align_live_lag = ctx->align_lag;
-        ctx->align_ports = ports;
-        ctx->align_blocks = blocks;
-        ctx->align.assign((size_t)ports * blocks, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
     }
-    ctx->tp_valid = false;                                                   /* ... and its true-peak records; with the switch on, zeroed ones */
-    ctx->tp_live = ctx->tp_on;
-    if (ctx->tp_live) {
-        ctx->tp_ports = ports;
-        ctx->tp_blocks = blocks;
-        ctx->true_peak.assign((size_t)ports * blocks, gdg_block_true_peak{ 0.0, 0u, 0u });
+    const bool on[REPORT_KINDS] = { ctx->report_on, !ctx->spec_live_edges.empty(), !ctx->align_live_ref.empty(), ctx->tp_on };
+    const size_t n_bands = ctx->spec_live_edges.empty() ? 0 : ctx->spec_live_edges.size() - 1;      /* the bands a call collects are its live edges' */
+    for (int k = 0; k < REPORT_KINDS; k++) {
+        gdg_ctx::ReportKind &K = ctx->report[k];
+        K.valid = false;
+        K.live = on[k];
+        if (!K.live) continue;
+        K.ports = ports;
+        K.blocks = blocks;
+        K.elem = report_elem(k, n_bands);
+        K.store.assign((size_t)ports * blocks * K.elem, 0);
     }
-    ctx->spec_valid = false;                                                 /* ... and so is its spectrum; with edges in force, zeroed bands */
-    ctx->spec_live_edges = ctx->spec_edges;
-    if (!ctx->spec_live_edges.empty()) {
-        ctx->spec_ports = ports;
-        ctx->spec_blocks = blocks;
-        ctx->spec_bands = (int)ctx->spec_live_edges.size() - 1;
-        ctx->spectrum.assign((size_t)ports * blocks * (size_t)ctx->spec_bands, 0.0);
-    }
-    ctx->report_valid = false;
-    ctx->report_live = ctx->report_on;
-    if (!ctx->report_live) return;
-    ctx->report_ports = ports;
-    ctx->report_blocks = blocks;
-    ctx->report.assign((size_t)ports * blocks, gdg_block_stats{ 0.0, 0.0, 0u, 0u, 0u, 0u });
 }
 /* ... and has completed (rc == GDG_OK) or not */
 static inline int report_end(gdg_ctx *ctx, int rc) {
-    ctx->report_valid = ctx->report_live && rc == GDG_OK;
-    ctx->report_live = false;
-    ctx->spec_valid = !ctx->spec_live_edges.empty() && rc == GDG_OK;
+    for (gdg_ctx::ReportKind &K : ctx->report) {
+        K.valid = K.live && rc == GDG_OK;
+        K.live = false;
+    }
     ctx->spec_live_edges.clear();
-    ctx->align_valid = !ctx->align_live_ref.empty() && rc == GDG_OK;
     ctx->align_live_ref.clear();
-    ctx->tp_valid = ctx->tp_live && rc == GDG_OK;
-    ctx->tp_live = false;
     return rc;
+}
+/* the kinds the running call collects, with their element sizes */
+static inline ReportLive report_live(const gdg_ctx *ctx) {
+    ReportLive live;
+    for (int k = 0; k < REPORT_KINDS; k++) live.elem[k] = ctx->report[k].live ? ctx->report[k].elem : 0;
+    return live;
+}
+/* rows `rows` of a section that has come down ([..][w] elements of kind k) into the kind's store, under the blocks from b0 on */
+static inline void report_file(gdg_ctx *ctx, int k, const unsigned char *section, const std::vector<size_t> &rows, size_t w, size_t b0) {
+    gdg_ctx::ReportKind &K = ctx->report[k];
+    for (size_t o : rows) memcpy(&K.store[(o * K.blocks + b0) * K.elem], section + o * w * K.elem, w * K.elem);
 }
 #define GDG_STREAM_CARRY 8            /* source frames kept per resampled input: the window reaches 2 back and 3 ahead, so a step looks at most 6 back */
 /* gdg_ctx::batch_dev, slot by slot (the slice runner, api_batch.cpp) */

@@ -1,0 +1,49 @@
+/*
+ * report_sections.h -- where the render report's record kinds ride in a batch call's download half: the ONE statement of that layout.
+ * A step (or a master finish's piece) sends its encoded rows down; behind them follows one section per live kind, in this fixed order:
+ * block statistics, band spectrum, alignment records, true-peak records.  A section is [rows][w] elements -- `rows` record rows (N + 3 for
+ * a plain call, N + 1 for a shard, 2 for a finish), `w` blocks -- of the kind's element size per port and block.  The block loop starts
+ * every live section at the next 16 bytes behind whatever precedes it; the finish packs them.  Pure host arithmetic: no HIP header is
+ * needed to compile this file (tests/native/report_sections_check.cpp holds it against the formulas it replaced).
+ */
+#ifndef GDG_REPORT_SECTIONS_H
+#define GDG_REPORT_SECTIONS_H
+
+#include <stddef.h>
+
+enum { REPORT_STATS, REPORT_BANDS, REPORT_ALIGN, REPORT_TRUE_PEAK, REPORT_KINDS };
+
+/* bytes per port and block: a gdg_block_stats (32), n_bands doubles, a gdg_block_align (40), a gdg_block_true_peak (16) */
+static inline size_t report_elem(int kind, size_t n_bands) {
+    return kind == REPORT_STATS ? 32 : kind == REPORT_BANDS ? n_bands * 8 : kind == REPORT_ALIGN ? 40 : 16;
+}
+
+/* the kinds a call collects: elem[k] = the kind's element size, 0 = the kind is off */
+struct ReportLive {
+    size_t elem[REPORT_KINDS];
+    bool on(int k) const { return elem[k] != 0; }
+    bool any() const { for (int k = 0; k < REPORT_KINDS; k++) if (elem[k]) return true; return false; }
+};
+
+/* every live kind's section (at, bytes; both 0 for a kind that is off) and the end of the last one (= base when none is live) */
+struct ReportSections { size_t at[REPORT_KINDS], bytes[REPORT_KINDS], end; };
+
+static inline ReportSections report_sections(const ReportLive &live, size_t rows, size_t w, size_t base, bool align16) {
+    ReportSections s = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 }, base };
+    for (int k = 0; k < REPORT_KINDS; k++) {
+        if (!live.on(k)) continue;
+        s.at[k] = align16 ? (s.end + 15) & ~(size_t)15 : s.end;
+        s.bytes[k] = rows * w * live.elem[k];
+        s.end = s.at[k] + s.bytes[k];
+    }
+    return s;
+}
+
+/* what a half holds beside its rows for a window of W blocks: every live section and the 16 bytes its start may be moved by */
+static inline size_t report_room(const ReportLive &live, size_t rows, size_t W) {
+    size_t room = 0;
+    for (int k = 0; k < REPORT_KINDS; k++) if (live.on(k)) room += 16 + rows * W * live.elem[k];
+    return room;
+}
+
+#endif

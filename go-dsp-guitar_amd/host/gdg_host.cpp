@@ -19,6 +19,7 @@
 #include <map>
 #include <sstream>
 #include <thread>
+#include <type_traits>
 
 namespace gdg {
 
@@ -1060,18 +1061,52 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     return "";
 }
 
-/* ---- the render report of the last batch call, [N + 3][blocks] in gdg_batch_run's port order, from three sources ---- */
+/* ---- the render report of the last batch call: four kinds of records (statistics, band spectrum, alignment, true peak), each
+ * [N + 3][blocks] in gdg_batch_run's port order and from three sources -- the shards' chain rows, shard 0's metronome row, the finish's two
+ * master rows (which carry no alignment records: over shards those rows stay zero) ---- */
 void Engine::reportBegin(size_t blocks) {
-    reportValid_ = false;
+    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = false;
     reportBlocks_ = blocks;
-    if (report_) lastReport_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_stats{ 0.0, 0.0, 0u, 0u, 0u, 0u });
-    spectrumValid_ = false;                              /* the band spectrum rides along: the same ports, blocks and three sources */
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
-    if (!spectrumEdges_.empty()) lastSpectrum_.assign((size_t)(nChannels_ + 3) * blocks * (spectrumEdges_.size() - 1), 0.0);
-    truePeakValid_ = false;                              /* ... and the true-peak records: the report's ports, blocks and three sources */
-    if (truePeak_) lastTruePeak_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_true_peak{ 0.0, 0u, 0u });
-    alignValid_ = false;                                 /* ... and so do the alignment records; the master's rows stay zero over shards */
-    if (!alignRef_.empty()) lastAlign_.assign((size_t)(nChannels_ + 3) * blocks, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
+    const size_t n = (size_t)(nChannels_ + 3) * blocks;
+    if (report_) lastReport_.assign(n, gdg_block_stats{});
+    if (spectrumBands_) lastSpectrum_.assign(n * (size_t)spectrumBands_, 0.0);
+    if (truePeak_) lastTruePeak_.assign(n, gdg_block_true_peak{});
+    if (!alignRef_.empty()) lastAlign_.assign(n, gdg_block_align{});
+}
+
+/* a kind's getter by its element type */
+static int getKind(gdg_ctx *c, gdg_block_stats *r, size_t cap, int *ports, size_t *blocks, int *) { return gdg_batch_report(c, r, cap, ports, blocks); }
+static int getKind(gdg_ctx *c, double *r, size_t cap, int *ports, size_t *blocks, int *bands) { return gdg_batch_spectrum(c, r, cap, ports, blocks, bands); }
+static int getKind(gdg_ctx *c, gdg_block_align *r, size_t cap, int *ports, size_t *blocks, int *) { return gdg_batch_align(c, r, cap, ports, blocks); }
+static int getKind(gdg_ctx *c, gdg_block_true_peak *r, size_t cap, int *ports, size_t *blocks, int *) { return gdg_batch_true_peak(c, r, cap, ports, blocks); }
+
+/* `ports` x `blocks` elements of one kind of a context's last call (an element: a record, or the `per` bands of a spectrum), checked
+ * against what the engine expects; `what` names the records in the refusal */
+template <class T>
+static Error kindOf(gdg_ctx *ctx, int ports, size_t blocks, int per, const char *what, std::vector<T> &rec) {
+    int p = 0, b = per;
+    size_t nb = 0;
+    rec.assign((size_t)ports * blocks * (size_t)per, T{});
+    if (getKind(ctx, rec.data(), rec.size(), &p, &nb, &b) != GDG_OK) return gdg_last_error(ctx);
+    if (std::is_same<T, double>::value) {
+        if (p != ports || nb != blocks || b != per)
+            return format("a spectrum of %d ports x %zu blocks x %d bands where %d x %zu x %d were expected", p, nb, b, ports, blocks, per);
+    } else if (p != ports || nb != blocks) return format("%s of %d ports x %zu blocks where %d x %zu were expected", what, p, nb, ports, blocks);
+    return "";
+}
+
+/* ... and filed into the engine's: the first `n0` rows a context gave to the engine's rows from `to0` on (a shard's chain rows to its
+ * channels, the finish's two to the master's), the `n1` rows behind them to the rows from `to1` on (shard 0's last row to the metronome's) */
+template <class T>
+static Error kindInto(gdg_ctx *ctx, int ports, size_t blocks, int per, const char *what, std::vector<T> &last, size_t to0, size_t n0, size_t to1, size_t n1) {
+    std::vector<T> rec;
+    Error e = kindOf(ctx, ports, blocks, per, what, rec);
+    if (!e.empty()) return e;
+    const size_t row = blocks * (size_t)per;
+    if (n0 && row) memcpy(&last[to0 * row], rec.data(), n0 * row * sizeof(T));
+    if (n1 && row) memcpy(&last[to1 * row], &rec[n0 * row], n1 * row * sizeof(T));
+    return "";
 }
 
 /* the shard a port of the job lives on: a chain output on its channel's, the metronome on shard 0, the master (made by the finish) on none */
@@ -1110,30 +1145,14 @@ int Engine::applyAlign(int shard, gdg_ctx *ctx) {
     return gdg_batch_align_enable(ctx, ref.data(), count + 1, alignLag_);
 }
 
-/* `ports` x reportBlocks_ records of a context's last call, checked against what the engine expects */
-Error Engine::alignOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_align> &rec) {
-    int p = 0;
-    size_t blocks = 0;
-    rec.assign((size_t)ports * reportBlocks_, gdg_block_align{ 0.0, 0.0, 0.0, 0.0, 0, 0u });
-    if (gdg_batch_align(ctx, rec.data(), rec.size(), &p, &blocks) != GDG_OK) return gdg_last_error(ctx);
-    if (p != ports || blocks != reportBlocks_) return format("alignment records of %d ports x %zu blocks where %d x %zu were expected", p, blocks, ports, reportBlocks_);
-    return "";
-}
+Error Engine::alignOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_align> &rec) { return kindOf(ctx, ports, reportBlocks_, 1, "alignment records", rec); }
 
 /* the edges in force onto a context (an empty list: off): a gdg_* status */
 int Engine::applySpectrum(gdg_ctx *ctx) {
     return gdg_batch_spectrum_enable(ctx, spectrumEdges_.empty() ? nullptr : spectrumEdges_.data(), (int)spectrumEdges_.size());
 }
 
-/* `ports` x reportBlocks_ true-peak records of a context's last call, checked against what the engine expects */
-Error Engine::truePeakOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_true_peak> &rec) {
-    int p = 0;
-    size_t blocks = 0;
-    rec.assign((size_t)ports * reportBlocks_, gdg_block_true_peak{ 0.0, 0u, 0u });
-    if (gdg_batch_true_peak(ctx, rec.data(), rec.size(), &p, &blocks) != GDG_OK) return gdg_last_error(ctx);
-    if (p != ports || blocks != reportBlocks_) return format("true-peak records of %d ports x %zu blocks where %d x %zu were expected", p, blocks, ports, reportBlocks_);
-    return "";
-}
+Error Engine::truePeakOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_true_peak> &rec) { return kindOf(ctx, ports, reportBlocks_, 1, "true-peak records", rec); }
 
 Error Engine::LastBatchTruePeak(std::vector<gdg_block_true_peak> &records, int *ports, size_t *blocks) const {
     if (!truePeakValid_) return "LastBatchTruePeak: the last batch call kept no true-peak records (SetBatchTruePeak comes before the call)";
@@ -1143,83 +1162,32 @@ Error Engine::LastBatchTruePeak(std::vector<gdg_block_true_peak> &records, int *
     return "";
 }
 
-/* `ports` x reportBlocks_ x bands values of a context's last call, checked against what the engine expects */
-Error Engine::spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val) {
-    const int nb = (int)spectrumEdges_.size() - 1;
-    int p = 0, b = 0;
-    size_t blocks = 0;
-    val.assign((size_t)ports * reportBlocks_ * (size_t)nb, 0.0);
-    if (gdg_batch_spectrum(ctx, val.data(), val.size(), &p, &blocks, &b) != GDG_OK) return gdg_last_error(ctx);
-    if (p != ports || blocks != reportBlocks_ || b != nb)
-        return format("a spectrum of %d ports x %zu blocks x %d bands where %d x %zu x %d were expected", p, blocks, b, ports, reportBlocks_, nb);
-    return "";
-}
+Error Engine::spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val) { return kindOf(ctx, ports, reportBlocks_, (int)spectrumEdges_.size() - 1, nullptr, val); }
 
-/* shard g's report (its n chain outputs, then the metronome): the chain rows to the shard's channels, shard 0's last row to the metronome's */
+/* shard g's records of every kind (its n chain outputs, then the metronome): the chain rows to the shard's channels, shard 0's last row to
+ * the metronome's */
 Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
-    int first = 0, count = 0, ports = 0;
-    size_t blocks = 0;
+    int first = 0, count = 0;
     shardRange(g, &first, &count);
-    if (truePeak_) {                                     /* the shard's true-peak records: chain rows to its channels, shard 0's last row to the metronome's */
-        std::vector<gdg_block_true_peak> rec;
-        Error e = truePeakOf(ctx, count + 1, rec);
-        if (!e.empty()) return e;
-        const size_t nb = reportBlocks_;
-        if (nb) memcpy(&lastTruePeak_[(size_t)first * nb], rec.data(), (size_t)count * nb * sizeof(gdg_block_true_peak));
-        if (g == 0 && nb) memcpy(&lastTruePeak_[(size_t)(nChannels_ + 2) * nb], &rec[(size_t)count * nb], nb * sizeof(gdg_block_true_peak));
-    }
-    if (!alignRef_.empty()) {                            /* the shard's alignment records: the same two destinations */
-        std::vector<gdg_block_align> rec;
-        Error e = alignOf(ctx, count + 1, rec);
-        if (!e.empty()) return e;
-        const size_t nb = reportBlocks_;
-        if (nb) memcpy(&lastAlign_[(size_t)first * nb], rec.data(), (size_t)count * nb * sizeof(gdg_block_align));
-        if (g == 0 && nb) memcpy(&lastAlign_[(size_t)(nChannels_ + 2) * nb], &rec[(size_t)count * nb], nb * sizeof(gdg_block_align));
-    }
-    if (!spectrumEdges_.empty()) {                       /* the shard's bands: chain rows to its channels, shard 0's last row to the metronome's */
-        std::vector<double> val;
-        Error e = spectrumOf(ctx, count + 1, val);
-        if (!e.empty()) return e;
-        const size_t row = reportBlocks_ * (spectrumEdges_.size() - 1);
-        if (row) memcpy(&lastSpectrum_[(size_t)first * row], val.data(), (size_t)count * row * sizeof(double));
-        if (g == 0 && row) memcpy(&lastSpectrum_[(size_t)(nChannels_ + 2) * row], &val[(size_t)count * row], row * sizeof(double));
-    }
-    if (!report_) return "";
-    std::vector<gdg_block_stats> rec((size_t)(count + 1) * reportBlocks_);
-    if (gdg_batch_report(ctx, rec.data(), rec.size(), &ports, &blocks) != GDG_OK) return gdg_last_error(ctx);
-    if (ports != count + 1 || blocks != reportBlocks_) return format("a report of %d ports x %zu blocks where %d x %zu were expected", ports, blocks, count + 1, reportBlocks_);
-    if (blocks) memcpy(&lastReport_[(size_t)first * blocks], rec.data(), (size_t)count * blocks * sizeof(gdg_block_stats));
-    if (g == 0 && blocks) memcpy(&lastReport_[(size_t)(nChannels_ + 2) * blocks], &rec[(size_t)count * blocks], blocks * sizeof(gdg_block_stats));
-    return "";
+    const size_t nb = reportBlocks_, n = (size_t)count, metro = (size_t)nChannels_ + 2, has_metro = g == 0 ? 1 : 0;
+    Error e;
+    if (truePeak_) e = kindInto(ctx, count + 1, nb, 1, "true-peak records", lastTruePeak_, (size_t)first, n, metro, has_metro);
+    if (e.empty() && !alignRef_.empty()) e = kindInto(ctx, count + 1, nb, 1, "alignment records", lastAlign_, (size_t)first, n, metro, has_metro);
+    if (e.empty() && !spectrumEdges_.empty()) e = kindInto(ctx, count + 1, nb, (int)spectrumEdges_.size() - 1, nullptr, lastSpectrum_, (size_t)first, n, metro, has_metro);
+    if (e.empty() && report_) e = kindInto(ctx, count + 1, nb, 1, "a report", lastReport_, (size_t)first, n, metro, has_metro);
+    return e;
 }
 
-/* the finish's report (master left, master right) completes the call's */
+/* the finish's two rows of every kind (master left, master right) complete the call's; it has no alignment records: the shards' are the
+ * call's, the master rows zero */
 Error Engine::reportOfMaster(gdg_ctx *ctx) {
-    alignValid_ = !alignRef_.empty();                    /* the finish has no alignment records: the shards' are the call's, the master rows zero */
-    if (truePeak_) {                                     /* the finish's two rows complete the call's true-peak records */
-        std::vector<gdg_block_true_peak> rec;
-        Error e = truePeakOf(ctx, 2, rec);
-        if (!e.empty()) return e;
-        if (reportBlocks_) memcpy(&lastTruePeak_[(size_t)nChannels_ * reportBlocks_], rec.data(), 2 * reportBlocks_ * sizeof(gdg_block_true_peak));
-        truePeakValid_ = true;
-    }
-    if (!spectrumEdges_.empty()) {
-        std::vector<double> val;
-        Error e = spectrumOf(ctx, 2, val);
-        if (!e.empty()) return e;
-        const size_t row = reportBlocks_ * (spectrumEdges_.size() - 1);
-        if (row) memcpy(&lastSpectrum_[(size_t)nChannels_ * row], val.data(), 2 * row * sizeof(double));
-        spectrumValid_ = true;
-    }
-    if (!report_) return "";
-    int ports = 0;
-    size_t blocks = 0;
-    std::vector<gdg_block_stats> rec(2 * reportBlocks_);
-    if (gdg_batch_report(ctx, rec.data(), rec.size(), &ports, &blocks) != GDG_OK) return gdg_last_error(ctx);
-    if (ports != 2 || blocks != reportBlocks_) return format("a master report of %d ports x %zu blocks where 2 x %zu were expected", ports, blocks, reportBlocks_);
-    if (blocks) memcpy(&lastReport_[(size_t)nChannels_ * blocks], rec.data(), 2 * blocks * sizeof(gdg_block_stats));
-    reportValid_ = true;
-    return "";
+    const size_t nb = reportBlocks_, master = (size_t)nChannels_;
+    alignValid_ = !alignRef_.empty();
+    Error e;
+    if (truePeak_ && (e = kindInto(ctx, 2, nb, 1, "true-peak records", lastTruePeak_, master, 2, 0, 0)).empty()) truePeakValid_ = true;
+    if (e.empty() && !spectrumEdges_.empty() && (e = kindInto(ctx, 2, nb, (int)spectrumEdges_.size() - 1, nullptr, lastSpectrum_, master, 2, 0, 0)).empty()) spectrumValid_ = true;
+    if (e.empty() && report_ && (e = kindInto(ctx, 2, nb, 1, "a master report", lastReport_, master, 2, 0, 0)).empty()) reportValid_ = true;
+    return e;
 }
 
 Error Engine::SetBatchSpectrum(const std::vector<double> &edges) {
@@ -1321,27 +1289,13 @@ Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *o
     if (!ctx) return "BatchStreamStep: no streamed batch run is open";
     reportBegin(blocks > 0 ? (size_t)blocks : 0);
     if (gdg_batch_stream_step(ctx, blocks, ins, outs) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
-    if (report_) {                                       /* one shard, the plain run: the context's report is the engine's */
-        int ports = 0;
-        size_t nb = 0;
-        if (gdg_batch_report(ctx, lastReport_.data(), lastReport_.size(), &ports, &nb) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
-        reportValid_ = true;
-    }
-    if (truePeak_) {                                     /* ... and so are its true-peak records */
-        Error te = truePeakOf(ctx, nChannels_ + 3, lastTruePeak_);
-        if (!te.empty()) { setError(te); return LastError(); }
-        truePeakValid_ = true;
-    }
-    if (!alignRef_.empty()) {                            /* ... and so are its alignment records */
-        Error ae = alignOf(ctx, nChannels_ + 3, lastAlign_);
-        if (!ae.empty()) { setError(ae); return LastError(); }
-        alignValid_ = true;
-    }
-    if (!spectrumEdges_.empty()) {                       /* ... and so is its spectrum */
-        Error se = spectrumOf(ctx, nChannels_ + 3, lastSpectrum_);
-        if (!se.empty()) { setError(se); return LastError(); }
-        spectrumValid_ = true;
-    }
+    /* one shard, the plain run: the context's records of every kind are the engine's */
+    Error re;
+    if (report_ && (re = kindOf(ctx, nChannels_ + 3, reportBlocks_, 1, "a report", lastReport_)).empty()) reportValid_ = true;
+    if (re.empty() && truePeak_ && (re = truePeakOf(ctx, nChannels_ + 3, lastTruePeak_)).empty()) truePeakValid_ = true;
+    if (re.empty() && !alignRef_.empty() && (re = alignOf(ctx, nChannels_ + 3, lastAlign_)).empty()) alignValid_ = true;
+    if (re.empty() && !spectrumEdges_.empty() && (re = spectrumOf(ctx, nChannels_ + 3, lastSpectrum_)).empty()) spectrumValid_ = true;
+    if (!re.empty()) { setError(re); return LastError(); }
     return "";
 }
 
