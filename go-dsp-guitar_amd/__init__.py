@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "gdg_block_align_rows", "gdg_block_align_rows_device", "gdg_batch_align_enable", "gdg_batch_align",
     "gdg_true_peak_taps", "gdg_block_true_peak_rows", "gdg_block_true_peak_rows_device", "gdg_batch_true_peak_enable", "gdg_batch_true_peak",
     "gdg_batch_set_trim", "gdg_wave_encode_trim", "gdg_wave_encode_trim_device", "gdg_trim_from_true_peak",
+    "gdg_batch_set_blends", "gdg_batch_blends", "gdg_blend_rows", "gdg_blend_rows_device",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -334,6 +335,10 @@ def lib():
             "gdg_wave_encode_trim": (i32, [vp, i32, vp, C.c_size_t, C.c_double, i32, C.c_uint64, u32, C.c_uint64, vp]),
             "gdg_wave_encode_trim_device": (i32, [vp, i32, vp, C.c_size_t, C.c_double, i32, C.c_uint64, u32, C.c_uint64, vp]),
             "gdg_trim_from_true_peak": (i32, [vp, i32, C.c_size_t, C.c_double, C.c_double, vp]),
+            "gdg_batch_set_blends": (i32, [vp, i32, vp, vp, vp, vp]),
+            "gdg_batch_blends": (i32, [vp]),
+            "gdg_blend_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp, vp, vp]),
+            "gdg_blend_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, vp, vp, C.c_size_t]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -776,8 +781,10 @@ class Context:
     def batch_run(self, inputs, target_rate, out_format, metronome_to_master=False, run_meters=False, tuner_enqueue=False, outs=None):
         """controller.processFiles on the device (controller/controller.go:2809-3219 without prompts and file I/O).
         inputs: per channel None ("leaving channel empty") or (data-section bytes, format, sample_rate[, channels, channel]);
-        returns the N + 3 output data sections (uint8 arrays): out_0 .. out_{N-1}, master left, master right, metronome."""
+        returns the N + 3 output data sections (uint8 arrays): out_0 .. out_{N-1}, master left, master right, metronome -- and behind them
+        one per blend in force (batch_set_blends)."""
         n = len(inputs)
+        no = n + 3 + self.batch_blends()
         arr, _keep = self._batch_inputs(inputs)
         fo = WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
         opt = BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
@@ -785,9 +792,9 @@ class Context:
         self._check(lib().gdg_batch_length(self._h, arr, n, target_rate, C.byref(length)))
         wo = lib().gdg_wave_bytes_per_sample(fo)
         if outs is None:
-            outs = [np.zeros(length.value * wo, dtype=np.uint8) for _ in range(n + 3)]
-        assert len(outs) == n + 3 and all(o.dtype == np.uint8 and o.size == length.value * wo for o in outs)
-        ptrs = (C.c_void_p * (n + 3))(*[(o.ctypes.data if o.size else None) for o in outs])
+            outs = [np.zeros(length.value * wo, dtype=np.uint8) for _ in range(no)]
+        assert len(outs) == no and all(o.dtype == np.uint8 and o.size == length.value * wo for o in outs)
+        ptrs = (C.c_void_p * no)(*[(o.ctypes.data if o.size else None) for o in outs])
         self._check(lib().gdg_batch_run(self._h, arr, n, C.byref(opt), ptrs))
         return outs
 
@@ -801,8 +808,9 @@ class Context:
         length = C.c_size_t(0)
         self._check(lib().gdg_batch_length(self._h, arr, n, target_rate, C.byref(length)))
         wo = lib().gdg_wave_bytes_per_sample(fo)
-        outs = [np.zeros(length.value * wo, dtype=np.uint8) for _ in range(n + 3)]
-        ptrs = (C.c_void_p * (n + 3))(*[(o.ctypes.data if o.size else None) for o in outs])
+        no = n + 3 + self.batch_blends()                # the blends in force when the call is prepared
+        outs = [np.zeros(length.value * wo, dtype=np.uint8) for _ in range(no)]
+        ptrs = (C.c_void_p * no)(*[(o.ctypes.data if o.size else None) for o in outs])
         fn, h, ref = lib().gdg_batch_run, self._h, C.byref(opt)
 
         def call(_keep=(keep, arr, opt, ptrs, outs)):
@@ -917,17 +925,18 @@ class Context:
 
     def batch_stream_step(self, blocks, in_bytes, outs=None):
         """One slice: in_bytes[i] = the interleaved frames batch_stream_need asked for (bytes-like or None); returns the N + 3 output
-        pieces of blocks * 8192 samples each (uint8 arrays)."""
+        pieces of blocks * 8192 samples each (uint8 arrays), and one per blend in force behind them."""
         n = self.n_channels
+        no = n + 3 + self.batch_blends()
         keep = [None if b is None else np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b, dtype=np.uint8)
                 for b in in_bytes]
         assert len(keep) == n
         ins = (C.c_void_p * n)(*[(b.ctypes.data if b is not None and b.size else None) for b in keep])
         size = blocks * 8192 * self._stream_width
         if outs is None:
-            outs = [np.zeros(size, dtype=np.uint8) for _ in range(n + 3)]
-        assert len(outs) == n + 3 and all(o is None or (o.dtype == np.uint8 and o.size == size) for o in outs)
-        ptrs = (C.c_void_p * (n + 3))(*[(o.ctypes.data if o is not None else None) for o in outs])
+            outs = [np.zeros(size, dtype=np.uint8) for _ in range(no)]
+        assert len(outs) == no and all(o is None or (o.dtype == np.uint8 and o.size == size) for o in outs)
+        ptrs = (C.c_void_p * no)(*[(o.ctypes.data if o is not None else None) for o in outs])
         self._check(lib().gdg_batch_stream_step(self._h, blocks, ins, ptrs))
         return outs
 
@@ -1153,6 +1162,55 @@ class Context:
         """gdg_wave_encode_trim_device on plain device pointers (ints), enqueued on the context's stream."""
         f = WAVE_FORMATS[fmt] if isinstance(fmt, str) else fmt
         self._check(lib().gdg_wave_encode_trim_device(self._h, f, d_samples, n, float(gain), int(mode), int(seed), int(port), int(first_index), d_bytes))
+
+    @staticmethod
+    def _blend_csr(blends):
+        """[[(channel, weight), ..], ..] -> (first, channel, weight) as int32 / int32 / float64 arrays; channel and weight carry a spare entry,
+        so that lists without a term still have an address and the library can name the empty blend"""
+        first = np.zeros(len(blends) + 1, dtype=np.int32)
+        first[1:] = np.cumsum([len(b) for b in blends], dtype=np.int64)
+        terms = [t for b in blends for t in b]
+        return first, np.array([int(c) for c, _ in terms] + [0], dtype=np.int32), np.array([float(w) for _, w in terms] + [0.0], dtype=np.float64)
+
+    def batch_set_blends(self, blends, gain=None):
+        """The blend outputs of the next batch calls (gdg_batch_set_blends): blends = a list of lists of (channel, weight) -- blend b is the
+        sum of its terms over this context's chain output rows, in term order, and port N + 3 + b of every batch call; gain: one output gain
+        per blend (None: all 1).  An empty list (or None): off.  Configuration: not in a checkpoint."""
+        blends = [] if blends is None else [list(b) for b in blends]
+        if not blends:
+            self._check(lib().gdg_batch_set_blends(self._h, 0, None, None, None, None))
+            return
+        first, channel, weight = self._blend_csr(blends)
+        g = None if gain is None else np.ascontiguousarray(gain, dtype=np.float64).reshape(-1)
+        if g is not None and g.size != len(blends):
+            raise ValueError("%d gains for %d blends" % (g.size, len(blends)))
+        self._check(lib().gdg_batch_set_blends(self._h, len(blends), first.ctypes.data, channel.ctypes.data,
+                                               weight.ctypes.data, None if g is None else g.ctypes.data))
+
+    def batch_blends(self):
+        """The number of blends in force (gdg_batch_blends)."""
+        return int(lib().gdg_batch_blends(self._h))
+
+    def blend_rows(self, rows, blends):
+        """gdg_blend_rows: rows [n_rows, samples] float64, blends as batch_set_blends takes them with `channel` naming a row -> [blends, samples]."""
+        x = np.ascontiguousarray(rows, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("rows: [n_rows, samples]")
+        blends = [list(b) for b in blends]
+        first, channel, weight = self._blend_csr(blends)
+        out = np.zeros((len(blends), x.shape[1]), dtype=np.float64)
+        rp = (C.c_void_p * max(x.shape[0], 1))(*[x[r].ctypes.data for r in range(x.shape[0])])
+        op = (C.c_void_p * max(len(blends), 1))(*[out[b].ctypes.data for b in range(len(blends))])
+        self._check(lib().gdg_blend_rows(self._h, rp, x.shape[0], x.shape[1], len(blends), first.ctypes.data, channel.ctypes.data,
+                                         weight.ctypes.data, op))
+        return out
+
+    def blend_rows_device(self, d_rows, row_stride, n_rows, samples, blends, d_out, out_stride):
+        """gdg_blend_rows_device on plain device pointers (ints); returns when the sums are written."""
+        blends = [list(b) for b in blends]
+        first, channel, weight = self._blend_csr(blends)
+        self._check(lib().gdg_blend_rows_device(self._h, d_rows, row_stride, n_rows, samples, len(blends), first.ctypes.data,
+                                                channel.ctypes.data, weight.ctypes.data, d_out, out_stride))
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

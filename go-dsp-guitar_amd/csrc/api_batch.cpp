@@ -114,6 +114,11 @@ struct BatchLoop {
     const gdg_spectrum_bands *bands;            /* the band spectrum's launch argument; null = off */
     const std::vector<gdg_align_pairs> *align;  /* the alignment report: the measured ports of this call, a launch's worth to a piece; null = off */
     const double *d_trim;                       /* the output trim: the gains of the window's N + 3 rows on the device; null = off */
+    /* the blend outputs: n_blends rows behind the window's N + 3 (0 = off, and always for a shard); their table on the device (blend.h) and
+     * their output gains -- null = every one 1.0: the blend rows go through the plain or the dithered encoder */
+    int n_blends;
+    const int *d_blend_first, *d_blend_channel;
+    const double *d_blend_weight, *d_blend_gain;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -139,7 +144,7 @@ static void job_step(size_t job, int W, size_t p, size_t *first, int *w) {
 typedef std::function<int(size_t i, size_t off, int w, int pool)> BatchStage;
 
 static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &stage_fn) {
-    const int N = p.N, NO = N + 3, B = GDG_BLOCK_SIZE, enc_rows = p.enc_rows, f64_rows = p.f64_rows, out_width = p.out_width, W = p.W;
+    const int N = p.N, NO = N + 3, NR = NO + p.n_blends, B = GDG_BLOCK_SIZE, enc_rows = p.enc_rows, f64_rows = p.f64_rows, out_width = p.out_width, W = p.W;
     const size_t length = p.length, ws = p.ws, enc_bytes = p.enc_bytes;
     double *const d_inputs = p.d_inputs, *const d_win = p.d_win;
     unsigned char *const d_enc = p.d_enc;
@@ -172,12 +177,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
      * scatter of piece c runs while piece c + 1 is on the bus -- the run's tail (last download, then last scatter) and its head are that
      * much shorter; in between the device sets the pace either way. */
     /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; behind them one section per live kind of the render
-     * report, [rows][w] -- N + 3 rows, a shard's N chain rows and the metronome's -- which come down with the last piece */
+     * report, [rows][w] -- N + 3 rows and the blends', a shard's N chain rows and the metronome's -- which come down with the last piece */
     auto down_bytes = [&](size_t i) {
         const size_t wb = (size_t)steps[i].w * B, row_bytes = wb * out_width;
-        return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NO * row_bytes;
+        return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
     };
-    const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NO;
+    const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NR;
     for (size_t i = 0; i < steps.size(); i++) steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
@@ -253,40 +258,49 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             ProfScope ps(ctx, GDG_K_WAVE);
             const size_t row_bytes = (size_t)wb * out_width;
             const ReportSections &sec = steps[i].sec;
+            /* the blend rows, behind the metronome's: sums of the chain rows, which are final; every reader below takes them as rows like the others */
+            if (p.n_blends)
+                HIP_TRY(ctx, gdg_launch_blend_rows(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight,
+                                                   d_win + (size_t)NO * ws, ws, ctx->stream));
             if (p.live.on(REPORT_STATS)) {                                   /* the rows as the encoder is about to read them */
                 gdg_block_stats *rec = reinterpret_cast<gdg_block_stats *>(enc + sec.at[REPORT_STATS]);
-                HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, (unsigned)B, rec, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, (unsigned)B, rec, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_stats(d_metro, ws, 1u, (size_t)wb, (unsigned)B, rec + (size_t)N * w, ctx->stream));
             }
             if (p.bands) {                                                   /* the same rows, one more reader */
                 double *sp = reinterpret_cast<double *>(enc + sec.at[REPORT_BANDS]);
-                HIP_TRY(ctx, gdg_launch_block_spectrum(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_block_spectrum(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp, ctx->stream));
                 if (sharded && run_metro)
                     HIP_TRY(ctx, gdg_launch_block_spectrum(d_metro, ws, 1u, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp + (size_t)N * w * n_bands, ctx->stream));
             }
             if (p.align)                                                     /* ... and one more: a shard's metronome port is row N + 2, as d_metro is */
                 for (const gdg_align_pairs &q : *p.align)
-                    HIP_TRY(ctx, gdg_launch_block_align(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (unsigned)N + 2u, (unsigned)rec_rows, (size_t)wb, q, align_tw,
+                    HIP_TRY(ctx, gdg_launch_block_align(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (unsigned)N + 2u, (unsigned)rec_rows, (size_t)wb, q, align_tw,
                                                         enc + sec.at[REPORT_ALIGN], ctx->stream));
             if (p.live.on(REPORT_TRUE_PEAK)) {                               /* ... and the inter-sample peaks of the same rows */
                 gdg_block_true_peak *tp = reinterpret_cast<gdg_block_true_peak *>(enc + sec.at[REPORT_TRUE_PEAK]);
-                HIP_TRY(ctx, gdg_launch_block_true_peak(d_win, ws, sharded ? (unsigned)N : (unsigned)NO, (size_t)wb, true_peak_table(), tp, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_block_true_peak(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, true_peak_table(), tp, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_true_peak(d_metro, ws, 1u, (size_t)wb, true_peak_table(), tp + (size_t)N * w, ctx->stream));
             }
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
-            /* trim on: the trimmed siblings of either; `gain_row` = the launch's first row in the window's order (the order of the gains) */
-            auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, unsigned gain_row) -> hipError_t {
+            /* trim on: the trimmed siblings of either; `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
+            auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
                 const gdg_dither_rows dz = { ctx->dither_seed, p.dither_first + off, port_base, n_chain };
-                if (p.d_trim)
-                    return gdg_launch_wave_encode_rows_trim(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, p.d_trim + gain_row, p.dither ? &dz : nullptr, ctx->stream);
+                if (gains)
+                    return gdg_launch_wave_encode_rows_trim(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, gains, p.dither ? &dz : nullptr, ctx->stream);
                 if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
                 return gdg_launch_wave_encode_rows_dither(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, dz, ctx->stream);
             };
-            if (!sharded) HIP_TRY(ctx, encode_rows(d_win, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, 0u));
-            else {
-                HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc, 0u));
+            if (!sharded) {
+                HIP_TRY(ctx, encode_rows(d_win, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
+                /* a launch of their own: blend b is port port_base + N + 3 + b of the dither, and its gain is the blend's, not the trim's */
+                if (p.n_blends)
+                    HIP_TRY(ctx, encode_rows(d_win + (size_t)NO * ws, (unsigned)p.n_blends, (unsigned)p.n_blends, ctx->dither_port_base + (uint32_t)NO,
+                                             enc + (size_t)NO * row_bytes, p.d_blend_gain));
+            } else {
+                HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
                 if (shard->metronome_bytes)
-                    HIP_TRY(ctx, encode_rows(d_metro, 1u, 1u, GDG_DITHER_PORT_METRONOME, enc + (size_t)N * row_bytes, (unsigned)N + GDG_TRIM_METRONOME));
+                    HIP_TRY(ctx, encode_rows(d_metro, 1u, 1u, GDG_DITHER_PORT_METRONOME, enc + (size_t)N * row_bytes, p.d_trim ? p.d_trim + N + GDG_TRIM_METRONOME : nullptr));
                 unsigned char *f64 = enc + (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15);
                 HIP_TRY(ctx, hipMemcpy2DAsync(f64, (size_t)wb * sizeof(double), d_master, ws * sizeof(double), (size_t)wb * sizeof(double), 2,
                                               hipMemcpyDeviceToDevice, ctx->stream));
@@ -462,12 +476,50 @@ int gdg_batch_set_trim(gdg_ctx *ctx, const double *chain_gain, int n, double mas
     return GDG_OK;
 }
 
+/* the blend outputs: validated whole before the list replaces the one in force (blend.h); read when a job is described and by every slice */
+int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set blends: a streamed batch run is open on this context; its blends hold until gdg_batch_stream_close");
+    int b = -1, k = -1;
+    switch (gdg_blend_check(n_blends, first, channel, weight, gain, ctx->nch, &b, &k)) {
+    case BLEND_OK: break;
+    case BLEND_COUNT: return fail(ctx, GDG_ERR_INVALID, "set blends: %d blends; 0 (off) to %d", n_blends, GDG_BLEND_MAX_BLENDS);
+    case BLEND_NULL: return fail(ctx, GDG_ERR_INVALID, "set blends: %d blends need first, channel and weight", n_blends);
+    case BLEND_FIRST: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d: first[%d] = %d, first[%d] = %d; the offsets start at 0 and never descend", b, b, first[b], b + 1, first[b + 1]);
+    case BLEND_EMPTY: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d has no term; 1 to %d", b, GDG_BLEND_MAX_TERMS);
+    case BLEND_TERMS: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d has %d terms; 1 to %d", b, first[b + 1] - first[b], GDG_BLEND_MAX_TERMS);
+    case BLEND_CHANNEL:
+        return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d names channel %d, the context has channels 0 to %d", b, k, channel[first[b] + k], ctx->nch - 1);
+    case BLEND_WEIGHT: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d: weight = %g is not finite", b, k, weight[first[b] + k]);
+    default: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d: gain = %g is not finite", b, gain[b]);
+    }
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    const bool resize = n_blends != ctx->blend.count();
+    /* another row count: whatever still reads the window and the encoded halves has to be done before they go -- and a wait that fails
+     * refuses the call with the setting in force untouched */
+    if (resize) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    gdg_blend_replace(ctx->blend, n_blends, first, channel, weight, gain, ctx->nch, &b, &k);      /* checked above: it cannot refuse */
+    if (resize) {
+        /* the window and the encoded halves are made anew by the next batch call, at the size of a context that was always configured like
+         * this one; off, the table goes as well */
+        for (int i : { (int)BATCH_WINDOW, (int)BATCH_ENCODED }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+        if (ctx->blend.count() == 0) { hipFree(ctx->d_blend); ctx->d_blend = nullptr; ctx->d_blend_cap = 0; }
+    }
+    return GDG_OK;
+}
+
+int gdg_batch_blends(const gdg_ctx *ctx) { return ctx ? ctx->blend.count() : 0; }
+
 /* the master cursor belongs to gdg_batch_finish_master_slice, which is no part of an open job: it may be set while one is open */
 int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
     if (!ctx) return GDG_ERR_INVALID;
     ctx->dither_cursor = sample_index;
     return GDG_OK;
 }
+
+/* a shard's rows are its own channels' and a blend's terms may live on two devices: neither is settled, so the shard calls refuse (include/gdg.h) */
+#define BLENDS_REFUSED(ctx, what) \
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d blends are in force on this context (gdg_batch_set_blends); a sharded job cannot write blend outputs yet", what, (ctx)->blend.count())
 
 #define SHARD_PORTS " (a shard: its N inputs, its N outputs, metronome, left, right)"
 static int check_meter_ports(gdg_ctx *ctx, const gdg_batch_options *opt, const char *note) {
@@ -488,9 +540,17 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
         return fail(ctx, GDG_ERR_INVALID, "the batch loop runs blocks of %d frames, the context allows %d", GDG_BLOCK_SIZE, ctx->max_frames);
     if (!gdg_wave_bytes_per_sample(opt->out_format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", opt->out_format);
     if (opt->target_rate == 0) return fail(ctx, GDG_ERR_INVALID, "sample rate must be positive");
-    if (!ctx->align_ref.empty() && (int)ctx->align_ref.size() != n_inputs + (shard ? 1 : 3))      /* before anything is done */
+    const int n_blends = shard ? 0 : ctx->blend.count();                         /* the shard calls refuse blends before they come here */
+    if (!ctx->align_ref.empty() && (int)ctx->align_ref.size() != n_inputs + (shard ? 1 : 3) && (n_blends == 0 || (int)ctx->align_ref.size() != n_inputs + 3 + n_blends)) {      /* before anything is done */
+        if (n_blends)
+            return fail(ctx, GDG_ERR_INVALID, "batch align: the list in force has %zu ports, this call %d (the N chain outputs, master left, master right, metronome) or %d "
+                        "(those and the %d blends in force)", ctx->align_ref.size(), n_inputs + 3, n_inputs + 3 + n_blends, n_blends);
         return fail(ctx, GDG_ERR_INVALID, "batch align: the list in force has %zu ports, this call %d (%s)", ctx->align_ref.size(), n_inputs + (shard ? 1 : 3),
                     shard ? "a shard's n chain outputs and the metronome" : "the N chain outputs, master left, master right, metronome");
+    }
+    if (n_blends && ctx->dither_mode != 0 && !gdg_dither_ports_ok(ctx->dither_port_base, n_inputs + 3 + n_blends))
+        return fail(ctx, GDG_ERR_INVALID, "blends: the dither's port_base %u + %d channels + 3 + %d blends reaches the job-wide ports from 0x%x on", ctx->dither_port_base,
+                    n_inputs, n_blends, GDG_DITHER_PORT_MASTER_LEFT);
     int rc;
     if (meters_at_open && (rc = check_meter_ports(ctx, opt, shard ? SHARD_PORTS : "")) != GDG_OK) return rc;
     std::vector<size_t> n_out((size_t)n_inputs, 0);
@@ -552,6 +612,7 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
 
 int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t job_samples,
                                 int run_metronome, size_t *samples) {
+    if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
     if (ctx && opt && opt->metronome_to_master)
         return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_open_shard: metronome_to_master must be 0 -- a shard's master mix is a partial sum; pass the metronome's "
@@ -610,7 +671,9 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const gdg_batch_options *opt = &S.opt;
     const int N = ctx->nch, NO = N + 3, B = GDG_BLOCK_SIZE, out_width = gdg_wave_bytes_per_sample(opt->out_format);
     const size_t length = (size_t)blocks * B, pos = S.pos;                       /* the slice: rows of `length` samples, the job's [pos, pos + length) */
-    report_begin(ctx, sharded ? N + 1 : NO, (size_t)blocks);
+    /* the blends in force (never a shard's): NR rows of the window leave the device encoded, and every record kind has NR ports */
+    const int n_blends = sharded ? 0 : ctx->blend.count(), NR = NO + n_blends;
+    report_begin(ctx, sharded ? N + 1 : NR, (size_t)blocks, true, n_blends);
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -627,15 +690,15 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const size_t ws = (size_t)W * B;
     /* a shard's slice: the rows that leave the device encoded and as float64 are this slice's (which metronome buffers it passes), the
      * room for them is the job's (whether the shard runs the metronome): no slice makes a buffer grow */
-    const int enc_rows = !sharded ? NO : N + (slice->metronome_bytes ? 1 : 0), f64_rows = !sharded ? 0 : 2 + (slice->metronome ? 1 : 0);
-    const int enc_room = !sharded ? NO : N + (S.run_metro ? 1 : 0), f64_room = !sharded ? 0 : 2 + (S.run_metro ? 1 : 0);
+    const int enc_rows = !sharded ? NR : N + (slice->metronome_bytes ? 1 : 0), f64_rows = !sharded ? 0 : 2 + (slice->metronome ? 1 : 0);
+    const int enc_room = !sharded ? NR : N + (S.run_metro ? 1 : 0), f64_room = !sharded ? 0 : 2 + (S.run_metro ? 1 : 0);
     /* a half also holds, behind its rows, a window's section of every kind of the render report the call collects (report_sections.h) */
     const ReportLive live = report_live(ctx);
     const gdg_spectrum_bands bands = live.on(REPORT_BANDS) ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), opt->target_rate) : gdg_spectrum_bands();
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
-                           + report_room(live, (size_t)(sharded ? N + 1 : NO), (size_t)W);
+                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -677,8 +740,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         int r;
         if ((r = batch_buffer(ctx, BATCH_INPUTS, (size_t)N * length * sizeof(double), (void **)&d_inputs)) != GDG_OK) return r;
         /* one window of the N + 3 outputs, rows in the output files' order (out_0 .. out_{N-1}, master left, master right, metronome,
-         * controller.go:3123-3219); the inputs are read where they lie */
-        if ((r = batch_buffer(ctx, BATCH_WINDOW, (size_t)NO * ws * sizeof(double), (void **)&d_win)) != GDG_OK) return r;
+         * controller.go:3123-3219), and behind them the rows of the blends in force; the inputs are read where they lie */
+        if ((r = batch_buffer(ctx, BATCH_WINDOW, (size_t)NR * ws * sizeof(double), (void **)&d_win)) != GDG_OK) return r;
         if ((r = batch_buffer(ctx, BATCH_ENCODED, 2 * enc_bytes, (void **)&d_enc)) != GDG_OK) return r;
         if ((r = batch_carry_buffer(ctx, &d_carry)) != GDG_OK) return r;
         if ((r = batch_buffer(ctx, BATCH_UPLOAD, 2 * up_half, (void **)&d_up)) != GDG_OK) return r;
@@ -805,13 +868,31 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr };
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
             if (!ctx->d_trim && hipMalloc((void **)&ctx->d_trim, (size_t)NO * sizeof(double)) != hipSuccess)
                 return fail(ctx, GDG_ERR_NOMEM, "the batch run cannot allocate the trim's %d gains on the device", NO);
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_trim, ctx->trim_gain.data(), (size_t)NO * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             loop.d_trim = ctx->d_trim;
+        }
+        /* the blends in force: their table goes up the same way -- first | channel | weight | gain, the doubles 8-byte aligned (BlendSet::packed) */
+        if (n_blends) {
+            const BlendSet &bs = ctx->blend;                                  /* packed when it was set: it lives as long as the setting, so nothing waits here */
+            const size_t ints = bs.packed_ints(), bytes = bs.packed.size();
+            if (bytes > ctx->d_blend_cap) {
+                hipFree(ctx->d_blend);
+                ctx->d_blend = nullptr;
+                ctx->d_blend_cap = 0;
+                if (hipMalloc((void **)&ctx->d_blend, bytes) != hipSuccess) return fail(ctx, GDG_ERR_NOMEM, "the batch run cannot allocate the table of %d blends on the device", n_blends);
+                ctx->d_blend_cap = bytes;
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_blend, bs.packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+            loop.n_blends = n_blends;
+            loop.d_blend_first = reinterpret_cast<const int *>(ctx->d_blend);
+            loop.d_blend_channel = loop.d_blend_first + n_blends + 1;
+            loop.d_blend_weight = reinterpret_cast<const double *>(ctx->d_blend + ints);
+            loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.d_blend_weight + bs.terms();
         }
         return batch_block_loop(ctx, loop, stage);
     };
@@ -875,7 +956,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
         if (job.inputs[(size_t)i].bytes && job.inputs[(size_t)i].samples_per_channel > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "input %d is too long", i);
     if (job.length == 0) {                                                       /* every output has 0 samples */
         ctx->batch_up_bytes = ctx->batch_resampled = 0;
-        report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3, 0);
+        report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
@@ -894,6 +975,7 @@ int gdg_batch_run(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
 int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes,
                         const gdg_batch_shard_out *shard) {
     if (!shard) return GDG_ERR_INVALID;
+    if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
      * metronome track of the shard that ran it).  A set flag here would be silently dropped -- refuse it instead. */
     if (ctx && opt && opt->metronome_to_master)

@@ -378,6 +378,9 @@ int gdg_batch_stream_resume(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_i
 
 int gdg_batch_stream_resume_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *options, size_t job_samples,
                                   int run_metronome, const void *blob, size_t bytes, size_t *samples_done) {
+    if (ctx && ctx->blend.count())
+        return fail(ctx, GDG_ERR_UNSUPPORTED, "gdg_batch_stream_resume_shard: %d blends are in force on this context (gdg_batch_set_blends); a sharded job cannot write blend outputs yet",
+                    ctx->blend.count());
     if (ctx && options && options->metronome_to_master)
         return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_resume_shard: metronome_to_master must be 0, as for gdg_batch_stream_open_shard");
     return resume(ctx, inputs, n_inputs, options, true, job_samples, run_metronome != 0, blob, bytes, samples_done);

@@ -738,6 +738,71 @@ int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int
     return batch_kind_get(ctx, REPORT_ALIGN, ctx && !ctx->align_ref.empty(), words, records, capacity, ports, blocks, nullptr);
 }
 
+/* ---- the blend on its own (include/gdg.h; the kernel: blend_kernels.h in io.hip; the list's validation: blend.h; the batch calls: api_batch.cpp) ---- */
+static int blend_rows_check(gdg_ctx *ctx, int n_rows, int n_blends, const int *first, const int *channel, const double *weight) {
+    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "blend rows: %d rows (at least 1)", n_rows);
+    int b = -1, k = -1;
+    switch (gdg_blend_check(n_blends, first, channel, weight, nullptr, n_rows, &b, &k)) {
+    case BLEND_OK: return GDG_OK;
+    case BLEND_COUNT: return fail(ctx, GDG_ERR_INVALID, "blend rows: %d blends; 0 to %d", n_blends, GDG_BLEND_MAX_BLENDS);
+    case BLEND_NULL: return fail(ctx, GDG_ERR_INVALID, "blend rows: %d blends need first, channel and weight", n_blends);
+    case BLEND_FIRST: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d: first[%d] = %d, first[%d] = %d; the offsets start at 0 and never descend", b, b, first[b], b + 1, first[b + 1]);
+    case BLEND_EMPTY: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d has no term; 1 to %d", b, GDG_BLEND_MAX_TERMS);
+    case BLEND_TERMS: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d has %d terms; 1 to %d", b, first[b + 1] - first[b], GDG_BLEND_MAX_TERMS);
+    case BLEND_CHANNEL: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d names row %d of %d", b, k, channel[first[b] + k], n_rows);
+    default: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d: weight = %g is not finite", b, k, weight[first[b] + k]);
+    }
+}
+
+/* the table is the caller's host memory: it goes up, the kernel runs, and the call returns when the rows are written */
+int gdg_blend_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                          const double *weight, double *d_out, size_t out_stride) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight);
+    if (rc != GDG_OK) return rc;
+    if (n_blends == 0 || samples == 0) return GDG_OK;
+    if (!d_rows || !d_out) return GDG_ERR_INVALID;
+    if (row_stride < samples || out_stride < samples) return fail(ctx, GDG_ERR_INVALID, "blend rows: strides of %zu and %zu samples for rows of %zu", row_stride, out_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7)) return fail(ctx, GDG_ERR_INVALID, "blend rows: rows and sums are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    const size_t terms = (size_t)first[n_blends], ints = (((size_t)n_blends + 1 + terms) * sizeof(int) + 7) & ~(size_t)7, bytes = ints + terms * sizeof(double);
+    std::vector<unsigned char> host(bytes, 0);
+    memcpy(host.data(), first, ((size_t)n_blends + 1) * sizeof(int));
+    memcpy(host.data() + ((size_t)n_blends + 1) * sizeof(int), channel, terms * sizeof(int));
+    memcpy(host.data() + ints, weight, terms * sizeof(double));
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, bytes));
+    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        const int *d_first = static_cast<const int *>(d);
+        e = gdg_launch_blend_rows(d_rows, row_stride, samples, (unsigned)n_blends, d_first, d_first + n_blends + 1,
+                                  reinterpret_cast<const double *>(static_cast<unsigned char *>(d) + ints), d_out, out_stride, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(w));
+    return GDG_OK;
+}
+
+int gdg_blend_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel, const double *weight,
+                   double *const *out) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight);
+    if (rc != GDG_OK) return rc;
+    if (n_blends == 0 || samples == 0) return GDG_OK;
+    if (!rows || !out) return GDG_ERR_INVALID;
+    for (int b = 0; b < n_blends; b++) if (!out[b]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the row of blend %d is NULL", b);
+    std::vector<double> sums((size_t)n_blends * samples);
+    rc = rows_round_trip(ctx, "blend rows", rows, n_rows, samples, sums.data(), sums.size() * sizeof(double), [&](const double *d_rows, void *d_out) {
+        return gdg_blend_rows_device(ctx, d_rows, samples, n_rows, samples, n_blends, first, channel, weight, static_cast<double *>(d_out), samples);
+    });
+    if (rc != GDG_OK) return rc;
+    for (int b = 0; b < n_blends; b++) memcpy(out[b], sums.data() + (size_t)b * samples, samples * sizeof(double));
+    return GDG_OK;
+}
+
 /* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */
 static_assert(sizeof(gdg_block_true_peak) == 16 && offsetof(gdg_block_true_peak, position) == 8 && offsetof(gdg_block_true_peak, overs) == 12,
               "gdg_block_true_peak: 16 bytes, no padding");

@@ -49,6 +49,7 @@
 #include "dither.h"
 #include "report_sections.h"
 #include "trim.h"
+#include "blend.h"
 
 #define NUM_FILTERS 8
 
@@ -400,6 +401,13 @@ struct gdg_ctx {
      * device copy is made and uploaded at the start of a batch call, only while a trim is in force.  Configuration like the dither: in no blob. */
     std::vector<double> trim_gain;
     double *d_trim = nullptr;
+    /* the blend outputs (gdg_batch_set_blends; blend.h): weighted sums of this context's chain rows as the ports behind the metronome's; an
+     * empty list = off (never set, or set with 0 blends).  While blends are in force a batch window has nch + 3 + count() rows and the device
+     * copy of the table -- first | channel | weight | gain, made and uploaded at the start of a batch call -- exists; off, neither does.
+     * Configuration like the trim: in no blob. */
+    BlendSet blend;
+    unsigned char *d_blend = nullptr;
+    size_t d_blend_cap = 0;
     /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;
@@ -692,11 +700,13 @@ int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
 static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_have_reader(ctx->batch_source); }
 /* a batch call begins: every kind's records of the call before are gone; a kind that is switched on gets zeroed records for `ports` x
  * `blocks`.  `align`: this call may collect alignment records (the finish calls never do) */
-static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool align = true) {
+static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool align = true, int blend_ports = 0) {
     ctx->spec_live_edges = ctx->spec_edges;
     ctx->align_live_ref.clear();
-    if (align && (int)ctx->align_ref.size() == ports) {                      /* any other count was refused when the job was described */
+    /* any other count was refused when the job was described; a list without the call's blend ports: each of them references itself */
+    if (align && ((int)ctx->align_ref.size() == ports || (blend_ports > 0 && (int)ctx->align_ref.size() == ports - blend_ports))) {
         ctx->align_live_ref = ctx->align_ref;
+        for (int p = (int)ctx->align_ref.size(); p < ports; p++) ctx->align_live_ref.push_back(p);
         ctx->align_live_lag = ctx->align_lag;
     }
     const bool on[REPORT_KINDS] = { ctx->report_on, !ctx->spec_live_edges.empty(), !ctx->align_live_ref.empty(), ctx->tp_on };
@@ -737,7 +747,7 @@ static inline void report_file(gdg_ctx *ctx, int k, const unsigned char *section
 /* gdg_ctx::batch_dev, slot by slot (the slice runner, api_batch.cpp) */
 enum {
     BATCH_INPUTS,                          /* [N][slice] decoded (and resampled) inputs */
-    BATCH_WINDOW,                          /* [N + 3][window] one step's outputs */
+    BATCH_WINDOW,                          /* [N + 3 + blends][window] one step's outputs, the blend rows (gdg_batch_set_blends) behind the metronome's */
     BATCH_ENCODED,                         /* two halves of a step on its way down: encoded rows, a shard's float64 rows */
     BATCH_CARRY,                           /* [N][GDG_STREAM_CARRY] source frames every resampled input keeps for its next step */
     BATCH_UPLOAD,                          /* two halves of a step on its way up: descriptors, then the inputs' bytes */

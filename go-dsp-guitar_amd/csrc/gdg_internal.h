@@ -355,6 +355,11 @@ hipError_t gdg_launch_block_align(const double *d_rows, size_t row_stride, unsig
  * n_rows rows one gdg_block_true_peak into d_records[r][ceil(samples / 8192)]; taps: the table of true_peak_taps.h, passed by value */
 hipError_t gdg_launch_block_true_peak(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, const gdg_true_peak_table &taps, void *d_records,
                                       hipStream_t s);
+/* the blend outputs (include/gdg.h; io.hip, blend_kernels.h; the arithmetic: blend.h): row b of d_out (row b at d_out + b * out_stride) is the sum of
+ * blend b's terms d_first[b] .. d_first[b + 1] over `samples` samples of the rows of d_rows, in term order.  The table lies in device memory and
+ * has been checked by the caller: every channel a row of d_rows, 1 to 32 terms a blend.  Rows 8-byte aligned, strides >= samples. */
+hipError_t gdg_launch_blend_rows(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
+                                 const double *d_weight, double *d_out, size_t out_stride, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

@@ -598,19 +598,20 @@ func (this *Context) BatchRun(inputs []BatchInput, opt BatchOptions) ([][]byte, 
 		return nil, e
 	}
 	each := int(samples) * int(C.gdg_wave_bytes_per_sample(o.out_format))
-	outs := make([][]byte, n+3)
+	no := n + 3 + int(C.gdg_batch_blends(this.ctx)) // the blends in force (BatchSetBlends): one more port each, behind the metronome's
+	outs := make([][]byte, no)
 	if each == 0 {
 		for i := range outs {
 			outs[i] = []byte{}
 		}
 		return outs, nil
 	}
-	ptrs := (*[1 << 20]unsafe.Pointer)(C.calloc(C.size_t(n+3), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	ptrs := (*[1 << 20]unsafe.Pointer)(C.calloc(C.size_t(no), C.size_t(unsafe.Sizeof(uintptr(0)))))
 	if ptrs == nil {
 		return nil, fmt.Errorf("gdg: out of memory")
 	}
 	defer C.free(unsafe.Pointer(ptrs))
-	for i := 0; i < n+3; i++ {
+	for i := 0; i < no; i++ {
 		ptrs[i] = C.malloc(C.size_t(each))
 		if ptrs[i] == nil {
 			return nil, fmt.Errorf("gdg: out of memory (%d bytes per output)", each)
@@ -857,7 +858,8 @@ func (this *Context) BatchStreamStep(blocks int, frames [][]byte) ([][]byte, err
 			C.free(p)
 		}
 	}()
-	ptrs := (*[1 << 20]unsafe.Pointer)(C.calloc(C.size_t(2*n+3), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	no := n + 3 + int(C.gdg_batch_blends(this.ctx)) // the blends in force: they cannot change while the job is open
+	ptrs := (*[1 << 20]unsafe.Pointer)(C.calloc(C.size_t(n+no), C.size_t(unsafe.Sizeof(uintptr(0)))))
 	if ptrs == nil {
 		return nil, fmt.Errorf("gdg: out of memory")
 	}
@@ -872,7 +874,7 @@ func (this *Context) BatchStreamStep(blocks int, frames [][]byte) ([][]byte, err
 		}
 		owned = append(owned, ptrs[i])
 	}
-	for i := n; i < 2*n+3; i++ {
+	for i := n; i < n+no; i++ {
 		ptrs[i] = C.malloc(C.size_t(each))
 		if ptrs[i] == nil {
 			return nil, fmt.Errorf("gdg: out of memory (%d bytes per output)", each)
@@ -882,7 +884,7 @@ func (this *Context) BatchStreamStep(blocks int, frames [][]byte) ([][]byte, err
 	if e := this.err(C.gdg_batch_stream_step(this.ctx, C.int(blocks), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[0])), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[n])))); e != nil {
 		return nil, e
 	}
-	outs := make([][]byte, n+3)
+	outs := make([][]byte, no)
 	for i := range outs {
 		outs[i] = goBytes(ptrs[n+i], each)
 	}
@@ -1852,4 +1854,141 @@ func TrimFromTruePeak(records [][]BlockTruePeak, target float64, maxGain float64
 		gain[i] = float64(out[i])
 	}
 	return gain, nil
+}
+
+// BlendTerm: one term of a blend output: a channel of the context (for BlendRows: a row) and its weight.
+type BlendTerm struct {
+	Channel int
+	Weight  float64
+}
+
+// blendTable: the blends in gdg_batch_set_blends' CSR form, in C memory (first: len(blends)+1 offsets; channel, weight: one entry per term,
+// one spare entry each so that a list without terms still has an address); release frees all three.
+func blendTable(blends [][]BlendTerm) (first *[1 << 28]C.int, channel *[1 << 28]C.int, weight *[1 << 28]C.double, release func(), err error) {
+	terms := 0
+	for _, b := range blends {
+		terms += len(b)
+	}
+	first = (*[1 << 28]C.int)(C.calloc(C.size_t(len(blends)+1), C.size_t(unsafe.Sizeof(C.int(0)))))
+	channel = (*[1 << 28]C.int)(C.calloc(C.size_t(terms+1), C.size_t(unsafe.Sizeof(C.int(0)))))
+	weight = (*[1 << 28]C.double)(C.calloc(C.size_t(terms+1), C.size_t(unsafe.Sizeof(C.double(0)))))
+	release = func() {
+		C.free(unsafe.Pointer(first))
+		C.free(unsafe.Pointer(channel))
+		C.free(unsafe.Pointer(weight))
+	}
+	if first == nil || channel == nil || weight == nil {
+		release()
+		return nil, nil, nil, func() {}, fmt.Errorf("gdg: out of memory")
+	}
+	k := 0
+	for b, list := range blends {
+		first[b] = C.int(k)
+		for _, t := range list {
+			channel[k] = C.int(t.Channel)
+			weight[k] = C.double(t.Weight)
+			k++
+		}
+	}
+	first[len(blends)] = C.int(k)
+	return first, channel, weight, release, nil
+}
+
+// BatchSetBlends: the blend outputs of the next batch calls (gdg_batch_set_blends).  Blend b is the sum of its terms over this context's
+// chain output rows -- s = w0*x[c0], then s = s + wk*x[ck] in term order, every product and every add rounded on its own -- and port
+// N + 3 + b of BatchRun and BatchStreamStep, behind the metronome's; all four record kinds hand out N + 3 + B ports.  gain has one output
+// gain per blend (nil or empty: every gain 1).  1 to 32 terms per blend, at most 1024 blends, finite weights and gains; nil or an empty
+// list turns the blends off.  Configuration, like BatchSetTrim: a checkpoint does not carry it -- set it again on the target of a resume --
+// and an error while a streamed job is open.  The shard calls refuse a context with blends in force.
+func (this *Context) BatchSetBlends(blends [][]BlendTerm, gain []float64) error {
+	n := len(blends)
+	if n == 0 {
+		return this.err(C.gdg_batch_set_blends(this.ctx, 0, nil, nil, nil, nil))
+	}
+	if len(gain) != 0 && len(gain) != n {
+		return fmt.Errorf("gdg: %d gains for %d blends", len(gain), n)
+	}
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return err
+	}
+	defer release()
+	if len(gain) == 0 {
+		return this.err(C.gdg_batch_set_blends(this.ctx, C.int(n), &first[0], &channel[0], &weight[0], nil))
+	}
+	g := (*[1 << 28]C.double)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.double(0)))))
+	if g == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(g))
+	for i, v := range gain {
+		g[i] = C.double(v)
+	}
+	return this.err(C.gdg_batch_set_blends(this.ctx, C.int(n), &first[0], &channel[0], &weight[0], &g[0]))
+}
+
+// BatchBlends: the number of blends in force (gdg_batch_blends).
+func (this *Context) BatchBlends() int {
+	return int(C.gdg_batch_blends(this.ctx))
+}
+
+// BlendRows: the blends' sums over any rows of equal length (gdg_blend_rows); a term's Channel names a row.  result[blend][sample].
+func (this *Context) BlendRows(rows [][]float64, blends [][]BlendTerm) ([][]float64, error) {
+	n := len(rows)
+	nb := len(blends)
+	if n == 0 {
+		return nil, fmt.Errorf("gdg: no rows")
+	}
+	samples := len(rows[0])
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n+nb+1), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i := 0; i < n+nb; i++ {
+		if i < n && len(rows[i]) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(rows[i]), samples)
+		}
+		p := C.calloc(C.size_t(samples+1), 8)
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		if i < n {
+			copy((*[1 << 37]float64)(p)[:samples:samples], rows[i])
+		}
+		rp[i] = (*C.double)(p)
+	}
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return nil, err
+	}
+	defer release()
+	if e := this.err(C.gdg_blend_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(nb), &first[0], &channel[0], &weight[0], &rp[n])); e != nil {
+		return nil, e
+	}
+	out := make([][]float64, nb)
+	for b := range out {
+		out[b] = make([]float64, samples)
+		copy(out[b], (*[1 << 37]float64)(unsafe.Pointer(rp[n+b]))[:samples:samples])
+	}
+	return out, nil
+}
+
+// BlendRowsDevice: the same on device memory (gdg_blend_rows_device): row r at dRows + r*rowStride float64, blend b's sums at
+// dOut + b*outStride (8-byte aligned, strides >= samples); returns when the sums are written.
+func (this *Context) BlendRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, blends [][]BlendTerm, dOut unsafe.Pointer, outStride int) error {
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return err
+	}
+	defer release()
+	return this.err(C.gdg_blend_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(len(blends)),
+		&first[0], &channel[0], &weight[0], (*C.double)(dOut), C.size_t(outStride)))
 }

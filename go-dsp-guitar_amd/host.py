@@ -49,6 +49,8 @@ def lib():
             "gdgh_engine_set_batch_dither": (None, [vp, i32, C.c_uint64]),
             "gdgh_engine_set_batch_trim": (cs, [vp, vp, i32, C.c_double, C.c_double, C.c_double]),
             "gdgh_engine_sync_chains": (cs, [vp, C.c_uint32]),
+            "gdgh_engine_set_batch_blends": (cs, [vp, i32, vp, vp, vp, vp]),
+            "gdgh_engine_batch_blends": (i32, [vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
@@ -288,11 +290,31 @@ class Engine:
         n = self.n_channels
         _err(lib().gdgh_engine_set_batch_trim(self._h, g.ctypes.data, n, float(g[n]), float(g[n + 1]), float(g[n + 2])))
 
+    def _set_blends(self, blends, blend_gain=None):
+        """Engine::SetBatchBlends, from the `blends` / `blend_gain` arguments of the batch calls: a list of lists of (job channel, weight) and
+        one output gain per blend (None: all 1); None or an empty list: off.  Returns the number of blends in force: the calls' outputs and
+        records then have N + 3 + B ports.  Refused on an engine of more than one shard."""
+        blends = [] if blends is None else [list(b) for b in blends]
+        if not blends:
+            _err(lib().gdgh_engine_set_batch_blends(self._h, 0, None, None, None, None))
+            return 0
+        first = np.zeros(len(blends) + 1, dtype=np.int32)
+        first[1:] = np.cumsum([len(b) for b in blends], dtype=np.int64)
+        terms = [t for b in blends for t in b]
+        channel = np.array([int(c) for c, _ in terms] + [0], dtype=np.int32)          # a spare entry: a list without terms still has an address
+        weight = np.array([float(w) for _, w in terms] + [0.0], dtype=np.float64)
+        g = None if blend_gain is None else np.ascontiguousarray(blend_gain, dtype=np.float64).reshape(-1)
+        if g is not None and g.size != len(blends):
+            raise HostError("blend_gain: %d gains for %d blends" % (g.size, len(blends)))
+        _err(lib().gdgh_engine_set_batch_blends(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data, None if g is None else g.ctypes.data))
+        return int(lib().gdgh_engine_batch_blends(self._h))
+
     def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
         """Two passes over one job: every output file is written with the gain that brings its true peak to target_dbtp (dBTP), capped at
         max_gain_db.  save_state; pass 1 renders with the true-peak records (and the report) on and every output skipped; the planner
         (trim_from_true_peak) turns the records into gains; load_state; pass 2 renders with the trim.  Returns (outs, gains): the N + 3
-        output data sections and the N + 3 gains used.  The master's gains come from the finish's own records of pass 1, whatever the
+        output data sections and the N + 3 gains used -- with blends= in kw N + 3 + B of each: a blend port's gain is planned from its own
+        true-peak records like any other port's and passed as its output gain (a blend_gain in kw is replaced).  The master's gains come from the finish's own records of pass 1, whatever the
         shard count.  Pass 1's records stay in normalize_true_peak / normalize_report.  The state blob is the channels': a configured
         metronome and the meters run on from pass 1.  kw: batch_run's other arguments (dither, run_meters ...)."""
         import __graft_entry__ as entry
@@ -301,26 +323,31 @@ class Engine:
         _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
         blob = self.save_state()
         self.batch_run(inputs, target_rate, out_format, window=window, report=True, true_peak=True, skip_outputs=True,
-                       **{k: v for k, v in kw.items() if k not in ("report", "true_peak", "trim")})
+                       **{k: v for k, v in kw.items() if k not in ("report", "true_peak", "trim", "blend_gain")})
         self.normalize_true_peak, self.normalize_report = self.last_true_peak, self.last_report
         gains = pkg.trim_from_true_peak(self.normalize_true_peak, 10.0 ** (target_dbtp / 20.0), 10.0 ** (max_gain_db / 20.0))
         self.load_state(blob, rate)
-        outs = self.batch_run(inputs, target_rate, out_format, window=window, trim=gains, **{k: v for k, v in kw.items() if k != "trim"})
+        n3 = self.n_channels + 3                              # the trim's ports; the gains behind them are the blend ports'
+        outs = self.batch_run(inputs, target_rate, out_format, window=window, trim=gains[:n3], blend_gain=gains[n3:] if gains.size > n3 else None,
+                              **{k: v for k, v in kw.items() if k not in ("trim", "blend_gain")})
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
         keep the alignment records in last_align ([N + 3, blocks]); over shards the master rows are zero records.  true_peak: keep the
         true-peak records in last_true_peak ([N + 3, blocks], the same order).  trim: the N + 3 gains in front of the encoders (None:
-        off).  skip_outputs: every output pointer NULL -- the job renders and measures, nothing is written; returns None."""
+        off).  skip_outputs: every output pointer NULL -- the job renders and measures, nothing is written; returns None.  blends: a list
+        of lists of (job channel, weight), blend_gain: one output gain per blend -- B more outputs and B more ports in every last_* record
+        list, behind the metronome's (one-shard engines only; None: off)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_trim(trim)
+        nb = self._set_blends(blends, blend_gain)            # before the alignment list, which may name blend ports
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -347,8 +374,9 @@ class Engine:
             first, count = self.shard_range(g)
             if count > 0:
                 length = max(length, self.raw_context(g).batch_length(inputs[first:first + count], target_rate))
-        outs = None if skip_outputs else [np.zeros(length * wo, dtype=np.uint8) for _ in range(n + 3)]
-        ptrs = (C.c_void_p * (n + 3))(*([None] * (n + 3) if skip_outputs else [(o.ctypes.data if o.size else None) for o in outs]))
+        no = n + 3 + nb
+        outs = None if skip_outputs else [np.zeros(length * wo, dtype=np.uint8) for _ in range(no)]
+        ptrs = (C.c_void_p * no)(*([None] * no if skip_outputs else [(o.ctypes.data if o.size else None) for o in outs]))
         samples = C.c_size_t(0)
         _err(lib().gdgh_engine_batch_run(self._h, arr, n, C.byref(opt), window, ptrs, C.byref(samples)))
         assert samples.value == length
@@ -363,14 +391,15 @@ class Engine:
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
-        yields every slice's N + 3 output pieces.  report: last_report grows by every slice's records and is the whole job's,
+        yields every slice's N + 3 output pieces (and one per blend of blends= / blend_gain=, as batch_run's).  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
+                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
+                                  blends=blends, blend_gain=blend_gain)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -395,13 +424,14 @@ class Engine:
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_trim(trim)
+        nb = self._set_blends(blends, blend_gain)            # the sharded form passes none: off
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -438,8 +468,8 @@ class Engine:
                 _err(f_need(self._h, blocks, first, count))
                 pieces = [None if datas[i] is None or not count[i] else datas[i][first[i] * widths[i]:(first[i] + count[i]) * widths[i]] for i in range(n)]
                 ins = (C.c_void_p * n)(*[(p.ctypes.data if p is not None else None) for p in pieces])
-                outs = [np.zeros(blocks * 8192 * wo, dtype=np.uint8) for _ in range(n + 3)]
-                ptrs = (C.c_void_p * (n + 3))(*[o.ctypes.data for o in outs])
+                outs = [np.zeros(blocks * 8192 * wo, dtype=np.uint8) for _ in range(n + 3 + nb)]
+                ptrs = (C.c_void_p * (n + 3 + nb))(*[o.ctypes.data for o in outs])
                 _err(f_step(self._h, blocks, ins, ptrs))
                 if report:
                     rec = self._fetch_report()

@@ -970,6 +970,41 @@ int Engine::applyTrim(int shard, gdg_ctx *ctx) {
     return gdg_batch_set_trim(ctx, trim_.data() + first, count, wide ? trim_[N] : 1.0, wide ? trim_[N + 1] : 1.0, wide ? trim_[N + 2] : 1.0);
 }
 
+/* Engine::SetBatchBlends: validated whole before the list replaces the one in force (the library checks again when it is applied) */
+Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain) {
+    if (blends.empty()) { blendFirst_.clear(); blendChannel_.clear(); blendWeight_.clear(); blendGain_.clear(); return ""; }
+    if (shards() > 1)
+        return format("SetBatchBlends: the engine has %d shards: every shard's context holds its own channels only, so a blend cannot read a term on another "
+                      "device, and the library's shard calls refuse blends; blends need a one-shard engine", shards());
+    if (blends.size() > GDG_BLEND_MAX_BLENDS) return format("SetBatchBlends: %zu blends; at most %d", blends.size(), GDG_BLEND_MAX_BLENDS);
+    if (!gain.empty() && gain.size() != blends.size()) return format("SetBatchBlends: %zu gains for %zu blends (none: every gain 1)", gain.size(), blends.size());
+    std::vector<int> first(1, 0), channel;
+    std::vector<double> weight;
+    for (size_t b = 0; b < blends.size(); b++) {
+        if (blends[b].empty() || blends[b].size() > GDG_BLEND_MAX_TERMS) return format("SetBatchBlends: blend %zu has %zu terms; 1 to %d", b, blends[b].size(), GDG_BLEND_MAX_TERMS);
+        for (size_t k = 0; k < blends[b].size(); k++) {
+            if (blends[b][k].first < 0 || blends[b][k].first >= nChannels_)
+                return format("SetBatchBlends: blend %zu, term %zu names channel %d; the job has channels 0 to %d", b, k, blends[b][k].first, nChannels_ - 1);
+            if (!std::isfinite(blends[b][k].second)) return format("SetBatchBlends: blend %zu, term %zu: the weight is not finite", b, k);
+            channel.push_back(blends[b][k].first);
+            weight.push_back(blends[b][k].second);
+        }
+        first.push_back((int)channel.size());
+        if (!gain.empty() && !std::isfinite(gain[b])) return format("SetBatchBlends: blend %zu: the gain is not finite", b);
+    }
+    blendFirst_.swap(first);
+    blendChannel_.swap(channel);
+    blendWeight_.swap(weight);
+    blendGain_ = gain.empty() ? std::vector<double>(blends.size(), 1.0) : gain;
+    return "";
+}
+
+/* one shard: job channel numbers are the context's; more shards: no blend is in force, and every context is told so */
+int Engine::applyBlends(gdg_ctx *ctx) {
+    if (blendFirst_.empty()) return gdg_batch_set_blends(ctx, 0, nullptr, nullptr, nullptr, nullptr);
+    return gdg_batch_set_blends(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendGain_.data());
+}
+
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
  * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
  * controller.go:3005-3045). */
@@ -980,7 +1015,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         chains = chains_;
     }
     size_t job = 0;
-    {
+    if (BatchBlends() == 0) {                            /* with blends BatchRun is the plain run, whose master rows are measured like any other */
         Error ae = alignOverShards(1);                   /* the shard forms make the master in the finish, at any shard count */
         if (!ae.empty()) { setError(ae); return ae; }
     }
@@ -995,7 +1030,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1016,6 +1051,14 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (samples) *samples = job;
     reportBegin(job / 8192);
     if (job == 0) { reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
+    /* blends in force (one shard: SetBatchBlends): the library's plain one-call run -- its shard calls refuse blends -- with `outs` of
+     * N + 3 + B entries; the alignment list goes on in its plain form, and the context's records of every kind are the engine's */
+    if (BatchBlends() > 0) {
+        std::lock_guard<std::mutex> lk(shards_[0]->mu);
+        gdg_ctx *ctx = shards_[0]->ctx;
+        if (applyAlign(-1, ctx) != GDG_OK || gdg_batch_run(ctx, inputs, nInputs, &options, outs) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        return recordsOfContext(ctx);
+    }
     /* 2. the shards, concurrently: encoded chain outputs straight into the caller's buffers, partial master mixes as float64 */
     std::vector<std::vector<double>> left((size_t)G), right((size_t)G);
     std::vector<double> metronome(job, 0.0);
@@ -1068,7 +1111,7 @@ void Engine::reportBegin(size_t blocks) {
     reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = false;
     reportBlocks_ = blocks;
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
-    const size_t n = (size_t)(nChannels_ + 3) * blocks;
+    const size_t n = (size_t)ports() * blocks;
     if (report_) lastReport_.assign(n, gdg_block_stats{});
     if (spectrumBands_) lastSpectrum_.assign(n * (size_t)spectrumBands_, 0.0);
     if (truePeak_) lastTruePeak_.assign(n, gdg_block_true_peak{});
@@ -1135,7 +1178,7 @@ Error Engine::alignOverShards(int minShards) {
  * the metronome, in the shard's own port numbers (alignOverShards has kept every reference on its port's shard).  A gdg_* status */
 int Engine::applyAlign(int shard, gdg_ctx *ctx) {
     if (alignRef_.empty()) return gdg_batch_align_enable(ctx, nullptr, 0, 0);
-    if (shard < 0) return gdg_batch_align_enable(ctx, alignRef_.data(), nChannels_ + 3, alignLag_);
+    if (shard < 0) return gdg_batch_align_enable(ctx, alignRef_.data(), (int)alignRef_.size(), alignLag_);      /* N + 3, or N + 3 + B with blends */
     int first = 0, count = 0;
     shardRange(shard, &first, &count);
     auto local = [&](int port) { return port < 0 ? -1 : (port < nChannels_ ? port - first : count); };
@@ -1157,7 +1200,7 @@ Error Engine::truePeakOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_true_pea
 Error Engine::LastBatchTruePeak(std::vector<gdg_block_true_peak> &records, int *ports, size_t *blocks) const {
     if (!truePeakValid_) return "LastBatchTruePeak: the last batch call kept no true-peak records (SetBatchTruePeak comes before the call)";
     records = lastTruePeak_;
-    if (ports) *ports = nChannels_ + 3;
+    if (ports) *ports = this->ports();
     if (blocks) *blocks = reportBlocks_;
     return "";
 }
@@ -1203,10 +1246,13 @@ Error Engine::SetBatchSpectrum(const std::vector<double> &edges) {
 
 Error Engine::SetBatchAlign(const std::vector<int> &ref, int maxLag) {
     if (ref.empty()) { alignRef_.clear(); alignLag_ = 0; return ""; }
-    if ((int)ref.size() != nChannels_ + 3) return format("SetBatchAlign: a list of %zu ports; the job has N + 3 = %d", ref.size(), nChannels_ + 3);
+    if ((int)ref.size() != nChannels_ + 3 && (BatchBlends() == 0 || (int)ref.size() != ports())) {
+        if (BatchBlends()) return format("SetBatchAlign: a list of %zu ports; the job has N + 3 = %d, or %d with its %d blends", ref.size(), nChannels_ + 3, ports(), BatchBlends());
+        return format("SetBatchAlign: a list of %zu ports; the job has N + 3 = %d", ref.size(), nChannels_ + 3);
+    }
     if (maxLag < 1 || maxLag > 2048) return format("SetBatchAlign: a lag range of %d; 1 to 2048", maxLag);
     for (size_t p = 0; p < ref.size(); p++)
-        if (ref[p] < -1 || ref[p] >= nChannels_ + 3) return format("SetBatchAlign: port %zu names reference %d; -1 or a port below %d", p, ref[p], nChannels_ + 3);
+        if (ref[p] < -1 || ref[p] >= (int)ref.size()) return format("SetBatchAlign: port %zu names reference %d; -1 or a port below %zu", p, ref[p], ref.size());
     const std::vector<int> keep = alignRef_;
     alignRef_ = ref;
     Error e = alignOverShards(2);                        /* more than one shard: the list must split */
@@ -1218,7 +1264,7 @@ Error Engine::SetBatchAlign(const std::vector<int> &ref, int maxLag) {
 Error Engine::LastBatchAlign(std::vector<gdg_block_align> &records, int *ports, size_t *blocks) const {
     if (!alignValid_) return "LastBatchAlign: the last batch call kept no alignment records (SetBatchAlign comes before the call)";
     records = lastAlign_;
-    if (ports) *ports = nChannels_ + 3;
+    if (ports) *ports = this->ports();
     if (blocks) *blocks = reportBlocks_;
     return "";
 }
@@ -1226,7 +1272,7 @@ Error Engine::LastBatchAlign(std::vector<gdg_block_align> &records, int *ports, 
 Error Engine::LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *blocks, int *nBands) const {
     if (!spectrumValid_) return "LastBatchSpectrum: the last batch call kept no spectrum (SetBatchSpectrum comes before the call)";
     bands = lastSpectrum_;
-    if (ports) *ports = nChannels_ + 3;
+    if (ports) *ports = this->ports();
     if (blocks) *blocks = reportBlocks_;
     if (nBands) *nBands = spectrumBands_;
     return "";
@@ -1235,7 +1281,7 @@ Error Engine::LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *
 Error Engine::LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const {
     if (!reportValid_) return "LastBatchReport: the last batch call kept no report (SetBatchReport comes before the call)";
     records = lastReport_;
-    if (ports) *ports = nChannels_ + 3;
+    if (ports) *ports = this->ports();
     if (blocks) *blocks = reportBlocks_;
     return "";
 }
@@ -1264,7 +1310,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1289,12 +1335,16 @@ Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *o
     if (!ctx) return "BatchStreamStep: no streamed batch run is open";
     reportBegin(blocks > 0 ? (size_t)blocks : 0);
     if (gdg_batch_stream_step(ctx, blocks, ins, outs) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
-    /* one shard, the plain run: the context's records of every kind are the engine's */
+    return recordsOfContext(ctx);
+}
+
+/* one shard, the plain run: the context's records of every kind -- N + 3 ports and the blends' -- are the engine's */
+Error Engine::recordsOfContext(gdg_ctx *ctx) {
     Error re;
-    if (report_ && (re = kindOf(ctx, nChannels_ + 3, reportBlocks_, 1, "a report", lastReport_)).empty()) reportValid_ = true;
-    if (re.empty() && truePeak_ && (re = truePeakOf(ctx, nChannels_ + 3, lastTruePeak_)).empty()) truePeakValid_ = true;
-    if (re.empty() && !alignRef_.empty() && (re = alignOf(ctx, nChannels_ + 3, lastAlign_)).empty()) alignValid_ = true;
-    if (re.empty() && !spectrumEdges_.empty() && (re = spectrumOf(ctx, nChannels_ + 3, lastSpectrum_)).empty()) spectrumValid_ = true;
+    if (report_ && (re = kindOf(ctx, ports(), reportBlocks_, 1, "a report", lastReport_)).empty()) reportValid_ = true;
+    if (re.empty() && truePeak_ && (re = truePeakOf(ctx, ports(), lastTruePeak_)).empty()) truePeakValid_ = true;
+    if (re.empty() && !alignRef_.empty() && (re = alignOf(ctx, ports(), lastAlign_)).empty()) alignValid_ = true;
+    if (re.empty() && !spectrumEdges_.empty() && (re = spectrumOf(ctx, ports(), lastSpectrum_)).empty()) spectrumValid_ = true;
     if (!re.empty()) { setError(re); return LastError(); }
     return "";
 }
@@ -1474,7 +1524,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1789,6 +1839,19 @@ const char *gdgh_engine_sync_chains(void *e, uint32_t sample_rate) { return ret(
 const char *gdgh_engine_set_batch_trim(void *e, const double *chain_gain, int n, double master_left, double master_right, double metronome) {
     return ret(((Engine *)e)->SetBatchTrim(chain_gain && n > 0 ? std::vector<double>(chain_gain, chain_gain + n) : std::vector<double>(), master_left, master_right, metronome));
 }
+/* the blends in gdg_batch_set_blends' CSR form, job channel numbers; n_blends == 0: off; gain == NULL: every gain 1.  A `first` that does
+ * not start at 0 or descends is refused here: the lists below are cut by it */
+const char *gdgh_engine_set_batch_blends(void *e, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
+    std::vector<std::vector<std::pair<int, double>>> blends;
+    if (n_blends < 0 || (n_blends > 0 && (!first || !channel || !weight || first[0] != 0))) return ret("SetBatchBlends: n_blends >= 0, and first (from 0 on), channel and weight");
+    for (int b = 0; b < n_blends; b++) {
+        if (first[b + 1] < first[b]) return ret(format("SetBatchBlends: blend %d: first descends from %d to %d", b, first[b], first[b + 1]));
+        blends.emplace_back();
+        for (int k = first[b]; k < first[b + 1]; k++) blends.back().emplace_back(channel[k], weight[k]);
+    }
+    return ret(((Engine *)e)->SetBatchBlends(blends, gain && n_blends > 0 ? std::vector<double>(gain, gain + n_blends) : std::vector<double>()));
+}
+int gdgh_engine_batch_blends(void *e) { return ((Engine *)e)->BatchBlends(); }
 void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchReport(on != 0); }
 /* n == 0: off */
 const char *gdgh_engine_set_batch_spectrum(void *e, const double *edges, int n) {

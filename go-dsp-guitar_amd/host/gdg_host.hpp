@@ -285,6 +285,15 @@ public:
      * a later LoadState finds, also on an engine that has not processed yet (the two-pass render saves before its first pass) */
     Error SyncChains(uint32_t sampleRate);
     Error SetBatchTrim(const std::vector<double> &chainGain, double masterLeft = 1.0, double masterRight = 1.0, double metronome = 1.0);
+    /* No reference counterpart.  The blend outputs (include/gdg.h, gdg_batch_set_blends): blend b is the weighted sum of its terms -- (job
+     * channel, weight) pairs, 1 to 32 of them -- over the chain outputs, in term order, and port N + 3 + b of BatchRun and the plain streamed
+     * job; gain: one output gain per blend, or none (every gain 1).  While blends are in force every call's `outs` and every Last* record
+     * list have N + 3 + B ports, and SetBatchAlign takes N + 3 or N + 3 + B entries.  Refused with more than one shard: a shard's context
+     * holds its own channels only, so a term on another shard's device cannot be summed there, and the library's shard calls refuse blends.
+     * BatchRun of a one-shard engine with blends is the library's plain gdg_batch_run.  A refused list leaves the one in force; an empty
+     * list: off. */
+    Error SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain = {});
+    int BatchBlends() const { return blendFirst_.empty() ? 0 : (int)blendFirst_.size() - 1; }
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -350,6 +359,11 @@ private:
     int applyDither(int shard, gdg_ctx *ctx);              /* mode, seed and the shard's port_base onto its context: a gdg_* status */
     std::vector<double> trim_;                             /* SetBatchTrim: N chain gains, master left, master right, metronome; empty: off */
     int applyTrim(int shard, gdg_ctx *ctx);                /* the shard's slice of it onto its context: a gdg_* status */
+    std::vector<int> blendFirst_, blendChannel_;           /* SetBatchBlends, in gdg_batch_set_blends' CSR form; blendFirst_ empty: off */
+    std::vector<double> blendWeight_, blendGain_;
+    int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
+    int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
+    Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */
     void reportBegin(size_t blocks);
     Error reportOfShard(int shard, gdg_ctx *ctx);
     Error reportOfMaster(gdg_ctx *ctx);

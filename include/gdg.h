@@ -1056,6 +1056,67 @@ int gdg_wave_encode_trim(gdg_ctx *ctx, int format, const double *samples, size_t
 int gdg_wave_encode_trim_device(gdg_ctx *ctx, int format, const double *d_samples, size_t n, double gain, int mode, uint64_t seed, uint32_t port,
                                 uint64_t first_index, void *d_bytes);
 int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_t blocks, double target, double max_gain, double *gain);
+/*
+ * BLEND: no reference counterpart.  A re-amping job renders one take through many rigs (gdg_batch_set_sources), and what its user does with
+ * the renders is blend a few of them: two amps at 60/40, two microphone positions of one cabinet, a clean rig under a driven one.  A blend
+ * output is a weighted sum of chain outputs, made from the float64 rows as they lie on the device -- before any of them is truncated to 16
+ * or 24 bits -- and written as one more port behind the metronome's.  Stateless per sample: no place in the checkpoint, no rule for
+ * windows or slices, the same bits however the job is cut, no change to the container version.
+ *   gdg_batch_set_blends(ctx, n_blends, first, channel, weight, gain)
+ *                                                      the blends in CSR form: blend b has the terms k = first[b] .. first[b + 1] - 1,
+ *                                                      term k is channel[k] of THIS context with weight[k]; first has n_blends + 1
+ *                                                      entries, starts at 0 and never descends.  gain: one output gain per blend, or
+ *                                                      NULL: every gain 1.0.  n_blends == 0 turns the blends off (the lists may be NULL).
+ *   gdg_batch_blends(ctx)                              the number of blends in force
+ * LIMITS: 1 <= terms per blend <= GDG_BLEND_MAX_TERMS (32); 0 <= n_blends <= GDG_BLEND_MAX_BLENDS (1024); every channel lies in [0, N), N =
+ * gdg_ctx_channels.  Weights and gains are finite; negative and zero values are allowed; a channel may appear more than once in a blend.
+ * GDG_ERR_INVALID, with gdg_last_error naming the blend and the term, and the setting in force unchanged: a blend without a term or with
+ * more than 32, a channel out of range, a weight or a gain that is not finite, a `first` that does not start at 0 or descends, a count
+ * outside the limits, a call while a streamed job is open.  The whole argument is validated before it replaces the setting in force.
+ * OFF: n_blends == 0, or never called.  Off, no launch, allocation, upload or byte differs from a context that never heard of the call, and
+ * option stat_batch_device_kib is unchanged.
+ * Configuration, like gdg_batch_set_trim and gdg_batch_set_sources: it holds from the next batch call on, survives batch calls and is part
+ * of no blob -- set it again on the target of a resume.
+ * DEFINITION, for every sample index i of the job, with x[c] the float64 chain output row of channel c -- the row the encoder reads: before
+ * the trim, before the spatializer:
+ *   s = w_0 * x[c_0][i]                                ONE rounded IEEE-754 double multiply
+ *   s = s + (w_k * x[c_k][i])      k = 1 .. K - 1      one rounded multiply, one rounded add, in term order
+ * never contracted into a fused multiply-add and never reassociated.  s is the blend port's float64 row.  The port is encoded from
+ *   y = s * g_b                                        exactly as the trim encodes x * g (TRIM, above): the plain or the dithered encoder, in
+ *                                                      any of the six formats; IEEE64 writes y's 8 bytes
+ * and with g_b == 1.0 from s itself.  NaN and inf in a row follow IEEE arithmetic; 0 * inf is NaN.  WHERE a sample of s is a NaN is defined;
+ * the sign and the payload of a NaN the arithmetic produces are not (IEEE 754 leaves them open: 0 * inf is the negative quiet NaN on x86
+ * and the positive one on gfx950), so the 8 bytes IEEE64 writes for such a sample are those of some NaN.
+ * Known answer: weights {0.1, 0.2, 0.3} on three rows of 1.0 give 0.6000000000000001; the same terms in reverse order give 0.6.
+ * PORTS: with B blends in force gdg_batch_run, gdg_batch_stream_step and the job of gdg_batch_stream_resume take out_bytes of N + 3 + B
+ * entries: blend b is port N + 3 + b, behind the metronome's.  A NULL entry skips the file as for any port.
+ *   records     gdg_batch_report, gdg_batch_spectrum, gdg_batch_align and gdg_batch_true_peak hand out N + 3 + B ports; a blend port's
+ *               records are taken from s, before the gain, as the others are taken before the trim
+ *   dither      blend b is port port_base + N + 3 + b of the dither, with the sample index in the job as ever; that range stays below the
+ *               job-wide ports (refused when the job is described)
+ *   alignment   gdg_batch_align_enable's n_ports is N + 3 or N + 3 + B for the B in force when a job is described.  With N + 3 every blend
+ *               port references itself; with N + 3 + B a blend may name any port as its reference, one of its own terms included.  Any
+ *               other count is refused when the job is described, with both numbers in the message.
+ * WHAT NEVER CHANGES: the chain, master and metronome files of a job with blends are byte for byte those of the job without; the master
+ * mix, the meters (still 2 N + 3 ports), the tuner and the channel state never see a blend.  The trim's gains are those of ports 0 .. N + 2;
+ * a blend port has its own g_b.
+ * SHARDS: gdg_batch_run_shard, gdg_batch_stream_open_shard and gdg_batch_stream_resume_shard return GDG_ERR_UNSUPPORTED while blends are in force
+ * on their context; gdg_batch_stream_step_shard then never finds a job of theirs open (and the setting cannot change while one is).  A shard's row layout is a different problem, and a blend whose terms live
+ * on two devices is another one.
+ * The sum on its own, over any rows (`channel` then names a row: 0 .. n_rows - 1; no gain), both blocking -- the table is host memory:
+ *   gdg_blend_rows(ctx, rows, n_rows, samples, n_blends, first, channel, weight, out)        host rows; out[b]: `samples` doubles
+ *   gdg_blend_rows_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, d_out, out_stride)
+ *                                                      device rows, 8-byte aligned: row r at d_rows + r * row_stride, blend b's sums at
+ *                                                      d_out + b * out_stride (strides in samples, >= samples); d_out overlaps no row
+ */
+#define GDG_BLEND_MAX_TERMS 32
+#define GDG_BLEND_MAX_BLENDS 1024
+int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const double *gain);
+int gdg_batch_blends(const gdg_ctx *ctx);
+int gdg_blend_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                   const double *weight, double *const *out);
+int gdg_blend_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
+                          const int *channel, const double *weight, double *d_out, size_t out_stride);
 
 #ifdef __cplusplus
 
