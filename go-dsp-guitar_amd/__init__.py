@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "gdg_true_peak_taps", "gdg_block_true_peak_rows", "gdg_block_true_peak_rows_device", "gdg_batch_true_peak_enable", "gdg_batch_true_peak",
     "gdg_batch_set_trim", "gdg_wave_encode_trim", "gdg_wave_encode_trim_device", "gdg_trim_from_true_peak",
     "gdg_batch_set_blends", "gdg_batch_blends", "gdg_blend_rows", "gdg_blend_rows_device",
+    "gdg_batch_set_blends_delayed", "gdg_batch_blend_max_delay", "gdg_blend_rows_delayed", "gdg_blend_rows_delayed_device", "gdg_blend_delays_from_align",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -91,6 +92,33 @@ def trim_from_true_peak(records, target, max_gain):
     if rc != GDG_OK:
         raise GdgError(rc, lib().gdg_last_error(None).decode())
     return gain
+
+
+BLEND_MAX_DELAY = 4096       # GDG_BLEND_MAX_DELAY (include/gdg.h): the largest delay of a blend's term, and the samples of history a row keeps
+
+
+def blend_delays_from_align(records, ref, blends, min_coeff=0.5):
+    """gdg_blend_delays_from_align: records [ports, blocks] (BLOCK_ALIGN_DTYPE, as batch_align hands them out) measured with the reference
+    list `ref`; blends = lists of terms whose first entry names a port (what follows it in a term is ignored).  Returns (delays, signs):
+    per blend one list of ints per term -- delay_k = the blend's largest lag - the term's lag, sign_k = +1 or -1, to be multiplied into the
+    weight.  Host arithmetic: no context, no device.  GdgError when a blend's terms do not share one reference port."""
+    rec = np.ascontiguousarray(records, dtype=BLOCK_ALIGN_DTYPE)
+    if rec.ndim != 2:
+        raise ValueError("records: [ports, blocks]")
+    refs = np.ascontiguousarray(np.array(ref, dtype=np.int64).reshape(-1), dtype=np.int32)
+    if refs.size != rec.shape[0]:
+        raise ValueError("%d references for %d ports" % (refs.size, rec.shape[0]))
+    blends = [list(b) for b in blends]
+    first = np.zeros(len(blends) + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(b) for b in blends], dtype=np.int64)
+    channel = np.array([int(t[0]) for b in blends for t in b] + [0], dtype=np.int32)
+    delay, sign = np.zeros(channel.size, dtype=np.int32), np.zeros(channel.size, dtype=np.int32)
+    rc = lib().gdg_blend_delays_from_align(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], refs.ctypes.data if refs.size else None,
+                                           float(min_coeff), len(blends), first.ctypes.data, channel.ctypes.data, delay.ctypes.data, sign.ctypes.data)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    cut = lambda v: [[int(x) for x in v[first[b]:first[b + 1]]] for b in range(len(blends))]
+    return cut(delay), cut(sign)
 
 
 ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
@@ -339,6 +367,11 @@ def lib():
             "gdg_batch_blends": (i32, [vp]),
             "gdg_blend_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp, vp, vp]),
             "gdg_blend_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, vp, vp, C.c_size_t]),
+            "gdg_batch_set_blends_delayed": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+            "gdg_batch_blend_max_delay": (i32, [vp]),
+            "gdg_blend_rows_delayed": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp, vp, vp, vp, vp]),
+            "gdg_blend_rows_delayed_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]),
+            "gdg_blend_delays_from_align": (i32, [vp, i32, C.c_size_t, vp, C.c_double, i32, vp, vp, vp, vp]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1170,12 +1203,21 @@ class Context:
         first = np.zeros(len(blends) + 1, dtype=np.int32)
         first[1:] = np.cumsum([len(b) for b in blends], dtype=np.int64)
         terms = [t for b in blends for t in b]
-        return first, np.array([int(c) for c, _ in terms] + [0], dtype=np.int32), np.array([float(w) for _, w in terms] + [0.0], dtype=np.float64)
+        return first, np.array([int(t[0]) for t in terms] + [0], dtype=np.int32), np.array([float(t[1]) for t in terms] + [0.0], dtype=np.float64)
+
+    @staticmethod
+    def _blend_delays(blends):
+        """the delays of terms given as (channel, weight) or (channel, weight, delay): an int32 array with a spare entry, or None where no term has one"""
+        terms = [t for b in blends for t in b]
+        if not any(len(t) > 2 for t in terms):
+            return None
+        return np.array([int(t[2]) if len(t) > 2 else 0 for t in terms] + [0], dtype=np.int32)
 
     def batch_set_blends(self, blends, gain=None):
-        """The blend outputs of the next batch calls (gdg_batch_set_blends): blends = a list of lists of (channel, weight) -- blend b is the
-        sum of its terms over this context's chain output rows, in term order, and port N + 3 + b of every batch call; gain: one output gain
-        per blend (None: all 1).  An empty list (or None): off.  Configuration: not in a checkpoint."""
+        """The blend outputs of the next batch calls (gdg_batch_set_blends, gdg_batch_set_blends_delayed): blends = a list of lists of
+        (channel, weight) or (channel, weight, delay) -- blend b is the sum of its terms over this context's chain output rows, in term
+        order, a term with a delay reading its row that many samples back (0 to BLEND_MAX_DELAY), and port N + 3 + b of every batch call;
+        gain: one output gain per blend (None: all 1).  An empty list (or None): off.  Configuration: not in a checkpoint."""
         blends = [] if blends is None else [list(b) for b in blends]
         if not blends:
             self._check(lib().gdg_batch_set_blends(self._h, 0, None, None, None, None))
@@ -1184,12 +1226,50 @@ class Context:
         g = None if gain is None else np.ascontiguousarray(gain, dtype=np.float64).reshape(-1)
         if g is not None and g.size != len(blends):
             raise ValueError("%d gains for %d blends" % (g.size, len(blends)))
+        delay = self._blend_delays(blends)
+        if delay is not None:
+            self._check(lib().gdg_batch_set_blends_delayed(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data,
+                                                           delay.ctypes.data, None if g is None else g.ctypes.data))
+            return
         self._check(lib().gdg_batch_set_blends(self._h, len(blends), first.ctypes.data, channel.ctypes.data,
                                                weight.ctypes.data, None if g is None else g.ctypes.data))
 
     def batch_blends(self):
         """The number of blends in force (gdg_batch_blends)."""
         return int(lib().gdg_batch_blends(self._h))
+
+    def batch_blend_max_delay(self):
+        """The largest delay of the blends in force (gdg_batch_blend_max_delay); 0: the blends are stateless."""
+        return int(lib().gdg_batch_blend_max_delay(self._h))
+
+    def blend_rows_delayed(self, rows, blends, history=None):
+        """gdg_blend_rows_delayed: rows [n_rows, samples] float64, blends of (row, weight, delay) terms, history None (zeros in front of sample
+        0) or [n_rows, BLEND_MAX_DELAY] float64 whose last column is sample -1 -> [blends, samples]."""
+        x = np.ascontiguousarray(rows, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("rows: [n_rows, samples]")
+        blends = [list(b) for b in blends]
+        first, channel, weight = self._blend_csr(blends)
+        delay = self._blend_delays(blends)
+        h = None if history is None else np.ascontiguousarray(history, dtype=np.float64)
+        if h is not None and h.shape != (x.shape[0], BLEND_MAX_DELAY):
+            raise ValueError("history: [n_rows, %d]" % BLEND_MAX_DELAY)
+        out = np.zeros((len(blends), x.shape[1]), dtype=np.float64)
+        rp = (C.c_void_p * max(x.shape[0], 1))(*[x[r].ctypes.data for r in range(x.shape[0])])
+        hp = None if h is None else (C.c_void_p * max(x.shape[0], 1))(*[h[r].ctypes.data for r in range(x.shape[0])])
+        op = (C.c_void_p * max(len(blends), 1))(*[out[b].ctypes.data for b in range(len(blends))])
+        self._check(lib().gdg_blend_rows_delayed(self._h, rp, x.shape[0], x.shape[1], len(blends), first.ctypes.data, channel.ctypes.data,
+                                                 weight.ctypes.data, None if delay is None else delay.ctypes.data, hp, op))
+        return out
+
+    def blend_rows_delayed_device(self, d_rows, row_stride, n_rows, samples, blends, d_out, out_stride, d_history=None, hist_stride=BLEND_MAX_DELAY):
+        """gdg_blend_rows_delayed_device on plain device pointers (ints); d_history: None or row r's BLEND_MAX_DELAY samples in front of
+        sample 0 at d_history + r * hist_stride; returns when the sums are written."""
+        blends = [list(b) for b in blends]
+        first, channel, weight = self._blend_csr(blends)
+        delay = self._blend_delays(blends)
+        self._check(lib().gdg_blend_rows_delayed_device(self._h, d_rows, row_stride, n_rows, samples, len(blends), first.ctypes.data, channel.ctypes.data,
+                                                        weight.ctypes.data, None if delay is None else delay.ctypes.data, d_history, hist_stride, d_out, out_stride))
 
     def blend_rows(self, rows, blends):
         """gdg_blend_rows: rows [n_rows, samples] float64, blends as batch_set_blends takes them with `channel` naming a row -> [blends, samples]."""

@@ -64,7 +64,7 @@ int gdg_batch_release(gdg_ctx *ctx) {
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is open on this context: its buffers are in use");
     enter(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 6; i++) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    for (int i = 0; i < BATCH_DEV_SLOTS; i++) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
     return GDG_OK;
 }
 
@@ -119,6 +119,10 @@ struct BatchLoop {
     int n_blends;
     const int *d_blend_first, *d_blend_channel;
     const double *d_blend_weight, *d_blend_gain;
+    /* a delay in force (gdg_batch_set_blends_delayed): one per term, and the context's history of the N chain rows -- what the step before
+     * left of them, zeros at the job's start; both null while every delay is 0 */
+    const int *d_blend_delay;
+    double *d_blend_history;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -259,9 +263,16 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             const size_t row_bytes = (size_t)wb * out_width;
             const ReportSections &sec = steps[i].sec;
             /* the blend rows, behind the metronome's: sums of the chain rows, which are final; every reader below takes them as rows like the others */
-            if (p.n_blends)
+            if (p.n_blends && !p.d_blend_delay)
                 HIP_TRY(ctx, gdg_launch_blend_rows(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight,
                                                    d_win + (size_t)NO * ws, ws, ctx->stream));
+            if (p.n_blends && p.d_blend_delay) {
+                /* delayed terms reach into the step before: its tail is the history (a step has at least 8192 samples, a delay at most 4096).
+                 * This step's tail replaces it behind the sum and before the next step writes the window. */
+                HIP_TRY(ctx, gdg_launch_blend_rows_delayed(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight, p.d_blend_delay,
+                                                           p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, d_win + (size_t)NO * ws, ws, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_blend_history_save(d_win, ws, (size_t)wb, (unsigned)N, p.d_blend_history, ctx->stream));
+            }
             if (p.live.on(REPORT_STATS)) {                                   /* the rows as the encoder is about to read them */
                 gdg_block_stats *rec = reinterpret_cast<gdg_block_stats *>(enc + sec.at[REPORT_STATS]);
                 HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, (unsigned)B, rec, ctx->stream));
@@ -477,11 +488,11 @@ int gdg_batch_set_trim(gdg_ctx *ctx, const double *chain_gain, int n, double mas
 }
 
 /* the blend outputs: validated whole before the list replaces the one in force (blend.h); read when a job is described and by every slice */
-int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
+int gdg_batch_set_blends_delayed(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const double *gain) {
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set blends: a streamed batch run is open on this context; its blends hold until gdg_batch_stream_close");
     int b = -1, k = -1;
-    switch (gdg_blend_check(n_blends, first, channel, weight, gain, ctx->nch, &b, &k)) {
+    switch (gdg_blend_check(n_blends, first, channel, weight, delay, gain, ctx->nch, &b, &k)) {
     case BLEND_OK: break;
     case BLEND_COUNT: return fail(ctx, GDG_ERR_INVALID, "set blends: %d blends; 0 (off) to %d", n_blends, GDG_BLEND_MAX_BLENDS);
     case BLEND_NULL: return fail(ctx, GDG_ERR_INVALID, "set blends: %d blends need first, channel and weight", n_blends);
@@ -491,14 +502,17 @@ int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int
     case BLEND_CHANNEL:
         return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d names channel %d, the context has channels 0 to %d", b, k, channel[first[b] + k], ctx->nch - 1);
     case BLEND_WEIGHT: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d: weight = %g is not finite", b, k, weight[first[b] + k]);
+    case BLEND_DELAY: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d: delay = %d; 0 to %d samples", b, k, delay[first[b] + k], GDG_BLEND_MAX_DELAY);
     default: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d: gain = %g is not finite", b, gain[b]);
     }
     enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
-    const bool resize = n_blends != ctx->blend.count();
+    const bool resize = n_blends != ctx->blend.count(), had_delay = ctx->blend.max_delay() > 0;
     /* another row count: whatever still reads the window and the encoded halves has to be done before they go -- and a wait that fails
      * refuses the call with the setting in force untouched */
-    if (resize) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    gdg_blend_replace(ctx->blend, n_blends, first, channel, weight, gain, ctx->nch, &b, &k);      /* checked above: it cannot refuse */
+    if (resize || had_delay) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    gdg_blend_replace(ctx->blend, n_blends, first, channel, weight, delay, gain, ctx->nch, &b, &k);      /* checked above: it cannot refuse */
+    /* no delay left in force: the history goes (the next job with one begins from zeros anyway) */
+    if (had_delay && ctx->blend.max_delay() == 0) { hipFree(ctx->batch_dev[BATCH_BLEND_HISTORY]); ctx->batch_dev[BATCH_BLEND_HISTORY] = nullptr; ctx->batch_dev_cap[BATCH_BLEND_HISTORY] = 0; }
     if (resize) {
         /* the window and the encoded halves are made anew by the next batch call, at the size of a context that was always configured like
          * this one; off, the table goes as well */
@@ -508,7 +522,12 @@ int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int
     return GDG_OK;
 }
 
+int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
+    return gdg_batch_set_blends_delayed(ctx, n_blends, first, channel, weight, nullptr, gain);
+}
+
 int gdg_batch_blends(const gdg_ctx *ctx) { return ctx ? ctx->blend.count() : 0; }
+int gdg_batch_blend_max_delay(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_delay() : 0; }
 
 /* the master cursor belongs to gdg_batch_finish_master_slice, which is no part of an open job: it may be set while one is open */
 int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
@@ -868,7 +887,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
             if (!ctx->d_trim && hipMalloc((void **)&ctx->d_trim, (size_t)NO * sizeof(double)) != hipSuccess)
@@ -893,6 +912,16 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             loop.d_blend_channel = loop.d_blend_first + n_blends + 1;
             loop.d_blend_weight = reinterpret_cast<const double *>(ctx->d_blend + ints);
             loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.d_blend_weight + bs.terms();
+            if (bs.max_delay() > 0) {
+                /* the history of the N chain rows: the job's first slice begins from zeros, every later one from what the slice before left */
+                const size_t hist_bytes = (size_t)N * GDG_BLEND_MAX_DELAY * sizeof(double);
+                const bool fresh = ctx->batch_dev_cap[BATCH_BLEND_HISTORY] < hist_bytes;
+                int r;
+                if ((r = batch_buffer(ctx, BATCH_BLEND_HISTORY, hist_bytes, (void **)&loop.d_blend_history)) != GDG_OK) return r;
+                if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the blend history of the open job is gone (gdg_batch_release between two slices?)");
+                if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_blend_history, 0, hist_bytes, ctx->stream));
+                loop.d_blend_delay = loop.d_blend_channel + bs.terms();
+            }
         }
         return batch_block_loop(ctx, loop, stage);
     };

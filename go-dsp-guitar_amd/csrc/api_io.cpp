@@ -739,10 +739,10 @@ int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int
 }
 
 /* ---- the blend on its own (include/gdg.h; the kernel: blend_kernels.h in io.hip; the list's validation: blend.h; the batch calls: api_batch.cpp) ---- */
-static int blend_rows_check(gdg_ctx *ctx, int n_rows, int n_blends, const int *first, const int *channel, const double *weight) {
+static int blend_rows_check(gdg_ctx *ctx, int n_rows, int n_blends, const int *first, const int *channel, const double *weight, const int *delay = nullptr) {
     if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "blend rows: %d rows (at least 1)", n_rows);
     int b = -1, k = -1;
-    switch (gdg_blend_check(n_blends, first, channel, weight, nullptr, n_rows, &b, &k)) {
+    switch (gdg_blend_check(n_blends, first, channel, weight, delay, nullptr, n_rows, &b, &k)) {
     case BLEND_OK: return GDG_OK;
     case BLEND_COUNT: return fail(ctx, GDG_ERR_INVALID, "blend rows: %d blends; 0 to %d", n_blends, GDG_BLEND_MAX_BLENDS);
     case BLEND_NULL: return fail(ctx, GDG_ERR_INVALID, "blend rows: %d blends need first, channel and weight", n_blends);
@@ -750,6 +750,7 @@ static int blend_rows_check(gdg_ctx *ctx, int n_rows, int n_blends, const int *f
     case BLEND_EMPTY: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d has no term; 1 to %d", b, GDG_BLEND_MAX_TERMS);
     case BLEND_TERMS: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d has %d terms; 1 to %d", b, first[b + 1] - first[b], GDG_BLEND_MAX_TERMS);
     case BLEND_CHANNEL: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d names row %d of %d", b, k, channel[first[b] + k], n_rows);
+    case BLEND_DELAY: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d: delay = %d; 0 to %d", b, k, delay[first[b] + k], GDG_BLEND_MAX_DELAY);
     default: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d: weight = %g is not finite", b, k, weight[first[b] + k]);
     }
 }
@@ -801,6 +802,98 @@ int gdg_blend_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t s
     if (rc != GDG_OK) return rc;
     for (int b = 0; b < n_blends; b++) memcpy(out[b], sums.data() + (size_t)b * samples, samples * sizeof(double));
     return GDG_OK;
+}
+
+/* ---- the delayed blend on its own: the table goes up with its delays, the history is read where it lies ---- */
+int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
+                                  const int *channel, const double *weight, const int *delay, const double *d_history, size_t hist_stride, double *d_out,
+                                  size_t out_stride) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
+    if (rc != GDG_OK) return rc;
+    if (n_blends == 0 || samples == 0) return GDG_OK;
+    if (!d_rows || !d_out) return GDG_ERR_INVALID;
+    if (row_stride < samples || out_stride < samples) return fail(ctx, GDG_ERR_INVALID, "blend rows: strides of %zu and %zu samples for rows of %zu", row_stride, out_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7)) return fail(ctx, GDG_ERR_INVALID, "blend rows: rows and sums are 8-byte aligned");
+    if (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY))
+        return fail(ctx, GDG_ERR_INVALID, "blend rows: the history is 8-byte aligned, a row's run has %d samples; its stride is %zu", GDG_BLEND_MAX_DELAY, hist_stride);
+    enter_keep_fir_sums(ctx);
+    /* first | channel | delay | pad | weight */
+    const size_t terms = (size_t)first[n_blends], ints = (((size_t)n_blends + 1 + 2 * terms) * sizeof(int) + 7) & ~(size_t)7, bytes = ints + terms * sizeof(double);
+    std::vector<unsigned char> host(bytes, 0);
+    memcpy(host.data(), first, ((size_t)n_blends + 1) * sizeof(int));
+    memcpy(host.data() + ((size_t)n_blends + 1) * sizeof(int), channel, terms * sizeof(int));
+    if (delay) memcpy(host.data() + ((size_t)n_blends + 1 + terms) * sizeof(int), delay, terms * sizeof(int));
+    memcpy(host.data() + ints, weight, terms * sizeof(double));
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, bytes));
+    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        const int *d_first = static_cast<const int *>(d);
+        e = gdg_launch_blend_rows_delayed(d_rows, row_stride, samples, (unsigned)n_blends, d_first, d_first + n_blends + 1, reinterpret_cast<const double *>(static_cast<unsigned char *>(d) + ints),
+                                          d_first + n_blends + 1 + terms, d_history, hist_stride, d_out, out_stride, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(w));
+    return GDG_OK;
+}
+
+int gdg_blend_rows_delayed(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                           const double *weight, const int *delay, const double *const *history, double *const *out) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
+    if (rc != GDG_OK) return rc;
+    if (n_blends == 0 || samples == 0) return GDG_OK;
+    if (!rows || !out) return GDG_ERR_INVALID;
+    for (int b = 0; b < n_blends; b++) if (!out[b]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the row of blend %d is NULL", b);
+    if (history) for (int r = 0; r < n_rows; r++) if (!history[r]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the history of row %d is NULL", r);
+    const size_t H = (size_t)GDG_BLEND_MAX_DELAY;
+    void *d_hist = nullptr;
+    if (history) {
+        enter_keep_fir_sums(ctx);
+        HIP_TRY(ctx, ctx->arena.alloc(&d_hist, (size_t)n_rows * H * sizeof(double)));
+        for (int r = 0; r < n_rows; r++) {
+            const hipError_t e = hipMemcpyAsync(static_cast<double *>(d_hist) + (size_t)r * H, history[r], H * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) {
+                hipStreamSynchronize(ctx->stream);
+                ctx->arena.release(d_hist);
+                return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
+            }
+        }
+    }
+    std::vector<double> sums((size_t)n_blends * samples);
+    rc = rows_round_trip(ctx, "blend rows", rows, n_rows, samples, sums.data(), sums.size() * sizeof(double), [&](const double *d_rows, void *d_out) {
+        return gdg_blend_rows_delayed_device(ctx, d_rows, samples, n_rows, samples, n_blends, first, channel, weight, delay, static_cast<const double *>(d_hist), H,
+                                             static_cast<double *>(d_out), samples);
+    });
+    if (d_hist) {
+        hipStreamSynchronize(ctx->stream);
+        ctx->arena.release(d_hist);
+    }
+    if (rc != GDG_OK) return rc;
+    for (int b = 0; b < n_blends; b++) memcpy(out[b], sums.data() + (size_t)b * samples, samples * sizeof(double));
+    return GDG_OK;
+}
+
+/* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
+int gdg_blend_delays_from_align(const gdg_block_align *records, int ports, size_t blocks, const int *ref, double min_coeff, int n_blends, const int *first,
+                                const int *channel, int *delay, int *sign) {
+    static_assert(sizeof(gdg_blend_align_rec) == sizeof(gdg_block_align) && offsetof(gdg_blend_align_rec, corr) == offsetof(gdg_block_align, corr) &&
+                  offsetof(gdg_blend_align_rec, ref_sq) == offsetof(gdg_block_align, ref_sq) && offsetof(gdg_blend_align_rec, sq_at_lag) == offsetof(gdg_block_align, sq_at_lag) &&
+                  offsetof(gdg_blend_align_rec, lag) == offsetof(gdg_block_align, lag), "blend.h restates gdg_block_align");
+    int bad = -1;
+    char msg[200];
+    switch (gdg_blend_plan_delays(reinterpret_cast<const gdg_blend_align_rec *>(records), ports, blocks, ref, min_coeff, n_blends, first, channel, delay, sign, &bad)) {
+    case BLEND_PLAN_OK: return GDG_OK;
+    case BLEND_PLAN_LIST: snprintf(msg, sizeof msg, "blend delays from align: blend %d: 1 to %d terms, offsets from 0 that ascend, every channel and its reference a port below %d", bad, GDG_BLEND_MAX_TERMS, ports); break;
+    case BLEND_PLAN_MIXED: snprintf(msg, sizeof msg, "blend delays from align: blend %d: its terms are not measured against one reference port", bad); break;
+    default: snprintf(msg, sizeof msg, "blend delays from align: %d ports, %d blends, min_coeff = %g (0 to 1); records, ref, first, channel, delay and sign are needed", ports, n_blends, min_coeff); break;
+    }
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
 }
 
 /* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */

@@ -1,9 +1,10 @@
 /*
  * blend.h -- the blend outputs (gdg_batch_set_blends, gdg_blend_rows; include/gdg.h states the arithmetic): a blend is a weighted sum of
- * chain output rows, s = w_0 x[c_0], then s = s + w_k x[c_k] in term order, every product and every add rounded on its own.  Here: the two
- * rounded operations as __host__ __device__ inlines -- the kernel of blend_kernels.h uses them, and so can a stand-alone host program
- * (tests/native/blend_check.cpp) -- the validation of a blend list in its CSR form, the rule by which a list replaces the one in force, and
- * the sum on the host.  No HIP header is needed to compile this file.
+ * chain output rows, s = w_0 x[c_0], then s = s + w_k x[c_k] in term order, every product and every add rounded on its own; a term may be
+ * delayed by a whole number of samples (gdg_batch_set_blends_delayed).  Here: the two rounded operations as __host__ __device__ inlines --
+ * the kernels of blend_kernels.h use them, and so can a stand-alone host program (tests/native/blend_check.cpp, blend_delay_check.cpp) --
+ * the validation of a blend list in its CSR form, the rule by which a list replaces the one in force, the sum on the host, and the planner
+ * that turns alignment records into delays and signs (gdg_blend_delays_from_align).  No HIP header is needed to compile this file.
  */
 #ifndef GDG_BLEND_H
 #define GDG_BLEND_H
@@ -18,6 +19,9 @@
 #ifndef GDG_BLEND_MAX_TERMS
 #define GDG_BLEND_MAX_TERMS 32
 #define GDG_BLEND_MAX_BLENDS 1024
+#endif
+#ifndef GDG_BLEND_MAX_DELAY
+#define GDG_BLEND_MAX_DELAY 4096
 #endif
 
 #if defined(__HIPCC__)
@@ -54,13 +58,15 @@ enum {
     BLEND_TERMS = 5,                           /* blend b has more than GDG_BLEND_MAX_TERMS terms */
     BLEND_CHANNEL = 6,                         /* term `term` of blend b names a channel outside [0, n_channels) */
     BLEND_WEIGHT = 7,                          /* ... has a weight that is not finite */
-    BLEND_GAIN = 8                             /* blend b's output gain is not finite */
+    BLEND_GAIN = 8,                            /* blend b's output gain is not finite */
+    BLEND_DELAY = 9                            /* term `term` of blend b has a delay outside 0 .. GDG_BLEND_MAX_DELAY */
 };
 
-/* The whole list: n_blends blends, blend b's terms at [first[b], first[b + 1]) of channel[] and weight[]; gain: one per blend, or null (all
- * 1.0).  *blend, *term: the first offender (the term counted within its blend), -1 where the status names none. */
-static inline int gdg_blend_check(int n_blends, const int *first, const int *channel, const double *weight, const double *gain, int n_channels,
-                                  int *blend, int *term) {
+/* The whole list: n_blends blends, blend b's terms at [first[b], first[b + 1]) of channel[], weight[] and delay[]; delay: one per term, or
+ * null (all 0); gain: one per blend, or null (all 1.0).  *blend, *term: the first offender (the term counted within its blend), -1 where the
+ * status names none. */
+static inline int gdg_blend_check(int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const double *gain,
+                                  int n_channels, int *blend, int *term) {
     *blend = *term = -1;
     if (n_blends < 0 || n_blends > GDG_BLEND_MAX_BLENDS) return BLEND_COUNT;
     if (n_blends == 0) return BLEND_OK;
@@ -78,6 +84,7 @@ static inline int gdg_blend_check(int n_blends, const int *first, const int *cha
             *term = k - first[b];
             if (channel[k] < 0 || channel[k] >= n_channels) return BLEND_CHANNEL;
             if (!isfinite(weight[k])) return BLEND_WEIGHT;
+            if (delay && (delay[k] < 0 || delay[k] > GDG_BLEND_MAX_DELAY)) return BLEND_DELAY;
         }
         *term = -1;
         if (gain && !isfinite(gain[b])) return BLEND_GAIN;
@@ -85,31 +92,40 @@ static inline int gdg_blend_check(int n_blends, const int *first, const int *cha
     *blend = -1;
     return BLEND_OK;
 }
+/* the list without delays */
+static inline int gdg_blend_check(int n_blends, const int *first, const int *channel, const double *weight, const double *gain, int n_channels,
+                                  int *blend, int *term) {
+    return gdg_blend_check(n_blends, first, channel, weight, (const int *)nullptr, gain, n_channels, blend, term);
+}
 
 /* the list in force */
 struct BlendSet {
     std::vector<int> first, channel;           /* first: count() + 1 offsets, empty = off */
     std::vector<double> weight, gain;          /* gain: one per blend, 1.0 where none was given */
+    std::vector<int> delay;                    /* one per term; empty = every delay 0, and the list is what it was before delays existed */
     int count() const { return first.empty() ? 0 : (int)first.size() - 1; }
     int terms() const { return (int)channel.size(); }
+    int max_delay() const { int m = 0; for (int d : delay) if (d > m) m = d; return m; }
     bool unit_gains() const { for (double g : gain) if (g != 1.0) return false; return true; }
-    /* the table as a batch call uploads it, made when the list is taken: first | channel | pad to 8 bytes | weight | gain */
+    /* the table as a batch call uploads it, made when the list is taken: first | channel | delay | pad to 8 bytes | weight | gain; the delays
+     * are there only while one of them is not 0 */
     std::vector<unsigned char> packed;
-    size_t packed_ints() const { return ((first.size() + channel.size()) * sizeof(int) + 7) & ~(size_t)7; }
+    size_t packed_ints() const { return ((first.size() + channel.size() + delay.size()) * sizeof(int) + 7) & ~(size_t)7; }
     void pack() {
         packed.assign(first.empty() ? 0 : packed_ints() + (weight.size() + gain.size()) * sizeof(double), 0);
         if (packed.empty()) return;
         memcpy(packed.data(), first.data(), first.size() * sizeof(int));
         memcpy(packed.data() + first.size() * sizeof(int), channel.data(), channel.size() * sizeof(int));
+        if (!delay.empty()) memcpy(packed.data() + (first.size() + channel.size()) * sizeof(int), delay.data(), delay.size() * sizeof(int));
         memcpy(packed.data() + packed_ints(), weight.data(), weight.size() * sizeof(double));
         memcpy(packed.data() + packed_ints() + weight.size() * sizeof(double), gain.data(), gain.size() * sizeof(double));
     }
 };
 
 /* whole or not at all: a refused list leaves the one in force as it is */
-static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *first, const int *channel, const double *weight, const double *gain,
-                                    int n_channels, int *blend, int *term) {
-    const int rc = gdg_blend_check(n_blends, first, channel, weight, gain, n_channels, blend, term);
+static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *first, const int *channel, const double *weight, const int *delay,
+                                    const double *gain, int n_channels, int *blend, int *term) {
+    const int rc = gdg_blend_check(n_blends, first, channel, weight, delay, gain, n_channels, blend, term);
     if (rc != BLEND_OK) return rc;
     BlendSet next;
     if (n_blends > 0) {
@@ -119,10 +135,18 @@ static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *firs
         next.weight.assign(weight, weight + terms);
         if (gain) next.gain.assign(gain, gain + n_blends);
         else next.gain.assign((size_t)n_blends, 1.0);
+        if (delay) {
+            next.delay.assign(delay, delay + terms);
+            if (next.max_delay() == 0) next.delay.clear();                   /* all zeros: the list without delays */
+        }
     }
     next.pack();
     set = next;
     return BLEND_OK;
+}
+static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *first, const int *channel, const double *weight, const double *gain,
+                                    int n_channels, int *blend, int *term) {
+    return gdg_blend_replace(set, n_blends, first, channel, weight, (const int *)nullptr, gain, n_channels, blend, term);
 }
 
 /* the definition on the host: sample i of the blend with terms [k0, k1) over rows[channel][i] */
@@ -137,6 +161,111 @@ static inline void gdg_blend_sum_host(const double *const *rows, size_t samples,
                                       double *const *out) {
     for (int b = 0; b < n_blends; b++)
         for (size_t i = 0; i < samples; i++) out[b][i] = gdg_blend_sample(rows, i, channel, weight, first[b], first[b + 1]);
+}
+
+/* ---- delayed terms (include/gdg.h, BLEND: x_k[i] = x[c_k][i - d_k], +0.0 in front of the job) ------------------------------------------- */
+/* sample i - d of a row; what lies in front of its sample 0 is `history` -- GDG_BLEND_MAX_DELAY doubles, the last of them sample -1 -- or,
+ * without one, +0.0 */
+static inline double gdg_blend_delayed_x(const double *row, const double *history, size_t i, int d) {
+    if (i >= (size_t)d) return row[i - (size_t)d];
+    return history ? history[(size_t)GDG_BLEND_MAX_DELAY + i - (size_t)d] : 0.0;
+}
+
+/* the definition on the host: history = one run per row, or null; delay = one per term, or null */
+static inline double gdg_blend_sample_delayed(const double *const *rows, const double *const *history, size_t i, const int *channel, const double *weight,
+                                              const int *delay, int k0, int k1) {
+    auto x = [&](int k) { return gdg_blend_delayed_x(rows[channel[k]], history ? history[channel[k]] : nullptr, i, delay ? delay[k] : 0); };
+    double s = gdg_blend_mul(weight[k0], x(k0));
+    for (int k = k0 + 1; k < k1; k++) s = gdg_blend_add(s, gdg_blend_mul(weight[k], x(k)));
+    return s;
+}
+
+static inline void gdg_blend_sum_host_delayed(const double *const *rows, const double *const *history, size_t samples, int n_blends, const int *first,
+                                              const int *channel, const double *weight, const int *delay, double *const *out) {
+    for (int b = 0; b < n_blends; b++)
+        for (size_t i = 0; i < samples; i++) out[b][i] = gdg_blend_sample_delayed(rows, history, i, channel, weight, delay, first[b], first[b + 1]);
+}
+
+/* ---- the delays from the alignment records (gdg_blend_delays_from_align) --------------------------------------------------------------- */
+struct gdg_blend_align_rec { double corr, corr0, ref_sq, sq_at_lag; int32_t lag; uint32_t reserved; };      /* gdg_block_align of include/gdg.h */
+
+enum {
+    BLEND_PLAN_OK = 0,
+    BLEND_PLAN_ARGS = 1,                       /* a list is missing, a count is out of range, min_coeff lies outside [0, 1] */
+    BLEND_PLAN_LIST = 2,                       /* the CSR form of *blend is broken, it names a port outside [0, ports), or that port's reference is none */
+    BLEND_PLAN_MIXED = 3                       /* the terms of *blend do not share one reference port */
+};
+
+/* lag and sign of one port from its records: the blocks with both energies and a coefficient of at least min_coeff count; the lower median
+ * of their lags, the sign of the sum of their corr; no such block: lag 0, sign +1 */
+static inline void gdg_blend_port_lag(const gdg_blend_align_rec *rec, size_t blocks, double min_coeff, int *lag, int *sign) {
+    std::vector<int> lags;
+    double sum = 0.0;
+    for (size_t b = 0; b < blocks; b++) {
+        const gdg_blend_align_rec &r = rec[b];
+        if (!(r.ref_sq > 0.0) || !(r.sq_at_lag > 0.0)) continue;
+        if (!(fabs(r.corr) / sqrt(r.ref_sq * r.sq_at_lag) >= min_coeff)) continue;
+        lags.push_back(r.lag);
+        sum += r.corr;
+    }
+    *lag = 0;
+    *sign = 1;
+    if (lags.empty()) return;
+    for (size_t i = 1; i < lags.size(); i++) {                               /* sorted by insertion: no <algorithm> for a few blocks */
+        const int v = lags[i];
+        size_t j = i;
+        for (; j > 0 && lags[j - 1] > v; j--) lags[j] = lags[j - 1];
+        lags[j] = v;
+    }
+    *lag = lags[(lags.size() - 1) / 2];
+    *sign = sum < 0.0 ? -1 : 1;
+}
+
+/* records[ports][blocks] as measured against ref[ports]; the blends in CSR form with `channel` naming a port.  Everything is checked before
+ * delay[] and sign[] (one per term) are written; *blend: the offender. */
+static inline int gdg_blend_plan_delays(const gdg_blend_align_rec *records, int ports, size_t blocks, const int *ref, double min_coeff, int n_blends,
+                                        const int *first, const int *channel, int *delay, int *sign, int *blend) {
+    *blend = -1;
+    if (ports < 1 || n_blends < 0 || n_blends > GDG_BLEND_MAX_BLENDS || !ref || (blocks && !records) || !(min_coeff >= 0.0 && min_coeff <= 1.0)) return BLEND_PLAN_ARGS;
+    if (n_blends == 0) return BLEND_PLAN_OK;
+    if (!first || !channel || !delay || !sign) return BLEND_PLAN_ARGS;
+    if (first[0] != 0) { *blend = 0; return BLEND_PLAN_LIST; }
+    for (int b = 0; b < n_blends; b++) {
+        *blend = b;
+        if (first[b + 1] <= first[b] || first[b + 1] - first[b] > GDG_BLEND_MAX_TERMS) return BLEND_PLAN_LIST;
+    }
+    std::vector<int> root((size_t)n_blends, -1);
+    for (int b = 0; b < n_blends; b++) {
+        *blend = b;
+        int r = -1;
+        for (int k = first[b]; k < first[b + 1]; k++) {                      /* the terms that are measured against another port: all against one */
+            const int c = channel[k];
+            if (c < 0 || c >= ports || ref[c] < -1 || ref[c] >= ports) return BLEND_PLAN_LIST;
+            if (ref[c] < 0 || ref[c] == c) continue;
+            if (r >= 0 && r != ref[c]) return BLEND_PLAN_MIXED;
+            r = ref[c];
+        }
+        for (int k = first[b]; k < first[b + 1]; k++) {                      /* a term measured against nothing else has to BE that port */
+            const int c = channel[k];
+            if (ref[c] >= 0 && ref[c] != c) continue;
+            if (r >= 0 && r != c) return BLEND_PLAN_MIXED;
+            r = c;
+        }
+        root[(size_t)b] = r;
+    }
+    *blend = -1;
+    for (int b = 0; b < n_blends; b++) {
+        int lag[GDG_BLEND_MAX_TERMS], most = 0;
+        for (int k = first[b]; k < first[b + 1]; k++) {
+            const int c = channel[k], t = k - first[b];
+            lag[t] = 0;
+            sign[k] = 1;
+            if (c != root[(size_t)b]) gdg_blend_port_lag(records + (size_t)c * blocks, blocks, min_coeff, &lag[t], &sign[k]);
+            if (t == 0 || lag[t] > most) most = lag[t];
+        }
+        for (int k = first[b]; k < first[b + 1]; k++) delay[k] = most - lag[k - first[b]];
+    }
+    return BLEND_PLAN_OK;
 }
 
 #endif

@@ -71,3 +71,130 @@ hipError_t gdg_launch_blend_rows(const double *d_rows, size_t row_stride, size_t
     else blend_rows_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_out, out_stride);
     return hipGetLastError();
 }
+
+/*
+ * Delayed terms (include/gdg.h, BLEND: x_k[i] = x[c_k][i - d_k]).  The same grid, the same table through scalar loads --
+ * now with one delay per term --, the same unroll and the same 16-byte store.  What differs is the load of a term:
+ *   - a pair of samples at i - d is 16-byte aligned only when d is even (i is, and so are the row's base and stride in a VEC launch): an
+ *     even d loads the pair, an odd d two 8-byte samples.  d comes from the table, so the choice is uniform over the workgroup.
+ *   - samples in front of the launch's first come from the history: GDG_BLEND_MAX_DELAY doubles per row, the last of them sample -1, or
+ *     +0.0 where the caller has none.  Whether a lane can meet them is decided per TILE: GDG_BLEND_MAX_DELAY is a multiple of a tile's
+ *     width, so a tile that starts at or behind it never does and runs the path without the compare (HIST = false); only the first
+ *     GDG_BLEND_MAX_DELAY samples of a launch run the other.
+ * A load address is formed only after the compare that chose its side: rows are read inside [0, samples), the history inside its run.
+ */
+static_assert(GDG_BLEND_MAX_DELAY % (2 * BLEND_T) == 0, "a tile lies wholly in front of or wholly behind GDG_BLEND_MAX_DELAY");
+
+/* sample `at` - d of row c (at < samples) */
+template <bool HIST>
+__device__ __forceinline__ double blend_delayed_one(const double *rows, size_t row_stride, const double *history, size_t hist_stride, int c, size_t at, int d) {
+    if (!HIST || at >= (size_t)d) return rows[(size_t)c * row_stride + (at - (size_t)d)];
+    return history ? history[(size_t)c * hist_stride + ((size_t)GDG_BLEND_MAX_DELAY + at - (size_t)d)] : 0.0;
+}
+
+template <typename T, bool HIST> struct blend_delayed_load;
+template <bool HIST> struct blend_delayed_load<double, HIST> {
+    static __device__ __forceinline__ double at(const double *rows, size_t row_stride, const double *history, size_t hist_stride, int c, size_t i, int d) {
+        return blend_delayed_one<HIST>(rows, row_stride, history, hist_stride, c, i, d);
+    }
+};
+template <bool HIST> struct blend_delayed_load<v2d, HIST> {
+    /* i is even and i + 1 < samples; an even d keeps i - d even, and both samples lie on one side of sample 0 */
+    static __device__ __forceinline__ v2d at(const double *rows, size_t row_stride, const double *history, size_t hist_stride, int c, size_t i, int d) {
+        if (!(d & 1)) {
+            if (!HIST || i >= (size_t)d) return *reinterpret_cast<const v2d *>(rows + (size_t)c * row_stride + (i - (size_t)d));
+            if (history) return *reinterpret_cast<const v2d *>(history + (size_t)c * hist_stride + ((size_t)GDG_BLEND_MAX_DELAY + i - (size_t)d));
+            const v2d z = { 0.0, 0.0 };
+            return z;
+        }
+        const v2d r = { blend_delayed_one<HIST>(rows, row_stride, history, hist_stride, c, i, d),
+                        blend_delayed_one<HIST>(rows, row_stride, history, hist_stride, c, i + 1, d) };
+        return r;
+    }
+};
+
+/* the terms [k0, k1) at sample `at` (T = v2d: the pair at, at + 1) */
+template <typename T, bool HIST>
+__device__ __forceinline__ void blend_delayed_terms(const double *rows, size_t row_stride, const double *history, size_t hist_stride, size_t at,
+                                                    const int *__restrict__ channel, const double *__restrict__ weight, const int *__restrict__ delay, int k0, int k1,
+                                                    double *dst) {
+    typedef blend_ops<T> op;
+    auto load = [&](int k) { return blend_delayed_load<T, HIST>::at(rows, row_stride, history, hist_stride, channel[k], at, delay[k]); };
+    int k = k0;
+    T s = op::mul(weight[k], load(k));
+    k++;
+    for (; k + 4 <= k1; k += 4) {
+        const T x0 = load(k), x1 = load(k + 1), x2 = load(k + 2), x3 = load(k + 3);
+        s = op::add(s, op::mul(weight[k], x0));
+        s = op::add(s, op::mul(weight[k + 1], x1));
+        s = op::add(s, op::mul(weight[k + 2], x2));
+        s = op::add(s, op::mul(weight[k + 3], x3));
+    }
+    for (; k < k1; k++) s = op::add(s, op::mul(weight[k], load(k)));
+    *reinterpret_cast<T *>(dst + at) = s;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(BLEND_T)
+blend_delayed_kernel(const double *rows, size_t row_stride, size_t samples, const int *__restrict__ first, const int *__restrict__ channel,
+                     const double *__restrict__ weight, const int *__restrict__ delay, const double *history, size_t hist_stride, double *out, size_t out_stride) {
+    const int k0 = first[blockIdx.y], k1 = first[blockIdx.y + 1];
+    double *dst = out + (size_t)blockIdx.y * out_stride;
+    const size_t tile = (size_t)blockIdx.x * BLEND_T * (VEC ? 2 : 1), at = tile + (size_t)threadIdx.x * (VEC ? 2 : 1);
+    if (at >= samples) return;
+    const bool pair = VEC && at + 1 < samples;
+    if (tile >= (size_t)GDG_BLEND_MAX_DELAY) {                               /* uniform: no sample of this tile lies in front of the launch */
+        if (pair) blend_delayed_terms<v2d, false>(rows, row_stride, history, hist_stride, at, channel, weight, delay, k0, k1, dst);
+        else blend_delayed_terms<double, false>(rows, row_stride, history, hist_stride, at, channel, weight, delay, k0, k1, dst);
+    } else {
+        if (pair) blend_delayed_terms<v2d, true>(rows, row_stride, history, hist_stride, at, channel, weight, delay, k0, k1, dst);
+        else blend_delayed_terms<double, true>(rows, row_stride, history, hist_stride, at, channel, weight, delay, k0, k1, dst);
+    }
+}
+
+/* as gdg_launch_blend_rows, with d_delay[d_first[n_blends]] (every one in 0 .. GDG_BLEND_MAX_DELAY, checked by the caller) and d_history:
+ * null (+0.0 in front of sample 0) or row r's GDG_BLEND_MAX_DELAY samples in front of sample 0 at d_history + r * hist_stride; read, never
+ * written.  d_out overlaps neither the rows nor the history. */
+hipError_t gdg_launch_blend_rows_delayed(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
+                                         const double *d_weight, const int *d_delay, const double *d_history, size_t hist_stride, double *d_out, size_t out_stride,
+                                         hipStream_t s) {
+    if (n_blends == 0 || samples == 0) return hipSuccess;
+    if (!d_rows || !d_out || !d_first || !d_channel || !d_weight || !d_delay || row_stride < samples || out_stride < samples || n_blends > 65535u ||
+        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_weight & 7) || ((uintptr_t)d_first & 3) || ((uintptr_t)d_channel & 3) ||
+        ((uintptr_t)d_delay & 3) || (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY)))
+        return hipErrorInvalidValue;
+    const bool vec = !((uintptr_t)d_rows & 15) && !(row_stride & 1) && !((uintptr_t)d_out & 15) && !(out_stride & 1) &&
+                     (!d_history || (!((uintptr_t)d_history & 15) && !(hist_stride & 1)));
+    const size_t lanes = vec ? (samples + 1) / 2 : samples, tiles = (lanes + BLEND_T - 1) / BLEND_T;
+    if (tiles > 0x7fffffffu) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)tiles, n_blends);
+    if (vec) blend_delayed_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_history, hist_stride, d_out, out_stride);
+    else blend_delayed_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_history, hist_stride, d_out, out_stride);
+    return hipGetLastError();
+}
+
+/* The history of the next launch: the last GDG_BLEND_MAX_DELAY of `samples` samples of rows 0 .. n_rows - 1 go to d_history[r][GDG_BLEND_MAX_DELAY],
+ * so that its last entry is the rows' last sample.  blockIdx.y = the row; a lane moves 16 bytes where both sides allow it, 8 otherwise. */
+template <bool VEC>
+__global__ void __launch_bounds__(BLEND_T)
+blend_history_save_kernel(const double *rows, size_t row_stride, size_t samples, double *history) {
+    const size_t at = ((size_t)blockIdx.x * BLEND_T + threadIdx.x) * (VEC ? 2 : 1);
+    if (at >= (size_t)GDG_BLEND_MAX_DELAY) return;
+    const double *src = rows + (size_t)blockIdx.y * row_stride + (samples - (size_t)GDG_BLEND_MAX_DELAY) + at;
+    double *dst = history + (size_t)blockIdx.y * GDG_BLEND_MAX_DELAY + at;
+    if (VEC) *reinterpret_cast<v2d *>(dst) = *reinterpret_cast<const v2d *>(src);
+    else *dst = *src;
+}
+
+/* samples >= GDG_BLEND_MAX_DELAY (a batch step is a whole number of blocks of 8192); d_history overlaps no row */
+hipError_t gdg_launch_blend_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s) {
+    if (n_rows == 0) return hipSuccess;
+    if (!d_rows || !d_history || samples < (size_t)GDG_BLEND_MAX_DELAY || row_stride < samples || n_rows > 65535u || ((uintptr_t)d_rows & 7) || ((uintptr_t)d_history & 7))
+        return hipErrorInvalidValue;
+    const bool vec = !((uintptr_t)d_rows & 15) && !(row_stride & 1) && !(samples & 1) && !((uintptr_t)d_history & 15);
+    const unsigned lanes = GDG_BLEND_MAX_DELAY / (vec ? 2 : 1);
+    const dim3 grid((lanes + BLEND_T - 1) / BLEND_T, n_rows);
+    if (vec) blend_history_save_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_history);
+    else blend_history_save_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_history);
+    return hipGetLastError();
+}

@@ -352,8 +352,8 @@ struct gdg_ctx {
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
     /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
      * grown when a slice needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
-    void *batch_dev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t batch_dev_cap[6] = { 0, 0, 0, 0, 0, 0 };
+    void *batch_dev[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    size_t batch_dev_cap[7] = { 0, 0, 0, 0, 0, 0, 0 };
     int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
     /* a batch job, how far it has come, and per input the source frames handed over: the context's is the streamed run's
      * (gdg_batch_stream_open .. _close); a one-call run describes its own and leaves this one closed */
@@ -403,7 +403,9 @@ struct gdg_ctx {
     double *d_trim = nullptr;
     /* the blend outputs (gdg_batch_set_blends; blend.h): weighted sums of this context's chain rows as the ports behind the metronome's; an
      * empty list = off (never set, or set with 0 blends).  While blends are in force a batch window has nch + 3 + count() rows and the device
-     * copy of the table -- first | channel | weight | gain, made and uploaded at the start of a batch call -- exists; off, neither does.
+     * copy of the table -- first | channel | delay | weight | gain, made and uploaded at the start of a batch call -- exists; off, neither does.
+     * While one of the delays is not 0 (gdg_batch_set_blends_delayed) batch_dev[BATCH_BLEND_HISTORY] holds the chain rows' last 4096 samples
+     * from step to step; it is zeroed by the first slice of a job and is in no checkpoint (the checkpoint calls then refuse).
      * Configuration like the trim: in no blob. */
     BlendSet blend;
     unsigned char *d_blend = nullptr;
@@ -751,8 +753,11 @@ enum {
     BATCH_ENCODED,                         /* two halves of a step on its way down: encoded rows, a shard's float64 rows */
     BATCH_CARRY,                           /* [N][GDG_STREAM_CARRY] source frames every resampled input keeps for its next step */
     BATCH_UPLOAD,                          /* two halves of a step on its way up: descriptors, then the inputs' bytes */
-    BATCH_SOURCE                           /* two halves of the resampler's source frames: [kept | this step's] per resampled input */
+    BATCH_SOURCE,                          /* two halves of the resampler's source frames: [kept | this step's] per resampled input */
+    BATCH_BLEND_HISTORY,                   /* [N][GDG_BLEND_MAX_DELAY] the chain rows' last samples of the step before, only while a blend delay is in force */
+    BATCH_DEV_SLOTS
 };
+static_assert(BATCH_DEV_SLOTS == 7, "gdg_ctx::batch_dev has one entry per slot");
 int ensure_tuner(gdg_ctx *ctx);
 
 #pragma GCC visibility pop

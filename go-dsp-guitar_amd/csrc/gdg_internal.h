@@ -360,6 +360,14 @@ hipError_t gdg_launch_block_true_peak(const double *d_rows, size_t row_stride, u
  * has been checked by the caller: every channel a row of d_rows, 1 to 32 terms a blend.  Rows 8-byte aligned, strides >= samples. */
 hipError_t gdg_launch_blend_rows(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
                                  const double *d_weight, double *d_out, size_t out_stride, hipStream_t s);
+/* ... with one delay per term, d_delay[d_first[n_blends]], each in 0 .. GDG_BLEND_MAX_DELAY (checked by the caller): term k reads sample i - d_k.
+ * d_history: null (+0.0 in front of sample 0) or, per row, the GDG_BLEND_MAX_DELAY samples in front of sample 0 at d_history + r * hist_stride
+ * (hist_stride >= GDG_BLEND_MAX_DELAY, 8-byte aligned); read, never written.  d_out overlaps neither. */
+hipError_t gdg_launch_blend_rows_delayed(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
+                                         const double *d_weight, const int *d_delay, const double *d_history, size_t hist_stride, double *d_out, size_t out_stride,
+                                         hipStream_t s);
+/* the last GDG_BLEND_MAX_DELAY of `samples` samples (samples >= GDG_BLEND_MAX_DELAY) of rows 0 .. n_rows - 1 into d_history[n_rows][GDG_BLEND_MAX_DELAY] */
+hipError_t gdg_launch_blend_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

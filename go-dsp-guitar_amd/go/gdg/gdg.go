@@ -1992,3 +1992,245 @@ func (this *Context) BlendRowsDevice(dRows unsafe.Pointer, rowStride int, nRows 
 	return this.err(C.gdg_blend_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(len(blends)),
 		&first[0], &channel[0], &weight[0], (*C.double)(dOut), C.size_t(outStride)))
 }
+
+// BlendMaxDelay: the largest delay of a blend's term in samples (GDG_BLEND_MAX_DELAY), and the samples of history a row keeps.
+const BlendMaxDelay = 4096
+
+// blendDelays: one delay per term of blends, in C memory with a spare entry (the caller frees it); delay[b][k] belongs to blends[b][k].
+func blendDelays(blends [][]BlendTerm, delay [][]int) (unsafe.Pointer, error) {
+	if len(delay) != len(blends) {
+		return nil, fmt.Errorf("gdg: delays for %d blends, %d blends", len(delay), len(blends))
+	}
+	terms := 0
+	for b, list := range blends {
+		if len(delay[b]) != len(list) {
+			return nil, fmt.Errorf("gdg: blend %d has %d terms and %d delays", b, len(list), len(delay[b]))
+		}
+		terms += len(list)
+	}
+	p := C.calloc(C.size_t(terms+1), 4)
+	if p == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	dst := (*[1 << 28]C.int)(p)[:terms:terms]
+	k := 0
+	for _, list := range delay {
+		for _, d := range list {
+			dst[k] = C.int(d)
+			k++
+		}
+	}
+	return p, nil
+}
+
+// BatchSetBlendsDelayed: BatchSetBlends with one delay per term (gdg_batch_set_blends_delayed): term k of blend b reads its row
+// delay[b][k] samples back, 0 to BlendMaxDelay, and zeros in front of the job; nil delays: every delay 0, which is BatchSetBlends.  While
+// a delay is in force the context keeps the chain rows' last 4096 samples from step to step, the bytes do not depend on how the job is
+// cut, and the checkpoint calls return an error: the history is not in the container.
+func (this *Context) BatchSetBlendsDelayed(blends [][]BlendTerm, delay [][]int, gain []float64) error {
+	n := len(blends)
+	if n == 0 || delay == nil {
+		return this.BatchSetBlends(blends, gain)
+	}
+	if len(gain) != 0 && len(gain) != n {
+		return fmt.Errorf("gdg: %d gains for %d blends", len(gain), n)
+	}
+	dp, e := blendDelays(blends, delay)
+	if e != nil {
+		return e
+	}
+	defer C.free(dp)
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return err
+	}
+	defer release()
+	if len(gain) == 0 {
+		return this.err(C.gdg_batch_set_blends_delayed(this.ctx, C.int(n), &first[0], &channel[0], &weight[0], (*C.int)(dp), nil))
+	}
+	g := (*[1 << 28]C.double)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.double(0)))))
+	if g == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(g))
+	for i, v := range gain {
+		g[i] = C.double(v)
+	}
+	return this.err(C.gdg_batch_set_blends_delayed(this.ctx, C.int(n), &first[0], &channel[0], &weight[0], (*C.int)(dp), &g[0]))
+}
+
+// BatchBlendMaxDelay: the largest delay of the blends in force (gdg_batch_blend_max_delay); 0: the blends are stateless.
+func (this *Context) BatchBlendMaxDelay() int {
+	return int(C.gdg_batch_blend_max_delay(this.ctx))
+}
+
+// BlendRowsDelayed: the delayed blends' sums over any rows of equal length (gdg_blend_rows_delayed); history is nil (zeros in front of
+// sample 0) or one run of BlendMaxDelay samples per row whose last entry is sample -1.  result[blend][sample].
+func (this *Context) BlendRowsDelayed(rows [][]float64, blends [][]BlendTerm, delay [][]int, history [][]float64) ([][]float64, error) {
+	n := len(rows)
+	nb := len(blends)
+	if n == 0 {
+		return nil, fmt.Errorf("gdg: no rows")
+	}
+	if history != nil && len(history) != n {
+		return nil, fmt.Errorf("gdg: %d histories for %d rows", len(history), n)
+	}
+	samples := len(rows[0])
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n+nb+1), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i := 0; i < n+nb; i++ {
+		if i < n && len(rows[i]) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(rows[i]), samples)
+		}
+		p := C.calloc(C.size_t(samples+1), 8)
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		if i < n {
+			copy((*[1 << 37]float64)(p)[:samples:samples], rows[i])
+		}
+		rp[i] = (*C.double)(p)
+	}
+	hp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n+1), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if hp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(hp))
+	for i := range history {
+		if len(history[i]) != BlendMaxDelay {
+			return nil, fmt.Errorf("gdg: the history of row %d has %d samples; %d", i, len(history[i]), BlendMaxDelay)
+		}
+		p := C.calloc(C.size_t(BlendMaxDelay), 8)
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:BlendMaxDelay:BlendMaxDelay], history[i])
+		hp[i] = (*C.double)(p)
+	}
+	if delay == nil {
+		delay = make([][]int, nb)
+		for b := range delay {
+			delay[b] = make([]int, len(blends[b]))
+		}
+	}
+	dp, e := blendDelays(blends, delay)
+	if e != nil {
+		return nil, e
+	}
+	owned = append(owned, dp)
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return nil, err
+	}
+	defer release()
+	var rc C.int
+	if history == nil {
+		rc = C.gdg_blend_rows_delayed(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(nb), &first[0], &channel[0], &weight[0], (*C.int)(dp), nil, &rp[n])
+	} else {
+		rc = C.gdg_blend_rows_delayed(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(nb), &first[0], &channel[0], &weight[0], (*C.int)(dp), &hp[0], &rp[n])
+	}
+	if e := this.err(rc); e != nil {
+		return nil, e
+	}
+	out := make([][]float64, nb)
+	for b := range out {
+		out[b] = make([]float64, samples)
+		copy(out[b], (*[1 << 37]float64)(unsafe.Pointer(rp[n+b]))[:samples:samples])
+	}
+	return out, nil
+}
+
+// BlendRowsDelayedDevice: the same on device memory (gdg_blend_rows_delayed_device): row r at dRows + r*rowStride float64, its history --
+// nil, or BlendMaxDelay samples -- at dHistory + r*histStride, blend b's sums at dOut + b*outStride; returns when the sums are written.
+func (this *Context) BlendRowsDelayedDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, blends [][]BlendTerm, delay [][]int, dHistory unsafe.Pointer, histStride int, dOut unsafe.Pointer, outStride int) error {
+	dp, e := blendDelays(blends, delay)
+	if e != nil {
+		return e
+	}
+	defer C.free(dp)
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return err
+	}
+	defer release()
+	return this.err(C.gdg_blend_rows_delayed_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(len(blends)),
+		&first[0], &channel[0], &weight[0], (*C.int)(dp), (*C.double)(dHistory), C.size_t(histStride), (*C.double)(dOut), C.size_t(outStride)))
+}
+
+// BlendDelaysFromAlign: delays and signs of the blends' terms from alignment records (gdg_blend_delays_from_align): records[port][block] as
+// BatchAlign hands them out, measured with the reference list ref; a term's Channel names a port.  A port's lag is the lower median of Lag
+// over its blocks with a normalised coefficient of at least minCoeff, its sign that of the sum of their Corr; delay[b][k] = the blend's
+// largest lag - the term's, sign[b][k] = +1 or -1, to be multiplied into the weight.  Host arithmetic: no context and no device.  An
+// error when the terms of a blend are not measured against one reference port.
+func BlendDelaysFromAlign(records [][]BlockAlign, ref []int, minCoeff float64, blends [][]BlendTerm) ([][]int, [][]int, error) {
+	ports := len(records)
+	if ports == 0 || len(ref) != ports {
+		return nil, nil, fmt.Errorf("gdg: %d references for %d ports", len(ref), ports)
+	}
+	blocks := len(records[0])
+	for r, row := range records {
+		if len(row) != blocks {
+			return nil, nil, fmt.Errorf("gdg: port %d has %d records, port 0 has %d", r, len(row), blocks)
+		}
+	}
+	rec := (*[1 << 25]C.gdg_block_align)(C.calloc(C.size_t(ports*blocks+1), 40))
+	if rec == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	for r, row := range records {
+		for b, v := range row {
+			rec[r*blocks+b].corr = C.double(v.Corr)
+			rec[r*blocks+b].corr0 = C.double(v.Corr0)
+			rec[r*blocks+b].ref_sq = C.double(v.RefSq)
+			rec[r*blocks+b].sq_at_lag = C.double(v.SqAtLag)
+			rec[r*blocks+b].lag = C.int32_t(v.Lag)
+		}
+	}
+	fp, e := cRefs(ref)
+	if e != nil {
+		return nil, nil, e
+	}
+	defer C.free(fp)
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return nil, nil, err
+	}
+	defer release()
+	terms := int(first[len(blends)])
+	if weight == nil || terms < 0 {
+		return nil, nil, fmt.Errorf("gdg: no blend table")
+	}
+	res := (*[1 << 28]C.int)(C.calloc(C.size_t(2*terms+2), 4))
+	if res == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(res))
+	if rc := C.gdg_blend_delays_from_align(&rec[0], C.int(ports), C.size_t(blocks), (*C.int)(fp), C.double(minCoeff), C.int(len(blends)), &first[0], &channel[0], &res[0], &res[terms+1]); rc != 0 {
+		return nil, nil, fmt.Errorf("gdg: gdg_blend_delays_from_align: %d (the terms of a blend share one reference port; 0 <= minCoeff <= 1)", int(rc))
+	}
+	delay := make([][]int, len(blends))
+	sign := make([][]int, len(blends))
+	k := 0
+	for b, list := range blends {
+		delay[b] = make([]int, len(list))
+		sign[b] = make([]int, len(list))
+		for t := range list {
+			delay[b][t] = int(res[k])
+			sign[b][t] = int(res[terms+1+k])
+			k++
+		}
+	}
+	return delay, sign, nil
+}

@@ -51,6 +51,7 @@ def lib():
             "gdgh_engine_sync_chains": (cs, [vp, C.c_uint32]),
             "gdgh_engine_set_batch_blends": (cs, [vp, i32, vp, vp, vp, vp]),
             "gdgh_engine_batch_blends": (i32, [vp]),
+            "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
@@ -291,9 +292,9 @@ class Engine:
         _err(lib().gdgh_engine_set_batch_trim(self._h, g.ctypes.data, n, float(g[n]), float(g[n + 1]), float(g[n + 2])))
 
     def _set_blends(self, blends, blend_gain=None):
-        """Engine::SetBatchBlends, from the `blends` / `blend_gain` arguments of the batch calls: a list of lists of (job channel, weight) and
-        one output gain per blend (None: all 1); None or an empty list: off.  Returns the number of blends in force: the calls' outputs and
-        records then have N + 3 + B ports.  Refused on an engine of more than one shard."""
+        """Engine::SetBatchBlends, from the `blends` / `blend_gain` arguments of the batch calls: a list of lists of (job channel, weight) or
+        (job channel, weight, delay in samples) and one output gain per blend (None: all 1); None or an empty list: off.  Returns the number
+        of blends in force: the calls' outputs and records then have N + 3 + B ports.  Refused on an engine of more than one shard."""
         blends = [] if blends is None else [list(b) for b in blends]
         if not blends:
             _err(lib().gdgh_engine_set_batch_blends(self._h, 0, None, None, None, None))
@@ -301,13 +302,53 @@ class Engine:
         first = np.zeros(len(blends) + 1, dtype=np.int32)
         first[1:] = np.cumsum([len(b) for b in blends], dtype=np.int64)
         terms = [t for b in blends for t in b]
-        channel = np.array([int(c) for c, _ in terms] + [0], dtype=np.int32)          # a spare entry: a list without terms still has an address
-        weight = np.array([float(w) for _, w in terms] + [0.0], dtype=np.float64)
+        channel = np.array([int(t[0]) for t in terms] + [0], dtype=np.int32)          # a spare entry: a list without terms still has an address
+        weight = np.array([float(t[1]) for t in terms] + [0.0], dtype=np.float64)
         g = None if blend_gain is None else np.ascontiguousarray(blend_gain, dtype=np.float64).reshape(-1)
         if g is not None and g.size != len(blends):
             raise HostError("blend_gain: %d gains for %d blends" % (g.size, len(blends)))
+        if any(len(t) > 2 for t in terms):
+            delay = np.array([int(t[2]) if len(t) > 2 else 0 for t in terms] + [0], dtype=np.int32)
+            _err(lib().gdgh_engine_set_batch_blends_delayed(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data, delay.ctypes.data,
+                                                            None if g is None else g.ctypes.data))
+            return int(lib().gdgh_engine_batch_blends(self._h))
         _err(lib().gdgh_engine_set_batch_blends(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data, None if g is None else g.ctypes.data))
         return int(lib().gdgh_engine_batch_blends(self._h))
+
+    def render_aligned(self, blends, max_lag, min_coeff, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
+        """Two passes over one job: the terms of every blend are lined up before they are summed.  save_state; pass 1 renders with every
+        output skipped and the alignment records on, every term's channel measured against the channel of its blend's first term (a channel
+        that two blends measure against different first terms is refused); the planner (blend_delays_from_align) turns the records into
+        one delay and one sign per term; load_state; pass 2 renders with the delayed blends, the weights multiplied by the signs.  blends:
+        lists of (job channel, weight).  Returns (outs, delays, signs): the N + 3 + B output data sections, and per blend the list of delays
+        and of signs used.  Pass 1's records stay in aligned_records.  kw: batch_run's other arguments (an align in kw is replaced)."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        blends = [[(int(t[0]), float(t[1])) for t in b] for b in blends]
+        n3 = self.n_channels + 3
+        ref = [-1] * n3
+        for b, terms in enumerate(blends):
+            root = terms[0][0]
+            for c, _ in terms:
+                if c == root:
+                    continue
+                if ref[c] not in (-1, root):
+                    raise HostError("render_aligned: channel %d is measured against channel %d and, in blend %d, against channel %d" % (c, ref[c], b, root))
+                ref[c] = root
+        for b, terms in enumerate(blends):                      # a first term that another blend measures against something else
+            if ref[terms[0][0]] != -1 and any(c != terms[0][0] for c, _ in terms):
+                raise HostError("render_aligned: blend %d's first term, channel %d, is measured against channel %d in another blend" % (b, terms[0][0], ref[terms[0][0]]))
+        rate = target_rate if sample_rate is None else sample_rate
+        _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
+        blob = self.save_state()
+        rest = {k: v for k, v in kw.items() if k not in ("align", "blends", "skip_outputs")}
+        self.batch_run(inputs, target_rate, out_format, window=window, align=(ref, max_lag), skip_outputs=True, **rest)
+        self.aligned_records = self.last_align
+        delays, signs = pkg.blend_delays_from_align(self.aligned_records, ref, blends, min_coeff)
+        self.load_state(blob, rate)
+        lined = [[(c, w * signs[b][k], delays[b][k]) for k, (c, w) in enumerate(terms)] for b, terms in enumerate(blends)]
+        outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=lined, **rest)
+        return outs, delays, signs
 
     def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
         """Two passes over one job: every output file is written with the gain that brings its true peak to target_dbtp (dBTP), capped at
@@ -340,7 +381,7 @@ class Engine:
         keep the alignment records in last_align ([N + 3, blocks]); over shards the master rows are zero records.  true_peak: keep the
         true-peak records in last_true_peak ([N + 3, blocks], the same order).  trim: the N + 3 gains in front of the encoders (None:
         off).  skip_outputs: every output pointer NULL -- the job renders and measures, nothing is written; returns None.  blends: a list
-        of lists of (job channel, weight), blend_gain: one output gain per blend -- B more outputs and B more ports in every last_* record
+        of lists of (job channel, weight) or (job channel, weight, delay), blend_gain: one output gain per blend -- B more outputs and B more ports in every last_* record
         list, behind the metronome's (one-shard engines only; None: off)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()

@@ -971,23 +971,28 @@ int Engine::applyTrim(int shard, gdg_ctx *ctx) {
 }
 
 /* Engine::SetBatchBlends: validated whole before the list replaces the one in force (the library checks again when it is applied) */
-Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain) {
-    if (blends.empty()) { blendFirst_.clear(); blendChannel_.clear(); blendWeight_.clear(); blendGain_.clear(); return ""; }
+Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain, const std::vector<std::vector<int>> &delay) {
+    if (blends.empty()) { blendFirst_.clear(); blendChannel_.clear(); blendWeight_.clear(); blendGain_.clear(); blendDelay_.clear(); return ""; }
     if (shards() > 1)
         return format("SetBatchBlends: the engine has %d shards: every shard's context holds its own channels only, so a blend cannot read a term on another "
                       "device, and the library's shard calls refuse blends; blends need a one-shard engine", shards());
     if (blends.size() > GDG_BLEND_MAX_BLENDS) return format("SetBatchBlends: %zu blends; at most %d", blends.size(), GDG_BLEND_MAX_BLENDS);
     if (!gain.empty() && gain.size() != blends.size()) return format("SetBatchBlends: %zu gains for %zu blends (none: every gain 1)", gain.size(), blends.size());
-    std::vector<int> first(1, 0), channel;
+    if (!delay.empty() && delay.size() != blends.size()) return format("SetBatchBlends: delays for %zu blends, %zu blends (none: every delay 0)", delay.size(), blends.size());
+    std::vector<int> first(1, 0), channel, delays;
     std::vector<double> weight;
     for (size_t b = 0; b < blends.size(); b++) {
+        if (!delay.empty() && delay[b].size() != blends[b].size()) return format("SetBatchBlends: blend %zu has %zu terms and %zu delays", b, blends[b].size(), delay[b].size());
         if (blends[b].empty() || blends[b].size() > GDG_BLEND_MAX_TERMS) return format("SetBatchBlends: blend %zu has %zu terms; 1 to %d", b, blends[b].size(), GDG_BLEND_MAX_TERMS);
         for (size_t k = 0; k < blends[b].size(); k++) {
             if (blends[b][k].first < 0 || blends[b][k].first >= nChannels_)
                 return format("SetBatchBlends: blend %zu, term %zu names channel %d; the job has channels 0 to %d", b, k, blends[b][k].first, nChannels_ - 1);
             if (!std::isfinite(blends[b][k].second)) return format("SetBatchBlends: blend %zu, term %zu: the weight is not finite", b, k);
+            if (!delay.empty() && (delay[b][k] < 0 || delay[b][k] > GDG_BLEND_MAX_DELAY))
+                return format("SetBatchBlends: blend %zu, term %zu: delay = %d; 0 to %d samples", b, k, delay[b][k], GDG_BLEND_MAX_DELAY);
             channel.push_back(blends[b][k].first);
             weight.push_back(blends[b][k].second);
+            if (!delay.empty()) delays.push_back(delay[b][k]);
         }
         first.push_back((int)channel.size());
         if (!gain.empty() && !std::isfinite(gain[b])) return format("SetBatchBlends: blend %zu: the gain is not finite", b);
@@ -995,6 +1000,7 @@ Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double
     blendFirst_.swap(first);
     blendChannel_.swap(channel);
     blendWeight_.swap(weight);
+    blendDelay_.swap(delays);
     blendGain_ = gain.empty() ? std::vector<double>(blends.size(), 1.0) : gain;
     return "";
 }
@@ -1002,7 +1008,8 @@ Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double
 /* one shard: job channel numbers are the context's; more shards: no blend is in force, and every context is told so */
 int Engine::applyBlends(gdg_ctx *ctx) {
     if (blendFirst_.empty()) return gdg_batch_set_blends(ctx, 0, nullptr, nullptr, nullptr, nullptr);
-    return gdg_batch_set_blends(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendGain_.data());
+    if (blendDelay_.empty()) return gdg_batch_set_blends(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendGain_.data());
+    return gdg_batch_set_blends_delayed(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendDelay_.data(), blendGain_.data());
 }
 
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
@@ -1841,15 +1848,20 @@ const char *gdgh_engine_set_batch_trim(void *e, const double *chain_gain, int n,
 }
 /* the blends in gdg_batch_set_blends' CSR form, job channel numbers; n_blends == 0: off; gain == NULL: every gain 1.  A `first` that does
  * not start at 0 or descends is refused here: the lists below are cut by it */
-const char *gdgh_engine_set_batch_blends(void *e, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
+const char *gdgh_engine_set_batch_blends_delayed(void *e, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const double *gain) {
     std::vector<std::vector<std::pair<int, double>>> blends;
+    std::vector<std::vector<int>> delays;
     if (n_blends < 0 || (n_blends > 0 && (!first || !channel || !weight || first[0] != 0))) return ret("SetBatchBlends: n_blends >= 0, and first (from 0 on), channel and weight");
     for (int b = 0; b < n_blends; b++) {
         if (first[b + 1] < first[b]) return ret(format("SetBatchBlends: blend %d: first descends from %d to %d", b, first[b], first[b + 1]));
         blends.emplace_back();
         for (int k = first[b]; k < first[b + 1]; k++) blends.back().emplace_back(channel[k], weight[k]);
+        if (delay) delays.emplace_back(delay + first[b], delay + first[b + 1]);
     }
-    return ret(((Engine *)e)->SetBatchBlends(blends, gain && n_blends > 0 ? std::vector<double>(gain, gain + n_blends) : std::vector<double>()));
+    return ret(((Engine *)e)->SetBatchBlends(blends, gain && n_blends > 0 ? std::vector<double>(gain, gain + n_blends) : std::vector<double>(), delays));
+}
+const char *gdgh_engine_set_batch_blends(void *e, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
+    return gdgh_engine_set_batch_blends_delayed(e, n_blends, first, channel, weight, nullptr, gain);
 }
 int gdgh_engine_batch_blends(void *e) { return ((Engine *)e)->BatchBlends(); }
 void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchReport(on != 0); }

@@ -292,7 +292,8 @@ public:
      * holds its own channels only, so a term on another shard's device cannot be summed there, and the library's shard calls refuse blends.
      * BatchRun of a one-shard engine with blends is the library's plain gdg_batch_run.  A refused list leaves the one in force; an empty
      * list: off. */
-    Error SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain = {});
+    Error SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain = {},
+                         const std::vector<std::vector<int>> &delay = {});      /* delay[b][k]: term k of blend b reads its row that many samples back (gdg_batch_set_blends_delayed); none: every delay 0 */
     int BatchBlends() const { return blendFirst_.empty() ? 0 : (int)blendFirst_.size() - 1; }
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
@@ -361,6 +362,7 @@ private:
     int applyTrim(int shard, gdg_ctx *ctx);                /* the shard's slice of it onto its context: a gdg_* status */
     std::vector<int> blendFirst_, blendChannel_;           /* SetBatchBlends, in gdg_batch_set_blends' CSR form; blendFirst_ empty: off */
     std::vector<double> blendWeight_, blendGain_;
+    std::vector<int> blendDelay_;                          /* one per term, or empty: every delay 0 and the list goes through gdg_batch_set_blends */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

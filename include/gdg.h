@@ -1060,8 +1060,8 @@ int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_
  * BLEND: no reference counterpart.  A re-amping job renders one take through many rigs (gdg_batch_set_sources), and what its user does with
  * the renders is blend a few of them: two amps at 60/40, two microphone positions of one cabinet, a clean rig under a driven one.  A blend
  * output is a weighted sum of chain outputs, made from the float64 rows as they lie on the device -- before any of them is truncated to 16
- * or 24 bits -- and written as one more port behind the metronome's.  Stateless per sample: no place in the checkpoint, no rule for
- * windows or slices, the same bits however the job is cut, no change to the container version.
+ * or 24 bits -- and written as one more port behind the metronome's.  Stateless per sample while every delay is 0 (DELAYS, below): no place
+ * in the checkpoint, no rule for windows or slices, the same bits however the job is cut, no change to the container version.
  *   gdg_batch_set_blends(ctx, n_blends, first, channel, weight, gain)
  *                                                      the blends in CSR form: blend b has the terms k = first[b] .. first[b + 1] - 1,
  *                                                      term k is channel[k] of THIS context with weight[k]; first has n_blends + 1
@@ -1108,15 +1108,69 @@ int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_
  *   gdg_blend_rows_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, d_out, out_stride)
  *                                                      device rows, 8-byte aligned: row r at d_rows + r * row_stride, blend b's sums at
  *                                                      d_out + b * out_stride (strides in samples, >= samples); d_out overlaps no row
+ * DELAYS: the alignment records say how far apart two renders of one take lie (ALIGNMENT, above); a delay per term lines them up before
+ * they are summed.  Term k of a blend has an integer delay d_k, 0 <= d_k <= GDG_BLEND_MAX_DELAY (4096: the alignment measures lags within
+ * +-2048, so two terms of one blend lie at most 4096 samples apart).  With i the sample index in the job:
+ *   x_k[i] = x[c_k][i - d_k]       for i >= d_k
+ *   x_k[i] = +0.0                  for i <  d_k
+ *   s = w_0 * x_0[i]
+ *   s = s + (w_k * x_k[i])         in term order
+ * every product and every add rounded on its own exactly as above (0 * +0.0 is still a product: a negative weight in front of the job gives
+ * -0.0).  The port's length stays the job's length: the last d_k samples of a delayed term are never written to any port.  Records, dither
+ * ports, output gains and the alignment list are those of blend ports without delays.
+ * Known answer: two terms on one row x with d = {0, 1} and weights {1, -1} give the first difference of the row: s[0] = x[0] - (+0.0) =
+ * x[0], s[i] = x[i] - x[i - 1].
+ *   gdg_batch_set_blends_delayed(ctx, n_blends, first, channel, weight, delay, gain)
+ *                                                      gdg_batch_set_blends with one delay per term; delay == NULL: every delay 0, and
+ *                                                      gdg_batch_set_blends is this call with delay == NULL.  A delay outside the range
+ *                                                      is GDG_ERR_INVALID, names blend and term, and leaves the list in force unchanged.
+ *   gdg_batch_blend_max_delay(ctx)                     the largest delay in force; 0: the blends are stateless
+ * With every delay 0 no buffer, launch, upload byte or output byte differs from gdg_batch_set_blends.  With a delay in force the context
+ * keeps the last GDG_BLEND_MAX_DELAY samples of its N chain rows from step to step and from slice to slice: N * 4096 doubles, counted by
+ * stat_batch_device_kib, zeroed when a job begins (gdg_batch_run, the first slice after gdg_batch_stream_open), freed when the delays go back
+ * to zero or the blends go off.  The bytes do not depend on the window or on how the job is sliced.
+ * That history is not in the version-1 checkpoint container: while a non-zero delay is in force gdg_batch_stream_checkpoint_size,
+ * gdg_batch_stream_checkpoint, gdg_batch_stream_resume and the shard forms return GDG_ERR_UNSUPPORTED and write nothing.  With every delay
+ * 0 a checkpoint is what it was.
+ * The delayed sum on its own, both blocking, refusing what gdg_blend_rows refuses and a delay out of range:
+ *   gdg_blend_rows_delayed(ctx, rows, n_rows, samples, n_blends, first, channel, weight, delay, history, out)
+ *                                                      history: NULL (zeros in front of sample 0) or n_rows pointers to
+ *                                                      GDG_BLEND_MAX_DELAY doubles each: history[r][GDG_BLEND_MAX_DELAY - 1] is sample -1
+ *                                                      of row r.  Read, never written.
+ *   gdg_blend_rows_delayed_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, delay, d_history, hist_stride,
+ *                                 d_out, out_stride)   d_history: NULL or device memory, 8-byte aligned, row r's run at d_history + r *
+ *                                                      hist_stride (hist_stride >= GDG_BLEND_MAX_DELAY); d_out overlaps neither side
+ * The delays from the alignment records -- host only: no context, no device, like gdg_trim_from_true_peak (gdg_last_error(NULL) says what
+ * was refused):
+ *   gdg_blend_delays_from_align(records, ports, blocks, ref, min_coeff, n_blends, first, channel, delay, sign)
+ *                                                      records[ports][blocks] as gdg_batch_align hands them out, ref: the list they were
+ *                                                      measured with; the blends in CSR form, `channel` naming a port; delay and sign:
+ *                                                      one int per term
+ * Per port: the blocks with ref_sq > 0, sq_at_lag > 0 and |corr| / sqrt(ref_sq * sq_at_lag) >= min_coeff (0 <= min_coeff <= 1) count; the
+ * port's lag is the lower median of `lag` over those blocks, its sign the sign of the sum of `corr` over them.  A port with no such block
+ * gets lag 0 and sign +1, and so does a port that is its own reference or is the reference of the others.  Per blend: every term's
+ * channel is measured against one reference port, or is that port; otherwise the call returns GDG_ERR_INVALID, writes nothing and names the
+ * blend.  delay_k = max_j lag_j - lag_k; sign_k is the port's sign: the caller multiplies the weights by it.
  */
 #define GDG_BLEND_MAX_TERMS 32
 #define GDG_BLEND_MAX_BLENDS 1024
+#define GDG_BLEND_MAX_DELAY 4096
 int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const double *gain);
 int gdg_batch_blends(const gdg_ctx *ctx);
 int gdg_blend_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
                    const double *weight, double *const *out);
 int gdg_blend_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
                           const int *channel, const double *weight, double *d_out, size_t out_stride);
+int gdg_batch_set_blends_delayed(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay,
+                                 const double *gain);
+int gdg_batch_blend_max_delay(const gdg_ctx *ctx);
+int gdg_blend_rows_delayed(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                           const double *weight, const int *delay, const double *const *history, double *const *out);
+int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
+                                  const int *channel, const double *weight, const int *delay, const double *d_history, size_t hist_stride,
+                                  double *d_out, size_t out_stride);
+int gdg_blend_delays_from_align(const gdg_block_align *records, int ports, size_t blocks, const int *ref, double min_coeff, int n_blends,
+                                const int *first, const int *channel, int *delay, int *sign);
 
 #ifdef __cplusplus
 
