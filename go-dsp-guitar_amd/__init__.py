@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "gdg_batch_set_trim", "gdg_wave_encode_trim", "gdg_wave_encode_trim_device", "gdg_trim_from_true_peak",
     "gdg_batch_set_blends", "gdg_batch_blends", "gdg_blend_rows", "gdg_blend_rows_device",
     "gdg_batch_set_blends_delayed", "gdg_batch_blend_max_delay", "gdg_blend_rows_delayed", "gdg_blend_rows_delayed_device", "gdg_blend_delays_from_align",
+    "gdg_batch_fit_enable", "gdg_batch_fits", "gdg_batch_fit", "gdg_block_fit_rows", "gdg_block_fit_rows_device", "gdg_blend_weights_from_fit",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -119,6 +120,41 @@ def blend_delays_from_align(records, ref, blends, min_coeff=0.5):
         raise GdgError(rc, lib().gdg_last_error(None).decode())
     cut = lambda v: [[int(x) for x in v[first[b]:first[b + 1]]] for b in range(len(blends))]
     return cut(delay), cut(sign)
+
+
+FIT_MAX_TERMS = 8            # GDG_FIT_MAX_TERMS (include/gdg.h): the terms of one fit
+FIT_MAX_FITS = 256           # GDG_FIT_MAX_FITS: the fits of one list
+FIT_BLOCK = 8192             # the block of a batch call's fit records
+# gdg_block_fit (include/gdg.h): one record of the blend fit, 368 bytes, little-endian, no padding
+FIT_DTYPE = np.dtype([("tt", "<f8"), ("tx", "<f8", (8,)), ("xx", "<f8", (36,)), ("skipped", "<u4"), ("terms", "<u4")])
+assert FIT_DTYPE.itemsize == 368
+
+
+def _fit_csr(fits):
+    """fits = [(target, [ports]), ...] -> first, port, target as int32 arrays, one spare entry behind each so that an empty list has an address"""
+    fits = [(int(t), [int(p) for p in ports]) for t, ports in fits]
+    first = np.zeros(len(fits) + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(ports) for _, ports in fits], dtype=np.int64)
+    port = np.array([p for _, ports in fits for p in ports] + [0], dtype=np.int32)
+    target = np.array([t for t, _ in fits] + [0], dtype=np.int32)
+    return first, port, target
+
+
+def blend_weights_from_fit(records, ridge=0.0):
+    """gdg_blend_weights_from_fit: records [fits, blocks] (FIT_DTYPE, as batch_fit hands them out) -> (weights [fits, 8] float64, residuals
+    [fits] float64): per fit the least-squares weights of its terms against its target -- (G + ridge * mean(diag G) * I) w = b, unpivoted
+    Cholesky in term order -- and the share of the target's energy the fitted blend leaves.  Host arithmetic: no context, no device.
+    GdgError for a silent term or a port used twice with ridge = 0 (the message names the fit)."""
+    rec = np.ascontiguousarray(records, dtype=FIT_DTYPE)
+    if rec.ndim != 2:
+        raise ValueError("records: [fits, blocks]")
+    weight = np.zeros((rec.shape[0], FIT_MAX_TERMS), dtype=np.float64)
+    residual = np.zeros(rec.shape[0], dtype=np.float64)
+    rc = lib().gdg_blend_weights_from_fit(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], float(ridge),
+                                          weight.ctypes.data if weight.size else None, residual.ctypes.data if residual.size else None)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return weight, residual
 
 
 ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
@@ -372,6 +408,12 @@ def lib():
             "gdg_blend_rows_delayed": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp, vp, vp, vp, vp]),
             "gdg_blend_rows_delayed_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]),
             "gdg_blend_delays_from_align": (i32, [vp, i32, C.c_size_t, vp, C.c_double, i32, vp, vp, vp, vp]),
+            "gdg_batch_fit_enable": (i32, [vp, i32, vp, vp, vp]),
+            "gdg_batch_fits": (i32, [vp]),
+            "gdg_batch_fit": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdg_block_fit_rows": (i32, [vp, vp, i32, C.c_size_t, i32, i32, vp, vp, vp, vp]),
+            "gdg_block_fit_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, i32, vp, vp, vp, vp]),
+            "gdg_blend_weights_from_fit": (i32, [vp, i32, C.c_size_t, C.c_double, vp, vp]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1291,6 +1333,54 @@ class Context:
         first, channel, weight = self._blend_csr(blends)
         self._check(lib().gdg_blend_rows_device(self._h, d_rows, row_stride, n_rows, samples, len(blends), first.ctypes.data,
                                                 channel.ctypes.data, weight.ctypes.data, d_out, out_stride))
+
+    # -- the blend fit: Gram records per fit and block, the least-squares weights from them (include/gdg.h, FIT) --------------------------------
+    def batch_fit_enable(self, fits):
+        """From the next batch call on, every batch call keeps the fit records of what it rendered (gdg_batch_fit_enable): fits = a list of
+        (target, [ports]) -- 1 to 8 ports of the call per fit, the chain outputs, master left, master right, metronome and the blend ports
+        in force.  None or an empty list: off.  Configuration: not in a checkpoint, refused while a streamed job is open."""
+        fits = [] if fits is None else list(fits)
+        if not fits:
+            self._check(lib().gdg_batch_fit_enable(self._h, 0, None, None, None))
+            return
+        first, port, target = _fit_csr(fits)
+        self._check(lib().gdg_batch_fit_enable(self._h, len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data))
+
+    def batch_fits(self):
+        """The number of fits in force (gdg_batch_fits)."""
+        return int(lib().gdg_batch_fits(self._h))
+
+    def batch_fit(self):
+        """The [fits][blocks] FIT_DTYPE records of the last completed batch call; GdgError when there are none."""
+        fits, blocks = C.c_int(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_fit(self._h, None, 0, C.byref(fits), C.byref(blocks)))
+        out = np.zeros((fits.value, blocks.value), dtype=FIT_DTYPE)
+        self._check(lib().gdg_batch_fit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(fits), C.byref(blocks)))
+        return out
+
+    def block_fit(self, rows, fits, block=FIT_BLOCK):
+        """gdg_block_fit_rows: rows [n_rows, samples] float64 (or a list of equally long 1-D arrays), fits = (target, [ports]) naming rows ->
+        the [fits][ceil(samples / block)] FIT_DTYPE records."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        fits = list(fits)
+        first, port, target = _fit_csr(fits)
+        out = np.zeros((len(fits), -(-samples // int(block)) if int(block) > 0 else 0), dtype=FIT_DTYPE)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_fit_rows(self._h, ptrs, n, samples, int(block), len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data,
+                                             out.ctypes.data if out.size else None))
+        return out
+
+    def block_fit_device(self, d_rows, row_stride, n_rows, samples, fits, d_records, block=FIT_BLOCK):
+        """gdg_block_fit_rows_device on plain device pointers (ints); returns when the records are written."""
+        fits = list(fits)
+        first, port, target = _fit_csr(fits)
+        self._check(lib().gdg_block_fit_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(block), len(fits), first.ctypes.data, port.ctypes.data,
+                                                    target.ctypes.data, d_records))
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

@@ -123,6 +123,9 @@ struct BatchLoop {
      * left of them, zeros at the job's start; both null while every delay is 0 */
     const int *d_blend_delay;
     double *d_blend_history;
+    /* the blend fits: n_fits entries of the table (blend.h, FitSet) on the host and on the device; 0 = off, and always for a shard */
+    int n_fits;
+    const int *h_fit_table, *d_fit_table;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -162,7 +165,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; };
+    struct Step { size_t off; int w; ReportSections sec; FitSection fit; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -174,7 +177,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {} });
+        steps.push_back({ off, w, {}, {} });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
@@ -187,7 +190,10 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
     };
     const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NR;
-    for (size_t i = 0; i < steps.size(); i++) steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
+    for (size_t i = 0; i < steps.size(); i++) {
+        steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
+        steps[i].fit = fit_section(steps[i].sec.end, (size_t)p.n_fits, (size_t)steps[i].w);      /* behind the last of them: [fits][w] */
+    }
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
     std::vector<size_t> filed[REPORT_KINDS];
@@ -226,6 +232,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         }
         for (int k = 0; k < REPORT_KINDS; k++)                               /* the last piece brought the step's sections: filed under the step's blocks */
             if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
+        if (p.n_fits) fit_file(ctx, src + steps[i].fit.at, (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -293,6 +300,9 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 HIP_TRY(ctx, gdg_launch_block_true_peak(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, true_peak_table(), tp, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_true_peak(d_metro, ws, 1u, (size_t)wb, true_peak_table(), tp + (size_t)N * w, ctx->stream));
             }
+            if (p.n_fits)                                                    /* the fits' inner products of the same rows, the blends' among them */
+                HIP_TRY(ctx, gdg_launch_block_fit(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_fit_table, p.d_fit_table, (unsigned)p.n_fits,
+                                                  enc + steps[i].fit.at, ctx->stream));
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: the trimmed siblings of either; `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
@@ -328,7 +338,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = steps[i].sec.end;
+        const size_t down = steps[i].fit.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -529,6 +539,25 @@ int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int
 int gdg_batch_blends(const gdg_ctx *ctx) { return ctx ? ctx->blend.count() : 0; }
 int gdg_batch_blend_max_delay(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_delay() : 0; }
 
+/* the blend fits: validated whole before the list replaces the one in force (blend.h); the ports' upper bound is the job's, checked when one is described */
+int gdg_batch_fit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *port, const int *target) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "batch fit: a streamed batch run is open on this context; its fits hold until gdg_batch_stream_close");
+    const int rc = fit_list_check(ctx, "batch fit", n_fits, first, port, target, -1);      /* the ports' upper bound is the job's */
+    if (rc != GDG_OK) return rc;
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    if (n_fits != ctx->fit.count()) {
+        /* another count: the download halves are made anew by the next batch call, at the size of a context that was always configured like
+         * this one -- whatever still reads them has to be done first -- and off, the table goes as well */
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i : { (int)BATCH_ENCODED, (int)BATCH_FIT_TABLE }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    }
+    ctx->fit.table = gdg_fit_table(n_fits, first, port, target);
+    return GDG_OK;
+}
+
+int gdg_batch_fits(const gdg_ctx *ctx) { return ctx ? ctx->fit.count() : 0; }
+
 /* the master cursor belongs to gdg_batch_finish_master_slice, which is no part of an open job: it may be set while one is open */
 int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
     if (!ctx) return GDG_ERR_INVALID;
@@ -539,6 +568,10 @@ int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
 /* a shard's rows are its own channels' and a blend's terms may live on two devices: neither is settled, so the shard calls refuse (include/gdg.h) */
 #define BLENDS_REFUSED(ctx, what) \
     fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d blends are in force on this context (gdg_batch_set_blends); a sharded job cannot write blend outputs yet", what, (ctx)->blend.count())
+
+/* ... and a fit's ports are rows of the one-device window: the same refusal */
+#define FITS_REFUSED(ctx, what) \
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d fits are in force on this context (gdg_batch_fit_enable); a sharded job cannot collect fit records yet", what, (ctx)->fit.count())
 
 #define SHARD_PORTS " (a shard: its N inputs, its N outputs, metronome, left, right)"
 static int check_meter_ports(gdg_ctx *ctx, const gdg_batch_options *opt, const char *note) {
@@ -570,6 +603,16 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
     if (n_blends && ctx->dither_mode != 0 && !gdg_dither_ports_ok(ctx->dither_port_base, n_inputs + 3 + n_blends))
         return fail(ctx, GDG_ERR_INVALID, "blends: the dither's port_base %u + %d channels + 3 + %d blends reaches the job-wide ports from 0x%x on", ctx->dither_port_base,
                     n_inputs, n_blends, GDG_DITHER_PORT_MASTER_LEFT);
+    if (!shard && ctx->fit.count()) {                                            /* the fits' ports against this call's: the shard calls refuse fits before they come here */
+        int term = -1;
+        const int f = ctx->fit.first_outside(n_inputs + 3 + n_blends, &term);
+        if (f >= 0 && term < 0)
+            return fail(ctx, GDG_ERR_INVALID, "batch fit: fit %d has the target port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", f, ctx->fit.target(f),
+                        n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
+        if (f >= 0)
+            return fail(ctx, GDG_ERR_INVALID, "batch fit: fit %d, term %d names port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", f, term, ctx->fit.port(f, term),
+                        n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
+    }
     int rc;
     if (meters_at_open && (rc = check_meter_ports(ctx, opt, shard ? SHARD_PORTS : "")) != GDG_OK) return rc;
     std::vector<size_t> n_out((size_t)n_inputs, 0);
@@ -632,6 +675,7 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
 int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t job_samples,
                                 int run_metronome, size_t *samples) {
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
+    if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
     if (ctx && opt && opt->metronome_to_master)
         return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_open_shard: metronome_to_master must be 0 -- a shard's master mix is a partial sum; pass the metronome's "
@@ -693,6 +737,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* the blends in force (never a shard's): NR rows of the window leave the device encoded, and every record kind has NR ports */
     const int n_blends = sharded ? 0 : ctx->blend.count(), NR = NO + n_blends;
     report_begin(ctx, sharded ? N + 1 : NR, (size_t)blocks, true, n_blends);
+    const int n_fits = sharded ? 0 : ctx->fit.count();                           /* never a shard's: its calls refuse them */
+    if (n_fits) fit_begin(ctx, (size_t)blocks);
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -717,7 +763,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
-                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W);
+                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + fit_room((size_t)n_fits, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -887,7 +933,17 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr };
+        /* the fits in force: their table goes up on the context's stream, ahead of everything the slice enqueues there; it lives as long as
+         * the setting, so nothing waits here */
+        if (n_fits) {
+            int *d_table = nullptr;
+            if ((r = batch_buffer(ctx, BATCH_FIT_TABLE, ctx->fit.table.size() * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->fit.table.data(), ctx->fit.table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            loop.n_fits = n_fits;
+            loop.h_fit_table = ctx->fit.table.data();
+            loop.d_fit_table = d_table;
+        }
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
             if (!ctx->d_trim && hipMalloc((void **)&ctx->d_trim, (size_t)NO * sizeof(double)) != hipSuccess)
@@ -963,6 +1019,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 }
 
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
+    if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_step_shard");
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
 
@@ -986,6 +1043,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
     if (job.length == 0) {                                                       /* every output has 0 samples */
         ctx->batch_up_bytes = ctx->batch_resampled = 0;
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
+        if (!shard) fit_begin(ctx, 0);
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
@@ -1005,6 +1063,7 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
                         const gdg_batch_shard_out *shard) {
     if (!shard) return GDG_ERR_INVALID;
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
+    if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_run_shard");
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
      * metronome track of the shard that ran it).  A set flag here would be silently dropped -- refuse it instead. */
     if (ctx && opt && opt->metronome_to_master)

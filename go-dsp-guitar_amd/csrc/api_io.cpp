@@ -896,6 +896,113 @@ int gdg_blend_delays_from_align(const gdg_block_align *records, int ports, size_
     return GDG_ERR_INVALID;
 }
 
+/* ---- the blend fit (include/gdg.h, FIT; the kernel: fit_kernels.h in io.hip; the list's validation and the planner: blend.h; the batch calls fill it: api_batch.cpp) ---- */
+static_assert(sizeof(gdg_block_fit) == FIT_RECORD_BYTES && offsetof(gdg_block_fit, tx) == 8 && offsetof(gdg_block_fit, xx) == 72 && offsetof(gdg_block_fit, skipped) == 360 &&
+              offsetof(gdg_block_fit, terms) == 364, "gdg_block_fit: 368 bytes, no padding (report_sections.h)");
+static_assert(sizeof(gdg_blend_fit_rec) == sizeof(gdg_block_fit) && offsetof(gdg_blend_fit_rec, tx) == offsetof(gdg_block_fit, tx) &&
+              offsetof(gdg_blend_fit_rec, xx) == offsetof(gdg_block_fit, xx) && offsetof(gdg_blend_fit_rec, terms) == offsetof(gdg_block_fit, terms), "blend.h restates gdg_block_fit");
+
+/* A list of fits held against gdg_fit_check, refused in the words of the call `what`: the ONE place they are worded.  n_rows >= 0: the ports
+ * name rows 0 .. n_rows - 1 (the stand-alone forms); n_rows < 0: ports of a job to come, whose count is checked when it is described. */
+int fit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, int n_rows) {
+    int f = -1, k = -1;
+    switch (gdg_fit_check(n_fits, first, port, target, n_rows, &f, &k)) {
+    case FIT_OK: return GDG_OK;
+    case FIT_COUNT: return fail(ctx, GDG_ERR_INVALID, "%s: %d fits; 0 (off) to %d", what, n_fits, GDG_FIT_MAX_FITS);
+    case FIT_NULL: return fail(ctx, GDG_ERR_INVALID, "%s: %d fits need first, port and target", what, n_fits);
+    case FIT_FIRST: return fail(ctx, GDG_ERR_INVALID, "%s: fit %d: first[%d] = %d, first[%d] = %d; the offsets start at 0 and never descend", what, f, f, first[f], f + 1, first[f + 1]);
+    case FIT_TERMS: return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has %d terms; 1 to %d", what, f, first[f + 1] - first[f], GDG_FIT_MAX_TERMS);
+    case FIT_PORT:
+        if (n_rows >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: fit %d, term %d names row %d of %d", what, f, k, port[first[f] + k], n_rows);
+        return fail(ctx, GDG_ERR_INVALID, "%s: fit %d, term %d names port %d; ports start at 0", what, f, k, port[first[f] + k]);
+    default:
+        if (n_rows >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has the target row %d of %d", what, f, target[f], n_rows);
+        return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has the target port %d; ports start at 0", what, f, target[f]);
+    }
+}
+
+static int block_fit_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port, const int *target, size_t *blocks) {
+    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "block fit: %d rows (at least 1)", n_rows);
+    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block fit: blocks of %d samples (at least 1)", block);
+    const int rc = fit_list_check(ctx, "block fit", n_fits, first, port, target, n_rows);
+    if (rc != GDG_OK) return rc;
+    *blocks = (samples + (size_t)block - 1) / (size_t)block;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block fit: %zu blocks per row are too many for one launch", *blocks);
+    return GDG_OK;
+}
+
+/* the table is the caller's host memory: it goes up, the kernel runs, and the call returns when the records are written */
+int gdg_block_fit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
+                              const int *port, const int *target, gdg_block_fit *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_fit_check(ctx, n_rows, samples, block, n_fits, first, port, target, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_fits == 0 || samples == 0) return GDG_OK;
+    if (!d_rows || !d_records) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block fit: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block fit: rows and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    const std::vector<int> table = gdg_fit_table(n_fits, first, port, target);
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, table.size() * sizeof(int)));
+    hipError_t e = hipMemcpyAsync(d, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        e = gdg_launch_block_fit(d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, table.data(), static_cast<const int *>(d), (unsigned)n_fits, d_records, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block fit: %s", hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block fit: %s", hipGetErrorString(w));
+    return GDG_OK;
+}
+
+int gdg_block_fit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port,
+                       const int *target, gdg_block_fit *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_fit_check(ctx, n_rows, samples, block, n_fits, first, port, target, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_fits == 0 || samples == 0) return GDG_OK;
+    if (!rows || !records) return GDG_ERR_INVALID;
+    return rows_round_trip(ctx, "block fit", rows, n_rows, samples, records, (size_t)n_fits * blocks * sizeof(gdg_block_fit), [&](const double *d_rows, void *d_out) {
+        return gdg_block_fit_rows_device(ctx, d_rows, samples, n_rows, samples, block, n_fits, first, port, target, static_cast<gdg_block_fit *>(d_out));
+    });
+}
+
+/* the getter: the fits' own store, by the four kinds' rule and in their words */
+int gdg_batch_fit(gdg_ctx *ctx, gdg_block_fit *records, size_t capacity, int *fits, size_t *blocks) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const gdg_ctx::FitRecords &F = ctx->fit_rec;
+    if (!F.valid)
+        return fail(ctx, GDG_ERR_INVALID, "no fit records: the last batch call of this context %s", ctx->fit.count()
+                    ? "has not completed, was a master finish, or none has run since gdg_batch_fit_enable" : "ran without them (gdg_batch_fit_enable comes before the call)");
+    if (fits) *fits = F.fits;
+    if (blocks) *blocks = F.blocks;
+    if (!records) return GDG_OK;
+    const size_t n = (size_t)F.fits * F.blocks;
+    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "fit: room for %zu records, the call has %d fits x %zu blocks = %zu", capacity, F.fits, F.blocks, n);
+    if (n) memcpy(records, F.store.data(), F.store.size());
+    return GDG_OK;
+}
+
+/* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
+int gdg_blend_weights_from_fit(const gdg_block_fit *records, int n_fits, size_t blocks, double ridge, double *weight, double *residual) {
+    int bad = -1;
+    char msg[240];
+    switch (gdg_blend_plan_weights(reinterpret_cast<const gdg_blend_fit_rec *>(records), n_fits, blocks, ridge, weight, residual, &bad)) {
+    case FIT_PLAN_OK: return GDG_OK;
+    case FIT_PLAN_TERMS: snprintf(msg, sizeof msg, "blend weights from fit: fit %d: its records do not agree on a term count in 1 to %d", bad, GDG_FIT_MAX_TERMS); break;
+    case FIT_PLAN_PIVOT:
+        snprintf(msg, sizeof msg, "blend weights from fit: fit %d: a pivot at or below K * 2^-52 * max(diag G) -- a silent term, or a port used twice with ridge = 0", bad);
+        break;
+    default: snprintf(msg, sizeof msg, "blend weights from fit: %d fits (0 to %d) of %zu blocks (at least 1), ridge = %g (finite, >= 0); records, weight and residual are needed", n_fits, GDG_FIT_MAX_FITS, blocks, ridge); break;
+    }
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
+}
+
 /* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */
 static_assert(sizeof(gdg_block_true_peak) == 16 && offsetof(gdg_block_true_peak, position) == 8 && offsetof(gdg_block_true_peak, overs) == 12,
               "gdg_block_true_peak: 16 bytes, no padding");

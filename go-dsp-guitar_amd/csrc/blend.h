@@ -4,7 +4,9 @@
  * delayed by a whole number of samples (gdg_batch_set_blends_delayed).  Here: the two rounded operations as __host__ __device__ inlines --
  * the kernels of blend_kernels.h use them, and so can a stand-alone host program (tests/native/blend_check.cpp, blend_delay_check.cpp) --
  * the validation of a blend list in its CSR form, the rule by which a list replaces the one in force, the sum on the host, and the planner
- * that turns alignment records into delays and signs (gdg_blend_delays_from_align).  No HIP header is needed to compile this file.
+ * that turns alignment records into delays and signs (gdg_blend_delays_from_align); and, for the blend fit (include/gdg.h, FIT), the
+ * validation of a list of fits, the table a launch reads, and the planner that turns fit records into weights (gdg_blend_weights_from_fit;
+ * tests/native/fit_plan_check.cpp).  No HIP header is needed to compile this file.
  */
 #ifndef GDG_BLEND_H
 #define GDG_BLEND_H
@@ -266,6 +268,153 @@ static inline int gdg_blend_plan_delays(const gdg_blend_align_rec *records, int 
         for (int k = first[b]; k < first[b + 1]; k++) delay[k] = most - lag[k - first[b]];
     }
     return BLEND_PLAN_OK;
+}
+
+/* ---- the blend fit (include/gdg.h, FIT): a list of fits, and the weights from their records (gdg_blend_weights_from_fit) ---------------- */
+#ifndef GDG_FIT_MAX_TERMS
+#define GDG_FIT_MAX_TERMS 8
+#define GDG_FIT_MAX_FITS 256
+#endif
+#define GDG_FIT_TABLE_INTS (2 + GDG_FIT_MAX_TERMS)                           /* a fit as the kernel reads it: target | terms | port[8] */
+
+enum {
+    FIT_OK = 0,
+    FIT_COUNT = 1,                             /* n_fits outside 0 .. GDG_FIT_MAX_FITS */
+    FIT_NULL = 2,                              /* a list is missing */
+    FIT_FIRST = 3,                             /* first[0] != 0, or first[f + 1] < first[f]: *fit = f */
+    FIT_TERMS = 4,                             /* fit f has no term or more than GDG_FIT_MAX_TERMS */
+    FIT_PORT = 5,                              /* term `term` of fit f names a port outside [0, n_ports) */
+    FIT_TARGET = 6                             /* fit f's target lies outside [0, n_ports) */
+};
+
+/* The list in its CSR form: fit f has the terms port[first[f] .. first[f + 1]) and the target target[f].  n_ports < 0: the port count is
+ * not known yet (it is the job's: N + 3 + B) and only negative ports are refused.  *fit, *term: the first offender, -1 where none is named. */
+static inline int gdg_fit_check(int n_fits, const int *first, const int *port, const int *target, int n_ports, int *fit, int *term) {
+    *fit = *term = -1;
+    if (n_fits < 0 || n_fits > GDG_FIT_MAX_FITS) return FIT_COUNT;
+    if (n_fits == 0) return FIT_OK;
+    if (!first || !port || !target) return FIT_NULL;
+    if (first[0] != 0) { *fit = 0; return FIT_FIRST; }
+    for (int f = 0; f < n_fits; f++) {                                       /* the offsets first: nothing is read through a bad one */
+        *fit = f;
+        if (first[f + 1] < first[f]) return FIT_FIRST;
+        if (first[f + 1] == first[f] || first[f + 1] - first[f] > GDG_FIT_MAX_TERMS) return FIT_TERMS;
+    }
+    for (int f = 0; f < n_fits; f++) {
+        *fit = f;
+        if (target[f] < 0 || (n_ports >= 0 && target[f] >= n_ports)) return FIT_TARGET;
+        for (int k = first[f]; k < first[f + 1]; k++)
+            if (port[k] < 0 || (n_ports >= 0 && port[k] >= n_ports)) { *term = k - first[f]; return FIT_PORT; }
+    }
+    *fit = -1;
+    return FIT_OK;
+}
+
+/* the list in force, as the table a launch reads: [fits][target | terms | port[8]], the ports behind a fit's last term 0 */
+struct FitSet {
+    std::vector<int> table;
+    int count() const { return (int)(table.size() / GDG_FIT_TABLE_INTS); }
+    int target(int f) const { return table[(size_t)f * GDG_FIT_TABLE_INTS]; }
+    int terms(int f) const { return table[(size_t)f * GDG_FIT_TABLE_INTS + 1]; }
+    int port(int f, int k) const { return table[(size_t)f * GDG_FIT_TABLE_INTS + 2 + (size_t)k]; }
+    /* the first fit that names a port outside [0, n_ports): -1 = none; *term: the term, -1 = the target */
+    int first_outside(int n_ports, int *term) const {
+        for (int f = 0; f < count(); f++) {
+            *term = -1;
+            if (target(f) >= n_ports) return f;
+            for (int k = 0; k < terms(f); k++) if (port(f, k) >= n_ports) { *term = k; return f; }
+        }
+        return -1;
+    }
+};
+
+/* a checked list as a table */
+static inline std::vector<int> gdg_fit_table(int n_fits, const int *first, const int *port, const int *target) {
+    std::vector<int> t((size_t)n_fits * GDG_FIT_TABLE_INTS, 0);
+    for (int f = 0; f < n_fits; f++) {
+        int *e = &t[(size_t)f * GDG_FIT_TABLE_INTS];
+        e[0] = target[f];
+        e[1] = first[f + 1] - first[f];
+        for (int k = first[f]; k < first[f + 1]; k++) e[2 + k - first[f]] = port[k];
+    }
+    return t;
+}
+
+struct gdg_blend_fit_rec { double tt, tx[GDG_FIT_MAX_TERMS], xx[GDG_FIT_MAX_TERMS * (GDG_FIT_MAX_TERMS + 1) / 2]; uint32_t skipped, terms; };      /* gdg_block_fit of include/gdg.h */
+
+enum {
+    FIT_PLAN_OK = 0,
+    FIT_PLAN_ARGS = 1,                         /* a list is missing, a count is out of range, no block, ridge is negative or not finite */
+    FIT_PLAN_TERMS = 2,                        /* the records of *fit do not agree on a term count in 1 .. GDG_FIT_MAX_TERMS */
+    FIT_PLAN_PIVOT = 3                         /* the factorisation of *fit met a pivot at or below the bound: a silent term, or a port twice without a ridge */
+};
+
+/* records[n_fits][blocks].  Per fit: the blocks' sums added in block order -- T, b[K], G[K][K] --, (G + ridge * mean(diag G) * I) w = b by
+ * an unpivoted Cholesky factorisation in term order, residual = max(0, T - 2 w.b + w'Gw) / T (0 where T == 0).  Every fit is solved before
+ * weight[n_fits][8] and residual[n_fits] are written; *fit: the offender. */
+static inline int gdg_blend_plan_weights(const gdg_blend_fit_rec *records, int n_fits, size_t blocks, double ridge, double *weight, double *residual, int *fit) {
+    *fit = -1;
+    if (n_fits < 0 || n_fits > GDG_FIT_MAX_FITS || !(ridge >= 0.0) || !isfinite(ridge)) return FIT_PLAN_ARGS;
+    if (n_fits == 0) return FIT_PLAN_OK;
+    if (!records || !weight || !residual || blocks == 0) return FIT_PLAN_ARGS;
+    constexpr int M = GDG_FIT_MAX_TERMS;
+    std::vector<double> w_all((size_t)n_fits * M, 0.0), res_all((size_t)n_fits, 0.0);
+    for (int f = 0; f < n_fits; f++) {
+        *fit = f;
+        const gdg_blend_fit_rec *rec = records + (size_t)f * blocks;
+        const int K = (int)rec[0].terms;
+        if (K < 1 || K > M) return FIT_PLAN_TERMS;
+        double T = 0.0, b[M], G[M][M];
+        for (int j = 0; j < K; j++) { b[j] = 0.0; for (int k = 0; k < K; k++) G[j][k] = 0.0; }
+        for (size_t q = 0; q < blocks; q++) {
+            if ((int)rec[q].terms != K) return FIT_PLAN_TERMS;
+            T += rec[q].tt;
+            for (int j = 0; j < K; j++) {
+                b[j] += rec[q].tx[j];
+                for (int k = 0; k <= j; k++) G[j][k] += rec[q].xx[j * (j + 1) / 2 + k];
+            }
+        }
+        for (int j = 0; j < K; j++) for (int k = j + 1; k < K; k++) G[j][k] = G[k][j];
+        double trace = 0.0, most = 0.0;
+        for (int j = 0; j < K; j++) { trace += G[j][j]; if (G[j][j] > most) most = G[j][j]; }
+        const double shift = ridge * (trace / (double)K), least = (double)K * 2.220446049250313e-16 * most;      /* K * 2^-52 * max(diag G) */
+        double Lo[M][M];
+        for (int j = 0; j < K; j++) {
+            double d = G[j][j] + shift;
+            for (int k = 0; k < j; k++) d -= Lo[j][k] * Lo[j][k];
+            if (!(d > least)) return FIT_PLAN_PIVOT;
+            Lo[j][j] = sqrt(d);
+            for (int i = j + 1; i < K; i++) {
+                double s = G[i][j];
+                for (int k = 0; k < j; k++) s -= Lo[i][k] * Lo[j][k];
+                Lo[i][j] = s / Lo[j][j];
+            }
+        }
+        double y[M], *w = &w_all[(size_t)f * M];
+        for (int j = 0; j < K; j++) {                                        /* L y = b, then L' w = y */
+            double s = b[j];
+            for (int k = 0; k < j; k++) s -= Lo[j][k] * y[k];
+            y[j] = s / Lo[j][j];
+        }
+        for (int j = K - 1; j >= 0; j--) {
+            double s = y[j];
+            for (int k = j + 1; k < K; k++) s -= Lo[k][j] * w[k];
+            w[j] = s / Lo[j][j];
+        }
+        double wb = 0.0, wGw = 0.0;
+        for (int j = 0; j < K; j++) {
+            wb += w[j] * b[j];
+            double row = 0.0;
+            for (int k = 0; k < K; k++) row += G[j][k] * w[k];
+            wGw += w[j] * row;
+        }
+        const double left = T - 2.0 * wb + wGw;
+        res_all[(size_t)f] = T == 0.0 ? 0.0 : (left > 0.0 ? left : 0.0) / T;
+    }
+    *fit = -1;
+    memcpy(weight, w_all.data(), w_all.size() * sizeof(double));
+    memcpy(residual, res_all.data(), res_all.size() * sizeof(double));
+    return FIT_PLAN_OK;
 }
 
 #endif

@@ -368,6 +368,11 @@ hipError_t gdg_launch_blend_rows_delayed(const double *d_rows, size_t row_stride
                                          hipStream_t s);
 /* the last GDG_BLEND_MAX_DELAY of `samples` samples (samples >= GDG_BLEND_MAX_DELAY) of rows 0 .. n_rows - 1 into d_history[n_rows][GDG_BLEND_MAX_DELAY] */
 hipError_t gdg_launch_blend_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
+/* the blend fit's records (include/gdg.h, FIT; io.hip, fit_kernels.h): per fit and block of `block` samples (the last of a row may be short)
+ * one gdg_block_fit, d_records[n_fits][ceil(samples / block)].  A fit is target | terms | port[8] (blend.h, FitSet): h_table is the host's copy
+ * of the device's d_table, held against n_rows before anything is launched. */
+hipError_t gdg_launch_block_fit(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, const int *h_table, const int *d_table,
+                                unsigned n_fits, void *d_records, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

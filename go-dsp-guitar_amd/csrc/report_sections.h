@@ -46,4 +46,22 @@ static inline size_t report_room(const ReportLive &live, size_t rows, size_t W) 
     return room;
 }
 
+/* The blend fit's records (include/gdg.h, FIT) are no fifth kind: their rows are the call's fits, not its ports.  A step of the block loop
+ * sends them down behind the last live kind's section -- behind its rows when no kind is live -- from the next 16 bytes on: [fits][w]
+ * records of 368 bytes.  No fit: no byte (at = end = `end`).  The finish calls never carry them. */
+enum { FIT_RECORD_BYTES = 368 };
+struct FitSection { size_t at, bytes, end; };
+
+static inline FitSection fit_section(size_t end, size_t fits, size_t w) {
+    FitSection s = { end, 0, end };
+    if (!fits) return s;
+    s.at = (end + 15) & ~(size_t)15;
+    s.bytes = fits * w * FIT_RECORD_BYTES;
+    s.end = s.at + s.bytes;
+    return s;
+}
+
+/* ... and what a half holds for them for a window of W blocks, beside report_room */
+static inline size_t fit_room(size_t fits, size_t W) { return fits ? 16 + fits * W * FIT_RECORD_BYTES : 0; }
+
 #endif

@@ -2234,3 +2234,221 @@ func BlendDelaysFromAlign(records [][]BlockAlign, ref []int, minCoeff float64, b
 	}
 	return delay, sign, nil
 }
+
+// BlockFit: one record of the blend fit (gdg_block_fit, 368 bytes in this layout): for one fit and one block the inner products a
+// least-squares fit of blend weights needs.  Tt = sum t^2 of the target; Tx[k] = sum t*x_k; Xx holds the lower triangle of the terms' Gram
+// matrix by rows, Xx[j*(j+1)/2+k] = sum x_j*x_k for k <= j.  Entries of terms >= Terms are 0.  Skipped counts the sample indices left out
+// of every sum because one of the fit's rows was NaN or +-inf there.
+type BlockFit struct {
+	Tt      float64
+	Tx      [8]float64
+	Xx      [36]float64
+	Skipped uint32
+	Terms   uint32
+}
+
+// Fit: one fit of a list: the target port and 1 to 8 term ports.
+type Fit struct {
+	Target int
+	Ports  []int
+}
+
+func goBlockFit(p unsafe.Pointer, fits int, blocks int) [][]BlockFit {
+	out := make([][]BlockFit, fits)
+	if fits*blocks == 0 {
+		for f := range out {
+			out[f] = []BlockFit{}
+		}
+		return out
+	}
+	recs := (*[1 << 22]BlockFit)(p)[: fits*blocks : fits*blocks]
+	for f := range out {
+		out[f] = make([]BlockFit, blocks)
+		copy(out[f], recs[f*blocks:(f+1)*blocks])
+	}
+	return out
+}
+
+// fitTable: a list of fits in its CSR form in C memory -- first[len(fits)+1], then the ports, then the targets, one spare entry behind each --
+// which the caller frees; the library validates it.
+func fitTable(fits []Fit) (first *[1 << 28]C.int, port *[1 << 28]C.int, target *[1 << 28]C.int, release func()) {
+	terms := 0
+	for _, f := range fits {
+		terms += len(f.Ports)
+	}
+	n := len(fits)
+	p := C.calloc(C.size_t((n+2)+(terms+1)+(n+1)), 4)
+	if p == nil {
+		return nil, nil, nil, func() {}
+	}
+	all := (*[1 << 28]C.int)(p)
+	first = (*[1 << 28]C.int)(unsafe.Pointer(&all[0]))
+	port = (*[1 << 28]C.int)(unsafe.Pointer(&all[n+2]))
+	target = (*[1 << 28]C.int)(unsafe.Pointer(&all[n+2+terms+1]))
+	k := 0
+	for i, f := range fits {
+		first[i] = C.int(k)
+		target[i] = C.int(f.Target)
+		for _, v := range f.Ports {
+			port[k] = C.int(v)
+			k++
+		}
+	}
+	first[n] = C.int(k)
+	return first, port, target, func() { C.free(p) }
+}
+
+// BatchFitEnable: from the next batch call on, every batch call of the context keeps the fit records of what it rendered
+// (gdg_batch_fit_enable): per fit a target port and 1 to 8 term ports of the call -- chain outputs, master left, master right, metronome,
+// blend ports.  nil or an empty slice switches it off.  Configuration, like BatchSetBlends: a checkpoint does not carry it, and an error
+// while a streamed job is open.
+func (this *Context) BatchFitEnable(fits []Fit) error {
+	if len(fits) == 0 {
+		return this.err(C.gdg_batch_fit_enable(this.ctx, 0, nil, nil, nil))
+	}
+	first, port, target, release := fitTable(fits)
+	if first == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_batch_fit_enable(this.ctx, C.int(len(fits)), &first[0], &port[0], &target[0]))
+}
+
+// BatchFits: the number of fits in force (gdg_batch_fits).
+func (this *Context) BatchFits() int {
+	return int(C.gdg_batch_fits(this.ctx))
+}
+
+// BatchFit: the fit records of the last completed batch call, result[fit][block] (gdg_batch_fit).  An error when the call ran without
+// them, or was a master finish.
+func (this *Context) BatchFit() ([][]BlockFit, error) {
+	var fits C.int
+	var blocks C.size_t
+	if e := this.err(C.gdg_batch_fit(this.ctx, nil, 0, &fits, &blocks)); e != nil {
+		return nil, e
+	}
+	n := int(fits) * int(blocks)
+	if n == 0 {
+		return goBlockFit(nil, int(fits), int(blocks)), nil
+	}
+	rec := C.calloc(C.size_t(n), 368)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	if e := this.err(C.gdg_batch_fit(this.ctx, (*C.gdg_block_fit)(rec), C.size_t(n), &fits, &blocks)); e != nil {
+		return nil, e
+	}
+	return goBlockFit(rec, int(fits), int(blocks)), nil
+}
+
+// BlockFitRows: the fit records of equally long host rows per block of `block` samples, the last one of a row possibly short
+// (gdg_block_fit_rows); a fit's ports name rows; result[fit][block].
+func (this *Context) BlockFitRows(rows [][]float64, block int, fits []Fit) ([][]BlockFit, error) {
+	n := len(rows)
+	if len(fits) == 0 {
+		return [][]BlockFit{}, nil // as the C call: no fit, no record
+	}
+	if n == 0 || block < 1 {
+		return nil, fmt.Errorf("gdg: %d rows, blocks of %d samples", n, block)
+	}
+	samples := len(rows[0])
+	blocks := (samples + block - 1) / block
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	first, port, target, release := fitTable(fits)
+	if first == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	out := C.calloc(C.size_t(len(fits)*blocks+1), 368)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_fit_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(block), C.int(len(fits)), &first[0], &port[0], &target[0], (*C.gdg_block_fit)(out))); e != nil {
+		return nil, e
+	}
+	return goBlockFit(out, len(fits), blocks), nil
+}
+
+// BlockFitRowsDevice: the same on device memory (gdg_block_fit_rows_device): row r at dRows + r*rowStride float64 (any 8-byte alignment,
+// rowStride >= samples), the records into dRecords[len(fits)][ceil(samples/block)]; returns when they are written.
+func (this *Context) BlockFitRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, block int, fits []Fit, dRecords unsafe.Pointer) error {
+	if len(fits) == 0 {
+		return nil // as the C call: no fit, no record
+	}
+	first, port, target, release := fitTable(fits)
+	if first == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_block_fit_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(block), C.int(len(fits)), &first[0], &port[0], &target[0],
+		(*C.gdg_block_fit)(dRecords)))
+}
+
+// BlendWeightsFromFit: the least-squares blend weights of every fit from its records (gdg_blend_weights_from_fit): records[fit][block] as
+// BatchFit hands them out; (G + ridge*mean(diag G)*I) w = b by an unpivoted Cholesky factorisation in term order.  weights[fit] has the
+// fit's Terms entries; residual[fit] is the share of the target's energy the fitted blend leaves.  Host arithmetic: no context and no
+// device.  An error for a silent term, or a port used twice with ridge = 0.
+func BlendWeightsFromFit(records [][]BlockFit, ridge float64) ([][]float64, []float64, error) {
+	fits := len(records)
+	if fits == 0 {
+		return [][]float64{}, []float64{}, nil
+	}
+	blocks := len(records[0])
+	for f, row := range records {
+		if len(row) != blocks || blocks == 0 {
+			return nil, nil, fmt.Errorf("gdg: fit %d has %d records, fit 0 has %d (at least 1)", f, len(row), blocks)
+		}
+	}
+	rec := C.calloc(C.size_t(fits*blocks+1), 368)
+	if rec == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	dst := (*[1 << 22]BlockFit)(rec)[: fits*blocks : fits*blocks]
+	for f, row := range records {
+		copy(dst[f*blocks:(f+1)*blocks], row)
+	}
+	res := (*[1 << 28]C.double)(C.calloc(C.size_t(fits*9+1), 8))
+	if res == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(res))
+	if rc := C.gdg_blend_weights_from_fit((*C.gdg_block_fit)(rec), C.int(fits), C.size_t(blocks), C.double(ridge), &res[0], &res[fits*8]); rc != 0 {
+		return nil, nil, fmt.Errorf("gdg: gdg_blend_weights_from_fit: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	weights := make([][]float64, fits)
+	residual := make([]float64, fits)
+	for f := range weights {
+		k := int(records[f][0].Terms)
+		weights[f] = make([]float64, k)
+		for t := 0; t < k; t++ {
+			weights[f][t] = float64(res[f*8+t])
+		}
+		residual[f] = float64(res[fits*8+f])
+	}
+	return weights, residual, nil
+}

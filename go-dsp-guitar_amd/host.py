@@ -51,6 +51,9 @@ def lib():
             "gdgh_engine_sync_chains": (cs, [vp, C.c_uint32]),
             "gdgh_engine_set_batch_blends": (cs, [vp, i32, vp, vp, vp, vp]),
             "gdgh_engine_batch_blends": (i32, [vp]),
+            "gdgh_engine_set_batch_fits": (cs, [vp, i32, vp, vp, vp]),
+            "gdgh_engine_batch_fits": (i32, [vp]),
+            "gdgh_engine_last_batch_fit": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -130,6 +133,7 @@ class Engine:
         self.last_report = None          # the render report of the last batch call made with report=True: [N + 3, blocks] records
         self.last_spectrum = None        # the band spectrum of the last batch call made with spectrum=edges: [N + 3, blocks, bands] float64
         self.last_true_peak = None       # the true-peak records of the last batch call made with true_peak=True: [N + 3, blocks] records
+        self.last_fit = None             # the fit records of the last batch call made with fits=: [fits, blocks] records (FIT_DTYPE)
         self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
     def shards(self):
@@ -315,6 +319,69 @@ class Engine:
         _err(lib().gdgh_engine_set_batch_blends(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data, None if g is None else g.ctypes.data))
         return int(lib().gdgh_engine_batch_blends(self._h))
 
+    def _set_fits(self, fits):
+        """Engine::SetBatchFits, from the `fits` argument of the batch calls: a list of (target port, [term ports]); None or an empty list:
+        off.  Returns the number of fits in force.  Refused on an engine of more than one shard."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        self.last_fit = None
+        fits = [] if fits is None else list(fits)
+        if not fits:
+            _err(lib().gdgh_engine_set_batch_fits(self._h, 0, None, None, None))
+            return 0
+        first, port, target = pkg._fit_csr(fits)
+        _err(lib().gdgh_engine_set_batch_fits(self._h, len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data))
+        return int(lib().gdgh_engine_batch_fits(self._h))
+
+    def _fetch_fit(self):
+        """Engine::LastBatchFit -> [fits, blocks] records (FIT_DTYPE)"""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        fits, blocks = C.c_int(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_fit(self._h, None, 0, C.byref(fits), C.byref(blocks)))
+        out = np.zeros((fits.value, blocks.value), dtype=pkg.FIT_DTYPE)
+        _err(lib().gdgh_engine_last_batch_fit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(fits), C.byref(blocks)))
+        return out
+
+    def render_fitted(self, target, terms, inputs, target_rate, out_format, ridge=0.0, delays=None, signs=None, window=16, sample_rate=None, **kw):
+        """Two passes over one job: the blend of the chain outputs `terms` (job channels, 1 to 8) that comes closest to port `target` (a chain
+        output, master left, master right or the metronome) in the least-squares sense.  save_state; pass 1 renders with every output
+        skipped and one fit on: against `target`, each term the chain port itself -- or, with delays and / or signs given (one per term, as
+        render_aligned returns them), the port of a one-term blend that delays it and turns its polarity; the planner
+        (blend_weights_from_fit) turns the records into weights; load_state; pass 2 renders with the one blend of weights sign_k * w_k and
+        the given delays.  Returns (outs, weights, residual): the N + 3 + 1 output data sections, the K weights as fitted (before the
+        signs) and the share of the target's energy the blend leaves.  Pass 1's records stay in fitted_records.  kw: batch_run's other
+        arguments (fits, blends and blend_gain in kw are replaced)."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        terms = [int(c) for c in terms]
+        K, n3 = len(terms), self.n_channels + 3
+        if not 1 <= K <= pkg.FIT_MAX_TERMS:
+            raise HostError("render_fitted: %d terms; 1 to %d" % (K, pkg.FIT_MAX_TERMS))
+        if not 0 <= int(target) < n3:
+            raise HostError("render_fitted: the target is port %d; the job has ports 0 to %d" % (target, n3 - 1))
+        delays = [0] * K if delays is None else [int(d) for d in delays]
+        signs = [1] * K if signs is None else [int(g) for g in signs]
+        if len(delays) != K or len(signs) != K or any(g not in (1, -1) for g in signs):
+            raise HostError("render_fitted: one delay and one sign (+1 or -1) per term")
+        shaped = any(delays) or any(g != 1 for g in signs)
+        rate = target_rate if sample_rate is None else sample_rate
+        _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
+        blob = self.save_state()
+        rest = {k: v for k, v in kw.items() if k not in ("fits", "blends", "blend_gain", "skip_outputs")}
+        if shaped:                                           # term k as blend port N + 3 + k: delayed and turned before it is measured
+            first = [[(c, float(signs[k]), delays[k])] for k, c in enumerate(terms)]
+            self.batch_run(inputs, target_rate, out_format, window=window, blends=first, fits=[(int(target), [n3 + k for k in range(K)])], skip_outputs=True, **rest)
+        else:
+            self.batch_run(inputs, target_rate, out_format, window=window, fits=[(int(target), terms)], skip_outputs=True, **rest)
+        self.fitted_records = self.last_fit
+        weight, residual = pkg.blend_weights_from_fit(self.fitted_records, ridge)
+        weights = [float(w) for w in weight[0, :K]]
+        self.load_state(blob, rate)
+        blend = [[(c, signs[k] * weights[k], delays[k]) for k, c in enumerate(terms)]]
+        outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=blend, **rest)
+        return outs, weights, float(residual[0])
+
     def render_aligned(self, blends, max_lag, min_coeff, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
         """Two passes over one job: the terms of every blend are lined up before they are summed.  save_state; pass 1 renders with every
         output skipped and the alignment records on, every term's channel measured against the channel of its blend's first term (a channel
@@ -374,7 +441,7 @@ class Engine:
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
@@ -382,13 +449,15 @@ class Engine:
         true-peak records in last_true_peak ([N + 3, blocks], the same order).  trim: the N + 3 gains in front of the encoders (None:
         off).  skip_outputs: every output pointer NULL -- the job renders and measures, nothing is written; returns None.  blends: a list
         of lists of (job channel, weight) or (job channel, weight, delay), blend_gain: one output gain per blend -- B more outputs and B more ports in every last_* record
-        list, behind the metronome's (one-shard engines only; None: off)."""
+        list, behind the metronome's (one-shard engines only; None: off).  fits: a list of (target port, [term ports]) -- keep the fit
+        records in last_fit ([fits, blocks], FIT_DTYPE; one-shard engines only; None: off)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_trim(trim)
         nb = self._set_blends(blends, blend_gain)            # before the alignment list, which may name blend ports
+        fitted = self._set_fits(fits)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -429,18 +498,21 @@ class Engine:
             self.last_align = self._fetch_align()
         if peaked:
             self.last_true_peak = self._fetch_true_peak()
+        if fitted:
+            self.last_fit = self._fetch_fit()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces (and one per blend of blends= / blend_gain=, as batch_run's).  report: last_report grows by every slice's records and is the whole job's,
-        [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]."""
+        [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]; fits=: last_fit likewise,
+        [fits, blocks]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
                                   metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
-                                  blends=blends, blend_gain=blend_gain)
+                                  blends=blends, blend_gain=blend_gain, fits=fits)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -465,7 +537,7 @@ class Engine:
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
@@ -473,6 +545,7 @@ class Engine:
         self._set_dither(dither)
         self._set_trim(trim)
         nb = self._set_blends(blends, blend_gain)            # the sharded form passes none: off
+        fitted = self._set_fits(fits)                        # ... and no fits
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -524,6 +597,9 @@ class Engine:
                 if peaked:
                     tp = self._fetch_true_peak()
                     self.last_true_peak = tp if self.last_true_peak is None else np.concatenate([self.last_true_peak, tp], axis=1)
+                if fitted:
+                    ft = self._fetch_fit()
+                    self.last_fit = ft if self.last_fit is None else np.concatenate([self.last_fit, ft], axis=1)
                 yield outs
                 left -= blocks
         finally:

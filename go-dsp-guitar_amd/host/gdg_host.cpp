@@ -1012,6 +1012,43 @@ int Engine::applyBlends(gdg_ctx *ctx) {
     return gdg_batch_set_blends_delayed(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendDelay_.data(), blendGain_.data());
 }
 
+/* Engine::SetBatchFits: validated whole before the list replaces the one in force (the library checks again, and the ports against the job's) */
+Error Engine::SetBatchFits(const std::vector<std::pair<int, std::vector<int>>> &fits) {
+    if (fits.empty()) { fitFirst_.clear(); fitPort_.clear(); fitTarget_.clear(); return ""; }
+    if (shards() > 1)
+        return format("SetBatchFits: the engine has %d shards: a fit's ports are rows of one device's window, and the library's shard calls refuse fits; fits need a "
+                      "one-shard engine", shards());
+    if (fits.size() > GDG_FIT_MAX_FITS) return format("SetBatchFits: %zu fits; at most %d", fits.size(), GDG_FIT_MAX_FITS);
+    std::vector<int> first(1, 0), port, target;
+    for (size_t f = 0; f < fits.size(); f++) {
+        if (fits[f].second.empty() || fits[f].second.size() > GDG_FIT_MAX_TERMS) return format("SetBatchFits: fit %zu has %zu terms; 1 to %d", f, fits[f].second.size(), GDG_FIT_MAX_TERMS);
+        if (fits[f].first < 0) return format("SetBatchFits: fit %zu has the target port %d; ports start at 0", f, fits[f].first);
+        for (size_t k = 0; k < fits[f].second.size(); k++) {
+            if (fits[f].second[k] < 0) return format("SetBatchFits: fit %zu, term %zu names port %d; ports start at 0", f, k, fits[f].second[k]);
+            port.push_back(fits[f].second[k]);
+        }
+        first.push_back((int)port.size());
+        target.push_back(fits[f].first);
+    }
+    fitFirst_.swap(first);
+    fitPort_.swap(port);
+    fitTarget_.swap(target);
+    return "";
+}
+
+int Engine::applyFits(gdg_ctx *ctx) {
+    if (fitTarget_.empty()) return gdg_batch_fit_enable(ctx, 0, nullptr, nullptr, nullptr);
+    return gdg_batch_fit_enable(ctx, BatchFits(), fitFirst_.data(), fitPort_.data(), fitTarget_.data());
+}
+
+Error Engine::LastBatchFit(std::vector<gdg_block_fit> &records, int *fits, size_t *blocks) const {
+    if (!fitValid_) return "LastBatchFit: the last batch call kept no fit records (SetBatchFits comes before the call)";
+    records = lastFit_;
+    if (fits) *fits = fitBlocks_ ? (int)(lastFit_.size() / fitBlocks_) : BatchFits();
+    if (blocks) *blocks = fitBlocks_;
+    return "";
+}
+
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
  * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
  * controller.go:3005-3045). */
@@ -1022,7 +1059,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         chains = chains_;
     }
     size_t job = 0;
-    if (BatchBlends() == 0) {                            /* with blends BatchRun is the plain run, whose master rows are measured like any other */
+    if (!plainRun()) {                                   /* with blends or fits BatchRun is the plain run, whose master rows are measured like any other */
         Error ae = alignOverShards(1);                   /* the shard forms make the master in the finish, at any shard count */
         if (!ae.empty()) { setError(ae); return ae; }
     }
@@ -1037,7 +1074,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1057,10 +1094,10 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
-    /* blends in force (one shard: SetBatchBlends): the library's plain one-call run -- its shard calls refuse blends -- with `outs` of
-     * N + 3 + B entries; the alignment list goes on in its plain form, and the context's records of every kind are the engine's */
-    if (BatchBlends() > 0) {
+    if (job == 0) { fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
+    /* blends or fits in force (one shard: SetBatchBlends, SetBatchFits): the library's plain one-call run -- its shard calls refuse both --
+     * with `outs` of N + 3 + B entries; the alignment list goes on in its plain form, and the context's records of every kind are the engine's */
+    if (plainRun()) {
         std::lock_guard<std::mutex> lk(shards_[0]->mu);
         gdg_ctx *ctx = shards_[0]->ctx;
         if (applyAlign(-1, ctx) != GDG_OK || gdg_batch_run(ctx, inputs, nInputs, &options, outs) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
@@ -1115,7 +1152,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
  * [N + 3][blocks] in gdg_batch_run's port order and from three sources -- the shards' chain rows, shard 0's metronome row, the finish's two
  * master rows (which carry no alignment records: over shards those rows stay zero) ---- */
 void Engine::reportBegin(size_t blocks) {
-    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = false;
+    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = false;
     reportBlocks_ = blocks;
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
     const size_t n = (size_t)ports() * blocks;
@@ -1317,7 +1354,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1352,6 +1389,17 @@ Error Engine::recordsOfContext(gdg_ctx *ctx) {
     if (re.empty() && truePeak_ && (re = truePeakOf(ctx, ports(), lastTruePeak_)).empty()) truePeakValid_ = true;
     if (re.empty() && !alignRef_.empty() && (re = alignOf(ctx, ports(), lastAlign_)).empty()) alignValid_ = true;
     if (re.empty() && !spectrumEdges_.empty() && (re = spectrumOf(ctx, ports(), lastSpectrum_)).empty()) spectrumValid_ = true;
+    if (re.empty() && BatchFits() > 0) {                   /* the fits' records: [fits][blocks], rows of their own */
+        int fits = 0;
+        size_t blocks = 0;
+        if (gdg_batch_fit(ctx, nullptr, 0, &fits, &blocks) != GDG_OK) re = gdg_last_error(ctx);
+        else {
+            lastFit_.assign((size_t)fits * blocks, gdg_block_fit{});
+            fitBlocks_ = blocks;
+            if (!lastFit_.empty() && gdg_batch_fit(ctx, lastFit_.data(), lastFit_.size(), &fits, &blocks) != GDG_OK) re = gdg_last_error(ctx);
+            else fitValid_ = true;
+        }
+    }
     if (!re.empty()) { setError(re); return LastError(); }
     return "";
 }
@@ -1898,6 +1946,33 @@ const char *gdgh_engine_last_batch_true_peak(void *e, gdg_block_true_peak *recor
     if (records) {
         if (capacity < rec.size()) return ret(Error("LastBatchTruePeak: too little room for the records"));
         if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_true_peak));
+    }
+    return ret(Error(""));
+}
+/* n_fits == 0: off */
+const char *gdgh_engine_set_batch_fits(void *e, int n_fits, const int *first, const int *port, const int *target) {
+    if (!e) return ret(Error("no engine"));
+    if (n_fits < 0 || (n_fits > 0 && (!first || !port || !target || first[0] != 0))) return ret(Error("SetBatchFits: n_fits >= 0, and first (from 0 on), port and target"));
+    std::vector<std::pair<int, std::vector<int>>> fits;
+    for (int f = 0; f < n_fits; f++) {
+        if (first[f + 1] < first[f]) return ret(format("SetBatchFits: fit %d: first descends from %d to %d", f, first[f], first[f + 1]));
+        fits.emplace_back(target[f], std::vector<int>(port + first[f], port + first[f + 1]));
+    }
+    return ret(((Engine *)e)->SetBatchFits(fits));
+}
+int gdgh_engine_batch_fits(void *e) { return ((Engine *)e)->BatchFits(); }
+/* records == NULL: the two counts only */
+const char *gdgh_engine_last_batch_fit(void *e, gdg_block_fit *records, size_t capacity, int *fits, size_t *blocks) {
+    std::vector<gdg_block_fit> rec;
+    int f = 0;
+    size_t b = 0;
+    Error err = ((Engine *)e)->LastBatchFit(rec, &f, &b);
+    if (!err.empty()) return ret(err);
+    if (fits) *fits = f;
+    if (blocks) *blocks = b;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchFit: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_fit));
     }
     return ret(Error(""));
 }

@@ -295,6 +295,15 @@ public:
     Error SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain = {},
                          const std::vector<std::vector<int>> &delay = {});      /* delay[b][k]: term k of blend b reads its row that many samples back (gdg_batch_set_blends_delayed); none: every delay 0 */
     int BatchBlends() const { return blendFirst_.empty() ? 0 : (int)blendFirst_.size() - 1; }
+    /* No reference counterpart.  The blend fits (include/gdg.h, gdg_batch_fit_enable): per fit a target port and 1 to 8 term ports of the
+     * job -- chain outputs, master left, master right, metronome and the blend ports in force.  While fits are in force BatchRun and the plain
+     * streamed job keep one gdg_block_fit per fit and block (LastBatchFit: [fits][blocks]) for gdg_blend_weights_from_fit.  Refused with more
+     * than one shard, as the blends are and for their reason: the library's shard calls refuse fits, and BatchRun of a one-shard engine with
+     * fits is the library's plain gdg_batch_run.  The ports' upper bound is checked when a job is described.  A refused list leaves the one in
+     * force; an empty list: off. */
+    Error SetBatchFits(const std::vector<std::pair<int, std::vector<int>>> &fits);
+    int BatchFits() const { return (int)fitTarget_.size(); }
+    Error LastBatchFit(std::vector<gdg_block_fit> &records, int *fits, size_t *blocks) const;
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -363,6 +372,12 @@ private:
     std::vector<int> blendFirst_, blendChannel_;           /* SetBatchBlends, in gdg_batch_set_blends' CSR form; blendFirst_ empty: off */
     std::vector<double> blendWeight_, blendGain_;
     std::vector<int> blendDelay_;                          /* one per term, or empty: every delay 0 and the list goes through gdg_batch_set_blends */
+    std::vector<int> fitFirst_, fitPort_, fitTarget_;      /* SetBatchFits, in gdg_batch_fit_enable's CSR form; fitTarget_ empty: off */
+    std::vector<gdg_block_fit> lastFit_;                   /* [fits][blocks] of the last batch call that kept them */
+    size_t fitBlocks_ = 0;
+    bool fitValid_ = false;
+    int applyFits(gdg_ctx *ctx);                           /* onto a context (more shards: none are in force): a gdg_* status */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

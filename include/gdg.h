@@ -1171,6 +1171,81 @@ int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row
                                   double *d_out, size_t out_stride);
 int gdg_blend_delays_from_align(const gdg_block_align *records, int ports, size_t blocks, const int *ref, double min_coeff, int n_blends,
                                 const int *first, const int *channel, int *delay, int *sign);
+/*
+ * FIT: no reference counterpart.  The one blend parameter the records above do not measure is the weight: "which mix of these few rigs
+ * comes closest to THAT track?" is a linear least-squares problem, and everything it needs is an inner product of float64 rows that already
+ * lie in the batch window on the device, before anything is truncated to 16 or 24 bits.  A fit record holds those inner products per block;
+ * a host planner turns the records into blend weights.  Stateless: a function of the block's samples alone -- a term that has to be delayed
+ * or inverted first is fitted as the port of a one-term delayed blend (DELAYS, above).
+ * INPUTS: a fit f has a target port t and terms p_0 .. p_{K-1}, 1 <= K <= GDG_FIT_MAX_TERMS (8).  Ports are rows of the batch window, 0 ..
+ * N + 2 + B: chain outputs, master left, master right, metronome and the B blend ports.  A port may repeat; the target may be a term.  Up to
+ * GDG_FIT_MAX_FITS (256) fits.  Rows are read as the record kernels read them: before the trim, and a blend port's s before g_b.
+ * RECORD: per fit and block of 8192 samples one gdg_block_fit (below): tt = sum t[i]^2, tx[k] = sum t[i] * x_k[i], and the lower triangle
+ * of the Gram matrix by rows, xx[j (j + 1) / 2 + k] = sum x_j[i] * x_k[i] for k <= j.  Entries for terms >= K are +0.0.  A sample index i
+ * at which ANY of the fit's K + 1 rows is NaN or +-inf is left out of ALL 45 sums and counted in `skipped`.
+ * ORDER OF THE SUMS: the block statistics' order, for every entry: one workgroup of 256 threads per (block, fit); thread t walks the sample
+ * pairs t, t + 256, ... -- sample 2 p, then 2 p + 1 -- with one running sum per entry; the 64 lanes meet in the fixed tree lane i <- lane i +
+ * 32, 16, ... 1; the four wave results are added in the order 0, 1, 2, 3.  Every product and every add is rounded on its own, never
+ * contracted, and there are no floating-point atomics: nothing depends on the grid, the row, the window, the slice or arrival order.
+ *   With skipped == 0, xx[k (k + 1) / 2 + k] is bit for bit the sum_sq of gdg_block_stats for port p_k and that block, and tt that of port t.
+ *   xx is bitwise symmetric under exchanging two terms.
+ *   The records are the same bits whatever the window, the slicing, a resume or a source map.
+ *   gdg_batch_fit_enable(ctx, n_fits, first, port, target)
+ *                                                      the fits in CSR form: fit f has the terms port[first[f]] .. port[first[f + 1] - 1]
+ *                                                      and the target target[f]; first has n_fits + 1 entries, starts at 0 and never
+ *                                                      descends.  n_fits == 0: off (the lists may be NULL).  Refused whole, with the fit
+ *                                                      named and the list in force unchanged: a fit without a term or with more than 8, a
+ *                                                      negative port, a broken `first`, a count outside 0 .. 256, a streamed job open.
+ *   gdg_batch_fits(ctx)                                the number of fits in force
+ *   gdg_batch_fit(ctx, records, capacity, &fits, &blocks)
+ *                                                      the [fits][blocks] records of the LAST COMPLETED batch call; records == NULL: the
+ *                                                      counts only.  GDG_ERR_INVALID when capacity < fits * blocks, or when there are no
+ *                                                      records: no call has completed since the switch, or the last one was a master finish.
+ * Port numbers are checked when a job is described -- gdg_batch_run, gdg_batch_stream_open, gdg_batch_stream_resume -- against N + 3 + B of
+ * that call; a port at or beyond it is GDG_ERR_INVALID with the fit named.
+ * OFF: n_fits == 0, or never called.  Off, no launch, buffer, upload byte or output byte differs from a context that never heard of the call,
+ * and option stat_batch_device_kib is unchanged; on, it counts the fits' table and the records' room in the download halves.
+ * Configuration, like the blends: it holds from the next batch call on, is part of no blob -- set it again on the target of a resume -- and a
+ * checkpoint and a resume work with fits on.  The records come down with each step's own download, behind the four record kinds' sections.
+ * SHARDS: gdg_batch_run_shard, gdg_batch_stream_open_shard, gdg_batch_stream_step_shard and gdg_batch_stream_resume_shard return
+ * GDG_ERR_UNSUPPORTED while fits are in force on their context.  gdg_batch_finish_master and gdg_batch_finish_master_slice never collect fits.
+ * The record on its own, over any rows and any block length >= 1 (ports name rows 0 .. n_rows - 1; the last block of a row may be short);
+ * both blocking -- the table is host memory:
+ *   gdg_block_fit_rows(ctx, rows, n_rows, samples, block, n_fits, first, port, target, records)
+ *                                                      host rows of `samples` float64; records: [n_fits][ceil(samples / block)]
+ *   gdg_block_fit_rows_device(ctx, d_rows, row_stride, n_rows, samples, block, n_fits, first, port, target, d_records)
+ *                                                      device rows, 8-byte aligned: row r at d_rows + r * row_stride (row_stride >=
+ *                                                      samples); no sample outside [row, row + samples) is read; d_records: device
+ *                                                      memory, 8-byte aligned
+ * THE PLANNER, pure host arithmetic (csrc/blend.h), no context and no device (gdg_last_error(NULL) says what was refused):
+ *   gdg_blend_weights_from_fit(records, n_fits, blocks, ridge, weight, residual)
+ *                                                      records[n_fits][blocks] as gdg_batch_fit hands them out, blocks >= 1;
+ *                                                      weight[n_fits][8], residual[n_fits]
+ * Per fit: the blocks' records are added in block order with plain double adds: T, b[K], G[K][K].  (G + ridge * mean(diag G) * I) w = b is
+ * solved by an unpivoted Cholesky factorisation in term order; ridge >= 0 and finite.  A pivot <= K * 2^-52 * max(diag G) -- a silent term,
+ * or a port used twice with ridge = 0 -- is GDG_ERR_INVALID: nothing is written and the fit is named.  residual = max(0, T - 2 w.b + w'Gw)
+ * / T, and 0 when T == 0: the share of the target's energy that the fitted blend leaves.  Weights of terms >= K are 0.
+ * Known answers: one term with G = 4 and b = 2 gives w = 0.5; two orthogonal terms with G = diag(4, 1), b = {2, 3} and T = 10 give w =
+ * {0.5, 3} and residual 0; a target that is term 0 gives w = {1, 0, ..} and residual 0; one port twice with G = 4 everywhere, b = {2, 2}
+ * is refused with ridge = 0 and gives two equal weights with ridge > 0.
+ */
+#define GDG_FIT_MAX_TERMS 8
+#define GDG_FIT_MAX_FITS 256
+typedef struct gdg_block_fit {
+    double   tt;          /* sum t[i]^2 */
+    double   tx[8];       /* tx[k] = sum t[i] * x_k[i] */
+    double   xx[36];      /* lower triangle by rows: xx[j (j + 1) / 2 + k] = sum x_j[i] * x_k[i], k <= j */
+    uint32_t skipped;     /* sample indices left out of every sum: some row of the fit was NaN or +-inf there */
+    uint32_t terms;       /* K */
+} gdg_block_fit;          /* 368 bytes, little-endian, no padding */
+int gdg_batch_fit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *port, const int *target);
+int gdg_batch_fits(const gdg_ctx *ctx);
+int gdg_batch_fit(gdg_ctx *ctx, gdg_block_fit *records, size_t capacity, int *fits, size_t *blocks);
+int gdg_block_fit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port,
+                       const int *target, gdg_block_fit *records);
+int gdg_block_fit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
+                              const int *port, const int *target, gdg_block_fit *d_records);
+int gdg_blend_weights_from_fit(const gdg_block_fit *records, int n_fits, size_t blocks, double ridge, double *weight, double *residual);
 
 #ifdef __cplusplus
 

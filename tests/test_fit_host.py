@@ -1,0 +1,199 @@
+"""The blend fit without a GPU: the planner and the fit section's layout as a stand-alone program (tests/native/fit_plan_check.cpp), built
+plainly and once more under AddressSanitizer and UBSan; the planner through the library against numpy.linalg.solve on the same sums; the
+header as pedantic C99 with the new record; every layer's names; and the compiler's resource summary of every instantiation of the record
+kernel: no scratch, and the LDS of the four waves' meeting alone."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as entry
+
+ROOT = entry.ROOT
+CSRC = os.path.join(ROOT, "go-dsp-guitar_amd", "csrc")
+NEW = ["gdg_batch_fit_enable", "gdg_batch_fits", "gdg_batch_fit", "gdg_block_fit_rows", "gdg_block_fit_rows_device", "gdg_blend_weights_from_fit"]
+
+C_PROBE = r"""
+#include <stddef.h>
+#include <stdio.h>
+#include "gdg.h"
+typedef char size_is_368[sizeof(gdg_block_fit) == 368 ? 1 : -1];
+typedef char tx_at_8[offsetof(gdg_block_fit, tx) == 8 ? 1 : -1];
+typedef char xx_at_72[offsetof(gdg_block_fit, xx) == 72 ? 1 : -1];
+typedef char skipped_at_360[offsetof(gdg_block_fit, skipped) == 360 ? 1 : -1];
+typedef char terms_at_364[offsetof(gdg_block_fit, terms) == 364 ? 1 : -1];
+int main(void) {
+    const int first[2] = { 0, 2 }, port[2] = { 0, 1 }, target[1] = { 1 };
+    double a[2] = { 1.0, 2.0 }, b[2] = { 3.0, 4.0 }, w[8], res[1];
+    const double *rows[2];
+    gdg_block_fit rec;
+    size_t blocks = 7;
+    int fits = 7;
+    rows[0] = a; rows[1] = b;
+    rec.tt = 4.0; rec.tx[0] = 2.0; rec.xx[0] = 4.0; rec.skipped = 0; rec.terms = 1;
+    printf("%d %d %d %d %d\n", gdg_batch_fit_enable(NULL, 1, first, port, target), gdg_batch_fits(NULL), gdg_batch_fit(NULL, &rec, 1, &fits, &blocks),
+           gdg_block_fit_rows(NULL, rows, 2, 2, 2, 1, first, port, target, &rec), gdg_block_fit_rows_device(NULL, a, 2, 2, 2, 2, 1, first, port, target, &rec));
+    fits = gdg_blend_weights_from_fit(&rec, 1, 1, 0.0, w, res);
+    printf("%d %g %g\n", fits, w[0], w[1]);
+    printf("%d %d %d\n", GDG_FIT_MAX_TERMS, GDG_FIT_MAX_FITS, (int)sizeof(gdg_block_fit));
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    p = entry.load_package()
+    p.build()
+    return p
+
+
+@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]], ids=["plain", "asan-ubsan"])
+def test_planner_list_and_fit_section_as_a_stand_alone_program(tmp_path, flags):
+    exe = str(tmp_path / "fit_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-Wall"] + flags + ["-I", CSRC, os.path.join(ROOT, "tests", "native", "fit_plan_check.cpp"), "-o", exe], check=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.match(r"OK planner and list; (\d+) section cases, (\d+) moved by the 16-byte step\n", r.stdout)
+    assert m, r.stdout + r.stderr
+    # 16 sets of kinds x 3 row counts x 4 step widths x 4 sample widths x 2 band counts x 4 fit counts
+    assert int(m.group(1)) == 16 * 3 * 4 * 4 * 2 * 4 and int(m.group(2)) > 0
+
+
+def test_the_fit_section_is_stated_once_and_is_no_fifth_kind():
+    with open(os.path.join(CSRC, "report_sections.h")) as f:
+        text = f.read()
+    assert "enum { REPORT_STATS, REPORT_BANDS, REPORT_ALIGN, REPORT_TRUE_PEAK, REPORT_KINDS };" in text
+    assert "static inline FitSection fit_section(" in text and "static inline size_t fit_room(" in text
+    with open(os.path.join(CSRC, "api_batch.cpp")) as f:
+        batch = f.read()
+    assert "fit_section(" in batch and "fit_room(" in batch
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        make = f.read()
+    assert "fit_kernels.h" in [w for line in make.splitlines() if line.startswith("io.o:") for w in line.split()]
+
+
+def random_records(pkg, rng, K, blocks, samples=4096):
+    """records of K random rows against a random mix of them plus noise, summed with numpy per block; -> records, G, b, T"""
+    x = rng.normal(size=(K, blocks * samples)) + 0.3 * rng.normal(size=(1, blocks * samples))
+    t = rng.uniform(-1, 1, K) @ x + 0.05 * rng.normal(size=blocks * samples)
+    rec = np.zeros((1, blocks), dtype=pkg.FIT_DTYPE)
+    for q in range(blocks):
+        s = slice(q * samples, (q + 1) * samples)
+        rec[0, q]["tt"] = t[s] @ t[s]
+        rec[0, q]["terms"] = K
+        for j in range(K):
+            rec[0, q]["tx"][j] = t[s] @ x[j, s]
+            for k in range(j + 1):
+                rec[0, q]["xx"][j * (j + 1) // 2 + k] = x[j, s] @ x[k, s]
+    G = np.zeros((K, K))
+    for j in range(K):
+        for k in range(j + 1):
+            G[j, k] = G[k, j] = sum(rec[0, q]["xx"][j * (j + 1) // 2 + k] for q in range(blocks))      # block order, plain adds
+    b = np.array([sum(rec[0, q]["tx"][j] for q in range(blocks)) for j in range(K)])
+    T = sum(rec[0, q]["tt"] for q in range(blocks))
+    return rec, G, b, T
+
+
+@pytest.mark.parametrize("K", [1, 2, 3, 5, 8])
+def test_planner_against_numpy_solve_on_the_same_sums(pkg, K):
+    """Cholesky's error is about K * 2^-53 * cond = 1e-12 at cond = 1e3: 1e-10 relative to the largest weight leaves a factor 100"""
+    rng = np.random.default_rng(500 + K)
+    rec, G, b, T = random_records(pkg, rng, K, 3)
+    assert np.linalg.cond(G) <= 1e3, np.linalg.cond(G)
+    for ridge in (0.0, 0.01):
+        w, res = pkg.blend_weights_from_fit(rec, ridge)
+        want = np.linalg.solve(G + ridge * np.trace(G) / K * np.eye(K), b)
+        assert w.shape == (1, 8) and not w[0, K:].any()
+        assert np.abs(w[0, :K] - want).max() <= 1e-10 * np.abs(want).max(), (K, ridge, w[0, :K], want)
+        want_res = max(0.0, T - 2.0 * want @ b + want @ G @ want) / T
+        assert abs(res[0] - want_res) <= 1e-10, (K, ridge, res[0], want_res)
+    assert 0.0 < res[0] < 0.1                                                   # the noise the mix cannot reach
+
+
+def test_planner_refusals_reach_the_caller(pkg):
+    rec = np.zeros((2, 1), dtype=pkg.FIT_DTYPE)
+    rec["terms"] = 2
+    rec["tt"] = 1.0
+    rec["tx"][:, :, :2] = 2.0
+    rec["xx"][:, :, :3] = 4.0                                                   # one port twice
+    rec[0, 0]["xx"][1] = 0.0                                                    # fit 0: orthogonal, fine
+    with pytest.raises(pkg.GdgError, match="fit 1: a pivot") as e:
+        pkg.blend_weights_from_fit(rec)
+    assert e.value.code == pkg.GDG_ERR_INVALID
+    w, _ = pkg.blend_weights_from_fit(rec, 1e-3)
+    assert abs(w[1, 0] - w[1, 1]) <= 1e-12 and w[0, 0] == w[0, 1]
+    with pytest.raises(pkg.GdgError, match="ridge = -1"):
+        pkg.blend_weights_from_fit(rec, -1.0)
+
+
+def test_the_header_is_pedantic_c99_and_the_record_has_368_bytes(pkg, tmp_path):
+    src = tmp_path / "fit_probe.c"
+    src.write_text(C_PROBE)
+    exe = tmp_path / "fit_probe"
+    lib_dir = os.path.dirname(pkg.LIB_PATH)
+    cmd = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
+           "-L", lib_dir, "-lgdg", "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    lines = r.stdout.splitlines()
+    inv = pkg.GDG_ERR_INVALID
+    assert [int(v) for v in lines[0].split()] == [inv, 0, inv, inv, inv]             # no context: refused, nothing touched; no fit in force
+    assert lines[1] == "0 0.5 0" and lines[2] == "8 256 368"
+
+
+def test_every_layer_knows_the_calls(pkg):
+    out = subprocess.run(["nm", "-D", "--defined-only", pkg.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
+    with open(os.path.join(ROOT, "include", "gdg.h")) as f:
+        header = f.read()
+    for name in NEW:
+        assert name in exported and name in pkg.ABI_SYMBOLS and re.search(r"^int %s\(" % name, header, re.M), name
+    for name in ("batch_fit_enable", "batch_fits", "batch_fit", "block_fit", "block_fit_device"):
+        assert callable(getattr(pkg.Context, name)), name
+    assert pkg.FIT_DTYPE.itemsize == 368 and pkg.FIT_DTYPE.fields["skipped"][1] == 360 and pkg.FIT_DTYPE.fields["xx"][1] == 72
+    flat = " ".join(header.replace(" * ", " ").split())
+    for phrase in ("is left out of ALL 45 sums and counted in `skipped`", "bit for bit the sum_sq of gdg_block_stats", "xx is bitwise symmetric under exchanging two terms",
+                   "unpivoted Cholesky factorisation in term order", "GDG_ERR_UNSUPPORTED while fits are in force", "never collect fits"):
+        assert phrase in flat, phrase
+    assert re.search(r"^#define GDG_FIT_MAX_TERMS 8$", header, re.M)
+    with open(os.path.join(os.path.dirname(os.path.dirname(pkg.LIB_PATH)), "go", "gdg", "gdg.go")) as f:
+        go = f.read()
+    for sig in (r"^type BlockFit struct \{", r"^func \(this \*Context\) BatchFitEnable\(fits \[\]Fit\) error", r"^func \(this \*Context\) BatchFits\(\) int",
+                r"^func \(this \*Context\) BatchFit\(\) \(\[\]\[\]BlockFit, error\)", r"^func \(this \*Context\) BlockFitRows\(", r"^func \(this \*Context\) BlockFitRowsDevice\(",
+                r"^func BlendWeightsFromFit\(records \[\]\[\]BlockFit, ridge float64\)"):
+        assert re.search(sig, go, re.M), sig
+    from go_dsp_guitar_amd import host
+    assert callable(host.Engine._set_fits) and callable(host.Engine.render_fitted) and host.lib().gdgh_engine_set_batch_fits is not None
+    assert host.lib().gdgh_engine_last_batch_fit is not None
+    with open(os.path.join(os.path.dirname(os.path.dirname(pkg.LIB_PATH)), "host", "gdg_host.hpp")) as f:
+        hpp = f.read()
+    assert "Error SetBatchFits(const std::vector<std::pair<int, std::vector<int>>> &fits);" in hpp
+    assert "Error LastBatchFit(std::vector<gdg_block_fit> &records, int *fits, size_t *blocks) const;" in hpp
+    assert os.path.exists(os.path.join(ROOT, "profiles", "probes", "batch_fit.py"))
+    for call in ("C.gdg_batch_fit_enable(", "C.gdg_batch_fits(", "C.gdg_batch_fit(", "C.gdg_block_fit_rows(", "C.gdg_block_fit_rows_device(", "C.gdg_blend_weights_from_fit("):
+        assert call in go, call
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+def test_the_fit_kernel_uses_no_scratch_and_the_wave_meet_s_lds(tmp_path):
+    """Every instantiation of block_fit_kernel -- 16-byte and 8-byte lanes x 1 to 8 terms -- from the compiler's resource summary: no scratch,
+    and the LDS is what the four waves leave for their meeting: 4 x 45 sums of 8 bytes and 4 counts of 4, 1456 bytes.  The instruction
+    stream is not looked at: that no product is contracted is what the bitwise equality with sum_sq shows on the device."""
+    out = str(tmp_path / "io.s")
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only", "-x", "hip",
+                    os.path.join(CSRC, "io.hip"), "-o", out], check=True, timeout=900, cwd=CSRC, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    text = open(out).read()
+    found = {}
+    for m in re.finditer(r"^(_Z\w+):\s*; @(.*?)^; TotalNumVgprs: (\d+).*?^; ScratchSize: (\d+).*?^; LDSByteSize: (\d+)", text, re.S | re.M):
+        if "block_fit_kernel" in m.group(1):
+            found[m.group(1)] = (int(m.group(3)), int(m.group(4)), int(m.group(5)))
+    assert len(found) == 16, sorted(found)
+    for name, (vgprs, scratch, lds) in found.items():
+        assert scratch == 0 and lds == 4 * 45 * 8 + 4 * 4 and vgprs <= 512, (name, vgprs, scratch, lds)
+    # the registers follow the term count: a fit of two terms does not pay for 45 sums
+    assert min(v for v, _, _ in found.values()) <= 64
