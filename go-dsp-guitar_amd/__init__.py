@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "gdg_batch_set_blends", "gdg_batch_blends", "gdg_blend_rows", "gdg_blend_rows_device",
     "gdg_batch_set_blends_delayed", "gdg_batch_blend_max_delay", "gdg_blend_rows_delayed", "gdg_blend_rows_delayed_device", "gdg_blend_delays_from_align",
     "gdg_batch_fit_enable", "gdg_batch_fits", "gdg_batch_fit", "gdg_block_fit_rows", "gdg_block_fit_rows_device", "gdg_blend_weights_from_fit",
+    "gdg_batch_gram_enable", "gdg_batch_gram_ports", "gdg_batch_gram", "gdg_block_gram_rows", "gdg_block_gram_rows_device", "gdg_blend_pick_from_gram",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -155,6 +156,43 @@ def blend_weights_from_fit(records, ridge=0.0):
     if rc != GDG_OK:
         raise GdgError(rc, lib().gdg_last_error(None).decode())
     return weight, residual
+
+
+GRAM_MAX_PORTS = 512         # GDG_GRAM_MAX_PORTS (include/gdg.h): the ports of the one Gram list
+GRAM_BLOCK = 8192            # the block of a batch call's Gram records
+
+
+def gram_index(i, j):
+    """the place of entry (i, j) in a Gram record: the lower triangle by rows (either order of i and j)"""
+    i, j = (i, j) if i >= j else (j, i)
+    return i * (i + 1) // 2 + j
+
+
+def gram_matrix(record, n_ports):
+    """one Gram record (or a sum of records), P (P + 1) / 2 doubles, as the full symmetric [P, P] matrix"""
+    G = np.zeros((n_ports, n_ports), dtype=np.float64)
+    G[np.tril_indices(n_ports)] = np.asarray(record, dtype=np.float64).reshape(-1)
+    return G + np.tril(G, -1).T
+
+
+def blend_pick_from_gram(records, n_ports, target, candidates, max_terms, ridge=0.0, min_gain=0.0):
+    """gdg_blend_pick_from_gram: records [blocks, P (P + 1) / 2] float64 (as batch_gram hands them out); target and candidates are positions
+    in the Gram list -> (picked, weights, residuals): the list positions picked greedily, in pick order, their least-squares weights
+    against the target, and the share of the target's energy left after every pick.  Host arithmetic: no context, no device.  GdgError
+    for a silent target, a NaN or inf entry, a repeated candidate or max_terms outside 1 to 8."""
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    if rec.ndim != 2 or rec.shape[1] != int(n_ports) * (int(n_ports) + 1) // 2:
+        raise ValueError("records: [blocks, n_ports (n_ports + 1) / 2]")
+    cand = np.array([int(c) for c in candidates] + [0], dtype=np.int32)
+    picked = np.full(FIT_MAX_TERMS, -1, dtype=np.int32)
+    weight = np.zeros(FIT_MAX_TERMS, dtype=np.float64)
+    residual = np.zeros(FIT_MAX_TERMS, dtype=np.float64)
+    n = C.c_int(0)
+    rc = lib().gdg_blend_pick_from_gram(rec.ctypes.data if rec.size else None, int(n_ports), rec.shape[0], int(target), cand.ctypes.data, cand.size - 1, int(max_terms),
+                                        float(ridge), float(min_gain), picked.ctypes.data, weight.ctypes.data, residual.ctypes.data, C.byref(n))
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return [int(p) for p in picked[:n.value]], weight[:n.value].copy(), residual[:n.value].copy()
 
 
 ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
@@ -414,6 +452,12 @@ def lib():
             "gdg_block_fit_rows": (i32, [vp, vp, i32, C.c_size_t, i32, i32, vp, vp, vp, vp]),
             "gdg_block_fit_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, i32, vp, vp, vp, vp]),
             "gdg_blend_weights_from_fit": (i32, [vp, i32, C.c_size_t, C.c_double, vp, vp]),
+            "gdg_batch_gram_enable": (i32, [vp, vp, i32]),
+            "gdg_batch_gram_ports": (i32, [vp, vp, i32]),
+            "gdg_batch_gram": (i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+            "gdg_block_gram_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp, i32, vp]),
+            "gdg_block_gram_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, i32, vp]),
+            "gdg_blend_pick_from_gram": (i32, [vp, i32, C.c_size_t, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, C.POINTER(i32)]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1381,6 +1425,55 @@ class Context:
         first, port, target = _fit_csr(fits)
         self._check(lib().gdg_block_fit_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(block), len(fits), first.ctypes.data, port.ctypes.data,
                                                     target.ctypes.data, d_records))
+
+    # -- the Gram of a port list: per block the inner products of all listed rows, on the matrix cores (include/gdg.h, GRAM) ---------------------
+    def batch_gram_enable(self, ports):
+        """From the next batch call on, every batch call keeps the Gram records of what it rendered (gdg_batch_gram_enable): ports = 2 to 512
+        different ports of the call -- chain outputs, master left, master right, metronome, blend ports.  None or an empty list: off.
+        Configuration: not in a checkpoint, refused while a streamed job is open."""
+        ports = [] if ports is None else [int(p) for p in ports]
+        if not ports:
+            self._check(lib().gdg_batch_gram_enable(self._h, None, 0))
+            return
+        port = np.array(ports, dtype=np.int32)
+        self._check(lib().gdg_batch_gram_enable(self._h, port.ctypes.data, port.size))
+
+    def batch_gram_ports(self):
+        """The Gram list in force (gdg_batch_gram_ports); empty: off."""
+        n = int(lib().gdg_batch_gram_ports(self._h, None, 0))
+        port = np.zeros(max(n, 1), dtype=np.int32)
+        lib().gdg_batch_gram_ports(self._h, port.ctypes.data, n)
+        return [int(p) for p in port[:n]]
+
+    def batch_gram(self):
+        """The [blocks, P (P + 1) / 2] float64 Gram records of the last completed batch call; GdgError when there are none."""
+        blocks = C.c_size_t(0)
+        self._check(lib().gdg_batch_gram(self._h, None, 0, C.byref(blocks)))
+        n = len(self.batch_gram_ports())
+        out = np.zeros((blocks.value, n * (n + 1) // 2), dtype=np.float64)
+        self._check(lib().gdg_batch_gram(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks)))
+        return out
+
+    def block_gram(self, rows, ports, block=GRAM_BLOCK):
+        """gdg_block_gram_rows: rows [n_rows, samples] float64 (or a list of equally long 1-D arrays), ports = 1 to 512 different rows ->
+        the [ceil(samples / block), P (P + 1) / 2] records."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        port = np.array([int(p) for p in ports] + [0], dtype=np.int32)
+        P = port.size - 1
+        out = np.zeros((-(-samples // int(block)) if int(block) > 0 else 0, P * (P + 1) // 2), dtype=np.float64)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_gram_rows(self._h, ptrs, n, samples, int(block), port.ctypes.data, P, out.ctypes.data if out.size else None))
+        return out
+
+    def block_gram_device(self, d_rows, row_stride, n_rows, samples, ports, d_records, block=GRAM_BLOCK):
+        """gdg_block_gram_rows_device on plain device pointers (ints); returns when the records are written."""
+        port = np.array([int(p) for p in ports] + [0], dtype=np.int32)
+        self._check(lib().gdg_block_gram_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(block), port.ctypes.data, port.size - 1, d_records))
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

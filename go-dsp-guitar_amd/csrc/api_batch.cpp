@@ -126,6 +126,9 @@ struct BatchLoop {
     /* the blend fits: n_fits entries of the table (blend.h, FitSet) on the host and on the device; 0 = off, and always for a shard */
     int n_fits;
     const int *h_fit_table, *d_fit_table;
+    /* the Gram list: n_gram ports on the host and on the device; 0 = off, and always for a shard */
+    int n_gram;
+    const int *h_gram_port, *d_gram_port;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -165,7 +168,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; FitSection fit; };
+    struct Step { size_t off; int w; ReportSections sec; FitSection fit; GramSection gram; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -177,7 +180,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {}, {} });
+        steps.push_back({ off, w, {}, {}, {} });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
@@ -193,6 +196,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     for (size_t i = 0; i < steps.size(); i++) {
         steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
         steps[i].fit = fit_section(steps[i].sec.end, (size_t)p.n_fits, (size_t)steps[i].w);      /* behind the last of them: [fits][w] */
+        steps[i].gram = gram_section(steps[i].fit.end, (size_t)p.n_gram, (size_t)steps[i].w);    /* ... and behind those: [w] */
     }
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
@@ -233,6 +237,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         for (int k = 0; k < REPORT_KINDS; k++)                               /* the last piece brought the step's sections: filed under the step's blocks */
             if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
         if (p.n_fits) fit_file(ctx, src + steps[i].fit.at, (size_t)steps[i].w, steps[i].off / B);
+        if (p.n_gram) gram_file(ctx, src + steps[i].gram.at, (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -303,6 +308,9 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             if (p.n_fits)                                                    /* the fits' inner products of the same rows, the blends' among them */
                 HIP_TRY(ctx, gdg_launch_block_fit(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_fit_table, p.d_fit_table, (unsigned)p.n_fits,
                                                   enc + steps[i].fit.at, ctx->stream));
+            if (p.n_gram)                                                    /* the Gram of the listed rows, on the matrix cores */
+                HIP_TRY(ctx, gdg_launch_block_gram(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_gram_port, p.d_gram_port, (unsigned)p.n_gram,
+                                                   reinterpret_cast<double *>(enc + steps[i].gram.at), ctx->stream));
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: the trimmed siblings of either; `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
@@ -338,7 +346,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = steps[i].fit.end;
+        const size_t down = steps[i].gram.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -558,6 +566,33 @@ int gdg_batch_fit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *
 
 int gdg_batch_fits(const gdg_ctx *ctx) { return ctx ? ctx->fit.count() : 0; }
 
+/* the Gram list: validated whole before it replaces the one in force (blend.h); the ports' upper bound is the job's, checked when one is described */
+int gdg_batch_gram_enable(gdg_ctx *ctx, const int *port, int n_ports) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "batch gram: a streamed batch run is open on this context; its list holds until gdg_batch_stream_close");
+    if (n_ports != 0) {
+        const int rc = gram_list_check(ctx, "batch gram", port, n_ports, 2, -1);
+        if (rc != GDG_OK) return rc;
+    }
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    if ((size_t)n_ports != ctx->gram_port.size()) {
+        /* another count: the download halves are made anew by the next batch call, at the size of a context that was always configured like
+         * this one -- whatever still reads them has to be done first -- and off, the list goes as well */
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i : { (int)BATCH_ENCODED, (int)BATCH_GRAM_PORTS }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    }
+    ctx->gram_port.assign(port, port + n_ports);
+    ctx->gram_rec.valid = false;                                             /* records are read with the list that made them */
+    return GDG_OK;
+}
+
+int gdg_batch_gram_ports(const gdg_ctx *ctx, int *port, int capacity) {
+    if (!ctx) return 0;
+    const int n = (int)ctx->gram_port.size();
+    if (port) for (int i = 0; i < n && i < capacity; i++) port[i] = ctx->gram_port[(size_t)i];
+    return n;
+}
+
 /* the master cursor belongs to gdg_batch_finish_master_slice, which is no part of an open job: it may be set while one is open */
 int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
     if (!ctx) return GDG_ERR_INVALID;
@@ -572,6 +607,10 @@ int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
 /* ... and a fit's ports are rows of the one-device window: the same refusal */
 #define FITS_REFUSED(ctx, what) \
     fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d fits are in force on this context (gdg_batch_fit_enable); a sharded job cannot collect fit records yet", what, (ctx)->fit.count())
+
+/* ... and so are a Gram list's */
+#define GRAM_REFUSED(ctx, what) \
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: a Gram list of %d ports is in force on this context (gdg_batch_gram_enable); a sharded job cannot collect Gram records yet", what, (int)(ctx)->gram_port.size())
 
 #define SHARD_PORTS " (a shard: its N inputs, its N outputs, metronome, left, right)"
 static int check_meter_ports(gdg_ctx *ctx, const gdg_batch_options *opt, const char *note) {
@@ -611,6 +650,12 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
                         n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
         if (f >= 0)
             return fail(ctx, GDG_ERR_INVALID, "batch fit: fit %d, term %d names port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", f, term, ctx->fit.port(f, term),
+                        n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
+    }
+    if (!shard && !ctx->gram_port.empty()) {                                     /* the list's ports against this call's */
+        const int at = gdg_gram_list_bad(ctx->gram_port.data(), (int)ctx->gram_port.size(), n_inputs + 3 + n_blends);
+        if (at >= 0)
+            return fail(ctx, GDG_ERR_INVALID, "batch gram: list entry %d names port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", at, ctx->gram_port[(size_t)at],
                         n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
     }
     int rc;
@@ -676,6 +721,7 @@ int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int
                                 int run_metronome, size_t *samples) {
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_open_shard");
+    if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_stream_open_shard");
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
     if (ctx && opt && opt->metronome_to_master)
         return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_open_shard: metronome_to_master must be 0 -- a shard's master mix is a partial sum; pass the metronome's "
@@ -739,6 +785,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     report_begin(ctx, sharded ? N + 1 : NR, (size_t)blocks, true, n_blends);
     const int n_fits = sharded ? 0 : ctx->fit.count();                           /* never a shard's: its calls refuse them */
     if (n_fits) fit_begin(ctx, (size_t)blocks);
+    const int n_gram = sharded ? 0 : (int)ctx->gram_port.size();                 /* never a shard's either */
+    if (n_gram) gram_begin(ctx, (size_t)blocks);
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -763,7 +811,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
-                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + fit_room((size_t)n_fits, (size_t)W);
+                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + fit_room((size_t)n_fits, (size_t)W) + gram_room((size_t)n_gram, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -933,7 +981,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr };
         /* the fits in force: their table goes up on the context's stream, ahead of everything the slice enqueues there; it lives as long as
          * the setting, so nothing waits here */
         if (n_fits) {
@@ -943,6 +991,14 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             loop.n_fits = n_fits;
             loop.h_fit_table = ctx->fit.table.data();
             loop.d_fit_table = d_table;
+        }
+        if (n_gram) {                                                        /* the Gram list likewise */
+            int *d_port = nullptr;
+            if ((r = batch_buffer(ctx, BATCH_GRAM_PORTS, (size_t)n_gram * sizeof(int), (void **)&d_port)) != GDG_OK) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(d_port, ctx->gram_port.data(), (size_t)n_gram * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            loop.n_gram = n_gram;
+            loop.h_gram_port = ctx->gram_port.data();
+            loop.d_gram_port = d_port;
         }
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
@@ -1020,6 +1076,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
     if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_step_shard");
+    if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_stream_step_shard");
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
 
@@ -1044,6 +1101,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
         ctx->batch_up_bytes = ctx->batch_resampled = 0;
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
         if (!shard) fit_begin(ctx, 0);
+        if (!shard) gram_begin(ctx, 0);
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
@@ -1064,6 +1122,7 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
     if (!shard) return GDG_ERR_INVALID;
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
     if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_run_shard");
+    if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_run_shard");
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
      * metronome track of the shard that ran it).  A set flag here would be silently dropped -- refuse it instead. */
     if (ctx && opt && opt->metronome_to_master)

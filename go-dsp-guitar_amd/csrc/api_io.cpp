@@ -1003,6 +1003,105 @@ int gdg_blend_weights_from_fit(const gdg_block_fit *records, int n_fits, size_t 
     return GDG_ERR_INVALID;
 }
 
+/* ---- the Gram of a port list (include/gdg.h, GRAM; the kernel: gram_kernels.h in gram.hip; the list's checks and the planner: blend.h; the batch calls fill it: api_batch.cpp) ---- */
+int gram_list_check(gdg_ctx *ctx, const char *what, const int *port, int n_ports, int least, int n_rows) {
+    if (n_ports < least || n_ports > GDG_GRAM_MAX_PORTS) return fail(ctx, GDG_ERR_INVALID, "%s: a list of %d ports; %d to %d", what, n_ports, least, GDG_GRAM_MAX_PORTS);
+    if (!port) return fail(ctx, GDG_ERR_INVALID, "%s: %d ports need a list", what, n_ports);
+    const int bad = gdg_gram_list_bad(port, n_ports, n_rows);
+    if (bad >= 0 && n_rows >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: list entry %d names row %d of %d", what, bad, port[bad], n_rows);
+    if (bad >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: list entry %d names port %d; ports start at 0", what, bad, port[bad]);
+    int earlier = -1;
+    const int again = gdg_gram_list_repeat(port, n_ports, &earlier);
+    if (again >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: list entry %d names port %d, which entry %d names already", what, again, port[again], earlier);
+    return GDG_OK;
+}
+
+static int block_gram_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, const int *port, int n_ports, size_t *blocks) {
+    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "block gram: %d rows (at least 1)", n_rows);
+    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block gram: blocks of %d samples (at least 1)", block);
+    const int rc = gram_list_check(ctx, "block gram", port, n_ports, 1, n_rows);
+    if (rc != GDG_OK) return rc;
+    *blocks = (samples + (size_t)block - 1) / (size_t)block;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block gram: %zu blocks per row are too many for one call", *blocks);
+    return GDG_OK;
+}
+
+/* the list is the caller's host memory: it goes up, the kernel runs, and the call returns when the records are written */
+int gdg_block_gram_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, const int *port, int n_ports, double *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_gram_check(ctx, n_rows, samples, block, port, n_ports, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (samples == 0) return GDG_OK;
+    if (!d_rows || !d_records) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block gram: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block gram: rows and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, (size_t)n_ports * sizeof(int)));
+    hipError_t e = hipMemcpyAsync(d, port, (size_t)n_ports * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        e = gdg_launch_block_gram(d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, port, static_cast<const int *>(d), (unsigned)n_ports, d_records, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block gram: %s", hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block gram: %s", hipGetErrorString(w));
+    return GDG_OK;
+}
+
+int gdg_block_gram_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, const int *port, int n_ports, double *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_gram_check(ctx, n_rows, samples, block, port, n_ports, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (samples == 0) return GDG_OK;
+    if (!rows || !records) return GDG_ERR_INVALID;
+    return rows_round_trip(ctx, "block gram", rows, n_rows, samples, records, blocks * gram_record_bytes((size_t)n_ports), [&](const double *d_rows, void *d_out) {
+        return gdg_block_gram_rows_device(ctx, d_rows, samples, n_rows, samples, block, port, n_ports, static_cast<double *>(d_out));
+    });
+}
+
+/* the getter: the Gram records' own store, by the four kinds' rule and in their words; capacity in doubles */
+int gdg_batch_gram(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const gdg_ctx::GramRecords &G = ctx->gram_rec;
+    if (!G.valid)
+        return fail(ctx, GDG_ERR_INVALID, "no Gram records: the last batch call of this context %s", !ctx->gram_port.empty()
+                    ? "has not completed, was a master finish, or none has run since gdg_batch_gram_enable" : "ran without them (gdg_batch_gram_enable comes before the call)");
+    if (blocks) *blocks = G.blocks;
+    if (!out) return GDG_OK;
+    if (capacity < G.store.size())
+        return fail(ctx, GDG_ERR_INVALID, "gram: room for %zu doubles, the call has %zu blocks x %d (%d + 1) / 2 = %zu", capacity, G.blocks, G.ports, G.ports, G.store.size());
+    if (!G.store.empty()) memcpy(out, G.store.data(), G.store.size() * sizeof(double));
+    return GDG_OK;
+}
+
+/* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
+int gdg_blend_pick_from_gram(const double *records, int n_ports, size_t blocks, int target, const int *candidate, int n_candidates, int max_terms, double ridge,
+                             double min_gain, int *picked, double *weight, double *residual, int *n_picked) {
+    int at = -1;
+    char msg[280];
+    switch (gdg_blend_pick(records, n_ports, blocks, target, candidate, n_candidates, max_terms, ridge, min_gain, picked, weight, residual, n_picked, &at)) {
+    case PICK_OK: return GDG_OK;
+    case PICK_POSITION:
+        if (at < 0) snprintf(msg, sizeof msg, "blend pick from gram: the target is list position %d of %d", target, n_ports);
+        else snprintf(msg, sizeof msg, "blend pick from gram: candidate %d is list position %d of %d", at, candidate[at], n_ports);
+        break;
+    case PICK_REPEAT: snprintf(msg, sizeof msg, "blend pick from gram: candidate %d is list position %d, which is the target or an earlier candidate", at, candidate[at]); break;
+    case PICK_NONFINITE: snprintf(msg, sizeof msg, "blend pick from gram: the summed Gram has a NaN or inf entry at list position %d (the block statistics count non-finite samples per port)", at); break;
+    case PICK_SILENT: snprintf(msg, sizeof msg, "blend pick from gram: the target (list position %d) is silent: its energy over the %zu blocks is not above 0", target, blocks); break;
+    default:
+        snprintf(msg, sizeof msg, "blend pick from gram: %d ports (2 to %d), %zu blocks (at least 1), %d candidates (1 to ports - 1), max_terms = %d (1 to %d), ridge = %g and "
+                 "min_gain = %g (finite, >= 0); records, candidate, picked, weight, residual and n_picked are needed", n_ports, GDG_GRAM_MAX_PORTS, blocks, n_candidates, max_terms,
+                 GDG_FIT_MAX_TERMS, ridge, min_gain);
+        break;
+    }
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
+}
+
 /* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */
 static_assert(sizeof(gdg_block_true_peak) == 16 && offsetof(gdg_block_true_peak, position) == 8 && offsetof(gdg_block_true_peak, overs) == 12,
               "gdg_block_true_peak: 16 bytes, no padding");

@@ -6,7 +6,9 @@
  * the validation of a blend list in its CSR form, the rule by which a list replaces the one in force, the sum on the host, and the planner
  * that turns alignment records into delays and signs (gdg_blend_delays_from_align); and, for the blend fit (include/gdg.h, FIT), the
  * validation of a list of fits, the table a launch reads, and the planner that turns fit records into weights (gdg_blend_weights_from_fit;
- * tests/native/fit_plan_check.cpp).  No HIP header is needed to compile this file.
+ * tests/native/fit_plan_check.cpp); and, for the Gram of a port list (include/gdg.h, GRAM), the validation of the list, the packed index
+ * and the greedy planner that picks ports from Gram records (gdg_blend_pick_from_gram; tests/native/gram_plan_check.cpp).  No HIP header
+ * is needed to compile this file.
  */
 #ifndef GDG_BLEND_H
 #define GDG_BLEND_H
@@ -349,6 +351,50 @@ enum {
     FIT_PLAN_PIVOT = 3                         /* the factorisation of *fit met a pivot at or below the bound: a silent term, or a port twice without a ridge */
 };
 
+/* The ONE solve, for a fit's sums and for a pick's (gdg_blend_pick): T, b[K] and the lower triangle of G[K][K] in -> (G + ridge * mean(diag G)
+ * I) w = b by an unpivoted Cholesky factorisation in term order, *res = max(0, T - 2 w.b + w'Gw) / T (0 where T == 0).  false: a pivot at
+ * or below K * 2^-52 * max(diag G); w and *res are then not to be used.  The upper triangle of G is filled here. */
+static inline bool gdg_fit_solve(int K, double T, const double *b, double (*G)[GDG_FIT_MAX_TERMS], double ridge, double *w, double *res) {
+    constexpr int M = GDG_FIT_MAX_TERMS;
+    for (int j = 0; j < K; j++) for (int k = j + 1; k < K; k++) G[j][k] = G[k][j];
+    double trace = 0.0, most = 0.0;
+    for (int j = 0; j < K; j++) { trace += G[j][j]; if (G[j][j] > most) most = G[j][j]; }
+    const double shift = ridge * (trace / (double)K), least = (double)K * 2.220446049250313e-16 * most;      /* K * 2^-52 * max(diag G) */
+    double Lo[M][M];
+    for (int j = 0; j < K; j++) {
+        double d = G[j][j] + shift;
+        for (int k = 0; k < j; k++) d -= Lo[j][k] * Lo[j][k];
+        if (!(d > least)) return false;
+        Lo[j][j] = sqrt(d);
+        for (int i = j + 1; i < K; i++) {
+            double s = G[i][j];
+            for (int k = 0; k < j; k++) s -= Lo[i][k] * Lo[j][k];
+            Lo[i][j] = s / Lo[j][j];
+        }
+    }
+    double y[M];
+    for (int j = 0; j < K; j++) {                                        /* L y = b, then L' w = y */
+        double s = b[j];
+        for (int k = 0; k < j; k++) s -= Lo[j][k] * y[k];
+        y[j] = s / Lo[j][j];
+    }
+    for (int j = K - 1; j >= 0; j--) {
+        double s = y[j];
+        for (int k = j + 1; k < K; k++) s -= Lo[k][j] * w[k];
+        w[j] = s / Lo[j][j];
+    }
+    double wb = 0.0, wGw = 0.0;
+    for (int j = 0; j < K; j++) {
+        wb += w[j] * b[j];
+        double row = 0.0;
+        for (int k = 0; k < K; k++) row += G[j][k] * w[k];
+        wGw += w[j] * row;
+    }
+    const double left = T - 2.0 * wb + wGw;
+    *res = T == 0.0 ? 0.0 : (left > 0.0 ? left : 0.0) / T;
+    return true;
+}
+
 /* records[n_fits][blocks].  Per fit: the blocks' sums added in block order -- T, b[K], G[K][K] --, (G + ridge * mean(diag G) * I) w = b by
  * an unpivoted Cholesky factorisation in term order, residual = max(0, T - 2 w.b + w'Gw) / T (0 where T == 0).  Every fit is solved before
  * weight[n_fits][8] and residual[n_fits] are written; *fit: the offender. */
@@ -374,47 +420,114 @@ static inline int gdg_blend_plan_weights(const gdg_blend_fit_rec *records, int n
                 for (int k = 0; k <= j; k++) G[j][k] += rec[q].xx[j * (j + 1) / 2 + k];
             }
         }
-        for (int j = 0; j < K; j++) for (int k = j + 1; k < K; k++) G[j][k] = G[k][j];
-        double trace = 0.0, most = 0.0;
-        for (int j = 0; j < K; j++) { trace += G[j][j]; if (G[j][j] > most) most = G[j][j]; }
-        const double shift = ridge * (trace / (double)K), least = (double)K * 2.220446049250313e-16 * most;      /* K * 2^-52 * max(diag G) */
-        double Lo[M][M];
-        for (int j = 0; j < K; j++) {
-            double d = G[j][j] + shift;
-            for (int k = 0; k < j; k++) d -= Lo[j][k] * Lo[j][k];
-            if (!(d > least)) return FIT_PLAN_PIVOT;
-            Lo[j][j] = sqrt(d);
-            for (int i = j + 1; i < K; i++) {
-                double s = G[i][j];
-                for (int k = 0; k < j; k++) s -= Lo[i][k] * Lo[j][k];
-                Lo[i][j] = s / Lo[j][j];
-            }
-        }
-        double y[M], *w = &w_all[(size_t)f * M];
-        for (int j = 0; j < K; j++) {                                        /* L y = b, then L' w = y */
-            double s = b[j];
-            for (int k = 0; k < j; k++) s -= Lo[j][k] * y[k];
-            y[j] = s / Lo[j][j];
-        }
-        for (int j = K - 1; j >= 0; j--) {
-            double s = y[j];
-            for (int k = j + 1; k < K; k++) s -= Lo[k][j] * w[k];
-            w[j] = s / Lo[j][j];
-        }
-        double wb = 0.0, wGw = 0.0;
-        for (int j = 0; j < K; j++) {
-            wb += w[j] * b[j];
-            double row = 0.0;
-            for (int k = 0; k < K; k++) row += G[j][k] * w[k];
-            wGw += w[j] * row;
-        }
-        const double left = T - 2.0 * wb + wGw;
-        res_all[(size_t)f] = T == 0.0 ? 0.0 : (left > 0.0 ? left : 0.0) / T;
+        if (!gdg_fit_solve(K, T, b, G, ridge, &w_all[(size_t)f * M], &res_all[(size_t)f])) return FIT_PLAN_PIVOT;
     }
     *fit = -1;
     memcpy(weight, w_all.data(), w_all.size() * sizeof(double));
     memcpy(residual, res_all.data(), res_all.size() * sizeof(double));
     return FIT_PLAN_OK;
+}
+
+/* ---- the Gram of a port list (include/gdg.h, GRAM): the list, the packed index, and the picks from its records (gdg_blend_pick_from_gram) ---- */
+#ifndef GDG_GRAM_MAX_PORTS
+#define GDG_GRAM_MAX_PORTS 512
+#endif
+
+/* entry (i, j), j <= i, of a record: the lower triangle by rows -- the fit's xx layout */
+static inline size_t gdg_gram_index(size_t i, size_t j) { return i * (i + 1) / 2 + j; }
+static inline size_t gdg_gram_doubles(size_t n_ports) { return n_ports * (n_ports + 1) / 2; }
+
+/* the first entry of a list outside [0, n_rows) -- n_rows < 0: the count is not known yet (the job's N + 3 + B), only negatives --, -1 = none */
+static inline int gdg_gram_list_bad(const int *port, int n_ports, int n_rows) {
+    for (int i = 0; i < n_ports; i++) if (port[i] < 0 || (n_rows >= 0 && port[i] >= n_rows)) return i;
+    return -1;
+}
+
+/* the first entry that repeats an earlier one, -1 = none; *earlier: that one's position */
+static inline int gdg_gram_list_repeat(const int *port, int n_ports, int *earlier) {
+    for (int i = 1; i < n_ports; i++)
+        for (int j = 0; j < i; j++) if (port[j] == port[i]) { *earlier = j; return i; }
+    return -1;
+}
+
+enum {
+    PICK_OK = 0,
+    PICK_ARGS = 1,                             /* a list is missing, a count is out of range, no block, ridge or min_gain negative or not finite */
+    PICK_POSITION = 2,                         /* the target or candidate *at lies outside the list (*at = -1: the target) */
+    PICK_REPEAT = 3,                           /* candidate *at repeats an earlier one or is the target */
+    PICK_NONFINITE = 4,                        /* the summed Gram has a NaN or inf in the row or column of list position *at */
+    PICK_SILENT = 5                            /* T = G[target][target] <= 0 */
+};
+
+/* records[blocks][n_ports (n_ports + 1) / 2]; target and candidate[] are positions in the list.  The blocks' records are added in block
+ * order with plain adds; T = G[target][target].  Greedy forward selection: with the set S picked so far, in pick order, every candidate not
+ * in S is tried in list order -- gdg_fit_solve on S and the candidate, whose unpivoted factorisation extends the one of S by the candidate's
+ * row; a candidate that brings a pivot at or below the bound is skipped: a silent port, or a duplicate of a picked one --, the smallest
+ * residual share wins, the earlier entry on a tie.  It stops after max_terms picks, when the best candidate improves the share by less than
+ * min_gain (the share before the first pick is 1), or when no candidate is admissible.  Everything is decided before picked[8], weight[8],
+ * residual[8] and *n_picked are written; entries behind *n_picked are -1, 0.0 and 0.0.  The weights are those of gdg_fit_solve for the picked
+ * ports in pick order: bit for bit gdg_blend_plan_weights on a fit record with the same sums. */
+static inline int gdg_blend_pick(const double *records, int n_ports, size_t blocks, int target, const int *candidate, int n_candidates, int max_terms, double ridge,
+                                 double min_gain, int *picked, double *weight, double *residual, int *n_picked, int *at) {
+    *at = -1;
+    constexpr int M = GDG_FIT_MAX_TERMS;
+    if (n_ports < 2 || n_ports > GDG_GRAM_MAX_PORTS || blocks == 0 || n_candidates < 1 || n_candidates >= n_ports || max_terms < 1 || max_terms > M ||
+        !(ridge >= 0.0) || !isfinite(ridge) || !(min_gain >= 0.0) || !isfinite(min_gain) || !records || !candidate || !picked || !weight || !residual || !n_picked)
+        return PICK_ARGS;
+    if (target < 0 || target >= n_ports) return PICK_POSITION;
+    for (int c = 0; c < n_candidates; c++) {
+        *at = c;
+        if (candidate[c] < 0 || candidate[c] >= n_ports) return PICK_POSITION;
+        if (candidate[c] == target) return PICK_REPEAT;
+        for (int d = 0; d < c; d++) if (candidate[d] == candidate[c]) return PICK_REPEAT;
+    }
+    const size_t E = gdg_gram_doubles((size_t)n_ports);
+    std::vector<double> sum(E, 0.0);
+    for (size_t q = 0; q < blocks; q++) for (size_t e = 0; e < E; e++) sum[e] += records[q * E + e];
+    auto g = [&](int i, int j) { return i >= j ? sum[gdg_gram_index((size_t)i, (size_t)j)] : sum[gdg_gram_index((size_t)j, (size_t)i)]; };
+    /* what the picks can read: the entries among the target and the candidates */
+    for (int a = -1; a < n_candidates; a++) {
+        const int i = a < 0 ? target : candidate[a];
+        *at = i;
+        if (!isfinite(g(i, target))) return PICK_NONFINITE;
+        for (int c = 0; c < n_candidates; c++) if (!isfinite(g(i, candidate[c]))) return PICK_NONFINITE;
+    }
+    *at = -1;
+    const double T = g(target, target);
+    if (!(T > 0.0)) return PICK_SILENT;
+    int S[M], n = 0;
+    double w_S[M], res_S[M], before = 1.0;
+    for (int k = 0; k < M; k++) { S[k] = -1; w_S[k] = res_S[k] = 0.0; }
+    while (n < max_terms) {
+        int best = -1;
+        double best_res = 0.0, best_w[M];
+        for (int c = 0; c < n_candidates; c++) {
+            bool in = false;
+            for (int k = 0; k < n; k++) in = in || S[k] == candidate[c];
+            if (in) continue;
+            S[n] = candidate[c];
+            double b[M], G[M][M], w[M], res = 0.0;
+            for (int j = 0; j <= n; j++) {
+                b[j] = g(target, S[j]);
+                for (int k = 0; k <= j; k++) G[j][k] = g(S[j], S[k]);
+            }
+            if (!gdg_fit_solve(n + 1, T, b, G, ridge, w, &res)) continue;        /* skipped, not refused */
+            if (best < 0 || res < best_res) {
+                best = candidate[c];
+                best_res = res;
+                for (int k = 0; k <= n; k++) best_w[k] = w[k];
+            }
+        }
+        S[n] = -1;
+        if (best < 0 || before - best_res < min_gain) break;
+        S[n] = best;
+        res_S[n] = before = best_res;
+        for (int k = 0; k <= n; k++) w_S[k] = best_w[k];
+        n++;
+    }
+    for (int k = 0; k < M; k++) { picked[k] = S[k]; weight[k] = w_S[k]; residual[k] = res_S[k]; }
+    *n_picked = n;
+    return PICK_OK;
 }
 
 #endif

@@ -64,4 +64,22 @@ static inline FitSection fit_section(size_t end, size_t fits, size_t w) {
 /* ... and what a half holds for them for a window of W blocks, beside report_room */
 static inline size_t fit_room(size_t fits, size_t W) { return fits ? 16 + fits * W * FIT_RECORD_BYTES : 0; }
 
+/* The Gram records (include/gdg.h, GRAM) ride behind the fit section -- behind whatever precedes it when there is none -- from the next 16
+ * bytes on: [w] records of P (P + 1) / 2 doubles for a list of P ports.  No list: no byte.  The finish calls never carry them. */
+struct GramSection { size_t at, bytes, end; };
+
+static inline size_t gram_record_bytes(size_t ports) { return ports * (ports + 1) / 2 * 8; }
+
+static inline GramSection gram_section(size_t end, size_t ports, size_t w) {
+    GramSection s = { end, 0, end };
+    if (!ports) return s;
+    s.at = (end + 15) & ~(size_t)15;
+    s.bytes = w * gram_record_bytes(ports);
+    s.end = s.at + s.bytes;
+    return s;
+}
+
+/* ... and what a half holds for them for a window of W blocks */
+static inline size_t gram_room(size_t ports, size_t W) { return ports ? 16 + W * gram_record_bytes(ports) : 0; }
+
 #endif

@@ -2452,3 +2452,220 @@ func BlendWeightsFromFit(records [][]BlockFit, ridge float64) ([][]float64, []fl
 	}
 	return weights, residual, nil
 }
+
+// GramIndex: the place of entry (i, j) in a Gram record -- the lower triangle by rows, the fit's Xx layout -- for either order of i and j.
+func GramIndex(i int, j int) int {
+	if j > i {
+		return j*(j+1)/2 + i
+	}
+	return i*(i+1)/2 + j
+}
+
+// gramList: a list of ports in C memory, one spare entry behind it, which the caller frees; the library validates it.
+func gramList(ports []int) (list *[1 << 28]C.int, release func()) {
+	p := C.calloc(C.size_t(len(ports)+1), 4)
+	if p == nil {
+		return nil, func() {}
+	}
+	list = (*[1 << 28]C.int)(p)
+	for i, v := range ports {
+		list[i] = C.int(v)
+	}
+	return list, func() { C.free(p) }
+}
+
+func goGram(p unsafe.Pointer, blocks int, per int) [][]float64 {
+	out := make([][]float64, blocks)
+	if blocks*per == 0 {
+		for b := range out {
+			out[b] = []float64{}
+		}
+		return out
+	}
+	vals := (*[1 << 37]float64)(p)[: blocks*per : blocks*per]
+	for b := range out {
+		out[b] = make([]float64, per)
+		copy(out[b], vals[b*per:(b+1)*per])
+	}
+	return out
+}
+
+// BatchGramEnable: from the next batch call on, every batch call of the context keeps the Gram records of what it rendered
+// (gdg_batch_gram_enable): one list of 2 to 512 different ports of the call -- chain outputs, master left, master right, metronome, blend
+// ports.  nil or an empty slice switches it off.  Configuration, like BatchFitEnable: a checkpoint does not carry it, and an error while a
+// streamed job is open.
+func (this *Context) BatchGramEnable(ports []int) error {
+	if len(ports) == 0 {
+		return this.err(C.gdg_batch_gram_enable(this.ctx, nil, 0))
+	}
+	list, release := gramList(ports)
+	if list == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_batch_gram_enable(this.ctx, &list[0], C.int(len(ports))))
+}
+
+// BatchGramPorts: the Gram list in force (gdg_batch_gram_ports); empty: off.
+func (this *Context) BatchGramPorts() []int {
+	n := int(C.gdg_batch_gram_ports(this.ctx, nil, 0))
+	out := make([]int, n)
+	if n == 0 {
+		return out
+	}
+	list, release := gramList(out)
+	if list == nil {
+		return []int{}
+	}
+	defer release()
+	C.gdg_batch_gram_ports(this.ctx, &list[0], C.int(n))
+	for i := range out {
+		out[i] = int(list[i])
+	}
+	return out
+}
+
+// BatchGram: the Gram records of the last completed batch call, result[block][GramIndex(i, j)] with i and j positions in the list
+// (gdg_batch_gram).  An error when the call ran without them, or was a master finish.
+func (this *Context) BatchGram() ([][]float64, error) {
+	var blocks C.size_t
+	if e := this.err(C.gdg_batch_gram(this.ctx, nil, 0, &blocks)); e != nil {
+		return nil, e
+	}
+	p := len(this.BatchGramPorts())
+	per := p * (p + 1) / 2
+	n := int(blocks) * per
+	if n == 0 {
+		return goGram(nil, int(blocks), per), nil
+	}
+	rec := (*[1 << 28]C.double)(C.calloc(C.size_t(n), 8))
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	if e := this.err(C.gdg_batch_gram(this.ctx, &rec[0], C.size_t(n), &blocks)); e != nil {
+		return nil, e
+	}
+	return goGram(unsafe.Pointer(rec), int(blocks), per), nil
+}
+
+// BlockGramRows: the Gram records of equally long host rows per block of `block` samples, the last one of a row possibly short
+// (gdg_block_gram_rows); ports names 1 to 512 different rows; result[block][GramIndex(i, j)].
+func (this *Context) BlockGramRows(rows [][]float64, block int, ports []int) ([][]float64, error) {
+	n := len(rows)
+	if n == 0 || block < 1 || len(ports) == 0 {
+		return nil, fmt.Errorf("gdg: %d rows, blocks of %d samples, %d ports", n, block, len(ports))
+	}
+	samples := len(rows[0])
+	blocks := (samples + block - 1) / block
+	per := len(ports) * (len(ports) + 1) / 2
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	list, release := gramList(ports)
+	if list == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	out := C.calloc(C.size_t(blocks*per+1), 8)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_gram_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(block), &list[0], C.int(len(ports)), (*C.double)(out))); e != nil {
+		return nil, e
+	}
+	return goGram(out, blocks, per), nil
+}
+
+// BlockGramRowsDevice: the same on device memory (gdg_block_gram_rows_device): row r at dRows + r*rowStride float64 (any 8-byte alignment,
+// rowStride >= samples), the records into dRecords[ceil(samples/block)][P*(P+1)/2]; returns when they are written.
+func (this *Context) BlockGramRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, block int, ports []int, dRecords unsafe.Pointer) error {
+	if len(ports) == 0 {
+		return fmt.Errorf("gdg: no ports")
+	}
+	list, release := gramList(ports)
+	if list == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_block_gram_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(block), &list[0], C.int(len(ports)),
+		(*C.double)(dRecords)))
+}
+
+// BlendPickFromGram: up to maxTerms (1 to 8) of the candidates, picked greedily from Gram records so that their least-squares blend comes
+// closest to the target (gdg_blend_pick_from_gram): records[block] as BatchGram hands them out for a list of nPorts ports; target and
+// candidates are positions in that list.  picked holds list positions in pick order, weights their weights, residual[m] the share of the
+// target's energy left after pick m.  Host arithmetic: no context and no device.  An error for a silent target, a NaN or inf entry, a
+// repeated candidate.
+func BlendPickFromGram(records [][]float64, nPorts int, target int, candidates []int, maxTerms int, ridge float64, minGain float64) ([]int, []float64, []float64, error) {
+	blocks := len(records)
+	per := nPorts * (nPorts + 1) / 2
+	if blocks == 0 || nPorts < 2 || len(candidates) == 0 {
+		return nil, nil, nil, fmt.Errorf("gdg: %d blocks (at least 1), %d ports (at least 2), %d candidates (at least 1)", blocks, nPorts, len(candidates))
+	}
+	for b, row := range records {
+		if len(row) != per {
+			return nil, nil, nil, fmt.Errorf("gdg: record %d has %d entries, %d ports make %d", b, len(row), nPorts, per)
+		}
+	}
+	rec := (*[1 << 28]C.double)(C.calloc(C.size_t(blocks*per+1), 8))
+	if rec == nil {
+		return nil, nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	for b, row := range records {
+		for e, v := range row {
+			rec[b*per+e] = C.double(v)
+		}
+	}
+	list, release := gramList(candidates)
+	if list == nil {
+		return nil, nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	res := (*[1 << 28]C.double)(C.calloc(17, 8))
+	if res == nil {
+		return nil, nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(res))
+	got, releaseGot := gramList(make([]int, 8))
+	if got == nil {
+		return nil, nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer releaseGot()
+	var n C.int
+	if rc := C.gdg_blend_pick_from_gram(&rec[0], C.int(nPorts), C.size_t(blocks), C.int(target), &list[0], C.int(len(candidates)), C.int(maxTerms), C.double(ridge), C.double(minGain),
+		&got[0], &res[0], &res[8], &n); rc != 0 {
+		return nil, nil, nil, fmt.Errorf("gdg: gdg_blend_pick_from_gram: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	picked := make([]int, int(n))
+	weights := make([]float64, int(n))
+	residual := make([]float64, int(n))
+	for m := range picked {
+		picked[m] = int(got[m])
+		weights[m] = float64(res[m])
+		residual[m] = float64(res[8+m])
+	}
+	return picked, weights, residual, nil
+}

@@ -54,6 +54,9 @@ def lib():
             "gdgh_engine_set_batch_fits": (cs, [vp, i32, vp, vp, vp]),
             "gdgh_engine_batch_fits": (i32, [vp]),
             "gdgh_engine_last_batch_fit": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdgh_engine_set_batch_gram": (cs, [vp, vp, i32]),
+            "gdgh_engine_batch_gram_ports": (i32, [vp]),
+            "gdgh_engine_last_batch_gram": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -134,6 +137,7 @@ class Engine:
         self.last_spectrum = None        # the band spectrum of the last batch call made with spectrum=edges: [N + 3, blocks, bands] float64
         self.last_true_peak = None       # the true-peak records of the last batch call made with true_peak=True: [N + 3, blocks] records
         self.last_fit = None             # the fit records of the last batch call made with fits=: [fits, blocks] records (FIT_DTYPE)
+        self.last_gram = None            # the Gram records of the last batch call made with gram=: [blocks, P (P + 1) / 2] float64
         self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
     def shards(self):
@@ -343,6 +347,57 @@ class Engine:
         _err(lib().gdgh_engine_last_batch_fit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(fits), C.byref(blocks)))
         return out
 
+    def _set_gram(self, gram):
+        """Engine::SetBatchGram, from the `gram` argument of the batch calls: a list of 2 to 512 different ports; None or an empty list: off.
+        Returns the number of ports in force.  Refused on an engine of more than one shard."""
+        self.last_gram = None
+        ports = np.array([] if gram is None else [int(p) for p in gram], dtype=np.int32)
+        _err(lib().gdgh_engine_set_batch_gram(self._h, ports.ctypes.data if ports.size else None, ports.size))
+        return int(lib().gdgh_engine_batch_gram_ports(self._h))
+
+    def _fetch_gram(self):
+        """Engine::LastBatchGram -> [blocks, P (P + 1) / 2] float64"""
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_gram(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((blocks.value, ports.value * (ports.value + 1) // 2), dtype=np.float64)
+        _err(lib().gdgh_engine_last_batch_gram(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
+    def render_matched(self, target, candidates, max_terms, inputs, target_rate, out_format, ridge=0.0, min_gain=0.0, window=16, sample_rate=None, **kw):
+        """Two passes over one job: which few of `candidates`, in which mix, come closest to port `target` (a chain output, master left,
+        master right or the metronome).  A candidate is a job channel, or (job channel, delay, sign) -- then it is measured as the port of a
+        one-term blend that delays it and turns its polarity, as in render_fitted.  save_state; pass 1 renders with every output skipped and
+        the Gram list [target] + candidates on; the planner (blend_pick_from_gram) picks up to max_terms of them greedily; load_state;
+        pass 2 renders with the one blend of the picked candidates at weights sign * w and their delays.  Returns (outs, picked, weights,
+        residuals): the N + 3 + 1 output data sections (N + 3 when nothing was picked), the positions in `candidates` in pick order, the
+        weights as fitted (before the signs) and the share of the target's energy left after every pick.  Pass 1's records stay in
+        matched_records.  kw: batch_run's other arguments (gram, fits, blends and blend_gain in kw are replaced)."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        n3 = self.n_channels + 3
+        cands = [(int(c), 0, 1) if np.isscalar(c) else (int(c[0]), int(c[1]), int(c[2])) for c in candidates]
+        if not 1 <= len(cands) <= pkg.GRAM_MAX_PORTS - 1:
+            raise HostError("render_matched: %d candidates; 1 to %d" % (len(cands), pkg.GRAM_MAX_PORTS - 1))
+        if not 0 <= int(target) < n3:
+            raise HostError("render_matched: the target is port %d; the job has ports 0 to %d" % (target, n3 - 1))
+        if any(g not in (1, -1) for _, _, g in cands):
+            raise HostError("render_matched: a candidate's sign is +1 or -1")
+        rate = target_rate if sample_rate is None else sample_rate
+        _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
+        blob = self.save_state()
+        rest = {k: v for k, v in kw.items() if k not in ("gram", "fits", "blends", "blend_gain", "skip_outputs")}
+        shaped = [k for k, (_, d, g) in enumerate(cands) if d or g != 1]       # these go through a one-term blend each: ports N + 3 + ...
+        first = [[(cands[k][0], float(cands[k][2]), cands[k][1])] for k in shaped]
+        ports = [n3 + shaped.index(k) if k in shaped else cands[k][0] for k in range(len(cands))]
+        self.batch_run(inputs, target_rate, out_format, window=window, blends=first or None, gram=[int(target)] + ports, skip_outputs=True, **rest)
+        self.matched_records = self.last_gram
+        picked, weights, residuals = pkg.blend_pick_from_gram(self.matched_records, 1 + len(cands), 0, list(range(1, 1 + len(cands))), max_terms, ridge, min_gain)
+        picked = [p - 1 for p in picked]
+        self.load_state(blob, rate)
+        blend = [[(cands[k][0], cands[k][2] * float(w), cands[k][1]) for k, w in zip(picked, weights)]] if picked else None
+        outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=blend, **rest)
+        return outs, picked, [float(w) for w in weights], [float(r) for r in residuals]
+
     def render_fitted(self, target, terms, inputs, target_rate, out_format, ridge=0.0, delays=None, signs=None, window=16, sample_rate=None, **kw):
         """Two passes over one job: the blend of the chain outputs `terms` (job channels, 1 to 8) that comes closest to port `target` (a chain
         output, master left, master right or the metronome) in the least-squares sense.  save_state; pass 1 renders with every output
@@ -441,7 +496,7 @@ class Engine:
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
@@ -450,7 +505,8 @@ class Engine:
         off).  skip_outputs: every output pointer NULL -- the job renders and measures, nothing is written; returns None.  blends: a list
         of lists of (job channel, weight) or (job channel, weight, delay), blend_gain: one output gain per blend -- B more outputs and B more ports in every last_* record
         list, behind the metronome's (one-shard engines only; None: off).  fits: a list of (target port, [term ports]) -- keep the fit
-        records in last_fit ([fits, blocks], FIT_DTYPE; one-shard engines only; None: off)."""
+        records in last_fit ([fits, blocks], FIT_DTYPE; one-shard engines only; None: off).  gram: a list of 2 to 512 different ports -- keep the
+        Gram records in last_gram ([blocks, P (P + 1) / 2] float64; one-shard engines only; None: off)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
@@ -458,6 +514,7 @@ class Engine:
         self._set_trim(trim)
         nb = self._set_blends(blends, blend_gain)            # before the alignment list, which may name blend ports
         fitted = self._set_fits(fits)
+        grammed = self._set_gram(gram)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -500,19 +557,21 @@ class Engine:
             self.last_true_peak = self._fetch_true_peak()
         if fitted:
             self.last_fit = self._fetch_fit()
+        if grammed:
+            self.last_gram = self._fetch_gram()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces (and one per blend of blends= / blend_gain=, as batch_run's).  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]; fits=: last_fit likewise,
-        [fits, blocks]."""
+        [fits, blocks]; gram=: last_gram likewise, [blocks, P (P + 1) / 2]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
                                   metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
-                                  blends=blends, blend_gain=blend_gain, fits=fits)
+                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -537,7 +596,7 @@ class Engine:
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
@@ -546,6 +605,7 @@ class Engine:
         self._set_trim(trim)
         nb = self._set_blends(blends, blend_gain)            # the sharded form passes none: off
         fitted = self._set_fits(fits)                        # ... and no fits
+        grammed = self._set_gram(gram)                       # ... and no Gram list
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -600,6 +660,9 @@ class Engine:
                 if fitted:
                     ft = self._fetch_fit()
                     self.last_fit = ft if self.last_fit is None else np.concatenate([self.last_fit, ft], axis=1)
+                if grammed:
+                    gm = self._fetch_gram()
+                    self.last_gram = gm if self.last_gram is None else np.concatenate([self.last_gram, gm], axis=0)
                 yield outs
                 left -= blocks
         finally:

@@ -1049,6 +1049,34 @@ Error Engine::LastBatchFit(std::vector<gdg_block_fit> &records, int *fits, size_
     return "";
 }
 
+/* Engine::SetBatchGram: validated whole before the list replaces the one in force (the library checks again, and the ports against the job's) */
+Error Engine::SetBatchGram(const std::vector<int> &ports) {
+    if (ports.empty()) { gramPort_.clear(); return ""; }
+    if (shards() > 1)
+        return format("SetBatchGram: the engine has %d shards: the list's ports are rows of one device's window, and the library's shard calls refuse a Gram list; it needs a "
+                      "one-shard engine", shards());
+    if (ports.size() < 2 || ports.size() > GDG_GRAM_MAX_PORTS) return format("SetBatchGram: a list of %zu ports; 2 to %d", ports.size(), GDG_GRAM_MAX_PORTS);
+    for (size_t i = 0; i < ports.size(); i++) {
+        if (ports[i] < 0) return format("SetBatchGram: list entry %zu names port %d; ports start at 0", i, ports[i]);
+        for (size_t j = 0; j < i; j++) if (ports[j] == ports[i]) return format("SetBatchGram: list entry %zu names port %d, which entry %zu names already", i, ports[i], j);
+    }
+    gramPort_ = ports;
+    return "";
+}
+
+int Engine::applyGram(gdg_ctx *ctx) {
+    if (gramPort_.empty()) return gdg_batch_gram_enable(ctx, nullptr, 0);
+    return gdg_batch_gram_enable(ctx, gramPort_.data(), BatchGramPorts());
+}
+
+Error Engine::LastBatchGram(std::vector<double> &records, int *ports, size_t *blocks) const {
+    if (!gramValid_) return "LastBatchGram: the last batch call kept no Gram records (SetBatchGram comes before the call)";
+    records = lastGram_;
+    if (ports) *ports = gramPorts_;
+    if (blocks) *blocks = gramBlocks_;
+    return "";
+}
+
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
  * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
  * controller.go:3005-3045). */
@@ -1074,7 +1102,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1094,7 +1122,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
+    if (job == 0) { gramValid_ = BatchGramPorts() > 0; gramBlocks_ = 0; gramPorts_ = BatchGramPorts(); lastGram_.clear(); fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
     /* blends or fits in force (one shard: SetBatchBlends, SetBatchFits): the library's plain one-call run -- its shard calls refuse both --
      * with `outs` of N + 3 + B entries; the alignment list goes on in its plain form, and the context's records of every kind are the engine's */
     if (plainRun()) {
@@ -1152,7 +1180,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
  * [N + 3][blocks] in gdg_batch_run's port order and from three sources -- the shards' chain rows, shard 0's metronome row, the finish's two
  * master rows (which carry no alignment records: over shards those rows stay zero) ---- */
 void Engine::reportBegin(size_t blocks) {
-    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = false;
+    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = false;
     reportBlocks_ = blocks;
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
     const size_t n = (size_t)ports() * blocks;
@@ -1354,7 +1382,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1398,6 +1426,18 @@ Error Engine::recordsOfContext(gdg_ctx *ctx) {
             fitBlocks_ = blocks;
             if (!lastFit_.empty() && gdg_batch_fit(ctx, lastFit_.data(), lastFit_.size(), &fits, &blocks) != GDG_OK) re = gdg_last_error(ctx);
             else fitValid_ = true;
+        }
+    }
+    if (re.empty() && BatchGramPorts() > 0) {              /* the Gram records: [blocks][P (P + 1) / 2] */
+        size_t blocks = 0;
+        const size_t per = (size_t)BatchGramPorts() * ((size_t)BatchGramPorts() + 1) / 2;
+        if (gdg_batch_gram(ctx, nullptr, 0, &blocks) != GDG_OK) re = gdg_last_error(ctx);
+        else {
+            lastGram_.assign(blocks * per, 0.0);
+            gramBlocks_ = blocks;
+            gramPorts_ = BatchGramPorts();
+            if (!lastGram_.empty() && gdg_batch_gram(ctx, lastGram_.data(), lastGram_.size(), &blocks) != GDG_OK) re = gdg_last_error(ctx);
+            else gramValid_ = true;
         }
     }
     if (!re.empty()) { setError(re); return LastError(); }
@@ -1973,6 +2013,28 @@ const char *gdgh_engine_last_batch_fit(void *e, gdg_block_fit *records, size_t c
     if (records) {
         if (capacity < rec.size()) return ret(Error("LastBatchFit: too little room for the records"));
         if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_fit));
+    }
+    return ret(Error(""));
+}
+/* n_ports == 0: off */
+const char *gdgh_engine_set_batch_gram(void *e, const int *port, int n_ports) {
+    if (!e) return ret(Error("no engine"));
+    if (n_ports < 0 || (n_ports > 0 && !port)) return ret(Error("SetBatchGram: n_ports >= 0, and the list"));
+    return ret(((Engine *)e)->SetBatchGram(n_ports ? std::vector<int>(port, port + n_ports) : std::vector<int>()));
+}
+int gdgh_engine_batch_gram_ports(void *e) { return ((Engine *)e)->BatchGramPorts(); }
+/* records == NULL: the two counts only; capacity in doubles */
+const char *gdgh_engine_last_batch_gram(void *e, double *records, size_t capacity, int *ports, size_t *blocks) {
+    std::vector<double> rec;
+    int p = 0;
+    size_t b = 0;
+    Error err = ((Engine *)e)->LastBatchGram(rec, &p, &b);
+    if (!err.empty()) return ret(err);
+    if (ports) *ports = p;
+    if (blocks) *blocks = b;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchGram: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(double));
     }
     return ret(Error(""));
 }

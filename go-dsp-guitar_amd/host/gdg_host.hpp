@@ -304,6 +304,14 @@ public:
     Error SetBatchFits(const std::vector<std::pair<int, std::vector<int>>> &fits);
     int BatchFits() const { return (int)fitTarget_.size(); }
     Error LastBatchFit(std::vector<gdg_block_fit> &records, int *fits, size_t *blocks) const;
+    /* No reference counterpart.  The Gram list (include/gdg.h, gdg_batch_gram_enable): 2 to 512 different ports of the job.  While a list is in
+     * force BatchRun and the plain streamed job keep one Gram record per block (LastBatchGram: [blocks][P (P + 1) / 2] doubles) for
+     * gdg_blend_pick_from_gram.  Refused with more than one shard, as the fits are and for their reason; BatchRun of a one-shard engine with a
+     * list is the library's plain gdg_batch_run.  The ports' upper bound is checked when a job is described.  A refused list leaves the one in
+     * force; an empty list: off. */
+    Error SetBatchGram(const std::vector<int> &ports);
+    int BatchGramPorts() const { return (int)gramPort_.size(); }
+    Error LastBatchGram(std::vector<double> &records, int *ports, size_t *blocks) const;
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -377,7 +385,13 @@ private:
     size_t fitBlocks_ = 0;
     bool fitValid_ = false;
     int applyFits(gdg_ctx *ctx);                           /* onto a context (more shards: none are in force): a gdg_* status */
-    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0; }      /* BatchRun is the library's plain one-call run */
+    std::vector<int> gramPort_;                            /* SetBatchGram; empty: off */
+    std::vector<double> lastGram_;                         /* [blocks][P (P + 1) / 2] of the last batch call that kept them */
+    size_t gramBlocks_ = 0;
+    int gramPorts_ = 0;                                    /* P of lastGram_ */
+    bool gramValid_ = false;
+    int applyGram(gdg_ctx *ctx);                           /* onto a context (more shards: none is in force): a gdg_* status */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

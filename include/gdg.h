@@ -1246,6 +1246,77 @@ int gdg_block_fit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size
 int gdg_block_fit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
                               const int *port, const int *target, gdg_block_fit *d_records);
 int gdg_blend_weights_from_fit(const gdg_block_fit *records, int n_fits, size_t blocks, double ridge, double *weight, double *residual);
+/*
+ * GRAM: no reference counterpart.  A fit needs its 1 to 8 term ports named.  The question in front of it -- "which few of these many rigs, in
+ * which mix, come closest to THAT track?" -- needs one object: the Gram matrix G = X X' of all candidate rows and the target.  A Gram record
+ * holds it per block for one list of ports; a host planner picks up to 8 of them greedily from the records and returns their weights.
+ * Stateless: a function of the block's samples alone.  A delayed or inverted candidate is listed as the port of a one-term delayed blend.
+ * LIST: gdg_batch_gram_enable names ONE list of 2 to GDG_GRAM_MAX_PORTS (512) ports.  Ports are rows of the batch window, 0 .. N + 2 + B: chain
+ * outputs, master left, master right, metronome and the B blend ports, read as the record kernels read them: before the trim, a blend port's
+ * s before g_b.  A port that repeats an earlier entry is refused.
+ * RECORD: per block of 8192 samples the lower triangle of the P x P Gram matrix of the listed rows over that block: P (P + 1) / 2 doubles,
+ * entry (i, j), j <= i, at index i (i + 1) / 2 + j -- the fit's xx layout --, i and j positions in the list.  No header and no counts.  A NaN
+ * or inf sample makes the entries of its row whatever IEEE arithmetic makes them: the block statistics count non-finite samples per port,
+ * and the planner refuses a Gram it cannot use.
+ * ORDER OF THE SUM: the sums are made by the FP64 matrix instruction v_mfma_f64_16x16x4_f64.  Entry (i, j) of a block is one accumulator
+ * chain of that instruction, started at +0.0, over k = 0, 4, 8, ... ascending: each step adds the four products x_i[k + m] * x_j[k + m], m = 0
+ * .. 3, to the accumulator as the instruction does (fused, not rounded one by one).  Samples behind the block's end count as +0.0.  The sum
+ * is never split over k across waves or workgroups, uses no atomics and is never finished by a second pass: an entry depends on the block's
+ * samples of its two rows and on nothing else -- not on P, the positions in the list, the window, the slicing, a resume, a source map or the grid.
+ *   The entry is NOT bit for bit the sum_sq of gdg_block_stats, nor the xx of a gdg_block_fit: the order differs and the products are fused.
+ *   It is within L * 2^-52 * sum_k |x_i[k] x_j[k]| of the exact sum for a block of L samples.
+ *   The records are the same bits whatever the window, the slicing, a resume or a source map, and those of gdg_block_gram_rows on the same rows.
+ *   gdg_batch_gram_enable(ctx, port, n_ports)          the list; n_ports == 0: off (port may be NULL).  Refused whole, with the entry named and
+ *                                                      the list in force unchanged: a count of 1 or above 512, a negative port, a repeat, a
+ *                                                      streamed job open.
+ *   gdg_batch_gram_ports(ctx, port, capacity)          returns the number of ports in force and writes the first `capacity` of them (port may be NULL)
+ *   gdg_batch_gram(ctx, out, capacity, &blocks)        the [blocks][P (P + 1) / 2] doubles of the LAST COMPLETED batch call, P the list in force --
+ *                                                      setting a list drops the records of the one before; out == NULL: the count only;
+ *                                                      capacity in doubles.  GDG_ERR_INVALID when capacity is too small, or when there are no
+ *                                                      records: no call has completed since the switch, or the last one was a master finish.
+ * Port numbers are checked when a job is described -- gdg_batch_run, gdg_batch_stream_open, gdg_batch_stream_resume -- against N + 3 + B of
+ * that call; a port at or beyond it is GDG_ERR_INVALID with the entry named.
+ * OFF: n_ports == 0, or never called.  Off, no launch, buffer, upload byte or output byte differs from a context that never heard of the call,
+ * and option stat_batch_device_kib is unchanged; on, it counts the list and the records' room in the download halves.
+ * SIZE: at P = 512 a record is 1 050 624 bytes.  Each of the two download halves grows by window x that (16.8 MB at a window of 16), every
+ * step brings its records down with its rows, and the host keeps the whole call's records until the next batch call: 1 MiB per block, 128
+ * MiB for a call of 128 blocks (22 s at 48 kHz).  A long job should run streamed and add each slice's records into one sum on the host.
+ * Configuration, like the fits: it holds from the next batch call on, is part of no blob -- set it again on the target of a resume -- and a
+ * checkpoint and a resume work with a list on.  The records come down with each step's own download, behind the fit section.
+ * SHARDS: gdg_batch_run_shard, gdg_batch_stream_open_shard, gdg_batch_stream_step_shard and gdg_batch_stream_resume_shard return
+ * GDG_ERR_UNSUPPORTED while a Gram list is in force on their context.  gdg_batch_finish_master and gdg_batch_finish_master_slice never collect Gram records.
+ * The record on its own, over any rows and any block length >= 1 (a list of 1 to 512 entries naming rows 0 .. n_rows - 1; the last block of
+ * a row may be short); both blocking -- the list is host memory:
+ *   gdg_block_gram_rows(ctx, rows, n_rows, samples, block, port, n_ports, records)
+ *                                                      host rows of `samples` float64; records: [ceil(samples / block)][P (P + 1) / 2]
+ *   gdg_block_gram_rows_device(ctx, d_rows, row_stride, n_rows, samples, block, port, n_ports, d_records)
+ *                                                      device rows, 8-byte aligned: row r at d_rows + r * row_stride (row_stride >=
+ *                                                      samples); no sample outside [row, row + samples) is read; d_records: device
+ *                                                      memory, 8-byte aligned
+ * THE PLANNER, pure host arithmetic (csrc/blend.h), no context and no device (gdg_last_error(NULL) says what was refused):
+ *   gdg_blend_pick_from_gram(records, n_ports, blocks, target, candidate, n_candidates, max_terms, ridge, min_gain, picked, weight, residual, &n_picked)
+ *                                                      records[blocks][P (P + 1) / 2] as gdg_batch_gram hands them out, blocks >= 1; target
+ *                                                      and candidate[n_candidates] are positions in the list; picked[8], weight[8], residual[8]
+ * The blocks' records are added in block order with plain double adds.  T = G[target][target]; T <= 0 is refused, and so is a NaN or inf among
+ * the entries of the target and the candidates, with the list position named, a candidate that is the target or repeats an earlier one, and
+ * max_terms outside 1 .. 8.  Nothing is written on a refusal.  Greedy forward selection: with the set S picked so far, in pick order, every
+ * candidate not in S is tried in list order: the unpivoted Cholesky factor of G_S + ridge * mean(diag) * I is extended by the candidate's row
+ * -- the fit planner's solve on S and the candidate.  A candidate that brings a pivot at or below the fit planner's bound, K * 2^-52 * max(diag)
+ * for the K rows then in the factor, is skipped, not refused: a silent rig, or a duplicate of a picked one.  r_c = max(0, T - 2 w.b + w'Gw) /
+ * T; the smallest r_c wins, ties go to the earlier list entry.  It stops after max_terms picks, when the best candidate improves the
+ * residual by less than min_gain (the residual before the first pick is 1), or when no candidate is admissible.  picked[m] is the list
+ * position of pick m, residual[m] the share left after it; entries behind n_picked are -1, 0.0 and 0.0.  The weights are, bit for bit, what
+ * gdg_blend_weights_from_fit returns for a gdg_block_fit holding the same sums of the picked ports in pick order.
+ */
+#define GDG_GRAM_MAX_PORTS 512
+int gdg_batch_gram_enable(gdg_ctx *ctx, const int *port, int n_ports);
+int gdg_batch_gram_ports(const gdg_ctx *ctx, int *port, int capacity);
+int gdg_batch_gram(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks);
+int gdg_block_gram_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, const int *port, int n_ports, double *records);
+int gdg_block_gram_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, const int *port, int n_ports,
+                               double *d_records);
+int gdg_blend_pick_from_gram(const double *records, int n_ports, size_t blocks, int target, const int *candidate, int n_candidates, int max_terms, double ridge,
+                             double min_gain, int *picked, double *weight, double *residual, int *n_picked);
 
 #ifdef __cplusplus
 
