@@ -141,6 +141,26 @@ __device__ __forceinline__ double fmod_2pi(double x) {
     return x;
 }
 
+/* The chorus's delay (in samples) of LFO j at sample `index` of the frame by the reference's own expressions, operation for operation
+ * (chorus.go:52-62): the kernels take the five sines from one sincos per thread by rotation, good to ~1e-15, i.e. ~1e-12 samples of
+ * delay -- enough everywhere but where the delay falls on a whole number of samples.  The reference counts the sample TWICE there (early ==
+ * late, both weights 1), and it happens by construction, not by luck: the LFOs are 2 pi / 5 apart and the phase advances by rational
+ * fractions of a turn, so an LFO reaches sin(pi) = 1.2e-16 on a sample, 40 + 10 sin rounds to 40 and the delay is 7680 samples to the
+ * bit (192 kHz, call 133, sample 3200, LFO 2).  A sine that is 1e-16 off in absolute terms decides that rounding the other way: one sample
+ * of the frame is then off by 0.1 x the input.  So a tap whose delay comes out within CHORUS_NEAR_WHOLE of a whole number is made again
+ * with this function (about one tap in 10^7; every other tap keeps the rotated LFO's bits). */
+#define CHORUS_NEAR_WHOLE 0x1p-24
+/* fr = delay - floor(delay), in [0, 1) */
+__device__ __forceinline__ bool chorus_near_whole(double fr) { return fabs(fr - 0.5) > 0.5 - CHORUS_NEAR_WHOLE; }
+__device__ __forceinline__ double chorus_delay_exact(double prev, double angular, double sr, double depth, int index, int j) {
+    double time = (double)index / sr;
+    double zero_phase = fmod_2pi(prev + (angular * time));
+    double phase = fmod_2pi(zero_phase + (GO_MATH_TWO_PI_FIFTH * (double)j));          /* both arguments in [0, 4 pi): exact, as fmod is */
+    double offset = depth * sin(phase);
+    double delay_time = 0.001 * (40.0 + offset);
+    return delay_time * sr;
+}
+
 /* ---- workgroup scan of (A, B) maps:  affine x -> A x + B   or   max-affine x -> max(A x, B) ---- */
 template <bool MAXOP>
 __device__ __forceinline__ void compose(double &A, double &B, double A1, double B1) {
@@ -1261,6 +1281,7 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
     auto samples = [&](const int (&idx)[2], int G, const double (&sv)[2], const double (&cv)[2]) {
         seg_v2d v[2][5];
         double frs[2][5];
+        bool any_near = false;                                      /* a delay of this lane sits on a whole number, or next to one */
 #pragma unroll
         for (int g = 0; g < 2; g++) {
             if (g < G) {
@@ -1273,8 +1294,35 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
                      * (exact): fr != 0: late = early + 1 and the weights are exactly 1 - fr and fr; fr == 0: late = early, both 1 */
                     const double early = floor(delay_samples);
                     frs[g][j] = delay_samples - early;
+                    any_near |= chorus_near_whole(frs[g][j]);
                     const int t = g0 + idx[g] - (int)early - 1;     /* the older neighbour; t >= -C - 1, and t = -C - 1 only with fr == 0 */
                     v[g][j] = *(const GDG_GLOBAL seg_v2d *)(ring + ((wp + t) & mask));      /* (V[t], V[t + 1]) */
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(any_near) != 0) {          /* rare: those taps again, by the reference's expressions (chorus_delay_exact) */
+#pragma nounroll
+            for (int k = 0; k < 5 * G; k++) {
+                const int gk = k >= 5 ? 1 : 0, jk = k - 5 * gk;
+                double fr = 0.5;
+#pragma unroll
+                for (int g = 0; g < 2; g++) {
+#pragma unroll
+                    for (int j = 0; j < 5; j++) fr = (5 * g + j == k) ? frs[g][j] : fr;
+                }
+                if (chorus_near_whole(fr)) {
+                    const int index = g0 + (gk ? idx[1] : idx[0]);
+                    const double delay_samples = chorus_delay_exact(prev, angular, sr, depth, index, jk);
+                    const double early = floor(delay_samples);
+                    fr = delay_samples - early;
+                    const seg_v2d vk = *(const GDG_GLOBAL seg_v2d *)(ring + ((wp + (index - (int)early - 1)) & mask));
+#pragma unroll
+                    for (int g = 0; g < 2; g++) {
+#pragma unroll
+                        for (int j = 0; j < 5; j++) {
+                            if (5 * g + j == k) { frs[g][j] = fr; v[g][j] = vk; }
+                        }
+                    }
                 }
             }
         }
@@ -1438,6 +1486,7 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
     auto samples = [&](const int (&idx)[2], int G) {
         seg_v2d v[2][5];
         double frs[2][5];
+        bool any_near = false;                                      /* a delay of this lane sits on a whole number, or next to one */
 #pragma unroll
         for (int g = 0; g < 2; g++) {
             if (g < G) {
@@ -1450,11 +1499,38 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
                      * (exact): fr != 0: late = early + 1 and the weights are exactly 1 - fr and fr; fr == 0: late = early, both 1 */
                     const double early = floor(delay_samples);
                     frs[g][j] = delay_samples - early;
+                    any_near |= chorus_near_whole(frs[g][j]);
                     const int t = idx[g] - (int)early - 1;          /* the older neighbour; t >= -C - 1, and t = -C - 1 only with fr == 0 */
                     v[g][j] = *(const GDG_GLOBAL seg_v2d *)(ring + ((wp + t) & mask));      /* (V[t], V[t + 1]) */
                 }
                 double sn = (s0 * cd) + (c0 * sd), cn = (c0 * cd) - (s0 * sd);
                 s0 = sn; c0 = cn;
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(any_near) != 0) {          /* rare: those taps again, by the reference's expressions (chorus_delay_exact) */
+#pragma nounroll
+            for (int k = 0; k < 5 * G; k++) {
+                const int gk = k >= 5 ? 1 : 0, jk = k - 5 * gk;
+                double fr = 0.5;
+#pragma unroll
+                for (int g = 0; g < 2; g++) {
+#pragma unroll
+                    for (int j = 0; j < 5; j++) fr = (5 * g + j == k) ? frs[g][j] : fr;
+                }
+                if (chorus_near_whole(fr)) {
+                    const int index = gk ? idx[1] : idx[0];
+                    const double delay_samples = chorus_delay_exact(prev, angular, sr, depth, index, jk);
+                    const double early = floor(delay_samples);
+                    fr = delay_samples - early;
+                    const seg_v2d vk = *(const GDG_GLOBAL seg_v2d *)(ring + ((wp + (index - (int)early - 1)) & mask));
+#pragma unroll
+                    for (int g = 0; g < 2; g++) {
+#pragma unroll
+                        for (int j = 0; j < 5; j++) {
+                            if (5 * g + j == k) { frs[g][j] = fr; v[g][j] = vk; }
+                        }
+                    }
+                }
             }
         }
         /* an integral delay (both weights 1, the sample counted twice) is rare -- depth 0 or a lucky phase -- and costs six selects per
