@@ -160,6 +160,19 @@ __device__ __forceinline__ double chorus_delay_exact(double prev, double angular
     double delay_time = 0.001 * (40.0 + offset);
     return delay_time * sr;
 }
+/* The same for the flanger and the phaser (flanger.go:58-65, phaser.go:64-71; time is i * (1 / sr) there, not i / sr): unit_flanger rotates its
+ * sincos up to seven times, and sin = 1 (a delay of the whole ring), sin = -1 (a delay of 0) and sin = 0.5 fall on samples by construction.
+ * The rotated sine missed 32 of 40 such samples at 48 kHz, depth 100, speed 100 (0.5 x the input each; profiles/parity_lfo_delay.txt), and one
+ * that comes out below -1 gives a NEGATIVE delay: floor -1, and frac_delay reads in[i + 1].  The exact sine is never below -1, so the same
+ * branch covers that. */
+__device__ __forceinline__ bool flanger_near_whole(double delay_samples) { return fabs(delay_samples - rint(delay_samples)) < CHORUS_NEAR_WHOLE; }
+__device__ __forceinline__ double flanger_delay_exact(double prev, double angular, double sr, double sr_inv, double depth, int index) {
+    double time = (double)index * sr_inv;
+    double phase = fmod_2pi(prev + (angular * time));
+    double offset = depth * sin(phase);
+    double delay_time = 0.001 * (depth + offset);
+    return delay_time * sr;
+}
 
 /* ---- workgroup scan of (A, B) maps:  affine x -> A x + B   or   max-affine x -> max(A x, B) ---- */
 template <bool MAXOP>
@@ -1611,6 +1624,8 @@ UNIT_FN unit_flanger(UNIT_ARGS) {
         double offset = depth * s0;
         double delay_time = 0.001 * (depth + offset);
         double delay_samples = delay_time * sr;
+        /* rare: on a whole number of samples or next to one, the delay again by the reference's expressions (every other sample keeps its bits) */
+        if (flanger_near_whole(delay_samples)) delay_samples = flanger_delay_exact(prev, angular, sr, sr_inv, depth, i);
         double delayed = frac_delay(in, ring, C, wp, i, delay_samples);
         out[LX(i)] = (mix_dry * in[LX(i)]) + (mix_wet * delayed);
         double sn = (s0 * cd) + (c0 * sd), cn = (c0 * cd) - (s0 * sd);
