@@ -320,7 +320,11 @@ __device__ __forceinline__ void tab_fetch(double *dst, const double *src_generic
  * (wave_spin_expired: the context's error word, never a hung device). */
 struct TileCtx { unsigned long long *xch; int *d_error; int tile; int epoch; int xid; int pad; };
 __shared__ TileCtx s_tc;
-#define GDG_TILE_XIDS 32                  /* exchange ids per segment (api_plan.cpp counts them: compressor 1, tone stack 4, cabinet 7, chorus 1) */
+#define GDG_TILE_XIDS 32                  /* exchange ids per segment (api_plan.cpp sums tile_exchanges, below, through gdg_segt_exchanges) */
+/* exchange ids a unit of that type uses: seg_frame hands them out unit by unit, the plan keeps a segment's sum within GDG_TILE_XIDS */
+__host__ __device__ constexpr int tile_exchanges(int type) {
+    return type == GDG_UNIT_COMPRESSOR ? 1 : type == GDG_UNIT_TONESTACK ? 4 : type == GDG_UNIT_CABINET ? 7 : (type == GDG_UNIT_CHORUS || type == GDG_UNIT_REVERB) ? 1 : 0;
+}
 __device__ __forceinline__ void tile_put(int xid, int wave, int value, double v);       /* (defined behind the hand-off primitives below) */
 __device__ __forceinline__ double tile_get(int xid, int wave, int value);
 #endif
@@ -1202,9 +1206,55 @@ UNIT_FN unit_cabinet(UNIT_ARGS) {
  * before it appends (s = 1 at 192 kHz: 32768 cells, C = 9600; s = 0, i.e. no overlap and the plain hand-off, at 96 kHz).  "Done" marks are
  * per frame (cell 2 + (f & 3)) and carry the launch's epoch, so a mark left by an earlier launch never passes for this one's.
  * *posted says to the caller that the unit's counter has been posted. */
+/* ONE text for the three builds.  What the tile build (a tile of the frame per workgroup) does differently is the offset g0 of its tile in
+ * the frame, appends that are always write-through, the hand-off between the tiles behind the append, "the last tile leaves the state" -- short
+ * #ifdef SEG_TILE blocks in unit_chorus -- and the LFO's schedule, which is a policy handed to the sample routine:
+ *   at(g, s, c)   the LFO's (sin, cos) at sample g (0 or 1) of the pair in hand;
+ *   loaded(g)     called in the load loop, right behind the five loads of sample g;
+ *   next()        called behind the pair.
+ * One sincos per thread: a thread's samples are a fixed stride apart, so its LFO phase advances by a fixed angle from one to the next and
+ * (sin, cos) follow by rotation (error ~1e-16 per step, eight steps). */
+template <class I>                  /* (the thread index as it is, unsigned, or a frame index made from it) */
+__device__ __forceinline__ void chorus_lfo_start(double prev, double angular, double sr, I index, double &s, double &c) {
+    double time = (double)index / sr;
+    double zero_phase = fmod_2pi(prev + (angular * time));
+    sincos(zero_phase, &s, &c);
+}
+/* (text, not a function, and the one-state ChorusLfo below keeps c in front of s: with the operands handed through a call, or the members the
+ * other way round, the compiler commutes some of the additions -- the same bits, but no longer the instruction stream that seg.o and segf.o
+ * had with the rotation written out in the sample loop, the one their timings were taken with) */
+#define CHORUS_LFO_STEP(s, c, sd, cd) { double sn = ((s) * (cd)) + ((c) * (sd)), cn = ((c) * (cd)) - ((s) * (sd)); (s) = sn; (c) = cn; }
 #ifdef SEG_TILE
-/* (the tile build's form: a tile of the frame per workgroup, two LFO states per thread; the other builds keep theirs, below, to the letter --
- * moving the LFO's rotation out of the sample loop cost the two-per-CU kernel 2.5 us per launch at 512 channels) */
+/* segt.o: the thread of the GENERAL kernel that owns a sample is its frame index mod 1024, and the value it uses is that thread's sincos
+ * rotated (index div 1024) times: the same here.  Local samples tid + 512 q, q = 0 .. 7, are frame index (tid + 512 (q & 1)) + 1024 (4 tile + q / 2):
+ * two states per thread (the general kernel's threads tid and tid + 512), each already 4 x tile steps along when the tile starts, stepped
+ * behind each pair. */
+struct ChorusLfo {
+    double s[2], c[2], sd, cd;
+    __device__ __forceinline__ ChorusLfo(double prev, double angular, double sr) {
+        sincos(angular * ((double)(SEG_T * SEG_TILES) / sr), &sd, &cd);
+        chorus_lfo_start(prev, angular, sr, (int)seg_tid(), s[0], c[0]);
+        chorus_lfo_start(prev, angular, sr, (int)seg_tid() + SEG_T, s[1], c[1]);
+        for (int r = 0; r < (CHK / 2) * s_tc.tile; r++) next();
+    }
+    __device__ __forceinline__ void at(int g, double &s_, double &c_) const { s_ = s[g]; c_ = c[g]; }
+    __device__ __forceinline__ void loaded(int) {}
+    __device__ __forceinline__ void next() { CHORUS_LFO_STEP(s[0], c[0], sd, cd) CHORUS_LFO_STEP(s[1], c[1], sd, cd) }
+};
+#else
+/* seg.o, segf.o: one state, the thread's samples SEG_T apart.  It is read for sample g and rotated INSIDE the load loop, behind the five
+ * loads of that sample: moving the rotation out of the sample loop cost the two-per-CU kernel 2.5 us per launch at 512 channels. */
+struct ChorusLfo {
+    double c, s, sd, cd;
+    __device__ __forceinline__ ChorusLfo(double prev, double angular, double sr) {
+        chorus_lfo_start(prev, angular, sr, seg_tid(), s, c);
+        sincos(angular * ((double)SEG_T / sr), &sd, &cd);
+    }
+    __device__ __forceinline__ void at(int, double &s_, double &c_) const { s_ = s; c_ = c; }
+    __device__ __forceinline__ void loaded(int) { CHORUS_LFO_STEP(s, c, sd, cd) }
+    __device__ __forceinline__ void next() {}
+};
+#endif
 UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
     UNIT_PROLOGUE
     const GDG_CONST gdg_seg_unit *Uc = uniform_unit(U);
@@ -1218,9 +1268,9 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
 #ifdef SEG_TILE
     /* a tile of the frame: its samples are g0 .. g0 + N - 1 of the frame; what it appends, the tiles behind it may tap (write-through) */
     const int g0 = s_tc.tile * SEG_N;
-    const bool wts = true;
+    constexpr bool wts = true;
 #else
-    const int g0 = 0;
+    constexpr int g0 = 0;
     const bool wts = wt;
 #endif
     if (wt) {
@@ -1260,7 +1310,7 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
 #endif
     /* (this frame's taps read t = -C - 1 .. N - 1 relative to wp; frame f + j appends at wp + j N ..) */
     const int slack = wt ? ((mask + 1) - C - 2) / N - 1 : 0;        /* s: how many later frames may append while this one still reads */
-    const bool early = wt && slack >= 1 && slack <= 2;
+    const bool early = wt && slack >= 1 && slack <= 2;                /* (never in the tile build: its launch has a frame per call, wt is false) */
     if (early) {
         if (seg_tid() == 0) {
             st_f64(ds, fmod(prev + (angular * ((double)C / sr)), GO_MATH_TWO_PI), true);      /* the end-of-unit update below, same expression */
@@ -1273,34 +1323,22 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
      * differs from the reference's sin(fmod(zero_phase + j 2pi/5, 2pi)) by ~1e-16, i.e. ~1e-13 samples of delay */
     const double cj[5] = { 1.0, 0.30901699437494742410, -0.80901699437494742410, -0.80901699437494742410, 0.30901699437494742410 };
     const double sj[5] = { 0.0, 0.95105651629515357212, 0.58778525229247312917, -0.58778525229247312917, -0.95105651629515357212 };
-    /* one sincos per thread: a thread's samples are SEG_T apart, so its LFO phase advances by a fixed angle from one to the
-     * next and (sin, cos) follow by rotation (error ~1e-16 per step, eight steps).  (SEG_TILE: the thread of the GENERAL kernel that owns a
-     * sample is its frame index mod 1024, and the value it uses is that thread's sincos rotated (index div 1024) times: the same here.) */
-    constexpr int LFO_STRIDE = SEG_T * SEG_TILES;
-    double sd, cd;
-    sincos(angular * ((double)LFO_STRIDE / sr), &sd, &cd);
-    auto lfo_start = [&](int index, double &s_, double &c_) {
-        double time = (double)index / sr;
-        double zero_phase = fmod_2pi(prev + (angular * time));
-        sincos(zero_phase, &s_, &c_);
-    };
-    auto lfo_step = [&](double &s_, double &c_) {
-        double sn = (s_ * cd) + (c_ * sd), cn = (c_ * cd) - (s_ * sd);
-        s_ = sn; c_ = cn;
-    };
+    ChorusLfo lfo(prev, angular, sr);
     /* G samples at a time: first every address and ALL 5 G tap loads (16 bytes each), then the arithmetic -- written as two
      * loops because the compiler otherwise waits for each load right where it is used: 40 exposed L2 / HBM latencies per thread
-     * were the whole cost of this unit (the ALU work is a third of it).  sv / cv: the LFO's (sin, cos) at the two samples */
-    auto samples = [&](const int (&idx)[2], int G, const double (&sv)[2], const double (&cv)[2]) {
+     * were the whole cost of this unit (the ALU work is a third of it) */
+    auto samples = [&](const int (&idx)[2], int G) {
         seg_v2d v[2][5];
         double frs[2][5];
         bool any_near = false;                                      /* a delay of this lane sits on a whole number, or next to one */
 #pragma unroll
         for (int g = 0; g < 2; g++) {
             if (g < G) {
+                double sg, cg;
+                lfo.at(g, sg, cg);
 #pragma unroll
                 for (int j = 0; j < 5; j++) {
-                    double offset = depth * ((sv[g] * cj[j]) + (cv[g] * sj[j]));
+                    double offset = depth * ((sg * cj[j]) + (cg * sj[j]));
                     double delay_time = 0.001 * (40.0 + offset);
                     double delay_samples = delay_time * sr;
                     /* chorus.go:63-90: early = floor, late = ceil, weights 1 - (d - early) and 1 - (late - d).  With fr = d - early
@@ -1311,6 +1349,7 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
                     const int t = g0 + idx[g] - (int)early - 1;     /* the older neighbour; t >= -C - 1, and t = -C - 1 only with fr == 0 */
                     v[g][j] = *(const GDG_GLOBAL seg_v2d *)(ring + ((wp + t) & mask));      /* (V[t], V[t + 1]) */
                 }
+                lfo.loaded(g);
             }
         }
         if (__builtin_amdgcn_ballot_w64(any_near) != 0) {          /* rare: those taps again, by the reference's expressions (chorus_delay_exact) */
@@ -1374,215 +1413,9 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
                 out[LX(idx[g])] = (0.5 * in[LX(idx[g])]) + (0.5 * effected);
             }
         }
+        lfo.next();
     };
-#ifdef SEG_TILE
-    {
-        /* local samples tid + 512 q, q = 0 .. 7: frame index g0 + tid + 512 q = (tid + 512 (q & 1)) + 1024 (4 tile + q / 2): two LFO states per
-         * thread (the general kernel's threads tid and tid + 512), each already 4 x tile steps along when the tile starts */
-        double sa, ca, sb, cb;
-        lfo_start((int)seg_tid(), sa, ca);
-        lfo_start((int)seg_tid() + SEG_T, sb, cb);
-        for (int r = 0; r < 4 * s_tc.tile; r++) { lfo_step(sa, ca); lfo_step(sb, cb); }
-#pragma unroll
-        for (int q = 0; q < CHK; q += 2) {
-            const int idx[2] = { (int)seg_tid() + q * SEG_T, (int)seg_tid() + (q + 1) * SEG_T };
-            const double sv[2] = { sa, sb }, cv[2] = { ca, cb };
-            samples(idx, 2, sv, cv);
-            lfo_step(sa, ca);
-            lfo_step(sb, cb);
-        }
-    }
-#else
-    double s0, c0;
-    lfo_start((int)seg_tid(), s0, c0);
-    if (N == CHK * SEG_T) {
-#pragma unroll
-        for (int q = 0; q < CHK; q += 2) {                         /* the batch block size: a fixed trip count */
-            const int idx[2] = { (int)seg_tid() + q * SEG_T, (int)seg_tid() + (q + 1) * SEG_T };
-            double sv[2], cv[2];
-            sv[0] = s0; cv[0] = c0;
-            lfo_step(s0, c0);
-            sv[1] = s0; cv[1] = c0;
-            lfo_step(s0, c0);
-            samples(idx, 2, sv, cv);
-        }
-    } else {
-        for (int i = seg_tid(); i < N; i += 2 * SEG_T) {
-            const int idx[2] = { i, i + SEG_T };
-            double sv[2], cv[2];
-            sv[0] = s0; cv[0] = c0;
-            lfo_step(s0, c0);
-            sv[1] = s0; cv[1] = c0;
-            lfo_step(s0, c0);
-            samples(idx, (i + SEG_T < N) ? 2 : 1, sv, cv);
-        }
-    }
-#endif
-#ifdef SEG_TILE
-    if (seg_tid() == 0 && s_tc.tile == SEG_TILES - 1) {
-        /* the frame's last tile leaves the state: it has seen every other tile's "in the ring", which they posted after reading wp and the phase */
-        st_f64(ds, fmod(prev + (angular * ((double)C / sr)), GO_MATH_TWO_PI), false);
-        st_i32(is, (wp + GDG_MAX_FRAMES) & mask, false);
-    }
-#else
-    if (seg_tid() == 0 && !early) {
-        double buffer_time = (double)C / sr;          /* quirk: advances by the buffer length, not by N */
-        st_f64(ds, fmod(prev + (angular * buffer_time), GO_MATH_TWO_PI), wt);
-        st_i32(is, (wp + N) & mask, wt);
-    }
-#endif
-    if (early) wave_post(gate.cell + 1 + (gate.wf & 3), gate.epoch * 32 + gate.wf + 1, false);      /* this frame's taps are done (nothing to publish: no release) */
-}
-#else
-UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
-    UNIT_PROLOGUE
-    const GDG_CONST gdg_seg_unit *Uc = uniform_unit(U);
-    const double depth = Uc->dp[0], angular = Uc->dp[1], sr = Uc->dp[2];
-    const int C = Uc->jp[0], mask = Uc->jp[1];
-    GDG_GLOBAL double *ring = as_global(Uc->hist);
-    GDG_GLOBAL int *is = as_global(Uc->is);
-    GDG_GLOBAL double *ds = as_global(Uc->ds);
-    const int wp = is[0];
-    const double prev = ds[0];
-    if (wt) {
-        const int s_ok = ((mask + 1) - C - 2) / N - 1;
-        if (s_ok >= 1 && s_ok <= 2 && gate.wf - s_ok - 1 >= 0) {
-            const int fd = gate.wf - s_ok - 1;                        /* the frame whose taps this frame's append would run into */
-            wave_wait(gate.cell + 1 + (fd & 3), gate.epoch * 32 + fd + 1, false, gate.d_error);
-        }
-    }
-    /* 1. append the frame (pairs where possible); cell 0 is mirrored into the guard cell mask + 1 */
-    if ((N & 1) == 0 && (wp & 1) == 0) {
-        for (int i = 2 * (int)seg_tid(); i < N; i += 2 * SEG_T) {
-            const int p = (wp + i) & mask;                          /* even, so p + 1 <= mask */
-            seg_v2d v = { in[LX(i)], in[LX(i + 1)] };
-            st_v2d((GDG_GLOBAL seg_v2d *)(ring + p), v, wt);
-            if (p == 0) st_f64(ring + mask + 1, v.x, wt);
-        }
-    } else {
-        for (int i = seg_tid(); i < N; i += SEG_T) {
-            const int p = (wp + i) & mask;
-            const double v = in[LX(i)];
-            st_f64(ring + p, v, wt);
-            if (p == 0) st_f64(ring + mask + 1, v, wt);
-        }
-    }
-    if (wt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      /* the sc1 pair stores are inline assembly: the compiler does not wait for them */
-    __syncthreads();                                                /* the frame is in the ring (visible to the whole workgroup) */
-    /* (this frame's taps read t = -C - 1 .. N - 1 relative to wp; frame f + j appends at wp + j N ..) */
-    const int slack = wt ? ((mask + 1) - C - 2) / N - 1 : 0;        /* s: how many later frames may append while this one still reads */
-    const bool early = wt && slack >= 1 && slack <= 2;
-    if (early) {
-        if (seg_tid() == 0) {
-            st_f64(ds, fmod(prev + (angular * ((double)C / sr)), GO_MATH_TWO_PI), true);      /* the end-of-unit update below, same expression */
-            st_i32(is, (wp + N) & mask, true);
-        }
-        wave_post(gate.cell - 1, gate.wf_next, gate.release);
-        *posted = 1;
-    }
-    /* sin(zero_phase + j 2pi/5) by the angle-addition formula from ONE sincos (the five LFOs are 72 degrees apart):
-     * differs from the reference's sin(fmod(zero_phase + j 2pi/5, 2pi)) by ~1e-16, i.e. ~1e-13 samples of delay */
-    const double cj[5] = { 1.0, 0.30901699437494742410, -0.80901699437494742410, -0.80901699437494742410, 0.30901699437494742410 };
-    const double sj[5] = { 0.0, 0.95105651629515357212, 0.58778525229247312917, -0.58778525229247312917, -0.95105651629515357212 };
-    /* one sincos per thread: a thread's samples are SEG_T apart, so its LFO phase advances by a fixed angle from one to the
-     * next and (sin, cos) follow by rotation (error ~1e-16 per step, eight steps) */
-    double s0, c0, sd, cd;
-    {
-        double time = (double)seg_tid() / sr;
-        double zero_phase = fmod_2pi(prev + (angular * time));
-        sincos(zero_phase, &s0, &c0);
-        sincos(angular * ((double)SEG_T / sr), &sd, &cd);
-    }
-    /* G samples at a time: first every address and ALL 5 G tap loads (16 bytes each), then the arithmetic -- written as two
-     * loops because the compiler otherwise waits for each load right where it is used: 40 exposed L2 / HBM latencies per thread
-     * were the whole cost of this unit (the ALU work is a third of it) */
-    auto samples = [&](const int (&idx)[2], int G) {
-        seg_v2d v[2][5];
-        double frs[2][5];
-        bool any_near = false;                                      /* a delay of this lane sits on a whole number, or next to one */
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            if (g < G) {
-#pragma unroll
-                for (int j = 0; j < 5; j++) {
-                    double offset = depth * ((s0 * cj[j]) + (c0 * sj[j]));
-                    double delay_time = 0.001 * (40.0 + offset);
-                    double delay_samples = delay_time * sr;
-                    /* chorus.go:63-90: early = floor, late = ceil, weights 1 - (d - early) and 1 - (late - d).  With fr = d - early
-                     * (exact): fr != 0: late = early + 1 and the weights are exactly 1 - fr and fr; fr == 0: late = early, both 1 */
-                    const double early = floor(delay_samples);
-                    frs[g][j] = delay_samples - early;
-                    any_near |= chorus_near_whole(frs[g][j]);
-                    const int t = idx[g] - (int)early - 1;          /* the older neighbour; t >= -C - 1, and t = -C - 1 only with fr == 0 */
-                    v[g][j] = *(const GDG_GLOBAL seg_v2d *)(ring + ((wp + t) & mask));      /* (V[t], V[t + 1]) */
-                }
-                double sn = (s0 * cd) + (c0 * sd), cn = (c0 * cd) - (s0 * sd);
-                s0 = sn; c0 = cn;
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(any_near) != 0) {          /* rare: those taps again, by the reference's expressions (chorus_delay_exact) */
-#pragma nounroll
-            for (int k = 0; k < 5 * G; k++) {
-                const int gk = k >= 5 ? 1 : 0, jk = k - 5 * gk;
-                double fr = 0.5;
-#pragma unroll
-                for (int g = 0; g < 2; g++) {
-#pragma unroll
-                    for (int j = 0; j < 5; j++) fr = (5 * g + j == k) ? frs[g][j] : fr;
-                }
-                if (chorus_near_whole(fr)) {
-                    const int index = gk ? idx[1] : idx[0];
-                    const double delay_samples = chorus_delay_exact(prev, angular, sr, depth, index, jk);
-                    const double early = floor(delay_samples);
-                    fr = delay_samples - early;
-                    const seg_v2d vk = *(const GDG_GLOBAL seg_v2d *)(ring + ((wp + (index - (int)early - 1)) & mask));
-#pragma unroll
-                    for (int g = 0; g < 2; g++) {
-#pragma unroll
-                        for (int j = 0; j < 5; j++) {
-                            if (5 * g + j == k) { frs[g][j] = fr; v[g][j] = vk; }
-                        }
-                    }
-                }
-            }
-        }
-        /* an integral delay (both weights 1, the sample counted twice) is rare -- depth 0 or a lucky phase -- and costs six selects per
-         * tap: the wave asks once per sample pair whether any of its lanes has one and otherwise takes the plain interpolation (the same
-         * operations in the same order: the same bits) */
-        bool any_whole = false;
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            if (g < G) {
-#pragma unroll
-                for (int j = 0; j < 5; j++) any_whole |= frs[g][j] == 0.0;
-            }
-        }
-        const bool plain = __builtin_amdgcn_ballot_w64(any_whole) == 0;
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            if (g < G) {
-                double effected = 0.0;
-                if (plain) {
-#pragma unroll
-                    for (int j = 0; j < 5; j++) {
-                        const double fr = frs[g][j];
-                        effected += 0.2 * (((1.0 - fr) * v[g][j].y) + (fr * v[g][j].x));
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 5; j++) {
-                        const double fr = frs[g][j];
-                        const bool whole = fr == 0.0;
-                        const double se = v[g][j].y, sl = whole ? v[g][j].y : v[g][j].x;
-                        const double we = whole ? 1.0 : 1.0 - fr, wl = whole ? 1.0 : fr;
-                        effected += 0.2 * ((we * se) + (wl * sl));
-                    }
-                }
-                out[LX(idx[g])] = (0.5 * in[LX(idx[g])]) + (0.5 * effected);
-            }
-        }
-    };
-    if (N == CHK * SEG_T) {
+    if (N == CHK * SEG_T) {                                         /* (always, in the tile build) */
 #pragma unroll
         for (int q = 0; q < CHK; q += 2) {                         /* the batch block size: a fixed trip count */
             const int idx[2] = { (int)seg_tid() + q * SEG_T, (int)seg_tid() + (q + 1) * SEG_T };
@@ -1594,14 +1427,19 @@ UNIT_FN unit_chorus(UNIT_ARGS, const WaveGate &gate, int *posted) {
             samples(idx, (i + SEG_T < N) ? 2 : 1);
         }
     }
-    if (seg_tid() == 0 && !early) {
+#ifdef SEG_TILE
+    /* the frame's last tile leaves the state: it has seen every other tile's "in the ring", which they posted after reading wp and the phase */
+    const bool leaves = s_tc.tile == SEG_TILES - 1;
+#else
+    constexpr bool leaves = true;
+#endif
+    if (seg_tid() == 0 && !early && leaves) {
         double buffer_time = (double)C / sr;          /* quirk: advances by the buffer length, not by N */
         st_f64(ds, fmod(prev + (angular * buffer_time), GO_MATH_TWO_PI), wt);
-        st_i32(is, (wp + N) & mask, wt);
+        st_i32(is, (wp + SEG_TILES * N) & mask, wt);
     }
     if (early) wave_post(gate.cell + 1 + (gate.wf & 3), gate.epoch * 32 + gate.wf + 1, false);      /* this frame's taps are done (nothing to publish: no release) */
 }
-#endif
 
 #ifndef SEG_SUBSET
 /* ---- flanger / phaser: effects/flanger.go:19-119, effects/phaser.go:19-125 --------------------------------
@@ -3202,7 +3040,7 @@ __device__ __forceinline__ void seg_frame(const double *src, double *dst, const 
         /* (the barrier that ended the previous unit lies between its last read of s_tc.xid and this write; every unit has a barrier of its
          * own between here and its first exchange) */
         if (tid == 0) s_tc.xid = xid;
-        xid += type == GDG_UNIT_COMPRESSOR ? 1 : type == GDG_UNIT_TONESTACK ? 4 : type == GDG_UNIT_CABINET ? 7 : (type == GDG_UNIT_CHORUS || type == GDG_UNIT_REVERB) ? 1 : 0;
+        xid += tile_exchanges(type);
 #endif
         /* a unit that keeps nothing from frame to frame (a shaper without oversampling) meets nobody */
         const bool gated = WAVE && (u >= 15 || ((wave_mask >> u) & 1u));
@@ -3328,11 +3166,7 @@ int gdg_segt_supported(int unit_type) {
         return 0;
     }
 }
-/* exchange ids a unit of that type uses (the plan keeps a segment's sum within GDG_TILE_XIDS) */
-int gdg_segt_exchanges(int unit_type) {
-    return unit_type == GDG_UNIT_COMPRESSOR ? 1 : unit_type == GDG_UNIT_TONESTACK ? 4 : unit_type == GDG_UNIT_CABINET ? 7 :
-           (unit_type == GDG_UNIT_CHORUS || unit_type == GDG_UNIT_REVERB) ? 1 : 0;
-}
+int gdg_segt_exchanges(int unit_type) { return tile_exchanges(unit_type); }
 size_t gdg_segt_xch_words(void) { return GDG_TILE_XCH_WORDS; }
 
 hipError_t gdg_launch_segt(const gdg_seg_chan *d_chans, int n_chans, const gdg_seg_unit *d_units, gdg_shift shift, gdg_os_tables os, int *d_error,

@@ -11,8 +11,8 @@ whole delays), so a whole delay sits in some lanes of a wave beside lanes withou
     value for one of the ulp offsets -2 .. +2 of that hit's sine;
   - channel 0 within TOL_RMS of the oracle; everything finite.
 
-The chorus's near-whole branch exists in two texts of seg.hip (the tile build and the one the other shapes share) and runs in four shapes;
-the 8192-frame chorus cases run in each, confirmed from the GDG_PLAN_TRACE=2 lines: SEGT (the defaults), GENERAL (seg_tile_max_channels = 0),
+The chorus's near-whole branch is one text in seg.hip (unit_chorus), compiled three times (the general, the two-per-CU and the tile build, which
+differ in the LFO's schedule and the tile's offset), and runs in four shapes; the 8192-frame chorus cases run in each, confirmed from the GDG_PLAN_TRACE=2 lines: SEGT (the defaults), GENERAL (seg_tile_max_channels = 0),
 SEGF (seg_two_per_cu_min_channels = 2; segf_unit_ok holds for the chorus at every rate) and WAVE (windows of 4, also bit for bit against
 the per-frame calls).  The flanger and the phaser run in the general kernel only; one flanger case also runs in windows.
 

@@ -5,7 +5,7 @@ All tests need a real MI355X: run with `pytest -m gpu`.
 import numpy as np
 import pytest
 
-from helpers import ChainPair, TOL_RMS, package, rms, run_pairs, synth_ir, synth_signal
+from helpers import ChainPair, TOL_RMS, package, rms, run_pairs, shapes, synth_ir, synth_signal
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +130,31 @@ def test_single_unit_stream(pkg, oracle, unit, params, sr, frames):
     got, want = run_pairs(ctx, pairs, x, frames, sr)
     check(got, want)
     ctx.close()
+
+
+def test_chorus_at_an_odd_frame_size(pkg, oracle, capfd, monkeypatch):
+    """The chorus alone in the general kernel at 999 frames, after two calls of 1000 (which append to the ring in pairs): from the second odd call
+    on the ring's write position is odd, so the frame is appended cell by cell, and every thread's pair of samples is a pair of one."""
+    sr, sizes = 48000, [1000] * 2 + [999] * 12
+    monkeypatch.setenv("GDG_PLAN_TRACE", "2")
+    ctx = pkg.Context(2, 1000)
+    pairs = []
+    for c, params in enumerate((None, [35, 77])):
+        p = ChainPair(ctx, c, oracle)
+        p.append("chorus", params=params)
+        pairs.append(p)
+    x = np.stack([synth_signal(5 * c + 2, sum(sizes), sr) for c in range(2)])
+    capfd.readouterr()
+    pos = 0
+    for n in sizes:
+        blk = x[:, pos:pos + n]
+        got = ctx.process(blk, sr)
+        assert got.shape == (2, n) and np.isfinite(got).all()
+        check(got, np.stack([p.ref.process(blk[c], sr) for c, p in enumerate(pairs)]))
+        pos += n
+    ctx.close()
+    ran = shapes(capfd.readouterr().err)
+    assert ran == {"GENERAL"}, ran
 
 
 # ---- chains -----------------------------------------------------------------------------------------------------
