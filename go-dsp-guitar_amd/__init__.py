@@ -54,6 +54,8 @@ ABI_SYMBOLS = [
     "gdg_batch_set_trim", "gdg_wave_encode_trim", "gdg_wave_encode_trim_device", "gdg_trim_from_true_peak",
     "gdg_batch_set_blends", "gdg_batch_blends", "gdg_blend_rows", "gdg_blend_rows_device",
     "gdg_batch_set_blends_delayed", "gdg_batch_blend_max_delay", "gdg_blend_rows_delayed", "gdg_blend_rows_delayed_device", "gdg_blend_delays_from_align",
+    "gdg_batch_set_blends_filtered", "gdg_batch_blend_max_reach", "gdg_blend_rows_filtered", "gdg_blend_rows_filtered_device", "gdg_blend_fraction_taps",
+    "gdg_blend_fractions_from_fit",
     "gdg_batch_fit_enable", "gdg_batch_fits", "gdg_batch_fit", "gdg_block_fit_rows", "gdg_block_fit_rows_device", "gdg_blend_weights_from_fit",
     "gdg_batch_gram_enable", "gdg_batch_gram_ports", "gdg_batch_gram", "gdg_block_gram_rows", "gdg_block_gram_rows_device", "gdg_blend_pick_from_gram",
 ]
@@ -156,6 +158,34 @@ def blend_weights_from_fit(records, ridge=0.0):
     if rc != GDG_OK:
         raise GdgError(rc, lib().gdg_last_error(None).decode())
     return weight, residual
+
+
+BLEND_MAX_TAPS = 64          # GDG_BLEND_MAX_TAPS (include/gdg.h, FILTERS): the taps of one blend term
+
+
+def blend_fraction_taps(n_taps, fraction):
+    """gdg_blend_fraction_taps: n_taps (even, 2 to BLEND_MAX_TAPS) windowed-sinc taps that delay by n_taps / 2 - 1 + fraction samples,
+    0 <= fraction < 1, normalised to sum 1; fraction 0 is the exact unit impulse.  Host arithmetic: no context, no device."""
+    tap = np.zeros(max(int(n_taps), 1), dtype=np.float64)
+    rc = lib().gdg_blend_fraction_taps(int(n_taps), float(fraction), tap.ctypes.data if 2 <= int(n_taps) <= BLEND_MAX_TAPS else None)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return tap
+
+
+def blend_fractions_from_fit(records, steps):
+    """gdg_blend_fractions_from_fit: records [fits, blocks] (FIT_DTYPE) of fits whose 2 * steps - 1 terms are one channel's candidates at
+    (k - (steps - 1)) / steps samples around its whole-sample plan -> one int per fit, the winner's k - (steps - 1): the candidate with the
+    largest tx / sqrt(xx) over all blocks.  Host arithmetic: no context, no device.  GdgError names a fit with another term count or a
+    sum that is not finite."""
+    rec = np.ascontiguousarray(records, dtype=FIT_DTYPE)
+    if rec.ndim != 2:
+        raise ValueError("records: [fits, blocks]")
+    step = np.zeros(max(rec.shape[0], 1), dtype=np.int32)
+    rc = lib().gdg_blend_fractions_from_fit(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], int(steps), step.ctypes.data)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return [int(v) for v in step[:rec.shape[0]]]
 
 
 GRAM_MAX_PORTS = 512         # GDG_GRAM_MAX_PORTS (include/gdg.h): the ports of the one Gram list
@@ -452,6 +482,12 @@ def lib():
             "gdg_block_fit_rows": (i32, [vp, vp, i32, C.c_size_t, i32, i32, vp, vp, vp, vp]),
             "gdg_block_fit_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, i32, vp, vp, vp, vp]),
             "gdg_blend_weights_from_fit": (i32, [vp, i32, C.c_size_t, C.c_double, vp, vp]),
+            "gdg_batch_set_blends_filtered": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+            "gdg_batch_blend_max_reach": (i32, [vp]),
+            "gdg_blend_rows_filtered": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "gdg_blend_rows_filtered_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]),
+            "gdg_blend_fraction_taps": (i32, [i32, C.c_double, vp]),
+            "gdg_blend_fractions_from_fit": (i32, [vp, i32, C.c_size_t, i32, vp]),
             "gdg_batch_gram_enable": (i32, [vp, vp, i32]),
             "gdg_batch_gram_ports": (i32, [vp, vp, i32]),
             "gdg_batch_gram": (i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -1299,11 +1335,25 @@ class Context:
             return None
         return np.array([int(t[2]) if len(t) > 2 else 0 for t in terms] + [0], dtype=np.int32)
 
+    @staticmethod
+    def _blend_taps(blends):
+        """the taps of terms given as (channel, weight, delay, taps): (tap_first int32 [terms + 1], tap float64 with a spare entry), or None
+        where no term has a fourth entry"""
+        terms = [t for b in blends for t in b]
+        if not any(len(t) > 3 for t in terms):
+            return None
+        taps = [np.asarray(t[3], dtype=np.float64).reshape(-1) if len(t) > 3 and t[3] is not None else np.zeros(0) for t in terms]
+        tap_first = np.zeros(len(terms) + 1, dtype=np.int32)
+        tap_first[1:] = np.cumsum([h.size for h in taps], dtype=np.int64)
+        return tap_first, np.ascontiguousarray(np.concatenate(taps + [np.zeros(1)]), dtype=np.float64)
+
     def batch_set_blends(self, blends, gain=None):
-        """The blend outputs of the next batch calls (gdg_batch_set_blends, gdg_batch_set_blends_delayed): blends = a list of lists of
-        (channel, weight) or (channel, weight, delay) -- blend b is the sum of its terms over this context's chain output rows, in term
-        order, a term with a delay reading its row that many samples back (0 to BLEND_MAX_DELAY), and port N + 3 + b of every batch call;
-        gain: one output gain per blend (None: all 1).  An empty list (or None): off.  Configuration: not in a checkpoint."""
+        """The blend outputs of the next batch calls (gdg_batch_set_blends, gdg_batch_set_blends_delayed, gdg_batch_set_blends_filtered):
+        blends = a list of lists of (channel, weight), (channel, weight, delay) or (channel, weight, delay, taps) -- blend b is the sum of its
+        terms over this context's chain output rows, in term order, a term with a delay reading its row that many samples back (0 to
+        BLEND_MAX_DELAY) and a term with taps (up to BLEND_MAX_TAPS doubles) through that FIR, and port N + 3 + b of every batch call; gain:
+        one output gain per blend (None: all 1).  An empty list (or None): off.  Only a list that holds a four-entry term goes through the
+        filtered call.  Configuration: not in a checkpoint."""
         blends = [] if blends is None else [list(b) for b in blends]
         if not blends:
             self._check(lib().gdg_batch_set_blends(self._h, 0, None, None, None, None))
@@ -1313,6 +1363,11 @@ class Context:
         if g is not None and g.size != len(blends):
             raise ValueError("%d gains for %d blends" % (g.size, len(blends)))
         delay = self._blend_delays(blends)
+        taps = self._blend_taps(blends)
+        if taps is not None:
+            self._check(lib().gdg_batch_set_blends_filtered(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data, delay.ctypes.data,
+                                                            taps[0].ctypes.data, taps[1].ctypes.data, None if g is None else g.ctypes.data))
+            return
         if delay is not None:
             self._check(lib().gdg_batch_set_blends_delayed(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data,
                                                            delay.ctypes.data, None if g is None else g.ctypes.data))
@@ -1327,6 +1382,41 @@ class Context:
     def batch_blend_max_delay(self):
         """The largest delay of the blends in force (gdg_batch_blend_max_delay); 0: the blends are stateless."""
         return int(lib().gdg_batch_blend_max_delay(self._h))
+
+    def batch_blend_max_reach(self):
+        """The largest d + max(T, 1) - 1 of the blends in force (gdg_batch_blend_max_reach): how far back a term reads; 0: stateless."""
+        return int(lib().gdg_batch_blend_max_reach(self._h))
+
+    def blend_rows_filtered(self, rows, blends, history=None):
+        """gdg_blend_rows_filtered: rows [n_rows, samples] float64, blends of (row, weight[, delay[, taps]]) terms, history None (zeros in front
+        of sample 0) or [n_rows, BLEND_MAX_DELAY] float64 whose last column is sample -1 -> [blends, samples]."""
+        x = np.ascontiguousarray(rows, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("rows: [n_rows, samples]")
+        blends = [list(b) for b in blends]
+        first, channel, weight = self._blend_csr(blends)
+        delay, taps = self._blend_delays(blends), self._blend_taps(blends)
+        h = None if history is None else np.ascontiguousarray(history, dtype=np.float64)
+        if h is not None and h.shape != (x.shape[0], BLEND_MAX_DELAY):
+            raise ValueError("history: [n_rows, %d]" % BLEND_MAX_DELAY)
+        out = np.zeros((len(blends), x.shape[1]), dtype=np.float64)
+        rp = (C.c_void_p * max(x.shape[0], 1))(*[x[r].ctypes.data for r in range(x.shape[0])])
+        hp = None if h is None else (C.c_void_p * max(x.shape[0], 1))(*[h[r].ctypes.data for r in range(x.shape[0])])
+        op = (C.c_void_p * max(len(blends), 1))(*[out[b].ctypes.data for b in range(len(blends))])
+        self._check(lib().gdg_blend_rows_filtered(self._h, rp, x.shape[0], x.shape[1], len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data,
+                                                  None if delay is None else delay.ctypes.data, None if taps is None else taps[0].ctypes.data,
+                                                  None if taps is None else taps[1].ctypes.data, hp, op))
+        return out
+
+    def blend_rows_filtered_device(self, d_rows, row_stride, n_rows, samples, blends, d_out, out_stride, d_history=None, hist_stride=BLEND_MAX_DELAY):
+        """gdg_blend_rows_filtered_device on plain device pointers (ints); d_history as blend_rows_delayed_device takes it; returns when the
+        sums are written."""
+        blends = [list(b) for b in blends]
+        first, channel, weight = self._blend_csr(blends)
+        delay, taps = self._blend_delays(blends), self._blend_taps(blends)
+        self._check(lib().gdg_blend_rows_filtered_device(self._h, d_rows, row_stride, n_rows, samples, len(blends), first.ctypes.data, channel.ctypes.data,
+                                                         weight.ctypes.data, None if delay is None else delay.ctypes.data, None if taps is None else taps[0].ctypes.data,
+                                                         None if taps is None else taps[1].ctypes.data, d_history, hist_stride, d_out, out_stride))
 
     def blend_rows_delayed(self, rows, blends, history=None):
         """gdg_blend_rows_delayed: rows [n_rows, samples] float64, blends of (row, weight, delay) terms, history None (zeros in front of sample

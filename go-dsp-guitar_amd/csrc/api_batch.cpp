@@ -129,6 +129,10 @@ struct BatchLoop {
     /* the Gram list: n_gram ports on the host and on the device; 0 = off, and always for a shard */
     int n_gram;
     const int *h_gram_port, *d_gram_port;
+    /* taps in force (gdg_batch_set_blends_filtered): the offsets, one per term and one more, and the taps; null = no term has one.  The delays are then there as well,
+     * and the history only while a term reaches back -- null otherwise, and then no slot of a window lies in front of the job */
+    const int *d_blend_tap_first;
+    const double *d_blend_tap;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -278,7 +282,13 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             if (p.n_blends && !p.d_blend_delay)
                 HIP_TRY(ctx, gdg_launch_blend_rows(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight,
                                                    d_win + (size_t)NO * ws, ws, ctx->stream));
-            if (p.n_blends && p.d_blend_delay) {
+            if (p.n_blends && p.d_blend_tap_first) {
+                /* filtered terms: the same history, read up to d + T - 1 samples back and replaced behind the sum */
+                HIP_TRY(ctx, gdg_launch_blend_rows_filtered(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight, p.d_blend_delay,
+                                                            p.d_blend_tap_first, p.d_blend_tap, p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, d_win + (size_t)NO * ws, ws,
+                                                            ctx->stream));
+                if (p.d_blend_history) HIP_TRY(ctx, gdg_launch_blend_history_save(d_win, ws, (size_t)wb, (unsigned)N, p.d_blend_history, ctx->stream));
+            } else if (p.n_blends && p.d_blend_delay) {
                 /* delayed terms reach into the step before: its tail is the history (a step has at least 8192 samples, a delay at most 4096).
                  * This step's tail replaces it behind the sum and before the next step writes the window. */
                 HIP_TRY(ctx, gdg_launch_blend_rows_delayed(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight, p.d_blend_delay,
@@ -506,7 +516,8 @@ int gdg_batch_set_trim(gdg_ctx *ctx, const double *chain_gain, int n, double mas
 }
 
 /* the blend outputs: validated whole before the list replaces the one in force (blend.h); read when a job is described and by every slice */
-int gdg_batch_set_blends_delayed(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const double *gain) {
+int gdg_batch_set_blends_filtered(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const int *tap_first,
+                                  const double *tap, const double *gain) {
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set blends: a streamed batch run is open on this context; its blends hold until gdg_batch_stream_close");
     int b = -1, k = -1;
@@ -523,14 +534,20 @@ int gdg_batch_set_blends_delayed(gdg_ctx *ctx, int n_blends, const int *first, c
     case BLEND_DELAY: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d: delay = %d; 0 to %d samples", b, k, delay[first[b] + k], GDG_BLEND_MAX_DELAY);
     default: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d: gain = %g is not finite", b, gain[b]);
     }
+    int t = -1;
+    if (const int rc = gdg_blend_check_taps(n_blends, first, delay, tap_first, tap, &b, &k, &t)) {
+        char msg[240];
+        gdg_blend_taps_message(msg, sizeof msg, "set blends", rc, b, k, t, first, delay, tap_first, tap, n_blends);
+        return fail(ctx, GDG_ERR_INVALID, "%s", msg);
+    }
     enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
-    const bool resize = n_blends != ctx->blend.count(), had_delay = ctx->blend.max_delay() > 0;
+    const bool resize = n_blends != ctx->blend.count(), had_delay = ctx->blend.max_reach() > 0;
     /* another row count: whatever still reads the window and the encoded halves has to be done before they go -- and a wait that fails
      * refuses the call with the setting in force untouched */
     if (resize || had_delay) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    gdg_blend_replace(ctx->blend, n_blends, first, channel, weight, delay, gain, ctx->nch, &b, &k);      /* checked above: it cannot refuse */
-    /* no delay left in force: the history goes (the next job with one begins from zeros anyway) */
-    if (had_delay && ctx->blend.max_delay() == 0) { hipFree(ctx->batch_dev[BATCH_BLEND_HISTORY]); ctx->batch_dev[BATCH_BLEND_HISTORY] = nullptr; ctx->batch_dev_cap[BATCH_BLEND_HISTORY] = 0; }
+    gdg_blend_replace(ctx->blend, n_blends, first, channel, weight, delay, tap_first, tap, gain, ctx->nch, &b, &k);      /* checked above: it cannot refuse */
+    /* no term reaches back any more: the history goes (the next job with one begins from zeros anyway) */
+    if (had_delay && ctx->blend.max_reach() == 0) { hipFree(ctx->batch_dev[BATCH_BLEND_HISTORY]); ctx->batch_dev[BATCH_BLEND_HISTORY] = nullptr; ctx->batch_dev_cap[BATCH_BLEND_HISTORY] = 0; }
     if (resize) {
         /* the window and the encoded halves are made anew by the next batch call, at the size of a context that was always configured like
          * this one; off, the table goes as well */
@@ -540,12 +557,18 @@ int gdg_batch_set_blends_delayed(gdg_ctx *ctx, int n_blends, const int *first, c
     return GDG_OK;
 }
 
+/* without taps: the filtered call with tap_first == NULL, which takes, packs and uploads the list as it did before taps existed */
+int gdg_batch_set_blends_delayed(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const double *gain) {
+    return gdg_batch_set_blends_filtered(ctx, n_blends, first, channel, weight, delay, nullptr, nullptr, gain);
+}
+
 int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
     return gdg_batch_set_blends_delayed(ctx, n_blends, first, channel, weight, nullptr, gain);
 }
 
 int gdg_batch_blends(const gdg_ctx *ctx) { return ctx ? ctx->blend.count() : 0; }
 int gdg_batch_blend_max_delay(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_delay() : 0; }
+int gdg_batch_blend_max_reach(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_reach() : 0; }
 
 /* the blend fits: validated whole before the list replaces the one in force (blend.h); the ports' upper bound is the job's, checked when one is described */
 int gdg_batch_fit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *port, const int *target) {
@@ -981,7 +1004,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr };
         /* the fits in force: their table goes up on the context's stream, ahead of everything the slice enqueues there; it lives as long as
          * the setting, so nothing waits here */
         if (n_fits) {
@@ -1007,7 +1030,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_trim, ctx->trim_gain.data(), (size_t)NO * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             loop.d_trim = ctx->d_trim;
         }
-        /* the blends in force: their table goes up the same way -- first | channel | weight | gain, the doubles 8-byte aligned (BlendSet::packed) */
+        /* the blends in force: their table goes up the same way -- first | channel | delay | tap_first | pad | weight | gain | taps, the delays and the
+         * tap offsets only where the list has them, the doubles 8-byte aligned (BlendSet::packed) */
         if (n_blends) {
             const BlendSet &bs = ctx->blend;                                  /* packed when it was set: it lives as long as the setting, so nothing waits here */
             const size_t ints = bs.packed_ints(), bytes = bs.packed.size();
@@ -1024,7 +1048,12 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             loop.d_blend_channel = loop.d_blend_first + n_blends + 1;
             loop.d_blend_weight = reinterpret_cast<const double *>(ctx->d_blend + ints);
             loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.d_blend_weight + bs.terms();
-            if (bs.max_delay() > 0) {
+            if (!bs.delay.empty()) loop.d_blend_delay = loop.d_blend_channel + bs.terms();      /* there while a delay is not 0 or a term has taps */
+            if (!bs.tap_first.empty()) {
+                loop.d_blend_tap_first = loop.d_blend_delay + bs.terms();
+                loop.d_blend_tap = reinterpret_cast<const double *>(ctx->d_blend + bs.packed_taps());
+            }
+            if (bs.max_reach() > 0) {
                 /* the history of the N chain rows: the job's first slice begins from zeros, every later one from what the slice before left */
                 const size_t hist_bytes = (size_t)N * GDG_BLEND_MAX_DELAY * sizeof(double);
                 const bool fresh = ctx->batch_dev_cap[BATCH_BLEND_HISTORY] < hist_bytes;
@@ -1032,7 +1061,6 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
                 if ((r = batch_buffer(ctx, BATCH_BLEND_HISTORY, hist_bytes, (void **)&loop.d_blend_history)) != GDG_OK) return r;
                 if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the blend history of the open job is gone (gdg_batch_release between two slices?)");
                 if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_blend_history, 0, hist_bytes, ctx->stream));
-                loop.d_blend_delay = loop.d_blend_channel + bs.terms();
             }
         }
         return batch_block_loop(ctx, loop, stage);

@@ -101,10 +101,11 @@ static int checkpoint_plan(gdg_ctx *ctx, CkptPlan &P) {
 /* version 1 records positions and resampler carries per input; a reader has neither of its own */
 #define SHARED_SOURCES_REFUSED(ctx, what) \
     fail(ctx, GDG_ERR_UNSUPPORTED, "%s: a job with shared sources (gdg_batch_set_sources: a channel reads another's input) cannot be checkpointed yet", what)
-/* ... and nothing of the blend history (gdg_batch_set_blends_delayed): the chain rows' last samples, which a delayed term reads */
+/* ... and nothing of the blend history (gdg_batch_set_blends_delayed, gdg_batch_set_blends_filtered): the chain rows' last samples, which a
+ * delayed or filtered term reads */
 #define BLEND_HISTORY_REFUSED(ctx, what) \
-    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: a blend delay of up to %d samples is in force (gdg_batch_set_blends_delayed); the blend history is not in the version-1 container", what, \
-         (ctx)->blend.max_delay())
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: a blend term reaches up to %d samples back (gdg_batch_set_blends_delayed, gdg_batch_set_blends_filtered); the blend history is not in the version-1 container", what, \
+         (ctx)->blend.max_reach())
 static bool input_has_samples(const gdg_batch_input &in) { return in.bytes && in.samples_per_channel; }
 /* the frames of input i's carry that hold source frames: what the next step of the job will read from it (api_batch.cpp, stream_step) */
 static uint32_t carry_valid(const gdg_ctx::BatchStreamState &S, size_t i) {
@@ -116,7 +117,7 @@ static uint32_t carry_valid(const gdg_ctx::BatchStreamState &S, size_t i) {
 int gdg_batch_stream_checkpoint_size(gdg_ctx *ctx, size_t *bytes) {
     if (!ctx || !bytes) return GDG_ERR_INVALID;
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, "checkpoint");
-    if (ctx->blend.max_delay() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
+    if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
     if (!ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     const int rc = checkpoint_plan(ctx, P);
@@ -128,7 +129,7 @@ int gdg_batch_stream_checkpoint(gdg_ctx *ctx, void *blob, size_t capacity, size_
     if (!ctx || !blob) return GDG_ERR_INVALID;
     const auto &S = ctx->bstream;
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, "checkpoint");
-    if (ctx->blend.max_delay() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
+    if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
     if (!S.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     int rc = checkpoint_plan(ctx, P);
@@ -264,7 +265,7 @@ static int resume(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
     if (!ctx || !inputs || !opt || !blob || !samples_done) return GDG_ERR_INVALID;
     const char *what = shard ? "resume (shard)" : "resume";
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, what);
-    if (ctx->blend.max_delay() > 0) return BLEND_HISTORY_REFUSED(ctx, what);
+    if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, what);
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "%s: a streamed batch run is already open on this context", what);
     CkptHeader h;
     int rc = read_header(ctx, what, blob, bytes, h);

@@ -878,6 +878,106 @@ int gdg_blend_rows_delayed(gdg_ctx *ctx, const double *const *rows, int n_rows, 
     return GDG_OK;
 }
 
+/* ---- the filtered blend on its own: the table goes up with its delays, offsets and taps; without a tap it is the delayed call ---- */
+static int blend_rows_check_taps(gdg_ctx *ctx, int n_blends, const int *first, const int *delay, const int *tap_first, const double *tap) {
+    int b = -1, k = -1, t = -1;
+    const int rc = gdg_blend_check_taps(n_blends, first, delay, tap_first, tap, &b, &k, &t);
+    if (rc == BLEND_OK) return GDG_OK;
+    char msg[240];
+    gdg_blend_taps_message(msg, sizeof msg, "blend rows", rc, b, k, t, first, delay, tap_first, tap, n_blends);
+    return fail(ctx, GDG_ERR_INVALID, "%s", msg);
+}
+
+int gdg_blend_rows_filtered_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
+                                   const int *channel, const double *weight, const int *delay, const int *tap_first, const double *tap, const double *d_history,
+                                   size_t hist_stride, double *d_out, size_t out_stride) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
+    if (rc == GDG_OK) rc = blend_rows_check_taps(ctx, n_blends, first, delay, tap_first, tap);
+    if (rc != GDG_OK) return rc;
+    if (n_blends == 0 || samples == 0) return GDG_OK;
+    if (!tap_first || tap_first[first[n_blends]] == 0)                       /* no tap anywhere: the delayed sum, by its own kernel */
+        return gdg_blend_rows_delayed_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, delay, d_history, hist_stride, d_out, out_stride);
+    if (!d_rows || !d_out) return GDG_ERR_INVALID;
+    if (row_stride < samples || out_stride < samples) return fail(ctx, GDG_ERR_INVALID, "blend rows: strides of %zu and %zu samples for rows of %zu", row_stride, out_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7)) return fail(ctx, GDG_ERR_INVALID, "blend rows: rows and sums are 8-byte aligned");
+    if (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY))
+        return fail(ctx, GDG_ERR_INVALID, "blend rows: the history is 8-byte aligned, a row's run has %d samples; its stride is %zu", GDG_BLEND_MAX_DELAY, hist_stride);
+    enter_keep_fir_sums(ctx);
+    /* first | channel | delay | tap_first | pad | weight | taps */
+    const size_t terms = (size_t)first[n_blends], n_taps = (size_t)tap_first[terms], ints = (((size_t)n_blends + 1 + 3 * terms + 1) * sizeof(int) + 7) & ~(size_t)7,
+                 bytes = ints + (terms + n_taps) * sizeof(double);
+    std::vector<unsigned char> host(bytes, 0);
+    memcpy(host.data(), first, ((size_t)n_blends + 1) * sizeof(int));
+    memcpy(host.data() + ((size_t)n_blends + 1) * sizeof(int), channel, terms * sizeof(int));
+    if (delay) memcpy(host.data() + ((size_t)n_blends + 1 + terms) * sizeof(int), delay, terms * sizeof(int));
+    memcpy(host.data() + ((size_t)n_blends + 1 + 2 * terms) * sizeof(int), tap_first, (terms + 1) * sizeof(int));
+    memcpy(host.data() + ints, weight, terms * sizeof(double));
+    memcpy(host.data() + ints + terms * sizeof(double), tap, n_taps * sizeof(double));
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, bytes));
+    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        const int *d_first = static_cast<const int *>(d);
+        const double *d_weight = reinterpret_cast<const double *>(static_cast<unsigned char *>(d) + ints);
+        e = gdg_launch_blend_rows_filtered(d_rows, row_stride, samples, (unsigned)n_blends, d_first, d_first + n_blends + 1, d_weight, d_first + n_blends + 1 + terms,
+                                           d_first + n_blends + 1 + 2 * terms, d_weight + terms, d_history, hist_stride, d_out, out_stride, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(w));
+    return GDG_OK;
+}
+
+int gdg_blend_rows_filtered(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                            const double *weight, const int *delay, const int *tap_first, const double *tap, const double *const *history, double *const *out) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
+    if (rc == GDG_OK) rc = blend_rows_check_taps(ctx, n_blends, first, delay, tap_first, tap);
+    if (rc != GDG_OK) return rc;
+    if (n_blends == 0 || samples == 0) return GDG_OK;
+    if (!rows || !out) return GDG_ERR_INVALID;
+    for (int b = 0; b < n_blends; b++) if (!out[b]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the row of blend %d is NULL", b);
+    if (history) for (int r = 0; r < n_rows; r++) if (!history[r]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the history of row %d is NULL", r);
+    const size_t H = (size_t)GDG_BLEND_MAX_DELAY;
+    void *d_hist = nullptr;
+    if (history) {
+        enter_keep_fir_sums(ctx);
+        HIP_TRY(ctx, ctx->arena.alloc(&d_hist, (size_t)n_rows * H * sizeof(double)));
+        for (int r = 0; r < n_rows; r++) {
+            const hipError_t e = hipMemcpyAsync(static_cast<double *>(d_hist) + (size_t)r * H, history[r], H * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) {
+                hipStreamSynchronize(ctx->stream);
+                ctx->arena.release(d_hist);
+                return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
+            }
+        }
+    }
+    std::vector<double> sums((size_t)n_blends * samples);
+    rc = rows_round_trip(ctx, "blend rows", rows, n_rows, samples, sums.data(), sums.size() * sizeof(double), [&](const double *d_rows, void *d_out) {
+        return gdg_blend_rows_filtered_device(ctx, d_rows, samples, n_rows, samples, n_blends, first, channel, weight, delay, tap_first, tap,
+                                              static_cast<const double *>(d_hist), H, static_cast<double *>(d_out), samples);
+    });
+    if (d_hist) {
+        hipStreamSynchronize(ctx->stream);
+        ctx->arena.release(d_hist);
+    }
+    if (rc != GDG_OK) return rc;
+    for (int b = 0; b < n_blends; b++) memcpy(out[b], sums.data() + (size_t)b * samples, samples * sizeof(double));
+    return GDG_OK;
+}
+
+/* the taps of a fractional delay (blend.h): pure host arithmetic, no context */
+int gdg_blend_fraction_taps(int n_taps, double fraction, double *tap) {
+    if (gdg_blend_fraction_taps_plan(n_taps, fraction, tap)) return GDG_OK;
+    char msg[200];
+    snprintf(msg, sizeof msg, "blend fraction taps: %d taps (even, 2 to %d) for a fraction of %g (0 <= fraction < 1); tap is needed", n_taps, GDG_BLEND_MAX_TAPS, fraction);
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
+}
+
 /* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
 int gdg_blend_delays_from_align(const gdg_block_align *records, int ports, size_t blocks, const int *ref, double min_coeff, int n_blends, const int *first,
                                 const int *channel, int *delay, int *sign) {
@@ -998,6 +1098,20 @@ int gdg_blend_weights_from_fit(const gdg_block_fit *records, int n_fits, size_t 
         snprintf(msg, sizeof msg, "blend weights from fit: fit %d: a pivot at or below K * 2^-52 * max(diag G) -- a silent term, or a port used twice with ridge = 0", bad);
         break;
     default: snprintf(msg, sizeof msg, "blend weights from fit: %d fits (0 to %d) of %zu blocks (at least 1), ridge = %g (finite, >= 0); records, weight and residual are needed", n_fits, GDG_FIT_MAX_FITS, blocks, ridge); break;
+    }
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
+}
+
+/* the fraction of a delay from fit records (blend.h): pure host arithmetic, no context */
+int gdg_blend_fractions_from_fit(const gdg_block_fit *records, int n_fits, size_t blocks, int steps, int *step) {
+    int bad = -1;
+    char msg[240];
+    switch (gdg_blend_plan_fractions(reinterpret_cast<const gdg_blend_fit_rec *>(records), n_fits, blocks, steps, step, &bad)) {
+    case FRACTION_OK: return GDG_OK;
+    case FRACTION_TERMS: snprintf(msg, sizeof msg, "blend fractions from fit: fit %d: a record has another term count than 2 * %d - 1 = %d candidates", bad, steps, 2 * steps - 1); break;
+    case FRACTION_NONFINITE: snprintf(msg, sizeof msg, "blend fractions from fit: fit %d: a sum over its %zu blocks is a NaN or inf", bad, blocks); break;
+    default: snprintf(msg, sizeof msg, "blend fractions from fit: %d fits (0 to %d) of %zu blocks (at least 1), steps = %d (1 to 4); records and step are needed", n_fits, GDG_FIT_MAX_FITS, blocks, steps); break;
     }
     set_free_error(msg);
     return GDG_ERR_INVALID;

@@ -1,7 +1,7 @@
 /*
  * blend.h -- the blend outputs (gdg_batch_set_blends, gdg_blend_rows; include/gdg.h states the arithmetic): a blend is a weighted sum of
  * chain output rows, s = w_0 x[c_0], then s = s + w_k x[c_k] in term order, every product and every add rounded on its own; a term may be
- * delayed by a whole number of samples (gdg_batch_set_blends_delayed).  Here: the two rounded operations as __host__ __device__ inlines --
+ * delayed by a whole number of samples (gdg_batch_set_blends_delayed) and pass a short FIR of its own (gdg_batch_set_blends_filtered).  Here: the two rounded operations as __host__ __device__ inlines --
  * the kernels of blend_kernels.h use them, and so can a stand-alone host program (tests/native/blend_check.cpp, blend_delay_check.cpp) --
  * the validation of a blend list in its CSR form, the rule by which a list replaces the one in force, the sum on the host, and the planner
  * that turns alignment records into delays and signs (gdg_blend_delays_from_align); and, for the blend fit (include/gdg.h, FIT), the
@@ -16,6 +16,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 #include <vector>
 
@@ -26,6 +27,9 @@
 #endif
 #ifndef GDG_BLEND_MAX_DELAY
 #define GDG_BLEND_MAX_DELAY 4096
+#endif
+#ifndef GDG_BLEND_MAX_TAPS
+#define GDG_BLEND_MAX_TAPS 64
 #endif
 
 #if defined(__HIPCC__)
@@ -63,7 +67,11 @@ enum {
     BLEND_CHANNEL = 6,                         /* term `term` of blend b names a channel outside [0, n_channels) */
     BLEND_WEIGHT = 7,                          /* ... has a weight that is not finite */
     BLEND_GAIN = 8,                            /* blend b's output gain is not finite */
-    BLEND_DELAY = 9                            /* term `term` of blend b has a delay outside 0 .. GDG_BLEND_MAX_DELAY */
+    BLEND_DELAY = 9,                           /* term `term` of blend b has a delay outside 0 .. GDG_BLEND_MAX_DELAY */
+    BLEND_TAP_FIRST = 10,                      /* tap_first does not start at 0, or descends at term `term` of blend b */
+    BLEND_TAP_COUNT = 11,                      /* ... has more than GDG_BLEND_MAX_TAPS taps */
+    BLEND_TAP = 12,                            /* ... has a tap that is not finite: *tap_at is its place among the term's taps */
+    BLEND_REACH = 13                           /* ... reaches further back than GDG_BLEND_MAX_DELAY: d + max(T, 1) - 1 */
 };
 
 /* The whole list: n_blends blends, blend b's terms at [first[b], first[b + 1]) of channel[], weight[] and delay[]; delay: one per term, or
@@ -102,6 +110,45 @@ static inline int gdg_blend_check(int n_blends, const int *first, const int *cha
     return gdg_blend_check(n_blends, first, channel, weight, (const int *)nullptr, gain, n_channels, blend, term);
 }
 
+/* The taps of a list that gdg_blend_check has passed (include/gdg.h, FILTERS): tap_first has one entry per term and one more, over all terms
+ * of all blends; term k's taps are tap[tap_first[k] .. tap_first[k + 1]).  *blend, *term: the first offender, *tap_at: the tap where one is
+ * named.  The offsets are checked first: nothing is read through a bad one. */
+static inline int gdg_blend_check_taps(int n_blends, const int *first, const int *delay, const int *tap_first, const double *tap, int *blend, int *term, int *tap_at) {
+    *blend = *term = *tap_at = -1;
+    if (n_blends == 0 || !tap_first) return BLEND_OK;
+    const int terms = first[n_blends];
+    auto name = [&](int k) { int b = 0; while (first[b + 1] <= k) b++; *blend = b; *term = k - first[b]; };
+    if (tap_first[0] != 0) { name(0); return BLEND_TAP_FIRST; }
+    for (int k = 0; k < terms; k++) {
+        if (tap_first[k + 1] < tap_first[k]) { name(k); return BLEND_TAP_FIRST; }
+        if (tap_first[k + 1] - tap_first[k] > GDG_BLEND_MAX_TAPS) { name(k); return BLEND_TAP_COUNT; }
+    }
+    if (tap_first[terms] > 0 && !tap) return BLEND_NULL;
+    for (int k = 0; k < terms; k++) {
+        const int T = tap_first[k + 1] - tap_first[k], d = delay ? delay[k] : 0;
+        for (int t = 0; t < T; t++) if (!isfinite(tap[tap_first[k] + t])) { name(k); *tap_at = t; return BLEND_TAP; }
+        if (d + (T > 1 ? T : 1) - 1 > GDG_BLEND_MAX_DELAY) { name(k); return BLEND_REACH; }
+    }
+    return BLEND_OK;
+}
+
+/* what gdg_blend_check_taps refused, in words, for the call `what` ("set blends", "blend rows"): one text for both */
+static inline void gdg_blend_taps_message(char *msg, size_t size, const char *what, int rc, int b, int k, int t, const int *first, const int *delay, const int *tap_first,
+                                          const double *tap, int n_blends) {
+    const int at = b >= 0 ? first[b] + k : 0, T = b >= 0 ? tap_first[at + 1] - tap_first[at] : 0, d = b >= 0 && delay ? delay[at] : 0;
+    switch (rc) {
+    case BLEND_NULL: snprintf(msg, size, "%s: tap_first names %d taps and tap is NULL", what, tap_first[first[n_blends]]); break;
+    case BLEND_TAP_FIRST:
+        snprintf(msg, size, "%s: blend %d, term %d: tap_first[%d] = %d, tap_first[%d] = %d; the offsets start at 0 and never descend", what, b, k, at, tap_first[at], at + 1, tap_first[at + 1]);
+        break;
+    case BLEND_TAP_COUNT: snprintf(msg, size, "%s: blend %d, term %d has %d taps; 0 to %d", what, b, k, T, GDG_BLEND_MAX_TAPS); break;
+    case BLEND_TAP: snprintf(msg, size, "%s: blend %d, term %d: tap %d = %g is not finite", what, b, k, t, tap[tap_first[at] + t]); break;
+    default:
+        snprintf(msg, size, "%s: blend %d, term %d: a delay of %d samples and %d taps reach %d samples back; at most %d", what, b, k, d, T, d + (T > 1 ? T : 1) - 1, GDG_BLEND_MAX_DELAY);
+        break;
+    }
+}
+
 /* the list in force */
 struct BlendSet {
     std::vector<int> first, channel;           /* first: count() + 1 offsets, empty = off */
@@ -109,27 +156,41 @@ struct BlendSet {
     std::vector<int> delay;                    /* one per term; empty = every delay 0, and the list is what it was before delays existed */
     int count() const { return first.empty() ? 0 : (int)first.size() - 1; }
     int terms() const { return (int)channel.size(); }
+    /* the taps (FILTERS): terms() + 1 offsets into tap; both empty = no term has a tap, and the list is what it was before taps existed */
+    std::vector<int> tap_first;
+    std::vector<double> tap;
     int max_delay() const { int m = 0; for (int d : delay) if (d > m) m = d; return m; }
+    int taps(int k) const { return tap_first.empty() ? 0 : tap_first[(size_t)k + 1] - tap_first[(size_t)k]; }
+    /* how far back a term reads: the largest d_k + max(T_k, 1) - 1; without taps the largest delay */
+    int max_reach() const {
+        int m = max_delay();
+        for (int k = 0; k < terms() && !tap_first.empty(); k++) { const int r = delay[(size_t)k] + (taps(k) > 1 ? taps(k) : 1) - 1; if (r > m) m = r; }
+        return m;
+    }
     bool unit_gains() const { for (double g : gain) if (g != 1.0) return false; return true; }
-    /* the table as a batch call uploads it, made when the list is taken: first | channel | delay | pad to 8 bytes | weight | gain; the delays
-     * are there only while one of them is not 0 */
+    /* the table as a batch call uploads it, made when the list is taken: first | channel | delay | tap_first | pad to 8 bytes | weight | gain |
+     * taps; the delays are there only while one of them is not 0 or a term has taps, tap_first and the taps only while a term has taps */
     std::vector<unsigned char> packed;
-    size_t packed_ints() const { return ((first.size() + channel.size() + delay.size()) * sizeof(int) + 7) & ~(size_t)7; }
+    size_t packed_ints() const { return ((first.size() + channel.size() + delay.size() + tap_first.size()) * sizeof(int) + 7) & ~(size_t)7; }
+    size_t packed_taps() const { return packed_ints() + (weight.size() + gain.size()) * sizeof(double); }      /* where the taps begin */
     void pack() {
-        packed.assign(first.empty() ? 0 : packed_ints() + (weight.size() + gain.size()) * sizeof(double), 0);
+        packed.assign(first.empty() ? 0 : packed_taps() + tap.size() * sizeof(double), 0);
         if (packed.empty()) return;
         memcpy(packed.data(), first.data(), first.size() * sizeof(int));
         memcpy(packed.data() + first.size() * sizeof(int), channel.data(), channel.size() * sizeof(int));
         if (!delay.empty()) memcpy(packed.data() + (first.size() + channel.size()) * sizeof(int), delay.data(), delay.size() * sizeof(int));
         memcpy(packed.data() + packed_ints(), weight.data(), weight.size() * sizeof(double));
         memcpy(packed.data() + packed_ints() + weight.size() * sizeof(double), gain.data(), gain.size() * sizeof(double));
+        if (!tap_first.empty()) memcpy(packed.data() + (first.size() + channel.size() + delay.size()) * sizeof(int), tap_first.data(), tap_first.size() * sizeof(int));
+        if (!tap.empty()) memcpy(packed.data() + packed_taps(), tap.data(), tap.size() * sizeof(double));
     }
 };
 
 /* whole or not at all: a refused list leaves the one in force as it is */
 static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *first, const int *channel, const double *weight, const int *delay,
-                                    const double *gain, int n_channels, int *blend, int *term) {
-    const int rc = gdg_blend_check(n_blends, first, channel, weight, delay, gain, n_channels, blend, term);
+                                    const int *tap_first, const double *tap, const double *gain, int n_channels, int *blend, int *term) {
+    int rc = gdg_blend_check(n_blends, first, channel, weight, delay, gain, n_channels, blend, term), tap_at = -1;
+    if (rc == BLEND_OK) rc = gdg_blend_check_taps(n_blends, first, delay, tap_first, tap, blend, term, &tap_at);
     if (rc != BLEND_OK) return rc;
     BlendSet next;
     if (n_blends > 0) {
@@ -143,10 +204,19 @@ static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *firs
             next.delay.assign(delay, delay + terms);
             if (next.max_delay() == 0) next.delay.clear();                   /* all zeros: the list without delays */
         }
+        if (tap_first && tap_first[terms] > 0) {                             /* no tap anywhere: the list without taps */
+            next.tap_first.assign(tap_first, tap_first + terms + 1);
+            next.tap.assign(tap, tap + tap_first[terms]);
+            if (next.delay.empty()) next.delay.assign((size_t)terms, 0);     /* a filtered table always carries its delays */
+        }
     }
     next.pack();
     set = next;
     return BLEND_OK;
+}
+static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *first, const int *channel, const double *weight, const int *delay,
+                                    const double *gain, int n_channels, int *blend, int *term) {
+    return gdg_blend_replace(set, n_blends, first, channel, weight, delay, (const int *)nullptr, (const double *)nullptr, gain, n_channels, blend, term);
 }
 static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *first, const int *channel, const double *weight, const double *gain,
                                     int n_channels, int *blend, int *term) {
@@ -188,6 +258,53 @@ static inline void gdg_blend_sum_host_delayed(const double *const *rows, const d
                                               const int *channel, const double *weight, const int *delay, double *const *out) {
     for (int b = 0; b < n_blends; b++)
         for (size_t i = 0; i < samples; i++) out[b][i] = gdg_blend_sample_delayed(rows, history, i, channel, weight, delay, first[b], first[b + 1]);
+}
+
+/* ---- filtered terms (include/gdg.h, FILTERS: x_k[i] = h_k[0] x[c_k][i - d_k], then + h_k[t] x[c_k][i - d_k - t] in ascending t) ------------------ */
+/* the definition on the host: tap_first = one offset per term and one more, or null (no taps: the delayed sum) */
+static inline double gdg_blend_sample_filtered(const double *const *rows, const double *const *history, size_t i, const int *channel, const double *weight,
+                                               const int *delay, const int *tap_first, const double *tap, int k0, int k1) {
+    auto x = [&](int k) {
+        const double *row = rows[channel[k]], *hist = history ? history[channel[k]] : nullptr;
+        const int d = delay ? delay[k] : 0, T = tap_first ? tap_first[k + 1] - tap_first[k] : 0;
+        if (T == 0) return gdg_blend_delayed_x(row, hist, i, d);
+        const double *h = tap + tap_first[k];
+        double f = gdg_blend_mul(h[0], gdg_blend_delayed_x(row, hist, i, d));
+        for (int t = 1; t < T; t++) f = gdg_blend_add(f, gdg_blend_mul(h[t], gdg_blend_delayed_x(row, hist, i, d + t)));
+        return f;
+    };
+    double s = gdg_blend_mul(weight[k0], x(k0));
+    for (int k = k0 + 1; k < k1; k++) s = gdg_blend_add(s, gdg_blend_mul(weight[k], x(k)));
+    return s;
+}
+
+static inline void gdg_blend_sum_host_filtered(const double *const *rows, const double *const *history, size_t samples, int n_blends, const int *first,
+                                               const int *channel, const double *weight, const int *delay, const int *tap_first, const double *tap,
+                                               double *const *out) {
+    for (int b = 0; b < n_blends; b++)
+        for (size_t i = 0; i < samples; i++)
+            out[b][i] = gdg_blend_sample_filtered(rows, history, i, channel, weight, delay, tap_first, tap, first[b], first[b + 1]);
+}
+
+/* ---- the taps of a fractional delay (gdg_blend_fraction_taps) ---------------------------------------------------------------------------- */
+/* T taps (even, 2 .. GDG_BLEND_MAX_TAPS) that delay by T/2 - 1 + f samples, 0 <= f < 1: sinc(u) (0.5 + 0.5 cos(2 pi u / T)) with u = t -
+ * (T/2 - 1) - f, divided by their sum (added in ascending t).  f == 0: the unit impulse at T/2 - 1, exactly, and no call into libm.
+ * false: an argument out of range; nothing is written. */
+static inline bool gdg_blend_fraction_taps_plan(int T, double f, double *tap) {
+    if (T < 2 || T > GDG_BLEND_MAX_TAPS || (T & 1) || !(f >= 0.0 && f < 1.0) || !tap) return false;
+    if (f == 0.0) {
+        for (int t = 0; t < T; t++) tap[t] = t == T / 2 - 1 ? 1.0 : 0.0;
+        return true;
+    }
+    const double pi = 3.141592653589793;
+    double h[GDG_BLEND_MAX_TAPS], sum = 0.0;
+    for (int t = 0; t < T; t++) {
+        const double u = (double)(t - (T / 2 - 1)) - f;                      /* never 0: 0 < f < 1 */
+        h[t] = sin(pi * u) / (pi * u) * (0.5 + 0.5 * cos(2.0 * pi * u / (double)T));
+        sum += h[t];
+    }
+    for (int t = 0; t < T; t++) tap[t] = h[t] / sum;
+    return true;
 }
 
 /* ---- the delays from the alignment records (gdg_blend_delays_from_align) --------------------------------------------------------------- */
@@ -426,6 +543,52 @@ static inline int gdg_blend_plan_weights(const gdg_blend_fit_rec *records, int n
     memcpy(weight, w_all.data(), w_all.size() * sizeof(double));
     memcpy(residual, res_all.data(), res_all.size() * sizeof(double));
     return FIT_PLAN_OK;
+}
+
+/* ---- the fraction of a delay from fit records (gdg_blend_fractions_from_fit) ---------------------------------------------------------------- */
+enum {
+    FRACTION_OK = 0,
+    FRACTION_ARGS = 1,                         /* a list is missing, a count is out of range, no block, steps outside 1 .. 4 */
+    FRACTION_TERMS = 2,                        /* a record of *fit has another term count than 2 steps - 1 */
+    FRACTION_NONFINITE = 3                     /* a sum of *fit -- tt, a tx or a diagonal xx -- is a NaN or inf */
+};
+
+/* records[n_fits][blocks]; a fit has the 2Q - 1 candidates of one channel, term k at (k - (Q - 1)) / Q samples, measured against the target.
+ * The blocks' sums are added in block order; the candidate with the largest tx[k] / sqrt(xx[k][k]) among those with xx[k][k] > 0 wins, the
+ * earlier entry on a tie; step[f] = k - (Q - 1), 0 where tt <= 0 or no candidate is admissible.  Every fit is decided before step[] is
+ * written; *fit: the offender. */
+static inline int gdg_blend_plan_fractions(const gdg_blend_fit_rec *records, int n_fits, size_t blocks, int steps, int *step, int *fit) {
+    *fit = -1;
+    if (n_fits < 0 || n_fits > GDG_FIT_MAX_FITS || steps < 1 || steps > 4) return FRACTION_ARGS;
+    if (n_fits == 0) return FRACTION_OK;
+    if (!records || !step || blocks == 0) return FRACTION_ARGS;
+    const int K = 2 * steps - 1;
+    std::vector<int> all((size_t)n_fits, 0);
+    for (int f = 0; f < n_fits; f++) {
+        *fit = f;
+        const gdg_blend_fit_rec *rec = records + (size_t)f * blocks;
+        double tt = 0.0, tx[GDG_FIT_MAX_TERMS], xx[GDG_FIT_MAX_TERMS];
+        for (int k = 0; k < K; k++) tx[k] = xx[k] = 0.0;
+        for (size_t q = 0; q < blocks; q++) {
+            if ((int)rec[q].terms != K) return FRACTION_TERMS;
+            tt += rec[q].tt;
+            for (int k = 0; k < K; k++) { tx[k] += rec[q].tx[k]; xx[k] += rec[q].xx[k * (k + 1) / 2 + k]; }
+        }
+        if (!isfinite(tt)) return FRACTION_NONFINITE;
+        for (int k = 0; k < K; k++) if (!isfinite(tx[k]) || !isfinite(xx[k])) return FRACTION_NONFINITE;
+        if (!(tt > 0.0)) continue;
+        int best = -1;
+        double best_score = 0.0;
+        for (int k = 0; k < K; k++) {
+            if (!(xx[k] > 0.0)) continue;
+            const double score = tx[k] / sqrt(xx[k]);
+            if (best < 0 || score > best_score) { best = k; best_score = score; }
+        }
+        if (best >= 0) all[(size_t)f] = best - (steps - 1);
+    }
+    *fit = -1;
+    memcpy(step, all.data(), all.size() * sizeof(int));
+    return FRACTION_OK;
 }
 
 /* ---- the Gram of a port list (include/gdg.h, GRAM): the list, the packed index, and the picks from its records (gdg_blend_pick_from_gram) ---- */

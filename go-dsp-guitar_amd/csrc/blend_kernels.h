@@ -198,3 +198,173 @@ hipError_t gdg_launch_blend_history_save(const double *d_rows, size_t row_stride
     else blend_history_save_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_history);
     return hipGetLastError();
 }
+
+/*
+ * Filtered terms (include/gdg.h, FILTERS: x_k[i] = h_k[0] x[c_k][i - d_k], then + h_k[t] x[c_k][i - d_k - t] in ascending t; DESIGN.md
+ * 4.12f).  The grid and the tiles of blend_delayed_kernel, the table through scalar loads -- now with tap_first and the taps --, the same
+ * 16-byte store.  What is new is arithmetic: up to 32 terms x 64 taps per output sample, so a row sample is fetched from global memory once
+ * per term and tile, not once per tap:
+ *   - a term's WINDOW -- the tile's samples i - d_k and BLEND_F_HALO = 64 samples in front of them, of which the T_k - 1 nearest are read --
+ *     is staged in LDS by 8-byte loads, every lane BLEND_F_ROUNDS of them; a slot nothing fills holds +0.0, which is also what lies in front
+ *     of a job without a history.  The window's slot m is sample tile - d_k - 64 + m of the row.
+ *   - two windows: while the lanes run term k's taps out of one, the loads of term k + 1 are in flight in registers and go into the other
+ *     behind the arithmetic; one barrier per term.
+ *   - a 16-byte lane owns the outputs l, l + 1 (l even) and slides over the window in aligned pairs A_e = slots (64 + l - e, 65 + l - e), e
+ *     even: tap t reads slot 64 + l - t for the first output and 65 + l - t for the second, so an even tap takes A_t and an odd tap the halves
+ *     A_{t+1}.y and A_{t-1}.x -- one 16-byte LDS read per two taps, lanes 16 bytes apart.  Each output's taps stay in ascending order.
+ *   - a term without taps skips the window: the plain delayed load of blend_delayed_kernel, held in registers over the barrier.
+ * Whether a slot can lie in front of the launch is decided per tile as before: a term reaches at most GDG_BLEND_MAX_DELAY samples back, so a
+ * tile that starts at or behind it runs the path without the compare.  An address is formed only behind the compare that chose its side:
+ * rows are read inside [0, samples), the history inside its run (slot m >= 65 - T_k lies at most d_k + T_k - 1 <= 4096 samples back).
+ * No lane leaves before the last barrier; a lane past the width fetches its share of the windows and stores nothing.
+ * LDS: 2 windows x (tile + 64) doubles -- 9216 bytes with 16-byte lanes (tile 512), 5120 with 8-byte lanes (tile 256).  No scratch, no atomics.
+ */
+#define BLEND_F_HALO 64
+static_assert(BLEND_F_HALO >= GDG_BLEND_MAX_TAPS && BLEND_F_HALO % 2 == 0, "the halo holds the taps behind the first and keeps pairs aligned");
+
+template <bool VEC> struct blend_filtered_shape {
+    static constexpr int PER = VEC ? 2 : 1, TILE = BLEND_T * PER, WIN = TILE + BLEND_F_HALO, ROUNDS = (WIN + BLEND_T - 1) / BLEND_T;
+};
+
+/* this lane's share of term (c, d, T)'s window over the tile at `tile`, T >= 1: slot r * BLEND_T + threadIdx.x in x[r] */
+template <bool VEC, bool HIST>
+__device__ __forceinline__ void blend_filtered_fetch(const double *rows, size_t row_stride, size_t samples, const double *history, size_t hist_stride, int c, int d,
+                                                     int T, size_t tile, double (&x)[blend_filtered_shape<VEC>::ROUNDS]) {
+    typedef blend_filtered_shape<VEC> S;
+#pragma unroll
+    for (int r = 0; r < S::ROUNDS; r++) {
+        const int m = r * BLEND_T + (int)threadIdx.x;
+        x[r] = 0.0;
+        if (m >= S::WIN || m < BLEND_F_HALO + 1 - T) continue;
+        const size_t to = tile + (size_t)m, back = (size_t)d + BLEND_F_HALO;        /* the slot is sample to - back */
+        if (!HIST || to >= back) {
+            if (to - back < samples) x[r] = rows[(size_t)c * row_stride + (to - back)];
+        } else if (history) {
+            x[r] = history[(size_t)c * hist_stride + ((size_t)GDG_BLEND_MAX_DELAY + to - back)];
+        }
+    }
+}
+
+template <bool VEC, bool HIST>
+__device__ __forceinline__ void blend_filtered_tile(const double *rows, size_t row_stride, size_t samples, const int *__restrict__ channel,
+                                                    const double *__restrict__ weight, const int *__restrict__ delay, const int *__restrict__ tap_first,
+                                                    const double *__restrict__ tap, const double *history, size_t hist_stride, int k0, int k1, size_t tile,
+                                                    double *dst, double (*win)[blend_filtered_shape<VEC>::WIN]) {
+    typedef blend_filtered_shape<VEC> S;
+    const int l = (int)threadIdx.x * S::PER;
+    const size_t at = tile + (size_t)l;
+    const bool live = at < samples, pair = VEC && at + 1 < samples;
+    double x[S::ROUNDS];
+    /* what term k needs from memory, into x: its window's share, or -- without taps -- this lane's own samples */
+    auto fetch = [&](int k) {
+        const int T = tap_first[k + 1] - tap_first[k];
+        if (T > 0) { blend_filtered_fetch<VEC, HIST>(rows, row_stride, samples, history, hist_stride, channel[k], delay[k], T, tile, x); return; }
+        x[0] = x[1] = 0.0;
+        if (pair) {
+            const v2d p = blend_delayed_load<v2d, HIST>::at(rows, row_stride, history, hist_stride, channel[k], at, delay[k]);
+            x[0] = p.x;
+            x[1] = p.y;
+        } else if (live) {
+            x[0] = blend_delayed_load<double, HIST>::at(rows, row_stride, history, hist_stride, channel[k], at, delay[k]);
+        }
+    };
+    auto stage = [&](int k, int buf) {
+        if (tap_first[k + 1] == tap_first[k]) return;
+#pragma unroll
+        for (int r = 0; r < S::ROUNDS; r++) {
+            const int m = r * BLEND_T + (int)threadIdx.x;
+            if (m < S::WIN) win[buf][m] = x[r];
+        }
+    };
+    fetch(k0);
+    stage(k0, 0);
+    __syncthreads();
+    double s0 = 0.0, s1 = 0.0;
+    int cur = 0;
+    for (int k = k0; k < k1; k++, cur ^= 1) {
+        const int T = tap_first[k + 1] - tap_first[k];
+        double f0 = x[0], f1 = x[1];                                        /* a term without taps: its samples, before the next fetch takes x */
+        if (k + 1 < k1) fetch(k + 1);                                       /* in flight under this term's taps */
+        if (T > 0) {
+            const double *__restrict__ h = tap + tap_first[k];
+            const double *w = &win[cur][BLEND_F_HALO + l];
+            if (VEC) {
+                v2d a = *reinterpret_cast<const v2d *>(w);                   /* A_0 */
+                f0 = gdg_blend_mul(h[0], a.x);
+                f1 = gdg_blend_mul(h[0], a.y);
+                for (int t = 1; t < T; t += 2) {
+                    const v2d b = *reinterpret_cast<const v2d *>(w - t - 1);  /* A_{t+1}; its first slot is 63 + l - t >= 64 - T >= 0 */
+                    f0 = gdg_blend_add(f0, gdg_blend_mul(h[t], b.y));
+                    f1 = gdg_blend_add(f1, gdg_blend_mul(h[t], a.x));
+                    if (t + 1 < T) {
+                        f0 = gdg_blend_add(f0, gdg_blend_mul(h[t + 1], b.x));
+                        f1 = gdg_blend_add(f1, gdg_blend_mul(h[t + 1], b.y));
+                    }
+                    a = b;
+                }
+            } else {
+                f0 = gdg_blend_mul(h[0], w[0]);
+                for (int t = 1; t < T; t++) f0 = gdg_blend_add(f0, gdg_blend_mul(h[t], w[-t]));
+                f1 = 0.0;
+            }
+        }
+        const double wk = weight[k];
+        if (k == k0) {
+            s0 = gdg_blend_mul(wk, f0);
+            s1 = gdg_blend_mul(wk, f1);
+        } else {
+            s0 = gdg_blend_add(s0, gdg_blend_mul(wk, f0));
+            s1 = gdg_blend_add(s1, gdg_blend_mul(wk, f1));
+        }
+        if (k + 1 < k1) stage(k + 1, cur ^ 1);
+        __syncthreads();                                                     /* every lane is done with win[cur], and win[cur ^ 1] is whole */
+    }
+    if (pair) {
+        const v2d s = { s0, s1 };
+        *reinterpret_cast<v2d *>(dst + at) = s;
+    } else if (live) {
+        dst[at] = s0;
+    }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(BLEND_T)
+blend_filtered_kernel(const double *rows, size_t row_stride, size_t samples, const int *__restrict__ first, const int *__restrict__ channel,
+                      const double *__restrict__ weight, const int *__restrict__ delay, const int *__restrict__ tap_first, const double *__restrict__ tap,
+                      const double *history, size_t hist_stride, double *out, size_t out_stride) {
+    typedef blend_filtered_shape<VEC> S;
+    __shared__ __attribute__((aligned(16))) double win[2][S::WIN];
+    const int k0 = first[blockIdx.y], k1 = first[blockIdx.y + 1];
+    double *dst = out + (size_t)blockIdx.y * out_stride;
+    const size_t tile = (size_t)blockIdx.x * S::TILE;
+    if (tile >= (size_t)GDG_BLEND_MAX_DELAY)                                 /* uniform: no slot of this tile's windows lies in front of the launch */
+        blend_filtered_tile<VEC, false>(rows, row_stride, samples, channel, weight, delay, tap_first, tap, history, hist_stride, k0, k1, tile, dst, win);
+    else
+        blend_filtered_tile<VEC, true>(rows, row_stride, samples, channel, weight, delay, tap_first, tap, history, hist_stride, k0, k1, tile, dst, win);
+}
+
+/* as gdg_launch_blend_rows_delayed, with d_tap_first[d_first[n_blends] + 1] and the taps d_tap (8-byte aligned); every term's d + max(T, 1) - 1
+ * is at most GDG_BLEND_MAX_DELAY and every T at most GDG_BLEND_MAX_TAPS (checked by the caller).  A table without taps -- d_tap_first null --
+ * is the delayed launch, and without delays as well the plain one: the same kernels as before filters existed. */
+hipError_t gdg_launch_blend_rows_filtered(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
+                                          const double *d_weight, const int *d_delay, const int *d_tap_first, const double *d_tap, const double *d_history,
+                                          size_t hist_stride, double *d_out, size_t out_stride, hipStream_t s) {
+    if (!d_tap_first) {
+        if (!d_delay) return gdg_launch_blend_rows(d_rows, row_stride, samples, n_blends, d_first, d_channel, d_weight, d_out, out_stride, s);
+        return gdg_launch_blend_rows_delayed(d_rows, row_stride, samples, n_blends, d_first, d_channel, d_weight, d_delay, d_history, hist_stride, d_out, out_stride, s);
+    }
+    if (n_blends == 0 || samples == 0) return hipSuccess;
+    if (!d_rows || !d_out || !d_first || !d_channel || !d_weight || !d_delay || !d_tap || row_stride < samples || out_stride < samples || n_blends > 65535u ||
+        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_weight & 7) || ((uintptr_t)d_tap & 7) || ((uintptr_t)d_first & 3) ||
+        ((uintptr_t)d_channel & 3) || ((uintptr_t)d_delay & 3) || ((uintptr_t)d_tap_first & 3) ||
+        (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY)))
+        return hipErrorInvalidValue;
+    const bool vec = !((uintptr_t)d_rows & 15) && !(row_stride & 1) && !((uintptr_t)d_out & 15) && !(out_stride & 1) &&
+                     (!d_history || (!((uintptr_t)d_history & 15) && !(hist_stride & 1)));
+    const size_t lanes = vec ? (samples + 1) / 2 : samples, tiles = (lanes + BLEND_T - 1) / BLEND_T;
+    if (tiles > 0x7fffffffu) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)tiles, n_blends);
+    if (vec) blend_filtered_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_tap_first, d_tap, d_history, hist_stride, d_out, out_stride);
+    else blend_filtered_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_tap_first, d_tap, d_history, hist_stride, d_out, out_stride);
+    return hipGetLastError();
+}

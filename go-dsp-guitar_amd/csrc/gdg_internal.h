@@ -366,6 +366,11 @@ hipError_t gdg_launch_blend_rows(const double *d_rows, size_t row_stride, size_t
 hipError_t gdg_launch_blend_rows_delayed(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
                                          const double *d_weight, const int *d_delay, const double *d_history, size_t hist_stride, double *d_out, size_t out_stride,
                                          hipStream_t s);
+/* ... and with a short FIR per term (include/gdg.h, FILTERS): term k's taps are d_tap[d_tap_first[k] .. d_tap_first[k + 1]), at most GDG_BLEND_MAX_TAPS,
+ * and d_k + max(T_k, 1) - 1 <= GDG_BLEND_MAX_DELAY (checked by the caller).  d_tap_first null: the delayed launch; d_delay null as well: the plain one. */
+hipError_t gdg_launch_blend_rows_filtered(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
+                                          const double *d_weight, const int *d_delay, const int *d_tap_first, const double *d_tap, const double *d_history,
+                                          size_t hist_stride, double *d_out, size_t out_stride, hipStream_t s);
 /* the last GDG_BLEND_MAX_DELAY of `samples` samples (samples >= GDG_BLEND_MAX_DELAY) of rows 0 .. n_rows - 1 into d_history[n_rows][GDG_BLEND_MAX_DELAY] */
 hipError_t gdg_launch_blend_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
 /* the blend fit's records (include/gdg.h, FIT; io.hip, fit_kernels.h): per fit and block of `block` samples (the last of a row may be short)

@@ -2168,6 +2168,243 @@ func (this *Context) BlendRowsDelayedDevice(dRows unsafe.Pointer, rowStride int,
 		&first[0], &channel[0], &weight[0], (*C.int)(dp), (*C.double)(dHistory), C.size_t(histStride), (*C.double)(dOut), C.size_t(outStride)))
 }
 
+// BlendMaxTaps: the most taps of a blend's term (GDG_BLEND_MAX_TAPS).
+const BlendMaxTaps = 64
+
+// blendTaps: the taps of every term of blends in CSR form, in C memory with a spare entry each (the caller frees both); taps[b][k] belongs
+// to blends[b][k], an empty list is a term without taps.
+func blendTaps(blends [][]BlendTerm, taps [][][]float64) (unsafe.Pointer, unsafe.Pointer, error) {
+	if len(taps) != len(blends) {
+		return nil, nil, fmt.Errorf("gdg: taps for %d blends, %d blends", len(taps), len(blends))
+	}
+	terms := 0
+	total := 0
+	for b, list := range blends {
+		if len(taps[b]) != len(list) {
+			return nil, nil, fmt.Errorf("gdg: blend %d has %d terms and %d tap lists", b, len(list), len(taps[b]))
+		}
+		terms += len(list)
+		for _, h := range taps[b] {
+			total += len(h)
+		}
+	}
+	fp := C.calloc(C.size_t(terms+2), 4)
+	if fp == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	tp := C.calloc(C.size_t(total+1), 8)
+	if tp == nil {
+		C.free(fp)
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	first := (*[1 << 28]C.int)(fp)[: terms+1 : terms+1]
+	dst := (*[1 << 28]C.double)(tp)[:total:total]
+	k := 0
+	at := 0
+	for _, list := range taps {
+		for _, h := range list {
+			for _, v := range h {
+				dst[at] = C.double(v)
+				at++
+			}
+			k++
+			first[k] = C.int(at)
+		}
+	}
+	return fp, tp, nil
+}
+
+// BatchSetBlendsFiltered: BatchSetBlendsDelayed with a short FIR per term (gdg_batch_set_blends_filtered): term k of blend b reads its row
+// through taps[b][k] -- up to BlendMaxTaps finite values, tap t on the sample delay[b][k] + t back -- and a term with an empty list is a
+// delayed term.  A term reaches delay + max(taps, 1) - 1 samples back, BlendMaxDelay at the most.  nil taps: BatchSetBlendsDelayed.
+func (this *Context) BatchSetBlendsFiltered(blends [][]BlendTerm, delay [][]int, taps [][][]float64, gain []float64) error {
+	n := len(blends)
+	if n == 0 || taps == nil {
+		return this.BatchSetBlendsDelayed(blends, delay, gain)
+	}
+	if len(gain) != 0 && len(gain) != n {
+		return fmt.Errorf("gdg: %d gains for %d blends", len(gain), n)
+	}
+	if delay == nil {
+		delay = make([][]int, n)
+		for b := range delay {
+			delay[b] = make([]int, len(blends[b]))
+		}
+	}
+	dp, e := blendDelays(blends, delay)
+	if e != nil {
+		return e
+	}
+	defer C.free(dp)
+	fp, tp, e2 := blendTaps(blends, taps)
+	if e2 != nil {
+		return e2
+	}
+	defer C.free(fp)
+	defer C.free(tp)
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return err
+	}
+	defer release()
+	if len(gain) == 0 {
+		return this.err(C.gdg_batch_set_blends_filtered(this.ctx, C.int(n), &first[0], &channel[0], &weight[0], (*C.int)(dp), (*C.int)(fp), (*C.double)(tp), nil))
+	}
+	g := (*[1 << 28]C.double)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(C.double(0)))))
+	if g == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(g))
+	for i, v := range gain {
+		g[i] = C.double(v)
+	}
+	return this.err(C.gdg_batch_set_blends_filtered(this.ctx, C.int(n), &first[0], &channel[0], &weight[0], (*C.int)(dp), (*C.int)(fp), (*C.double)(tp), &g[0]))
+}
+
+// BatchBlendMaxReach: how far back the blends in force read (gdg_batch_blend_max_reach): the largest delay + max(taps, 1) - 1; 0: stateless.
+func (this *Context) BatchBlendMaxReach() int {
+	return int(C.gdg_batch_blend_max_reach(this.ctx))
+}
+
+// BlendRowsFiltered: the filtered blends' sums over any rows of equal length (gdg_blend_rows_filtered); history as BlendRowsDelayed takes
+// it.  result[blend][sample].
+func (this *Context) BlendRowsFiltered(rows [][]float64, blends [][]BlendTerm, delay [][]int, taps [][][]float64, history [][]float64) ([][]float64, error) {
+	n := len(rows)
+	nb := len(blends)
+	if n == 0 {
+		return nil, fmt.Errorf("gdg: no rows")
+	}
+	if taps == nil {
+		return this.BlendRowsDelayed(rows, blends, delay, history)
+	}
+	if history != nil && len(history) != n {
+		return nil, fmt.Errorf("gdg: %d histories for %d rows", len(history), n)
+	}
+	samples := len(rows[0])
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n+nb+1), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i := 0; i < n+nb; i++ {
+		if i < n && len(rows[i]) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(rows[i]), samples)
+		}
+		p := C.calloc(C.size_t(samples+1), 8)
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		if i < n {
+			copy((*[1 << 37]float64)(p)[:samples:samples], rows[i])
+		}
+		rp[i] = (*C.double)(p)
+	}
+	hp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n+1), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if hp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(hp))
+	for i := range history {
+		if len(history[i]) != BlendMaxDelay {
+			return nil, fmt.Errorf("gdg: the history of row %d has %d samples; %d", i, len(history[i]), BlendMaxDelay)
+		}
+		p := C.calloc(C.size_t(BlendMaxDelay), 8)
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:BlendMaxDelay:BlendMaxDelay], history[i])
+		hp[i] = (*C.double)(p)
+	}
+	if delay == nil {
+		delay = make([][]int, nb)
+		for b := range delay {
+			delay[b] = make([]int, len(blends[b]))
+		}
+	}
+	dp, e := blendDelays(blends, delay)
+	if e != nil {
+		return nil, e
+	}
+	owned = append(owned, dp)
+	fp, tp, e2 := blendTaps(blends, taps)
+	if e2 != nil {
+		return nil, e2
+	}
+	owned = append(owned, fp, tp)
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return nil, err
+	}
+	defer release()
+	var rc C.int
+	if history == nil {
+		rc = C.gdg_blend_rows_filtered(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(nb), &first[0], &channel[0], &weight[0], (*C.int)(dp), (*C.int)(fp), (*C.double)(tp), nil, &rp[n])
+	} else {
+		rc = C.gdg_blend_rows_filtered(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(nb), &first[0], &channel[0], &weight[0], (*C.int)(dp), (*C.int)(fp), (*C.double)(tp), &hp[0], &rp[n])
+	}
+	if e := this.err(rc); e != nil {
+		return nil, e
+	}
+	out := make([][]float64, nb)
+	for b := range out {
+		out[b] = make([]float64, samples)
+		copy(out[b], (*[1 << 37]float64)(unsafe.Pointer(rp[n+b]))[:samples:samples])
+	}
+	return out, nil
+}
+
+// BlendRowsFilteredDevice: the same on device memory (gdg_blend_rows_filtered_device), laid out as BlendRowsDelayedDevice takes it; returns
+// when the sums are written.
+func (this *Context) BlendRowsFilteredDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, blends [][]BlendTerm, delay [][]int, taps [][][]float64, dHistory unsafe.Pointer, histStride int, dOut unsafe.Pointer, outStride int) error {
+	dp, e := blendDelays(blends, delay)
+	if e != nil {
+		return e
+	}
+	defer C.free(dp)
+	fp, tp, e2 := blendTaps(blends, taps)
+	if e2 != nil {
+		return e2
+	}
+	defer C.free(fp)
+	defer C.free(tp)
+	first, channel, weight, release, err := blendTable(blends)
+	if err != nil {
+		return err
+	}
+	defer release()
+	return this.err(C.gdg_blend_rows_filtered_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(len(blends)),
+		&first[0], &channel[0], &weight[0], (*C.int)(dp), (*C.int)(fp), (*C.double)(tp), (*C.double)(dHistory), C.size_t(histStride), (*C.double)(dOut), C.size_t(outStride)))
+}
+
+// BlendFractionTaps: nTaps windowed-sinc taps (even, 2 to BlendMaxTaps) that delay by nTaps/2 - 1 + fraction samples, 0 <= fraction < 1,
+// normalised to sum 1 (gdg_blend_fraction_taps); fraction 0 is the exact unit impulse.  Host arithmetic: no context and no device.
+func BlendFractionTaps(nTaps int, fraction float64) ([]float64, error) {
+	if nTaps < 2 || nTaps > BlendMaxTaps {
+		return nil, fmt.Errorf("gdg: %d taps; an even count from 2 to %d", nTaps, BlendMaxTaps)
+	}
+	res := (*[1 << 28]C.double)(C.calloc(C.size_t(nTaps+1), 8))
+	if res == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(res))
+	if rc := C.gdg_blend_fraction_taps(C.int(nTaps), C.double(fraction), &res[0]); rc != 0 {
+		return nil, fmt.Errorf("gdg: gdg_blend_fraction_taps: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	taps := make([]float64, nTaps)
+	for t := range taps {
+		taps[t] = float64(res[t])
+	}
+	return taps, nil
+}
+
 // BlendDelaysFromAlign: delays and signs of the blends' terms from alignment records (gdg_blend_delays_from_align): records[port][block] as
 // BatchAlign hands them out, measured with the reference list ref; a term's Channel names a port.  A port's lag is the lower median of Lag
 // over its blocks with a normalised coefficient of at least minCoeff, its sign that of the sum of their Corr; delay[b][k] = the blend's
@@ -2451,6 +2688,45 @@ func BlendWeightsFromFit(records [][]BlockFit, ridge float64) ([][]float64, []fl
 		residual[f] = float64(res[fits*8+f])
 	}
 	return weights, residual, nil
+}
+
+// BlendFractionsFromFit: the fraction of a delay per fit from its records (gdg_blend_fractions_from_fit): records[fit][block] as BatchFit
+// hands them out, every fit with the 2*steps - 1 candidates of one channel, term k at (k - (steps - 1)) / steps samples.  The candidate
+// with the largest Tx[k] / sqrt(Xx[k][k]) over all blocks wins, the earlier on a tie; result[fit] is its k - (steps - 1), 0 for a silent
+// target or no admissible candidate.  Host arithmetic: no context and no device.
+func BlendFractionsFromFit(records [][]BlockFit, steps int) ([]int, error) {
+	fits := len(records)
+	if fits == 0 {
+		return []int{}, nil
+	}
+	blocks := len(records[0])
+	for f, row := range records {
+		if len(row) != blocks || blocks == 0 {
+			return nil, fmt.Errorf("gdg: fit %d has %d records, fit 0 has %d (at least 1)", f, len(row), blocks)
+		}
+	}
+	rec := C.calloc(C.size_t(fits*blocks+1), 368)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	dst := (*[1 << 22]BlockFit)(rec)[: fits*blocks : fits*blocks]
+	for f, row := range records {
+		copy(dst[f*blocks:(f+1)*blocks], row)
+	}
+	res := (*[1 << 28]C.int)(C.calloc(C.size_t(fits+1), 4))
+	if res == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(res))
+	if rc := C.gdg_blend_fractions_from_fit((*C.gdg_block_fit)(rec), C.int(fits), C.size_t(blocks), C.int(steps), &res[0]); rc != 0 {
+		return nil, fmt.Errorf("gdg: gdg_blend_fractions_from_fit: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	step := make([]int, fits)
+	for f := range step {
+		step[f] = int(res[f])
+	}
+	return step, nil
 }
 
 // GramIndex: the place of entry (i, j) in a Gram record -- the lower triangle by rows, the fit's Xx layout -- for either order of i and j.

@@ -58,6 +58,7 @@ def lib():
             "gdgh_engine_batch_gram_ports": (i32, [vp]),
             "gdgh_engine_last_batch_gram": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
+            "gdgh_engine_set_batch_blends_filtered": (cs, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
@@ -300,8 +301,9 @@ class Engine:
         _err(lib().gdgh_engine_set_batch_trim(self._h, g.ctypes.data, n, float(g[n]), float(g[n + 1]), float(g[n + 2])))
 
     def _set_blends(self, blends, blend_gain=None):
-        """Engine::SetBatchBlends, from the `blends` / `blend_gain` arguments of the batch calls: a list of lists of (job channel, weight) or
-        (job channel, weight, delay in samples) and one output gain per blend (None: all 1); None or an empty list: off.  Returns the number
+        """Engine::SetBatchBlends, from the `blends` / `blend_gain` arguments of the batch calls: a list of lists of (job channel, weight),
+        (job channel, weight, delay in samples) or (job channel, weight, delay, taps) -- the term's FIR, up to 64 taps -- and one output
+        gain per blend (None: all 1); None or an empty list: off.  Returns the number
         of blends in force: the calls' outputs and records then have N + 3 + B ports.  Refused on an engine of more than one shard."""
         blends = [] if blends is None else [list(b) for b in blends]
         if not blends:
@@ -315,6 +317,15 @@ class Engine:
         g = None if blend_gain is None else np.ascontiguousarray(blend_gain, dtype=np.float64).reshape(-1)
         if g is not None and g.size != len(blends):
             raise HostError("blend_gain: %d gains for %d blends" % (g.size, len(blends)))
+        if any(len(t) > 3 for t in terms):
+            delay = np.array([int(t[2]) if len(t) > 2 else 0 for t in terms] + [0], dtype=np.int32)
+            taps =[np.asarray(t[3], dtype=np.float64).reshape(-1) if len(t) > 3 and t[3] is not None else np.zeros(0) for t in terms]
+            tap_first = np.zeros(len(terms) + 1, dtype=np.int32)
+            tap_first[1:] = np.cumsum([h.size for h in taps], dtype=np.int64)
+            tap = np.ascontiguousarray(np.concatenate(taps + [np.zeros(1)]), dtype=np.float64)
+            _err(lib().gdgh_engine_set_batch_blends_filtered(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data, delay.ctypes.data,
+                                                             tap_first.ctypes.data, tap.ctypes.data, None if g is None else g.ctypes.data))
+            return int(lib().gdgh_engine_batch_blends(self._h))
         if any(len(t) > 2 for t in terms):
             delay = np.array([int(t[2]) if len(t) > 2 else 0 for t in terms] + [0], dtype=np.int32)
             _err(lib().gdgh_engine_set_batch_blends_delayed(self._h, len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data, delay.ctypes.data,
@@ -437,15 +448,27 @@ class Engine:
         outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=blend, **rest)
         return outs, weights, float(residual[0])
 
-    def render_aligned(self, blends, max_lag, min_coeff, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
+    def render_aligned(self, blends, max_lag, min_coeff, inputs, target_rate, out_format, window=16, sample_rate=None, fraction_steps=0, fraction_taps=32, **kw):
         """Two passes over one job: the terms of every blend are lined up before they are summed.  save_state; pass 1 renders with every
         output skipped and the alignment records on, every term's channel measured against the channel of its blend's first term (a channel
         that two blends measure against different first terms is refused); the planner (blend_delays_from_align) turns the records into
         one delay and one sign per term; load_state; pass 2 renders with the delayed blends, the weights multiplied by the signs.  blends:
         lists of (job channel, weight).  Returns (outs, delays, signs): the N + 3 + B output data sections, and per blend the list of delays
-        and of signs used.  Pass 1's records stay in aligned_records.  kw: batch_run's other arguments (an align in kw is replaced)."""
+        and of signs used.  Pass 1's records stay in aligned_records.  kw: batch_run's other arguments (an align in kw is replaced).
+        fraction_steps = Q > 0 (1 to 4) lines the terms up to 1/Q of a sample: a pass between the planner and the render gives every
+        measured channel 2Q - 1 one-term filtered blend ports around its whole-sample plan -- candidate `step` of -(Q - 1) .. Q - 1 delays by
+        n samples and fraction_taps windowed-sinc taps for f (blend_fraction_taps), n + f = d + 1 + step / Q -- and its blend's first term
+        one port delayed by the common latency, d + fraction_taps / 2; one fit per measured channel against that port, every output
+        skipped; blend_fractions_from_fit picks the step, and the last pass renders with it.  Every term of such a blend ends
+        fraction_taps / 2 samples later than the whole-sample plan put it -- a term without taps gets d + fraction_taps / 2 --, so the
+        blend port LAGS the chain ports by fraction_taps / 2 samples.  A plan that reaches further back than 4096 samples is a HostError
+        that names the blend.  Returns (outs, delays, signs, fractions) in this mode: fractions[b][k] = step / Q of term k, 0.0 for a term
+        that was not measured; the pass's records stay in fraction_records.  fraction_steps = 0: exactly the two passes above."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
+        Q, T = int(fraction_steps), int(fraction_taps)
+        if Q < 0 or Q > 4 or (Q > 0 and (T < 2 or T > pkg.BLEND_MAX_TAPS or T % 2)):
+            raise HostError("render_aligned: fraction_steps = %d (0 to 4), fraction_taps = %d (even, 2 to %d)" % (Q, T, pkg.BLEND_MAX_TAPS))
         blends = [[(int(t[0]), float(t[1])) for t in b] for b in blends]
         n3 = self.n_channels + 3
         ref = [-1] * n3
@@ -468,9 +491,57 @@ class Engine:
         self.aligned_records = self.last_align
         delays, signs = pkg.blend_delays_from_align(self.aligned_records, ref, blends, min_coeff)
         self.load_state(blob, rate)
+        if Q > 0:
+            return self._render_fractions(pkg, blends, delays, signs, ref, Q, T, blob, rate, inputs, target_rate, out_format, window, rest)
         lined = [[(c, w * signs[b][k], delays[b][k]) for k, (c, w) in enumerate(terms)] for b, terms in enumerate(blends)]
         outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=lined, **rest)
         return outs, delays, signs
+
+    def _render_fractions(self, pkg, blends, delays, signs, ref, Q, T, blob, rate, inputs, target_rate, out_format, window, rest):
+        """render_aligned's pass between the planner and the render, and the render: see there"""
+        n3 = self.n_channels + 3
+
+        def filtered(c, w, d, step):                          # n + f = d + 1 + step / Q, in whole Q-ths
+            num = (d + 1) * Q + step
+            return (c, w, num // Q, pkg.blend_fraction_taps(T, (num % Q) / float(Q)))
+
+        def reach_ok(b, term):
+            d, taps = term[2], term[3] if len(term) > 3 else ()
+            if d + max(len(taps), 1) - 1 > pkg.BLEND_MAX_DELAY:
+                raise HostError("render_aligned: blend %d: channel %d would be read %d samples back with %d taps; a term reaches at most %d samples"
+                                % (b, term[0], d, len(taps), pkg.BLEND_MAX_DELAY))
+            return term
+
+        # the ports of the pass: per root one, per measured channel 2Q - 1, planned in the first blend that holds the channel
+        ports, root_port, fits, measured = [], {}, [], []
+        for b, terms in enumerate(blends):
+            root = terms[0][0]
+            for k, (c, _) in enumerate(terms):
+                if c == root or c in measured:
+                    continue
+                if (b, root) not in root_port:
+                    root_port[(b, root)] = n3 + len(ports)
+                    ports.append([reach_ok(b, (root, 1.0, delays[b][0] + T // 2))])
+                cand = []
+                for step in range(-(Q - 1), Q):
+                    cand.append(n3 + len(ports))
+                    ports.append([reach_ok(b, filtered(c, float(signs[b][k]), delays[b][k], step))])
+                fits.append((root_port[(b, root)], cand))
+                measured.append(c)
+        steps = {}
+        if fits:
+            self.batch_run(inputs, target_rate, out_format, window=window, blends=ports, fits=fits, skip_outputs=True,
+                           **{k: v for k, v in rest.items() if k not in ("fits", "blend_gain")})
+            self.fraction_records = self.last_fit
+            steps = dict(zip(measured, pkg.blend_fractions_from_fit(self.fraction_records, Q)))
+            self.load_state(blob, rate)
+        lined, fractions = [], []
+        for b, terms in enumerate(blends):
+            lined.append([reach_ok(b, filtered(c, w * signs[b][k], delays[b][k], steps[c]) if c in steps and c != terms[0][0] else (c, w * signs[b][k], delays[b][k] + T // 2))
+                          for k, (c, w) in enumerate(terms)])
+            fractions.append([steps[c] / float(Q) if c in steps and c != terms[0][0] else 0.0 for c, _ in terms])
+        outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=lined, **rest)
+        return outs, delays, signs, fractions
 
     def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
         """Two passes over one job: every output file is written with the gain that brings its true peak to target_dbtp (dBTP), capped at

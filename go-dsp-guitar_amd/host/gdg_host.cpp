@@ -971,17 +971,20 @@ int Engine::applyTrim(int shard, gdg_ctx *ctx) {
 }
 
 /* Engine::SetBatchBlends: validated whole before the list replaces the one in force (the library checks again when it is applied) */
-Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain, const std::vector<std::vector<int>> &delay) {
-    if (blends.empty()) { blendFirst_.clear(); blendChannel_.clear(); blendWeight_.clear(); blendGain_.clear(); blendDelay_.clear(); return ""; }
+Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain, const std::vector<std::vector<int>> &delay,
+                             const std::vector<std::vector<std::vector<double>>> &taps) {
+    if (blends.empty()) { blendFirst_.clear(); blendChannel_.clear(); blendWeight_.clear(); blendGain_.clear(); blendDelay_.clear(); blendTapFirst_.clear(); blendTap_.clear(); return ""; }
     if (shards() > 1)
         return format("SetBatchBlends: the engine has %d shards: every shard's context holds its own channels only, so a blend cannot read a term on another "
                       "device, and the library's shard calls refuse blends; blends need a one-shard engine", shards());
     if (blends.size() > GDG_BLEND_MAX_BLENDS) return format("SetBatchBlends: %zu blends; at most %d", blends.size(), GDG_BLEND_MAX_BLENDS);
     if (!gain.empty() && gain.size() != blends.size()) return format("SetBatchBlends: %zu gains for %zu blends (none: every gain 1)", gain.size(), blends.size());
     if (!delay.empty() && delay.size() != blends.size()) return format("SetBatchBlends: delays for %zu blends, %zu blends (none: every delay 0)", delay.size(), blends.size());
-    std::vector<int> first(1, 0), channel, delays;
-    std::vector<double> weight;
+    if (!taps.empty() && taps.size() != blends.size()) return format("SetBatchBlends: taps for %zu blends, %zu blends (none: no term has taps)", taps.size(), blends.size());
+    std::vector<int> first(1, 0), channel, delays, tapFirst(1, 0);
+    std::vector<double> weight, tap;
     for (size_t b = 0; b < blends.size(); b++) {
+        if (!taps.empty() && taps[b].size() != blends[b].size()) return format("SetBatchBlends: blend %zu has %zu terms and %zu tap lists", b, blends[b].size(), taps[b].size());
         if (!delay.empty() && delay[b].size() != blends[b].size()) return format("SetBatchBlends: blend %zu has %zu terms and %zu delays", b, blends[b].size(), delay[b].size());
         if (blends[b].empty() || blends[b].size() > GDG_BLEND_MAX_TERMS) return format("SetBatchBlends: blend %zu has %zu terms; 1 to %d", b, blends[b].size(), GDG_BLEND_MAX_TERMS);
         for (size_t k = 0; k < blends[b].size(); k++) {
@@ -990,6 +993,16 @@ Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double
             if (!std::isfinite(blends[b][k].second)) return format("SetBatchBlends: blend %zu, term %zu: the weight is not finite", b, k);
             if (!delay.empty() && (delay[b][k] < 0 || delay[b][k] > GDG_BLEND_MAX_DELAY))
                 return format("SetBatchBlends: blend %zu, term %zu: delay = %d; 0 to %d samples", b, k, delay[b][k], GDG_BLEND_MAX_DELAY);
+            if (!taps.empty()) {
+                const std::vector<double> &h = taps[b][k];
+                const int d = delay.empty() ? 0 : delay[b][k];
+                if (h.size() > GDG_BLEND_MAX_TAPS) return format("SetBatchBlends: blend %zu, term %zu has %zu taps; 0 to %d", b, k, h.size(), GDG_BLEND_MAX_TAPS);
+                for (size_t t = 0; t < h.size(); t++) if (!std::isfinite(h[t])) return format("SetBatchBlends: blend %zu, term %zu: tap %zu is not finite", b, k, t);
+                if (d + (int)std::max<size_t>(h.size(), 1) - 1 > GDG_BLEND_MAX_DELAY)
+                    return format("SetBatchBlends: blend %zu, term %zu: a delay of %d samples and %zu taps reach further back than %d samples", b, k, d, h.size(), GDG_BLEND_MAX_DELAY);
+                tap.insert(tap.end(), h.begin(), h.end());
+                tapFirst.push_back((int)tap.size());
+            }
             channel.push_back(blends[b][k].first);
             weight.push_back(blends[b][k].second);
             if (!delay.empty()) delays.push_back(delay[b][k]);
@@ -1001,6 +1014,9 @@ Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double
     blendChannel_.swap(channel);
     blendWeight_.swap(weight);
     blendDelay_.swap(delays);
+    if (tap.empty()) tapFirst.clear();                   /* no tap anywhere: the delayed list */
+    blendTapFirst_.swap(tapFirst);
+    blendTap_.swap(tap);
     blendGain_ = gain.empty() ? std::vector<double>(blends.size(), 1.0) : gain;
     return "";
 }
@@ -1008,6 +1024,9 @@ Error Engine::SetBatchBlends(const std::vector<std::vector<std::pair<int, double
 /* one shard: job channel numbers are the context's; more shards: no blend is in force, and every context is told so */
 int Engine::applyBlends(gdg_ctx *ctx) {
     if (blendFirst_.empty()) return gdg_batch_set_blends(ctx, 0, nullptr, nullptr, nullptr, nullptr);
+    if (!blendTapFirst_.empty())
+        return gdg_batch_set_blends_filtered(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendDelay_.empty() ? nullptr : blendDelay_.data(),
+                                             blendTapFirst_.data(), blendTap_.data(), blendGain_.data());
     if (blendDelay_.empty()) return gdg_batch_set_blends(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendGain_.data());
     return gdg_batch_set_blends_delayed(ctx, BatchBlends(), blendFirst_.data(), blendChannel_.data(), blendWeight_.data(), blendDelay_.data(), blendGain_.data());
 }
@@ -1936,17 +1955,30 @@ const char *gdgh_engine_set_batch_trim(void *e, const double *chain_gain, int n,
 }
 /* the blends in gdg_batch_set_blends' CSR form, job channel numbers; n_blends == 0: off; gain == NULL: every gain 1.  A `first` that does
  * not start at 0 or descends is refused here: the lists below are cut by it */
-const char *gdgh_engine_set_batch_blends_delayed(void *e, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const double *gain) {
+const char *gdgh_engine_set_batch_blends_filtered(void *e, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const int *tap_first,
+                                                  const double *tap, const double *gain) {
     std::vector<std::vector<std::pair<int, double>>> blends;
     std::vector<std::vector<int>> delays;
+    std::vector<std::vector<std::vector<double>>> taps;
+    if (n_blends > 0 && tap_first && (!tap || !first || tap_first[0] != 0)) return ret("SetBatchBlends: tap_first (from 0 on) needs tap");
     if (n_blends < 0 || (n_blends > 0 && (!first || !channel || !weight || first[0] != 0))) return ret("SetBatchBlends: n_blends >= 0, and first (from 0 on), channel and weight");
     for (int b = 0; b < n_blends; b++) {
         if (first[b + 1] < first[b]) return ret(format("SetBatchBlends: blend %d: first descends from %d to %d", b, first[b], first[b + 1]));
         blends.emplace_back();
         for (int k = first[b]; k < first[b + 1]; k++) blends.back().emplace_back(channel[k], weight[k]);
         if (delay) delays.emplace_back(delay + first[b], delay + first[b + 1]);
+        if (tap_first) {
+            taps.emplace_back();
+            for (int k = first[b]; k < first[b + 1]; k++) {
+                if (tap_first[k + 1] < tap_first[k]) return ret(format("SetBatchBlends: blend %d, term %d: tap_first descends from %d to %d", b, k - first[b], tap_first[k], tap_first[k + 1]));
+                taps.back().emplace_back(tap + tap_first[k], tap + tap_first[k + 1]);
+            }
+        }
     }
-    return ret(((Engine *)e)->SetBatchBlends(blends, gain && n_blends > 0 ? std::vector<double>(gain, gain + n_blends) : std::vector<double>(), delays));
+    return ret(((Engine *)e)->SetBatchBlends(blends, gain && n_blends > 0 ? std::vector<double>(gain, gain + n_blends) : std::vector<double>(), delays, taps));
+}
+const char *gdgh_engine_set_batch_blends_delayed(void *e, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const double *gain) {
+    return gdgh_engine_set_batch_blends_filtered(e, n_blends, first, channel, weight, delay, nullptr, nullptr, gain);
 }
 const char *gdgh_engine_set_batch_blends(void *e, int n_blends, const int *first, const int *channel, const double *weight, const double *gain) {
     return gdgh_engine_set_batch_blends_delayed(e, n_blends, first, channel, weight, nullptr, gain);

@@ -293,7 +293,8 @@ public:
      * BatchRun of a one-shard engine with blends is the library's plain gdg_batch_run.  A refused list leaves the one in force; an empty
      * list: off. */
     Error SetBatchBlends(const std::vector<std::vector<std::pair<int, double>>> &blends, const std::vector<double> &gain = {},
-                         const std::vector<std::vector<int>> &delay = {});      /* delay[b][k]: term k of blend b reads its row that many samples back (gdg_batch_set_blends_delayed); none: every delay 0 */
+                         const std::vector<std::vector<int>> &delay = {},      /* delay[b][k]: term k of blend b reads its row that many samples back (gdg_batch_set_blends_delayed); none: every delay 0 */
+                         const std::vector<std::vector<std::vector<double>>> &taps = {});      /* taps[b][k]: that term's FIR, 0 to 64 finite taps (gdg_batch_set_blends_filtered); none: no term has one */
     int BatchBlends() const { return blendFirst_.empty() ? 0 : (int)blendFirst_.size() - 1; }
     /* No reference counterpart.  The blend fits (include/gdg.h, gdg_batch_fit_enable): per fit a target port and 1 to 8 term ports of the
      * job -- chain outputs, master left, master right, metronome and the blend ports in force.  While fits are in force BatchRun and the plain
@@ -380,6 +381,8 @@ private:
     std::vector<int> blendFirst_, blendChannel_;           /* SetBatchBlends, in gdg_batch_set_blends' CSR form; blendFirst_ empty: off */
     std::vector<double> blendWeight_, blendGain_;
     std::vector<int> blendDelay_;                          /* one per term, or empty: every delay 0 and the list goes through gdg_batch_set_blends */
+    std::vector<int> blendTapFirst_;                       /* one offset per term and one more into blendTap_, or empty: no term has taps and the list goes the delayed way */
+    std::vector<double> blendTap_;
     std::vector<int> fitFirst_, fitPort_, fitTarget_;      /* SetBatchFits, in gdg_batch_fit_enable's CSR form; fitTarget_ empty: off */
     std::vector<gdg_block_fit> lastFit_;                   /* [fits][blocks] of the last batch call that kept them */
     size_t fitBlocks_ = 0;

@@ -1151,10 +1151,58 @@ int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_
  * gets lag 0 and sign +1, and so does a port that is its own reference or is the reference of the others.  Per blend: every term's
  * channel is measured against one reference port, or is that port; otherwise the call returns GDG_ERR_INVALID, writes nothing and names the
  * blend.  delay_k = max_j lag_j - lag_k; sign_k is the port's sign: the caller multiplies the weights by it.
+ * FILTERS: a short FIR per term.  With windowed-sinc taps it is a fractional delay -- at 44.1 or 48 kHz half a sample of offset between two
+ * microphone positions is 90 degrees at 11-12 kHz, the comb filter the alignment was built to remove, an octave up --, with other taps a
+ * per-term tilt or match EQ, taken from the float64 rows before anything is truncated.  Term k of a blend has, beside c_k, w_k and d_k, a
+ * tap count T_k, 0 <= T_k <= GDG_BLEND_MAX_TAPS (64), and taps h_k[0 .. T_k - 1].  The taps are finite doubles; zero and negative taps are
+ * allowed.  With i the sample index in the job, and x[c][j] = +0.0 for j < 0:
+ *   T_k == 0:  x_k[i] = x[c_k][i - d_k]                                  exactly DELAYS
+ *   T_k >= 1:  f = h_k[0] * x[c_k][i - d_k]                              one rounded multiply
+ *              f = f + (h_k[t] * x[c_k][i - d_k - t])    t = 1 .. T_k - 1   one rounded multiply, one rounded add, ascending t
+ *              x_k[i] = f
+ *   s = w_0 * x_0[i];  s = s + (w_k * x_k[i])   in term order            unchanged
+ * Nothing is ever contracted into a fused multiply-add and nothing is reassociated (csrc/blend.h: gdg_blend_mul, gdg_blend_add).
+ * The limit per term is d_k + max(T_k, 1) - 1 <= GDG_BLEND_MAX_DELAY: the term's REACH.  The history of [N][4096] doubles is therefore
+ * enough, and it is used exactly as DELAYS uses it: allocated only while some term's reach is above 0, zeroed by the first slice of a job,
+ * saved behind the sum of each step, counted by stat_batch_device_kib.
+ * Known answer: one term on row x with d = 0, T = 2, h = {1, -1} and w = 1 gives s[0] = x[0] and s[i] = x[i] - x[i - 1]: the bits of the
+ * DELAYS known answer.
+ * Where a NaN lands is defined: a NaN at x[c][j] reaches i = j + d .. j + d + T - 1; its sign and payload are not, as elsewhere.
+ * Ports, records, dither ports, output gains, the alignment list, fits and Gram lists treat a filtered blend port like any other blend
+ * port: they read s, before g_b.
+ *   gdg_batch_set_blends_filtered(ctx, n_blends, first, channel, weight, delay, tap_first, tap, gain)
+ *                                                      tap_first: one entry per term plus one, in CSR form over all terms of all blends;
+ *                                                      it starts at 0 and never descends; term k has the taps tap[tap_first[k] ..
+ *                                                      tap_first[k + 1] - 1].  tap_first == NULL: the call IS
+ *                                                      gdg_batch_set_blends_delayed -- the same table byte for byte, the same kernels and
+ *                                                      buffers, the same bytes uploaded and written.  So is a list whose every T_k is 0.
+ *   gdg_batch_blend_max_reach(ctx)                     the largest d_k + max(T_k, 1) - 1 in force; 0: the blends are stateless
+ * Validation follows the delayed call: the whole argument is checked before anything replaces the setting in force; GDG_ERR_INVALID, with
+ * gdg_last_error naming the blend and the term, and the setting unchanged: a tap that is not finite, a count above 64, a reach above 4096,
+ * a tap_first that does not start at 0 or descends, a call while a streamed job is open.  gdg_batch_blend_max_delay keeps its meaning: the
+ * largest d_k.  The checkpoint calls, gdg_batch_stream_resume and their shard forms return GDG_ERR_UNSUPPORTED while
+ * gdg_batch_blend_max_reach > 0; the four shard calls refuse blends as ever.
+ * The filtered sum on its own, both blocking, refusing what gdg_blend_rows_delayed refuses and the taps refused above:
+ *   gdg_blend_rows_filtered(ctx, rows, n_rows, samples, n_blends, first, channel, weight, delay, tap_first, tap, history, out)
+ *   gdg_blend_rows_filtered_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, delay, tap_first, tap,
+ *                                  d_history, hist_stride, d_out, out_stride)
+ * The taps of a fractional delay and the fraction from fit records -- host only: no context, no device (gdg_last_error(NULL) says what was
+ * refused):
+ *   gdg_blend_fraction_taps(n_taps, fraction, tap)     T = n_taps even, 2 <= T <= 64; 0 <= fraction < 1.  The taps delay by T/2 - 1 +
+ *                                                      fraction samples: sinc(u) * (0.5 + 0.5 cos(2 pi u / T)) with u = t - (T/2 - 1) -
+ *                                                      fraction, divided by their sum.  fraction == 0 returns the exact unit impulse at
+ *                                                      T/2 - 1, with no call into libm.
+ *   gdg_blend_fractions_from_fit(records, n_fits, blocks, steps, step)
+ *                                                      records[n_fits][blocks] of gdg_batch_fit (FIT, below); steps = Q, 1 <= Q <= 4.
+ *                                                      Fit f has 2Q - 1 terms, term k the candidate at offset (k - (Q - 1)) / Q samples.
+ * The records of the blocks are added in block order.  The candidate with the largest tx[k] / sqrt(xx[k][k]) wins; only candidates with
+ * xx[k][k] > 0 count; the earlier entry wins a tie.  step[f] is its k - (Q - 1).  A fit with tt <= 0 or without an admissible candidate
+ * gives 0.  A fit with another term count, or a non-finite sum, is refused whole and nothing is written.
  */
 #define GDG_BLEND_MAX_TERMS 32
 #define GDG_BLEND_MAX_BLENDS 1024
 #define GDG_BLEND_MAX_DELAY 4096
+#define GDG_BLEND_MAX_TAPS 64
 int gdg_batch_set_blends(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const double *gain);
 int gdg_batch_blends(const gdg_ctx *ctx);
 int gdg_blend_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
@@ -1171,6 +1219,16 @@ int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row
                                   double *d_out, size_t out_stride);
 int gdg_blend_delays_from_align(const gdg_block_align *records, int ports, size_t blocks, const int *ref, double min_coeff, int n_blends,
                                 const int *first, const int *channel, int *delay, int *sign);
+int gdg_batch_set_blends_filtered(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay,
+                                  const int *tap_first, const double *tap, const double *gain);
+int gdg_batch_blend_max_reach(const gdg_ctx *ctx);
+int gdg_blend_rows_filtered(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                            const double *weight, const int *delay, const int *tap_first, const double *tap, const double *const *history,
+                            double *const *out);
+int gdg_blend_rows_filtered_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
+                                   const int *channel, const double *weight, const int *delay, const int *tap_first, const double *tap,
+                                   const double *d_history, size_t hist_stride, double *d_out, size_t out_stride);
+int gdg_blend_fraction_taps(int n_taps, double fraction, double *tap);
 /*
  * FIT: no reference counterpart.  The one blend parameter the records above do not measure is the weight: "which mix of these few rigs
  * comes closest to THAT track?" is a linear least-squares problem, and everything it needs is an inner product of float64 rows that already
@@ -1246,6 +1304,8 @@ int gdg_block_fit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size
 int gdg_block_fit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
                               const int *port, const int *target, gdg_block_fit *d_records);
 int gdg_blend_weights_from_fit(const gdg_block_fit *records, int n_fits, size_t blocks, double ridge, double *weight, double *residual);
+/* BLEND, FILTERS: the fraction of a delay from the records of one fit per channel */
+int gdg_blend_fractions_from_fit(const gdg_block_fit *records, int n_fits, size_t blocks, int steps, int *step);
 /*
  * GRAM: no reference counterpart.  A fit needs its 1 to 8 term ports named.  The question in front of it -- "which few of these many rigs, in
  * which mix, come closest to THAT track?" -- needs one object: the Gram matrix G = X X' of all candidate rows and the target.  A Gram record
