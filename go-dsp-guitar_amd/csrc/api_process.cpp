@@ -393,6 +393,17 @@ static int pcie_groups(const gdg_ctx *ctx, int n) {
  * or env GDG_DEVICE_GROUPS -- because a caller that caches gdg_ctx_stream() and enqueues its own work behind a process call is only
  * ordered after the call's kernels when they run on that stream: the default is ONE group on the context's stream.
  * Measured (profiles/device_groups_r02.txt): two groups gain 7-10 % from 512 channels on, nothing below, four lose. */
+/* The callers' frames are read and written as sample PAIRS wherever a kernel knows the frame length to be even without looking: the forward
+ * transforms' first pass and the inverse transforms' last (fir.hip: gload / gstore of a cplx at bsrc + 2 e, dst + 2 n), the oversampling tiles'
+ * decimator store and their compressor prefix's frame load (seg.hip: os_tiles_kernel).  Only seg_frame tests the pointers and falls back to
+ * single samples.  Rows start at base + c * stride: a 16-byte-aligned base leaves the rows of an odd stride to the paths that handle any
+ * parity (an odd stride is an odd frame length in gdg_process_device); a base that is only 8-byte aligned is refused here. */
+static int check_pair_alignment(gdg_ctx *ctx, const double *d_in, const double *d_out) {
+    if ((uintptr_t)d_in & 15) return fail(ctx, GDG_ERR_INVALID, "d_in %p is not 16-byte aligned", (const void *)d_in);
+    if ((uintptr_t)d_out & 15) return fail(ctx, GDG_ERR_INVALID, "d_out %p is not 16-byte aligned", (const void *)d_out);
+    return GDG_OK;
+}
+
 static int device_groups(const gdg_ctx *ctx) {
     const int forced = ctx->device_groups_env;
     const int n = ctx->nch;
@@ -403,6 +414,7 @@ static int device_groups(const gdg_ctx *ctx) {
 
 int gdg_process_device(gdg_ctx *ctx, const double *d_in, double *d_out, int frames, uint32_t sample_rate) {
     if (!ctx || !d_in || !d_out) return GDG_ERR_INVALID;
+    if (int rc = check_pair_alignment(ctx, d_in, d_out)) return rc;
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
     return process_rows(ctx, ctx->all_channels, d_in, d_out, frames, sample_rate, 0, false, device_groups(ctx));
 }
@@ -445,6 +457,8 @@ int gdg_process_window_device(gdg_ctx *ctx, const double *d_in, double *d_out, s
     if (W != 1 && W != 2 && W != 4 && W != 8 && W != 16) return fail(ctx, GDG_ERR_INVALID, "window of %d frames: 1, 2, 4, 8 or 16", W);
     if (row_stride < (size_t)W * (size_t)ctx->max_frames || row_stride > 0x7fffffff)
         return fail(ctx, GDG_ERR_INVALID, "row stride %zu is shorter than the window (%d x %d)", row_stride, W, ctx->max_frames);
+    if (int rc = check_pair_alignment(ctx, d_in, d_out)) return rc;
+    if (row_stride & 1) return fail(ctx, GDG_ERR_INVALID, "row stride %zu is odd: the rows of d_in and d_out would not all be 16-byte aligned", row_stride);
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
     return process_rows(ctx, ctx->all_channels, d_in, d_out, ctx->max_frames, sample_rate, (int)row_stride, false, device_groups(ctx), nullptr, nullptr, W);
 }

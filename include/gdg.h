@@ -310,6 +310,9 @@ int gdg_process_staged(gdg_ctx *ctx, const int *channels, int n, int frames, uin
  * Same, device-resident: d_in / d_out are device pointers to [n_channels][frames] float64
  * (row-major, row stride = frames).  Enqueued on gdg_ctx_stream() and NOT synchronised;
  * d_in == d_out is not allowed.
+ * Alignment: d_in and d_out must be 16-byte aligned (the kernels read and write the frames as sample pairs); any frame
+ * length goes, odd ones included.  A pointer that is only 8-byte aligned -- a slice x[:, 1:] of an aligned tensor -- is
+ * refused with GDG_ERR_INVALID and a message naming the pointer; nothing is launched and no state changes.
  */
 int gdg_process_device(gdg_ctx *ctx, const double *d_in, double *d_out, int frames, uint32_t sample_rate);
 
@@ -323,6 +326,8 @@ int gdg_process_device(gdg_ctx *ctx, const double *d_in, double *d_out, int fram
  * the larger delay-line ring (K + W - 1 slots) like on a frame-size change.
  * gdg_process_window_device: d_in / d_out = [n_channels][row_stride] float64, frame j of channel c at c * row_stride + j * 8192;
  * frames_in_window in {1, 2, 4, 8, 16}, <= W (the tail of a file).  Enqueued on gdg_ctx_stream(), not synchronised.
+ * Alignment: d_in and d_out must be 16-byte aligned and row_stride even, so that every row is; anything else is refused with
+ * GDG_ERR_INVALID and a message naming the pointer or the stride, as in gdg_process_device.
  */
 int gdg_ctx_set_window(gdg_ctx *ctx, int frames_per_call);
 /*
