@@ -1387,15 +1387,25 @@ class Context:
         """The largest d + max(T, 1) - 1 of the blends in force (gdg_batch_blend_max_reach): how far back a term reads; 0: stateless."""
         return int(lib().gdg_batch_blend_max_reach(self._h))
 
-    def blend_rows_filtered(self, rows, blends, history=None):
-        """gdg_blend_rows_filtered: rows [n_rows, samples] float64, blends of (row, weight[, delay[, taps]]) terms, history None (zeros in front
-        of sample 0) or [n_rows, BLEND_MAX_DELAY] float64 whose last column is sample -1 -> [blends, samples]."""
+    def _blend_args(self, blends, parts):
+        """the list's pointers in the order of the C calls -- first, channel, weight and then `parts` of "delay", "taps" (two pointers) -- and
+        the arrays that keep them alive"""
+        first, channel, weight = self._blend_csr(blends)
+        delay, taps = self._blend_delays(blends), self._blend_taps(blends)
+        args = [first.ctypes.data, channel.ctypes.data, weight.ctypes.data]
+        if "delay" in parts:
+            args.append(None if delay is None else delay.ctypes.data)
+        if "taps" in parts:
+            args += [None, None] if taps is None else [taps[0].ctypes.data, taps[1].ctypes.data]
+        return args, (first, channel, weight, delay, taps)
+
+    def _blend_rows_host(self, call, parts, rows, blends, history=None):
+        """the host form of the three blend calls: rows and the optional history up, [blends, samples] back; the plain call (no parts) takes no history"""
         x = np.ascontiguousarray(rows, dtype=np.float64)
         if x.ndim != 2:
             raise ValueError("rows: [n_rows, samples]")
         blends = [list(b) for b in blends]
-        first, channel, weight = self._blend_csr(blends)
-        delay, taps = self._blend_delays(blends), self._blend_taps(blends)
+        args, keep = self._blend_args(blends, parts)
         h = None if history is None else np.ascontiguousarray(history, dtype=np.float64)
         if h is not None and h.shape != (x.shape[0], BLEND_MAX_DELAY):
             raise ValueError("history: [n_rows, %d]" % BLEND_MAX_DELAY)
@@ -1403,70 +1413,42 @@ class Context:
         rp = (C.c_void_p * max(x.shape[0], 1))(*[x[r].ctypes.data for r in range(x.shape[0])])
         hp = None if h is None else (C.c_void_p * max(x.shape[0], 1))(*[h[r].ctypes.data for r in range(x.shape[0])])
         op = (C.c_void_p * max(len(blends), 1))(*[out[b].ctypes.data for b in range(len(blends))])
-        self._check(lib().gdg_blend_rows_filtered(self._h, rp, x.shape[0], x.shape[1], len(blends), first.ctypes.data, channel.ctypes.data, weight.ctypes.data,
-                                                  None if delay is None else delay.ctypes.data, None if taps is None else taps[0].ctypes.data,
-                                                  None if taps is None else taps[1].ctypes.data, hp, op))
+        self._check(call(self._h, rp, x.shape[0], x.shape[1], len(blends), *args, *([hp] if parts else []), op))
         return out
+
+    def _blend_rows_device(self, call, parts, d_rows, row_stride, n_rows, samples, blends, d_out, out_stride, history=()):
+        """the device form of the three blend calls; history: () or (d_history, hist_stride)"""
+        blends = [list(b) for b in blends]
+        args, keep = self._blend_args(blends, parts)
+        self._check(call(self._h, d_rows, row_stride, n_rows, samples, len(blends), *args, *history, d_out, out_stride))
+
+    def blend_rows_filtered(self, rows, blends, history=None):
+        """gdg_blend_rows_filtered: rows [n_rows, samples] float64, blends of (row, weight[, delay[, taps]]) terms, history None (zeros in front
+        of sample 0) or [n_rows, BLEND_MAX_DELAY] float64 whose last column is sample -1 -> [blends, samples]."""
+        return self._blend_rows_host(lib().gdg_blend_rows_filtered, ("delay", "taps"), rows, blends, history)
 
     def blend_rows_filtered_device(self, d_rows, row_stride, n_rows, samples, blends, d_out, out_stride, d_history=None, hist_stride=BLEND_MAX_DELAY):
         """gdg_blend_rows_filtered_device on plain device pointers (ints); d_history as blend_rows_delayed_device takes it; returns when the
         sums are written."""
-        blends = [list(b) for b in blends]
-        first, channel, weight = self._blend_csr(blends)
-        delay, taps = self._blend_delays(blends), self._blend_taps(blends)
-        self._check(lib().gdg_blend_rows_filtered_device(self._h, d_rows, row_stride, n_rows, samples, len(blends), first.ctypes.data, channel.ctypes.data,
-                                                         weight.ctypes.data, None if delay is None else delay.ctypes.data, None if taps is None else taps[0].ctypes.data,
-                                                         None if taps is None else taps[1].ctypes.data, d_history, hist_stride, d_out, out_stride))
+        self._blend_rows_device(lib().gdg_blend_rows_filtered_device, ("delay", "taps"), d_rows, row_stride, n_rows, samples, blends, d_out, out_stride, (d_history, hist_stride))
 
     def blend_rows_delayed(self, rows, blends, history=None):
         """gdg_blend_rows_delayed: rows [n_rows, samples] float64, blends of (row, weight, delay) terms, history None (zeros in front of sample
         0) or [n_rows, BLEND_MAX_DELAY] float64 whose last column is sample -1 -> [blends, samples]."""
-        x = np.ascontiguousarray(rows, dtype=np.float64)
-        if x.ndim != 2:
-            raise ValueError("rows: [n_rows, samples]")
-        blends = [list(b) for b in blends]
-        first, channel, weight = self._blend_csr(blends)
-        delay = self._blend_delays(blends)
-        h = None if history is None else np.ascontiguousarray(history, dtype=np.float64)
-        if h is not None and h.shape != (x.shape[0], BLEND_MAX_DELAY):
-            raise ValueError("history: [n_rows, %d]" % BLEND_MAX_DELAY)
-        out = np.zeros((len(blends), x.shape[1]), dtype=np.float64)
-        rp = (C.c_void_p * max(x.shape[0], 1))(*[x[r].ctypes.data for r in range(x.shape[0])])
-        hp = None if h is None else (C.c_void_p * max(x.shape[0], 1))(*[h[r].ctypes.data for r in range(x.shape[0])])
-        op = (C.c_void_p * max(len(blends), 1))(*[out[b].ctypes.data for b in range(len(blends))])
-        self._check(lib().gdg_blend_rows_delayed(self._h, rp, x.shape[0], x.shape[1], len(blends), first.ctypes.data, channel.ctypes.data,
-                                                 weight.ctypes.data, None if delay is None else delay.ctypes.data, hp, op))
-        return out
+        return self._blend_rows_host(lib().gdg_blend_rows_delayed, ("delay",), rows, blends, history)
 
     def blend_rows_delayed_device(self, d_rows, row_stride, n_rows, samples, blends, d_out, out_stride, d_history=None, hist_stride=BLEND_MAX_DELAY):
         """gdg_blend_rows_delayed_device on plain device pointers (ints); d_history: None or row r's BLEND_MAX_DELAY samples in front of
         sample 0 at d_history + r * hist_stride; returns when the sums are written."""
-        blends = [list(b) for b in blends]
-        first, channel, weight = self._blend_csr(blends)
-        delay = self._blend_delays(blends)
-        self._check(lib().gdg_blend_rows_delayed_device(self._h, d_rows, row_stride, n_rows, samples, len(blends), first.ctypes.data, channel.ctypes.data,
-                                                        weight.ctypes.data, None if delay is None else delay.ctypes.data, d_history, hist_stride, d_out, out_stride))
+        self._blend_rows_device(lib().gdg_blend_rows_delayed_device, ("delay",), d_rows, row_stride, n_rows, samples, blends, d_out, out_stride, (d_history, hist_stride))
 
     def blend_rows(self, rows, blends):
         """gdg_blend_rows: rows [n_rows, samples] float64, blends as batch_set_blends takes them with `channel` naming a row -> [blends, samples]."""
-        x = np.ascontiguousarray(rows, dtype=np.float64)
-        if x.ndim != 2:
-            raise ValueError("rows: [n_rows, samples]")
-        blends = [list(b) for b in blends]
-        first, channel, weight = self._blend_csr(blends)
-        out = np.zeros((len(blends), x.shape[1]), dtype=np.float64)
-        rp = (C.c_void_p * max(x.shape[0], 1))(*[x[r].ctypes.data for r in range(x.shape[0])])
-        op = (C.c_void_p * max(len(blends), 1))(*[out[b].ctypes.data for b in range(len(blends))])
-        self._check(lib().gdg_blend_rows(self._h, rp, x.shape[0], x.shape[1], len(blends), first.ctypes.data, channel.ctypes.data,
-                                         weight.ctypes.data, op))
-        return out
+        return self._blend_rows_host(lib().gdg_blend_rows, (), rows, blends)
 
     def blend_rows_device(self, d_rows, row_stride, n_rows, samples, blends, d_out, out_stride):
         """gdg_blend_rows_device on plain device pointers (ints); returns when the sums are written."""
-        blends = [list(b) for b in blends]
-        first, channel, weight = self._blend_csr(blends)
-        self._check(lib().gdg_blend_rows_device(self._h, d_rows, row_stride, n_rows, samples, len(blends), first.ctypes.data,
-                                                channel.ctypes.data, weight.ctypes.data, d_out, out_stride))
+        self._blend_rows_device(lib().gdg_blend_rows_device, (), d_rows, row_stride, n_rows, samples, blends, d_out, out_stride)
 
     # -- the blend fit: Gram records per fit and block, the least-squares weights from them (include/gdg.h, FIT) --------------------------------
     def batch_fit_enable(self, fits):

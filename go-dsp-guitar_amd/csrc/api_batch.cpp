@@ -117,11 +117,10 @@ struct BatchLoop {
     /* the blend outputs: n_blends rows behind the window's N + 3 (0 = off, and always for a shard); their table on the device (blend.h) and
      * their output gains -- null = every one 1.0: the blend rows go through the plain or the dithered encoder */
     int n_blends;
-    const int *d_blend_first, *d_blend_channel;
-    const double *d_blend_weight, *d_blend_gain;
-    /* a delay in force (gdg_batch_set_blends_delayed): one per term, and the context's history of the N chain rows -- what the step before
-     * left of them, zeros at the job's start; both null while every delay is 0 */
-    const int *d_blend_delay;
+    gdg_blend_view blend;
+    const double *d_blend_gain;
+    /* while a term reaches back (a delay, or taps behind the first): the context's history of the N chain rows -- what the step before left
+     * of them, zeros at the job's start; null otherwise, and then no sample a term reads lies in front of the job */
     double *d_blend_history;
     /* the blend fits: n_fits entries of the table (blend.h, FitSet) on the host and on the device; 0 = off, and always for a shard */
     int n_fits;
@@ -129,10 +128,6 @@ struct BatchLoop {
     /* the Gram list: n_gram ports on the host and on the device; 0 = off, and always for a shard */
     int n_gram;
     const int *h_gram_port, *d_gram_port;
-    /* taps in force (gdg_batch_set_blends_filtered): the offsets, one per term and one more, and the taps; null = no term has one.  The delays are then there as well,
-     * and the history only while a term reaches back -- null otherwise, and then no slot of a window lies in front of the job */
-    const int *d_blend_tap_first;
-    const double *d_blend_tap;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -279,21 +274,11 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             const size_t row_bytes = (size_t)wb * out_width;
             const ReportSections &sec = steps[i].sec;
             /* the blend rows, behind the metronome's: sums of the chain rows, which are final; every reader below takes them as rows like the others */
-            if (p.n_blends && !p.d_blend_delay)
-                HIP_TRY(ctx, gdg_launch_blend_rows(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight,
-                                                   d_win + (size_t)NO * ws, ws, ctx->stream));
-            if (p.n_blends && p.d_blend_tap_first) {
-                /* filtered terms: the same history, read up to d + T - 1 samples back and replaced behind the sum */
-                HIP_TRY(ctx, gdg_launch_blend_rows_filtered(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight, p.d_blend_delay,
-                                                            p.d_blend_tap_first, p.d_blend_tap, p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, d_win + (size_t)NO * ws, ws,
-                                                            ctx->stream));
+            if (p.n_blends) {
+                /* terms that reach back read the step before: its tail is the history (a step has at least 8192 samples, a term reaches at most
+                 * 4096 back).  This step's tail replaces it behind the sum and before the next step writes the window. */
+                HIP_TRY(ctx, gdg_launch_blend(p.blend, d_win, ws, (size_t)wb, p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, d_win + (size_t)NO * ws, ws, ctx->stream));
                 if (p.d_blend_history) HIP_TRY(ctx, gdg_launch_blend_history_save(d_win, ws, (size_t)wb, (unsigned)N, p.d_blend_history, ctx->stream));
-            } else if (p.n_blends && p.d_blend_delay) {
-                /* delayed terms reach into the step before: its tail is the history (a step has at least 8192 samples, a delay at most 4096).
-                 * This step's tail replaces it behind the sum and before the next step writes the window. */
-                HIP_TRY(ctx, gdg_launch_blend_rows_delayed(d_win, ws, (size_t)wb, (unsigned)p.n_blends, p.d_blend_first, p.d_blend_channel, p.d_blend_weight, p.d_blend_delay,
-                                                           p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, d_win + (size_t)NO * ws, ws, ctx->stream));
-                HIP_TRY(ctx, gdg_launch_blend_history_save(d_win, ws, (size_t)wb, (unsigned)N, p.d_blend_history, ctx->stream));
             }
             if (p.live.on(REPORT_STATS)) {                                   /* the rows as the encoder is about to read them */
                 gdg_block_stats *rec = reinterpret_cast<gdg_block_stats *>(enc + sec.at[REPORT_STATS]);
@@ -520,23 +505,13 @@ int gdg_batch_set_blends_filtered(gdg_ctx *ctx, int n_blends, const int *first, 
                                   const double *tap, const double *gain) {
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set blends: a streamed batch run is open on this context; its blends hold until gdg_batch_stream_close");
-    int b = -1, k = -1;
-    switch (gdg_blend_check(n_blends, first, channel, weight, delay, gain, ctx->nch, &b, &k)) {
-    case BLEND_OK: break;
-    case BLEND_COUNT: return fail(ctx, GDG_ERR_INVALID, "set blends: %d blends; 0 (off) to %d", n_blends, GDG_BLEND_MAX_BLENDS);
-    case BLEND_NULL: return fail(ctx, GDG_ERR_INVALID, "set blends: %d blends need first, channel and weight", n_blends);
-    case BLEND_FIRST: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d: first[%d] = %d, first[%d] = %d; the offsets start at 0 and never descend", b, b, first[b], b + 1, first[b + 1]);
-    case BLEND_EMPTY: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d has no term; 1 to %d", b, GDG_BLEND_MAX_TERMS);
-    case BLEND_TERMS: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d has %d terms; 1 to %d", b, first[b + 1] - first[b], GDG_BLEND_MAX_TERMS);
-    case BLEND_CHANNEL:
-        return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d names channel %d, the context has channels 0 to %d", b, k, channel[first[b] + k], ctx->nch - 1);
-    case BLEND_WEIGHT: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d: weight = %g is not finite", b, k, weight[first[b] + k]);
-    case BLEND_DELAY: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d, term %d: delay = %d; 0 to %d samples", b, k, delay[first[b] + k], GDG_BLEND_MAX_DELAY);
-    default: return fail(ctx, GDG_ERR_INVALID, "set blends: blend %d: gain = %g is not finite", b, gain[b]);
+    int b = -1, k = -1, t = -1;
+    char msg[240];
+    if (const int rc = gdg_blend_check(n_blends, first, channel, weight, delay, gain, ctx->nch, &b, &k)) {
+        gdg_blend_list_message(msg, sizeof msg, "set blends", false, rc, b, k, n_blends, first, channel, weight, delay, gain, ctx->nch);
+        return fail(ctx, GDG_ERR_INVALID, "%s", msg);
     }
-    int t = -1;
     if (const int rc = gdg_blend_check_taps(n_blends, first, delay, tap_first, tap, &b, &k, &t)) {
-        char msg[240];
         gdg_blend_taps_message(msg, sizeof msg, "set blends", rc, b, k, t, first, delay, tap_first, tap, n_blends);
         return fail(ctx, GDG_ERR_INVALID, "%s", msg);
     }
@@ -1004,7 +979,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr };
         /* the fits in force: their table goes up on the context's stream, ahead of everything the slice enqueues there; it lives as long as
          * the setting, so nothing waits here */
         if (n_fits) {
@@ -1030,11 +1005,10 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_trim, ctx->trim_gain.data(), (size_t)NO * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             loop.d_trim = ctx->d_trim;
         }
-        /* the blends in force: their table goes up the same way -- first | channel | delay | tap_first | pad | weight | gain | taps, the delays and the
-         * tap offsets only where the list has them, the doubles 8-byte aligned (BlendSet::packed) */
+        /* the blends in force: their table goes up the same way, as it was packed when the list was taken (blend.h, gdg_blend_pack) */
         if (n_blends) {
-            const BlendSet &bs = ctx->blend;                                  /* packed when it was set: it lives as long as the setting, so nothing waits here */
-            const size_t ints = bs.packed_ints(), bytes = bs.packed.size();
+            const BlendSet &bs = ctx->blend;                                  /* it lives as long as the setting, so nothing waits here */
+            const size_t bytes = bs.packed.size();
             if (bytes > ctx->d_blend_cap) {
                 hipFree(ctx->d_blend);
                 ctx->d_blend = nullptr;
@@ -1044,15 +1018,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             }
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_blend, bs.packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
             loop.n_blends = n_blends;
-            loop.d_blend_first = reinterpret_cast<const int *>(ctx->d_blend);
-            loop.d_blend_channel = loop.d_blend_first + n_blends + 1;
-            loop.d_blend_weight = reinterpret_cast<const double *>(ctx->d_blend + ints);
-            loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.d_blend_weight + bs.terms();
-            if (!bs.delay.empty()) loop.d_blend_delay = loop.d_blend_channel + bs.terms();      /* there while a delay is not 0 or a term has taps */
-            if (!bs.tap_first.empty()) {
-                loop.d_blend_tap_first = loop.d_blend_delay + bs.terms();
-                loop.d_blend_tap = reinterpret_cast<const double *>(ctx->d_blend + bs.packed_taps());
-            }
+            loop.blend = bs.view(ctx->d_blend);
+            loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.blend.gain;
             if (bs.max_reach() > 0) {
                 /* the history of the N chain rows: the job's first slice begins from zeros, every later one from what the slice before left */
                 const size_t hist_bytes = (size_t)N * GDG_BLEND_MAX_DELAY * sizeof(double);

@@ -738,78 +738,32 @@ int gdg_batch_align(gdg_ctx *ctx, gdg_block_align *records, size_t capacity, int
     return batch_kind_get(ctx, REPORT_ALIGN, ctx && !ctx->align_ref.empty(), words, records, capacity, ports, blocks, nullptr);
 }
 
-/* ---- the blend on its own (include/gdg.h; the kernel: blend_kernels.h in io.hip; the list's validation: blend.h; the batch calls: api_batch.cpp) ---- */
-static int blend_rows_check(gdg_ctx *ctx, int n_rows, int n_blends, const int *first, const int *channel, const double *weight, const int *delay = nullptr) {
+/* ---- the blend on its own (include/gdg.h; the kernels and their launcher: blend_kernels.h in io.hip; the list, its table and its view: blend.h; the batch calls:
+ * api_batch.cpp).  The plain, the delayed and the filtered call are one device body and one host body; a form passes null for what it lacks ---- */
+static int blend_rows_check(gdg_ctx *ctx, int n_rows, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const int *tap_first,
+                            const double *tap) {
     if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "blend rows: %d rows (at least 1)", n_rows);
-    int b = -1, k = -1;
-    switch (gdg_blend_check(n_blends, first, channel, weight, delay, nullptr, n_rows, &b, &k)) {
-    case BLEND_OK: return GDG_OK;
-    case BLEND_COUNT: return fail(ctx, GDG_ERR_INVALID, "blend rows: %d blends; 0 to %d", n_blends, GDG_BLEND_MAX_BLENDS);
-    case BLEND_NULL: return fail(ctx, GDG_ERR_INVALID, "blend rows: %d blends need first, channel and weight", n_blends);
-    case BLEND_FIRST: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d: first[%d] = %d, first[%d] = %d; the offsets start at 0 and never descend", b, b, first[b], b + 1, first[b + 1]);
-    case BLEND_EMPTY: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d has no term; 1 to %d", b, GDG_BLEND_MAX_TERMS);
-    case BLEND_TERMS: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d has %d terms; 1 to %d", b, first[b + 1] - first[b], GDG_BLEND_MAX_TERMS);
-    case BLEND_CHANNEL: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d names row %d of %d", b, k, channel[first[b] + k], n_rows);
-    case BLEND_DELAY: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d: delay = %d; 0 to %d", b, k, delay[first[b] + k], GDG_BLEND_MAX_DELAY);
-    default: return fail(ctx, GDG_ERR_INVALID, "blend rows: blend %d, term %d: weight = %g is not finite", b, k, weight[first[b] + k]);
+    int b = -1, k = -1, t = -1;
+    char msg[240];
+    if (const int rc = gdg_blend_check(n_blends, first, channel, weight, delay, nullptr, n_rows, &b, &k)) {
+        gdg_blend_list_message(msg, sizeof msg, "blend rows", true, rc, b, k, n_blends, first, channel, weight, delay, nullptr, n_rows);
+        return fail(ctx, GDG_ERR_INVALID, "%s", msg);
     }
-}
-
-/* the table is the caller's host memory: it goes up, the kernel runs, and the call returns when the rows are written */
-int gdg_blend_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
-                          const double *weight, double *d_out, size_t out_stride) {
-    if (!ctx) return GDG_ERR_INVALID;
-    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight);
-    if (rc != GDG_OK) return rc;
-    if (n_blends == 0 || samples == 0) return GDG_OK;
-    if (!d_rows || !d_out) return GDG_ERR_INVALID;
-    if (row_stride < samples || out_stride < samples) return fail(ctx, GDG_ERR_INVALID, "blend rows: strides of %zu and %zu samples for rows of %zu", row_stride, out_stride, samples);
-    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7)) return fail(ctx, GDG_ERR_INVALID, "blend rows: rows and sums are 8-byte aligned");
-    enter_keep_fir_sums(ctx);
-    const size_t terms = (size_t)first[n_blends], ints = (((size_t)n_blends + 1 + terms) * sizeof(int) + 7) & ~(size_t)7, bytes = ints + terms * sizeof(double);
-    std::vector<unsigned char> host(bytes, 0);
-    memcpy(host.data(), first, ((size_t)n_blends + 1) * sizeof(int));
-    memcpy(host.data() + ((size_t)n_blends + 1) * sizeof(int), channel, terms * sizeof(int));
-    memcpy(host.data() + ints, weight, terms * sizeof(double));
-    void *d = nullptr;
-    HIP_TRY(ctx, ctx->arena.alloc(&d, bytes));
-    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        ProfScope ps(ctx, GDG_K_WAVE);
-        const int *d_first = static_cast<const int *>(d);
-        e = gdg_launch_blend_rows(d_rows, row_stride, samples, (unsigned)n_blends, d_first, d_first + n_blends + 1,
-                                  reinterpret_cast<const double *>(static_cast<unsigned char *>(d) + ints), d_out, out_stride, ctx->stream);
+    if (const int rc = gdg_blend_check_taps(n_blends, first, delay, tap_first, tap, &b, &k, &t)) {
+        gdg_blend_taps_message(msg, sizeof msg, "blend rows", rc, b, k, t, first, delay, tap_first, tap, n_blends);
+        return fail(ctx, GDG_ERR_INVALID, "%s", msg);
     }
-    const hipError_t w = hipStreamSynchronize(ctx->stream);
-    ctx->arena.release(d);
-    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
-    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(w));
     return GDG_OK;
 }
 
-int gdg_blend_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel, const double *weight,
-                   double *const *out) {
+/* The table is the caller's host memory: it is taken as the batch takes a list in force (gdg_blend_replace: delays that are all 0 and taps
+ * that are none are dropped, so such a list runs the kernel of the form without them), goes up, the kernel runs, and the call returns when
+ * the rows are written.  The history is held against its rules whether or not the kernel will read it. */
+static int blend_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                             const double *weight, const int *delay, const int *tap_first, const double *tap, const double *d_history, size_t hist_stride, double *d_out,
+                             size_t out_stride) {
     if (!ctx) return GDG_ERR_INVALID;
-    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight);
-    if (rc != GDG_OK) return rc;
-    if (n_blends == 0 || samples == 0) return GDG_OK;
-    if (!rows || !out) return GDG_ERR_INVALID;
-    for (int b = 0; b < n_blends; b++) if (!out[b]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the row of blend %d is NULL", b);
-    std::vector<double> sums((size_t)n_blends * samples);
-    rc = rows_round_trip(ctx, "blend rows", rows, n_rows, samples, sums.data(), sums.size() * sizeof(double), [&](const double *d_rows, void *d_out) {
-        return gdg_blend_rows_device(ctx, d_rows, samples, n_rows, samples, n_blends, first, channel, weight, static_cast<double *>(d_out), samples);
-    });
-    if (rc != GDG_OK) return rc;
-    for (int b = 0; b < n_blends; b++) memcpy(out[b], sums.data() + (size_t)b * samples, samples * sizeof(double));
-    return GDG_OK;
-}
-
-/* ---- the delayed blend on its own: the table goes up with its delays, the history is read where it lies ---- */
-int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
-                                  const int *channel, const double *weight, const int *delay, const double *d_history, size_t hist_stride, double *d_out,
-                                  size_t out_stride) {
-    if (!ctx) return GDG_ERR_INVALID;
-    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
+    const int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay, tap_first, tap);
     if (rc != GDG_OK) return rc;
     if (n_blends == 0 || samples == 0) return GDG_OK;
     if (!d_rows || !d_out) return GDG_ERR_INVALID;
@@ -818,21 +772,15 @@ int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row
     if (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY))
         return fail(ctx, GDG_ERR_INVALID, "blend rows: the history is 8-byte aligned, a row's run has %d samples; its stride is %zu", GDG_BLEND_MAX_DELAY, hist_stride);
     enter_keep_fir_sums(ctx);
-    /* first | channel | delay | pad | weight */
-    const size_t terms = (size_t)first[n_blends], ints = (((size_t)n_blends + 1 + 2 * terms) * sizeof(int) + 7) & ~(size_t)7, bytes = ints + terms * sizeof(double);
-    std::vector<unsigned char> host(bytes, 0);
-    memcpy(host.data(), first, ((size_t)n_blends + 1) * sizeof(int));
-    memcpy(host.data() + ((size_t)n_blends + 1) * sizeof(int), channel, terms * sizeof(int));
-    if (delay) memcpy(host.data() + ((size_t)n_blends + 1 + terms) * sizeof(int), delay, terms * sizeof(int));
-    memcpy(host.data() + ints, weight, terms * sizeof(double));
+    BlendSet set;
+    int b = -1, k = -1;
+    gdg_blend_replace(set, n_blends, first, channel, weight, delay, tap_first, tap, nullptr, n_rows, &b, &k);      /* checked above: it cannot refuse */
     void *d = nullptr;
-    HIP_TRY(ctx, ctx->arena.alloc(&d, bytes));
-    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    HIP_TRY(ctx, ctx->arena.alloc(&d, set.packed.size()));
+    hipError_t e = hipMemcpyAsync(d, set.packed.data(), set.packed.size(), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         ProfScope ps(ctx, GDG_K_WAVE);
-        const int *d_first = static_cast<const int *>(d);
-        e = gdg_launch_blend_rows_delayed(d_rows, row_stride, samples, (unsigned)n_blends, d_first, d_first + n_blends + 1, reinterpret_cast<const double *>(static_cast<unsigned char *>(d) + ints),
-                                          d_first + n_blends + 1 + terms, d_history, hist_stride, d_out, out_stride, ctx->stream);
+        e = gdg_launch_blend(set.view(d), d_rows, row_stride, samples, d_history, hist_stride, d_out, out_stride, ctx->stream);
     }
     const hipError_t w = hipStreamSynchronize(ctx->stream);
     ctx->arena.release(d);
@@ -841,10 +789,11 @@ int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row
     return GDG_OK;
 }
 
-int gdg_blend_rows_delayed(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
-                           const double *weight, const int *delay, const double *const *history, double *const *out) {
+/* rows, history (null: none) and sums in host memory: the history goes up, the rows make the round trip through the device body */
+static int blend_rows_host(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel, const double *weight,
+                           const int *delay, const int *tap_first, const double *tap, const double *const *history, double *const *out) {
     if (!ctx) return GDG_ERR_INVALID;
-    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
+    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay, tap_first, tap);
     if (rc != GDG_OK) return rc;
     if (n_blends == 0 || samples == 0) return GDG_OK;
     if (!rows || !out) return GDG_ERR_INVALID;
@@ -866,8 +815,8 @@ int gdg_blend_rows_delayed(gdg_ctx *ctx, const double *const *rows, int n_rows, 
     }
     std::vector<double> sums((size_t)n_blends * samples);
     rc = rows_round_trip(ctx, "blend rows", rows, n_rows, samples, sums.data(), sums.size() * sizeof(double), [&](const double *d_rows, void *d_out) {
-        return gdg_blend_rows_delayed_device(ctx, d_rows, samples, n_rows, samples, n_blends, first, channel, weight, delay, static_cast<const double *>(d_hist), H,
-                                             static_cast<double *>(d_out), samples);
+        return blend_rows_device(ctx, d_rows, samples, n_rows, samples, n_blends, first, channel, weight, delay, tap_first, tap, static_cast<const double *>(d_hist), H,
+                                 static_cast<double *>(d_out), samples);
     });
     if (d_hist) {
         hipStreamSynchronize(ctx->stream);
@@ -878,95 +827,36 @@ int gdg_blend_rows_delayed(gdg_ctx *ctx, const double *const *rows, int n_rows, 
     return GDG_OK;
 }
 
-/* ---- the filtered blend on its own: the table goes up with its delays, offsets and taps; without a tap it is the delayed call ---- */
-static int blend_rows_check_taps(gdg_ctx *ctx, int n_blends, const int *first, const int *delay, const int *tap_first, const double *tap) {
-    int b = -1, k = -1, t = -1;
-    const int rc = gdg_blend_check_taps(n_blends, first, delay, tap_first, tap, &b, &k, &t);
-    if (rc == BLEND_OK) return GDG_OK;
-    char msg[240];
-    gdg_blend_taps_message(msg, sizeof msg, "blend rows", rc, b, k, t, first, delay, tap_first, tap, n_blends);
-    return fail(ctx, GDG_ERR_INVALID, "%s", msg);
+int gdg_blend_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                          const double *weight, double *d_out, size_t out_stride) {
+    return blend_rows_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, nullptr, nullptr, nullptr, nullptr, 0, d_out, out_stride);
+}
+
+int gdg_blend_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel, const double *weight,
+                   double *const *out) {
+    return blend_rows_host(ctx, rows, n_rows, samples, n_blends, first, channel, weight, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+int gdg_blend_rows_delayed_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
+                                  const int *channel, const double *weight, const int *delay, const double *d_history, size_t hist_stride, double *d_out,
+                                  size_t out_stride) {
+    return blend_rows_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, delay, nullptr, nullptr, d_history, hist_stride, d_out, out_stride);
+}
+
+int gdg_blend_rows_delayed(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
+                           const double *weight, const int *delay, const double *const *history, double *const *out) {
+    return blend_rows_host(ctx, rows, n_rows, samples, n_blends, first, channel, weight, delay, nullptr, nullptr, history, out);
 }
 
 int gdg_blend_rows_filtered_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_blends, const int *first,
                                    const int *channel, const double *weight, const int *delay, const int *tap_first, const double *tap, const double *d_history,
                                    size_t hist_stride, double *d_out, size_t out_stride) {
-    if (!ctx) return GDG_ERR_INVALID;
-    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
-    if (rc == GDG_OK) rc = blend_rows_check_taps(ctx, n_blends, first, delay, tap_first, tap);
-    if (rc != GDG_OK) return rc;
-    if (n_blends == 0 || samples == 0) return GDG_OK;
-    if (!tap_first || tap_first[first[n_blends]] == 0)                       /* no tap anywhere: the delayed sum, by its own kernel */
-        return gdg_blend_rows_delayed_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, delay, d_history, hist_stride, d_out, out_stride);
-    if (!d_rows || !d_out) return GDG_ERR_INVALID;
-    if (row_stride < samples || out_stride < samples) return fail(ctx, GDG_ERR_INVALID, "blend rows: strides of %zu and %zu samples for rows of %zu", row_stride, out_stride, samples);
-    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7)) return fail(ctx, GDG_ERR_INVALID, "blend rows: rows and sums are 8-byte aligned");
-    if (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY))
-        return fail(ctx, GDG_ERR_INVALID, "blend rows: the history is 8-byte aligned, a row's run has %d samples; its stride is %zu", GDG_BLEND_MAX_DELAY, hist_stride);
-    enter_keep_fir_sums(ctx);
-    /* first | channel | delay | tap_first | pad | weight | taps */
-    const size_t terms = (size_t)first[n_blends], n_taps = (size_t)tap_first[terms], ints = (((size_t)n_blends + 1 + 3 * terms + 1) * sizeof(int) + 7) & ~(size_t)7,
-                 bytes = ints + (terms + n_taps) * sizeof(double);
-    std::vector<unsigned char> host(bytes, 0);
-    memcpy(host.data(), first, ((size_t)n_blends + 1) * sizeof(int));
-    memcpy(host.data() + ((size_t)n_blends + 1) * sizeof(int), channel, terms * sizeof(int));
-    if (delay) memcpy(host.data() + ((size_t)n_blends + 1 + terms) * sizeof(int), delay, terms * sizeof(int));
-    memcpy(host.data() + ((size_t)n_blends + 1 + 2 * terms) * sizeof(int), tap_first, (terms + 1) * sizeof(int));
-    memcpy(host.data() + ints, weight, terms * sizeof(double));
-    memcpy(host.data() + ints + terms * sizeof(double), tap, n_taps * sizeof(double));
-    void *d = nullptr;
-    HIP_TRY(ctx, ctx->arena.alloc(&d, bytes));
-    hipError_t e = hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        ProfScope ps(ctx, GDG_K_WAVE);
-        const int *d_first = static_cast<const int *>(d);
-        const double *d_weight = reinterpret_cast<const double *>(static_cast<unsigned char *>(d) + ints);
-        e = gdg_launch_blend_rows_filtered(d_rows, row_stride, samples, (unsigned)n_blends, d_first, d_first + n_blends + 1, d_weight, d_first + n_blends + 1 + terms,
-                                           d_first + n_blends + 1 + 2 * terms, d_weight + terms, d_history, hist_stride, d_out, out_stride, ctx->stream);
-    }
-    const hipError_t w = hipStreamSynchronize(ctx->stream);
-    ctx->arena.release(d);
-    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
-    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(w));
-    return GDG_OK;
+    return blend_rows_device(ctx, d_rows, row_stride, n_rows, samples, n_blends, first, channel, weight, delay, tap_first, tap, d_history, hist_stride, d_out, out_stride);
 }
 
 int gdg_blend_rows_filtered(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_blends, const int *first, const int *channel,
                             const double *weight, const int *delay, const int *tap_first, const double *tap, const double *const *history, double *const *out) {
-    if (!ctx) return GDG_ERR_INVALID;
-    int rc = blend_rows_check(ctx, n_rows, n_blends, first, channel, weight, delay);
-    if (rc == GDG_OK) rc = blend_rows_check_taps(ctx, n_blends, first, delay, tap_first, tap);
-    if (rc != GDG_OK) return rc;
-    if (n_blends == 0 || samples == 0) return GDG_OK;
-    if (!rows || !out) return GDG_ERR_INVALID;
-    for (int b = 0; b < n_blends; b++) if (!out[b]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the row of blend %d is NULL", b);
-    if (history) for (int r = 0; r < n_rows; r++) if (!history[r]) return fail(ctx, GDG_ERR_INVALID, "blend rows: the history of row %d is NULL", r);
-    const size_t H = (size_t)GDG_BLEND_MAX_DELAY;
-    void *d_hist = nullptr;
-    if (history) {
-        enter_keep_fir_sums(ctx);
-        HIP_TRY(ctx, ctx->arena.alloc(&d_hist, (size_t)n_rows * H * sizeof(double)));
-        for (int r = 0; r < n_rows; r++) {
-            const hipError_t e = hipMemcpyAsync(static_cast<double *>(d_hist) + (size_t)r * H, history[r], H * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) {
-                hipStreamSynchronize(ctx->stream);
-                ctx->arena.release(d_hist);
-                return fail(ctx, GDG_ERR_HIP, "blend rows: %s", hipGetErrorString(e));
-            }
-        }
-    }
-    std::vector<double> sums((size_t)n_blends * samples);
-    rc = rows_round_trip(ctx, "blend rows", rows, n_rows, samples, sums.data(), sums.size() * sizeof(double), [&](const double *d_rows, void *d_out) {
-        return gdg_blend_rows_filtered_device(ctx, d_rows, samples, n_rows, samples, n_blends, first, channel, weight, delay, tap_first, tap,
-                                              static_cast<const double *>(d_hist), H, static_cast<double *>(d_out), samples);
-    });
-    if (d_hist) {
-        hipStreamSynchronize(ctx->stream);
-        ctx->arena.release(d_hist);
-    }
-    if (rc != GDG_OK) return rc;
-    for (int b = 0; b < n_blends; b++) memcpy(out[b], sums.data() + (size_t)b * samples, samples * sizeof(double));
-    return GDG_OK;
+    return blend_rows_host(ctx, rows, n_rows, samples, n_blends, first, channel, weight, delay, tap_first, tap, history, out);
 }
 
 /* the taps of a fractional delay (blend.h): pure host arithmetic, no context */

@@ -1,10 +1,13 @@
 /*
  * blend.h -- the blend outputs (gdg_batch_set_blends, gdg_blend_rows; include/gdg.h states the arithmetic): a blend is a weighted sum of
  * chain output rows, s = w_0 x[c_0], then s = s + w_k x[c_k] in term order, every product and every add rounded on its own; a term may be
- * delayed by a whole number of samples (gdg_batch_set_blends_delayed) and pass a short FIR of its own (gdg_batch_set_blends_filtered).  Here: the two rounded operations as __host__ __device__ inlines --
- * the kernels of blend_kernels.h use them, and so can a stand-alone host program (tests/native/blend_check.cpp, blend_delay_check.cpp) --
- * the validation of a blend list in its CSR form, the rule by which a list replaces the one in force, the sum on the host, and the planner
- * that turns alignment records into delays and signs (gdg_blend_delays_from_align); and, for the blend fit (include/gdg.h, FIT), the
+ * delayed by a whole number of samples (gdg_batch_set_blends_delayed) and pass a short FIR of its own (gdg_batch_set_blends_filtered).  The
+ * three forms are ONE list with absent parts: here it is validated once (gdg_blend_check, gdg_blend_check_taps) and refused in one set of
+ * words (gdg_blend_list_message, gdg_blend_taps_message), kept as one BlendSet, packed into one table (gdg_blend_pack) that is read through
+ * one view (gdg_blend_view, gdg_blend_view_at) on the host and on the device, and summed on the host by one definition
+ * (gdg_blend_sample_filtered).  Also here: the two rounded operations as __host__ __device__ inlines -- the kernels of blend_kernels.h use
+ * them, and so can a stand-alone host program (tests/native/blend_check.cpp, blend_delay_check.cpp, blend_filter_check.cpp) --, and the
+ * planner that turns alignment records into delays and signs (gdg_blend_delays_from_align); and, for the blend fit (include/gdg.h, FIT), the
  * validation of a list of fits, the table a launch reads, and the planner that turns fit records into weights (gdg_blend_weights_from_fit;
  * tests/native/fit_plan_check.cpp); and, for the Gram of a port list (include/gdg.h, GRAM), the validation of the list, the packed index
  * and the greedy planner that picks ports from Gram records (gdg_blend_pick_from_gram; tests/native/gram_plan_check.cpp).  No HIP header
@@ -132,6 +135,27 @@ static inline int gdg_blend_check_taps(int n_blends, const int *first, const int
     return BLEND_OK;
 }
 
+/* what gdg_blend_check refused, in words, for the call `what`: one text for both callers.  standalone: the channels are the n_channels rows
+ * of a stand-alone call ("blend rows"); otherwise the channels of a context ("set blends"), where 0 blends switch the outputs off */
+static inline void gdg_blend_list_message(char *msg, size_t size, const char *what, bool standalone, int rc, int b, int k, int n_blends, const int *first, const int *channel,
+                                          const double *weight, const int *delay, const double *gain, int n_channels) {
+    const int at = b >= 0 && k >= 0 ? first[b] + k : 0;
+    switch (rc) {
+    case BLEND_COUNT: snprintf(msg, size, "%s: %d blends; 0 %sto %d", what, n_blends, standalone ? "" : "(off) ", GDG_BLEND_MAX_BLENDS); break;
+    case BLEND_NULL: snprintf(msg, size, "%s: %d blends need first, channel and weight", what, n_blends); break;
+    case BLEND_FIRST: snprintf(msg, size, "%s: blend %d: first[%d] = %d, first[%d] = %d; the offsets start at 0 and never descend", what, b, b, first[b], b + 1, first[b + 1]); break;
+    case BLEND_EMPTY: snprintf(msg, size, "%s: blend %d has no term; 1 to %d", what, b, GDG_BLEND_MAX_TERMS); break;
+    case BLEND_TERMS: snprintf(msg, size, "%s: blend %d has %d terms; 1 to %d", what, b, first[b + 1] - first[b], GDG_BLEND_MAX_TERMS); break;
+    case BLEND_CHANNEL:
+        if (standalone) snprintf(msg, size, "%s: blend %d, term %d names row %d of %d", what, b, k, channel[at], n_channels);
+        else snprintf(msg, size, "%s: blend %d, term %d names channel %d, the context has channels 0 to %d", what, b, k, channel[at], n_channels - 1);
+        break;
+    case BLEND_WEIGHT: snprintf(msg, size, "%s: blend %d, term %d: weight = %g is not finite", what, b, k, weight[at]); break;
+    case BLEND_DELAY: snprintf(msg, size, "%s: blend %d, term %d: delay = %d; 0 to %d%s", what, b, k, delay[at], GDG_BLEND_MAX_DELAY, standalone ? "" : " samples"); break;
+    default: snprintf(msg, size, "%s: blend %d: gain = %g is not finite", what, b, gain[b]); break;
+    }
+}
+
 /* what gdg_blend_check_taps refused, in words, for the call `what` ("set blends", "blend rows"): one text for both */
 static inline void gdg_blend_taps_message(char *msg, size_t size, const char *what, int rc, int b, int k, int t, const int *first, const int *delay, const int *tap_first,
                                           const double *tap, int n_blends) {
@@ -147,6 +171,59 @@ static inline void gdg_blend_taps_message(char *msg, size_t size, const char *wh
         snprintf(msg, size, "%s: blend %d, term %d: a delay of %d samples and %d taps reach %d samples back; at most %d", what, b, k, d, T, d + (T > 1 ? T : 1) - 1, GDG_BLEND_MAX_DELAY);
         break;
     }
+}
+
+/* ---- the table a launch reads, and its view ------------------------------------------------------------------------------------------------ */
+/* A checked list as the kernels take it, on the host or on the device.  A null member is an absent part: delay = every delay 0, tap_first and
+ * tap = no term has a tap, gain = every gain 1.0. */
+struct gdg_blend_view {
+    int n_blends;
+    const int *first, *channel;                /* n_blends + 1 offsets; one channel per term */
+    const double *weight, *gain;               /* one per term; one per blend */
+    const int *delay, *tap_first;              /* one per term; one per term and one more */
+    const double *tap;
+};
+
+/* THE layout: first | channel | delay | tap_first | pad to 8 bytes | weight | gain | taps, an absent part taking no room; the doubles are
+ * 8-byte aligned where base is.  The view of a table of n_blends blends and `terms` terms at base -- host bytes or their device copy; base
+ * is never read here --, n_taps < 0: no tap_first and no taps.  *bytes (where asked for): the table's size. */
+static inline gdg_blend_view gdg_blend_view_at(const void *base, int n_blends, int terms, bool delays, int n_taps, bool gains, size_t *bytes = nullptr) {
+    gdg_blend_view v = { n_blends, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    uintptr_t at = (uintptr_t)base;
+    auto take = [&](size_t count, size_t size, bool there) { const uintptr_t p = there ? at : 0; if (there) at += count * size; return p; };
+    if (n_blends > 0) {
+        v.first = (const int *)take((size_t)n_blends + 1, sizeof(int), true);
+        v.channel = (const int *)take((size_t)terms, sizeof(int), true);
+        v.delay = (const int *)take((size_t)terms, sizeof(int), delays);
+        v.tap_first = (const int *)take((size_t)terms + 1, sizeof(int), n_taps >= 0);
+        at += (8 - (at - (uintptr_t)base) % 8) % 8;
+        v.weight = (const double *)take((size_t)terms, sizeof(double), true);
+        v.gain = (const double *)take((size_t)n_blends, sizeof(double), gains);
+        v.tap = (const double *)take((size_t)(n_taps > 0 ? n_taps : 0), sizeof(double), n_taps >= 0);
+    }
+    if (bytes) *bytes = (size_t)(at - (uintptr_t)base);
+    return v;
+}
+
+/* a checked list as the table's bytes; delay, tap_first (with tap) and gain may be null: absent */
+static inline std::vector<unsigned char> gdg_blend_pack(int n_blends, const int *first, const int *channel, const double *weight, const double *gain, const int *delay,
+                                                        const int *tap_first, const double *tap) {
+    std::vector<unsigned char> packed;
+    if (n_blends <= 0) return packed;
+    const int terms = first[n_blends], n_taps = tap_first ? tap_first[terms] : -1;
+    size_t bytes = 0;
+    gdg_blend_view_at(nullptr, n_blends, terms, delay != nullptr, n_taps, gain != nullptr, &bytes);
+    packed.assign(bytes, 0);
+    const gdg_blend_view v = gdg_blend_view_at(packed.data(), n_blends, terms, delay != nullptr, n_taps, gain != nullptr);
+    auto put = [](const void *to, const void *from, size_t n) { if (n) memcpy(const_cast<void *>(to), from, n); };
+    put(v.first, first, ((size_t)n_blends + 1) * sizeof(int));
+    put(v.channel, channel, (size_t)terms * sizeof(int));
+    put(v.weight, weight, (size_t)terms * sizeof(double));
+    if (delay) put(v.delay, delay, (size_t)terms * sizeof(int));
+    if (gain) put(v.gain, gain, (size_t)n_blends * sizeof(double));
+    if (tap_first) put(v.tap_first, tap_first, ((size_t)terms + 1) * sizeof(int));
+    if (n_taps > 0) put(v.tap, tap, (size_t)n_taps * sizeof(double));
+    return packed;
 }
 
 /* the list in force */
@@ -168,22 +245,18 @@ struct BlendSet {
         return m;
     }
     bool unit_gains() const { for (double g : gain) if (g != 1.0) return false; return true; }
-    /* the table as a batch call uploads it, made when the list is taken: first | channel | delay | tap_first | pad to 8 bytes | weight | gain |
-     * taps; the delays are there only while one of them is not 0 or a term has taps, tap_first and the taps only while a term has taps */
+    /* the table as a launch reads it (gdg_blend_pack), made when the list is taken: the delays are there only while one of them is not 0 or a
+     * term has taps, tap_first and the taps only while a term has taps, the gains always */
     std::vector<unsigned char> packed;
-    size_t packed_ints() const { return ((first.size() + channel.size() + delay.size() + tap_first.size()) * sizeof(int) + 7) & ~(size_t)7; }
-    size_t packed_taps() const { return packed_ints() + (weight.size() + gain.size()) * sizeof(double); }      /* where the taps begin */
     void pack() {
-        packed.assign(first.empty() ? 0 : packed_taps() + tap.size() * sizeof(double), 0);
-        if (packed.empty()) return;
-        memcpy(packed.data(), first.data(), first.size() * sizeof(int));
-        memcpy(packed.data() + first.size() * sizeof(int), channel.data(), channel.size() * sizeof(int));
-        if (!delay.empty()) memcpy(packed.data() + (first.size() + channel.size()) * sizeof(int), delay.data(), delay.size() * sizeof(int));
-        memcpy(packed.data() + packed_ints(), weight.data(), weight.size() * sizeof(double));
-        memcpy(packed.data() + packed_ints() + weight.size() * sizeof(double), gain.data(), gain.size() * sizeof(double));
-        if (!tap_first.empty()) memcpy(packed.data() + (first.size() + channel.size() + delay.size()) * sizeof(int), tap_first.data(), tap_first.size() * sizeof(int));
-        if (!tap.empty()) memcpy(packed.data() + packed_taps(), tap.data(), tap.size() * sizeof(double));
+        packed = gdg_blend_pack(count(), first.data(), channel.data(), weight.data(), gain.data(), delay.empty() ? nullptr : delay.data(),
+                                tap_first.empty() ? nullptr : tap_first.data(), tap.data());
     }
+    /* the view of `packed` or of a copy of it at base */
+    gdg_blend_view view(const void *base) const { return gdg_blend_view_at(base, count(), terms(), !delay.empty(), tap_first.empty() ? -1 : (int)tap.size(), true); }
+    /* where the doubles and where the taps begin: the view of a table at address 0 holds offsets */
+    size_t packed_ints() const { return (size_t)(uintptr_t)view(nullptr).weight; }
+    size_t packed_taps() const { return packed_ints() + (weight.size() + gain.size()) * sizeof(double); }
 };
 
 /* whole or not at all: a refused list leaves the one in force as it is */
@@ -223,21 +296,7 @@ static inline int gdg_blend_replace(BlendSet &set, int n_blends, const int *firs
     return gdg_blend_replace(set, n_blends, first, channel, weight, (const int *)nullptr, gain, n_channels, blend, term);
 }
 
-/* the definition on the host: sample i of the blend with terms [k0, k1) over rows[channel][i] */
-static inline double gdg_blend_sample(const double *const *rows, size_t i, const int *channel, const double *weight, int k0, int k1) {
-    double s = gdg_blend_mul(weight[k0], rows[channel[k0]][i]);
-    for (int k = k0 + 1; k < k1; k++) s = gdg_blend_add(s, gdg_blend_mul(weight[k], rows[channel[k]][i]));
-    return s;
-}
-
-/* a checked list over `samples` samples of every row: out[b][i] */
-static inline void gdg_blend_sum_host(const double *const *rows, size_t samples, int n_blends, const int *first, const int *channel, const double *weight,
-                                      double *const *out) {
-    for (int b = 0; b < n_blends; b++)
-        for (size_t i = 0; i < samples; i++) out[b][i] = gdg_blend_sample(rows, i, channel, weight, first[b], first[b + 1]);
-}
-
-/* ---- delayed terms (include/gdg.h, BLEND: x_k[i] = x[c_k][i - d_k], +0.0 in front of the job) ------------------------------------------- */
+/* ---- the sum on the host: ONE definition (include/gdg.h, BLEND, DELAYS, FILTERS) --------------------------------------------------------------- */
 /* sample i - d of a row; what lies in front of its sample 0 is `history` -- GDG_BLEND_MAX_DELAY doubles, the last of them sample -1 -- or,
  * without one, +0.0 */
 static inline double gdg_blend_delayed_x(const double *row, const double *history, size_t i, int d) {
@@ -245,23 +304,9 @@ static inline double gdg_blend_delayed_x(const double *row, const double *histor
     return history ? history[(size_t)GDG_BLEND_MAX_DELAY + i - (size_t)d] : 0.0;
 }
 
-/* the definition on the host: history = one run per row, or null; delay = one per term, or null */
-static inline double gdg_blend_sample_delayed(const double *const *rows, const double *const *history, size_t i, const int *channel, const double *weight,
-                                              const int *delay, int k0, int k1) {
-    auto x = [&](int k) { return gdg_blend_delayed_x(rows[channel[k]], history ? history[channel[k]] : nullptr, i, delay ? delay[k] : 0); };
-    double s = gdg_blend_mul(weight[k0], x(k0));
-    for (int k = k0 + 1; k < k1; k++) s = gdg_blend_add(s, gdg_blend_mul(weight[k], x(k)));
-    return s;
-}
-
-static inline void gdg_blend_sum_host_delayed(const double *const *rows, const double *const *history, size_t samples, int n_blends, const int *first,
-                                              const int *channel, const double *weight, const int *delay, double *const *out) {
-    for (int b = 0; b < n_blends; b++)
-        for (size_t i = 0; i < samples; i++) out[b][i] = gdg_blend_sample_delayed(rows, history, i, channel, weight, delay, first[b], first[b + 1]);
-}
-
-/* ---- filtered terms (include/gdg.h, FILTERS: x_k[i] = h_k[0] x[c_k][i - d_k], then + h_k[t] x[c_k][i - d_k - t] in ascending t) ------------------ */
-/* the definition on the host: tap_first = one offset per term and one more, or null (no taps: the delayed sum) */
+/* sample i of the blend with terms [k0, k1): x_k[i] = x[c_k][i - d_k], or through its taps h_k[0] x[c_k][i - d_k], then + h_k[t] x[c_k][i -
+ * d_k - t] in ascending t.  history = one run per row, or null; delay = one per term, or null (all 0); tap_first = one offset per term and
+ * one more, or null (no taps).  A term with T == 0 is the delayed sample, and with d == 0 the row's own: the bits of the sums without */
 static inline double gdg_blend_sample_filtered(const double *const *rows, const double *const *history, size_t i, const int *channel, const double *weight,
                                                const int *delay, const int *tap_first, const double *tap, int k0, int k1) {
     auto x = [&](int k) {
@@ -278,12 +323,30 @@ static inline double gdg_blend_sample_filtered(const double *const *rows, const 
     return s;
 }
 
+/* a checked list over `samples` samples of every row: out[b][i] */
 static inline void gdg_blend_sum_host_filtered(const double *const *rows, const double *const *history, size_t samples, int n_blends, const int *first,
                                                const int *channel, const double *weight, const int *delay, const int *tap_first, const double *tap,
                                                double *const *out) {
     for (int b = 0; b < n_blends; b++)
         for (size_t i = 0; i < samples; i++)
             out[b][i] = gdg_blend_sample_filtered(rows, history, i, channel, weight, delay, tap_first, tap, first[b], first[b + 1]);
+}
+
+/* the names of the list without taps, and without delays as well */
+static inline double gdg_blend_sample_delayed(const double *const *rows, const double *const *history, size_t i, const int *channel, const double *weight,
+                                              const int *delay, int k0, int k1) {
+    return gdg_blend_sample_filtered(rows, history, i, channel, weight, delay, nullptr, nullptr, k0, k1);
+}
+static inline void gdg_blend_sum_host_delayed(const double *const *rows, const double *const *history, size_t samples, int n_blends, const int *first,
+                                              const int *channel, const double *weight, const int *delay, double *const *out) {
+    gdg_blend_sum_host_filtered(rows, history, samples, n_blends, first, channel, weight, delay, nullptr, nullptr, out);
+}
+static inline double gdg_blend_sample(const double *const *rows, size_t i, const int *channel, const double *weight, int k0, int k1) {
+    return gdg_blend_sample_filtered(rows, nullptr, i, channel, weight, nullptr, nullptr, nullptr, k0, k1);
+}
+static inline void gdg_blend_sum_host(const double *const *rows, size_t samples, int n_blends, const int *first, const int *channel, const double *weight,
+                                      double *const *out) {
+    gdg_blend_sum_host_filtered(rows, nullptr, samples, n_blends, first, channel, weight, nullptr, nullptr, nullptr, out);
 }
 
 /* ---- the taps of a fractional delay (gdg_blend_fraction_taps) ---------------------------------------------------------------------------- */

@@ -1,9 +1,12 @@
 /*
- * blend_kernels.h -- the blend outputs (include/gdg.h, gdg_batch_set_blends and gdg_blend_rows): row b of `out` is the
- * weighted sum of blend b's terms over the rows of `rows`, s = w_0 x[c_0] and then s = s + w_k x[c_k] in term order, every product and every
- * add rounded on its own (blend.h).  No reference counterpart; included by io.hip next to the record kernels and compiled like them without
- * contraction.
+ * blend_kernels.h -- the blend outputs (include/gdg.h, gdg_batch_set_blends and gdg_blend_rows): row b of
+ * `out` is the weighted sum of blend b's terms over the rows of `rows`, s = w_0 x[c_0] and then s = s + w_k x[c_k] in term order, every
+ * product and every add rounded on its own (blend.h).  Three kernels -- plain terms, delayed terms, filtered terms -- behind ONE launcher,
+ * gdg_launch_blend at the end of this file, which takes the table as a gdg_blend_view and picks the kernel by what the view holds; the plain
+ * and the delayed kernel share one term loop (blend_terms) and differ in how a term is loaded.  No reference counterpart; included by io.hip
+ * next to the record kernels and compiled like them without contraction.
  *
+ * The plain kernel:
  * blockIdx.y = the blend, blockIdx.x covers the live width.  A lane takes one 16-byte pair of samples where the launcher has seen that every
  * row of both sides starts 16-byte aligned (VEC), one 8-byte sample otherwise; a VEC launch's last lane takes the odd sample of an odd
  * width by the 8-byte path.  A lane reads and writes only inside [0, samples) of a row.  The term table -- first, channel, weight -- is
@@ -23,12 +26,10 @@ template <> struct blend_ops<v2d> {
     static __device__ __forceinline__ v2d add(v2d s, v2d p) { const v2d r = { gdg_blend_add(s.x, p.x), gdg_blend_add(s.y, p.y) }; return r; }
 };
 
-/* the terms [k0, k1) at sample `at` of every row (T = v2d: the pair at, at + 1) */
-template <typename T>
-__device__ __forceinline__ void blend_terms(const double *rows, size_t row_stride, size_t at, const int *__restrict__ channel, const double *__restrict__ weight,
-                                            int k0, int k1, double *dst) {
+/* the terms [k0, k1) at sample `at` (T = v2d: the pair at, at + 1); load(k): term k's sample or pair */
+template <typename T, typename Load>
+__device__ __forceinline__ void blend_terms(size_t at, const double *__restrict__ weight, int k0, int k1, double *dst, Load load) {
     typedef blend_ops<T> op;
-    auto load = [&](int k) { return *reinterpret_cast<const T *>(rows + (size_t)channel[k] * row_stride + at); };
     int k = k0;
     T s = op::mul(weight[k], load(k));
     k++;
@@ -43,6 +44,13 @@ __device__ __forceinline__ void blend_terms(const double *rows, size_t row_strid
     *reinterpret_cast<T *>(dst + at) = s;
 }
 
+/* plain terms: sample `at` of row channel[k] */
+template <typename T>
+__device__ __forceinline__ void blend_row_terms(const double *rows, size_t row_stride, size_t at, const int *__restrict__ channel, const double *__restrict__ weight,
+                                                int k0, int k1, double *dst) {
+    blend_terms<T>(at, weight, k0, k1, dst, [&](int k) { return *reinterpret_cast<const T *>(rows + (size_t)channel[k] * row_stride + at); });
+}
+
 template <bool VEC>
 __global__ void __launch_bounds__(BLEND_T)
 blend_rows_kernel(const double *rows, size_t row_stride, size_t samples, const int *__restrict__ first, const int *__restrict__ channel,
@@ -51,25 +59,8 @@ blend_rows_kernel(const double *rows, size_t row_stride, size_t samples, const i
     double *dst = out + (size_t)blockIdx.y * out_stride;
     const size_t at = ((size_t)blockIdx.x * BLEND_T + threadIdx.x) * (VEC ? 2 : 1);
     if (at >= samples) return;
-    if (VEC && at + 1 < samples) blend_terms<v2d>(rows, row_stride, at, channel, weight, k0, k1, dst);
-    else blend_terms<double>(rows, row_stride, at, channel, weight, k0, k1, dst);
-}
-
-/* d_out: [n_blends][out_stride]; row r at d_rows + r * row_stride.  The term table lies in device memory: d_first[n_blends + 1],
- * d_channel and d_weight [d_first[n_blends]], checked by the caller (blend.h: every channel a row of d_rows, 1 to 32 terms a blend). */
-hipError_t gdg_launch_blend_rows(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
-                                 const double *d_weight, double *d_out, size_t out_stride, hipStream_t s) {
-    if (n_blends == 0 || samples == 0) return hipSuccess;
-    if (!d_rows || !d_out || !d_first || !d_channel || !d_weight || row_stride < samples || out_stride < samples || n_blends > 65535u ||
-        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_weight & 7) || ((uintptr_t)d_first & 3) || ((uintptr_t)d_channel & 3))
-        return hipErrorInvalidValue;
-    const bool vec = !((uintptr_t)d_rows & 15) && !(row_stride & 1) && !((uintptr_t)d_out & 15) && !(out_stride & 1);
-    const size_t lanes = vec ? (samples + 1) / 2 : samples, tiles = (lanes + BLEND_T - 1) / BLEND_T;
-    if (tiles > 0x7fffffffu) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)tiles, n_blends);
-    if (vec) blend_rows_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_out, out_stride);
-    else blend_rows_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_out, out_stride);
-    return hipGetLastError();
+    if (VEC && at + 1 < samples) blend_row_terms<v2d>(rows, row_stride, at, channel, weight, k0, k1, dst);
+    else blend_row_terms<double>(rows, row_stride, at, channel, weight, k0, k1, dst);
 }
 
 /*
@@ -113,25 +104,12 @@ template <bool HIST> struct blend_delayed_load<v2d, HIST> {
     }
 };
 
-/* the terms [k0, k1) at sample `at` (T = v2d: the pair at, at + 1) */
+/* delayed terms: sample `at` - delay[k] of row channel[k] */
 template <typename T, bool HIST>
 __device__ __forceinline__ void blend_delayed_terms(const double *rows, size_t row_stride, const double *history, size_t hist_stride, size_t at,
                                                     const int *__restrict__ channel, const double *__restrict__ weight, const int *__restrict__ delay, int k0, int k1,
                                                     double *dst) {
-    typedef blend_ops<T> op;
-    auto load = [&](int k) { return blend_delayed_load<T, HIST>::at(rows, row_stride, history, hist_stride, channel[k], at, delay[k]); };
-    int k = k0;
-    T s = op::mul(weight[k], load(k));
-    k++;
-    for (; k + 4 <= k1; k += 4) {
-        const T x0 = load(k), x1 = load(k + 1), x2 = load(k + 2), x3 = load(k + 3);
-        s = op::add(s, op::mul(weight[k], x0));
-        s = op::add(s, op::mul(weight[k + 1], x1));
-        s = op::add(s, op::mul(weight[k + 2], x2));
-        s = op::add(s, op::mul(weight[k + 3], x3));
-    }
-    for (; k < k1; k++) s = op::add(s, op::mul(weight[k], load(k)));
-    *reinterpret_cast<T *>(dst + at) = s;
+    blend_terms<T>(at, weight, k0, k1, dst, [&](int k) { return blend_delayed_load<T, HIST>::at(rows, row_stride, history, hist_stride, channel[k], at, delay[k]); });
 }
 
 template <bool VEC>
@@ -150,27 +128,6 @@ blend_delayed_kernel(const double *rows, size_t row_stride, size_t samples, cons
         if (pair) blend_delayed_terms<v2d, true>(rows, row_stride, history, hist_stride, at, channel, weight, delay, k0, k1, dst);
         else blend_delayed_terms<double, true>(rows, row_stride, history, hist_stride, at, channel, weight, delay, k0, k1, dst);
     }
-}
-
-/* as gdg_launch_blend_rows, with d_delay[d_first[n_blends]] (every one in 0 .. GDG_BLEND_MAX_DELAY, checked by the caller) and d_history:
- * null (+0.0 in front of sample 0) or row r's GDG_BLEND_MAX_DELAY samples in front of sample 0 at d_history + r * hist_stride; read, never
- * written.  d_out overlaps neither the rows nor the history. */
-hipError_t gdg_launch_blend_rows_delayed(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
-                                         const double *d_weight, const int *d_delay, const double *d_history, size_t hist_stride, double *d_out, size_t out_stride,
-                                         hipStream_t s) {
-    if (n_blends == 0 || samples == 0) return hipSuccess;
-    if (!d_rows || !d_out || !d_first || !d_channel || !d_weight || !d_delay || row_stride < samples || out_stride < samples || n_blends > 65535u ||
-        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_weight & 7) || ((uintptr_t)d_first & 3) || ((uintptr_t)d_channel & 3) ||
-        ((uintptr_t)d_delay & 3) || (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY)))
-        return hipErrorInvalidValue;
-    const bool vec = !((uintptr_t)d_rows & 15) && !(row_stride & 1) && !((uintptr_t)d_out & 15) && !(out_stride & 1) &&
-                     (!d_history || (!((uintptr_t)d_history & 15) && !(hist_stride & 1)));
-    const size_t lanes = vec ? (samples + 1) / 2 : samples, tiles = (lanes + BLEND_T - 1) / BLEND_T;
-    if (tiles > 0x7fffffffu) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)tiles, n_blends);
-    if (vec) blend_delayed_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_history, hist_stride, d_out, out_stride);
-    else blend_delayed_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_history, hist_stride, d_out, out_stride);
-    return hipGetLastError();
 }
 
 /* The history of the next launch: the last GDG_BLEND_MAX_DELAY of `samples` samples of rows 0 .. n_rows - 1 go to d_history[r][GDG_BLEND_MAX_DELAY],
@@ -343,28 +300,35 @@ blend_filtered_kernel(const double *rows, size_t row_stride, size_t samples, con
         blend_filtered_tile<VEC, true>(rows, row_stride, samples, channel, weight, delay, tap_first, tap, history, hist_stride, k0, k1, tile, dst, win);
 }
 
-/* as gdg_launch_blend_rows_delayed, with d_tap_first[d_first[n_blends] + 1] and the taps d_tap (8-byte aligned); every term's d + max(T, 1) - 1
- * is at most GDG_BLEND_MAX_DELAY and every T at most GDG_BLEND_MAX_TAPS (checked by the caller).  A table without taps -- d_tap_first null --
- * is the delayed launch, and without delays as well the plain one: the same kernels as before filters existed. */
-hipError_t gdg_launch_blend_rows_filtered(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
-                                          const double *d_weight, const int *d_delay, const int *d_tap_first, const double *d_tap, const double *d_history,
-                                          size_t hist_stride, double *d_out, size_t out_stride, hipStream_t s) {
-    if (!d_tap_first) {
-        if (!d_delay) return gdg_launch_blend_rows(d_rows, row_stride, samples, n_blends, d_first, d_channel, d_weight, d_out, out_stride, s);
-        return gdg_launch_blend_rows_delayed(d_rows, row_stride, samples, n_blends, d_first, d_channel, d_weight, d_delay, d_history, hist_stride, d_out, out_stride, s);
-    }
-    if (n_blends == 0 || samples == 0) return hipSuccess;
-    if (!d_rows || !d_out || !d_first || !d_channel || !d_weight || !d_delay || !d_tap || row_stride < samples || out_stride < samples || n_blends > 65535u ||
-        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_weight & 7) || ((uintptr_t)d_tap & 7) || ((uintptr_t)d_first & 3) ||
-        ((uintptr_t)d_channel & 3) || ((uintptr_t)d_delay & 3) || ((uintptr_t)d_tap_first & 3) ||
+/* THE launcher (gdg_internal.h).  d_out: [n_blends][out_stride]; row r at d_rows + r * row_stride.  The table lies in device memory and has
+ * been checked by the caller (blend.h: every channel a row of d_rows, 1 to 32 terms a blend, every delay in 0 .. GDG_BLEND_MAX_DELAY, every
+ * T at most GDG_BLEND_MAX_TAPS, every d + max(T, 1) - 1 at most GDG_BLEND_MAX_DELAY).  The kernel by what the view holds: taps = filtered,
+ * else delays = delayed, else plain -- and the plain kernel reads no history, so none counts there.  d_history: null (+0.0 in front of
+ * sample 0) or row r's GDG_BLEND_MAX_DELAY samples in front of sample 0 at d_history + r * hist_stride; read, never written.  d_out overlaps
+ * neither the rows nor the history.  A lane takes 16 bytes where every base and stride the kernel reads allows it. */
+hipError_t gdg_launch_blend(const gdg_blend_view &v, const double *d_rows, size_t row_stride, size_t samples, const double *d_history, size_t hist_stride, double *d_out,
+                            size_t out_stride, hipStream_t s) {
+    if (v.n_blends <= 0 || samples == 0) return hipSuccess;
+    if (!v.delay) d_history = nullptr;
+    if (!d_rows || !d_out || !v.first || !v.channel || !v.weight || (v.tap_first && (!v.delay || !v.tap)) || row_stride < samples || out_stride < samples ||
+        v.n_blends > 65535 || ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)v.weight & 7) || ((uintptr_t)v.tap & 7) || ((uintptr_t)v.first & 3) ||
+        ((uintptr_t)v.channel & 3) || ((uintptr_t)v.delay & 3) || ((uintptr_t)v.tap_first & 3) ||
         (d_history && (((uintptr_t)d_history & 7) || hist_stride < (size_t)GDG_BLEND_MAX_DELAY)))
         return hipErrorInvalidValue;
     const bool vec = !((uintptr_t)d_rows & 15) && !(row_stride & 1) && !((uintptr_t)d_out & 15) && !(out_stride & 1) &&
                      (!d_history || (!((uintptr_t)d_history & 15) && !(hist_stride & 1)));
     const size_t lanes = vec ? (samples + 1) / 2 : samples, tiles = (lanes + BLEND_T - 1) / BLEND_T;
     if (tiles > 0x7fffffffu) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)tiles, n_blends);
-    if (vec) blend_filtered_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_tap_first, d_tap, d_history, hist_stride, d_out, out_stride);
-    else blend_filtered_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, d_first, d_channel, d_weight, d_delay, d_tap_first, d_tap, d_history, hist_stride, d_out, out_stride);
+    const dim3 grid((unsigned)tiles, (unsigned)v.n_blends);
+    if (v.tap_first) {
+        if (vec) blend_filtered_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, v.first, v.channel, v.weight, v.delay, v.tap_first, v.tap, d_history, hist_stride, d_out, out_stride);
+        else blend_filtered_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, v.first, v.channel, v.weight, v.delay, v.tap_first, v.tap, d_history, hist_stride, d_out, out_stride);
+    } else if (v.delay) {
+        if (vec) blend_delayed_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, v.first, v.channel, v.weight, v.delay, d_history, hist_stride, d_out, out_stride);
+        else blend_delayed_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, v.first, v.channel, v.weight, v.delay, d_history, hist_stride, d_out, out_stride);
+    } else {
+        if (vec) blend_rows_kernel<true><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, v.first, v.channel, v.weight, d_out, out_stride);
+        else blend_rows_kernel<false><<<grid, BLEND_T, 0, s>>>(d_rows, row_stride, samples, v.first, v.channel, v.weight, d_out, out_stride);
+    }
     return hipGetLastError();
 }

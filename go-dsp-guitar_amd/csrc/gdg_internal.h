@@ -355,22 +355,15 @@ hipError_t gdg_launch_block_align(const double *d_rows, size_t row_stride, unsig
  * n_rows rows one gdg_block_true_peak into d_records[r][ceil(samples / 8192)]; taps: the table of true_peak_taps.h, passed by value */
 hipError_t gdg_launch_block_true_peak(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, const gdg_true_peak_table &taps, void *d_records,
                                       hipStream_t s);
-/* the blend outputs (include/gdg.h; io.hip, blend_kernels.h; the arithmetic: blend.h): row b of d_out (row b at d_out + b * out_stride) is the sum of
- * blend b's terms d_first[b] .. d_first[b + 1] over `samples` samples of the rows of d_rows, in term order.  The table lies in device memory and
- * has been checked by the caller: every channel a row of d_rows, 1 to 32 terms a blend.  Rows 8-byte aligned, strides >= samples. */
-hipError_t gdg_launch_blend_rows(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
-                                 const double *d_weight, double *d_out, size_t out_stride, hipStream_t s);
-/* ... with one delay per term, d_delay[d_first[n_blends]], each in 0 .. GDG_BLEND_MAX_DELAY (checked by the caller): term k reads sample i - d_k.
+/* the blend outputs (include/gdg.h; io.hip, blend_kernels.h; the arithmetic, the table and its view: blend.h): row b of d_out (row b at d_out + b *
+ * out_stride) is the sum of blend b's terms over `samples` samples of the rows of d_rows, in term order.  The view's table lies in device memory
+ * and has been checked by the caller.  The kernel by what the view holds: taps = filtered terms, else delays = delayed terms, else plain ones.
  * d_history: null (+0.0 in front of sample 0) or, per row, the GDG_BLEND_MAX_DELAY samples in front of sample 0 at d_history + r * hist_stride
- * (hist_stride >= GDG_BLEND_MAX_DELAY, 8-byte aligned); read, never written.  d_out overlaps neither. */
-hipError_t gdg_launch_blend_rows_delayed(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
-                                         const double *d_weight, const int *d_delay, const double *d_history, size_t hist_stride, double *d_out, size_t out_stride,
-                                         hipStream_t s);
-/* ... and with a short FIR per term (include/gdg.h, FILTERS): term k's taps are d_tap[d_tap_first[k] .. d_tap_first[k + 1]), at most GDG_BLEND_MAX_TAPS,
- * and d_k + max(T_k, 1) - 1 <= GDG_BLEND_MAX_DELAY (checked by the caller).  d_tap_first null: the delayed launch; d_delay null as well: the plain one. */
-hipError_t gdg_launch_blend_rows_filtered(const double *d_rows, size_t row_stride, size_t samples, unsigned n_blends, const int *d_first, const int *d_channel,
-                                          const double *d_weight, const int *d_delay, const int *d_tap_first, const double *d_tap, const double *d_history,
-                                          size_t hist_stride, double *d_out, size_t out_stride, hipStream_t s);
+ * (hist_stride >= GDG_BLEND_MAX_DELAY); read, never written, and not looked at without delays.  Rows 8-byte aligned, strides >= samples;
+ * d_out overlaps neither the rows nor the history. */
+struct gdg_blend_view;
+hipError_t gdg_launch_blend(const gdg_blend_view &view, const double *d_rows, size_t row_stride, size_t samples, const double *d_history, size_t hist_stride,
+                            double *d_out, size_t out_stride, hipStream_t s);
 /* the last GDG_BLEND_MAX_DELAY of `samples` samples (samples >= GDG_BLEND_MAX_DELAY) of rows 0 .. n_rows - 1 into d_history[n_rows][GDG_BLEND_MAX_DELAY] */
 hipError_t gdg_launch_blend_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
 /* the blend fit's records (include/gdg.h, FIT; io.hip, fit_kernels.h): per fit and block of `block` samples (the last of a row may be short)

@@ -2,8 +2,10 @@
  * delayed table byte for byte, and so does a list whose every term has no tap; a list with taps packs first | channel | delay | tap_first |
  * weight | gain | taps; every refusal of the taps names blend and term and leaves the list in force as it was; the filtered sum on the host
  * against the known answer of include/gdg.h; the taps of a fractional delay; and the planner that picks the fraction from fit records -- the
- * winner, the tie rule, silent candidates, the refusals.  No device, no context. */
+ * winner, the tie rule, silent candidates, the refusals; the one table and its view over every list shape, the bytes the batch uploads against a
+ * literal, and the plain and delayed host sums as the filtered one with absent arguments.  No device, no context. */
 #include "blend.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +22,115 @@ static gdg_blend_fit_rec fit_rec(int K, double tt, const double *tx, const doubl
     r.terms = (uint32_t)K;
     for (int k = 0; k < K; k++) { r.tx[k] = tx[k]; r.xx[k * (k + 1) / 2 + k] = xx[k]; }
     return r;
+}
+
+/* ---- one table, one view (blend.h: gdg_blend_pack, gdg_blend_view_at, BlendSet::pack) ---- */
+/* a list of the given term counts with T taps on every term (T < 0: no tap_first), packed with and without each optional part: the view of
+ * the bytes points at values equal to the inputs, every double is 8-byte aligned, and the last byte read is the buffer's last */
+static void pack_and_view(const std::vector<int> &terms_of, int T, bool with_delay, bool with_gain) {
+    const int n_blends = (int)terms_of.size();
+    std::vector<int> first(1, 0), channel, delay, tap_first(1, 0);
+    std::vector<double> weight, gain, tap;
+    for (int b = 0; b < n_blends; b++) {
+        for (int k = 0; k < terms_of[(size_t)b]; k++) {
+            channel.push_back((b + 3 * k) % 5);
+            weight.push_back(0.25 * (double)(k + 1) - (double)b);
+            delay.push_back((7 * k + b) % (GDG_BLEND_MAX_DELAY - 64));
+            for (int t = 0; t < (T > 0 ? T : 0); t++) tap.push_back(1.0 / (double)(1 + t + k));
+            tap_first.push_back((int)tap.size());
+        }
+        first.push_back((int)channel.size());
+        gain.push_back(0.5 + (double)b);
+    }
+    const int terms = (int)channel.size();
+    tap.push_back(9.0);                                                      /* a spare entry: a list without a tap still has an address */
+    const std::vector<unsigned char> bytes = gdg_blend_pack(n_blends, first.data(), channel.data(), weight.data(), with_gain ? gain.data() : nullptr,
+                                                            with_delay ? delay.data() : nullptr, T >= 0 ? tap_first.data() : nullptr, tap.data());
+    size_t size = 0;
+    const gdg_blend_view v = gdg_blend_view_at(bytes.data(), n_blends, terms, with_delay, T >= 0 ? tap_first[(size_t)terms] : -1, with_gain, &size);
+    CHECK(size == bytes.size() && v.n_blends == n_blends);
+    CHECK(v.first && v.channel && v.weight && !memcmp(v.first, first.data(), first.size() * sizeof(int)) && !memcmp(v.channel, channel.data(), channel.size() * sizeof(int)) &&
+          !memcmp(v.weight, weight.data(), weight.size() * sizeof(double)));
+    CHECK(with_delay ? v.delay && !memcmp(v.delay, delay.data(), delay.size() * sizeof(int)) : !v.delay);
+    CHECK(with_gain ? v.gain && !memcmp(v.gain, gain.data(), gain.size() * sizeof(double)) : !v.gain);
+    CHECK(T >= 0 ? v.tap_first && v.tap && !memcmp(v.tap_first, tap_first.data(), tap_first.size() * sizeof(int)) && !memcmp(v.tap, tap.data(), (tap.size() - 1) * sizeof(double))
+                 : !v.tap_first && !v.tap);
+    CHECK((uintptr_t)bytes.data() % 8 == 0 && (uintptr_t)v.weight % 8 == 0 && (uintptr_t)v.gain % 8 == 0 && (uintptr_t)v.tap % 8 == 0);
+    /* the last part that is there ends where the buffer ends, and the first begins where it begins */
+    const unsigned char *end = T >= 0 ? (const unsigned char *)(v.tap + (tap.size() - 1)) : with_gain ? (const unsigned char *)(v.gain + n_blends) : (const unsigned char *)(v.weight + terms);
+    CHECK(end == bytes.data() + bytes.size() && (const unsigned char *)v.first == bytes.data());
+}
+
+static void one_table_one_view() {
+    const std::vector<std::vector<int>> shapes = { { 1 }, { 32, 1, 5 } };
+    for (const std::vector<int> &terms_of : shapes)
+        for (int gains = 0; gains < 2; gains++) {
+            pack_and_view(terms_of, -1, false, gains);                        /* plain */
+            pack_and_view(terms_of, -1, true, gains);                         /* delays only */
+            for (int T : { 0, 1, 2, 63, 64 }) {
+                pack_and_view(terms_of, T, false, gains);                     /* taps, delays absent */
+                pack_and_view(terms_of, T, true, gains);
+            }
+        }
+    size_t size = 9;
+    const gdg_blend_view none = gdg_blend_view_at(nullptr, 0, 0, false, -1, false, &size);
+    CHECK(size == 0 && !none.first && !none.weight && gdg_blend_pack(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr).empty());
+    /* the layout the batch uploads, byte for byte (little-endian): first | channel | delay | tap_first | pad to 8 | weight | gain | taps */
+    const int first[3] = { 0, 2, 3 }, channel[3] = { 0, 1, 2 }, delay[3] = { 0, 7, 1 }, tap_first[4] = { 0, 2, 2, 5 };
+    const double weight[3] = { 1.0, -1.0, 0.5 }, gain[2] = { 1.0, 2.0 }, tap[5] = { 1.0, -1.0, 0.25, 0.0, -0.5 };
+    int b = 0, k = 0;
+    BlendSet set;
+    CHECK(gdg_blend_replace(set, 2, first, channel, weight, delay, tap_first, tap, gain, 3, &b, &k) == BLEND_OK);
+#define I32(v) (v), 0, 0, 0
+#define F64(hi, lo) 0, 0, 0, 0, 0, 0, (lo), (hi)
+    const unsigned char want[] = { I32(0), I32(2), I32(3), I32(0), I32(1), I32(2), I32(0), I32(7), I32(1), I32(0), I32(2), I32(2), I32(5), 0, 0, 0, 0,
+                                   F64(0x3f, 0xf0), F64(0xbf, 0xf0), F64(0x3f, 0xe0),                                    /* 1.0, -1.0, 0.5 */
+                                   F64(0x3f, 0xf0), F64(0x40, 0x00),                                                     /* 1.0, 2.0 */
+                                   F64(0x3f, 0xf0), F64(0xbf, 0xf0), F64(0x3f, 0xd0), F64(0x00, 0x00), F64(0xbf, 0xe0) };  /* 1.0, -1.0, 0.25, 0.0, -0.5 */
+    CHECK(set.packed.size() == sizeof want && !memcmp(set.packed.data(), want, sizeof want));
+    /* without taps, and without delays: the same bytes with those parts gone -- 9 ints and 4 bytes of pad, 6 ints */
+    CHECK(gdg_blend_replace(set, 2, first, channel, weight, delay, nullptr, nullptr, gain, 3, &b, &k) == BLEND_OK);
+    CHECK(set.packed.size() == 40 + 40 && !memcmp(set.packed.data(), want, 36) && !memcmp(set.packed.data() + 40, want + 56, 40));
+    CHECK(gdg_blend_replace(set, 2, first, channel, weight, gain, 3, &b, &k) == BLEND_OK);
+    CHECK(set.packed.size() == 24 + 40 && !memcmp(set.packed.data(), want, 24) && !memcmp(set.packed.data() + 24, want + 56, 40));
+#undef I32
+#undef F64
+    /* the view of the set is the view of its bytes, wherever they lie */
+    CHECK(gdg_blend_replace(set, 2, first, channel, weight, delay, tap_first, tap, gain, 3, &b, &k) == BLEND_OK);
+    const gdg_blend_view v = set.view(set.packed.data());
+    CHECK(v.n_blends == 2 && v.delay[1] == 7 && v.tap_first[3] == 5 && v.weight[2] == 0.5 && v.gain[1] == 2.0 && v.tap[4] == -0.5);
+}
+
+/* ---- one host definition: the plain and the delayed names are the filtered sum with the absent arguments null, bit for bit ---- */
+static void one_host_definition() {
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    const size_t samples = 257;
+    std::vector<std::vector<double>> x(3, std::vector<double>(samples)), hist(3, std::vector<double>((size_t)GDG_BLEND_MAX_DELAY));
+    uint64_t state = 88172645463325252ull;
+    auto next = [&]() { state ^= state << 13; state ^= state >> 7; state ^= state << 17; return (double)(int64_t)(state >> 11) / 4503599627370496.0 - 1.0; };
+    for (int r = 0; r < 3; r++) {
+        for (double &v : x[(size_t)r]) v = next();
+        for (double &v : hist[(size_t)r]) v = next();
+    }
+    x[0][5] = inf; x[1][9] = -inf; x[2][11] = nan; x[0][13] = -0.0; x[1][13] = -0.0; x[2][200] = inf;      /* row 2 carries the zero weight */
+    hist[1][(size_t)GDG_BLEND_MAX_DELAY - 1] = inf; hist[2][(size_t)GDG_BLEND_MAX_DELAY - 2] = nan;
+    const double *rows[3] = { x[0].data(), x[1].data(), x[2].data() }, *hs[3] = { hist[0].data(), hist[1].data(), hist[2].data() };
+    const int first[3] = { 0, 5, 6 }, channel[6] = { 0, 1, 2, 1, 0, 2 }, delay[6] = { 0, 1, 3, 256, 2, 0 };
+    const double weight[6] = { 0.75, -1.25, 0.0, 1e-3, -0.0, 1.0 };
+    std::vector<double> a(2 * samples), c(2 * samples);
+    double *oa[2] = { a.data(), a.data() + samples }, *oc[2] = { c.data(), c.data() + samples };
+    gdg_blend_sum_host(rows, samples, 2, first, channel, weight, oa);
+    gdg_blend_sum_host_filtered(rows, nullptr, samples, 2, first, channel, weight, nullptr, nullptr, nullptr, oc);
+    CHECK(!memcmp(a.data(), c.data(), a.size() * sizeof(double)));
+    CHECK(std::isnan(a[200]) && std::isnan(a[5]) && std::isinf(a[samples + 200]));      /* 0.0 * inf; inf + -0.0 * inf; 1.0 * inf */
+    for (const double *const *h : { (const double *const *)nullptr, (const double *const *)hs })
+        for (const int *d : { (const int *)delay, (const int *)nullptr }) {
+            gdg_blend_sum_host_delayed(rows, h, samples, 2, first, channel, weight, d, oa);
+            gdg_blend_sum_host_filtered(rows, h, samples, 2, first, channel, weight, d, nullptr, nullptr, oc);
+            CHECK(!memcmp(a.data(), c.data(), a.size() * sizeof(double)));
+        }
+    for (size_t i = 0; i < samples; i += 50)
+        CHECK(gdg_blend_sample(rows, i, channel, weight, 0, 5) == gdg_blend_sample_delayed(rows, hs, i, channel, weight, nullptr, 0, 5) || std::isnan(gdg_blend_sample(rows, i, channel, weight, 0, 5)));
 }
 
 int main() {
@@ -184,6 +295,8 @@ int main() {
         CHECK(step[0] == 9 && step[1] == 9);
         CHECK(gdg_blend_plan_fractions(nullptr, 0, 0, 2, nullptr, &b) == FRACTION_OK);
     }
+    one_table_one_view();
+    one_host_definition();
     if (failures) { printf("FAILED %d checks\n", failures); return 1; }
     printf("OK\n");
     return 0;

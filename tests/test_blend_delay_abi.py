@@ -99,7 +99,7 @@ def test_every_layer_knows_the_calls(pkg):
     assert "hip/hip_runtime" not in plain and "BLEND_DELAY" in plain and "gdg_blend_plan_delays" in plain
     with open(os.path.join(CSRC, "blend_kernels.h")) as f:
         kernels = f.read()
-    assert "blend_delayed_kernel" in kernels and "blend_history_save_kernel" in kernels and "gdg_launch_blend_rows_delayed" in kernels
+    assert "blend_delayed_kernel" in kernels and "blend_history_save_kernel" in kernels and "gdg_launch_blend(" in kernels
     base = os.path.dirname(os.path.dirname(pkg.LIB_PATH))
     with open(os.path.join(base, "go", "gdg", "gdg.go")) as f:
         go = f.read()
