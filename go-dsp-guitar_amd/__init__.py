@@ -58,6 +58,8 @@ ABI_SYMBOLS = [
     "gdg_blend_fractions_from_fit",
     "gdg_batch_fit_enable", "gdg_batch_fits", "gdg_batch_fit", "gdg_block_fit_rows", "gdg_block_fit_rows_device", "gdg_blend_weights_from_fit",
     "gdg_batch_gram_enable", "gdg_batch_gram_ports", "gdg_batch_gram", "gdg_block_gram_rows", "gdg_block_gram_rows_device", "gdg_blend_pick_from_gram",
+    "gdg_batch_tapfit_enable", "gdg_batch_tapfits", "gdg_batch_tapfit", "gdg_block_tapfit_rows", "gdg_block_tapfit_rows_device", "gdg_tapfit_doubles",
+    "gdg_blend_taps_from_tapfit",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -223,6 +225,63 @@ def blend_pick_from_gram(records, n_ports, target, candidates, max_terms, ridge=
     if rc != GDG_OK:
         raise GdgError(rc, lib().gdg_last_error(None).decode())
     return [int(p) for p in picked[:n.value]], weight[:n.value].copy(), residual[:n.value].copy()
+
+
+TAPFIT_MAX_TERMS = 4         # GDG_TAPFIT_MAX_TERMS (include/gdg.h, TAPFIT): the terms of one tap fit
+TAPFIT_MAX_UNKNOWNS = 128    # GDG_TAPFIT_MAX_UNKNOWNS: terms x taps of one tap fit
+TAPFIT_MAX_FITS = 16         # GDG_TAPFIT_MAX_FITS: the tap fits of one list
+TAPFIT_BLOCK = 8192          # the block of a batch call's tap-fit records
+TAPFIT_CHUNK = 128           # TAPFIT_KC (csrc/tapfit_kernels.h): the positions the kernel holds in LDS at a time -- no part of the record's definition
+
+
+def _tapfit_csr(fits):
+    """fits = [(target, [ports], taps), ...] -> first, port, target, taps as int32 arrays, one spare entry behind each"""
+    fits = [(int(t), [int(p) for p in ports], int(T)) for t, ports, T in fits]
+    first = np.zeros(len(fits) + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(ports) for _, ports, _ in fits], dtype=np.int64)
+    port = np.array([p for _, ports, _ in fits for p in ports] + [0], dtype=np.int32)
+    target = np.array([t for t, _, _ in fits] + [0], dtype=np.int32)
+    taps = np.array([T for _, _, T in fits] + [0], dtype=np.int32)
+    return first, port, target, taps
+
+
+def tapfit_doubles(fits):
+    """gdg_tapfit_doubles: D, the doubles of one block's tap-fit record -- the sum over the fits of V (V + 1) / 2, V = terms x taps + 1"""
+    fits = list(fits)
+    first, _, _, taps = _tapfit_csr(fits)
+    return int(lib().gdg_tapfit_doubles(len(fits), first.ctypes.data, taps.ctypes.data))
+
+
+def tapfit_matrix(record, terms, taps):
+    """one fit's part of a tap-fit record (or a sum of them), V (V + 1) / 2 doubles, as the full symmetric [V, V] matrix, V = terms x taps + 1"""
+    return gram_matrix(record, int(terms) * int(taps) + 1)
+
+
+def blend_taps_from_tapfit(records, fits, ridge=0.0):
+    """gdg_blend_taps_from_tapfit: records [blocks, D] float64 (as batch_tapfit hands them out), fits as batch_tapfit_enable takes them ->
+    (taps, residuals): per fit a [terms, T] float64 array -- term by term, lag ascending: the h_k of a filtered blend term -- and the share
+    of the target's energy the fitted filters leave.  (A + ridge * mean(diag A) * I) h = b, unpivoted Cholesky in virtual-row order.  Host
+    arithmetic: no context, no device.  GdgError for a pivot at or below the bound (the message names fit, term and lag: a silent or
+    band-limited term, a port twice -- try ridge > 0) and for a NaN or inf entry."""
+    fits = list(fits)
+    first, _, _, taps = _tapfit_csr(fits)
+    D = tapfit_doubles(fits)
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    if rec.ndim != 2 or rec.shape[1] != D:
+        raise ValueError("records: [blocks, %d]" % D)
+    total = int(sum((first[f + 1] - first[f]) * taps[f] for f in range(len(fits))))
+    tap = np.zeros(total + 1, dtype=np.float64)
+    residual = np.zeros(len(fits) + 1, dtype=np.float64)
+    rc = lib().gdg_blend_taps_from_tapfit(rec.ctypes.data if rec.size else None, len(fits), first.ctypes.data, taps.ctypes.data, rec.shape[0], float(ridge),
+                                          tap.ctypes.data, residual.ctypes.data)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    out, at = [], 0
+    for f in range(len(fits)):
+        K, T = int(first[f + 1] - first[f]), int(taps[f])
+        out.append(tap[at:at + K * T].reshape(K, T).copy())
+        at += K * T
+    return out, residual[:len(fits)].copy()
 
 
 ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
@@ -494,6 +553,13 @@ def lib():
             "gdg_block_gram_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp, i32, vp]),
             "gdg_block_gram_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, i32, vp]),
             "gdg_blend_pick_from_gram": (i32, [vp, i32, C.c_size_t, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, C.POINTER(i32)]),
+            "gdg_batch_tapfit_enable": (i32, [vp, i32, vp, vp, vp, vp]),
+            "gdg_batch_tapfits": (i32, [vp]),
+            "gdg_batch_tapfit": (i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+            "gdg_block_tapfit_rows": (i32, [vp, vp, i32, C.c_size_t, i32, i32, vp, vp, vp, vp, vp]),
+            "gdg_block_tapfit_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, i32, vp, vp, vp, vp, vp]),
+            "gdg_tapfit_doubles": (C.c_size_t, [i32, vp, vp]),
+            "gdg_blend_taps_from_tapfit": (i32, [vp, i32, vp, vp, C.c_size_t, C.c_double, vp, vp]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1546,6 +1612,54 @@ class Context:
         """gdg_block_gram_rows_device on plain device pointers (ints); returns when the records are written."""
         port = np.array([int(p) for p in ports] + [0], dtype=np.int32)
         self._check(lib().gdg_block_gram_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(block), port.ctypes.data, port.size - 1, d_records))
+
+    # -- the tap fit: per block and fit the Gram of shifted rows, the least-squares taps from it (include/gdg.h, TAPFIT) ------------------------
+    def batch_tapfit_enable(self, fits):
+        """From the next batch call on, every batch call keeps the tap-fit records of what it rendered (gdg_batch_tapfit_enable): fits = a
+        list of (target, [ports], taps) -- 1 to 4 ports of the call per fit, 1 to 64 taps per term, ports x taps <= 128, up to 16 fits.
+        None or an empty list: off.  Configuration: not in a checkpoint, refused while a streamed job is open."""
+        fits = [] if fits is None else list(fits)
+        if not fits:
+            self._check(lib().gdg_batch_tapfit_enable(self._h, 0, None, None, None, None))
+            return
+        first, port, target, taps = _tapfit_csr(fits)
+        self._check(lib().gdg_batch_tapfit_enable(self._h, len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data, taps.ctypes.data))
+
+    def batch_tapfits(self):
+        """The number of tap fits in force (gdg_batch_tapfits)."""
+        return int(lib().gdg_batch_tapfits(self._h))
+
+    def batch_tapfit(self):
+        """The [blocks, D] float64 tap-fit records of the last completed batch call; GdgError when there are none."""
+        blocks, per = C.c_size_t(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_tapfit(self._h, None, 0, C.byref(blocks), C.byref(per)))
+        out = np.zeros((blocks.value, per.value), dtype=np.float64)
+        self._check(lib().gdg_batch_tapfit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
+        return out
+
+    def block_tapfit(self, rows, fits, block=TAPFIT_BLOCK):
+        """gdg_block_tapfit_rows: rows [n_rows, samples] float64 (or a list of equally long 1-D arrays), fits = (target, [ports], taps) naming
+        rows -> the [ceil(samples / block), D] records."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        fits = list(fits)
+        first, port, target, taps = _tapfit_csr(fits)
+        out = np.zeros((-(-samples // int(block)) if int(block) > 0 else 0, tapfit_doubles(fits)), dtype=np.float64)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_tapfit_rows(self._h, ptrs, n, samples, int(block), len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data, taps.ctypes.data,
+                                                out.ctypes.data if out.size else None))
+        return out
+
+    def block_tapfit_device(self, d_rows, row_stride, n_rows, samples, fits, d_records, block=TAPFIT_BLOCK):
+        """gdg_block_tapfit_rows_device on plain device pointers (ints); returns when the records are written."""
+        fits = list(fits)
+        first, port, target, taps = _tapfit_csr(fits)
+        self._check(lib().gdg_block_tapfit_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(block), len(fits), first.ctypes.data, port.ctypes.data,
+                                                       target.ctypes.data, taps.ctypes.data, d_records))
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

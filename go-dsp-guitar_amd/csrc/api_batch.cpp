@@ -128,6 +128,10 @@ struct BatchLoop {
     /* the Gram list: n_gram ports on the host and on the device; 0 = off, and always for a shard */
     int n_gram;
     const int *h_gram_port, *d_gram_port;
+    /* the tap fits: n_tapfits entries of the table (blend.h, TapFitSet) on the host and on the device, D doubles per block; 0 = off, and always for a shard */
+    int n_tapfits;
+    size_t tapfit_doubles;
+    const int *h_tapfit_table, *d_tapfit_table;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -167,7 +171,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; FitSection fit; GramSection gram; };
+    struct Step { size_t off; int w; ReportSections sec; FitSection fit; GramSection gram; TapFitSection tapfit; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -179,7 +183,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {}, {}, {} });
+        steps.push_back({ off, w, {}, {}, {}, {} });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
@@ -196,6 +200,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
         steps[i].fit = fit_section(steps[i].sec.end, (size_t)p.n_fits, (size_t)steps[i].w);      /* behind the last of them: [fits][w] */
         steps[i].gram = gram_section(steps[i].fit.end, (size_t)p.n_gram, (size_t)steps[i].w);    /* ... and behind those: [w] */
+        steps[i].tapfit = tapfit_section(steps[i].gram.end, p.n_tapfits ? p.tapfit_doubles : 0, (size_t)steps[i].w);      /* ... and the tap fits': [w] */
     }
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
@@ -237,6 +242,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
         if (p.n_fits) fit_file(ctx, src + steps[i].fit.at, (size_t)steps[i].w, steps[i].off / B);
         if (p.n_gram) gram_file(ctx, src + steps[i].gram.at, (size_t)steps[i].w, steps[i].off / B);
+        if (p.n_tapfits) tapfit_file(ctx, src + steps[i].tapfit.at, (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -306,6 +312,9 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             if (p.n_gram)                                                    /* the Gram of the listed rows, on the matrix cores */
                 HIP_TRY(ctx, gdg_launch_block_gram(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_gram_port, p.d_gram_port, (unsigned)p.n_gram,
                                                    reinterpret_cast<double *>(enc + steps[i].gram.at), ctx->stream));
+            if (p.n_tapfits)                                                 /* the tap fits' Gram of shifted rows, likewise */
+                HIP_TRY(ctx, gdg_launch_block_tapfit(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_tapfit_table, p.d_tapfit_table, (unsigned)p.n_tapfits,
+                                                     reinterpret_cast<double *>(enc + steps[i].tapfit.at), ctx->stream));
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: the trimmed siblings of either; `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
@@ -341,7 +350,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = steps[i].gram.end;
+        const size_t down = steps[i].tapfit.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -591,6 +600,27 @@ int gdg_batch_gram_ports(const gdg_ctx *ctx, int *port, int capacity) {
     return n;
 }
 
+/* the tap fits: validated whole before they replace the list in force (blend.h); the ports' upper bound is the job's, checked when one is described */
+int gdg_batch_tapfit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *port, const int *target, const int *taps) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "batch tapfit: a streamed batch run is open on this context; its list holds until gdg_batch_stream_close");
+    const int rc = tapfit_list_check(ctx, "batch tapfit", n_fits, first, port, target, taps, -1);
+    if (rc != GDG_OK) return rc;
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    std::vector<int> table = gdg_tapfit_table(n_fits, first, port, target, taps);
+    if (table.size() != ctx->tapfit.table.size() || gdg_tapfit_list_doubles(n_fits, first, taps) != ctx->tapfit.doubles()) {
+        /* another size: the download halves are made anew by the next batch call, at the size of a context that was always configured like
+         * this one -- whatever still reads them has to be done first -- and off, the table goes as well */
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i : { (int)BATCH_ENCODED, (int)BATCH_TAPFIT_TABLE }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    }
+    ctx->tapfit.table.swap(table);
+    ctx->tapfit_rec.valid = false;                                           /* records are read with the list that made them */
+    return GDG_OK;
+}
+
+int gdg_batch_tapfits(const gdg_ctx *ctx) { return ctx ? ctx->tapfit.count() : 0; }
+
 /* the master cursor belongs to gdg_batch_finish_master_slice, which is no part of an open job: it may be set while one is open */
 int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
     if (!ctx) return GDG_ERR_INVALID;
@@ -609,6 +639,10 @@ int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
 /* ... and so are a Gram list's */
 #define GRAM_REFUSED(ctx, what) \
     fail(ctx, GDG_ERR_UNSUPPORTED, "%s: a Gram list of %d ports is in force on this context (gdg_batch_gram_enable); a sharded job cannot collect Gram records yet", what, (int)(ctx)->gram_port.size())
+
+/* ... and tap fits' */
+#define TAPFITS_REFUSED(ctx, what) \
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d tap fits are in force on this context (gdg_batch_tapfit_enable); a sharded job cannot collect tap-fit records yet", what, (ctx)->tapfit.count())
 
 #define SHARD_PORTS " (a shard: its N inputs, its N outputs, metronome, left, right)"
 static int check_meter_ports(gdg_ctx *ctx, const gdg_batch_options *opt, const char *note) {
@@ -654,6 +688,16 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
         const int at = gdg_gram_list_bad(ctx->gram_port.data(), (int)ctx->gram_port.size(), n_inputs + 3 + n_blends);
         if (at >= 0)
             return fail(ctx, GDG_ERR_INVALID, "batch gram: list entry %d names port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", at, ctx->gram_port[(size_t)at],
+                        n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
+    }
+    if (!shard && ctx->tapfit.count()) {                                         /* the tap fits' ports against this call's */
+        int term = -1;
+        const int f = ctx->tapfit.first_outside(n_inputs + 3 + n_blends, &term);
+        if (f >= 0 && term < 0)
+            return fail(ctx, GDG_ERR_INVALID, "batch tapfit: fit %d has the target port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", f, ctx->tapfit.target(f),
+                        n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
+        if (f >= 0)
+            return fail(ctx, GDG_ERR_INVALID, "batch tapfit: fit %d, term %d names port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", f, term, ctx->tapfit.port(f, term),
                         n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
     }
     int rc;
@@ -720,6 +764,7 @@ int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_stream_open_shard");
+    if (ctx && ctx->tapfit.count()) return TAPFITS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
     if (ctx && opt && opt->metronome_to_master)
         return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_open_shard: metronome_to_master must be 0 -- a shard's master mix is a partial sum; pass the metronome's "
@@ -785,6 +830,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     if (n_fits) fit_begin(ctx, (size_t)blocks);
     const int n_gram = sharded ? 0 : (int)ctx->gram_port.size();                 /* never a shard's either */
     if (n_gram) gram_begin(ctx, (size_t)blocks);
+    const int n_tapfits = sharded ? 0 : ctx->tapfit.count();                     /* nor tap fits */
+    if (n_tapfits) tapfit_begin(ctx, (size_t)blocks);
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -809,7 +856,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
-                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + fit_room((size_t)n_fits, (size_t)W) + gram_room((size_t)n_gram, (size_t)W);
+                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + fit_room((size_t)n_fits, (size_t)W) + gram_room((size_t)n_gram, (size_t)W)
+                           + tapfit_room(n_tapfits ? ctx->tapfit.doubles() : 0, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -979,7 +1027,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, nullptr, nullptr };
         /* the fits in force: their table goes up on the context's stream, ahead of everything the slice enqueues there; it lives as long as
          * the setting, so nothing waits here */
         if (n_fits) {
@@ -997,6 +1045,15 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             loop.n_gram = n_gram;
             loop.h_gram_port = ctx->gram_port.data();
             loop.d_gram_port = d_port;
+        }
+        if (n_tapfits) {                                                     /* ... and the tap fits' table */
+            int *d_table = nullptr;
+            if ((r = batch_buffer(ctx, BATCH_TAPFIT_TABLE, ctx->tapfit.table.size() * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->tapfit.table.data(), ctx->tapfit.table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            loop.n_tapfits = n_tapfits;
+            loop.tapfit_doubles = ctx->tapfit.doubles();
+            loop.h_tapfit_table = ctx->tapfit.table.data();
+            loop.d_tapfit_table = d_table;
         }
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
@@ -1072,6 +1129,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
     if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_step_shard");
     if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_stream_step_shard");
+    if (ctx && ctx->tapfit.count()) return TAPFITS_REFUSED(ctx, "gdg_batch_stream_step_shard");
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
 
@@ -1097,6 +1155,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
         if (!shard) fit_begin(ctx, 0);
         if (!shard) gram_begin(ctx, 0);
+        if (!shard) tapfit_begin(ctx, 0);
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
@@ -1118,6 +1177,7 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
     if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_run_shard");
     if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_run_shard");
+    if (ctx && ctx->tapfit.count()) return TAPFITS_REFUSED(ctx, "gdg_batch_run_shard");
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
      * metronome track of the shard that ran it).  A set flag here would be silently dropped -- refuse it instead. */
     if (ctx && opt && opt->metronome_to_master)

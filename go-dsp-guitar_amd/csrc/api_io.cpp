@@ -1106,6 +1106,128 @@ int gdg_blend_pick_from_gram(const double *records, int n_ports, size_t blocks, 
     return GDG_ERR_INVALID;
 }
 
+/* ---- the tap fit (include/gdg.h, TAPFIT; the kernel: tapfit_kernels.h in gram.hip; the list's validation and the planner: blend.h; the batch calls fill it: api_batch.cpp) ---- */
+/* A list of tap fits held against gdg_tapfit_check, refused in the words of the call `what`: the ONE place they are worded; n_rows as for the fits */
+int tapfit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, const int *taps, int n_rows) {
+    int f = -1, k = -1;
+    switch (gdg_tapfit_check(n_fits, first, port, target, taps, n_rows, &f, &k)) {
+    case TAPFIT_OK: return GDG_OK;
+    case TAPFIT_COUNT: return fail(ctx, GDG_ERR_INVALID, "%s: %d fits; 0 (off) to %d", what, n_fits, GDG_TAPFIT_MAX_FITS);
+    case TAPFIT_NULL: return fail(ctx, GDG_ERR_INVALID, "%s: %d fits need first, port, target and taps", what, n_fits);
+    case TAPFIT_FIRST: return fail(ctx, GDG_ERR_INVALID, "%s: fit %d: first[%d] = %d, first[%d] = %d; the offsets start at 0 and never descend", what, f, f, first[f], f + 1, first[f + 1]);
+    case TAPFIT_TERMS: return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has %d terms; 1 to %d", what, f, first[f + 1] - first[f], GDG_TAPFIT_MAX_TERMS);
+    case TAPFIT_TAPS: return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has %d taps per term; 1 to %d", what, f, taps[f], GDG_BLEND_MAX_TAPS);
+    case TAPFIT_UNKNOWNS:
+        return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has %d terms x %d taps = %d unknowns; at most %d", what, f, first[f + 1] - first[f], taps[f], (first[f + 1] - first[f]) * taps[f],
+                    GDG_TAPFIT_MAX_UNKNOWNS);
+    case TAPFIT_PORT:
+        if (n_rows >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: fit %d, term %d names row %d of %d", what, f, k, port[first[f] + k], n_rows);
+        return fail(ctx, GDG_ERR_INVALID, "%s: fit %d, term %d names port %d; ports start at 0", what, f, k, port[first[f] + k]);
+    default:
+        if (n_rows >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has the target row %d of %d", what, f, target[f], n_rows);
+        return fail(ctx, GDG_ERR_INVALID, "%s: fit %d has the target port %d; ports start at 0", what, f, target[f]);
+    }
+}
+
+/* D: pure arithmetic; 0 for a list it cannot size */
+size_t gdg_tapfit_doubles(int n_fits, const int *first, const int *taps) {
+    if (n_fits < 1 || !first || !taps) return 0;
+    for (int f = 0; f < n_fits; f++) if (first[f + 1] < first[f] || taps[f] < 0) return 0;
+    return gdg_tapfit_list_doubles(n_fits, first, taps);
+}
+
+static int block_tapfit_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port, const int *target, const int *taps, size_t *blocks) {
+    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "block tapfit: %d rows (at least 1)", n_rows);
+    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block tapfit: blocks of %d samples (at least 1)", block);
+    const int rc = tapfit_list_check(ctx, "block tapfit", n_fits, first, port, target, taps, n_rows);
+    if (rc != GDG_OK) return rc;
+    *blocks = (samples + (size_t)block - 1) / (size_t)block;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block tapfit: %zu blocks per row are too many for one call", *blocks);
+    return GDG_OK;
+}
+
+/* the table is made from the caller's host lists: it goes up, the kernel runs, and the call returns when the records are written */
+int gdg_block_tapfit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
+                                 const int *port, const int *target, const int *taps, double *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_tapfit_check(ctx, n_rows, samples, block, n_fits, first, port, target, taps, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_fits == 0 || samples == 0) return GDG_OK;
+    if (!d_rows || !d_records) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block tapfit: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block tapfit: rows and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    const std::vector<int> table = gdg_tapfit_table(n_fits, first, port, target, taps);
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, table.size() * sizeof(int)));
+    hipError_t e = hipMemcpyAsync(d, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        e = gdg_launch_block_tapfit(d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, table.data(), static_cast<const int *>(d), (unsigned)n_fits, d_records, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block tapfit: %s", hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block tapfit: %s", hipGetErrorString(w));
+    return GDG_OK;
+}
+
+int gdg_block_tapfit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port,
+                          const int *target, const int *taps, double *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_tapfit_check(ctx, n_rows, samples, block, n_fits, first, port, target, taps, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (n_fits == 0 || samples == 0) return GDG_OK;
+    if (!rows || !records) return GDG_ERR_INVALID;
+    return rows_round_trip(ctx, "block tapfit", rows, n_rows, samples, records, blocks * gdg_tapfit_list_doubles(n_fits, first, taps) * sizeof(double), [&](const double *d_rows, void *d_out) {
+        return gdg_block_tapfit_rows_device(ctx, d_rows, samples, n_rows, samples, block, n_fits, first, port, target, taps, static_cast<double *>(d_out));
+    });
+}
+
+/* the getter: the tap fits' own store, by the four kinds' rule and in their words; capacity in doubles */
+int gdg_batch_tapfit(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const gdg_ctx::TapFitRecords &F = ctx->tapfit_rec;
+    if (!F.valid)
+        return fail(ctx, GDG_ERR_INVALID, "no tap-fit records: the last batch call of this context %s", ctx->tapfit.count()
+                    ? "has not completed, was a master finish, or none has run since gdg_batch_tapfit_enable" : "ran without them (gdg_batch_tapfit_enable comes before the call)");
+    if (blocks) *blocks = F.blocks;
+    if (doubles_per_block) *doubles_per_block = F.doubles;
+    if (!out) return GDG_OK;
+    if (capacity < F.store.size())
+        return fail(ctx, GDG_ERR_INVALID, "tapfit: room for %zu doubles, the call has %zu blocks x %zu = %zu", capacity, F.blocks, F.doubles, F.store.size());
+    if (!F.store.empty()) memcpy(out, F.store.data(), F.store.size() * sizeof(double));
+    return GDG_OK;
+}
+
+/* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
+int gdg_blend_taps_from_tapfit(const double *records, int n_fits, const int *first, const int *taps, size_t blocks, double ridge, double *tap, double *residual) {
+    int bad = -1, row = -1;
+    char msg[320];
+    const int rc = gdg_blend_plan_taps(records, n_fits, first, taps, blocks, ridge, tap, residual, &bad, &row);
+    if (rc == TAPS_PLAN_OK) return GDG_OK;
+    const int T = (bad >= 0 && taps && taps[bad] > 0) ? taps[bad] : 1, U = (bad >= 0 && first && taps) ? (first[bad + 1] - first[bad]) * taps[bad] : 0;
+    switch (rc) {
+    case TAPS_PLAN_NONFINITE:
+        if (row >= U) snprintf(msg, sizeof msg, "blend taps from tapfit: fit %d: the summed record has a NaN or inf entry in the target's row", bad);
+        else snprintf(msg, sizeof msg, "blend taps from tapfit: fit %d, term %d, lag %d: the summed record has a NaN or inf entry in that row", bad, row / T, row % T);
+        break;
+    case TAPS_PLAN_PIVOT:
+        snprintf(msg, sizeof msg, "blend taps from tapfit: fit %d, term %d, lag %d: a pivot at or below U * 2^-52 * max(diag A) -- a silent or band-limited term, or a port used twice; "
+                 "try ridge > 0", bad, row / T, row % T);
+        break;
+    default:
+        snprintf(msg, sizeof msg, "blend taps from tapfit: %d fits (0 to %d) of %zu blocks (at least 1), ridge = %g (finite, >= 0), every fit 1 to %d terms x 1 to %d taps, at most %d "
+                 "unknowns (fit %d); records, first, taps, tap and residual are needed", n_fits, GDG_TAPFIT_MAX_FITS, blocks, ridge, GDG_TAPFIT_MAX_TERMS, GDG_BLEND_MAX_TAPS,
+                 GDG_TAPFIT_MAX_UNKNOWNS, bad);
+        break;
+    }
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
+}
+
 /* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */
 static_assert(sizeof(gdg_block_true_peak) == 16 && offsetof(gdg_block_true_peak, position) == 8 && offsetof(gdg_block_true_peak, overs) == 12,
               "gdg_block_true_peak: 16 bytes, no padding");

@@ -10,8 +10,9 @@
  * planner that turns alignment records into delays and signs (gdg_blend_delays_from_align); and, for the blend fit (include/gdg.h, FIT), the
  * validation of a list of fits, the table a launch reads, and the planner that turns fit records into weights (gdg_blend_weights_from_fit;
  * tests/native/fit_plan_check.cpp); and, for the Gram of a port list (include/gdg.h, GRAM), the validation of the list, the packed index
- * and the greedy planner that picks ports from Gram records (gdg_blend_pick_from_gram; tests/native/gram_plan_check.cpp).  No HIP header
- * is needed to compile this file.
+ * and the greedy planner that picks ports from Gram records (gdg_blend_pick_from_gram; tests/native/gram_plan_check.cpp); and, for the tap
+ * fit (include/gdg.h, TAPFIT), the validation of its list, the table a launch reads and the planner that turns its records into taps
+ * (gdg_blend_taps_from_tapfit; tests/native/tapfit_plan_check.cpp).  No HIP header is needed to compile this file.
  */
 #ifndef GDG_BLEND_H
 #define GDG_BLEND_H
@@ -531,48 +532,54 @@ enum {
     FIT_PLAN_PIVOT = 3                         /* the factorisation of *fit met a pivot at or below the bound: a silent term, or a port twice without a ridge */
 };
 
-/* The ONE solve, for a fit's sums and for a pick's (gdg_blend_pick): T, b[K] and the lower triangle of G[K][K] in -> (G + ridge * mean(diag G)
- * I) w = b by an unpivoted Cholesky factorisation in term order, *res = max(0, T - 2 w.b + w'Gw) / T (0 where T == 0).  false: a pivot at
- * or below K * 2^-52 * max(diag G); w and *res are then not to be used.  The upper triangle of G is filled here. */
-static inline bool gdg_fit_solve(int K, double T, const double *b, double (*G)[GDG_FIT_MAX_TERMS], double ridge, double *w, double *res) {
-    constexpr int M = GDG_FIT_MAX_TERMS;
-    for (int j = 0; j < K; j++) for (int k = j + 1; k < K; k++) G[j][k] = G[k][j];
+/* The ONE solve at any size, for a fit's sums, a pick's (gdg_blend_pick) and a tap fit's (gdg_blend_plan_taps): T, b[K] and the lower triangle
+ * of G[K][K] (row j at G + j * ld) in -> (G + ridge * mean(diag G) I) w = b by an unpivoted Cholesky factorisation in row order, *res = max(0,
+ * T - 2 w.b + w'Gw) / T (0 where T == 0).  false: a pivot at or below K * 2^-52 * max(diag G) in row *pivot; w and *res are then not to be
+ * used.  The upper triangle of G is filled here.  Lo: K * ld doubles of room, y: K. */
+static inline bool gdg_solve_n(int K, double T, const double *b, double *G, size_t ld, double ridge, double *w, double *res, int *pivot, double *Lo, double *y) {
+    for (int j = 0; j < K; j++) for (int k = j + 1; k < K; k++) G[j * ld + k] = G[k * ld + j];
     double trace = 0.0, most = 0.0;
-    for (int j = 0; j < K; j++) { trace += G[j][j]; if (G[j][j] > most) most = G[j][j]; }
+    for (int j = 0; j < K; j++) { trace += G[j * ld + j]; if (G[j * ld + j] > most) most = G[j * ld + j]; }
     const double shift = ridge * (trace / (double)K), least = (double)K * 2.220446049250313e-16 * most;      /* K * 2^-52 * max(diag G) */
-    double Lo[M][M];
     for (int j = 0; j < K; j++) {
-        double d = G[j][j] + shift;
-        for (int k = 0; k < j; k++) d -= Lo[j][k] * Lo[j][k];
-        if (!(d > least)) return false;
-        Lo[j][j] = sqrt(d);
+        double d = G[j * ld + j] + shift;
+        for (int k = 0; k < j; k++) d -= Lo[j * ld + k] * Lo[j * ld + k];
+        if (!(d > least)) { *pivot = j; return false; }
+        Lo[j * ld + j] = sqrt(d);
         for (int i = j + 1; i < K; i++) {
-            double s = G[i][j];
-            for (int k = 0; k < j; k++) s -= Lo[i][k] * Lo[j][k];
-            Lo[i][j] = s / Lo[j][j];
+            double s = G[i * ld + j];
+            for (int k = 0; k < j; k++) s -= Lo[i * ld + k] * Lo[j * ld + k];
+            Lo[i * ld + j] = s / Lo[j * ld + j];
         }
     }
-    double y[M];
     for (int j = 0; j < K; j++) {                                        /* L y = b, then L' w = y */
         double s = b[j];
-        for (int k = 0; k < j; k++) s -= Lo[j][k] * y[k];
-        y[j] = s / Lo[j][j];
+        for (int k = 0; k < j; k++) s -= Lo[j * ld + k] * y[k];
+        y[j] = s / Lo[j * ld + j];
     }
     for (int j = K - 1; j >= 0; j--) {
         double s = y[j];
-        for (int k = j + 1; k < K; k++) s -= Lo[k][j] * w[k];
-        w[j] = s / Lo[j][j];
+        for (int k = j + 1; k < K; k++) s -= Lo[k * ld + j] * w[k];
+        w[j] = s / Lo[j * ld + j];
     }
     double wb = 0.0, wGw = 0.0;
     for (int j = 0; j < K; j++) {
         wb += w[j] * b[j];
         double row = 0.0;
-        for (int k = 0; k < K; k++) row += G[j][k] * w[k];
+        for (int k = 0; k < K; k++) row += G[j * ld + k] * w[k];
         wGw += w[j] * row;
     }
     const double left = T - 2.0 * wb + wGw;
     *res = T == 0.0 ? 0.0 : (left > 0.0 ? left : 0.0) / T;
     return true;
+}
+
+/* ... at the fits' and the picks' size: up to 8 rows on the stack */
+static inline bool gdg_fit_solve(int K, double T, const double *b, double (*G)[GDG_FIT_MAX_TERMS], double ridge, double *w, double *res) {
+    constexpr int M = GDG_FIT_MAX_TERMS;
+    double Lo[M][M], y[M];
+    int pivot = -1;
+    return gdg_solve_n(K, T, b, &G[0][0], (size_t)M, ridge, w, res, &pivot, &Lo[0][0], y);
 }
 
 /* records[n_fits][blocks].  Per fit: the blocks' sums added in block order -- T, b[K], G[K][K] --, (G + ridge * mean(diag G) * I) w = b by
@@ -754,6 +761,159 @@ static inline int gdg_blend_pick(const double *records, int n_ports, size_t bloc
     for (int k = 0; k < M; k++) { picked[k] = S[k]; weight[k] = w_S[k]; residual[k] = res_S[k]; }
     *n_picked = n;
     return PICK_OK;
+}
+
+/* ---- the tap fit (include/gdg.h, TAPFIT): a list of fits with T taps per term, the table a launch reads, and the taps from its records
+ * (gdg_blend_taps_from_tapfit; tests/native/tapfit_plan_check.cpp) ---------------------------------------------------------------------------- */
+#ifndef GDG_TAPFIT_MAX_TERMS
+#define GDG_TAPFIT_MAX_TERMS 4
+#define GDG_TAPFIT_MAX_UNKNOWNS 128
+#define GDG_TAPFIT_MAX_FITS 16
+#endif
+#define GDG_TAPFIT_TILE 32                                                   /* the kernel's tile of a fit's lower triangle (tapfit_kernels.h) */
+/* a fit as the kernel reads it: target | terms | taps | port[4] | where its part of a block's record begins, in doubles | its first tile */
+enum { TAPFIT_E_TARGET = 0, TAPFIT_E_TERMS = 1, TAPFIT_E_TAPS = 2, TAPFIT_E_PORT = 3, TAPFIT_E_OFFSET = 3 + GDG_TAPFIT_MAX_TERMS, TAPFIT_E_TILE0, GDG_TAPFIT_TABLE_INTS };
+
+enum {
+    TAPFIT_OK = 0,
+    TAPFIT_COUNT = 1,                          /* n_fits outside 0 .. GDG_TAPFIT_MAX_FITS */
+    TAPFIT_NULL = 2,                           /* a list is missing */
+    TAPFIT_FIRST = 3,                          /* first[0] != 0, or first[f + 1] < first[f]: *fit = f */
+    TAPFIT_TERMS = 4,                          /* fit f has no term or more than GDG_TAPFIT_MAX_TERMS */
+    TAPFIT_TAPS = 5,                           /* fit f has taps outside 1 .. GDG_BLEND_MAX_TAPS */
+    TAPFIT_UNKNOWNS = 6,                       /* fit f has more than GDG_TAPFIT_MAX_UNKNOWNS terms x taps */
+    TAPFIT_PORT = 7,                           /* term `term` of fit f names a port outside [0, n_ports) */
+    TAPFIT_TARGET = 8                          /* fit f's target lies outside [0, n_ports) */
+};
+
+/* The list in its CSR form, as the fits': fit f has the terms port[first[f] .. first[f + 1]), the target target[f] and taps[f] taps per term.
+ * n_ports < 0: the port count is not known yet and only negative ports are refused.  *fit, *term: the first offender, -1 where none is named. */
+static inline int gdg_tapfit_check(int n_fits, const int *first, const int *port, const int *target, const int *taps, int n_ports, int *fit, int *term) {
+    *fit = *term = -1;
+    if (n_fits < 0 || n_fits > GDG_TAPFIT_MAX_FITS) return TAPFIT_COUNT;
+    if (n_fits == 0) return TAPFIT_OK;
+    if (!first || !port || !target || !taps) return TAPFIT_NULL;
+    if (first[0] != 0) { *fit = 0; return TAPFIT_FIRST; }
+    for (int f = 0; f < n_fits; f++) {                                       /* the offsets first: nothing is read through a bad one */
+        *fit = f;
+        if (first[f + 1] < first[f]) return TAPFIT_FIRST;
+        if (first[f + 1] == first[f] || first[f + 1] - first[f] > GDG_TAPFIT_MAX_TERMS) return TAPFIT_TERMS;
+        if (taps[f] < 1 || taps[f] > GDG_BLEND_MAX_TAPS) return TAPFIT_TAPS;
+        if ((first[f + 1] - first[f]) * taps[f] > GDG_TAPFIT_MAX_UNKNOWNS) return TAPFIT_UNKNOWNS;
+    }
+    for (int f = 0; f < n_fits; f++) {
+        *fit = f;
+        if (target[f] < 0 || (n_ports >= 0 && target[f] >= n_ports)) return TAPFIT_TARGET;
+        for (int k = first[f]; k < first[f + 1]; k++)
+            if (port[k] < 0 || (n_ports >= 0 && port[k] >= n_ports)) { *term = k - first[f]; return TAPFIT_PORT; }
+    }
+    *fit = -1;
+    return TAPFIT_OK;
+}
+
+/* V (V + 1) / 2 of one fit, and D of a checked list: the doubles of a block's record */
+static inline size_t gdg_tapfit_fit_doubles(int terms, int taps) { const size_t V = (size_t)terms * (size_t)taps + 1; return V * (V + 1) / 2; }
+static inline size_t gdg_tapfit_list_doubles(int n_fits, const int *first, const int *taps) {
+    size_t D = 0;
+    for (int f = 0; f < n_fits; f++) D += gdg_tapfit_fit_doubles(first[f + 1] - first[f], taps[f]);
+    return D;
+}
+
+/* the list in force, as the table a launch reads */
+struct TapFitSet {
+    std::vector<int> table;
+    int count() const { return (int)(table.size() / GDG_TAPFIT_TABLE_INTS); }
+    const int *entry(int f) const { return &table[(size_t)f * GDG_TAPFIT_TABLE_INTS]; }
+    int target(int f) const { return entry(f)[TAPFIT_E_TARGET]; }
+    int terms(int f) const { return entry(f)[TAPFIT_E_TERMS]; }
+    int taps(int f) const { return entry(f)[TAPFIT_E_TAPS]; }
+    int port(int f, int k) const { return entry(f)[TAPFIT_E_PORT + k]; }
+    size_t doubles() const {                   /* D */
+        size_t D = 0;
+        for (int f = 0; f < count(); f++) D += gdg_tapfit_fit_doubles(terms(f), taps(f));
+        return D;
+    }
+    /* the first fit that names a port outside [0, n_ports): -1 = none; *term: the term, -1 = the target */
+    int first_outside(int n_ports, int *term) const {
+        for (int f = 0; f < count(); f++) {
+            *term = -1;
+            if (target(f) >= n_ports) return f;
+            for (int k = 0; k < terms(f); k++) if (port(f, k) >= n_ports) { *term = k; return f; }
+        }
+        return -1;
+    }
+};
+
+/* a checked list as a table */
+static inline std::vector<int> gdg_tapfit_table(int n_fits, const int *first, const int *port, const int *target, const int *taps) {
+    std::vector<int> t((size_t)n_fits * GDG_TAPFIT_TABLE_INTS, 0);
+    size_t D = 0;
+    int tiles = 0;
+    for (int f = 0; f < n_fits; f++) {
+        int *e = &t[(size_t)f * GDG_TAPFIT_TABLE_INTS];
+        const int K = first[f + 1] - first[f], R = (K * taps[f] + 1 + GDG_TAPFIT_TILE - 1) / GDG_TAPFIT_TILE;
+        e[TAPFIT_E_TARGET] = target[f];
+        e[TAPFIT_E_TERMS] = K;
+        e[TAPFIT_E_TAPS] = taps[f];
+        for (int k = 0; k < K; k++) e[TAPFIT_E_PORT + k] = port[first[f] + k];
+        e[TAPFIT_E_OFFSET] = (int)D;
+        e[TAPFIT_E_TILE0] = tiles;
+        D += gdg_tapfit_fit_doubles(K, taps[f]);
+        tiles += R * (R + 1) / 2;
+    }
+    return t;
+}
+
+enum {
+    TAPS_PLAN_OK = 0,
+    TAPS_PLAN_ARGS = 1,                        /* a list is missing, a count or a fit's shape is out of range, no block, ridge is negative or not finite */
+    TAPS_PLAN_NONFINITE = 2,                   /* the summed record of *fit has a NaN or inf in virtual row *row */
+    TAPS_PLAN_PIVOT = 3                        /* the factorisation of *fit met a pivot at or below the bound in virtual row *row */
+};
+
+/* records[blocks][D].  Per fit: the blocks' records added in block order with plain adds; A = G[0 .. U)[0 .. U), b = G[U][0 .. U), Tt = G[U][U];
+ * gdg_solve_n on them in virtual-row order.  Every fit is solved before tap (U_f doubles per fit, concatenated) and residual[n_fits] are
+ * written; *fit, *row: the offender (term = *row / taps, lag = *row % taps). */
+static inline int gdg_blend_plan_taps(const double *records, int n_fits, const int *first, const int *taps, size_t blocks, double ridge, double *tap, double *residual,
+                                      int *fit, int *row) {
+    *fit = *row = -1;
+    if (n_fits < 0 || n_fits > GDG_TAPFIT_MAX_FITS || !(ridge >= 0.0) || !isfinite(ridge)) return TAPS_PLAN_ARGS;
+    if (n_fits == 0) return TAPS_PLAN_OK;
+    if (!records || !first || !taps || !tap || !residual || blocks == 0 || first[0] != 0) return TAPS_PLAN_ARGS;
+    size_t total = 0;
+    for (int f = 0; f < n_fits; f++) {
+        *fit = f;
+        const int K = first[f + 1] - first[f];
+        if (K < 1 || K > GDG_TAPFIT_MAX_TERMS || taps[f] < 1 || taps[f] > GDG_BLEND_MAX_TAPS || K * taps[f] > GDG_TAPFIT_MAX_UNKNOWNS) return TAPS_PLAN_ARGS;
+        total += (size_t)(K * taps[f]);
+    }
+    const size_t D = gdg_tapfit_list_doubles(n_fits, first, taps);
+    std::vector<double> h_all(total, 0.0), res_all((size_t)n_fits, 0.0), sum, G, Lo, y, b;
+    size_t off = 0, at = 0;
+    for (int f = 0; f < n_fits; f++) {
+        *fit = f;
+        const int U = (first[f + 1] - first[f]) * taps[f];
+        const size_t E = gdg_tapfit_fit_doubles(first[f + 1] - first[f], taps[f]), ld = (size_t)U;
+        sum.assign(E, 0.0);
+        for (size_t q = 0; q < blocks; q++) for (size_t e = 0; e < E; e++) sum[e] += records[q * D + off + e];
+        for (int i = 0; i <= U; i++)
+            for (int j = 0; j <= i; j++) if (!isfinite(sum[gdg_gram_index((size_t)i, (size_t)j)])) { *row = i; return TAPS_PLAN_NONFINITE; }
+        G.assign(ld * ld, 0.0);
+        Lo.assign(ld * ld, 0.0);
+        y.assign(ld, 0.0);
+        b.assign(ld, 0.0);
+        for (int i = 0; i < U; i++) {
+            b[(size_t)i] = sum[gdg_gram_index((size_t)U, (size_t)i)];
+            for (int j = 0; j <= i; j++) G[(size_t)i * ld + (size_t)j] = sum[gdg_gram_index((size_t)i, (size_t)j)];
+        }
+        if (!gdg_solve_n(U, sum[gdg_gram_index((size_t)U, (size_t)U)], b.data(), G.data(), ld, ridge, &h_all[at], &res_all[(size_t)f], row, Lo.data(), y.data())) return TAPS_PLAN_PIVOT;
+        off += E;
+        at += (size_t)U;
+    }
+    *fit = *row = -1;
+    memcpy(tap, h_all.data(), h_all.size() * sizeof(double));
+    memcpy(residual, res_all.data(), res_all.size() * sizeof(double));
+    return TAPS_PLAN_OK;
 }
 
 #endif

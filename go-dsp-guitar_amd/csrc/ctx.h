@@ -352,8 +352,8 @@ struct gdg_ctx {
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
     /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
      * grown when a slice needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
-    void *batch_dev[9] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t batch_dev_cap[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    void *batch_dev[10] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    size_t batch_dev_cap[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
     /* a batch job, how far it has come, and per input the source frames handed over: the context's is the streamed run's
      * (gdg_batch_stream_open .. _close); a one-call run describes its own and leaves this one closed */
@@ -433,6 +433,16 @@ struct gdg_ctx {
         size_t blocks = 0;
         std::vector<double> store;
     } gram_rec;
+    /* the tap fits (gdg_batch_tapfit_enable; blend.h, report_sections.h): the list in force as the table a launch reads, empty = off.  While
+     * fits are in force batch_dev[BATCH_TAPFIT_TABLE] holds the table -- uploaded at the start of a batch call -- and a download half has
+     * room for [window] records of D doubles behind the Gram section; off, neither exists.  The records of the last completed batch call,
+     * [blocks][D], by the fit records' rule.  Stateless configuration: in no blob. */
+    TapFitSet tapfit;
+    struct TapFitRecords {
+        bool live = false, valid = false;
+        size_t doubles = 0, blocks = 0;
+        std::vector<double> store;
+    } tapfit_rec;
     /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;
@@ -725,6 +735,8 @@ int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
 int fit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, int n_rows);
 /* api_io.cpp: a Gram list of `least` to GDG_GRAM_MAX_PORTS ports against blend.h's checks, refused in the words of `what`; n_rows < 0: the port count is not known yet */
 int gram_list_check(gdg_ctx *ctx, const char *what, const int *port, int n_ports, int least, int n_rows);
+/* api_io.cpp: a list of tap fits against gdg_tapfit_check (blend.h), refused in the words of `what`; n_rows < 0: the port count is not known yet */
+int tapfit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, const int *taps, int n_rows);
 /* the map in force has a reader: what a checkpoint cannot record yet */
 static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_have_reader(ctx->batch_source); }
 /* a batch call begins: every kind's records of the call before are gone; a kind that is switched on gets zeroed records for `ports` x
@@ -734,6 +746,7 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
     ctx->align_live_ref.clear();
     ctx->fit_rec.valid = ctx->fit_rec.live = false;                              /* a call that collects fits says so itself (fit_begin) */
     ctx->gram_rec.valid = ctx->gram_rec.live = false;                            /* ... and so does one that collects Gram records (gram_begin) */
+    ctx->tapfit_rec.valid = ctx->tapfit_rec.live = false;                        /* ... or tap-fit records (tapfit_begin) */
     /* any other count was refused when the job was described; a list without the call's blend ports: each of them references itself */
     if (align && ((int)ctx->align_ref.size() == ports || (blend_ports > 0 && (int)ctx->align_ref.size() == ports - blend_ports))) {
         ctx->align_live_ref = ctx->align_ref;
@@ -782,8 +795,24 @@ static inline void gram_file(gdg_ctx *ctx, const unsigned char *section, size_t 
     const size_t rec = gram_record_bytes((size_t)G.ports);
     memcpy(reinterpret_cast<unsigned char *>(G.store.data()) + b0 * rec, section, w * rec);
 }
+/* behind report_begin, by the calls that collect tap-fit records: zeroed records for the fits in force x `blocks` */
+static inline void tapfit_begin(gdg_ctx *ctx, size_t blocks) {
+    gdg_ctx::TapFitRecords &F = ctx->tapfit_rec;
+    F.live = ctx->tapfit.count() > 0;
+    if (!F.live) return;
+    F.doubles = ctx->tapfit.doubles();
+    F.blocks = blocks;
+    F.store.assign(blocks * F.doubles, 0.0);
+}
+/* a step's tap-fit section ([w] records) that has come down, into the store under the blocks from b0 on */
+static inline void tapfit_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
+    gdg_ctx::TapFitRecords &F = ctx->tapfit_rec;
+    memcpy(F.store.data() + b0 * F.doubles, section, w * F.doubles * sizeof(double));
+}
 /* ... and has completed (rc == GDG_OK) or not */
 static inline int report_end(gdg_ctx *ctx, int rc) {
+    ctx->tapfit_rec.valid = ctx->tapfit_rec.live && rc == GDG_OK;
+    ctx->tapfit_rec.live = false;
     ctx->gram_rec.valid = ctx->gram_rec.live && rc == GDG_OK;
     ctx->gram_rec.live = false;
     ctx->fit_rec.valid = ctx->fit_rec.live && rc == GDG_OK;
@@ -819,9 +848,10 @@ enum {
     BATCH_BLEND_HISTORY,                   /* [N][GDG_BLEND_MAX_DELAY] the chain rows' last samples of the step before, only while a blend delay is in force */
     BATCH_FIT_TABLE,                       /* [fits][target | terms | port[8]] the blend fits' table, only while fits are in force (gdg_batch_fit_enable) */
     BATCH_GRAM_PORTS,                      /* [P] the Gram list's ports, only while a list is in force (gdg_batch_gram_enable) */
+    BATCH_TAPFIT_TABLE,                    /* [fits][target | terms | taps | port[4] | offset | tile] the tap fits' table, only while tap fits are in force (gdg_batch_tapfit_enable) */
     BATCH_DEV_SLOTS
 };
-static_assert(BATCH_DEV_SLOTS == 9, "gdg_ctx::batch_dev has one entry per slot");
+static_assert(BATCH_DEV_SLOTS == 10, "gdg_ctx::batch_dev has one entry per slot");
 int ensure_tuner(gdg_ctx *ctx);
 
 #pragma GCC visibility pop

@@ -1,7 +1,7 @@
 /*
  * gram_kernels.h -- the Gram record (include/gdg.h, GRAM): per block the lower triangle of the P x P matrix of inner
  * products of P listed float64 rows, P up to 512 -- what a selection among many rigs needs, taken from the rows where they lie.  No
- * reference counterpart.  The first dense contraction of this code base and the only kernel on the matrix cores: v_mfma_f64_16x16x4_f64.
+ * reference counterpart.  The first dense contraction of this code base, on the matrix cores: v_mfma_f64_16x16x4_f64 (tapfit_kernels.h is the second).
  * Included by gram.hip alone; contraction flags do not matter to it, the instruction is the arithmetic.
  *
  * blockIdx.x = a 64 x 64 tile of the lower triangle, diagonal tiles included, by rows: tile (ti, tj), tj <= ti, at ti (ti + 1) / 2 + tj;

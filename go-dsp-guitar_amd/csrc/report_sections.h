@@ -82,4 +82,20 @@ static inline GramSection gram_section(size_t end, size_t ports, size_t w) {
 /* ... and what a half holds for them for a window of W blocks */
 static inline size_t gram_room(size_t ports, size_t W) { return ports ? 16 + W * gram_record_bytes(ports) : 0; }
 
+/* The tap-fit records (include/gdg.h, TAPFIT) ride behind the Gram section -- behind whatever precedes it when there is none -- from the next
+ * 16 bytes on: [w] records of D doubles, D the list's sum of V (V + 1) / 2.  No list: no byte.  The finish calls never carry them. */
+struct TapFitSection { size_t at, bytes, end; };
+
+static inline TapFitSection tapfit_section(size_t end, size_t doubles, size_t w) {
+    TapFitSection s = { end, 0, end };
+    if (!doubles) return s;
+    s.at = (end + 15) & ~(size_t)15;
+    s.bytes = w * doubles * 8;
+    s.end = s.at + s.bytes;
+    return s;
+}
+
+/* ... and what a half holds for them for a window of W blocks */
+static inline size_t tapfit_room(size_t doubles, size_t W) { return doubles ? 16 + W * doubles * 8 : 0; }
+
 #endif

@@ -2945,3 +2945,224 @@ func BlendPickFromGram(records [][]float64, nPorts int, target int, candidates [
 	}
 	return picked, weights, residual, nil
 }
+
+// TapFit: one tap fit of a list: the target port, 1 to 4 term ports and the taps per term (1 to 64, ports x taps at most 128).
+type TapFit struct {
+	Target int
+	Ports  []int
+	Taps   int
+}
+
+// tapFitTable: a list of tap fits in its CSR form in C memory -- first[len(fits)+1], the ports, the targets, the taps, one spare entry behind
+// each -- which the caller frees; the library validates it.
+func tapFitTable(fits []TapFit) (first *[1 << 28]C.int, port *[1 << 28]C.int, target *[1 << 28]C.int, taps *[1 << 28]C.int, release func()) {
+	terms := 0
+	for _, f := range fits {
+		terms += len(f.Ports)
+	}
+	n := len(fits)
+	p := C.calloc(C.size_t((n+2)+(terms+1)+(n+1)+(n+1)), 4)
+	if p == nil {
+		return nil, nil, nil, nil, func() {}
+	}
+	all := (*[1 << 28]C.int)(p)
+	first = (*[1 << 28]C.int)(unsafe.Pointer(&all[0]))
+	port = (*[1 << 28]C.int)(unsafe.Pointer(&all[n+2]))
+	target = (*[1 << 28]C.int)(unsafe.Pointer(&all[n+2+terms+1]))
+	taps = (*[1 << 28]C.int)(unsafe.Pointer(&all[n+2+terms+1+n+1]))
+	k := 0
+	for i, f := range fits {
+		first[i] = C.int(k)
+		target[i] = C.int(f.Target)
+		taps[i] = C.int(f.Taps)
+		for _, v := range f.Ports {
+			port[k] = C.int(v)
+			k++
+		}
+	}
+	first[n] = C.int(k)
+	return first, port, target, taps, func() { C.free(p) }
+}
+
+// TapFitDoubles: D, the doubles of one block's tap-fit record (gdg_tapfit_doubles): the sum over the fits of V*(V+1)/2, V = ports x taps + 1.
+func TapFitDoubles(fits []TapFit) int {
+	if len(fits) == 0 {
+		return 0
+	}
+	first, _, _, taps, release := tapFitTable(fits)
+	if first == nil {
+		return 0
+	}
+	defer release()
+	return int(C.gdg_tapfit_doubles(C.int(len(fits)), &first[0], &taps[0]))
+}
+
+// BatchTapFitEnable: from the next batch call on, every batch call of the context keeps the tap-fit records of what it rendered
+// (gdg_batch_tapfit_enable).  nil or an empty slice switches it off.  Configuration, like BatchFitEnable: a checkpoint does not carry it,
+// and an error while a streamed job is open.
+func (this *Context) BatchTapFitEnable(fits []TapFit) error {
+	if len(fits) == 0 {
+		return this.err(C.gdg_batch_tapfit_enable(this.ctx, 0, nil, nil, nil, nil))
+	}
+	first, port, target, taps, release := tapFitTable(fits)
+	if first == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_batch_tapfit_enable(this.ctx, C.int(len(fits)), &first[0], &port[0], &target[0], &taps[0]))
+}
+
+// BatchTapFits: the number of tap fits in force (gdg_batch_tapfits).
+func (this *Context) BatchTapFits() int {
+	return int(C.gdg_batch_tapfits(this.ctx))
+}
+
+// BatchTapFit: the tap-fit records of the last completed batch call, result[block][D] (gdg_batch_tapfit).  An error when the call ran
+// without them, or was a master finish.
+func (this *Context) BatchTapFit() ([][]float64, error) {
+	var blocks C.size_t
+	var per C.size_t
+	if e := this.err(C.gdg_batch_tapfit(this.ctx, nil, 0, &blocks, &per)); e != nil {
+		return nil, e
+	}
+	n := int(blocks) * int(per)
+	if n == 0 {
+		return goGram(nil, int(blocks), int(per)), nil
+	}
+	rec := (*[1 << 28]C.double)(C.calloc(C.size_t(n), 8))
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	if e := this.err(C.gdg_batch_tapfit(this.ctx, &rec[0], C.size_t(n), &blocks, &per)); e != nil {
+		return nil, e
+	}
+	return goGram(unsafe.Pointer(rec), int(blocks), int(per)), nil
+}
+
+// BlockTapFitRows: the tap-fit records of equally long host rows per block of `block` samples, the last one of a row possibly short
+// (gdg_block_tapfit_rows); a fit's ports name rows; result[block][D].
+func (this *Context) BlockTapFitRows(rows [][]float64, block int, fits []TapFit) ([][]float64, error) {
+	n := len(rows)
+	if len(fits) == 0 {
+		return [][]float64{}, nil // as the C call: no fit, no record
+	}
+	if n == 0 || block < 1 {
+		return nil, fmt.Errorf("gdg: %d rows, blocks of %d samples", n, block)
+	}
+	samples := len(rows[0])
+	blocks := (samples + block - 1) / block
+	per := TapFitDoubles(fits)
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	first, port, target, taps, release := tapFitTable(fits)
+	if first == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	out := C.calloc(C.size_t(blocks*per+1), 8)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_tapfit_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(block), C.int(len(fits)), &first[0], &port[0], &target[0], &taps[0], (*C.double)(out))); e != nil {
+		return nil, e
+	}
+	return goGram(out, blocks, per), nil
+}
+
+// BlockTapFitRowsDevice: the same on device memory (gdg_block_tapfit_rows_device): row r at dRows + r*rowStride float64 (any 8-byte
+// alignment, rowStride >= samples), the records into dRecords[ceil(samples/block)][D]; returns when they are written.
+func (this *Context) BlockTapFitRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, block int, fits []TapFit, dRecords unsafe.Pointer) error {
+	if len(fits) == 0 {
+		return nil // as the C call: no fit, no record
+	}
+	first, port, target, taps, release := tapFitTable(fits)
+	if first == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_block_tapfit_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(block), C.int(len(fits)), &first[0], &port[0], &target[0], &taps[0],
+		(*C.double)(dRecords)))
+}
+
+// BlendTapsFromTapFit: the least-squares taps of every fit from its records (gdg_blend_taps_from_tapfit): records[block] as BatchTapFit hands
+// them out; (A + ridge*mean(diag A)*I) h = b by an unpivoted Cholesky factorisation in virtual-row order.  taps[fit][term] has the fit's Taps
+// entries, lag ascending -- the taps of a filtered blend term; residual[fit] is the share of the target's energy the fitted filters leave.
+// Host arithmetic: no context and no device.  An error, with fit, term and lag named, for a pivot at or below the bound -- a silent or
+// band-limited term, a port used twice: try ridge > 0 -- and for a NaN or inf entry.
+func BlendTapsFromTapFit(records [][]float64, fits []TapFit, ridge float64) ([][][]float64, []float64, error) {
+	blocks := len(records)
+	per := TapFitDoubles(fits)
+	if blocks == 0 || len(fits) == 0 {
+		return nil, nil, fmt.Errorf("gdg: %d blocks (at least 1), %d fits (at least 1)", blocks, len(fits))
+	}
+	total := 0
+	for _, f := range fits {
+		total += len(f.Ports) * f.Taps
+	}
+	for b, row := range records {
+		if len(row) != per {
+			return nil, nil, fmt.Errorf("gdg: record %d has %d entries, the fits make %d", b, len(row), per)
+		}
+	}
+	rec := (*[1 << 28]C.double)(C.calloc(C.size_t(blocks*per+1), 8))
+	if rec == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	for b, row := range records {
+		for e, v := range row {
+			rec[b*per+e] = C.double(v)
+		}
+	}
+	first, _, _, taps, release := tapFitTable(fits)
+	if first == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	res := (*[1 << 28]C.double)(C.calloc(C.size_t(total+len(fits)+1), 8))
+	if res == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(res))
+	if rc := C.gdg_blend_taps_from_tapfit(&rec[0], C.int(len(fits)), &first[0], &taps[0], C.size_t(blocks), C.double(ridge), &res[0], &res[total]); rc != 0 {
+		return nil, nil, fmt.Errorf("gdg: gdg_blend_taps_from_tapfit: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	out := make([][][]float64, len(fits))
+	residual := make([]float64, len(fits))
+	at := 0
+	for f, fit := range fits {
+		out[f] = make([][]float64, len(fit.Ports))
+		for j := range fit.Ports {
+			out[f][j] = make([]float64, fit.Taps)
+			for a := range out[f][j] {
+				out[f][j][a] = float64(res[at])
+				at++
+			}
+		}
+		residual[f] = float64(res[total+f])
+	}
+	return out, residual, nil
+}

@@ -57,6 +57,9 @@ def lib():
             "gdgh_engine_set_batch_gram": (cs, [vp, vp, i32]),
             "gdgh_engine_batch_gram_ports": (i32, [vp]),
             "gdgh_engine_last_batch_gram": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdgh_engine_set_batch_tapfits": (cs, [vp, i32, vp, vp, vp, vp]),
+            "gdgh_engine_batch_tapfits": (i32, [vp]),
+            "gdgh_engine_last_batch_tapfit": (cs, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_set_batch_blends_filtered": (cs, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -139,6 +142,7 @@ class Engine:
         self.last_true_peak = None       # the true-peak records of the last batch call made with true_peak=True: [N + 3, blocks] records
         self.last_fit = None             # the fit records of the last batch call made with fits=: [fits, blocks] records (FIT_DTYPE)
         self.last_gram = None            # the Gram records of the last batch call made with gram=: [blocks, P (P + 1) / 2] float64
+        self.last_tapfit = None          # the tap-fit records of the last batch call made with tapfits=: [blocks, D] float64
         self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
     def shards(self):
@@ -374,6 +378,83 @@ class Engine:
         _err(lib().gdgh_engine_last_batch_gram(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
         return out
 
+    def _set_tapfits(self, tapfits):
+        """Engine::SetBatchTapFits, from the `tapfits` argument of the batch calls: a list of (target port, [term ports], taps); None or an
+        empty list: off.  Returns the number of tap fits in force.  Refused on an engine of more than one shard."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        self.last_tapfit = None
+        fits = [] if tapfits is None else list(tapfits)
+        if not fits:
+            _err(lib().gdgh_engine_set_batch_tapfits(self._h, 0, None, None, None, None))
+            return 0
+        first, port, target, taps = pkg._tapfit_csr(fits)
+        _err(lib().gdgh_engine_set_batch_tapfits(self._h, len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data, taps.ctypes.data))
+        return int(lib().gdgh_engine_batch_tapfits(self._h))
+
+    def _fetch_tapfit(self):
+        """Engine::LastBatchTapFit -> [blocks, D] float64"""
+        blocks, per = C.c_size_t(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_tapfit(self._h, None, 0, C.byref(blocks), C.byref(per)))
+        out = np.zeros((blocks.value, per.value), dtype=np.float64)
+        _err(lib().gdgh_engine_last_batch_tapfit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
+        return out
+
+    def render_tap_fitted(self, target, terms, taps, inputs, target_rate, out_format, ridge=0.0, delays=None, signs=None, center=None, window=16, sample_rate=None, **kw):
+        """Two passes over one job: the `taps`-tap filters on the chain outputs `terms` (job channels, 1 to 4, terms x taps <= 128) whose sum
+        comes closest to port `target` in the least-squares sense.  save_state; pass 1 renders with every output skipped and one tap fit
+        on.  A term with a delay d_k or a sign (one per term, as render_aligned returns them) is measured as the port of a one-term blend
+        that delays it and turns its polarity, else as the chain port itself.  The target is measured as the port of a one-term blend
+        that delays it by `center` samples (default taps // 2; the target is then a chain output) -- which is what allows taps on both sides
+        of the peak; center = 0 measures the target port itself (any of the N + 3 ports).  The planner (blend_taps_from_tapfit, with
+        `ridge`) turns the records into taps; load_state; pass 2 renders with the one blend of the terms (channel_k, sign_k, d_k, h_k).
+        THE BLEND PORT LAGS THE TARGET BY `center` SAMPLES: it approximates target[i - center].  A reach d_k + taps - 1 above 4096 is a
+        HostError that names the term.  Returns (outs, taps, residual): the N + 3 + 1 output data sections, the fitted taps [terms, taps]
+        and the share of the (delayed) target's energy the blend leaves.  Pass 1's records stay in tap_fitted_records.  kw: batch_run's
+        other arguments (tapfits, blends and blend_gain in kw are replaced)."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        terms = [int(c) for c in terms]
+        K, T, n3, N = len(terms), int(taps), self.n_channels + 3, self.n_channels
+        if not 1 <= K <= pkg.TAPFIT_MAX_TERMS or not 1 <= T <= pkg.BLEND_MAX_TAPS or K * T > pkg.TAPFIT_MAX_UNKNOWNS:
+            raise HostError("render_tap_fitted: %d terms (1 to %d) of %d taps (1 to %d); at most %d unknowns" % (K, pkg.TAPFIT_MAX_TERMS, T, pkg.BLEND_MAX_TAPS, pkg.TAPFIT_MAX_UNKNOWNS))
+        if not 0 <= int(target) < n3:
+            raise HostError("render_tap_fitted: the target is port %d; the job has ports 0 to %d" % (target, n3 - 1))
+        center = T // 2 if center is None else int(center)
+        if not 0 <= center <= pkg.BLEND_MAX_DELAY:
+            raise HostError("render_tap_fitted: center = %d; 0 to %d" % (center, pkg.BLEND_MAX_DELAY))
+        if center and int(target) >= N:
+            raise HostError("render_tap_fitted: the target is port %d and center = %d: only a chain output (ports 0 to %d) can be delayed; pass center=0" % (target, center, N - 1))
+        delays = [0] * K if delays is None else [int(d) for d in delays]
+        signs = [1] * K if signs is None else [int(g) for g in signs]
+        if len(delays) != K or len(signs) != K or any(g not in (1, -1) for g in signs) or any(d < 0 for d in delays):
+            raise HostError("render_tap_fitted: one delay (>= 0) and one sign (+1 or -1) per term")
+        for k in range(K):
+            if delays[k] + T - 1 > pkg.BLEND_MAX_DELAY:
+                raise HostError("render_tap_fitted: term %d reaches %d + %d - 1 = %d samples back; at most %d" % (k, delays[k], T, delays[k] + T - 1, pkg.BLEND_MAX_DELAY))
+        rate = target_rate if sample_rate is None else sample_rate
+        _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
+        blob = self.save_state()
+        rest = {k: v for k, v in kw.items() if k not in ("tapfits", "blends", "blend_gain", "skip_outputs")}
+        first, ports = [], []
+        for k, c in enumerate(terms):                          # a shaped term goes through a one-term blend: ports N + 3 + ...
+            if delays[k] or signs[k] != 1:
+                ports.append(n3 + len(first))
+                first.append([(c, float(signs[k]), delays[k])])
+            else:
+                ports.append(c)
+        t_port = int(target)
+        if center:
+            t_port = n3 + len(first)
+            first.append([(int(target), 1.0, center)])
+        self.batch_run(inputs, target_rate, out_format, window=window, blends=first or None, tapfits=[(t_port, ports, T)], skip_outputs=True, **rest)
+        self.tap_fitted_records = self.last_tapfit
+        h, residual = pkg.blend_taps_from_tapfit(self.tap_fitted_records, [(t_port, ports, T)], ridge)
+        self.load_state(blob, rate)
+        blend = [[(c, float(signs[k]), delays[k], h[0][k]) for k, c in enumerate(terms)]]
+        outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=blend, **rest)
+        return outs, h[0], float(residual[0])
+
     def render_matched(self, target, candidates, max_terms, inputs, target_rate, out_format, ridge=0.0, min_gain=0.0, window=16, sample_rate=None, **kw):
         """Two passes over one job: which few of `candidates`, in which mix, come closest to port `target` (a chain output, master left,
         master right or the metronome).  A candidate is a job channel, or (job channel, delay, sign) -- then it is measured as the port of a
@@ -567,7 +648,7 @@ class Engine:
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
@@ -577,7 +658,8 @@ class Engine:
         of lists of (job channel, weight) or (job channel, weight, delay), blend_gain: one output gain per blend -- B more outputs and B more ports in every last_* record
         list, behind the metronome's (one-shard engines only; None: off).  fits: a list of (target port, [term ports]) -- keep the fit
         records in last_fit ([fits, blocks], FIT_DTYPE; one-shard engines only; None: off).  gram: a list of 2 to 512 different ports -- keep the
-        Gram records in last_gram ([blocks, P (P + 1) / 2] float64; one-shard engines only; None: off)."""
+        Gram records in last_gram ([blocks, P (P + 1) / 2] float64; one-shard engines only; None: off).  tapfits: a list of (target port,
+        [term ports], taps) -- keep the tap-fit records in last_tapfit ([blocks, D] float64; one-shard engines only; None: off)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
@@ -586,6 +668,7 @@ class Engine:
         nb = self._set_blends(blends, blend_gain)            # before the alignment list, which may name blend ports
         fitted = self._set_fits(fits)
         grammed = self._set_gram(gram)
+        tapped = self._set_tapfits(tapfits)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -630,19 +713,21 @@ class Engine:
             self.last_fit = self._fetch_fit()
         if grammed:
             self.last_gram = self._fetch_gram()
+        if tapped:
+            self.last_tapfit = self._fetch_tapfit()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces (and one per blend of blends= / blend_gain=, as batch_run's).  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]; fits=: last_fit likewise,
-        [fits, blocks]; gram=: last_gram likewise, [blocks, P (P + 1) / 2]."""
+        [fits, blocks]; gram=: last_gram likewise, [blocks, P (P + 1) / 2]; tapfits=: last_tapfit likewise, [blocks, D]."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
                                   metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
-                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram)
+                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -667,7 +752,7 @@ class Engine:
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
@@ -677,6 +762,7 @@ class Engine:
         nb = self._set_blends(blends, blend_gain)            # the sharded form passes none: off
         fitted = self._set_fits(fits)                        # ... and no fits
         grammed = self._set_gram(gram)                       # ... and no Gram list
+        tapped = self._set_tapfits(tapfits)                  # ... and no tap fits
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -734,6 +820,9 @@ class Engine:
                 if grammed:
                     gm = self._fetch_gram()
                     self.last_gram = gm if self.last_gram is None else np.concatenate([self.last_gram, gm], axis=0)
+                if tapped:
+                    tf = self._fetch_tapfit()
+                    self.last_tapfit = tf if self.last_tapfit is None else np.concatenate([self.last_tapfit, tf], axis=0)
                 yield outs
                 left -= blocks
         finally:

@@ -1096,6 +1096,44 @@ Error Engine::LastBatchGram(std::vector<double> &records, int *ports, size_t *bl
     return "";
 }
 
+/* Engine::SetBatchTapFits: validated whole before the list replaces the one in force (the library checks again, and the ports against the job's) */
+Error Engine::SetBatchTapFits(const std::vector<TapFit> &fits) {
+    if (fits.empty()) { tapFitFirst_.clear(); tapFitPort_.clear(); tapFitTarget_.clear(); tapFitTaps_.clear(); return ""; }
+    if (shards() > 1)
+        return format("SetBatchTapFits: the engine has %d shards: a fit's ports are rows of one device's window, and the library's shard calls refuse tap fits; it needs a "
+                      "one-shard engine", shards());
+    if (fits.size() > GDG_TAPFIT_MAX_FITS) return format("SetBatchTapFits: %zu fits; 0 (off) to %d", fits.size(), GDG_TAPFIT_MAX_FITS);
+    std::vector<int> first(1, 0), port, target, taps;
+    for (size_t f = 0; f < fits.size(); f++) {
+        const TapFit &t = fits[f];
+        if (t.ports.empty() || t.ports.size() > GDG_TAPFIT_MAX_TERMS) return format("SetBatchTapFits: fit %zu has %zu terms; 1 to %d", f, t.ports.size(), GDG_TAPFIT_MAX_TERMS);
+        if (t.taps < 1 || t.taps > GDG_BLEND_MAX_TAPS) return format("SetBatchTapFits: fit %zu has %d taps per term; 1 to %d", f, t.taps, GDG_BLEND_MAX_TAPS);
+        if ((int)t.ports.size() * t.taps > GDG_TAPFIT_MAX_UNKNOWNS)
+            return format("SetBatchTapFits: fit %zu has %zu terms x %d taps = %d unknowns; at most %d", f, t.ports.size(), t.taps, (int)t.ports.size() * t.taps, GDG_TAPFIT_MAX_UNKNOWNS);
+        if (t.target < 0) return format("SetBatchTapFits: fit %zu has the target port %d; ports start at 0", f, t.target);
+        for (size_t k = 0; k < t.ports.size(); k++) if (t.ports[k] < 0) return format("SetBatchTapFits: fit %zu, term %zu names port %d; ports start at 0", f, k, t.ports[k]);
+        port.insert(port.end(), t.ports.begin(), t.ports.end());
+        first.push_back((int)port.size());
+        target.push_back(t.target);
+        taps.push_back(t.taps);
+    }
+    tapFitFirst_.swap(first); tapFitPort_.swap(port); tapFitTarget_.swap(target); tapFitTaps_.swap(taps);
+    return "";
+}
+
+int Engine::applyTapFits(gdg_ctx *ctx) {
+    if (tapFitTarget_.empty()) return gdg_batch_tapfit_enable(ctx, 0, nullptr, nullptr, nullptr, nullptr);
+    return gdg_batch_tapfit_enable(ctx, BatchTapFits(), tapFitFirst_.data(), tapFitPort_.data(), tapFitTarget_.data(), tapFitTaps_.data());
+}
+
+Error Engine::LastBatchTapFit(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const {
+    if (!tapFitValid_) return "LastBatchTapFit: the last batch call kept no tap-fit records (SetBatchTapFits comes before the call)";
+    records = lastTapFit_;
+    if (blocks) *blocks = tapFitBlocks_;
+    if (doublesPerBlock) *doublesPerBlock = tapFitDoubles_;
+    return "";
+}
+
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
  * Process call and takes the window; the job's length is the longest shard's (the reference pads every channel to the longest input,
  * controller.go:3005-3045). */
@@ -1121,7 +1159,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1141,7 +1179,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { gramValid_ = BatchGramPorts() > 0; gramBlocks_ = 0; gramPorts_ = BatchGramPorts(); lastGram_.clear(); fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
+    if (job == 0) { tapFitValid_ = BatchTapFits() > 0; tapFitBlocks_ = 0; tapFitDoubles_ = tapFitValid_ ? gdg_tapfit_doubles(BatchTapFits(), tapFitFirst_.data(), tapFitTaps_.data()) : 0; lastTapFit_.clear(); gramValid_ = BatchGramPorts() > 0; gramBlocks_ = 0; gramPorts_ = BatchGramPorts(); lastGram_.clear(); fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
     /* blends or fits in force (one shard: SetBatchBlends, SetBatchFits): the library's plain one-call run -- its shard calls refuse both --
      * with `outs` of N + 3 + B entries; the alignment list goes on in its plain form, and the context's records of every kind are the engine's */
     if (plainRun()) {
@@ -1199,7 +1237,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
  * [N + 3][blocks] in gdg_batch_run's port order and from three sources -- the shards' chain rows, shard 0's metronome row, the finish's two
  * master rows (which carry no alignment records: over shards those rows stay zero) ---- */
 void Engine::reportBegin(size_t blocks) {
-    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = false;
+    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = tapFitValid_ = false;
     reportBlocks_ = blocks;
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
     const size_t n = (size_t)ports() * blocks;
@@ -1401,7 +1439,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1457,6 +1495,17 @@ Error Engine::recordsOfContext(gdg_ctx *ctx) {
             gramPorts_ = BatchGramPorts();
             if (!lastGram_.empty() && gdg_batch_gram(ctx, lastGram_.data(), lastGram_.size(), &blocks) != GDG_OK) re = gdg_last_error(ctx);
             else gramValid_ = true;
+        }
+    }
+    if (re.empty() && BatchTapFits() > 0) {                /* the tap-fit records: [blocks][D] */
+        size_t blocks = 0, per = 0;
+        if (gdg_batch_tapfit(ctx, nullptr, 0, &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
+        else {
+            lastTapFit_.assign(blocks * per, 0.0);
+            tapFitBlocks_ = blocks;
+            tapFitDoubles_ = per;
+            if (!lastTapFit_.empty() && gdg_batch_tapfit(ctx, lastTapFit_.data(), lastTapFit_.size(), &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
+            else tapFitValid_ = true;
         }
     }
     if (!re.empty()) { setError(re); return LastError(); }
@@ -2066,6 +2115,32 @@ const char *gdgh_engine_last_batch_gram(void *e, double *records, size_t capacit
     if (blocks) *blocks = b;
     if (records) {
         if (capacity < rec.size()) return ret(Error("LastBatchGram: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(double));
+    }
+    return ret(Error(""));
+}
+/* n_fits == 0: off; the list in the CSR form of gdg_batch_tapfit_enable */
+const char *gdgh_engine_set_batch_tapfits(void *e, int n_fits, const int *first, const int *port, const int *target, const int *taps) {
+    if (!e) return ret(Error("no engine"));
+    if (n_fits < 0 || (n_fits > 0 && (!first || !port || !target || !taps))) return ret(Error("SetBatchTapFits: n_fits >= 0, and the four lists"));
+    std::vector<Engine::TapFit> fits;
+    for (int f = 0; f < n_fits; f++) {
+        if (first[f] < 0 || first[f + 1] < first[f]) return ret(Error("SetBatchTapFits: the offsets start at 0 and never descend"));
+        fits.push_back({ target[f], std::vector<int>(port + first[f], port + first[f + 1]), taps[f] });
+    }
+    return ret(((Engine *)e)->SetBatchTapFits(fits));
+}
+int gdgh_engine_batch_tapfits(void *e) { return ((Engine *)e)->BatchTapFits(); }
+/* records == NULL: the two counts only; capacity in doubles */
+const char *gdgh_engine_last_batch_tapfit(void *e, double *records, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
+    std::vector<double> rec;
+    size_t b = 0, d = 0;
+    Error err = ((Engine *)e)->LastBatchTapFit(rec, &b, &d);
+    if (!err.empty()) return ret(err);
+    if (blocks) *blocks = b;
+    if (doubles_per_block) *doubles_per_block = d;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchTapFit: too little room for the records"));
         if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(double));
     }
     return ret(Error(""));

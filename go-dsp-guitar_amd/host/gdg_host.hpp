@@ -313,6 +313,15 @@ public:
     Error SetBatchGram(const std::vector<int> &ports);
     int BatchGramPorts() const { return (int)gramPort_.size(); }
     Error LastBatchGram(std::vector<double> &records, int *ports, size_t *blocks) const;
+    /* No reference counterpart.  The tap fits (include/gdg.h, gdg_batch_tapfit_enable): per fit a target port, 1 to 4 term ports and 1 to 64 taps
+     * per term, at most 128 unknowns, up to 16 fits.  While fits are in force BatchRun and the plain streamed job keep one tap-fit record per
+     * block (LastBatchTapFit: [blocks][D] doubles) for gdg_blend_taps_from_tapfit.  Refused with more than one shard, as the fits are and for
+     * their reason; BatchRun of a one-shard engine with tap fits is the library's plain gdg_batch_run.  The ports' upper bound is checked when
+     * a job is described.  A refused list leaves the one in force; an empty list: off. */
+    struct TapFit { int target; std::vector<int> ports; int taps; };
+    Error SetBatchTapFits(const std::vector<TapFit> &fits);
+    int BatchTapFits() const { return (int)tapFitTarget_.size(); }
+    Error LastBatchTapFit(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const;
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -394,7 +403,12 @@ private:
     int gramPorts_ = 0;                                    /* P of lastGram_ */
     bool gramValid_ = false;
     int applyGram(gdg_ctx *ctx);                           /* onto a context (more shards: none is in force): a gdg_* status */
-    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0; }      /* BatchRun is the library's plain one-call run */
+    std::vector<int> tapFitFirst_, tapFitPort_, tapFitTarget_, tapFitTaps_;      /* SetBatchTapFits, in the CSR form of the C call; no target: off */
+    std::vector<double> lastTapFit_;                       /* [blocks][D] of the last batch call that kept them */
+    size_t tapFitBlocks_ = 0, tapFitDoubles_ = 0;
+    bool tapFitValid_ = false;
+    int applyTapFits(gdg_ctx *ctx);                        /* onto a context (more shards: none are in force): a gdg_* status */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

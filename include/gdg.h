@@ -1382,6 +1382,81 @@ int gdg_block_gram_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_st
                                double *d_records);
 int gdg_blend_pick_from_gram(const double *records, int n_ports, size_t blocks, int target, const int *candidate, int n_candidates, int max_terms, double ridge,
                              double min_gain, int *picked, double *weight, double *residual, int *n_picked);
+/*
+ * TAPFIT: no reference counterpart.  gdg_batch_set_blends_filtered gives every blend term up to 64 taps; until here the only taps the library
+ * could make were windowed sincs.  "Which T-tap filter on this rig, or on these two microphone positions, comes closest to THAT track?" is
+ * the fit's and the pick's normal-equations problem over shifted copies of a row.  A tap-fit record holds its sums per block; a host planner
+ * solves them for the taps.  Stateless: a function of the block's samples alone.
+ * FIT: a tap fit f has a target port t, term ports p_0 .. p_(K-1) and a tap count T, the same for all its terms: 1 <= K <=
+ * GDG_TAPFIT_MAX_TERMS (4), 1 <= T <= GDG_BLEND_MAX_TAPS (64), U = K T <= GDG_TAPFIT_MAX_UNKNOWNS (128); up to GDG_TAPFIT_MAX_FITS (16) fits.
+ * Ports are rows of the batch window, 0 .. N + 2 + B, read as the record kernels read them: before the trim, a blend port's s before g_b.  A
+ * port may repeat and the target may be a term: the planner refuses what it cannot solve.
+ * VIRTUAL ROWS: V = U + 1.  Row v = j T + a is term j at lag a, a = 0 .. T - 1; row U is the target at lag 0.  For a block of L samples that
+ * starts at `first`, n = 0 .. L - T and i = first + T - 1 + n: row (j, a) has the value x[p_j][i - a], the target x[t][i].  Nothing outside
+ * [first, first + L) is ever read: the first T - 1 samples of a block appear only as lags (stateless, like the 23 intervals the true peak
+ * skips).  L < T: every entry is +0.0.
+ * RECORD: the lower triangle of the V x V Gram matrix of the virtual rows, V (V + 1) / 2 doubles, entry (u, v), v <= u, at u (u + 1) / 2 + v --
+ * the Gram record's layout.  No header.  A block's record is the concatenation over the fits in list order: D = sum_f V_f (V_f + 1) / 2
+ * doubles per block (gdg_tapfit_doubles).
+ * ORDER OF THE SUM: the Gram record's.  Entry (u, v) is one accumulator chain of v_mfma_f64_16x16x4_f64 started at +0.0 over n = 0, 4, 8, ...
+ * ascending; positions behind L - T count as +0.0.  The chain is never split over waves or workgroups, uses no atomics and has no second
+ * pass: an entry depends on the block's samples of its two ports, the two lags and T, and on nothing else -- not on K, the fit's position,
+ * the other fits, the window, the slicing, a resume, a source map or the grid.  Two consequences:
+ *   With T = 1 and different ports the record is bit for bit the gdg_block_gram_rows record of the list { p_0 .. p_(K-1), t }.
+ *   For any T the record of one block is bit for bit what gdg_block_gram_rows returns for the V shifted rows written out on the host
+ *   (row_v[n] as above, L - T + 1 samples, block = L - T + 1).
+ * The fits come in CSR form, like the blend fits: fit f has the terms port[first[f] .. first[f + 1]), the target target[f] and taps[f] = T.
+ *   gdg_batch_tapfit_enable(ctx, n_fits, first, port, target, taps)
+ *                                                      the list; n_fits == 0: off (the lists may be NULL).  The whole list is validated
+ *                                                      before it replaces the list in force; GDG_ERR_INVALID names the fit and the term.
+ *                                                      Refused while a streamed job is open.
+ *   gdg_batch_tapfits(ctx)                             the number of tap fits in force
+ *   gdg_batch_tapfit(ctx, out, capacity, &blocks, &doubles_per_block)
+ *                                                      the [blocks][D] doubles of the LAST COMPLETED batch call; out == NULL: the counts
+ *                                                      only; capacity in doubles.  GDG_ERR_INVALID when capacity is too small, or when there
+ *                                                      are no records: no call has completed since the switch, or the last one was a master finish.
+ *   gdg_tapfit_doubles(n_fits, first, taps)            D, pure arithmetic (0 for no fit)
+ * Port numbers are checked when a job is described -- gdg_batch_run, gdg_batch_stream_open, gdg_batch_stream_resume -- against N + 3 + B of
+ * that call; a port at or beyond it is GDG_ERR_INVALID with the fit and the term named.
+ * OFF: n_fits == 0, or never called.  Off, no launch, buffer, upload byte or output byte differs from a context that never heard of the call,
+ * and option stat_batch_device_kib is unchanged; on, it counts the table and the records' room in the download halves.
+ * Configuration, like the fits: it holds from the next batch call on, is part of no blob -- set it again on the target of a resume -- and a
+ * checkpoint and a resume work with tap fits on.  The records come down with each step's own download, behind the Gram section.
+ * SHARDS: gdg_batch_run_shard, gdg_batch_stream_open_shard, gdg_batch_stream_step_shard and gdg_batch_stream_resume_shard return
+ * GDG_ERR_UNSUPPORTED while tap fits are in force on their context.  gdg_batch_finish_master and gdg_batch_finish_master_slice never collect tap-fit records.
+ * The record on its own, over any rows and any block length >= 1 (ports name rows 0 .. n_rows - 1; the last block of a row may be short);
+ * both blocking -- the lists are host memory:
+ *   gdg_block_tapfit_rows(ctx, rows, n_rows, samples, block, n_fits, first, port, target, taps, records)
+ *                                                      host rows of `samples` float64; records: [ceil(samples / block)][D]
+ *   gdg_block_tapfit_rows_device(ctx, d_rows, row_stride, n_rows, samples, block, n_fits, first, port, target, taps, d_records)
+ *                                                      device rows, 8-byte aligned: row r at d_rows + r * row_stride (row_stride >=
+ *                                                      samples); no sample outside [row, row + samples) is read; d_records: device
+ *                                                      memory, 8-byte aligned
+ * THE PLANNER, pure host arithmetic (csrc/blend.h), no context and no device (gdg_last_error(NULL) says what was refused):
+ *   gdg_blend_taps_from_tapfit(records, n_fits, first, taps, blocks, ridge, tap, residual)
+ *                                                      records[blocks][D] as gdg_batch_tapfit hands them out, blocks >= 1; tap gets U_f
+ *                                                      doubles per fit, concatenated, term by term, lag ascending; residual[n_fits]
+ * Per fit the blocks' records are added in block order with plain double adds.  A = G[0 .. U)[0 .. U), b = G[U][0 .. U), Tt = G[U][U];
+ * (A + ridge * mean(diag A) * I) h = b is solved by an unpivoted Cholesky factorisation in virtual-row order.  A pivot at or below U * 2^-52 *
+ * max(diag A) is refused -- nothing is written, and the fit, the term and the lag are named -- and so is a NaN or inf entry.  residual =
+ * max(0, Tt - 2 h.b + h'Ah) / Tt, and 0 when Tt == 0.  This is the fit planner's solve at any size: for U <= 8 the taps are bit for bit the
+ * weights gdg_blend_weights_from_fit returns for a gdg_block_fit holding the same sums.  The taps are used as they come: term j of the blend
+ * is (p_j's channel, weight 1.0, delay d_j, h_j) of gdg_batch_set_blends_filtered.
+ * CONDITIONING: band-limited material -- a low-passed rig, an oversampled track -- makes the shifted copies of a row nearly dependent and A
+ * ill-conditioned: the taps then carry large, cancelling values, or a pivot is refused.  ridge > 0 is the remedy; 1e-9 .. 1e-6 is a usual range.
+ */
+#define GDG_TAPFIT_MAX_TERMS 4
+#define GDG_TAPFIT_MAX_UNKNOWNS 128
+#define GDG_TAPFIT_MAX_FITS 16
+int gdg_batch_tapfit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *port, const int *target, const int *taps);
+int gdg_batch_tapfits(const gdg_ctx *ctx);
+int gdg_batch_tapfit(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks, size_t *doubles_per_block);
+int gdg_block_tapfit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port,
+                          const int *target, const int *taps, double *records);
+int gdg_block_tapfit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
+                                 const int *port, const int *target, const int *taps, double *d_records);
+size_t gdg_tapfit_doubles(int n_fits, const int *first, const int *taps);
+int gdg_blend_taps_from_tapfit(const double *records, int n_fits, const int *first, const int *taps, size_t blocks, double ridge, double *tap, double *residual);
 
 #ifdef __cplusplus
 
