@@ -122,16 +122,9 @@ struct BatchLoop {
     /* while a term reaches back (a delay, or taps behind the first): the context's history of the N chain rows -- what the step before left
      * of them, zeros at the job's start; null otherwise, and then no sample a term reads lies in front of the job */
     double *d_blend_history;
-    /* the blend fits: n_fits entries of the table (blend.h, FitSet) on the host and on the device; 0 = off, and always for a shard */
-    int n_fits;
-    const int *h_fit_table, *d_fit_table;
-    /* the Gram list: n_gram ports on the host and on the device; 0 = off, and always for a shard */
-    int n_gram;
-    const int *h_gram_port, *d_gram_port;
-    /* the tap fits: n_tapfits entries of the table (blend.h, TapFitSet) on the host and on the device, D doubles per block; 0 = off, and always for a shard */
-    int n_tapfits;
-    size_t tapfit_doubles;
-    const int *h_tapfit_table, *d_tapfit_table;
+    /* the list records (report_sections.h: the blend fits, the Gram list, the tap fits): per kind the list's table on the host and on the
+     * device, the entries it counts and what it sends down per block; count 0 and a shape that is off = off, and always for a shard */
+    struct List { const int *h_table, *d_table; int count; ListShape shape; } list[LIST_KINDS];
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -171,7 +164,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; FitSection fit; GramSection gram; TapFitSection tapfit; };
+    struct Step { size_t off; int w; ReportSections sec; ListSections lists; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -183,7 +176,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {}, {}, {}, {} });
+        steps.push_back({ off, w, {}, {} });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
@@ -196,11 +189,10 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
     };
     const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NR;
+    const ListShape list_shape[LIST_KINDS] = { p.list[LIST_FIT].shape, p.list[LIST_GRAM].shape, p.list[LIST_TAPFIT].shape };
     for (size_t i = 0; i < steps.size(); i++) {
         steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
-        steps[i].fit = fit_section(steps[i].sec.end, (size_t)p.n_fits, (size_t)steps[i].w);      /* behind the last of them: [fits][w] */
-        steps[i].gram = gram_section(steps[i].fit.end, (size_t)p.n_gram, (size_t)steps[i].w);    /* ... and behind those: [w] */
-        steps[i].tapfit = tapfit_section(steps[i].gram.end, p.n_tapfits ? p.tapfit_doubles : 0, (size_t)steps[i].w);      /* ... and the tap fits': [w] */
+        steps[i].lists = list_sections(steps[i].sec.end, list_shape, (size_t)steps[i].w);        /* behind the last of them: [fits][w], [w], [w] */
     }
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
@@ -240,9 +232,8 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         }
         for (int k = 0; k < REPORT_KINDS; k++)                               /* the last piece brought the step's sections: filed under the step's blocks */
             if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
-        if (p.n_fits) fit_file(ctx, src + steps[i].fit.at, (size_t)steps[i].w, steps[i].off / B);
-        if (p.n_gram) gram_file(ctx, src + steps[i].gram.at, (size_t)steps[i].w, steps[i].off / B);
-        if (p.n_tapfits) tapfit_file(ctx, src + steps[i].tapfit.at, (size_t)steps[i].w, steps[i].off / B);
+        for (int k = 0; k < LIST_KINDS; k++)
+            if (p.list[k].count) list_file(ctx, k, src + steps[i].lists.of[k].at, (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -306,15 +297,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 HIP_TRY(ctx, gdg_launch_block_true_peak(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, true_peak_table(), tp, ctx->stream));
                 if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_true_peak(d_metro, ws, 1u, (size_t)wb, true_peak_table(), tp + (size_t)N * w, ctx->stream));
             }
-            if (p.n_fits)                                                    /* the fits' inner products of the same rows, the blends' among them */
-                HIP_TRY(ctx, gdg_launch_block_fit(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_fit_table, p.d_fit_table, (unsigned)p.n_fits,
-                                                  enc + steps[i].fit.at, ctx->stream));
-            if (p.n_gram)                                                    /* the Gram of the listed rows, on the matrix cores */
-                HIP_TRY(ctx, gdg_launch_block_gram(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_gram_port, p.d_gram_port, (unsigned)p.n_gram,
-                                                   reinterpret_cast<double *>(enc + steps[i].gram.at), ctx->stream));
-            if (p.n_tapfits)                                                 /* the tap fits' Gram of shifted rows, likewise */
-                HIP_TRY(ctx, gdg_launch_block_tapfit(d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.h_tapfit_table, p.d_tapfit_table, (unsigned)p.n_tapfits,
-                                                     reinterpret_cast<double *>(enc + steps[i].tapfit.at), ctx->stream));
+            /* the list records of the same rows, the blends' among them: the fits' inner products, then the Gram of the listed rows and the
+             * tap fits' Gram of shifted rows on the matrix cores */
+            for (int k = 0; k < LIST_KINDS; k++)
+                if (p.list[k].count)
+                    HIP_TRY(ctx, list_launch[k](d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.list[k].h_table, p.list[k].d_table, (unsigned)p.list[k].count,
+                                                enc + steps[i].lists.of[k].at, ctx->stream));
             /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: the trimmed siblings of either; `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
@@ -350,7 +338,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = steps[i].tapfit.end;
+        const size_t down = steps[i].lists.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -554,19 +542,30 @@ int gdg_batch_blends(const gdg_ctx *ctx) { return ctx ? ctx->blend.count() : 0; 
 int gdg_batch_blend_max_delay(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_delay() : 0; }
 int gdg_batch_blend_max_reach(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_reach() : 0; }
 
+/* Whether taking a new list of kind k drops the last call's records of that kind.  A fit record carries its own term count and stays
+ * readable; a Gram or tap-fit record is read with the list that made it. */
+static const bool list_enable_drops_records[LIST_KINDS] = { false, true, true };
+
+/* What the three gdg_batch_*_enable calls do once their list is checked, in front of taking it.  `resized`: the list sends down another
+ * size than the one in force -- the download halves are made anew by the next batch call, at the size of a context that was always
+ * configured like this one -- whatever still reads them has to be done first -- and off, the table goes as well */
+static int list_enable(gdg_ctx *ctx, int k, bool resized) {
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    if (resized) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i : { (int)BATCH_ENCODED, (int)BATCH_FIT_TABLE + k }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    }
+    if (list_enable_drops_records[k]) ctx->list_rec[k].valid = false;
+    return GDG_OK;
+}
+
 /* the blend fits: validated whole before the list replaces the one in force (blend.h); the ports' upper bound is the job's, checked when one is described */
 int gdg_batch_fit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *port, const int *target) {
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "batch fit: a streamed batch run is open on this context; its fits hold until gdg_batch_stream_close");
-    const int rc = fit_list_check(ctx, "batch fit", n_fits, first, port, target, -1);      /* the ports' upper bound is the job's */
+    int rc = fit_list_check(ctx, "batch fit", n_fits, first, port, target, -1);            /* the ports' upper bound is the job's */
     if (rc != GDG_OK) return rc;
-    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
-    if (n_fits != ctx->fit.count()) {
-        /* another count: the download halves are made anew by the next batch call, at the size of a context that was always configured like
-         * this one -- whatever still reads them has to be done first -- and off, the table goes as well */
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i : { (int)BATCH_ENCODED, (int)BATCH_FIT_TABLE }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
-    }
+    if ((rc = list_enable(ctx, LIST_FIT, n_fits != ctx->fit.count())) != GDG_OK) return rc;
     ctx->fit.table = gdg_fit_table(n_fits, first, port, target);
     return GDG_OK;
 }
@@ -581,15 +580,9 @@ int gdg_batch_gram_enable(gdg_ctx *ctx, const int *port, int n_ports) {
         const int rc = gram_list_check(ctx, "batch gram", port, n_ports, 2, -1);
         if (rc != GDG_OK) return rc;
     }
-    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
-    if ((size_t)n_ports != ctx->gram_port.size()) {
-        /* another count: the download halves are made anew by the next batch call, at the size of a context that was always configured like
-         * this one -- whatever still reads them has to be done first -- and off, the list goes as well */
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i : { (int)BATCH_ENCODED, (int)BATCH_GRAM_PORTS }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
-    }
+    const int rc = list_enable(ctx, LIST_GRAM, (size_t)n_ports != ctx->gram_port.size());
+    if (rc != GDG_OK) return rc;
     ctx->gram_port.assign(port, port + n_ports);
-    ctx->gram_rec.valid = false;                                             /* records are read with the list that made them */
     return GDG_OK;
 }
 
@@ -604,18 +597,11 @@ int gdg_batch_gram_ports(const gdg_ctx *ctx, int *port, int capacity) {
 int gdg_batch_tapfit_enable(gdg_ctx *ctx, int n_fits, const int *first, const int *port, const int *target, const int *taps) {
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "batch tapfit: a streamed batch run is open on this context; its list holds until gdg_batch_stream_close");
-    const int rc = tapfit_list_check(ctx, "batch tapfit", n_fits, first, port, target, taps, -1);
+    int rc = tapfit_list_check(ctx, "batch tapfit", n_fits, first, port, target, taps, -1);
     if (rc != GDG_OK) return rc;
-    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
     std::vector<int> table = gdg_tapfit_table(n_fits, first, port, target, taps);
-    if (table.size() != ctx->tapfit.table.size() || gdg_tapfit_list_doubles(n_fits, first, taps) != ctx->tapfit.doubles()) {
-        /* another size: the download halves are made anew by the next batch call, at the size of a context that was always configured like
-         * this one -- whatever still reads them has to be done first -- and off, the table goes as well */
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i : { (int)BATCH_ENCODED, (int)BATCH_TAPFIT_TABLE }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
-    }
+    if ((rc = list_enable(ctx, LIST_TAPFIT, table.size() != ctx->tapfit.table.size() || gdg_tapfit_list_doubles(n_fits, first, taps) != ctx->tapfit.doubles())) != GDG_OK) return rc;
     ctx->tapfit.table.swap(table);
-    ctx->tapfit_rec.valid = false;                                           /* records are read with the list that made them */
     return GDG_OK;
 }
 
@@ -632,17 +618,18 @@ int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
 #define BLENDS_REFUSED(ctx, what) \
     fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d blends are in force on this context (gdg_batch_set_blends); a sharded job cannot write blend outputs yet", what, (ctx)->blend.count())
 
-/* ... and a fit's ports are rows of the one-device window: the same refusal */
-#define FITS_REFUSED(ctx, what) \
-    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d fits are in force on this context (gdg_batch_fit_enable); a sharded job cannot collect fit records yet", what, (ctx)->fit.count())
-
-/* ... and so are a Gram list's */
-#define GRAM_REFUSED(ctx, what) \
-    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: a Gram list of %d ports is in force on this context (gdg_batch_gram_enable); a sharded job cannot collect Gram records yet", what, (int)(ctx)->gram_port.size())
-
-/* ... and tap fits' */
-#define TAPFITS_REFUSED(ctx, what) \
-    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d tap fits are in force on this context (gdg_batch_tapfit_enable); a sharded job cannot collect tap-fit records yet", what, (ctx)->tapfit.count())
+/* ... and a fit's, a Gram list's and a tap fit's ports are rows of the one-device window: the same refusal, the first kind in force in its own words */
+int lists_refused(gdg_ctx *ctx, const char *what) {
+    static const char *const text[LIST_KINDS] = {
+        "%s: %d fits are in force on this context (gdg_batch_fit_enable); a sharded job cannot collect fit records yet",
+        "%s: a Gram list of %d ports is in force on this context (gdg_batch_gram_enable); a sharded job cannot collect Gram records yet",
+        "%s: %d tap fits are in force on this context (gdg_batch_tapfit_enable); a sharded job cannot collect tap-fit records yet" };
+    for (int k = 0; ctx && k < LIST_KINDS; k++) {
+        const int count = list_in_force(ctx, k).count;
+        if (count) return fail(ctx, GDG_ERR_UNSUPPORTED, text[k], what, count);
+    }
+    return GDG_OK;
+}
 
 #define SHARD_PORTS " (a shard: its N inputs, its N outputs, metronome, left, right)"
 static int check_meter_ports(gdg_ctx *ctx, const gdg_batch_options *opt, const char *note) {
@@ -762,9 +749,7 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
 int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t job_samples,
                                 int run_metronome, size_t *samples) {
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
-    if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_open_shard");
-    if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_stream_open_shard");
-    if (ctx && ctx->tapfit.count()) return TAPFITS_REFUSED(ctx, "gdg_batch_stream_open_shard");
+    if (const int rc = lists_refused(ctx, "gdg_batch_stream_open_shard")) return rc;
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
     if (ctx && opt && opt->metronome_to_master)
         return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_open_shard: metronome_to_master must be 0 -- a shard's master mix is a partial sum; pass the metronome's "
@@ -826,12 +811,11 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* the blends in force (never a shard's): NR rows of the window leave the device encoded, and every record kind has NR ports */
     const int n_blends = sharded ? 0 : ctx->blend.count(), NR = NO + n_blends;
     report_begin(ctx, sharded ? N + 1 : NR, (size_t)blocks, true, n_blends);
-    const int n_fits = sharded ? 0 : ctx->fit.count();                           /* never a shard's: its calls refuse them */
-    if (n_fits) fit_begin(ctx, (size_t)blocks);
-    const int n_gram = sharded ? 0 : (int)ctx->gram_port.size();                 /* never a shard's either */
-    if (n_gram) gram_begin(ctx, (size_t)blocks);
-    const int n_tapfits = sharded ? 0 : ctx->tapfit.count();                     /* nor tap fits */
-    if (n_tapfits) tapfit_begin(ctx, (size_t)blocks);
+    ListInForce lists[LIST_KINDS];                                               /* the lists in force; never a shard's: its calls refuse them */
+    for (int k = 0; k < LIST_KINDS; k++) {
+        lists[k] = sharded ? ListInForce{ nullptr, 0, 0, { 0, 0 } } : list_in_force(ctx, k);
+        if (lists[k].count) list_begin(ctx, k, (size_t)blocks);
+    }
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -856,8 +840,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
-                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + fit_room((size_t)n_fits, (size_t)W) + gram_room((size_t)n_gram, (size_t)W)
-                           + tapfit_room(n_tapfits ? ctx->tapfit.doubles() : 0, (size_t)W);
+                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + list_room(lists[LIST_FIT].shape, (size_t)W)
+                           + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -1027,33 +1011,16 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, nullptr, nullptr };
-        /* the fits in force: their table goes up on the context's stream, ahead of everything the slice enqueues there; it lives as long as
-         * the setting, so nothing waits here */
-        if (n_fits) {
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, {} };
+        /* the lists in force -- the fits' table, the Gram list, the tap fits' table: each goes up on the context's stream, ahead of everything
+         * the slice enqueues there; it lives as long as the setting, so nothing waits here */
+        for (int k = 0; k < LIST_KINDS; k++) {
+            const ListInForce &L = lists[k];
+            if (!L.count) continue;
             int *d_table = nullptr;
-            if ((r = batch_buffer(ctx, BATCH_FIT_TABLE, ctx->fit.table.size() * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
-            HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->fit.table.data(), ctx->fit.table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            loop.n_fits = n_fits;
-            loop.h_fit_table = ctx->fit.table.data();
-            loop.d_fit_table = d_table;
-        }
-        if (n_gram) {                                                        /* the Gram list likewise */
-            int *d_port = nullptr;
-            if ((r = batch_buffer(ctx, BATCH_GRAM_PORTS, (size_t)n_gram * sizeof(int), (void **)&d_port)) != GDG_OK) return r;
-            HIP_TRY(ctx, hipMemcpyAsync(d_port, ctx->gram_port.data(), (size_t)n_gram * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            loop.n_gram = n_gram;
-            loop.h_gram_port = ctx->gram_port.data();
-            loop.d_gram_port = d_port;
-        }
-        if (n_tapfits) {                                                     /* ... and the tap fits' table */
-            int *d_table = nullptr;
-            if ((r = batch_buffer(ctx, BATCH_TAPFIT_TABLE, ctx->tapfit.table.size() * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
-            HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->tapfit.table.data(), ctx->tapfit.table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            loop.n_tapfits = n_tapfits;
-            loop.tapfit_doubles = ctx->tapfit.doubles();
-            loop.h_tapfit_table = ctx->tapfit.table.data();
-            loop.d_tapfit_table = d_table;
+            if ((r = batch_buffer(ctx, BATCH_FIT_TABLE + k, L.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(d_table, L.table, L.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            loop.list[k] = { L.table, d_table, L.count, L.shape };
         }
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
@@ -1127,9 +1094,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 }
 
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
-    if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_stream_step_shard");
-    if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_stream_step_shard");
-    if (ctx && ctx->tapfit.count()) return TAPFITS_REFUSED(ctx, "gdg_batch_stream_step_shard");
+    if (const int rc = lists_refused(ctx, "gdg_batch_stream_step_shard")) return rc;
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
 
@@ -1153,9 +1118,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
     if (job.length == 0) {                                                       /* every output has 0 samples */
         ctx->batch_up_bytes = ctx->batch_resampled = 0;
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
-        if (!shard) fit_begin(ctx, 0);
-        if (!shard) gram_begin(ctx, 0);
-        if (!shard) tapfit_begin(ctx, 0);
+        for (int k = 0; k < LIST_KINDS && !shard; k++) list_begin(ctx, k, 0);
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
@@ -1175,9 +1138,7 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
                         const gdg_batch_shard_out *shard) {
     if (!shard) return GDG_ERR_INVALID;
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
-    if (ctx && ctx->fit.count()) return FITS_REFUSED(ctx, "gdg_batch_run_shard");
-    if (ctx && !ctx->gram_port.empty()) return GRAM_REFUSED(ctx, "gdg_batch_run_shard");
-    if (ctx && ctx->tapfit.count()) return TAPFITS_REFUSED(ctx, "gdg_batch_run_shard");
+    if (const int rc = lists_refused(ctx, "gdg_batch_run_shard")) return rc;
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
      * metronome track of the shard that ran it).  A set flag here would be silently dropped -- refuse it instead. */
     if (ctx && opt && opt->metronome_to_master)

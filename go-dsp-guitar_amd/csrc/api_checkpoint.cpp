@@ -389,15 +389,7 @@ int gdg_batch_stream_resume_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, i
     if (ctx && ctx->blend.count())
         return fail(ctx, GDG_ERR_UNSUPPORTED, "gdg_batch_stream_resume_shard: %d blends are in force on this context (gdg_batch_set_blends); a sharded job cannot write blend outputs yet",
                     ctx->blend.count());
-    if (ctx && ctx->fit.count())
-        return fail(ctx, GDG_ERR_UNSUPPORTED, "gdg_batch_stream_resume_shard: %d fits are in force on this context (gdg_batch_fit_enable); a sharded job cannot collect fit records yet",
-                    ctx->fit.count());
-    if (ctx && !ctx->gram_port.empty())
-        return fail(ctx, GDG_ERR_UNSUPPORTED, "gdg_batch_stream_resume_shard: a Gram list of %d ports is in force on this context (gdg_batch_gram_enable); a sharded job cannot collect Gram records yet",
-                    (int)ctx->gram_port.size());
-    if (ctx && ctx->tapfit.count())
-        return fail(ctx, GDG_ERR_UNSUPPORTED, "gdg_batch_stream_resume_shard: %d tap fits are in force on this context (gdg_batch_tapfit_enable); a sharded job cannot collect tap-fit records yet",
-                    ctx->tapfit.count());
+    if (const int rc = lists_refused(ctx, "gdg_batch_stream_resume_shard")) return rc;
     if (ctx && options && options->metronome_to_master)
         return fail(ctx, GDG_ERR_INVALID, "gdg_batch_stream_resume_shard: metronome_to_master must be 0, as for gdg_batch_stream_open_shard");
     return resume(ctx, inputs, n_inputs, options, true, job_samples, run_metronome != 0, blob, bytes, samples_done);

@@ -911,17 +911,68 @@ int fit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first,
     }
 }
 
-static int block_fit_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port, const int *target, size_t *blocks) {
-    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "block fit: %d rows (at least 1)", n_rows);
-    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block fit: blocks of %d samples (at least 1)", block);
-    const int rc = fit_list_check(ctx, "block fit", n_fits, first, port, target, n_rows);
+/* What the stand-alone calls and the getters of the three list records share (report_sections.h, LIST_KINDS; their list checks above and
+ * below differ and stay).  The rows, block and blocks-limit refusals around a kind's list check, in the words of the call `what`; `one`:
+ * "launch" or "call", as the kind words its limit. */
+template <class ListCheck>
+static int block_list_check(gdg_ctx *ctx, const char *what, const char *one, int n_rows, size_t samples, int block, const ListCheck &list_check, size_t *blocks) {
+    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "%s: %d rows (at least 1)", what, n_rows);
+    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "%s: blocks of %d samples (at least 1)", what, block);
+    const int rc = list_check();
     if (rc != GDG_OK) return rc;
     *blocks = (samples + (size_t)block - 1) / (size_t)block;
-    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block fit: %zu blocks per row are too many for one launch", *blocks);
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "%s: %zu blocks per row are too many for one %s", what, *blocks, one);
     return GDG_OK;
 }
 
-/* the table is the caller's host memory: it goes up, the kernel runs, and the call returns when the records are written */
+/* The device body of kind k behind its checked list: the table of `ints` ints is host memory -- it goes up, the kernel runs, and the call
+ * returns when the records are written */
+static int block_list_rows_device(gdg_ctx *ctx, int k, const char *what, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, const int *table,
+                                  size_t ints, int count, void *d_records) {
+    if (!d_rows || !d_records) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "%s: a row stride of %zu samples for rows of %zu", what, row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "%s: rows and records are 8-byte aligned", what);
+    enter_keep_fir_sums(ctx);
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, ints * sizeof(int)));
+    hipError_t e = hipMemcpyAsync(d, table, ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        e = list_launch[k](d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, table, static_cast<const int *>(d), (unsigned)count, d_records, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "%s: %s", what, hipGetErrorString(w));
+    return GDG_OK;
+}
+
+/* The getter of kind k: its own store, by the four kinds' rule and in their words (KindWords above): `none` opens the refusal of a call that
+ * kept nothing, `pending` / `without` end it with the list in force / off; `name` and `unit` word the refusal of too little room -- capacity
+ * counts records for the fits and doubles for the other two.  NULL gives the count of blocks alone. */
+struct ListWords { const char *none, *pending, *without, *name, *unit; };
+static int batch_list_get(gdg_ctx *ctx, int k, const ListWords &w, void *out, size_t capacity, size_t *blocks) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const gdg_ctx::ListRecords &R = ctx->list_rec[k];
+    if (!R.valid) return fail(ctx, GDG_ERR_INVALID, "%s: the last batch call of this context %s", w.none, list_in_force(ctx, k).count ? w.pending : w.without);
+    if (blocks) *blocks = R.blocks;
+    if (!out) return GDG_OK;
+    const size_t n = R.store.size() / (k == LIST_FIT ? R.elem : sizeof(double));
+    if (capacity < n) {
+        char has[64];
+        if (k == LIST_FIT) snprintf(has, sizeof has, "%d fits x %zu blocks", R.count, R.blocks);
+        else if (k == LIST_GRAM) snprintf(has, sizeof has, "%zu blocks x %d (%d + 1) / 2", R.blocks, R.count, R.count);
+        else snprintf(has, sizeof has, "%zu blocks x %zu", R.blocks, R.elem / sizeof(double));
+        return fail(ctx, GDG_ERR_INVALID, "%s: room for %zu %s, the call has %s = %zu", w.name, capacity, w.unit, has, n);
+    }
+    if (n) memcpy(out, R.store.data(), R.store.size());
+    return GDG_OK;
+}
+
+static int block_fit_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port, const int *target, size_t *blocks) {
+    return block_list_check(ctx, "block fit", "launch", n_rows, samples, block, [&] { return fit_list_check(ctx, "block fit", n_fits, first, port, target, n_rows); }, blocks);
+}
+
 int gdg_block_fit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
                               const int *port, const int *target, gdg_block_fit *d_records) {
     if (!ctx) return GDG_ERR_INVALID;
@@ -929,23 +980,8 @@ int gdg_block_fit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_str
     const int rc = block_fit_check(ctx, n_rows, samples, block, n_fits, first, port, target, &blocks);
     if (rc != GDG_OK) return rc;
     if (n_fits == 0 || samples == 0) return GDG_OK;
-    if (!d_rows || !d_records) return GDG_ERR_INVALID;
-    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block fit: a row stride of %zu samples for rows of %zu", row_stride, samples);
-    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block fit: rows and records are 8-byte aligned");
-    enter_keep_fir_sums(ctx);
     const std::vector<int> table = gdg_fit_table(n_fits, first, port, target);
-    void *d = nullptr;
-    HIP_TRY(ctx, ctx->arena.alloc(&d, table.size() * sizeof(int)));
-    hipError_t e = hipMemcpyAsync(d, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        ProfScope ps(ctx, GDG_K_WAVE);
-        e = gdg_launch_block_fit(d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, table.data(), static_cast<const int *>(d), (unsigned)n_fits, d_records, ctx->stream);
-    }
-    const hipError_t w = hipStreamSynchronize(ctx->stream);
-    ctx->arena.release(d);
-    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block fit: %s", hipGetErrorString(e));
-    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block fit: %s", hipGetErrorString(w));
-    return GDG_OK;
+    return block_list_rows_device(ctx, LIST_FIT, "block fit", d_rows, row_stride, n_rows, samples, block, table.data(), table.size(), n_fits, d_records);
 }
 
 int gdg_block_fit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port,
@@ -961,20 +997,11 @@ int gdg_block_fit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size
     });
 }
 
-/* the getter: the fits' own store, by the four kinds' rule and in their words */
 int gdg_batch_fit(gdg_ctx *ctx, gdg_block_fit *records, size_t capacity, int *fits, size_t *blocks) {
-    if (!ctx) return GDG_ERR_INVALID;
-    const gdg_ctx::FitRecords &F = ctx->fit_rec;
-    if (!F.valid)
-        return fail(ctx, GDG_ERR_INVALID, "no fit records: the last batch call of this context %s", ctx->fit.count()
-                    ? "has not completed, was a master finish, or none has run since gdg_batch_fit_enable" : "ran without them (gdg_batch_fit_enable comes before the call)");
-    if (fits) *fits = F.fits;
-    if (blocks) *blocks = F.blocks;
-    if (!records) return GDG_OK;
-    const size_t n = (size_t)F.fits * F.blocks;
-    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "fit: room for %zu records, the call has %d fits x %zu blocks = %zu", capacity, F.fits, F.blocks, n);
-    if (n) memcpy(records, F.store.data(), F.store.size());
-    return GDG_OK;
+    static const ListWords words = { "no fit records", "has not completed, was a master finish, or none has run since gdg_batch_fit_enable",
+                                     "ran without them (gdg_batch_fit_enable comes before the call)", "fit", "records" };
+    if (ctx && fits && ctx->list_rec[LIST_FIT].valid) *fits = ctx->list_rec[LIST_FIT].count;
+    return batch_list_get(ctx, LIST_FIT, words, records, capacity, blocks);
 }
 
 /* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
@@ -1021,38 +1048,16 @@ int gram_list_check(gdg_ctx *ctx, const char *what, const int *port, int n_ports
 }
 
 static int block_gram_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, const int *port, int n_ports, size_t *blocks) {
-    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "block gram: %d rows (at least 1)", n_rows);
-    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block gram: blocks of %d samples (at least 1)", block);
-    const int rc = gram_list_check(ctx, "block gram", port, n_ports, 1, n_rows);
-    if (rc != GDG_OK) return rc;
-    *blocks = (samples + (size_t)block - 1) / (size_t)block;
-    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block gram: %zu blocks per row are too many for one call", *blocks);
-    return GDG_OK;
+    return block_list_check(ctx, "block gram", "call", n_rows, samples, block, [&] { return gram_list_check(ctx, "block gram", port, n_ports, 1, n_rows); }, blocks);
 }
 
-/* the list is the caller's host memory: it goes up, the kernel runs, and the call returns when the records are written */
 int gdg_block_gram_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, const int *port, int n_ports, double *d_records) {
     if (!ctx) return GDG_ERR_INVALID;
     size_t blocks = 0;
     const int rc = block_gram_check(ctx, n_rows, samples, block, port, n_ports, &blocks);
     if (rc != GDG_OK) return rc;
     if (samples == 0) return GDG_OK;
-    if (!d_rows || !d_records) return GDG_ERR_INVALID;
-    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block gram: a row stride of %zu samples for rows of %zu", row_stride, samples);
-    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block gram: rows and records are 8-byte aligned");
-    enter_keep_fir_sums(ctx);
-    void *d = nullptr;
-    HIP_TRY(ctx, ctx->arena.alloc(&d, (size_t)n_ports * sizeof(int)));
-    hipError_t e = hipMemcpyAsync(d, port, (size_t)n_ports * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        ProfScope ps(ctx, GDG_K_WAVE);
-        e = gdg_launch_block_gram(d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, port, static_cast<const int *>(d), (unsigned)n_ports, d_records, ctx->stream);
-    }
-    const hipError_t w = hipStreamSynchronize(ctx->stream);
-    ctx->arena.release(d);
-    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block gram: %s", hipGetErrorString(e));
-    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block gram: %s", hipGetErrorString(w));
-    return GDG_OK;
+    return block_list_rows_device(ctx, LIST_GRAM, "block gram", d_rows, row_stride, n_rows, samples, block, port, (size_t)n_ports, n_ports, d_records);
 }
 
 int gdg_block_gram_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, const int *port, int n_ports, double *records) {
@@ -1067,19 +1072,11 @@ int gdg_block_gram_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, siz
     });
 }
 
-/* the getter: the Gram records' own store, by the four kinds' rule and in their words; capacity in doubles */
+/* capacity in doubles */
 int gdg_batch_gram(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks) {
-    if (!ctx) return GDG_ERR_INVALID;
-    const gdg_ctx::GramRecords &G = ctx->gram_rec;
-    if (!G.valid)
-        return fail(ctx, GDG_ERR_INVALID, "no Gram records: the last batch call of this context %s", !ctx->gram_port.empty()
-                    ? "has not completed, was a master finish, or none has run since gdg_batch_gram_enable" : "ran without them (gdg_batch_gram_enable comes before the call)");
-    if (blocks) *blocks = G.blocks;
-    if (!out) return GDG_OK;
-    if (capacity < G.store.size())
-        return fail(ctx, GDG_ERR_INVALID, "gram: room for %zu doubles, the call has %zu blocks x %d (%d + 1) / 2 = %zu", capacity, G.blocks, G.ports, G.ports, G.store.size());
-    if (!G.store.empty()) memcpy(out, G.store.data(), G.store.size() * sizeof(double));
-    return GDG_OK;
+    static const ListWords words = { "no Gram records", "has not completed, was a master finish, or none has run since gdg_batch_gram_enable",
+                                     "ran without them (gdg_batch_gram_enable comes before the call)", "gram", "doubles" };
+    return batch_list_get(ctx, LIST_GRAM, words, out, capacity, blocks);
 }
 
 /* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
@@ -1137,16 +1134,10 @@ size_t gdg_tapfit_doubles(int n_fits, const int *first, const int *taps) {
 }
 
 static int block_tapfit_check(gdg_ctx *ctx, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port, const int *target, const int *taps, size_t *blocks) {
-    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "block tapfit: %d rows (at least 1)", n_rows);
-    if (block < 1) return fail(ctx, GDG_ERR_INVALID, "block tapfit: blocks of %d samples (at least 1)", block);
-    const int rc = tapfit_list_check(ctx, "block tapfit", n_fits, first, port, target, taps, n_rows);
-    if (rc != GDG_OK) return rc;
-    *blocks = (samples + (size_t)block - 1) / (size_t)block;
-    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block tapfit: %zu blocks per row are too many for one call", *blocks);
-    return GDG_OK;
+    return block_list_check(ctx, "block tapfit", "call", n_rows, samples, block,
+                            [&] { return tapfit_list_check(ctx, "block tapfit", n_fits, first, port, target, taps, n_rows); }, blocks);
 }
 
-/* the table is made from the caller's host lists: it goes up, the kernel runs, and the call returns when the records are written */
 int gdg_block_tapfit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int block, int n_fits, const int *first,
                                  const int *port, const int *target, const int *taps, double *d_records) {
     if (!ctx) return GDG_ERR_INVALID;
@@ -1154,23 +1145,8 @@ int gdg_block_tapfit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_
     const int rc = block_tapfit_check(ctx, n_rows, samples, block, n_fits, first, port, target, taps, &blocks);
     if (rc != GDG_OK) return rc;
     if (n_fits == 0 || samples == 0) return GDG_OK;
-    if (!d_rows || !d_records) return GDG_ERR_INVALID;
-    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block tapfit: a row stride of %zu samples for rows of %zu", row_stride, samples);
-    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block tapfit: rows and records are 8-byte aligned");
-    enter_keep_fir_sums(ctx);
     const std::vector<int> table = gdg_tapfit_table(n_fits, first, port, target, taps);
-    void *d = nullptr;
-    HIP_TRY(ctx, ctx->arena.alloc(&d, table.size() * sizeof(int)));
-    hipError_t e = hipMemcpyAsync(d, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        ProfScope ps(ctx, GDG_K_WAVE);
-        e = gdg_launch_block_tapfit(d_rows, row_stride, (unsigned)n_rows, samples, (unsigned)block, table.data(), static_cast<const int *>(d), (unsigned)n_fits, d_records, ctx->stream);
-    }
-    const hipError_t w = hipStreamSynchronize(ctx->stream);
-    ctx->arena.release(d);
-    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block tapfit: %s", hipGetErrorString(e));
-    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block tapfit: %s", hipGetErrorString(w));
-    return GDG_OK;
+    return block_list_rows_device(ctx, LIST_TAPFIT, "block tapfit", d_rows, row_stride, n_rows, samples, block, table.data(), table.size(), n_fits, d_records);
 }
 
 int gdg_block_tapfit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int block, int n_fits, const int *first, const int *port,
@@ -1186,20 +1162,12 @@ int gdg_block_tapfit_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, s
     });
 }
 
-/* the getter: the tap fits' own store, by the four kinds' rule and in their words; capacity in doubles */
+/* capacity in doubles */
 int gdg_batch_tapfit(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
-    if (!ctx) return GDG_ERR_INVALID;
-    const gdg_ctx::TapFitRecords &F = ctx->tapfit_rec;
-    if (!F.valid)
-        return fail(ctx, GDG_ERR_INVALID, "no tap-fit records: the last batch call of this context %s", ctx->tapfit.count()
-                    ? "has not completed, was a master finish, or none has run since gdg_batch_tapfit_enable" : "ran without them (gdg_batch_tapfit_enable comes before the call)");
-    if (blocks) *blocks = F.blocks;
-    if (doubles_per_block) *doubles_per_block = F.doubles;
-    if (!out) return GDG_OK;
-    if (capacity < F.store.size())
-        return fail(ctx, GDG_ERR_INVALID, "tapfit: room for %zu doubles, the call has %zu blocks x %zu = %zu", capacity, F.blocks, F.doubles, F.store.size());
-    if (!F.store.empty()) memcpy(out, F.store.data(), F.store.size() * sizeof(double));
-    return GDG_OK;
+    static const ListWords words = { "no tap-fit records", "has not completed, was a master finish, or none has run since gdg_batch_tapfit_enable",
+                                     "ran without them (gdg_batch_tapfit_enable comes before the call)", "tapfit", "doubles" };
+    if (ctx && doubles_per_block && ctx->list_rec[LIST_TAPFIT].valid) *doubles_per_block = ctx->list_rec[LIST_TAPFIT].elem / sizeof(double);
+    return batch_list_get(ctx, LIST_TAPFIT, words, out, capacity, blocks);
 }
 
 /* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */

@@ -410,39 +410,24 @@ struct gdg_ctx {
     BlendSet blend;
     unsigned char *d_blend = nullptr;
     size_t d_blend_cap = 0;
-    /* the blend fits (gdg_batch_fit_enable; blend.h, report_sections.h): the list in force as the table a launch reads, empty = off.  While
-     * fits are in force batch_dev[BATCH_FIT_TABLE] holds the table -- uploaded at the start of a batch call -- and a download half has room for
-     * [fits][window] records behind the four kinds' sections; off, neither exists.  The records of the last completed batch call,
-     * [fits][blocks], live beside the four kinds' and by their rule: a call that collects (`live`, decided when it begins) fills the store
-     * step by step and validates it at its end; a master finish collects none.  Configuration like the blends: in no blob. */
+    /* the list records (report_sections.h, LIST_KINDS; blend.h), each list in force as the table of ints a launch reads, empty = off: the
+     * blend fits (gdg_batch_fit_enable), the Gram list (gdg_batch_gram_enable: the listed ports in list order) and the tap fits
+     * (gdg_batch_tapfit_enable).  While kind k's list is in force batch_dev[BATCH_FIT_TABLE + k] holds its table -- uploaded at the start of
+     * a batch call -- and a download half has room for its [rows][window] elements behind the four kinds' sections and the lists' before
+     * it; off, neither exists.  Configuration like the blends: in no blob. */
     FitSet fit;
-    struct FitRecords {
-        bool live = false, valid = false;
-        int fits = 0;
-        size_t blocks = 0;
-        std::vector<unsigned char> store;
-    } fit_rec;
-    /* the Gram list (gdg_batch_gram_enable; blend.h, report_sections.h): the listed ports in list order, empty = off.  While a list is in force
-     * batch_dev[BATCH_GRAM_PORTS] holds it -- uploaded at the start of a batch call -- and a download half has room for [window] records of
-     * P (P + 1) / 2 doubles behind the fit section; off, neither exists.  The records of the last completed batch call, [blocks][P (P + 1) / 2],
-     * by the fit records' rule.  Stateless configuration: in no blob. */
     std::vector<int> gram_port;
-    struct GramRecords {
-        bool live = false, valid = false;
-        int ports = 0;
-        size_t blocks = 0;
-        std::vector<double> store;
-    } gram_rec;
-    /* the tap fits (gdg_batch_tapfit_enable; blend.h, report_sections.h): the list in force as the table a launch reads, empty = off.  While
-     * fits are in force batch_dev[BATCH_TAPFIT_TABLE] holds the table -- uploaded at the start of a batch call -- and a download half has
-     * room for [window] records of D doubles behind the Gram section; off, neither exists.  The records of the last completed batch call,
-     * [blocks][D], by the fit records' rule.  Stateless configuration: in no blob. */
     TapFitSet tapfit;
-    struct TapFitRecords {
+    /* ... and their records of the last completed batch call, [rows][blocks] elements of `elem` bytes ([fits][blocks] records, [blocks]
+     * [P (P + 1) / 2] and [blocks][D] doubles) beside the four kinds' and by their rule: a call that collects (`live`, decided when it
+     * begins) fills the store step by step and validates it at its end; a master finish collects none.  `count`: the entries the list had
+     * when the call began (fits, ports, tap fits). */
+    struct ListRecords {
         bool live = false, valid = false;
-        size_t doubles = 0, blocks = 0;
-        std::vector<double> store;
-    } tapfit_rec;
+        int count = 0;
+        size_t rows = 0, elem = 0, blocks = 0;
+        std::vector<unsigned char> store;
+    } list_rec[LIST_KINDS];
     /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;
@@ -731,6 +716,8 @@ int state_load_device_with(gdg_ctx *ctx, const void *d_blob, size_t bytes, const
 int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
                bool run_metronome, gdg_ctx::BatchStreamState &job, bool meters_at_open = true);
 int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
+/* api_batch.cpp: what a shard's entry point `what` refuses while list records are in force -- fits, then the Gram list, then tap fits; GDG_OK: none is (or no context) */
+int lists_refused(gdg_ctx *ctx, const char *what);
 /* api_io.cpp: a list of fits against gdg_fit_check (blend.h), refused in the words of `what`; n_rows < 0: the port count is not known yet */
 int fit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, int n_rows);
 /* api_io.cpp: a Gram list of `least` to GDG_GRAM_MAX_PORTS ports against blend.h's checks, refused in the words of `what`; n_rows < 0: the port count is not known yet */
@@ -744,9 +731,7 @@ static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_hav
 static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool align = true, int blend_ports = 0) {
     ctx->spec_live_edges = ctx->spec_edges;
     ctx->align_live_ref.clear();
-    ctx->fit_rec.valid = ctx->fit_rec.live = false;                              /* a call that collects fits says so itself (fit_begin) */
-    ctx->gram_rec.valid = ctx->gram_rec.live = false;                            /* ... and so does one that collects Gram records (gram_begin) */
-    ctx->tapfit_rec.valid = ctx->tapfit_rec.live = false;                        /* ... or tap-fit records (tapfit_begin) */
+    for (gdg_ctx::ListRecords &R : ctx->list_rec) R.valid = R.live = false;      /* a call that collects list records says so itself (list_begin) */
     /* any other count was refused when the job was described; a list without the call's blend ports: each of them references itself */
     if (align && ((int)ctx->align_ref.size() == ports || (blend_ports > 0 && (int)ctx->align_ref.size() == ports - blend_ports))) {
         ctx->align_live_ref = ctx->align_ref;
@@ -766,57 +751,40 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
         K.store.assign((size_t)ports * blocks * K.elem, 0);
     }
 }
-/* behind report_begin, by the calls that collect fit records: zeroed records for the fits in force x `blocks` */
-static inline void fit_begin(gdg_ctx *ctx, size_t blocks) {
-    gdg_ctx::FitRecords &F = ctx->fit_rec;
-    F.live = ctx->fit.count() > 0;
-    if (!F.live) return;
-    F.fits = ctx->fit.count();
-    F.blocks = blocks;
-    F.store.assign((size_t)F.fits * blocks * FIT_RECORD_BYTES, 0);
+/* kind k's list in force: the table of ints a launch reads (the fits' and tap fits' tables, the Gram list's ports), the entries it counts
+ * (fits, ports, tap fits) and what it sends down per block; nothing in force: no int, count 0, a shape that is off */
+struct ListInForce { const int *table; size_t ints; int count; ListShape shape; };
+static inline ListInForce list_in_force(const gdg_ctx *ctx, int k) {
+    if (k == LIST_FIT) return { ctx->fit.table.data(), ctx->fit.table.size(), ctx->fit.count(), { (size_t)ctx->fit.count(), ctx->fit.count() ? (size_t)FIT_RECORD_BYTES : 0 } };
+    if (k == LIST_GRAM) return { ctx->gram_port.data(), ctx->gram_port.size(), (int)ctx->gram_port.size(), { 1, gram_record_bytes(ctx->gram_port.size()) } };
+    return { ctx->tapfit.table.data(), ctx->tapfit.table.size(), ctx->tapfit.count(), { 1, ctx->tapfit.doubles() * sizeof(double) } };
 }
-/* a step's fit section ([fits][w] records) that has come down, into the store under the blocks from b0 on */
-static inline void fit_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
-    gdg_ctx::FitRecords &F = ctx->fit_rec;
-    for (size_t f = 0; f < (size_t)F.fits; f++) memcpy(&F.store[(f * F.blocks + b0) * FIT_RECORD_BYTES], section + f * w * FIT_RECORD_BYTES, w * FIT_RECORD_BYTES);
+/* the three launchers take one argument list (gdg_internal.h): rows, stride, n_rows, samples, block, host table, device table, count, records, stream */
+typedef hipError_t ListLaunch(const double *, size_t, unsigned, size_t, unsigned, const int *, const int *, unsigned, void *, hipStream_t);
+static ListLaunch *const list_launch[LIST_KINDS] = { gdg_launch_block_fit, gdg_launch_block_gram, gdg_launch_block_tapfit };
+/* behind report_begin, by the calls that collect list records: zeroed records for kind k's list in force x `blocks` */
+static inline void list_begin(gdg_ctx *ctx, int k, size_t blocks) {
+    const ListInForce L = list_in_force(ctx, k);
+    gdg_ctx::ListRecords &R = ctx->list_rec[k];
+    R.live = L.shape.on();
+    if (!R.live) return;
+    R.count = L.count;
+    R.rows = L.shape.rows;
+    R.elem = L.shape.elem;
+    R.blocks = blocks;
+    R.store.assign(R.rows * blocks * R.elem, 0);
 }
-/* behind report_begin, by the calls that collect Gram records: zeroed records for the list in force x `blocks` */
-static inline void gram_begin(gdg_ctx *ctx, size_t blocks) {
-    gdg_ctx::GramRecords &G = ctx->gram_rec;
-    G.live = !ctx->gram_port.empty();
-    if (!G.live) return;
-    G.ports = (int)ctx->gram_port.size();
-    G.blocks = blocks;
-    G.store.assign(blocks * (gram_record_bytes((size_t)G.ports) / sizeof(double)), 0.0);
-}
-/* a step's Gram section ([w] records) that has come down, into the store under the blocks from b0 on */
-static inline void gram_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
-    gdg_ctx::GramRecords &G = ctx->gram_rec;
-    const size_t rec = gram_record_bytes((size_t)G.ports);
-    memcpy(reinterpret_cast<unsigned char *>(G.store.data()) + b0 * rec, section, w * rec);
-}
-/* behind report_begin, by the calls that collect tap-fit records: zeroed records for the fits in force x `blocks` */
-static inline void tapfit_begin(gdg_ctx *ctx, size_t blocks) {
-    gdg_ctx::TapFitRecords &F = ctx->tapfit_rec;
-    F.live = ctx->tapfit.count() > 0;
-    if (!F.live) return;
-    F.doubles = ctx->tapfit.doubles();
-    F.blocks = blocks;
-    F.store.assign(blocks * F.doubles, 0.0);
-}
-/* a step's tap-fit section ([w] records) that has come down, into the store under the blocks from b0 on */
-static inline void tapfit_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
-    gdg_ctx::TapFitRecords &F = ctx->tapfit_rec;
-    memcpy(F.store.data() + b0 * F.doubles, section, w * F.doubles * sizeof(double));
+/* a step's section of kind k ([rows][w] elements) that has come down, into the store under the blocks from b0 on */
+static inline void list_file(gdg_ctx *ctx, int k, const unsigned char *section, size_t w, size_t b0) {
+    gdg_ctx::ListRecords &R = ctx->list_rec[k];
+    list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
 }
 /* ... and has completed (rc == GDG_OK) or not */
 static inline int report_end(gdg_ctx *ctx, int rc) {
-    ctx->tapfit_rec.valid = ctx->tapfit_rec.live && rc == GDG_OK;
-    ctx->tapfit_rec.live = false;
-    ctx->gram_rec.valid = ctx->gram_rec.live && rc == GDG_OK;
-    ctx->gram_rec.live = false;
-    ctx->fit_rec.valid = ctx->fit_rec.live && rc == GDG_OK;
-    ctx->fit_rec.live = false;
+    for (gdg_ctx::ListRecords &R : ctx->list_rec) {
+        R.valid = R.live && rc == GDG_OK;
+        R.live = false;
+    }
     for (gdg_ctx::ReportKind &K : ctx->report) {
         K.valid = K.live && rc == GDG_OK;
         K.live = false;
@@ -852,6 +820,7 @@ enum {
     BATCH_DEV_SLOTS
 };
 static_assert(BATCH_DEV_SLOTS == 10, "gdg_ctx::batch_dev has one entry per slot");
+static_assert(BATCH_GRAM_PORTS == BATCH_FIT_TABLE + LIST_GRAM && BATCH_TAPFIT_TABLE == BATCH_FIT_TABLE + LIST_TAPFIT, "BATCH_FIT_TABLE + k is list kind k's slot");
 int ensure_tuner(gdg_ctx *ctx);
 
 #pragma GCC visibility pop

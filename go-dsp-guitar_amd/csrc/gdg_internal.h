@@ -375,12 +375,12 @@ hipError_t gdg_launch_block_fit(const double *d_rows, size_t row_stride, unsigne
  * triangle of the Gram matrix of the n_ports listed rows, d_records[ceil(samples / block)][n_ports (n_ports + 1) / 2].  h_ports is the host's
  * copy of the device's d_ports, held against n_rows before anything is launched. */
 hipError_t gdg_launch_block_gram(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, const int *h_ports, const int *d_ports,
-                                 unsigned n_ports, double *d_records, hipStream_t s);
+                                 unsigned n_ports, void *d_records, hipStream_t s);
 /* the tap-fit records (include/gdg.h, TAPFIT; gram.hip, tapfit_kernels.h): per block of `block` samples (the last of a row may be short) and
  * fit the lower triangle of the Gram matrix of its K T + 1 shifted rows, d_records[ceil(samples / block)][D].  h_table is the host's copy of
  * the device's d_table (blend.h, gdg_tapfit_table), held against the limits and n_rows before anything is launched. */
 hipError_t gdg_launch_block_tapfit(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, const int *h_table, const int *d_table,
-                                   unsigned n_fits, double *d_records, hipStream_t s);
+                                   unsigned n_fits, void *d_records, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

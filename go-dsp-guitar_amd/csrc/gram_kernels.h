@@ -109,7 +109,7 @@ block_gram_kernel(const double *__restrict__ rows, size_t row_stride, size_t sam
 /* d_records: [ceil(samples / block)][P (P + 1) / 2] doubles.  h_ports is the host's copy of the P entries at d_ports, checked here against
  * n_rows (and for repeats) before anything is launched: the kernel reads rows by what the table says */
 hipError_t gdg_launch_block_gram(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, const int *h_ports, const int *d_ports,
-                                 unsigned n_ports, double *d_records, hipStream_t s) {
+                                 unsigned n_ports, void *d_records, hipStream_t s) {
     if (n_ports == 0 || samples == 0) return hipSuccess;
     if (block == 0 || n_ports > GDG_GRAM_MAX_PORTS || !h_ports || !d_ports || !d_rows || !d_records) return hipErrorInvalidValue;
     if (gdg_gram_list_bad(h_ports, (int)n_ports, (int)n_rows) >= 0) return hipErrorInvalidValue;
@@ -118,7 +118,7 @@ hipError_t gdg_launch_block_gram(const double *d_rows, size_t row_stride, unsign
     const unsigned T = (n_ports + GRAM_TILE - 1) / GRAM_TILE;
     for (size_t b0 = 0; b0 < blocks; b0 += 65535u) {
         const unsigned n = (unsigned)(blocks - b0 < 65535u ? blocks - b0 : 65535u);
-        block_gram_kernel<<<dim3(T * (T + 1u) / 2u, n), GRAM_T, 0, s>>>(d_rows, row_stride, samples, block, (unsigned)b0, d_ports, n_ports, d_records);
+        block_gram_kernel<<<dim3(T * (T + 1u) / 2u, n), GRAM_T, 0, s>>>(d_rows, row_stride, samples, block, (unsigned)b0, d_ports, n_ports, static_cast<double *>(d_records));
     }
     return hipGetLastError();
 }

@@ -10,6 +10,7 @@
 #define GDG_REPORT_SECTIONS_H
 
 #include <stddef.h>
+#include <string.h>
 
 enum { REPORT_STATS, REPORT_BANDS, REPORT_ALIGN, REPORT_TRUE_PEAK, REPORT_KINDS };
 
@@ -46,56 +47,49 @@ static inline size_t report_room(const ReportLive &live, size_t rows, size_t W) 
     return room;
 }
 
-/* The blend fit's records (include/gdg.h, FIT) are no fifth kind: their rows are the call's fits, not its ports.  A step of the block loop
- * sends them down behind the last live kind's section -- behind its rows when no kind is live -- from the next 16 bytes on: [fits][w]
- * records of 368 bytes.  No fit: no byte (at = end = `end`).  The finish calls never carry them. */
+/* The list records -- the blend fit's (include/gdg.h, FIT), the Gram list's (GRAM) and the tap fit's (TAPFIT) -- are no further kinds: their
+ * rows are a call's fits or one row of packed sums, not its ports.  A step of the block loop sends them down behind the last live kind's
+ * section -- behind its rows when no kind is live -- in this fixed order, each from the next 16 bytes behind whatever precedes it:
+ * [rows][w] elements of `elem` bytes.  (rows, elem) = (fits, 368) for the fits, (1, P (P + 1) / 2 doubles) for a Gram list of P ports and
+ * (1, D doubles) for tap fits, D the list's sum of V (V + 1) / 2.  A list that is off: no byte.  The finish calls never carry them. */
+enum { LIST_FIT, LIST_GRAM, LIST_TAPFIT, LIST_KINDS };
 enum { FIT_RECORD_BYTES = 368 };
-struct FitSection { size_t at, bytes, end; };
-
-static inline FitSection fit_section(size_t end, size_t fits, size_t w) {
-    FitSection s = { end, 0, end };
-    if (!fits) return s;
-    s.at = (end + 15) & ~(size_t)15;
-    s.bytes = fits * w * FIT_RECORD_BYTES;
-    s.end = s.at + s.bytes;
-    return s;
-}
-
-/* ... and what a half holds for them for a window of W blocks, beside report_room */
-static inline size_t fit_room(size_t fits, size_t W) { return fits ? 16 + fits * W * FIT_RECORD_BYTES : 0; }
-
-/* The Gram records (include/gdg.h, GRAM) ride behind the fit section -- behind whatever precedes it when there is none -- from the next 16
- * bytes on: [w] records of P (P + 1) / 2 doubles for a list of P ports.  No list: no byte.  The finish calls never carry them. */
-struct GramSection { size_t at, bytes, end; };
-
 static inline size_t gram_record_bytes(size_t ports) { return ports * (ports + 1) / 2 * 8; }
 
-static inline GramSection gram_section(size_t end, size_t ports, size_t w) {
-    GramSection s = { end, 0, end };
-    if (!ports) return s;
+/* what a list in force sends down per block: `rows` rows of one element of `elem` bytes; elem == 0 = the kind is off */
+struct ListShape {
+    size_t rows, elem;
+    bool on() const { return elem != 0; }
+};
+
+/* a list's section behind `end` (at = end = `end` and no byte for a list that is off) ... */
+struct ListSection { size_t at, bytes, end; };
+
+static inline ListSection list_section(size_t end, const ListShape &shape, size_t w) {
+    ListSection s = { end, 0, end };
+    if (!shape.on()) return s;
     s.at = (end + 15) & ~(size_t)15;
-    s.bytes = w * gram_record_bytes(ports);
+    s.bytes = shape.rows * w * shape.elem;
     s.end = s.at + s.bytes;
     return s;
 }
 
-/* ... and what a half holds for them for a window of W blocks */
-static inline size_t gram_room(size_t ports, size_t W) { return ports ? 16 + W * gram_record_bytes(ports) : 0; }
+/* ... and what a half holds for it for a window of W blocks, beside report_room */
+static inline size_t list_room(const ListShape &shape, size_t W) { return shape.on() ? 16 + shape.rows * W * shape.elem : 0; }
 
-/* The tap-fit records (include/gdg.h, TAPFIT) ride behind the Gram section -- behind whatever precedes it when there is none -- from the next
- * 16 bytes on: [w] records of D doubles, D the list's sum of V (V + 1) / 2.  No list: no byte.  The finish calls never carry them. */
-struct TapFitSection { size_t at, bytes, end; };
+/* the three sections of a step, chained behind ReportSections::end; `end` is the end of what the step sends down */
+struct ListSections { ListSection of[LIST_KINDS]; size_t end; };
 
-static inline TapFitSection tapfit_section(size_t end, size_t doubles, size_t w) {
-    TapFitSection s = { end, 0, end };
-    if (!doubles) return s;
-    s.at = (end + 15) & ~(size_t)15;
-    s.bytes = w * doubles * 8;
-    s.end = s.at + s.bytes;
+static inline ListSections list_sections(size_t end, const ListShape *shape, size_t w) {
+    ListSections s;
+    for (int k = 0; k < LIST_KINDS; k++) end = (s.of[k] = list_section(end, shape[k], w)).end;
+    s.end = end;
     return s;
 }
 
-/* ... and what a half holds for them for a window of W blocks */
-static inline size_t tapfit_room(size_t doubles, size_t W) { return doubles ? 16 + W * doubles * 8 : 0; }
+/* Filing a section that has come down: [rows][w] elements into a store of [rows][blocks], under the blocks from b0 on. */
+static inline void list_file_rows(unsigned char *store, size_t blocks, const ListShape &shape, const unsigned char *section, size_t w, size_t b0) {
+    for (size_t r = 0; r < shape.rows; r++) memcpy(store + (r * blocks + b0) * shape.elem, section + r * w * shape.elem, w * shape.elem);
+}
 
 #endif

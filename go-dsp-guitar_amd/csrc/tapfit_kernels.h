@@ -122,7 +122,7 @@ block_tapfit_kernel(const double *__restrict__ rows, size_t row_stride, size_t s
  * d_table (blend.h, gdg_tapfit_table), checked here -- limits, ports against n_rows, offsets and tiles against what the limits allow --
  * before anything is launched: the kernel reads rows and writes records by what the table says */
 hipError_t gdg_launch_block_tapfit(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, const int *h_table, const int *d_table,
-                                   unsigned n_fits, double *d_records, hipStream_t s) {
+                                   unsigned n_fits, void *d_records, hipStream_t s) {
     if (n_fits == 0 || samples == 0) return hipSuccess;
     if (block == 0 || n_fits > GDG_TAPFIT_MAX_FITS || !h_table || !d_table || !d_rows || !d_records) return hipErrorInvalidValue;
     unsigned tiles = 0;
@@ -142,7 +142,7 @@ hipError_t gdg_launch_block_tapfit(const double *d_rows, size_t row_stride, unsi
     if (row_stride < samples || blocks > 0x7fffffffu || ((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7) || ((uintptr_t)d_table & 3)) return hipErrorInvalidValue;
     for (size_t b0 = 0; b0 < blocks; b0 += 65535u) {
         const unsigned n = (unsigned)(blocks - b0 < 65535u ? blocks - b0 : 65535u);
-        block_tapfit_kernel<<<dim3(tiles, n), TAPFIT_T, 0, s>>>(d_rows, row_stride, samples, block, (unsigned)b0, d_table, n_fits, D, d_records);
+        block_tapfit_kernel<<<dim3(tiles, n), TAPFIT_T, 0, s>>>(d_rows, row_stride, samples, block, (unsigned)b0, d_table, n_fits, D, static_cast<double *>(d_records));
     }
     return hipGetLastError();
 }

@@ -1,8 +1,9 @@
 /*
  * fit_plan_check.cpp -- the blend fit's host arithmetic without HIP: the planner of csrc/blend.h (gdg_blend_plan_weights) against hand-made
  * records whose answers are known in closed form, the list's validation (gdg_fit_check, gdg_fit_table), and the place and room of the fit
- * section in a step's download half (csrc/report_sections.h: fit_section, fit_room) against the formula spelled out here, over the on/off
- * combinations of the four record kinds.  Built by tests/test_fit_host.py, once more under AddressSanitizer and UBSan.
+ * section in a step's download half (csrc/report_sections.h: list_section, list_room with the fits' shape) against the formula spelled out
+ * here, over the on/off combinations of the four record kinds; and the chain of the three list sections behind a report layout, over the
+ * 8 on/off subsets of the lists.  Built by tests/test_fit_host.py, once more under AddressSanitizer and UBSan.
  */
 #include "blend.h"
 #include "report_sections.h"
@@ -141,18 +142,48 @@ int main() {
                             if (mask & 4) end = ((end + 15) / 16) * 16 + rows * w * 40;
                             if (mask & 8) end = ((end + 15) / 16) * 16 + rows * w * 16;
                             CHECK(sec.end == end);
-                            const FitSection fs = fit_section(sec.end, fits, w);
-                            if (fits == 0) CHECK(fs.at == end && fs.bytes == 0 && fs.end == end && fit_room(0, w) == 0);
+                            const ListShape shape = { fits, fits ? (size_t)FIT_RECORD_BYTES : 0 };
+                            const ListSection fs = list_section(sec.end, shape, w);
+                            if (fits == 0) CHECK(fs.at == end && fs.bytes == 0 && fs.end == end && list_room(shape, w) == 0);
                             else {
                                 const size_t at = ((end + 15) / 16) * 16;
                                 CHECK(fs.at == at && fs.bytes == fits * w * 368 && fs.end == at + fits * w * 368);
-                                CHECK(fit_room(fits, w) == 16 + fits * w * 368);
-                                CHECK(fs.end - base <= report_room(live, rows, w) + fit_room(fits, w));      /* a step of the whole window fits its half */
+                                CHECK(list_room(shape, w) == 16 + fits * w * 368);
+                                CHECK(fs.end - base <= report_room(live, rows, w) + list_room(shape, w));      /* a step of the whole window fits its half */
                                 if (at != end) moved++;
                             }
                             cases++;
                         }
     CHECK(moved > 0);
+    /* the chain of the three list sections (list_sections) behind a report layout, over the 8 on/off subsets of the lists: every live
+     * section starts at the next 16 bytes behind what precedes it, an off kind takes no byte and moves nothing, and a step of the whole
+     * window fits the room of its half.  3 fits, a Gram list of 5 ports, tap fits of 21 doubles. */
+    {
+        static_assert(LIST_FIT == 0 && LIST_GRAM == 1 && LIST_TAPFIT == 2 && LIST_KINDS == 3, "the sections ride in this order");
+        const size_t elem[LIST_KINDS] = { 368, 5 * 6 / 2 * 8, 21 * 8 }, rows[LIST_KINDS] = { 3, 1, 1 };
+        CHECK(gram_record_bytes(5) == elem[LIST_GRAM]);
+        for (int report = 0; report < 2; report++)
+            for (size_t base : { (size_t)0, (size_t)1001, (size_t)4096, (size_t)98312 })
+                for (size_t w : { (size_t)1, (size_t)2, (size_t)16 })
+                    for (int on = 0; on < 8; on++) {
+                        const ReportLive live = { { report ? (size_t)32 : 0, 0, report ? (size_t)40 : 0, 0 } };
+                        const ReportSections sec = report_sections(live, 7, w, base, true);
+                        ListShape shape[LIST_KINDS];
+                        for (int k = 0; k < LIST_KINDS; k++) shape[k] = { rows[k], (on >> k) & 1 ? elem[k] : 0 };
+                        const ListSections ls = list_sections(sec.end, shape, w);
+                        size_t end = sec.end, room = report_room(live, 7, w);
+                        for (int k = 0; k < LIST_KINDS; k++) {
+                            const ListSection &s = ls.of[k];
+                            if ((on >> k) & 1) {
+                                CHECK(s.at == (end + 15) / 16 * 16 && s.bytes == rows[k] * w * elem[k] && s.end == s.at + s.bytes);
+                                end = s.end;
+                            } else CHECK(s.at == end && s.bytes == 0 && s.end == end && list_room(shape[k], w) == 0);
+                            room += list_room(shape[k], w);
+                        }
+                        CHECK(ls.end == end && ls.end - base <= room);
+                        if (!on) CHECK(ls.end == sec.end);
+                    }
+    }
     if (failures) { printf("%d checks failed\n", failures); return 1; }
     printf("OK planner and list; %zu section cases, %zu moved by the 16-byte step\n", cases, moved);
     return 0;

@@ -1,6 +1,6 @@
 /*
  * gram_plan_check.cpp -- the Gram list's host arithmetic without HIP: the place and room of the Gram section in a step's download half
- * (csrc/report_sections.h: gram_section, gram_room) against the formula spelled out here; the packed index of a record (csrc/blend.h:
+ * (csrc/report_sections.h: list_section, list_room with the Gram list's shape) against the formula spelled out here; the packed index of a record (csrc/blend.h:
  * gdg_gram_index) against a full matrix; the list's checks; and the greedy planner (gdg_blend_pick) on hand-made Grams whose answers are
  * known, its weights against the fit planner's on a fit record with the same sums.  Built by tests/test_gram_host.py, once more under
  * AddressSanitizer and UBSan.
@@ -36,12 +36,13 @@ int main() {
     for (size_t end : { (size_t)0, (size_t)8, (size_t)16, (size_t)1000, (size_t)4095, (size_t)123457 })
         for (size_t P : { (size_t)0, (size_t)2, (size_t)3, (size_t)64, (size_t)65, (size_t)512 })
             for (size_t w : { (size_t)1, (size_t)2, (size_t)4, (size_t)16 }) {
-                const GramSection s = gram_section(end, P, w);
+                const ListShape shape = { 1, gram_record_bytes(P) };
+                const ListSection s = list_section(end, shape, w);
                 cases++;
-                if (P == 0) { CHECK(s.at == end && s.bytes == 0 && s.end == end && gram_room(P, w) == 0); continue; }
+                if (P == 0) { CHECK(s.at == end && s.bytes == 0 && s.end == end && list_room(shape, w) == 0); continue; }
                 const size_t at = end % 16 ? end + (16 - end % 16) : end, bytes = w * (P * (P + 1) / 2) * 8;
                 CHECK(s.at == at && s.bytes == bytes && s.end == at + bytes);
-                CHECK(gram_room(P, w) == 16 + bytes && s.end - end <= gram_room(P, w));
+                CHECK(list_room(shape, w) == 16 + bytes && s.end - end <= list_room(shape, w));
                 if (at != end) moved++;
             }
     CHECK(gram_record_bytes(512) == 1050624);
@@ -49,10 +50,10 @@ int main() {
     {
         const ReportLive live = { { 32, 0, 40, 0 } };
         const ReportSections sec = report_sections(live, 10, 4, 1001, true);
-        const FitSection fit = fit_section(sec.end, 3, 4);
-        const GramSection g = gram_section(fit.end, 5, 4);
+        const ListSection fit = list_section(sec.end, { 3, FIT_RECORD_BYTES }, 4);
+        const ListSection g = list_section(fit.end, { 1, gram_record_bytes(5) }, 4);
         CHECK(g.at == ((fit.end + 15) & ~(size_t)15) && g.at >= fit.at + 3 * 4 * 368 && g.bytes == 4 * 15 * 8);
-        const GramSection alone = gram_section(fit_section(report_sections({ { 0, 0, 0, 0 } }, 10, 4, 1001, true).end, 0, 4).end, 5, 4);
+        const ListSection alone = list_section(list_section(report_sections({ { 0, 0, 0, 0 } }, 10, 4, 1001, true).end, { 0, 0 }, 4).end, { 1, gram_record_bytes(5) }, 4);
         CHECK(alone.at == 1008);
     }
 

@@ -154,11 +154,12 @@ int main() {
     for (size_t end : { (size_t)0, (size_t)8, (size_t)16, (size_t)1000, (size_t)4097 })
         for (size_t D : { (size_t)0, (size_t)3, (size_t)2145, (size_t)134160 })
             for (size_t w : { (size_t)1, (size_t)2, (size_t)16 }) {
-                const TapFitSection s = tapfit_section(end, D, w);
+                const ListShape shape = { 1, D * 8 };
+                const ListSection s = list_section(end, shape, w);
                 cases++;
-                if (!D) { CHECK(s.at == end && s.bytes == 0 && s.end == end && tapfit_room(D, w) == 0); continue; }
+                if (!D) { CHECK(s.at == end && s.bytes == 0 && s.end == end && list_room(shape, w) == 0); continue; }
                 CHECK(s.at % 16 == 0 && s.at >= end && s.at < end + 16 && s.bytes == w * D * 8 && s.end == s.at + s.bytes);
-                CHECK(s.end - end <= tapfit_room(D, w));
+                CHECK(s.end - end <= list_room(shape, w) && list_room(shape, w) == 16 + w * D * 8);
                 moved += s.at != end;
             }
     if (failures) { printf("%d checks failed\n", failures); return 1; }

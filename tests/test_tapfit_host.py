@@ -61,10 +61,11 @@ def test_the_section_is_stated_once_and_the_kernel_is_part_of_gram_o():
     with open(os.path.join(CSRC, "report_sections.h")) as f:
         text = f.read()
     assert "enum { REPORT_STATS, REPORT_BANDS, REPORT_ALIGN, REPORT_TRUE_PEAK, REPORT_KINDS };" in text
-    assert "static inline TapFitSection tapfit_section(" in text and "static inline size_t tapfit_room(" in text
+    assert "enum { LIST_FIT, LIST_GRAM, LIST_TAPFIT, LIST_KINDS };" in text       # a list record of its own, in the order the sections ride
+    assert text.count("static inline ListSection list_section(") == 1 and text.count("static inline size_t list_room(") == 1
     with open(os.path.join(CSRC, "api_batch.cpp")) as f:
         batch = f.read()
-    assert "tapfit_section(" in batch and "tapfit_room(" in batch
+    assert "list_sections(" in batch and "list_room(" in batch
     with open(os.path.join(CSRC, "Makefile")) as f:
         make = f.read()
     assert "tapfit_kernels.h" in [w for line in make.splitlines() if line.startswith("gram.o:") for w in line.split()]
