@@ -303,14 +303,11 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 if (p.list[k].count)
                     HIP_TRY(ctx, list_launch[k](d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.list[k].h_table, p.list[k].d_table, (unsigned)p.list[k].count,
                                                 enc + steps[i].lists.of[k].at, ctx->stream));
-            /* dither on: the sibling kernels; n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
-            /* trim on: the trimmed siblings of either; `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
+            /* dither on: n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
+            /* trim on: `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
-                const gdg_dither_rows dz = { ctx->dither_seed, p.dither_first + off, port_base, n_chain };
-                if (gains)
-                    return gdg_launch_wave_encode_rows_trim(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, gains, p.dither ? &dz : nullptr, ctx->stream);
-                if (!p.dither) return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, ctx->stream);
-                return gdg_launch_wave_encode_rows_dither(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, dz, ctx->stream);
+                const gdg_encode_mode m = { gains != nullptr, p.dither, gains, { 1.0, 1.0 }, { ctx->dither_seed, p.dither_first + off, port_base, n_chain } };
+                return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, m, ctx->stream);
             };
             if (!sharded) {
                 HIP_TRY(ctx, encode_rows(d_win, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
@@ -1229,16 +1226,10 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
             HIP_TRY(ctx, hipEventRecord(ctx->fin_up[h], ctx->stream));
             {
                 ProfScope ps(ctx, GDG_K_WAVE);
-                if (trim)                                                        /* the sums stay as they are; the encoder reads them times the gains */
-                    HIP_TRY(ctx, gdg_launch_finish_master_trim(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc,
-                                                               enc + piece * width, d_sums, piece, trim_left, trim_right, dither ? 1 : 0, ctx->dither_seed,
-                                                               dither_first + k * piece, ctx->stream));
-                else if (!dither)
-                    HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc, enc + piece * width,
-                                                          d_sums, piece, ctx->stream));
-                else                                                             /* the piece's first sample: dither_first + k * piece */
-                    HIP_TRY(ctx, gdg_launch_finish_master_dither(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc,
-                                                                 enc + piece * width, d_sums, piece, ctx->dither_seed, dither_first + k * piece, ctx->stream));
+                /* the sums stay as they are; the encoder reads them times the gains.  The piece's first sample: dither_first + k * piece */
+                const gdg_encode_mode m = { trim, dither, nullptr, { trim_left, trim_right }, { ctx->dither_seed, dither_first + k * piece, 0, 0 } };
+                HIP_TRY(ctx, gdg_launch_finish_master(out_format, reinterpret_cast<const double *>(slab), stride, n_shards, aux != nullptr, stride, enc, enc + piece * width,
+                                                      d_sums, piece, m, ctx->stream));
             }
             if (run_meters)
                 for (size_t o = 0; o < n; o += B)                                /* block by block, like the loop that fed the other ports */

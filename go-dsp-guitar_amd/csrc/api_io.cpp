@@ -39,7 +39,7 @@ int gdg_wave_encode_device(gdg_ctx *ctx, int format, const double *d_samples, si
     if (!d_bytes || !d_samples) return GDG_ERR_INVALID;
     enter_keep_fir_sums(ctx);
     ProfScope ps(ctx, GDG_K_WAVE);
-    HIP_TRY(ctx, gdg_launch_wave_encode(format, d_samples, per, channels, d_bytes, ctx->stream));
+    HIP_TRY(ctx, gdg_launch_wave_encode(format, d_samples, per, channels, d_bytes, gdg_encode_mode{}, ctx->stream));
     return GDG_OK;
 }
 
@@ -63,24 +63,30 @@ int gdg_wave_decode(gdg_ctx *ctx, int format, const void *bytes, size_t per, uns
     return GDG_OK;
 }
 
-int gdg_wave_encode(gdg_ctx *ctx, int format, const double *samples, size_t per, unsigned channels, void *bytes) {
-    if (!ctx) return GDG_ERR_INVALID;
-    int w = gdg_wave_bytes_per_sample(format);
-    if (!w) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", format);
-    if (channels == 0) return fail(ctx, GDG_ERR_INVALID, "channel count must be positive");
-    size_t n = per * channels;
-    if (n == 0) return GDG_OK;
-    if (!bytes || !samples) return GDG_ERR_INVALID;
+/* the host form of the three encoders: n samples up, `device_form` from one io buffer into the other, n * width bytes down, synchronised */
+template <class F>
+static int encode_host(gdg_ctx *ctx, int format, const double *samples, size_t n, void *bytes, F device_form) {
+    const size_t w = (size_t)gdg_wave_bytes_per_sample(format);
     enter_keep_fir_sums(ctx);
     int rc = ensure_io(ctx, 0, n * w);
     if (rc == GDG_OK) rc = ensure_io(ctx, 1, n * sizeof(double));
     if (rc != GDG_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_io[1], samples, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gdg_wave_encode_device(ctx, format, static_cast<const double *>(ctx->d_io[1]), per, channels, ctx->d_io[0]);
+    rc = device_form(static_cast<const double *>(ctx->d_io[1]), ctx->d_io[0]);
     if (rc != GDG_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(bytes, ctx->d_io[0], n * w, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GDG_OK;
+}
+
+int gdg_wave_encode(gdg_ctx *ctx, int format, const double *samples, size_t per, unsigned channels, void *bytes) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (!gdg_wave_bytes_per_sample(format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", format);
+    if (channels == 0) return fail(ctx, GDG_ERR_INVALID, "channel count must be positive");
+    size_t n = per * channels;
+    if (n == 0) return GDG_OK;
+    if (!bytes || !samples) return GDG_ERR_INVALID;
+    return encode_host(ctx, format, samples, n, bytes, [&](const double *d, void *b) { return gdg_wave_encode_device(ctx, format, d, per, channels, b); });
 }
 
 /* the dithered encoder on its own (dither.h): mono; mode 0 and the IEEE formats are gdg_wave_encode's calls, kernels and bytes */
@@ -95,28 +101,20 @@ int gdg_wave_encode_dither_device(gdg_ctx *ctx, int format, const double *d_samp
     if ((uintptr_t)d_samples & 7) return fail(ctx, GDG_ERR_INVALID, "encode dither: the samples are float64, 8-byte aligned");
     enter_keep_fir_sums(ctx);
     ProfScope ps(ctx, GDG_K_WAVE);
-    HIP_TRY(ctx, gdg_launch_wave_encode_dither(format, d_samples, n, d_bytes, seed, port, first_index, ctx->stream));
+    const gdg_encode_mode m = { false, true, nullptr, { 1.0, 1.0 }, { seed, first_index, port, 0 } };
+    HIP_TRY(ctx, gdg_launch_wave_encode(format, d_samples, n, 1, d_bytes, m, ctx->stream));
     return GDG_OK;
 }
 
 int gdg_wave_encode_dither(gdg_ctx *ctx, int format, const double *samples, size_t n, int mode, uint64_t seed, uint32_t port, uint64_t first_index, void *bytes) {
     if (!ctx) return GDG_ERR_INVALID;
-    const int w = gdg_wave_bytes_per_sample(format);
-    if (!w) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", format);
+    if (!gdg_wave_bytes_per_sample(format)) return fail(ctx, GDG_ERR_UNSUPPORTED, "unknown sample format %d", format);
     if (mode != 0 && mode != 1) return fail(ctx, GDG_ERR_INVALID, "encode dither: mode %d; 0 is off, 1 is TPDF", mode);
     if (!gdg_dither_applies(mode, format)) return gdg_wave_encode(ctx, format, samples, n, 1, bytes);
     if (n == 0) return GDG_OK;
     if (!bytes || !samples) return GDG_ERR_INVALID;
-    enter_keep_fir_sums(ctx);
-    int rc = ensure_io(ctx, 0, n * w);
-    if (rc == GDG_OK) rc = ensure_io(ctx, 1, n * sizeof(double));
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_io[1], samples, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gdg_wave_encode_dither_device(ctx, format, static_cast<const double *>(ctx->d_io[1]), n, mode, seed, port, first_index, ctx->d_io[0]);
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(bytes, ctx->d_io[0], n * w, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GDG_OK;
+    return encode_host(ctx, format, samples, n, bytes,
+                       [&](const double *d, void *b) { return gdg_wave_encode_dither_device(ctx, format, d, n, mode, seed, port, first_index, b); });
 }
 
 /* the trimmed encoder on its own (trim.h): mono, y = x * gain in front of gdg_wave_encode_dither's encoder; gain 1.0 is that call itself */
@@ -138,7 +136,8 @@ int gdg_wave_encode_trim_device(gdg_ctx *ctx, int format, const double *d_sample
     if ((uintptr_t)d_samples & 7) return fail(ctx, GDG_ERR_INVALID, "encode trim: the samples are float64, 8-byte aligned");
     enter_keep_fir_sums(ctx);
     ProfScope ps(ctx, GDG_K_WAVE);
-    HIP_TRY(ctx, gdg_launch_wave_encode_trim(format, d_samples, n, d_bytes, gain, gdg_dither_applies(mode, format) ? 1 : 0, seed, port, first_index, ctx->stream));
+    const gdg_encode_mode m = { true, gdg_dither_applies(mode, format), nullptr, { gain, gain }, { seed, first_index, port, 0 } };
+    HIP_TRY(ctx, gdg_launch_wave_encode(format, d_samples, n, 1, d_bytes, m, ctx->stream));
     return GDG_OK;
 }
 
@@ -150,17 +149,8 @@ int gdg_wave_encode_trim(gdg_ctx *ctx, int format, const double *samples, size_t
     if (gain == 1.0) return gdg_wave_encode_dither(ctx, format, samples, n, mode, seed, port, first_index, bytes);
     if (n == 0) return GDG_OK;
     if (!bytes || !samples) return GDG_ERR_INVALID;
-    const size_t w = (size_t)gdg_wave_bytes_per_sample(format);
-    enter_keep_fir_sums(ctx);
-    rc = ensure_io(ctx, 0, n * w);
-    if (rc == GDG_OK) rc = ensure_io(ctx, 1, n * sizeof(double));
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_io[1], samples, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = gdg_wave_encode_trim_device(ctx, format, static_cast<const double *>(ctx->d_io[1]), n, gain, mode, seed, port, first_index, ctx->d_io[0]);
-    if (rc != GDG_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(bytes, ctx->d_io[0], n * w, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GDG_OK;
+    return encode_host(ctx, format, samples, n, bytes,
+                       [&](const double *d, void *b) { return gdg_wave_encode_trim_device(ctx, format, d, n, gain, mode, seed, port, first_index, b); });
 }
 
 /* the planner (trim.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */

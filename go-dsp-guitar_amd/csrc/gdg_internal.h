@@ -272,9 +272,23 @@ hipError_t gdg_launch_tuner_analyze(const double *d_rings, int nch, int wp, doub
 #define GDG_METER_SEG 8192
 struct gdg_meter_rec { double current, peak; unsigned long long counter; int enabled, pad; };
 hipError_t gdg_launch_wave_decode(int fmt, const void *d_bytes, size_t per, unsigned channels, double *d_out, hipStream_t s);
-hipError_t gdg_launch_wave_encode(int fmt, const double *d_in, size_t per, unsigned channels, void *d_bytes, hipStream_t s);
-/* rows of one strided array -> compact encoded rows (row_len % 4 == 0) */
-hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes, hipStream_t s);
+/* What an encode launch does beyond the plain encoder (io.hip, the encode launchers): `trim`, every sample times its port's gain -- one rounded
+ * product (trim.h; include/gdg.h, gdg_batch_set_trim) -- and `dither`, TPDF dither of the LPCM formats, a sample's noise a function of
+ * (seed, port, index) alone (dither.h; gdg_batch_set_dither).  The callers' rules set the two (a gain of 1.0 or no gains: no trim; mode 0
+ * or an IEEE format: no dither); a launcher reads only what a switch that is on needs.  {} is the plain encoder. */
+struct gdg_dither_rows { unsigned long long seed, first; unsigned port_base, n_chain; };
+struct gdg_encode_mode {
+    bool trim, dither;
+    const double *d_gains;       /* trim, rows: row r has gain d_gains[r] (device memory) */
+    double gain[2];              /* trim, the master: left and right; stand-alone: gain[0] */
+    gdg_dither_rows dz;          /* dither, rows: row r is sample `first` .. of port gdg_dither_row_port(port_base, n_chain, r); the master: seed and
+                                  * the piece's `first` (left is port 0xfffffffd, right 0xfffffffe); stand-alone: seed, first and port_base = the port */
+};
+/* stand-alone: planar [channels][per] -> interleaved bytes; trimmed or dithered: mono, d_in 8-byte aligned (unaligned buffers and n % 4 go one sample per thread) */
+hipError_t gdg_launch_wave_encode(int fmt, const double *d_in, size_t per, unsigned channels, void *d_bytes, const gdg_encode_mode &m, hipStream_t s);
+/* rows of one strided array -> compact encoded rows (row_len % 4 == 0); trimmed IEEE64 needs d_bytes 8-byte aligned */
+hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
+                                       const gdg_encode_mode &m, hipStream_t s);
 /* many mono pieces in one launch (the batch run's streamed upload): piece r = `count` samples of format `fmt` at `src` -> dst */
 /* stride > 1: the piece holds interleaved frames of `stride` channels, of which channel `offset` is decoded (0 / 1: mono, as above) */
 struct gdg_decode_row { const unsigned char *src; double *dst; unsigned count; int fmt; unsigned stride, offset; };
@@ -308,35 +322,9 @@ hipError_t gdg_launch_meter(const double *d_rows, size_t stride, int n_ports, in
 hipError_t gdg_launch_add_aux(double *d_a, double *d_b, const double *d_src, int n, hipStream_t s);
 /* the master of one piece of a sharded job (gdg_batch_finish_master, gdg_batch_finish_master_slice): d_slab = [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux] rows of
  * `stride` samples; per side ((p_0 + p_1) + ... + p_{G-1}) + aux, encoded into n * width bytes at d_left_bytes / d_right_bytes; d_sums
- * non-null: the float64 sums as well, left at d_sums, right at d_sums + sums_stride (the meters read them).  n a multiple of 4: a ragged piece comes with zeros up to the next one. */
+ * non-null: the float64 sums as well, left at d_sums, right at d_sums + sums_stride (the meters read them), taken before trim and dither.  n a multiple of 4: a ragged piece comes with zeros up to the next one. */
 hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
-                                    void *d_right_bytes, double *d_sums, size_t sums_stride, hipStream_t s);
-/* The dithered siblings of the three encoders above (dither.h; include/gdg.h, gdg_batch_set_dither): LPCM formats only -- the callers send
- * every other call (dither off, IEEE32, IEEE64) to the plain launchers, which stay as they are.  A sample's noise depends on (seed, port,
- * index) alone.  Rows: row r of the launch is sample `first` .. of port gdg_dither_row_port(port_base, n_chain, r). */
-struct gdg_dither_rows { unsigned long long seed, first; unsigned port_base, n_chain; };
-hipError_t gdg_launch_wave_encode_rows_dither(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
-                                              gdg_dither_rows dither, hipStream_t s);
-/* the master: left is port 0xfffffffd, right 0xfffffffe, the piece's first sample has index `first`; the sums (d_sums) are taken before the dither */
-hipError_t gdg_launch_finish_master_dither(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
-                                           void *d_right_bytes, double *d_sums, size_t sums_stride, unsigned long long seed, unsigned long long first,
-                                           hipStream_t s);
-/* mono, any 8-byte alignment of d_in and any byte alignment of d_bytes (unaligned buffers and n % 4 go one sample per thread) */
-hipError_t gdg_launch_wave_encode_dither(int fmt, const double *d_in, size_t n, void *d_bytes, unsigned long long seed, unsigned port,
-                                         unsigned long long first, hipStream_t s);
-/* The trimmed siblings of the encoders above (trim.h; include/gdg.h, gdg_batch_set_trim): every sample times its row's gain -- one rounded
- * product -- and then the plain encoder (all six formats) or the dithered one (LPCM formats).  The callers send every call with the trim off
- * to the launchers above, which stay as they are.  Rows: row r has gain d_gains[r] (device memory); `dither` null = the plain encoder.
- * IEEE64 needs d_bytes 8-byte aligned. */
-hipError_t gdg_launch_wave_encode_rows_trim(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
-                                            const double *d_gains, const gdg_dither_rows *dither, hipStream_t s);
-/* the master: the gains are kernel arguments; the sums (d_sums) are taken before the trim; dither != 0: seed and first as above */
-hipError_t gdg_launch_finish_master_trim(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
-                                         void *d_right_bytes, double *d_sums, size_t sums_stride, double gain_left, double gain_right, int dither,
-                                         unsigned long long seed, unsigned long long first, hipStream_t s);
-/* mono, any 8-byte alignment of d_in and any byte alignment of d_bytes (unaligned buffers and n % 4 go one sample per thread) */
-hipError_t gdg_launch_wave_encode_trim(int fmt, const double *d_in, size_t n, void *d_bytes, double gain, int dither, unsigned long long seed,
-                                       unsigned port, unsigned long long first, hipStream_t s);
+                                    void *d_right_bytes, double *d_sums, size_t sums_stride, const gdg_encode_mode &m, hipStream_t s);
 hipError_t gdg_launch_metronome(const double *d_tick, unsigned n_tick, const double *d_tock, unsigned n_tock, double *d_out, int n,
                                 unsigned sc0, unsigned tc0, unsigned spb, unsigned beats, unsigned j0, hipStream_t s);
 /* the render report (include/gdg.h): one gdg_block_stats per block of `block` samples (the last of a row may be short) of n_rows rows of

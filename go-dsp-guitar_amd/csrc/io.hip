@@ -302,6 +302,12 @@ static int grid_for(size_t n) {
 
 /* ---- mono fast path: four samples per thread, word-sized loads and stores ---------------------------------------- */
 template <int FMT> struct fmt_width { static const int W = FMT == GDG_FMT_LPCM8 ? 1 : FMT == GDG_FMT_LPCM16 ? 2 : FMT == GDG_FMT_LPCM24 ? 3 : 4; };
+/* STMT once with FMT a constant: every format (GDG_DISPATCH_FMT) or the four LPCM ones (GDG_DISPATCH_LPCM); any other value is refused */
+#define GDG_FMT_CASE(F, STMT) case F: { constexpr int FMT = F; STMT; break; }
+#define GDG_LPCM_CASES(STMT) GDG_FMT_CASE(GDG_FMT_LPCM8, STMT) GDG_FMT_CASE(GDG_FMT_LPCM16, STMT) GDG_FMT_CASE(GDG_FMT_LPCM24, STMT) GDG_FMT_CASE(GDG_FMT_LPCM32, STMT)
+#define GDG_DISPATCH_LPCM(F, STMT) switch (F) { GDG_LPCM_CASES(STMT) default: return hipErrorInvalidValue; }
+#define GDG_DISPATCH_FMT(F, STMT) \
+    switch (F) { GDG_LPCM_CASES(STMT) GDG_FMT_CASE(GDG_FMT_IEEE32, STMT) GDG_FMT_CASE(GDG_FMT_IEEE64, STMT) default: return hipErrorInvalidValue; }
 __device__ __forceinline__ unsigned getb(const unsigned *w, int k) { return (w[k >> 2] >> ((k & 3) * 8)) & 0xffu; }
 
 template <int FMT>
@@ -371,30 +377,6 @@ wave_decode4_kernel(const unsigned *__restrict__ words, size_t groups, v2d *__re
     }
 }
 
-template <int FMT, bool NT>
-__global__ void __launch_bounds__(256)
-wave_encode4_kernel(const v2d *__restrict__ in, size_t groups, unsigned *__restrict__ words) {
-    constexpr int W = fmt_width<FMT>::W;
-    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (size_t)gridDim.x * 256) {
-        v2d a = NT ? __builtin_nontemporal_load(in + 2 * g) : in[2 * g], b = NT ? __builtin_nontemporal_load(in + 2 * g + 1) : in[2 * g + 1];
-        double r[4] = { a.x, a.y, b.x, b.y };
-        unsigned w[W];
-#pragma unroll
-        for (int k = 0; k < W; k++) w[k] = 0;
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            unsigned code = encode_code<FMT>(r[s]);
-#pragma unroll
-            for (int k = 0; k < W; k++) {
-                int byte = s * W + k;
-                w[byte >> 2] |= ((code >> (8 * k)) & 0xffu) << ((byte & 3) * 8);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < W; k++) { if (NT) __builtin_nontemporal_store(w[k], words + g * W + k); else words[g * W + k] = w[k]; }
-    }
-}
-
 template <int FMT>
 static void launch_decode(const unsigned char *p, size_t per, unsigned channels, double *d_out, hipStream_t s) {
     size_t n = per * channels, done = 0;
@@ -408,21 +390,6 @@ static void launch_decode(const unsigned char *p, size_t per, unsigned channels,
         size_t off = done * gdg_wave_bytes_per_sample(FMT);
         if (channels == 1) wave_decode_kernel<FMT><<<grid_for(n - done), 256, 0, s>>>(p + off, n - done, d_out + done, 1, n - done);
         else wave_decode_kernel<FMT><<<grid_for(n), 256, 0, s>>>(p, n, d_out, channels, per);
-    }
-}
-
-template <int FMT>
-static void launch_encode(const double *d_in, size_t per, unsigned channels, unsigned char *p, hipStream_t s) {
-    size_t n = per * channels, done = 0;
-    if (FMT != GDG_FMT_IEEE64 && channels == 1 && n >= 4 && ((uintptr_t)p & 3) == 0 && ((uintptr_t)d_in & 15) == 0) {
-        size_t groups = n / 4;
-        wave_encode4_kernel<FMT, true><<<(unsigned)((groups + 255) / 256), 256, 0, s>>>(reinterpret_cast<const v2d *>(d_in), groups, reinterpret_cast<unsigned *>(p));
-        done = groups * 4;
-    }
-    if (done < n) {
-        size_t off = done * gdg_wave_bytes_per_sample(FMT);
-        if (channels == 1) wave_encode_kernel<FMT><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + off, 1, n - done);
-        else wave_encode_kernel<FMT><<<grid_for(n), 256, 0, s>>>(d_in, n, p, channels, per);
     }
 }
 
@@ -594,32 +561,34 @@ hipError_t gdg_launch_wave_decode(int fmt, const void *d_bytes, size_t per, unsi
     size_t n = per * channels;
     if (n == 0) return hipSuccess;
     const unsigned char *p = static_cast<const unsigned char *>(d_bytes);
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_decode<GDG_FMT_LPCM8>(p, per, channels, d_out, s); break;
-    case GDG_FMT_LPCM16: launch_decode<GDG_FMT_LPCM16>(p, per, channels, d_out, s); break;
-    case GDG_FMT_LPCM24: launch_decode<GDG_FMT_LPCM24>(p, per, channels, d_out, s); break;
-    case GDG_FMT_LPCM32: launch_decode<GDG_FMT_LPCM32>(p, per, channels, d_out, s); break;
-    case GDG_FMT_IEEE32: launch_decode<GDG_FMT_IEEE32>(p, per, channels, d_out, s); break;
-    case GDG_FMT_IEEE64: launch_decode<GDG_FMT_IEEE64>(p, per, channels, d_out, s); break;
-    default: return hipErrorInvalidValue;
-    }
+    GDG_DISPATCH_FMT(fmt, launch_decode<FMT>(p, per, channels, d_out, s));
     return hipGetLastError();
 }
 
-hipError_t gdg_launch_wave_encode(int fmt, const double *d_in, size_t per, unsigned channels, void *d_bytes, hipStream_t s) {
-    size_t n = per * channels;
-    if (n == 0) return hipSuccess;
-    unsigned char *p = static_cast<unsigned char *>(d_bytes);
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_encode<GDG_FMT_LPCM8>(d_in, per, channels, p, s); break;
-    case GDG_FMT_LPCM16: launch_encode<GDG_FMT_LPCM16>(d_in, per, channels, p, s); break;
-    case GDG_FMT_LPCM24: launch_encode<GDG_FMT_LPCM24>(d_in, per, channels, p, s); break;
-    case GDG_FMT_LPCM32: launch_encode<GDG_FMT_LPCM32>(d_in, per, channels, p, s); break;
-    case GDG_FMT_IEEE32: launch_encode<GDG_FMT_IEEE32>(d_in, per, channels, p, s); break;
-    case GDG_FMT_IEEE64: launch_encode<GDG_FMT_IEEE64>(d_in, per, channels, p, s); break;
-    default: return hipErrorInvalidValue;
+/* the stand-alone mono form's aligned bulk: one group per thread without a grid cap, non-temporal loads and stores (measured,
+ * profiles/io_variants_r01.txt) */
+template <int FMT>
+__global__ void __launch_bounds__(256)
+wave_encode4_kernel(const v2d *__restrict__ in, size_t groups, unsigned *__restrict__ words) {
+    constexpr int W = fmt_width<FMT>::W;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (size_t)gridDim.x * 256) {
+        v2d a = __builtin_nontemporal_load(in + 2 * g), b = __builtin_nontemporal_load(in + 2 * g + 1);
+        double r[4] = { a.x, a.y, b.x, b.y };
+        unsigned w[W];
+#pragma unroll
+        for (int k = 0; k < W; k++) w[k] = 0;
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            unsigned code = encode_code<FMT>(r[s]);
+#pragma unroll
+            for (int k = 0; k < W; k++) {
+                int byte = s * W + k;
+                w[byte >> 2] |= ((code >> (8 * k)) & 0xffu) << ((byte & 3) * 8);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], words + g * W + k);
     }
-    return hipGetLastError();
 }
 
 /* n_rows rows of row_len samples each, row r at d_in + r * row_stride, encoded into COMPACT rows of row_len * width bytes: the batch
@@ -649,30 +618,6 @@ wave_encode4_rows_kernel(const double *__restrict__ in, size_t row_stride, size_
 #pragma unroll
         for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], dst + g * W + k);
     }
-}
-
-template <int FMT>
-static void launch_encode_rows(const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, unsigned char *p, hipStream_t s) {
-    size_t groups = row_len / 4;
-    unsigned tiles = (unsigned)((groups + 255) / 256);
-    wave_encode4_rows_kernel<FMT><<<dim3(tiles, n_rows), dim3(256), 0, s>>>(d_in, row_stride, groups, reinterpret_cast<unsigned *>(p));
-}
-
-hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes, hipStream_t s) {
-    if (n_rows == 0 || row_len == 0) return hipSuccess;
-    if ((row_len & 3) || (row_stride & 1) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_bytes & 3)) return hipErrorInvalidValue;
-    unsigned char *p = static_cast<unsigned char *>(d_bytes);
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_encode_rows<GDG_FMT_LPCM8>(d_in, row_stride, row_len, n_rows, p, s); break;
-    case GDG_FMT_LPCM16: launch_encode_rows<GDG_FMT_LPCM16>(d_in, row_stride, row_len, n_rows, p, s); break;
-    case GDG_FMT_LPCM24: launch_encode_rows<GDG_FMT_LPCM24>(d_in, row_stride, row_len, n_rows, p, s); break;
-    case GDG_FMT_LPCM32: launch_encode_rows<GDG_FMT_LPCM32>(d_in, row_stride, row_len, n_rows, p, s); break;
-    case GDG_FMT_IEEE32: launch_encode_rows<GDG_FMT_IEEE32>(d_in, row_stride, row_len, n_rows, p, s); break;
-    case GDG_FMT_IEEE64:                                       /* wave.go:694-709: the sample's bytes, no clipping */
-        return hipMemcpy2DAsync(p, row_len * sizeof(double), d_in, row_stride * sizeof(double), row_len * sizeof(double), n_rows, hipMemcpyDeviceToDevice, s);
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
 }
 
 /* The master of one piece of a sharded job in ONE launch (gdg_batch_finish_master and _slice): the slab holds G left rows, G right rows and
@@ -733,40 +678,12 @@ finish_master_kernel(const double *__restrict__ slab, size_t stride, int G, int 
     }
 }
 
-template <int FMT>
-static void launch_finish_master(const double *d_slab, size_t stride, int G, int has_aux, size_t n, void *d_left, void *d_right, double *d_sums,
-                                 size_t sums_stride, hipStream_t s) {
-    const size_t groups = n / 4;
-    const unsigned grid = (unsigned)((groups + 255) / 256);
-    unsigned *wl = static_cast<unsigned *>(d_left), *wr = static_cast<unsigned *>(d_right);
-    if (d_sums) finish_master_kernel<FMT, true><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride);
-    else finish_master_kernel<FMT, false><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, nullptr, 0);
-}
-
-hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
-                                    void *d_right_bytes, double *d_sums, size_t sums_stride, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (n_shards < 1 || (n & 3) || n > stride || (stride & 1) || (sums_stride & 1) || (d_sums && n > sums_stride) || ((uintptr_t)d_slab & 15) ||
-        ((uintptr_t)d_left_bytes & 15) || ((uintptr_t)d_right_bytes & 15) || ((uintptr_t)d_sums & 15))
-        return hipErrorInvalidValue;
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_finish_master<GDG_FMT_LPCM8>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
-    case GDG_FMT_LPCM16: launch_finish_master<GDG_FMT_LPCM16>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
-    case GDG_FMT_LPCM24: launch_finish_master<GDG_FMT_LPCM24>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
-    case GDG_FMT_LPCM32: launch_finish_master<GDG_FMT_LPCM32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
-    case GDG_FMT_IEEE32: launch_finish_master<GDG_FMT_IEEE32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
-    case GDG_FMT_IEEE64: launch_finish_master<GDG_FMT_IEEE64>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, s); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 /* ------------------------------------------------------------------------------------------------
  * The dithered encoders (dither.h; include/gdg.h, gdg_batch_set_dither): TPDF dither with rounding for the four LPCM formats.  No reference
  * counterpart.  The noise of a sample is a hash of (seed, port, index) -- one fmix per sample, two 64-bit multiplies, both 32-bit words
  * used -- so the bytes of a file do not depend on the window, the slicing, the sharding or the launch shape.  Product and adds of the
  * quantiser are __dmul_rn / __dadd_rn (dither.h): never contracted, the bits of the numpy restatement.  Loads, packing and the word-sized
- * non-temporal stores are those of the plain kernels, which stay as they are and serve every call with dither off.
+ * non-temporal stores are those of the plain kernels, which serve every call with dither off.
  * ---------------------------------------------------------------------------------------------- */
 static_assert(GDG_DITHER_K == GDG_DIGEST_K && GDG_DITHER_M0 == GDG_DIGEST_M0 && GDG_DITHER_M1 == GDG_DIGEST_M1, "the dither hashes with the digest's constants");
 
@@ -804,28 +721,6 @@ wave_encode4_rows_dither_kernel(const double *__restrict__ in, size_t row_stride
 #pragma unroll
         for (int k = 0; k < W; k++) __builtin_nontemporal_store(w[k], dst + g * W + k);
     }
-}
-
-template <int FMT>
-static void launch_encode_rows_dither(const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, unsigned char *p, gdg_dither_rows dz, hipStream_t s) {
-    size_t groups = row_len / 4;
-    unsigned tiles = (unsigned)((groups + 255) / 256);
-    wave_encode4_rows_dither_kernel<FMT><<<dim3(tiles, n_rows), dim3(256), 0, s>>>(d_in, row_stride, groups, reinterpret_cast<unsigned *>(p), dz);
-}
-
-hipError_t gdg_launch_wave_encode_rows_dither(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
-                                              gdg_dither_rows dz, hipStream_t s) {
-    if (n_rows == 0 || row_len == 0) return hipSuccess;
-    if ((row_len & 3) || (row_stride & 1) || ((uintptr_t)d_in & 15) || ((uintptr_t)d_bytes & 3)) return hipErrorInvalidValue;
-    unsigned char *p = static_cast<unsigned char *>(d_bytes);
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_encode_rows_dither<GDG_FMT_LPCM8>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
-    case GDG_FMT_LPCM16: launch_encode_rows_dither<GDG_FMT_LPCM16>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
-    case GDG_FMT_LPCM24: launch_encode_rows_dither<GDG_FMT_LPCM24>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
-    case GDG_FMT_LPCM32: launch_encode_rows_dither<GDG_FMT_LPCM32>(d_in, row_stride, row_len, n_rows, p, dz, s); break;
-    default: return hipErrorInvalidValue;                      /* IEEE formats are never dithered: the plain launcher's */
-    }
-    return hipGetLastError();
 }
 
 /* finish_master_kernel's sibling: the same loads and the same adds in the same order; SUMS keeps the float64 sums for the meters and the
@@ -869,33 +764,6 @@ finish_master_dither_kernel(const double *__restrict__ slab, size_t stride, int 
     }
 }
 
-template <int FMT>
-static void launch_finish_master_dither(const double *d_slab, size_t stride, int G, int has_aux, size_t n, void *d_left, void *d_right, double *d_sums,
-                                        size_t sums_stride, unsigned long long seed, unsigned long long first, hipStream_t s) {
-    const size_t groups = n / 4;
-    const unsigned grid = (unsigned)((groups + 255) / 256);
-    unsigned *wl = static_cast<unsigned *>(d_left), *wr = static_cast<unsigned *>(d_right);
-    if (d_sums) finish_master_dither_kernel<FMT, true><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride, seed, first);
-    else finish_master_dither_kernel<FMT, false><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, nullptr, 0, seed, first);
-}
-
-hipError_t gdg_launch_finish_master_dither(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
-                                           void *d_right_bytes, double *d_sums, size_t sums_stride, unsigned long long seed, unsigned long long first,
-                                           hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (n_shards < 1 || (n & 3) || n > stride || (stride & 1) || (sums_stride & 1) || (d_sums && n > sums_stride) || ((uintptr_t)d_slab & 15) ||
-        ((uintptr_t)d_left_bytes & 15) || ((uintptr_t)d_right_bytes & 15) || ((uintptr_t)d_sums & 15))
-        return hipErrorInvalidValue;
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_finish_master_dither<GDG_FMT_LPCM8>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
-    case GDG_FMT_LPCM16: launch_finish_master_dither<GDG_FMT_LPCM16>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
-    case GDG_FMT_LPCM24: launch_finish_master_dither<GDG_FMT_LPCM24>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
-    case GDG_FMT_LPCM32: launch_finish_master_dither<GDG_FMT_LPCM32>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, seed, first, s); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 /* the stand-alone mono form: wave_encode4_kernel's sibling for the aligned bulk ... */
 template <int FMT>
 __global__ void __launch_bounds__(256)
@@ -923,40 +791,12 @@ wave_encode_dither_tail_kernel(const double *__restrict__ in, size_t n, unsigned
     }
 }
 
-template <int FMT>
-static void launch_encode_dither(const double *d_in, size_t n, unsigned char *p, unsigned long long key, unsigned long long first, hipStream_t s) {
-    size_t done = 0;
-    if (n >= 4 && ((uintptr_t)p & 3) == 0 && ((uintptr_t)d_in & 15) == 0) {
-        const size_t groups = n / 4;
-        wave_encode4_dither_kernel<FMT><<<(unsigned)((groups + 255) / 256), 256, 0, s>>>(reinterpret_cast<const v2d *>(d_in), groups, reinterpret_cast<unsigned *>(p), key, first);
-        done = groups * 4;
-    }
-    if (done < n)
-        wave_encode_dither_tail_kernel<FMT><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + done * fmt_width<FMT>::W, key, first + done);
-}
-
-hipError_t gdg_launch_wave_encode_dither(int fmt, const double *d_in, size_t n, void *d_bytes, unsigned long long seed, unsigned port,
-                                         unsigned long long first, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if ((uintptr_t)d_in & 7) return hipErrorInvalidValue;
-    unsigned char *p = static_cast<unsigned char *>(d_bytes);
-    const unsigned long long key = gdg_dither_key(seed, port);
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_encode_dither<GDG_FMT_LPCM8>(d_in, n, p, key, first, s); break;
-    case GDG_FMT_LPCM16: launch_encode_dither<GDG_FMT_LPCM16>(d_in, n, p, key, first, s); break;
-    case GDG_FMT_LPCM24: launch_encode_dither<GDG_FMT_LPCM24>(d_in, n, p, key, first, s); break;
-    case GDG_FMT_LPCM32: launch_encode_dither<GDG_FMT_LPCM32>(d_in, n, p, key, first, s); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 /* ------------------------------------------------------------------------------------------------
  * The trimmed encoders (trim.h; include/gdg.h, gdg_batch_set_trim): a gain per output port in front of the encoder.  No reference
  * counterpart.  y = x * g is ONE __dmul_rn -- rounded before the encoder's scale sees it, never contracted with it -- and then the plain
  * encoder's code (DITHER false: all six formats) or the dithered one's (DITHER true: the four LPCM formats) of y.  Siblings of the four
  * encode paths and of the stand-alone form: the same 16-byte non-temporal loads, packing and word-sized non-temporal stores; the plain
- * and the dithered kernels stay as they are and serve every call with the trim off.  A row's gain is uniform over its workgroup: read once
+ * and the dithered kernels serve every call with the trim off.  A row's gain is uniform over its workgroup: read once
  * from a small device array through the scalar unit (the rows kernel) or a kernel argument (the finish and the stand-alone form).  IEEE64
  * has no code: the product's 8 bytes are the sample's (the plain path copies the rows; here a kernel has to touch them).
  * One FP64 multiply per sample beside 8 bytes read and 1 .. 8 written: no atomics, no LDS, no scratch.
@@ -1028,44 +868,6 @@ wave_encode4_rows_trim_kernel(const double *__restrict__ in, size_t row_stride, 
     }
 }
 
-template <int FMT, bool DITHER>
-static void launch_encode_rows_trim(const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, unsigned char *p, const double *d_gains,
-                                    gdg_dither_rows dz, hipStream_t s) {
-    size_t groups = row_len / 4;
-    unsigned tiles = (unsigned)((groups + 255) / 256);
-    wave_encode4_rows_trim_kernel<FMT, DITHER><<<dim3(tiles, n_rows), dim3(256), 0, s>>>(d_in, row_stride, groups, reinterpret_cast<unsigned *>(p), d_gains, dz);
-}
-
-hipError_t gdg_launch_wave_encode_rows_trim(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
-                                            const double *d_gains, const gdg_dither_rows *dither, hipStream_t s) {
-    if (n_rows == 0 || row_len == 0) return hipSuccess;
-    if (!d_gains || ((uintptr_t)d_gains & 7) || (row_len & 3) || (row_stride & 1) || ((uintptr_t)d_in & 15) ||
-        ((uintptr_t)d_bytes & (fmt == GDG_FMT_IEEE64 ? 7 : 3)))
-        return hipErrorInvalidValue;
-    unsigned char *p = static_cast<unsigned char *>(d_bytes);
-    const gdg_dither_rows none = { 0, 0, 0, 0 };
-    if (dither) {
-        switch (fmt) {
-        case GDG_FMT_LPCM8: launch_encode_rows_trim<GDG_FMT_LPCM8, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
-        case GDG_FMT_LPCM16: launch_encode_rows_trim<GDG_FMT_LPCM16, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
-        case GDG_FMT_LPCM24: launch_encode_rows_trim<GDG_FMT_LPCM24, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
-        case GDG_FMT_LPCM32: launch_encode_rows_trim<GDG_FMT_LPCM32, true>(d_in, row_stride, row_len, n_rows, p, d_gains, *dither, s); break;
-        default: return hipErrorInvalidValue;                  /* IEEE formats are never dithered */
-        }
-        return hipGetLastError();
-    }
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_encode_rows_trim<GDG_FMT_LPCM8, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
-    case GDG_FMT_LPCM16: launch_encode_rows_trim<GDG_FMT_LPCM16, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
-    case GDG_FMT_LPCM24: launch_encode_rows_trim<GDG_FMT_LPCM24, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
-    case GDG_FMT_LPCM32: launch_encode_rows_trim<GDG_FMT_LPCM32, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
-    case GDG_FMT_IEEE32: launch_encode_rows_trim<GDG_FMT_IEEE32, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
-    case GDG_FMT_IEEE64: launch_encode_rows_trim<GDG_FMT_IEEE64, false>(d_in, row_stride, row_len, n_rows, p, d_gains, none, s); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 /* finish_master_kernel's and finish_master_dither_kernel's sibling: the same loads and the same adds in the same order; SUMS keeps the
  * float64 sums for the meters and the records BEFORE the trim; the left side is encoded times gain_left, the right times gain_right */
 template <int FMT, bool SUMS, bool DITHER>
@@ -1102,47 +904,6 @@ finish_master_trim_kernel(const double *__restrict__ slab, size_t stride, int G,
     }
 }
 
-template <int FMT, bool DITHER>
-static void launch_finish_master_trim(const double *d_slab, size_t stride, int G, int has_aux, size_t n, void *d_left, void *d_right, double *d_sums,
-                                      size_t sums_stride, double gl, double gr, unsigned long long seed, unsigned long long first, hipStream_t s) {
-    const size_t groups = n / 4;
-    const unsigned grid = (unsigned)((groups + 255) / 256);
-    unsigned *wl = static_cast<unsigned *>(d_left), *wr = static_cast<unsigned *>(d_right);
-    if (d_sums) finish_master_trim_kernel<FMT, true, DITHER><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride, gl, gr, seed, first);
-    else finish_master_trim_kernel<FMT, false, DITHER><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, nullptr, 0, gl, gr, seed, first);
-}
-
-hipError_t gdg_launch_finish_master_trim(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
-                                         void *d_right_bytes, double *d_sums, size_t sums_stride, double gain_left, double gain_right, int dither,
-                                         unsigned long long seed, unsigned long long first, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (n_shards < 1 || (n & 3) || n > stride || (stride & 1) || (sums_stride & 1) || (d_sums && n > sums_stride) || ((uintptr_t)d_slab & 15) ||
-        ((uintptr_t)d_left_bytes & 15) || ((uintptr_t)d_right_bytes & 15) || ((uintptr_t)d_sums & 15))
-        return hipErrorInvalidValue;
-#define GDG_FINISH_TRIM(F, D) launch_finish_master_trim<F, D>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, gain_left, gain_right, seed, first, s)
-    if (dither) {
-        switch (fmt) {
-        case GDG_FMT_LPCM8: GDG_FINISH_TRIM(GDG_FMT_LPCM8, true); break;
-        case GDG_FMT_LPCM16: GDG_FINISH_TRIM(GDG_FMT_LPCM16, true); break;
-        case GDG_FMT_LPCM24: GDG_FINISH_TRIM(GDG_FMT_LPCM24, true); break;
-        case GDG_FMT_LPCM32: GDG_FINISH_TRIM(GDG_FMT_LPCM32, true); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (fmt) {
-    case GDG_FMT_LPCM8: GDG_FINISH_TRIM(GDG_FMT_LPCM8, false); break;
-    case GDG_FMT_LPCM16: GDG_FINISH_TRIM(GDG_FMT_LPCM16, false); break;
-    case GDG_FMT_LPCM24: GDG_FINISH_TRIM(GDG_FMT_LPCM24, false); break;
-    case GDG_FMT_LPCM32: GDG_FINISH_TRIM(GDG_FMT_LPCM32, false); break;
-    case GDG_FMT_IEEE32: GDG_FINISH_TRIM(GDG_FMT_IEEE32, false); break;
-    case GDG_FMT_IEEE64: GDG_FINISH_TRIM(GDG_FMT_IEEE64, false); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef GDG_FINISH_TRIM
-    return hipGetLastError();
-}
-
 /* the stand-alone mono form: wave_encode4_kernel's and wave_encode4_dither_kernel's sibling for the aligned bulk ... */
 template <int FMT, bool DITHER>
 __global__ void __launch_bounds__(256)
@@ -1168,45 +929,110 @@ wave_encode_trim_tail_kernel(const double *__restrict__ in, size_t n, unsigned c
     }
 }
 
-template <int FMT, bool DITHER>
-static void launch_encode_trim(const double *d_in, size_t n, unsigned char *p, double g, unsigned long long key, unsigned long long first, hipStream_t s) {
-    constexpr size_t BYTES = FMT == GDG_FMT_IEEE64 ? 8 : fmt_width<FMT>::W;
-    size_t done = 0;
-    if (n >= 4 && ((uintptr_t)p & (FMT == GDG_FMT_IEEE64 ? 7 : 3)) == 0 && ((uintptr_t)d_in & 15) == 0) {
-        const size_t groups = n / 4;
-        wave_encode4_trim_kernel<FMT, DITHER><<<(unsigned)((groups + 255) / 256), 256, 0, s>>>(reinterpret_cast<const v2d *>(d_in), groups, reinterpret_cast<unsigned *>(p), g, key, first);
-        done = groups * 4;
+/* ------------------------------------------------------------------------------------------------
+ * The encode launchers: one per form -- rows of a window, the master finish, stand-alone mono -- for the three generations of kernels
+ * above.  A gdg_encode_mode says what the launch does beyond the plain encoder; GDG_DISPATCH_ENCODE turns it and the format into the
+ * constants <FMT, TRIM, DITHER>, and each launch template picks the kernel of that generation: the trimmed one (plain or dithered) when
+ * TRIM, else the dithered one when DITHER, else the plain one.  The kernels' texts are kept apart on purpose: folded into one template
+ * the untrimmed instantiations compiled to other instruction streams than these (profiles/encode_one_path.txt).
+ * ---------------------------------------------------------------------------------------------- */
+/* STMT once with FMT, TRIM and DITHER constants, as the mode M has them: all six formats undithered, the four LPCM formats dithered (the
+ * callers send the IEEE formats here with dither off: gdg_dither_applies) */
+#define GDG_DISPATCH_ENCODE(F, M, STMT)                                                                                 \
+    if ((M).dither) {                                                                                                   \
+        constexpr bool DITHER = true;                                                                                   \
+        if ((M).trim) { constexpr bool TRIM = true; GDG_DISPATCH_LPCM(F, STMT) }                                        \
+        else { constexpr bool TRIM = false; GDG_DISPATCH_LPCM(F, STMT) }                                                \
+    } else {                                                                                                            \
+        constexpr bool DITHER = false;                                                                                  \
+        if ((M).trim) { constexpr bool TRIM = true; GDG_DISPATCH_FMT(F, STMT) }                                         \
+        else { constexpr bool TRIM = false; GDG_DISPATCH_FMT(F, STMT) }                                                 \
     }
-    if (done < n)
-        wave_encode_trim_tail_kernel<FMT, DITHER><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + done * BYTES, g, key, first + done);
-}
 
-hipError_t gdg_launch_wave_encode_trim(int fmt, const double *d_in, size_t n, void *d_bytes, double gain, int dither, unsigned long long seed, unsigned port,
-                                       unsigned long long first, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if ((uintptr_t)d_in & 7) return hipErrorInvalidValue;
-    unsigned char *p = static_cast<unsigned char *>(d_bytes);
-    if (dither) {
-        const unsigned long long key = gdg_dither_key(seed, port);
-        switch (fmt) {
-        case GDG_FMT_LPCM8: launch_encode_trim<GDG_FMT_LPCM8, true>(d_in, n, p, gain, key, first, s); break;
-        case GDG_FMT_LPCM16: launch_encode_trim<GDG_FMT_LPCM16, true>(d_in, n, p, gain, key, first, s); break;
-        case GDG_FMT_LPCM24: launch_encode_trim<GDG_FMT_LPCM24, true>(d_in, n, p, gain, key, first, s); break;
-        case GDG_FMT_LPCM32: launch_encode_trim<GDG_FMT_LPCM32, true>(d_in, n, p, gain, key, first, s); break;
-        default: return hipErrorInvalidValue;
-        }
+template <int FMT, bool TRIM, bool DITHER>
+static hipError_t launch_encode_rows(const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes, const gdg_encode_mode &m, hipStream_t s) {
+    if constexpr (FMT == GDG_FMT_IEEE64 && !TRIM)                  /* wave.go:694-709: the sample's bytes, no clipping -- a copy */
+        return hipMemcpy2DAsync(d_bytes, row_len * sizeof(double), d_in, row_stride * sizeof(double), row_len * sizeof(double), n_rows, hipMemcpyDeviceToDevice, s);
+    else {
+        const size_t groups = row_len / 4;
+        const dim3 grid((unsigned)((groups + 255) / 256), n_rows);
+        unsigned *words = static_cast<unsigned *>(d_bytes);
+        if constexpr (TRIM) wave_encode4_rows_trim_kernel<FMT, DITHER><<<grid, dim3(256), 0, s>>>(d_in, row_stride, groups, words, m.d_gains, m.dz);
+        else if constexpr (DITHER) wave_encode4_rows_dither_kernel<FMT><<<grid, dim3(256), 0, s>>>(d_in, row_stride, groups, words, m.dz);
+        else wave_encode4_rows_kernel<FMT><<<grid, dim3(256), 0, s>>>(d_in, row_stride, groups, words);
         return hipGetLastError();
     }
-    switch (fmt) {
-    case GDG_FMT_LPCM8: launch_encode_trim<GDG_FMT_LPCM8, false>(d_in, n, p, gain, 0, first, s); break;
-    case GDG_FMT_LPCM16: launch_encode_trim<GDG_FMT_LPCM16, false>(d_in, n, p, gain, 0, first, s); break;
-    case GDG_FMT_LPCM24: launch_encode_trim<GDG_FMT_LPCM24, false>(d_in, n, p, gain, 0, first, s); break;
-    case GDG_FMT_LPCM32: launch_encode_trim<GDG_FMT_LPCM32, false>(d_in, n, p, gain, 0, first, s); break;
-    case GDG_FMT_IEEE32: launch_encode_trim<GDG_FMT_IEEE32, false>(d_in, n, p, gain, 0, first, s); break;
-    case GDG_FMT_IEEE64: launch_encode_trim<GDG_FMT_IEEE64, false>(d_in, n, p, gain, 0, first, s); break;
-    default: return hipErrorInvalidValue;
+}
+
+hipError_t gdg_launch_wave_encode_rows(int fmt, const double *d_in, size_t row_stride, size_t row_len, unsigned n_rows, void *d_bytes,
+                                       const gdg_encode_mode &m, hipStream_t s) {
+    if (n_rows == 0 || row_len == 0) return hipSuccess;
+    if ((m.trim && (!m.d_gains || ((uintptr_t)m.d_gains & 7))) || (row_len & 3) || (row_stride & 1) || ((uintptr_t)d_in & 15) ||
+        ((uintptr_t)d_bytes & (m.trim && fmt == GDG_FMT_IEEE64 ? 7 : 3)))      /* the trimmed IEEE64 rows are written 8 bytes at a time */
+        return hipErrorInvalidValue;
+    GDG_DISPATCH_ENCODE(fmt, m, return (launch_encode_rows<FMT, TRIM, DITHER>(d_in, row_stride, row_len, n_rows, d_bytes, m, s)));
+}
+
+template <int FMT, bool SUMS, bool TRIM, bool DITHER>
+static void launch_finish_master_sums(const double *d_slab, size_t stride, int G, int has_aux, size_t groups, unsigned *wl, unsigned *wr, double *d_sums,
+                                      size_t sums_stride, const gdg_encode_mode &m, hipStream_t s) {
+    const unsigned grid = (unsigned)((groups + 255) / 256);
+    if constexpr (TRIM)
+        finish_master_trim_kernel<FMT, SUMS, DITHER><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride, m.gain[0], m.gain[1], m.dz.seed, m.dz.first);
+    else if constexpr (DITHER)
+        finish_master_dither_kernel<FMT, SUMS><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride, m.dz.seed, m.dz.first);
+    else
+        finish_master_kernel<FMT, SUMS><<<grid, 256, 0, s>>>(d_slab, stride, G, has_aux, groups, wl, wr, d_sums, sums_stride);
+}
+
+template <int FMT, bool TRIM, bool DITHER>
+static hipError_t launch_finish_master(const double *d_slab, size_t stride, int G, int has_aux, size_t n, void *d_left, void *d_right, double *d_sums,
+                                       size_t sums_stride, const gdg_encode_mode &m, hipStream_t s) {
+    unsigned *wl = static_cast<unsigned *>(d_left), *wr = static_cast<unsigned *>(d_right);
+    if (d_sums) launch_finish_master_sums<FMT, true, TRIM, DITHER>(d_slab, stride, G, has_aux, n / 4, wl, wr, d_sums, sums_stride, m, s);
+    else launch_finish_master_sums<FMT, false, TRIM, DITHER>(d_slab, stride, G, has_aux, n / 4, wl, wr, nullptr, 0, m, s);
+    return hipGetLastError();
+}
+
+hipError_t gdg_launch_finish_master(int fmt, const double *d_slab, size_t stride, int n_shards, int has_aux, size_t n, void *d_left_bytes,
+                                    void *d_right_bytes, double *d_sums, size_t sums_stride, const gdg_encode_mode &m, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n_shards < 1 || (n & 3) || n > stride || (stride & 1) || (sums_stride & 1) || (d_sums && n > sums_stride) || ((uintptr_t)d_slab & 15) ||
+        ((uintptr_t)d_left_bytes & 15) || ((uintptr_t)d_right_bytes & 15) || ((uintptr_t)d_sums & 15))
+        return hipErrorInvalidValue;
+    GDG_DISPATCH_ENCODE(fmt, m, return (launch_finish_master<FMT, TRIM, DITHER>(d_slab, stride, n_shards, has_aux, n, d_left_bytes, d_right_bytes, d_sums, sums_stride, m, s)));
+}
+
+template <int FMT, bool TRIM, bool DITHER>
+static hipError_t launch_encode(const double *d_in, size_t per, unsigned channels, unsigned char *p, const gdg_encode_mode &m, hipStream_t s) {
+    constexpr size_t BYTES = FMT == GDG_FMT_IEEE64 ? 8 : fmt_width<FMT>::W;     /* per sample */
+    const unsigned long long key = DITHER ? gdg_dither_key(m.dz.seed, m.dz.port_base) : 0ull, first = m.dz.first;
+    size_t n = per * channels, done = 0;
+    /* the untrimmed IEEE64 bytes are the samples: the one-sample kernel copies them, whatever the alignment */
+    if ((TRIM || FMT != GDG_FMT_IEEE64) && channels == 1 && n >= 4 && ((uintptr_t)p & (FMT == GDG_FMT_IEEE64 ? 7 : 3)) == 0 && ((uintptr_t)d_in & 15) == 0) {
+        const size_t groups = n / 4;
+        const unsigned grid = (unsigned)((groups + 255) / 256);
+        const v2d *in = reinterpret_cast<const v2d *>(d_in);
+        unsigned *words = reinterpret_cast<unsigned *>(p);
+        if constexpr (TRIM) wave_encode4_trim_kernel<FMT, DITHER><<<grid, 256, 0, s>>>(in, groups, words, m.gain[0], key, first);
+        else if constexpr (DITHER) wave_encode4_dither_kernel<FMT><<<grid, 256, 0, s>>>(in, groups, words, key, first);
+        else wave_encode4_kernel<FMT><<<grid, 256, 0, s>>>(in, groups, words);
+        done = groups * 4;
+    }
+    if (done < n) {         /* tail and unaligned buffers, and the plain encoder's multi-channel files: one sample per thread */
+        if constexpr (TRIM) wave_encode_trim_tail_kernel<FMT, DITHER><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + done * BYTES, m.gain[0], key, first + done);
+        else if constexpr (DITHER) wave_encode_dither_tail_kernel<FMT><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + done * BYTES, key, first + done);
+        else if (channels == 1) wave_encode_kernel<FMT><<<grid_for(n - done), 256, 0, s>>>(d_in + done, n - done, p + done * BYTES, 1, n - done);
+        else wave_encode_kernel<FMT><<<grid_for(n), 256, 0, s>>>(d_in, n, p, channels, per);
     }
     return hipGetLastError();
+}
+
+/* trimmed or dithered: mono, any 8-byte alignment of d_in and any byte alignment of d_bytes */
+hipError_t gdg_launch_wave_encode(int fmt, const double *d_in, size_t per, unsigned channels, void *d_bytes, const gdg_encode_mode &m, hipStream_t s) {
+    if (per * channels == 0) return hipSuccess;
+    if ((m.trim || m.dither) && (channels != 1 || ((uintptr_t)d_in & 7))) return hipErrorInvalidValue;
+    GDG_DISPATCH_ENCODE(fmt, m, return (launch_encode<FMT, TRIM, DITHER>(d_in, per, channels, static_cast<unsigned char *>(d_bytes), m, s)));
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -9,6 +9,10 @@ The parent's tree, built, is expected beside this one:
 
     python profiles/probes/batch_dither_ab.py [rounds]        -> the table on stdout (and in $AB_OUT when set)
 
+AB_MODES=all: the parent AND this commit in each of the encoders' four modes -- plain, dithered, trimmed (every gain 0.5), trimmed with
+dither -- as forms parent-off, new-off, parent-on, new-on, parent-trim, new-trim, parent-trim_on, new-trim_on (the fold of the encoders,
+profiles/encode_one_path.txt).
+
 A leg: 3 warm-up calls, then CALLS timed calls of the C call alone (arguments marshalled once, as bench.py times it); then, outside
 the timed calls, 2 more calls with the encoder launches bracketed by events (profile kind K_WAVE: in a batch run without the render
 report that is the encoder of every step and nothing else).  Per form the table gives the median over all timed calls of all rounds,
@@ -29,15 +33,18 @@ LEG_TIMEOUT = 300                                        # seconds; a leg takes 
 K_WAVE = 6
 
 
-def child(root, form):
+def child(root, form, mode=None):
+    mode = mode or ("on" if form == "on" else "off")
     sys.path.insert(0, root)
     import bench
     import __graft_entry__ as entry
     pkg = entry.load_package()
     ctx = bench.make_context(pkg, NCH, 8192, 0, TAPS)
     ctx.set_window(W)
-    if form == "on":
+    if mode in ("on", "trim_on"):
         ctx.batch_set_dither(1, 0x5eed, 0)
+    if mode in ("trim", "trim_on"):
+        ctx.batch_set_trim([0.5] * NCH, 0.5, 0.5, 0.5)
     call, outs = ctx.batch_prepared(bench.batch_files(NCH, SR, BLOCKS), SR, "lpcm24")
     for _ in range(3):
         call()
@@ -61,10 +68,14 @@ def main():
     parent = os.environ.get("AB_PARENT", os.path.join(ROOT, ".ab_parent"))
     forms = [("parent", parent)] if os.path.exists(os.path.join(parent, "go-dsp-guitar_amd", "lib", "libgdg.so")) else []
     forms += [("off", ROOT), ("on", ROOT)]
+    modes = {"off": "off", "on": "on", "parent": "off"}
+    if os.environ.get("AB_MODES") == "all":
+        forms = [(who + "-" + m, root) for m in ("off", "on", "trim", "trim_on") for who, root in (("parent", parent), ("new", ROOT))]
+        modes = {f: f.split("-", 1)[1] for f, _ in forms}
     legs, enc, lines = {}, {}, []
     for r in range(rounds):
         for form, root in forms:
-            cmd = ["timeout", "-k", "10", str(LEG_TIMEOUT), sys.executable, os.path.abspath(__file__), "--child", root, form]
+            cmd = ["timeout", "-k", "10", str(LEG_TIMEOUT), sys.executable, os.path.abspath(__file__), "--child", root, form, modes[form]]
             p = subprocess.run(cmd, capture_output=True, text=True, cwd=root)
             got = [l for l in p.stdout.splitlines() if l.startswith("LEG ")]
             if p.returncode != 0 or not got:
@@ -75,7 +86,7 @@ def main():
             legs.setdefault(form, []).append(leg["ms"])
             if leg["enc_n"]:
                 enc.setdefault(form, []).append(leg["enc_ms"] / PROFILED)
-            lines.append("%-6s round %d: median %.2f | %s | encoder %.3f ms per call (%d launches in %d calls)" % (
+            lines.append("%-14s round %d: median %.2f | %s | encoder %.3f ms per call (%d launches in %d calls)" % (
                 form, r + 1, statistics.median(leg["ms"]), " ".join("%.2f" % v for v in leg["ms"]), leg["enc_ms"] / PROFILED, leg["enc_n"], PROFILED))
             print(lines[-1], flush=True)
     report(lines, legs, enc, forms)
@@ -90,7 +101,7 @@ def report(lines, legs, enc, forms):
             "# fastest .. slowest process median (the run-to-run spread); best = the fastest call.  encoder = the encode launches of one call,",
             "# summed, bracketed by events in %d further calls; its rate = the job's %.1f MB (%d rows x %d blocks x 8192 samples x 11 bytes) over that time." % (
                 PROFILED, call_bytes / 1e6, NCH + 3, BLOCKS)]
-    if not any(f == "parent" for f, _ in forms):
+    if not any(f.startswith("parent") for f, _ in forms):
         head.append("# NO PARENT TREE was found beside this one: the parent's legs are missing.")
     for form, _ in forms:
         runs = legs.get(form)
@@ -100,7 +111,7 @@ def report(lines, legs, enc, forms):
         meds = [statistics.median(r) for r in runs]
         e = enc.get(form, [])
         tail = "   encoder %.3f ms per call (%.3f .. %.3f), %.2f TB/s" % (statistics.median(e), min(e), max(e), call_bytes / (statistics.median(e) * 1e-3) / 1e12) if e else ""
-        head.append("#   %-6s: median %.2f   processes %.2f .. %.2f   best %.2f   (%d processes)%s" % (form, statistics.median(allms), min(meds), max(meds), min(allms),
+        head.append("#   %-14s: median %.2f   processes %.2f .. %.2f   best %.2f   (%d processes)%s" % (form, statistics.median(allms), min(meds), max(meds), min(allms),
                                                                                                   len(runs), tail))
     if legs.get("on") and legs.get("off"):
         on, off = statistics.median([v for r in legs["on"] for v in r]), statistics.median([v for r in legs["off"] for v in r])
@@ -119,6 +130,6 @@ def report(lines, legs, enc, forms):
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
-        child(sys.argv[2], sys.argv[3])
+        child(*sys.argv[2:5])
     else:
         sys.exit(main())

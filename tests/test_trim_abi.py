@@ -106,7 +106,8 @@ def test_every_layer_knows_the_calls(pkg):
 def test_the_trim_kernels_use_no_scratch(tmp_path):
     """Every instantiation of the five new kernels, from the compiler's resource summary: no scratch, no LDS, no atomics, and the product is
     a v_mul_f64 of its own -- no fused multiply-add of doubles anywhere in them.  50 instantiations: the rows kernel and the two
-    stand-alone ones in six plain and four dithered formats, the finish kernel in those with and without the sums."""
+    stand-alone ones in six plain and four dithered formats, the finish kernel in those with and without the sums.  And the 43 untrimmed
+    instantiations beside them: the same figures without the product's multiply."""
     out = str(tmp_path / "io.s")
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only", "-x", "hip",
                     os.path.join(CSRC, "io.hip"), "-o", out], check=True, timeout=900, cwd=CSRC, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -121,3 +122,21 @@ def test_the_trim_kernels_use_no_scratch(tmp_path):
     assert kinds == {"wave_encode4_rows_trim_kernel": 10, "finish_master_trim_kernel": 20, "wave_encode4_trim_kernel": 10, "wave_encode_trim_tail_kernel": 10}, kinds
     for name, (vgprs, scratch, lds, fma, mul, atomic, scratch_ops) in found.items():
         assert scratch == 0 and scratch_ops == 0 and lds == 0 and fma == 0 and atomic == 0 and mul >= 1 and vgprs <= 128, (name, vgprs, scratch, lds, fma, mul, atomic)
+    # The plain and the dithered kernels, which the same three launchers start with the trim off: the same figures, and the only v_mul_f64
+    # are the quantiser's scale -- one per LPCM sample a thread encodes (4 per group, 8 in the finish's two sides, 1 in the tail), none
+    # for the IEEE formats.  A multiply by a gain of 1.0 would show here.
+    per_thread = {"wave_encode4_rows_kernel": 4, "wave_encode4_rows_dither_kernel": 4, "finish_master_kernel": 8, "finish_master_dither_kernel": 8,
+                  "wave_encode4_kernel": 4, "wave_encode4_dither_kernel": 4, "wave_encode_dither_tail_kernel": 1}
+    untrimmed = {k: 0 for k in per_thread}
+    for m in re.finditer(r"^(_Z\d+([a-z0-9_]+)ILi(\d+)E\w+):\s*; @(.*?)^; TotalNumVgprs: (\d+).*?^; ScratchSize: (\d+).*?^; LDSByteSize: (\d+)", text, re.S | re.M):
+        name, kind, fmt, body = m.group(1), m.group(2), int(m.group(3)), m.group(4)
+        if kind not in per_thread:
+            continue
+        untrimmed[kind] += 1
+        figures = (int(m.group(5)), int(m.group(6)), int(m.group(7)), body.count("v_fma_f64"), body.count("atomic"), body.count("scratch_"))
+        assert figures[1:] == (0, 0, 0, 0, 0) and figures[0] <= 128, (name, figures)
+        assert body.count("v_mul_f64") == (per_thread[kind] if fmt <= 3 else 0), (name, body.count("v_mul_f64"))
+    # the plain kernels in five formats (IEEE64's rows are a copy, its bytes the one-sample kernel's; the bulk kernel's IEEE64 instantiation
+    # is never launched), the dithered ones in four, the finish in six and four with and without the sums
+    assert untrimmed == {"wave_encode4_rows_kernel": 5, "wave_encode4_rows_dither_kernel": 4, "finish_master_kernel": 12, "finish_master_dither_kernel": 8,
+                         "wave_encode4_kernel": 6, "wave_encode4_dither_kernel": 4, "wave_encode_dither_tail_kernel": 4}, untrimmed
