@@ -60,6 +60,8 @@ ABI_SYMBOLS = [
     "gdg_batch_gram_enable", "gdg_batch_gram_ports", "gdg_batch_gram", "gdg_block_gram_rows", "gdg_block_gram_rows_device", "gdg_blend_pick_from_gram",
     "gdg_batch_tapfit_enable", "gdg_batch_tapfits", "gdg_batch_tapfit", "gdg_block_tapfit_rows", "gdg_block_tapfit_rows_device", "gdg_tapfit_doubles",
     "gdg_blend_taps_from_tapfit",
+    "gdg_batch_transfer_enable", "gdg_batch_transfers", "gdg_batch_transfer", "gdg_block_transfer_rows", "gdg_block_transfer_rows_device", "gdg_transfer_doubles",
+    "gdg_match_taps_from_transfer",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -282,6 +284,42 @@ def blend_taps_from_tapfit(records, fits, ridge=0.0):
         out.append(tap[at:at + K * T].reshape(K, T).copy())
         at += K * T
     return out, residual[:len(fits)].copy()
+
+
+TRANSFER_BLOCK = 8192        # GDG_TRANSFER_BLOCK (include/gdg.h, TRANSFER): the block of a transfer record = its transform
+TRANSFER_MAX_PAIRS = 16      # GDG_TRANSFER_MAX_PAIRS: the (port, target) pairs of one list
+TRANSFER_MAX_GROUP = 64      # GDG_TRANSFER_MAX_GROUP: the widest group of bins, D in 1, 2, 4 .. 64
+
+
+def _transfer_lists(pairs):
+    """pairs = [(port, target), ...] -> port, target as int32 arrays, one spare entry behind each"""
+    pairs = [(int(p), int(t)) for p, t in pairs]
+    return np.array([p for p, _ in pairs] + [0], dtype=np.int32), np.array([t for _, t in pairs] + [0], dtype=np.int32)
+
+
+def transfer_doubles(n_pairs, group):
+    """gdg_transfer_doubles: the doubles of one block's transfer record, n_pairs x (4096 / group + 1) x 4; 0 for no pair or a width that is none"""
+    return int(lib().gdg_transfer_doubles(int(n_pairs), int(group)))
+
+
+def match_taps_from_transfer(records, n_pairs, group, n_taps, center=0, ridge=0.0):
+    """gdg_match_taps_from_transfer: records [blocks, n_pairs x G x 4] float64 (as batch_transfer hands them out; any shape of that size per
+    block) -> (taps [n_pairs, n_taps], coherence [n_pairs]).  Per pair H = Sxy / (Sxx + ridge * mean Sxx) over the summed blocks, the inverse
+    real transform of length N' = 8192 / group, n_taps <= N' / 2 taps around `center` under a raised-cosine taper.  Host arithmetic: no
+    context, no device.  GdgError for a NaN or inf entry and for a pair with no energy in its port (the message names the pair)."""
+    per = transfer_doubles(n_pairs, group)
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    rec = rec.reshape(rec.shape[0], -1) if rec.ndim >= 1 and rec.size else rec.reshape(0, per)
+    if per and rec.shape[1] != per:
+        raise ValueError("records: [blocks, %d]" % per)
+    tap = np.full((max(int(n_pairs), 0), max(int(n_taps), 0)), np.nan, dtype=np.float64)
+    coherence = np.full(max(int(n_pairs), 0), np.nan, dtype=np.float64)
+    spare = np.zeros(1, dtype=np.float64)
+    rc = lib().gdg_match_taps_from_transfer(rec.ctypes.data if rec.size else None, int(n_pairs), int(group), rec.shape[0], float(ridge), int(n_taps), int(center),
+                                            tap.ctypes.data if tap.size else spare.ctypes.data, coherence.ctypes.data if coherence.size else spare.ctypes.data)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return tap, coherence
 
 
 ALIGN_BLOCK = 8192           # the alignment report's block = its transform (include/gdg.h)
@@ -560,6 +598,13 @@ def lib():
             "gdg_block_tapfit_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, i32, vp, vp, vp, vp, vp]),
             "gdg_tapfit_doubles": (C.c_size_t, [i32, vp, vp]),
             "gdg_blend_taps_from_tapfit": (i32, [vp, i32, vp, vp, C.c_size_t, C.c_double, vp, vp]),
+            "gdg_batch_transfer_enable": (i32, [vp, i32, vp, vp, i32]),
+            "gdg_batch_transfers": (i32, [vp]),
+            "gdg_batch_transfer": (i32, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+            "gdg_block_transfer_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp, i32, vp]),
+            "gdg_block_transfer_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, i32, vp]),
+            "gdg_transfer_doubles": (C.c_size_t, [i32, i32]),
+            "gdg_match_taps_from_transfer": (i32, [vp, i32, i32, C.c_size_t, C.c_double, i32, i32, vp, vp]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1660,6 +1705,56 @@ class Context:
         first, port, target, taps = _tapfit_csr(fits)
         self._check(lib().gdg_block_tapfit_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(block), len(fits), first.ctypes.data, port.ctypes.data,
                                                        target.ctypes.data, taps.ctypes.data, d_records))
+
+    # -- the transfer records: per block and pair the auto- and cross-spectra in groups of bins, match taps from them (include/gdg.h, TRANSFER) --
+    def batch_transfer_enable(self, pairs, group=1):
+        """From the next batch call on, every batch call keeps the transfer records of what it rendered (gdg_batch_transfer_enable): pairs =
+        a list of up to 16 (port, target) of the call, group = the bins summed into one group (1, 2, 4 .. 64).  None or an empty list: off.
+        Configuration: not in a checkpoint, refused while a streamed job is open."""
+        pairs = [] if pairs is None else list(pairs)
+        if not pairs:
+            self._check(lib().gdg_batch_transfer_enable(self._h, 0, None, None, int(group)))
+            return
+        port, target = _transfer_lists(pairs)
+        self._check(lib().gdg_batch_transfer_enable(self._h, len(pairs), port.ctypes.data, target.ctypes.data, int(group)))
+
+    def batch_transfers(self):
+        """The number of transfer pairs in force (gdg_batch_transfers)."""
+        return int(lib().gdg_batch_transfers(self._h))
+
+    def batch_transfer(self):
+        """The [blocks, n_pairs x G x 4] float64 transfer records of the last completed batch call; GdgError when there are none."""
+        blocks, per = C.c_size_t(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_transfer(self._h, None, 0, C.byref(blocks), C.byref(per)))
+        out = np.zeros((blocks.value, per.value), dtype=np.float64)
+        self._check(lib().gdg_batch_transfer(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
+        return out
+
+    def block_transfer(self, rows, pairs, group=1):
+        """gdg_block_transfer_rows: rows [n_rows, samples] float64 (or a list of equally long 1-D arrays), pairs = (port, target) naming rows
+        -> the [ceil(samples / 8192), n_pairs, 4096 / group + 1, 4] records (Sxx, Syy, Re Sxy, Im Sxy)."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        pairs = list(pairs)
+        port, target = _transfer_lists(pairs)
+        per = transfer_doubles(len(pairs), group)
+        out = np.zeros((-(-samples // TRANSFER_BLOCK), per), dtype=np.float64)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_transfer_rows(self._h, ptrs, n, samples, len(pairs), port.ctypes.data, target.ctypes.data, int(group), out.ctypes.data if out.size else None))
+        return out.reshape(out.shape[0], len(pairs), -1, 4) if per else out
+
+    def block_transfer_device(self, d_rows, row_stride, n_rows, samples, pairs, group, d_records):
+        """gdg_block_transfer_rows_device on plain device pointers (ints); returns when the records are written."""
+        pairs = list(pairs)
+        port, target = _transfer_lists(pairs)
+        self._check(lib().gdg_block_transfer_rows_device(self._h, d_rows, row_stride, n_rows, samples, len(pairs), port.ctypes.data, target.ctypes.data, int(group), d_records))
+
+    transfer_doubles = staticmethod(transfer_doubles)
+    match_taps_from_transfer = staticmethod(match_taps_from_transfer)
 
     def batch_report(self):
         """The [ports][blocks] records (BLOCK_STATS_DTYPE) of the last completed batch call; GdgError when there is none."""

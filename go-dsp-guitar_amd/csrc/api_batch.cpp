@@ -125,6 +125,8 @@ struct BatchLoop {
     /* the list records (report_sections.h: the blend fits, the Gram list, the tap fits): per kind the list's table on the host and on the
      * device, the entries it counts and what it sends down per block; count 0 and a shape that is off = off, and always for a shard */
     struct List { const int *h_table, *d_table; int count; ListShape shape; } list[LIST_KINDS];
+    /* ... and the transfer list (include/gdg.h, TRANSFER) in the same terms: its section rides behind theirs; count 0 = off, and always for a shard */
+    List transfer;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -164,7 +166,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; ListSections lists; };
+    struct Step { size_t off; int w; ReportSections sec; ListSections lists; ListSection transfer; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -176,7 +178,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {}, {} });
+        steps.push_back({ off, w, {}, {}, {} });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
@@ -193,6 +195,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     for (size_t i = 0; i < steps.size(); i++) {
         steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
         steps[i].lists = list_sections(steps[i].sec.end, list_shape, (size_t)steps[i].w);        /* behind the last of them: [fits][w], [w], [w] */
+        steps[i].transfer = transfer_section(steps[i].lists, p.transfer.shape, (size_t)steps[i].w);  /* ... and the transfer records behind those: [w] */
     }
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
@@ -208,6 +211,8 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     if (p.bands && (r = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2)) != GDG_OK) return r;
     double2 *align_tw = nullptr, *align_tw2 = nullptr;
     if (p.align && (r = fir_tables(ctx, GDG_ALIGN_BLOCK, &align_tw, &align_tw2)) != GDG_OK) return r;
+    double2 *transfer_tw = nullptr;
+    if (p.transfer.count && (r = fir_tables(ctx, GDG_TRANSFER_BLOCK, &transfer_tw, &align_tw2)) != GDG_OK) return r;      /* the same transform's tables as the alignment's */
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
     auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
@@ -234,6 +239,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
         for (int k = 0; k < LIST_KINDS; k++)
             if (p.list[k].count) list_file(ctx, k, src + steps[i].lists.of[k].at, (size_t)steps[i].w, steps[i].off / B);
+        if (p.transfer.count) transfer_file(ctx, src + steps[i].transfer.at, (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -303,6 +309,10 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 if (p.list[k].count)
                     HIP_TRY(ctx, list_launch[k](d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.list[k].h_table, p.list[k].d_table, (unsigned)p.list[k].count,
                                                 enc + steps[i].lists.of[k].at, ctx->stream));
+            /* ... and the transfer records of the same rows: a block of the loop is a block of the record (8192 samples) */
+            if (p.transfer.count)
+                HIP_TRY(ctx, gdg_launch_block_transfer(d_win, ws, (unsigned)NR, (size_t)wb, p.transfer.h_table, p.transfer.d_table, (unsigned)p.transfer.count, transfer_tw,
+                                                       enc + steps[i].transfer.at, ctx->stream));
             /* dither on: n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
@@ -335,7 +345,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = (size_t)wb * out_width;
-        const size_t down = steps[i].lists.end;
+        const size_t down = steps[i].transfer.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
@@ -604,6 +614,34 @@ int gdg_batch_tapfit_enable(gdg_ctx *ctx, int n_fits, const int *first, const in
 
 int gdg_batch_tapfits(const gdg_ctx *ctx) { return ctx ? ctx->tapfit.count() : 0; }
 
+/* the transfer list: validated whole before it replaces the list in force (blend.h); the ports' upper bound is the job's, checked when one is
+ * described.  What list_enable does for the three kinds, on the list's own slot and store: another size sent down -- the download halves are
+ * made anew by the next batch call -- and off, the table goes as well; the last call's records are read with the list that made them */
+int gdg_batch_transfer_enable(gdg_ctx *ctx, int n_pairs, const int *port, const int *target, int group) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "batch transfer: a streamed batch run is open on this context; its list holds until gdg_batch_stream_close");
+    if (!port) n_pairs = 0;
+    const int rc = transfer_list_check(ctx, "batch transfer", n_pairs, port, target, group, -1);
+    if (rc != GDG_OK) return rc;
+    static_assert(GDG_TRANSFER_BLOCK == GDG_BLOCK_SIZE, "a block of the batch loop is a block of the transfer record");
+    std::vector<int> table = gdg_transfer_table(n_pairs, port, target, group);
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    if (n_pairs) {                                                           /* made here: no batch call allocates or uploads the transform's table */
+        double2 *tw = nullptr, *tw2 = nullptr;
+        const int rt = fir_tables(ctx, GDG_TRANSFER_BLOCK, &tw, &tw2);
+        if (rt != GDG_OK) return rt;
+    }
+    if (gdg_transfer_list_doubles(n_pairs, group) != ctx->transfer.doubles() || table.size() != ctx->transfer.table.size()) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i : { (int)BATCH_ENCODED, (int)BATCH_TRANSFER_TABLE }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    }
+    ctx->transfer_rec.valid = false;
+    ctx->transfer.table.swap(table);
+    return GDG_OK;
+}
+
+int gdg_batch_transfers(const gdg_ctx *ctx) { return ctx ? ctx->transfer.count() : 0; }
+
 /* the master cursor belongs to gdg_batch_finish_master_slice, which is no part of an open job: it may be set while one is open */
 int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
     if (!ctx) return GDG_ERR_INVALID;
@@ -625,6 +663,9 @@ int lists_refused(gdg_ctx *ctx, const char *what) {
         const int count = list_in_force(ctx, k).count;
         if (count) return fail(ctx, GDG_ERR_UNSUPPORTED, text[k], what, count);
     }
+    if (ctx && ctx->transfer.count())
+        return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d transfer pairs are in force on this context (gdg_batch_transfer_enable); a sharded job cannot collect transfer records yet",
+                    what, ctx->transfer.count());
     return GDG_OK;
 }
 
@@ -683,6 +724,13 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
         if (f >= 0)
             return fail(ctx, GDG_ERR_INVALID, "batch tapfit: fit %d, term %d names port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", f, term, ctx->tapfit.port(f, term),
                         n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
+    }
+    if (!shard && ctx->transfer.count()) {                                       /* the transfer pairs' ports against this call's */
+        int side = 0;
+        const int q = ctx->transfer.first_outside(n_inputs + 3 + n_blends, &side);
+        if (q >= 0)
+            return fail(ctx, GDG_ERR_INVALID, "batch transfer: pair %d has the %s port %d, this call has ports 0 to %d (N + 3 = %d and %d blends)", q, side ? "target" : "measured",
+                        side ? ctx->transfer.target(q) : ctx->transfer.port(q), n_inputs + 2 + n_blends, n_inputs + 3, n_blends);
     }
     int rc;
     if (meters_at_open && (rc = check_meter_ports(ctx, opt, shard ? SHARD_PORTS : "")) != GDG_OK) return rc;
@@ -813,6 +861,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         lists[k] = sharded ? ListInForce{ nullptr, 0, 0, { 0, 0 } } : list_in_force(ctx, k);
         if (lists[k].count) list_begin(ctx, k, (size_t)blocks);
     }
+    const ListInForce transfer = sharded ? ListInForce{ nullptr, 0, 0, { 0, 0 } } : transfer_in_force(ctx);
+    if (transfer.count) transfer_begin(ctx, (size_t)blocks);
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -838,7 +888,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
                            + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + list_room(lists[LIST_FIT].shape, (size_t)W)
-                           + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W);
+                           + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W) + list_room(transfer.shape, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -1008,7 +1058,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, {} };
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, {}, { nullptr, nullptr, 0, { 0, 0 } } };
         /* the lists in force -- the fits' table, the Gram list, the tap fits' table: each goes up on the context's stream, ahead of everything
          * the slice enqueues there; it lives as long as the setting, so nothing waits here */
         for (int k = 0; k < LIST_KINDS; k++) {
@@ -1018,6 +1068,12 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             if ((r = batch_buffer(ctx, BATCH_FIT_TABLE + k, L.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
             HIP_TRY(ctx, hipMemcpyAsync(d_table, L.table, L.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
             loop.list[k] = { L.table, d_table, L.count, L.shape };
+        }
+        if (transfer.count) {                                                 /* ... and the transfer list's, into its own slot */
+            int *d_table = nullptr;
+            if ((r = batch_buffer(ctx, BATCH_TRANSFER_TABLE, transfer.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(d_table, transfer.table, transfer.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            loop.transfer = { transfer.table, d_table, transfer.count, transfer.shape };
         }
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
@@ -1116,6 +1172,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
         ctx->batch_up_bytes = ctx->batch_resampled = 0;
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
         for (int k = 0; k < LIST_KINDS && !shard; k++) list_begin(ctx, k, 0);
+        if (!shard) transfer_begin(ctx, 0);
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;

@@ -1186,6 +1186,113 @@ int gdg_blend_taps_from_tapfit(const double *records, int n_fits, const int *fir
     return GDG_ERR_INVALID;
 }
 
+/* ---- the transfer records (include/gdg.h, TRANSFER; the kernel: transfer_kernels.h in fir.hip; the list's validation and the planner: blend.h; the batch calls fill it: api_batch.cpp) ---- */
+/* A transfer list held against gdg_transfer_check, refused in the words of the call `what`: the ONE place they are worded; n_rows as for the fits */
+int transfer_list_check(gdg_ctx *ctx, const char *what, int n_pairs, const int *port, const int *target, int group, int n_rows) {
+    int q = -1;
+    switch (gdg_transfer_check(n_pairs, port, target, group, n_rows, &q)) {
+    case TRANSFER_OK: return GDG_OK;
+    case TRANSFER_COUNT: return fail(ctx, GDG_ERR_INVALID, "%s: %d pairs; 0 (off) to %d", what, n_pairs, GDG_TRANSFER_MAX_PAIRS);
+    case TRANSFER_NULL: return fail(ctx, GDG_ERR_INVALID, "%s: %d pairs need port and target", what, n_pairs);
+    case TRANSFER_GROUP: return fail(ctx, GDG_ERR_INVALID, "%s: a group width of %d bins; 1, 2, 4, 8, 16, 32 or %d", what, group, GDG_TRANSFER_MAX_GROUP);
+    case TRANSFER_PORT:
+        if (n_rows >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: pair %d names row %d of %d", what, q, port[q], n_rows);
+        return fail(ctx, GDG_ERR_INVALID, "%s: pair %d names port %d; ports start at 0", what, q, port[q]);
+    default:
+        if (n_rows >= 0) return fail(ctx, GDG_ERR_INVALID, "%s: pair %d has the target row %d of %d", what, q, target[q], n_rows);
+        return fail(ctx, GDG_ERR_INVALID, "%s: pair %d has the target port %d; ports start at 0", what, q, target[q]);
+    }
+}
+
+/* n_pairs (4096 / D + 1) 4: pure arithmetic; 0 for a list it cannot size */
+size_t gdg_transfer_doubles(int n_pairs, int group) { return gdg_transfer_list_doubles(n_pairs, group); }
+
+static int block_transfer_check(gdg_ctx *ctx, int n_rows, size_t samples, int n_pairs, const int *port, const int *target, int group, size_t *blocks) {
+    if (n_rows < 1) return fail(ctx, GDG_ERR_INVALID, "block transfer: %d rows (at least 1)", n_rows);
+    if (n_pairs < 1) return fail(ctx, GDG_ERR_INVALID, "block transfer: %d pairs; 1 to %d", n_pairs, GDG_TRANSFER_MAX_PAIRS);
+    const int rc = transfer_list_check(ctx, "block transfer", n_pairs, port, target, group, n_rows);
+    if (rc != GDG_OK) return rc;
+    *blocks = (samples + GDG_TRANSFER_BLOCK - 1) / GDG_TRANSFER_BLOCK;
+    if (*blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block transfer: %zu blocks per row are too many for one call", *blocks);
+    return GDG_OK;
+}
+
+/* the table goes up, the kernel runs, and the call returns when the records are written */
+int gdg_block_transfer_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_pairs, const int *port, const int *target,
+                                   int group, double *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    int rc = block_transfer_check(ctx, n_rows, samples, n_pairs, port, target, group, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (samples == 0) return GDG_OK;
+    if (!d_rows || !d_records) return GDG_ERR_INVALID;
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block transfer: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7)) return fail(ctx, GDG_ERR_INVALID, "block transfer: rows and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    double2 *tw = nullptr, *tw2 = nullptr;
+    if ((rc = fir_tables(ctx, GDG_TRANSFER_BLOCK, &tw, &tw2)) != GDG_OK) return rc;
+    const std::vector<int> table = gdg_transfer_table(n_pairs, port, target, group);
+    void *d = nullptr;
+    HIP_TRY(ctx, ctx->arena.alloc(&d, table.size() * sizeof(int)));
+    hipError_t e = hipMemcpyAsync(d, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, GDG_K_WAVE);
+        e = gdg_launch_block_transfer(d_rows, row_stride, (unsigned)n_rows, samples, table.data(), static_cast<const int *>(d), (unsigned)n_pairs, tw, d_records, ctx->stream);
+    }
+    const hipError_t w = hipStreamSynchronize(ctx->stream);
+    ctx->arena.release(d);
+    if (e != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block transfer: %s", hipGetErrorString(e));
+    if (w != hipSuccess) return fail(ctx, GDG_ERR_HIP, "block transfer: %s", hipGetErrorString(w));
+    return GDG_OK;
+}
+
+int gdg_block_transfer_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_pairs, const int *port, const int *target, int group,
+                            double *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    size_t blocks = 0;
+    const int rc = block_transfer_check(ctx, n_rows, samples, n_pairs, port, target, group, &blocks);
+    if (rc != GDG_OK) return rc;
+    if (samples == 0) return GDG_OK;
+    if (!rows || !records) return GDG_ERR_INVALID;
+    return rows_round_trip(ctx, "block transfer", rows, n_rows, samples, records, blocks * gdg_transfer_list_doubles(n_pairs, group) * sizeof(double), [&](const double *d_rows, void *d_out) {
+        return gdg_block_transfer_rows_device(ctx, d_rows, samples, n_rows, samples, n_pairs, port, target, group, static_cast<double *>(d_out));
+    });
+}
+
+/* the getter: the transfer records' own store, by the list records' rule and in their words; capacity in doubles */
+int gdg_batch_transfer(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const gdg_ctx::ListRecords &R = ctx->transfer_rec;
+    if (!R.valid)
+        return fail(ctx, GDG_ERR_INVALID, "no transfer records: the last batch call of this context %s", ctx->transfer.count()
+                    ? "has not completed, was a master finish, or none has run since gdg_batch_transfer_enable" : "ran without them (gdg_batch_transfer_enable comes before the call)");
+    if (blocks) *blocks = R.blocks;
+    if (doubles_per_block) *doubles_per_block = R.elem / sizeof(double);
+    if (!out) return GDG_OK;
+    const size_t n = R.store.size() / sizeof(double);
+    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "transfer: room for %zu doubles, the call has %zu blocks x %zu = %zu", capacity, R.blocks, R.elem / sizeof(double), n);
+    if (n) memcpy(out, R.store.data(), R.store.size());
+    return GDG_OK;
+}
+
+/* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
+int gdg_match_taps_from_transfer(const double *records, int n_pairs, int group, size_t blocks, double ridge, int n_taps, int center, double *tap, double *coherence) {
+    int bad = -1;
+    char msg[320];
+    switch (gdg_match_plan_taps(records, n_pairs, group, blocks, ridge, n_taps, center, tap, coherence, &bad)) {
+    case MATCH_PLAN_OK: return GDG_OK;
+    case MATCH_PLAN_NONFINITE: snprintf(msg, sizeof msg, "match taps from transfer: pair %d: the summed record has a NaN or inf entry", bad); break;
+    case MATCH_PLAN_SILENT: snprintf(msg, sizeof msg, "match taps from transfer: pair %d: the summed record has no energy in the port (every Sxx is 0): nothing to divide by", bad); break;
+    default:
+        snprintf(msg, sizeof msg, "match taps from transfer: %d pairs (0 to %d) of %zu blocks (at least 1), group = %d (1, 2, 4 .. %d), ridge = %g (finite, >= 0), n_taps = %d (1 to "
+                 "N' / 2 = 4096 / group), center = %d (0 to n_taps - 1); records, tap and coherence are needed", n_pairs, GDG_TRANSFER_MAX_PAIRS, blocks, group,
+                 GDG_TRANSFER_MAX_GROUP, ridge, n_taps, center);
+        break;
+    }
+    set_free_error(msg);
+    return GDG_ERR_INVALID;
+}
+
 /* ---- the true-peak record (include/gdg.h; the kernel: true_peak_kernels.h in io.hip; the taps: true_peak_taps.h; the batch calls fill it: api_batch.cpp) ---- */
 static_assert(sizeof(gdg_block_true_peak) == 16 && offsetof(gdg_block_true_peak, position) == 8 && offsetof(gdg_block_true_peak, overs) == 12,
               "gdg_block_true_peak: 16 bytes, no padding");

@@ -916,4 +916,164 @@ static inline int gdg_blend_plan_taps(const double *records, int n_fits, const i
     return TAPS_PLAN_OK;
 }
 
+/* ---- the transfer records (include/gdg.h, TRANSFER): a list of (port, target) pairs and one group width, the table a launch reads, and the
+ * match taps from its records (gdg_match_taps_from_transfer; tests/native/transfer_plan_check.cpp) ------------------------------------------- */
+#ifndef GDG_TRANSFER_MAX_PAIRS
+#define GDG_TRANSFER_BLOCK 8192
+#define GDG_TRANSFER_MAX_PAIRS 16
+#define GDG_TRANSFER_MAX_GROUP 64
+#endif
+/* include/gdg.h states the three for the callers, this file for the code that is compiled without it (fir.hip): they may not drift apart */
+static_assert(GDG_TRANSFER_BLOCK == 8192 && GDG_TRANSFER_MAX_PAIRS == 16 && GDG_TRANSFER_MAX_GROUP == 64, "the limits of include/gdg.h, TRANSFER");
+
+enum {
+    TRANSFER_OK = 0,
+    TRANSFER_COUNT = 1,                        /* n_pairs outside 0 .. GDG_TRANSFER_MAX_PAIRS */
+    TRANSFER_NULL = 2,                         /* a list is missing */
+    TRANSFER_GROUP = 3,                        /* the group width is not one of 1, 2, 4 .. GDG_TRANSFER_MAX_GROUP */
+    TRANSFER_PORT = 4,                         /* pair *pair names a port outside [0, n_ports) */
+    TRANSFER_TARGET = 5                        /* pair *pair names a target outside [0, n_ports) */
+};
+
+static inline bool gdg_transfer_group_ok(int group) { return group >= 1 && group <= GDG_TRANSFER_MAX_GROUP && !(group & (group - 1)); }
+
+/* the whole list; n_ports < 0: the port count is not known yet.  n_pairs == 0 is a list (off), whatever the group */
+static inline int gdg_transfer_check(int n_pairs, const int *port, const int *target, int group, int n_ports, int *pair) {
+    *pair = -1;
+    if (n_pairs < 0 || n_pairs > GDG_TRANSFER_MAX_PAIRS) return TRANSFER_COUNT;
+    if (n_pairs == 0) return TRANSFER_OK;
+    if (!port || !target) return TRANSFER_NULL;
+    if (!gdg_transfer_group_ok(group)) return TRANSFER_GROUP;
+    for (int i = 0; i < n_pairs; i++) {
+        *pair = i;
+        if (port[i] < 0 || (n_ports >= 0 && port[i] >= n_ports)) return TRANSFER_PORT;
+        if (target[i] < 0 || (n_ports >= 0 && target[i] >= n_ports)) return TRANSFER_TARGET;
+    }
+    *pair = -1;
+    return TRANSFER_OK;
+}
+
+/* G = 4096 / D + 1 groups of four doubles per pair; 0 for no pair or a width that is none */
+static inline size_t gdg_transfer_groups(int group) { return gdg_transfer_group_ok(group) ? (size_t)(GDG_TRANSFER_BLOCK / 2 / group + 1) : 0; }
+static inline size_t gdg_transfer_list_doubles(int n_pairs, int group) {
+    return n_pairs < 1 || n_pairs > GDG_TRANSFER_MAX_PAIRS ? 0 : (size_t)n_pairs * gdg_transfer_groups(group) * 4;
+}
+
+/* the table of a checked list, as a launch reads it: port, target per pair, the group width behind them; no pair: no int */
+static inline std::vector<int> gdg_transfer_table(int n_pairs, const int *port, const int *target, int group) {
+    std::vector<int> t;
+    for (int i = 0; i < n_pairs; i++) { t.push_back(port[i]); t.push_back(target[i]); }
+    if (n_pairs > 0) t.push_back(group);
+    return t;
+}
+
+/* the list in force (ctx.h): its table, empty = off */
+struct TransferSet {
+    std::vector<int> table;
+    int count() const { return table.empty() ? 0 : (int)(table.size() / 2); }
+    int group() const { return table.empty() ? 0 : table.back(); }
+    int port(int i) const { return table[(size_t)2 * i]; }
+    int target(int i) const { return table[(size_t)2 * i + 1]; }
+    size_t doubles() const { return gdg_transfer_list_doubles(count(), group()); }
+    /* the first pair that names a port at or beyond n_ports; *side: 0 = its port, 1 = its target; -1: none */
+    int first_outside(int n_ports, int *side) const {
+        for (int i = 0; i < count(); i++) {
+            if (port(i) >= n_ports) { *side = 0; return i; }
+            if (target(i) >= n_ports) { *side = 1; return i; }
+        }
+        return -1;
+    }
+};
+
+/* The inverse real transform of the planner: h[n] = (1 / M) sum_k F[k] exp(+2 pi i k n / M), M = 2 Gm a power of two (128 .. 8192), F the
+ * Hermitian extension of H[0 .. Gm] (F[M - k] = conj H[k]; the imaginary parts of H[0] and H[Gm] are not looked at).  The algorithm is
+ * the textbook iterative radix-2 decimation-in-time complex transform of length M -- bit-reversed input, log2 M butterfly passes, every
+ * twiddle taken from one table of cos and sin evaluated per entry (no recurrence) -- on F; the real parts are the result. */
+static inline void gdg_transfer_irfft(const double *Hre, const double *Him, int Gm, double *h) {
+    const int M = 2 * Gm;
+    const double pi = 3.14159265358979323846;
+    std::vector<double> re((size_t)M), im((size_t)M), wr((size_t)Gm), wi((size_t)Gm);
+    for (int k = 0; k < Gm; k++) { wr[(size_t)k] = cos(2.0 * pi * (double)k / (double)M); wi[(size_t)k] = sin(2.0 * pi * (double)k / (double)M); }
+    int bits = 0;
+    while ((1 << bits) < M) bits++;
+    for (int k = 0; k < M; k++) {
+        int r = 0;
+        for (int b = 0; b < bits; b++) if (k & (1 << b)) r |= 1 << (bits - 1 - b);
+        double a, c;
+        if (k == 0 || k == Gm) { a = Hre[k]; c = 0.0; }
+        else if (k < Gm) { a = Hre[k]; c = Him[k]; }
+        else { a = Hre[M - k]; c = -Him[M - k]; }
+        re[(size_t)r] = a;
+        im[(size_t)r] = c;
+    }
+    for (int len = 2; len <= M; len <<= 1) {
+        const int half = len / 2, step = M / len;
+        for (int s = 0; s < M; s += len)
+            for (int j = 0; j < half; j++) {
+                const double cr = wr[(size_t)(j * step)], ci = wi[(size_t)(j * step)];
+                const size_t u = (size_t)(s + j), v = u + (size_t)half;
+                const double tr = re[v] * cr - im[v] * ci, ti = re[v] * ci + im[v] * cr;
+                re[v] = re[u] - tr; im[v] = im[u] - ti;
+                re[u] = re[u] + tr; im[u] = im[u] + ti;
+            }
+    }
+    for (int n = 0; n < M; n++) h[n] = re[(size_t)n] / (double)M;
+}
+
+enum {
+    MATCH_PLAN_OK = 0,
+    MATCH_PLAN_ARGS = 1,                       /* a list is missing, a count, the group, n_taps or center is out of range, no block, ridge is negative or not finite */
+    MATCH_PLAN_NONFINITE = 2,                  /* the summed record of *pair has a NaN or inf entry */
+    MATCH_PLAN_SILENT = 3                      /* the summed record of *pair has no energy in the port: every Sxx[g] is 0 */
+};
+
+/* records[blocks][n_pairs][G][4] (Sxx, Syy, Re Sxy, Im Sxy).  Per pair: the blocks' records added in block order with plain adds; N' = 2 Gm;
+ * H[g] = Sxy[g] / (Sxx[g] + ridge * mean_g Sxx), 0 where that denominator is 0; h = gdg_transfer_irfft(H); tap[m] = t[m] h[(m - center) mod
+ * N'] with the raised-cosine taper t (1 at the centre, E = center + 1 in front, n_taps - center behind: never 0 inside); coherence =
+ * sum_g (|Sxy[g]|^2 / Sxx[g]) / sum_g Syy[g] over the groups with Sxx[g] > 0, 0 when sum Syy is 0.  Every pair is planned before
+ * tap[n_pairs][n_taps] and coherence[n_pairs] are written; *pair: the offender. */
+static inline int gdg_match_plan_taps(const double *records, int n_pairs, int group, size_t blocks, double ridge, int n_taps, int center, double *tap, double *coherence,
+                                      int *pair) {
+    *pair = -1;
+    if (n_pairs < 0 || n_pairs > GDG_TRANSFER_MAX_PAIRS || !(ridge >= 0.0) || !isfinite(ridge) || !gdg_transfer_group_ok(group)) return MATCH_PLAN_ARGS;
+    const int Gm = GDG_TRANSFER_BLOCK / 2 / group, G = Gm + 1, M = 2 * Gm;
+    if (n_taps < 1 || n_taps > M / 2 || center < 0 || center >= n_taps) return MATCH_PLAN_ARGS;
+    if (n_pairs == 0) return MATCH_PLAN_OK;
+    if (!records || !tap || !coherence || blocks == 0) return MATCH_PLAN_ARGS;
+    const double pi = 3.14159265358979323846;
+    const size_t per = (size_t)n_pairs * (size_t)G * 4;
+    std::vector<double> tap_all((size_t)n_pairs * (size_t)n_taps, 0.0), coh_all((size_t)n_pairs, 0.0), sum((size_t)G * 4), Hre((size_t)G), Him((size_t)G), h((size_t)M);
+    for (int p = 0; p < n_pairs; p++) {
+        *pair = p;
+        sum.assign((size_t)G * 4, 0.0);
+        for (size_t q = 0; q < blocks; q++) for (size_t e = 0; e < (size_t)G * 4; e++) sum[e] += records[q * per + (size_t)p * (size_t)G * 4 + e];
+        double total = 0.0, syy = 0.0, explained = 0.0;
+        for (int g = 0; g < G; g++) {
+            for (int c = 0; c < 4; c++) if (!isfinite(sum[(size_t)g * 4 + c])) return MATCH_PLAN_NONFINITE;
+            total += sum[(size_t)g * 4];
+        }
+        if (!(total > 0.0)) return MATCH_PLAN_SILENT;
+        const double load = ridge * (total / (double)G);
+        for (int g = 0; g < G; g++) {
+            const double sxx = sum[(size_t)g * 4], re = sum[(size_t)g * 4 + 2], im = sum[(size_t)g * 4 + 3], den = sxx + load;
+            Hre[(size_t)g] = den != 0.0 ? re / den : 0.0;
+            Him[(size_t)g] = den != 0.0 ? im / den : 0.0;
+            syy += sum[(size_t)g * 4 + 1];
+            if (sxx > 0.0) explained += (re * re + im * im) / sxx;
+        }
+        gdg_transfer_irfft(Hre.data(), Him.data(), Gm, h.data());
+        for (int m = 0; m < n_taps; m++) {
+            const int d = m - center;
+            const double E = d < 0 ? (double)(center + 1) : (double)(n_taps - center);
+            const double t = 0.5 + 0.5 * cos(pi * (double)d / E);
+            tap_all[(size_t)p * (size_t)n_taps + (size_t)m] = t * h[(size_t)((d + M) % M)];
+        }
+        coh_all[(size_t)p] = syy > 0.0 ? explained / syy : 0.0;
+    }
+    *pair = -1;
+    memcpy(tap, tap_all.data(), tap_all.size() * sizeof(double));
+    memcpy(coherence, coh_all.data(), coh_all.size() * sizeof(double));
+    return MATCH_PLAN_OK;
+}
+
 #endif

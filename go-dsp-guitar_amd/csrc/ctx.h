@@ -352,8 +352,8 @@ struct gdg_ctx {
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
     /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
      * grown when a slice needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
-    void *batch_dev[10] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t batch_dev_cap[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    void *batch_dev[11] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    size_t batch_dev_cap[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
     /* a batch job, how far it has come, and per input the source frames handed over: the context's is the streamed run's
      * (gdg_batch_stream_open .. _close); a one-call run describes its own and leaves this one closed */
@@ -428,6 +428,11 @@ struct gdg_ctx {
         size_t rows = 0, elem = 0, blocks = 0;
         std::vector<unsigned char> store;
     } list_rec[LIST_KINDS];
+    /* the transfer list (gdg_batch_transfer_enable; blend.h, TransferSet) and its records of the last completed batch call, [blocks] records of
+     * n_pairs (4096 / D + 1) 4 doubles: a list record by every rule above, in a store of its own behind the three kinds' -- its section rides
+     * behind theirs (report_sections.h, transfer_section) and its table lies in batch_dev[BATCH_TRANSFER_TABLE].  Configuration: in no blob. */
+    TransferSet transfer;
+    ListRecords transfer_rec;
     /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;
@@ -724,6 +729,8 @@ int fit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first,
 int gram_list_check(gdg_ctx *ctx, const char *what, const int *port, int n_ports, int least, int n_rows);
 /* api_io.cpp: a list of tap fits against gdg_tapfit_check (blend.h), refused in the words of `what`; n_rows < 0: the port count is not known yet */
 int tapfit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, const int *taps, int n_rows);
+/* api_io.cpp: a transfer list against gdg_transfer_check (blend.h), refused in the words of `what`; n_rows < 0: the port count is not known yet */
+int transfer_list_check(gdg_ctx *ctx, const char *what, int n_pairs, const int *port, const int *target, int group, int n_rows);
 /* the map in force has a reader: what a checkpoint cannot record yet */
 static inline bool batch_sources_shared(const gdg_ctx *ctx) { return sources_have_reader(ctx->batch_source); }
 /* a batch call begins: every kind's records of the call before are gone; a kind that is switched on gets zeroed records for `ports` x
@@ -732,6 +739,7 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
     ctx->spec_live_edges = ctx->spec_edges;
     ctx->align_live_ref.clear();
     for (gdg_ctx::ListRecords &R : ctx->list_rec) R.valid = R.live = false;      /* a call that collects list records says so itself (list_begin) */
+    ctx->transfer_rec.valid = ctx->transfer_rec.live = false;                    /* ... and transfer records (transfer_begin) */
     /* any other count was refused when the job was described; a list without the call's blend ports: each of them references itself */
     if (align && ((int)ctx->align_ref.size() == ports || (blend_ports > 0 && (int)ctx->align_ref.size() == ports - blend_ports))) {
         ctx->align_live_ref = ctx->align_ref;
@@ -779,8 +787,30 @@ static inline void list_file(gdg_ctx *ctx, int k, const unsigned char *section, 
     gdg_ctx::ListRecords &R = ctx->list_rec[k];
     list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
 }
+/* the transfer list in force: its table, its pairs and what it sends down per block -- one row of the list's doubles */
+static inline ListInForce transfer_in_force(const gdg_ctx *ctx) {
+    return { ctx->transfer.table.data(), ctx->transfer.table.size(), ctx->transfer.count(), { 1, ctx->transfer.doubles() * sizeof(double) } };
+}
+/* list_begin and list_file for the transfer records' own store */
+static inline void transfer_begin(gdg_ctx *ctx, size_t blocks) {
+    const ListInForce L = transfer_in_force(ctx);
+    gdg_ctx::ListRecords &R = ctx->transfer_rec;
+    R.live = L.shape.on();
+    if (!R.live) return;
+    R.count = L.count;
+    R.rows = L.shape.rows;
+    R.elem = L.shape.elem;
+    R.blocks = blocks;
+    R.store.assign(R.rows * blocks * R.elem, 0);
+}
+static inline void transfer_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
+    gdg_ctx::ListRecords &R = ctx->transfer_rec;
+    list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
+}
 /* ... and has completed (rc == GDG_OK) or not */
 static inline int report_end(gdg_ctx *ctx, int rc) {
+    ctx->transfer_rec.valid = ctx->transfer_rec.live && rc == GDG_OK;
+    ctx->transfer_rec.live = false;
     for (gdg_ctx::ListRecords &R : ctx->list_rec) {
         R.valid = R.live && rc == GDG_OK;
         R.live = false;
@@ -817,9 +847,11 @@ enum {
     BATCH_FIT_TABLE,                       /* [fits][target | terms | port[8]] the blend fits' table, only while fits are in force (gdg_batch_fit_enable) */
     BATCH_GRAM_PORTS,                      /* [P] the Gram list's ports, only while a list is in force (gdg_batch_gram_enable) */
     BATCH_TAPFIT_TABLE,                    /* [fits][target | terms | taps | port[4] | offset | tile] the tap fits' table, only while tap fits are in force (gdg_batch_tapfit_enable) */
+    BATCH_TRANSFER_TABLE,                  /* [pairs][port | target], then the group width: the transfer list's table, only while one is in force (gdg_batch_transfer_enable) */
     BATCH_DEV_SLOTS
 };
-static_assert(BATCH_DEV_SLOTS == 10, "gdg_ctx::batch_dev has one entry per slot");
+static_assert(sizeof(gdg_ctx::batch_dev) / sizeof(void *) == BATCH_DEV_SLOTS && sizeof(gdg_ctx::batch_dev_cap) / sizeof(size_t) == BATCH_DEV_SLOTS,
+              "gdg_ctx::batch_dev and batch_dev_cap have one entry per slot");
 static_assert(BATCH_GRAM_PORTS == BATCH_FIT_TABLE + LIST_GRAM && BATCH_TAPFIT_TABLE == BATCH_FIT_TABLE + LIST_TAPFIT, "BATCH_FIT_TABLE + k is list kind k's slot");
 int ensure_tuner(gdg_ctx *ctx);
 

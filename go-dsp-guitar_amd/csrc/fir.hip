@@ -1864,6 +1864,7 @@ hipError_t gdg_launch_fir_ahead(int P, const gdg_ahead_steps &steps, gdg_ahead a
 
 #include "spectrum_kernels.h"        /* the band spectrum of the render report: still without contraction */
 #include "align_kernels.h"           /* ... and its alignment records: the same passes, forward and inverse */
+#include "transfer_kernels.h"        /* ... and the transfer records: the alignment's shared transform, kept as spectra */
 
 #pragma clang fp contract(fast)     /* the tuner has no second path to agree with bit for bit */
 #include "tuner_kernels.h"

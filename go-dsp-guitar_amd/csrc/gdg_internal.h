@@ -369,6 +369,12 @@ hipError_t gdg_launch_block_gram(const double *d_rows, size_t row_stride, unsign
  * the device's d_table (blend.h, gdg_tapfit_table), held against the limits and n_rows before anything is launched. */
 hipError_t gdg_launch_block_tapfit(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, unsigned block, const int *h_table, const int *d_table,
                                    unsigned n_fits, void *d_records, hipStream_t s);
+/* the transfer records (include/gdg.h, TRANSFER; fir.hip, transfer_kernels.h): per block of 8192 samples (the last of a row may be short:
+ * zero-padded) and (port, target) pair the auto-spectra and the cross-spectrum in groups of D bins, d_records[ceil(samples / 8192)][n_pairs]
+ * [4096 / D + 1][4].  h_table is the host's copy of the device's d_table (blend.h, gdg_transfer_table: port, target per pair, then D), held
+ * against the limits (blend.h, GDG_TRANSFER_*) and n_rows before anything is launched; tw8192: the 8192-point table */
+hipError_t gdg_launch_block_transfer(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, const int *h_table, const int *d_table,
+                                     unsigned n_pairs, const double2 *tw8192, void *d_records, hipStream_t s);
 
 /* compile.hip: power-amp filter compilation */
 hipError_t gdg_launch_filter_reduce(const double *d_taps, int n, unsigned order, double2 *work_a, double2 *work_b, double2 *work_pos, double *d_out,

@@ -3166,3 +3166,185 @@ func BlendTapsFromTapFit(records [][]float64, fits []TapFit, ridge float64) ([][
 	}
 	return out, residual, nil
 }
+
+// TransferPair: one (port, target) pair of a transfer list: the port whose spectrum is measured and the target it is measured against.
+type TransferPair struct {
+	Port   int
+	Target int
+}
+
+// transferLists: the pairs as the two C int lists of the transfer calls (one spare entry behind each), and what frees them.
+func transferLists(pairs []TransferPair) (port *[1 << 28]C.int, target *[1 << 28]C.int, release func()) {
+	port = (*[1 << 28]C.int)(C.calloc(C.size_t(len(pairs)+1), 4))
+	target = (*[1 << 28]C.int)(C.calloc(C.size_t(len(pairs)+1), 4))
+	release = func() {
+		C.free(unsafe.Pointer(port))
+		C.free(unsafe.Pointer(target))
+	}
+	if port == nil || target == nil {
+		release()
+		return nil, nil, func() {}
+	}
+	for i, p := range pairs {
+		port[i] = C.int(p.Port)
+		target[i] = C.int(p.Target)
+	}
+	return port, target, release
+}
+
+// TransferDoubles: the doubles of one block's transfer record (gdg_transfer_doubles): nPairs * (4096/group + 1) * 4; 0 for no pair or a
+// group width that is none of 1, 2, 4 .. 64.
+func TransferDoubles(nPairs int, group int) int {
+	return int(C.gdg_transfer_doubles(C.int(nPairs), C.int(group)))
+}
+
+// BatchTransferEnable: from the next batch call on, every batch call of the context keeps the transfer records of what it rendered
+// (gdg_batch_transfer_enable): per block and pair the auto-spectra and the cross-spectrum in groups of `group` bins.  nil or an empty
+// slice switches it off.  Configuration, like BatchTapFitEnable: a checkpoint does not carry it, and it is refused while a streamed job is open.
+func (this *Context) BatchTransferEnable(pairs []TransferPair, group int) error {
+	if len(pairs) == 0 {
+		return this.err(C.gdg_batch_transfer_enable(this.ctx, 0, nil, nil, C.int(group)))
+	}
+	port, target, release := transferLists(pairs)
+	if port == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_batch_transfer_enable(this.ctx, C.int(len(pairs)), &port[0], &target[0], C.int(group)))
+}
+
+// BatchTransfers: the number of transfer pairs in force (gdg_batch_transfers).
+func (this *Context) BatchTransfers() int {
+	return int(C.gdg_batch_transfers(this.ctx))
+}
+
+// BatchTransfer: the transfer records of the last completed batch call, result[block][nPairs*G*4] (gdg_batch_transfer).  An error when the
+// call ran without them, or was a master finish.
+func (this *Context) BatchTransfer() ([][]float64, error) {
+	var blocks C.size_t
+	var per C.size_t
+	if e := this.err(C.gdg_batch_transfer(this.ctx, nil, 0, &blocks, &per)); e != nil {
+		return nil, e
+	}
+	n := int(blocks) * int(per)
+	if n == 0 {
+		return goGram(nil, int(blocks), int(per)), nil
+	}
+	rec := (*[1 << 28]C.double)(C.calloc(C.size_t(n), 8))
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	if e := this.err(C.gdg_batch_transfer(this.ctx, &rec[0], C.size_t(n), &blocks, &per)); e != nil {
+		return nil, e
+	}
+	return goGram(unsafe.Pointer(rec), int(blocks), int(per)), nil
+}
+
+// BlockTransferRows: the transfer records of equally long host rows per block of 8192 samples, the last one of a row possibly short
+// (gdg_block_transfer_rows); a pair's ports name rows; result[block][nPairs*G*4].
+func (this *Context) BlockTransferRows(rows [][]float64, pairs []TransferPair, group int) ([][]float64, error) {
+	n := len(rows)
+	if n == 0 || len(pairs) == 0 {
+		return nil, fmt.Errorf("gdg: %d rows, %d pairs", n, len(pairs))
+	}
+	samples := len(rows[0])
+	blocks := (samples + 8191) / 8192
+	per := TransferDoubles(len(pairs), group)
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	port, target, release := transferLists(pairs)
+	if port == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	out := C.calloc(C.size_t(blocks*per+1), 8)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_transfer_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), C.int(len(pairs)), &port[0], &target[0], C.int(group), (*C.double)(out))); e != nil {
+		return nil, e
+	}
+	return goGram(out, blocks, per), nil
+}
+
+// BlockTransferRowsDevice: the same on device memory (gdg_block_transfer_rows_device): row r at dRows + r*rowStride float64 (any 8-byte
+// alignment, rowStride >= samples), the records into dRecords[ceil(samples/8192)][nPairs*G*4]; returns when they are written.
+func (this *Context) BlockTransferRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, pairs []TransferPair, group int, dRecords unsafe.Pointer) error {
+	port, target, release := transferLists(pairs)
+	if port == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer release()
+	return this.err(C.gdg_block_transfer_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(len(pairs)), &port[0], &target[0], C.int(group),
+		(*C.double)(dRecords)))
+}
+
+// MatchTapsFromTransfer: the match taps of every pair from its records (gdg_match_taps_from_transfer): records[block] as BatchTransfer hands
+// them out; H = Sxy / (Sxx + ridge*mean Sxx) over the summed blocks, its inverse real transform of length 8192/group, nTaps of it around
+// `center` under a raised-cosine taper.  taps[pair] has nTaps entries -- an impulse response like any other; coherence[pair] is the share of
+// the target's energy a linear filter on the port explains.  Host arithmetic: no context and no device.  An error, with the pair named,
+// for a NaN or inf entry and for a pair with no energy in its port.
+func MatchTapsFromTransfer(records [][]float64, nPairs int, group int, ridge float64, nTaps int, center int) ([][]float64, []float64, error) {
+	blocks := len(records)
+	per := TransferDoubles(nPairs, group)
+	if blocks == 0 || per == 0 || nTaps < 1 {
+		return nil, nil, fmt.Errorf("gdg: %d blocks (at least 1), %d pairs in groups of %d, %d taps", blocks, nPairs, group, nTaps)
+	}
+	for b, row := range records {
+		if len(row) != per {
+			return nil, nil, fmt.Errorf("gdg: record %d has %d entries, the pairs make %d", b, len(row), per)
+		}
+	}
+	rec := (*[1 << 28]C.double)(C.calloc(C.size_t(blocks*per+1), 8))
+	if rec == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	for b, row := range records {
+		for e, v := range row {
+			rec[b*per+e] = C.double(v)
+		}
+	}
+	total := nPairs * nTaps
+	res := (*[1 << 28]C.double)(C.calloc(C.size_t(total+nPairs+1), 8))
+	if res == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(res))
+	if rc := C.gdg_match_taps_from_transfer(&rec[0], C.int(nPairs), C.int(group), C.size_t(blocks), C.double(ridge), C.int(nTaps), C.int(center), &res[0], &res[total]); rc != 0 {
+		return nil, nil, fmt.Errorf("gdg: gdg_match_taps_from_transfer: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	taps := make([][]float64, nPairs)
+	coherence := make([]float64, nPairs)
+	for p := range taps {
+		taps[p] = make([]float64, nTaps)
+		for m := range taps[p] {
+			taps[p][m] = float64(res[p*nTaps+m])
+		}
+		coherence[p] = float64(res[total+p])
+	}
+	return taps, coherence, nil
+}

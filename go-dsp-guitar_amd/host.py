@@ -59,6 +59,9 @@ def lib():
             "gdgh_engine_last_batch_gram": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_tapfits": (cs, [vp, i32, vp, vp, vp, vp]),
             "gdgh_engine_batch_tapfits": (i32, [vp]),
+            "gdgh_engine_set_batch_transfers": (cs, [vp, i32, vp, vp, i32]),
+            "gdgh_engine_batch_transfers": (i32, [vp]),
+            "gdgh_engine_last_batch_transfer": (cs, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
             "gdgh_engine_last_batch_tapfit": (cs, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_set_batch_blends_filtered": (cs, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
@@ -142,6 +145,7 @@ class Engine:
         self.last_true_peak = None       # the true-peak records of the last batch call made with true_peak=True: [N + 3, blocks] records
         self.last_fit = None             # the fit records of the last batch call made with fits=: [fits, blocks] records (FIT_DTYPE)
         self.last_gram = None            # the Gram records of the last batch call made with gram=: [blocks, P (P + 1) / 2] float64
+        self.last_transfer = None        # the transfer records of the last batch call made with transfers=: [blocks, pairs x G x 4] float64
         self.last_tapfit = None          # the tap-fit records of the last batch call made with tapfits=: [blocks, D] float64
         self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
@@ -400,6 +404,54 @@ class Engine:
         _err(lib().gdgh_engine_last_batch_tapfit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
         return out
 
+    def _set_transfers(self, transfers):
+        """Engine::SetBatchTransfers, from the `transfers` argument of the batch calls: ([(port, target), ...], group), or a list of pairs
+        alone (group 1); None or an empty list: off.  Returns the number of pairs in force.  Refused on an engine of more than one shard."""
+        self.last_transfer = None
+        pairs, group = [], 1
+        if transfers:
+            if len(transfers) == 2 and np.isscalar(transfers[1]) and not np.isscalar(transfers[0]):
+                pairs, group = list(transfers[0]), int(transfers[1])
+            else:
+                pairs = list(transfers)
+        if not pairs:
+            _err(lib().gdgh_engine_set_batch_transfers(self._h, 0, None, None, 1))
+            return 0
+        port = np.array([int(p) for p, _ in pairs] + [0], dtype=np.int32)
+        target = np.array([int(t) for _, t in pairs] + [0], dtype=np.int32)
+        _err(lib().gdgh_engine_set_batch_transfers(self._h, len(pairs), port.ctypes.data, target.ctypes.data, group))
+        return int(lib().gdgh_engine_batch_transfers(self._h))
+
+    def _fetch_transfer(self):
+        """Engine::LastBatchTransfer -> [blocks, pairs x G x 4] float64"""
+        blocks, per = C.c_size_t(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_transfer(self._h, None, 0, C.byref(blocks), C.byref(per)))
+        out = np.zeros((blocks.value, per.value), dtype=np.float64)
+        _err(lib().gdgh_engine_last_batch_transfer(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
+        return out
+
+    def match_ir(self, port, target, taps, inputs, target_rate, out_format, group=32, ridge=0.0, center=0, window=16, sample_rate=None, **kw):
+        """The match filter of one pass over a job: the `taps`-tap impulse response that, applied to port `port`, comes closest to port
+        `target` over the whole band.  save_state; one pass with every output skipped and the one transfer pair (port, target) at group
+        width `group` on; the planner (match_taps_from_transfer, with `ridge` and `center`) turns the summed records into taps; load_state:
+        the engine is left as it was found.  Returns (taps [taps] float64, coherence): the taps go into ImpulseResponses.add or
+        unit_set_fir like any impulse response; a response centred at `center` lags by that many samples.  Pass 1's records stay in
+        match_records.  kw: batch_run's other arguments (transfers and skip_outputs in kw are replaced)."""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        rate = target_rate if sample_rate is None else sample_rate
+        _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
+        blob = self.save_state()
+        rest = {k: v for k, v in kw.items() if k not in ("transfers", "skip_outputs")}
+        try:
+            self.batch_run(inputs, target_rate, out_format, window=window, transfers=([(int(port), int(target))], int(group)), skip_outputs=True, **rest)
+            self.match_records = self.last_transfer
+            h, coherence = pkg.match_taps_from_transfer(self.match_records, 1, int(group), int(taps), int(center), float(ridge))
+        finally:
+            self.load_state(blob, rate)
+            self._set_transfers(None)
+        return h[0], float(coherence[0])
+
     def render_tap_fitted(self, target, terms, taps, inputs, target_rate, out_format, ridge=0.0, delays=None, signs=None, center=None, window=16, sample_rate=None, **kw):
         """Two passes over one job: the `taps`-tap filters on the chain outputs `terms` (job channels, 1 to 4, terms x taps <= 128) whose sum
         comes closest to port `target` in the least-squares sense.  save_state; pass 1 renders with every output skipped and one tap fit
@@ -648,7 +700,7 @@ class Engine:
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
@@ -659,7 +711,8 @@ class Engine:
         list, behind the metronome's (one-shard engines only; None: off).  fits: a list of (target port, [term ports]) -- keep the fit
         records in last_fit ([fits, blocks], FIT_DTYPE; one-shard engines only; None: off).  gram: a list of 2 to 512 different ports -- keep the
         Gram records in last_gram ([blocks, P (P + 1) / 2] float64; one-shard engines only; None: off).  tapfits: a list of (target port,
-        [term ports], taps) -- keep the tap-fit records in last_tapfit ([blocks, D] float64; one-shard engines only; None: off)."""
+        [term ports], taps) -- keep the tap-fit records in last_tapfit ([blocks, D] float64; one-shard engines only; None: off).  transfers:
+        ([(port, target), ...], group) -- keep the transfer records in last_transfer ([blocks, pairs x G x 4] float64; one-shard engines only; None: off)."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
@@ -669,6 +722,7 @@ class Engine:
         fitted = self._set_fits(fits)
         grammed = self._set_gram(gram)
         tapped = self._set_tapfits(tapfits)
+        transferred = self._set_transfers(transfers)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -715,10 +769,12 @@ class Engine:
             self.last_gram = self._fetch_gram()
         if tapped:
             self.last_tapfit = self._fetch_tapfit()
+        if transferred:
+            self.last_transfer = self._fetch_transfer()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces (and one per blend of blends= / blend_gain=, as batch_run's).  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]; fits=: last_fit likewise,
@@ -727,7 +783,7 @@ class Engine:
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
                                   metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
-                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits)
+                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits, transfers=transfers)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -752,7 +808,7 @@ class Engine:
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
@@ -763,6 +819,7 @@ class Engine:
         fitted = self._set_fits(fits)                        # ... and no fits
         grammed = self._set_gram(gram)                       # ... and no Gram list
         tapped = self._set_tapfits(tapfits)                  # ... and no tap fits
+        transferred = self._set_transfers(transfers)         # ... and no transfer list
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -823,6 +880,9 @@ class Engine:
                 if tapped:
                     tf = self._fetch_tapfit()
                     self.last_tapfit = tf if self.last_tapfit is None else np.concatenate([self.last_tapfit, tf], axis=0)
+                if transferred:
+                    tr = self._fetch_transfer()
+                    self.last_transfer = tr if self.last_transfer is None else np.concatenate([self.last_transfer, tr], axis=0)
                 yield outs
                 left -= blocks
         finally:

@@ -1126,6 +1126,39 @@ int Engine::applyTapFits(gdg_ctx *ctx) {
     return gdg_batch_tapfit_enable(ctx, BatchTapFits(), tapFitFirst_.data(), tapFitPort_.data(), tapFitTarget_.data(), tapFitTaps_.data());
 }
 
+/* Engine::SetBatchTransfers: validated whole before the list replaces the one in force (the library checks again, and the ports against the job's) */
+Error Engine::SetBatchTransfers(const std::vector<TransferPair> &pairs, int group) {
+    if (pairs.empty()) { transferPort_.clear(); transferTarget_.clear(); return ""; }
+    if (shards() > 1)
+        return format("SetBatchTransfers: the engine has %d shards: a pair's ports are rows of one device's window, and the library's shard calls refuse a transfer list; it "
+                      "needs a one-shard engine", shards());
+    if (pairs.size() > GDG_TRANSFER_MAX_PAIRS) return format("SetBatchTransfers: %zu pairs; 0 (off) to %d", pairs.size(), GDG_TRANSFER_MAX_PAIRS);
+    if (group < 1 || group > GDG_TRANSFER_MAX_GROUP || (group & (group - 1))) return format("SetBatchTransfers: a group width of %d bins; 1, 2, 4, 8, 16, 32 or %d", group, GDG_TRANSFER_MAX_GROUP);
+    std::vector<int> port, target;
+    for (size_t i = 0; i < pairs.size(); i++) {
+        if (pairs[i].port < 0) return format("SetBatchTransfers: pair %zu names port %d; ports start at 0", i, pairs[i].port);
+        if (pairs[i].target < 0) return format("SetBatchTransfers: pair %zu has the target port %d; ports start at 0", i, pairs[i].target);
+        port.push_back(pairs[i].port);
+        target.push_back(pairs[i].target);
+    }
+    transferPort_.swap(port); transferTarget_.swap(target);
+    transferGroup_ = group;
+    return "";
+}
+
+int Engine::applyTransfers(gdg_ctx *ctx) {
+    if (transferPort_.empty()) return gdg_batch_transfer_enable(ctx, 0, nullptr, nullptr, 1);
+    return gdg_batch_transfer_enable(ctx, BatchTransfers(), transferPort_.data(), transferTarget_.data(), transferGroup_);
+}
+
+Error Engine::LastBatchTransfer(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const {
+    if (!transferValid_) return "LastBatchTransfer: the last batch call kept no transfer records (SetBatchTransfers comes before the call)";
+    records = lastTransfer_;
+    if (blocks) *blocks = transferBlocks_;
+    if (doublesPerBlock) *doublesPerBlock = transferDoubles_;
+    return "";
+}
+
 Error Engine::LastBatchTapFit(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const {
     if (!tapFitValid_) return "LastBatchTapFit: the last batch call kept no tap-fit records (SetBatchTapFits comes before the call)";
     records = lastTapFit_;
@@ -1159,7 +1192,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1179,7 +1212,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { tapFitValid_ = BatchTapFits() > 0; tapFitBlocks_ = 0; tapFitDoubles_ = tapFitValid_ ? gdg_tapfit_doubles(BatchTapFits(), tapFitFirst_.data(), tapFitTaps_.data()) : 0; lastTapFit_.clear(); gramValid_ = BatchGramPorts() > 0; gramBlocks_ = 0; gramPorts_ = BatchGramPorts(); lastGram_.clear(); fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
+    if (job == 0) { transferValid_ = BatchTransfers() > 0; transferBlocks_ = 0; transferDoubles_ = gdg_transfer_doubles(BatchTransfers(), transferGroup_); lastTransfer_.clear(); tapFitValid_ = BatchTapFits() > 0; tapFitBlocks_ = 0; tapFitDoubles_ = tapFitValid_ ? gdg_tapfit_doubles(BatchTapFits(), tapFitFirst_.data(), tapFitTaps_.data()) : 0; lastTapFit_.clear(); gramValid_ = BatchGramPorts() > 0; gramBlocks_ = 0; gramPorts_ = BatchGramPorts(); lastGram_.clear(); fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
     /* blends or fits in force (one shard: SetBatchBlends, SetBatchFits): the library's plain one-call run -- its shard calls refuse both --
      * with `outs` of N + 3 + B entries; the alignment list goes on in its plain form, and the context's records of every kind are the engine's */
     if (plainRun()) {
@@ -1237,7 +1270,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
  * [N + 3][blocks] in gdg_batch_run's port order and from three sources -- the shards' chain rows, shard 0's metronome row, the finish's two
  * master rows (which carry no alignment records: over shards those rows stay zero) ---- */
 void Engine::reportBegin(size_t blocks) {
-    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = tapFitValid_ = false;
+    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = tapFitValid_ = transferValid_ = false;
     reportBlocks_ = blocks;
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
     const size_t n = (size_t)ports() * blocks;
@@ -1439,7 +1472,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1495,6 +1528,17 @@ Error Engine::recordsOfContext(gdg_ctx *ctx) {
             gramPorts_ = BatchGramPorts();
             if (!lastGram_.empty() && gdg_batch_gram(ctx, lastGram_.data(), lastGram_.size(), &blocks) != GDG_OK) re = gdg_last_error(ctx);
             else gramValid_ = true;
+        }
+    }
+    if (re.empty() && BatchTransfers() > 0) {              /* the transfer records: [blocks][doubles] */
+        size_t blocks = 0, per = 0;
+        if (gdg_batch_transfer(ctx, nullptr, 0, &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
+        else {
+            lastTransfer_.assign(blocks * per, 0.0);
+            transferBlocks_ = blocks;
+            transferDoubles_ = per;
+            if (!lastTransfer_.empty() && gdg_batch_transfer(ctx, lastTransfer_.data(), lastTransfer_.size(), &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
+            else transferValid_ = true;
         }
     }
     if (re.empty() && BatchTapFits() > 0) {                /* the tap-fit records: [blocks][D] */
@@ -2131,6 +2175,29 @@ const char *gdgh_engine_set_batch_tapfits(void *e, int n_fits, const int *first,
     return ret(((Engine *)e)->SetBatchTapFits(fits));
 }
 int gdgh_engine_batch_tapfits(void *e) { return ((Engine *)e)->BatchTapFits(); }
+/* n_pairs == 0: off */
+const char *gdgh_engine_set_batch_transfers(void *e, int n_pairs, const int *port, const int *target, int group) {
+    if (!e) return ret(Error("no engine"));
+    if (n_pairs < 0 || (n_pairs > 0 && (!port || !target))) return ret(Error("SetBatchTransfers: n_pairs >= 0, and the two lists"));
+    std::vector<Engine::TransferPair> pairs;
+    for (int i = 0; i < n_pairs; i++) pairs.push_back({ port[i], target[i] });
+    return ret(((Engine *)e)->SetBatchTransfers(pairs, group));
+}
+int gdgh_engine_batch_transfers(void *e) { return ((Engine *)e)->BatchTransfers(); }
+/* records == NULL: the two counts only; capacity in doubles */
+const char *gdgh_engine_last_batch_transfer(void *e, double *records, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
+    std::vector<double> rec;
+    size_t b = 0, d = 0;
+    Error err = ((Engine *)e)->LastBatchTransfer(rec, &b, &d);
+    if (!err.empty()) return ret(err);
+    if (blocks) *blocks = b;
+    if (doubles_per_block) *doubles_per_block = d;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchTransfer: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(double));
+    }
+    return ret(Error(""));
+}
 /* records == NULL: the two counts only; capacity in doubles */
 const char *gdgh_engine_last_batch_tapfit(void *e, double *records, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
     std::vector<double> rec;

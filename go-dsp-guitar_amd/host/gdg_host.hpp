@@ -322,6 +322,15 @@ public:
     Error SetBatchTapFits(const std::vector<TapFit> &fits);
     int BatchTapFits() const { return (int)tapFitTarget_.size(); }
     Error LastBatchTapFit(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const;
+    /* No reference counterpart.  The transfer list (include/gdg.h, gdg_batch_transfer_enable): up to 16 (port, target) pairs and one group
+     * width of 1, 2, 4 .. 64 bins.  While a list is in force BatchRun and the plain streamed job keep one transfer record per block
+     * (LastBatchTransfer: [blocks][pairs x (4096 / group + 1) x 4] doubles) for gdg_match_taps_from_transfer.  Refused with more than one
+     * shard, as the tap fits are and for their reason; the ports' upper bound is checked when a job is described.  A refused list leaves
+     * the one in force; an empty list: off. */
+    struct TransferPair { int port; int target; };
+    Error SetBatchTransfers(const std::vector<TransferPair> &pairs, int group);
+    int BatchTransfers() const { return (int)transferPort_.size(); }
+    Error LastBatchTransfer(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const;
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -407,8 +416,14 @@ private:
     std::vector<double> lastTapFit_;                       /* [blocks][D] of the last batch call that kept them */
     size_t tapFitBlocks_ = 0, tapFitDoubles_ = 0;
     bool tapFitValid_ = false;
+    std::vector<int> transferPort_, transferTarget_;      /* SetBatchTransfers; no pair: off */
+    int transferGroup_ = 1;
+    std::vector<double> lastTransfer_;                     /* [blocks][doubles] of the last batch call that kept them */
+    size_t transferBlocks_ = 0, transferDoubles_ = 0;
+    bool transferValid_ = false;
+    int applyTransfers(gdg_ctx *ctx);                      /* onto a context (more shards: none is in force): a gdg_* status */
     int applyTapFits(gdg_ctx *ctx);                        /* onto a context (more shards: none are in force): a gdg_* status */
-    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0; }      /* BatchRun is the library's plain one-call run */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

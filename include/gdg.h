@@ -1457,6 +1457,91 @@ int gdg_block_tapfit_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_
                                  const int *port, const int *target, const int *taps, double *d_records);
 size_t gdg_tapfit_doubles(int n_fits, const int *first, const int *taps);
 int gdg_blend_taps_from_tapfit(const double *records, int n_fits, const int *first, const int *taps, size_t blocks, double ridge, double *tap, double *residual);
+/*
+ * TRANSFER: no reference counterpart.  "Make this rig sound like that track" is a match EQ: a transfer function estimated over the whole
+ * band and turned into an impulse response of hundreds to thousands of taps.  The tap fit stops at 128 unknowns and the band spectrum keeps
+ * no phase.  A transfer record is the frequency-domain twin of the fit record: per block the two auto-spectra and the complex cross-spectrum
+ * of a port against a target; summed over blocks they give the H1 estimate Sxy / Sxx and a coherence, and a host planner turns them into a
+ * FIR that gdg_unit_set_fir takes like any other impulse response.  Stateless: a function of the block's samples alone.
+ * LIST: 1 <= n_pairs <= GDG_TRANSFER_MAX_PAIRS (16) pairs (port[i], target[i]) and ONE group width D for the list, D in {1, 2, 4, 8, 16, 32,
+ * 64}.  port == target is allowed, and a port may repeat.  Ports are rows of the batch window, 0 .. N + 2 + B, read as the record kernels read
+ * them: before the trim, a blend port's s before g_b.
+ * RECORD: the block length is L = 8192 (GDG_TRANSFER_BLOCK) always.  For block b, x is the block of row `port` and y the block of row
+ * `target`; NaN and +-inf are taken as 0; a short last block is zero-padded.  Then
+ *   w[n] = 0.5 - 0.5 cos(2 pi n / L)                        the periodic Hann window, the band spectrum's
+ *   X[k] = sum_n w[n] x[n] exp(-2 pi i k n / L), Y[k] likewise, k = 0 .. L/2
+ *   S = L^2 * 3/8;  Pxx[k] = |X[k]|^2 / S;  Pyy[k] = |Y[k]|^2 / S;  Pxy[k] = conj(X[k]) Y[k] / S
+ * There is no doubling of the inner bins: these are sums to be divided, not powers to be read.  Im Pxy[0] = Im Pxy[L/2] = +0.0.
+ * GROUPS: Gm = 4096 / D, groups g = 0 .. Gm, G = Gm + 1.  Group g is the sum over the bins g D - (D - 1) / 2 .. g D + D / 2 (integer division),
+ * clipped to 0 .. 4096; D = 1 gives one bin per group; every bin lies in exactly one group.  The record of a pair and block is [G][4] doubles,
+ * Sxx[g], Syy[g], Re Sxy[g], Im Sxy[g]; the record of the list and block is the pairs' parts concatenated in list order: n_pairs * G * 4
+ * doubles (gdg_transfer_doubles), 131 104 bytes per pair at D = 1.  No header.
+ * ORDER OF THE SUM: a group's four sums start at +0.0 and are added over ascending k; every product and every add is rounded on its own (no
+ * contraction), no atomics.  An entry is a function of the two blocks' samples and D alone -- not of the pair's place in the list, the other
+ * pairs, the row, the grid, the batch window, the slicing, a resume or the source map.
+ * A SILENT SIDE: if all windowed samples of a side are zero after the non-finite rule, every entry that involves it is exactly +0.0; no
+ * transform rounding from the other side leaks in.
+ * UNEQUAL LEVELS: the two sides share one complex transform; each side is brought below 2 by an exact power of two of its own (from its
+ * largest windowed magnitude) before the transform and the sums are scaled back by the same powers, so a port 2^-30 times the size of its
+ * target keeps its Sxx to the transform's relative accuracy, measured against its OWN total.  SUPPORTED RANGE: the division by S acts
+ * on the SCALED values (of a size near 1), and the powers go back on afterwards, one factor at a time -- exactly, as long as the entry itself
+ * is a normal double.  That holds for a side whose largest windowed magnitude lies in 2^-480 .. 2^480; beyond it the entries -- squares of
+ * the samples -- leave the doubles' range themselves: they lose bits or become 0 below, inf above.
+ * KNOWN ANSWERS: x a cosine of amplitude 0.5 at bin 100 (x[n] = 0.5 cos(2 pi 100 n / L)) and y the sine there: at D = 1, Sxx = 0.25/24, 0.25/6,
+ * 0.25/24 in groups 99, 100, 101, Re Sxy[100] = 0 and Im Sxy[100] = -0.25/6.  At D = 4 the three bins lie in group 25 (bins 99 .. 102): Sxx[25] =
+ * 0.25/4 + 0 (bin 102 is empty).  PARSEVAL, in the raw form: sum_g Sxx[g] = ( L sum_n (w[n] x[n])^2 + |X[0]|^2 + |X[L/2]|^2 ) / (2 S) -- that is,
+ * sum (w x)^2 / (L * 3/8) minus half of what bins 1 .. 4095 would carry doubled.
+ *   gdg_batch_transfer_enable(ctx, n_pairs, port, target, group)
+ *                                                      the list; n_pairs == 0 or port == NULL: off.  The whole list is validated before it
+ *                                                      replaces the list in force; GDG_ERR_INVALID names the pair.  Refused while a streamed
+ *                                                      job is open.
+ *   gdg_batch_transfers(ctx)                           the number of pairs in force
+ *   gdg_batch_transfer(ctx, out, capacity, &blocks, &doubles_per_block)
+ *                                                      the [blocks][n_pairs][G][4] doubles of the LAST COMPLETED batch call; out == NULL: the
+ *                                                      counts only; capacity in doubles.  GDG_ERR_INVALID when capacity is too small, or when
+ *                                                      there are no records: no call has completed since the switch, or the last one was a master finish.
+ *   gdg_transfer_doubles(n_pairs, group)               n_pairs (4096 / D + 1) 4, pure arithmetic (0 for no pair or a width that is none)
+ * Port numbers are checked when a job is described -- gdg_batch_run, gdg_batch_stream_open, gdg_batch_stream_resume -- against N + 3 + B of
+ * that call; a port at or beyond it is GDG_ERR_INVALID with the pair named.  Blend ports may be named.
+ * OFF: no launch, buffer, upload byte or output byte differs from a context that never heard of the call, and option stat_batch_device_kib is
+ * unchanged; on, it counts the table and the records' room in the download halves.
+ * Configuration, like the fits: it holds from the next batch call on, is part of no blob -- set it again on the target of a resume -- and a
+ * checkpoint and a resume work with a list in force.  The records come down with each step's own download, behind the tap-fit section.
+ * SHARDS: gdg_batch_run_shard, gdg_batch_stream_open_shard, gdg_batch_stream_step_shard and gdg_batch_stream_resume_shard return
+ * GDG_ERR_UNSUPPORTED while a transfer list is in force on their context.  gdg_batch_finish_master and gdg_batch_finish_master_slice never collect transfer records.
+ * The record on its own, over any rows (ports name rows 0 .. n_rows - 1; the last block of a row may be short); both blocking -- the lists are
+ * host memory, and the whole list is checked before anything is launched:
+ *   gdg_block_transfer_rows(ctx, rows, n_rows, samples, n_pairs, port, target, group, records)
+ *                                                      host rows of `samples` float64; records: [ceil(samples / 8192)][n_pairs][G][4]
+ *   gdg_block_transfer_rows_device(ctx, d_rows, row_stride, n_rows, samples, n_pairs, port, target, group, d_records)
+ *                                                      device rows, 8-byte aligned: row r at d_rows + r * row_stride (row_stride >=
+ *                                                      samples); no sample outside [row, row + samples) is read; d_records: device
+ *                                                      memory, 8-byte aligned
+ * THE PLANNER, pure host arithmetic (csrc/blend.h), no context and no device (gdg_last_error(NULL) says what was refused):
+ *   gdg_match_taps_from_transfer(records, n_pairs, group, blocks, ridge, n_taps, center, tap, coherence)
+ *                                                      records[blocks][n_pairs][G][4] as gdg_batch_transfer hands them out, blocks >= 1;
+ *                                                      tap[n_pairs][n_taps], coherence[n_pairs]
+ * Per pair the blocks' records are added in block order with plain double adds.  N' = 2 Gm.  H[g] = Sxy[g] / (Sxx[g] + ridge * mean_g Sxx), 0
+ * where the denominator is 0; the imaginary parts at g = 0 and g = Gm are dropped.  h is the inverse real transform of length N' (a host
+ * float64 radix-2 decimation-in-time transform of the Hermitian extension).  tap[m] = t[m] * h[(m - center) mod N'] for m = 0 .. n_taps - 1, 1 <=
+ * n_taps <= N' / 2, 0 <= center < n_taps, with the taper t[m] = 0.5 + 0.5 cos(pi (m - center) / E), E = center + 1 in front of the centre and
+ * E = n_taps - center behind it: 1 at the centre and never 0 inside.  coherence = sum_g (|Sxy[g]|^2 / Sxx[g]) / sum_g Syy[g] over the groups with
+ * Sxx[g] > 0: the share of the target's energy a linear filter on the port explains.  The coherence is 1 by construction for one block at
+ * D = 1 (|Sxy|^2 = Sxx Syy bin by bin); averaging over blocks or groups is what makes it a measurement.  A NaN or inf entry is refused with
+ * the pair named, and so is a pair with no energy in the port; nothing is written on a refusal.
+ */
+#define GDG_TRANSFER_BLOCK 8192
+#define GDG_TRANSFER_MAX_PAIRS 16
+#define GDG_TRANSFER_MAX_GROUP 64
+int gdg_batch_transfer_enable(gdg_ctx *ctx, int n_pairs, const int *port, const int *target, int group);
+int gdg_batch_transfers(const gdg_ctx *ctx);
+int gdg_batch_transfer(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks, size_t *doubles_per_block);
+int gdg_block_transfer_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, int n_pairs, const int *port, const int *target, int group,
+                            double *records);
+int gdg_block_transfer_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int n_pairs, const int *port, const int *target,
+                                   int group, double *d_records);
+size_t gdg_transfer_doubles(int n_pairs, int group);
+int gdg_match_taps_from_transfer(const double *records, int n_pairs, int group, size_t blocks, double ridge, int n_taps, int center, double *tap, double *coherence);
 
 #ifdef __cplusplus
 
