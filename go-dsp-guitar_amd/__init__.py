@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "gdg_blend_taps_from_tapfit",
     "gdg_batch_transfer_enable", "gdg_batch_transfers", "gdg_batch_transfer", "gdg_block_transfer_rows", "gdg_block_transfer_rows_device", "gdg_transfer_doubles",
     "gdg_match_taps_from_transfer",
+    "gdg_batch_set_delivery", "gdg_batch_delivery", "gdg_batch_delivery_latency", "gdg_deliver_rows", "gdg_deliver_rows_device", "gdg_deliver_taps",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -295,6 +296,24 @@ def _transfer_lists(pairs):
     """pairs = [(port, target), ...] -> port, target as int32 arrays, one spare entry behind each"""
     pairs = [(int(p), int(t)) for p, t in pairs]
     return np.array([p for p, _ in pairs] + [0], dtype=np.int32), np.array([t for _, t in pairs] + [0], dtype=np.int32)
+
+
+DELIVER_HISTORY = 154        # GDG_DELIVER_HISTORY (include/gdg.h, DELIVERY): the session samples a delivered port keeps from call to call
+DELIVER_ATTENUATION = 0.9440608762859234
+
+
+def batch_delivery_latency(factor):
+    """gdg_batch_delivery_latency: the session samples a port delivered at `factor` lags the render by (0, 38, 77)."""
+    return int(lib().gdg_batch_delivery_latency(int(factor)))
+
+
+def deliver_taps(factor):
+    """gdg_deliver_taps: the expanded anti-aliasing taps of a delivery factor (77 at 2, 155 at 4; empty otherwise)."""
+    n = int(lib().gdg_deliver_taps(int(factor), None, 0))
+    out = np.zeros(n, dtype=np.float64)
+    if n:
+        lib().gdg_deliver_taps(int(factor), out.ctypes.data, n)
+    return out
 
 
 def transfer_doubles(n_pairs, group):
@@ -605,6 +624,12 @@ def lib():
             "gdg_block_transfer_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, i32, vp]),
             "gdg_transfer_doubles": (C.c_size_t, [i32, i32]),
             "gdg_match_taps_from_transfer": (i32, [vp, i32, i32, C.c_size_t, C.c_double, i32, i32, vp, vp]),
+            "gdg_batch_set_delivery": (i32, [vp, i32]),
+            "gdg_batch_delivery": (i32, [vp]),
+            "gdg_batch_delivery_latency": (i32, [i32]),
+            "gdg_deliver_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp]),
+            "gdg_deliver_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, C.c_size_t]),
+            "gdg_deliver_taps": (i32, [i32, vp, i32]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1057,9 +1082,10 @@ class Context:
         length = C.c_size_t(0)
         self._check(lib().gdg_batch_length(self._h, arr, n, target_rate, C.byref(length)))
         wo = lib().gdg_wave_bytes_per_sample(fo)
+        size = length.value // self.batch_delivery() * wo      # every port at the delivered rate (batch_set_delivery)
         if outs is None:
-            outs = [np.zeros(length.value * wo, dtype=np.uint8) for _ in range(no)]
-        assert len(outs) == no and all(o.dtype == np.uint8 and o.size == length.value * wo for o in outs)
+            outs = [np.zeros(size, dtype=np.uint8) for _ in range(no)]
+        assert len(outs) == no and all(o.dtype == np.uint8 and o.size == size for o in outs)
         ptrs = (C.c_void_p * no)(*[(o.ctypes.data if o.size else None) for o in outs])
         self._check(lib().gdg_batch_run(self._h, arr, n, C.byref(opt), ptrs))
         return outs
@@ -1075,7 +1101,7 @@ class Context:
         self._check(lib().gdg_batch_length(self._h, arr, n, target_rate, C.byref(length)))
         wo = lib().gdg_wave_bytes_per_sample(fo)
         no = n + 3 + self.batch_blends()                # the blends in force when the call is prepared
-        outs = [np.zeros(length.value * wo, dtype=np.uint8) for _ in range(no)]
+        outs = [np.zeros(length.value // self.batch_delivery() * wo, dtype=np.uint8) for _ in range(no)]      # ... and the delivery factor
         ptrs = (C.c_void_p * no)(*[(o.ctypes.data if o.size else None) for o in outs])
         fn, h, ref = lib().gdg_batch_run, self._h, C.byref(opt)
 
@@ -1198,7 +1224,7 @@ class Context:
                 for b in in_bytes]
         assert len(keep) == n
         ins = (C.c_void_p * n)(*[(b.ctypes.data if b is not None and b.size else None) for b in keep])
-        size = blocks * 8192 * self._stream_width
+        size = blocks * 8192 // self.batch_delivery() * self._stream_width
         if outs is None:
             outs = [np.zeros(size, dtype=np.uint8) for _ in range(no)]
         assert len(outs) == no and all(o is None or (o.dtype == np.uint8 and o.size == size) for o in outs)
@@ -1754,6 +1780,42 @@ class Context:
         self._check(lib().gdg_block_transfer_rows_device(self._h, d_rows, row_stride, n_rows, samples, len(pairs), port.ctypes.data, target.ctypes.data, int(group), d_records))
 
     transfer_doubles = staticmethod(transfer_doubles)
+
+    # -- the delivery: every encoded port of a batch call at a half or a quarter of the session rate (include/gdg.h, DELIVERY) ----------------
+    def batch_set_delivery(self, factor):
+        """From the next batch call on, batch_run and batch_stream_step write every port at 1 / factor of the session rate
+        (gdg_batch_set_delivery): factor 1 (off), 2 or 4.  Each output then has length // factor samples and lags the render by
+        batch_delivery_latency(factor) session samples; the records stay those of the session-rate render.  Configuration: not in a
+        checkpoint, refused while a streamed job is open; the checkpoint, shard and finish_master calls refuse while it is on."""
+        self._check(lib().gdg_batch_set_delivery(self._h, int(factor)))
+
+    def batch_delivery(self):
+        """The delivery factor in force (gdg_batch_delivery): 1 = off."""
+        return int(lib().gdg_batch_delivery(self._h))
+
+    def deliver_rows(self, rows, factor, history=None):
+        """gdg_deliver_rows: rows [n_rows, samples] float64 (or one 1-D row), samples a positive multiple of factor -> [n_rows, samples //
+        factor].  history: None (zeros in front of sample 0) or a C-contiguous [n_rows, 154] float64 array, read before and UPDATED IN PLACE
+        after, so consecutive calls continue a stream."""
+        x = np.ascontiguousarray(rows, dtype=np.float64)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        n, samples = x.shape
+        f = int(factor)
+        if history is not None:
+            assert isinstance(history, np.ndarray) and history.dtype == np.float64 and history.flags.c_contiguous and history.size == n * DELIVER_HISTORY
+        out = np.zeros((n, samples // f if f > 0 else 0), dtype=np.float64)
+        self._check(lib().gdg_deliver_rows(self._h, x.ctypes.data if x.size else None, n, samples, f, None if history is None else history.ctypes.data,
+                                           out.ctypes.data if out.size else None))
+        return out[0] if one else out
+
+    def deliver_rows_device(self, d_rows, row_stride, n_rows, samples, factor, d_history, d_out, out_stride):
+        """gdg_deliver_rows_device on plain device pointers (ints; d_history 0 or None: zeros in front), enqueued on the context's stream."""
+        self._check(lib().gdg_deliver_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(factor), d_history or None, d_out, out_stride))
+
+    batch_delivery_latency = staticmethod(batch_delivery_latency)
+    deliver_taps = staticmethod(deliver_taps)
     match_taps_from_transfer = staticmethod(match_taps_from_transfer)
 
     def batch_report(self):

@@ -127,6 +127,11 @@ struct BatchLoop {
     struct List { const int *h_table, *d_table; int count; ListShape shape; } list[LIST_KINDS];
     /* ... and the transfer list (include/gdg.h, TRANSFER) in the same terms: its section rides behind theirs; count 0 = off, and always for a shard */
     List transfer;
+    /* the delivery (include/gdg.h, DELIVERY; deliver.h): the factor (0 or 1 = off, and always for a shard), the scratch rows [NR][ws / R] the
+     * encoders read instead of the window, the factor's taps on the device and the window rows' history [NR][154] */
+    int deliver;
+    double *d_delivered, *d_deliver_history;
+    const double *d_deliver_taps;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -154,6 +159,7 @@ typedef std::function<int(size_t i, size_t off, int w, int pool)> BatchStage;
 static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &stage_fn) {
     const int N = p.N, NO = N + 3, NR = NO + p.n_blends, B = GDG_BLOCK_SIZE, enc_rows = p.enc_rows, f64_rows = p.f64_rows, out_width = p.out_width, W = p.W;
     const size_t length = p.length, ws = p.ws, enc_bytes = p.enc_bytes;
+    const int R = p.deliver > 1 ? p.deliver : 1;                              /* the delivery factor: every byte count below is of the delivered length (deliver.h) */
     double *const d_inputs = p.d_inputs, *const d_win = p.d_win;
     unsigned char *const d_enc = p.d_enc;
     const gdg_batch_options *opt = p.opt;
@@ -187,7 +193,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; behind them one section per live kind of the render
      * report, [rows][w] -- N + 3 rows and the blends', a shard's N chain rows and the metronome's -- which come down with the last piece */
     auto down_bytes = [&](size_t i) {
-        const size_t wb = (size_t)steps[i].w * B, row_bytes = wb * out_width;
+        const size_t wb = (size_t)steps[i].w * B, row_bytes = deliver_step((size_t)steps[i].w, steps[i].off, R, (size_t)out_width, 0).row_bytes;
         return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
     };
     const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NR;
@@ -214,10 +220,11 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     double2 *transfer_tw = nullptr;
     if (p.transfer.count && (r = fir_tables(ctx, GDG_TRANSFER_BLOCK, &transfer_tw, &align_tw2)) != GDG_OK) return r;      /* the same transform's tables as the alignment's */
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
-    auto chunk_rows = [&](size_t i, int c) { return (size_t)enc_rows * (size_t)c / (size_t)chunks_of(i); };      /* first encoded row of piece c */
+    auto chunk_rows = [&](size_t i, int c) { return deliver_chunk_row((size_t)enc_rows, c, chunks_of(i)); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
         const unsigned char *src = ctx->h_batch[i & 1];
-        const size_t wb = (size_t)steps[i].w * B, row_bytes = wb * out_width, at = steps[i].off * out_width;
+        const DeliverStep ds = deliver_step((size_t)steps[i].w, steps[i].off, R, (size_t)out_width, (size_t)enc_rows);
+        const size_t wb = (size_t)steps[i].w * B, row_bytes = ds.row_bytes, at = ds.file_at;
         const size_t f64_at = ((size_t)enc_rows * row_bytes + 15) & ~(size_t)15;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
@@ -274,7 +281,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_moved[h], 0));     /* step i - 2 has left enc */
         {
             ProfScope ps(ctx, GDG_K_WAVE);
-            const size_t row_bytes = (size_t)wb * out_width;
+            const size_t row_bytes = deliver_step((size_t)w, off, R, (size_t)out_width, 0).row_bytes;
             const ReportSections &sec = steps[i].sec;
             /* the blend rows, behind the metronome's: sums of the chain rows, which are final; every reader below takes them as rows like the others */
             if (p.n_blends) {
@@ -316,14 +323,24 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             /* dither on: n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
-                const gdg_encode_mode m = { gains != nullptr, p.dither, gains, { 1.0, 1.0 }, { ctx->dither_seed, p.dither_first + off, port_base, n_chain } };
-                return gdg_launch_wave_encode_rows(opt->out_format, rows, ws, (size_t)wb, n_rows, dst, m, ctx->stream);
+                /* delivered: the rows are the scratch rows' -- a row ws / R apart, wb / R samples of it -- and a sample's index is its index in the delivered job */
+                const gdg_encode_mode m = { gains != nullptr, p.dither, gains, { 1.0, 1.0 }, { ctx->dither_seed, (p.dither_first + off) / (uint64_t)R, port_base, n_chain } };
+                return gdg_launch_wave_encode_rows(opt->out_format, rows, ws / (size_t)R, (size_t)wb / (size_t)R, n_rows, dst, m, ctx->stream);
             };
+            /* the delivery: the window's NR rows, final by now and read by every record above as they are, decimated into the scratch rows -- the
+             * samples in front of the step come from the history, which this step's tail replaces behind the launch and before the next step
+             * writes the window.  The order is decimate, then gain, then the plain or dithered encoder: the encoders read the scratch rows. */
+            const double *enc_src = d_win;
+            if (R > 1) {
+                HIP_TRY(ctx, gdg_launch_deliver_rows(R, d_win, ws, (size_t)wb, (unsigned)NR, p.d_deliver_taps, p.d_deliver_history, p.d_delivered, ws / (size_t)R, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_deliver_history_save(d_win, ws, (size_t)wb, (unsigned)NR, p.d_deliver_history, ctx->stream));
+                enc_src = p.d_delivered;
+            }
             if (!sharded) {
-                HIP_TRY(ctx, encode_rows(d_win, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
+                HIP_TRY(ctx, encode_rows(enc_src, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
                 /* a launch of their own: blend b is port port_base + N + 3 + b of the dither, and its gain is the blend's, not the trim's */
                 if (p.n_blends)
-                    HIP_TRY(ctx, encode_rows(d_win + (size_t)NO * ws, (unsigned)p.n_blends, (unsigned)p.n_blends, ctx->dither_port_base + (uint32_t)NO,
+                    HIP_TRY(ctx, encode_rows(enc_src + (size_t)NO * (ws / (size_t)R), (unsigned)p.n_blends, (unsigned)p.n_blends, ctx->dither_port_base + (uint32_t)NO,
                                              enc + (size_t)NO * row_bytes, p.d_blend_gain));
             } else {
                 HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
@@ -341,14 +358,15 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     };
     /* ... and its way down on the download stream, into the step's pinned half (which step i - 2 must have left: scatter(i - 2) is done) */
     auto enqueue_down = [&](size_t i) -> int {
-        const int h = (int)(i & 1), wb = steps[i].w * B;
+        const int h = (int)(i & 1);
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
-        const size_t row_bytes = (size_t)wb * out_width;
+        const size_t row_bytes = deliver_step((size_t)steps[i].w, steps[i].off, R, (size_t)out_width, 0).row_bytes;
         const size_t down = steps[i].transfer.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
-            const size_t b0 = chunk_rows(i, c) * row_bytes, b1 = (c + 1 == K) ? down : chunk_rows(i, c + 1) * row_bytes;
+            size_t b0 = 0, b1 = 0;
+            deliver_chunk_bytes((size_t)enc_rows, row_bytes, c, K, down, &b0, &b1);
             if (b1 > b0) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_batch[h] + b0, enc + b0, b1 - b0, hipMemcpyDeviceToHost, ctx->batch_stream));
             HIP_TRY(ctx, hipEventRecord(ctx->batch_chunk[h][c], ctx->batch_stream));
         }
@@ -503,6 +521,30 @@ int gdg_batch_set_trim(gdg_ctx *ctx, const double *chain_gain, int n, double mas
     ctx->trim_gain.swap(gain);
     return GDG_OK;
 }
+
+/* the delivery factor: validated before it replaces the one in force (deliver.h); read by every call that encodes */
+int gdg_batch_set_delivery(gdg_ctx *ctx, int factor) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set delivery: a streamed batch run is open on this context; its delivery factor %d holds until gdg_batch_stream_close", ctx->deliver);
+    if (!gdg_deliver_factor_ok(factor)) return fail(ctx, GDG_ERR_INVALID, "set delivery: delivery factor %d; 1 is the session rate, 2 a half of it, 4 a quarter", factor);
+    if (factor == ctx->deliver) return GDG_OK;
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    /* another row length: whatever still reads the encoded halves and the scratch rows has to be done before they go -- and a wait that fails
+     * refuses the call with the factor in force untouched.  The halves are made anew by the next batch call, at the size of a context that
+     * was always configured like this one; back at 1 the scratch rows and the history go as well (the next job with a factor begins from zeros anyway) */
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i : { (int)BATCH_ENCODED, (int)BATCH_DELIVERED, (int)BATCH_DELIVER_HISTORY }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    ctx->deliver = factor;
+    return GDG_OK;
+}
+
+int gdg_batch_delivery(const gdg_ctx *ctx) { return ctx ? ctx->deliver : 1; }
+int gdg_batch_delivery_latency(int factor) { return gdg_deliver_latency(factor); }
+
+/* a shard's master mix is finished elsewhere, from float64 partials at the session rate, and the history is per context: the shard forms and
+ * the finish calls refuse while a factor is in force (include/gdg.h) */
+#define DELIVERY_REFUSED(ctx, what) \
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d is in force on this context (gdg_batch_set_delivery); a sharded job cannot deliver at another rate yet", what, (ctx)->deliver)
 
 /* the blend outputs: validated whole before the list replaces the one in force (blend.h); read when a job is described and by every slice */
 int gdg_batch_set_blends_filtered(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const int *tap_first,
@@ -793,6 +835,7 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
 
 int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t job_samples,
                                 int run_metronome, size_t *samples) {
+    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_open_shard")) return rc;
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
@@ -855,6 +898,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const size_t length = (size_t)blocks * B, pos = S.pos;                       /* the slice: rows of `length` samples, the job's [pos, pos + length) */
     /* the blends in force (never a shard's): NR rows of the window leave the device encoded, and every record kind has NR ports */
     const int n_blends = sharded ? 0 : ctx->blend.count(), NR = NO + n_blends;
+    const int R = sharded ? 1 : ctx->deliver;                                    /* the delivery factor in force (never a shard's: its calls refuse it) */
     report_begin(ctx, sharded ? N + 1 : NR, (size_t)blocks, true, n_blends);
     ListInForce lists[LIST_KINDS];                                               /* the lists in force; never a shard's: its calls refuse them */
     for (int k = 0; k < LIST_KINDS; k++) {
@@ -886,7 +930,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const gdg_spectrum_bands bands = live.on(REPORT_BANDS) ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), opt->target_rate) : gdg_spectrum_bands();
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
-    const size_t enc_bytes = (((size_t)enc_room * ws * (size_t)out_width + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
+    const size_t enc_bytes = ((deliver_window_bytes((size_t)W, R, (size_t)out_width, (size_t)enc_room) + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
                            + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + list_room(lists[LIST_FIT].shape, (size_t)W)
                            + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W) + list_room(transfer.shape, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
@@ -1107,6 +1151,18 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
                 if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_blend_history, 0, hist_bytes, ctx->stream));
             }
         }
+        /* the delivery in force: the scratch rows the encoders read, and the history of the window's NR rows -- the job's first slice begins from
+         * zeros, every later one from what the slice before left */
+        if (R > 1) {
+            const size_t hist_bytes = (size_t)NR * GDG_DELIVER_HISTORY * sizeof(double);
+            const bool fresh = ctx->batch_dev_cap[BATCH_DELIVER_HISTORY] < hist_bytes;
+            if ((r = batch_buffer(ctx, BATCH_DELIVERED, (size_t)NR * (ws / (size_t)R) * sizeof(double), (void **)&loop.d_delivered)) != GDG_OK) return r;
+            if ((r = batch_buffer(ctx, BATCH_DELIVER_HISTORY, hist_bytes, (void **)&loop.d_deliver_history)) != GDG_OK) return r;
+            if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the delivery history of the open job is gone (gdg_batch_release between two slices?)");
+            if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_deliver_history, 0, hist_bytes, ctx->stream));
+            loop.deliver = R;
+            loop.d_deliver_taps = R == 2 ? ctx->os.taps2 : ctx->os.taps4;       /* the oversampler's expanded tables (api_ctx.cpp) */
+        }
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -1147,6 +1203,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 }
 
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
+    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_step_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_step_shard")) return rc;
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
@@ -1191,6 +1248,7 @@ int gdg_batch_run(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
 int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes,
                         const gdg_batch_shard_out *shard) {
     if (!shard) return GDG_ERR_INVALID;
+    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_run_shard");
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_run_shard")) return rc;
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
@@ -1344,6 +1402,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
 /* the master mix of a whole job: any sample count */
 int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                             size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master");
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes, 0);      /* the cursor stays */
@@ -1352,6 +1411,7 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
 /* ... and of one slice of a streamed sharded job, where it runs once per slice on the job's critical path: whole blocks, as the slices are */
 int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                                   size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
+    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master_slice");
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);

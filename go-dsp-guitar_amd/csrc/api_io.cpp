@@ -153,6 +153,66 @@ int gdg_wave_encode_trim(gdg_ctx *ctx, int format, const double *samples, size_t
                        [&](const double *d, void *b) { return gdg_wave_encode_trim_device(ctx, format, d, n, gain, mode, seed, port, first_index, b); });
 }
 
+/* the delivery on its own (deliver.h; io.hip, deliver_kernels.h): rows at the session rate -> rows at a half or a quarter of it; factor 1 copies */
+static int deliver_check(gdg_ctx *ctx, const char *what, int n_rows, size_t samples, int factor) {
+    if (!gdg_deliver_factor_ok(factor)) return fail(ctx, GDG_ERR_INVALID, "%s: delivery factor %d; 1 is the session rate, 2 a half of it, 4 a quarter", what, factor);
+    if (n_rows <= 0) return fail(ctx, GDG_ERR_INVALID, "%s: %d rows", what, n_rows);
+    if (samples == 0 || samples % (size_t)factor) return fail(ctx, GDG_ERR_INVALID, "%s: %zu samples; a positive multiple of the delivery factor %d", what, samples, factor);
+    return GDG_OK;
+}
+
+int gdg_deliver_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int factor, double *d_history, double *d_out,
+                            size_t out_stride) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const int rc = deliver_check(ctx, "deliver rows", n_rows, samples, factor);
+    if (rc != GDG_OK) return rc;
+    if (!d_rows || !d_out) return GDG_ERR_INVALID;
+    if (row_stride < samples || out_stride < samples / (size_t)factor)
+        return fail(ctx, GDG_ERR_INVALID, "deliver rows: strides of %zu and %zu samples for rows of %zu and %zu", row_stride, out_stride, samples, samples / (size_t)factor);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_history & 7)) return fail(ctx, GDG_ERR_INVALID, "deliver rows: the samples are float64, 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    ProfScope ps(ctx, GDG_K_WAVE);
+    if (factor == 1)
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_out, out_stride * sizeof(double), d_rows, row_stride * sizeof(double), samples * sizeof(double), (size_t)n_rows, hipMemcpyDeviceToDevice, ctx->stream));
+    else
+        HIP_TRY(ctx, gdg_launch_deliver_rows(factor, d_rows, row_stride, samples, (unsigned)n_rows, factor == 2 ? ctx->os.taps2 : ctx->os.taps4, d_history, d_out, out_stride, ctx->stream));
+    /* behind the sum: the rows' last 154 samples are what the next call finds in front of its own */
+    if (d_history) HIP_TRY(ctx, gdg_launch_deliver_history_save(d_rows, row_stride, samples, (unsigned)n_rows, d_history, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_deliver_rows(gdg_ctx *ctx, const double *rows, int n_rows, size_t samples, int factor, double *history, double *out) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = deliver_check(ctx, "deliver rows", n_rows, samples, factor);
+    if (rc != GDG_OK) return rc;
+    if (!rows || !out) return GDG_ERR_INVALID;
+    enter_keep_fir_sums(ctx);
+    const size_t n_out = samples / (size_t)factor, rows_bytes = ((size_t)n_rows * samples * sizeof(double) + 15) & ~(size_t)15;
+    const size_t hist_bytes = history ? (size_t)n_rows * GDG_DELIVER_HISTORY * sizeof(double) : 0;
+    rc = ensure_io(ctx, 1, rows_bytes + hist_bytes);
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, (size_t)n_rows * n_out * sizeof(double));
+    if (rc != GDG_OK) return rc;
+    double *d_rows = static_cast<double *>(ctx->d_io[1]), *d_out = static_cast<double *>(ctx->d_io[0]);
+    double *d_hist = history ? reinterpret_cast<double *>(static_cast<unsigned char *>(ctx->d_io[1]) + rows_bytes) : nullptr;
+    HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows, (size_t)n_rows * samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (history) HIP_TRY(ctx, hipMemcpyAsync(d_hist, history, hist_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_deliver_rows_device(ctx, d_rows, samples, n_rows, samples, factor, d_hist, d_out, n_out);
+    if (rc != GDG_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)n_rows * n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (history) HIP_TRY(ctx, hipMemcpyAsync(history, d_hist, hist_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
+/* the factor's expanded anti-aliasing taps (aa_taps.h), as the oversampler's table has them: 77 or 155 doubles; pure host arithmetic */
+int gdg_deliver_taps(int factor, double *taps, int capacity) {
+    const int T = gdg_deliver_tap_count(factor);
+    if (!T) return 0;
+    const double *half = factor == 2 ? GDG_AA2_HALF : GDG_AA4_HALF;
+    for (int k = 0; taps && k < T && k < capacity; k++) taps[k] = half[k <= T / 2 ? k : T - 1 - k];
+    return T;
+}
+
 /* the planner (trim.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
 int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_t blocks, double target, double max_gain, double *gain) {
     static_assert(sizeof(gdg_block_true_peak) == 2 * sizeof(double) && offsetof(gdg_block_true_peak, true_peak) == 0, "the planner strides over true_peak in doubles");

@@ -19,6 +19,7 @@
 #include "../../include/gdg.h"
 #include "gdg_internal.h"
 #include "aa_taps.h"
+#include "deliver.h"
 #include "go_consts.h"
 #include "notes.h"
 
@@ -352,8 +353,8 @@ struct gdg_ctx {
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
     /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
      * grown when a slice needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
-    void *batch_dev[11] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t batch_dev_cap[11] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    void *batch_dev[13] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    size_t batch_dev_cap[13] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
     /* a batch job, how far it has come, and per input the source frames handed over: the context's is the streamed run's
      * (gdg_batch_stream_open .. _close); a one-call run describes its own and leaves this one closed */
@@ -401,6 +402,12 @@ struct gdg_ctx {
      * device copy is made and uploaded at the start of a batch call, only while a trim is in force.  Configuration like the dither: in no blob. */
     std::vector<double> trim_gain;
     double *d_trim = nullptr;
+    /* the delivery (gdg_batch_set_delivery; deliver.h): 1 = off (never set, or set to 1), 2 or 4: every encoded port of gdg_batch_run and
+     * gdg_batch_stream_step leaves the device at a half or a quarter of the session rate.  While it is on batch_dev[BATCH_DELIVERED] holds a
+     * step's decimated rows in front of the encoders and batch_dev[BATCH_DELIVER_HISTORY] the last 154 samples of every row of the window from
+     * step to step; the history is zeroed by the first slice of a job and is in no checkpoint (the checkpoint calls then refuse).  Off, neither
+     * exists.  Configuration like the trim: in no blob. */
+    int deliver = 1;
     /* the blend outputs (gdg_batch_set_blends; blend.h): weighted sums of this context's chain rows as the ports behind the metronome's; an
      * empty list = off (never set, or set with 0 blends).  While blends are in force a batch window has nch + 3 + count() rows and the device
      * copy of the table -- first | channel | delay | weight | gain, made and uploaded at the start of a batch call -- exists; off, neither does.
@@ -848,6 +855,8 @@ enum {
     BATCH_GRAM_PORTS,                      /* [P] the Gram list's ports, only while a list is in force (gdg_batch_gram_enable) */
     BATCH_TAPFIT_TABLE,                    /* [fits][target | terms | taps | port[4] | offset | tile] the tap fits' table, only while tap fits are in force (gdg_batch_tapfit_enable) */
     BATCH_TRANSFER_TABLE,                  /* [pairs][port | target], then the group width: the transfer list's table, only while one is in force (gdg_batch_transfer_enable) */
+    BATCH_DELIVERED,                       /* [N + 3 + blends][window / R] one step's rows at the delivered rate, what the encoders read; only while a delivery factor is in force (gdg_batch_set_delivery) */
+    BATCH_DELIVER_HISTORY,                 /* [N + 3 + blends][154] the window rows' last samples of the step before, only while a delivery factor is in force */
     BATCH_DEV_SLOTS
 };
 static_assert(sizeof(gdg_ctx::batch_dev) / sizeof(void *) == BATCH_DEV_SLOTS && sizeof(gdg_ctx::batch_dev_cap) / sizeof(size_t) == BATCH_DEV_SLOTS,

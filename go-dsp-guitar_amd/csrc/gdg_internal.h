@@ -354,6 +354,14 @@ hipError_t gdg_launch_blend(const gdg_blend_view &view, const double *d_rows, si
                             double *d_out, size_t out_stride, hipStream_t s);
 /* the last GDG_BLEND_MAX_DELAY of `samples` samples (samples >= GDG_BLEND_MAX_DELAY) of rows 0 .. n_rows - 1 into d_history[n_rows][GDG_BLEND_MAX_DELAY] */
 hipError_t gdg_launch_blend_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
+/* the delivery (include/gdg.h, DELIVERY; io.hip, deliver_kernels.h; deliver.h): n_rows rows of `samples` session samples (a positive multiple of
+ * `factor`, 2 or 4) -> rows of samples / factor samples at d_out + r * out_stride: the factor's anti-aliasing FIR (d_taps: its 77 or 155 expanded
+ * taps in device memory), every factor-th sample, times ATTENUATION_HALF_DECIBEL.  d_history: null (+0.0 in front of sample 0) or [n_rows][154],
+ * the session samples in front of the launch; read, never written.  Rows 8-byte aligned; d_out overlaps neither the rows nor the history. */
+hipError_t gdg_launch_deliver_rows(int factor, const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, const double *d_taps, const double *d_history,
+                                   double *d_out, size_t out_stride, hipStream_t s);
+/* ... and behind it, before the rows are written again: the rows' last 154 samples into d_history[n_rows][154]; a launch of fewer moves the old ones up */
+hipError_t gdg_launch_deliver_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
 /* the blend fit's records (include/gdg.h, FIT; io.hip, fit_kernels.h): per fit and block of `block` samples (the last of a row may be short)
  * one gdg_block_fit, d_records[n_fits][ceil(samples / block)].  A fit is target | terms | port[8] (blend.h, FitSet): h_table is the host's copy
  * of the device's d_table, held against n_rows before anything is launched. */

@@ -597,7 +597,7 @@ func (this *Context) BatchRun(inputs []BatchInput, opt BatchOptions) ([][]byte, 
 	if e := this.err(C.gdg_batch_length(this.ctx, &arr[0], C.int(n), o.target_rate, &samples)); e != nil {
 		return nil, e
 	}
-	each := int(samples) * int(C.gdg_wave_bytes_per_sample(o.out_format))
+	each := int(samples) / int(C.gdg_batch_delivery(this.ctx)) * int(C.gdg_wave_bytes_per_sample(o.out_format)) // every port at the delivered rate (BatchSetDelivery)
 	no := n + 3 + int(C.gdg_batch_blends(this.ctx)) // the blends in force (BatchSetBlends): one more port each, behind the metronome's
 	outs := make([][]byte, no)
 	if each == 0 {
@@ -848,7 +848,7 @@ func (this *Context) BatchStreamStep(blocks int, frames [][]byte) ([][]byte, err
 	if n == 0 || len(frames) != n {
 		return nil, fmt.Errorf("gdg: %d inputs for a streamed batch run of %d", len(frames), n)
 	}
-	each := blocks * 8192 * this.streamWidth
+	each := blocks * 8192 / int(C.gdg_batch_delivery(this.ctx)) * this.streamWidth // every piece at the delivered rate (BatchSetDelivery)
 	if blocks <= 0 || each <= 0 {
 		return nil, fmt.Errorf("gdg: a slice of %d blocks", blocks)
 	}
@@ -1787,6 +1787,67 @@ func (this *Context) BatchSetTrim(chainGain []float64, masterLeft float64, maste
 		p[i] = C.double(v)
 	}
 	return this.err(C.gdg_batch_set_trim(this.ctx, &p[0], C.int(n), C.double(masterLeft), C.double(masterRight), C.double(metronome)))
+}
+
+// DeliverHistory: the session samples a delivered row keeps from call to call (GDG_DELIVER_HISTORY of the C header).
+const DeliverHistory = 154
+
+// BatchSetDelivery: from the next batch call on BatchRun and BatchStreamStep write every port -- chain outputs, master left and right,
+// metronome, blends -- at 1 / factor of the session rate (gdg_batch_set_delivery): factor 1 (off), 2 or 4.  The reference's decimator
+// (oversampling.Decimate: the anti-aliasing FIR of 77 or 155 taps, every factor-th sample, times ATTENUATION_HALF_DECIBEL) on the finished
+// float64 rows; an output has samples / factor samples and lags the render by BatchDeliveryLatency(factor) session samples.  Records,
+// meters and float64 rows stay those of the session-rate render.  Configuration, like BatchSetTrim: a checkpoint does not carry it, and
+// the checkpoint, shard and master-finish calls refuse while a factor is in force; an error while a streamed job is open.
+func (this *Context) BatchSetDelivery(factor int) error {
+	return this.err(C.gdg_batch_set_delivery(this.ctx, C.int(factor)))
+}
+
+// BatchDelivery: the delivery factor in force (gdg_batch_delivery): 1 = off.
+func (this *Context) BatchDelivery() int {
+	return int(C.gdg_batch_delivery(this.ctx))
+}
+
+// BatchDeliveryLatency: the session samples a port delivered at factor lags the render by (gdg_batch_delivery_latency): 0, 38, 77.
+func BatchDeliveryLatency(factor int) int {
+	return int(C.gdg_batch_delivery_latency(C.int(factor)))
+}
+
+// DeliverTaps: the expanded anti-aliasing taps of a delivery factor (gdg_deliver_taps): 77 at 2, 155 at 4, none otherwise.
+func DeliverTaps(factor int) []float64 {
+	n := int(C.gdg_deliver_taps(C.int(factor), nil, 0))
+	taps := make([]float64, n)
+	if n > 0 {
+		C.gdg_deliver_taps(C.int(factor), (*C.double)(unsafe.Pointer(&taps[0])), C.int(n))
+	}
+	return taps
+}
+
+// DeliverRows: nRows rows of samples float64 each, one after the other in rows, at 1 / factor of their rate (gdg_deliver_rows): samples
+// is a positive multiple of factor.  history is nil (zeros in front of the first sample) or nRows * DeliverHistory values, read before and
+// written after, so that consecutive calls continue a stream.
+func (this *Context) DeliverRows(rows []float64, nRows int, samples int, factor int, history []float64) ([]float64, error) {
+	if nRows <= 0 || samples <= 0 || factor <= 0 || len(rows) != nRows*samples {
+		return nil, fmt.Errorf("gdg: %d values for %d rows of %d samples at factor %d", len(rows), nRows, samples, factor)
+	}
+	if history != nil && len(history) != nRows*DeliverHistory {
+		return nil, fmt.Errorf("gdg: a history of %d values for %d rows", len(history), nRows)
+	}
+	out := make([]float64, nRows*(samples/factor))
+	if len(out) == 0 {
+		return nil, fmt.Errorf("gdg: %d samples at factor %d", samples, factor)
+	}
+	var hist *C.double
+	if history != nil {
+		hist = (*C.double)(unsafe.Pointer(&history[0]))
+	}
+	rc := C.gdg_deliver_rows(this.ctx, (*C.double)(unsafe.Pointer(&rows[0])), C.int(nRows), C.size_t(samples), C.int(factor), hist, (*C.double)(unsafe.Pointer(&out[0])))
+	return out, this.err(rc)
+}
+
+// DeliverRowsDevice: the same on device memory, enqueued on the context's stream (gdg_deliver_rows_device): row r at dRows + r * rowStride,
+// its delivered samples at dOut + r * outStride; dHistory nil or nRows * DeliverHistory doubles.
+func (this *Context) DeliverRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, factor int, dHistory unsafe.Pointer, dOut unsafe.Pointer, outStride int) error {
+	return this.err(C.gdg_deliver_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(factor), (*C.double)(dHistory), (*C.double)(dOut), C.size_t(outStride)))
 }
 
 // WaveEncodeTrim: one mono row times gain through the encoder (gdg_wave_encode_trim): mode 0 the plain encoder, 1 the dithered one of

@@ -48,6 +48,8 @@ def lib():
             "gdgh_engine_set_batch_report": (None, [vp, i32]),
             "gdgh_engine_set_batch_dither": (None, [vp, i32, C.c_uint64]),
             "gdgh_engine_set_batch_trim": (cs, [vp, vp, i32, C.c_double, C.c_double, C.c_double]),
+            "gdgh_engine_set_batch_delivery": (cs, [vp, i32]),
+            "gdgh_engine_batch_delivery": (i32, [vp]),
             "gdgh_engine_sync_chains": (cs, [vp, C.c_uint32]),
             "gdgh_engine_set_batch_blends": (cs, [vp, i32, vp, vp, vp, vp]),
             "gdgh_engine_batch_blends": (i32, [vp]),
@@ -294,6 +296,12 @@ class Engine:
         """Engine::SetBatchDither, from the `dither` argument of the batch calls: TPDF dither of the job's LPCM outputs with this seed
         (None: off); every shard gets its port_base from the engine, so the files do not depend on the shard count."""
         lib().gdgh_engine_set_batch_dither(self._h, 0 if seed is None else 1, 0 if seed is None else int(seed))
+
+    def _set_delivery(self, deliver):
+        """Engine::SetBatchDelivery, from the `deliver` argument of the batch calls: None or 1 = the session rate, 2 or 4 = every output at a
+        half or a quarter of it (one-shard engines only).  Returns the factor in force."""
+        _err(lib().gdgh_engine_set_batch_delivery(self._h, 1 if deliver is None else int(deliver)))
+        return int(lib().gdgh_engine_batch_delivery(self._h))
 
     def _set_trim(self, trim):
         """Engine::SetBatchTrim, from the `trim` argument of the batch calls: the gains of the job's N + 3 output ports in the files' order
@@ -683,7 +691,9 @@ class Engine:
         output data sections and the N + 3 gains used -- with blends= in kw N + 3 + B of each: a blend port's gain is planned from its own
         true-peak records like any other port's and passed as its output gain (a blend_gain in kw is replaced).  The master's gains come from the finish's own records of pass 1, whatever the
         shard count.  Pass 1's records stay in normalize_true_peak / normalize_report.  The state blob is the channels': a configured
-        metronome and the meters run on from pass 1.  kw: batch_run's other arguments (dither, run_meters ...)."""
+        metronome and the meters run on from pass 1.  kw: batch_run's other arguments (dither, run_meters ...).  deliver= is carried through
+        both passes unchanged: the gains are planned from the session-rate records, and a delivered file's true peak can differ from the
+        render's (the anti-aliasing filter rings), so leave the headroom the target is meant to leave."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         rate = target_rate if sample_rate is None else sample_rate
@@ -700,7 +710,7 @@ class Engine:
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
@@ -712,12 +722,17 @@ class Engine:
         records in last_fit ([fits, blocks], FIT_DTYPE; one-shard engines only; None: off).  gram: a list of 2 to 512 different ports -- keep the
         Gram records in last_gram ([blocks, P (P + 1) / 2] float64; one-shard engines only; None: off).  tapfits: a list of (target port,
         [term ports], taps) -- keep the tap-fit records in last_tapfit ([blocks, D] float64; one-shard engines only; None: off).  transfers:
-        ([(port, target), ...], group) -- keep the transfer records in last_transfer ([blocks, pairs x G x 4] float64; one-shard engines only; None: off)."""
+        ([(port, target), ...], group) -- keep the transfer records in last_transfer ([blocks, pairs x G x 4] float64; one-shard engines only; None: off).
+        deliver: 2 or 4 -- every output at a half or a quarter of the session rate (Engine::SetBatchDelivery; one-shard engines only; None
+        or 1: off): each data section then has length // deliver samples and lags the render by 38 or 77 session samples.  Every last_*
+        record stays that of the session-rate render, so a delivered file's true peak can differ from last_true_peak: the anti-aliasing
+        filter removes what lies above the new Nyquist frequency, and it rings."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_trim(trim)
+        R = self._set_delivery(deliver)
         nb = self._set_blends(blends, blend_gain)            # before the alignment list, which may name blend ports
         fitted = self._set_fits(fits)
         grammed = self._set_gram(gram)
@@ -750,7 +765,7 @@ class Engine:
             if count > 0:
                 length = max(length, self.raw_context(g).batch_length(inputs[first:first + count], target_rate))
         no = n + 3 + nb
-        outs = None if skip_outputs else [np.zeros(length * wo, dtype=np.uint8) for _ in range(no)]
+        outs = None if skip_outputs else [np.zeros(length // R * wo, dtype=np.uint8) for _ in range(no)]
         ptrs = (C.c_void_p * no)(*([None] * no if skip_outputs else [(o.ctypes.data if o.size else None) for o in outs]))
         samples = C.c_size_t(0)
         _err(lib().gdgh_engine_batch_run(self._h, arr, n, C.byref(opt), window, ptrs, C.byref(samples)))
@@ -774,16 +789,17 @@ class Engine:
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces (and one per blend of blends= / blend_gain=, as batch_run's).  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]; fits=: last_fit likewise,
-        [fits, blocks]; gram=: last_gram likewise, [blocks, P (P + 1) / 2]; tapfits=: last_tapfit likewise, [blocks, D]."""
+        [fits, blocks]; gram=: last_gram likewise, [blocks, P (P + 1) / 2]; tapfits=: last_tapfit likewise, [blocks, D].  deliver=: as
+        batch_run's -- every piece has blocks * 8192 // deliver samples; the records stay those of the session-rate render."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
                                   metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
-                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits, transfers=transfers)
+                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits, transfers=transfers, deliver=deliver)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -808,13 +824,14 @@ class Engine:
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_trim(trim)
+        R = self._set_delivery(deliver)                      # the sharded form passes none: off
         nb = self._set_blends(blends, blend_gain)            # the sharded form passes none: off
         fitted = self._set_fits(fits)                        # ... and no fits
         grammed = self._set_gram(gram)                       # ... and no Gram list
@@ -856,7 +873,7 @@ class Engine:
                 _err(f_need(self._h, blocks, first, count))
                 pieces = [None if datas[i] is None or not count[i] else datas[i][first[i] * widths[i]:(first[i] + count[i]) * widths[i]] for i in range(n)]
                 ins = (C.c_void_p * n)(*[(p.ctypes.data if p is not None else None) for p in pieces])
-                outs = [np.zeros(blocks * 8192 * wo, dtype=np.uint8) for _ in range(n + 3 + nb)]
+                outs = [np.zeros(blocks * 8192 // R * wo, dtype=np.uint8) for _ in range(n + 3 + nb)]
                 ptrs = (C.c_void_p * (n + 3 + nb))(*[o.ctypes.data for o in outs])
                 _err(f_step(self._h, blocks, ins, ptrs))
                 if report:

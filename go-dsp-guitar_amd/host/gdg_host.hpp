@@ -285,6 +285,13 @@ public:
      * a later LoadState finds, also on an engine that has not processed yet (the two-pass render saves before its first pass) */
     Error SyncChains(uint32_t sampleRate);
     Error SetBatchTrim(const std::vector<double> &chainGain, double masterLeft = 1.0, double masterRight = 1.0, double metronome = 1.0);
+    /* No reference counterpart.  The delivery (include/gdg.h, gdg_batch_set_delivery): from the next job on BatchRun and the plain streamed
+     * job write every port at 1 / factor of the session rate (factor 1: off, 2 or 4) -- `outs` of samples / factor samples each -- through
+     * the reference's decimator on the finished float64 rows.  Records stay those of the session-rate render.  One-shard engines only: the
+     * library's shard and master-finish calls refuse a factor, so an engine of more shards refuses it here, as it does blends; a factor
+     * other than 1, 2, 4 is refused and the factor in force stays.  The checkpoint calls refuse while a factor is in force. */
+    Error SetBatchDelivery(int factor);
+    int BatchDelivery() const { return delivery_; }
     /* No reference counterpart.  The blend outputs (include/gdg.h, gdg_batch_set_blends): blend b is the weighted sum of its terms -- (job
      * channel, weight) pairs, 1 to 32 of them -- over the chain outputs, in term order, and port N + 3 + b of BatchRun and the plain streamed
      * job; gain: one output gain per blend, or none (every gain 1).  While blends are in force every call's `outs` and every Last* record
@@ -395,6 +402,7 @@ private:
     uint64_t ditherSeed_ = 0;
     int applyDither(int shard, gdg_ctx *ctx);              /* mode, seed and the shard's port_base onto its context: a gdg_* status */
     std::vector<double> trim_;                             /* SetBatchTrim: N chain gains, master left, master right, metronome; empty: off */
+    int delivery_ = 1;                                     /* SetBatchDelivery: 1 = off; never another value on an engine of several shards */
     int applyTrim(int shard, gdg_ctx *ctx);                /* the shard's slice of it onto its context: a gdg_* status */
     std::vector<int> blendFirst_, blendChannel_;           /* SetBatchBlends, in gdg_batch_set_blends' CSR form; blendFirst_ empty: off */
     std::vector<double> blendWeight_, blendGain_;
@@ -423,7 +431,7 @@ private:
     bool transferValid_ = false;
     int applyTransfers(gdg_ctx *ctx);                      /* onto a context (more shards: none is in force): a gdg_* status */
     int applyTapFits(gdg_ctx *ctx);                        /* onto a context (more shards: none are in force): a gdg_* status */
-    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0; }      /* BatchRun is the library's plain one-call run */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivery_ > 1; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

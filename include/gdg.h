@@ -1542,6 +1542,62 @@ int gdg_block_transfer_rows_device(gdg_ctx *ctx, const double *d_rows, size_t ro
                                    int group, double *d_records);
 size_t gdg_transfer_doubles(int n_pairs, int group);
 int gdg_match_taps_from_transfer(const double *records, int n_pairs, int group, size_t blocks, double ridge, int n_taps, int center, double *tap, double *coherence);
+/*
+ * DELIVERY: the batch calls render at the session rate -- 192 kHz serves the non-linear units -- and the deliverable is a half or a quarter
+ * of it (48 kHz from 192, 96 from 192, 44.1 from 88.2 or 176.4).  With a delivery factor in force every encoded port leaves the device at
+ * the delivered rate, decimated from the finished float64 rows as they lie on the device: a quarter of the bytes come down and are scattered,
+ * and nothing is decimated on a CPU afterwards.
+ *   gdg_batch_set_delivery(ctx, factor)                factor 1 (off), 2 or 4
+ *   gdg_batch_delivery(ctx)                            the factor in force (1: off, or never set)
+ *   gdg_batch_delivery_latency(factor)                 session samples a delivered port lags the render by: 0, 38, 77 (anything else: 0)
+ * GDG_ERR_INVALID, with gdg_last_error naming the delivery factor, and the factor in force unchanged: a factor other than 1, 2, 4; a call
+ * while a streamed job is open.
+ * DEFINITION -- oversampling.Decimate (oversampling/oversampling.go:126-184: a causal anti-aliasing FIR, every factor-th sample, times
+ * ATTENUATION_HALF_DECIBEL) without the clip to [-1, 1] the reference's filter applies to its output; the encoders clip.  Factor R; T = 77 taps
+ * for R = 2 and 155 for R = 4; h the expanded symmetric table (oversampling.go:239-317, :357-513; gdg_deliver_taps hands it out);
+ * A = 0.9440608762859234.  For a port's row x over the WHOLE JOB, with x[n] = 0 for n < 0:
+ *   f = h[0] * x[R i]
+ *   f = f + (h[k] * x[R i - k])                        for k = 1 .. T - 1, in ascending order
+ *   y[i] = A * f
+ * every product and every add an IEEE-754 double operation rounded on its own: no fused multiply-add, and the symmetric taps are not folded.
+ * A delivered port has samples / R samples and lags the render by (T - 1) / 2 session samples (38 and 77).
+ * Known answers: an impulse 1.0 at sample 0 gives y[i] = A * h[R i]; an impulse at sample 1 gives y[i] = A * h[R i - 1] (y[0] = +0.0);
+ * silence gives exactly +0.0 everywhere.
+ * OFF: factor 1, or never set.  Off, no launch, allocation, buffer or byte differs from a context that never heard of the call; option
+ * stat_batch_device_kib is unchanged.
+ * WHERE: gdg_batch_run and gdg_batch_stream_step: every encoded port -- the N chain outputs, master left, master right, metronome, the blends.
+ * Each out_bytes buffer is gdg_batch_length() / R * width bytes; a streamed slice of b blocks writes b * 8192 / R samples to each.
+ * ORDER: decimate, then the gain (gdg_batch_set_trim, a blend's output gain) times the delivered sample, then the plain or the dithered
+ * encoder.  The dither's sample index is the delivered sample's index in the job: (the step's first session sample) / R + i.
+ * STATE: the last 154 session samples of every port, kept on the device from step to step and from slice to slice: the bytes do not depend on
+ * the window or on how a stream is sliced.  Zeroed when a job starts; freed when the factor returns to 1.
+ * WHAT STAYS AT THE SESSION RATE: the float64 rows, the master mix, the meters, the tuner, and EVERY record kind -- report, spectrum,
+ * alignment, true peak, fits, Gram, tap fits, transfer: they describe the render.  A delivered file's true peak can differ from the render's
+ * record (the filter removes what lies above the new Nyquist frequency and rings); the stand-alone record calls can be run on delivered rows.
+ * GDG_ERR_UNSUPPORTED while a factor other than 1 is in force, gdg_last_error naming the delivery factor: gdg_batch_stream_checkpoint,
+ * gdg_batch_stream_checkpoint_size and the resume calls (the history is not in the version-1 container, as the blend history is not);
+ * gdg_batch_run_shard, gdg_batch_stream_open_shard, gdg_batch_stream_step_shard; gdg_batch_finish_master, gdg_batch_finish_master_slice.
+ * Configuration, like gdg_batch_set_trim: it holds from the next batch call on, survives batch calls and is part of no blob.
+ * The operation on its own:
+ *   gdg_deliver_rows(ctx, rows, n_rows, samples, factor, history, out)                                   host buffers, blocking
+ *   gdg_deliver_rows_device(ctx, d_rows, row_stride, n_rows, samples, factor, d_history, d_out, out_stride)   enqueued on gdg_ctx_stream
+ *                                                      rows: [n_rows][samples] (device: row r at d_rows + r * row_stride); out:
+ *                                                      [n_rows][samples / factor] (device: out_stride apart).  samples: any positive
+ *                                                      multiple of factor.  history: NULL (zeros in front of sample 0) or [n_rows][154]
+ *                                                      doubles, the session samples in front of the call, the newest last; read before and
+ *                                                      written after (the call's last 154 samples; a call of fewer moves the old ones up),
+ *                                                      so consecutive calls continue a stream.  Factor 1 copies.  Nothing outside
+ *                                                      [row, row + samples / factor) of out is written.
+ *   gdg_deliver_taps(factor, taps, capacity)           the expanded table h: writes min(T, capacity) doubles (taps may be NULL), returns T
+ *                                                      (0 for a factor without a filter); pure host arithmetic
+ */
+int gdg_batch_set_delivery(gdg_ctx *ctx, int factor);
+int gdg_batch_delivery(const gdg_ctx *ctx);
+int gdg_batch_delivery_latency(int factor);
+int gdg_deliver_rows(gdg_ctx *ctx, const double *rows, int n_rows, size_t samples, int factor, double *history, double *out);
+int gdg_deliver_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int factor, double *d_history, double *d_out,
+                            size_t out_stride);
+int gdg_deliver_taps(int factor, double *taps, int capacity);
 
 #ifdef __cplusplus
 
