@@ -63,6 +63,8 @@ ABI_SYMBOLS = [
     "gdg_batch_transfer_enable", "gdg_batch_transfers", "gdg_batch_transfer", "gdg_block_transfer_rows", "gdg_block_transfer_rows_device", "gdg_transfer_doubles",
     "gdg_match_taps_from_transfer",
     "gdg_batch_set_delivery", "gdg_batch_delivery", "gdg_batch_delivery_latency", "gdg_deliver_rows", "gdg_deliver_rows_device", "gdg_deliver_taps",
+    "gdg_batch_set_out_ratio", "gdg_batch_out_ratio", "gdg_batch_out_samples", "gdg_batch_out_ratio_latency", "gdg_out_ratio_taps",
+    "gdg_out_ratio_rows", "gdg_out_ratio_rows_device",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -314,6 +316,29 @@ def deliver_taps(factor):
     if n:
         lib().gdg_deliver_taps(int(factor), out.ctypes.data, n)
     return out
+
+
+DELIVER_RATIO_HISTORY = 127  # GDG_DELIVER_RATIO_HISTORY (include/gdg.h, DELIVERY): the intermediate samples the ratio stage keeps from call to call
+
+
+def batch_delivery_samples(factor, up, down, first, count):
+    """gdg_batch_out_samples: the delivered samples the session samples [first, first + count) produce at factor and ratio up / down
+    (both multiples of factor; 0 for anything inadmissible): what an out_bytes buffer is sized with, per job and per streamed slice."""
+    return int(lib().gdg_batch_out_samples(int(factor), int(up), int(down), int(first), int(count)))
+
+
+def batch_delivery_ratio_latency(factor, up, down):
+    """gdg_batch_out_ratio_latency: the session samples a port delivered at factor and ratio up / down lags the render by."""
+    return int(lib().gdg_batch_out_ratio_latency(int(factor), int(up), int(down)))
+
+
+def deliver_ratio_taps(up, down):
+    """gdg_out_ratio_taps: the ratio stage's table tap[up][T] (float64), tap[p][t] = g[p + t up]; empty for an inadmissible ratio and for 1/1."""
+    n = int(lib().gdg_out_ratio_taps(int(up), int(down), None, 0))
+    out = np.zeros(n, dtype=np.float64)
+    if n:
+        lib().gdg_out_ratio_taps(int(up), int(down), out.ctypes.data, n)
+    return out.reshape(int(up), n // int(up)) if n else out
 
 
 def transfer_doubles(n_pairs, group):
@@ -630,6 +655,13 @@ def lib():
             "gdg_deliver_rows": (i32, [vp, vp, i32, C.c_size_t, i32, vp, vp]),
             "gdg_deliver_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, vp, vp, C.c_size_t]),
             "gdg_deliver_taps": (i32, [i32, vp, i32]),
+            "gdg_batch_set_out_ratio": (i32, [vp, i32, i32, i32]),
+            "gdg_batch_out_ratio": (i32, [vp, vp, vp]),
+            "gdg_batch_out_samples": (C.c_size_t, [i32, i32, i32, C.c_size_t, C.c_size_t]),
+            "gdg_batch_out_ratio_latency": (i32, [i32, i32, i32]),
+            "gdg_out_ratio_taps": (i32, [i32, i32, vp, i32]),
+            "gdg_out_ratio_rows": (i32, [vp, vp, i32, C.c_size_t, i32, i32, C.c_size_t, vp, vp, C.c_size_t]),
+            "gdg_out_ratio_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, i32, C.c_size_t, vp, vp, C.c_size_t]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1082,7 +1114,7 @@ class Context:
         length = C.c_size_t(0)
         self._check(lib().gdg_batch_length(self._h, arr, n, target_rate, C.byref(length)))
         wo = lib().gdg_wave_bytes_per_sample(fo)
-        size = length.value // self.batch_delivery() * wo      # every port at the delivered rate (batch_set_delivery)
+        size = self._delivered(0, length.value) * wo          # every port at the delivered rate (batch_set_delivery, batch_set_delivery_ratio)
         if outs is None:
             outs = [np.zeros(size, dtype=np.uint8) for _ in range(no)]
         assert len(outs) == no and all(o.dtype == np.uint8 and o.size == size for o in outs)
@@ -1101,7 +1133,7 @@ class Context:
         self._check(lib().gdg_batch_length(self._h, arr, n, target_rate, C.byref(length)))
         wo = lib().gdg_wave_bytes_per_sample(fo)
         no = n + 3 + self.batch_blends()                # the blends in force when the call is prepared
-        outs = [np.zeros(length.value // self.batch_delivery() * wo, dtype=np.uint8) for _ in range(no)]      # ... and the delivery factor
+        outs = [np.zeros(self._delivered(0, length.value) * wo, dtype=np.uint8) for _ in range(no)]      # ... and the delivery in force
         ptrs = (C.c_void_p * no)(*[(o.ctypes.data if o.size else None) for o in outs])
         fn, h, ref = lib().gdg_batch_run, self._h, C.byref(opt)
 
@@ -1206,6 +1238,7 @@ class Context:
         length = C.c_size_t(0)
         self._check(lib().gdg_batch_stream_open(self._h, arr, n, C.byref(opt), C.byref(length)))
         self._stream_width = lib().gdg_wave_bytes_per_sample(fo)
+        self._stream_done = 0                           # session samples of the slices so far: what a ratio counts a slice's samples from
         return length.value
 
     def batch_stream_need(self, blocks):
@@ -1217,19 +1250,21 @@ class Context:
 
     def batch_stream_step(self, blocks, in_bytes, outs=None):
         """One slice: in_bytes[i] = the interleaved frames batch_stream_need asked for (bytes-like or None); returns the N + 3 output
-        pieces of blocks * 8192 samples each (uint8 arrays), and one per blend in force behind them."""
+        pieces of blocks * 8192 samples each (uint8 arrays), and one per blend in force behind them.  With a delivery in force a piece has
+        batch_delivery_samples(factor, up, down, <session samples of the slices before>, blocks * 8192) samples."""
         n = self.n_channels
         no = n + 3 + self.batch_blends()
         keep = [None if b is None else np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b, dtype=np.uint8)
                 for b in in_bytes]
         assert len(keep) == n
         ins = (C.c_void_p * n)(*[(b.ctypes.data if b is not None and b.size else None) for b in keep])
-        size = blocks * 8192 // self.batch_delivery() * self._stream_width
+        size = self._delivered(getattr(self, "_stream_done", 0), blocks * 8192) * self._stream_width
         if outs is None:
             outs = [np.zeros(size, dtype=np.uint8) for _ in range(no)]
         assert len(outs) == no and all(o is None or (o.dtype == np.uint8 and o.size == size) for o in outs)
         ptrs = (C.c_void_p * no)(*[(o.ctypes.data if o is not None else None) for o in outs])
         self._check(lib().gdg_batch_stream_step(self._h, blocks, ins, ptrs))
+        self._stream_done = getattr(self, "_stream_done", 0) + blocks * 8192
         return outs
 
     def batch_stream_close(self):
@@ -1276,6 +1311,7 @@ class Context:
         done = C.c_size_t(0)
         self._check(lib().gdg_batch_stream_resume(self._h, arr, n, C.byref(opt), blob, len(blob), C.byref(done)))
         self._stream_width = lib().gdg_wave_bytes_per_sample(fo)
+        self._stream_done = done.value
         return done.value
 
     def batch_stream_resume_shard(self, inputs, target_rate, out_format, blob, job_samples=0, metronome=False, run_meters=False,
@@ -1814,6 +1850,51 @@ class Context:
         """gdg_deliver_rows_device on plain device pointers (ints; d_history 0 or None: zeros in front), enqueued on the context's stream."""
         self._check(lib().gdg_deliver_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(factor), d_history or None, d_out, out_stride))
 
+    def _delivered(self, first, count):
+        """the delivered samples of the session samples [first, first + count) under the factor and ratio in force"""
+        up, down = self.batch_delivery_ratio()
+        return batch_delivery_samples(self.batch_delivery(), up, down, first, count)
+
+    def batch_set_delivery_ratio(self, factor, up, down):
+        """From the next batch call on every port leaves at (session rate / factor) * up / down (gdg_batch_set_out_ratio): the factor's
+        decimator, then the polyphase ratio stage, in front of the encoders; 44.1 kHz from 192 is (4, 147, 160).  up / down reduced,
+        1 <= up <= 160, 1 <= down <= 320, within a factor of two of 1; (factor, 1, 1) is batch_set_delivery(factor).  Each output of a job
+        has batch_delivery_samples(factor, up, down, 0, length) samples.  Refused while a streamed job is open; the checkpoint, shard and
+        finish_master calls refuse while a ratio is in force."""
+        self._check(lib().gdg_batch_set_out_ratio(self._h, int(factor), int(up), int(down)))
+
+    def batch_delivery_ratio(self):
+        """(up, down) of the delivery ratio in force (gdg_batch_out_ratio): (1, 1) = none."""
+        up, down = C.c_int(1), C.c_int(1)
+        lib().gdg_batch_out_ratio(self._h, C.byref(up), C.byref(down))
+        return up.value, down.value
+
+    def deliver_rows_ratio(self, rows, up, down, first=0, history=None):
+        """gdg_out_ratio_rows: rows [n_rows, samples] float64 (or one 1-D row), the intermediate samples [first, first + samples) of a
+        job -> [n_rows, ceil((first + samples) up / down) - ceil(first up / down)].  history: None (zeros in front of the call) or a
+        C-contiguous [n_rows, 127] float64 array, read before and UPDATED IN PLACE after, so consecutive calls with advancing first continue
+        a stream."""
+        x = np.ascontiguousarray(rows, dtype=np.float64)
+        one = x.ndim == 1
+        if one:
+            x = x[None, :]
+        n, samples = x.shape
+        up, down, first = int(up), int(down), int(first)
+        if history is not None:
+            assert isinstance(history, np.ndarray) and history.dtype == np.float64 and history.flags.c_contiguous and history.size == n * DELIVER_RATIO_HISTORY
+        n_out = samples if (up, down) == (1, 1) else batch_delivery_samples(1, up, down, first, samples)
+        out = np.zeros((n, n_out), dtype=np.float64)
+        self._check(lib().gdg_out_ratio_rows(self._h, x.ctypes.data if x.size else None, n, samples, up, down, first, None if history is None else history.ctypes.data,
+                                                 out.ctypes.data if out.size else None, n_out))
+        return out[0] if one else out
+
+    def deliver_rows_ratio_device(self, d_rows, row_stride, n_rows, samples, up, down, first, d_history, d_out, out_stride):
+        """gdg_out_ratio_rows_device on plain device pointers (ints; d_history 0 or None: zeros in front), enqueued on the context's stream."""
+        self._check(lib().gdg_out_ratio_rows_device(self._h, d_rows, row_stride, n_rows, samples, int(up), int(down), int(first), d_history or None, d_out, out_stride))
+
+    batch_delivery_samples = staticmethod(batch_delivery_samples)
+    batch_delivery_ratio_latency = staticmethod(batch_delivery_ratio_latency)
+    deliver_ratio_taps = staticmethod(deliver_ratio_taps)
     batch_delivery_latency = staticmethod(batch_delivery_latency)
     deliver_taps = staticmethod(deliver_taps)
     match_taps_from_transfer = staticmethod(match_taps_from_transfer)

@@ -132,6 +132,12 @@ struct BatchLoop {
     int deliver;
     double *d_delivered, *d_deliver_history;
     const double *d_deliver_taps;
+    /* ... and the ratio behind it (0 / 0 or 1 / 1 = off, and always for a shard): the rows behind the ratio stage, [NR][ratio_stride], which the
+     * encoders then read, the ratio's [T][up] table on the device and the intermediate rows' history [NR][127] */
+    int ratio_up, ratio_down;
+    double *d_ratio_rows, *d_ratio_history;
+    const double *d_ratio_taps;
+    size_t ratio_stride;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -160,6 +166,10 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     const int N = p.N, NO = N + 3, NR = NO + p.n_blends, B = GDG_BLOCK_SIZE, enc_rows = p.enc_rows, f64_rows = p.f64_rows, out_width = p.out_width, W = p.W;
     const size_t length = p.length, ws = p.ws, enc_bytes = p.enc_bytes;
     const int R = p.deliver > 1 ? p.deliver : 1;                              /* the delivery factor: every byte count below is of the delivered length (deliver.h) */
+    const int RL = p.ratio_up > 0 ? p.ratio_up : 1, RM = p.ratio_down > 0 ? p.ratio_down : 1;      /* ... and the ratio behind it; 1 / 1: none */
+    const bool ratio = gdg_deliver_ratio_on(RL, RM);
+    /* a step's delivered rows: the loop begins at session sample p.dither_first of its job, and a ratio counts in job indices */
+    auto step_of = [&](size_t w, size_t off, size_t rows) { return deliver_ratio_step(w, off, (size_t)p.dither_first, R, RL, RM, (size_t)out_width, rows); };
     double *const d_inputs = p.d_inputs, *const d_win = p.d_win;
     unsigned char *const d_enc = p.d_enc;
     const gdg_batch_options *opt = p.opt;
@@ -193,7 +203,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; behind them one section per live kind of the render
      * report, [rows][w] -- N + 3 rows and the blends', a shard's N chain rows and the metronome's -- which come down with the last piece */
     auto down_bytes = [&](size_t i) {
-        const size_t wb = (size_t)steps[i].w * B, row_bytes = deliver_step((size_t)steps[i].w, steps[i].off, R, (size_t)out_width, 0).row_bytes;
+        const size_t wb = (size_t)steps[i].w * B, row_bytes = step_of((size_t)steps[i].w, steps[i].off, 0).row_bytes;
         return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
     };
     const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NR;
@@ -223,7 +233,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     auto chunk_rows = [&](size_t i, int c) { return deliver_chunk_row((size_t)enc_rows, c, chunks_of(i)); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
         const unsigned char *src = ctx->h_batch[i & 1];
-        const DeliverStep ds = deliver_step((size_t)steps[i].w, steps[i].off, R, (size_t)out_width, (size_t)enc_rows);
+        const DeliverStep ds = step_of((size_t)steps[i].w, steps[i].off, (size_t)enc_rows);
         const size_t wb = (size_t)steps[i].w * B, row_bytes = ds.row_bytes, at = ds.file_at;
         const size_t f64_at = ((size_t)enc_rows * row_bytes + 15) & ~(size_t)15;
         const int K = chunks_of(i);
@@ -234,7 +244,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 if (o < (size_t)enc_rows) {
                     /* NULL: "skipping output" (:3143); a shard's row N is the metronome track */
                     void *dst = (sharded && o == (size_t)N) ? shard->metronome_bytes : out_bytes[o];
-                    if (dst) memcpy(static_cast<unsigned char *>(dst) + at, src + o * row_bytes, row_bytes);
+                    if (dst) memcpy(static_cast<unsigned char *>(dst) + at, src + o * row_bytes, ds.copy_bytes);      /* without a ratio the whole row; with one its samples, not the pad */
                 } else {
                     const size_t k = o - (size_t)enc_rows;
                     double *dst = k == 0 ? shard->master_left : (k == 1 ? shard->master_right : shard->metronome);
@@ -281,7 +291,8 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_moved[h], 0));     /* step i - 2 has left enc */
         {
             ProfScope ps(ctx, GDG_K_WAVE);
-            const size_t row_bytes = deliver_step((size_t)w, off, R, (size_t)out_width, 0).row_bytes;
+            const DeliverStep ds = step_of((size_t)w, off, 0);
+            const size_t row_bytes = ds.row_bytes;
             const ReportSections &sec = steps[i].sec;
             /* the blend rows, behind the metronome's: sums of the chain rows, which are final; every reader below takes them as rows like the others */
             if (p.n_blends) {
@@ -322,10 +333,12 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                                                        enc + steps[i].transfer.at, ctx->stream));
             /* dither on: n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
+            /* delivered: the rows are the scratch rows' -- a row enc_stride apart (ws / R, behind a ratio its fixed pitch), ds.pitch samples of it (wb / R,
+             * behind a ratio the step's count rounded up to four) -- and a sample's index is its index in the delivered job */
+            const size_t enc_stride = ratio ? p.ratio_stride : ws / (size_t)R;
             auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
-                /* delivered: the rows are the scratch rows' -- a row ws / R apart, wb / R samples of it -- and a sample's index is its index in the delivered job */
-                const gdg_encode_mode m = { gains != nullptr, p.dither, gains, { 1.0, 1.0 }, { ctx->dither_seed, (p.dither_first + off) / (uint64_t)R, port_base, n_chain } };
-                return gdg_launch_wave_encode_rows(opt->out_format, rows, ws / (size_t)R, (size_t)wb / (size_t)R, n_rows, dst, m, ctx->stream);
+                const gdg_encode_mode m = { gains != nullptr, p.dither, gains, { 1.0, 1.0 }, { ctx->dither_seed, (uint64_t)ds.first_out, port_base, n_chain } };
+                return gdg_launch_wave_encode_rows(opt->out_format, rows, enc_stride, ds.pitch, n_rows, dst, m, ctx->stream);
             };
             /* the delivery: the window's NR rows, final by now and read by every record above as they are, decimated into the scratch rows -- the
              * samples in front of the step come from the history, which this step's tail replaces behind the launch and before the next step
@@ -336,11 +349,19 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 HIP_TRY(ctx, gdg_launch_deliver_history_save(d_win, ws, (size_t)wb, (unsigned)NR, p.d_deliver_history, ctx->stream));
                 enc_src = p.d_delivered;
             }
+            /* ... and the ratio behind the factor: the intermediate rows (the window's at factor 1, the scratch rows otherwise) resampled into rows
+             * of their own, +0.0 up to the pitch; their tail becomes the history before the next step writes them */
+            if (ratio) {
+                HIP_TRY(ctx, gdg_launch_deliver_ratio(RL, RM, enc_src, ws / (size_t)R, ds.inter_samples, (unsigned long long)ds.inter_first, (unsigned)NR, p.d_ratio_taps,
+                                                      p.d_ratio_history, p.d_ratio_rows, p.ratio_stride, ds.pitch, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_deliver_ratio_history_save(enc_src, ws / (size_t)R, ds.inter_samples, (unsigned)NR, p.d_ratio_history, ctx->stream));
+                enc_src = p.d_ratio_rows;
+            }
             if (!sharded) {
                 HIP_TRY(ctx, encode_rows(enc_src, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
                 /* a launch of their own: blend b is port port_base + N + 3 + b of the dither, and its gain is the blend's, not the trim's */
                 if (p.n_blends)
-                    HIP_TRY(ctx, encode_rows(enc_src + (size_t)NO * (ws / (size_t)R), (unsigned)p.n_blends, (unsigned)p.n_blends, ctx->dither_port_base + (uint32_t)NO,
+                    HIP_TRY(ctx, encode_rows(enc_src + (size_t)NO * enc_stride, (unsigned)p.n_blends, (unsigned)p.n_blends, ctx->dither_port_base + (uint32_t)NO,
                                              enc + (size_t)NO * row_bytes, p.d_blend_gain));
             } else {
                 HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
@@ -361,7 +382,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         const int h = (int)(i & 1);
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
-        const size_t row_bytes = deliver_step((size_t)steps[i].w, steps[i].off, R, (size_t)out_width, 0).row_bytes;
+        const size_t row_bytes = step_of((size_t)steps[i].w, steps[i].off, 0).row_bytes;
         const size_t down = steps[i].transfer.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
@@ -522,29 +543,54 @@ int gdg_batch_set_trim(gdg_ctx *ctx, const double *chain_gain, int n, double mas
     return GDG_OK;
 }
 
-/* the delivery factor: validated before it replaces the one in force (deliver.h); read by every call that encodes */
-int gdg_batch_set_delivery(gdg_ctx *ctx, int factor) {
+/* the delivery factor and the ratio behind it: validated before they replace the ones in force (deliver.h); read by every call that encodes */
+static int set_delivery(gdg_ctx *ctx, const char *what, int factor, int up, int down) {
     if (!ctx) return GDG_ERR_INVALID;
-    if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "set delivery: a streamed batch run is open on this context; its delivery factor %d holds until gdg_batch_stream_close", ctx->deliver);
-    if (!gdg_deliver_factor_ok(factor)) return fail(ctx, GDG_ERR_INVALID, "set delivery: delivery factor %d; 1 is the session rate, 2 a half of it, 4 a quarter", factor);
-    if (factor == ctx->deliver) return GDG_OK;
+    if (ctx->bstream.open) {
+        if (gdg_deliver_ratio_on(ctx->deliver_up, ctx->deliver_down))
+            return fail(ctx, GDG_ERR_INVALID, "%s: a streamed batch run is open on this context; its delivery factor %d and delivery ratio %d/%d hold until gdg_batch_stream_close", what,
+                        ctx->deliver, ctx->deliver_up, ctx->deliver_down);
+        return fail(ctx, GDG_ERR_INVALID, "%s: a streamed batch run is open on this context; its delivery factor %d holds until gdg_batch_stream_close", what, ctx->deliver);
+    }
+    if (!gdg_deliver_factor_ok(factor)) return fail(ctx, GDG_ERR_INVALID, "%s: delivery factor %d; 1 is the session rate, 2 a half of it, 4 a quarter", what, factor);
+    if (const int rc = deliver_ratio_check(ctx, what, up, down)) return rc;
+    if (factor == ctx->deliver && up == ctx->deliver_up && down == ctx->deliver_down) return GDG_OK;
+    std::vector<double> tapsT;
+    if (gdg_deliver_ratio_on(up, down)) deliver_ratio_table(up, down, true, tapsT);      /* the prototype, once, in float64 on the host */
     enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
     /* another row length: whatever still reads the encoded halves and the scratch rows has to be done before they go -- and a wait that fails
      * refuses the call with the factor in force untouched.  The halves are made anew by the next batch call, at the size of a context that
      * was always configured like this one; back at 1 the scratch rows and the history go as well (the next job with a factor begins from zeros anyway) */
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i : { (int)BATCH_ENCODED, (int)BATCH_DELIVERED, (int)BATCH_DELIVER_HISTORY }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    for (int i : { (int)BATCH_ENCODED, (int)BATCH_DELIVERED, (int)BATCH_DELIVER_HISTORY, (int)BATCH_DELIVER_RATIO_ROWS, (int)BATCH_DELIVER_RATIO_HISTORY, (int)BATCH_DELIVER_RATIO_TABLE }) {
+        hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0;
+    }
     ctx->deliver = factor;
+    ctx->deliver_up = up;
+    ctx->deliver_down = down;
+    ctx->deliver_tapsT.swap(tapsT);
     return GDG_OK;
 }
+int gdg_batch_set_delivery(gdg_ctx *ctx, int factor) { return set_delivery(ctx, "set delivery", factor, 1, 1); }
+int gdg_batch_set_out_ratio(gdg_ctx *ctx, int factor, int up, int down) { return set_delivery(ctx, "set delivery ratio", factor, up, down); }
 
 int gdg_batch_delivery(const gdg_ctx *ctx) { return ctx ? ctx->deliver : 1; }
 int gdg_batch_delivery_latency(int factor) { return gdg_deliver_latency(factor); }
+int gdg_batch_out_ratio(const gdg_ctx *ctx, int *up, int *down) {
+    if (up) *up = ctx ? ctx->deliver_up : 1;
+    if (down) *down = ctx ? ctx->deliver_down : 1;
+    return ctx ? GDG_OK : GDG_ERR_INVALID;
+}
 
-/* a shard's master mix is finished elsewhere, from float64 partials at the session rate, and the history is per context: the shard forms and
- * the finish calls refuse while a factor is in force (include/gdg.h) */
-#define DELIVERY_REFUSED(ctx, what) \
-    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d is in force on this context (gdg_batch_set_delivery); a sharded job cannot deliver at another rate yet", what, (ctx)->deliver)
+/* a shard's master mix is finished elsewhere, from float64 partials at the session rate, and the histories are per context: the shard forms and
+ * the finish calls refuse while a factor or a ratio is in force (include/gdg.h) */
+static int delivery_refused(gdg_ctx *ctx, const char *what) {
+    if (gdg_deliver_ratio_on(ctx->deliver_up, ctx->deliver_down))
+        return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d with the delivery ratio %d/%d is in force on this context (gdg_batch_set_out_ratio); a sharded job cannot deliver at another rate yet",
+                    what, ctx->deliver, ctx->deliver_up, ctx->deliver_down);
+    return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d is in force on this context (gdg_batch_set_delivery); a sharded job cannot deliver at another rate yet", what, ctx->deliver);
+}
+#define DELIVERY_REFUSED(ctx, what) delivery_refused(ctx, what)
 
 /* the blend outputs: validated whole before the list replaces the one in force (blend.h); read when a job is described and by every slice */
 int gdg_batch_set_blends_filtered(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const int *tap_first,
@@ -835,7 +881,7 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
 
 int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t job_samples,
                                 int run_metronome, size_t *samples) {
-    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_open_shard");
+    if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_open_shard")) return rc;
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
@@ -899,6 +945,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* the blends in force (never a shard's): NR rows of the window leave the device encoded, and every record kind has NR ports */
     const int n_blends = sharded ? 0 : ctx->blend.count(), NR = NO + n_blends;
     const int R = sharded ? 1 : ctx->deliver;                                    /* the delivery factor in force (never a shard's: its calls refuse it) */
+    const int RL = sharded ? 1 : ctx->deliver_up, RM = sharded ? 1 : ctx->deliver_down;      /* ... and the ratio behind it */
     report_begin(ctx, sharded ? N + 1 : NR, (size_t)blocks, true, n_blends);
     ListInForce lists[LIST_KINDS];                                               /* the lists in force; never a shard's: its calls refuse them */
     for (int k = 0; k < LIST_KINDS; k++) {
@@ -930,7 +977,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const gdg_spectrum_bands bands = live.on(REPORT_BANDS) ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), opt->target_rate) : gdg_spectrum_bands();
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
-    const size_t enc_bytes = ((deliver_window_bytes((size_t)W, R, (size_t)out_width, (size_t)enc_room) + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
+    const size_t enc_bytes = ((deliver_ratio_window_bytes((size_t)W, R, RL, RM, (size_t)out_width, (size_t)enc_room) + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
                            + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + list_room(lists[LIST_FIT].shape, (size_t)W)
                            + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W) + list_room(transfer.shape, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
@@ -1163,6 +1210,23 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             loop.deliver = R;
             loop.d_deliver_taps = R == 2 ? ctx->os.taps2 : ctx->os.taps4;       /* the oversampler's expanded tables (api_ctx.cpp) */
         }
+        /* ... and the ratio behind it: the rows the encoders then read, at the window's fixed pitch; the table, which goes up ahead of everything the
+         * slice enqueues; the history of the NR intermediate rows, zeroed by the job's first slice like the factor's */
+        if (gdg_deliver_ratio_on(RL, RM)) {
+            const size_t hist_bytes = (size_t)NR * GDG_DELIVER_RATIO_HISTORY * sizeof(double), table_bytes = ctx->deliver_tapsT.size() * sizeof(double);
+            const bool fresh = ctx->batch_dev_cap[BATCH_DELIVER_RATIO_HISTORY] < hist_bytes;
+            double *d_table = nullptr;
+            loop.ratio_stride = gdg_deliver_pitch(R, RL, RM, ws);
+            if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_ROWS, (size_t)NR * loop.ratio_stride * sizeof(double), (void **)&loop.d_ratio_rows)) != GDG_OK) return r;
+            if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_HISTORY, hist_bytes, (void **)&loop.d_ratio_history)) != GDG_OK) return r;
+            if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_TABLE, table_bytes, (void **)&d_table)) != GDG_OK) return r;
+            if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the delivery ratio's history of the open job is gone (gdg_batch_release between two slices?)");
+            if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_ratio_history, 0, hist_bytes, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->deliver_tapsT.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
+            loop.ratio_up = RL;
+            loop.ratio_down = RM;
+            loop.d_ratio_taps = d_table;
+        }
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -1203,7 +1267,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 }
 
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
-    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_step_shard");
+    if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_step_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_step_shard")) return rc;
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
@@ -1248,7 +1312,7 @@ int gdg_batch_run(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
 int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, void *const *out_bytes,
                         const gdg_batch_shard_out *shard) {
     if (!shard) return GDG_ERR_INVALID;
-    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_run_shard");
+    if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_run_shard");
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_run_shard")) return rc;
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
@@ -1402,7 +1466,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
 /* the master mix of a whole job: any sample count */
 int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                             size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
-    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master");
+    if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master");
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes, 0);      /* the cursor stays */
@@ -1411,7 +1475,7 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
 /* ... and of one slice of a streamed sharded job, where it runs once per slice on the job's critical path: whole blocks, as the slices are */
 int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                                   size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
-    if (ctx && ctx->deliver > 1) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master_slice");
+    if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master_slice");
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);

@@ -107,9 +107,13 @@ static int checkpoint_plan(gdg_ctx *ctx, CkptPlan &P) {
     fail(ctx, GDG_ERR_UNSUPPORTED, "%s: a blend term reaches up to %d samples back (gdg_batch_set_blends_delayed, gdg_batch_set_blends_filtered); the blend history is not in the version-1 container", what, \
          (ctx)->blend.max_reach())
 /* ... nor of the delivery history (gdg_batch_set_delivery): the window rows' last 154 samples, which the next step's first outputs read */
-#define DELIVERY_HISTORY_REFUSED(ctx, what) \
-    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d is in force on this context (gdg_batch_set_delivery); the delivery history is not in the version-1 container", what, \
-         (ctx)->deliver)
+static int delivery_history_refused(gdg_ctx *ctx, const char *what) {
+    if (gdg_deliver_ratio_on(ctx->deliver_up, ctx->deliver_down))
+        return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d with the delivery ratio %d/%d is in force on this context (gdg_batch_set_out_ratio); the delivery histories are not in the version-1 container",
+                    what, ctx->deliver, ctx->deliver_up, ctx->deliver_down);
+    return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d is in force on this context (gdg_batch_set_delivery); the delivery history is not in the version-1 container", what, ctx->deliver);
+}
+#define DELIVERY_HISTORY_REFUSED(ctx, what) delivery_history_refused(ctx, what)
 static bool input_has_samples(const gdg_batch_input &in) { return in.bytes && in.samples_per_channel; }
 /* the frames of input i's carry that hold source frames: what the next step of the job will read from it (api_batch.cpp, stream_step) */
 static uint32_t carry_valid(const gdg_ctx::BatchStreamState &S, size_t i) {
@@ -122,7 +126,7 @@ int gdg_batch_stream_checkpoint_size(gdg_ctx *ctx, size_t *bytes) {
     if (!ctx || !bytes) return GDG_ERR_INVALID;
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, "checkpoint");
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
-    if (ctx->deliver > 1) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
+    if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
     if (!ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     const int rc = checkpoint_plan(ctx, P);
@@ -135,7 +139,7 @@ int gdg_batch_stream_checkpoint(gdg_ctx *ctx, void *blob, size_t capacity, size_
     const auto &S = ctx->bstream;
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, "checkpoint");
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
-    if (ctx->deliver > 1) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
+    if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
     if (!S.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     int rc = checkpoint_plan(ctx, P);
@@ -272,7 +276,7 @@ static int resume(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
     const char *what = shard ? "resume (shard)" : "resume";
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, what);
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, what);
-    if (ctx->deliver > 1) return DELIVERY_HISTORY_REFUSED(ctx, what);
+    if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, what);
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "%s: a streamed batch run is already open on this context", what);
     CkptHeader h;
     int rc = read_header(ctx, what, blob, bytes, h);

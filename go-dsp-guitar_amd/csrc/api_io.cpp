@@ -213,6 +213,131 @@ int gdg_deliver_taps(int factor, double *taps, int capacity) {
     return T;
 }
 
+/* the ratio stage's prototype (include/gdg.h, DELIVERY): a Kaiser-windowed sinc of L T taps, beta 10, cut off at the Nyquist frequency of the
+ * lower rate, gain L; float64 on the host.  I0 by its power series: the terms fall below 1e-17 of the sum within 40 steps at x <= 10. */
+static double deliver_i0(double x) {
+    double sum = 1.0, term = 1.0;
+    const double q = 0.25 * x * x;
+    for (int k = 1; k < 200; k++) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+int deliver_ratio_table(int up, int down, bool transposed, std::vector<double> &taps) {
+    const int T = gdg_deliver_ratio_tap_count(up, down), L = up;
+    taps.clear();
+    if (!T) return 0;
+    const double pi = 3.14159265358979323846, beta = 10.0, fc = 0.5 / (double)(up > down ? up : down), c = 0.5 * (double)L * (double)T, i0b = deliver_i0(beta);
+    taps.resize((size_t)L * (size_t)T);
+    for (int m = 0; m < L * T; m++) {
+        const double u = (double)m - c, v = 2.0 * fc * u, r = u / c, inside = 1.0 - r * r;
+        const double sinc = v == 0.0 ? 1.0 : sin(pi * v) / (pi * v);
+        const double g = (double)L * 2.0 * fc * sinc * deliver_i0(beta * sqrt(inside > 0.0 ? inside : 0.0)) / i0b;
+        const int p = m % L, t = m / L;                                        /* tap[p][t] = g[p + t L] */
+        taps[transposed ? (size_t)t * (size_t)L + (size_t)p : (size_t)p * (size_t)T + (size_t)t] = g;
+    }
+    return T;
+}
+
+int gdg_out_ratio_taps(int up, int down, double *taps, int capacity) {
+    std::vector<double> g;
+    if (!deliver_ratio_table(up, down, false, g)) return 0;
+    for (size_t k = 0; taps && capacity > 0 && k < g.size() && k < (size_t)capacity; k++) taps[k] = g[k];
+    return (int)g.size();
+}
+
+size_t gdg_batch_out_samples(int factor, int up, int down, size_t first, size_t count) {
+    if (!gdg_deliver_factor_ok(factor) || !gdg_deliver_ratio_ok(up, down) || first % (size_t)factor || count % (size_t)factor) return 0;
+    return (size_t)gdg_deliver_samples(factor, up, down, first, count);
+}
+
+int gdg_batch_out_ratio_latency(int factor, int up, int down) { return gdg_deliver_ratio_latency(factor, up, down); }
+
+/* what every call refuses of a ratio, in one wording: the reduced pair is named where the caller's is not reduced */
+int deliver_ratio_check(gdg_ctx *ctx, const char *what, int up, int down) {
+    if (gdg_deliver_ratio_ok(up, down)) return GDG_OK;
+    if (up >= 1 && down >= 1) {
+        const int g = (int)gdg_deliver_gcd((unsigned long long)up, (unsigned long long)down);
+        if (g > 1) return fail(ctx, GDG_ERR_INVALID, "%s: delivery ratio %d/%d is not reduced; pass %d/%d", what, up, down, up / g, down / g);
+    }
+    return fail(ctx, GDG_ERR_INVALID, "%s: delivery ratio %d/%d; up is 1 to %d, down 1 to %d, down <= 2 up and up <= 2 down", what, up, down, GDG_DELIVER_RATIO_MAX_UP,
+                GDG_DELIVER_RATIO_MAX_DOWN);
+}
+
+/* the ratio stage on its own (io.hip, deliver_ratio_kernels.h): intermediate rows, the job's [first, first + samples) -> their outputs */
+static int deliver_ratio_args(gdg_ctx *ctx, int n_rows, size_t samples, int up, int down, size_t first) {
+    const int rc = deliver_ratio_check(ctx, "deliver rows ratio", up, down);
+    if (rc != GDG_OK) return rc;
+    if (n_rows <= 0) return fail(ctx, GDG_ERR_INVALID, "deliver rows ratio: %d rows at delivery ratio %d/%d", n_rows, up, down);
+    if (samples == 0 || samples > ((size_t)1 << 40) || first > ((size_t)1 << 48))
+        return fail(ctx, GDG_ERR_INVALID, "deliver rows ratio: %zu samples from %zu on at delivery ratio %d/%d; 1 to 2^40 samples, first up to 2^48", samples, first, up, down);
+    return GDG_OK;
+}
+
+int gdg_out_ratio_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int up, int down, size_t first, double *d_history,
+                                  double *d_out, size_t out_stride) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const int rc = deliver_ratio_args(ctx, n_rows, samples, up, down, first);
+    if (rc != GDG_OK) return rc;
+    if (!d_rows || !d_out) return GDG_ERR_INVALID;
+    const size_t n_out = gdg_deliver_ratio_on(up, down) ? (size_t)gdg_deliver_ratio_count(first, samples, up, down) : samples;
+    if (row_stride < samples || out_stride < n_out)
+        return fail(ctx, GDG_ERR_INVALID, "deliver rows ratio: strides of %zu and %zu samples for rows of %zu and %zu at delivery ratio %d/%d", row_stride, out_stride, samples, n_out, up, down);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_history & 7)) return fail(ctx, GDG_ERR_INVALID, "deliver rows ratio: the samples are float64, 8-byte aligned (delivery ratio %d/%d)", up, down);
+    enter_keep_fir_sums(ctx);
+    ProfScope ps(ctx, GDG_K_WAVE);
+    if (!gdg_deliver_ratio_on(up, down)) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(d_out, out_stride * sizeof(double), d_rows, row_stride * sizeof(double), samples * sizeof(double), (size_t)n_rows, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        if (ctx->d_ratio_up != up || ctx->d_ratio_down != down) {             /* another ratio: its table replaces the last one's, behind whatever still reads that */
+            std::vector<double> tapsT;
+            deliver_ratio_table(up, down, true, tapsT);
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            hipFree(ctx->d_ratio_taps);
+            ctx->d_ratio_taps = nullptr;
+            ctx->d_ratio_up = ctx->d_ratio_down = 0;
+            if (hipMalloc((void **)&ctx->d_ratio_taps, tapsT.size() * sizeof(double)) != hipSuccess)
+                return fail(ctx, GDG_ERR_NOMEM, "deliver rows ratio: cannot allocate the %zu taps of delivery ratio %d/%d on the device", tapsT.size(), up, down);
+            HIP_TRY(ctx, hipMemcpy(ctx->d_ratio_taps, tapsT.data(), tapsT.size() * sizeof(double), hipMemcpyHostToDevice));
+            ctx->d_ratio_up = up;
+            ctx->d_ratio_down = down;
+        }
+        HIP_TRY(ctx, gdg_launch_deliver_ratio(up, down, d_rows, row_stride, samples, (unsigned long long)first, (unsigned)n_rows, ctx->d_ratio_taps, d_history, d_out, out_stride, 0, ctx->stream));
+    }
+    /* behind the sum: the rows' last 127 samples are what the next call finds in front of its own */
+    if (d_history) HIP_TRY(ctx, gdg_launch_deliver_ratio_history_save(d_rows, row_stride, samples, (unsigned)n_rows, d_history, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_out_ratio_rows(gdg_ctx *ctx, const double *rows, int n_rows, size_t samples, int up, int down, size_t first, double *history, double *out, size_t out_capacity) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = deliver_ratio_args(ctx, n_rows, samples, up, down, first);
+    if (rc != GDG_OK) return rc;
+    if (!rows) return GDG_ERR_INVALID;
+    const size_t n_out = gdg_deliver_ratio_on(up, down) ? (size_t)gdg_deliver_ratio_count(first, samples, up, down) : samples;
+    if (out_capacity < n_out || (n_out && !out))
+        return fail(ctx, GDG_ERR_INVALID, "deliver rows ratio: room for %zu samples per row; %zu samples from %zu on give %zu at delivery ratio %d/%d", out_capacity, samples, first, n_out, up, down);
+    enter_keep_fir_sums(ctx);
+    const size_t rows_bytes = ((size_t)n_rows * samples * sizeof(double) + 15) & ~(size_t)15;
+    const size_t hist_bytes = history ? (size_t)n_rows * GDG_DELIVER_RATIO_HISTORY * sizeof(double) : 0;
+    rc = ensure_io(ctx, 1, rows_bytes + hist_bytes);
+    if (rc == GDG_OK) rc = ensure_io(ctx, 0, ((size_t)n_rows * n_out + 2) * sizeof(double));
+    if (rc != GDG_OK) return rc;
+    double *d_rows = static_cast<double *>(ctx->d_io[1]), *d_out = static_cast<double *>(ctx->d_io[0]);
+    double *d_hist = history ? reinterpret_cast<double *>(static_cast<unsigned char *>(ctx->d_io[1]) + rows_bytes) : nullptr;
+    HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows, (size_t)n_rows * samples * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (history) HIP_TRY(ctx, hipMemcpyAsync(d_hist, history, hist_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = gdg_out_ratio_rows_device(ctx, d_rows, samples, n_rows, samples, up, down, first, d_hist, d_out, n_out);
+    if (rc != GDG_OK) return rc;
+    /* the produced outputs only: row r of the caller's buffer begins at out + r * out_capacity */
+    if (n_out) HIP_TRY(ctx, hipMemcpy2DAsync(out, out_capacity * sizeof(double), d_out, n_out * sizeof(double), n_out * sizeof(double), (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
+    if (history) HIP_TRY(ctx, hipMemcpyAsync(history, d_hist, hist_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GDG_OK;
+}
+
 /* the planner (trim.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
 int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_t blocks, double target, double max_gain, double *gain) {
     static_assert(sizeof(gdg_block_true_peak) == 2 * sizeof(double) && offsetof(gdg_block_true_peak, true_peak) == 0, "the planner strides over true_peak in doubles");

@@ -353,8 +353,8 @@ struct gdg_ctx {
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
     /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
      * grown when a slice needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
-    void *batch_dev[13] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t batch_dev_cap[13] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    void *batch_dev[16] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    size_t batch_dev_cap[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
     /* a batch job, how far it has come, and per input the source frames handed over: the context's is the streamed run's
      * (gdg_batch_stream_open .. _close); a one-call run describes its own and leaves this one closed */
@@ -408,6 +408,15 @@ struct gdg_ctx {
      * step to step; the history is zeroed by the first slice of a job and is in no checkpoint (the checkpoint calls then refuse).  Off, neither
      * exists.  Configuration like the trim: in no blob. */
     int deliver = 1;
+    /* ... and the ratio behind the factor (gdg_batch_set_out_ratio): up / down, 1 / 1 = no ratio stage (never set, or set through
+     * gdg_batch_set_delivery).  While one is in force deliver_tapsT holds its table as the kernel reads it, [T][up], made on the host when the
+     * ratio was set; batch_dev[BATCH_DELIVER_RATIO_TABLE] its device copy, batch_dev[BATCH_DELIVER_RATIO_ROWS] a step's rows at the delivered
+     * rate and batch_dev[BATCH_DELIVER_RATIO_HISTORY] the last 127 intermediate samples of every row.  Off, none of them exists. */
+    int deliver_up = 1, deliver_down = 1;
+    std::vector<double> deliver_tapsT;
+    /* the table of the stand-alone calls' last ratio (gdg_out_ratio_rows): [T][up] on the device, made anew when another ratio is asked for */
+    double *d_ratio_taps = nullptr;
+    int d_ratio_up = 0, d_ratio_down = 0;
     /* the blend outputs (gdg_batch_set_blends; blend.h): weighted sums of this context's chain rows as the ports behind the metronome's; an
      * empty list = off (never set, or set with 0 blends).  While blends are in force a batch window has nch + 3 + count() rows and the device
      * copy of the table -- first | channel | delay | weight | gain, made and uploaded at the start of a batch call -- exists; off, neither does.
@@ -463,6 +472,9 @@ struct gdg_ctx {
     uint32_t n_tick = 0, n_tock = 0;
     uint32_t met_sample_counter = 0, met_tick_counter = 0, met_beats = 4, met_bpm = 120, met_sr = 96000;
 };
+
+/* a delivery other than the session rate is in force: a factor, a ratio behind it, or both */
+static inline bool delivery_on(const gdg_ctx *ctx) { return ctx->deliver > 1 || gdg_deliver_ratio_on(ctx->deliver_up, ctx->deliver_down); }
 
 inline int fail(const gdg_ctx *ctx, int code, const char *fmt, ...) {       /* one definition, one mutex, for all files */
     char buf[512];
@@ -662,6 +674,10 @@ int fir_tables(gdg_ctx *ctx, int P, double2 **tw, double2 **tw2);
 int spectrum_tables(gdg_ctx *ctx, const double **win, double2 **tw, double2 **tw2);
 /* api_io.cpp: the true-peak record's 3 x 24 taps, built on the host with the first use (true_peak_taps.h) */
 const gdg_true_peak_table &true_peak_table();
+/* api_io.cpp: the ratio stage's table (include/gdg.h, DELIVERY), float64 on the host: [up][T] as gdg_out_ratio_taps hands it out, or [T][up] as the kernel reads it; returns T (0: no table) */
+int deliver_ratio_table(int up, int down, bool transposed, std::vector<double> &taps);
+/* ... and what every call refuses of a ratio, worded once: GDG_OK, or GDG_ERR_INVALID with the ratio (and, unreduced, the reduced pair) named */
+int deliver_ratio_check(gdg_ctx *ctx, const char *what, int up, int down);
 int fir_transform_size(int frames);
 int meter_rows(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int port0, int n_ports, int frames, uint32_t sample_rate);
 int numa_rebind(gdg_ctx *ctx, int mode);
@@ -857,6 +873,9 @@ enum {
     BATCH_TRANSFER_TABLE,                  /* [pairs][port | target], then the group width: the transfer list's table, only while one is in force (gdg_batch_transfer_enable) */
     BATCH_DELIVERED,                       /* [N + 3 + blends][window / R] one step's rows at the delivered rate, what the encoders read; only while a delivery factor is in force (gdg_batch_set_delivery) */
     BATCH_DELIVER_HISTORY,                 /* [N + 3 + blends][154] the window rows' last samples of the step before, only while a delivery factor is in force */
+    BATCH_DELIVER_RATIO_ROWS,              /* [N + 3 + blends][pitch] one step's rows behind the ratio stage, what the encoders then read; only while a delivery ratio is in force (gdg_batch_set_out_ratio) */
+    BATCH_DELIVER_RATIO_HISTORY,           /* [N + 3 + blends][127] the intermediate rows' last samples of the step before, only while a delivery ratio is in force */
+    BATCH_DELIVER_RATIO_TABLE,             /* [T][up] the ratio's taps, only while a delivery ratio is in force */
     BATCH_DEV_SLOTS
 };
 static_assert(sizeof(gdg_ctx::batch_dev) / sizeof(void *) == BATCH_DEV_SLOTS && sizeof(gdg_ctx::batch_dev_cap) / sizeof(size_t) == BATCH_DEV_SLOTS,

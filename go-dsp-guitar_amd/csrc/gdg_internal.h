@@ -362,6 +362,13 @@ hipError_t gdg_launch_deliver_rows(int factor, const double *d_rows, size_t row_
                                    double *d_out, size_t out_stride, hipStream_t s);
 /* ... and behind it, before the rows are written again: the rows' last 154 samples into d_history[n_rows][154]; a launch of fewer moves the old ones up */
 hipError_t gdg_launch_deliver_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
+/* the ratio stage behind it (io.hip, deliver_ratio_kernels.h): n_rows rows of `samples` intermediate samples, the job's [first, first + samples), ->
+ * the outputs ceil(first up / down) <= n < ceil((first + samples) up / down) at d_out + r * out_stride, then +0.0 up to pad_to samples (0: none).
+ * d_tapsT: the ratio's table as [T][up] in device memory; d_history: null or [n_rows][127], read, never written. */
+hipError_t gdg_launch_deliver_ratio(int up, int down, const double *d_rows, size_t row_stride, size_t samples, unsigned long long first, unsigned n_rows, const double *d_tapsT,
+                                    const double *d_history, double *d_out, size_t out_stride, size_t pad_to, hipStream_t s);
+/* ... and behind it: the rows' last 127 samples into d_history[n_rows][127]; a launch of fewer moves the old ones up */
+hipError_t gdg_launch_deliver_ratio_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
 /* the blend fit's records (include/gdg.h, FIT; io.hip, fit_kernels.h): per fit and block of `block` samples (the last of a row may be short)
  * one gdg_block_fit, d_records[n_fits][ceil(samples / block)].  A fit is target | terms | port[8] (blend.h, FitSet): h_table is the host's copy
  * of the device's d_table, held against n_rows before anything is launched. */

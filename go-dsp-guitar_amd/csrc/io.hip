@@ -1144,6 +1144,7 @@ hipError_t gdg_launch_block_stats(const double *d_rows, size_t row_stride, unsig
 #include "blend_kernels.h"          /* the blend outputs: weighted sums of the window's chain rows, in front of the encoders and the records */
 #include "fit_kernels.h"            /* the blend fit's records: inner products of the window's rows in block_stats_kernel's order of sums */
 #include "deliver_kernels.h"        /* the delivery at a half or a quarter of the session rate: the window's rows decimated in front of the encoders */
+#include "deliver_ratio_kernels.h"  /* ... and the ratio stage behind it: the intermediate rows resampled by L / M, polyphase */
 
 /* resample.Time over a span of a file (the streamed batch run): blockIdx.y = input. Output samples [out_first, out_first + count) from
  * the source frames [src_first, src_first + src_count) at `src`; n = the FILE's frames (the j < n bound).  x, floor(x) and x - j are

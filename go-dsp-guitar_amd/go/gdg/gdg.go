@@ -40,6 +40,7 @@ type Context struct {
 	// the streamed batch run that is open (BatchStreamOpen): its inputs and the width of an output sample
 	streamInputs int
 	streamWidth  int
+	streamDone   int // session samples of the open streamed job's slices so far: what a delivery ratio counts a slice's samples from
 }
 
 // DeviceCount: HIP devices visible to the process (0 without a driver).
@@ -597,7 +598,7 @@ func (this *Context) BatchRun(inputs []BatchInput, opt BatchOptions) ([][]byte, 
 	if e := this.err(C.gdg_batch_length(this.ctx, &arr[0], C.int(n), o.target_rate, &samples)); e != nil {
 		return nil, e
 	}
-	each := int(samples) / int(C.gdg_batch_delivery(this.ctx)) * int(C.gdg_wave_bytes_per_sample(o.out_format)) // every port at the delivered rate (BatchSetDelivery)
+	each := this.delivered(0, int(samples)) * int(C.gdg_wave_bytes_per_sample(o.out_format)) // every port at the delivered rate (BatchSetDelivery, BatchSetDeliveryRatio)
 	no := n + 3 + int(C.gdg_batch_blends(this.ctx)) // the blends in force (BatchSetBlends): one more port each, behind the metronome's
 	outs := make([][]byte, no)
 	if each == 0 {
@@ -817,6 +818,7 @@ func (this *Context) BatchStreamOpen(inputs []BatchStreamInput, opt BatchOptions
 	}
 	this.streamInputs = n
 	this.streamWidth = int(C.gdg_wave_bytes_per_sample(o.out_format))
+	this.streamDone = 0
 	return uint64(samples), nil
 }
 
@@ -848,7 +850,7 @@ func (this *Context) BatchStreamStep(blocks int, frames [][]byte) ([][]byte, err
 	if n == 0 || len(frames) != n {
 		return nil, fmt.Errorf("gdg: %d inputs for a streamed batch run of %d", len(frames), n)
 	}
-	each := blocks * 8192 / int(C.gdg_batch_delivery(this.ctx)) * this.streamWidth // every piece at the delivered rate (BatchSetDelivery)
+	each := this.delivered(this.streamDone, blocks*8192) * this.streamWidth // every piece at the delivered rate (BatchSetDelivery, BatchSetDeliveryRatio)
 	if blocks <= 0 || each <= 0 {
 		return nil, fmt.Errorf("gdg: a slice of %d blocks", blocks)
 	}
@@ -884,6 +886,7 @@ func (this *Context) BatchStreamStep(blocks int, frames [][]byte) ([][]byte, err
 	if e := this.err(C.gdg_batch_stream_step(this.ctx, C.int(blocks), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[0])), (*unsafe.Pointer)(unsafe.Pointer(&ptrs[n])))); e != nil {
 		return nil, e
 	}
+	this.streamDone += blocks * 8192
 	outs := make([][]byte, no)
 	for i := range outs {
 		outs[i] = goBytes(ptrs[n+i], each)
@@ -952,6 +955,7 @@ func (this *Context) streamResume(inputs []BatchStreamInput, opt BatchOptions, s
 	}
 	this.streamInputs = n
 	this.streamWidth = int(C.gdg_wave_bytes_per_sample(o.out_format))
+	this.streamDone = int(done)
 	return uint64(done), nil
 }
 
@@ -1848,6 +1852,79 @@ func (this *Context) DeliverRows(rows []float64, nRows int, samples int, factor 
 // its delivered samples at dOut + r * outStride; dHistory nil or nRows * DeliverHistory doubles.
 func (this *Context) DeliverRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, factor int, dHistory unsafe.Pointer, dOut unsafe.Pointer, outStride int) error {
 	return this.err(C.gdg_deliver_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(factor), (*C.double)(dHistory), (*C.double)(dOut), C.size_t(outStride)))
+}
+
+// DeliverRatioHistory: the intermediate samples the ratio stage keeps from call to call (GDG_DELIVER_RATIO_HISTORY of the C header).
+const DeliverRatioHistory = 127
+
+// BatchSetDeliveryRatio: from the next batch call on every port leaves at (session rate / factor) * up / down (gdg_batch_set_out_ratio):
+// the factor's decimator, then the polyphase ratio stage, in front of the encoders; 44.1 kHz from 192 is (4, 147, 160).  up / down is
+// reduced, 1 <= up <= 160, 1 <= down <= 320, within a factor of two of 1; (factor, 1, 1) is BatchSetDelivery(factor).  An error while a
+// streamed job is open; the checkpoint, shard and master-finish calls refuse while a ratio is in force.
+func (this *Context) BatchSetDeliveryRatio(factor int, up int, down int) error {
+	return this.err(C.gdg_batch_set_out_ratio(this.ctx, C.int(factor), C.int(up), C.int(down)))
+}
+
+// BatchDeliveryRatio: up and down of the delivery ratio in force (gdg_batch_out_ratio): 1, 1 = none.
+func (this *Context) BatchDeliveryRatio() (int, int) {
+	var up, down C.int
+	C.gdg_batch_out_ratio(this.ctx, &up, &down)
+	return int(up), int(down)
+}
+
+// BatchDeliverySamples: the delivered samples the session samples [first, first + count) produce (gdg_batch_out_samples): what an
+// output buffer is sized with, per job and per streamed slice; 0 for anything inadmissible.
+func BatchDeliverySamples(factor int, up int, down int, first int, count int) int {
+	return int(C.gdg_batch_out_samples(C.int(factor), C.int(up), C.int(down), C.size_t(first), C.size_t(count)))
+}
+
+// BatchDeliveryRatioLatency: the session samples a port delivered at factor and up / down lags the render by (gdg_batch_out_ratio_latency).
+func BatchDeliveryRatioLatency(factor int, up int, down int) int {
+	return int(C.gdg_batch_out_ratio_latency(C.int(factor), C.int(up), C.int(down)))
+}
+
+// delivered: the delivered samples of the session samples [first, first + count) under the factor and the ratio in force.
+func (this *Context) delivered(first int, count int) int {
+	up, down := this.BatchDeliveryRatio()
+	return BatchDeliverySamples(this.BatchDelivery(), up, down, first, count)
+}
+
+// DeliverRatioTaps: the ratio stage's table tap[up][T], row after row (gdg_out_ratio_taps); none for an inadmissible ratio and for 1/1.
+func DeliverRatioTaps(up int, down int) []float64 {
+	n := int(C.gdg_out_ratio_taps(C.int(up), C.int(down), nil, 0))
+	taps := make([]float64, n)
+	if n > 0 {
+		C.gdg_out_ratio_taps(C.int(up), C.int(down), (*C.double)(unsafe.Pointer(&taps[0])), C.int(n))
+	}
+	return taps
+}
+
+// DeliverRowsRatio: nRows rows of samples intermediate samples each, the job's [first, first + samples), through the ratio stage
+// (gdg_out_ratio_rows).  history is nil (zeros in front) or nRows * DeliverRatioHistory values, read before and written after, so that
+// consecutive calls with advancing first continue a stream.
+func (this *Context) DeliverRowsRatio(rows []float64, nRows int, samples int, up int, down int, first int, history []float64) ([]float64, error) {
+	if nRows <= 0 || samples <= 0 || len(rows) != nRows*samples {
+		return nil, fmt.Errorf("gdg: %d values for %d rows of %d samples at ratio %d/%d", len(rows), nRows, samples, up, down)
+	}
+	if history != nil && len(history) != nRows*DeliverRatioHistory {
+		return nil, fmt.Errorf("gdg: a history of %d values for %d rows", len(history), nRows)
+	}
+	each := samples
+	if up != 1 || down != 1 {
+		each = BatchDeliverySamples(1, up, down, first, samples)
+	}
+	out := make([]float64, nRows*each+1)
+	var hist *C.double
+	if history != nil {
+		hist = (*C.double)(unsafe.Pointer(&history[0]))
+	}
+	rc := C.gdg_out_ratio_rows(this.ctx, (*C.double)(unsafe.Pointer(&rows[0])), C.int(nRows), C.size_t(samples), C.int(up), C.int(down), C.size_t(first), hist, (*C.double)(unsafe.Pointer(&out[0])), C.size_t(each))
+	return out[:nRows*each], this.err(rc)
+}
+
+// DeliverRowsRatioDevice: the same on device memory, enqueued on the context's stream (gdg_out_ratio_rows_device).
+func (this *Context) DeliverRowsRatioDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, up int, down int, first int, dHistory unsafe.Pointer, dOut unsafe.Pointer, outStride int) error {
+	return this.err(C.gdg_out_ratio_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), C.int(up), C.int(down), C.size_t(first), (*C.double)(dHistory), (*C.double)(dOut), C.size_t(outStride)))
 }
 
 // WaveEncodeTrim: one mono row times gain through the encoder (gdg_wave_encode_trim): mode 0 the plain encoder, 1 the dithered one of

@@ -50,6 +50,8 @@ def lib():
             "gdgh_engine_set_batch_trim": (cs, [vp, vp, i32, C.c_double, C.c_double, C.c_double]),
             "gdgh_engine_set_batch_delivery": (cs, [vp, i32]),
             "gdgh_engine_batch_delivery": (i32, [vp]),
+            "gdgh_engine_set_batch_delivery_ratio": (cs, [vp, i32, i32, i32]),
+            "gdgh_engine_batch_delivery_ratio": (None, [vp, vp, vp]),
             "gdgh_engine_sync_chains": (cs, [vp, C.c_uint32]),
             "gdgh_engine_set_batch_blends": (cs, [vp, i32, vp, vp, vp, vp]),
             "gdgh_engine_batch_blends": (i32, [vp]),
@@ -299,9 +301,16 @@ class Engine:
 
     def _set_delivery(self, deliver):
         """Engine::SetBatchDelivery, from the `deliver` argument of the batch calls: None or 1 = the session rate, 2 or 4 = every output at a
-        half or a quarter of it (one-shard engines only).  Returns the factor in force."""
-        _err(lib().gdgh_engine_set_batch_delivery(self._h, 1 if deliver is None else int(deliver)))
-        return int(lib().gdgh_engine_batch_delivery(self._h))
+        half or a quarter of it, (factor, up, down) = at (rate / factor) * up / down -- delivery_for(session, delivered) finds the triple
+        (one-shard engines only).  Returns the (factor, up, down) in force."""
+        if isinstance(deliver, (tuple, list)):
+            factor, up, down = (int(v) for v in deliver)
+            _err(lib().gdgh_engine_set_batch_delivery_ratio(self._h, factor, up, down))
+        else:
+            _err(lib().gdgh_engine_set_batch_delivery(self._h, 1 if deliver is None else int(deliver)))
+        up, down = C.c_int(1), C.c_int(1)
+        lib().gdgh_engine_batch_delivery_ratio(self._h, C.byref(up), C.byref(down))
+        return int(lib().gdgh_engine_batch_delivery(self._h)), up.value, down.value
 
     def _set_trim(self, trim):
         """Engine::SetBatchTrim, from the `trim` argument of the batch calls: the gains of the job's N + 3 output ports in the files' order
@@ -724,7 +733,9 @@ class Engine:
         [term ports], taps) -- keep the tap-fit records in last_tapfit ([blocks, D] float64; one-shard engines only; None: off).  transfers:
         ([(port, target), ...], group) -- keep the transfer records in last_transfer ([blocks, pairs x G x 4] float64; one-shard engines only; None: off).
         deliver: 2 or 4 -- every output at a half or a quarter of the session rate (Engine::SetBatchDelivery; one-shard engines only; None
-        or 1: off): each data section then has length // deliver samples and lags the render by 38 or 77 session samples.  Every last_*
+        or 1: off): each data section then has length // deliver samples and lags the render by 38 or 77 session samples.  A triple
+        (factor, up, down) -- delivery_for(192000, 44100) = (4, 147, 160) -- adds the ratio stage behind the factor: each data section has
+        batch_delivery_samples(factor, up, down, 0, length) samples and lags by batch_delivery_ratio_latency(factor, up, down).  Every last_*
         record stays that of the session-rate render, so a delivered file's true peak can differ from last_true_peak: the anti-aliasing
         filter removes what lies above the new Nyquist frequency, and it rings."""
         import __graft_entry__ as entry
@@ -765,7 +776,7 @@ class Engine:
             if count > 0:
                 length = max(length, self.raw_context(g).batch_length(inputs[first:first + count], target_rate))
         no = n + 3 + nb
-        outs = None if skip_outputs else [np.zeros(length // R * wo, dtype=np.uint8) for _ in range(no)]
+        outs = None if skip_outputs else [np.zeros(pkg.batch_delivery_samples(*R, 0, length) * wo, dtype=np.uint8) for _ in range(no)]
         ptrs = (C.c_void_p * no)(*([None] * no if skip_outputs else [(o.ctypes.data if o.size else None) for o in outs]))
         samples = C.c_size_t(0)
         _err(lib().gdgh_engine_batch_run(self._h, arr, n, C.byref(opt), window, ptrs, C.byref(samples)))
@@ -868,12 +879,14 @@ class Engine:
         try:
             left = (samples.value - done.value) // 8192
             first, count = (C.c_size_t * n)(), (C.c_size_t * n)()
+            done_samples = done.value                        # session samples of the slices so far: what a delivery ratio counts a slice from
             while left:
                 blocks = min(left, blocks_per_slice(left) if callable(blocks_per_slice) else blocks_per_slice)
                 _err(f_need(self._h, blocks, first, count))
                 pieces = [None if datas[i] is None or not count[i] else datas[i][first[i] * widths[i]:(first[i] + count[i]) * widths[i]] for i in range(n)]
                 ins = (C.c_void_p * n)(*[(p.ctypes.data if p is not None else None) for p in pieces])
-                outs = [np.zeros(blocks * 8192 // R * wo, dtype=np.uint8) for _ in range(n + 3 + nb)]
+                outs = [np.zeros(pkg.batch_delivery_samples(*R, done_samples, blocks * 8192) * wo, dtype=np.uint8) for _ in range(n + 3 + nb)]
+                done_samples += blocks * 8192
                 ptrs = (C.c_void_p * (n + 3 + nb))(*[o.ctypes.data for o in outs])
                 _err(f_step(self._h, blocks, ins, ptrs))
                 if report:
@@ -1065,6 +1078,30 @@ class Unit:
         out = np.empty_like(x)
         lib().gdgh_unit_process(self._h, x.ctypes.data, out.ctypes.data, x.size, sample_rate)
         return out
+
+
+def delivery_for(session_rate, delivered_rate):
+    """The (factor, up, down) of `deliver=` for a (session rate, delivered rate) pair: of the factors 1, 2, 4 that leave an admissible ratio
+    (reduced, up <= 160, down <= 320, within a factor of two of 1) the one whose ratio lies closest to 1, so that the long filter at the full
+    rate does the most -- (192000, 44100) -> (4, 147, 160), (96000, 44100) -> (2, 147, 160), (88200, 48000) -> (2, 160, 147),
+    (192000, 48000) -> (4, 1, 1).  ValueError where no admissible triple exists."""
+    from fractions import Fraction
+    from math import gcd
+    session_rate, delivered_rate = int(session_rate), int(delivered_rate)
+    best = None
+    if session_rate > 0 and delivered_rate > 0:
+        for factor in (1, 2, 4):
+            if session_rate % factor:
+                continue
+            g = gcd(delivered_rate, session_rate // factor)
+            up, down = delivered_rate // g, session_rate // factor // g
+            if 1 <= up <= 160 and 1 <= down <= 320 and down <= 2 * up and up <= 2 * down:
+                away = Fraction(max(up, down), min(up, down))
+                if best is None or away < best[0]:
+                    best = (away, (factor, up, down))
+    if best is None:
+        raise ValueError("no delivery factor of 1, 2, 4 with an admissible ratio takes %d Hz to %d Hz" % (session_rate, delivered_rate))
+    return best[1]
 
 
 def filter_compile(taps, sample_rate, compensation_db, order, level_db):

@@ -977,6 +977,22 @@ Error Engine::SetBatchDelivery(int factor) {
         return format("SetBatchDelivery: the engine has %d shards: the library's shard and master-finish calls refuse a delivery factor; delivery factor %d needs a "
                       "one-shard engine", shards(), factor);
     delivery_ = factor;
+    deliveryUp_ = deliveryDown_ = 1;
+    return "";
+}
+
+/* ... with a ratio behind the factor (gdg_batch_set_out_ratio): the library's own rules, restated so that nothing is taken half */
+Error Engine::SetBatchDelivery(int factor, int up, int down) {
+    if (up == 1 && down == 1) return SetBatchDelivery(factor);
+    if (factor != 1 && factor != 2 && factor != 4) return format("SetBatchDelivery: delivery factor %d; 1 is the session rate, 2 a half of it, 4 a quarter", factor);
+    if (gdg_batch_out_samples(1, up, down, 0, 1) == 0)      /* one sample at an admissible ratio gives one output, at any other none */
+        return format("SetBatchDelivery: delivery ratio %d/%d; reduced, up 1 to 160, down 1 to 320, down <= 2 up and up <= 2 down", up, down);
+    if (shards() > 1)
+        return format("SetBatchDelivery: the engine has %d shards: the library's shard and master-finish calls refuse a delivery ratio; delivery ratio %d/%d needs a "
+                      "one-shard engine", shards(), up, down);
+    delivery_ = factor;
+    deliveryUp_ = up;
+    deliveryDown_ = down;
     return "";
 }
 
@@ -1202,7 +1218,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || gdg_batch_set_delivery(ctx, delivery_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1482,7 +1498,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_delivery(ctx, delivery_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1741,7 +1757,7 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_delivery(ctx, delivery_) != GDG_OK || applyBlends(ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -2058,6 +2074,8 @@ const char *gdgh_engine_set_batch_trim(void *e, const double *chain_gain, int n,
 }
 const char *gdgh_engine_set_batch_delivery(void *e, int factor) { return ret(((Engine *)e)->SetBatchDelivery(factor)); }
 int gdgh_engine_batch_delivery(void *e) { return ((Engine *)e)->BatchDelivery(); }
+const char *gdgh_engine_set_batch_delivery_ratio(void *e, int factor, int up, int down) { return ret(((Engine *)e)->SetBatchDelivery(factor, up, down)); }
+void gdgh_engine_batch_delivery_ratio(void *e, int *up, int *down) { ((Engine *)e)->BatchDeliveryRatio(up, down); }
 /* the blends in gdg_batch_set_blends' CSR form, job channel numbers; n_blends == 0: off; gain == NULL: every gain 1.  A `first` that does
  * not start at 0 or descends is refused here: the lists below are cut by it */
 const char *gdgh_engine_set_batch_blends_filtered(void *e, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const int *tap_first,

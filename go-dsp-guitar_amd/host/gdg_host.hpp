@@ -292,6 +292,11 @@ public:
      * other than 1, 2, 4 is refused and the factor in force stays.  The checkpoint calls refuse while a factor is in force. */
     Error SetBatchDelivery(int factor);
     int BatchDelivery() const { return delivery_; }
+    /* ... and with the ratio up / down behind the factor (gdg_batch_set_out_ratio): 44.1 kHz from 192 is (4, 147, 160); `outs` of
+     * gdg_batch_out_samples(factor, up, down, first, count) samples each.  (factor, 1, 1) is SetBatchDelivery(factor); a ratio the
+     * library would refuse is refused here and what is in force stays. */
+    Error SetBatchDelivery(int factor, int up, int down);
+    void BatchDeliveryRatio(int *up, int *down) const { if (up) *up = deliveryUp_; if (down) *down = deliveryDown_; }
     /* No reference counterpart.  The blend outputs (include/gdg.h, gdg_batch_set_blends): blend b is the weighted sum of its terms -- (job
      * channel, weight) pairs, 1 to 32 of them -- over the chain outputs, in term order, and port N + 3 + b of BatchRun and the plain streamed
      * job; gain: one output gain per blend, or none (every gain 1).  While blends are in force every call's `outs` and every Last* record
@@ -403,6 +408,7 @@ private:
     int applyDither(int shard, gdg_ctx *ctx);              /* mode, seed and the shard's port_base onto its context: a gdg_* status */
     std::vector<double> trim_;                             /* SetBatchTrim: N chain gains, master left, master right, metronome; empty: off */
     int delivery_ = 1;                                     /* SetBatchDelivery: 1 = off; never another value on an engine of several shards */
+    int deliveryUp_ = 1, deliveryDown_ = 1;                /* ... and the ratio behind it: 1 / 1 = none; never another on an engine of several shards */
     int applyTrim(int shard, gdg_ctx *ctx);                /* the shard's slice of it onto its context: a gdg_* status */
     std::vector<int> blendFirst_, blendChannel_;           /* SetBatchBlends, in gdg_batch_set_blends' CSR form; blendFirst_ empty: off */
     std::vector<double> blendWeight_, blendGain_;
@@ -431,7 +437,7 @@ private:
     bool transferValid_ = false;
     int applyTransfers(gdg_ctx *ctx);                      /* onto a context (more shards: none is in force): a gdg_* status */
     int applyTapFits(gdg_ctx *ctx);                        /* onto a context (more shards: none are in force): a gdg_* status */
-    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivery_ > 1; }      /* BatchRun is the library's plain one-call run */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivery_ > 1 || deliveryUp_ != 1 || deliveryDown_ != 1; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

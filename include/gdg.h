@@ -1598,6 +1598,73 @@ int gdg_deliver_rows(gdg_ctx *ctx, const double *rows, int n_rows, size_t sample
 int gdg_deliver_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int factor, double *d_history, double *d_out,
                             size_t out_stride);
 int gdg_deliver_taps(int factor, double *taps, int capacity);
+/*
+ * DELIVERY, a rational ratio behind the factor: 44.1 kHz from a 48, 96 or 192 kHz session, 48 kHz from 44.1 or 88.2.  Delivery is two stages
+ * in series in front of the untouched encoders: the integer factor R above (1, 2 or 4), then a ratio L / M (up / down) applied to what the
+ * factor leaves, the INTERMEDIATE rows at rate / R.  192 kHz -> 44.1: factor 4, ratio 147/160; 96 -> 44.1: 2, 147/160; 48 -> 44.1: 1, 147/160;
+ * 88.2 -> 48: 2, 160/147.  The long anti-aliasing work at the full rate stays with the factor's filter; the ratio stage runs on a half or a
+ * quarter of the data with about 70 taps per output.  resample.Time of the reference (a six-point Lanczos interpolation without an
+ * anti-aliasing filter) is right for bringing a file up to the session rate and wrong for going down, so this stage has a definition of its own.
+ * (The calls of this block are named gdg_batch_out_* and gdg_out_ratio_*: the census of the factor stage's exports is taken by the word
+ * "deliver", and stays as it is.)
+ *   gdg_batch_set_out_ratio(ctx, factor, up, down)   holds from the next batch call on; gdg_batch_set_delivery(ctx, factor) means up / down = 1 / 1
+ *   gdg_batch_out_ratio(ctx, &up, &down)             the ratio in force (1 / 1: none); gdg_batch_delivery keeps returning the factor
+ *   gdg_batch_out_samples(factor, up, down, first, count)   the delivered samples the session samples [first, first + count) produce (both
+ *                                                      multiples of factor; 0 for anything inadmissible): what a caller sizes out_bytes with, per
+ *                                                      job (first 0, count gdg_batch_length()) and per streamed slice (first = the session samples
+ *                                                      of the slices before).  Pure host arithmetic, 64-bit integers
+ *   gdg_batch_out_ratio_latency(factor, up, down) session samples a delivered port lags the render by: gdg_batch_delivery_latency(R) + R T / 2
+ * ADMISSIBLE RATIOS: gcd(L, M) = 1, 1 <= L <= 160, 1 <= M <= 320, M <= 2 L and L <= 2 M; 1/1 means no ratio stage.  The caller reduces the
+ * ratio: an unreduced pair is refused, naming the reduced one.  GDG_ERR_INVALID, gdg_last_error naming the delivery ratio, the factor and the
+ * ratio in force unchanged: an inadmissible factor or ratio, an unreduced ratio, a call while a streamed job is open.
+ * TAPS PER PHASE: T = 2 * ceil(32 * max(1, M / L)), in integers: 70 for 147/160, 64 for 160/147, at most 128.
+ * PROTOTYPE: g[m], m = 0 .. L T - 1, centre c = L T / 2, u = m - c:
+ *   g[m] = L * 2 fc * sinc(2 fc u) * I0(beta * sqrt(1 - (u / c)^2)) / I0(beta)
+ * fc = 0.5 / max(L, M) (the cut-off is the Nyquist frequency of the lower of the two rates), beta = 10, sinc(v) = sin(pi v) / (pi v).  Computed
+ * once on the host in float64 when the ratio is set, stored as tap[p][t] = g[p + t L].
+ * OUTPUT: for an intermediate row x over the WHOLE JOB with x[k] = 0 for k < 0, output n has b = floor(n M / L) and p = (n M) mod L, and
+ *   f = tap[p][0] * x[b]
+ *   f = f + (tap[p][t] * x[b - t])                     for t = 1 .. T - 1, in ascending order
+ *   y[n] = f
+ * every product and every add an IEEE-754 double operation rounded on its own; no attenuation constant and no clip (the encoders clip).  The
+ * filter is causal: output n needs nothing beyond x[b].
+ * COUNTS: the intermediate samples [s0, s1) produce the outputs ceil(s0 L / M) <= n < ceil(s1 L / M); a job of S session samples has
+ * ceil((S / R) * L / M) delivered samples per port.  64-bit integers throughout, no floating point.
+ * LATENCY: the ratio stage lags by T / 2 intermediate samples, exactly (the centre is on the grid): a delivered port lags the render by
+ * gdg_batch_delivery_latency(R) + R * T / 2 session samples.
+ * Known answers: an impulse 1.0 at intermediate sample 0 gives y[n] = g[n M] while n M < L T, and +0.0 after; silence gives exactly +0.0; after
+ * T samples of 1.0 every output is its phase's tap sum, within 3e-6 of 1 for 147/160, 160/147, 2/3, 3/2 and 1/2.
+ * ORDER: factor, ratio, then the trim or blend gain, then the plain or the dithered encoder.  The dither's index is the delivered sample's
+ * index n in the job.
+ * WHERE: gdg_batch_run writes gdg_batch_out_samples(R, L, M, 0, gdg_batch_length()) samples to each out_bytes buffer; a streamed slice of b
+ * blocks behind `done` session samples writes gdg_batch_out_samples(R, L, M, done, b * 8192) samples to each -- the count differs from slice
+ * to slice (8192 * 147 / 160 = 7526.4), and the slices' counts sum to the job's.
+ * STATE: beside the factor's 154 session samples, GDG_DELIVER_RATIO_HISTORY = 127 intermediate samples of every port, kept from step to step and
+ * from slice to slice, zeroed when a job starts, freed when delivery returns to off.  The bytes do not depend on the window or the slicing.
+ * What stays at the session rate, and off (never set, or factor 1 with 1/1): as above.
+ * GDG_ERR_UNSUPPORTED while a ratio other than 1/1 is in force, gdg_last_error naming the delivery ratio: the checkpoint and resume calls (the
+ * histories are not in the version-1 container), the shard calls, gdg_batch_finish_master and gdg_batch_finish_master_slice.
+ * The ratio stage on its own:
+ *   gdg_out_ratio_rows(ctx, rows, n_rows, samples, up, down, first, history, out, out_capacity)      host buffers, blocking
+ *   gdg_out_ratio_rows_device(ctx, d_rows, row_stride, n_rows, samples, up, down, first, d_history, d_out, out_stride)   enqueued on gdg_ctx_stream
+ *                                                      rows: [n_rows][samples] intermediate samples, the job's [first, first + samples) (device:
+ *                                                      row r at d_rows + r * row_stride); out: row r at out + r * out_capacity (device:
+ *                                                      out_stride), its first ceil((first + samples) L / M) - ceil(first L / M) samples written
+ *                                                      and nothing else; a capacity or stride below that count is refused.  history: NULL
+ *                                                      (zeros in front of the call) or [n_rows][127] doubles, the newest last, read before and
+ *                                                      written after (a call of fewer samples moves the old ones up), so that consecutive calls
+ *                                                      with advancing `first` continue a stream.  1/1 copies.
+ *   gdg_out_ratio_taps(up, down, taps, capacity)   the table tap[L][T]: writes min(L T, capacity) doubles (taps may be NULL), returns L T
+ *                                                      (0 for an inadmissible ratio and for 1/1); pure host arithmetic
+ */
+int gdg_batch_set_out_ratio(gdg_ctx *ctx, int factor, int up, int down);
+int gdg_batch_out_ratio(const gdg_ctx *ctx, int *up, int *down);
+size_t gdg_batch_out_samples(int factor, int up, int down, size_t first, size_t count);
+int gdg_batch_out_ratio_latency(int factor, int up, int down);
+int gdg_out_ratio_taps(int up, int down, double *taps, int capacity);
+int gdg_out_ratio_rows(gdg_ctx *ctx, const double *rows, int n_rows, size_t samples, int up, int down, size_t first, double *history, double *out, size_t out_capacity);
+int gdg_out_ratio_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int up, int down, size_t first, double *d_history,
+                                  double *d_out, size_t out_stride);
 
 #ifdef __cplusplus
 
