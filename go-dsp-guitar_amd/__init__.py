@@ -65,6 +65,7 @@ ABI_SYMBOLS = [
     "gdg_batch_set_delivery", "gdg_batch_delivery", "gdg_batch_delivery_latency", "gdg_deliver_rows", "gdg_deliver_rows_device", "gdg_deliver_taps",
     "gdg_batch_set_out_ratio", "gdg_batch_out_ratio", "gdg_batch_out_samples", "gdg_batch_out_ratio_latency", "gdg_out_ratio_taps",
     "gdg_out_ratio_rows", "gdg_out_ratio_rows_device",
+    "gdg_block_out_rows", "gdg_block_out_rows_device", "gdg_batch_out_records_enable", "gdg_batch_out_records", "gdg_trim_from_out_records",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -100,6 +101,27 @@ def trim_from_true_peak(records, target, max_gain):
     gain = np.zeros(rec.shape[0], dtype=np.float64)
     rc = lib().gdg_trim_from_true_peak(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], float(target), float(max_gain),
                                        gain.ctypes.data if gain.size else None)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return gain
+
+
+# gdg_block_delivered (include/gdg.h, DELIVERED RECORDS): one record of a delivered block, 40 bytes, little-endian, no padding
+BLOCK_DELIVERED_DTYPE = np.dtype([("true_peak", "<f8"), ("peak", "<f8"), ("sum_sq", "<f8"), ("position", "<i4"), ("peak_index", "<u4"), ("overs", "<u4"), ("clipped", "<u4")])
+assert BLOCK_DELIVERED_DTYPE.itemsize == 40
+DELIVERED_HISTORY = 23       # GDG_OUT_RECORDS_HISTORY: the samples in front of a block its record reads
+DELIVERED_MAX_BLOCK = 16384  # GDG_OUT_RECORDS_MAX_BLOCK: the longest block of the stand-alone call
+
+
+def trim_from_delivered(records, target, max_gain):
+    """gdg_trim_from_out_records: trim_from_true_peak's rule on the true_peak of the delivered rows' records ([ports, blocks],
+    BLOCK_DELIVERED_DTYPE, as batch_delivered hands them out).  Host arithmetic: no context, no device."""
+    rec = np.ascontiguousarray(records, dtype=BLOCK_DELIVERED_DTYPE)
+    if rec.ndim != 2:
+        raise ValueError("records: [ports, blocks]")
+    gain = np.zeros(rec.shape[0], dtype=np.float64)
+    rc = lib().gdg_trim_from_out_records(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], float(target), float(max_gain),
+                                         gain.ctypes.data if gain.size else None)
     if rc != GDG_OK:
         raise GdgError(rc, lib().gdg_last_error(None).decode())
     return gain
@@ -662,6 +684,11 @@ def lib():
             "gdg_out_ratio_taps": (i32, [i32, i32, vp, i32]),
             "gdg_out_ratio_rows": (i32, [vp, vp, i32, C.c_size_t, i32, i32, C.c_size_t, vp, vp, C.c_size_t]),
             "gdg_out_ratio_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, i32, i32, C.c_size_t, vp, vp, C.c_size_t]),
+            "gdg_block_out_rows": (i32, [vp, vp, i32, C.c_size_t, vp, C.c_size_t, vp, vp]),
+            "gdg_block_out_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp, C.c_size_t, vp, vp]),
+            "gdg_batch_out_records_enable": (i32, [vp, i32]),
+            "gdg_batch_out_records": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdg_trim_from_out_records": (i32, [vp, i32, C.c_size_t, C.c_double, C.c_double, vp]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -1101,11 +1128,12 @@ class Context:
         self._check(lib().gdg_batch_length(self._h, arr, len(inputs), target_rate, C.byref(length)))
         return length.value
 
-    def batch_run(self, inputs, target_rate, out_format, metronome_to_master=False, run_meters=False, tuner_enqueue=False, outs=None):
+    def batch_run(self, inputs, target_rate, out_format, metronome_to_master=False, run_meters=False, tuner_enqueue=False, outs=None, skip_outputs=False):
         """controller.processFiles on the device (controller/controller.go:2809-3219 without prompts and file I/O).
         inputs: per channel None ("leaving channel empty") or (data-section bytes, format, sample_rate[, channels, channel]);
         returns the N + 3 output data sections (uint8 arrays): out_0 .. out_{N-1}, master left, master right, metronome -- and behind them
-        one per blend in force (batch_set_blends)."""
+        one per blend in force (batch_set_blends).  skip_outputs: every output pointer NULL -- the job renders and measures (the records
+        that are switched on), nothing is written; returns None."""
         n = len(inputs)
         no = n + 3 + self.batch_blends()
         arr, _keep = self._batch_inputs(inputs)
@@ -1115,6 +1143,9 @@ class Context:
         self._check(lib().gdg_batch_length(self._h, arr, n, target_rate, C.byref(length)))
         wo = lib().gdg_wave_bytes_per_sample(fo)
         size = self._delivered(0, length.value) * wo          # every port at the delivered rate (batch_set_delivery, batch_set_delivery_ratio)
+        if skip_outputs:
+            self._check(lib().gdg_batch_run(self._h, arr, n, C.byref(opt), (C.c_void_p * no)()))
+            return None
         if outs is None:
             outs = [np.zeros(size, dtype=np.uint8) for _ in range(no)]
         assert len(outs) == no and all(o.dtype == np.uint8 and o.size == size for o in outs)
@@ -2021,6 +2052,50 @@ class Context:
         out = np.zeros((ports.value, blocks.value), dtype=BLOCK_TRUE_PEAK_DTYPE)
         self._check(lib().gdg_batch_true_peak(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
         return out
+
+    # -- the records of the delivered rows: peak, sum of squares and a true peak that is seamless across blocks of any length (include/gdg.h) --
+    def block_delivered_rows(self, rows, span, history=None):
+        """gdg_block_out_rows: rows [n_rows][samples] float64 (or a list of equally long 1-D arrays, or one 1-D row) cut into blocks by
+        span[0 .. n_blocks] (ascending, span[0] = 0, span[-1] = samples, lengths 1 to 16384); returns the [n_rows][n_blocks]
+        BLOCK_DELIVERED_DTYPE records.  history: None (zeros stand in front, nothing is kept) or a C-contiguous [n_rows, 23] float64 array,
+        read before and UPDATED IN PLACE after, so consecutive calls continue a stream."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = rows[None, :]
+        keep = [_f64(r) for r in rows]
+        n = len(keep)
+        samples = keep[0].size if n else 0
+        assert all(r.ndim == 1 and r.size == samples for r in keep)
+        sp = np.ascontiguousarray(span, dtype=np.uint64)
+        assert sp.ndim == 1 and sp.size >= 1
+        if history is not None:
+            assert isinstance(history, np.ndarray) and history.dtype == np.float64 and history.flags.c_contiguous and history.size == n * DELIVERED_HISTORY
+        out = np.zeros((n, sp.size - 1), dtype=BLOCK_DELIVERED_DTYPE)
+        ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in keep])
+        self._check(lib().gdg_block_out_rows(self._h, ptrs, n, samples, sp.ctypes.data, sp.size - 1, None if history is None else history.ctypes.data,
+                                             out.ctypes.data if out.size else None))
+        return out
+
+    def block_delivered_rows_device(self, d_rows, row_stride, n_rows, samples, span, d_history, d_records):
+        """gdg_block_out_rows_device on plain device pointers (ints; d_history 0 or None: zeros in front); span is a host sequence.  Enqueued
+        on the context's stream."""
+        sp = np.ascontiguousarray(span, dtype=np.uint64)
+        self._check(lib().gdg_block_out_rows_device(self._h, d_rows, row_stride, n_rows, samples, sp.ctypes.data, sp.size - 1, d_history or None, d_records))
+
+    def batch_delivered_enable(self, enable=True):
+        """From the next batch call on, batch_run and batch_stream_step keep the records of the rows the encoders read -- the delivered rows,
+        in front of any gain -- of every encoded port (gdg_batch_out_records_enable; off by default).  Configuration: not in a checkpoint,
+        refused while a streamed job is open; the checkpoint, shard and finish_master calls refuse while it is on."""
+        self._check(lib().gdg_batch_out_records_enable(self._h, 1 if enable else 0))
+
+    def batch_delivered(self):
+        """The [ports][blocks] BLOCK_DELIVERED_DTYPE records of the last completed batch call; GdgError when there are none."""
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_out_records(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=BLOCK_DELIVERED_DTYPE)
+        self._check(lib().gdg_batch_out_records(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
+    trim_from_delivered = staticmethod(trim_from_delivered)
 
     def metronome_process(self, frames):
         out = np.empty(frames, dtype=np.float64)

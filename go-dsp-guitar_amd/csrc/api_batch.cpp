@@ -138,6 +138,11 @@ struct BatchLoop {
     double *d_ratio_rows, *d_ratio_history;
     const double *d_ratio_taps;
     size_t ratio_stride;
+    /* the records of the delivered rows (include/gdg.h, DELIVERED RECORDS; a shape that is off = off, and always for a shard): what a step sends
+     * down per block, the 23 samples every encoded row keeps from step to step, [NR][23], and room for the steps' block spans on the device */
+    ListShape delivered;
+    double *d_out_rec_history;
+    unsigned long long *d_out_rec_spans;
 };
 
 /* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
@@ -182,7 +187,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; ListSections lists; ListSection transfer; };
+    struct Step { size_t off; int w; ReportSections sec; ListSections lists; ListSection transfer, delivered; size_t span_at; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -194,7 +199,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {}, {}, {} });
+        steps.push_back({ off, w, {}, {}, {}, {}, 0 });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
@@ -212,6 +217,18 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
         steps[i].lists = list_sections(steps[i].sec.end, list_shape, (size_t)steps[i].w);        /* behind the last of them: [fits][w], [w], [w] */
         steps[i].transfer = transfer_section(steps[i].lists, p.transfer.shape, (size_t)steps[i].w);  /* ... and the transfer records behind those: [w] */
+        steps[i].delivered = delivered_section(steps[i].transfer, p.delivered, (size_t)steps[i].w);  /* ... and the delivered rows' records behind those: [NR][w] */
+    }
+    /* the delivered rows' blocks: session block j of a step delivers the samples [span[j], span[j + 1]) of the step's rows, counted where every
+     * other count of a delivered step comes from (deliver.h); all steps' spans go up once, ahead of everything the loop enqueues */
+    if (p.delivered.on()) {
+        std::vector<unsigned long long> &spans = ctx->out_rec_spans;
+        spans.clear();
+        for (Step &st : steps) {
+            st.span_at = spans.size();
+            for (int j = 0; j <= st.w; j++) spans.push_back((unsigned long long)step_of((size_t)j, st.off, 0).samples);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(p.d_out_rec_spans, spans.data(), spans.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
     }
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
@@ -257,6 +274,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         for (int k = 0; k < LIST_KINDS; k++)
             if (p.list[k].count) list_file(ctx, k, src + steps[i].lists.of[k].at, (size_t)steps[i].w, steps[i].off / B);
         if (p.transfer.count) transfer_file(ctx, src + steps[i].transfer.at, (size_t)steps[i].w, steps[i].off / B);
+        if (p.delivered.on()) delivered_file(ctx, src + steps[i].delivered.at, (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -357,6 +375,13 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
                 HIP_TRY(ctx, gdg_launch_deliver_ratio_history_save(enc_src, ws / (size_t)R, ds.inter_samples, (unsigned)NR, p.d_ratio_history, ctx->stream));
                 enc_src = p.d_ratio_rows;
             }
+            /* the records of the rows the encoders are about to read, in front of any gain: the step's w blocks as the delivery cut them, the 23
+             * samples in front of the step from the history, which the step's tail replaces behind the launch */
+            if (p.delivered.on()) {
+                HIP_TRY(ctx, gdg_launch_block_delivered(enc_src, enc_stride, (unsigned)NR, ds.samples, p.d_out_rec_spans + steps[i].span_at, (unsigned)w, p.d_out_rec_history,
+                                                        true_peak_table(), enc + steps[i].delivered.at, ctx->stream));
+                HIP_TRY(ctx, gdg_launch_delivered_history_save(enc_src, enc_stride, ds.samples, (unsigned)NR, p.d_out_rec_history, ctx->stream));
+            }
             if (!sharded) {
                 HIP_TRY(ctx, encode_rows(enc_src, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
                 /* a launch of their own: blend b is port port_base + N + 3 + b of the dither, and its gain is the blend's, not the trim's */
@@ -383,7 +408,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = step_of((size_t)steps[i].w, steps[i].off, 0).row_bytes;
-        const size_t down = steps[i].transfer.end;
+        const size_t down = steps[i].delivered.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             size_t b0 = 0, b1 = 0;
@@ -591,6 +616,25 @@ static int delivery_refused(gdg_ctx *ctx, const char *what) {
     return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d is in force on this context (gdg_batch_set_delivery); a sharded job cannot deliver at another rate yet", what, ctx->deliver);
 }
 #define DELIVERY_REFUSED(ctx, what) delivery_refused(ctx, what)
+/* ... and the delivered rows' records are the encoders' rows', with a history per context: the same calls refuse while their switch is on */
+#define OUT_RECORDS_REFUSED(ctx, what) \
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivered rows' records are on on this context (gdg_batch_out_records_enable); a sharded job cannot collect them yet", what)
+
+int gdg_batch_out_records_enable(gdg_ctx *ctx, int enable) {
+    if (!ctx) return GDG_ERR_INVALID;
+    if (ctx->bstream.open)
+        return fail(ctx, GDG_ERR_INVALID, "batch out records: a streamed batch run is open on this context; its setting holds until gdg_batch_stream_close");
+    const bool on = enable != 0;
+    if (on == ctx->out_rec_on) return GDG_OK;
+    enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
+    /* another size of a download half, and off the history and the spans go: whatever still reads them has to be done first -- a wait that
+     * fails refuses the call with the switch untouched.  The halves are made anew by the next batch call, at the size of a context that was
+     * always configured like this one. */
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i : { (int)BATCH_ENCODED, (int)BATCH_DELIVERED_REC_HISTORY, (int)BATCH_DELIVERED_REC_SPANS }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    ctx->out_rec_on = on;
+    return GDG_OK;
+}
 
 /* the blend outputs: validated whole before the list replaces the one in force (blend.h); read when a job is described and by every slice */
 int gdg_batch_set_blends_filtered(gdg_ctx *ctx, int n_blends, const int *first, const int *channel, const double *weight, const int *delay, const int *tap_first,
@@ -882,6 +926,7 @@ int gdg_batch_stream_open(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
 int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, size_t job_samples,
                                 int run_metronome, size_t *samples) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_open_shard");
+    if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_open_shard")) return rc;
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
@@ -954,6 +999,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     }
     const ListInForce transfer = sharded ? ListInForce{ nullptr, 0, 0, { 0, 0 } } : transfer_in_force(ctx);
     if (transfer.count) transfer_begin(ctx, (size_t)blocks);
+    const ListShape delivered = sharded ? ListShape{ 0, 0 } : delivered_shape(ctx, (size_t)NR);      /* the delivered rows' records; never a shard's: its calls refuse them */
+    if (delivered.on()) delivered_begin(ctx, (size_t)NR, (size_t)blocks);
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -979,7 +1026,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = ((deliver_ratio_window_bytes((size_t)W, R, RL, RM, (size_t)out_width, (size_t)enc_room) + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
                            + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + list_room(lists[LIST_FIT].shape, (size_t)W)
-                           + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W) + list_room(transfer.shape, (size_t)W);
+                           + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W) + list_room(transfer.shape, (size_t)W)
+                           + list_room(delivered, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -1227,6 +1275,17 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             loop.ratio_down = RM;
             loop.d_ratio_taps = d_table;
         }
+        /* the delivered rows' records: the history of the NR rows the encoders read, zeroed by the job's first slice like the deliveries'; room for
+         * the spans of the slice's steps -- a step has w + 1 of them, so never more than two per block */
+        if (delivered.on()) {
+            const size_t hist_bytes = (size_t)NR * GDG_OUT_RECORDS_HISTORY * sizeof(double);
+            const bool fresh = ctx->batch_dev_cap[BATCH_DELIVERED_REC_HISTORY] < hist_bytes;
+            if ((r = batch_buffer(ctx, BATCH_DELIVERED_REC_HISTORY, hist_bytes, (void **)&loop.d_out_rec_history)) != GDG_OK) return r;
+            if ((r = batch_buffer(ctx, BATCH_DELIVERED_REC_SPANS, (size_t)2 * (size_t)blocks * sizeof(unsigned long long), (void **)&loop.d_out_rec_spans)) != GDG_OK) return r;
+            if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the delivered rows' history of the open job is gone (gdg_batch_release between two slices?)");
+            if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_out_rec_history, 0, hist_bytes, ctx->stream));
+            loop.delivered = delivered;
+        }
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -1268,6 +1327,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_step_shard");
+    if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_stream_step_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_step_shard")) return rc;
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
@@ -1294,6 +1354,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
         for (int k = 0; k < LIST_KINDS && !shard; k++) list_begin(ctx, k, 0);
         if (!shard) transfer_begin(ctx, 0);
+        if (!shard) delivered_begin(ctx, (size_t)(n_inputs + 3 + ctx->blend.count()), 0);
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;
@@ -1313,6 +1374,7 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
                         const gdg_batch_shard_out *shard) {
     if (!shard) return GDG_ERR_INVALID;
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_run_shard");
+    if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_run_shard");
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_run_shard")) return rc;
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
@@ -1467,6 +1529,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
 int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                             size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master");
+    if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_finish_master");
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes, 0);      /* the cursor stays */
@@ -1476,6 +1539,7 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
 int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *const *left, const double *const *right, int n_shards, const double *aux,
                                   size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master_slice");
+    if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_finish_master_slice");
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);

@@ -114,6 +114,9 @@ static int delivery_history_refused(gdg_ctx *ctx, const char *what) {
     return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivery factor %d is in force on this context (gdg_batch_set_delivery); the delivery history is not in the version-1 container", what, ctx->deliver);
 }
 #define DELIVERY_HISTORY_REFUSED(ctx, what) delivery_history_refused(ctx, what)
+/* ... nor of the delivered rows' records' (gdg_batch_out_records_enable): the 23 samples in front of the next step's first block */
+#define OUT_RECORDS_HISTORY_REFUSED(ctx, what) \
+    fail(ctx, GDG_ERR_UNSUPPORTED, "%s: the delivered rows' records are on on this context (gdg_batch_out_records_enable); their history is not in the version-1 container", what)
 static bool input_has_samples(const gdg_batch_input &in) { return in.bytes && in.samples_per_channel; }
 /* the frames of input i's carry that hold source frames: what the next step of the job will read from it (api_batch.cpp, stream_step) */
 static uint32_t carry_valid(const gdg_ctx::BatchStreamState &S, size_t i) {
@@ -127,6 +130,7 @@ int gdg_batch_stream_checkpoint_size(gdg_ctx *ctx, size_t *bytes) {
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, "checkpoint");
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
     if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
+    if (ctx->out_rec_on) return OUT_RECORDS_HISTORY_REFUSED(ctx, "checkpoint");
     if (!ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     const int rc = checkpoint_plan(ctx, P);
@@ -140,6 +144,7 @@ int gdg_batch_stream_checkpoint(gdg_ctx *ctx, void *blob, size_t capacity, size_
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, "checkpoint");
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
     if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
+    if (ctx->out_rec_on) return OUT_RECORDS_HISTORY_REFUSED(ctx, "checkpoint");
     if (!S.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     int rc = checkpoint_plan(ctx, P);
@@ -277,6 +282,7 @@ static int resume(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
     if (batch_sources_shared(ctx)) return SHARED_SOURCES_REFUSED(ctx, what);
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, what);
     if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, what);
+    if (ctx->out_rec_on) return OUT_RECORDS_HISTORY_REFUSED(ctx, what);
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "%s: a streamed batch run is already open on this context", what);
     CkptHeader h;
     int rc = read_header(ctx, what, blob, bytes, h);

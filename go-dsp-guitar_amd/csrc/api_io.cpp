@@ -339,19 +339,34 @@ int gdg_out_ratio_rows(gdg_ctx *ctx, const double *rows, int n_rows, size_t samp
 }
 
 /* the planner (trim.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
-int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_t blocks, double target, double max_gain, double *gain) {
-    static_assert(sizeof(gdg_block_true_peak) == 2 * sizeof(double) && offsetof(gdg_block_true_peak, true_peak) == 0, "the planner strides over true_peak in doubles");
+/* one planner body for both record kinds: `stride` doubles from one record's true_peak to the next's; `what` words the refusals */
+static int trim_from_records(const char *what, const double *true_peaks, size_t stride, bool given, int ports, size_t blocks, double target, double max_gain, double *gain) {
     int bad = -1;
     char msg[160];
-    switch (gdg_trim_plan(reinterpret_cast<const double *>(records), 2, ports, blocks, target, max_gain, gain, &bad)) {
+    switch (gdg_trim_plan(true_peaks, stride, ports, blocks, target, max_gain, gain, &bad)) {
     case GDG_TRIM_PLAN_OK: return GDG_OK;
-    case GDG_TRIM_PLAN_TARGET: snprintf(msg, sizeof msg, "trim from true peak: target = %g; finite and greater than 0", target); break;
-    case GDG_TRIM_PLAN_MAX_GAIN: snprintf(msg, sizeof msg, "trim from true peak: max_gain = %g; finite and greater than 0", max_gain); break;
-    case GDG_TRIM_PLAN_NAN: snprintf(msg, sizeof msg, "trim from true peak: port %d has a NaN true_peak", bad); break;
-    default: snprintf(msg, sizeof msg, "trim from true peak: %d ports, records %s, gain %s", ports, records ? "given" : "NULL", gain ? "given" : "NULL"); break;
+    case GDG_TRIM_PLAN_TARGET: snprintf(msg, sizeof msg, "%s: target = %g; finite and greater than 0", what, target); break;
+    case GDG_TRIM_PLAN_MAX_GAIN: snprintf(msg, sizeof msg, "%s: max_gain = %g; finite and greater than 0", what, max_gain); break;
+    case GDG_TRIM_PLAN_NAN: snprintf(msg, sizeof msg, "%s: port %d has a NaN true_peak", what, bad); break;
+    default: snprintf(msg, sizeof msg, "%s: %d ports, records %s, gain %s", what, ports, given ? "given" : "NULL", gain ? "given" : "NULL"); break;
     }
     set_free_error(msg);
     return GDG_ERR_INVALID;
+}
+int gdg_trim_from_true_peak(const gdg_block_true_peak *records, int ports, size_t blocks, double target, double max_gain, double *gain) {
+    static_assert(sizeof(gdg_block_true_peak) == 2 * sizeof(double) && offsetof(gdg_block_true_peak, true_peak) == 0, "the planner strides over true_peak in doubles");
+    return trim_from_records("trim from true peak", reinterpret_cast<const double *>(records), 2, records != nullptr, ports, blocks, target, max_gain, gain);
+}
+/* ... and on the delivered rows' records (include/gdg.h, DELIVERED RECORDS): the same rule on their true_peak, five doubles apart */
+int gdg_trim_from_out_records(const gdg_block_delivered *records, int ports, size_t blocks, double target, double max_gain, double *gain) {
+    static_assert(sizeof(gdg_block_delivered) == 5 * sizeof(double) && offsetof(gdg_block_delivered, true_peak) == 0, "the planner strides over true_peak in doubles");
+    if (ports <= 0 || blocks == 0) {                                          /* no record to plan from: refused, where the true-peak form plans nothing */
+        char msg[160];
+        snprintf(msg, sizeof msg, "trim from out records: %d ports x %zu blocks; at least one record per port", ports, blocks);
+        set_free_error(msg);
+        return GDG_ERR_INVALID;
+    }
+    return trim_from_records("trim from out records", reinterpret_cast<const double *>(records), 5, records != nullptr, ports, blocks, target, max_gain, gain);
 }
 
 /* resample/resample.go:72-87 */
@@ -1533,4 +1548,89 @@ int gdg_batch_true_peak(gdg_ctx *ctx, gdg_block_true_peak *records, size_t capac
     static const KindWords words = { "no true-peak records", "has not completed (or none has run since gdg_batch_true_peak_enable)",
                                      "ran without them (gdg_batch_true_peak_enable comes before the call)", "true peak", "records", "call" };
     return batch_kind_get(ctx, REPORT_TRUE_PEAK, ctx && ctx->tp_on, words, records, capacity, ports, blocks, nullptr);
+}
+
+/* ---- the records of the delivered rows (include/gdg.h, DELIVERED RECORDS; the kernels: delivered_kernels.h in io.hip; the batch calls fill them: api_batch.cpp) ---- */
+static_assert(sizeof(gdg_block_delivered) == DELIVERED_RECORD_BYTES && offsetof(gdg_block_delivered, true_peak) == 0 && offsetof(gdg_block_delivered, position) == 24 &&
+              offsetof(gdg_block_delivered, clipped) == 36, "gdg_block_delivered: 40 bytes, no padding");
+
+/* rows, samples and the spans: ascending from 0 to `samples`, every block 1 to 16384 samples */
+static int block_out_check(gdg_ctx *ctx, int n_rows, size_t samples, const size_t *span, size_t n_blocks) {
+    if (n_rows <= 0) return fail(ctx, GDG_ERR_INVALID, "block out rows: %d rows (at least 1)", n_rows);
+    if (!span || n_blocks == 0 || n_blocks > 0x7fffffff) return fail(ctx, GDG_ERR_INVALID, "block out rows: %zu blocks, spans %s; 1 to 2^31 - 1 blocks need their spans", n_blocks, span ? "given" : "NULL");
+    if (span[0] != 0 || span[n_blocks] != samples)
+        return fail(ctx, GDG_ERR_INVALID, "block out rows: the spans run from %zu to %zu; they cover the rows' samples, 0 to %zu", span[0], span[n_blocks], samples);
+    for (size_t k = 0; k < n_blocks; k++)
+        if (span[k + 1] <= span[k] || span[k + 1] - span[k] > (size_t)GDG_OUT_RECORDS_MAX_BLOCK)
+            return fail(ctx, GDG_ERR_INVALID, "block out rows: block %zu is the samples %zu to %zu; a block has 1 to %d samples and the spans ascend", k, span[k], span[k + 1],
+                        GDG_OUT_RECORDS_MAX_BLOCK);
+    return GDG_OK;
+}
+
+int gdg_block_out_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, const size_t *span, size_t n_blocks, double *d_history,
+                              gdg_block_delivered *d_records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const int rc = block_out_check(ctx, n_rows, samples, span, n_blocks);
+    if (rc != GDG_OK) return rc;
+    if (!d_rows || !d_records) return fail(ctx, GDG_ERR_INVALID, "block out rows: %s is NULL", !d_rows ? "the rows' pointer" : "the records' pointer");
+    if (row_stride < samples) return fail(ctx, GDG_ERR_INVALID, "block out rows: a row stride of %zu samples for rows of %zu", row_stride, samples);
+    if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_records & 7) || ((uintptr_t)d_history & 7)) return fail(ctx, GDG_ERR_INVALID, "block out rows: rows, history and records are 8-byte aligned");
+    enter_keep_fir_sums(ctx);
+    /* the spans go up from the context's own copy: whatever the last call's launch still reads has to be done before either copy changes */
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t bytes = (n_blocks + 1) * sizeof(unsigned long long);
+    if (bytes > ctx->d_out_rows_spans_cap) {
+        hipFree(ctx->d_out_rows_spans);
+        ctx->d_out_rows_spans = nullptr;
+        ctx->d_out_rows_spans_cap = 0;
+        if (hipMalloc((void **)&ctx->d_out_rows_spans, bytes) != hipSuccess) return fail(ctx, GDG_ERR_NOMEM, "block out rows: cannot allocate the spans of %zu blocks on the device", n_blocks);
+        ctx->d_out_rows_spans_cap = bytes;
+    }
+    ctx->out_rows_spans.assign(span, span + n_blocks + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_out_rows_spans, ctx->out_rows_spans.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    ProfScope ps(ctx, GDG_K_WAVE);
+    HIP_TRY(ctx, gdg_launch_block_delivered(d_rows, row_stride, (unsigned)n_rows, samples, ctx->d_out_rows_spans, (unsigned)n_blocks, d_history, true_peak_table(), d_records, ctx->stream));
+    /* behind the records: the last 23 samples of (history ++ rows) are what the next call finds in front of its own */
+    if (d_history) HIP_TRY(ctx, gdg_launch_delivered_history_save(d_rows, row_stride, samples, (unsigned)n_rows, d_history, ctx->stream));
+    return GDG_OK;
+}
+
+int gdg_block_out_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, const size_t *span, size_t n_blocks, double *history, gdg_block_delivered *records) {
+    if (!ctx) return GDG_ERR_INVALID;
+    int rc = block_out_check(ctx, n_rows, samples, span, n_blocks);
+    if (rc != GDG_OK) return rc;
+    if (!rows || !records) return fail(ctx, GDG_ERR_INVALID, "block out rows: %s is NULL", !rows ? "the rows' list" : "the records' pointer");
+    /* rows up into d_io[1] and records down from d_io[0] as the other kinds' go; the history, up before the launch and down behind it, takes a
+     * buffer the call owns -- growing either d_io buffer now would move what is already enqueued */
+    const size_t hist_bytes = history ? (size_t)n_rows * GDG_OUT_RECORDS_HISTORY * sizeof(double) : 0;
+    return rows_round_trip(ctx, "block out rows", rows, n_rows, samples, records, (size_t)n_rows * n_blocks * sizeof(gdg_block_delivered), [&](const double *d_rows, void *d_out) {
+        double *d_hist = nullptr;
+        if (history) {
+            if (hipMalloc((void **)&d_hist, hist_bytes) != hipSuccess) return fail(ctx, GDG_ERR_NOMEM, "block out rows: cannot allocate the history of %d rows on the device", n_rows);
+            const hipError_t e = hipMemcpyAsync(d_hist, history, hist_bytes, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) { hipFree(d_hist); return fail(ctx, GDG_ERR_HIP, "block out rows: %s", hipGetErrorString(e)); }
+        }
+        int r = gdg_block_out_rows_device(ctx, d_rows, samples, n_rows, samples, span, n_blocks, d_hist, static_cast<gdg_block_delivered *>(d_out));
+        if (d_hist) {
+            if (r == GDG_OK && hipMemcpyAsync(history, d_hist, hist_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = GDG_ERR_HIP;
+            hipStreamSynchronize(ctx->stream);
+            hipFree(d_hist);
+        }
+        return r;
+    });
+}
+
+int gdg_batch_out_records(gdg_ctx *ctx, gdg_block_delivered *records, size_t capacity, int *ports, size_t *blocks) {
+    if (!ctx) return GDG_ERR_INVALID;
+    const gdg_ctx::ListRecords &R = ctx->delivered_rec;
+    if (!R.valid)
+        return fail(ctx, GDG_ERR_INVALID, "no records of the delivered rows: the last batch call of this context %s", ctx->out_rec_on
+                    ? "has not completed, was a master finish, or none has run since gdg_batch_out_records_enable" : "ran without them (gdg_batch_out_records_enable comes before the call)");
+    if (ports) *ports = R.count;
+    if (blocks) *blocks = R.blocks;
+    if (!records) return GDG_OK;
+    const size_t n = R.rows * R.blocks;
+    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "out records: room for %zu records, the call has %d ports x %zu blocks = %zu", capacity, R.count, R.blocks, n);
+    if (n) memcpy(records, R.store.data(), R.store.size());
+    return GDG_OK;
 }

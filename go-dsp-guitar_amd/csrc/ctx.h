@@ -353,8 +353,8 @@ struct gdg_ctx {
     hipEvent_t batch_up_ready[2] = { nullptr, nullptr }, batch_begin = nullptr;
     /* the batch run's device buffers, one meaning each for every kind of run (BATCH_INPUTS .. BATCH_SOURCE below): kept from call to call,
      * grown when a slice needs more -- allocating and mapping gigabytes per call cost more than the run (gdg_batch_release frees them) */
-    void *batch_dev[16] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t batch_dev_cap[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    void *batch_dev[18] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    size_t batch_dev_cap[18] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     int stat_batch_dev_kib = 0;                /* option "stat_batch_device_kib": the sum of batch_dev_cap in KiB, made when it is read */
     /* a batch job, how far it has come, and per input the source frames handed over: the context's is the streamed run's
      * (gdg_batch_stream_open .. _close); a one-call run describes its own and leaves this one closed */
@@ -449,6 +449,18 @@ struct gdg_ctx {
      * behind theirs (report_sections.h, transfer_section) and its table lies in batch_dev[BATCH_TRANSFER_TABLE].  Configuration: in no blob. */
     TransferSet transfer;
     ListRecords transfer_rec;
+    /* the records of the delivered rows (gdg_batch_out_records_enable; include/gdg.h, DELIVERED RECORDS): a list record by every rule above with
+     * the shape (ports, 40), in a store of its own -- its section rides behind the transfer records' (report_sections.h, delivered_section).
+     * While the switch is on batch_dev[BATCH_DELIVERED_REC_HISTORY] holds the 23 samples every port keeps from step to step and
+     * batch_dev[BATCH_DELIVERED_REC_SPANS] the block spans of a slice's steps, which out_rec_spans holds on the host until the slice has run; off,
+     * neither exists.  Configuration: in no blob. */
+    bool out_rec_on = false;
+    ListRecords delivered_rec;
+    std::vector<unsigned long long> out_rec_spans;
+    /* ... and the spans of the stand-alone calls' last launch (gdg_block_out_rows): the host's copy, which the upload reads, and the device's */
+    std::vector<unsigned long long> out_rows_spans;
+    unsigned long long *d_out_rows_spans = nullptr;
+    size_t d_out_rows_spans_cap = 0;
     /* options "stat_batch_upload_bytes" / "stat_batch_resampled_samples": input file bytes moved to the device and output samples the
      * Lanczos sum was evaluated for, by the last batch run call or slice; the int fields are made (saturated) when they are read */
     unsigned long long batch_up_bytes = 0, batch_resampled = 0;
@@ -763,6 +775,7 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
     ctx->align_live_ref.clear();
     for (gdg_ctx::ListRecords &R : ctx->list_rec) R.valid = R.live = false;      /* a call that collects list records says so itself (list_begin) */
     ctx->transfer_rec.valid = ctx->transfer_rec.live = false;                    /* ... and transfer records (transfer_begin) */
+    ctx->delivered_rec.valid = ctx->delivered_rec.live = false;                  /* ... and the delivered rows' records (delivered_begin) */
     /* any other count was refused when the job was described; a list without the call's blend ports: each of them references itself */
     if (align && ((int)ctx->align_ref.size() == ports || (blend_ports > 0 && (int)ctx->align_ref.size() == ports - blend_ports))) {
         ctx->align_live_ref = ctx->align_ref;
@@ -830,8 +843,28 @@ static inline void transfer_file(gdg_ctx *ctx, const unsigned char *section, siz
     gdg_ctx::ListRecords &R = ctx->transfer_rec;
     list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
 }
+/* the delivered rows' records: what a call sends down per block while the switch is on -- one record of 40 bytes per port */
+static inline ListShape delivered_shape(const gdg_ctx *ctx, size_t ports) { return { ctx->out_rec_on ? ports : 0, ctx->out_rec_on ? (size_t)DELIVERED_RECORD_BYTES : 0 }; }
+/* list_begin and list_file for their own store */
+static inline void delivered_begin(gdg_ctx *ctx, size_t ports, size_t blocks) {
+    const ListShape shape = delivered_shape(ctx, ports);
+    gdg_ctx::ListRecords &R = ctx->delivered_rec;
+    R.live = shape.on();
+    if (!R.live) return;
+    R.count = (int)ports;
+    R.rows = shape.rows;
+    R.elem = shape.elem;
+    R.blocks = blocks;
+    R.store.assign(R.rows * blocks * R.elem, 0);
+}
+static inline void delivered_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
+    gdg_ctx::ListRecords &R = ctx->delivered_rec;
+    list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
+}
 /* ... and has completed (rc == GDG_OK) or not */
 static inline int report_end(gdg_ctx *ctx, int rc) {
+    ctx->delivered_rec.valid = ctx->delivered_rec.live && rc == GDG_OK;
+    ctx->delivered_rec.live = false;
     ctx->transfer_rec.valid = ctx->transfer_rec.live && rc == GDG_OK;
     ctx->transfer_rec.live = false;
     for (gdg_ctx::ListRecords &R : ctx->list_rec) {
@@ -876,6 +909,8 @@ enum {
     BATCH_DELIVER_RATIO_ROWS,              /* [N + 3 + blends][pitch] one step's rows behind the ratio stage, what the encoders then read; only while a delivery ratio is in force (gdg_batch_set_out_ratio) */
     BATCH_DELIVER_RATIO_HISTORY,           /* [N + 3 + blends][127] the intermediate rows' last samples of the step before, only while a delivery ratio is in force */
     BATCH_DELIVER_RATIO_TABLE,             /* [T][up] the ratio's taps, only while a delivery ratio is in force */
+    BATCH_DELIVERED_REC_HISTORY,           /* [N + 3 + blends][23] the encoders' rows' last samples of the step before, only while the delivered rows' records are on (gdg_batch_out_records_enable) */
+    BATCH_DELIVERED_REC_SPANS,             /* per step of a slice its w + 1 block spans, 64-bit, only while the delivered rows' records are on */
     BATCH_DEV_SLOTS
 };
 static_assert(sizeof(gdg_ctx::batch_dev) / sizeof(void *) == BATCH_DEV_SLOTS && sizeof(gdg_ctx::batch_dev_cap) / sizeof(size_t) == BATCH_DEV_SLOTS,

@@ -369,6 +369,13 @@ hipError_t gdg_launch_deliver_ratio(int up, int down, const double *d_rows, size
                                     const double *d_history, double *d_out, size_t out_stride, size_t pad_to, hipStream_t s);
 /* ... and behind it: the rows' last 127 samples into d_history[n_rows][127]; a launch of fewer moves the old ones up */
 hipError_t gdg_launch_deliver_ratio_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
+/* the records of the delivered rows (io.hip, delivered_kernels.h; include/gdg.h, DELIVERED RECORDS): n_rows rows of `samples` float64 cut into
+ * n_blocks blocks by d_span[0 .. n_blocks] (device memory; ascending from 0 to `samples`, lengths 1 to 16384: held by the caller against the
+ * host's copy) -> d_records[n_rows][n_blocks] of 40 bytes.  d_history: null or [n_rows][23], read, never written. */
+hipError_t gdg_launch_block_delivered(const double *d_rows, size_t row_stride, unsigned n_rows, size_t samples, const unsigned long long *d_span, unsigned n_blocks,
+                                      const double *d_history, const gdg_true_peak_table &taps, void *d_records, hipStream_t s);
+/* ... and behind it: the last 23 samples of (history ++ rows) into d_history[n_rows][23] */
+hipError_t gdg_launch_delivered_history_save(const double *d_rows, size_t row_stride, size_t samples, unsigned n_rows, double *d_history, hipStream_t s);
 /* the blend fit's records (include/gdg.h, FIT; io.hip, fit_kernels.h): per fit and block of `block` samples (the last of a row may be short)
  * one gdg_block_fit, d_records[n_fits][ceil(samples / block)].  A fit is target | terms | port[8] (blend.h, FitSet): h_table is the host's copy
  * of the device's d_table, held against n_rows before anything is launched. */

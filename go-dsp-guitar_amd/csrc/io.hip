@@ -1145,6 +1145,7 @@ hipError_t gdg_launch_block_stats(const double *d_rows, size_t row_stride, unsig
 #include "fit_kernels.h"            /* the blend fit's records: inner products of the window's rows in block_stats_kernel's order of sums */
 #include "deliver_kernels.h"        /* the delivery at a half or a quarter of the session rate: the window's rows decimated in front of the encoders */
 #include "deliver_ratio_kernels.h"  /* ... and the ratio stage behind it: the intermediate rows resampled by L / M, polyphase */
+#include "delivered_kernels.h"      /* the records of the delivered rows: blocks of any length, a true peak that is seamless across them */
 
 /* resample.Time over a span of a file (the streamed batch run): blockIdx.y = input. Output samples [out_first, out_first + count) from
  * the source frames [src_first, src_first + src_count) at `src`; n = the FILE's frames (the j < n bound).  x, floor(x) and x - j are

@@ -93,6 +93,12 @@ static inline ListSections list_sections(size_t end, const ListShape *shape, siz
 static inline size_t transfer_record_bytes(size_t pairs, size_t group) { return pairs && group ? pairs * (4096 / group + 1) * 4 * 8 : 0; }
 static inline ListSection transfer_section(const ListSections &lists, const ListShape &shape, size_t w) { return list_section(lists.end, shape, w); }
 
+/* The records of the delivered rows (include/gdg.h, DELIVERED RECORDS) ride behind the transfer records' section, from the next 16 bytes on, as
+ * [ports][w] records of 40 bytes -- the shape (ports, 40) through the same list_section and list_room, filed by list_file_rows.  Off: no byte,
+ * and `end` is the transfer section's. */
+enum { DELIVERED_RECORD_BYTES = 40 };
+static inline ListSection delivered_section(const ListSection &transfer, const ListShape &shape, size_t w) { return list_section(transfer.end, shape, w); }
+
 /* Filing a section that has come down: [rows][w] elements into a store of [rows][blocks], under the blocks from b0 on. */
 static inline void list_file_rows(unsigned char *store, size_t blocks, const ListShape &shape, const unsigned char *section, size_t w, size_t b0) {
     for (size_t r = 0; r < shape.rows; r++) memcpy(store + (r * blocks + b0) * shape.elem, section + r * w * shape.elem, w * shape.elem);

@@ -3486,3 +3486,208 @@ func MatchTapsFromTransfer(records [][]float64, nPairs int, group int, ridge flo
 	}
 	return taps, coherence, nil
 }
+
+// BlockDelivered: one record of a delivered block (gdg_block_delivered; include/gdg.h, DELIVERED RECORDS): the samples' peak, sum of squares
+// and clipped count in the block statistics' order at the block's length, and a true peak over the block's samples and the interpolated
+// points that complete in it -- seamless across blocks.  Position = 4*(n - o) + phase of the first point that attains TruePeak, o the
+// block's first sample; it can be as low as -47.
+type BlockDelivered struct {
+	TruePeak  float64
+	Peak      float64
+	SumSq     float64
+	Position  int32
+	PeakIndex uint32
+	Overs     uint32
+	Clipped   uint32
+}
+
+func goBlockDelivered(p unsafe.Pointer, rows int, blocks int) [][]BlockDelivered {
+	out := make([][]BlockDelivered, rows)
+	if rows*blocks == 0 {
+		for r := range out {
+			out[r] = []BlockDelivered{}
+		}
+		return out
+	}
+	recs := (*[1 << 25]C.gdg_block_delivered)(p)[: rows*blocks : rows*blocks]
+	for r := range out {
+		out[r] = make([]BlockDelivered, blocks)
+		for b := range out[r] {
+			c := recs[r*blocks+b]
+			out[r][b] = BlockDelivered{float64(c.true_peak), float64(c.peak), float64(c.sum_sq), int32(c.position), uint32(c.peak_index), uint32(c.overs), uint32(c.clipped)}
+		}
+	}
+	return out
+}
+
+// BlockDeliveredRows: the records of equally long host rows cut into blocks by span[0 .. nBlocks] -- ascending, span[0] = 0, the last the
+// rows' length, every block 1 to 16384 samples (gdg_block_out_rows); result[row][block].  history: nil (zeros stand in front of the rows,
+// nothing is kept) or nRows*23 float64, the newest last, read before and written after: two calls that continue each other through it give
+// the records of the one call.
+func (this *Context) BlockDeliveredRows(rows [][]float64, span []int, history []float64) ([][]BlockDelivered, error) {
+	n := len(rows)
+	if n == 0 || len(span) < 2 {
+		return nil, fmt.Errorf("gdg: BlockDeliveredRows needs rows and the spans of at least one block")
+	}
+	if history != nil && len(history) != n*23 {
+		return nil, fmt.Errorf("gdg: a history of %d values for %d rows; 23 per row", len(history), n)
+	}
+	samples := len(rows[0])
+	blocks := len(span) - 1
+	var owned []unsafe.Pointer
+	defer func() {
+		for _, p := range owned {
+			C.free(p)
+		}
+	}()
+	rp := (*[1 << 20]*C.double)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))
+	if rp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(rp))
+	for i, r := range rows {
+		if len(r) != samples {
+			return nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), samples)
+		}
+		p := C.malloc(C.size_t(samples*8 + 8))
+		if p == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, p)
+		copy((*[1 << 37]float64)(p)[:samples:samples], r)
+		rp[i] = (*C.double)(p)
+	}
+	sp := (*[1 << 28]C.size_t)(C.calloc(C.size_t(len(span)), 8))
+	if sp == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, unsafe.Pointer(sp))
+	for i, v := range span {
+		if v < 0 {
+			return nil, fmt.Errorf("gdg: span %d is %d", i, v)
+		}
+		sp[i] = C.size_t(v)
+	}
+	var hp *C.double
+	if history != nil {
+		h := C.malloc(C.size_t(n * 23 * 8))
+		if h == nil {
+			return nil, fmt.Errorf("gdg: out of memory")
+		}
+		owned = append(owned, h)
+		copy((*[1 << 30]float64)(h)[:n*23:n*23], history)
+		hp = (*C.double)(h)
+	}
+	out := C.calloc(C.size_t(n*blocks+1), 40)
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	owned = append(owned, out)
+	if e := this.err(C.gdg_block_out_rows(this.ctx, &rp[0], C.int(n), C.size_t(samples), &sp[0], C.size_t(blocks), hp, (*C.gdg_block_delivered)(out))); e != nil {
+		return nil, e
+	}
+	if history != nil {
+		copy(history, (*[1 << 30]float64)(unsafe.Pointer(hp))[:n*23:n*23])
+	}
+	return goBlockDelivered(out, n, blocks), nil
+}
+
+// BlockDeliveredRowsDevice: the same on device memory, enqueued on the context's stream (gdg_block_out_rows_device): row r at
+// dRows + r*rowStride float64 (any 8-byte alignment, rowStride >= samples), span a host slice, dHistory nil or nRows*23 float64 on the
+// device, the records into dRecords[nRows][len(span)-1].
+func (this *Context) BlockDeliveredRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, samples int, span []int, dHistory unsafe.Pointer, dRecords unsafe.Pointer) error {
+	if len(span) < 2 {
+		return fmt.Errorf("gdg: BlockDeliveredRowsDevice needs the spans of at least one block")
+	}
+	sp := (*[1 << 28]C.size_t)(C.calloc(C.size_t(len(span)), 8))
+	if sp == nil {
+		return fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(sp))
+	for i, v := range span {
+		if v < 0 {
+			return fmt.Errorf("gdg: span %d is %d", i, v)
+		}
+		sp[i] = C.size_t(v)
+	}
+	return this.err(C.gdg_block_out_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(samples), &sp[0], C.size_t(len(span)-1),
+		(*C.double)(dHistory), (*C.gdg_block_delivered)(dRecords)))
+}
+
+// BatchDeliveredEnable: from the next batch call on, BatchRun and BatchStreamStep keep the records of the rows the encoders read -- the
+// delivered rows, in front of the trim and blend gains -- of every encoded port (gdg_batch_out_records_enable); off by default.
+// Configuration: a checkpoint does not carry it, an error while a streamed job is open; the checkpoint, shard and master-finish calls
+// refuse while it is on.
+func (this *Context) BatchDeliveredEnable(enable bool) error {
+	v := C.int(0)
+	if enable {
+		v = 1
+	}
+	return this.err(C.gdg_batch_out_records_enable(this.ctx, v))
+}
+
+// BatchDelivered: the records of the delivered rows of the last completed batch call, result[port][block] (gdg_batch_out_records).  An
+// error when the call ran without them.
+func (this *Context) BatchDelivered() ([][]BlockDelivered, error) {
+	var ports C.int
+	var blocks C.size_t
+	if e := this.err(C.gdg_batch_out_records(this.ctx, nil, 0, &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	n := int(ports) * int(blocks)
+	if n == 0 {
+		return goBlockDelivered(nil, int(ports), int(blocks)), nil
+	}
+	rec := C.calloc(C.size_t(n), 40)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	if e := this.err(C.gdg_batch_out_records(this.ctx, (*C.gdg_block_delivered)(rec), C.size_t(n), &ports, &blocks)); e != nil {
+		return nil, e
+	}
+	return goBlockDelivered(rec, int(ports), int(blocks)), nil
+}
+
+// TrimFromDelivered: TrimFromTruePeak's rule on the TruePeak of the delivered rows' records (gdg_trim_from_out_records),
+// records[port][block] as BatchDelivered hands them out.  Host arithmetic: no context and no device.
+func TrimFromDelivered(records [][]BlockDelivered, target float64, maxGain float64) ([]float64, error) {
+	ports := len(records)
+	gain := make([]float64, ports)
+	if ports == 0 {
+		return gain, nil
+	}
+	blocks := len(records[0])
+	for r, row := range records {
+		if len(row) != blocks {
+			return nil, fmt.Errorf("gdg: port %d has %d records, port 0 has %d", r, len(row), blocks)
+		}
+		for _, rec := range row {
+			if rec.TruePeak != rec.TruePeak {
+				return nil, fmt.Errorf("gdg: port %d has a NaN true peak", r)
+			}
+		}
+	}
+	rec := (*[1 << 25]C.gdg_block_delivered)(C.calloc(C.size_t(ports*blocks+1), 40))
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(rec))
+	for r, row := range records {
+		for b, v := range row {
+			rec[r*blocks+b].true_peak = C.double(v.TruePeak)
+		}
+	}
+	out := (*[1 << 28]C.double)(C.calloc(C.size_t(ports), 8))
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(out))
+	if rc := C.gdg_trim_from_out_records(&rec[0], C.int(ports), C.size_t(blocks), C.double(target), C.double(maxGain), &out[0]); rc != 0 {
+		return nil, fmt.Errorf("gdg: gdg_trim_from_out_records: %d (target and maxGain: finite and greater than 0)", int(rc))
+	}
+	for i := range gain {
+		gain[i] = float64(out[i])
+	}
+	return gain, nil
+}

@@ -66,6 +66,8 @@ def lib():
             "gdgh_engine_set_batch_transfers": (cs, [vp, i32, vp, vp, i32]),
             "gdgh_engine_batch_transfers": (i32, [vp]),
             "gdgh_engine_last_batch_transfer": (cs, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+            "gdgh_engine_set_batch_delivered": (cs, [vp, i32]),
+            "gdgh_engine_last_batch_delivered": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_last_batch_tapfit": (cs, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_set_batch_blends_filtered": (cs, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
@@ -151,6 +153,8 @@ class Engine:
         self.last_gram = None            # the Gram records of the last batch call made with gram=: [blocks, P (P + 1) / 2] float64
         self.last_transfer = None        # the transfer records of the last batch call made with transfers=: [blocks, pairs x G x 4] float64
         self.last_tapfit = None          # the tap-fit records of the last batch call made with tapfits=: [blocks, D] float64
+        self.last_delivered = None       # the records of the delivered rows of the last batch call made with delivered=True: [N + 3 + B, blocks] records
+        self.normalize_delivered = None  # ... and those of render_normalized(measure="delivered")'s measuring pass
         self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
     def shards(self):
@@ -447,6 +451,23 @@ class Engine:
         _err(lib().gdgh_engine_last_batch_transfer(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
         return out
 
+    def _set_delivered(self, delivered):
+        """Engine::SetBatchDelivered, from the `delivered` argument of the batch calls: keep the records of the rows the encoders read (the
+        delivered rows, in front of the gains).  Returns whether they are on.  Refused on an engine of more than one shard."""
+        self.last_delivered = None
+        _err(lib().gdgh_engine_set_batch_delivered(self._h, int(bool(delivered))))
+        return bool(delivered)
+
+    def _fetch_delivered(self):
+        """Engine::LastBatchDelivered -> [ports, blocks] BLOCK_DELIVERED_DTYPE"""
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        ports, blocks = C.c_int(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_delivered(self._h, None, 0, C.byref(ports), C.byref(blocks)))
+        out = np.zeros((ports.value, blocks.value), dtype=pkg.BLOCK_DELIVERED_DTYPE)
+        _err(lib().gdgh_engine_last_batch_delivered(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+        return out
+
     def match_ir(self, port, target, taps, inputs, target_rate, out_format, group=32, ridge=0.0, center=0, window=16, sample_rate=None, **kw):
         """The match filter of one pass over a job: the `taps`-tap impulse response that, applied to port `port`, comes closest to port
         `target` over the whole band.  save_state; one pass with every output skipped and the one transfer pair (port, target) at group
@@ -693,7 +714,7 @@ class Engine:
         outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=lined, **rest)
         return outs, delays, signs, fractions
 
-    def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, **kw):
+    def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, measure="render", **kw):
         """Two passes over one job: every output file is written with the gain that brings its true peak to target_dbtp (dBTP), capped at
         max_gain_db.  save_state; pass 1 renders with the true-peak records (and the report) on and every output skipped; the planner
         (trim_from_true_peak) turns the records into gains; load_state; pass 2 renders with the trim.  Returns (outs, gains): the N + 3
@@ -701,17 +722,26 @@ class Engine:
         true-peak records like any other port's and passed as its output gain (a blend_gain in kw is replaced).  The master's gains come from the finish's own records of pass 1, whatever the
         shard count.  Pass 1's records stay in normalize_true_peak / normalize_report.  The state blob is the channels': a configured
         metronome and the meters run on from pass 1.  kw: batch_run's other arguments (dither, run_meters ...).  deliver= is carried through
-        both passes unchanged: the gains are planned from the session-rate records, and a delivered file's true peak can differ from the
-        render's (the anti-aliasing filter rings), so leave the headroom the target is meant to leave."""
+        both passes unchanged.  measure="render" (the default): the gains are planned from the session-rate records, and a delivered file's
+        true peak can differ from the render's (the anti-aliasing filter rings), so leave the headroom the target is meant to leave.
+        measure="delivered" (one-shard engines): pass 1 runs with the delivery in force and the records of the delivered rows on; the
+        planner (trim_from_delivered) takes their true peak -- that of the rows the files are encoded from, seamless across blocks -- and
+        the records stay in normalize_delivered: a file normalised to -1 dBTP then measures -1 dBTP."""
+        if measure not in ("render", "delivered"):
+            raise ValueError("measure: 'render' or 'delivered'")
         import __graft_entry__ as entry
         pkg = entry.load_package()
         rate = target_rate if sample_rate is None else sample_rate
         _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
         blob = self.save_state()
-        self.batch_run(inputs, target_rate, out_format, window=window, report=True, true_peak=True, skip_outputs=True,
-                       **{k: v for k, v in kw.items() if k not in ("report", "true_peak", "trim", "blend_gain")})
+        self.batch_run(inputs, target_rate, out_format, window=window, report=True, true_peak=True, skip_outputs=True, delivered=measure == "delivered",
+                       **{k: v for k, v in kw.items() if k not in ("report", "true_peak", "trim", "blend_gain", "delivered")})
         self.normalize_true_peak, self.normalize_report = self.last_true_peak, self.last_report
-        gains = pkg.trim_from_true_peak(self.normalize_true_peak, 10.0 ** (target_dbtp / 20.0), 10.0 ** (max_gain_db / 20.0))
+        if measure == "delivered":
+            self.normalize_delivered = self.last_delivered
+            gains = pkg.trim_from_delivered(self.normalize_delivered, 10.0 ** (target_dbtp / 20.0), 10.0 ** (max_gain_db / 20.0))
+        else:
+            gains = pkg.trim_from_true_peak(self.normalize_true_peak, 10.0 ** (target_dbtp / 20.0), 10.0 ** (max_gain_db / 20.0))
         self.load_state(blob, rate)
         n3 = self.n_channels + 3                              # the trim's ports; the gains behind them are the blend ports'
         outs = self.batch_run(inputs, target_rate, out_format, window=window, trim=gains[:n3], blend_gain=gains[n3:] if gains.size > n3 else None,
@@ -719,7 +749,7 @@ class Engine:
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None, delivered=False):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
@@ -737,7 +767,9 @@ class Engine:
         (factor, up, down) -- delivery_for(192000, 44100) = (4, 147, 160) -- adds the ratio stage behind the factor: each data section has
         batch_delivery_samples(factor, up, down, 0, length) samples and lags by batch_delivery_ratio_latency(factor, up, down).  Every last_*
         record stays that of the session-rate render, so a delivered file's true peak can differ from last_true_peak: the anti-aliasing
-        filter removes what lies above the new Nyquist frequency, and it rings."""
+        filter removes what lies above the new Nyquist frequency, and it rings.  delivered: keep the records of the rows the encoders read
+        -- behind the delivery, in front of the trim and blend gains -- in last_delivered ([N + 3 + B, blocks], BLOCK_DELIVERED_DTYPE; one-shard
+        engines only): their true_peak is the delivered file's, seamless across blocks."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
@@ -749,6 +781,7 @@ class Engine:
         grammed = self._set_gram(gram)
         tapped = self._set_tapfits(tapfits)
         transferred = self._set_transfers(transfers)
+        measured = self._set_delivered(delivered)
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -797,20 +830,23 @@ class Engine:
             self.last_tapfit = self._fetch_tapfit()
         if transferred:
             self.last_transfer = self._fetch_transfer()
+        if measured:
+            self.last_delivered = self._fetch_delivered()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None):
+                     report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None, delivered=False):
         """Engine::BatchStreamOpen / Need / Step / Close over the `inputs` tuples of batch_run, `blocks_per_slice` blocks at a time:
         yields every slice's N + 3 output pieces (and one per blend of blends= / blend_gain=, as batch_run's).  report: last_report grows by every slice's records and is the whole job's,
         [N + 3, blocks], when the generator ends; spectrum=edges: last_spectrum likewise, [N + 3, blocks, bands]; fits=: last_fit likewise,
         [fits, blocks]; gram=: last_gram likewise, [blocks, P (P + 1) / 2]; tapfits=: last_tapfit likewise, [blocks, D].  deliver=: as
-        batch_run's -- every piece has blocks * 8192 // deliver samples; the records stay those of the session-rate render."""
+        batch_run's -- every piece has blocks * 8192 // deliver samples; the records stay those of the session-rate render.  delivered=True:
+        last_delivered grows by every slice's records of the delivered rows, [N + 3 + B, blocks] when the generator ends."""
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
                                   metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
-                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits, transfers=transfers, deliver=deliver)
+                                  blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits, transfers=transfers, deliver=deliver, delivered=delivered)
 
     def batch_stream_sharded_checkpoint(self):
         """Engine::BatchStreamShardedCheckpoint -> bytes: the open sharded job (call it between two slices of batch_stream_sharded)"""
@@ -835,7 +871,7 @@ class Engine:
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
     def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None):
+                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None, delivered=False):
         f_open, f_need, f_step, f_close = calls
         import __graft_entry__ as entry
         pkg = entry.load_package()
@@ -848,6 +884,7 @@ class Engine:
         grammed = self._set_gram(gram)                       # ... and no Gram list
         tapped = self._set_tapfits(tapfits)                  # ... and no tap fits
         transferred = self._set_transfers(transfers)         # ... and no transfer list
+        measured = self._set_delivered(delivered)            # ... and no records of the delivered rows
         self._set_spectrum(spectrum)
         aligned = self._set_align(align)
         peaked = self._set_true_peak(true_peak)
@@ -913,6 +950,9 @@ class Engine:
                 if transferred:
                     tr = self._fetch_transfer()
                     self.last_transfer = tr if self.last_transfer is None else np.concatenate([self.last_transfer, tr], axis=0)
+                if measured:
+                    dl = self._fetch_delivered()
+                    self.last_delivered = dl if self.last_delivered is None else np.concatenate([self.last_delivered, dl], axis=1)
                 yield outs
                 left -= blocks
         finally:

@@ -1177,6 +1177,23 @@ int Engine::applyTransfers(gdg_ctx *ctx) {
     return gdg_batch_transfer_enable(ctx, BatchTransfers(), transferPort_.data(), transferTarget_.data(), transferGroup_);
 }
 
+/* Engine::SetBatchDelivered: the switch of the delivered rows' records; an engine of more shards refuses it, as the library's shard calls would */
+Error Engine::SetBatchDelivered(bool on) {
+    if (on && shards() > 1)
+        return format("SetBatchDelivered: the engine has %d shards: the records are taken from the rows one device's encoders read, and the library's shard and master-finish "
+                      "calls refuse them (gdg_batch_out_records_enable); it needs an engine of one shard", shards());
+    delivered_ = on;
+    return "";
+}
+
+Error Engine::LastBatchDelivered(std::vector<gdg_block_delivered> &records, int *ports, size_t *blocks) const {
+    if (!deliveredValid_) return "LastBatchDelivered: the last batch call kept no records of the delivered rows (SetBatchDelivered comes before the call)";
+    records = lastDelivered_;
+    if (ports) *ports = deliveredPorts_;
+    if (blocks) *blocks = deliveredBlocks_;
+    return "";
+}
+
 Error Engine::LastBatchTransfer(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const {
     if (!transferValid_) return "LastBatchTransfer: the last batch call kept no transfer records (SetBatchTransfers comes before the call)";
     records = lastTransfer_;
@@ -1218,7 +1235,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_out_records_enable(ctx, delivered_) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1296,7 +1313,7 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
  * [N + 3][blocks] in gdg_batch_run's port order and from three sources -- the shards' chain rows, shard 0's metronome row, the finish's two
  * master rows (which carry no alignment records: over shards those rows stay zero) ---- */
 void Engine::reportBegin(size_t blocks) {
-    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = tapFitValid_ = transferValid_ = false;
+    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = tapFitValid_ = transferValid_ = deliveredValid_ = false;
     reportBlocks_ = blocks;
     spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
     const size_t n = (size_t)ports() * blocks;
@@ -1498,7 +1515,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_out_records_enable(ctx, delivered_) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1565,6 +1582,18 @@ Error Engine::recordsOfContext(gdg_ctx *ctx) {
             transferDoubles_ = per;
             if (!lastTransfer_.empty() && gdg_batch_transfer(ctx, lastTransfer_.data(), lastTransfer_.size(), &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
             else transferValid_ = true;
+        }
+    }
+    if (re.empty() && delivered_) {                        /* the delivered rows' records: [ports][blocks] */
+        int nports = 0;
+        size_t blocks = 0;
+        if (gdg_batch_out_records(ctx, nullptr, 0, &nports, &blocks) != GDG_OK) re = gdg_last_error(ctx);
+        else {
+            lastDelivered_.assign((size_t)nports * blocks, gdg_block_delivered{});
+            deliveredPorts_ = nports;
+            deliveredBlocks_ = blocks;
+            if (!lastDelivered_.empty() && gdg_batch_out_records(ctx, lastDelivered_.data(), lastDelivered_.size(), &nports, &blocks) != GDG_OK) re = gdg_last_error(ctx);
+            else deliveredValid_ = true;
         }
     }
     if (re.empty() && BatchTapFits() > 0) {                /* the tap-fit records: [blocks][D] */
@@ -2214,6 +2243,26 @@ const char *gdgh_engine_set_batch_transfers(void *e, int n_pairs, const int *por
     return ret(((Engine *)e)->SetBatchTransfers(pairs, group));
 }
 int gdgh_engine_batch_transfers(void *e) { return ((Engine *)e)->BatchTransfers(); }
+const char *gdgh_engine_set_batch_delivered(void *e, int on) {
+    if (!e) return ret(Error("no engine"));
+    return ret(((Engine *)e)->SetBatchDelivered(on != 0));
+}
+/* records == NULL: the two counts only; capacity in records */
+const char *gdgh_engine_last_batch_delivered(void *e, gdg_block_delivered *records, size_t capacity, int *ports, size_t *blocks) {
+    if (!e) return ret(Error("no engine"));
+    std::vector<gdg_block_delivered> rec;
+    int p = 0;
+    size_t b = 0;
+    Error err = ((Engine *)e)->LastBatchDelivered(rec, &p, &b);
+    if (!err.empty()) return ret(err);
+    if (ports) *ports = p;
+    if (blocks) *blocks = b;
+    if (records) {
+        if (capacity < rec.size()) return ret(Error("LastBatchDelivered: too little room for the records"));
+        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_delivered));
+    }
+    return ret(Error(""));
+}
 /* records == NULL: the two counts only; capacity in doubles */
 const char *gdgh_engine_last_batch_transfer(void *e, double *records, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
     std::vector<double> rec;

@@ -343,6 +343,14 @@ public:
     Error SetBatchTransfers(const std::vector<TransferPair> &pairs, int group);
     int BatchTransfers() const { return (int)transferPort_.size(); }
     Error LastBatchTransfer(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const;
+    /* No reference counterpart.  The records of the delivered rows (include/gdg.h, DELIVERED RECORDS; gdg_batch_out_records_enable): from the
+     * next job on BatchRun and the plain streamed job keep [N + 3 + blends][blocks] gdg_block_delivered records of the rows the encoders read
+     * -- behind the delivery in force, in front of the trim and blend gains -- with a true peak that is seamless across blocks.  One-shard
+     * engines only: the library's shard and master-finish calls refuse the switch, so an engine of more shards refuses it here.  The
+     * checkpoint calls refuse while it is on. */
+    Error SetBatchDelivered(bool on);
+    bool BatchDelivered() const { return delivered_; }
+    Error LastBatchDelivered(std::vector<gdg_block_delivered> &records, int *ports, size_t *blocks) const;
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -435,9 +443,14 @@ private:
     std::vector<double> lastTransfer_;                     /* [blocks][doubles] of the last batch call that kept them */
     size_t transferBlocks_ = 0, transferDoubles_ = 0;
     bool transferValid_ = false;
+    bool delivered_ = false;                               /* SetBatchDelivered; never on on an engine of several shards */
+    std::vector<gdg_block_delivered> lastDelivered_;       /* [ports][blocks] of the last batch call that kept them */
+    int deliveredPorts_ = 0;
+    size_t deliveredBlocks_ = 0;
+    bool deliveredValid_ = false;
     int applyTransfers(gdg_ctx *ctx);                      /* onto a context (more shards: none is in force): a gdg_* status */
     int applyTapFits(gdg_ctx *ctx);                        /* onto a context (more shards: none are in force): a gdg_* status */
-    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivery_ > 1 || deliveryUp_ != 1 || deliveryDown_ != 1; }      /* BatchRun is the library's plain one-call run */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivered_ || delivery_ > 1 || deliveryUp_ != 1 || deliveryDown_ != 1; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */

@@ -1665,6 +1665,84 @@ int gdg_out_ratio_taps(int up, int down, double *taps, int capacity);
 int gdg_out_ratio_rows(gdg_ctx *ctx, const double *rows, int n_rows, size_t samples, int up, int down, size_t first, double *history, double *out, size_t out_capacity);
 int gdg_out_ratio_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, int up, int down, size_t first, double *d_history,
                                   double *d_out, size_t out_stride);
+/*
+ * DELIVERED RECORDS: every record kind above describes the session-rate render.  With a delivery in force what a job writes is something else
+ * -- rows passed through the factor's decimator and perhaps the ratio stage -- and a band-limiting filter moves peaks: a file "normalised to
+ * -1 dBTP" from the render's records can come out above it.  This record measures the rows the encoders read: the delivered rows, in the
+ * blocks the delivery gives them, with a true peak defined over the whole delivered stream -- a short history goes from step to step, as the
+ * delivery stages themselves keep one -- so that no interval at a block boundary is left out.
+ * (The calls of this block are named gdg_block_out_rows, gdg_batch_out_records* and gdg_trim_from_out_records: the census of the factor
+ * stage's exports is taken by the word "deliver", and stays as it is.)
+ */
+typedef struct {
+    double   true_peak;   /* max of |x[i]| over the block's samples and of |v_p[n]| over the points that complete in it */
+    double   peak;        /* max of |x[i]| over the block's samples */
+    double   sum_sq;      /* sum of x[i]^2 over the block's samples, in block_stats_kernel's order at L = the block's length */
+    int32_t  position;    /* 4 (n - o) + p of the first point that attains true_peak, o = the block's first delivered sample; p = 0 for a sample;
+                             can be as low as -47; 0 when true_peak == 0 */
+    uint32_t peak_index;  /* i - o of the first sample that attains peak */
+    uint32_t overs;       /* interpolated points (p = 1, 2, 3) completing in the block with |v| > 1 */
+    uint32_t clipped;     /* samples of the block with |x| > 1 */
+} gdg_block_delivered;    /* 40 bytes, little-endian, no padding */
+/*
+ * BLOCKS: delivered block k of a port is the delivered samples N(8192 k) <= n < N(8192 (k + 1)) with N(s) = gdg_batch_out_samples(factor, up,
+ * down, 0, s): exactly the samples session block k produces.  Its length is 8192 / R behind a factor alone, one of two neighbouring counts
+ * behind a ratio (8192 / 4 * 147 / 160 = 1881.6: 1881 or 1882), between 1024 and 16384 over the admissible ratios.  One record per port and
+ * session block: [ports][blocks], the shape of every other record kind.  With no delivery in force the blocks are the 8192-sample session
+ * blocks: a seamless true peak of a session-rate job.
+ * THE SAMPLES' PART (peak, peak_index, sum_sq, clipped) is gdg_block_stats' definition and order at L = the block's length: thread t of 256
+ * takes the pairs t, t + 256, .. in ascending order into one running sum; a wave reduces by the tree + 32, + 16 .. + 1; the four wave sums are
+ * added in wave order; every square and add is an IEEE-754 double operation rounded on its own.  A non-finite sample is taken as 0 everywhere
+ * in this record (gdg_block_stats.nonfinite already counts them at the session rate).
+ * THE INTERPOLATED PART uses the taps of gdg_true_peak_taps (H = 12, three phases of 24): for interval n, between the samples n and n + 1,
+ *   v_p[n] = sum_j x[n + j] * h_p[j],  j = -H+1 .. H                     the value at position n + p/4
+ * accumulated from 0.0 in ascending j, every product and add rounded on its own.  Interval n belongs to the block that holds sample n + 12,
+ * the last sample it reads: a block needs the 23 samples in front of it and nothing behind it, and every interval of the stream belongs to
+ * exactly one block.  In front of a stream stand zeros, so the twelve intervals that end with the first block's first twelve samples are
+ * evaluated over them (the band-limited onset of the stream).  The last 12 intervals of a job -- the ones that would read beyond its last
+ * sample -- are the only ones never looked at.  "Better" is the greater magnitude, then the lower signed position.
+ * A record is a function of the block's samples and the 23 in front of them alone: not of the window, the slicing, the row or the grid.
+ * Known answers: silence gives all zeros.  An impulse of 1.0 at o + 100 gives true_peak 1.0, position 400 and overs 0.  Two samples of 0.8
+ * at o - 1 and o (the last of block k - 1 and the first of block k) and nothing else: block k has peak 0.8, true_peak = 0.8 (h_2[0] + h_2[1])
+ * ~ 1.0141 (the two centre taps of the half-way phase, each 0.633825), position -2 and overs 1; block k - 1 has true_peak 0.8; and
+ * gdg_block_true_peak_rows on either block alone reports 0.8 -- the hole this record closes.
+ *   gdg_block_out_rows(ctx, rows, n_rows, samples, span, n_blocks, history, records)
+ *                                                      n_rows host rows of `samples` float64 each, cut into n_blocks blocks by span[0 .. n_blocks]:
+ *                                                      ascending, span[0] = 0, span[n_blocks] = samples, every length 1 to 16384 -- anything
+ *                                                      else is refused.  records: [n_rows][n_blocks], row-major.  history: NULL (zeros stand in
+ *                                                      front, nothing is kept) or [n_rows][23] doubles, the newest last, read before and
+ *                                                      written after (a call of fewer than 23 samples moves the old ones up): two calls that
+ *                                                      continue each other through it give the records of the one call
+ *   gdg_block_out_rows_device(ctx, d_rows, row_stride, n_rows, samples, span, n_blocks, d_history, d_records)
+ *                                                      the same on device memory, enqueued on gdg_ctx_stream: row r at d_rows + r * row_stride
+ *                                                      (row_stride >= samples, any 8-byte alignment); span stays a host array; no sample
+ *                                                      outside [row, row + samples) is read
+ *   gdg_batch_out_records_enable(ctx, enable)          from the next batch call on, gdg_batch_run and gdg_batch_stream_step keep the records of
+ *                                                      every encoded port -- chain outputs, master left and right, metronome, blends, in the
+ *                                                      encoders' order -- taken from the rows the encoders read, BEFORE the trim or blend gain (a
+ *                                                      gain g scales true_peak and peak by |g| up to one rounding).  The delivery stages run
+ *                                                      whether or not the call passes output buffers.  State: 23 doubles per port, zeroed by a
+ *                                                      job's first slice, kept from step to step and slice to slice, freed when the switch goes
+ *                                                      off.  Off (the default): no launch, buffer or byte differs.  GDG_ERR_INVALID while a
+ *                                                      streamed job is open.  Configuration: part of no blob
+ *   gdg_batch_out_records(ctx, records, capacity, &ports, &blocks)
+ *                                                      the records of the LAST COMPLETED batch call, [ports][blocks] row-major; records == NULL:
+ *                                                      the counts only.  GDG_ERR_INVALID when capacity < ports * blocks or there are none
+ *   gdg_trim_from_out_records(records, ports, blocks, target, max_gain, gain)
+ *                                                      gdg_trim_from_true_peak's rule on this record's true_peak; ports and blocks are at
+ *                                                      least 1 (GDG_ERR_INVALID otherwise, as for NULL records or gain)
+ * The records come down with each step's own download, behind the transfer records.  GDG_ERR_UNSUPPORTED while the switch is on,
+ * gdg_last_error naming gdg_batch_out_records_enable: the checkpoint and resume calls (the history is not in the version-1 container), the
+ * shard calls, gdg_batch_finish_master and gdg_batch_finish_master_slice.
+ */
+#define GDG_OUT_RECORDS_HISTORY 23
+#define GDG_OUT_RECORDS_MAX_BLOCK 16384
+int gdg_block_out_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size_t samples, const size_t *span, size_t n_blocks, double *history, gdg_block_delivered *records);
+int gdg_block_out_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t samples, const size_t *span, size_t n_blocks, double *d_history,
+                              gdg_block_delivered *d_records);
+int gdg_batch_out_records_enable(gdg_ctx *ctx, int enable);
+int gdg_batch_out_records(gdg_ctx *ctx, gdg_block_delivered *records, size_t capacity, int *ports, size_t *blocks);
+int gdg_trim_from_out_records(const gdg_block_delivered *records, int ports, size_t blocks, double target, double max_gain, double *gain);
 
 #ifdef __cplusplus
 
