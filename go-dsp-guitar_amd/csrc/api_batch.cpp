@@ -54,6 +54,25 @@ static int batch_buffer(gdg_ctx *ctx, int i, size_t bytes, void **out) {
     return GDG_OK;
 }
 
+/* the slots `slots` go: freed, and made anew at the size then asked for by the next batch_buffer.  Whatever still reads them is done (the caller has waited). */
+static void batch_drop(gdg_ctx *ctx, std::initializer_list<int> slots) {
+    for (int i : slots) {
+        hipFree(ctx->batch_dev[i]);
+        ctx->batch_dev[i] = nullptr;
+        ctx->batch_dev_cap[i] = 0;
+    }
+}
+
+/* A history the job carries from slice to slice in slot `slot`, `bytes` long: the job's first slice (pos == 0) begins from zeros, every later one
+ * from what the slice before left -- which is lost when the slot had to be made (gdg_batch_release between two slices).  `whose` words that. */
+static int carried_history(gdg_ctx *ctx, int slot, size_t bytes, size_t pos, const char *whose, double **d) {
+    const bool fresh = ctx->batch_dev_cap[slot] < bytes;
+    if (const int r = batch_buffer(ctx, slot, bytes, (void **)d)) return r;
+    if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the %s history of the open job is gone (gdg_batch_release between two slices?)", whose);
+    if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(*d, 0, bytes, ctx->stream));
+    return GDG_OK;
+}
+
 /* the frames every resampled input keeps for its next step: the same few bytes for every job of the context's channels */
 int batch_carry_buffer(gdg_ctx *ctx, double **d_carry) {
     return batch_buffer(ctx, BATCH_CARRY, (size_t)ctx->nch * GDG_STREAM_CARRY * sizeof(double), (void **)d_carry);
@@ -64,7 +83,7 @@ int gdg_batch_release(gdg_ctx *ctx) {
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "a streamed batch run is open on this context: its buffers are in use");
     enter(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < BATCH_DEV_SLOTS; i++) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    for (int i = 0; i < BATCH_DEV_SLOTS; i++) batch_drop(ctx, { i });
     return GDG_OK;
 }
 
@@ -122,11 +141,10 @@ struct BatchLoop {
     /* while a term reaches back (a delay, or taps behind the first): the context's history of the N chain rows -- what the step before left
      * of them, zeros at the job's start; null otherwise, and then no sample a term reads lies in front of the job */
     double *d_blend_history;
-    /* the list records (report_sections.h: the blend fits, the Gram list, the tap fits): per kind the list's table on the host and on the
-     * device, the entries it counts and what it sends down per block; count 0 and a shape that is off = off, and always for a shard */
+    /* the list records (report_sections.h: the blend fits, the Gram list, the tap fits, the transfer list, the delivered rows' records): per
+     * kind the list's table on the host and on the device (null for the delivered rows' records, which have none), the entries it counts
+     * and what it sends down per block; count 0 and a shape that is off = off, and always for a shard */
     struct List { const int *h_table, *d_table; int count; ListShape shape; } list[LIST_KINDS];
-    /* ... and the transfer list (include/gdg.h, TRANSFER) in the same terms: its section rides behind theirs; count 0 = off, and always for a shard */
-    List transfer;
     /* the delivery (include/gdg.h, DELIVERY; deliver.h): the factor (0 or 1 = off, and always for a shard), the scratch rows [NR][ws / R] the
      * encoders read instead of the window, the factor's taps on the device and the window rows' history [NR][154] */
     int deliver;
@@ -138,9 +156,8 @@ struct BatchLoop {
     double *d_ratio_rows, *d_ratio_history;
     const double *d_ratio_taps;
     size_t ratio_stride;
-    /* the records of the delivered rows (include/gdg.h, DELIVERED RECORDS; a shape that is off = off, and always for a shard): what a step sends
-     * down per block, the 23 samples every encoded row keeps from step to step, [NR][23], and room for the steps' block spans on the device */
-    ListShape delivered;
+    /* what the records of the delivered rows (list[LIST_DELIVERED]; include/gdg.h, DELIVERED RECORDS) read beside the rows: the 23 samples every
+     * encoded row keeps from step to step, [NR][23], and room for the steps' block spans on the device */
     double *d_out_rec_history;
     unsigned long long *d_out_rec_spans;
 };
@@ -187,7 +204,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     int r;
     /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
     if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; ListSections lists; ListSection transfer, delivered; size_t span_at; };
+    struct Step { size_t off; int w; ReportSections sec; ListSections lists; size_t span_at; };
     std::vector<Step> steps;
     /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
      * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
@@ -199,7 +216,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         job_step(p.job_blocks, W, at, &first, &w1);
         const size_t room = std::min(first + (size_t)w1, end) - at;
         while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {}, {}, {}, {}, 0 });
+        steps.push_back({ off, w, {}, {}, 0 });
         off += (size_t)w * B;
     }
     /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
@@ -212,16 +229,15 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
     };
     const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NR;
-    const ListShape list_shape[LIST_KINDS] = { p.list[LIST_FIT].shape, p.list[LIST_GRAM].shape, p.list[LIST_TAPFIT].shape };
+    ListShape list_shape[LIST_KINDS];
+    for (int k = 0; k < LIST_KINDS; k++) list_shape[k] = p.list[k].shape;
     for (size_t i = 0; i < steps.size(); i++) {
         steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
-        steps[i].lists = list_sections(steps[i].sec.end, list_shape, (size_t)steps[i].w);        /* behind the last of them: [fits][w], [w], [w] */
-        steps[i].transfer = transfer_section(steps[i].lists, p.transfer.shape, (size_t)steps[i].w);  /* ... and the transfer records behind those: [w] */
-        steps[i].delivered = delivered_section(steps[i].transfer, p.delivered, (size_t)steps[i].w);  /* ... and the delivered rows' records behind those: [NR][w] */
+        steps[i].lists = list_sections(steps[i].sec.end, list_shape, (size_t)steps[i].w);        /* behind the last of them: [fits][w], [w], [w], [w], [NR][w] */
     }
     /* the delivered rows' blocks: session block j of a step delivers the samples [span[j], span[j + 1]) of the step's rows, counted where every
      * other count of a delivered step comes from (deliver.h); all steps' spans go up once, ahead of everything the loop enqueues */
-    if (p.delivered.on()) {
+    if (p.list[LIST_DELIVERED].count) {
         std::vector<unsigned long long> &spans = ctx->out_rec_spans;
         spans.clear();
         for (Step &st : steps) {
@@ -245,7 +261,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
     double2 *align_tw = nullptr, *align_tw2 = nullptr;
     if (p.align && (r = fir_tables(ctx, GDG_ALIGN_BLOCK, &align_tw, &align_tw2)) != GDG_OK) return r;
     double2 *transfer_tw = nullptr;
-    if (p.transfer.count && (r = fir_tables(ctx, GDG_TRANSFER_BLOCK, &transfer_tw, &align_tw2)) != GDG_OK) return r;      /* the same transform's tables as the alignment's */
+    if (p.list[LIST_TRANSFER].count && (r = fir_tables(ctx, GDG_TRANSFER_BLOCK, &transfer_tw, &align_tw2)) != GDG_OK) return r;      /* the same transform's tables as the alignment's */
     auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
     auto chunk_rows = [&](size_t i, int c) { return deliver_chunk_row((size_t)enc_rows, c, chunks_of(i)); };      /* first encoded row of piece c */
     auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
@@ -273,8 +289,6 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
         for (int k = 0; k < LIST_KINDS; k++)
             if (p.list[k].count) list_file(ctx, k, src + steps[i].lists.of[k].at, (size_t)steps[i].w, steps[i].off / B);
-        if (p.transfer.count) transfer_file(ctx, src + steps[i].transfer.at, (size_t)steps[i].w, steps[i].off / B);
-        if (p.delivered.on()) delivered_file(ctx, src + steps[i].delivered.at, (size_t)steps[i].w, steps[i].off / B);
         return GDG_OK;
     };
     HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
@@ -341,14 +355,14 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             }
             /* the list records of the same rows, the blends' among them: the fits' inner products, then the Gram of the listed rows and the
              * tap fits' Gram of shifted rows on the matrix cores */
-            for (int k = 0; k < LIST_KINDS; k++)
+            for (int k = 0; k < LIST_LAUNCHERS; k++)
                 if (p.list[k].count)
                     HIP_TRY(ctx, list_launch[k](d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.list[k].h_table, p.list[k].d_table, (unsigned)p.list[k].count,
                                                 enc + steps[i].lists.of[k].at, ctx->stream));
             /* ... and the transfer records of the same rows: a block of the loop is a block of the record (8192 samples) */
-            if (p.transfer.count)
-                HIP_TRY(ctx, gdg_launch_block_transfer(d_win, ws, (unsigned)NR, (size_t)wb, p.transfer.h_table, p.transfer.d_table, (unsigned)p.transfer.count, transfer_tw,
-                                                       enc + steps[i].transfer.at, ctx->stream));
+            if (const BatchLoop::List &T = p.list[LIST_TRANSFER]; T.count)
+                HIP_TRY(ctx, gdg_launch_block_transfer(d_win, ws, (unsigned)NR, (size_t)wb, T.h_table, T.d_table, (unsigned)T.count, transfer_tw,
+                                                       enc + steps[i].lists.of[LIST_TRANSFER].at, ctx->stream));
             /* dither on: n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
             /* trim on: `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
             /* delivered: the rows are the scratch rows' -- a row enc_stride apart (ws / R, behind a ratio its fixed pitch), ds.pitch samples of it (wb / R,
@@ -377,9 +391,9 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             }
             /* the records of the rows the encoders are about to read, in front of any gain: the step's w blocks as the delivery cut them, the 23
              * samples in front of the step from the history, which the step's tail replaces behind the launch */
-            if (p.delivered.on()) {
+            if (p.list[LIST_DELIVERED].count) {
                 HIP_TRY(ctx, gdg_launch_block_delivered(enc_src, enc_stride, (unsigned)NR, ds.samples, p.d_out_rec_spans + steps[i].span_at, (unsigned)w, p.d_out_rec_history,
-                                                        true_peak_table(), enc + steps[i].delivered.at, ctx->stream));
+                                                        true_peak_table(), enc + steps[i].lists.of[LIST_DELIVERED].at, ctx->stream));
                 HIP_TRY(ctx, gdg_launch_delivered_history_save(enc_src, enc_stride, ds.samples, (unsigned)NR, p.d_out_rec_history, ctx->stream));
             }
             if (!sharded) {
@@ -408,7 +422,7 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
         unsigned char *enc = d_enc + h * enc_bytes;
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = step_of((size_t)steps[i].w, steps[i].off, 0).row_bytes;
-        const size_t down = steps[i].delivered.end;
+        const size_t down = steps[i].lists.end;
         const int K = chunks_of(i);
         for (int c = 0; c < K; c++) {
             size_t b0 = 0, b1 = 0;
@@ -587,9 +601,7 @@ static int set_delivery(gdg_ctx *ctx, const char *what, int factor, int up, int 
      * refuses the call with the factor in force untouched.  The halves are made anew by the next batch call, at the size of a context that
      * was always configured like this one; back at 1 the scratch rows and the history go as well (the next job with a factor begins from zeros anyway) */
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i : { (int)BATCH_ENCODED, (int)BATCH_DELIVERED, (int)BATCH_DELIVER_HISTORY, (int)BATCH_DELIVER_RATIO_ROWS, (int)BATCH_DELIVER_RATIO_HISTORY, (int)BATCH_DELIVER_RATIO_TABLE }) {
-        hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0;
-    }
+    batch_drop(ctx, { BATCH_ENCODED, BATCH_DELIVERED, BATCH_DELIVER_HISTORY, BATCH_DELIVER_RATIO_ROWS, BATCH_DELIVER_RATIO_HISTORY, BATCH_DELIVER_RATIO_TABLE });
     ctx->deliver = factor;
     ctx->deliver_up = up;
     ctx->deliver_down = down;
@@ -631,7 +643,7 @@ int gdg_batch_out_records_enable(gdg_ctx *ctx, int enable) {
      * fails refuses the call with the switch untouched.  The halves are made anew by the next batch call, at the size of a context that was
      * always configured like this one. */
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i : { (int)BATCH_ENCODED, (int)BATCH_DELIVERED_REC_HISTORY, (int)BATCH_DELIVERED_REC_SPANS }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+    batch_drop(ctx, { BATCH_ENCODED, BATCH_DELIVERED_REC_HISTORY, BATCH_DELIVERED_REC_SPANS });
     ctx->out_rec_on = on;
     return GDG_OK;
 }
@@ -658,11 +670,11 @@ int gdg_batch_set_blends_filtered(gdg_ctx *ctx, int n_blends, const int *first, 
     if (resize || had_delay) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     gdg_blend_replace(ctx->blend, n_blends, first, channel, weight, delay, tap_first, tap, gain, ctx->nch, &b, &k);      /* checked above: it cannot refuse */
     /* no term reaches back any more: the history goes (the next job with one begins from zeros anyway) */
-    if (had_delay && ctx->blend.max_reach() == 0) { hipFree(ctx->batch_dev[BATCH_BLEND_HISTORY]); ctx->batch_dev[BATCH_BLEND_HISTORY] = nullptr; ctx->batch_dev_cap[BATCH_BLEND_HISTORY] = 0; }
+    if (had_delay && ctx->blend.max_reach() == 0) batch_drop(ctx, { BATCH_BLEND_HISTORY });
     if (resize) {
         /* the window and the encoded halves are made anew by the next batch call, at the size of a context that was always configured like
          * this one; off, the table goes as well */
-        for (int i : { (int)BATCH_WINDOW, (int)BATCH_ENCODED }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+        batch_drop(ctx, { BATCH_WINDOW, BATCH_ENCODED });
         if (ctx->blend.count() == 0) { hipFree(ctx->d_blend); ctx->d_blend = nullptr; ctx->d_blend_cap = 0; }
     }
     return GDG_OK;
@@ -682,17 +694,17 @@ int gdg_batch_blend_max_delay(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_
 int gdg_batch_blend_max_reach(const gdg_ctx *ctx) { return ctx ? ctx->blend.max_reach() : 0; }
 
 /* Whether taking a new list of kind k drops the last call's records of that kind.  A fit record carries its own term count and stays
- * readable; a Gram or tap-fit record is read with the list that made it. */
-static const bool list_enable_drops_records[LIST_KINDS] = { false, true, true };
+ * readable; a Gram, tap-fit or transfer record is read with the list that made it.  (The delivered rows' records have no list to take.) */
+static const bool list_enable_drops_records[LIST_DELIVERED] = { false, true, true, true };
 
-/* What the three gdg_batch_*_enable calls do once their list is checked, in front of taking it.  `resized`: the list sends down another
+/* What the four gdg_batch_*_enable calls that take a list do once it is checked, in front of taking it.  `resized`: the list sends down another
  * size than the one in force -- the download halves are made anew by the next batch call, at the size of a context that was always
  * configured like this one -- whatever still reads them has to be done first -- and off, the table goes as well */
 static int list_enable(gdg_ctx *ctx, int k, bool resized) {
     enter(ctx, /*read_only=*/true);                                          /* configuration: no state of the context changes */
     if (resized) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i : { (int)BATCH_ENCODED, (int)BATCH_FIT_TABLE + k }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
+        batch_drop(ctx, { BATCH_ENCODED, BATCH_FIT_TABLE + k });
     }
     if (list_enable_drops_records[k]) ctx->list_rec[k].valid = false;
     return GDG_OK;
@@ -746,9 +758,7 @@ int gdg_batch_tapfit_enable(gdg_ctx *ctx, int n_fits, const int *first, const in
 
 int gdg_batch_tapfits(const gdg_ctx *ctx) { return ctx ? ctx->tapfit.count() : 0; }
 
-/* the transfer list: validated whole before it replaces the list in force (blend.h); the ports' upper bound is the job's, checked when one is
- * described.  What list_enable does for the three kinds, on the list's own slot and store: another size sent down -- the download halves are
- * made anew by the next batch call -- and off, the table goes as well; the last call's records are read with the list that made them */
+/* the transfer list: validated whole before it replaces the list in force (blend.h); the ports' upper bound is the job's, checked when one is described */
 int gdg_batch_transfer_enable(gdg_ctx *ctx, int n_pairs, const int *port, const int *target, int group) {
     if (!ctx) return GDG_ERR_INVALID;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "batch transfer: a streamed batch run is open on this context; its list holds until gdg_batch_stream_close");
@@ -763,11 +773,7 @@ int gdg_batch_transfer_enable(gdg_ctx *ctx, int n_pairs, const int *port, const 
         const int rt = fir_tables(ctx, GDG_TRANSFER_BLOCK, &tw, &tw2);
         if (rt != GDG_OK) return rt;
     }
-    if (gdg_transfer_list_doubles(n_pairs, group) != ctx->transfer.doubles() || table.size() != ctx->transfer.table.size()) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i : { (int)BATCH_ENCODED, (int)BATCH_TRANSFER_TABLE }) { hipFree(ctx->batch_dev[i]); ctx->batch_dev[i] = nullptr; ctx->batch_dev_cap[i] = 0; }
-    }
-    ctx->transfer_rec.valid = false;
+    if (const int re = list_enable(ctx, LIST_TRANSFER, gdg_transfer_list_doubles(n_pairs, group) != ctx->transfer.doubles() || table.size() != ctx->transfer.table.size())) return re;
     ctx->transfer.table.swap(table);
     return GDG_OK;
 }
@@ -785,19 +791,18 @@ int gdg_batch_dither_seek(gdg_ctx *ctx, uint64_t sample_index) {
 #define BLENDS_REFUSED(ctx, what) \
     fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d blends are in force on this context (gdg_batch_set_blends); a sharded job cannot write blend outputs yet", what, (ctx)->blend.count())
 
-/* ... and a fit's, a Gram list's and a tap fit's ports are rows of the one-device window: the same refusal, the first kind in force in its own words */
+/* ... and a fit's, a Gram list's, a tap fit's and a transfer pair's ports are rows of the one-device window: the same refusal, the first kind in
+ * force in its own words -- the four kinds that have a list; the delivered rows' records refuse in theirs (OUT_RECORDS_REFUSED) */
 int lists_refused(gdg_ctx *ctx, const char *what) {
-    static const char *const text[LIST_KINDS] = {
+    static const char *const text[LIST_DELIVERED] = {
         "%s: %d fits are in force on this context (gdg_batch_fit_enable); a sharded job cannot collect fit records yet",
         "%s: a Gram list of %d ports is in force on this context (gdg_batch_gram_enable); a sharded job cannot collect Gram records yet",
-        "%s: %d tap fits are in force on this context (gdg_batch_tapfit_enable); a sharded job cannot collect tap-fit records yet" };
-    for (int k = 0; ctx && k < LIST_KINDS; k++) {
-        const int count = list_in_force(ctx, k).count;
+        "%s: %d tap fits are in force on this context (gdg_batch_tapfit_enable); a sharded job cannot collect tap-fit records yet",
+        "%s: %d transfer pairs are in force on this context (gdg_batch_transfer_enable); a sharded job cannot collect transfer records yet" };
+    for (int k = 0; ctx && k < LIST_DELIVERED; k++) {
+        const int count = list_in_force(ctx, k, 0).count;
         if (count) return fail(ctx, GDG_ERR_UNSUPPORTED, text[k], what, count);
     }
-    if (ctx && ctx->transfer.count())
-        return fail(ctx, GDG_ERR_UNSUPPORTED, "%s: %d transfer pairs are in force on this context (gdg_batch_transfer_enable); a sharded job cannot collect transfer records yet",
-                    what, ctx->transfer.count());
     return GDG_OK;
 }
 
@@ -992,15 +997,13 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const int R = sharded ? 1 : ctx->deliver;                                    /* the delivery factor in force (never a shard's: its calls refuse it) */
     const int RL = sharded ? 1 : ctx->deliver_up, RM = sharded ? 1 : ctx->deliver_down;      /* ... and the ratio behind it */
     report_begin(ctx, sharded ? N + 1 : NR, (size_t)blocks, true, n_blends);
-    ListInForce lists[LIST_KINDS];                                               /* the lists in force; never a shard's: its calls refuse them */
+    ListInForce lists[LIST_KINDS];                                               /* the list records in force; never a shard's: its calls refuse them */
+    ListShape list_shape[LIST_KINDS];
     for (int k = 0; k < LIST_KINDS; k++) {
-        lists[k] = sharded ? ListInForce{ nullptr, 0, 0, { 0, 0 } } : list_in_force(ctx, k);
-        if (lists[k].count) list_begin(ctx, k, (size_t)blocks);
+        lists[k] = sharded ? ListInForce{ nullptr, 0, 0, { 0, 0 } } : list_in_force(ctx, k, NR);
+        list_shape[k] = lists[k].shape;
+        if (lists[k].count) list_begin(ctx, k, (size_t)blocks, NR);
     }
-    const ListInForce transfer = sharded ? ListInForce{ nullptr, 0, 0, { 0, 0 } } : transfer_in_force(ctx);
-    if (transfer.count) transfer_begin(ctx, (size_t)blocks);
-    const ListShape delivered = sharded ? ListShape{ 0, 0 } : delivered_shape(ctx, (size_t)NR);      /* the delivered rows' records; never a shard's: its calls refuse them */
-    if (delivered.on()) delivered_begin(ctx, (size_t)NR, (size_t)blocks);
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
     /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
     const bool shared = !S.source.empty();
@@ -1025,9 +1028,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* a shard that does not run the metronome measures nothing against that port */
     const std::vector<gdg_align_pairs> pairs = live.on(REPORT_ALIGN) ? align_map_pieces(ctx->align_live_ref, ctx->align_live_lag, (sharded && !S.run_metro) ? N : -1) : std::vector<gdg_align_pairs>();
     const size_t enc_bytes = ((deliver_ratio_window_bytes((size_t)W, R, RL, RM, (size_t)out_width, (size_t)enc_room) + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
-                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + list_room(lists[LIST_FIT].shape, (size_t)W)
-                           + list_room(lists[LIST_GRAM].shape, (size_t)W) + list_room(lists[LIST_TAPFIT].shape, (size_t)W) + list_room(transfer.shape, (size_t)W)
-                           + list_room(delivered, (size_t)W);
+                           + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + lists_room(list_shape, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
     /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
     std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
@@ -1197,22 +1198,18 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         };
         BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
-                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, {}, { nullptr, nullptr, 0, { 0, 0 } } };
-        /* the lists in force -- the fits' table, the Gram list, the tap fits' table: each goes up on the context's stream, ahead of everything
-         * the slice enqueues there; it lives as long as the setting, so nothing waits here */
+                        live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, {} };
+        /* the list records in force.  A kind with a table -- the fits', the Gram list, the tap fits', the transfer list's: it goes up into the
+         * kind's slot on the context's stream, ahead of everything the slice enqueues there; it lives as long as the setting, so nothing waits here */
         for (int k = 0; k < LIST_KINDS; k++) {
             const ListInForce &L = lists[k];
             if (!L.count) continue;
             int *d_table = nullptr;
-            if ((r = batch_buffer(ctx, BATCH_FIT_TABLE + k, L.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
-            HIP_TRY(ctx, hipMemcpyAsync(d_table, L.table, L.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            if (L.ints > 0) {
+                if ((r = batch_buffer(ctx, BATCH_FIT_TABLE + k, L.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
+                HIP_TRY(ctx, hipMemcpyAsync(d_table, L.table, L.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            }
             loop.list[k] = { L.table, d_table, L.count, L.shape };
-        }
-        if (transfer.count) {                                                 /* ... and the transfer list's, into its own slot */
-            int *d_table = nullptr;
-            if ((r = batch_buffer(ctx, BATCH_TRANSFER_TABLE, transfer.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
-            HIP_TRY(ctx, hipMemcpyAsync(d_table, transfer.table, transfer.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            loop.transfer = { transfer.table, d_table, transfer.count, transfer.shape };
         }
         /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
         if (!ctx->trim_gain.empty()) {
@@ -1238,38 +1235,26 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.blend.gain;
             if (bs.max_reach() > 0) {
                 /* the history of the N chain rows: the job's first slice begins from zeros, every later one from what the slice before left */
-                const size_t hist_bytes = (size_t)N * GDG_BLEND_MAX_DELAY * sizeof(double);
-                const bool fresh = ctx->batch_dev_cap[BATCH_BLEND_HISTORY] < hist_bytes;
-                int r;
-                if ((r = batch_buffer(ctx, BATCH_BLEND_HISTORY, hist_bytes, (void **)&loop.d_blend_history)) != GDG_OK) return r;
-                if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the blend history of the open job is gone (gdg_batch_release between two slices?)");
-                if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_blend_history, 0, hist_bytes, ctx->stream));
+                if ((r = carried_history(ctx, BATCH_BLEND_HISTORY, (size_t)N * GDG_BLEND_MAX_DELAY * sizeof(double), pos, "blend", &loop.d_blend_history)) != GDG_OK) return r;
             }
         }
         /* the delivery in force: the scratch rows the encoders read, and the history of the window's NR rows -- the job's first slice begins from
          * zeros, every later one from what the slice before left */
         if (R > 1) {
-            const size_t hist_bytes = (size_t)NR * GDG_DELIVER_HISTORY * sizeof(double);
-            const bool fresh = ctx->batch_dev_cap[BATCH_DELIVER_HISTORY] < hist_bytes;
             if ((r = batch_buffer(ctx, BATCH_DELIVERED, (size_t)NR * (ws / (size_t)R) * sizeof(double), (void **)&loop.d_delivered)) != GDG_OK) return r;
-            if ((r = batch_buffer(ctx, BATCH_DELIVER_HISTORY, hist_bytes, (void **)&loop.d_deliver_history)) != GDG_OK) return r;
-            if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the delivery history of the open job is gone (gdg_batch_release between two slices?)");
-            if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_deliver_history, 0, hist_bytes, ctx->stream));
+            if ((r = carried_history(ctx, BATCH_DELIVER_HISTORY, (size_t)NR * GDG_DELIVER_HISTORY * sizeof(double), pos, "delivery", &loop.d_deliver_history)) != GDG_OK) return r;
             loop.deliver = R;
             loop.d_deliver_taps = R == 2 ? ctx->os.taps2 : ctx->os.taps4;       /* the oversampler's expanded tables (api_ctx.cpp) */
         }
         /* ... and the ratio behind it: the rows the encoders then read, at the window's fixed pitch; the table, which goes up ahead of everything the
          * slice enqueues; the history of the NR intermediate rows, zeroed by the job's first slice like the factor's */
         if (gdg_deliver_ratio_on(RL, RM)) {
-            const size_t hist_bytes = (size_t)NR * GDG_DELIVER_RATIO_HISTORY * sizeof(double), table_bytes = ctx->deliver_tapsT.size() * sizeof(double);
-            const bool fresh = ctx->batch_dev_cap[BATCH_DELIVER_RATIO_HISTORY] < hist_bytes;
+            const size_t table_bytes = ctx->deliver_tapsT.size() * sizeof(double);
             double *d_table = nullptr;
             loop.ratio_stride = gdg_deliver_pitch(R, RL, RM, ws);
             if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_ROWS, (size_t)NR * loop.ratio_stride * sizeof(double), (void **)&loop.d_ratio_rows)) != GDG_OK) return r;
-            if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_HISTORY, hist_bytes, (void **)&loop.d_ratio_history)) != GDG_OK) return r;
             if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_TABLE, table_bytes, (void **)&d_table)) != GDG_OK) return r;
-            if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the delivery ratio's history of the open job is gone (gdg_batch_release between two slices?)");
-            if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_ratio_history, 0, hist_bytes, ctx->stream));
+            if ((r = carried_history(ctx, BATCH_DELIVER_RATIO_HISTORY, (size_t)NR * GDG_DELIVER_RATIO_HISTORY * sizeof(double), pos, "delivery ratio's", &loop.d_ratio_history)) != GDG_OK) return r;
             HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->deliver_tapsT.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
             loop.ratio_up = RL;
             loop.ratio_down = RM;
@@ -1277,14 +1262,9 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         }
         /* the delivered rows' records: the history of the NR rows the encoders read, zeroed by the job's first slice like the deliveries'; room for
          * the spans of the slice's steps -- a step has w + 1 of them, so never more than two per block */
-        if (delivered.on()) {
-            const size_t hist_bytes = (size_t)NR * GDG_OUT_RECORDS_HISTORY * sizeof(double);
-            const bool fresh = ctx->batch_dev_cap[BATCH_DELIVERED_REC_HISTORY] < hist_bytes;
-            if ((r = batch_buffer(ctx, BATCH_DELIVERED_REC_HISTORY, hist_bytes, (void **)&loop.d_out_rec_history)) != GDG_OK) return r;
+        if (lists[LIST_DELIVERED].count) {
             if ((r = batch_buffer(ctx, BATCH_DELIVERED_REC_SPANS, (size_t)2 * (size_t)blocks * sizeof(unsigned long long), (void **)&loop.d_out_rec_spans)) != GDG_OK) return r;
-            if (fresh && pos != 0) return fail(ctx, GDG_ERR_INVALID, "the delivered rows' history of the open job is gone (gdg_batch_release between two slices?)");
-            if (pos == 0) HIP_TRY(ctx, hipMemsetAsync(loop.d_out_rec_history, 0, hist_bytes, ctx->stream));
-            loop.delivered = delivered;
+            if ((r = carried_history(ctx, BATCH_DELIVERED_REC_HISTORY, (size_t)NR * GDG_OUT_RECORDS_HISTORY * sizeof(double), pos, "delivered rows'", &loop.d_out_rec_history)) != GDG_OK) return r;
         }
         return batch_block_loop(ctx, loop, stage);
     };
@@ -1352,9 +1332,7 @@ static int batch_run_impl(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inp
     if (job.length == 0) {                                                       /* every output has 0 samples */
         ctx->batch_up_bytes = ctx->batch_resampled = 0;
         report_begin(ctx, shard ? n_inputs + 1 : n_inputs + 3 + ctx->blend.count(), 0, true, shard ? 0 : ctx->blend.count());
-        for (int k = 0; k < LIST_KINDS && !shard; k++) list_begin(ctx, k, 0);
-        if (!shard) transfer_begin(ctx, 0);
-        if (!shard) delivered_begin(ctx, (size_t)(n_inputs + 3 + ctx->blend.count()), 0);
+        for (int k = 0; k < LIST_KINDS && !shard; k++) list_begin(ctx, k, 0, n_inputs + 3 + ctx->blend.count());
         return report_end(ctx, GDG_OK);
     }
     if ((rc = check_meter_ports(ctx, opt, SHARD_PORTS)) != GDG_OK) return rc;

@@ -1139,18 +1139,21 @@ static int block_list_rows_device(gdg_ctx *ctx, int k, const char *what, const d
 
 /* The getter of kind k: its own store, by the four kinds' rule and in their words (KindWords above): `none` opens the refusal of a call that
  * kept nothing, `pending` / `without` end it with the list in force / off; `name` and `unit` word the refusal of too little room -- capacity
- * counts records for the fits and doubles for the other two.  NULL gives the count of blocks alone. */
+ * counts records for the fits and the delivered rows' records and doubles for the other three.  NULL gives the count of blocks alone. */
 struct ListWords { const char *none, *pending, *without, *name, *unit; };
 static int batch_list_get(gdg_ctx *ctx, int k, const ListWords &w, void *out, size_t capacity, size_t *blocks) {
     if (!ctx) return GDG_ERR_INVALID;
     const gdg_ctx::ListRecords &R = ctx->list_rec[k];
-    if (!R.valid) return fail(ctx, GDG_ERR_INVALID, "%s: the last batch call of this context %s", w.none, list_in_force(ctx, k).count ? w.pending : w.without);
+    /* in force or not does not hang on a call's ports: the shape of no ports answers for every kind */
+    if (!R.valid) return fail(ctx, GDG_ERR_INVALID, "%s: the last batch call of this context %s", w.none, list_in_force(ctx, k, 0).shape.on() ? w.pending : w.without);
     if (blocks) *blocks = R.blocks;
     if (!out) return GDG_OK;
-    const size_t n = R.store.size() / (k == LIST_FIT ? R.elem : sizeof(double));
+    const bool records = k == LIST_FIT || k == LIST_DELIVERED;
+    const size_t n = records ? R.rows * R.blocks : R.store.size() / sizeof(double);
     if (capacity < n) {
         char has[64];
         if (k == LIST_FIT) snprintf(has, sizeof has, "%d fits x %zu blocks", R.count, R.blocks);
+        else if (k == LIST_DELIVERED) snprintf(has, sizeof has, "%d ports x %zu blocks", R.count, R.blocks);
         else if (k == LIST_GRAM) snprintf(has, sizeof has, "%zu blocks x %d (%d + 1) / 2", R.blocks, R.count, R.count);
         else snprintf(has, sizeof has, "%zu blocks x %zu", R.blocks, R.elem / sizeof(double));
         return fail(ctx, GDG_ERR_INVALID, "%s: room for %zu %s, the call has %s = %zu", w.name, capacity, w.unit, has, n);
@@ -1459,20 +1462,12 @@ int gdg_block_transfer_rows(gdg_ctx *ctx, const double *const *rows, int n_rows,
     });
 }
 
-/* the getter: the transfer records' own store, by the list records' rule and in their words; capacity in doubles */
+/* capacity in doubles */
 int gdg_batch_transfer(gdg_ctx *ctx, double *out, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
-    if (!ctx) return GDG_ERR_INVALID;
-    const gdg_ctx::ListRecords &R = ctx->transfer_rec;
-    if (!R.valid)
-        return fail(ctx, GDG_ERR_INVALID, "no transfer records: the last batch call of this context %s", ctx->transfer.count()
-                    ? "has not completed, was a master finish, or none has run since gdg_batch_transfer_enable" : "ran without them (gdg_batch_transfer_enable comes before the call)");
-    if (blocks) *blocks = R.blocks;
-    if (doubles_per_block) *doubles_per_block = R.elem / sizeof(double);
-    if (!out) return GDG_OK;
-    const size_t n = R.store.size() / sizeof(double);
-    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "transfer: room for %zu doubles, the call has %zu blocks x %zu = %zu", capacity, R.blocks, R.elem / sizeof(double), n);
-    if (n) memcpy(out, R.store.data(), R.store.size());
-    return GDG_OK;
+    static const ListWords words = { "no transfer records", "has not completed, was a master finish, or none has run since gdg_batch_transfer_enable",
+                                     "ran without them (gdg_batch_transfer_enable comes before the call)", "transfer", "doubles" };
+    if (ctx && doubles_per_block && ctx->list_rec[LIST_TRANSFER].valid) *doubles_per_block = ctx->list_rec[LIST_TRANSFER].elem / sizeof(double);
+    return batch_list_get(ctx, LIST_TRANSFER, words, out, capacity, blocks);
 }
 
 /* the planner (blend.h): pure host arithmetic, no context -- what it refuses is kept per thread for gdg_last_error(NULL) */
@@ -1620,17 +1615,10 @@ int gdg_block_out_rows(gdg_ctx *ctx, const double *const *rows, int n_rows, size
     });
 }
 
+/* capacity in records */
 int gdg_batch_out_records(gdg_ctx *ctx, gdg_block_delivered *records, size_t capacity, int *ports, size_t *blocks) {
-    if (!ctx) return GDG_ERR_INVALID;
-    const gdg_ctx::ListRecords &R = ctx->delivered_rec;
-    if (!R.valid)
-        return fail(ctx, GDG_ERR_INVALID, "no records of the delivered rows: the last batch call of this context %s", ctx->out_rec_on
-                    ? "has not completed, was a master finish, or none has run since gdg_batch_out_records_enable" : "ran without them (gdg_batch_out_records_enable comes before the call)");
-    if (ports) *ports = R.count;
-    if (blocks) *blocks = R.blocks;
-    if (!records) return GDG_OK;
-    const size_t n = R.rows * R.blocks;
-    if (capacity < n) return fail(ctx, GDG_ERR_INVALID, "out records: room for %zu records, the call has %d ports x %zu blocks = %zu", capacity, R.count, R.blocks, n);
-    if (n) memcpy(records, R.store.data(), R.store.size());
-    return GDG_OK;
+    static const ListWords words = { "no records of the delivered rows", "has not completed, was a master finish, or none has run since gdg_batch_out_records_enable",
+                                     "ran without them (gdg_batch_out_records_enable comes before the call)", "out records", "records" };
+    if (ctx && ports && ctx->list_rec[LIST_DELIVERED].valid) *ports = ctx->list_rec[LIST_DELIVERED].count;
+    return batch_list_get(ctx, LIST_DELIVERED, words, records, capacity, blocks);
 }

@@ -426,37 +426,32 @@ struct gdg_ctx {
     BlendSet blend;
     unsigned char *d_blend = nullptr;
     size_t d_blend_cap = 0;
-    /* the list records (report_sections.h, LIST_KINDS; blend.h), each list in force as the table of ints a launch reads, empty = off: the
-     * blend fits (gdg_batch_fit_enable), the Gram list (gdg_batch_gram_enable: the listed ports in list order) and the tap fits
-     * (gdg_batch_tapfit_enable).  While kind k's list is in force batch_dev[BATCH_FIT_TABLE + k] holds its table -- uploaded at the start of
-     * a batch call -- and a download half has room for its [rows][window] elements behind the four kinds' sections and the lists' before
-     * it; off, neither exists.  Configuration like the blends: in no blob. */
+    /* the list records (report_sections.h, LIST_KINDS; blend.h), what puts each of the five kinds in force (list_in_force): the blend fits
+     * (gdg_batch_fit_enable), the Gram list (gdg_batch_gram_enable: the listed ports in list order), the tap fits (gdg_batch_tapfit_enable)
+     * and the transfer list (gdg_batch_transfer_enable) as the table of ints a launch reads, empty = off; the records of the delivered rows
+     * (gdg_batch_out_records_enable) as a switch: they have no list, every port of the call is recorded.  While kind k's table is in force
+     * batch_dev[BATCH_FIT_TABLE + k] holds it -- uploaded at the start of a batch call; while a kind is in force a download half has room for
+     * its [rows][window] elements behind the four kinds' sections and the lists' before it; off, neither exists.  While the delivered rows'
+     * switch is on batch_dev[BATCH_DELIVERED_REC_HISTORY] holds the 23 samples every port keeps from step to step and
+     * batch_dev[BATCH_DELIVERED_REC_SPANS] the block spans of a slice's steps, which out_rec_spans holds on the host until the slice has run;
+     * off, neither exists.  Configuration like the blends: in no blob. */
     FitSet fit;
     std::vector<int> gram_port;
     TapFitSet tapfit;
-    /* ... and their records of the last completed batch call, [rows][blocks] elements of `elem` bytes ([fits][blocks] records, [blocks]
-     * [P (P + 1) / 2] and [blocks][D] doubles) beside the four kinds' and by their rule: a call that collects (`live`, decided when it
-     * begins) fills the store step by step and validates it at its end; a master finish collects none.  `count`: the entries the list had
-     * when the call began (fits, ports, tap fits). */
+    TransferSet transfer;
+    bool out_rec_on = false;
+    std::vector<unsigned long long> out_rec_spans;
+    /* ... and their records of the last completed batch call, one store per kind: [rows][blocks] elements of `elem` bytes ([fits][blocks]
+     * records, [blocks][P (P + 1) / 2], [blocks][D] and [blocks][n_pairs (4096 / D + 1) 4] doubles, [ports][blocks] records of 40 bytes)
+     * beside the four kinds' and by their rule: a call that collects (`live`, decided when it begins) fills the store step by step and
+     * validates it at its end; a master finish collects none.  `count`: the entries the list had when the call began (fits, ports, tap
+     * fits, pairs; the call's ports). */
     struct ListRecords {
         bool live = false, valid = false;
         int count = 0;
         size_t rows = 0, elem = 0, blocks = 0;
         std::vector<unsigned char> store;
     } list_rec[LIST_KINDS];
-    /* the transfer list (gdg_batch_transfer_enable; blend.h, TransferSet) and its records of the last completed batch call, [blocks] records of
-     * n_pairs (4096 / D + 1) 4 doubles: a list record by every rule above, in a store of its own behind the three kinds' -- its section rides
-     * behind theirs (report_sections.h, transfer_section) and its table lies in batch_dev[BATCH_TRANSFER_TABLE].  Configuration: in no blob. */
-    TransferSet transfer;
-    ListRecords transfer_rec;
-    /* the records of the delivered rows (gdg_batch_out_records_enable; include/gdg.h, DELIVERED RECORDS): a list record by every rule above with
-     * the shape (ports, 40), in a store of its own -- its section rides behind the transfer records' (report_sections.h, delivered_section).
-     * While the switch is on batch_dev[BATCH_DELIVERED_REC_HISTORY] holds the 23 samples every port keeps from step to step and
-     * batch_dev[BATCH_DELIVERED_REC_SPANS] the block spans of a slice's steps, which out_rec_spans holds on the host until the slice has run; off,
-     * neither exists.  Configuration: in no blob. */
-    bool out_rec_on = false;
-    ListRecords delivered_rec;
-    std::vector<unsigned long long> out_rec_spans;
     /* ... and the spans of the stand-alone calls' last launch (gdg_block_out_rows): the host's copy, which the upload reads, and the device's */
     std::vector<unsigned long long> out_rows_spans;
     unsigned long long *d_out_rows_spans = nullptr;
@@ -756,7 +751,7 @@ int state_load_device_with(gdg_ctx *ctx, const void *d_blob, size_t bytes, const
 int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const gdg_batch_options *opt, bool shard, size_t job_samples,
                bool run_metronome, gdg_ctx::BatchStreamState &job, bool meters_at_open = true);
 int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
-/* api_batch.cpp: what a shard's entry point `what` refuses while list records are in force -- fits, then the Gram list, then tap fits; GDG_OK: none is (or no context) */
+/* api_batch.cpp: what a shard's entry point `what` refuses while list records are in force -- fits, then the Gram list, then tap fits, then transfer pairs; GDG_OK: none is (or no context) */
 int lists_refused(gdg_ctx *ctx, const char *what);
 /* api_io.cpp: a list of fits against gdg_fit_check (blend.h), refused in the words of `what`; n_rows < 0: the port count is not known yet */
 int fit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, int n_rows);
@@ -774,8 +769,6 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
     ctx->spec_live_edges = ctx->spec_edges;
     ctx->align_live_ref.clear();
     for (gdg_ctx::ListRecords &R : ctx->list_rec) R.valid = R.live = false;      /* a call that collects list records says so itself (list_begin) */
-    ctx->transfer_rec.valid = ctx->transfer_rec.live = false;                    /* ... and transfer records (transfer_begin) */
-    ctx->delivered_rec.valid = ctx->delivered_rec.live = false;                  /* ... and the delivered rows' records (delivered_begin) */
     /* any other count was refused when the job was described; a list without the call's blend ports: each of them references itself */
     if (align && ((int)ctx->align_ref.size() == ports || (blend_ports > 0 && (int)ctx->align_ref.size() == ports - blend_ports))) {
         ctx->align_live_ref = ctx->align_ref;
@@ -795,20 +788,27 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
         K.store.assign((size_t)ports * blocks * K.elem, 0);
     }
 }
-/* kind k's list in force: the table of ints a launch reads (the fits' and tap fits' tables, the Gram list's ports), the entries it counts
- * (fits, ports, tap fits) and what it sends down per block; nothing in force: no int, count 0, a shape that is off */
+/* kind k in force for a call of `ports` ports: the table of ints a launch reads (the fits', tap fits' and transfer list's tables, the Gram
+ * list's ports; the delivered rows' records have none), the entries it counts (fits, ports, tap fits, pairs; the call's ports) and what it
+ * sends down per block; nothing in force: no int, count 0, a shape that is off */
 struct ListInForce { const int *table; size_t ints; int count; ListShape shape; };
-static inline ListInForce list_in_force(const gdg_ctx *ctx, int k) {
+static inline ListInForce list_in_force(const gdg_ctx *ctx, int k, int ports) {
     if (k == LIST_FIT) return { ctx->fit.table.data(), ctx->fit.table.size(), ctx->fit.count(), { (size_t)ctx->fit.count(), ctx->fit.count() ? (size_t)FIT_RECORD_BYTES : 0 } };
     if (k == LIST_GRAM) return { ctx->gram_port.data(), ctx->gram_port.size(), (int)ctx->gram_port.size(), { 1, gram_record_bytes(ctx->gram_port.size()) } };
-    return { ctx->tapfit.table.data(), ctx->tapfit.table.size(), ctx->tapfit.count(), { 1, ctx->tapfit.doubles() * sizeof(double) } };
+    if (k == LIST_TAPFIT) return { ctx->tapfit.table.data(), ctx->tapfit.table.size(), ctx->tapfit.count(), { 1, ctx->tapfit.doubles() * sizeof(double) } };
+    if (k == LIST_TRANSFER) return { ctx->transfer.table.data(), ctx->transfer.table.size(), ctx->transfer.count(), { 1, ctx->transfer.doubles() * sizeof(double) } };
+    if (!ctx->out_rec_on) return { nullptr, 0, 0, { 0, 0 } };
+    return { nullptr, 0, ports, { (size_t)ports, (size_t)DELIVERED_RECORD_BYTES } };
 }
-/* the three launchers take one argument list (gdg_internal.h): rows, stride, n_rows, samples, block, host table, device table, count, records, stream */
+/* the first three kinds' launchers take one argument list (gdg_internal.h): rows, stride, n_rows, samples, block, host table, device table,
+ * count, records, stream; the transfer records' takes its transform's table, the delivered rows' records' their spans and history */
 typedef hipError_t ListLaunch(const double *, size_t, unsigned, size_t, unsigned, const int *, const int *, unsigned, void *, hipStream_t);
-static ListLaunch *const list_launch[LIST_KINDS] = { gdg_launch_block_fit, gdg_launch_block_gram, gdg_launch_block_tapfit };
-/* behind report_begin, by the calls that collect list records: zeroed records for kind k's list in force x `blocks` */
-static inline void list_begin(gdg_ctx *ctx, int k, size_t blocks) {
-    const ListInForce L = list_in_force(ctx, k);
+enum { LIST_LAUNCHERS = 3 };
+static ListLaunch *const list_launch[LIST_LAUNCHERS] = { gdg_launch_block_fit, gdg_launch_block_gram, gdg_launch_block_tapfit };
+static_assert(LIST_FIT == 0 && LIST_GRAM == 1 && LIST_TAPFIT == 2 && LIST_TRANSFER == LIST_LAUNCHERS, "list_launch[k] is kind k's launcher for the kinds in front of LIST_TRANSFER only");
+/* behind report_begin, by the calls that collect list records: zeroed records for kind k in force x `blocks` */
+static inline void list_begin(gdg_ctx *ctx, int k, size_t blocks, int ports) {
+    const ListInForce L = list_in_force(ctx, k, ports);
     gdg_ctx::ListRecords &R = ctx->list_rec[k];
     R.live = L.shape.on();
     if (!R.live) return;
@@ -823,50 +823,8 @@ static inline void list_file(gdg_ctx *ctx, int k, const unsigned char *section, 
     gdg_ctx::ListRecords &R = ctx->list_rec[k];
     list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
 }
-/* the transfer list in force: its table, its pairs and what it sends down per block -- one row of the list's doubles */
-static inline ListInForce transfer_in_force(const gdg_ctx *ctx) {
-    return { ctx->transfer.table.data(), ctx->transfer.table.size(), ctx->transfer.count(), { 1, ctx->transfer.doubles() * sizeof(double) } };
-}
-/* list_begin and list_file for the transfer records' own store */
-static inline void transfer_begin(gdg_ctx *ctx, size_t blocks) {
-    const ListInForce L = transfer_in_force(ctx);
-    gdg_ctx::ListRecords &R = ctx->transfer_rec;
-    R.live = L.shape.on();
-    if (!R.live) return;
-    R.count = L.count;
-    R.rows = L.shape.rows;
-    R.elem = L.shape.elem;
-    R.blocks = blocks;
-    R.store.assign(R.rows * blocks * R.elem, 0);
-}
-static inline void transfer_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
-    gdg_ctx::ListRecords &R = ctx->transfer_rec;
-    list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
-}
-/* the delivered rows' records: what a call sends down per block while the switch is on -- one record of 40 bytes per port */
-static inline ListShape delivered_shape(const gdg_ctx *ctx, size_t ports) { return { ctx->out_rec_on ? ports : 0, ctx->out_rec_on ? (size_t)DELIVERED_RECORD_BYTES : 0 }; }
-/* list_begin and list_file for their own store */
-static inline void delivered_begin(gdg_ctx *ctx, size_t ports, size_t blocks) {
-    const ListShape shape = delivered_shape(ctx, ports);
-    gdg_ctx::ListRecords &R = ctx->delivered_rec;
-    R.live = shape.on();
-    if (!R.live) return;
-    R.count = (int)ports;
-    R.rows = shape.rows;
-    R.elem = shape.elem;
-    R.blocks = blocks;
-    R.store.assign(R.rows * blocks * R.elem, 0);
-}
-static inline void delivered_file(gdg_ctx *ctx, const unsigned char *section, size_t w, size_t b0) {
-    gdg_ctx::ListRecords &R = ctx->delivered_rec;
-    list_file_rows(R.store.data(), R.blocks, { R.rows, R.elem }, section, w, b0);
-}
 /* ... and has completed (rc == GDG_OK) or not */
 static inline int report_end(gdg_ctx *ctx, int rc) {
-    ctx->delivered_rec.valid = ctx->delivered_rec.live && rc == GDG_OK;
-    ctx->delivered_rec.live = false;
-    ctx->transfer_rec.valid = ctx->transfer_rec.live && rc == GDG_OK;
-    ctx->transfer_rec.live = false;
     for (gdg_ctx::ListRecords &R : ctx->list_rec) {
         R.valid = R.live && rc == GDG_OK;
         R.live = false;
@@ -915,7 +873,8 @@ enum {
 };
 static_assert(sizeof(gdg_ctx::batch_dev) / sizeof(void *) == BATCH_DEV_SLOTS && sizeof(gdg_ctx::batch_dev_cap) / sizeof(size_t) == BATCH_DEV_SLOTS,
               "gdg_ctx::batch_dev and batch_dev_cap have one entry per slot");
-static_assert(BATCH_GRAM_PORTS == BATCH_FIT_TABLE + LIST_GRAM && BATCH_TAPFIT_TABLE == BATCH_FIT_TABLE + LIST_TAPFIT, "BATCH_FIT_TABLE + k is list kind k's slot");
+static_assert(BATCH_GRAM_PORTS == BATCH_FIT_TABLE + LIST_GRAM && BATCH_TAPFIT_TABLE == BATCH_FIT_TABLE + LIST_TAPFIT && BATCH_TRANSFER_TABLE == BATCH_FIT_TABLE + LIST_TRANSFER,
+              "BATCH_FIT_TABLE + k is list kind k's slot");
 int ensure_tuner(gdg_ctx *ctx);
 
 #pragma GCC visibility pop

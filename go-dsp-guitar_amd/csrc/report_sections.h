@@ -3,8 +3,9 @@
  * A step (or a master finish's piece) sends its encoded rows down; behind them follows one section per live kind, in this fixed order:
  * block statistics, band spectrum, alignment records, true-peak records.  A section is [rows][w] elements -- `rows` record rows (N + 3 for
  * a plain call, N + 1 for a shard, 2 for a finish), `w` blocks -- of the kind's element size per port and block.  The block loop starts
- * every live section at the next 16 bytes behind whatever precedes it; the finish packs them.  Pure host arithmetic: no HIP header is
- * needed to compile this file (tests/native/report_sections_check.cpp holds it against the formulas it replaced).
+ * every live section at the next 16 bytes behind whatever precedes it; the finish packs them.  Behind the kinds' sections a step of the
+ * block loop sends the five list records' (LIST_KINDS below), by the same 16-byte rule.  Pure host arithmetic: no HIP header is needed to
+ * compile this file (tests/native/report_sections_check.cpp and list_chain_check.cpp hold it against the formulas it replaced).
  */
 #ifndef GDG_REPORT_SECTIONS_H
 #define GDG_REPORT_SECTIONS_H
@@ -47,14 +48,20 @@ static inline size_t report_room(const ReportLive &live, size_t rows, size_t W) 
     return room;
 }
 
-/* The list records -- the blend fit's (include/gdg.h, FIT), the Gram list's (GRAM) and the tap fit's (TAPFIT) -- are no further kinds: their
- * rows are a call's fits or one row of packed sums, not its ports.  A step of the block loop sends them down behind the last live kind's
- * section -- behind its rows when no kind is live -- in this fixed order, each from the next 16 bytes behind whatever precedes it:
- * [rows][w] elements of `elem` bytes.  (rows, elem) = (fits, 368) for the fits, (1, P (P + 1) / 2 doubles) for a Gram list of P ports and
- * (1, D doubles) for tap fits, D the list's sum of V (V + 1) / 2.  A list that is off: no byte.  The finish calls never carry them. */
-enum { LIST_FIT, LIST_GRAM, LIST_TAPFIT, LIST_KINDS };
+/* The list records are no further kinds: their rows are a call's own lists, not its ports.  ONE RULE for all five: a step of the block loop
+ * sends them down behind the last live kind's section -- behind its rows when no kind is live -- in the order of this enum, each as [rows][w]
+ * elements of `elem` bytes from the next 16 bytes behind whatever precedes it; a list that is off takes no byte and moves nothing.  The
+ * finish calls never carry them.  (rows, elem) per kind (include/gdg.h: FIT, GRAM, TAPFIT, TRANSFER, DELIVERED RECORDS):
+ *   LIST_FIT        (fits, 368)                            the blend fits' records
+ *   LIST_GRAM       (1, P (P + 1) / 2 doubles)             the Gram list of P ports
+ *   LIST_TAPFIT     (1, D doubles)                         the tap fits, D the list's sum of V (V + 1) / 2
+ *   LIST_TRANSFER   (1, n_pairs (4096 / D + 1) 4 doubles)  the transfer records of n_pairs pairs in groups of D bins
+ *   LIST_DELIVERED  (ports, 40)                            the records of the delivered rows */
+enum { LIST_FIT, LIST_GRAM, LIST_TAPFIT, LIST_TRANSFER, LIST_DELIVERED, LIST_KINDS };
 enum { FIT_RECORD_BYTES = 368 };
 static inline size_t gram_record_bytes(size_t ports) { return ports * (ports + 1) / 2 * 8; }
+static inline size_t transfer_record_bytes(size_t pairs, size_t group) { return pairs && group ? pairs * (4096 / group + 1) * 4 * 8 : 0; }
+enum { DELIVERED_RECORD_BYTES = 40 };
 
 /* what a list in force sends down per block: `rows` rows of one element of `elem` bytes; elem == 0 = the kind is off */
 struct ListShape {
@@ -74,10 +81,10 @@ static inline ListSection list_section(size_t end, const ListShape &shape, size_
     return s;
 }
 
-/* ... and what a half holds for it for a window of W blocks, beside report_room */
+/* ... and what a half holds for it for a window of W blocks */
 static inline size_t list_room(const ListShape &shape, size_t W) { return shape.on() ? 16 + shape.rows * W * shape.elem : 0; }
 
-/* the three sections of a step, chained behind ReportSections::end; `end` is the end of what the step sends down */
+/* the five sections of a step, chained behind ReportSections::end; `end` is the end of what the step sends down */
 struct ListSections { ListSection of[LIST_KINDS]; size_t end; };
 
 static inline ListSections list_sections(size_t end, const ListShape *shape, size_t w) {
@@ -87,17 +94,12 @@ static inline ListSections list_sections(size_t end, const ListShape *shape, siz
     return s;
 }
 
-/* The transfer records (include/gdg.h, TRANSFER) are a list record too, but no fourth entry of the chain above: their section rides behind
- * ListSections::end, from the next 16 bytes on, as [w] records -- the shape (1, n_pairs (4096 / D + 1) 4 doubles) through the same
- * list_section and list_room.  Off: no byte, and `end` is ListSections::end. */
-static inline size_t transfer_record_bytes(size_t pairs, size_t group) { return pairs && group ? pairs * (4096 / group + 1) * 4 * 8 : 0; }
-static inline ListSection transfer_section(const ListSections &lists, const ListShape &shape, size_t w) { return list_section(lists.end, shape, w); }
-
-/* The records of the delivered rows (include/gdg.h, DELIVERED RECORDS) ride behind the transfer records' section, from the next 16 bytes on, as
- * [ports][w] records of 40 bytes -- the shape (ports, 40) through the same list_section and list_room, filed by list_file_rows.  Off: no byte,
- * and `end` is the transfer section's. */
-enum { DELIVERED_RECORD_BYTES = 40 };
-static inline ListSection delivered_section(const ListSection &transfer, const ListShape &shape, size_t w) { return list_section(transfer.end, shape, w); }
+/* ... and what a half holds for the chain for a window of W blocks, beside report_room */
+static inline size_t lists_room(const ListShape *shape, size_t W) {
+    size_t room = 0;
+    for (int k = 0; k < LIST_KINDS; k++) room += list_room(shape[k], W);
+    return room;
+}
 
 /* Filing a section that has come down: [rows][w] elements into a store of [rows][blocks], under the blocks from b0 on. */
 static inline void list_file_rows(unsigned char *store, size_t blocks, const ListShape &shape, const unsigned char *section, size_t w, size_t b0) {

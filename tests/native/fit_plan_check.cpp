@@ -155,12 +155,12 @@ int main() {
                             cases++;
                         }
     CHECK(moved > 0);
-    /* the chain of the three list sections (list_sections) behind a report layout, over the 8 on/off subsets of the lists: every live
+    /* the chain of the list sections (list_sections) behind a report layout, over the 8 on/off subsets of the first three lists: every live
      * section starts at the next 16 bytes behind what precedes it, an off kind takes no byte and moves nothing, and a step of the whole
      * window fits the room of its half.  3 fits, a Gram list of 5 ports, tap fits of 21 doubles. */
     {
-        static_assert(LIST_FIT == 0 && LIST_GRAM == 1 && LIST_TAPFIT == 2 && LIST_KINDS == 3, "the sections ride in this order");
-        const size_t elem[LIST_KINDS] = { 368, 5 * 6 / 2 * 8, 21 * 8 }, rows[LIST_KINDS] = { 3, 1, 1 };
+        static_assert(LIST_FIT == 0 && LIST_GRAM == 1 && LIST_TAPFIT == 2 && LIST_TRANSFER == 3 && LIST_DELIVERED == 4 && LIST_KINDS == 5, "the sections ride in this order");
+        const size_t elem[LIST_KINDS] = { 368, 5 * 6 / 2 * 8, 21 * 8, 0, 0 }, rows[LIST_KINDS] = { 3, 1, 1, 1, 7 };      /* the last two kinds stay off here (`on` < 8) */
         CHECK(gram_record_bytes(5) == elem[LIST_GRAM]);
         for (int report = 0; report < 2; report++)
             for (size_t base : { (size_t)0, (size_t)1001, (size_t)4096, (size_t)98312 })

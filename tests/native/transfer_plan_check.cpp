@@ -1,7 +1,7 @@
 /*
  * transfer_plan_check.cpp -- the transfer records without HIP (csrc/report_sections.h, csrc/blend.h).  THE SECTION: with each of the 16
- * on/off combinations of the three list kinds and the transfer list, for w = 1, 3 and 16 blocks, the transfer section starts at the next 16
- * bytes behind ListSections::end, holds w records, and the three kinds' sections are where they are without a transfer list.  THE LIST: what
+ * on/off combinations of the three list kinds in front and the transfer list, for w = 1, 3 and 16 blocks, the transfer section starts at the
+ * next 16 bytes behind the three kinds' end, holds w records, and the three kinds' sections are where they are without a transfer list.  THE LIST: what
  * gdg_transfer_check refuses, the table a launch reads and the record's size.  THE PLANNER: the filter {1, -2, 3} from records synthesised
  * with Sxx = 1, Syy = |H|^2, Sxy = H -- the taps under the taper at center 0 and shifted at center 5, coherence 1 -- its refusals, which
  * write nothing, and the ridge, which shrinks every |H[g]| and with it the taps' energy.  Built by tests/test_transfer_host.py.
@@ -35,13 +35,15 @@ int main() {
     for (int mask = 0; mask < 16; mask++)
         for (size_t w : { (size_t)1, (size_t)3, (size_t)16 })
             for (size_t base : { (size_t)0, (size_t)4 * 8192 * 2 * w + 8, (size_t)1000003 }) {
-                const ListShape shape[LIST_KINDS] = { { (size_t)((mask & 1) ? 2 : 0), (size_t)((mask & 1) ? FIT_RECORD_BYTES : 0) }, { 1, (mask & 2) ? gram_record_bytes(3) : 0 },
-                                                      { 1, (mask & 4) ? (size_t)21 * 8 : 0 } };
                 const ListShape transfer = { 1, (mask & 8) ? transfer_record_bytes(2, 32) : 0 };
-                const ListSections lists = list_sections(base, shape, w);
-                const ListSection t = transfer_section(lists, transfer, w);
-                size_t end = base;                                             /* the three kinds, by hand: they do not know of a fourth */
-                for (int k = 0; k < LIST_KINDS; k++) {
+                const ListShape shape[LIST_KINDS] = { { (size_t)((mask & 1) ? 2 : 0), (size_t)((mask & 1) ? FIT_RECORD_BYTES : 0) }, { 1, (mask & 2) ? gram_record_bytes(3) : 0 },
+                                                      { 1, (mask & 4) ? (size_t)21 * 8 : 0 }, transfer, { 0, 0 } };      /* the delivered rows' records: off */
+                const ListSections all = list_sections(base, shape, w);
+                const ListSection t = all.of[LIST_TRANSFER];
+                CHECK(all.of[LIST_DELIVERED].bytes == 0 && all.of[LIST_DELIVERED].at == t.end && all.end == t.end);
+                struct { const ListSection *of; size_t end; } lists = { all.of, all.of[LIST_TAPFIT].end };      /* the three kinds in front, and their end */
+                size_t end = base;                                             /* the three kinds, by hand: a fourth behind them moves none of them */
+                for (int k = 0; k < LIST_TRANSFER; k++) {
                     if (!shape[k].on()) { CHECK(lists.of[k].bytes == 0 && lists.of[k].end == end); continue; }
                     const size_t at = (end + 15) / 16 * 16;
                     CHECK(lists.of[k].at == at && lists.of[k].bytes == shape[k].rows * w * shape[k].elem);
@@ -59,7 +61,7 @@ int main() {
                 cases++;
             }
     CHECK(transfer_record_bytes(1, 1) == 131104 && transfer_record_bytes(0, 1) == 0 && transfer_record_bytes(16, 64) == 16 * 65 * 32);
-    static_assert(LIST_KINDS == 3, "the transfer list is no fourth entry of the chain");
+    static_assert(LIST_TRANSFER == 3 && LIST_DELIVERED == 4 && LIST_KINDS == 5, "the transfer list is the fourth entry of the chain, behind the three kinds");
 
     /* ---- the list ---- */
     int pair = -2;

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as entry
+import list_chain_pins
 
 ROOT = entry.ROOT
 CSRC = os.path.join(ROOT, "go-dsp-guitar_amd", "csrc")
@@ -66,12 +67,8 @@ def test_the_fit_section_is_stated_once_and_is_no_fifth_kind():
     with open(os.path.join(CSRC, "report_sections.h")) as f:
         text = f.read()
     assert "enum { REPORT_STATS, REPORT_BANDS, REPORT_ALIGN, REPORT_TRUE_PEAK, REPORT_KINDS };" in text
-    assert "enum { LIST_FIT, LIST_GRAM, LIST_TAPFIT, LIST_KINDS };" in text       # a list record of its own, in the order the sections ride
-    assert text.count("static inline ListSection list_section(") == 1 and text.count("static inline size_t list_room(") == 1
+    list_chain_pins.assert_one_chain(CSRC)                                      # a list record of its own: one enum, one chain, one store array
     assert "enum { FIT_RECORD_BYTES = 368 };" in text                             # ... and what its element is stays said here
-    with open(os.path.join(CSRC, "api_batch.cpp")) as f:
-        batch = f.read()
-    assert "list_sections(" in batch and "list_room(" in batch
     with open(os.path.join(CSRC, "Makefile")) as f:
         make = f.read()
     assert "fit_kernels.h" in [w for line in make.splitlines() if line.startswith("io.o:") for w in line.split()]

@@ -12,6 +12,7 @@ import pytest
 
 import tapfit_ref as ref
 import __graft_entry__ as entry
+import list_chain_pins
 
 ROOT = entry.ROOT
 CSRC = os.path.join(ROOT, "go-dsp-guitar_amd", "csrc")
@@ -61,11 +62,7 @@ def test_the_section_is_stated_once_and_the_kernel_is_part_of_gram_o():
     with open(os.path.join(CSRC, "report_sections.h")) as f:
         text = f.read()
     assert "enum { REPORT_STATS, REPORT_BANDS, REPORT_ALIGN, REPORT_TRUE_PEAK, REPORT_KINDS };" in text
-    assert "enum { LIST_FIT, LIST_GRAM, LIST_TAPFIT, LIST_KINDS };" in text       # a list record of its own, in the order the sections ride
-    assert text.count("static inline ListSection list_section(") == 1 and text.count("static inline size_t list_room(") == 1
-    with open(os.path.join(CSRC, "api_batch.cpp")) as f:
-        batch = f.read()
-    assert "list_sections(" in batch and "list_room(" in batch
+    list_chain_pins.assert_one_chain(CSRC)                                      # a list record of its own: one enum, one chain, one store array
     with open(os.path.join(CSRC, "Makefile")) as f:
         make = f.read()
     assert "tapfit_kernels.h" in [w for line in make.splitlines() if line.startswith("gram.o:") for w in line.split()]

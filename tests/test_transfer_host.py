@@ -11,6 +11,7 @@ import pytest
 
 import transfer_ref as ref
 import __graft_entry__ as entry
+import list_chain_pins
 
 ROOT = entry.ROOT
 CSRC = os.path.join(ROOT, "go-dsp-guitar_amd", "csrc")
@@ -49,11 +50,10 @@ def test_section_list_and_planner_as_a_stand_alone_program(tmp_path):
 def test_the_section_rides_behind_the_three_kinds_and_the_kernel_is_part_of_fir_o():
     with open(os.path.join(CSRC, "report_sections.h")) as f:
         text = f.read()
-    assert "enum { LIST_FIT, LIST_GRAM, LIST_TAPFIT, LIST_KINDS };" in text       # no fourth entry
-    assert "static inline ListSection transfer_section(const ListSections &lists, const ListShape &shape, size_t w) { return list_section(lists.end, shape, w); }" in text
-    with open(os.path.join(CSRC, "api_batch.cpp")) as f:
-        batch = f.read()
-    assert "transfer_section(" in batch and "list_room(transfer.shape" in batch and "BATCH_TRANSFER_TABLE" in batch
+    list_chain_pins.assert_one_chain(CSRC)                                      # the fourth entry of the one chain, behind the three kinds
+    assert "static inline size_t transfer_record_bytes(size_t pairs, size_t group) { return pairs && group ? pairs * (4096 / group + 1) * 4 * 8 : 0; }" in text
+    with open(os.path.join(CSRC, "ctx.h")) as f:
+        assert "BATCH_TRANSFER_TABLE == BATCH_FIT_TABLE + LIST_TRANSFER" in f.read()       # its table's slot is the kind's
     with open(os.path.join(CSRC, "Makefile")) as f:
         make = f.read()
     assert "transfer_kernels.h" in [w for line in make.splitlines() if line.startswith("fir.o:") for w in line.split()]
