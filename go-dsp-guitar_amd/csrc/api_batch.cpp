@@ -5,6 +5,7 @@
  * There is no CPU compute path here: every sample is produced by a HIP kernel.
  */
 #include "ctx.h"
+#include "batch_steps.h"
 #include <future>
 
 #define GDG_BLOCK_SIZE 8192           /* controller/controller.go:36 */
@@ -162,299 +163,308 @@ struct BatchLoop {
     unsigned long long *d_out_rec_spans;
 };
 
-/* The step rule: the step [first, first + w) that holds block p of a job of `job` blocks in windows of W.
- * A long job opens with a quarter window and a half window: the device has nothing to do until the first step's bytes are gathered and
- * uploaded (16 blocks of 512 files: 1.9 + 2.4 ms), and what it computes first comes down and is scattered while nothing else waits for the
- * host; each step's upload fits behind the step before.  Then whole windows, then a tail of W/2, W/4 .. 1 (the last download and scatter
- * are a quarter step's).  Window sizes only change the time blocking, never a sample (tests/test_gpu_window.py). */
-static void job_step(size_t job, int W, size_t p, size_t *first, int *w) {
-    const size_t head = (W >= 8 && job >= (size_t)3 * W) ? (size_t)(W / 4 + W / 2) : 0;
-    if (head && p < (size_t)(W / 4)) { *first = 0; *w = W / 4; return; }
-    if (head && p < head) { *first = (size_t)(W / 4); *w = W / 2; return; }
-    const size_t full = (job - head) / (size_t)W * (size_t)W;
-    if (p - head < full) { *first = head + (p - head) / (size_t)W * (size_t)W; *w = W; return; }
-    size_t off = head + full;
-    int k = W;
-    for (;;) {
-        while ((size_t)k > job - off) k >>= 1;
-        if (p < off + (size_t)k || k <= 1) { *first = off; *w = k; return; }
-        off += (size_t)k;
-    }
-}
 /* the inputs of step i (samples [off, off + w * 8192) of the loop) go up: gathered into a pinned half, moved and decoded on the upload stream */
 typedef std::function<int(size_t i, size_t off, int w, int pool)> BatchStage;
 
-static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &stage_fn) {
-    const int N = p.N, NO = N + 3, NR = NO + p.n_blends, B = GDG_BLOCK_SIZE, enc_rows = p.enc_rows, f64_rows = p.f64_rows, out_width = p.out_width, W = p.W;
-    const size_t length = p.length, ws = p.ws, enc_bytes = p.enc_bytes;
-    const int R = p.deliver > 1 ? p.deliver : 1;                              /* the delivery factor: every byte count below is of the delivered length (deliver.h) */
-    const int RL = p.ratio_up > 0 ? p.ratio_up : 1, RM = p.ratio_down > 0 ? p.ratio_down : 1;      /* ... and the ratio behind it; 1 / 1: none */
-    const bool ratio = gdg_deliver_ratio_on(RL, RM);
-    /* a step's delivered rows: the loop begins at session sample p.dither_first of its job, and a ratio counts in job indices */
-    auto step_of = [&](size_t w, size_t off, size_t rows) { return deliver_ratio_step(w, off, (size_t)p.dither_first, R, RL, RM, (size_t)out_width, rows); };
-    double *const d_inputs = p.d_inputs, *const d_win = p.d_win;
-    unsigned char *const d_enc = p.d_enc;
-    const gdg_batch_options *opt = p.opt;
-    void *const *out_bytes = p.out_bytes;
-    const gdg_batch_shard_out *shard = p.shard;
-    const bool sharded = shard != nullptr, run_metro = p.run_metro, has_input = p.has_input;
-    const int trace = p.trace;
-    const double t_begin = p.t_begin;
-    auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    int r;
-    /* the block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step */
-    if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
-    struct Step { size_t off; int w; ReportSections sec; ListSections lists; size_t span_at; };
-    std::vector<Step> steps;
-    /* a slice steps where the whole job does (job_step): a step ends where the job's step ends (or the slice does), so that the windows --
-     * and with them what the units keep beyond the samples, the convolution's two history halves -- are those of the job run as one slice
-     * wherever the slicing allows it */
-    for (size_t off = 0; off < length;) {
-        const size_t at = p.origin_blocks + off / B, end = p.origin_blocks + length / B;
-        size_t first = 0;
-        int w1 = 1, w = 1;
-        job_step(p.job_blocks, W, at, &first, &w1);
-        const size_t room = std::min(first + (size_t)w1, end) - at;
-        while ((size_t)w * 2 <= room) w *= 2;
-        steps.push_back({ off, w, {}, {}, 0 });
-        off += (size_t)w * B;
-    }
-    /* A step comes down in `chunks` pieces of whole rows (the float64 rows of a shard ride with the last one), an event behind each: the
-     * scatter of piece c runs while piece c + 1 is on the bus -- the run's tail (last download, then last scatter) and its head are that
-     * much shorter; in between the device sets the pace either way. */
-    /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; behind them one section per live kind of the render
-     * report, [rows][w] -- N + 3 rows and the blends', a shard's N chain rows and the metronome's -- which come down with the last piece */
-    auto down_bytes = [&](size_t i) {
-        const size_t wb = (size_t)steps[i].w * B, row_bytes = step_of((size_t)steps[i].w, steps[i].off, 0).row_bytes;
-        return sharded ? (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
-    };
-    const size_t rec_rows = sharded ? (size_t)N + 1 : (size_t)NR;
-    ListShape list_shape[LIST_KINDS];
-    for (int k = 0; k < LIST_KINDS; k++) list_shape[k] = p.list[k].shape;
-    for (size_t i = 0; i < steps.size(); i++) {
-        steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
-        steps[i].lists = list_sections(steps[i].sec.end, list_shape, (size_t)steps[i].w);        /* behind the last of them: [fits][w], [w], [w], [w], [NR][w] */
-    }
-    /* the delivered rows' blocks: session block j of a step delivers the samples [span[j], span[j + 1]) of the step's rows, counted where every
-     * other count of a delivered step comes from (deliver.h); all steps' spans go up once, ahead of everything the loop enqueues */
-    if (p.list[LIST_DELIVERED].count) {
-        std::vector<unsigned long long> &spans = ctx->out_rec_spans;
-        spans.clear();
-        for (Step &st : steps) {
-            st.span_at = spans.size();
-            for (int j = 0; j <= st.w; j++) spans.push_back((unsigned long long)step_of((size_t)j, st.off, 0).samples);
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+/* ---- the three record kinds that are taken port by port: block statistics, band spectrum, true peak ----------------------------------- */
+/* rows that are measured as they lie: n_rows rows `stride` samples apart, whose records begin at record row first_rec of a kind's section */
+struct RowGroup { const double *rows; size_t stride; unsigned n_rows; size_t first_rec; };
+/* what the band spectrum's launch reads beside the rows */
+struct SpectrumTables { const gdg_spectrum_bands *bands; const double *win; double2 *tw, *tw2; };
+
+/* The launches of `kinds` (of REPORT_STATS, REPORT_BANDS and REPORT_TRUE_PEAK; one that is not live is passed over) over `samples` samples of
+ * every group's rows, the kinds in the outer loop: a group's records of kind k go to the rows [first_rec ..] of k's section [rows][w] in `enc` */
+static int port_records(gdg_ctx *ctx, std::initializer_list<int> kinds, const RowGroup *groups, int n_groups, size_t samples, size_t w, const ReportLive &live,
+                        const ReportSections &sec, unsigned char *enc, const SpectrumTables &spec) {
+    for (int k : kinds) {
+        if (!live.on(k)) continue;
+        for (int g = 0; g < n_groups; g++) {
+            const RowGroup &G = groups[g];
+            unsigned char *rec = enc + sec.at[k] + G.first_rec * w * live.elem[k];
+            if (k == REPORT_STATS) HIP_TRY(ctx, gdg_launch_block_stats(G.rows, G.stride, G.n_rows, samples, (unsigned)GDG_BLOCK_SIZE, rec, ctx->stream));
+            else if (k == REPORT_BANDS)
+                HIP_TRY(ctx, gdg_launch_block_spectrum(G.rows, G.stride, G.n_rows, samples, spec.win, spec.tw, spec.tw2, *spec.bands, reinterpret_cast<double *>(rec), ctx->stream));
+            else HIP_TRY(ctx, gdg_launch_block_true_peak(G.rows, G.stride, G.n_rows, samples, true_peak_table(), rec, ctx->stream));
         }
-        HIP_TRY(ctx, hipMemcpyAsync(p.d_out_rec_spans, spans.data(), spans.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
     }
+    return GDG_OK;
+}
+
+namespace {                                     /* nothing of the loop leaves this file */
+/* a step of the loop: the blocks [off / 8192, off / 8192 + w) of the slice (batch_steps.h), the sections behind its rows (report_sections.h) and
+ * where its block spans begin among the slice's (the delivered rows' records) */
+struct Step { size_t off; int w; ReportSections sec; ListSections lists; size_t span_at; };
+
+/* The block loop, controller.go:3076-3107 around controller.process (:2648-2783), `w` blocks per step: the steps of the slice `p` and what each
+ * of them enqueues on the compute, the download and (through stage_fn) the upload stream.  plan() lays the steps out, run() drives them. */
+struct BlockLoop {
+    static constexpr int B = GDG_BLOCK_SIZE;
+    gdg_ctx *const ctx;
+    const BatchLoop &p;
+    const BatchStage &stage_fn;
+    const int NO, NR;                           /* the window's N + 3 rows, and with the blends' behind them */
+    const int R, RL, RM;                        /* the delivery factor: every byte count below is of the delivered length (deliver.h); the ratio behind it; 1 / 1: none */
+    const bool ratio, sharded;
+    const size_t rec_rows;                      /* the record rows of a section: N + 3 and the blends', a shard's N chain rows and the metronome's */
+    std::vector<Step> steps;
     /* the rows of a section that are filed: every row (a shard without the metronome: that row stays zero); of the alignment records only
      * the measured ports' are written, and read */
     std::vector<size_t> filed[REPORT_KINDS];
-    for (int k = 0; k < REPORT_KINDS; k++) {
-        if (!p.live.on(k)) continue;
-        if (k == REPORT_ALIGN) { for (const gdg_align_pairs &q : *p.align) for (int j = 0; j < q.n; j++) filed[k].push_back((size_t)q.port[j]); }
-        else for (size_t o = 0; o < ((sharded && !run_metro) ? (size_t)N : rec_rows); o++) filed[k].push_back(o);
+    SpectrumTables spec = { nullptr, nullptr, nullptr, nullptr };
+    double2 *align_tw = nullptr, *transfer_tw = nullptr;
+    std::future<int> staged;                    /* the helper thread's gather in flight */
+    const std::vector<int> *helper_cpus = nullptr;
+
+    BlockLoop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &stage_fn)
+        : ctx(ctx), p(p), stage_fn(stage_fn), NO(p.N + 3), NR(p.N + 3 + p.n_blends), R(p.deliver > 1 ? p.deliver : 1), RL(p.ratio_up > 0 ? p.ratio_up : 1),
+          RM(p.ratio_down > 0 ? p.ratio_down : 1), ratio(gdg_deliver_ratio_on(RL, RM)), sharded(p.shard != nullptr), rec_rows(sharded ? (size_t)p.N + 1 : (size_t)NR) {}
+    ~BlockLoop() { if (staged.valid()) staged.wait(); }                      /* the helper thread works on this object */
+
+    /* a step's delivered rows: the loop begins at session sample p.dither_first of its job, and a ratio counts in job indices */
+    DeliverStep step_of(size_t w, size_t off, size_t rows) const { return deliver_ratio_step(w, off, (size_t)p.dither_first, R, RL, RM, (size_t)p.out_width, rows); }
+    int pieces(size_t i) const { return step_pieces(steps[i].w, p.enc_rows); }
+    size_t piece_row(size_t i, int c) const { return deliver_chunk_row((size_t)p.enc_rows, c, pieces(i)); }      /* first encoded row of piece c */
+    double *master() const { return p.d_win + (size_t)p.N * p.ws; }
+    double *metro() const { return master() + 2 * p.ws; }
+    unsigned char *enc_half(size_t i) const { return p.d_enc + (i & 1) * p.enc_bytes; }
+
+    /* what step i sends down: its encoded rows (and a shard's float64 rows), compact; behind them one section per live kind of the render
+     * report, [rows][w] -- N + 3 rows and the blends', a shard's N chain rows and the metronome's -- which come down with the last piece */
+    size_t down_bytes(size_t i) const {
+        const size_t wb = (size_t)steps[i].w * B, row_bytes = step_of((size_t)steps[i].w, steps[i].off, 0).row_bytes;
+        return sharded ? (((size_t)p.enc_rows * row_bytes + 15) & ~(size_t)15) + (size_t)p.f64_rows * wb * sizeof(double) : (size_t)NR * row_bytes;
     }
-    const size_t n_bands = p.bands ? (size_t)p.bands->n_bands : 0;
-    const double *spec_win = nullptr;
-    double2 *spec_tw = nullptr, *spec_tw2 = nullptr;
-    if (p.bands && (r = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2)) != GDG_OK) return r;
-    double2 *align_tw = nullptr, *align_tw2 = nullptr;
-    if (p.align && (r = fir_tables(ctx, GDG_ALIGN_BLOCK, &align_tw, &align_tw2)) != GDG_OK) return r;
-    double2 *transfer_tw = nullptr;
-    if (p.list[LIST_TRANSFER].count && (r = fir_tables(ctx, GDG_TRANSFER_BLOCK, &transfer_tw, &align_tw2)) != GDG_OK) return r;      /* the same transform's tables as the alignment's */
-    auto chunks_of = [&](size_t i) { return (steps[i].w >= 4 && enc_rows >= 8) ? 4 : 1; };
-    auto chunk_rows = [&](size_t i, int c) { return deliver_chunk_row((size_t)enc_rows, c, chunks_of(i)); };      /* first encoded row of piece c */
-    auto scatter = [&](size_t i) -> int {                                    /* step i's bytes from its pinned half into the files */
+
+    /* the steps (batch_steps.h), every step's sections, the delivered rows' spans, the filed rows and the kinds' tables */
+    int plan() {
+        int r;
+        if (ctx->all_channels.empty()) for (int c = 0; c < ctx->nch; c++) ctx->all_channels.push_back(c);
+        for (const SliceStep &s : slice_steps(p.job_blocks, p.origin_blocks, p.length / B, p.W)) steps.push_back({ s.off * B, s.w, {}, {}, 0 });
+        ListShape list_shape[LIST_KINDS];
+        for (int k = 0; k < LIST_KINDS; k++) list_shape[k] = p.list[k].shape;
+        for (size_t i = 0; i < steps.size(); i++) {
+            steps[i].sec = report_sections(p.live, rec_rows, (size_t)steps[i].w, down_bytes(i), true);
+            steps[i].lists = list_sections(steps[i].sec.end, list_shape, (size_t)steps[i].w);        /* behind the last of them: [fits][w], [w], [w], [w], [NR][w] */
+        }
+        /* the delivered rows' blocks: session block j of a step delivers the samples [span[j], span[j + 1]) of the step's rows, counted where every
+         * other count of a delivered step comes from (deliver.h); all steps' spans go up once, ahead of everything the loop enqueues */
+        if (p.list[LIST_DELIVERED].count) {
+            std::vector<unsigned long long> &spans = ctx->out_rec_spans;
+            spans.clear();
+            for (Step &st : steps) {
+                st.span_at = spans.size();
+                for (int j = 0; j <= st.w; j++) spans.push_back((unsigned long long)step_of((size_t)j, st.off, 0).samples);
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(p.d_out_rec_spans, spans.data(), spans.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+        }
+        for (int k = 0; k < REPORT_KINDS; k++) {
+            if (!p.live.on(k)) continue;
+            if (k == REPORT_ALIGN) { for (const gdg_align_pairs &q : *p.align) for (int j = 0; j < q.n; j++) filed[k].push_back((size_t)q.port[j]); }
+            else for (size_t o = 0; o < ((sharded && !p.run_metro) ? (size_t)p.N : rec_rows); o++) filed[k].push_back(o);
+        }
+        spec.bands = p.bands;
+        if (p.bands && (r = spectrum_tables(ctx, &spec.win, &spec.tw, &spec.tw2)) != GDG_OK) return r;
+        double2 *align_tw2 = nullptr;
+        if (p.align && (r = fir_tables(ctx, GDG_ALIGN_BLOCK, &align_tw, &align_tw2)) != GDG_OK) return r;
+        if (p.list[LIST_TRANSFER].count && (r = fir_tables(ctx, GDG_TRANSFER_BLOCK, &transfer_tw, &align_tw2)) != GDG_OK) return r;      /* the same transform's tables as the alignment's */
+        return GDG_OK;
+    }
+
+    /* step i's bytes from its pinned half into the files */
+    int scatter(size_t i) {
+        const Step &st = steps[i];
         const unsigned char *src = ctx->h_batch[i & 1];
-        const DeliverStep ds = step_of((size_t)steps[i].w, steps[i].off, (size_t)enc_rows);
-        const size_t wb = (size_t)steps[i].w * B, row_bytes = ds.row_bytes, at = ds.file_at;
-        const size_t f64_at = ((size_t)enc_rows * row_bytes + 15) & ~(size_t)15;
-        const int K = chunks_of(i);
+        const DeliverStep ds = step_of((size_t)st.w, st.off, (size_t)p.enc_rows);
+        const size_t wb = (size_t)st.w * B, row_bytes = ds.row_bytes, at = ds.file_at, enc_rows = (size_t)p.enc_rows;
+        const size_t f64_at = (enc_rows * row_bytes + 15) & ~(size_t)15;
+        const int K = pieces(i);
         for (int c = 0; c < K; c++) {
             HIP_TRY(ctx, hipEventSynchronize(ctx->batch_chunk[i & 1][c]));    /* piece c has landed */
-            const size_t o0 = chunk_rows(i, c), o1 = (c + 1 == K) ? (size_t)enc_rows + (size_t)f64_rows : chunk_rows(i, c + 1);
+            const size_t o0 = piece_row(i, c), o1 = (c + 1 == K) ? enc_rows + (size_t)p.f64_rows : piece_row(i, c + 1);
             copy_rows_parallel(ctx, o0, o1, [&](size_t o) {
-                if (o < (size_t)enc_rows) {
+                if (o < enc_rows) {
                     /* NULL: "skipping output" (:3143); a shard's row N is the metronome track */
-                    void *dst = (sharded && o == (size_t)N) ? shard->metronome_bytes : out_bytes[o];
+                    void *dst = (sharded && o == (size_t)p.N) ? p.shard->metronome_bytes : p.out_bytes[o];
                     if (dst) memcpy(static_cast<unsigned char *>(dst) + at, src + o * row_bytes, ds.copy_bytes);      /* without a ratio the whole row; with one its samples, not the pad */
                 } else {
-                    const size_t k = o - (size_t)enc_rows;
-                    double *dst = k == 0 ? shard->master_left : (k == 1 ? shard->master_right : shard->metronome);
-                    memcpy(dst + steps[i].off, src + f64_at + k * wb * sizeof(double), wb * sizeof(double));
+                    const size_t k = o - enc_rows;
+                    double *dst = k == 0 ? p.shard->master_left : (k == 1 ? p.shard->master_right : p.shard->metronome);
+                    memcpy(dst + st.off, src + f64_at + k * wb * sizeof(double), wb * sizeof(double));
                 }
             }, row_bytes);
         }
         for (int k = 0; k < REPORT_KINDS; k++)                               /* the last piece brought the step's sections: filed under the step's blocks */
-            if (p.live.on(k)) report_file(ctx, k, src + steps[i].sec.at[k], filed[k], (size_t)steps[i].w, steps[i].off / B);
+            if (p.live.on(k)) report_file(ctx, k, src + st.sec.at[k], filed[k], (size_t)st.w, st.off / B);
         for (int k = 0; k < LIST_KINDS; k++)
-            if (p.list[k].count) list_file(ctx, k, src + steps[i].lists.of[k].at, (size_t)steps[i].w, steps[i].off / B);
+            if (p.list[k].count) list_file(ctx, k, src + st.lists.of[k].at, (size_t)st.w, st.off / B);
         return GDG_OK;
-    };
-    HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));             /* rows zeroed */
-    if (has_input) HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_up_stream, ctx->batch_begin, 0));
-    auto stage = [&](size_t i, int pool = 0) -> int {
-        if (!has_input || i >= steps.size()) return GDG_OK;
+    }
+
+    int stage(size_t i, int pool = 0) {
+        if (!p.has_input || i >= steps.size()) return GDG_OK;
         return stage_fn(i, steps[i].off, steps[i].w, pool);
-    };
-    /* step i on the compute stream: the block loop's work for its w blocks, then the encoder into the step's half of `enc` */
-    auto enqueue_compute = [&](size_t i) -> int {
-        const size_t off = steps[i].off;
-        const int w = steps[i].w, h = (int)(i & 1), wb = w * B;               /* this step fills the first wb samples of the window's rows */
-        if (has_input) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_up_ready[h], 0));
-        const double *d_in = d_inputs + off;
-        double *d_master = d_win + (size_t)N * ws, *d_metro = d_master + 2 * ws;
-        unsigned char *enc = d_enc + h * enc_bytes;
-        if (opt->tuner_enqueue)
-            for (int j = 0; j < w; j++) if ((r = tuner_enqueue_rows(ctx, d_in + (size_t)j * B, length, B, opt->target_rate)) != GDG_OK) return r;
-        if ((r = process_rows(ctx, ctx->all_channels, d_in, d_win, B, opt->target_rate, (int)length, false, 1, nullptr, nullptr, w, (int)ws)) != GDG_OK) return r;
-        if (run_metro && (r = gdg_metronome_process_device(ctx, d_metro, wb)) != GDG_OK) return r;
+    }
+
+    /* step i's chain: the block loop's work for its w blocks, which fill the first w * 8192 samples of the window's rows */
+    int chain(size_t i) {
+        const int N = p.N, w = steps[i].w, wb = w * B;
+        const size_t ws = p.ws, length = p.length;
+        const uint32_t rate = p.opt->target_rate;
+        const double *d_in = p.d_inputs + steps[i].off;
+        double *d_master = master(), *d_metro = metro();
+        int r;
+        if (p.opt->tuner_enqueue)
+            for (int j = 0; j < w; j++) if ((r = tuner_enqueue_rows(ctx, d_in + (size_t)j * B, length, B, rate)) != GDG_OK) return r;
+        if ((r = process_rows(ctx, ctx->all_channels, d_in, p.d_win, B, rate, (int)length, false, 1, nullptr, nullptr, w, (int)ws)) != GDG_OK) return r;
+        if (p.run_metro && (r = gdg_metronome_process_device(ctx, d_metro, wb)) != GDG_OK) return r;
         /* the step's w frames are consecutive in their rows: ONE mix over w x 8192 samples gives the samples of w calls (a frame's first
          * samples find their delayed neighbours in the frame before instead of in the history, which holds the same values) */
-        if ((r = spatialize_rows(ctx, d_win, (int)ws, d_master, (int)ws, wb)) != GDG_OK) return r;
+        if ((r = spatialize_rows(ctx, p.d_win, (int)ws, d_master, (int)ws, wb)) != GDG_OK) return r;
         /* a shard's master rows stay partial sums: the aux input is added once, after the shards' sums (gdg_batch_finish_master) */
-        if (opt->metronome_to_master && !sharded) HIP_TRY(ctx, gdg_launch_add_aux(d_master, d_master + ws, d_metro, wb, ctx->stream));
-        if (opt->run_meters) {                                               /* ports: inputs | outputs | metronome | left, right (:2707-2777) */
-            if ((r = meter_rows(ctx, d_in, length, 0, N, wb, opt->target_rate)) != GDG_OK) return r;
-            if ((r = meter_rows(ctx, d_win, ws, N, N, wb, opt->target_rate)) != GDG_OK) return r;
-            if (run_metro && (r = meter_rows(ctx, d_metro, ws, 2 * N, 1, wb, opt->target_rate)) != GDG_OK) return r;
-            if (!sharded && (r = meter_rows(ctx, d_master, ws, 2 * N + 1, 2, wb, opt->target_rate)) != GDG_OK) return r;     /* a shard's master ports: gdg_batch_finish_master */
+        if (p.opt->metronome_to_master && !sharded) HIP_TRY(ctx, gdg_launch_add_aux(d_master, d_master + ws, d_metro, wb, ctx->stream));
+        if (p.opt->run_meters) {                                             /* ports: inputs | outputs | metronome | left, right (:2707-2777) */
+            if ((r = meter_rows(ctx, d_in, length, 0, N, wb, rate)) != GDG_OK) return r;
+            if ((r = meter_rows(ctx, p.d_win, ws, N, N, wb, rate)) != GDG_OK) return r;
+            if (p.run_metro && (r = meter_rows(ctx, d_metro, ws, 2 * N, 1, wb, rate)) != GDG_OK) return r;
+            if (!sharded && (r = meter_rows(ctx, d_master, ws, 2 * N + 1, 2, wb, rate)) != GDG_OK) return r;     /* a shard's master ports: gdg_batch_finish_master */
         }
+        return GDG_OK;
+    }
+
+    /* ... the blend rows and the records of the window's rows as the encoder is about to read them, into the sections of the step's half of `enc` */
+    int records(size_t i) {
+        const Step &st = steps[i];
+        const int N = p.N, w = st.w;
+        const size_t ws = p.ws, wb = (size_t)w * B;
+        unsigned char *enc = enc_half(i);
+        /* the blend rows, behind the metronome's: sums of the chain rows, which are final; every reader below takes them as rows like the others */
+        if (p.n_blends) {
+            /* terms that reach back read the step before: its tail is the history (a step has at least 8192 samples, a term reaches at most
+             * 4096 back).  This step's tail replaces it behind the sum and before the next step writes the window. */
+            HIP_TRY(ctx, gdg_launch_blend(p.blend, p.d_win, ws, wb, p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, p.d_win + (size_t)NO * ws, ws, ctx->stream));
+            if (p.d_blend_history) HIP_TRY(ctx, gdg_launch_blend_history_save(p.d_win, ws, wb, (unsigned)N, p.d_blend_history, ctx->stream));
+        }
+        /* statistics, then the band spectrum: the window's rows, and a shard's metronome row, which is row N + 2 of the window and record row N */
+        const unsigned n_win = sharded ? (unsigned)N : (unsigned)NR;
+        const RowGroup groups[2] = { { p.d_win, ws, n_win, 0 }, { metro(), ws, 1u, (size_t)N } };
+        const int n_groups = (sharded && p.run_metro) ? 2 : 1;
+        int r;
+        if ((r = port_records(ctx, { REPORT_STATS, REPORT_BANDS }, groups, n_groups, wb, (size_t)w, p.live, st.sec, enc, spec)) != GDG_OK) return r;
+        if (p.align)                                                         /* ... the same rows, one more reader: a shard's metronome port is row N + 2, as metro() is */
+            for (const gdg_align_pairs &q : *p.align)
+                HIP_TRY(ctx, gdg_launch_block_align(p.d_win, ws, n_win, (unsigned)N + 2u, (unsigned)rec_rows, wb, q, align_tw, enc + st.sec.at[REPORT_ALIGN], ctx->stream));
+        /* ... and the inter-sample peaks of the same rows */
+        if ((r = port_records(ctx, { REPORT_TRUE_PEAK }, groups, n_groups, wb, (size_t)w, p.live, st.sec, enc, spec)) != GDG_OK) return r;
+        /* the list records of the same rows, the blends' among them: the fits' inner products, then the Gram of the listed rows and the
+         * tap fits' Gram of shifted rows on the matrix cores */
+        for (int k = 0; k < LIST_LAUNCHERS; k++)
+            if (p.list[k].count)
+                HIP_TRY(ctx, list_launch[k](p.d_win, ws, (unsigned)NR, wb, (unsigned)B, p.list[k].h_table, p.list[k].d_table, (unsigned)p.list[k].count, enc + st.lists.of[k].at, ctx->stream));
+        /* ... and the transfer records of the same rows: a block of the loop is a block of the record (8192 samples) */
+        if (const BatchLoop::List &T = p.list[LIST_TRANSFER]; T.count)
+            HIP_TRY(ctx, gdg_launch_block_transfer(p.d_win, ws, (unsigned)NR, wb, T.h_table, T.d_table, (unsigned)T.count, transfer_tw, enc + st.lists.of[LIST_TRANSFER].at, ctx->stream));
+        return GDG_OK;
+    }
+
+    /* ... and the rows' way into the step's half of `enc`: the delivery, the ratio behind it, the records of the delivered rows, the encoders */
+    int deliver_encode(size_t i) {
+        const Step &st = steps[i];
+        const int N = p.N, w = st.w;
+        const size_t ws = p.ws, wb = (size_t)w * B;
+        unsigned char *enc = enc_half(i);
+        const DeliverStep ds = step_of((size_t)w, st.off, 0);
+        const size_t row_bytes = ds.row_bytes;
+        /* dither on: n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
+        /* trim on: `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
+        /* delivered: the rows are the scratch rows' -- a row enc_stride apart (ws / R, behind a ratio its fixed pitch), ds.pitch samples of it (wb / R,
+         * behind a ratio the step's count rounded up to four) -- and a sample's index is its index in the delivered job */
+        const size_t enc_stride = ratio ? p.ratio_stride : ws / (size_t)R;
+        auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
+            const gdg_encode_mode m = { gains != nullptr, p.dither, gains, { 1.0, 1.0 }, { ctx->dither_seed, (uint64_t)ds.first_out, port_base, n_chain } };
+            return gdg_launch_wave_encode_rows(p.opt->out_format, rows, enc_stride, ds.pitch, n_rows, dst, m, ctx->stream);
+        };
+        /* the delivery: the window's NR rows, final by now and read by every record above as they are, decimated into the scratch rows -- the
+         * samples in front of the step come from the history, which this step's tail replaces behind the launch and before the next step
+         * writes the window.  The order is decimate, then gain, then the plain or dithered encoder: the encoders read the scratch rows. */
+        const double *enc_src = p.d_win;
+        if (R > 1) {
+            HIP_TRY(ctx, gdg_launch_deliver_rows(R, p.d_win, ws, wb, (unsigned)NR, p.d_deliver_taps, p.d_deliver_history, p.d_delivered, ws / (size_t)R, ctx->stream));
+            HIP_TRY(ctx, gdg_launch_deliver_history_save(p.d_win, ws, wb, (unsigned)NR, p.d_deliver_history, ctx->stream));
+            enc_src = p.d_delivered;
+        }
+        /* ... and the ratio behind the factor: the intermediate rows (the window's at factor 1, the scratch rows otherwise) resampled into rows
+         * of their own, +0.0 up to the pitch; their tail becomes the history before the next step writes them */
+        if (ratio) {
+            HIP_TRY(ctx, gdg_launch_deliver_ratio(RL, RM, enc_src, ws / (size_t)R, ds.inter_samples, (unsigned long long)ds.inter_first, (unsigned)NR, p.d_ratio_taps,
+                                                  p.d_ratio_history, p.d_ratio_rows, p.ratio_stride, ds.pitch, ctx->stream));
+            HIP_TRY(ctx, gdg_launch_deliver_ratio_history_save(enc_src, ws / (size_t)R, ds.inter_samples, (unsigned)NR, p.d_ratio_history, ctx->stream));
+            enc_src = p.d_ratio_rows;
+        }
+        /* the records of the rows the encoders are about to read, in front of any gain: the step's w blocks as the delivery cut them, the 23
+         * samples in front of the step from the history, which the step's tail replaces behind the launch */
+        if (p.list[LIST_DELIVERED].count) {
+            HIP_TRY(ctx, gdg_launch_block_delivered(enc_src, enc_stride, (unsigned)NR, ds.samples, p.d_out_rec_spans + st.span_at, (unsigned)w, p.d_out_rec_history,
+                                                    true_peak_table(), enc + st.lists.of[LIST_DELIVERED].at, ctx->stream));
+            HIP_TRY(ctx, gdg_launch_delivered_history_save(enc_src, enc_stride, ds.samples, (unsigned)NR, p.d_out_rec_history, ctx->stream));
+        }
+        if (!sharded) {
+            HIP_TRY(ctx, encode_rows(enc_src, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
+            /* a launch of their own: blend b is port port_base + N + 3 + b of the dither, and its gain is the blend's, not the trim's */
+            if (p.n_blends)
+                HIP_TRY(ctx, encode_rows(enc_src + (size_t)NO * enc_stride, (unsigned)p.n_blends, (unsigned)p.n_blends, ctx->dither_port_base + (uint32_t)NO,
+                                         enc + (size_t)NO * row_bytes, p.d_blend_gain));
+            return GDG_OK;
+        }
+        HIP_TRY(ctx, encode_rows(p.d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
+        if (p.shard->metronome_bytes)
+            HIP_TRY(ctx, encode_rows(metro(), 1u, 1u, GDG_DITHER_PORT_METRONOME, enc + (size_t)N * row_bytes, p.d_trim ? p.d_trim + N + GDG_TRIM_METRONOME : nullptr));
+        unsigned char *f64 = enc + (((size_t)p.enc_rows * row_bytes + 15) & ~(size_t)15);
+        HIP_TRY(ctx, hipMemcpy2DAsync(f64, wb * sizeof(double), master(), ws * sizeof(double), wb * sizeof(double), 2, hipMemcpyDeviceToDevice, ctx->stream));
+        if (p.shard->metronome) HIP_TRY(ctx, hipMemcpyAsync(f64 + 2 * wb * sizeof(double), metro(), wb * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        return GDG_OK;
+    }
+
+    /* step i on the compute stream: its chain, then -- once step i - 2 has left the step's half of `enc` -- its records and the encoders into that half */
+    int enqueue_compute(size_t i) {
+        const int h = (int)(i & 1);
+        int r;
+        if (p.has_input) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_up_ready[h], 0));
+        if ((r = chain(i)) != GDG_OK) return r;
         if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->batch_moved[h], 0));     /* step i - 2 has left enc */
         {
             ProfScope ps(ctx, GDG_K_WAVE);
-            const DeliverStep ds = step_of((size_t)w, off, 0);
-            const size_t row_bytes = ds.row_bytes;
-            const ReportSections &sec = steps[i].sec;
-            /* the blend rows, behind the metronome's: sums of the chain rows, which are final; every reader below takes them as rows like the others */
-            if (p.n_blends) {
-                /* terms that reach back read the step before: its tail is the history (a step has at least 8192 samples, a term reaches at most
-                 * 4096 back).  This step's tail replaces it behind the sum and before the next step writes the window. */
-                HIP_TRY(ctx, gdg_launch_blend(p.blend, d_win, ws, (size_t)wb, p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, d_win + (size_t)NO * ws, ws, ctx->stream));
-                if (p.d_blend_history) HIP_TRY(ctx, gdg_launch_blend_history_save(d_win, ws, (size_t)wb, (unsigned)N, p.d_blend_history, ctx->stream));
-            }
-            if (p.live.on(REPORT_STATS)) {                                   /* the rows as the encoder is about to read them */
-                gdg_block_stats *rec = reinterpret_cast<gdg_block_stats *>(enc + sec.at[REPORT_STATS]);
-                HIP_TRY(ctx, gdg_launch_block_stats(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, (unsigned)B, rec, ctx->stream));
-                if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_stats(d_metro, ws, 1u, (size_t)wb, (unsigned)B, rec + (size_t)N * w, ctx->stream));
-            }
-            if (p.bands) {                                                   /* the same rows, one more reader */
-                double *sp = reinterpret_cast<double *>(enc + sec.at[REPORT_BANDS]);
-                HIP_TRY(ctx, gdg_launch_block_spectrum(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp, ctx->stream));
-                if (sharded && run_metro)
-                    HIP_TRY(ctx, gdg_launch_block_spectrum(d_metro, ws, 1u, (size_t)wb, spec_win, spec_tw, spec_tw2, *p.bands, sp + (size_t)N * w * n_bands, ctx->stream));
-            }
-            if (p.align)                                                     /* ... and one more: a shard's metronome port is row N + 2, as d_metro is */
-                for (const gdg_align_pairs &q : *p.align)
-                    HIP_TRY(ctx, gdg_launch_block_align(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (unsigned)N + 2u, (unsigned)rec_rows, (size_t)wb, q, align_tw,
-                                                        enc + sec.at[REPORT_ALIGN], ctx->stream));
-            if (p.live.on(REPORT_TRUE_PEAK)) {                               /* ... and the inter-sample peaks of the same rows */
-                gdg_block_true_peak *tp = reinterpret_cast<gdg_block_true_peak *>(enc + sec.at[REPORT_TRUE_PEAK]);
-                HIP_TRY(ctx, gdg_launch_block_true_peak(d_win, ws, sharded ? (unsigned)N : (unsigned)NR, (size_t)wb, true_peak_table(), tp, ctx->stream));
-                if (sharded && run_metro) HIP_TRY(ctx, gdg_launch_block_true_peak(d_metro, ws, 1u, (size_t)wb, true_peak_table(), tp + (size_t)N * w, ctx->stream));
-            }
-            /* the list records of the same rows, the blends' among them: the fits' inner products, then the Gram of the listed rows and the
-             * tap fits' Gram of shifted rows on the matrix cores */
-            for (int k = 0; k < LIST_LAUNCHERS; k++)
-                if (p.list[k].count)
-                    HIP_TRY(ctx, list_launch[k](d_win, ws, (unsigned)NR, (size_t)wb, (unsigned)B, p.list[k].h_table, p.list[k].d_table, (unsigned)p.list[k].count,
-                                                enc + steps[i].lists.of[k].at, ctx->stream));
-            /* ... and the transfer records of the same rows: a block of the loop is a block of the record (8192 samples) */
-            if (const BatchLoop::List &T = p.list[LIST_TRANSFER]; T.count)
-                HIP_TRY(ctx, gdg_launch_block_transfer(d_win, ws, (unsigned)NR, (size_t)wb, T.h_table, T.d_table, (unsigned)T.count, transfer_tw,
-                                                       enc + steps[i].lists.of[LIST_TRANSFER].at, ctx->stream));
-            /* dither on: n_chain rows are chain outputs from port_base on, the rows behind them the job-wide ones */
-            /* trim on: `gains` = the gain of the launch's first row (the trim's in the window's order, the blends' own), null: none */
-            /* delivered: the rows are the scratch rows' -- a row enc_stride apart (ws / R, behind a ratio its fixed pitch), ds.pitch samples of it (wb / R,
-             * behind a ratio the step's count rounded up to four) -- and a sample's index is its index in the delivered job */
-            const size_t enc_stride = ratio ? p.ratio_stride : ws / (size_t)R;
-            auto encode_rows = [&](const double *rows, unsigned n_rows, unsigned n_chain, uint32_t port_base, unsigned char *dst, const double *gains) -> hipError_t {
-                const gdg_encode_mode m = { gains != nullptr, p.dither, gains, { 1.0, 1.0 }, { ctx->dither_seed, (uint64_t)ds.first_out, port_base, n_chain } };
-                return gdg_launch_wave_encode_rows(opt->out_format, rows, enc_stride, ds.pitch, n_rows, dst, m, ctx->stream);
-            };
-            /* the delivery: the window's NR rows, final by now and read by every record above as they are, decimated into the scratch rows -- the
-             * samples in front of the step come from the history, which this step's tail replaces behind the launch and before the next step
-             * writes the window.  The order is decimate, then gain, then the plain or dithered encoder: the encoders read the scratch rows. */
-            const double *enc_src = d_win;
-            if (R > 1) {
-                HIP_TRY(ctx, gdg_launch_deliver_rows(R, d_win, ws, (size_t)wb, (unsigned)NR, p.d_deliver_taps, p.d_deliver_history, p.d_delivered, ws / (size_t)R, ctx->stream));
-                HIP_TRY(ctx, gdg_launch_deliver_history_save(d_win, ws, (size_t)wb, (unsigned)NR, p.d_deliver_history, ctx->stream));
-                enc_src = p.d_delivered;
-            }
-            /* ... and the ratio behind the factor: the intermediate rows (the window's at factor 1, the scratch rows otherwise) resampled into rows
-             * of their own, +0.0 up to the pitch; their tail becomes the history before the next step writes them */
-            if (ratio) {
-                HIP_TRY(ctx, gdg_launch_deliver_ratio(RL, RM, enc_src, ws / (size_t)R, ds.inter_samples, (unsigned long long)ds.inter_first, (unsigned)NR, p.d_ratio_taps,
-                                                      p.d_ratio_history, p.d_ratio_rows, p.ratio_stride, ds.pitch, ctx->stream));
-                HIP_TRY(ctx, gdg_launch_deliver_ratio_history_save(enc_src, ws / (size_t)R, ds.inter_samples, (unsigned)NR, p.d_ratio_history, ctx->stream));
-                enc_src = p.d_ratio_rows;
-            }
-            /* the records of the rows the encoders are about to read, in front of any gain: the step's w blocks as the delivery cut them, the 23
-             * samples in front of the step from the history, which the step's tail replaces behind the launch */
-            if (p.list[LIST_DELIVERED].count) {
-                HIP_TRY(ctx, gdg_launch_block_delivered(enc_src, enc_stride, (unsigned)NR, ds.samples, p.d_out_rec_spans + steps[i].span_at, (unsigned)w, p.d_out_rec_history,
-                                                        true_peak_table(), enc + steps[i].lists.of[LIST_DELIVERED].at, ctx->stream));
-                HIP_TRY(ctx, gdg_launch_delivered_history_save(enc_src, enc_stride, ds.samples, (unsigned)NR, p.d_out_rec_history, ctx->stream));
-            }
-            if (!sharded) {
-                HIP_TRY(ctx, encode_rows(enc_src, (unsigned)NO, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
-                /* a launch of their own: blend b is port port_base + N + 3 + b of the dither, and its gain is the blend's, not the trim's */
-                if (p.n_blends)
-                    HIP_TRY(ctx, encode_rows(enc_src + (size_t)NO * enc_stride, (unsigned)p.n_blends, (unsigned)p.n_blends, ctx->dither_port_base + (uint32_t)NO,
-                                             enc + (size_t)NO * row_bytes, p.d_blend_gain));
-            } else {
-                HIP_TRY(ctx, encode_rows(d_win, (unsigned)N, (unsigned)N, ctx->dither_port_base, enc, p.d_trim));
-                if (shard->metronome_bytes)
-                    HIP_TRY(ctx, encode_rows(d_metro, 1u, 1u, GDG_DITHER_PORT_METRONOME, enc + (size_t)N * row_bytes, p.d_trim ? p.d_trim + N + GDG_TRIM_METRONOME : nullptr));
-                unsigned char *f64 = enc + (((size_t)enc_rows * row_bytes + 15) & ~(size_t)15);
-                HIP_TRY(ctx, hipMemcpy2DAsync(f64, (size_t)wb * sizeof(double), d_master, ws * sizeof(double), (size_t)wb * sizeof(double), 2,
-                                              hipMemcpyDeviceToDevice, ctx->stream));
-                if (shard->metronome)
-                    HIP_TRY(ctx, hipMemcpyAsync(f64 + 2 * (size_t)wb * sizeof(double), d_metro, (size_t)wb * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            }
+            if ((r = records(i)) != GDG_OK || (r = deliver_encode(i)) != GDG_OK) return r;
         }
         HIP_TRY(ctx, hipEventRecord(ctx->batch_ready[h], ctx->stream));
         return GDG_OK;
-    };
-    /* ... and its way down on the download stream, into the step's pinned half (which step i - 2 must have left: scatter(i - 2) is done) */
-    auto enqueue_down = [&](size_t i) -> int {
+    }
+
+    /* ... and its way down on the download stream, into the step's pinned half (which step i - 2 must have left: scatter(i - 2) is done), in
+     * pieces(i) pieces of whole rows (batch_steps.h; the float64 rows of a shard and the sections ride with the last one), an event behind each */
+    int enqueue_down(size_t i) {
         const int h = (int)(i & 1);
-        unsigned char *enc = d_enc + h * enc_bytes;
+        unsigned char *enc = enc_half(i);
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_stream, ctx->batch_ready[h], 0));
         const size_t row_bytes = step_of((size_t)steps[i].w, steps[i].off, 0).row_bytes;
         const size_t down = steps[i].lists.end;
-        const int K = chunks_of(i);
+        const int K = pieces(i);
         for (int c = 0; c < K; c++) {
             size_t b0 = 0, b1 = 0;
-            deliver_chunk_bytes((size_t)enc_rows, row_bytes, c, K, down, &b0, &b1);
+            deliver_chunk_bytes((size_t)p.enc_rows, row_bytes, c, K, down, &b0, &b1);
             if (b1 > b0) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_batch[h] + b0, enc + b0, b1 - b0, hipMemcpyDeviceToHost, ctx->batch_stream));
             HIP_TRY(ctx, hipEventRecord(ctx->batch_chunk[h][c], ctx->batch_stream));
         }
         HIP_TRY(ctx, hipEventRecord(ctx->batch_moved[h], ctx->batch_stream));
         return GDG_OK;
-    };
-    /* The compute stream is kept TWO steps ahead of the files.  Round 2 enqueued step i + 1 only after step i - 1 had been scattered into
-     * the caller's buffers, which closed a loop of compute -> download -> scatter over two steps: (5.7 + 4.0 + 3.1) / 2 = 6.4 ms per step
-     * of 16 blocks where the device needs 5.7 (GDG_BATCH_TRACE).  Now step i + 2 is enqueued as soon as step i's download has finished (before
-     * its bytes are scattered), while step i + 1 is already queued behind step i on the device. */
-    if (trace) fprintf(stderr, "[batch] set-up %.2f ms\n", now_ms() - t_begin);
-    /* Gathering step i + 2's input bytes (1.9 ms of 16 blocks x 512 files) and scattering step i's output bytes (3.0 ms) were one thread's
-     * work, one after the other: 4.8 ms per step beside the device's 4.7 -- the host set the pace half of the time.  With windows of four
-     * blocks or more the gather runs on a helper thread with copy workers of its own (copy_pool_up), one step further ahead (step i + 3 while
-     * step i is scattered; its pinned half and its device half were step i + 1's, whose upload and decode are long done -- stage() waits
-     * for their event): the host's step is the scatter alone and the device sets the pace. */
-    const bool helper = has_input && ws >= (size_t)4 * B && steps.size() > 3;
-    std::future<int> staged;
-    struct Join { std::future<int> &f; ~Join() { if (f.valid()) f.wait(); } } join_on_exit{ staged };     /* stage() captures this frame by reference */
-    /* the upload side's copy workers are made HERE, by the caller's thread, and the helper thread goes where they go: with option "numa" = 2
-     * workers are bound to the node of the thread that makes them, and a helper the scheduler happened to start on the other socket would
-     * put the gather's workers a socket away from the caller's buffers and the pinned halves */
-    const std::vector<int> *helper_cpus = nullptr;
-    if (helper) { ensure_copy_pool(ctx, 1); numa_target(ctx, &helper_cpus); }
-    auto on_helper = [&](size_t first, size_t last) {                        /* stage(first .. last), one after the other, on the helper thread */
+    }
+
+    /* stage(first .. last), one after the other, on the helper thread */
+    void on_helper(size_t first, size_t last) {
         if (first >= steps.size()) return;
         try {
-            staged = std::async(std::launch::async, [&, first, last]() -> int {
+            staged = std::async(std::launch::async, [this, first, last]() -> int {
                 if (helper_cpus) numa_bind_thread(*helper_cpus);
                 if (hipSetDevice(ctx->device) != hipSuccess) return GDG_ERR_HIP;
                 for (size_t k = first; k <= last && k < steps.size(); k++) { const int rr = stage(k, 1); if (rr != GDG_OK) return rr; }
@@ -467,42 +477,69 @@ static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &
             done.set_value(rr);
             staged = done.get_future();
         }
-    };
-    auto stage_async = [&](size_t i) { on_helper(i, i); };
-    if (helper) {
-        /* the head: step 0 is gathered here; steps 1 and 2 on the helper meanwhile, so that the first whole window's bytes are on the bus
-         * while the quarter and the half window compute */
-        if ((r = stage(0)) != GDG_OK) return r;
-        on_helper(1, 2);
-        if ((r = enqueue_compute(0)) != GDG_OK || (r = enqueue_down(0)) != GDG_OK) return r;
-        if ((r = staged.get()) != GDG_OK) return r;
-        if ((r = enqueue_compute(1)) != GDG_OK || (r = enqueue_down(1)) != GDG_OK) return r;
-    } else {
-        for (size_t i = 0; i < 2 && i < steps.size(); i++) {
-            if ((r = stage(i)) != GDG_OK) return r;
-            if ((r = enqueue_compute(i)) != GDG_OK || (r = enqueue_down(i)) != GDG_OK) return r;
-        }
     }
-    if (trace) fprintf(stderr, "[batch] steps 0 and 1 staged and enqueued at %.2f ms\n", now_ms() - t_begin);
-    for (size_t i = 0; i < steps.size(); i++) {
-        const double t_it = now_ms();
+
+    int run() {
+        int r;
+        HIP_TRY(ctx, hipEventRecord(ctx->batch_begin, ctx->stream));         /* rows zeroed */
+        if (p.has_input) HIP_TRY(ctx, hipStreamWaitEvent(ctx->batch_up_stream, ctx->batch_begin, 0));
+        /* The compute stream is kept TWO steps ahead of the files.  Round 2 enqueued step i + 1 only after step i - 1 had been scattered into
+         * the caller's buffers, which closed a loop of compute -> download -> scatter over two steps: (5.7 + 4.0 + 3.1) / 2 = 6.4 ms per step
+         * of 16 blocks where the device needs 5.7 (GDG_BATCH_TRACE).  Now step i + 2 is enqueued as soon as step i's download has finished (before
+         * its bytes are scattered), while step i + 1 is already queued behind step i on the device. */
+        if (p.trace) fprintf(stderr, "[batch] set-up %.2f ms\n", now_ms() - p.t_begin);
+        /* Gathering step i + 2's input bytes (1.9 ms of 16 blocks x 512 files) and scattering step i's output bytes (3.0 ms) were one thread's
+         * work, one after the other: 4.8 ms per step beside the device's 4.7 -- the host set the pace half of the time.  With windows of four
+         * blocks or more the gather runs on a helper thread with copy workers of its own (copy_pool_up), one step further ahead (step i + 3 while
+         * step i is scattered; its pinned half and its device half were step i + 1's, whose upload and decode are long done -- stage() waits
+         * for their event): the host's step is the scatter alone and the device sets the pace. */
+        const bool helper = p.has_input && p.ws >= (size_t)4 * B && steps.size() > 3;
+        /* the upload side's copy workers are made HERE, by the caller's thread, and the helper thread goes where they go: with option "numa" = 2
+         * workers are bound to the node of the thread that makes them, and a helper the scheduler happened to start on the other socket would
+         * put the gather's workers a socket away from the caller's buffers and the pinned halves */
+        if (helper) { ensure_copy_pool(ctx, 1); numa_target(ctx, &helper_cpus); }
         if (helper) {
-            if (staged.valid() && (r = staged.get()) != GDG_OK) return r;     /* step i + 2's inputs are on their way up (i = 0: since the head) */
-            stage_async(i + 3);
-        } else if ((r = stage(i + 2)) != GDG_OK) return r;                   /* while steps i, i + 1 run: the inputs of step i + 2 go up ... */
-        const double t_st = now_ms();
-        const double t_wait = t_st;
-        /* step i + 2 needs step i's half of `enc` (the compute stream waits for its download itself) but not its pinned half: it goes onto
-         * the compute stream BEFORE the scatter, so the loop compute -> download -> compute spans 5.7 + 4.0 ms per two steps and the device,
-         * not the host, sets the pace */
-        if (i + 2 < steps.size() && (r = enqueue_compute(i + 2)) != GDG_OK) return r;
-        const double t_enq = now_ms();
-        if ((r = scatter(i)) != GDG_OK) return r;                            /* ... step i comes down and goes into the files, piece by piece */
-        if (i + 2 < steps.size() && (r = enqueue_down(i + 2)) != GDG_OK) return r;     /* its pinned half is free again */
-        if (trace) fprintf(stderr, "[batch] step %zu (w %d): stage %zu %.2f | (%.2f) | enqueue %zu %.2f | download + scatter %.2f  (at %.2f ms)\n", i, steps[i].w, i + 2,
-                           t_st - t_it, t_wait - t_st, i + 2, t_enq - t_wait, now_ms() - t_enq, now_ms() - t_begin);
+            /* the head: step 0 is gathered here; steps 1 and 2 on the helper meanwhile, so that the first whole window's bytes are on the bus
+             * while the quarter and the half window compute */
+            if ((r = stage(0)) != GDG_OK) return r;
+            on_helper(1, 2);
+            if ((r = enqueue_compute(0)) != GDG_OK || (r = enqueue_down(0)) != GDG_OK) return r;
+            if ((r = staged.get()) != GDG_OK) return r;
+            if ((r = enqueue_compute(1)) != GDG_OK || (r = enqueue_down(1)) != GDG_OK) return r;
+        } else {
+            for (size_t i = 0; i < 2 && i < steps.size(); i++) {
+                if ((r = stage(i)) != GDG_OK) return r;
+                if ((r = enqueue_compute(i)) != GDG_OK || (r = enqueue_down(i)) != GDG_OK) return r;
+            }
+        }
+        if (p.trace) fprintf(stderr, "[batch] steps 0 and 1 staged and enqueued at %.2f ms\n", now_ms() - p.t_begin);
+        for (size_t i = 0; i < steps.size(); i++) {
+            const double t_it = now_ms();
+            if (helper) {
+                if (staged.valid() && (r = staged.get()) != GDG_OK) return r;     /* step i + 2's inputs are on their way up (i = 0: since the head) */
+                on_helper(i + 3, i + 3);
+            } else if ((r = stage(i + 2)) != GDG_OK) return r;                   /* while steps i, i + 1 run: the inputs of step i + 2 go up ... */
+            const double t_st = now_ms();
+            const double t_wait = t_st;
+            /* step i + 2 needs step i's half of `enc` (the compute stream waits for its download itself) but not its pinned half: it goes onto
+             * the compute stream BEFORE the scatter, so the loop compute -> download -> compute spans 5.7 + 4.0 ms per two steps and the device,
+             * not the host, sets the pace */
+            if (i + 2 < steps.size() && (r = enqueue_compute(i + 2)) != GDG_OK) return r;
+            const double t_enq = now_ms();
+            if ((r = scatter(i)) != GDG_OK) return r;                            /* ... step i comes down and goes into the files, piece by piece */
+            if (i + 2 < steps.size() && (r = enqueue_down(i + 2)) != GDG_OK) return r;     /* its pinned half is free again */
+            if (p.trace) fprintf(stderr, "[batch] step %zu (w %d): stage %zu %.2f | (%.2f) | enqueue %zu %.2f | download + scatter %.2f  (at %.2f ms)\n", i, steps[i].w, i + 2,
+                                 t_st - t_it, t_wait - t_st, i + 2, t_enq - t_wait, now_ms() - t_enq, now_ms() - p.t_begin);
+        }
+        return check_device_error(ctx);
     }
-    return check_device_error(ctx);
+};
+}
+
+static int batch_block_loop(gdg_ctx *ctx, const BatchLoop &p, const BatchStage &stage_fn) {
+    BlockLoop loop(ctx, p, stage_fn);
+    const int r = loop.plan();
+    return r != GDG_OK ? r : loop.run();
 }
 
 /* ================================================================================================
@@ -981,6 +1018,272 @@ int gdg_batch_stream_close(gdg_ctx *ctx) {
     return GDG_OK;
 }
 
+/* a job with shared sources: channel c reads another channel's input (its root's piece is stored to its row as well) */
+static bool is_reader(const gdg_ctx::BatchStreamState &S, int c) { return !S.source.empty() && S.source[(size_t)c] != c; }
+
+/* What ONE STEP (at most W blocks) can bring per input, and the halves that hold it: the sizes depend on the window, not on the slice or the
+ * job.  An upload half: the descriptors -- a piece and a carry per input; with shared sources the descriptors are the fan-out forms (a step
+ * without a reader writes the plain ones into the same room) and a table of the rows they name follows: every channel's row once, two
+ * source-buffer rows per resampled root -- then the inputs' pieces.  A source half: the resampled inputs' frames. */
+namespace {                                     /* nothing of the upload side leaves this file */
+struct UploadLayout {
+    std::vector<size_t> cap, src_off;
+    std::vector<double> dx;
+    size_t dec_rows_bytes, spans_bytes, table_bytes, up_rows_bytes, up_half, src_half;
+    bool any;                                   /* some input has samples */
+};
+
+static UploadLayout upload_layout(const gdg_ctx::BatchStreamState &S, int N, size_t ws) {
+    const bool shared = !S.source.empty();
+    UploadLayout L = { std::vector<size_t>((size_t)N, 0), std::vector<size_t>((size_t)N, 0), std::vector<double>((size_t)N, 1.0), 0, 0, 0, 0, 0, 0, false };
+    L.dec_rows_bytes = ((size_t)2 * N * (shared ? sizeof(gdg_decode_fan) : sizeof(gdg_decode_row)) + 255) & ~(size_t)255;
+    L.spans_bytes = ((size_t)N * (shared ? sizeof(gdg_resample_fan) : sizeof(gdg_resample_span)) + 255) & ~(size_t)255;
+    L.table_bytes = shared ? ((size_t)3 * N * sizeof(double *) + 255) & ~(size_t)255 : 0;
+    L.up_half = L.up_rows_bytes = L.dec_rows_bytes + L.spans_bytes + L.table_bytes;
+    for (int i = 0; i < N; i++) {
+        const gdg_batch_input &in = S.inputs[(size_t)i];
+        if (!in.bytes || !in.samples_per_channel) continue;
+        L.any = true;
+        if (is_reader(S, i)) continue;                                           /* only roots size the upload halves and the source halves */
+        L.cap[(size_t)i] = ws;
+        if (in.sample_rate != S.opt.target_rate) {
+            L.dx[(size_t)i] = (double)in.sample_rate / (double)S.opt.target_rate;
+            L.cap[(size_t)i] = (size_t)((double)ws * L.dx[(size_t)i]) + 16;
+            L.src_off[(size_t)i] = L.src_half;
+            L.src_half += ((L.cap[(size_t)i] + GDG_STREAM_CARRY) * sizeof(double) + 15) & ~(size_t)15;
+        }
+        L.up_half += (L.cap[(size_t)i] * in.channels * (size_t)gdg_wave_bytes_per_sample(in.format) + 15) & ~(size_t)15;
+    }
+    L.up_half = (L.up_half + 255) & ~(size_t)255;                               /* the second half starts with descriptors: aligned like the first */
+    L.src_half = (L.src_half + 255) & ~(size_t)255;
+    return L;
+}
+
+/* One step's upload while it is put together in its pinned half: the plain descriptors where they go; with shared sources the fan-out forms,
+ * made aside and written into the half once the step is known to have a reader (or not: then as the plain descriptors, for the kernels every
+ * other job runs), and the table of the rows they name; the host pieces to move, and how far the half is filled */
+struct StepUpload {
+    gdg_decode_row *rows;
+    gdg_resample_span *spans;
+    size_t cur;
+    std::vector<gdg_decode_fan> dfans;
+    std::vector<gdg_resample_fan> rfans;
+    std::vector<double *> table;
+    std::vector<BatchPiece> pieces;
+    bool step_fans = false;
+    int n_rows = 0, n_spans = 0;
+    unsigned max_count = 0, max_out = 0;
+};
+
+/* The upload side of a slice (BatchStage): step i's inputs, the loop's samples [a, a + w * 8192), gathered into pinned half i & 1, moved and
+ * decoded -- and resampled -- on the upload stream.  It keeps, from step to step, which halves are in use and the frames handed over. */
+struct SliceStage {
+    gdg_ctx *ctx;
+    const gdg_ctx::BatchStreamState &S;
+    const void *const *in_bytes;
+    const UploadLayout &L;
+    const SourceFans &fans;
+    const std::vector<size_t> &first, &count;   /* the frames the slice brings per input (stream_need) */
+    size_t length, pos;
+    double *d_inputs, *d_carry;
+    unsigned char *d_up, *d_src;
+    std::vector<size_t> run;                    /* frames handed over, step by step */
+    int up_used[2];
+
+    /* the rows root c feeds in this step into the table: `own` (its row, or its place in the source buffer), then its readers' rows */
+    void fan_rows(StepUpload &u, double *own, int c, size_t a, bool with_readers, unsigned *dst_first, unsigned *n_dst, unsigned *vec) const {
+        *dst_first = (unsigned)u.table.size();
+        u.table.push_back(own);
+        if (with_readers)
+            for (int k = 0; k < fans.fan(c); k++) u.table.push_back(d_inputs + (size_t)fans.readers(c)[k] * length + a);
+        *n_dst = (unsigned)u.table.size() - *dst_first;
+        *vec = 1;
+        for (size_t k = *dst_first; k < u.table.size(); k++) if ((uintptr_t)u.table[k] & 15) *vec = 0;
+        if (*n_dst > 1) u.step_fans = true;
+    }
+    void put_row(StepUpload &u, const unsigned char *src, double *dst, int c, size_t a, bool with_readers, unsigned cnt, int fmt, unsigned stride, unsigned offset) const {
+        if (S.source.empty()) { u.rows[u.n_rows++] = gdg_decode_row{ src, dst, cnt, fmt, stride, offset }; return; }
+        gdg_decode_fan f = { src, cnt, fmt, stride, offset, 0, 0, 0, 0 };
+        fan_rows(u, dst, c, a, with_readers, &f.dst_first, &f.n_dst, &f.vec);
+        u.dfans.push_back(f);
+        u.n_rows++;
+    }
+
+    /* input c's part of the step [a, a + span) in half h: its fresh frames as host pieces, its decode rows and, at another rate, its span */
+    int input(StepUpload &u, int c, int h, size_t a, size_t span) {
+        const gdg_batch_input &in = S.inputs[(size_t)c];
+        const uint32_t rate = S.opt.target_rate;
+        const size_t abs = pos + a;                                          /* the step: the job's samples [abs, abs + span) */
+        if (is_reader(S, c)) return GDG_OK;                                  /* its root's piece is stored to its row as well */
+        if (!in.bytes || !in.samples_per_channel || abs >= S.n_out[(size_t)c]) return GDG_OK;      /* empty, or ended in an earlier step: zeros */
+        unsigned char *hb = ctx->h_up[h], *db = d_up + (size_t)h * L.up_half, *sb = d_src + (size_t)h * L.src_half;
+        const size_t cnt = std::min(S.n_out[(size_t)c] - abs, span), width = (size_t)gdg_wave_bytes_per_sample(in.format) * in.channels;
+        size_t sf = 0, sc = 0;
+        gdg_batch_stream_span(in.samples_per_channel, in.sample_rate, rate, abs, cnt, &sf, &sc);
+        const size_t bs = run[(size_t)c], e = std::max(bs, sf + sc), fresh = e - bs;
+        if (fresh > L.cap[(size_t)c] || bs < first[(size_t)c] || e > first[(size_t)c] + count[(size_t)c])
+            return fail(ctx, GDG_ERR_INVALID, "input %d: a step of %zu frames from %zu does not fit its slice", c, fresh, bs);
+        run[(size_t)c] = e;
+        const unsigned char *src = static_cast<const unsigned char *>(in_bytes[c]) + (bs - first[(size_t)c]) * width;
+        const unsigned stride = in.channels > 1 ? in.channels : 0;
+        double *row = d_inputs + (size_t)c * length + a;
+        unsigned char *piece = db + u.cur;
+        if (fresh) {
+            for (size_t q = 0; q < fresh * width; q += (size_t)1 << 20)
+                u.pieces.push_back({ hb + u.cur + q, src + q, std::min(fresh * width - q, (size_t)1 << 20) });
+            u.cur += (fresh * width + 15) & ~(size_t)15;
+            if (fresh > u.max_count) u.max_count = (unsigned)fresh;
+            ctx->batch_up_bytes += fresh * width;
+        }
+        if (in.sample_rate == rate) {
+            if (bs != abs || fresh != cnt) return fail(ctx, GDG_ERR_INVALID, "input %d: step at %zu, frames from %zu", c, abs, bs);
+            put_row(u, piece, row, c, a, true, (unsigned)cnt, in.format, stride, in.channel);
+            return GDG_OK;
+        }
+        /* resample.Time: [the frames kept from the step before | this step's], then the span kernel */
+        const size_t keep_in = std::min(bs, (size_t)GDG_STREAM_CARRY), held = keep_in + fresh;
+        if (sf < bs - keep_in) return fail(ctx, GDG_ERR_INVALID, "input %d: the resampler looks back to frame %zu, kept from %zu", c, sf, bs - keep_in);
+        double *frames = reinterpret_cast<double *>(sb + L.src_off[(size_t)c]), *carry = d_carry + (size_t)c * GDG_STREAM_CARRY;
+        if (keep_in) put_row(u, reinterpret_cast<const unsigned char *>(carry), frames, c, a, false, (unsigned)keep_in, GDG_FMT_IEEE64, 0, 0);
+        if (fresh) put_row(u, piece, frames + keep_in, c, a, false, (unsigned)fresh, in.format, stride, in.channel);
+        if (keep_in > u.max_count) u.max_count = (unsigned)keep_in;
+        const gdg_resample_span sp = { frames, row, carry, (long long)(bs - keep_in), (long long)in.samples_per_channel, (long long)abs,
+                                       L.dx[(size_t)c], (unsigned)cnt, (unsigned)held, (unsigned)std::min(held, (size_t)GDG_STREAM_CARRY), 0 };
+        if (S.source.empty()) u.spans[u.n_spans++] = sp;
+        else {
+            gdg_resample_fan f = { sp, 0, 0 };
+            unsigned vec = 0;
+            fan_rows(u, row, c, a, true, &f.dst_first, &f.n_dst, &vec);
+            u.rfans.push_back(f);
+            u.n_spans++;
+        }
+        ctx->batch_resampled += cnt;
+        if (cnt > u.max_out) u.max_out = (unsigned)cnt;
+        return GDG_OK;
+    }
+
+    /* the step put together: its descriptors written, its pieces moved into the pinned half, the half sent up, decode and resample launched */
+    int send(StepUpload &u, int h, int pool) {
+        unsigned char *hb = ctx->h_up[h], *db = d_up + (size_t)h * L.up_half;
+        if (!S.source.empty() && u.n_rows) {
+            if (u.table.size() * sizeof(double *) > L.table_bytes) return fail(ctx, GDG_ERR_INVALID, "a step names %zu rows, its table holds %d", u.table.size(), 3 * ctx->nch);
+            if (u.step_fans) {
+                memcpy(hb, u.dfans.data(), u.dfans.size() * sizeof(gdg_decode_fan));
+                if (u.n_spans) memcpy(hb + L.dec_rows_bytes, u.rfans.data(), u.rfans.size() * sizeof(gdg_resample_fan));
+                memcpy(hb + L.dec_rows_bytes + L.spans_bytes, u.table.data(), u.table.size() * sizeof(double *));
+            } else {                                                         /* no reader in this step: every fan is its first row */
+                for (size_t k = 0; k < u.dfans.size(); k++)
+                    u.rows[k] = gdg_decode_row{ u.dfans[k].src, u.table[u.dfans[k].dst_first], u.dfans[k].count, u.dfans[k].fmt, u.dfans[k].stride, u.dfans[k].offset };
+                for (size_t k = 0; k < u.rfans.size(); k++) u.spans[k] = u.rfans[k].span;
+            }
+        }
+        if (u.n_rows) {
+            move_pieces(ctx, u.pieces, pool);
+            HIP_TRY(ctx, hipMemcpyAsync(db, hb, u.cur, hipMemcpyHostToDevice, ctx->batch_up_stream));
+            if (u.step_fans) {
+                /* the fan-out launches: a root's piece decoded once, its span resampled once, stored to every row of its fan */
+                double *const *d_table = reinterpret_cast<double *const *>(db + L.dec_rows_bytes + L.spans_bytes);
+                HIP_TRY(ctx, gdg_launch_wave_decode_fans(reinterpret_cast<const gdg_decode_fan *>(db), d_table, u.n_rows, u.max_count, ctx->batch_up_stream));
+                HIP_TRY(ctx, gdg_launch_resample_fans(reinterpret_cast<const gdg_resample_fan *>(db + L.dec_rows_bytes), d_table, u.n_spans, u.max_out, ctx->batch_up_stream));
+            } else {
+                /* ONE decode launch for every piece and every kept frame, ONE resample launch for every resampled input */
+                HIP_TRY(ctx, gdg_launch_wave_decode_rows(reinterpret_cast<const gdg_decode_row *>(db), u.n_rows, u.max_count, ctx->batch_up_stream));
+                HIP_TRY(ctx, gdg_launch_resample_spans(reinterpret_cast<const gdg_resample_span *>(db + L.dec_rows_bytes), u.n_spans, u.max_out, ctx->batch_up_stream));
+            }
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
+        return GDG_OK;
+    }
+
+    int operator()(size_t i, size_t a, int w, int pool) {
+        const int h = (int)(i & 1);
+        if (up_used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_up_ready[h]));     /* step i - 2 has left this half */
+        StepUpload u = { reinterpret_cast<gdg_decode_row *>(ctx->h_up[h]), reinterpret_cast<gdg_resample_span *>(ctx->h_up[h] + L.dec_rows_bytes), L.up_rows_bytes };
+        for (int c = 0; c < ctx->nch; c++)
+            if (const int r = input(u, c, h, a, (size_t)w * GDG_BLOCK_SIZE)) return r;
+        up_used[h] = 1;
+        return send(u, h, pool);
+    }
+};
+}
+
+/* The settings in force go up, and `loop` gets what they need on the device: the list records' tables, the trim, the blends, the delivery, the
+ * ratio behind it and the delivered records' buffers of a slice of `blocks` blocks at the job's sample `pos`.  n_blends, R, RL / RM: the
+ * blends, the delivery factor and the ratio in force -- never a shard's. */
+static int slice_settings(gdg_ctx *ctx, const ListInForce *lists, int n_blends, int R, int RL, int RM, size_t pos, int blocks, BatchLoop &loop) {
+    const int N = ctx->nch, NO = N + 3, NR = NO + n_blends;
+    const size_t ws = loop.ws;
+    int r;
+    /* the list records in force.  A kind with a table -- the fits', the Gram list, the tap fits', the transfer list's: it goes up into the
+     * kind's slot on the context's stream, ahead of everything the slice enqueues there; it lives as long as the setting, so nothing waits here */
+    for (int k = 0; k < LIST_KINDS; k++) {
+        const ListInForce &L = lists[k];
+        if (!L.count) continue;
+        int *d_table = nullptr;
+        if (L.ints > 0) {
+            if ((r = batch_buffer(ctx, BATCH_FIT_TABLE + k, L.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(d_table, L.table, L.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        }
+        loop.list[k] = { L.table, d_table, L.count, L.shape };
+    }
+    /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
+    if (!ctx->trim_gain.empty()) {
+        if (!ctx->d_trim && hipMalloc((void **)&ctx->d_trim, (size_t)NO * sizeof(double)) != hipSuccess)
+            return fail(ctx, GDG_ERR_NOMEM, "the batch run cannot allocate the trim's %d gains on the device", NO);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_trim, ctx->trim_gain.data(), (size_t)NO * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        loop.d_trim = ctx->d_trim;
+    }
+    /* the blends in force: their table goes up the same way, as it was packed when the list was taken (blend.h, gdg_blend_pack) */
+    if (n_blends) {
+        const BlendSet &bs = ctx->blend;                                      /* it lives as long as the setting, so nothing waits here */
+        const size_t bytes = bs.packed.size();
+        if (bytes > ctx->d_blend_cap) {
+            hipFree(ctx->d_blend);
+            ctx->d_blend = nullptr;
+            ctx->d_blend_cap = 0;
+            if (hipMalloc((void **)&ctx->d_blend, bytes) != hipSuccess) return fail(ctx, GDG_ERR_NOMEM, "the batch run cannot allocate the table of %d blends on the device", n_blends);
+            ctx->d_blend_cap = bytes;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_blend, bs.packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        loop.n_blends = n_blends;
+        loop.blend = bs.view(ctx->d_blend);
+        loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.blend.gain;
+        if (bs.max_reach() > 0) {
+            /* the history of the N chain rows: the job's first slice begins from zeros, every later one from what the slice before left */
+            if ((r = carried_history(ctx, BATCH_BLEND_HISTORY, (size_t)N * GDG_BLEND_MAX_DELAY * sizeof(double), pos, "blend", &loop.d_blend_history)) != GDG_OK) return r;
+        }
+    }
+    /* the delivery in force: the scratch rows the encoders read, and the history of the window's NR rows -- the job's first slice begins from
+     * zeros, every later one from what the slice before left */
+    if (R > 1) {
+        if ((r = batch_buffer(ctx, BATCH_DELIVERED, (size_t)NR * (ws / (size_t)R) * sizeof(double), (void **)&loop.d_delivered)) != GDG_OK) return r;
+        if ((r = carried_history(ctx, BATCH_DELIVER_HISTORY, (size_t)NR * GDG_DELIVER_HISTORY * sizeof(double), pos, "delivery", &loop.d_deliver_history)) != GDG_OK) return r;
+        loop.deliver = R;
+        loop.d_deliver_taps = R == 2 ? ctx->os.taps2 : ctx->os.taps4;           /* the oversampler's expanded tables (api_ctx.cpp) */
+    }
+    /* ... and the ratio behind it: the rows the encoders then read, at the window's fixed pitch; the table, which goes up ahead of everything the
+     * slice enqueues; the history of the NR intermediate rows, zeroed by the job's first slice like the factor's */
+    if (gdg_deliver_ratio_on(RL, RM)) {
+        const size_t table_bytes = ctx->deliver_tapsT.size() * sizeof(double);
+        double *d_table = nullptr;
+        loop.ratio_stride = gdg_deliver_pitch(R, RL, RM, ws);
+        if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_ROWS, (size_t)NR * loop.ratio_stride * sizeof(double), (void **)&loop.d_ratio_rows)) != GDG_OK) return r;
+        if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_TABLE, table_bytes, (void **)&d_table)) != GDG_OK) return r;
+        if ((r = carried_history(ctx, BATCH_DELIVER_RATIO_HISTORY, (size_t)NR * GDG_DELIVER_RATIO_HISTORY * sizeof(double), pos, "delivery ratio's", &loop.d_ratio_history)) != GDG_OK) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->deliver_tapsT.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
+        loop.ratio_up = RL;
+        loop.ratio_down = RM;
+        loop.d_ratio_taps = d_table;
+    }
+    /* the delivered rows' records: the history of the NR rows the encoders read, zeroed by the job's first slice like the deliveries'; room for
+     * the spans of the slice's steps -- a step has w + 1 of them, so never more than two per block */
+    if (lists[LIST_DELIVERED].count) {
+        if ((r = batch_buffer(ctx, BATCH_DELIVERED_REC_SPANS, (size_t)2 * (size_t)blocks * sizeof(unsigned long long), (void **)&loop.d_out_rec_spans)) != GDG_OK) return r;
+        if ((r = carried_history(ctx, BATCH_DELIVERED_REC_HISTORY, (size_t)NR * GDG_OUT_RECORDS_HISTORY * sizeof(double), pos, "delivered rows'", &loop.d_out_rec_history)) != GDG_OK) return r;
+    }
+    return GDG_OK;
+}
+
 /* The slice runner: the job's samples [S.pos, S.pos + blocks * 8192), which the caller has checked to lie in the job; `slice`: the partial
  * master and metronome buffers of a shard's job, null for any other.  The job is the caller's (an open one of the context, or the
  * one-call run's own) and is left as it is: `brought` gets what the caller commits with S.pos once the slice has run.  `begun`: the
@@ -1005,10 +1308,8 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
         if (lists[k].count) list_begin(ctx, k, (size_t)blocks, NR);
     }
     ctx->batch_up_bytes = ctx->batch_resampled = 0;
-    /* a job with shared sources: the rows every root feeds beside its own; everything below that sizes, gathers or checks walks the roots */
-    const bool shared = !S.source.empty();
-    const SourceFans fans = shared ? sources_fans(S.source) : SourceFans();
-    auto reader = [&](int c) { return shared && S.source[(size_t)c] != c; };
+    /* a job with shared sources: the rows every root feeds beside its own; everything that sizes, gathers or checks walks the roots */
+    const SourceFans fans = S.source.empty() ? SourceFans() : sources_fans(S.source);
     std::vector<size_t> first((size_t)N), count((size_t)N);
     stream_need(S, length, first.data(), count.data());
     for (int i = 0; i < N; i++)
@@ -1030,52 +1331,25 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     const size_t enc_bytes = ((deliver_ratio_window_bytes((size_t)W, R, RL, RM, (size_t)out_width, (size_t)enc_room) + 15) & ~(size_t)15) + (size_t)f64_room * ws * sizeof(double)
                            + report_room(live, (size_t)(sharded ? N + 1 : NR), (size_t)W) + lists_room(list_shape, (size_t)W);
     const size_t half = std::max(enc_bytes, (size_t)8 << 20);
-    /* what ONE STEP (at most W blocks) can bring per input: the sizes below depend on the window, not on the slice or the job */
-    std::vector<size_t> cap((size_t)N, 0), src_off((size_t)N, 0);
-    std::vector<double> dx((size_t)N, 1.0);
-    /* a piece and a carry per input; with shared sources the descriptors are the fan-out forms (a step without a reader writes the plain ones
-     * into the same room) and a table of the rows they name follows: every channel's row once, two source-buffer rows per resampled root */
-    const size_t dec_rows_bytes = ((size_t)2 * N * (shared ? sizeof(gdg_decode_fan) : sizeof(gdg_decode_row)) + 255) & ~(size_t)255;
-    const size_t spans_bytes = ((size_t)N * (shared ? sizeof(gdg_resample_fan) : sizeof(gdg_resample_span)) + 255) & ~(size_t)255;
-    const size_t table_bytes = shared ? ((size_t)3 * N * sizeof(double *) + 255) & ~(size_t)255 : 0;
-    const size_t up_rows_bytes = dec_rows_bytes + spans_bytes + table_bytes;
-    size_t up_half = up_rows_bytes, src_half = 0;
-    bool any = false;
-    for (int i = 0; i < N; i++) {
-        const gdg_batch_input &in = S.inputs[(size_t)i];
-        if (!in.bytes || !in.samples_per_channel) continue;
-        any = true;
-        if (reader(i)) continue;                                                 /* only roots size the upload halves and the source halves */
-        cap[(size_t)i] = ws;
-        if (in.sample_rate != opt->target_rate) {
-            dx[(size_t)i] = (double)in.sample_rate / (double)opt->target_rate;
-            cap[(size_t)i] = (size_t)((double)ws * dx[(size_t)i]) + 16;
-            src_off[(size_t)i] = src_half;
-            src_half += ((cap[(size_t)i] + GDG_STREAM_CARRY) * sizeof(double) + 15) & ~(size_t)15;
-        }
-        up_half += (cap[(size_t)i] * in.channels * (size_t)gdg_wave_bytes_per_sample(in.format) + 15) & ~(size_t)15;
-    }
-    up_half = (up_half + 255) & ~(size_t)255;                                   /* the second half starts with descriptors: aligned like the first */
-    src_half = (src_half + 255) & ~(size_t)255;
-    rc = ensure_batch_pipe(ctx, half, up_half);
+    const UploadLayout L = upload_layout(S, N, ws);
+    rc = ensure_batch_pipe(ctx, half, L.up_half);
     if (rc != GDG_OK) return rc;
-    double *d_inputs = nullptr, *d_win = nullptr, *d_carry = nullptr;
-    unsigned char *d_enc = nullptr, *d_up = nullptr, *d_src = nullptr;
     static int trace = -1;
     if (trace < 0) { const char *e = getenv("GDG_BATCH_TRACE"); trace = e ? atoi(e) : 0; }
-    const double t_begin = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    std::vector<size_t> run(S.brought);                                          /* frames handed over, step by step */
+    const double t_begin = now_ms();
     begun = true;
     auto body = [&]() -> int {
         int r;
+        double *d_inputs = nullptr, *d_win = nullptr, *d_carry = nullptr;
+        unsigned char *d_enc = nullptr, *d_up = nullptr, *d_src = nullptr;
         if ((r = batch_buffer(ctx, BATCH_INPUTS, (size_t)N * length * sizeof(double), (void **)&d_inputs)) != GDG_OK) return r;
         /* one window of the N + 3 outputs, rows in the output files' order (out_0 .. out_{N-1}, master left, master right, metronome,
          * controller.go:3123-3219), and behind them the rows of the blends in force; the inputs are read where they lie */
         if ((r = batch_buffer(ctx, BATCH_WINDOW, (size_t)NR * ws * sizeof(double), (void **)&d_win)) != GDG_OK) return r;
         if ((r = batch_buffer(ctx, BATCH_ENCODED, 2 * enc_bytes, (void **)&d_enc)) != GDG_OK) return r;
         if ((r = batch_carry_buffer(ctx, &d_carry)) != GDG_OK) return r;
-        if ((r = batch_buffer(ctx, BATCH_UPLOAD, 2 * up_half, (void **)&d_up)) != GDG_OK) return r;
-        if (src_half && (r = batch_buffer(ctx, BATCH_SOURCE, 2 * src_half, (void **)&d_src)) != GDG_OK) return r;
+        if ((r = batch_buffer(ctx, BATCH_UPLOAD, 2 * L.up_half, (void **)&d_up)) != GDG_OK) return r;
+        if (L.src_half && (r = batch_buffer(ctx, BATCH_SOURCE, 2 * L.src_half, (void **)&d_src)) != GDG_OK) return r;
         /* the zero padding (controller.go:3018-3045): what no step of this slice will write */
         for (int i = 0; i < N; i++) {
             const size_t n_out = S.n_out[(size_t)i];
@@ -1083,189 +1357,13 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
             if (covered < length)
                 HIP_TRY(ctx, hipMemsetAsync(d_inputs + (size_t)i * length + covered, 0, (length - covered) * sizeof(double), ctx->stream));
         }
-        int up_used[2] = { 0, 0 };
-        BatchStage stage = [&](size_t i, size_t a, int w, int pool) -> int {
-            const int h = (int)(i & 1);
-            if (up_used[h]) HIP_TRY(ctx, hipEventSynchronize(ctx->batch_up_ready[h]));     /* step i - 2 has left this half */
-            unsigned char *hb = ctx->h_up[h], *db = d_up + (size_t)h * up_half, *sb = d_src + (size_t)h * src_half;
-            gdg_decode_row *rows = reinterpret_cast<gdg_decode_row *>(hb);
-            gdg_resample_span *spans = reinterpret_cast<gdg_resample_span *>(hb + dec_rows_bytes);
-            /* shared sources: the step's descriptors in their fan-out form, made here and written into the half once the step is known to have
-             * a reader (or not: then as the plain descriptors, for the kernels every other job runs) */
-            std::vector<gdg_decode_fan> dfans;
-            std::vector<gdg_resample_fan> rfans;
-            std::vector<double *> table;
-            bool step_fans = false;
-            /* the rows root c feeds in this step into the table: `own` (its row, or its place in the source buffer), then its readers' rows */
-            auto fan_rows = [&](double *own, int c, size_t a, bool with_readers, unsigned *dst_first, unsigned *n_dst, unsigned *vec) {
-                *dst_first = (unsigned)table.size();
-                table.push_back(own);
-                if (with_readers)
-                    for (int k = 0; k < fans.fan(c); k++) table.push_back(d_inputs + (size_t)fans.readers(c)[k] * length + a);
-                *n_dst = (unsigned)table.size() - *dst_first;
-                *vec = 1;
-                for (size_t k = *dst_first; k < table.size(); k++) if ((uintptr_t)table[k] & 15) *vec = 0;
-                if (*n_dst > 1) step_fans = true;
-            };
-            auto put_row = [&](const unsigned char *src, double *dst, int c, size_t a, bool with_readers, unsigned cnt, int fmt, unsigned stride, unsigned offset, int &n_rows) {
-                if (!shared) { rows[n_rows++] = gdg_decode_row{ src, dst, cnt, fmt, stride, offset }; return; }
-                gdg_decode_fan f = { src, cnt, fmt, stride, offset, 0, 0, 0, 0 };
-                fan_rows(dst, c, a, with_readers, &f.dst_first, &f.n_dst, &f.vec);
-                dfans.push_back(f);
-                n_rows++;
-            };
-            std::vector<BatchPiece> pieces;
-            size_t cur = up_rows_bytes;
-            int n_rows = 0, n_spans = 0;
-            unsigned max_count = 0, max_out = 0;
-            const size_t span = (size_t)w * B, abs = pos + a;                    /* the step: the job's samples [abs, abs + span) */
-            for (int c = 0; c < N; c++) {
-                const gdg_batch_input &in = S.inputs[(size_t)c];
-                if (reader(c)) continue;                                         /* its root's piece is stored to its row as well */
-                if (!in.bytes || !in.samples_per_channel || abs >= S.n_out[(size_t)c]) continue;      /* empty, or ended in an earlier step: zeros */
-                const size_t cnt = std::min(S.n_out[(size_t)c] - abs, span), width = (size_t)gdg_wave_bytes_per_sample(in.format) * in.channels;
-                size_t sf = 0, sc = 0;
-                gdg_batch_stream_span(in.samples_per_channel, in.sample_rate, opt->target_rate, abs, cnt, &sf, &sc);
-                const size_t bs = run[(size_t)c], e = std::max(bs, sf + sc), fresh = e - bs;
-                if (fresh > cap[(size_t)c] || bs < first[(size_t)c] || e > first[(size_t)c] + count[(size_t)c])
-                    return fail(ctx, GDG_ERR_INVALID, "input %d: a step of %zu frames from %zu does not fit its slice", c, fresh, bs);
-                run[(size_t)c] = e;
-                const unsigned char *src = static_cast<const unsigned char *>(in_bytes[c]) + (bs - first[(size_t)c]) * width;
-                const unsigned stride = in.channels > 1 ? in.channels : 0;
-                double *row = d_inputs + (size_t)c * length + a;
-                unsigned char *piece = db + cur;
-                if (fresh) {
-                    for (size_t q = 0; q < fresh * width; q += (size_t)1 << 20)
-                        pieces.push_back({ hb + cur + q, src + q, std::min(fresh * width - q, (size_t)1 << 20) });
-                    cur += (fresh * width + 15) & ~(size_t)15;
-                    if (fresh > max_count) max_count = (unsigned)fresh;
-                    ctx->batch_up_bytes += fresh * width;
-                }
-                if (in.sample_rate == opt->target_rate) {
-                    if (bs != abs || fresh != cnt) return fail(ctx, GDG_ERR_INVALID, "input %d: step at %zu, frames from %zu", c, abs, bs);
-                    put_row(piece, row, c, a, true, (unsigned)cnt, in.format, stride, in.channel, n_rows);
-                    continue;
-                }
-                /* resample.Time: [the frames kept from the step before | this step's], then the span kernel */
-                const size_t keep_in = std::min(bs, (size_t)GDG_STREAM_CARRY), held = keep_in + fresh;
-                if (sf < bs - keep_in) return fail(ctx, GDG_ERR_INVALID, "input %d: the resampler looks back to frame %zu, kept from %zu", c, sf, bs - keep_in);
-                double *frames = reinterpret_cast<double *>(sb + src_off[(size_t)c]), *carry = d_carry + (size_t)c * GDG_STREAM_CARRY;
-                if (keep_in) put_row(reinterpret_cast<const unsigned char *>(carry), frames, c, a, false, (unsigned)keep_in, GDG_FMT_IEEE64, 0, 0, n_rows);
-                if (fresh) put_row(piece, frames + keep_in, c, a, false, (unsigned)fresh, in.format, stride, in.channel, n_rows);
-                if (keep_in > max_count) max_count = (unsigned)keep_in;
-                const gdg_resample_span sp = { frames, row, carry, (long long)(bs - keep_in), (long long)in.samples_per_channel, (long long)abs,
-                                               dx[(size_t)c], (unsigned)cnt, (unsigned)held, (unsigned)std::min(held, (size_t)GDG_STREAM_CARRY), 0 };
-                if (!shared) spans[n_spans++] = sp;
-                else {
-                    gdg_resample_fan f = { sp, 0, 0 };
-                    unsigned vec = 0;
-                    fan_rows(row, c, a, true, &f.dst_first, &f.n_dst, &vec);
-                    rfans.push_back(f);
-                    n_spans++;
-                }
-                ctx->batch_resampled += cnt;
-                if (cnt > max_out) max_out = (unsigned)cnt;
-            }
-            up_used[h] = 1;
-            if (shared && n_rows) {
-                if (table.size() * sizeof(double *) > table_bytes) return fail(ctx, GDG_ERR_INVALID, "a step names %zu rows, its table holds %d", table.size(), 3 * N);
-                if (step_fans) {
-                    memcpy(hb, dfans.data(), dfans.size() * sizeof(gdg_decode_fan));
-                    if (n_spans) memcpy(hb + dec_rows_bytes, rfans.data(), rfans.size() * sizeof(gdg_resample_fan));
-                    memcpy(hb + dec_rows_bytes + spans_bytes, table.data(), table.size() * sizeof(double *));
-                } else {                                                         /* no reader in this step: every fan is its first row */
-                    for (size_t k = 0; k < dfans.size(); k++)
-                        rows[k] = gdg_decode_row{ dfans[k].src, table[dfans[k].dst_first], dfans[k].count, dfans[k].fmt, dfans[k].stride, dfans[k].offset };
-                    for (size_t k = 0; k < rfans.size(); k++) spans[k] = rfans[k].span;
-                }
-            }
-            if (n_rows) {
-                move_pieces(ctx, pieces, pool);
-                HIP_TRY(ctx, hipMemcpyAsync(db, hb, cur, hipMemcpyHostToDevice, ctx->batch_up_stream));
-                if (step_fans) {
-                    /* the fan-out launches: a root's piece decoded once, its span resampled once, stored to every row of its fan */
-                    double *const *d_table = reinterpret_cast<double *const *>(db + dec_rows_bytes + spans_bytes);
-                    HIP_TRY(ctx, gdg_launch_wave_decode_fans(reinterpret_cast<const gdg_decode_fan *>(db), d_table, n_rows, max_count, ctx->batch_up_stream));
-                    HIP_TRY(ctx, gdg_launch_resample_fans(reinterpret_cast<const gdg_resample_fan *>(db + dec_rows_bytes), d_table, n_spans, max_out, ctx->batch_up_stream));
-                } else {
-                    /* ONE decode launch for every piece and every kept frame, ONE resample launch for every resampled input */
-                    HIP_TRY(ctx, gdg_launch_wave_decode_rows(reinterpret_cast<const gdg_decode_row *>(db), n_rows, max_count, ctx->batch_up_stream));
-                    HIP_TRY(ctx, gdg_launch_resample_spans(reinterpret_cast<const gdg_resample_span *>(db + dec_rows_bytes), n_spans, max_out, ctx->batch_up_stream));
-                }
-            }
-            HIP_TRY(ctx, hipEventRecord(ctx->batch_up_ready[h], ctx->batch_up_stream));
-            return GDG_OK;
-        };
-        BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, any, trace, t_begin,
+        SliceStage stage_state = { ctx, S, in_bytes, L, fans, first, count, length, pos, d_inputs, d_carry, d_up, d_src, {}, { 0, 0 } };
+        stage_state.run = S.brought;
+        const BatchStage stage = std::ref(stage_state);
+        BatchLoop loop{ N, enc_rows, f64_rows, out_width, W, length, ws, enc_bytes, d_inputs, d_win, d_enc, opt, out_bytes, slice, S.run_metro, L.any, trace, t_begin,
                         S.length / B, pos / B, live, gdg_dither_applies(ctx->dither_mode, opt->out_format), (uint64_t)pos, live.on(REPORT_BANDS) ? &bands : nullptr,
                         live.on(REPORT_ALIGN) ? &pairs : nullptr, nullptr, 0, {}, nullptr, nullptr, {} };
-        /* the list records in force.  A kind with a table -- the fits', the Gram list, the tap fits', the transfer list's: it goes up into the
-         * kind's slot on the context's stream, ahead of everything the slice enqueues there; it lives as long as the setting, so nothing waits here */
-        for (int k = 0; k < LIST_KINDS; k++) {
-            const ListInForce &L = lists[k];
-            if (!L.count) continue;
-            int *d_table = nullptr;
-            if (L.ints > 0) {
-                if ((r = batch_buffer(ctx, BATCH_FIT_TABLE + k, L.ints * sizeof(int), (void **)&d_table)) != GDG_OK) return r;
-                HIP_TRY(ctx, hipMemcpyAsync(d_table, L.table, L.ints * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            }
-            loop.list[k] = { L.table, d_table, L.count, L.shape };
-        }
-        /* the trim in force: its N + 3 gains go up on the context's stream, ahead of everything the slice enqueues there */
-        if (!ctx->trim_gain.empty()) {
-            if (!ctx->d_trim && hipMalloc((void **)&ctx->d_trim, (size_t)NO * sizeof(double)) != hipSuccess)
-                return fail(ctx, GDG_ERR_NOMEM, "the batch run cannot allocate the trim's %d gains on the device", NO);
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_trim, ctx->trim_gain.data(), (size_t)NO * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            loop.d_trim = ctx->d_trim;
-        }
-        /* the blends in force: their table goes up the same way, as it was packed when the list was taken (blend.h, gdg_blend_pack) */
-        if (n_blends) {
-            const BlendSet &bs = ctx->blend;                                  /* it lives as long as the setting, so nothing waits here */
-            const size_t bytes = bs.packed.size();
-            if (bytes > ctx->d_blend_cap) {
-                hipFree(ctx->d_blend);
-                ctx->d_blend = nullptr;
-                ctx->d_blend_cap = 0;
-                if (hipMalloc((void **)&ctx->d_blend, bytes) != hipSuccess) return fail(ctx, GDG_ERR_NOMEM, "the batch run cannot allocate the table of %d blends on the device", n_blends);
-                ctx->d_blend_cap = bytes;
-            }
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_blend, bs.packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-            loop.n_blends = n_blends;
-            loop.blend = bs.view(ctx->d_blend);
-            loop.d_blend_gain = bs.unit_gains() ? nullptr : loop.blend.gain;
-            if (bs.max_reach() > 0) {
-                /* the history of the N chain rows: the job's first slice begins from zeros, every later one from what the slice before left */
-                if ((r = carried_history(ctx, BATCH_BLEND_HISTORY, (size_t)N * GDG_BLEND_MAX_DELAY * sizeof(double), pos, "blend", &loop.d_blend_history)) != GDG_OK) return r;
-            }
-        }
-        /* the delivery in force: the scratch rows the encoders read, and the history of the window's NR rows -- the job's first slice begins from
-         * zeros, every later one from what the slice before left */
-        if (R > 1) {
-            if ((r = batch_buffer(ctx, BATCH_DELIVERED, (size_t)NR * (ws / (size_t)R) * sizeof(double), (void **)&loop.d_delivered)) != GDG_OK) return r;
-            if ((r = carried_history(ctx, BATCH_DELIVER_HISTORY, (size_t)NR * GDG_DELIVER_HISTORY * sizeof(double), pos, "delivery", &loop.d_deliver_history)) != GDG_OK) return r;
-            loop.deliver = R;
-            loop.d_deliver_taps = R == 2 ? ctx->os.taps2 : ctx->os.taps4;       /* the oversampler's expanded tables (api_ctx.cpp) */
-        }
-        /* ... and the ratio behind it: the rows the encoders then read, at the window's fixed pitch; the table, which goes up ahead of everything the
-         * slice enqueues; the history of the NR intermediate rows, zeroed by the job's first slice like the factor's */
-        if (gdg_deliver_ratio_on(RL, RM)) {
-            const size_t table_bytes = ctx->deliver_tapsT.size() * sizeof(double);
-            double *d_table = nullptr;
-            loop.ratio_stride = gdg_deliver_pitch(R, RL, RM, ws);
-            if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_ROWS, (size_t)NR * loop.ratio_stride * sizeof(double), (void **)&loop.d_ratio_rows)) != GDG_OK) return r;
-            if ((r = batch_buffer(ctx, BATCH_DELIVER_RATIO_TABLE, table_bytes, (void **)&d_table)) != GDG_OK) return r;
-            if ((r = carried_history(ctx, BATCH_DELIVER_RATIO_HISTORY, (size_t)NR * GDG_DELIVER_RATIO_HISTORY * sizeof(double), pos, "delivery ratio's", &loop.d_ratio_history)) != GDG_OK) return r;
-            HIP_TRY(ctx, hipMemcpyAsync(d_table, ctx->deliver_tapsT.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
-            loop.ratio_up = RL;
-            loop.ratio_down = RM;
-            loop.d_ratio_taps = d_table;
-        }
-        /* the delivered rows' records: the history of the NR rows the encoders read, zeroed by the job's first slice like the deliveries'; room for
-         * the spans of the slice's steps -- a step has w + 1 of them, so never more than two per block */
-        if (lists[LIST_DELIVERED].count) {
-            if ((r = batch_buffer(ctx, BATCH_DELIVERED_REC_SPANS, (size_t)2 * (size_t)blocks * sizeof(unsigned long long), (void **)&loop.d_out_rec_spans)) != GDG_OK) return r;
-            if ((r = carried_history(ctx, BATCH_DELIVERED_REC_HISTORY, (size_t)NR * GDG_OUT_RECORDS_HISTORY * sizeof(double), pos, "delivered rows'", &loop.d_out_rec_history)) != GDG_OK) return r;
-        }
+        if ((r = slice_settings(ctx, lists, n_blends, R, RL, RM, pos, blocks, loop)) != GDG_OK) return r;
         return batch_block_loop(ctx, loop, stage);
     };
     rc = body();
@@ -1275,7 +1373,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     /* the device buffers stay with the context for the next slice or job (gdg_batch_release) */
     brought.resize((size_t)N);
     for (int i = 0; i < N; i++) brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
-    for (int i = 0; i < N; i++) if (reader(i)) brought[(size_t)i] = brought[(size_t)S.source[(size_t)i]];
+    for (int i = 0; i < N; i++) if (is_reader(S, i)) brought[(size_t)i] = brought[(size_t)S.source[(size_t)i]];
     return report_end(ctx, rc);
 }
 
@@ -1373,7 +1471,36 @@ static int finish_master_check(gdg_ctx *ctx, int out_format, const double *const
     return GDG_OK;
 }
 
-/* The master mix of a sharded job, or of one slice of it: master = ((p_0 + p_1) + ... + p_{G-1}) + aux per side, then the encoder (its clip
+/* what the master mix keeps on the context: its events, its two pairs of pinned halves, and on the device two slab halves (+ the two rows of
+ * sums the meters read, sums_bytes) and two halves of encoded rows */
+static int finish_master_room(gdg_ctx *ctx, size_t up_bytes, size_t down_bytes, size_t sums_bytes) {
+    if (!ctx->fin_up[0])
+        for (int h = 0; h < 2; h++) {
+            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_down[h], hipEventDisableTiming));
+        }
+    HIP_TRY(ctx, ctx->h_fin_up.grow(ctx, up_bytes));
+    HIP_TRY(ctx, ctx->h_fin_down.grow(ctx, down_bytes));
+    const int rc = ensure_io(ctx, 1, 2 * up_bytes + sums_bytes);
+    return rc != GDG_OK ? rc : ensure_io(ctx, 0, 2 * down_bytes);
+}
+
+/* the samples [at, at + n) of the G partial pairs and aux (null: none) into a pinned half: [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux],
+ * stride samples apart, the samples behind each row zeros */
+static void finish_master_gather(gdg_ctx *ctx, unsigned char *half, const double *const *left, const double *const *right, size_t G, const double *aux, size_t at,
+                                 size_t n, size_t stride) {
+    std::vector<BatchPiece> pieces;
+    for (size_t r = 0; r < 2 * G + (aux ? 1 : 0); r++) {
+        const double *src = (r < G ? left[r] : r < 2 * G ? right[r - G] : aux) + at;
+        unsigned char *row = half + r * stride * sizeof(double);
+        for (size_t q = 0; q < n * sizeof(double); q += (size_t)1 << 18)      /* pieces of <= 256 KiB: every worker gets some */
+            pieces.push_back({ row + q, reinterpret_cast<const unsigned char *>(src) + q, std::min(n * sizeof(double) - q, (size_t)1 << 18) });
+        memset(row + n * sizeof(double), 0, (stride - n) * sizeof(double));
+    }
+    move_pieces(ctx, pieces);
+}
+
+/* The master mix of a sharded job, or of one slice of it: master =((p_0 + p_1) + ... + p_{G-1}) + aux per side, then the encoder (its clip
  * included) -- all on this context's device, per piece ONE upload, ONE kernel and ONE download.  The copy workers gather the G partial
  * pairs and aux into a pinned slab half ([2 G + 1][stride] float64) while the piece before is on the bus; finish_master_kernel (io.hip)
  * adds and encodes; the encoded piece comes down into a pinned half and is scattered into the caller's buffers while the next piece
@@ -1388,15 +1515,14 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
         return report_end(ctx, fail(ctx, GDG_ERR_INVALID, "master mix: the band spectrum needs a positive sample rate"));
     if (samples == 0) return report_end(ctx, GDG_OK);
     const ReportLive live = report_live(ctx);                                    /* never the alignment records: report_begin above */
-    const bool report = live.on(REPORT_STATS), dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = live.on(REPORT_BANDS), true_peak = live.on(REPORT_TRUE_PEAK);
+    const bool dither = gdg_dither_applies(ctx->dither_mode, out_format), spectrum = live.on(REPORT_BANDS);
     /* the trim in force on the context that finishes: its two master gains, as kernel arguments */
     const bool trim = !ctx->trim_gain.empty();
     const double trim_left = trim ? ctx->trim_gain[(size_t)ctx->nch + GDG_TRIM_MASTER_LEFT] : 1.0, trim_right = trim ? ctx->trim_gain[(size_t)ctx->nch + GDG_TRIM_MASTER_RIGHT] : 1.0;
     enter(ctx);
     const gdg_spectrum_bands bands = spectrum ? spectrum_bands(ctx->spec_live_edges.data(), (int)ctx->spec_live_edges.size(), sample_rate) : gdg_spectrum_bands();
-    const double *spec_win = nullptr;
-    double2 *spec_tw = nullptr, *spec_tw2 = nullptr;
-    if (spectrum) { const int rs = spectrum_tables(ctx, &spec_win, &spec_tw, &spec_tw2); if (rs != GDG_OK) return report_end(ctx, rs); }
+    SpectrumTables spec = { &bands, nullptr, nullptr, nullptr };
+    if (spectrum) { const int rs = spectrum_tables(ctx, &spec.win, &spec.tw, &spec.tw2); if (rs != GDG_OK) return report_end(ctx, rs); }
     const size_t G = (size_t)n_shards, rows = 2 * G + (aux ? 1 : 0);
     /* a piece: whole blocks, a slab half of at most 8 MiB (one block at least) -- bounded whatever the sample count and the shard count */
     const size_t piece = B * std::min((size_t)128, std::max((size_t)1, ((size_t)8 << 20) / ((2 * G + 1) * B * sizeof(double))));
@@ -1404,16 +1530,7 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
     const ReportSections sec = report_sections(live, 2, piece / B, 2 * piece * width, false);
     const size_t up_bytes = (2 * G + 1) * piece * sizeof(double), down_bytes = sec.end;
     const std::vector<size_t> both_sides = { 0, 1 };
-    if (!ctx->fin_up[0])
-        for (int h = 0; h < 2; h++) {
-            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_up[h], hipEventDisableTiming));
-            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fin_down[h], hipEventDisableTiming));
-        }
-    HIP_TRY(ctx, ctx->h_fin_up.grow(ctx, up_bytes));
-    HIP_TRY(ctx, ctx->h_fin_down.grow(ctx, down_bytes));
-    /* the device side: two slab halves (+ the two rows of sums the meters read), two halves of encoded rows */
-    int rc = ensure_io(ctx, 1, 2 * up_bytes + 2 * piece * sizeof(double));
-    if (rc == GDG_OK) rc = ensure_io(ctx, 0, 2 * down_bytes);
+    int rc = finish_master_room(ctx, up_bytes, down_bytes, 2 * piece * sizeof(double));
     if (rc != GDG_OK) return rc;
     unsigned char *d_slab = static_cast<unsigned char *>(ctx->d_io[1]), *d_enc = static_cast<unsigned char *>(ctx->d_io[0]);
     double *d_sums = (run_meters || live.any()) ? reinterpret_cast<double *>(d_slab + 2 * up_bytes) : nullptr;
@@ -1424,17 +1541,9 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
         /* piece k's rows into its pinned half: [left_0 .. left_{G-1} | right_0 .. right_{G-1} | aux], stride samples apart */
         auto gather = [&](size_t k) -> int {
             const int h = (int)(k & 1);
-            const size_t n = span(k), stride = stride_of(n), at = k * piece;
+            const size_t n = span(k);
             if (k >= 2) HIP_TRY(ctx, hipEventSynchronize(ctx->fin_up[h]));     /* piece k - 2 has left this half */
-            std::vector<BatchPiece> pieces;
-            for (size_t r = 0; r < rows; r++) {
-                const double *src = (r < G ? left[r] : r < 2 * G ? right[r - G] : aux) + at;
-                unsigned char *row = ctx->h_fin_up[h] + r * stride * sizeof(double);
-                for (size_t q = 0; q < n * sizeof(double); q += (size_t)1 << 18)      /* pieces of <= 256 KiB: every worker gets some */
-                    pieces.push_back({ row + q, reinterpret_cast<const unsigned char *>(src) + q, std::min(n * sizeof(double) - q, (size_t)1 << 18) });
-                memset(row + n * sizeof(double), 0, (stride - n) * sizeof(double));
-            }
-            move_pieces(ctx, pieces);
+            finish_master_gather(ctx, ctx->h_fin_up[h], left, right, G, aux, k * piece, n, stride_of(n));
             return GDG_OK;
         };
         auto enqueue = [&](size_t k) -> int {
@@ -1453,20 +1562,12 @@ static int finish_master(gdg_ctx *ctx, int out_format, const double *const *left
             if (run_meters)
                 for (size_t o = 0; o < n; o += B)                                /* block by block, like the loop that fed the other ports */
                     if ((rc = meter_rows(ctx, d_sums + o, piece, ctx->n_meter - 2, 2, (int)std::min(B, n - o), sample_rate)) != GDG_OK) return rc;
-            /* kind k's [2][nb] elements of this piece, just launched into its section, on their way down */
-            auto section_down = [&](int k) { return hipMemcpyAsync(ctx->h_fin_down[h] + sec.at[k], enc + sec.at[k], 2 * nb * live.elem[k], hipMemcpyDeviceToHost, ctx->stream); };
-            if (report) {                                                    /* the sums: after the aux, before the encoder's clamp */
-                HIP_TRY(ctx, gdg_launch_block_stats(d_sums, piece, 2u, n, (unsigned)B, enc + sec.at[REPORT_STATS], ctx->stream));
-                HIP_TRY(ctx, section_down(REPORT_STATS));
-            }
-            if (spectrum) {                                                  /* the same sums; a short last block is zero-padded by the kernel */
-                HIP_TRY(ctx, gdg_launch_block_spectrum(d_sums, piece, 2u, n, spec_win, spec_tw, spec_tw2, bands, reinterpret_cast<double *>(enc + sec.at[REPORT_BANDS]), ctx->stream));
-                HIP_TRY(ctx, section_down(REPORT_BANDS));
-            }
-            if (true_peak) {                                                 /* the same sums; a short last block is just shorter */
-                HIP_TRY(ctx, gdg_launch_block_true_peak(d_sums, piece, 2u, n, true_peak_table(), enc + sec.at[REPORT_TRUE_PEAK], ctx->stream));
-                HIP_TRY(ctx, section_down(REPORT_TRUE_PEAK));
-            }
+            /* the records of the sums, after the aux and before the encoder's clamp: a short last block is zero-padded by the spectrum's kernel
+             * and just shorter for the true peak's; then every live kind's [2][nb] elements of this piece on their way down */
+            const RowGroup sums = { d_sums, piece, 2u, 0 };
+            if ((rc = port_records(ctx, { REPORT_STATS, REPORT_BANDS, REPORT_TRUE_PEAK }, &sums, 1, n, nb, live, sec, enc, spec)) != GDG_OK) return rc;
+            for (int j = 0; j < REPORT_KINDS; j++)
+                if (live.on(j)) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + sec.at[j], enc + sec.at[j], 2 * nb * live.elem[j], hipMemcpyDeviceToHost, ctx->stream));
             /* the download of piece k - 2 into this pinned half has been scattered: scatter(k - 2) ran before enqueue(k) */
             if (left_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h], enc, n * width, hipMemcpyDeviceToHost, ctx->stream));
             if (right_bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fin_down[h] + piece * width, enc + piece * width, n * width, hipMemcpyDeviceToHost, ctx->stream));

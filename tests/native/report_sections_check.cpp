@@ -24,7 +24,7 @@ static void differ(const char *what, const char *form, size_t got, size_t want, 
 /* ---- the formulas as they stood, as plain arithmetic -------------------------------------------------------------------------------- */
 struct Old { size_t at[4], bytes[4], down; };
 
-/* batch_block_loop: `down_bytes` = what the step's rows take, `rec_rows` = N + 3 or a shard's N + 1, `w` = the step's blocks */
+/* the block loop (BlockLoop::plan in api_batch.cpp): `down_bytes` = what the step's rows take, `rec_rows` = N + 3 or a shard's N + 1, `w` = the step's blocks */
 static Old old_loop(bool report, bool bands, bool align, bool true_peak, size_t down_bytes, size_t rec_rows, size_t w, size_t bands_n) {
     const size_t n_bands = bands ? bands_n : 0;
     const size_t rec_at = (down_bytes + 15) & ~(size_t)15;
