@@ -3,6 +3,7 @@
 Test and bench plumbing only; the mirrored interface itself is the C++ one (and its Go twin in go/).
 A Go `error` comes back as a Python exception (HostError) carrying the reference's message text.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -23,6 +24,24 @@ def build():
 
 
 _lib = None
+
+# The nine kinds of records a batch call keeps, in the order the batch calls fetch them.  attr: the Engine attribute that holds the last
+# call's; getter: the gdgh_ function; dtype: the name of a package constant, or "float64"; counts: what the getter reports behind (records,
+# capacity); shape: the array's shape over those counts; axis: the one along which a streamed job's slices are joined
+RecordKind = collections.namedtuple("RecordKind", "attr getter dtype counts shape axis")
+_PORTS_BLOCKS = ((C.c_int, C.c_size_t), lambda rows, blocks: (rows, blocks), 1)
+_BLOCKS_PER = ((C.c_size_t, C.c_size_t), lambda blocks, per: (blocks, per), 0)
+RECORD_KINDS = {
+    "report": RecordKind("last_report", "gdgh_engine_last_batch_report", "BLOCK_STATS_DTYPE", *_PORTS_BLOCKS),
+    "spectrum": RecordKind("last_spectrum", "gdgh_engine_last_batch_spectrum", "float64", (C.c_int, C.c_size_t, C.c_int), lambda ports, blocks, bands: (ports, blocks, bands), 1),
+    "align": RecordKind("last_align", "gdgh_engine_last_batch_align", "BLOCK_ALIGN_DTYPE", *_PORTS_BLOCKS),
+    "true_peak": RecordKind("last_true_peak", "gdgh_engine_last_batch_true_peak", "BLOCK_TRUE_PEAK_DTYPE", *_PORTS_BLOCKS),
+    "fit": RecordKind("last_fit", "gdgh_engine_last_batch_fit", "FIT_DTYPE", *_PORTS_BLOCKS),
+    "gram": RecordKind("last_gram", "gdgh_engine_last_batch_gram", "float64", (C.c_int, C.c_size_t), lambda ports, blocks: (blocks, ports * (ports + 1) // 2), 0),
+    "tapfit": RecordKind("last_tapfit", "gdgh_engine_last_batch_tapfit", "float64", *_BLOCKS_PER),
+    "transfer": RecordKind("last_transfer", "gdgh_engine_last_batch_transfer", "float64", *_BLOCKS_PER),
+    "delivered": RecordKind("last_delivered", "gdgh_engine_last_batch_delivered", "BLOCK_DELIVERED_DTYPE", *_PORTS_BLOCKS),
+}
 
 
 def lib():
@@ -57,30 +76,21 @@ def lib():
             "gdgh_engine_batch_blends": (i32, [vp]),
             "gdgh_engine_set_batch_fits": (cs, [vp, i32, vp, vp, vp]),
             "gdgh_engine_batch_fits": (i32, [vp]),
-            "gdgh_engine_last_batch_fit": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_gram": (cs, [vp, vp, i32]),
             "gdgh_engine_batch_gram_ports": (i32, [vp]),
-            "gdgh_engine_last_batch_gram": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_tapfits": (cs, [vp, i32, vp, vp, vp, vp]),
             "gdgh_engine_batch_tapfits": (i32, [vp]),
             "gdgh_engine_set_batch_transfers": (cs, [vp, i32, vp, vp, i32]),
             "gdgh_engine_batch_transfers": (i32, [vp]),
-            "gdgh_engine_last_batch_transfer": (cs, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_delivered": (cs, [vp, i32]),
-            "gdgh_engine_last_batch_delivered": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
-            "gdgh_engine_last_batch_tapfit": (cs, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_set_batch_blends_filtered": (cs, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
             "gdgh_engine_batch_stream_sharded_resume": (cs, [vp, vp, i32, vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_sources": (cs, [vp, vp, i32]),
-            "gdgh_engine_last_batch_report": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_spectrum": (cs, [vp, vp, i32]),
             "gdgh_engine_set_batch_align": (cs, [vp, vp, i32, i32]),
             "gdgh_engine_set_batch_true_peak": (None, [vp, i32]),
-            "gdgh_engine_last_batch_true_peak": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
-            "gdgh_engine_last_batch_align": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
-            "gdgh_engine_last_batch_spectrum": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t), C.POINTER(i32)]),
             "gdgh_engine_context": (vp, [vp, i32]), "gdgh_engine_shard_range": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32)]),
             "gdgh_engine_create_sharded": (vp, [i32, i32, vp, i32]), "gdgh_engine_shards": (i32, [vp]), "gdgh_engine_shard_of": (i32, [vp, i32]),
             "gdgh_engine_save_state": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -108,6 +118,8 @@ def lib():
             "gdgh_unit_process": (None, [vp, vp, vp, i32, C.c_uint32]),
             "gdgh_filter_compile": (i32, [vp, i32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, vp, i32]),
         }
+        for row in RECORD_KINDS.values():
+            sig[row.getter] = (cs, [vp, vp, C.c_size_t] + [C.POINTER(t) for t in row.counts])
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
             fn.restype = res
@@ -228,14 +240,18 @@ class Engine:
         ctx.close = lambda: None                      # the engine owns the context
         return ctx
 
-    def _fetch_report(self):
-        """Engine::LastBatchReport -> [N + 3, blocks] records (the package's BLOCK_STATS_DTYPE)"""
-        import __graft_entry__ as entry
-        pkg = entry.load_package()
-        ports, blocks = C.c_int(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_report(self._h, None, 0, C.byref(ports), C.byref(blocks)))
-        out = np.zeros((ports.value, blocks.value), dtype=pkg.BLOCK_STATS_DTYPE)
-        _err(lib().gdgh_engine_last_batch_report(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
+    def _fetch(self, kind):
+        """Engine::LastBatch<kind> -> the last batch call's records of that kind, in the shape and dtype RECORD_KINDS gives it"""
+        row = RECORD_KINDS[kind]
+        fn = getattr(lib(), row.getter)
+        n = [t(0) for t in row.counts]
+        _err(fn(self._h, None, 0, *[C.byref(v) for v in n]))
+        dtype = np.float64
+        if row.dtype != "float64":
+            import __graft_entry__ as entry
+            dtype = getattr(entry.load_package(), row.dtype)
+        out = np.zeros(row.shape(*[v.value for v in n]), dtype=dtype)
+        _err(fn(self._h, out.ctypes.data if out.size else None, out.size, *[C.byref(v) for v in n]))
         return out
 
     def _set_spectrum(self, edges):
@@ -247,28 +263,11 @@ class Engine:
         e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
         _err(lib().gdgh_engine_set_batch_spectrum(self._h, e.ctypes.data, e.size))
 
-    def _fetch_spectrum(self):
-        """Engine::LastBatchSpectrum -> [N + 3, blocks, bands] float64"""
-        ports, blocks, bands = C.c_int(0), C.c_size_t(0), C.c_int(0)
-        _err(lib().gdgh_engine_last_batch_spectrum(self._h, None, 0, C.byref(ports), C.byref(blocks), C.byref(bands)))
-        out = np.zeros((ports.value, blocks.value, bands.value), dtype=np.float64)
-        _err(lib().gdgh_engine_last_batch_spectrum(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks), C.byref(bands)))
-        return out
-
     def _set_true_peak(self, true_peak):
         """Engine::SetBatchTruePeak, from the `true_peak` argument of the batch calls"""
         self.last_true_peak = None
         lib().gdgh_engine_set_batch_true_peak(self._h, int(bool(true_peak)))
         return bool(true_peak)
-
-    def _fetch_true_peak(self):
-        """Engine::LastBatchTruePeak -> [N + 3, blocks] records (the package's BLOCK_TRUE_PEAK_DTYPE)"""
-        import __graft_entry__ as entry
-        ports, blocks = C.c_int(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_true_peak(self._h, None, 0, C.byref(ports), C.byref(blocks)))
-        out = np.zeros((ports.value, blocks.value), dtype=entry.load_package().BLOCK_TRUE_PEAK_DTYPE)
-        _err(lib().gdgh_engine_last_batch_true_peak(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
-        return out
 
     def _set_align(self, align):
         """Engine::SetBatchAlign, from the `align` argument of the batch calls: (ref over the job's N + 3 ports, max_lag) (None: off)"""
@@ -279,15 +278,6 @@ class Engine:
         ref = np.ascontiguousarray(align[0], dtype=np.int32).reshape(-1)
         _err(lib().gdgh_engine_set_batch_align(self._h, ref.ctypes.data, ref.size, int(align[1])))
         return True
-
-    def _fetch_align(self):
-        """Engine::LastBatchAlign -> [N + 3, blocks] records (the package's BLOCK_ALIGN_DTYPE)"""
-        import __graft_entry__ as entry
-        ports, blocks = C.c_int(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_align(self._h, None, 0, C.byref(ports), C.byref(blocks)))
-        out = np.zeros((ports.value, blocks.value), dtype=entry.load_package().BLOCK_ALIGN_DTYPE)
-        _err(lib().gdgh_engine_last_batch_align(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
-        return out
 
     def batch_set_sources(self, source):
         """Engine::SetBatchSources: the source map of the next jobs in JOB channel numbers (None clears it); a reader whose root lives on
@@ -377,16 +367,6 @@ class Engine:
         _err(lib().gdgh_engine_set_batch_fits(self._h, len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data))
         return int(lib().gdgh_engine_batch_fits(self._h))
 
-    def _fetch_fit(self):
-        """Engine::LastBatchFit -> [fits, blocks] records (FIT_DTYPE)"""
-        import __graft_entry__ as entry
-        pkg = entry.load_package()
-        fits, blocks = C.c_int(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_fit(self._h, None, 0, C.byref(fits), C.byref(blocks)))
-        out = np.zeros((fits.value, blocks.value), dtype=pkg.FIT_DTYPE)
-        _err(lib().gdgh_engine_last_batch_fit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(fits), C.byref(blocks)))
-        return out
-
     def _set_gram(self, gram):
         """Engine::SetBatchGram, from the `gram` argument of the batch calls: a list of 2 to 512 different ports; None or an empty list: off.
         Returns the number of ports in force.  Refused on an engine of more than one shard."""
@@ -394,14 +374,6 @@ class Engine:
         ports = np.array([] if gram is None else [int(p) for p in gram], dtype=np.int32)
         _err(lib().gdgh_engine_set_batch_gram(self._h, ports.ctypes.data if ports.size else None, ports.size))
         return int(lib().gdgh_engine_batch_gram_ports(self._h))
-
-    def _fetch_gram(self):
-        """Engine::LastBatchGram -> [blocks, P (P + 1) / 2] float64"""
-        ports, blocks = C.c_int(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_gram(self._h, None, 0, C.byref(ports), C.byref(blocks)))
-        out = np.zeros((blocks.value, ports.value * (ports.value + 1) // 2), dtype=np.float64)
-        _err(lib().gdgh_engine_last_batch_gram(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
-        return out
 
     def _set_tapfits(self, tapfits):
         """Engine::SetBatchTapFits, from the `tapfits` argument of the batch calls: a list of (target port, [term ports], taps); None or an
@@ -416,14 +388,6 @@ class Engine:
         first, port, target, taps = pkg._tapfit_csr(fits)
         _err(lib().gdgh_engine_set_batch_tapfits(self._h, len(fits), first.ctypes.data, port.ctypes.data, target.ctypes.data, taps.ctypes.data))
         return int(lib().gdgh_engine_batch_tapfits(self._h))
-
-    def _fetch_tapfit(self):
-        """Engine::LastBatchTapFit -> [blocks, D] float64"""
-        blocks, per = C.c_size_t(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_tapfit(self._h, None, 0, C.byref(blocks), C.byref(per)))
-        out = np.zeros((blocks.value, per.value), dtype=np.float64)
-        _err(lib().gdgh_engine_last_batch_tapfit(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
-        return out
 
     def _set_transfers(self, transfers):
         """Engine::SetBatchTransfers, from the `transfers` argument of the batch calls: ([(port, target), ...], group), or a list of pairs
@@ -443,30 +407,12 @@ class Engine:
         _err(lib().gdgh_engine_set_batch_transfers(self._h, len(pairs), port.ctypes.data, target.ctypes.data, group))
         return int(lib().gdgh_engine_batch_transfers(self._h))
 
-    def _fetch_transfer(self):
-        """Engine::LastBatchTransfer -> [blocks, pairs x G x 4] float64"""
-        blocks, per = C.c_size_t(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_transfer(self._h, None, 0, C.byref(blocks), C.byref(per)))
-        out = np.zeros((blocks.value, per.value), dtype=np.float64)
-        _err(lib().gdgh_engine_last_batch_transfer(self._h, out.ctypes.data if out.size else None, out.size, C.byref(blocks), C.byref(per)))
-        return out
-
     def _set_delivered(self, delivered):
         """Engine::SetBatchDelivered, from the `delivered` argument of the batch calls: keep the records of the rows the encoders read (the
         delivered rows, in front of the gains).  Returns whether they are on.  Refused on an engine of more than one shard."""
         self.last_delivered = None
         _err(lib().gdgh_engine_set_batch_delivered(self._h, int(bool(delivered))))
         return bool(delivered)
-
-    def _fetch_delivered(self):
-        """Engine::LastBatchDelivered -> [ports, blocks] BLOCK_DELIVERED_DTYPE"""
-        import __graft_entry__ as entry
-        pkg = entry.load_package()
-        ports, blocks = C.c_int(0), C.c_size_t(0)
-        _err(lib().gdgh_engine_last_batch_delivered(self._h, None, 0, C.byref(ports), C.byref(blocks)))
-        out = np.zeros((ports.value, blocks.value), dtype=pkg.BLOCK_DELIVERED_DTYPE)
-        _err(lib().gdgh_engine_last_batch_delivered(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(blocks)))
-        return out
 
     def match_ir(self, port, target, taps, inputs, target_rate, out_format, group=32, ridge=0.0, center=0, window=16, sample_rate=None, **kw):
         """The match filter of one pass over a job: the `taps`-tap impulse response that, applied to port `port`, comes closest to port
@@ -772,36 +718,10 @@ class Engine:
         engines only): their true_peak is the delivered file's, seamless across blocks."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
-        lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
-        self._set_dither(dither)
-        self._set_trim(trim)
-        R = self._set_delivery(deliver)
-        nb = self._set_blends(blends, blend_gain)            # before the alignment list, which may name blend ports
-        fitted = self._set_fits(fits)
-        grammed = self._set_gram(gram)
-        tapped = self._set_tapfits(tapfits)
-        transferred = self._set_transfers(transfers)
-        measured = self._set_delivered(delivered)
-        self._set_spectrum(spectrum)
-        aligned = self._set_align(align)
-        peaked = self._set_true_peak(true_peak)
-        self.last_report = None
+        R, nb, kinds = self._settings(report=report, dither=dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim, blends=blends, blend_gain=blend_gain,
+                                      fits=fits, gram=gram, tapfits=tapfits, transfers=transfers, deliver=deliver, delivered=delivered)
         n = len(inputs)
-        arr = (pkg.BatchInput * n)()
-        keep = []
-        for i, it in enumerate(inputs):
-            if it is None:
-                continue
-            data, fmt, rate = it[0], it[1], it[2]
-            channels, channel = (it[3], it[4]) if len(it) > 3 else (1, 0)
-            f = pkg.WAVE_FORMATS[fmt] if isinstance(fmt, str) else fmt
-            data = np.ascontiguousarray(data, dtype=np.uint8)
-            keep.append(data)
-            w = max(pkg.lib().gdg_wave_bytes_per_sample(f), 1)
-            arr[i] = pkg.BatchInput(data.ctypes.data if data.size else None, data.size // (w * max(channels, 1)), f, rate, channels, channel)
-        fo = pkg.WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
-        opt = pkg.BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
-        wo = pkg.lib().gdg_wave_bytes_per_sample(fo)
+        arr, _datas, _widths, opt, wo = self._job_inputs(pkg, inputs, target_rate, out_format, metronome_to_master, run_meters, tuner_enqueue)
         # the job's length: the longest shard's (asked from the shards' own contexts)
         length = 0
         for g in range(self.shards()):
@@ -814,24 +734,8 @@ class Engine:
         samples = C.c_size_t(0)
         _err(lib().gdgh_engine_batch_run(self._h, arr, n, C.byref(opt), window, ptrs, C.byref(samples)))
         assert samples.value == length
-        if report:
-            self.last_report = self._fetch_report()
-        if spectrum is not None and len(spectrum):
-            self.last_spectrum = self._fetch_spectrum()
-        if aligned:
-            self.last_align = self._fetch_align()
-        if peaked:
-            self.last_true_peak = self._fetch_true_peak()
-        if fitted:
-            self.last_fit = self._fetch_fit()
-        if grammed:
-            self.last_gram = self._fetch_gram()
-        if tapped:
-            self.last_tapfit = self._fetch_tapfit()
-        if transferred:
-            self.last_transfer = self._fetch_transfer()
-        if measured:
-            self.last_delivered = self._fetch_delivered()
+        for kind in kinds:
+            setattr(self, RECORD_KINDS[kind].attr, self._fetch(kind))
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
@@ -845,7 +749,7 @@ class Engine:
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_open, L.gdgh_engine_batch_stream_need, L.gdgh_engine_batch_stream_step,
                                    L.gdgh_engine_batch_stream_close), inputs, target_rate, out_format, blocks_per_slice, window,
-                                  metronome_to_master, run_meters, tuner_enqueue, report, dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
+                                  metronome_to_master, run_meters, tuner_enqueue, report=report, dither=dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim,
                                   blends=blends, blend_gain=blend_gain, fits=fits, gram=gram, tapfits=tapfits, transfers=transfers, deliver=deliver, delivered=delivered)
 
     def batch_stream_sharded_checkpoint(self):
@@ -867,28 +771,36 @@ class Engine:
         L = lib()
         return self._batch_stream((L.gdgh_engine_batch_stream_sharded_open, L.gdgh_engine_batch_stream_sharded_need,
                                    L.gdgh_engine_batch_stream_sharded_step, L.gdgh_engine_batch_stream_sharded_close), inputs, target_rate,
-                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, report, dither, resume,
+                                  out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, resume=resume, report=report, dither=dither,
                                   spectrum=spectrum, align=align, true_peak=true_peak, trim=trim)
 
-    def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue,
-                      report=False, dither=None, resume=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None, delivered=False):
-        f_open, f_need, f_step, f_close = calls
-        import __graft_entry__ as entry
-        pkg = entry.load_package()
+    def _settings(self, report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None,
+                  transfers=None, deliver=None, delivered=False):
+        """The batch calls' settings onto the engine (Engine::SetBatch*), in the one order both calls use; every last_* a call may fill is
+        None afterwards.  Returns ((factor, up, down) of the delivery in force, the blends in force, the kinds of records that are on, in
+        RECORD_KINDS' order)."""
         lib().gdgh_engine_set_batch_report(self._h, int(bool(report)))
         self._set_dither(dither)
         self._set_trim(trim)
-        R = self._set_delivery(deliver)                      # the sharded form passes none: off
-        nb = self._set_blends(blends, blend_gain)            # the sharded form passes none: off
-        fitted = self._set_fits(fits)                        # ... and no fits
-        grammed = self._set_gram(gram)                       # ... and no Gram list
-        tapped = self._set_tapfits(tapfits)                  # ... and no tap fits
-        transferred = self._set_transfers(transfers)         # ... and no transfer list
-        measured = self._set_delivered(delivered)            # ... and no records of the delivered rows
+        R = self._set_delivery(deliver)
+        nb = self._set_blends(blends, blend_gain)            # before the alignment list, which may name blend ports
+        on = {"report": bool(report), "spectrum": spectrum is not None and len(spectrum) > 0}
+        on["fit"] = self._set_fits(fits)
+        on["gram"] = self._set_gram(gram)
+        on["tapfit"] = self._set_tapfits(tapfits)
+        on["transfer"] = self._set_transfers(transfers)
+        on["delivered"] = self._set_delivered(delivered)
         self._set_spectrum(spectrum)
-        aligned = self._set_align(align)
-        peaked = self._set_true_peak(true_peak)
+        on["align"] = self._set_align(align)
+        on["true_peak"] = self._set_true_peak(true_peak)
         self.last_report = None
+        return R, nb, [kind for kind in RECORD_KINDS if on[kind]]
+
+    @staticmethod
+    def _job_inputs(pkg, inputs, target_rate, out_format, metronome_to_master, run_meters, tuner_enqueue):
+        """The `inputs` tuples (data, format, rate[, channels, channel]; None: no file) as the BatchInput array of the C calls -> (the
+        array, every input's bytes (they must outlive the call), the bytes of one source frame per input, the BatchOptions, the bytes of
+        one output sample)"""
         n = len(inputs)
         arr = (pkg.BatchInput * n)()
         datas, widths = [None] * n, [0] * n
@@ -902,7 +814,15 @@ class Engine:
             arr[i] = pkg.BatchInput(datas[i].ctypes.data if datas[i].size else None, datas[i].size // widths[i], f, it[2], channels, channel)
         fo = pkg.WAVE_FORMATS[out_format] if isinstance(out_format, str) else out_format
         opt = pkg.BatchOptions(target_rate, fo, int(bool(metronome_to_master)), int(bool(run_meters)), int(bool(tuner_enqueue)))
-        wo = pkg.lib().gdg_wave_bytes_per_sample(fo)
+        return arr, datas, widths, opt, pkg.lib().gdg_wave_bytes_per_sample(fo)
+
+    def _batch_stream(self, calls, inputs, target_rate, out_format, blocks_per_slice, window, metronome_to_master, run_meters, tuner_enqueue, resume=None, **settings):
+        f_open, f_need, f_step, f_close = calls
+        import __graft_entry__ as entry
+        pkg = entry.load_package()
+        R, nb, kinds = self._settings(**settings)             # the sharded form passes no delivery, no blends and none of the five list kinds: off
+        n = len(inputs)
+        arr, datas, widths, opt, wo = self._job_inputs(pkg, inputs, target_rate, out_format, metronome_to_master, run_meters, tuner_enqueue)
         samples, done = C.c_size_t(0), C.c_size_t(0)
         if resume is None:
             _err(f_open(self._h, arr, n, C.byref(opt), window, C.byref(samples)))
@@ -926,33 +846,9 @@ class Engine:
                 done_samples += blocks * 8192
                 ptrs = (C.c_void_p * (n + 3 + nb))(*[o.ctypes.data for o in outs])
                 _err(f_step(self._h, blocks, ins, ptrs))
-                if report:
-                    rec = self._fetch_report()
-                    self.last_report = rec if self.last_report is None else np.concatenate([self.last_report, rec], axis=1)
-                if spectrum is not None and len(spectrum):
-                    sp = self._fetch_spectrum()
-                    self.last_spectrum = sp if self.last_spectrum is None else np.concatenate([self.last_spectrum, sp], axis=1)
-                if aligned:
-                    al = self._fetch_align()
-                    self.last_align = al if self.last_align is None else np.concatenate([self.last_align, al], axis=1)
-                if peaked:
-                    tp = self._fetch_true_peak()
-                    self.last_true_peak = tp if self.last_true_peak is None else np.concatenate([self.last_true_peak, tp], axis=1)
-                if fitted:
-                    ft = self._fetch_fit()
-                    self.last_fit = ft if self.last_fit is None else np.concatenate([self.last_fit, ft], axis=1)
-                if grammed:
-                    gm = self._fetch_gram()
-                    self.last_gram = gm if self.last_gram is None else np.concatenate([self.last_gram, gm], axis=0)
-                if tapped:
-                    tf = self._fetch_tapfit()
-                    self.last_tapfit = tf if self.last_tapfit is None else np.concatenate([self.last_tapfit, tf], axis=0)
-                if transferred:
-                    tr = self._fetch_transfer()
-                    self.last_transfer = tr if self.last_transfer is None else np.concatenate([self.last_transfer, tr], axis=0)
-                if measured:
-                    dl = self._fetch_delivered()
-                    self.last_delivered = dl if self.last_delivered is None else np.concatenate([self.last_delivered, dl], axis=1)
+                for kind in kinds:                           # every last_* grows by the slice's records, along the kind's block axis
+                    row, rec = RECORD_KINDS[kind], self._fetch(kind)
+                    setattr(self, row.attr, rec if getattr(self, row.attr) is None else np.concatenate([getattr(self, row.attr), rec], axis=row.axis))
                 yield outs
                 left -= blocks
         finally:

@@ -19,7 +19,6 @@
 #include <map>
 #include <sstream>
 #include <thread>
-#include <type_traits>
 
 namespace gdg {
 
@@ -1086,14 +1085,6 @@ int Engine::applyFits(gdg_ctx *ctx) {
     return gdg_batch_fit_enable(ctx, BatchFits(), fitFirst_.data(), fitPort_.data(), fitTarget_.data());
 }
 
-Error Engine::LastBatchFit(std::vector<gdg_block_fit> &records, int *fits, size_t *blocks) const {
-    if (!fitValid_) return "LastBatchFit: the last batch call kept no fit records (SetBatchFits comes before the call)";
-    records = lastFit_;
-    if (fits) *fits = fitBlocks_ ? (int)(lastFit_.size() / fitBlocks_) : BatchFits();
-    if (blocks) *blocks = fitBlocks_;
-    return "";
-}
-
 /* Engine::SetBatchGram: validated whole before the list replaces the one in force (the library checks again, and the ports against the job's) */
 Error Engine::SetBatchGram(const std::vector<int> &ports) {
     if (ports.empty()) { gramPort_.clear(); return ""; }
@@ -1112,14 +1103,6 @@ Error Engine::SetBatchGram(const std::vector<int> &ports) {
 int Engine::applyGram(gdg_ctx *ctx) {
     if (gramPort_.empty()) return gdg_batch_gram_enable(ctx, nullptr, 0);
     return gdg_batch_gram_enable(ctx, gramPort_.data(), BatchGramPorts());
-}
-
-Error Engine::LastBatchGram(std::vector<double> &records, int *ports, size_t *blocks) const {
-    if (!gramValid_) return "LastBatchGram: the last batch call kept no Gram records (SetBatchGram comes before the call)";
-    records = lastGram_;
-    if (ports) *ports = gramPorts_;
-    if (blocks) *blocks = gramBlocks_;
-    return "";
 }
 
 /* Engine::SetBatchTapFits: validated whole before the list replaces the one in force (the library checks again, and the ports against the job's) */
@@ -1186,28 +1169,61 @@ Error Engine::SetBatchDelivered(bool on) {
     return "";
 }
 
-Error Engine::LastBatchDelivered(std::vector<gdg_block_delivered> &records, int *ports, size_t *blocks) const {
-    if (!deliveredValid_) return "LastBatchDelivered: the last batch call kept no records of the delivered rows (SetBatchDelivered comes before the call)";
-    records = lastDelivered_;
-    if (ports) *ports = deliveredPorts_;
-    if (blocks) *blocks = deliveredBlocks_;
-    return "";
+/* ---- the records of the last batch call, nine kinds through one table (batch_records.h): the typed faces of records::last ---- */
+Error Engine::LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const { return records::lastAs(records::REPORT, stores_[records::REPORT], records, ports, blocks); }
+Error Engine::LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *blocks, int *nBands) const { return records::lastAs(records::SPECTRUM, stores_[records::SPECTRUM], bands, ports, blocks, nBands); }
+Error Engine::LastBatchAlign(std::vector<gdg_block_align> &records, int *ports, size_t *blocks) const { return records::lastAs(records::ALIGN, stores_[records::ALIGN], records, ports, blocks); }
+Error Engine::LastBatchTruePeak(std::vector<gdg_block_true_peak> &records, int *ports, size_t *blocks) const { return records::lastAs(records::TRUE_PEAK, stores_[records::TRUE_PEAK], records, ports, blocks); }
+Error Engine::LastBatchFit(std::vector<gdg_block_fit> &records, int *fits, size_t *blocks) const { return records::lastAs(records::FIT, stores_[records::FIT], records, fits, blocks); }
+Error Engine::LastBatchGram(std::vector<double> &records, int *ports, size_t *blocks) const { return records::lastAs(records::GRAM, stores_[records::GRAM], records, ports, blocks); }
+Error Engine::LastBatchTapFit(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const { return records::lastAs(records::TAPFIT, stores_[records::TAPFIT], records, nullptr, blocks, doublesPerBlock); }
+Error Engine::LastBatchTransfer(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const { return records::lastAs(records::TRANSFER, stores_[records::TRANSFER], records, nullptr, blocks, doublesPerBlock); }
+Error Engine::LastBatchDelivered(std::vector<gdg_block_delivered> &records, int *ports, size_t *blocks) const { return records::lastAs(records::DELIVERED, stores_[records::DELIVERED], records, ports, blocks); }
+
+/* whether the settings in force keep a kind, and the counts its records then have: ports or fits, and the elements of one (port, block)
+ * or of one block */
+records::Expect Engine::expected(records::Kind kind) const {
+    const size_t P = (size_t)BatchGramPorts();
+    switch (kind) {
+    case records::REPORT: return { report_, ports(), 1 };
+    case records::TRUE_PEAK: return { truePeak_, ports(), 1 };
+    case records::ALIGN: return { !alignRef_.empty(), ports(), 1 };
+    case records::SPECTRUM: return { !spectrumEdges_.empty(), ports(), spectrumEdges_.empty() ? 0 : spectrumEdges_.size() - 1 };
+    case records::FIT: return { BatchFits() > 0, BatchFits(), 1 };
+    case records::GRAM: return { P > 0, (int)P, P * (P + 1) / 2 };
+    case records::TRANSFER: return { BatchTransfers() > 0, 0, gdg_transfer_doubles(BatchTransfers(), transferGroup_) };
+    case records::TAPFIT: return { BatchTapFits() > 0, 0, BatchTapFits() > 0 ? gdg_tapfit_doubles(BatchTapFits(), tapFitFirst_.data(), tapFitTaps_.data()) : 0 };
+    case records::DELIVERED: return { delivered_, ports(), 1 };
+    case records::KINDS: break;
+    }
+    return { false, 0, 0 };
 }
 
-Error Engine::LastBatchTransfer(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const {
-    if (!transferValid_) return "LastBatchTransfer: the last batch call kept no transfer records (SetBatchTransfers comes before the call)";
-    records = lastTransfer_;
-    if (blocks) *blocks = transferBlocks_;
-    if (doublesPerBlock) *doublesPerBlock = transferDoubles_;
-    return "";
+/* the settings every job has, a resumed one too: the window, the four port kinds, sources, dither, trim, delivery and blends */
+int Engine::applyPortSettings(int shard, gdg_ctx *ctx, int window) {
+    const int g = shard < 0 ? 0 : shard;
+    int rc = gdg_ctx_set_window(ctx, window);
+    if (rc == GDG_OK) rc = gdg_batch_report_enable(ctx, report_);
+    if (rc == GDG_OK) rc = gdg_batch_true_peak_enable(ctx, truePeak_);
+    if (rc == GDG_OK) rc = applySpectrum(ctx);
+    if (rc == GDG_OK) rc = applyAlign(shard, ctx);
+    if (rc == GDG_OK) rc = applySources(g, ctx);
+    if (rc == GDG_OK) rc = applyDither(g, ctx);
+    if (rc == GDG_OK) rc = applyTrim(g, ctx);
+    if (rc == GDG_OK) rc = gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_);
+    if (rc == GDG_OK) rc = applyBlends(ctx);
+    return rc;
 }
 
-Error Engine::LastBatchTapFit(std::vector<double> &records, size_t *blocks, size_t *doublesPerBlock) const {
-    if (!tapFitValid_) return "LastBatchTapFit: the last batch call kept no tap-fit records (SetBatchTapFits comes before the call)";
-    records = lastTapFit_;
-    if (blocks) *blocks = tapFitBlocks_;
-    if (doublesPerBlock) *doublesPerBlock = tapFitDoubles_;
-    return "";
+/* every setting a job is set up with onto a context (gdg_host.hpp states the order): a gdg_* status, the context's error the first failure's */
+int Engine::applySettings(int shard, gdg_ctx *ctx, int window) {
+    int rc = applyPortSettings(shard, ctx, window);
+    if (rc == GDG_OK) rc = applyFits(ctx);
+    if (rc == GDG_OK) rc = applyGram(ctx);
+    if (rc == GDG_OK) rc = applyTapFits(ctx);
+    if (rc == GDG_OK) rc = applyTransfers(ctx);
+    if (rc == GDG_OK) rc = gdg_batch_out_records_enable(ctx, delivered_);
+    return rc;
 }
 
 /* What every batch job over the shards opens with.  Per shard: the device follows the chains (units, parameters, filters, layout) as before a
@@ -1235,7 +1251,7 @@ Error Engine::prepareShards(const gdg_batch_input *inputs, const gdg_batch_optio
         for (auto &c : chains) if (c->channel() >= first && c->channel() < first + count) mine.push_back(c.get());
         Error e = sync(g, mine, options.target_rate);
         if (!e.empty()) { setError(e); return e; }
-        if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(g, ctx) != GDG_OK || applySources(g, ctx) != GDG_OK || applyDither(g, ctx) != GDG_OK || applyTrim(g, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_out_records_enable(ctx, delivered_) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
+        if (applySettings(g, ctx, window) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         size_t len = 0;
         if (gdg_batch_length(ctx, inputs + first, count, options.target_rate, &len) != GDG_OK) { setError(gdg_last_error(ctx)); return LastError(); }
         job = std::max(job, len);
@@ -1255,7 +1271,12 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
     if (!prepared.empty()) return prepared;
     if (samples) *samples = job;
     reportBegin(job / 8192);
-    if (job == 0) { transferValid_ = BatchTransfers() > 0; transferBlocks_ = 0; transferDoubles_ = gdg_transfer_doubles(BatchTransfers(), transferGroup_); lastTransfer_.clear(); tapFitValid_ = BatchTapFits() > 0; tapFitBlocks_ = 0; tapFitDoubles_ = tapFitValid_ ? gdg_tapfit_doubles(BatchTapFits(), tapFitFirst_.data(), tapFitTaps_.data()) : 0; lastTapFit_.clear(); gramValid_ = BatchGramPorts() > 0; gramBlocks_ = 0; gramPorts_ = BatchGramPorts(); lastGram_.clear(); fitValid_ = BatchFits() > 0; fitBlocks_ = 0; lastFit_.clear(); reportValid_ = report_; spectrumValid_ = !spectrumEdges_.empty(); alignValid_ = !alignRef_.empty(); truePeakValid_ = truePeak_; return ""; }
+    if (job == 0) {                                      /* no block: every kind in force is kept, as an empty list */
+        records::Expect want[records::KINDS];
+        for (int k = 0; k < records::KINDS; k++) want[k] = expected((records::Kind)k);
+        records::emptyJob(stores_, want);
+        return "";
+    }
     /* blends or fits in force (one shard: SetBatchBlends, SetBatchFits): the library's plain one-call run -- its shard calls refuse both --
      * with `outs` of N + 3 + B entries; the alignment list goes on in its plain form, and the context's records of every kind are the engine's */
     if (plainRun()) {
@@ -1313,48 +1334,11 @@ Error Engine::BatchRun(const gdg_batch_input *inputs, int nInputs, const gdg_bat
  * [N + 3][blocks] in gdg_batch_run's port order and from three sources -- the shards' chain rows, shard 0's metronome row, the finish's two
  * master rows (which carry no alignment records: over shards those rows stay zero) ---- */
 void Engine::reportBegin(size_t blocks) {
-    reportValid_ = spectrumValid_ = truePeakValid_ = alignValid_ = fitValid_ = gramValid_ = tapFitValid_ = transferValid_ = deliveredValid_ = false;
-    reportBlocks_ = blocks;
-    spectrumBands_ = spectrumEdges_.empty() ? 0 : (int)spectrumEdges_.size() - 1;
-    const size_t n = (size_t)ports() * blocks;
-    if (report_) lastReport_.assign(n, gdg_block_stats{});
-    if (spectrumBands_) lastSpectrum_.assign(n * (size_t)spectrumBands_, 0.0);
-    if (truePeak_) lastTruePeak_.assign(n, gdg_block_true_peak{});
-    if (!alignRef_.empty()) lastAlign_.assign(n, gdg_block_align{});
-}
-
-/* a kind's getter by its element type */
-static int getKind(gdg_ctx *c, gdg_block_stats *r, size_t cap, int *ports, size_t *blocks, int *) { return gdg_batch_report(c, r, cap, ports, blocks); }
-static int getKind(gdg_ctx *c, double *r, size_t cap, int *ports, size_t *blocks, int *bands) { return gdg_batch_spectrum(c, r, cap, ports, blocks, bands); }
-static int getKind(gdg_ctx *c, gdg_block_align *r, size_t cap, int *ports, size_t *blocks, int *) { return gdg_batch_align(c, r, cap, ports, blocks); }
-static int getKind(gdg_ctx *c, gdg_block_true_peak *r, size_t cap, int *ports, size_t *blocks, int *) { return gdg_batch_true_peak(c, r, cap, ports, blocks); }
-
-/* `ports` x `blocks` elements of one kind of a context's last call (an element: a record, or the `per` bands of a spectrum), checked
- * against what the engine expects; `what` names the records in the refusal */
-template <class T>
-static Error kindOf(gdg_ctx *ctx, int ports, size_t blocks, int per, const char *what, std::vector<T> &rec) {
-    int p = 0, b = per;
-    size_t nb = 0;
-    rec.assign((size_t)ports * blocks * (size_t)per, T{});
-    if (getKind(ctx, rec.data(), rec.size(), &p, &nb, &b) != GDG_OK) return gdg_last_error(ctx);
-    if (std::is_same<T, double>::value) {
-        if (p != ports || nb != blocks || b != per)
-            return format("a spectrum of %d ports x %zu blocks x %d bands where %d x %zu x %d were expected", p, nb, b, ports, blocks, per);
-    } else if (p != ports || nb != blocks) return format("%s of %d ports x %zu blocks where %d x %zu were expected", what, p, nb, ports, blocks);
-    return "";
-}
-
-/* ... and filed into the engine's: the first `n0` rows a context gave to the engine's rows from `to0` on (a shard's chain rows to its
- * channels, the finish's two to the master's), the `n1` rows behind them to the rows from `to1` on (shard 0's last row to the metronome's) */
-template <class T>
-static Error kindInto(gdg_ctx *ctx, int ports, size_t blocks, int per, const char *what, std::vector<T> &last, size_t to0, size_t n0, size_t to1, size_t n1) {
-    std::vector<T> rec;
-    Error e = kindOf(ctx, ports, blocks, per, what, rec);
-    if (!e.empty()) return e;
-    const size_t row = blocks * (size_t)per;
-    if (n0 && row) memcpy(&last[to0 * row], rec.data(), n0 * row * sizeof(T));
-    if (n1 && row) memcpy(&last[to1 * row], &rec[n0 * row], n1 * row * sizeof(T));
-    return "";
+    for (int k = 0; k < records::KINDS; k++) {
+        stores_[k].valid = false;
+        const records::Expect want = expected((records::Kind)k);
+        if (records::table[k].ports && want.on) records::begin((records::Kind)k, stores_[k], want.rows, blocks, want.per);      /* zero records: rows are filed in */
+    }
 }
 
 /* the shard a port of the job lives on: a chain output on its channel's, the metronome on shard 0, the master (made by the finish) on none */
@@ -1393,49 +1377,36 @@ int Engine::applyAlign(int shard, gdg_ctx *ctx) {
     return gdg_batch_align_enable(ctx, ref.data(), count + 1, alignLag_);
 }
 
-Error Engine::alignOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_align> &rec) { return kindOf(ctx, ports, reportBlocks_, 1, "alignment records", rec); }
-
 /* the edges in force onto a context (an empty list: off): a gdg_* status */
 int Engine::applySpectrum(gdg_ctx *ctx) {
     return gdg_batch_spectrum_enable(ctx, spectrumEdges_.empty() ? nullptr : spectrumEdges_.data(), (int)spectrumEdges_.size());
 }
-
-Error Engine::truePeakOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_true_peak> &rec) { return kindOf(ctx, ports, reportBlocks_, 1, "true-peak records", rec); }
-
-Error Engine::LastBatchTruePeak(std::vector<gdg_block_true_peak> &records, int *ports, size_t *blocks) const {
-    if (!truePeakValid_) return "LastBatchTruePeak: the last batch call kept no true-peak records (SetBatchTruePeak comes before the call)";
-    records = lastTruePeak_;
-    if (ports) *ports = this->ports();
-    if (blocks) *blocks = reportBlocks_;
-    return "";
-}
-
-Error Engine::spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val) { return kindOf(ctx, ports, reportBlocks_, (int)spectrumEdges_.size() - 1, nullptr, val); }
 
 /* shard g's records of every kind (its n chain outputs, then the metronome): the chain rows to the shard's channels, shard 0's last row to
  * the metronome's */
 Error Engine::reportOfShard(int g, gdg_ctx *ctx) {
     int first = 0, count = 0;
     shardRange(g, &first, &count);
-    const size_t nb = reportBlocks_, n = (size_t)count, metro = (size_t)nChannels_ + 2, has_metro = g == 0 ? 1 : 0;
-    Error e;
-    if (truePeak_) e = kindInto(ctx, count + 1, nb, 1, "true-peak records", lastTruePeak_, (size_t)first, n, metro, has_metro);
-    if (e.empty() && !alignRef_.empty()) e = kindInto(ctx, count + 1, nb, 1, "alignment records", lastAlign_, (size_t)first, n, metro, has_metro);
-    if (e.empty() && !spectrumEdges_.empty()) e = kindInto(ctx, count + 1, nb, (int)spectrumEdges_.size() - 1, nullptr, lastSpectrum_, (size_t)first, n, metro, has_metro);
-    if (e.empty() && report_) e = kindInto(ctx, count + 1, nb, 1, "a report", lastReport_, (size_t)first, n, metro, has_metro);
-    return e;
+    const size_t n = (size_t)count, metro = (size_t)nChannels_ + 2, has_metro = g == 0 ? 1 : 0;
+    for (int k = 0; k < records::KINDS; k++) {
+        if (!records::table[k].ports || !expected((records::Kind)k).on) continue;
+        Error e = records::fileRows((records::Kind)k, ctx, stores_[k], count + 1, (size_t)first, n, metro, has_metro);
+        if (!e.empty()) return e;
+    }
+    return "";
 }
 
 /* the finish's two rows of every kind (master left, master right) complete the call's; it has no alignment records: the shards' are the
  * call's, the master rows zero */
 Error Engine::reportOfMaster(gdg_ctx *ctx) {
-    const size_t nb = reportBlocks_, master = (size_t)nChannels_;
-    alignValid_ = !alignRef_.empty();
-    Error e;
-    if (truePeak_ && (e = kindInto(ctx, 2, nb, 1, "true-peak records", lastTruePeak_, master, 2, 0, 0)).empty()) truePeakValid_ = true;
-    if (e.empty() && !spectrumEdges_.empty() && (e = kindInto(ctx, 2, nb, (int)spectrumEdges_.size() - 1, nullptr, lastSpectrum_, master, 2, 0, 0)).empty()) spectrumValid_ = true;
-    if (e.empty() && report_ && (e = kindInto(ctx, 2, nb, 1, "a master report", lastReport_, master, 2, 0, 0)).empty()) reportValid_ = true;
-    return e;
+    stores_[records::ALIGN].valid = expected(records::ALIGN).on;
+    for (int k = 0; k < records::KINDS; k++) {
+        if (!records::table[k].ports || k == records::ALIGN || !expected((records::Kind)k).on) continue;
+        Error e = records::fileRows((records::Kind)k, ctx, stores_[k], 2, (size_t)nChannels_, 2, 0, 0, /*master=*/true);
+        if (!e.empty()) return e;
+        stores_[k].valid = true;
+    }
+    return "";
 }
 
 Error Engine::SetBatchSpectrum(const std::vector<double> &edges) {
@@ -1466,31 +1437,6 @@ Error Engine::SetBatchAlign(const std::vector<int> &ref, int maxLag) {
     return "";
 }
 
-Error Engine::LastBatchAlign(std::vector<gdg_block_align> &records, int *ports, size_t *blocks) const {
-    if (!alignValid_) return "LastBatchAlign: the last batch call kept no alignment records (SetBatchAlign comes before the call)";
-    records = lastAlign_;
-    if (ports) *ports = this->ports();
-    if (blocks) *blocks = reportBlocks_;
-    return "";
-}
-
-Error Engine::LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *blocks, int *nBands) const {
-    if (!spectrumValid_) return "LastBatchSpectrum: the last batch call kept no spectrum (SetBatchSpectrum comes before the call)";
-    bands = lastSpectrum_;
-    if (ports) *ports = this->ports();
-    if (blocks) *blocks = reportBlocks_;
-    if (nBands) *nBands = spectrumBands_;
-    return "";
-}
-
-Error Engine::LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const {
-    if (!reportValid_) return "LastBatchReport: the last batch call kept no report (SetBatchReport comes before the call)";
-    records = lastReport_;
-    if (ports) *ports = this->ports();
-    if (blocks) *blocks = reportBlocks_;
-    return "";
-}
-
 /* the one context of a one-shard engine, for the streamed batch run */
 static Error streamShard(Engine *e, const char *what) {
     if (e->shards() != 1) return format("BatchStream: unsupported on an engine of %d shards (%s)", e->shards(), what);
@@ -1515,7 +1461,7 @@ Error Engine::BatchStreamOpen(const gdg_batch_input *inputs, int nInputs, const 
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || applyFits(ctx) != GDG_OK || applyGram(ctx) != GDG_OK || applyTapFits(ctx) != GDG_OK || applyTransfers(ctx) != GDG_OK || gdg_batch_out_records_enable(ctx, delivered_) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
+    if (applySettings(-1, ctx, window) != GDG_OK || gdg_batch_stream_open(ctx, inputs, nInputs, &options, samples) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -1545,69 +1491,14 @@ Error Engine::BatchStreamStep(int blocks, const void *const *ins, void *const *o
 
 /* one shard, the plain run: the context's records of every kind -- N + 3 ports and the blends' -- are the engine's */
 Error Engine::recordsOfContext(gdg_ctx *ctx) {
-    Error re;
-    if (report_ && (re = kindOf(ctx, ports(), reportBlocks_, 1, "a report", lastReport_)).empty()) reportValid_ = true;
-    if (re.empty() && truePeak_ && (re = truePeakOf(ctx, ports(), lastTruePeak_)).empty()) truePeakValid_ = true;
-    if (re.empty() && !alignRef_.empty() && (re = alignOf(ctx, ports(), lastAlign_)).empty()) alignValid_ = true;
-    if (re.empty() && !spectrumEdges_.empty() && (re = spectrumOf(ctx, ports(), lastSpectrum_)).empty()) spectrumValid_ = true;
-    if (re.empty() && BatchFits() > 0) {                   /* the fits' records: [fits][blocks], rows of their own */
-        int fits = 0;
-        size_t blocks = 0;
-        if (gdg_batch_fit(ctx, nullptr, 0, &fits, &blocks) != GDG_OK) re = gdg_last_error(ctx);
-        else {
-            lastFit_.assign((size_t)fits * blocks, gdg_block_fit{});
-            fitBlocks_ = blocks;
-            if (!lastFit_.empty() && gdg_batch_fit(ctx, lastFit_.data(), lastFit_.size(), &fits, &blocks) != GDG_OK) re = gdg_last_error(ctx);
-            else fitValid_ = true;
-        }
+    for (int k = 0; k < records::KINDS; k++) {
+        const records::Expect want = expected((records::Kind)k);
+        if (!want.on) continue;
+        Error re = records::table[k].ports ? records::fetchExpected((records::Kind)k, ctx, stores_[k], want.rows, stores_[k].blocks, want.per)
+                                           : records::fetchWhole((records::Kind)k, ctx, stores_[k], want.rows);
+        if (!re.empty()) { setError(re); return LastError(); }
+        stores_[k].valid = true;
     }
-    if (re.empty() && BatchGramPorts() > 0) {              /* the Gram records: [blocks][P (P + 1) / 2] */
-        size_t blocks = 0;
-        const size_t per = (size_t)BatchGramPorts() * ((size_t)BatchGramPorts() + 1) / 2;
-        if (gdg_batch_gram(ctx, nullptr, 0, &blocks) != GDG_OK) re = gdg_last_error(ctx);
-        else {
-            lastGram_.assign(blocks * per, 0.0);
-            gramBlocks_ = blocks;
-            gramPorts_ = BatchGramPorts();
-            if (!lastGram_.empty() && gdg_batch_gram(ctx, lastGram_.data(), lastGram_.size(), &blocks) != GDG_OK) re = gdg_last_error(ctx);
-            else gramValid_ = true;
-        }
-    }
-    if (re.empty() && BatchTransfers() > 0) {              /* the transfer records: [blocks][doubles] */
-        size_t blocks = 0, per = 0;
-        if (gdg_batch_transfer(ctx, nullptr, 0, &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
-        else {
-            lastTransfer_.assign(blocks * per, 0.0);
-            transferBlocks_ = blocks;
-            transferDoubles_ = per;
-            if (!lastTransfer_.empty() && gdg_batch_transfer(ctx, lastTransfer_.data(), lastTransfer_.size(), &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
-            else transferValid_ = true;
-        }
-    }
-    if (re.empty() && delivered_) {                        /* the delivered rows' records: [ports][blocks] */
-        int nports = 0;
-        size_t blocks = 0;
-        if (gdg_batch_out_records(ctx, nullptr, 0, &nports, &blocks) != GDG_OK) re = gdg_last_error(ctx);
-        else {
-            lastDelivered_.assign((size_t)nports * blocks, gdg_block_delivered{});
-            deliveredPorts_ = nports;
-            deliveredBlocks_ = blocks;
-            if (!lastDelivered_.empty() && gdg_batch_out_records(ctx, lastDelivered_.data(), lastDelivered_.size(), &nports, &blocks) != GDG_OK) re = gdg_last_error(ctx);
-            else deliveredValid_ = true;
-        }
-    }
-    if (re.empty() && BatchTapFits() > 0) {                /* the tap-fit records: [blocks][D] */
-        size_t blocks = 0, per = 0;
-        if (gdg_batch_tapfit(ctx, nullptr, 0, &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
-        else {
-            lastTapFit_.assign(blocks * per, 0.0);
-            tapFitBlocks_ = blocks;
-            tapFitDoubles_ = per;
-            if (!lastTapFit_.empty() && gdg_batch_tapfit(ctx, lastTapFit_.data(), lastTapFit_.size(), &blocks, &per) != GDG_OK) re = gdg_last_error(ctx);
-            else tapFitValid_ = true;
-        }
-    }
-    if (!re.empty()) { setError(re); return LastError(); }
     return "";
 }
 
@@ -1786,7 +1677,8 @@ Error Engine::BatchStreamResume(const gdg_batch_input *inputs, int nInputs, cons
     for (auto &c : chains) mine.push_back(c.get());
     e = sync(0, mine, options.target_rate);               /* the device follows the chains as before a Process call: taps pushed before the load */
     if (!e.empty()) { setError(e); return e; }
-    if (gdg_ctx_set_window(ctx, window) != GDG_OK || gdg_batch_report_enable(ctx, report_) != GDG_OK || gdg_batch_true_peak_enable(ctx, truePeak_) != GDG_OK || applySpectrum(ctx) != GDG_OK || applyAlign(-1, ctx) != GDG_OK || applySources(0, ctx) != GDG_OK || applyDither(0, ctx) != GDG_OK || applyTrim(0, ctx) != GDG_OK || gdg_batch_set_out_ratio(ctx, delivery_, deliveryUp_, deliveryDown_) != GDG_OK || applyBlends(ctx) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
+    /* a resumed job takes the list kinds as the context holds them: the five calls behind the blends are not made here */
+    if (applyPortSettings(-1, ctx, window) != GDG_OK || gdg_batch_stream_resume(ctx, inputs, nInputs, &options, blob, bytes, samplesDone) != GDG_OK) {
         setError(gdg_last_error(ctx));
         return LastError();
     }
@@ -2141,37 +2033,13 @@ void gdgh_engine_set_batch_report(void *e, int on) { ((Engine *)e)->SetBatchRepo
 const char *gdgh_engine_set_batch_spectrum(void *e, const double *edges, int n) {
     return ret(((Engine *)e)->SetBatchSpectrum(edges && n > 0 ? std::vector<double>(edges, edges + n) : std::vector<double>()));
 }
-/* bands == NULL: the three counts only */
+/* the nine gdgh_engine_last_batch_*: records (bands) == NULL: the counts only; capacity in records, or in doubles (records::copyOut) */
 const char *gdgh_engine_last_batch_spectrum(void *e, double *bands, size_t capacity, int *ports, size_t *blocks, int *n_bands) {
-    std::vector<double> val;
-    int p = 0, nb = 0;
-    size_t b = 0;
-    Error err = ((Engine *)e)->LastBatchSpectrum(val, &p, &b, &nb);
-    if (!err.empty()) return ret(err);
-    if (ports) *ports = p;
-    if (blocks) *blocks = b;
-    if (n_bands) *n_bands = nb;
-    if (bands) {
-        if (capacity < val.size()) return ret(Error("LastBatchSpectrum: too little room for the bands"));
-        if (!val.empty()) memcpy(bands, val.data(), val.size() * sizeof(double));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::SPECTRUM, ((Engine *)e)->batchRecords(records::SPECTRUM), bands, capacity, ports, blocks, n_bands));
 }
 void gdgh_engine_set_batch_true_peak(void *e, int on) { ((Engine *)e)->SetBatchTruePeak(on != 0); }
-/* records == NULL: the two counts only */
 const char *gdgh_engine_last_batch_true_peak(void *e, gdg_block_true_peak *records, size_t capacity, int *ports, size_t *blocks) {
-    std::vector<gdg_block_true_peak> rec;
-    int p = 0;
-    size_t b = 0;
-    Error err = ((Engine *)e)->LastBatchTruePeak(rec, &p, &b);
-    if (!err.empty()) return ret(err);
-    if (ports) *ports = p;
-    if (blocks) *blocks = b;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchTruePeak: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_true_peak));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::TRUE_PEAK, ((Engine *)e)->batchRecords(records::TRUE_PEAK), records, capacity, ports, blocks));
 }
 /* n_fits == 0: off */
 const char *gdgh_engine_set_batch_fits(void *e, int n_fits, const int *first, const int *port, const int *target) {
@@ -2185,20 +2053,8 @@ const char *gdgh_engine_set_batch_fits(void *e, int n_fits, const int *first, co
     return ret(((Engine *)e)->SetBatchFits(fits));
 }
 int gdgh_engine_batch_fits(void *e) { return ((Engine *)e)->BatchFits(); }
-/* records == NULL: the two counts only */
 const char *gdgh_engine_last_batch_fit(void *e, gdg_block_fit *records, size_t capacity, int *fits, size_t *blocks) {
-    std::vector<gdg_block_fit> rec;
-    int f = 0;
-    size_t b = 0;
-    Error err = ((Engine *)e)->LastBatchFit(rec, &f, &b);
-    if (!err.empty()) return ret(err);
-    if (fits) *fits = f;
-    if (blocks) *blocks = b;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchFit: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_fit));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::FIT, ((Engine *)e)->batchRecords(records::FIT), records, capacity, fits, blocks));
 }
 /* n_ports == 0: off */
 const char *gdgh_engine_set_batch_gram(void *e, const int *port, int n_ports) {
@@ -2207,20 +2063,8 @@ const char *gdgh_engine_set_batch_gram(void *e, const int *port, int n_ports) {
     return ret(((Engine *)e)->SetBatchGram(n_ports ? std::vector<int>(port, port + n_ports) : std::vector<int>()));
 }
 int gdgh_engine_batch_gram_ports(void *e) { return ((Engine *)e)->BatchGramPorts(); }
-/* records == NULL: the two counts only; capacity in doubles */
 const char *gdgh_engine_last_batch_gram(void *e, double *records, size_t capacity, int *ports, size_t *blocks) {
-    std::vector<double> rec;
-    int p = 0;
-    size_t b = 0;
-    Error err = ((Engine *)e)->LastBatchGram(rec, &p, &b);
-    if (!err.empty()) return ret(err);
-    if (ports) *ports = p;
-    if (blocks) *blocks = b;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchGram: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(double));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::GRAM, ((Engine *)e)->batchRecords(records::GRAM), records, capacity, ports, blocks));
 }
 /* n_fits == 0: off; the list in the CSR form of gdg_batch_tapfit_enable */
 const char *gdgh_engine_set_batch_tapfits(void *e, int n_fits, const int *first, const int *port, const int *target, const int *taps) {
@@ -2247,83 +2091,25 @@ const char *gdgh_engine_set_batch_delivered(void *e, int on) {
     if (!e) return ret(Error("no engine"));
     return ret(((Engine *)e)->SetBatchDelivered(on != 0));
 }
-/* records == NULL: the two counts only; capacity in records */
 const char *gdgh_engine_last_batch_delivered(void *e, gdg_block_delivered *records, size_t capacity, int *ports, size_t *blocks) {
     if (!e) return ret(Error("no engine"));
-    std::vector<gdg_block_delivered> rec;
-    int p = 0;
-    size_t b = 0;
-    Error err = ((Engine *)e)->LastBatchDelivered(rec, &p, &b);
-    if (!err.empty()) return ret(err);
-    if (ports) *ports = p;
-    if (blocks) *blocks = b;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchDelivered: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_delivered));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::DELIVERED, ((Engine *)e)->batchRecords(records::DELIVERED), records, capacity, ports, blocks));
 }
-/* records == NULL: the two counts only; capacity in doubles */
 const char *gdgh_engine_last_batch_transfer(void *e, double *records, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
-    std::vector<double> rec;
-    size_t b = 0, d = 0;
-    Error err = ((Engine *)e)->LastBatchTransfer(rec, &b, &d);
-    if (!err.empty()) return ret(err);
-    if (blocks) *blocks = b;
-    if (doubles_per_block) *doubles_per_block = d;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchTransfer: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(double));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::TRANSFER, ((Engine *)e)->batchRecords(records::TRANSFER), records, capacity, nullptr, blocks, doubles_per_block));
 }
-/* records == NULL: the two counts only; capacity in doubles */
 const char *gdgh_engine_last_batch_tapfit(void *e, double *records, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
-    std::vector<double> rec;
-    size_t b = 0, d = 0;
-    Error err = ((Engine *)e)->LastBatchTapFit(rec, &b, &d);
-    if (!err.empty()) return ret(err);
-    if (blocks) *blocks = b;
-    if (doubles_per_block) *doubles_per_block = d;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchTapFit: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(double));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::TAPFIT, ((Engine *)e)->batchRecords(records::TAPFIT), records, capacity, nullptr, blocks, doubles_per_block));
 }
 /* n == 0: off */
 const char *gdgh_engine_set_batch_align(void *e, const int *ref, int n, int max_lag) {
     return ret(((Engine *)e)->SetBatchAlign(ref && n > 0 ? std::vector<int>(ref, ref + n) : std::vector<int>(), max_lag));
 }
-/* records == NULL: the two counts only */
 const char *gdgh_engine_last_batch_align(void *e, gdg_block_align *records, size_t capacity, int *ports, size_t *blocks) {
-    std::vector<gdg_block_align> rec;
-    int p = 0;
-    size_t b = 0;
-    Error err = ((Engine *)e)->LastBatchAlign(rec, &p, &b);
-    if (!err.empty()) return ret(err);
-    if (ports) *ports = p;
-    if (blocks) *blocks = b;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchAlign: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_align));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::ALIGN, ((Engine *)e)->batchRecords(records::ALIGN), records, capacity, ports, blocks));
 }
-/* records == NULL: the two counts only */
 const char *gdgh_engine_last_batch_report(void *e, gdg_block_stats *records, size_t capacity, int *ports, size_t *blocks) {
-    std::vector<gdg_block_stats> rec;
-    int p = 0;
-    size_t b = 0;
-    Error err = ((Engine *)e)->LastBatchReport(rec, &p, &b);
-    if (!err.empty()) return ret(err);
-    if (ports) *ports = p;
-    if (blocks) *blocks = b;
-    if (records) {
-        if (capacity < rec.size()) return ret(Error("LastBatchReport: too little room for the records"));
-        if (!rec.empty()) memcpy(records, rec.data(), rec.size() * sizeof(gdg_block_stats));
-    }
-    return ret(Error(""));
+    return ret(records::copyOut(records::REPORT, ((Engine *)e)->batchRecords(records::REPORT), records, capacity, ports, blocks));
 }
 const char *gdgh_engine_batch_stream_open(void *e, const gdg_batch_input *inputs, int n, const gdg_batch_options *opt, int window, size_t *samples) {
     return ret(((Engine *)e)->BatchStreamOpen(inputs, n, *opt, window, samples));

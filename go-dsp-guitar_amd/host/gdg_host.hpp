@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/gdg.h"      /* the C-ABI the twin is written against (gdg_ctx, gdg_batch_input, gdg_batch_options ...) */
+#include "batch_records.h"          /* the nine kinds of records a batch call keeps: one table, one store per kind */
 
 #define GDG_HOST_MAX_FRAMES 8192      /* controller/controller.go:36 BLOCK_SIZE */
 
@@ -367,6 +368,7 @@ public:
     gdg_ctx *context(int shard = 0);                       /* creates the device context on first use */
     std::mutex &shardMutex(int shard);                     /* a context takes one call at a time (include/gdg.h) */
     void setError(const Error &e);                         /* what lastError() returns; also used by the spatializer / tuner twins for per-shard failures */
+    const records::RecordStore &batchRecords(records::Kind kind) const { return stores_[kind]; }      /* what LastBatch* hands out of, for the C wrappers */
 
 private:
     friend class signal::Chain;
@@ -390,25 +392,17 @@ private:
     gdg_batch_options shardedOptions_ = {};
     uint64_t shardedSlices_ = 0;                           /* ... and this many slices done (a checkpoint's wrapper records it) */
     void closeSharded();
-    bool report_ = false, reportValid_ = false;            /* the render report: asked for; the last call's is complete */
-    size_t reportBlocks_ = 0;
-    std::vector<gdg_block_stats> lastReport_;
-    std::vector<double> spectrumEdges_, lastSpectrum_;     /* the band spectrum: the edges in force (empty: off); the last call's, over reportBlocks_ */
-    bool spectrumValid_ = false;
-    int spectrumBands_ = 0;                                /* ... and its band count */
+    records::RecordStore stores_[records::KINDS];          /* the last batch call's records, one store per kind (batch_records.h) */
+    records::Expect expected(records::Kind kind) const;              /* whether the settings in force keep a kind, and at which counts */
+    bool report_ = false;                                  /* the render report: asked for */
+    std::vector<double> spectrumEdges_;                    /* the band spectrum: the edges in force (empty: off) */
     int applySpectrum(gdg_ctx *ctx);
     std::vector<int> alignRef_;                            /* the alignment report: the list in force over the job's N + 3 ports (empty: off) ... */
-    int alignLag_ = 0;                                     /* ... its lag range, the last call's records over reportBlocks_, and whether they are complete */
-    std::vector<gdg_block_align> lastAlign_;
-    bool alignValid_ = false;
+    int alignLag_ = 0;                                     /* ... and its lag range */
     int shardOfPort(int port);
     Error alignOverShards(int minShards);
     int applyAlign(int shard, gdg_ctx *ctx);               /* shard < 0: the plain form's list */
-    Error alignOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_align> &rec);
-    Error spectrumOf(gdg_ctx *ctx, int ports, std::vector<double> &val);
-    bool truePeak_ = false, truePeakValid_ = false;        /* the true-peak records: asked for; the last call's, over reportBlocks_, are complete */
-    std::vector<gdg_block_true_peak> lastTruePeak_;
-    Error truePeakOf(gdg_ctx *ctx, int ports, std::vector<gdg_block_true_peak> &rec);
+    bool truePeak_ = false;                                /* the true-peak records: asked for */
     std::vector<int> sources_;                             /* the source map in job channel numbers; empty: none */
     int applySources(int shard, gdg_ctx *ctx);             /* the shard's part of it onto its context: a gdg_* status */
     bool dither_ = false;                                  /* SetBatchDither: on, and the seed */
@@ -424,34 +418,22 @@ private:
     std::vector<int> blendTapFirst_;                       /* one offset per term and one more into blendTap_, or empty: no term has taps and the list goes the delayed way */
     std::vector<double> blendTap_;
     std::vector<int> fitFirst_, fitPort_, fitTarget_;      /* SetBatchFits, in gdg_batch_fit_enable's CSR form; fitTarget_ empty: off */
-    std::vector<gdg_block_fit> lastFit_;                   /* [fits][blocks] of the last batch call that kept them */
-    size_t fitBlocks_ = 0;
-    bool fitValid_ = false;
     int applyFits(gdg_ctx *ctx);                           /* onto a context (more shards: none are in force): a gdg_* status */
     std::vector<int> gramPort_;                            /* SetBatchGram; empty: off */
-    std::vector<double> lastGram_;                         /* [blocks][P (P + 1) / 2] of the last batch call that kept them */
-    size_t gramBlocks_ = 0;
-    int gramPorts_ = 0;                                    /* P of lastGram_ */
-    bool gramValid_ = false;
     int applyGram(gdg_ctx *ctx);                           /* onto a context (more shards: none is in force): a gdg_* status */
     std::vector<int> tapFitFirst_, tapFitPort_, tapFitTarget_, tapFitTaps_;      /* SetBatchTapFits, in the CSR form of the C call; no target: off */
-    std::vector<double> lastTapFit_;                       /* [blocks][D] of the last batch call that kept them */
-    size_t tapFitBlocks_ = 0, tapFitDoubles_ = 0;
-    bool tapFitValid_ = false;
     std::vector<int> transferPort_, transferTarget_;      /* SetBatchTransfers; no pair: off */
     int transferGroup_ = 1;
-    std::vector<double> lastTransfer_;                     /* [blocks][doubles] of the last batch call that kept them */
-    size_t transferBlocks_ = 0, transferDoubles_ = 0;
-    bool transferValid_ = false;
     bool delivered_ = false;                               /* SetBatchDelivered; never on on an engine of several shards */
-    std::vector<gdg_block_delivered> lastDelivered_;       /* [ports][blocks] of the last batch call that kept them */
-    int deliveredPorts_ = 0;
-    size_t deliveredBlocks_ = 0;
-    bool deliveredValid_ = false;
     int applyTransfers(gdg_ctx *ctx);                      /* onto a context (more shards: none is in force): a gdg_* status */
     int applyTapFits(gdg_ctx *ctx);                        /* onto a context (more shards: none are in force): a gdg_* status */
     bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivered_ || delivery_ > 1 || deliveryUp_ != 1 || deliveryDown_ != 1; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
+    /* every setting in force onto a context, in the order the library's checks need: the window, the four port kinds, sources, dither,
+     * trim, delivery and blends (applyPortSettings: all that a resumed job is set up with), then the five list kinds.  shard < 0: the plain
+     * form of a one-shard engine, whose alignment list covers the master and the blend ports.  A gdg_* status */
+    int applyPortSettings(int shard, gdg_ctx *ctx, int window);
+    int applySettings(int shard, gdg_ctx *ctx, int window);
     int ports() const { return nChannels_ + 3 + BatchBlends(); }      /* of a batch call: N + 3 and the blends in force */
     Error recordsOfContext(gdg_ctx *ctx);                  /* one shard, the plain run: the context's records of every kind are the engine's */
     void reportBegin(size_t blocks);

@@ -40,7 +40,7 @@ def test_engine_keeps_the_plain_order_whatever_the_shard_count(host, oracle):
     plain = eng.batch_run(inputs, sr, "lpcm24", **kw)
     assert eng.last_align is None
     with pytest.raises(host.HostError, match="no alignment records"):
-        eng._fetch_align()
+        eng._fetch("align")
     # the shard forms make the master in the finish: a list that touches it is refused when the job is set up, at any shard count
     with pytest.raises(host.HostError, match="master mix"):
         eng.batch_run(inputs, sr, "lpcm24", align=(with_master, M), **kw)

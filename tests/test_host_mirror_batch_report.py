@@ -18,7 +18,7 @@ def test_engine_reports_the_plain_order_whatever_the_shard_count(host, oracle):
     outs = eng.batch_run(inputs, sr, "ieee64", window=4, metronome_to_master=True)
     assert eng.last_report is None, "off by default"
     with pytest.raises(host.HostError, match="no report"):
-        eng._fetch_report()
+        eng._fetch("report")
     del sp
     eng.close()
     eng, sp = _engine(host, nch, sr)

@@ -38,7 +38,7 @@ def test_engine_keeps_the_plain_order_whatever_the_shard_count(host, oracle):
     plain = eng.batch_run(inputs, sr, "lpcm24", **kw)
     assert eng.last_spectrum is None
     with pytest.raises(host.HostError, match="no spectrum"):
-        eng._fetch_spectrum()
+        eng._fetch("spectrum")
     del sp
     eng.close()
     keep = list(range(nch)) + [nch + 2]

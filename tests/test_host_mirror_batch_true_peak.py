@@ -37,7 +37,7 @@ def test_engine_keeps_the_plain_order_whatever_the_shard_count(host, oracle):
     plain = eng.batch_run(inputs, sr, "lpcm24", **kw)
     assert eng.last_true_peak is None
     with pytest.raises(host.HostError, match="no true-peak records"):
-        eng._fetch_true_peak()
+        eng._fetch("true_peak")
     del sp
     eng.close()
     keep = list(range(nch)) + [nch + 2]
