@@ -66,6 +66,8 @@ ABI_SYMBOLS = [
     "gdg_batch_set_out_ratio", "gdg_batch_out_ratio", "gdg_batch_out_samples", "gdg_batch_out_ratio_latency", "gdg_out_ratio_taps",
     "gdg_out_ratio_rows", "gdg_out_ratio_rows_device",
     "gdg_block_out_rows", "gdg_block_out_rows_device", "gdg_batch_out_records_enable", "gdg_batch_out_records", "gdg_trim_from_out_records",
+    "gdg_loudness_coefficients", "gdg_loudness_hops", "gdg_loudness_rows", "gdg_loudness_rows_device", "gdg_batch_loudness_enable", "gdg_batch_loudness",
+    "gdg_loudness_from_hops", "gdg_trim_from_loudness",
 ]
 
 # gdg_block_stats (include/gdg.h): one record of the render report, 32 bytes, little-endian, no padding
@@ -125,6 +127,61 @@ def trim_from_delivered(records, target, max_gain):
     if rc != GDG_OK:
         raise GdgError(rc, lib().gdg_last_error(None).decode())
     return gain
+
+
+LOUDNESS_STATE_DOUBLES = 7   # GDG_LOUDNESS_STATE_DOUBLES (include/gdg.h, LOUDNESS): what a port keeps from call to call
+LOUDNESS_TILE = 8192         # GDG_LOUDNESS_TILE: a continuing call begins at a multiple of it
+
+
+def loudness_coefficients(rate):
+    """gdg_loudness_coefficients: the K-weighting at `rate` -- shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2; host arithmetic"""
+    out = np.zeros(10, dtype=np.float64)
+    rc = lib().gdg_loudness_coefficients(int(rate), out.ctypes.data)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return out
+
+
+def loudness_hops(rate, first, count):
+    """gdg_loudness_hops: the hops of rate / 10 samples that complete in the job's samples [first, first + count); 0 for a rate without hops"""
+    return int(lib().gdg_loudness_hops(int(rate), int(first), int(count)))
+
+
+def loudness_from_hops(records, rate, ports, weights=None):
+    """gdg_loudness_from_hops: records [ports, hops] float64 (hop sums, as batch_loudness and loudness_rows hand them out); the programme is the
+    listed `ports` with BS.1770's channel `weights` (None: every one 1.0).  Returns (integrated, momentary_max, short_term_max) in LUFS, -inf
+    where no block passes the absolute gate.  Host arithmetic: no context, no device."""
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    if rec.ndim != 2:
+        raise ValueError("records: [ports, hops]")
+    port = np.ascontiguousarray(ports, dtype=np.int32).reshape(-1)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w is not None and w.size != port.size:
+        raise ValueError("one weight per listed port")
+    out = [C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)]
+    rc = lib().gdg_loudness_from_hops(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], int(rate), port.ctypes.data if port.size else None,
+                                      None if w is None else w.ctypes.data, port.size, C.byref(out[0]), C.byref(out[1]), C.byref(out[2]))
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return tuple(v.value for v in out)
+
+
+def trim_from_loudness(records, rate, target_lufs, ceiling_dbtp=0.0, true_peak=None):
+    """gdg_trim_from_loudness: one gain per port toward target_lufs from its hop records [ports, hops]; with true-peak records ([ports, blocks],
+    BLOCK_TRUE_PEAK_DTYPE) a gain that would carry the port over ceiling_dbtp is capped.  Returns (gain, capped).  Host arithmetic."""
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    if rec.ndim != 2:
+        raise ValueError("records: [ports, hops]")
+    tp = None if true_peak is None else np.ascontiguousarray(true_peak, dtype=BLOCK_TRUE_PEAK_DTYPE)
+    if tp is not None and (tp.ndim != 2 or tp.shape[0] != rec.shape[0]):
+        raise ValueError("true_peak: [ports, blocks] for the same ports")
+    gain, capped = np.zeros(rec.shape[0], dtype=np.float64), np.zeros(rec.shape[0], dtype=np.int32)
+    rc = lib().gdg_trim_from_loudness(rec.ctypes.data if rec.size else None, rec.shape[0], rec.shape[1], int(rate), float(target_lufs), float(ceiling_dbtp),
+                                      tp.ctypes.data if tp is not None and tp.size else None, 0 if tp is None else tp.shape[1],
+                                      gain.ctypes.data if gain.size else None, capped.ctypes.data if capped.size else None)
+    if rc != GDG_OK:
+        raise GdgError(rc, lib().gdg_last_error(None).decode())
+    return gain, capped.astype(bool)
 
 
 BLEND_MAX_DELAY = 4096       # GDG_BLEND_MAX_DELAY (include/gdg.h): the largest delay of a blend's term, and the samples of history a row keeps
@@ -689,6 +746,14 @@ def lib():
             "gdg_batch_out_records_enable": (i32, [vp, i32]),
             "gdg_batch_out_records": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdg_trim_from_out_records": (i32, [vp, i32, C.c_size_t, C.c_double, C.c_double, vp]),
+            "gdg_loudness_coefficients": (i32, [C.c_uint32, vp]),
+            "gdg_loudness_hops": (C.c_size_t, [C.c_uint32, C.c_size_t, C.c_size_t]),
+            "gdg_loudness_rows": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, C.c_size_t, C.c_uint32, vp, vp, vp, C.c_size_t]),
+            "gdg_loudness_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, C.c_size_t, C.c_uint32, vp, vp, vp, C.c_size_t]),
+            "gdg_batch_loudness_enable": (i32, [vp, i32]),
+            "gdg_batch_loudness": (i32, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+            "gdg_loudness_from_hops": (i32, [vp, i32, C.c_size_t, C.c_uint32, vp, vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+            "gdg_trim_from_loudness": (i32, [vp, i32, C.c_size_t, C.c_uint32, C.c_double, C.c_double, vp, C.c_size_t, vp, vp]),
             "gdg_block_true_peak_rows": (i32, [vp, vp, i32, C.c_size_t, vp]),
             "gdg_block_true_peak_rows_device": (i32, [vp, vp, C.c_size_t, i32, C.c_size_t, vp]),
             "gdg_batch_true_peak_enable": (i32, [vp, i32]),
@@ -2096,6 +2161,51 @@ class Context:
         return out
 
     trim_from_delivered = staticmethod(trim_from_delivered)
+
+    def loudness_rows(self, rows, rate, first=0, state=None):
+        """gdg_loudness_rows: rows [n_rows][count] float64 (or one 1-D row), the samples [first, first + count) of a stream at `rate`.  Returns
+        (records [n_rows][hops] -- the hop sums of the K-weighted samples that complete in them --, state [n_rows][LOUDNESS_STATE_DOUBLES]).
+        state None starts a stream (first must be 0); a continuing call passes the state the call before returned and begins at a multiple of
+        LOUDNESS_TILE samples."""
+        x = np.ascontiguousarray(rows, dtype=np.float64)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.ndim != 2:
+            raise ValueError("rows: [n_rows, count]")
+        n, count = x.shape
+        st_in = None if state is None else np.ascontiguousarray(state, dtype=np.float64)
+        if st_in is not None and st_in.shape != (n, LOUDNESS_STATE_DOUBLES):
+            raise ValueError("state: [n_rows, %d]" % LOUDNESS_STATE_DOUBLES)
+        hops = loudness_hops(rate, first, count)
+        out, st_out = np.zeros((n, hops), dtype=np.float64), np.zeros((n, LOUDNESS_STATE_DOUBLES), dtype=np.float64)
+        self._check(lib().gdg_loudness_rows(self._h, x.ctypes.data if x.size else None, count, n, int(first), count, int(rate), None if st_in is None else st_in.ctypes.data,
+                                            st_out.ctypes.data, out.ctypes.data if out.size else None, hops))
+        return out, st_out
+
+    def loudness_rows_device(self, d_rows, row_stride, n_rows, first, count, rate, d_state_in, d_state_out, d_records, records_stride):
+        """gdg_loudness_rows_device on plain device pointers (ints; d_state_in 0 or None starts a stream).  Enqueued on the context's stream."""
+        self._check(lib().gdg_loudness_rows_device(self._h, d_rows, row_stride, n_rows, first, count, int(rate), d_state_in or None, d_state_out or None, d_records or None,
+                                                   records_stride))
+
+    def batch_loudness_enable(self, enable=True):
+        """From the next batch call on, batch_run and batch_stream_step keep the hop records -- the sum of squares of the K-weighted samples of
+        every 100 ms -- of every encoded port, taken from the session-rate rows in front of delivery, trim and blend gain
+        (gdg_batch_loudness_enable; off by default).  Configuration: not in a checkpoint, refused while a streamed job is open; the checkpoint,
+        shard and finish_master calls refuse while it is on."""
+        self._check(lib().gdg_batch_loudness_enable(self._h, 1 if enable else 0))
+
+    def batch_loudness(self):
+        """The [ports][hops] float64 hop records of the last completed batch call or slice; GdgError when there are none."""
+        ports, hops = C.c_int(0), C.c_size_t(0)
+        self._check(lib().gdg_batch_loudness(self._h, None, 0, C.byref(ports), C.byref(hops)))
+        out = np.zeros((ports.value, hops.value), dtype=np.float64)
+        self._check(lib().gdg_batch_loudness(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(hops)))
+        return out
+
+    loudness_from_hops = staticmethod(loudness_from_hops)
+    trim_from_loudness = staticmethod(trim_from_loudness)
+    loudness_hops = staticmethod(loudness_hops)
+    loudness_coefficients = staticmethod(loudness_coefficients)
 
     def metronome_process(self, frames):
         out = np.empty(frames, dtype=np.float64)

@@ -85,6 +85,7 @@ int gdg_batch_release(gdg_ctx *ctx) {
     enter(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < BATCH_DEV_SLOTS; i++) batch_drop(ctx, { i });
+    loudness_release(ctx);
     return GDG_OK;
 }
 
@@ -346,6 +347,8 @@ struct BlockLoop {
             HIP_TRY(ctx, gdg_launch_blend(p.blend, p.d_win, ws, wb, p.d_blend_history, (size_t)GDG_BLEND_MAX_DELAY, p.d_win + (size_t)NO * ws, ws, ctx->stream));
             if (p.d_blend_history) HIP_TRY(ctx, gdg_launch_blend_history_save(p.d_win, ws, wb, (unsigned)N, p.d_blend_history, ctx->stream));
         }
+        /* the loudness records (api_loudness.cpp; off: nothing): the same rows, the job's samples from this step's first on */
+        if (const int rl = loudness_step(ctx, p.d_win, ws, (size_t)p.dither_first + st.off, wb)) return rl;
         /* statistics, then the band spectrum: the window's rows, and a shard's metronome row, which is row N + 2 of the window and record row N */
         const unsigned n_win = sharded ? (unsigned)N : (unsigned)NR;
         const RowGroup groups[2] = { { p.d_win, ws, n_win, 0 }, { metro(), ws, 1u, (size_t)N } };
@@ -969,6 +972,7 @@ int gdg_batch_stream_open_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int
                                 int run_metronome, size_t *samples) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
+    if (const int rl = loudness_refused(ctx, "gdg_batch_stream_open_shard", "a sharded job cannot collect them yet")) return rl;
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_stream_open_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_open_shard")) return rc;
     /* as gdg_batch_run_shard: a set flag would be silently dropped -- refuse it instead */
@@ -1317,6 +1321,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     int rc = check_meter_ports(ctx, opt, "");
     if (rc != GDG_OK) return rc;
     enter(ctx);
+    if ((rc = loudness_slice_begin(ctx, NR, pos, length, opt->target_rate)) != GDG_OK) return rc;      /* never a shard's: its calls refuse the switch */
     const int W = ctx->window;
     const size_t ws = (size_t)W * B;
     /* a shard's slice: the rows that leave the device encoded and as float64 are this slice's (which metronome buffers it passes), the
@@ -1374,7 +1379,7 @@ static int run_slice(gdg_ctx *ctx, const gdg_ctx::BatchStreamState &S, int block
     brought.resize((size_t)N);
     for (int i = 0; i < N; i++) brought[(size_t)i] = first[(size_t)i] + count[(size_t)i];
     for (int i = 0; i < N; i++) if (is_reader(S, i)) brought[(size_t)i] = brought[(size_t)S.source[(size_t)i]];
-    return report_end(ctx, rc);
+    return loudness_slice_end(ctx, report_end(ctx, rc));
 }
 
 /* one slice of the context's open job; `slice`: of a job opened as a shard (the slice's partial master and metronome buffers) */
@@ -1406,6 +1411,7 @@ int gdg_batch_stream_step(gdg_ctx *ctx, int blocks, const void *const *in_bytes,
 int gdg_batch_stream_step_shard(gdg_ctx *ctx, int blocks, const void *const *in_bytes, void *const *out_bytes, const gdg_batch_shard_out *slice) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_stream_step_shard");
     if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_stream_step_shard");
+    if (const int rl = loudness_refused(ctx, "gdg_batch_stream_step_shard", "a sharded job cannot collect them yet")) return rl;
     if (const int rc = lists_refused(ctx, "gdg_batch_stream_step_shard")) return rc;
     return stream_step(ctx, blocks, in_bytes, out_bytes, slice, true);
 }
@@ -1451,6 +1457,7 @@ int gdg_batch_run_shard(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_input
     if (!shard) return GDG_ERR_INVALID;
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_run_shard");
     if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_run_shard");
+    if (const int rl = loudness_refused(ctx, "gdg_batch_run_shard", "a sharded job cannot collect them yet")) return rl;
     if (ctx && ctx->blend.count()) return BLENDS_REFUSED(ctx, "gdg_batch_run_shard");
     if (const int rc = lists_refused(ctx, "gdg_batch_run_shard")) return rc;
     /* a shard's master mix is a PARTIAL sum: the aux input joins the master once, in gdg_batch_finish_master (its `aux` = the float64
@@ -1609,6 +1616,7 @@ int gdg_batch_finish_master(gdg_ctx *ctx, int out_format, const double *const *l
                             size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master");
     if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_finish_master");
+    if (const int rl = loudness_refused(ctx, "gdg_batch_finish_master", "a master mix has no hop records yet")) return rl;
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     return finish_master(ctx, out_format, left, right, n_shards, aux, samples, sample_rate, run_meters, left_bytes, right_bytes, 0);      /* the cursor stays */
@@ -1619,6 +1627,7 @@ int gdg_batch_finish_master_slice(gdg_ctx *ctx, int out_format, const double *co
                                   size_t samples, uint32_t sample_rate, int run_meters, void *left_bytes, void *right_bytes) {
     if (ctx && delivery_on(ctx)) return DELIVERY_REFUSED(ctx, "gdg_batch_finish_master_slice");
     if (ctx && ctx->out_rec_on) return OUT_RECORDS_REFUSED(ctx, "gdg_batch_finish_master_slice");
+    if (const int rl = loudness_refused(ctx, "gdg_batch_finish_master_slice", "a master mix has no hop records yet")) return rl;
     const int rc = finish_master_check(ctx, out_format, left, right, n_shards, sample_rate, run_meters);
     if (rc != GDG_OK) return rc;
     if (samples % GDG_BLOCK_SIZE) return fail(ctx, GDG_ERR_INVALID, "a slice of %zu samples: whole blocks of %d", samples, GDG_BLOCK_SIZE);

@@ -131,6 +131,7 @@ int gdg_batch_stream_checkpoint_size(gdg_ctx *ctx, size_t *bytes) {
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
     if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
     if (ctx->out_rec_on) return OUT_RECORDS_HISTORY_REFUSED(ctx, "checkpoint");
+    if (const int rl = loudness_refused(ctx, "checkpoint", "their state is not in the version-1 container")) return rl;
     if (!ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     const int rc = checkpoint_plan(ctx, P);
@@ -145,6 +146,7 @@ int gdg_batch_stream_checkpoint(gdg_ctx *ctx, void *blob, size_t capacity, size_
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, "checkpoint");
     if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, "checkpoint");
     if (ctx->out_rec_on) return OUT_RECORDS_HISTORY_REFUSED(ctx, "checkpoint");
+    if (const int rl = loudness_refused(ctx, "checkpoint", "their state is not in the version-1 container")) return rl;
     if (!S.open) return fail(ctx, GDG_ERR_INVALID, "checkpoint: no streamed batch run is open on this context");
     CkptPlan P;
     int rc = checkpoint_plan(ctx, P);
@@ -283,6 +285,7 @@ static int resume(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, con
     if (ctx->blend.max_reach() > 0) return BLEND_HISTORY_REFUSED(ctx, what);
     if (delivery_on(ctx)) return DELIVERY_HISTORY_REFUSED(ctx, what);
     if (ctx->out_rec_on) return OUT_RECORDS_HISTORY_REFUSED(ctx, what);
+    if (const int rl = loudness_refused(ctx, what, "their state is not in the version-1 container")) return rl;
     if (ctx->bstream.open) return fail(ctx, GDG_ERR_INVALID, "%s: a streamed batch run is already open on this context", what);
     CkptHeader h;
     int rc = read_header(ctx, what, blob, bytes, h);

@@ -321,6 +321,7 @@ int gdg_ctx_destroy(gdg_ctx *ctx) {
     for (PinnedHalves *p : { &ctx->h_batch, &ctx->h_up, &ctx->h_fin_up, &ctx->h_fin_down }) p->release();
     if (ctx->batch_begin) hipEventDestroy(ctx->batch_begin);
     for (int i = 0; i < BATCH_DEV_SLOTS; i++) hipFree(ctx->batch_dev[i]);
+    loudness_release(ctx);
     if (ctx->batch_up_stream) hipStreamDestroy(ctx->batch_up_stream);
     if (ctx->h_tuner_out) hipHostFree(ctx->h_tuner_out);
     if (ctx->h_stage_in) hipHostFree(ctx->h_stage_in);
@@ -378,6 +379,7 @@ int gdg_ctx_get_option(gdg_ctx *ctx, const char *key, long long *value) {
     if (o->field == &gdg_ctx::stat_batch_dev_kib) {
         size_t bytes = 0;
         for (int i = 0; i < BATCH_DEV_SLOTS; i++) bytes += ctx->batch_dev_cap[i];
+        bytes += loudness_device_bytes(ctx);
         const size_t kib = (bytes + 1023) / 1024;
         ctx->stat_batch_dev_kib = kib > 0x7fffffffull ? 0x7fffffff : (int)kib;
     }

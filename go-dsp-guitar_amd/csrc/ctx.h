@@ -12,6 +12,7 @@
  *   api_batch.cpp       the batch run (gdg_batch_run, its sharded form, the streamed forms of both, the master mix of a job and of a slice)
  *   api_state.cpp       channel state saved into / loaded from a blob (gdg_state_*; the copies: state.hip)
  *   api_checkpoint.cpp  a streamed batch run checkpointed into a container and resumed from it (gdg_batch_stream_checkpoint / _resume; the digest: state.hip)
+ *   api_loudness.cpp    the loudness records (gdg_loudness_*, gdg_batch_loudness*, gdg_trim_from_loudness; the kernel: loudness.hip)
  */
 #ifndef GDG_CTX_H
 #define GDG_CTX_H
@@ -51,6 +52,7 @@
 #include "report_sections.h"
 #include "trim.h"
 #include "blend.h"
+#include "loudness.h"
 
 #define NUM_FILTERS 8
 
@@ -452,6 +454,20 @@ struct gdg_ctx {
         size_t rows = 0, elem = 0, blocks = 0;
         std::vector<unsigned char> store;
     } list_rec[LIST_KINDS];
+    /* the loudness records (include/gdg.h, LOUDNESS; api_loudness.cpp): a path of its own beside the kinds above.  While the switch is on
+     * (gdg_batch_loudness_enable) d_state holds the [ports][7] doubles every port keeps from step to step and d_records the [ports][hops] hop
+     * sums of the running or the last slice, which come down when gdg_batch_loudness asks; off, neither exists.  `live`: the running slice
+     * collects (decided when it begins); `valid`: the last one completed.  d_own: the state of a stand-alone call that was given none. */
+    struct Loudness {
+        bool on = false, live = false, valid = false;
+        double *d_state = nullptr, *d_records = nullptr, *d_own = nullptr;
+        size_t state_cap = 0, records_cap = 0, own_cap = 0;
+        int ports = 0;
+        size_t hops = 0;
+        unsigned long long hop_base = 0;
+        uint32_t rate = 0;
+        gdg_loudness_params par;
+    } loud;
     /* ... and the spans of the stand-alone calls' last launch (gdg_block_out_rows): the host's copy, which the upload reads, and the device's */
     std::vector<unsigned long long> out_rows_spans;
     unsigned long long *d_out_rows_spans = nullptr;
@@ -753,6 +769,19 @@ int stream_job(gdg_ctx *ctx, const gdg_batch_input *inputs, int n_inputs, const 
 int batch_carry_buffer(gdg_ctx *ctx, double **d_carry);
 /* api_batch.cpp: what a shard's entry point `what` refuses while list records are in force -- fits, then the Gram list, then tap fits, then transfer pairs; GDG_OK: none is (or no context) */
 int lists_refused(gdg_ctx *ctx, const char *what);
+/* api_loudness.cpp: what the entry point `what` refuses while the loudness records are on, `why` in a few words; GDG_OK: they are off (or no context) */
+int loudness_refused(gdg_ctx *ctx, const char *what, const char *why);
+/* api_loudness.cpp, for the slice runner: a slice of `samples` samples at the job's sample `pos` begins (its buffers, zeroed by a job's first
+ * slice); a step's rows, the job's samples [first, first + count), are measured; the slice has ended with rc.  Off: nothing is done */
+int loudness_slice_begin(gdg_ctx *ctx, int ports, size_t pos, size_t samples, uint32_t rate);
+int loudness_step(gdg_ctx *ctx, const double *d_rows, size_t row_stride, size_t first, size_t count);
+int loudness_slice_end(gdg_ctx *ctx, int rc);
+/* ... its device buffers go (the caller has waited for whatever reads them); the bytes they hold */
+void loudness_release(gdg_ctx *ctx);
+size_t loudness_device_bytes(const gdg_ctx *ctx);
+/* loudness.hip */
+hipError_t gdg_launch_block_loudness(const double *d_rows, size_t row_stride, unsigned n_rows, unsigned long long first, unsigned long long count, uint32_t rate,
+                                     unsigned long long hop_base, unsigned long long hops_room, const gdg_loudness_params &par, double *d_state, double *d_records, hipStream_t s);
 /* api_io.cpp: a list of fits against gdg_fit_check (blend.h), refused in the words of `what`; n_rows < 0: the port count is not known yet */
 int fit_list_check(gdg_ctx *ctx, const char *what, int n_fits, const int *first, const int *port, const int *target, int n_rows);
 /* api_io.cpp: a Gram list of `least` to GDG_GRAM_MAX_PORTS ports against blend.h's checks, refused in the words of `what`; n_rows < 0: the port count is not known yet */
@@ -769,6 +798,7 @@ static inline void report_begin(gdg_ctx *ctx, int ports, size_t blocks, bool ali
     ctx->spec_live_edges = ctx->spec_edges;
     ctx->align_live_ref.clear();
     for (gdg_ctx::ListRecords &R : ctx->list_rec) R.valid = R.live = false;      /* a call that collects list records says so itself (list_begin) */
+    ctx->loud.valid = ctx->loud.live = false;                                    /* ... and so does one that collects loudness records (loudness_slice_begin) */
     /* any other count was refused when the job was described; a list without the call's blend ports: each of them references itself */
     if (align && ((int)ctx->align_ref.size() == ports || (blend_ports > 0 && (int)ctx->align_ref.size() == ports - blend_ports))) {
         ctx->align_live_ref = ctx->align_ref;

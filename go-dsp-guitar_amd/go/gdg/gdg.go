@@ -3691,3 +3691,250 @@ func TrimFromDelivered(records [][]BlockDelivered, target float64, maxGain float
 	}
 	return gain, nil
 }
+
+// ---- loudness (include/gdg.h, LOUDNESS): K-weighted hop records after ITU-R BS.1770, and the planners on them ----
+
+// LoudnessStateDoubles: GDG_LOUDNESS_STATE_DOUBLES, what a row keeps from call to call; LoudnessTile: a continuing call begins at a multiple of it.
+const (
+	LoudnessStateDoubles = 7
+	LoudnessTile         = 8192
+)
+
+// LoudnessCoefficients: the K-weighting at rate (gdg_loudness_coefficients): shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2.  Host arithmetic.
+func LoudnessCoefficients(rate uint32) ([]float64, error) {
+	out := (*[1 << 28]C.double)(C.calloc(10, 8))
+	if out == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(out))
+	if rc := C.gdg_loudness_coefficients(C.uint32_t(rate), &out[0]); rc != 0 {
+		return nil, fmt.Errorf("gdg: gdg_loudness_coefficients: %d (rate: a multiple of 10 from 8000 on)", int(rc))
+	}
+	c := make([]float64, 10)
+	for i := range c {
+		c[i] = float64(out[i])
+	}
+	return c, nil
+}
+
+// LoudnessHops: the hops of rate/10 samples that complete in the job's samples [first, first+count) (gdg_loudness_hops); 0 for a rate without hops.
+func LoudnessHops(rate uint32, first int, count int) int {
+	return int(C.gdg_loudness_hops(C.uint32_t(rate), C.size_t(first), C.size_t(count)))
+}
+
+// LoudnessRows: rows[r] holds the samples [first, first+len) of a stream at rate (gdg_loudness_rows); result[r][h] is the sum of squares of
+// the K-weighted samples of the h-th hop that completes in them.  state nil starts a stream (first must be 0); a continuing call passes
+// the nRows*LoudnessStateDoubles float64 the call before returned and begins at a multiple of LoudnessTile.  Returns the records and the state.
+func (this *Context) LoudnessRows(rows [][]float64, rate uint32, first int, state []float64) ([][]float64, []float64, error) {
+	n := len(rows)
+	if n == 0 {
+		return nil, nil, fmt.Errorf("gdg: LoudnessRows needs at least one row")
+	}
+	count := len(rows[0])
+	if state != nil && len(state) != n*LoudnessStateDoubles {
+		return nil, nil, fmt.Errorf("gdg: state has %d float64, %d rows keep %d", len(state), n, n*LoudnessStateDoubles)
+	}
+	hops := LoudnessHops(rate, first, count)
+	x := C.malloc(C.size_t(n*count*8 + 8))
+	if x == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(x)
+	for i, r := range rows {
+		if len(r) != count {
+			return nil, nil, fmt.Errorf("gdg: row %d has %d samples, row 0 has %d", i, len(r), count)
+		}
+		copy((*[1 << 37]float64)(x)[i*count:(i+1)*count:(i+1)*count], r)
+	}
+	st := C.calloc(C.size_t(2*n*LoudnessStateDoubles), 8)
+	if st == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(st)
+	stOut := unsafe.Pointer(uintptr(st) + uintptr(n*LoudnessStateDoubles*8))
+	var stIn unsafe.Pointer
+	if state != nil {
+		copy((*[1 << 30]float64)(st)[:n*LoudnessStateDoubles:n*LoudnessStateDoubles], state)
+		stIn = st
+	}
+	rec := C.calloc(C.size_t(n*hops+1), 8)
+	if rec == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	if e := this.err(C.gdg_loudness_rows(this.ctx, (*C.double)(x), C.size_t(count), C.int(n), C.size_t(first), C.size_t(count), C.uint32_t(rate), (*C.double)(stIn),
+		(*C.double)(stOut), (*C.double)(rec), C.size_t(hops))); e != nil {
+		return nil, nil, e
+	}
+	out := make([][]float64, n)
+	for r := range out {
+		out[r] = make([]float64, hops)
+		copy(out[r], (*[1 << 30]float64)(rec)[r*hops:(r+1)*hops:(r+1)*hops])
+	}
+	next := make([]float64, n*LoudnessStateDoubles)
+	copy(next, (*[1 << 30]float64)(stOut)[:n*LoudnessStateDoubles:n*LoudnessStateDoubles])
+	return out, next, nil
+}
+
+// LoudnessRowsDevice: the same on device memory, enqueued on the context's stream (gdg_loudness_rows_device): row r at dRows + r*rowStride
+// float64, its records at dRecords + r*recordsStride; dStateIn nil starts a stream, dStateOut may be nil or dStateIn.
+func (this *Context) LoudnessRowsDevice(dRows unsafe.Pointer, rowStride int, nRows int, first int, count int, rate uint32, dStateIn unsafe.Pointer, dStateOut unsafe.Pointer,
+	dRecords unsafe.Pointer, recordsStride int) error {
+	return this.err(C.gdg_loudness_rows_device(this.ctx, (*C.double)(dRows), C.size_t(rowStride), C.int(nRows), C.size_t(first), C.size_t(count), C.uint32_t(rate),
+		(*C.double)(dStateIn), (*C.double)(dStateOut), (*C.double)(dRecords), C.size_t(recordsStride)))
+}
+
+// BatchLoudnessEnable: from the next batch call on, BatchRun and BatchStreamStep keep the hop records of every encoded port, taken from the
+// session-rate rows in front of delivery, trim and blend gain (gdg_batch_loudness_enable); off by default.  Configuration: a checkpoint does
+// not carry it, an error while a streamed job is open; the checkpoint, shard and master-finish calls refuse while it is on.
+func (this *Context) BatchLoudnessEnable(enable bool) error {
+	v := C.int(0)
+	if enable {
+		v = 1
+	}
+	return this.err(C.gdg_batch_loudness_enable(this.ctx, v))
+}
+
+// BatchLoudness: the hop records of the last completed batch call or slice, result[port][hop] (gdg_batch_loudness).  An error when the
+// call ran without them.
+func (this *Context) BatchLoudness() ([][]float64, error) {
+	var ports C.int
+	var hops C.size_t
+	if e := this.err(C.gdg_batch_loudness(this.ctx, nil, 0, &ports, &hops)); e != nil {
+		return nil, e
+	}
+	out := make([][]float64, int(ports))
+	n := int(ports) * int(hops)
+	if n == 0 {
+		for r := range out {
+			out[r] = make([]float64, 0)
+		}
+		return out, nil
+	}
+	rec := C.calloc(C.size_t(n), 8)
+	if rec == nil {
+		return nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(rec)
+	if e := this.err(C.gdg_batch_loudness(this.ctx, (*C.double)(rec), C.size_t(n), &ports, &hops)); e != nil {
+		return nil, e
+	}
+	per := int(hops)
+	for r := range out {
+		out[r] = make([]float64, per)
+		copy(out[r], (*[1 << 30]float64)(rec)[r*per:(r+1)*per:(r+1)*per])
+	}
+	return out, nil
+}
+
+// loudnessRecords: records[port][hop] as one C array; the caller frees it
+func loudnessRecords(records [][]float64) (unsafe.Pointer, int, int, error) {
+	ports := len(records)
+	if ports == 0 {
+		return nil, 0, 0, fmt.Errorf("gdg: no port")
+	}
+	hops := len(records[0])
+	rec := C.calloc(C.size_t(ports*hops+1), 8)
+	if rec == nil {
+		return nil, 0, 0, fmt.Errorf("gdg: out of memory")
+	}
+	for r, row := range records {
+		if len(row) != hops {
+			C.free(rec)
+			return nil, 0, 0, fmt.Errorf("gdg: port %d has %d hops, port 0 has %d", r, len(row), hops)
+		}
+		copy((*[1 << 30]float64)(rec)[r*hops:(r+1)*hops:(r+1)*hops], row)
+	}
+	return rec, ports, hops, nil
+}
+
+// LoudnessFromHops: the programme made of the listed ports of records[port][hop] with BS.1770's channel weights (nil: every one 1.0)
+// (gdg_loudness_from_hops): integrated, largest momentary and largest short-term loudness in LUFS; -Inf where no block passes the absolute
+// gate.  Host arithmetic: no context and no device.
+func LoudnessFromHops(records [][]float64, rate uint32, port []int, weight []float64) (float64, float64, float64, error) {
+	if len(port) == 0 || (weight != nil && len(weight) != len(port)) {
+		return 0, 0, 0, fmt.Errorf("gdg: LoudnessFromHops needs at least one port, and one weight per port or none")
+	}
+	rec, ports, hops, e := loudnessRecords(records)
+	if e != nil {
+		return 0, 0, 0, e
+	}
+	defer C.free(rec)
+	pp := (*[1 << 28]C.int)(C.calloc(C.size_t(len(port)), 4))
+	if pp == nil {
+		return 0, 0, 0, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(pp))
+	for i, v := range port {
+		pp[i] = C.int(v)
+	}
+	wp := (*[1 << 28]C.double)(C.calloc(C.size_t(len(port)), 8))
+	if wp == nil {
+		return 0, 0, 0, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(wp))
+	for i := range port {
+		wp[i] = 1.0
+		if weight != nil {
+			wp[i] = C.double(weight[i])
+		}
+	}
+	var integrated, momentary, shortTerm C.double
+	if rc := C.gdg_loudness_from_hops((*C.double)(rec), C.int(ports), C.size_t(hops), C.uint32_t(rate), &pp[0], &wp[0], C.int(len(port)), &integrated, &momentary,
+		&shortTerm); rc != 0 {
+		return 0, 0, 0, fmt.Errorf("gdg: gdg_loudness_from_hops: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	return float64(integrated), float64(momentary), float64(shortTerm), nil
+}
+
+// TrimFromLoudness: one gain per port toward targetLufs from records[port][hop] (gdg_trim_from_loudness); with truePeak[port][block] (nil:
+// no cap) a gain that would carry the port's largest true peak over ceilingDbtp is capped, and capped[port] says so.  Host arithmetic.
+func TrimFromLoudness(records [][]float64, rate uint32, targetLufs float64, ceilingDbtp float64, truePeak [][]BlockTruePeak) ([]float64, []bool, error) {
+	rec, ports, hops, e := loudnessRecords(records)
+	if e != nil {
+		return nil, nil, e
+	}
+	defer C.free(rec)
+	blocks := 0
+	var tp *C.gdg_block_true_peak
+	if truePeak != nil {
+		if len(truePeak) != ports {
+			return nil, nil, fmt.Errorf("gdg: %d ports of true-peak records for %d ports of hop records", len(truePeak), ports)
+		}
+		blocks = len(truePeak[0])
+		arr := (*[1 << 25]C.gdg_block_true_peak)(C.calloc(C.size_t(ports*blocks+1), 16))
+		if arr == nil {
+			return nil, nil, fmt.Errorf("gdg: out of memory")
+		}
+		defer C.free(unsafe.Pointer(arr))
+		for r, row := range truePeak {
+			if len(row) != blocks {
+				return nil, nil, fmt.Errorf("gdg: port %d has %d true-peak records, port 0 has %d", r, len(row), blocks)
+			}
+			for b, v := range row {
+				arr[r*blocks+b].true_peak = C.double(v.TruePeak)
+			}
+		}
+		tp = &arr[0]
+	}
+	out := (*[1 << 28]C.double)(C.calloc(C.size_t(ports), 8))
+	if out == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(out))
+	cp := (*[1 << 28]C.int)(C.calloc(C.size_t(ports), 4))
+	if cp == nil {
+		return nil, nil, fmt.Errorf("gdg: out of memory")
+	}
+	defer C.free(unsafe.Pointer(cp))
+	if rc := C.gdg_trim_from_loudness((*C.double)(rec), C.int(ports), C.size_t(hops), C.uint32_t(rate), C.double(targetLufs), C.double(ceilingDbtp), tp, C.size_t(blocks),
+		&out[0], &cp[0]); rc != 0 {
+		return nil, nil, fmt.Errorf("gdg: gdg_trim_from_loudness: %d (%s)", int(rc), C.GoString(C.gdg_last_error(nil)))
+	}
+	gain, capped := make([]float64, ports), make([]bool, ports)
+	for i := range gain {
+		gain[i] = float64(out[i])
+		capped[i] = cp[i] != 0
+	}
+	return gain, capped, nil
+}

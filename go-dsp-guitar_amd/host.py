@@ -5,6 +5,7 @@ A Go `error` comes back as a Python exception (HostError) carrying the reference
 """
 import collections
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -24,6 +25,7 @@ def build():
 
 
 _lib = None
+ATTENUATION_HALF_DECIBEL = 0.9440608762859234      # what the delivery factor's decimator multiplies by (csrc/deliver.h, GDG_DELIVER_ATTENUATION)
 
 # The nine kinds of records a batch call keeps, in the order the batch calls fetch them.  attr: the Engine attribute that holds the last
 # call's; getter: the gdgh_ function; dtype: the name of a package constant, or "float64"; counts: what the getter reports behind (records,
@@ -83,6 +85,8 @@ def lib():
             "gdgh_engine_set_batch_transfers": (cs, [vp, i32, vp, vp, i32]),
             "gdgh_engine_batch_transfers": (i32, [vp]),
             "gdgh_engine_set_batch_delivered": (cs, [vp, i32]),
+            "gdgh_engine_set_batch_loudness": (cs, [vp, i32]),
+            "gdgh_engine_last_batch_loudness": (cs, [vp, vp, C.c_size_t, C.POINTER(i32), C.POINTER(C.c_size_t)]),
             "gdgh_engine_set_batch_blends_delayed": (cs, [vp, i32, vp, vp, vp, vp, vp]),
             "gdgh_engine_set_batch_blends_filtered": (cs, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
             "gdgh_engine_batch_stream_sharded_checkpoint": (cs, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
@@ -167,6 +171,9 @@ class Engine:
         self.last_tapfit = None          # the tap-fit records of the last batch call made with tapfits=: [blocks, D] float64
         self.last_delivered = None       # the records of the delivered rows of the last batch call made with delivered=True: [N + 3 + B, blocks] records
         self.normalize_delivered = None  # ... and those of render_normalized(measure="delivered")'s measuring pass
+        self.last_loudness = None        # the loudness records of the last batch call made with loudness=True: [N + 3 + B, hops] float64 hop sums
+        self.normalize_loudness = None   # ... those of render_normalized(measure="loudness")'s measuring pass,
+        self.normalize_capped = None     # ... and which of its ports' gains the true-peak ceiling capped
         self.last_align = None           # the alignment records of the last batch call made with align=(ref, max_lag): [N + 3, blocks] records
 
     def shards(self):
@@ -406,6 +413,21 @@ class Engine:
         target = np.array([int(t) for _, t in pairs] + [0], dtype=np.int32)
         _err(lib().gdgh_engine_set_batch_transfers(self._h, len(pairs), port.ctypes.data, target.ctypes.data, group))
         return int(lib().gdgh_engine_batch_transfers(self._h))
+
+    def _set_loudness(self, loudness):
+        """Engine::SetBatchLoudness, from the `loudness` argument of the batch calls: keep the hop records of the K-weighted session-rate rows.
+        Returns whether they are on.  Refused on an engine of more than one shard."""
+        self.last_loudness = None
+        _err(lib().gdgh_engine_set_batch_loudness(self._h, int(bool(loudness))))
+        return bool(loudness)
+
+    def _fetch_loudness(self):
+        """Engine::LastBatchLoudness: the [ports, hops] hop sums of the last batch call or slice"""
+        ports, hops = C.c_int(0), C.c_size_t(0)
+        _err(lib().gdgh_engine_last_batch_loudness(self._h, None, 0, C.byref(ports), C.byref(hops)))
+        out = np.zeros((ports.value, hops.value), dtype=np.float64)
+        _err(lib().gdgh_engine_last_batch_loudness(self._h, out.ctypes.data if out.size else None, out.size, C.byref(ports), C.byref(hops)))
+        return out
 
     def _set_delivered(self, delivered):
         """Engine::SetBatchDelivered, from the `delivered` argument of the batch calls: keep the records of the rows the encoders read (the
@@ -660,7 +682,8 @@ class Engine:
         outs = self.batch_run(inputs, target_rate, out_format, window=window, blends=lined, **rest)
         return outs, delays, signs, fractions
 
-    def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, measure="render", **kw):
+    def render_normalized(self, target_dbtp, max_gain_db, inputs, target_rate, out_format, window=16, sample_rate=None, measure="render", target_lufs=-23.0,
+                          ceiling_dbtp=None, **kw):
         """Two passes over one job: every output file is written with the gain that brings its true peak to target_dbtp (dBTP), capped at
         max_gain_db.  save_state; pass 1 renders with the true-peak records (and the report) on and every output skipped; the planner
         (trim_from_true_peak) turns the records into gains; load_state; pass 2 renders with the trim.  Returns (outs, gains): the N + 3
@@ -672,20 +695,33 @@ class Engine:
         true peak can differ from the render's (the anti-aliasing filter rings), so leave the headroom the target is meant to leave.
         measure="delivered" (one-shard engines): pass 1 runs with the delivery in force and the records of the delivered rows on; the
         planner (trim_from_delivered) takes their true peak -- that of the rows the files are encoded from, seamless across blocks -- and
-        the records stay in normalize_delivered: a file normalised to -1 dBTP then measures -1 dBTP."""
-        if measure not in ("render", "delivered"):
-            raise ValueError("measure: 'render' or 'delivered'")
+        the records stay in normalize_delivered: a file normalised to -1 dBTP then measures -1 dBTP.
+        measure="loudness" (one-shard engines): pass 1 runs with the loudness records (include/gdg.h, LOUDNESS) on; the planner
+        (trim_from_loudness) brings every port's own integrated loudness to target_lufs and caps a gain that would carry the port's true peak
+        over ceiling_dbtp (None: target_dbtp); max_gain_db caps it as well.  The records stay in normalize_loudness, and normalize_capped says
+        which ports the ceiling capped.  The records are of the session-rate render: with a delivery factor in force the file is quieter by the
+        decimator's attenuation (ATTENUATION_HALF_DECIBEL, once whatever the factor), so the plan adds that constant back."""
+        if measure not in ("render", "delivered", "loudness"):
+            raise ValueError("measure: 'render', 'delivered' or 'loudness'")
         import __graft_entry__ as entry
         pkg = entry.load_package()
         rate = target_rate if sample_rate is None else sample_rate
         _err(lib().gdgh_engine_sync_chains(self._h, rate))     # an engine that has not processed yet: the state to save exists from here on
         blob = self.save_state()
         self.batch_run(inputs, target_rate, out_format, window=window, report=True, true_peak=True, skip_outputs=True, delivered=measure == "delivered",
-                       **{k: v for k, v in kw.items() if k not in ("report", "true_peak", "trim", "blend_gain", "delivered")})
+                       loudness=measure == "loudness", **{k: v for k, v in kw.items() if k not in ("report", "true_peak", "trim", "blend_gain", "delivered", "loudness")})
         self.normalize_true_peak, self.normalize_report = self.last_true_peak, self.last_report
         if measure == "delivered":
             self.normalize_delivered = self.last_delivered
             gains = pkg.trim_from_delivered(self.normalize_delivered, 10.0 ** (target_dbtp / 20.0), 10.0 ** (max_gain_db / 20.0))
+        elif measure == "loudness":
+            self.normalize_loudness = self.last_loudness
+            deliver = kw.get("deliver")
+            factor = deliver[0] if isinstance(deliver, (tuple, list)) else (deliver or 1)
+            back = -20.0 * math.log10(ATTENUATION_HALF_DECIBEL) if int(factor) > 1 else 0.0      # what the factor's decimator takes from the file
+            gains, self.normalize_capped = pkg.trim_from_loudness(self.normalize_loudness, target_rate, target_lufs + back,
+                                                                  target_dbtp if ceiling_dbtp is None else ceiling_dbtp, self.normalize_true_peak)
+            gains = np.minimum(gains, 10.0 ** (max_gain_db / 20.0))
         else:
             gains = pkg.trim_from_true_peak(self.normalize_true_peak, 10.0 ** (target_dbtp / 20.0), 10.0 ** (max_gain_db / 20.0))
         self.load_state(blob, rate)
@@ -695,7 +731,7 @@ class Engine:
         return outs, gains
 
     def batch_run(self, inputs, target_rate, out_format, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,
-                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None, delivered=False):
+                  report=False, dither=None, spectrum=None, align=None, true_peak=False, trim=None, skip_outputs=False, blends=None, blend_gain=None, fits=None, gram=None, tapfits=None, transfers=None, deliver=None, delivered=False, loudness=False):
         """Engine::BatchRun: controller.processFiles' data path over all shards; returns the N + 3 output data sections.  report: keep the
         render report of the run in last_report ([N + 3, blocks], gdg_batch_run's port order whatever the shard count).  spectrum: band
         edges in Hz -- keep the band spectrum of the run in last_spectrum ([N + 3, blocks, bands], the same order).  align: (ref, max_lag) --
@@ -715,9 +751,12 @@ class Engine:
         record stays that of the session-rate render, so a delivered file's true peak can differ from last_true_peak: the anti-aliasing
         filter removes what lies above the new Nyquist frequency, and it rings.  delivered: keep the records of the rows the encoders read
         -- behind the delivery, in front of the trim and blend gains -- in last_delivered ([N + 3 + B, blocks], BLOCK_DELIVERED_DTYPE; one-shard
-        engines only): their true_peak is the delivered file's, seamless across blocks."""
+        engines only): their true_peak is the delivered file's, seamless across blocks.  loudness: keep the loudness records -- per port and
+        100 ms hop the sum of squares of the K-weighted session-rate samples -- in last_loudness ([N + 3 + B, hops] float64; one-shard engines
+        only); loudness_from_hops and trim_from_loudness of the package read them."""
         import __graft_entry__ as entry
         pkg = entry.load_package()
+        loud = self._set_loudness(loudness)
         R, nb, kinds = self._settings(report=report, dither=dither, spectrum=spectrum, align=align, true_peak=true_peak, trim=trim, blends=blends, blend_gain=blend_gain,
                                       fits=fits, gram=gram, tapfits=tapfits, transfers=transfers, deliver=deliver, delivered=delivered)
         n = len(inputs)
@@ -736,6 +775,8 @@ class Engine:
         assert samples.value == length
         for kind in kinds:
             setattr(self, RECORD_KINDS[kind].attr, self._fetch(kind))
+        if loud:
+            self.last_loudness = self._fetch_loudness()
         return outs
 
     def batch_stream(self, inputs, target_rate, out_format, blocks_per_slice, window=16, metronome_to_master=False, run_meters=False, tuner_enqueue=False,

@@ -1169,6 +1169,31 @@ Error Engine::SetBatchDelivered(bool on) {
     return "";
 }
 
+/* Engine::SetBatchLoudness: the switch of the loudness records; an engine of more shards refuses it, as the library's shard calls would */
+Error Engine::SetBatchLoudness(bool on) {
+    if (on && shards() > 1)
+        return format("SetBatchLoudness: the engine has %d shards: the records are taken from the rows of one device's window, and the library's shard and master-finish "
+                      "calls refuse them (gdg_batch_loudness_enable); it needs an engine of one shard", shards());
+    loudness_ = on;
+    return "";
+}
+
+/* ... and its records: not one of the nine kinds -- they stay on the device until they are asked for, so the context of the one shard is asked */
+Error Engine::LastBatchLoudness(std::vector<double> &records, int *ports, size_t *hops) const {
+    records.clear();
+    if (shards() != 1) return "LastBatchLoudness: the loudness records need an engine of one shard (SetBatchLoudness)";
+    std::lock_guard<std::mutex> lk(shards_[0]->mu);
+    gdg_ctx *ctx = shards_[0]->ctx;
+    int p = 0;
+    size_t h = 0;
+    if (!ctx || gdg_batch_loudness(ctx, nullptr, 0, &p, &h) != GDG_OK) return ctx ? Error(gdg_last_error(ctx)) : Error("LastBatchLoudness: no context yet");
+    records.assign((size_t)p * h, 0.0);
+    if (!records.empty() && gdg_batch_loudness(ctx, records.data(), records.size(), &p, &h) != GDG_OK) return Error(gdg_last_error(ctx));
+    if (ports) *ports = p;
+    if (hops) *hops = h;
+    return "";
+}
+
 /* ---- the records of the last batch call, nine kinds through one table (batch_records.h): the typed faces of records::last ---- */
 Error Engine::LastBatchReport(std::vector<gdg_block_stats> &records, int *ports, size_t *blocks) const { return records::lastAs(records::REPORT, stores_[records::REPORT], records, ports, blocks); }
 Error Engine::LastBatchSpectrum(std::vector<double> &bands, int *ports, size_t *blocks, int *nBands) const { return records::lastAs(records::SPECTRUM, stores_[records::SPECTRUM], bands, ports, blocks, nBands); }
@@ -1223,6 +1248,7 @@ int Engine::applySettings(int shard, gdg_ctx *ctx, int window) {
     if (rc == GDG_OK) rc = applyTapFits(ctx);
     if (rc == GDG_OK) rc = applyTransfers(ctx);
     if (rc == GDG_OK) rc = gdg_batch_out_records_enable(ctx, delivered_);
+    if (rc == GDG_OK) rc = gdg_batch_loudness_enable(ctx, loudness_);
     return rc;
 }
 
@@ -2094,6 +2120,26 @@ const char *gdgh_engine_set_batch_delivered(void *e, int on) {
 const char *gdgh_engine_last_batch_delivered(void *e, gdg_block_delivered *records, size_t capacity, int *ports, size_t *blocks) {
     if (!e) return ret(Error("no engine"));
     return ret(records::copyOut(records::DELIVERED, ((Engine *)e)->batchRecords(records::DELIVERED), records, capacity, ports, blocks));
+}
+const char *gdgh_engine_set_batch_loudness(void *e, int on) {
+    if (!e) return ret(Error("no engine"));
+    return ret(((Engine *)e)->SetBatchLoudness(on != 0));
+}
+/* records == NULL: the counts alone */
+const char *gdgh_engine_last_batch_loudness(void *e, double *records, size_t capacity, int *ports, size_t *hops) {
+    if (!e) return ret(Error("no engine"));
+    std::vector<double> got;
+    int p = 0;
+    size_t h = 0;
+    Error err = ((Engine *)e)->LastBatchLoudness(got, &p, &h);
+    if (!err.empty()) return ret(err);
+    if (ports) *ports = p;
+    if (hops) *hops = h;
+    if (records) {
+        if (capacity < got.size()) return ret(Error("LastBatchLoudness: too little room for the records"));
+        if (!got.empty()) memcpy(records, got.data(), got.size() * sizeof(double));
+    }
+    return ret(Error(""));
 }
 const char *gdgh_engine_last_batch_transfer(void *e, double *records, size_t capacity, size_t *blocks, size_t *doubles_per_block) {
     return ret(records::copyOut(records::TRANSFER, ((Engine *)e)->batchRecords(records::TRANSFER), records, capacity, nullptr, blocks, doubles_per_block));

@@ -352,6 +352,14 @@ public:
     Error SetBatchDelivered(bool on);
     bool BatchDelivered() const { return delivered_; }
     Error LastBatchDelivered(std::vector<gdg_block_delivered> &records, int *ports, size_t *blocks) const;
+    /* No reference counterpart.  The loudness records (include/gdg.h, LOUDNESS; gdg_batch_loudness_enable): from the next job on BatchRun and
+     * the plain streamed job keep, per port and 100 ms hop, the sum of squares of the K-weighted samples of the session-rate rows -- in front of
+     * delivery, trim and blend gain.  A small path of its own beside the nine kinds of batch_records.h: the records stay on the device and
+     * LastBatchLoudness asks the context for those of its last call or slice, [N + 3 + blends][hops].  One-shard engines only: the library's
+     * shard and master-finish calls refuse the switch, so an engine of more shards refuses it here.  The checkpoint calls refuse while it is on. */
+    Error SetBatchLoudness(bool on);
+    bool BatchLoudness() const { return loudness_; }
+    Error LastBatchLoudness(std::vector<double> &records, int *ports, size_t *hops) const;
     /* No reference counterpart.  The state every channel of the engine carries from one call to the next (include/gdg.h, gdg_state_*) as
      * ONE blob: a small engine header, then one gdg_state blob per global channel -- so that an engine with another shard count (another
      * routing of the channels to contexts) can load it.  LoadState first brings the device side of every chain up to date at `sampleRate`
@@ -427,7 +435,8 @@ private:
     bool delivered_ = false;                               /* SetBatchDelivered; never on on an engine of several shards */
     int applyTransfers(gdg_ctx *ctx);                      /* onto a context (more shards: none is in force): a gdg_* status */
     int applyTapFits(gdg_ctx *ctx);                        /* onto a context (more shards: none are in force): a gdg_* status */
-    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivered_ || delivery_ > 1 || deliveryUp_ != 1 || deliveryDown_ != 1; }      /* BatchRun is the library's plain one-call run */
+    bool loudness_ = false;                                /* SetBatchLoudness; never on on an engine of several shards */
+    bool plainRun() const { return BatchBlends() > 0 || BatchFits() > 0 || BatchGramPorts() > 0 || BatchTapFits() > 0 || BatchTransfers() > 0 || delivered_ || loudness_ || delivery_ > 1 || deliveryUp_ != 1 || deliveryDown_ != 1; }      /* BatchRun is the library's plain one-call run */
     int applyBlends(gdg_ctx *ctx);                         /* onto the one context of a one-shard engine (more shards: none are in force): a gdg_* status */
     /* every setting in force onto a context, in the order the library's checks need: the window, the four port kinds, sources, dither,
      * trim, delivery and blends (applyPortSettings: all that a resumed job is set up with), then the five list kinds.  shard < 0: the plain

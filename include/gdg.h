@@ -1743,6 +1743,96 @@ int gdg_block_out_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_str
 int gdg_batch_out_records_enable(gdg_ctx *ctx, int enable);
 int gdg_batch_out_records(gdg_ctx *ctx, gdg_block_delivered *records, size_t capacity, int *ports, size_t *blocks);
 int gdg_trim_from_out_records(const gdg_block_delivered *records, int ports, size_t blocks, double target, double max_gain, double *gain);
+/*
+ * LOUDNESS: K-weighted loudness after ITU-R BS.1770.  Rigs with equal peaks differ by many dB in loudness; "bring these renders to -18 LUFS"
+ * needs a record of its own.  BS.1770 gates 400 ms blocks on a 100 ms hop, and a hop -- H = rate / 10 samples: 19200, 9600, 4800, 4410 -- neither
+ * divides the 8192-sample block nor is divided by it: the records are kept per HOP, not per block, on a path of their own beside the block
+ * records.  A rate that is not a multiple of 10, or below 8000, is refused.
+ * K-WEIGHTING: two biquads in series at the session rate fs in float64, their coefficients made on the host at every rate by the same
+ * formulas.  With K = tan(pi f0 / fs) and a0 = 1 + K/Q + K^2:
+ *   shelf      f0 = 1681.974450955533  Q = 0.7071752369554196  G = 3.999843853973347 dB:  Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *              b0 = (Vh + Vb K/Q + K^2) / a0   b1 = 2 (K^2 - Vh) / a0   b2 = (Vh - Vb K/Q + K^2) / a0   a1 = 2 (K^2 - 1) / a0   a2 = (1 - K/Q + K^2) / a0
+ *   high-pass  f0 = 38.13547087602444  Q = 0.5003270373238773:  b = (1, -2, 1), a1 and a2 as above from this stage's f0 and Q
+ * gdg_loudness_coefficients(rate, out) hands out shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2; at 48000 they are the table printed in BS.1770
+ * to 3e-11.
+ * RECURRENCE, per sample x (non-finite: 0) from the states s0 = s1 = q0 = q1 = 0 in front of the job, every product, sum and difference an
+ * IEEE-754 double operation rounded on its own:
+ *   y1 = b0 x + s0        s0 = ((b1 x) - (a1 y1)) + s1        s1 = (b2 x) - (a2 y1)                       the shelf, transposed direct form II
+ *   y  = y1 + q0          q0 = q0 + (q1 - (beta y))           q1 = q1 - (alpha y)                          the high-pass
+ * with alpha = 4 K^2 / a0 (= 1 + a1 + a2) and beta = (2 K/Q + 4 K^2) / a0 (= 2 + a1) of the high-pass: the same transfer function as
+ * b = (1, -2, 1) over (1, a1, a2), in the states q0 = t0 and q1 = t0 + t1 of its transposed direct form II.  The poles lie within 0.3 % of z = 1,
+ * where the direct form loses five digits to the roundings of a1 and a2; this one does not.
+ * HOP RECORD: for port p and hop h one double, the sum of y[n]^2 over h H <= n < (h + 1) H, n counted from the job's start.  A hop that the job's
+ * end cuts is never emitted.  gdg_loudness_hops(rate, first, count) = floor((first + count) / H) - floor(first / H) is the number of hops that
+ * complete in the samples [first, first + count): slices and stand-alone calls size their buffers with it, as they do with
+ * gdg_batch_out_samples.  A silent port gives exactly +0.0.
+ * ORDER: the filter is recursive, so the order of evaluation is part of the definition.  Every 8192-sample block counted from the job's start
+ * is a tile of 256 chunks of 32 samples.  Chunk t run from zero states (chunk 0: from the tile's incoming states) ends in the states f_t; then
+ * v_t = f_t and, for k = 0 .. 7 in turn, v_t = (P_k v_(t - 2^k)) + v_t for every t >= 2^k at once, P_k = A^(32 * 2^k) in float64 by repeated
+ * squaring of A, the 4 x 4 map of the states at x = 0 (row i of P_k v: ((m0 v0 + m1 v1) + m2 v2) + m3 v3).  Chunk t is then run again from
+ * v_(t - 1), which gives y; v_255 goes into the next tile.  The squares are summed sequentially in cells of 64 samples counted from the hop's
+ * start (the last cell of a hop of 4410 has 58), the cells sequentially in ascending order.  So a hop's 64 bits are a function of the job's
+ * samples and the rate alone: not of the window, of how a streamed job is sliced, or of whether outputs are written.  Against the recurrence run
+ * sequentially in 80-bit arithmetic a hop differs by less than 1e-9 of its value (DESIGN.md 4.12l has the measured figures).
+ * STATE per port, GDG_LOUDNESS_STATE_DOUBLES = 7: s0, s1, q0, q1, the open cell's sum, the open hop's sum, the position (samples seen, exact).
+ * Known answers (BS.1770, EBU Tech 3341; their tolerance is 0.1 LU): a full-scale 997 Hz sine on one channel reads -3.01 LUFS at 44100, 48000
+ * and 192000; a 1 kHz sine at -23 dBFS on left and right reads -23.0 LUFS; -36 dBFS for 10 s, -23 dBFS for 60 s, -36 dBFS for 10 s reads
+ * -23.0 LUFS; silence reads -inf.
+ *   gdg_loudness_rows(ctx, rows, row_stride, n_rows, first, count, rate, state_in, state_out, records, capacity)      host buffers, blocking
+ *   gdg_loudness_rows_device(ctx, d_rows, row_stride, n_rows, first, count, rate, d_state_in, d_state_out, d_records, records_stride)
+ *                                                      enqueued on gdg_ctx_stream.  Row r at rows + r * row_stride holds the job's samples
+ *                                                      [first, first + count); its gdg_loudness_hops(rate, first, count) records go to
+ *                                                      records + r * capacity (records_stride), and nothing else is written; less room is
+ *                                                      refused.  state_in == NULL starts a stream, and then `first` must be 0; a continuing
+ *                                                      call passes the [n_rows][7] doubles the call before wrote to state_out and begins at a
+ *                                                      multiple of 8192 samples -- any other `first` is refused, and so (host form) is a state
+ *                                                      whose position is not `first`.  state_out may be NULL, and may be state_in
+ *   gdg_batch_loudness_enable(ctx, enable)             from the next batch call on, gdg_batch_run and gdg_batch_stream_step keep the hop records
+ *                                                      of every encoded port -- chain outputs, master left and right, metronome, blends --
+ *                                                      taken from the float64 rows at the session rate, where the block statistics take theirs:
+ *                                                      in front of delivery, trim and blend gain.  The kernel also runs in a call that passes
+ *                                                      no output buffers.  State and records stay in device buffers of their own: zeroed by a
+ *                                                      job's first slice, kept from step to step and slice to slice, freed when the switch goes
+ *                                                      off, when stat_batch_device_kib is that of a context that never heard of it.  Off (the
+ *                                                      default): no launch, buffer or byte differs.  GDG_ERR_INVALID while a streamed job is
+ *                                                      open.  Configuration: part of no blob
+ *   gdg_batch_loudness(ctx, records, capacity, &ports, &hops)
+ *                                                      the records of the LAST COMPLETED batch call or slice, [ports][hops] row-major, hops =
+ *                                                      gdg_loudness_hops(rate, slice's first sample, its samples); downloaded by this call.
+ *                                                      records == NULL: the counts only.  GDG_ERR_INVALID when capacity < ports * hops or there
+ *                                                      are none
+ *   gdg_loudness_from_hops(records, n_ports, n_hops, rate, port, weight, n, &integrated, &momentary_max, &short_term_max)
+ *                                                      pure float64 on the host, no context: the programme is the n listed ports with BS.1770's
+ *                                                      channel weights (weight == NULL: every one 1.0).  POWER over a hop is the weighted sum of
+ *                                                      the ports' hop sums / H.  A 400 ms block is four consecutive hops, block j = hops j ..
+ *                                                      j + 3, its power their mean.  integrated = -0.691 + 10 log10(mean of the blocks above
+ *                                                      -70 LUFS and above -10 LU relative to the mean of those); momentary_max the largest
+ *                                                      block, short_term_max the largest mean of 30 consecutive hops, each as LUFS.  With no
+ *                                                      block above the absolute gate: -inf, and success.  Any of the three may be NULL
+ *   gdg_trim_from_loudness(records, n_ports, n_hops, rate, target_lufs, ceiling_dbtp, true_peak, blocks, gain, capped)
+ *                                                      one gain per port, 10^((target_lufs - L) / 20) with L the port's own integrated loudness
+ *                                                      at weight 1; 1.0 for a port that has none.  With true_peak ([n_ports][blocks], NULL: no
+ *                                                      cap) a gain that would carry the port's largest true peak over 10^(ceiling_dbtp / 20) is
+ *                                                      capped by gdg_trim_from_true_peak's rule -- min(ceiling / peak, gain) -- and capped[p]
+ *                                                      (may be NULL) is 1 for such a port, 0 otherwise
+ * GDG_ERR_UNSUPPORTED while the switch is on, gdg_last_error naming gdg_batch_loudness_enable: the checkpoint and resume calls (the state is not
+ * in the version-1 container), the shard calls, gdg_batch_finish_master and gdg_batch_finish_master_slice.  With a delivery factor in force the
+ * file is quieter than the render's record by the decimator's attenuation; a record at the delivered rate is out of scope.
+ */
+#define GDG_LOUDNESS_STATE_DOUBLES 7
+#define GDG_LOUDNESS_TILE 8192
+int gdg_loudness_coefficients(uint32_t rate, double *out);
+size_t gdg_loudness_hops(uint32_t rate, size_t first, size_t count);
+int gdg_loudness_rows(gdg_ctx *ctx, const double *rows, size_t row_stride, int n_rows, size_t first, size_t count, uint32_t rate, const double *state_in, double *state_out,
+                      double *records, size_t capacity);
+int gdg_loudness_rows_device(gdg_ctx *ctx, const double *d_rows, size_t row_stride, int n_rows, size_t first, size_t count, uint32_t rate, const double *d_state_in,
+                             double *d_state_out, double *d_records, size_t records_stride);
+int gdg_batch_loudness_enable(gdg_ctx *ctx, int enable);
+int gdg_batch_loudness(gdg_ctx *ctx, double *records, size_t capacity, int *ports, size_t *hops);
+int gdg_loudness_from_hops(const double *records, int n_ports, size_t n_hops, uint32_t rate, const int *port, const double *weight, int n, double *integrated,
+                           double *momentary_max, double *short_term_max);
+int gdg_trim_from_loudness(const double *records, int n_ports, size_t n_hops, uint32_t rate, double target_lufs, double ceiling_dbtp, const gdg_block_true_peak *true_peak,
+                           size_t blocks, double *gain, int *capped);
 
 #ifdef __cplusplus
 
